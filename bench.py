@@ -9,13 +9,20 @@ A step = one pass of the whole hot path over one batch: voxelise -> forward -> t
 already resident in HBM when the timed region starts.  N>1: one process per GPU, each rank owns its own batch
 (independent scans, no data-path collective) => weak scaling.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 --mode graph (default): the step is captured once into a hipGraph per in-flight slot (reserved plan: the level sizes
 stay on the device) and every timed step is ONE hipGraphLaunch; --mode eager: ~150 launches + one size query per step.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel + a per-layer table,
-every layer against its binding roof) and `cpu_baseline` (the CPU oracle on a bounded sample, rank 0 at N=1 only).
+A plain run sets up, warms up (W eager steps, then the capture of every in-flight slot), times exactly K steps in one
+region and prints ONE JSON line on rank 0 with the headline figure (`value` scans/s, `ms_per_step`).
+--dump-outputs DIR: after the timed steps, what the last timed step returned (global descriptors, keypoints, local
+descriptors, selected rows, counts) is written as DIR/<name>.npy; the inputs and weights are seeded, so two builds run
+with the same arguments can be compared output for output.
+--full adds the side measurements to the line: `latency` (one batch in flight), `roofline` (dominant kernel + a per-layer
+table, every layer against its binding roof, from profiled eager passes of their own), `cpu_baseline` (the CPU oracle on
+a bounded sample, rank 0 at N=1 only), `extra` (the other BASELINE configs, each a run of its own) and, unless --repeats
+is given, reports the median of 5 timed regions of K steps each.
 """
 from __future__ import annotations
 
@@ -87,7 +94,7 @@ def parse():
     p.add_argument("--cpu-scans", type=int, default=6, help="scans timed on the numpy oracle (fallback only)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work given to the C/OpenMP oracle baseline")
     p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--layer-table", type=str, default="", help="also write the per-layer table (json) here")
+    p.add_argument("--layer-table", type=str, default="", help="--full: also write the per-layer table (json) here")
     p.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                    help="f32 = BASELINE configs[1] (default, the headline metric); bf16 = configs[2]: feature maps and "
                         "sparse-conv weights bf16 in HBM, fp32 accumulate")
@@ -99,7 +106,8 @@ def parse():
     p.add_argument("--conv-variant", type=int, default=0,
                    help="A/B measurements only: egonn_debug_set_naive_conv code (2 register-ring kernel, 16 LDS-DMA kernel with "
                         "split-phase fetch, 32 LDS-DMA kernel with 3 ring slots; all bitwise identical); 0 = product choice")
-    p.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps; the median one is reported")
+    p.add_argument("--repeats", type=int, default=None,
+                   help="timed regions of --steps steps; the median one is reported (default 1; 5 with --full)")
     p.add_argument("--distinct-batches", type=int, default=4,
                    help="the timed loop rotates over this many distinct resident batches (1 = replay one batch: A/B with round <= 3)")
     p.add_argument("--dry-run", action="store_true",
@@ -107,13 +115,50 @@ def parse():
                         "parsing, process group (gloo), barriers, max-over-ranks timing, the ranks-seen all-reduce, rank 0's JSON "
                         "line — around a stub step; the line is marked dry_run and carries no measurement")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the bounded side measurements of the other BASELINE configs (extra.configs[2], configs[3]_1gpu, db)")
-    return p.parse_args()
+                   help="--full: skip the bounded side measurements of the other BASELINE configs (extra.configs[2], configs[3]_1gpu, db)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure latency, roofline / per-layer table, cpu_baseline and the other BASELINE configs (runs of "
+                        "their own, minutes); a plain run measures only the headline figure")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="write what the last timed step returned as DIR/<name>.npy (float32; integer fields as float64)")
+    args = p.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.layer_table and not args.full:
+        p.error("--layer-table is a --full measurement")
+    return args
 
 
-def make_scans(rank: int, batch: int, n_points: int):
+def lidar_scans(seeds, n_points: int):
+    """lidar_scan(seed) for every seed, on a small thread pool (the ray casting is numpy that releases the GIL): the same
+    arrays as a serial loop, in a fraction of its time (~0.6 s per 50k-pt scan serially)."""
+    from concurrent.futures import ThreadPoolExecutor
     from egonn_amd.synth import lidar_scan
-    return [lidar_scan(1000 * rank + i, n_points=n_points) for i in range(batch)]
+    seeds = list(seeds)
+    workers = max(1, min(16, len(os.sched_getaffinity(0)), len(seeds)))
+    with ThreadPoolExecutor(workers) as pool:
+        return list(pool.map(lambda s: lidar_scan(s, n_points=n_points), seeds))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, d):
+    """The arrays a caller of the timed path receives from its last step -> d/<name>.npy.  Integer fields are stored as
+    float64 (exact).  Every array is indexed by scan first; above DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of
+    scans is kept from every array."""
+    arrs = {}
+    for k in ("global", "keypoints", "descriptors", "rows", "count"):
+        a = out[k].detach().cpu().numpy()
+        arrs[k] = a.astype(np.float64 if a.dtype.kind in "iu" else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        n_scans = arrs["global"].shape[0]
+        keep = np.sort(np.random.default_rng(0).choice(n_scans, max(1, n_scans * DUMP_LIMIT_BYTES // total), replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def layer_rows(recs, dtype):
@@ -203,129 +248,13 @@ def dry_run(args):
         dist.destroy_process_group()
 
 
-def main():
-    args = parse()
-    if args.dry_run:
-        return dry_run(args)
-    world, rank, local_rank, distributed, dist = dist_setup(args)
-
-    import __graft_entry__ as entry
-    if rank == 0:
-        entry.build()
-    if distributed:
-        dist.barrier()
-    from egonn_amd import ModelParams, model_factory, DescriptorExtractor
-    from egonn_amd.synth import seeded_state_dict
-
-    dev = torch.device("cuda", torch.cuda.current_device())
-    mp = ModelParams(model="egonn", coordinates="cartesian", quantization_step=args.voxel)
-    model = model_factory(mp)
-    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
-    sd = seeded_state_dict(1, shapes)                      # random-init weights (no pretrained weights exist)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    model = model.to(dev).eval()
-    model.coord_bits = 12                                  # +-204.8 m at 0.1 m voxels: fewer radix passes
-    model.precision = "bf16" if args.dtype == "bf16" else "fp32"
-    ex = DescriptorExtractor(model, n_k=128)
-
-    # NB distinct batches resident in HBM: the timed loop rotates over them (a stream never re-reads the same 9.6 MB)
-    NB = max(1, args.distinct_batches)
-    batches = []
-    for b in range(NB):
-        from egonn_amd.synth import lidar_scan
-        sc = [lidar_scan(1000 * rank + 100 * b + i, n_points=args.points) for i in range(args.batch)]
-        off_b = [0]
-        for s in sc:
-            off_b.append(off_b[-1] + len(s))
-        batches.append((torch.from_numpy(np.concatenate(sc, axis=0)).to(dev).contiguous(), off_b))
-    points, offsets = batches[0]
-    scans = [points[offsets[i]:offsets[i + 1]].cpu().numpy() for i in range(args.batch)]     # (cpu_baseline sample)
-    S = max(1, args.streams)
-    ctx = model.context()
-
-    def eager_step():
-        return ex.extract_packed(points, offsets)
-
-    # ---------------- warm-up (eager, one batch in flight); the last step times every tagged launch: per-layer table
-    # (exclusive durations) and the dominant kernel = the sparse-conv instantiation with the largest total time
-    for _ in range(max(args.warmup, 1)):
-        eager_step()
-    torch.cuda.synchronize()
-    # exact dispatch timing: the sparse-conv launchers attach the layer's HIP events to the kernel dispatch itself (begin of the
-    # kernel .. end of the kernel, of the reducer for an offset-split pair) — the duration rocprofv3 --kernel-trace reports for
-    # the same dispatch; the other tagged layers (conv0) are bracketed by event records on the stream
-    ctx.profile_enable(2, "/")
-    ctx.profile_fetch()
-    for _ in range(5):
-        eager_step()
-    layers = layer_rows(ctx.profile_fetch(), args.dtype)
-    ctx.profile_enable(0)
-    per_kernel = {}
-    for r in layers:
-        if r["layer"].startswith("sconv"):
-            per_kernel[r["layer"].split("/")[0]] = per_kernel.get(r["layer"].split("/")[0], 0.0) + r["us"]
-    dominant = max(per_kernel, key=per_kernel.get)
-    n_levels = [ctx.level_count(l) for l in range(8)]
-
-    # ---------------- host cost of one eager batch (enqueue only) vs its GPU time, one batch in flight
-    torch.cuda.synchronize()
-    h0 = time.perf_counter()
-    eager_step()
-    h1 = time.perf_counter()
-    torch.cuda.synchronize()
-    h2 = time.perf_counter()
-    host = {"eager_enqueue_ms": round((h1 - h0) * 1e3, 3), "eager_latency_ms": round((h2 - h0) * 1e3, 3)}
-
-    # ---------------- the timed step
-    graphs = []
-    if args.mode == "graph":
-        # capacities from OTHER scans than the timed ones (a deployment calibrates once, then streams unseen batches)
-        cal = make_scans(rank + 7919, args.batch, args.points)
-        cal_off = [0]
-        for sc in cal:
-            cal_off.append(cal_off[-1] + len(sc))
-        cal_pts = torch.from_numpy(np.concatenate(cal, axis=0)).to(dev).contiguous()
-        caps = ex.calibrate(cal_pts, cal_off, margin=1.25)
-        del cal_pts
-        for i in range(S):
-            gx = ex.graph(args.batch, points.shape[0], caps, slot=100 + i, stream=_masked_stream(dev, i, S, args.cu_partition))
-            if args.conv_variant:
-                gx.ctx.set_naive_conv(args.conv_variant)
-            gx.run(points, offsets)                        # eager once + capture + first replay
-            gx.status()
-            graphs.append(gx)
-        torch.cuda.synchronize()
-        g0 = time.perf_counter()
-        graphs[0].replay()
-        g1 = time.perf_counter()
-        graphs[0].stream.synchronize()
-        g2 = time.perf_counter()
-        host.update({"graph_launch_ms": round((g1 - g0) * 1e3, 3), "graph_latency_ms": round((g2 - g0) * 1e3, 3)})
-
-        def run_steps(k):                                  # every step loads its batch (9.6 MB device copy + the scan
-            for i in range(k):                             # offsets) into the graph's input buffers, then ONE graph launch;
-                graphs[i % S].run(*batches[(i // S + i) % NB])   # the batches rotate over NB distinct ones
-    else:
-        ctx.profile_enable(2, dominant + "/")              # HIP events attached to the dominant kernel's dispatches
-
-        def run_steps(k):
-            for _ in ex.extract_stream((batches[i % NB] for i in range(k)), n_streams=S):
-                pass
-        run_steps(2 * S)                                   # every in-flight slot grows its arenas before timing
-    torch.cuda.synchronize()
-    for c in ([g.ctx for g in graphs] or [ctx]):
-        c.profile_fetch()
-
-    elapsed_all = timed_regions(run_steps, args.steps, args.repeats, dist if distributed else None, dev, torch.cuda.synchronize)
-    elapsed = float(np.median(elapsed_all))
-
+def roofline_pass(args, ctx, eager_step, layers, dominant, S, rank, n_levels):
+    """--full: the roofline of the dominant kernel and the per-layer table (exclusive eager passes of their own)."""
     # ---------------- roofline of the dominant kernel: launches of the timed region(s)
     # graph mode: event records cannot be read back from inside a captured graph, so the dominant kernel is timed by an
     # exclusive eager pass right after the timed regions (HIP events attached to its dispatches, one batch in flight) —
     # the figure rocprofv3 --kernel-trace reports for it; eager mode: the events of the timed regions' own dispatches.
     if args.mode == "graph":
-        for g in graphs:
-            g.status()
         recs = []
     else:
         recs, timing = ctx.profile_fetch(), "HIP events attached to every dispatch of the dominant kernel in the timed regions"
@@ -431,14 +360,150 @@ def main():
     if args.layer_table and rank == 0:
         with open(args.layer_table, "w") as f:
             json.dump({"levels": n_levels, "batch": args.batch, "dtype": args.dtype, "rows": roofline["layers"]}, f, indent=1)
+    return roofline
+
+
+def main():
+    args = parse()
+    if args.dry_run:
+        return dry_run(args)
+    world, rank, local_rank, distributed, dist = dist_setup(args)
+
+    import __graft_entry__ as entry
+    if rank == 0:
+        entry.build()
+    if distributed:
+        dist.barrier()
+    from egonn_amd import ModelParams, model_factory, DescriptorExtractor
+    from egonn_amd.synth import seeded_state_dict
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    mp = ModelParams(model="egonn", coordinates="cartesian", quantization_step=args.voxel)
+    model = model_factory(mp)
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    sd = seeded_state_dict(1, shapes)                      # random-init weights (no pretrained weights exist)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    model = model.to(dev).eval()
+    model.coord_bits = 12                                  # +-204.8 m at 0.1 m voxels: fewer radix passes
+    model.precision = "bf16" if args.dtype == "bf16" else "fp32"
+    ex = DescriptorExtractor(model, n_k=128)
+
+    # NB distinct batches resident in HBM: the timed loop rotates over them (a stream never re-reads the same 9.6 MB)
+    NB = max(1, args.distinct_batches)
+    # every scan of the run (the NB timed batches, then graph mode's calibration batch) generated at once
+    seeds = [1000 * rank + 100 * b + i for b in range(NB) for i in range(args.batch)]
+    if args.mode == "graph":
+        seeds += [1000 * (rank + 7919) + i for i in range(args.batch)]
+    all_scans = lidar_scans(seeds, args.points)
+    batches = []
+    for b in range(NB):
+        sc = all_scans[b * args.batch:(b + 1) * args.batch]
+        off_b = [0]
+        for s in sc:
+            off_b.append(off_b[-1] + len(s))
+        batches.append((torch.from_numpy(np.concatenate(sc, axis=0)).to(dev).contiguous(), off_b))
+    points, offsets = batches[0]
+    S = max(1, args.streams)
+    ctx = model.context()
+
+    def eager_step():
+        return ex.extract_packed(points, offsets)
+
+    # ---------------- warm-up (eager, one batch in flight)
+    for _ in range(max(args.warmup, 1)):
+        eager_step()
+    torch.cuda.synchronize()
+    host, layers, dominant = {}, None, None
+    if args.full:
+        # one more pass times every tagged launch: per-layer table (exclusive durations) and the dominant kernel = the
+        # sparse-conv instantiation with the largest total time.
+        # exact dispatch timing: the sparse-conv launchers attach the layer's HIP events to the kernel dispatch itself (begin of the
+        # kernel .. end of the kernel, of the reducer for an offset-split pair) — the duration rocprofv3 --kernel-trace reports for
+        # the same dispatch; the other tagged layers (conv0) are bracketed by event records on the stream
+        ctx.profile_enable(2, "/")
+        ctx.profile_fetch()
+        for _ in range(5):
+            eager_step()
+        layers = layer_rows(ctx.profile_fetch(), args.dtype)
+        ctx.profile_enable(0)
+        per_kernel = {}
+        for r in layers:
+            if r["layer"].startswith("sconv"):
+                per_kernel[r["layer"].split("/")[0]] = per_kernel.get(r["layer"].split("/")[0], 0.0) + r["us"]
+        dominant = max(per_kernel, key=per_kernel.get)
+    n_levels = [ctx.level_count(l) for l in range(8)]
+
+    if args.full:
+        # ---------------- host cost of one eager batch (enqueue only) vs its GPU time, one batch in flight
+        torch.cuda.synchronize()
+        h0 = time.perf_counter()
+        eager_step()
+        h1 = time.perf_counter()
+        torch.cuda.synchronize()
+        h2 = time.perf_counter()
+        host = {"eager_enqueue_ms": round((h1 - h0) * 1e3, 3), "eager_latency_ms": round((h2 - h0) * 1e3, 3)}
+
+    # ---------------- the timed step
+    graphs = []
+    last = {}                                              # eager mode: the result of the latest step
+    if args.mode == "graph":
+        # capacities from OTHER scans than the timed ones (a deployment calibrates once, then streams unseen batches)
+        cal = all_scans[NB * args.batch:]
+        cal_off = [0]
+        for sc in cal:
+            cal_off.append(cal_off[-1] + len(sc))
+        cal_pts = torch.from_numpy(np.concatenate(cal, axis=0)).to(dev).contiguous()
+        caps = ex.calibrate(cal_pts, cal_off, margin=1.25)
+        del cal_pts
+        for i in range(S):
+            gx = ex.graph(args.batch, points.shape[0], caps, slot=100 + i, stream=_masked_stream(dev, i, S, args.cu_partition))
+            if args.conv_variant:
+                gx.ctx.set_naive_conv(args.conv_variant)
+            gx.run(points, offsets)                        # eager once + capture + first replay
+            gx.status()
+            graphs.append(gx)
+        torch.cuda.synchronize()
+        if args.full:
+            g0 = time.perf_counter()
+            graphs[0].replay()
+            g1 = time.perf_counter()
+            graphs[0].stream.synchronize()
+            g2 = time.perf_counter()
+            host.update({"graph_launch_ms": round((g1 - g0) * 1e3, 3), "graph_latency_ms": round((g2 - g0) * 1e3, 3)})
+
+        def run_steps(k):                                  # every step loads its batch (9.6 MB device copy + the scan
+            for i in range(k):                             # offsets) into the graph's input buffers, then ONE graph launch;
+                graphs[i % S].run(*batches[(i // S + i) % NB])   # the batches rotate over NB distinct ones
+    else:
+        if args.full:
+            ctx.profile_enable(2, dominant + "/")          # HIP events attached to the dominant kernel's dispatches
+
+        def run_steps(k):
+            for out in ex.extract_stream((batches[i % NB] for i in range(k)), n_streams=S):
+                last["out"] = out
+        run_steps(2 * S)                                   # every in-flight slot grows its arenas before timing
+    torch.cuda.synchronize()
+    if args.full:
+        for c in ([g.ctx for g in graphs] or [ctx]):
+            c.profile_fetch()
+
+    elapsed_all = timed_regions(run_steps, args.steps, args.repeats, dist if distributed else None, dev, torch.cuda.synchronize)
+    elapsed = float(np.median(elapsed_all))
+    if args.mode == "graph":
+        for g in graphs:
+            g.status()
+    if args.dump_outputs and rank == 0:                    # the last timed step ran on graph (steps - 1) % S
+        dump_outputs(graphs[(args.steps - 1) % S].out if args.mode == "graph" else last["out"], args.dump_outputs)
+
+    roofline = roofline_pass(args, ctx, eager_step, layers, dominant, S, rank, n_levels) if args.full else None
 
     # ---------------- CPU baseline: the oracle ("port") on a bounded sample of the same workload
     # oracle/egonn_cpu.c = C/OpenMP restatement of the reference path (one scan per forward, like the reference's
     # evaluator), built with -march=native on this box and run on all host cores; whole passes over the benchmark's
     # scans until >= --cpu-seconds of CPU work.  (numpy oracle as the fallback if gcc is unavailable.)
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cscans = scans[:16]
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cscans = all_scans[:min(args.batch, 16)]                         # scans of the first timed batch
         try:
             from oracle import egonn_cpu
             co = egonn_cpu.CpuOracle(sd, args.voxel, native=True)
@@ -470,7 +535,7 @@ def main():
 
     # ---------------- bounded side measurements of the other BASELINE configs (same process tree, after the headline)
     extra = None
-    if rank == 0 and world == 1 and not args.no_extras and args.dtype == "f32" and args.batch == 16:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.dtype == "f32" and args.batch == 16:
         import subprocess
         del graphs
         torch.cuda.synchronize()
@@ -485,7 +550,7 @@ def main():
             except Exception as e:                          # pragma: no cover
                 return {"error": str(e)[:300]}
         extra["configs[2]"] = side([os.path.join(REPO, "bench.py"), "--dtype", "bf16", "--batch", "64", "--steps", "30", "--warmup", "3",
-                                    "--repeats", "3", "--no-cpu-baseline", "--no-extras"],
+                                    "--repeats", "3", "--full", "--no-cpu-baseline", "--no-extras"],
                                    lambda d: {"value": d["value"], "unit": "scans/s", "ms_per_step": d["ms_per_step"], "batch": 64, "dtype": "bf16",
                                               "roofline": {k: d["roofline"][k] for k in ("kernel", "bound", "frac", "avg_launch_us")},
                                               "note": "bf16 maps, batch 64, on-device quantisation, hipGraph-captured step, 4 batches in flight"})
@@ -537,12 +602,11 @@ def main():
             "repeats": {"timed_regions": len(elapsed_all), "reported": "median",
                         "scans_per_s": [round(total_scans / e, 1) for e in elapsed_all],
                         "min": round(total_scans / max(elapsed_all), 1), "max": round(total_scans / min(elapsed_all), 1)},
-            "latency": dict(host, note="one batch in flight: host time to enqueue a batch / time until its results are ready"),
-            "roofline": roofline,
-            "cpu_baseline": cpu_baseline,
             "rccl_ranks_seen": rccl_ranks_seen,
-            "extra": extra,
         }
+        if args.full:
+            line.update({"latency": dict(host, note="one batch in flight: host time to enqueue a batch / time until its results are ready"),
+                         "roofline": roofline, "cpu_baseline": cpu_baseline, "extra": extra})
         print(json.dumps(line), flush=True)
     if distributed:
         dist.destroy_process_group()

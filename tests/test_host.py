@@ -137,3 +137,35 @@ def test_status_codes_map_to_exception_types(built):
     assert e.value.code == 3 and not isinstance(e.value, _lib.CapacityError)
     header = open(os.path.join(REPO, "include", "egonn_hip.h")).read()
     assert "EGONN_STATUS_CAPACITY = 5" in header and "EGONN_STATUS_RANGE = 3" in header
+
+
+def test_bench_dump_outputs_float_and_bounded(tmp_path):
+    """bench.py --dump-outputs: every field the timed path returns becomes DIR/<name>.npy, float32 or (integer fields,
+    exact) float64; above the size limit every array keeps the same seeded sample of scans.  Run in a child process:
+    importing bench.py sets the runtime's queue count for the process."""
+    import subprocess
+    import sys
+    code = """
+import sys, numpy as np, torch
+import bench
+g = torch.Generator().manual_seed(0)
+out = {"global": torch.randn((16, 256), generator=g), "keypoints": torch.randn((16, 128, 3), generator=g),
+       "descriptors": torch.randn((16, 128, 128), generator=g), "rows": torch.arange(16 * 128, dtype=torch.int32).view(16, 128),
+       "count": torch.full((16,), 128, dtype=torch.int32)}
+bench.dump_outputs(out, sys.argv[1])
+bench.DUMP_LIMIT_BYTES = 300_000
+bench.dump_outputs(out, sys.argv[2])
+"""
+    full, small = tmp_path / "full", tmp_path / "small"
+    r = subprocess.run([sys.executable, "-c", code, str(full), str(small)], capture_output=True, text=True, timeout=120, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-800:]
+    names = ["count", "descriptors", "global", "keypoints", "rows"]
+    assert sorted(p.stem for p in full.iterdir()) == names == sorted(p.stem for p in small.iterdir())
+    a = {n: np.load(full / (n + ".npy")) for n in names}
+    assert a["rows"].dtype == a["count"].dtype == np.float64 and a["global"].dtype == a["descriptors"].dtype == np.float32
+    assert a["descriptors"].shape == (16, 128, 128) and np.array_equal(a["rows"].ravel(), np.arange(16 * 128))
+    b = {n: np.load(small / (n + ".npy")) for n in names}
+    assert sum(v.nbytes for v in b.values()) <= 300_000 and 0 < len(b["global"]) < 16
+    keep = (b["rows"][:, 0] // 128).astype(int)                  # row r of scan s holds s * 128 + r: the sampled scans
+    for n in names:
+        assert np.array_equal(b[n], a[n][keep]), n

@@ -2,7 +2,7 @@
 # (measurement of round 3, profiles/r03j_small_levels.txt; the switches it sets exist only with tools/exp/r03j_small_map_experiments.patch applied)
 # per-layer times (bench.py --layer-table, exclusive eager pass) of levels 4-7 under the small-map switches
 cd /root/repo
-run() { echo "== $1"; env $2 timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 100 --repeats 3 --layer-table /tmp/lt.json 2>/dev/null | python -c "
+run() { echo "== $1"; env $2 timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 100 --repeats 3 --layer-table /tmp/lt.json 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('scans/s', d['value'], 'graph_latency_ms', d['latency'].get('graph_latency_ms'))
 t=json.load(open('/tmp/lt.json'))

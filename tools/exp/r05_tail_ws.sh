@@ -3,7 +3,7 @@
 cd /root/repo
 echo "== correctness (stand-alone, vs the plain kernel): AB=3000"
 EGONN_SPLIT_MAX_LEVEL=4 F32ONLY=1 AB=0,3000 ONLY=10,11,12,13,14,15 timeout 300 python tools/bench_sconv.py 2>&1 | grep "^kind" | awk '{print $1,$2,$3,$4,$5,$6,$7,$8,$9,$17,$18,$19,$20}'
-run() { echo "== $1"; env $2 timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 100 --repeats 3 --layer-table /tmp/lt.json 2>/dev/null | python -c "
+run() { echo "== $1"; env $2 timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 100 --repeats 3 --layer-table /tmp/lt.json 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('scans/s', d['value'], 'graph_latency_ms', d['latency'].get('graph_latency_ms'))
 t=json.load(open('/tmp/lt.json'))

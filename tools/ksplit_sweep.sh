@@ -3,7 +3,7 @@
 #   tools/ksplit_sweep.sh "ENV..." "ENV..."      each argument = one environment (space separated VAR=val), "" = defaults
 # prints scans/s [repeats], one-batch graph latency, the aggregate conv roofline and the conv layers of levels >= 3
 for v in "$@"; do
-env $v python bench.py --no-extras --no-cpu-baseline --repeats 3 --steps 60 2>/dev/null | python -c "
+env $v python bench.py --full --no-extras --no-cpu-baseline --repeats 3 --steps 60 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('[$v]', d['value'], d['repeats']['scans_per_s'], 'lat', d['latency'].get('graph_latency_ms'), 'agg', d['roofline']['aggregate']['frac'], d['roofline']['aggregate']['serial_us_per_step'])
 rows=[r for r in d['roofline']['layers'] if r['layer'].startswith('sconv')]

@@ -7,7 +7,7 @@ TAG=${1:-ks}; shift
 REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 STEPS=20
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o kt -- python $REPO/bench.py --mode eager --streams 1 --steps $STEPS --warmup 3 --repeats 1 --no-cpu-baseline "$@" > $OUT/${TAG}_kt.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o kt -- python $REPO/bench.py --full --mode eager --streams 1 --steps $STEPS --warmup 3 --repeats 1 --no-cpu-baseline "$@" > $OUT/${TAG}_kt.log 2>&1
 cd $REPO
 # bench.py runs warmup (3) + 5 profiled + 1 + 2 + STEPS timed + 5 exclusive eager steps = 36 steps
 python tools/rocpd_summary.py $(find $OUT/${TAG}_kt -name '*.db' | head -1) $OUT/${TAG}_kernel_stats.csv $((STEPS + 16)) > /dev/null

@@ -5,7 +5,7 @@ set -u
 TAG=${1:-ko}; shift
 REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 cd /tmp
-env "$@" timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o kt -- python $REPO/bench.py --steps 40 --warmup 3 --repeats 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_kt.log 2>&1
+env "$@" timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o kt -- python $REPO/bench.py --full --steps 40 --warmup 3 --repeats 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_kt.log 2>&1
 cd $REPO
 python tools/rocpd_summary.py $(find $OUT/${TAG}_kt -name '*.db' | head -1) $OUT/${TAG}_kernel_stats.csv > /dev/null
 rm -rf $OUT/${TAG}_kt
