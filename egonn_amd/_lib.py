@@ -139,8 +139,9 @@ class CapacityError(EgonnError):
 
 
 class Fp16RangeError(EgonnError):
-    """status 6: an fp32 sparse convolution on the fp16-split pipe met a non-finite accumulator (activation beyond +-65504 or
-    non-finite input): the batch's outputs are invalid; Context.set_exact_fp32(True) and run it again"""
+    """status 6: a kernel on the fp16-split pipe (fp32 sparse convolution or local heads) met an operand fp16 cannot hold
+    (|x| >= 65520) or a non-finite input: the batch's outputs are invalid; Context.set_exact_fp32(True) and run it again
+    (on the same plan: every forward clears this flag)"""
 
 
 def check(rc: int):
@@ -351,7 +352,7 @@ class Context:
 
     def set_operand_autoscale(self, on: bool):
         """fp16-split convolutions scale their input by a power of two per launch (max |in| -> [2^13, 2^14)): small operands
-        (input gradients) keep their low parts.  Eager plans only."""
+        (input gradients) keep their low parts.  Eager plans only: on a reserved context it raises (code 4)."""
         check(self.lib.egonn_ctx_set_operand_autoscale(self.h, int(bool(on))))
 
     def set_ksplit(self, map_class: int, level: int, kparts: int = -1, kw: int = -1, col_parts: int = -1):

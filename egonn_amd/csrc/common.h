@@ -223,8 +223,11 @@ struct Ctx {
   Plan plan;
   int32_t* host_counts = nullptr;    // pinned staging for the size query
   int32_t* dev_counts = nullptr;
-  int32_t* dev_flags = nullptr;      // bit 0 = out-of-range coordinate seen, bit 1 = batch larger than the reserved capacities,
-                                     // bit 3 = fp16 range guard of the split convolutions (sconv_split.hip)
+  int32_t* dev_flags = nullptr;      // bit 0 = out-of-range coordinate seen, bit 1 = batch larger than the reserved capacities
+                                     // (the plan's bits: cleared by the plan builders only)
+  int32_t* dev_fp16_flag = nullptr;  // bit 3 = fp16 range guard of the split kernels (sconv_split.hip, the tail split of sconv.hip,
+                                     // the local heads): its own word, cleared by the plan builders and at the start of every
+                                     // egonn_forward; egonn_plan_status reports the OR of both words
   bool reserved = false;             // egonn_ctx_reserve: fixed capacities, plans neither allocate nor synchronise
   int64_t reserve_points = 0;
   int reserve_batch = 0;

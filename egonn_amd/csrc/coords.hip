@@ -141,13 +141,17 @@ __global__ void points_to_keys_kernel(const float* __restrict__ pts, int64_t n_c
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   // riders (graph nodes saved): the plan's own copy of the scan offsets, and the zeroing of the sort's per-scan histograms —
   // both are read by LATER launches only
-  if (off_copy && i <= B) off_copy[i] = scan_off[i];
-  for (int64_t w = i; w < zero_words; w += (int64_t)gridDim.x * blockDim.x) zero_ptr[w] = 0;
+  // (grid-strided: the grid is sized by n_cap, which may hold fewer than B + 1 threads — 600 scans in 200 rows)
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (off_copy)
+    for (int64_t b = i; b <= B; b += stride) off_copy[b] = scan_off[b];
+  for (int64_t w = i; w < zero_words; w += stride) zero_ptr[w] = 0;
   const int64_t nn = scan_off[B];
   if (i == 0 && nn > n_cap) atomicOr(flags, 2);         // more points than the plan was reserved for
   // the segmented sort moves only rows inside [off[b], off[b+1]): offsets that do not start at 0 or that decrease would leave
   // rows unsorted (stale buffer contents) -> reported as a range error (egonn_voxelize raises, egonn_plan_status for reserved plans)
-  if (i <= B && ((i == 0 && scan_off[0] != 0) || (i > 0 && scan_off[i] < scan_off[i - 1]))) atomicOr(flags, 1);
+  for (int64_t b = i; b <= B; b += stride)
+    if ((b == 0 && scan_off[0] != 0) || (b > 0 && scan_off[b] < scan_off[b - 1])) atomicOr(flags, 1);
   if (i >= (nn < n_cap ? nn : n_cap)) return;
   // sample index = last b with scan_off[b] <= i
   int lo = 0, hi = B;   // invariant: scan_off[lo] <= i < scan_off[hi]
@@ -761,11 +765,11 @@ int plan_sync(Ctx* ctx, hipStream_t stream) {
   EGONN_REQUIRE(P.valid, EGONN_ERR_STATE, "no coordinate plan");
   if (P.exact) return EGONN_OK;
   const int B = P.batch, cb = P.coord_bits;
-  HIP_CHECK(hipMemcpyAsync(ctx->host_counts, ctx->dev_counts, sizeof(int32_t) * 17, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(ctx->host_counts, ctx->dev_counts, sizeof(int32_t) * 18, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipMemcpyAsync(ctx->host_counts + 32, P.lv[0].boff, sizeof(int32_t) * EGONN_NUM_LEVELS * (B + 1),
                            hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream));
-  const int32_t flags = ctx->host_counts[16];
+  const int32_t flags = ctx->host_counts[16] | ctx->host_counts[17];     // the plan's bits | the fp16 range flag
   if (flags & 1) {
     P.valid = false;
     set_error("coordinate outside the +-2^%d voxel range of coord_bits=%d (or non-finite point / batch index out of range)",
@@ -795,8 +799,8 @@ int plan_sync(Ctx* ctx, hipStream_t stream) {
   P.n_input = ctx->host_counts[NL + 1];
   P.exact = true;
   if (flags & 8) {             // (the plan itself is fine: the sizes above are valid; the feature maps of the forward are not)
-    set_error("an fp32 sparse convolution on the fp16-split matrix pipe met a non-finite accumulator: an activation beyond +-65504 "
-              "(the range of the fp16 operand parts) or a non-finite input; the outputs of this batch are invalid — "
+    set_error("a kernel on the fp16-split matrix pipe (fp32 sparse convolution or local heads) met an operand outside the fp16 "
+              "range (|x| >= 65520, which fp16 rounds to Inf) or a non-finite input; the outputs of this batch are invalid — "
               "egonn_ctx_set_exact_fp32(ctx, 1) selects the exact fp32 kernels");
     return EGONN_ERR_FP16_RANGE;
   }
@@ -1118,7 +1122,7 @@ int plan_from_points(Ctx* ctx, const float* points, const int64_t* scan_offsets,
   }
   // (device offsets: the key kernel copies them into the plan's array itself)
   ctx->plan.scan_off = doff;
-  HIP_CHECK(hipMemsetAsync(ctx->dev_flags, 0, sizeof(int32_t), stream));
+  HIP_CHECK(hipMemsetAsync(ctx->dev_flags, 0, 2 * sizeof(int32_t), stream));     // the plan's flags + the fp16 range flag
   QuantParams qp{mode, step[0], mode ? step[1] : step[0], mode ? step[2] : step[0]};
   const int idx_bits = plan_packed_idx_bits(ctx->coord_bits, n);
   int32_t *tilehist = nullptr, *scanhist = nullptr;
@@ -1148,7 +1152,7 @@ int plan_from_coords(Ctx* ctx, const int32_t* coords, int64_t n, int B, hipStrea
   uint32_t* v1 = A.alloc<uint32_t>(n);
   EGONN_REQUIRE(k0 && k1 && v0 && v1, EGONN_ERR_STATE, "plan arena too small");
   ctx->plan.scan_off = nullptr;
-  HIP_CHECK(hipMemsetAsync(ctx->dev_flags, 0, sizeof(int32_t), stream));
+  HIP_CHECK(hipMemsetAsync(ctx->dev_flags, 0, 2 * sizeof(int32_t), stream));     // the plan's flags + the fp16 range flag
   hipLaunchKernelGGL(coords_to_keys_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, coords, n,
                      ctx->coord_bits, B, k0, v0, ctx->dev_flags);
   return build_plan_from_sorted_input(ctx, k0, v0, k1, v1, n, nullptr, nullptr, B, false, stream);
@@ -1157,6 +1161,8 @@ int plan_from_coords(Ctx* ctx, const int32_t* coords, int64_t n, int B, hipStrea
 // Fixes the sizes of everything a plan allocates, so that later plans neither allocate nor synchronise (capturable).
 int plan_reserve(Ctx* ctx, int64_t max_points, int B, const int64_t* level_caps) {
   EGONN_REQUIRE(max_points >= 1 && B >= 1 && B <= EGONN_MAX_BATCH, EGONN_ERR_INVALID, "reserve: bad sizes");
+  EGONN_REQUIRE(!ctx->operand_autoscale, EGONN_ERR_STATE,
+                "reserve: operand autoscale is on — it reads the map's row count on the host (eager plans only)");
   ctx->plan.valid = false;
   for (int l = 0; l < NL; ++l) {
     int64_t c = max_points;

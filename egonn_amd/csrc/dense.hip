@@ -1105,8 +1105,10 @@ __global__ __launch_bounds__(LH_WAVES * 64) void local_heads_kernel(const LocalH
 // order of the register chain, one power-of-two scale per matrix; activations split in registers; three products on
 // v_mfma_f32_16x16x32_f16, small terms first): 138 MFMAs of 16 cycles.  The lateral 1x1 convolution in front stays on the exact
 // pipe in the accumulation order of the dense kernel (the fused / unfused switch stays bitwise).  Deviation of the outputs from
-// the exact kernel: < 3e-6 of the largest value per output (tests/test_gpu_fusions.py); non-finite head outputs raise the range
-// flag of the plan (an input beyond the fp16 range cannot pass silently).  egonn_ctx_set_exact_fp32 selects the kernel above.
+// the exact kernel: < 3e-6 of the largest value per output (tests/test_gpu_fusions.py).  Range guard (the plan's fp16 range flag):
+// the heads' input tile (lateral + transposed convolution, exact fp32) is tested for |x| >= 65520 and non-finite elements before it
+// is split — the first layers' ReLU would otherwise turn the NaN accumulators of such an input into 0 — and the outputs of the
+// second layers for non-finite values (a hidden activation beyond the range).  egonn_ctx_set_exact_fp32 selects the kernel above.
 typedef _Float16 lh_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 lh_f16x2 __attribute__((ext_vector_type(2)));
 typedef float lh_f32x2 __attribute__((ext_vector_type(2)));
@@ -1245,6 +1247,14 @@ __global__ __launch_bounds__(LH_WAVES * 64) void local_heads_split_kernel(const 
       for (int t = 0; t < 4; ++t) x[t] = l[t] + r[t];
     }
     float guard = 0.f;                                       // (v - v) is NaN for a non-finite v: sticky under addition
+    // the heads' input (fp32, or bf16 widened): an element fp16 cannot hold (|x| >= 65520 rounds to Inf; 65504 <= |x| < 65520 to
+    // 65504 with an exact low part) or a non-finite one turns the first layers' accumulators into NaN, which the bias + ReLU
+    // below (fmaxf) would turn into 0 — so the input tile itself is checked, before any of it enters the split
+    bool outside = false;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) outside |= !(fabsf(x[t][r]) < 65520.f);
     // ---- descriptor decoder + L2 normalisation
     {
       f32x4 h[6], o[8];
@@ -1311,7 +1321,7 @@ __global__ __launch_bounds__(LH_WAVES * 64) void local_heads_split_kernel(const 
         p.out_sigma[row] = apply_act(o[0][0] + p.sb1[0], ACT_SOFTPLUS);
       }
     }
-    if (ok && guard != 0.f && q.flags) atomicOr(q.flags, 8);
+    if (ok && (outside || guard != 0.f) && q.flags) atomicOr(q.flags, 8);
   }
 }
 

@@ -127,7 +127,8 @@ API int egonn_ctx_create(egonn_ctx** out, int device, int coord_bits) {
     delete c;
     return EGONN_ERR_HIP;
   }
-  c->dev_flags = c->dev_counts + 16;   // counts[0..11], flags at [16]: fetched by one copy
+  c->dev_flags = c->dev_counts + 16;   // counts[0..11], flags at [16], the fp16 range flag at [17]: fetched by one copy
+  c->dev_fp16_flag = c->dev_counts + 17;
   sconv_ksplit_defaults(&c->ks_rule);
   if (conv0_lut_init(c) != EGONN_OK) {
     egonn_ctx_destroy(c);
@@ -246,6 +247,9 @@ API int egonn_plan_status(egonn_ctx* c, void* stream) {
 // flushes below 2^-25 and carries 2^-25 absolute error below 2^-14.  Eager plans only (the element count comes from the host).
 API int egonn_ctx_set_operand_autoscale(egonn_ctx* c, int on) {
   EGONN_REQUIRE(c && (on == 0 || on == 1), EGONN_ERR_INVALID, "ctx_set_operand_autoscale: bad argument");
+  EGONN_REQUIRE(!on || !c->reserved, EGONN_ERR_STATE,
+                "ctx_set_operand_autoscale: eager plans only — the scale reads the map's row count on the host, which a reserved "
+                "(egonn_ctx_reserve) plan keeps on the device");
   c->operand_autoscale = on;
   return EGONN_OK;
 }
@@ -781,6 +785,9 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
   const bool do_local = !(flags & EGONN_FLAG_DISABLE_LOCAL);
   EGONN_REQUIRE(!do_global || out_global, EGONN_ERR_INVALID, "forward: out_global is null");
   EGONN_REQUIRE(!do_local || (out_desc && out_kp && out_sigma), EGONN_ERR_INVALID, "forward: local outputs are null");
+  // the fp16 range flag covers THIS forward: cleared in stream order (a memset node of a captured graph), so a status read after
+  // it reports this batch and not an earlier forward on the same plan; the plan's coordinate / capacity bits are another word
+  HIP_CHECK(hipMemsetAsync(c->dev_fp16_flag, 0, sizeof(int32_t), st));
 
   // ---- row-group tables of every map the graph uses: one launch per plan
   {
@@ -862,14 +869,14 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
       // 64-channel map they read is never written (bitwise the rows of the dense launch this replaces; bf16 maps are widened on load)
       EGONN_TRY(local_heads_forward(reinterpret_cast<const float*>(x[3]), n3, cnt + 3, hw, P.lv[3].keys, 3, P.coord_bits, quant_mode,
                                     step, (flags & EGONN_FLAG_IGNORE_KP_REGRESSOR) ? 1 : 0, out_desc, out_kp, out_sigma, st,
-                                    m->l1x1[3], reinterpret_cast<const float*>(u3), bf16, lh_pack, c->dev_flags));
+                                    m->l1x1[3], reinterpret_cast<const float*>(u3), bf16, lh_pack, c->dev_fp16_flag));
       return EGONN_OK;
     }
     WALLOC(l3, n3 * LOCAL_CH);
     EGONN_TRY(dense_forward_ex(x[3], bf16, n3, 64, m->l1x1[3], 0, LOCAL_CH, nullptr, nullptr, nullptr, ACT_NONE, u3, bf16, l3, 0, st, cnt + 3));
     EGONN_TRY(local_heads_forward(l3, n3, cnt + 3, hw, P.lv[3].keys, 3, P.coord_bits, quant_mode, step,
                                   (flags & EGONN_FLAG_IGNORE_KP_REGRESSOR) ? 1 : 0, out_desc, out_kp, out_sigma, st, nullptr, nullptr, 0,
-                                  lh_pack, c->dev_flags));
+                                  lh_pack, c->dev_fp16_flag));
     return EGONN_OK;
   };
   static const bool presplit_ok = getenv("EGONN_NO_PRESPLIT") == nullptr;     // measurement switch: conv2 splits in its loop

@@ -1360,7 +1360,7 @@ int sconv_map(Ctx* ctx, int kind, int level, const void* in, const float* W, con
     return sconv_split_forward(reinterpret_cast<const float*>(in), P.cap[lin], rg, rg.cap_groups, Wsp, cin, cout, scale, shift,
                                relu, reinterpret_cast<float*>(out), psum, stream,
                                ctx->conv_variant >= 1000 ? ctx->conv_variant - 1000 : 0, ctx->split_io, ctx->gated_in2, ctx->gated_gate,
-                               P.batch, kparts, ctx->ks_part, ctx->ks_part_floats, col_parts, kw, ctx->dev_flags,
+                               P.batch, kparts, ctx->ks_part, ctx->ks_part_floats, col_parts, kw, ctx->dev_fp16_flag,
                                ctx->operand_autoscale ? reinterpret_cast<uint32_t*>(ctx->dev_counts + 24) : nullptr,
                                ctx->operand_autoscale ? P.lv[lin].n * cin : 0, ctx->conv_residual);
   }
@@ -1377,7 +1377,7 @@ int sconv_map(Ctx* ctx, int kind, int level, const void* in, const float* W, con
       Wsp = scratch;
     }
     return sconv_rg_forward(in, P.cap[lin], rg, rg.cap_groups, Wsp, cin, cout, 0, scale, shift, relu, out, psum, stream, 0, level, 1,
-                            ctx->dev_flags, ctx->conv_residual);
+                            ctx->dev_fp16_flag, ctx->conv_residual);
   }
   if (!Wp) {      // stand-alone operator call: pack into the caller's scratch
     const size_t wn = (size_t)K * cin * cout;

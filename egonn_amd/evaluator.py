@@ -30,19 +30,7 @@ class DescriptorExtractor:
     def compute_embedding(self, pc, model: MinkGL = None):
         model = model or self.model
         pc = pc if isinstance(pc, torch.Tensor) else torch.as_tensor(np.asarray(pc), dtype=torch.float32)
-        out = self.extract([pc], model=model)
-        ctx = model.context()
-        try:                                           # (the host waits for the results below anyway)
-            ctx.plan_status()
-        except _lib.Fp16RangeError:
-            # an activation left the range of the fp16 operand parts (models/minkgl.py:105 is fp32 arithmetic): this scan again on
-            # the exact fp32 kernels
-            ctx.set_exact_fp32(True)
-            try:
-                out = self.extract([pc], model=model)
-                ctx.plan_status()
-            finally:
-                ctx.set_exact_fp32(False)
+        out = self.extract([pc], model=model)          # (checks the range flag and falls back to exact fp32 itself)
         n = int(out['count'][0].item())
         global_embedding = out['global'].cpu().numpy()
         return global_embedding, out['keypoints'][0, :n].cpu(), out['descriptors'][0, :n].cpu()
@@ -69,7 +57,11 @@ class DescriptorExtractor:
     @torch.no_grad()
     def extract(self, scans: Sequence[torch.Tensor], model: MinkGL = None) -> Dict[str, torch.Tensor]:
         """scans: list of (n_i,3) float32 tensors (any device).  Returns device tensors:
-        global (B,256), keypoints (B,n_k,3), descriptors (B,n_k,128), count (B,), rows (B,n_k)."""
+        global (B,256), keypoints (B,n_k,3), descriptors (B,n_k,128), count (B,), rows (B,n_k).
+
+        Never returns the outputs of a batch the fp16 range guard flagged: after the forward it reads the plan's status
+        (one host synchronisation) and, on `Fp16RangeError` (an activation beyond the range of the fp16 operand parts of the
+        split kernels), runs the batch again on the exact fp32 kernels and returns that result.  Other plan errors raise."""
         model = model or self.model
         ctx = model.context()
         dev = ctx.device
@@ -78,12 +70,33 @@ class DescriptorExtractor:
         for p in pts:
             offsets.append(offsets[-1] + p.shape[0])
         allpts = pts[0].contiguous() if len(pts) == 1 else torch.cat(pts, dim=0)
-        return self.extract_packed(allpts, offsets, model)
+        out = self.extract_packed(allpts, offsets, model)
+        try:
+            ctx.plan_status()
+        except _lib.Fp16RangeError:
+            # models/minkgl.py:105 is fp32 arithmetic: the same plan again on the exact fp32 kernels (egonn_forward clears the
+            # range flag, so the status below covers the rerun only)
+            ctx.set_exact_fp32(True)
+            try:
+                y = model._forward_on_plan(ctx, None)
+                d, k, s = model._last_local
+                if self.ignore_keypoint_saliency:
+                    s = torch.rand_like(s)
+                sel_kp, sel_desc, rows, cnt = ctx.select_keypoints(s, k, d, self.n_k)
+                ctx.plan_status()
+            finally:
+                ctx.set_exact_fp32(False)
+            out = {'global': y['global'], 'keypoints': sel_kp, 'descriptors': sel_desc, 'count': cnt, 'rows': rows}
+        return out
 
     @torch.no_grad()
     def extract_packed(self, points: torch.Tensor, offsets: List[int], model: MinkGL = None, slot: int = 0):
         """points: (sum n_i, 3) float32 already resident on the device; offsets: host list of B+1 scan bounds.
-        `slot` selects the egonn_ctx (plan + workspace): batches on different slots may be in flight at once."""
+        `slot` selects the egonn_ctx (plan + workspace): batches on different slots may be in flight at once.
+
+        Throughput path: it does NOT read the fp16 range flag (that would be one more host synchronisation per batch).  The
+        caller checks `model.context(slot).plan_status()` before the next batch on the slot: `Fp16RangeError` means the
+        outputs of this batch are invalid (`extract` does the check and the exact-fp32 rerun itself)."""
         model = model or self.model
         ctx = model.context(slot)
         q = self.quantizer
@@ -113,7 +126,9 @@ class DescriptorExtractor:
         on HIP stream i % n_streams with its own egonn_ctx, so the latency-bound tail of one batch (small levels,
         heads, top-k: few workgroups) overlaps the bandwidth/MFMA-bound head of the next.  The per-batch size query
         only blocks the host on that batch's stream.  Yields the per-batch result dicts in order; results are valid
-        after `torch.cuda.synchronize()` (or a sync on the batch's stream)."""
+        after `torch.cuda.synchronize()` (or a sync on the batch's stream).  As with `extract_packed`, the fp16 range flag
+        is not read here: the caller checks `model.context(i % n_streams).plan_status()` under the batch's stream before
+        the slot's next batch is drawn (`Fp16RangeError`: the batch's outputs are invalid)."""
         model = model or self.model
         dev = model.context(0).device
         model._sync_weights()

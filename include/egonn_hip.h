@@ -91,7 +91,11 @@ int egonn_voxelize(egonn_ctx* ctx, const float* points, const int64_t* scan_offs
  * coordinate left the +-2^(coord_bits-1) range (status 3) or the batch did not fit the reservation (status 5 =
  * EGONN_STATUS_CAPACITY; the outputs are then invalid — checking the status is MANDATORY for reserved plans: out-of-range /
  * non-finite points are clamped into their sample and overflowing rows are clipped, so an unchecked batch yields
- * plausible-looking but wrong descriptors); afterwards egonn_level_count / egonn_level_batch_offsets return that batch's true sizes. */
+ * plausible-looking but wrong descriptors); afterwards egonn_level_count / egonn_level_batch_offsets return that batch's true sizes.
+ * What a status read covers: the coordinate / capacity state of the latest plan, and the fp16 range flag (status 6, see
+ * egonn_ctx_set_exact_fp32) of everything run on the plan since the start of the latest egonn_forward — every forward clears that
+ * flag in stream order (captured with it), so a forward on the same plan after egonn_ctx_set_exact_fp32(ctx, 1) reports only
+ * itself; operator calls (egonn_sparse_conv, training steps) add to it until the next forward or plan. */
 int egonn_ctx_reserve(egonn_ctx* ctx, int64_t max_points, int batch_size, const int64_t* level_capacity);
 int egonn_voxelize_device(egonn_ctx* ctx, const float* points, int64_t n_rows, const int64_t* scan_offsets_dev,
                           int batch_size, int quant_mode, const float* step, void* stream);
@@ -100,17 +104,24 @@ int egonn_plan_status(egonn_ctx* ctx, void* stream);
  * maps of levels <= 5 run on the fp16 matrix pipe with split operands — x = hi + lo with fp16 parts (|x - hi - lo| <= 2^-22 |x|),
  * weights scaled by a power of two per kernel, the three products hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 with fp32
  * accumulation: within 3e-6 of the plain fp32 kernel relative to the largest output (tests/test_gpu_graph.py,
- * tests/test_gpu_ksplit.py), the low part of an activation below 2^-3 carrying an ABSOLUTE error <= 2^-25.  RANGE: an fp16 part
- * holds |x| < 65504; a finite activation beyond that turns every accumulator that gathers it into Inf / NaN, which the kernels'
- * epilogues detect before BatchNorm / ReLU can hide it: egonn_plan_status (eager and reserved plans alike) then returns
- * EGONN_STATUS_FP16_RANGE for that batch — there is no silent overflow.  on = 1: every level on the exact fp32 kernels
- * (v_mfma_f32_16x16x4_f32: fp32's range, 1/16 of the matrix rate).  Levels 6-7, bf16 maps and channel plans without a split
- * instantiation always run the exact kernels. */
+ * tests/test_gpu_ksplit.py), the low part of an activation below 2^-3 carrying an ABSOLUTE error <= 2^-25.  The two claims meet
+ * at small operands: the 3e-6 relative bound holds for maps whose largest |entry| is at least 2^-4.5 (measured: it stops holding
+ * between 2^-4.6 and 2^-5.0 on four layer shapes, tests/test_gpu_range_edges.py); below that only the absolute bound holds, per
+ * output |err| <= 2^-25 * sum over the gathered offsets and input channels of |W| (plus fp32 rounding) — scale such operands up
+ * (egonn_ctx_set_operand_autoscale) or use on = 1.  RANGE: an fp16 part holds |x| < 65520 (65504 <= |x| < 65520 round to 65504
+ * with an exact low part); an activation at or beyond that, or a non-finite one, turns every accumulator that gathers it into
+ * Inf / NaN, which the kernels' epilogues detect before BatchNorm / ReLU can hide it, and the local heads test their input
+ * before splitting it: egonn_plan_status (eager and reserved plans alike) then returns EGONN_STATUS_FP16_RANGE for that batch —
+ * there is no silent overflow.  on = 1: every level on the exact fp32 kernels (v_mfma_f32_16x16x4_f32: fp32's range, 1/16 of the
+ * matrix rate) and the exact heads.  The 128 -> 128 maps of levels 6-7 run the same split arithmetic on the per-tile kernel,
+ * guarded the same way; bf16 maps and channel plans without a split instantiation always run the exact kernels (the local heads
+ * of bf16 maps are split and guarded). */
 int egonn_ctx_set_exact_fp32(egonn_ctx* ctx, int on);
 /* on = 1: the fp16-split convolutions of this context scale their INPUT map by a power of two per launch (max |in| -> [2^13, 2^14),
  * one reduction launch, undone exactly in the epilogue) — for operands far below 1: the input-gradient convolutions of a training
  * step (training/trainer.py:160-175 -> loss.backward()), whose entries of 1e-6 .. 1e-8 would otherwise lose their fp16 low parts.
- * Eager plans only.  Default 0 (activations of a forward pass sit well inside the range). */
+ * Eager plans only: refused with EGONN_ERR_STATE on a reserved context (the scale reads the map's row count on the host), and
+ * egonn_ctx_reserve refuses a context that has it on.  Default 0 (activations of a forward pass sit well inside the range). */
 int egonn_ctx_set_operand_autoscale(egonn_ctx* ctx, int on);
 /* Row capacity of a level of the current plan (= its row count for eager plans).  No sync. */
 int egonn_level_capacity(egonn_ctx* ctx, int level, int64_t* capacity);
@@ -153,9 +164,9 @@ int egonn_conv_transpose(egonn_ctx* ctx, int level_in, const float* in, int cin,
  * (egonn_map_groups) — the conv2 epilogue form of MinkowskiGlobalPooling (layers/eca_block.py:16,26).  With bf16 maps the
  * sums are taken over the fp32 values BEFORE they are rounded to bf16 for storage (the pooled mean is then the mean of the
  * unrounded activations: closer to the fp32 path than a mean of the stored bf16 numbers; within the configs[2] tolerance).
- * fp32 maps of levels <= 5 run on the fp16 matrix pipe with split operands (fp16 hi + lo parts, three products, fp32
- * accumulate, range guard: see egonn_ctx_set_exact_fp32 above; deviation from the exact fp32 kernel < 3e-6 of the largest
- * output); the maps of levels 3-5 sum a row's offsets in a fixed partition (egonn_debug_set_ksplit).  Non-finite inputs: Inf
+ * fp32 maps of levels <= 5, and the 128 -> 128 maps of levels 6-7, run on the fp16 matrix pipe with split operands (fp16 hi +
+ * lo parts, three products, fp32 accumulate, range guard and small-operand limit: see egonn_ctx_set_exact_fp32 above; deviation
+ * from the exact fp32 kernel < 3e-6 of the largest output); the maps of levels 3-5 sum a row's offsets in a fixed partition (egonn_debug_set_ksplit).  Non-finite inputs: Inf
  * comes out as NaN / Inf and raises the range flag; NaN stays NaN on both paths. */
 int egonn_sparse_conv(egonn_ctx* ctx, int map_kind, int level_out, const void* in, int cin, const float* kernel, int cout,
                       int bf16, const float* scale, const float* shift, int relu, void* out, float* group_sums,

@@ -68,3 +68,22 @@ def make_quantizer(case, mod):
     if str(case["coordinates"]) == "cartesian":
         return mod.CartesianQuantizer(float(step[0]))
     return mod.PolarQuantizer([float(s) for s in step])
+
+
+def sparse_conv_f64(levels, kind, level_out, x, w):
+    """float64 host evaluation of egonn_sparse_conv without epilogue: out[o] = sum_k sum_{(j,o) in map_k} x[j] @ w[k], rows in
+    the order of `levels` (oracle.egonn_ref.SparseLevels).  kind 0: k=3 on level_out; 1: k=2/s=2 from level_out-1; 2: transposed
+    from level_out+1 (the strided map with input and output swapped, ME's conv_transpose).  Non-finite inputs propagate."""
+    x = np.asarray(x, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    if kind == 0:
+        maps = levels.kmap(level_out, level_out, 3)
+    elif kind == 1:
+        maps = levels.kmap(level_out - 1, level_out, 2)
+    else:
+        maps = [(o, j) for j, o in levels.kmap(level_out, level_out + 1, 2)]
+    out = np.zeros((levels.n(level_out), w.shape[-1]), dtype=np.float64)
+    for k, (j, o) in enumerate(maps):
+        if len(j):
+            out[o] += x[j] @ w[k]        # every output row appears at most once per offset
+    return out
