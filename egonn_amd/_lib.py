@@ -54,6 +54,8 @@ _SIGS = [
     ("egonn_bn_fold", C.c_int, [_P, _P, _P, _P, C.c_float, C.c_int, _P, _P, _P]),
     ("egonn_block_tail", C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, C.c_int, _P, _P]),
     ("egonn_gem", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P]),
+    ("egonn_global_max_pool", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
+    ("egonn_netvlad", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     ("egonn_add", C.c_int, [_P, _P, C.c_int64, _P, _P]),
     ("egonn_gather_input", C.c_int, [_P, _P, C.c_int, _P, _P]),
     ("egonn_model_create", C.c_int, [C.POINTER(_P)]),
@@ -408,6 +410,36 @@ class Context:
         out = torch.empty((self.batch_size, x.shape[1]), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             check(self.lib.egonn_gem(self.h, level, x.data_ptr(), x.shape[1], pp.data_ptr(), out.data_ptr(), _stream()))
+        return out
+
+    def global_max_pool(self, level: int, x: torch.Tensor):
+        x = _dev_f32(x, self.device)
+        out = torch.empty((self.batch_size, x.shape[1]), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.egonn_global_max_pool(self.h, level, x.data_ptr(), x.shape[1], out.data_ptr(), _stream()))
+        return out
+
+    def netvlad(self, level: int, x: torch.Tensor, cluster_weights: torch.Tensor, cluster_weights2: torch.Tensor,
+                bn1: torch.nn.BatchNorm1d, hidden1_weights: torch.Tensor, bn2: torch.nn.BatchNorm1d,
+                gating_weights: Optional[torch.Tensor] = None, gate_bn: Optional[torch.nn.BatchNorm1d] = None):
+        """NetVLADLoupe (layers/netvlad.py:18-112) in eval mode over the rows of `level`: (B, output_dim).  gating_weights /
+        gate_bn given = 'netvladgc'.  The BatchNorms are folded on the device; no host synchronisation."""
+        x = _dev_f32(x, self.device)
+        assert x.dim() == 2 and x.shape[0] >= self.level_count(level), "netvlad: x must hold every row of the level"
+        w = [_dev_f32(t.detach(), self.device) for t in (cluster_weights, cluster_weights2, hidden1_weights)]
+        d = w[2].shape[-1]
+        sc1, sh1 = self.bn_fold(bn1)
+        sc2, sh2 = self.bn_fold(bn2)
+        gating = gating_weights is not None
+        gw = scg = shg = None
+        if gating:
+            gw = _dev_f32(gating_weights.detach(), self.device)
+            scg, shg = self.bn_fold(gate_bn)
+        out = torch.empty((self.batch_size, d), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.egonn_netvlad(self.h, level, x.data_ptr(), x.shape[1], w[0].data_ptr(), w[1].data_ptr(),
+                                         sc1.data_ptr(), sh1.data_ptr(), w[2].data_ptr(), sc2.data_ptr(), sh2.data_ptr(),
+                                         _ptr(gw), _ptr(scg), _ptr(shg), d, int(gating), out.data_ptr(), _stream()))
         return out
 
     # ------------------------------------------------------------------ training-mode operators (egonn_amd/train.py)

@@ -120,6 +120,14 @@ int local_heads_pack(const float* const* w6_dev, void* out, hipStream_t stream);
 int select_topk(const float* sigma, const int32_t* boff_dev, int B, int k, const float* kp, const float* desc, int dc,
                 int32_t* sel_rows /*[B][k]*/, int32_t* sel_count /*[B]*/, float* out_kp, float* out_desc, hipStream_t stream);
 
+// netvlad.hip ------------------------------------------------------------------------------------
+// NetVLAD(-GC) pooling of MinkLoc (layers/netvlad.py:18-112) over the scans of boff (DEVICE, B+1): out (B, D).  Four launches;
+// weights in reference layout, bn scale/shift folded (bn_fold); ws: netvlad_workspace_floats(B, C, D) floats.
+size_t netvlad_workspace_floats(int B, int C, int D);
+int netvlad_forward(const float* x, const int32_t* boff, int B, int C, const float* wc, const float* w2, const float* sc1,
+                    const float* sh1, const float* H, int D, const float* sc2, const float* sh2, const float* wg,
+                    const float* scg, const float* shg, int gating, float* out, float* ws, hipStream_t stream);
+
 // loss.hip ---------------------------------------------------------------------------------------
 size_t triplet_loss_scratch_floats(int n);
 int triplet_loss_forward(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float margin,

@@ -547,6 +547,53 @@ API int egonn_gem(egonn_ctx* c, int level, const float* x, int channels, const f
   return gem_finish(partial, c->plan.lv[level].boff, B, channels, p, out, st);
 }
 
+// MAC pooling over the rows of level `level` (MinkowskiGlobalMaxPooling, layers/pooling.py:46-56): out (B, channels)
+API int egonn_global_max_pool(egonn_ctx* c, int level, const float* in, int channels, float* out, void* stream) {
+  REQUIRE_PLAN(c);
+  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && in && out, EGONN_ERR_INVALID, "global_max_pool: bad argument");
+  HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int B = c->plan.batch;
+  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
+  EGONN_TRY(c->work_arena.ensure((size_t)B * SEG_CHUNKS * channels * 4 + 4096));
+  c->work_arena.reset();
+  float* partial = c->work_arena.alloc<float>((size_t)B * SEG_CHUNKS * channels);
+  EGONN_REQUIRE(partial, EGONN_ERR_STATE, "work arena too small");
+  EGONN_TRY(segment_partial_sums(in, c->plan.lv[level].boff, B, channels, 2, nullptr, partial, st));
+  return pool_finish(partial, c->plan.lv[level].boff, B, channels, 2, out, st);
+}
+
+// NetVLAD / NetVLAD-GC pooling over the rows of level `level` (layers/netvlad.py:18-112, netvlad.hip): out (B, out_dim)
+API int egonn_netvlad(egonn_ctx* c, int level, const float* x, int channels, const float* cluster_weights,
+                      const float* cluster_weights2, const float* bn1_scale, const float* bn1_shift,
+                      const float* hidden1_weights, const float* bn2_scale, const float* bn2_shift,
+                      const float* gating_weights, const float* gate_scale, const float* gate_shift, int out_dim, int gating,
+                      float* out, void* stream) {
+  REQUIRE_PLAN(c);
+  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS, EGONN_ERR_INVALID, "netvlad: level %d out of range", level);
+  EGONN_REQUIRE(channels >= 16 && channels <= 512 && channels % 16 == 0, EGONN_ERR_INVALID,
+                "netvlad: %d channels unsupported (multiple of 16, 16..512)", channels);
+  EGONN_REQUIRE(out_dim >= 16 && out_dim <= 1024 && out_dim % 16 == 0, EGONN_ERR_INVALID,
+                "netvlad: output_dim %d unsupported (multiple of 16, 16..1024)", out_dim);
+  EGONN_REQUIRE(x && cluster_weights && cluster_weights2 && bn1_scale && bn1_shift && hidden1_weights && bn2_scale &&
+                    bn2_shift && out && (gating == 0 || gating == 1),
+                EGONN_ERR_INVALID, "netvlad: bad argument");
+  EGONN_REQUIRE(!gating || (gating_weights && gate_scale && gate_shift), EGONN_ERR_INVALID,
+                "netvlad: gating needs gating_weights and the folded gate BatchNorm");
+  EGONN_REQUIRE(((uintptr_t)x & 15) == 0, EGONN_ERR_INVALID, "netvlad: x must be 16-byte aligned");
+  HIP_CHECK(hipSetDevice(c->device));
+  const int B = c->plan.batch;
+  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
+  const size_t nws = netvlad_workspace_floats(B, channels, out_dim);
+  EGONN_TRY(c->work_arena.ensure(nws * 4 + 4096));
+  c->work_arena.reset();
+  float* ws = c->work_arena.alloc<float>(nws);
+  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
+  return netvlad_forward(x, c->plan.lv[level].boff, B, channels, cluster_weights, cluster_weights2, bn1_scale, bn1_shift,
+                         hidden1_weights, out_dim, bn2_scale, bn2_shift, gating_weights, gate_scale, gate_shift, gating, out,
+                         ws, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------ model
 API int egonn_model_create(egonn_model** m) {
   EGONN_REQUIRE(m, EGONN_ERR_INVALID, "model_create: null out pointer");

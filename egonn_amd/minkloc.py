@@ -1,7 +1,8 @@
 """MinkLoc / MinkLoc3D (MinkFPN backbone + GeM) with the reference's Python surface, executed through the
 per-operator entry points of libegonn_hip (reference: models/minkfpn.py, models/minkloc.py,
 third_party/minkloc3d/minkloc.py, models/resnet.py:81-117).  Same kernels as EgoNN, second graph; the module
-tree only holds parameters (identical state_dict keys/shapes), there is no PyTorch fallback.
+tree only holds parameters (identical state_dict keys/shapes), there is no PyTorch fallback.  MinkLoc's pooling
+(layers/pooling.py:13-43) is GeM, MAC, SPoC, netvlad or netvladgc; train mode implements GeM only.
 """
 from __future__ import annotations
 
@@ -119,7 +120,25 @@ class _MinkLocBase(nn.Module):
 
     sync_bn_group = None          # process group of the SyncBN statistics in train mode (None = this process)
 
-    def _forward(self, batch: Dict[str, torch.Tensor], gem_p: torch.Tensor):
+    pooling_method = 'GeM'
+
+    def _pool(self, ctx: _lib.Context, level: int, x: torch.Tensor) -> torch.Tensor:
+        """eval-mode global pooling over the rows of `level` (PoolingWrapper, layers/pooling.py:13-43)"""
+        method = self.pooling_method
+        if method == 'GeM':
+            return ctx.gem(level, x, self.pooling.p if isinstance(self.pooling, GeM) else self.pooling.pooling.p)
+        if method == 'MAC':
+            return ctx.global_max_pool(level, x)
+        if method == 'SPoC':
+            return ctx.global_avg_pool(level, x)
+        if method in ('netvlad', 'netvladgc'):
+            return self.pooling.pooling.run(ctx, level, x)
+        raise NotImplementedError(f'Unknown pooling method: {method}')
+
+    def _forward(self, batch: Dict[str, torch.Tensor], gem_p: torch.Tensor = None):
+        if self.training and self.pooling_method != 'GeM':
+            raise NotImplementedError(f"train mode implements GeM pooling only: pooling method {self.pooling_method!r} "
+                                      f"has no backward here (use the model in eval mode)")
         dev = self._device()
         ctx = self.context()
         coords = batch['coords'].to(device=dev, dtype=torch.int32).contiguous()
@@ -139,7 +158,7 @@ class _MinkLocBase(nn.Module):
         with torch.no_grad():
             level, x = self.backbone.run(ctx, ctx.gather_input(feats))
             assert x.shape[1] == self.feature_size
-            g = ctx.gem(level, x, gem_p)
+            g = self._pool(ctx, level, x)
         assert g.dim() == 2 and g.shape[1] == self.output_dim
         return {'global': g}
 
@@ -158,7 +177,7 @@ class MinkLoc(_MinkLocBase):
         self.pooled_feature_size = self.pooling.output_dim
 
     def forward(self, batch):
-        return self._forward(batch, self.pooling.pooling.p)
+        return self._forward(batch, self.pooling.pooling.p if self.pooling_method == 'GeM' else None)
 
     def print_info(self):
         print('Model class: MinkLoc')

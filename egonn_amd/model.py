@@ -181,16 +181,54 @@ class SPoC(nn.Module):                  # reference layers/pooling.py:59-69 (Min
         self.input_dim = self.output_dim = input_dim
 
 
+class GatingContext(nn.Module):         # reference layers/netvlad.py:83-112 (add_batch_norm=True: no gating_biases)
+    def __init__(self, dim):
+        super().__init__()
+        self.dim = dim
+        self.gating_weights = nn.Parameter(torch.randn(dim, dim) / np.sqrt(dim))
+        self.bn1 = nn.BatchNorm1d(dim)
+
+
+class NetVLADLoupe(nn.Module):          # reference layers/netvlad.py:18-80 (add_batch_norm=True: no cluster_biases)
+    def __init__(self, feature_size, cluster_size, output_dim, gating=True):
+        super().__init__()
+        self.feature_size, self.cluster_size, self.output_dim, self.gating = feature_size, cluster_size, output_dim, gating
+        self.cluster_weights = nn.Parameter(torch.randn(feature_size, cluster_size) / np.sqrt(feature_size))
+        self.cluster_weights2 = nn.Parameter(torch.randn(1, feature_size, cluster_size) / np.sqrt(feature_size))
+        self.hidden1_weights = nn.Parameter(torch.randn(cluster_size * feature_size, output_dim) / np.sqrt(feature_size))
+        self.bn1 = nn.BatchNorm1d(cluster_size)
+        self.bn2 = nn.BatchNorm1d(output_dim)
+        if gating:
+            self.context_gating = GatingContext(output_dim)
+
+
+class NetVLADWrapper(nn.Module):        # reference layers/pooling.py:89-109 (cluster_size fixed at 64)
+    def __init__(self, feature_size, output_dim, gating=True):
+        super().__init__()
+        self.feature_size = self.input_dim = feature_size
+        self.output_dim = output_dim
+        self.net_vlad = NetVLADLoupe(feature_size=feature_size, cluster_size=64, output_dim=output_dim, gating=gating)
+
+    def run(self, ctx: _lib.Context, level: int, x: torch.Tensor) -> torch.Tensor:
+        """eval-mode forward over the rows of `level` (egonn_netvlad): (B, output_dim)"""
+        nv = self.net_vlad
+        cg = nv.context_gating if nv.gating else None
+        return ctx.netvlad(level, x, nv.cluster_weights, nv.cluster_weights2, nv.bn1, nv.hidden1_weights, nv.bn2,
+                           None if cg is None else cg.gating_weights, None if cg is None else cg.bn1)
+
+
 class PoolingWrapper(nn.Module):        # reference layers/pooling.py:13-43
     def __init__(self, pool_method, in_dim, output_dim):
         super().__init__()
-        if pool_method not in ('GeM', 'MAC', 'SPoC'):
-            raise NotImplementedError(f'pooling method {pool_method!r}: the MI355X path implements GeM (the egonn '
-                                      f'configuration, models/model_factory.py:73-76), MAC and SPoC; NetVLAD is unused '
-                                      f'by the egonn configuration')
-        assert in_dim == output_dim
+        if pool_method in ('netvlad', 'netvladgc'):
+            pooling = NetVLADWrapper(feature_size=in_dim, output_dim=output_dim, gating=pool_method == 'netvladgc')
+        elif pool_method in ('GeM', 'MAC', 'SPoC'):
+            assert in_dim == output_dim
+            pooling = {'GeM': GeM, 'MAC': MAC, 'SPoC': SPoC}[pool_method](input_dim=in_dim)
+        else:
+            raise NotImplementedError('Unknown pooling method: {}'.format(pool_method))
         self.pool_method, self.in_dim, self.output_dim = pool_method, in_dim, output_dim
-        self.pooling = {'GeM': GeM, 'MAC': MAC, 'SPoC': SPoC}[pool_method](input_dim=in_dim)
+        self.pooling = pooling
 
 
 # ----------------------------------------------------------------------------- the model
@@ -204,6 +242,9 @@ class MinkGL(nn.Module):
         super().__init__()
         self.trunk = trunk
         self.global_head = global_head
+        if global_pool_method not in ('GeM', 'MAC', 'SPoC'):
+            raise NotImplementedError(f'global pooling method {global_pool_method!r}: the MinkGL (egonn) path implements '
+                                      f'GeM, MAC and SPoC; NetVLAD pooling is available in MinkLoc only')
         self.global_pool_method = global_pool_method
         self.global_channels = global_head.out_channels
         self.global_pooling = PoolingWrapper(global_pool_method, self.global_channels, self.global_channels)

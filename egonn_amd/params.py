@@ -9,7 +9,7 @@ from .quantization import CartesianQuantizer, PolarQuantizer
 
 class ModelParams:
     def __init__(self, model_params_path=None, *, model: str = "egonn", coordinates: str = "polar",
-                 quantization_step=None, **minkloc_kwargs):
+                 quantization_step=None, output_dim: int = 256, **minkloc_kwargs):
         if model_params_path is not None:
             config = configparser.ConfigParser()
             read = config.read(model_params_path)
@@ -27,7 +27,7 @@ class ModelParams:
             mk = dict(minkloc_kwargs)
             self.model_params_path = None
             self.model = model
-            self.output_dim = 256
+            self.output_dim = int(output_dim)
             self.coordinates = coordinates
             raw_step = quantization_step
         assert self.coordinates in ['polar', 'cartesian'], f'Unsupported coordinates: {self.coordinates}'

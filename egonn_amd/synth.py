@@ -68,7 +68,8 @@ def _key_seed(seed: int, key: str) -> int:
 def seeded_tensor(seed: int, key: str, shape: Tuple[int, ...]) -> np.ndarray:
     """Deterministic fp32 tensor for a state_dict entry.  Distribution by key suffix:
     conv kernels / linear weights ~ N(0, sqrt(2/fan)), BN weight ~ U(0.5,1.5), BN bias and
-    running_mean ~ N(0,0.1), running_var ~ U(0.5,1.5), linear bias ~ N(0,0.05), GeM p = 3."""
+    running_mean ~ N(0,0.1), running_var ~ U(0.5,1.5), linear bias ~ N(0,0.05), GeM p = 3; NetVLAD cluster / hidden
+    matrices ~ N(0,1)/sqrt(C), gate ~ N(0,1)/sqrt(D), its bn1 / bn2 weight ~ U(0.5,1.5) and bias ~ N(0,0.1)."""
     rng = np.random.default_rng(_key_seed(seed, key))
     shape = tuple(int(s) for s in shape)
     if key.endswith("num_batches_tracked"):
@@ -90,6 +91,19 @@ def seeded_tensor(seed: int, key: str, shape: Tuple[int, ...]) -> np.ndarray:
     if key.endswith("bn.weight"):
         return rng.uniform(0.5, 1.5, size=shape).astype(np.float32)
     if key.endswith("bn.bias"):
+        return (rng.standard_normal(shape) * 0.1).astype(np.float32)
+    # NetVLADLoupe / GatingContext (reference layers/netvlad.py:26-29,89-90 init scale): randn / sqrt(C), C = feature size
+    if key.endswith("cluster_weights"):
+        return (rng.standard_normal(shape) / np.sqrt(shape[0])).astype(np.float32)
+    if key.endswith("cluster_weights2"):
+        return (rng.standard_normal(shape) / np.sqrt(shape[1])).astype(np.float32)
+    if key.endswith("hidden1_weights"):
+        return (rng.standard_normal(shape) / np.sqrt(shape[0] // 64)).astype(np.float32)   # (C * 64 clusters, D)
+    if key.endswith("gating_weights"):
+        return (rng.standard_normal(shape) / np.sqrt(shape[0])).astype(np.float32)         # (D, D)
+    if key.endswith(("bn1.weight", "bn2.weight")):
+        return rng.uniform(0.5, 1.5, size=shape).astype(np.float32)
+    if key.endswith(("bn1.bias", "bn2.bias")):
         return (rng.standard_normal(shape) * 0.1).astype(np.float32)
     if key.endswith("linear.weight"):
         return (rng.standard_normal(shape) * np.sqrt(2.0 / shape[1])).astype(np.float32)

@@ -195,6 +195,27 @@ int egonn_add(const float* a, const float* b, int64_t n, float* out, void* strea
 int egonn_gather_input(egonn_ctx* ctx, const float* features, int channels, float* out, void* stream);
 /* GeM pooling (layers/pooling.py:82-86, third_party/minkloc3d/minkloc.py:47-59): out (B, channels). */
 int egonn_gem(egonn_ctx* ctx, int level, const float* x, int channels, const float* p, float* out, void* stream);
+/* MAC pooling, MinkowskiGlobalMaxPooling (layers/pooling.py:46-56): out (B, channels), per-sample column max (0 for an
+ * empty sample).  channels <= 256 and a divisor of 256. */
+int egonn_global_max_pool(egonn_ctx* ctx, int level, const float* in, int channels, float* out, void* stream);
+/* NetVLAD / NetVLAD-GC pooling of MinkLoc in eval mode: NetVLADWrapper (layers/pooling.py:89-109) around NetVLADLoupe
+ * (layers/netvlad.py:18-80, cluster_size 64, add_batch_norm=True) and GatingContext (layers/netvlad.py:83-112).
+ * x (N_l, channels) rows of level `level` in plan row order; out (B, out_dim).  Weights are raw device pointers in the
+ * reference layout: cluster_weights (C, 64), cluster_weights2 (1, C, 64), hidden1_weights (C*64, out_dim), gating_weights
+ * (out_dim, out_dim); bn1 / bn2 / gate scale+shift are the eval-mode BatchNorms folded by egonn_bn_fold (64 / out_dim /
+ * out_dim entries).  gating 0 = 'netvlad' (gating pointers ignored, may be NULL), 1 = 'netvladgc'.
+ * Pad rule: the reference zero-pads every scan to Nmax = max_b n_b rows (pad_sequence, layers/pooling.py:103); each pad row
+ * adds softmax(bn1 shift) to the cluster mass a_sum, so a scan's descriptor depends on Nmax of its batch.  That term is
+ * reproduced, with Nmax taken from the plan's device-side row offsets.
+ * Limits: channels % 16 == 0 and 16 <= channels <= 512; out_dim % 16 == 0 and 16 <= out_dim <= 1024; clusters fixed at 64;
+ * x 16-byte aligned.  Anything else returns EGONN_STATUS_INVALID.  Exact fp32 (f32 MFMA / FMA), four launches, no host
+ * sync, workspace from the context: capturable on one stream; bitwise reproducible and independent of the other scans'
+ * order in the batch. */
+int egonn_netvlad(egonn_ctx* ctx, int level, const float* x, int channels, const float* cluster_weights,
+                  const float* cluster_weights2, const float* bn1_scale, const float* bn1_shift,
+                  const float* hidden1_weights, const float* bn2_scale, const float* bn2_shift,
+                  const float* gating_weights, const float* gate_scale, const float* gate_shift, int out_dim, int gating,
+                  float* out, void* stream);
 
 /* ------------------------------------------------------------------ model
  * replaces model_factory(...) / MinkGL.forward: models/model_factory.py:31-76, models/minkgl.py:267-315       */
