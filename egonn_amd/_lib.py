@@ -495,8 +495,8 @@ class Context:
     def col_stats(self, mode: int, a, b=None, mask=None, mean=None):
         a = _dev_f32(a, self.device)
         n, c = a.shape
-        out = torch.empty((2, c), dtype=torch.float32, device=self.device)
-        sc = self.scratch(2 * c * max(1024, n // 512 + 2))
+        out = torch.empty((2, c), dtype=torch.float64, device=self.device)       # fp64 sums (egonn_col_stats)
+        sc = self.scratch(4 * c * max(1024, n // 512 + 2))
         self._call(self.lib.egonn_col_stats, mode, a.data_ptr(), _ptr(b), _ptr(mask), _ptr(mean), n, c, out.data_ptr(),
                    sc.data_ptr(), sc.numel())
         return out

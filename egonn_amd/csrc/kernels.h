@@ -148,11 +148,11 @@ int conv_wgrad(const float* in, const float* dout, const int32_t* nbr, int64_t n
                float* dW, float* scratch, size_t scratch_floats, hipStream_t stream, const RowGroups* rg = nullptr);
 int conv0_wgrad(Ctx* ctx, const float* feat, const float* dout, float* dW, float* scratch, size_t scratch_floats,
                 hipStream_t stream);
-int col_stats(int mode, const float* a, const float* b, const float* mask, const float* m, int64_t n, int c, float* out2c,
+int col_stats(int mode, const float* a, const float* b, const float* mask, const float* m, int64_t n, int c, double* out2c,
               float* scratch, size_t scratch_floats, hipStream_t stream);
-int bn_fwd_finalize(const float* sums, const float* m, double n, int c, const float* w, const float* b, float eps,
+int bn_fwd_finalize(const double* sums, const float* m, double n, int c, const float* w, const float* b, float eps,
                     float momentum, float* running_mean, float* running_var, float* out4, hipStream_t stream);
-int bn_bwd_finalize(const float* local, const float* global, double n, int c, const float* w, const float* mean,
+int bn_bwd_finalize(const double* local, const double* global, double n, int c, const float* w, const float* mean,
                     const float* invstd, float* out5, hipStream_t stream);
 int affine_act(const float* x, const float* A, const float* B, int64_t n, int c, int relu, float* out, hipStream_t stream);
 int affine3(const float* g, const float* mask, const float* x, const float* A, const float* B, const float* C, int64_t n,

@@ -593,51 +593,55 @@ int conv0_wgrad(Ctx* ctx, const float* feat, const float* dout, float* dW, float
 // mode 1: s0 = sum (a - m)^2    s1 = 0                                  (second pass of the batch variance)
 // mode 2: g = a * [mask > 0] (mask nullable);  s0 = sum g,  s1 = sum g * (b - m)     (BatchNorm backward)
 // mode 3: d = a - m;  s0 = sum d,  s1 = sum d^2     (single-pass batch statistics around the shift m, additive over ranks)
+// Every difference, product and sum is formed in fp64 (the fp32 inputs convert exactly; a - m and a^2 of two fp32 values are
+// exact in fp64).  Mode 3 feeds var = S2/n - (S1/n)^2, whose relative error is the sums' relative error times (mean/std)^2:
+// with fp32 sums that was 6e-8 (mean/std)^2, 5e-2 on invstd at mean/std = 1000, and the shift (the running mean) is 0 on the
+// first step and lags the batch mean after it.  Partials and the (2, c) result are doubles.
 // block = 256 threads = (256/CP) row lanes x CP channel lanes (CP = channels padded to a power of two <= 256)
 static constexpr int CS_ROWS = 512;   // rows per block
 __global__ __launch_bounds__(256) void col_stats_kernel(int mode, const float* __restrict__ a, const float* __restrict__ b,
                                                        const float* __restrict__ mask, const float* __restrict__ m,
-                                                       int64_t n, int c, int cp, float* __restrict__ partial) {
-  __shared__ float red[2][256];
+                                                       int64_t n, int c, int cp, double* __restrict__ partial) {
+  __shared__ double red[2][256];
   const int t = threadIdx.x;
   const int ci = t % cp, rl = t / cp, nrl = 256 / cp;
   const int64_t r0 = (int64_t)blockIdx.x * CS_ROWS, r1 = min(n, r0 + CS_ROWS);
-  float s0 = 0.f, s1 = 0.f;
+  double s0 = 0.0, s1 = 0.0;
   if (ci < c) {
-    const float mu = (mode != 0 && m) ? m[ci] : 0.f;
+    const double mu = (mode != 0 && m) ? (double)m[ci] : 0.0;
     if (mode == 0) {
 #pragma unroll 4
       for (int64_t r = r0 + rl; r < r1; r += nrl) {
-        const float av = a[r * c + ci];
+        const double av = a[r * c + ci];
         s0 += av;
-        s1 = fmaf(av, av, s1);
+        s1 = fma(av, av, s1);
       }
     } else if (mode == 1) {
 #pragma unroll 4
       for (int64_t r = r0 + rl; r < r1; r += nrl) {
-        const float d = a[r * c + ci] - mu;
-        s0 = fmaf(d, d, s0);
+        const double d = (double)a[r * c + ci] - mu;
+        s0 = fma(d, d, s0);
       }
     } else if (mode == 3) {
 #pragma unroll 4
       for (int64_t r = r0 + rl; r < r1; r += nrl) {
-        const float d = a[r * c + ci] - mu;
+        const double d = (double)a[r * c + ci] - mu;
         s0 += d;
-        s1 = fmaf(d, d, s1);
+        s1 = fma(d, d, s1);
       }
     } else if (mask) {
 #pragma unroll 4
       for (int64_t r = r0 + rl; r < r1; r += nrl) {
-        const float gq = (mask[r * c + ci] > 0.f) ? a[r * c + ci] : 0.f;
+        const double gq = (mask[r * c + ci] > 0.f) ? (double)a[r * c + ci] : 0.0;
         s0 += gq;
-        s1 = fmaf(gq, b[r * c + ci] - mu, s1);
+        s1 = fma(gq, (double)b[r * c + ci] - mu, s1);
       }
     } else {
 #pragma unroll 4
       for (int64_t r = r0 + rl; r < r1; r += nrl) {
-        const float gq = a[r * c + ci];
+        const double gq = a[r * c + ci];
         s0 += gq;
-        s1 = fmaf(gq, b[r * c + ci] - mu, s1);
+        s1 = fma(gq, (double)b[r * c + ci] - mu, s1);
       }
     }
   }
@@ -645,7 +649,7 @@ __global__ __launch_bounds__(256) void col_stats_kernel(int mode, const float* _
   red[1][t] = s1;
   __syncthreads();
   if (t < c) {
-    float u0 = 0.f, u1 = 0.f;
+    double u0 = 0.0, u1 = 0.0;
     for (int k = 0; k < nrl; ++k) {
       u0 += red[0][k * cp + t];
       u1 += red[1][k * cp + t];
@@ -656,25 +660,27 @@ __global__ __launch_bounds__(256) void col_stats_kernel(int mode, const float* _
 }
 
 
-// The same statistics with 16-byte accesses (channel counts that are multiples of 4: every BatchNorm of the models): thread =
+// The same statistics with 16-byte loads (channel counts that are multiples of 4: every BatchNorm of the models): thread =
 // (row lane, four consecutive channels), 1024 rows per block, four rows in flight per thread.  The scalar kernel above ran at
 // a third of the HBM rate (36 us per call on average over the 50 calls of a 32-scan step, 1.8 ms per step).
 static constexpr int CS4_ROWS = 1024;   // rows per block on big maps; small maps get fewer (a block of a 1 500-row map walked
                                         // 128 rows per thread one after the other: 28 us forward, 60 us backward per call)
 __global__ __launch_bounds__(256) void col_stats4_kernel(int mode, const float* __restrict__ a, const float* __restrict__ b,
                                                         const float* __restrict__ mask, const float* __restrict__ m,
-                                                        int64_t n, int c, int rows_per_block, float* __restrict__ partial) {
+                                                        int64_t n, int c, int rows_per_block, double* __restrict__ partial) {
   typedef float f4 __attribute__((ext_vector_type(4)));
-  __shared__ f4 red[2][256];
+  typedef double d4 __attribute__((ext_vector_type(4)));
+  __shared__ d4 red[2][256];
   const int t = threadIdx.x;
   const int lq = c >> 2;                                   // lanes per row (8 .. 64), a power of two or 24 / 48
   const int nrl = 256 / lq;                                // row lanes (threads beyond nrl * lq idle)
   const int ci = t % lq, rl = t / lq;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_block, r1 = min(n, r0 + rows_per_block);
-  f4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+  d4 s0 = {0.0, 0.0, 0.0, 0.0}, s1 = {0.0, 0.0, 0.0, 0.0};
   if (rl < nrl) {
     f4 mu = {0.f, 0.f, 0.f, 0.f};
     if (mode != 0 && m) mu = *reinterpret_cast<const f4*>(m + 4 * ci);
+    const d4 mud = __builtin_convertvector(mu, d4);
     const f4* a4 = reinterpret_cast<const f4*>(a) + ci;
     const f4* b4 = reinterpret_cast<const f4*>(b) + ci;
     const f4* k4 = reinterpret_cast<const f4*>(mask) + ci;
@@ -693,24 +699,25 @@ __global__ __launch_bounds__(256) void col_stats4_kernel(int mode, const float* 
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
+        const d4 ad = __builtin_convertvector(av[u], d4);
         if (mode == 0) {
-          s0 += av[u];
-          s1 += av[u] * av[u];
+          s0 += ad;
+          s1 += ad * ad;
         } else if (mode == 1) {
-          const f4 d = av[u] - mu;
+          const d4 d = ad - mud;
           s0 += d * d;
         } else if (mode == 3) {
-          const f4 d = av[u] - mu;
+          const d4 d = ad - mud;
           s0 += d;
           s1 += d * d;
         } else {
-          f4 g = av[u];
+          d4 g = ad;
           if (mask) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) g[q] = kv[u][q] > 0.f ? g[q] : 0.f;
+            for (int q = 0; q < 4; ++q) g[q] = kv[u][q] > 0.f ? g[q] : 0.0;
           }
           s0 += g;
-          s1 += g * (bv[u] - mu);
+          s1 += g * (__builtin_convertvector(bv[u], d4) - mud);
         }
       }
     }
@@ -719,36 +726,41 @@ __global__ __launch_bounds__(256) void col_stats4_kernel(int mode, const float* 
   red[1][t] = s1;
   __syncthreads();
   if (t < lq) {
-    f4 u0 = {0.f, 0.f, 0.f, 0.f}, u1 = {0.f, 0.f, 0.f, 0.f};
+    d4 u0 = {0.0, 0.0, 0.0, 0.0}, u1 = {0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < nrl; ++k) {
       u0 += red[0][k * lq + t];
       u1 += red[1][k * lq + t];
     }
-    *reinterpret_cast<f4*>(partial + ((int64_t)blockIdx.x * 2 + 0) * c + 4 * t) = u0;
-    *reinterpret_cast<f4*>(partial + ((int64_t)blockIdx.x * 2 + 1) * c + 4 * t) = u1;
+    double* p0 = partial + ((int64_t)blockIdx.x * 2 + 0) * c + 4 * t;
+    double* p1 = partial + ((int64_t)blockIdx.x * 2 + 1) * c + 4 * t;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      p0[q] = u0[q];
+      p1[q] = u1[q];
+    }
   }
 }
 
 // out[i] = sum over chunks of partial[ch][i]: one wave per output value (few values, many chunks), fp64, fixed order
-__global__ __launch_bounds__(64) void sum_partials_wave_kernel(const float* __restrict__ partial, int chunks, int64_t size,
-                                                              float* __restrict__ out) {
+__global__ __launch_bounds__(64) void sum_partials_wave_kernel(const double* __restrict__ partial, int chunks, int64_t size,
+                                                              double* __restrict__ out) {
   const int64_t i = blockIdx.x;
   double s = 0.0;
-  for (int ch = threadIdx.x; ch < chunks; ch += 64) s += (double)partial[(int64_t)ch * size + i];
+  for (int ch = threadIdx.x; ch < chunks; ch += 64) s += partial[(int64_t)ch * size + i];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-  if (threadIdx.x == 0) out[i] = (float)s;
+  if (threadIdx.x == 0) out[i] = s;
 }
 
 // the same with a whole workgroup per output value (the BatchNorm statistics: 64-512 outputs, 500-1 600 partial rows): thread t
 // adds rows t, t + 256, ... in ascending order, the 256 sums are added in a fixed binary tree
-__global__ __launch_bounds__(256) void sum_partials_block_kernel(const float* __restrict__ partial, int chunks, int64_t size,
-                                                                float* __restrict__ out) {
+__global__ __launch_bounds__(256) void sum_partials_block_kernel(const double* __restrict__ partial, int chunks, int64_t size,
+                                                                double* __restrict__ out) {
   __shared__ double red[256];
   const int64_t i = blockIdx.x;
   const int t = threadIdx.x;
   double s = 0.0;
-  for (int ch = t; ch < chunks; ch += 256) s += (double)partial[(int64_t)ch * size + i];
+  for (int ch = t; ch < chunks; ch += 256) s += partial[(int64_t)ch * size + i];
   red[t] = s;
   __syncthreads();
 #pragma unroll
@@ -756,29 +768,33 @@ __global__ __launch_bounds__(256) void sum_partials_block_kernel(const float* __
     if (t < o) red[t] += red[t + o];
     __syncthreads();
   }
-  if (t == 0) out[i] = (float)red[0];
+  if (t == 0) out[i] = red[0];
 }
 
-int col_stats(int mode, const float* a, const float* b, const float* mask, const float* m, int64_t n, int c, float* out2c,
-              float* scratch, size_t scratch_floats, hipStream_t stream) {
+int col_stats(int mode, const float* a, const float* b, const float* mask, const float* m, int64_t n, int c, double* out2c,
+              float* scratch_f, size_t scratch_floats, hipStream_t stream) {
   EGONN_REQUIRE(c >= 1 && c <= 256, EGONN_ERR_INVALID, "col_stats: %d channels unsupported (1..256)", c);
   EGONN_REQUIRE(mode >= 0 && mode <= 3 && a && (mode != 2 || b), EGONN_ERR_INVALID, "col_stats: bad arguments");
+  EGONN_REQUIRE((reinterpret_cast<uintptr_t>(out2c) & 7u) == 0 && (reinterpret_cast<uintptr_t>(scratch_f) & 7u) == 0,
+                EGONN_ERR_INVALID, "col_stats: out and scratch hold doubles (8-byte alignment)");
   if (n == 0) {
-    HIP_CHECK(hipMemsetAsync(out2c, 0, (size_t)2 * c * 4, stream));
+    HIP_CHECK(hipMemsetAsync(out2c, 0, (size_t)2 * c * sizeof(double), stream));
     return EGONN_OK;
   }
+  double* scratch = reinterpret_cast<double*>(scratch_f);
+  const size_t scratch_doubles = scratch_floats / 2;
   const bool aligned16 = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(mask) |
                            reinterpret_cast<uintptr_t>(m)) & 15u) == 0;
   if (c % 4 == 0 && c >= 32 && 256 % (c / 4) == 0 && aligned16) {      // 32 / 64 / 128 / 256 channels: 16-byte accesses
     // >= ~500 blocks whenever the map has the rows for it (a function of n only: deterministic)
     int rpb = CS4_ROWS;
     while (rpb > 32 && cdiv(n, rpb) < 512) rpb >>= 1;
-    // never more than 1 023 blocks below CS4_ROWS rows per block, so 2*c*max(1024, ceil(n/512)) floats (the header's contract)
+    // never more than 1 023 blocks below CS4_ROWS rows per block, so 4*c*max(1024, ceil(n/512)) floats (the header's contract)
     // always hold them; a caller with less gets coarser blocks (another fixed summation order) instead of an error
-    while (rpb < CS4_ROWS && (size_t)cdiv(n, rpb) * 2 * c > scratch_floats) rpb <<= 1;
+    while (rpb < CS4_ROWS && (size_t)cdiv(n, rpb) * 2 * c > scratch_doubles) rpb <<= 1;
     const int64_t blocks4 = cdiv(n, rpb);
-    EGONN_REQUIRE(scratch && scratch_floats >= (size_t)blocks4 * 2 * c, EGONN_ERR_INVALID,
-                  "col_stats: scratch too small (%zu < %lld floats)", scratch_floats, (long long)(blocks4 * 2 * c));
+    EGONN_REQUIRE(scratch && scratch_doubles >= (size_t)blocks4 * 2 * c, EGONN_ERR_INVALID,
+                  "col_stats: scratch too small (%zu < %lld floats)", scratch_floats, (long long)(blocks4 * 4 * c));
     hipLaunchKernelGGL(col_stats4_kernel, dim3((unsigned)blocks4), dim3(256), 0, stream, mode, a, b, mask, m, n, c, rpb, scratch);
     if (blocks4 >= 256)
       hipLaunchKernelGGL(sum_partials_block_kernel, dim3((unsigned)(2 * c)), dim3(256), 0, stream, scratch, (int)blocks4,
@@ -792,8 +808,8 @@ int col_stats(int mode, const float* a, const float* b, const float* mask, const
   int cp = 1;
   while (cp < c) cp <<= 1;
   const int64_t blocks = cdiv(n, CS_ROWS);
-  EGONN_REQUIRE(scratch && scratch_floats >= (size_t)blocks * 2 * c, EGONN_ERR_INVALID,
-                "col_stats: scratch too small (%zu < %lld floats)", scratch_floats, (long long)(blocks * 2 * c));
+  EGONN_REQUIRE(scratch && scratch_doubles >= (size_t)blocks * 2 * c, EGONN_ERR_INVALID,
+                "col_stats: scratch too small (%zu < %lld floats)", scratch_floats, (long long)(blocks * 4 * c));
   hipLaunchKernelGGL(col_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, mode, a, b, mask, m, n, c, cp,
                      scratch);
   hipLaunchKernelGGL(sum_partials_wave_kernel, dim3((unsigned)(2 * c)), dim3(64), 0, stream, scratch, (int)blocks,
@@ -803,10 +819,10 @@ int col_stats(int mode, const float* a, const float* b, const float* mask, const
 }
 
 // ------------------------------------------------------------------------------------------- BatchNorm vector math
-// forward: sums (2,c) = [sum d, sum d^2] around shift m (whole batch, after the SyncBN all-reduce), count n ->
+// forward: fp64 sums (2,c) = [sum d, sum d^2] around shift m (whole batch, after the SyncBN all-reduce), count n ->
 //   mean, invstd, scale = w * invstd, shift = b - mean * scale (out4: 4 x c), running statistics updated in place
 //   (momentum; unbiased variance), exactly nn.BatchNorm1d's bookkeeping.
-__global__ void bn_fwd_finalize_kernel(const float* __restrict__ sums, const float* __restrict__ m, double n, int c,
+__global__ void bn_fwd_finalize_kernel(const double* __restrict__ sums, const float* __restrict__ m, double n, int c,
                                        const float* __restrict__ w, const float* __restrict__ b, float eps, float momentum,
                                        float* __restrict__ running_mean, float* __restrict__ running_var,
                                        float* __restrict__ out4) {
@@ -822,38 +838,38 @@ __global__ void bn_fwd_finalize_kernel(const float* __restrict__ sums, const flo
   out4[i] = (float)mean;
   out4[c + i] = invstd;
   out4[2 * c + i] = scale;
-  out4[3 * c + i] = b[i] - (float)mean * scale;
+  out4[3 * c + i] = (float)((double)b[i] - mean * (double)scale);
   if (running_mean) {
     const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
     running_mean[i] = (1.f - momentum) * running_mean[i] + momentum * (float)mean;
     running_var[i] = (1.f - momentum) * running_var[i] + momentum * (float)unbiased;
   }
 }
-// backward: local sums (2,c) = [sum g', sum g'(x - mean)] of this rank, global sums (after the all-reduce), count n ->
+// backward: fp64 local sums (2,c) = [sum g', sum g'(x - mean)] of this rank, global sums (after the all-reduce), count n ->
 //   out5: A = w invstd, B = -w invstd^3 S2/n, C = -B mean - A S1/n, dgamma = S2_local invstd, dbeta = S1_local
-__global__ void bn_bwd_finalize_kernel(const float* __restrict__ local, const float* __restrict__ global, double n, int c,
+__global__ void bn_bwd_finalize_kernel(const double* __restrict__ local, const double* __restrict__ global, double n, int c,
                                        const float* __restrict__ w, const float* __restrict__ mean,
                                        const float* __restrict__ invstd, float* __restrict__ out5) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= c) return;
   const double inv = invstd[i], wi = w[i];
   const double A = wi * inv;
-  const double Bc = -wi * inv * inv * inv * (double)global[c + i] / n;
-  const double Cc = -Bc * (double)mean[i] - A * (double)global[i] / n;
+  const double Bc = -wi * inv * inv * inv * global[c + i] / n;
+  const double Cc = -Bc * (double)mean[i] - A * global[i] / n;
   out5[i] = (float)A;
   out5[c + i] = (float)Bc;
   out5[2 * c + i] = (float)Cc;
-  out5[3 * c + i] = (float)((double)local[c + i] * inv);
-  out5[4 * c + i] = local[i];
+  out5[3 * c + i] = (float)(local[c + i] * inv);
+  out5[4 * c + i] = (float)local[i];
 }
-int bn_fwd_finalize(const float* sums, const float* m, double n, int c, const float* w, const float* b, float eps,
+int bn_fwd_finalize(const double* sums, const float* m, double n, int c, const float* w, const float* b, float eps,
                     float momentum, float* running_mean, float* running_var, float* out4, hipStream_t stream) {
   hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((unsigned)cdiv(c, 64)), dim3(64), 0, stream, sums, m, n, c, w, b, eps,
                      momentum, running_mean, running_var, out4);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
-int bn_bwd_finalize(const float* local, const float* global, double n, int c, const float* w, const float* mean,
+int bn_bwd_finalize(const double* local, const double* global, double n, int c, const float* w, const float* mean,
                     const float* invstd, float* out5, hipStream_t stream) {
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(c, 64)), dim3(64), 0, stream, local, global, n, c, w, mean,
                      invstd, out5);

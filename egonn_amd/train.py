@@ -116,8 +116,10 @@ def level_totals(ctx: _lib.Context, group=None) -> List[float]:
 
 class BatchNormFn(Function):
     """nn.BatchNorm1d over all rows in train mode (MinkowskiBatchNorm), optional fused ReLU, optional SyncBN.
-    Statistics: ONE pass of shifted sums (sum d, sum d^2 with d = x - running_mean: additive over ranks, robust
-    against cancellation because the shift is close to the mean), all-reduced when `group` is given; the per-channel
+    Statistics: ONE pass of shifted sums (sum d, sum d^2 with d = x - running_mean: additive over ranks), formed and kept
+    in fp64 ((2, C) doubles through the all-reduce and both finalize kernels): the shift is 0 on a first step and lags the
+    batch mean after it, and var = S2/n - (S1/n)^2 loses (mean/std)^2 of the sums' relative precision, which fp32 sums
+    could not afford.  All-reduced when `group` is given; the per-channel
     bookkeeping (mean, invstd, folded scale/shift, running statistics; A/B/C, dgamma, dbeta in backward) runs in one
     small kernel each."""
 
@@ -270,7 +272,7 @@ class LinearFn(Function):
             g = ctx.act_backward(act, g, y)
         dx = ctx.dense(g, _c(weight.detach()), out_in=False) if fctx.needs_input_grad[0] else None
         dw = ctx.dense_backward_weight(g, x) if fctx.needs_input_grad[1] else None
-        db = ctx.col_stats(0, g)[0].clone() if has_bias and fctx.needs_input_grad[2] else None
+        db = ctx.col_stats(0, g)[0].float() if has_bias and fctx.needs_input_grad[2] else None
         return dx, dw, db, None, None
 
 
@@ -316,7 +318,11 @@ class GeMFn(Function):
         if fctx.needs_input_grad[1]:
             T = ctx.segment_sums(level, 1, x, p=_c(p.detach().reshape(-1).float()))    # sum_r t^p ln t
             S = out.pow(pv) * cnt                                                       # sum_r t^p
-            dout_dp = out * (-(torch.log(out.pow(pv))) / (pv * pv) + T / (pv * S))
+            # dout/dp = out/p (T/S - ln out): ln(out) directly, not ln(out^p)/p, which is -inf once out^p underflows (out near
+            # the 1e-6 clamp with p > 6.3).  An empty sample (out = 0, S = 0) pools to a constant 0 and contributes nothing:
+            # 0 * (inf + nan) would be NaN for the whole batch.
+            live = out > 0
+            dout_dp = torch.where(live, out / pv * (T / S - torch.log(out.clamp_min(1e-30))), torch.zeros_like(out))
             dp = (g * dout_dp).sum().reshape(p.shape)
         return dx, dp, None, None
 

@@ -305,21 +305,23 @@ int egonn_dense_backward_weight(const float* a, int ca, const float* b, int cb, 
 int egonn_conv_backward_weight(egonn_ctx* ctx, int level_in, int level_out, int kernel_size, int transposed,
                                const float* in, int cin, const float* grad_out, int cout, float* grad_kernel,
                                float* scratch, int64_t scratch_floats, void* stream);
-/* Per-channel reductions over (n,c) rows -> out (2,c).  MinkowskiBatchNorm in train mode = nn.BatchNorm1d over all
- * rows (models/minkgl.py:102,107):  mode 0: sum a, sum a^2;  mode 1: sum (a-mean)^2, 0;
+/* Per-channel reductions over (n,c) fp32 rows -> out (2,c) DOUBLES.  MinkowskiBatchNorm in train mode = nn.BatchNorm1d over
+ * all rows (models/minkgl.py:102,107):  mode 0: sum a, sum a^2;  mode 1: sum (a-mean)^2, 0;
  * mode 2 (backward): g = a*[mask>0] (mask nullable): sum g, sum g*(b-mean);  mode 3: d = a-mean: sum d, sum d^2 (one-pass
- * statistics around a shift point, additive over ranks for SyncBN).  scratch >= 2*c*max(1024, ceil(n/512)) floats makes the
- * row blocking (and so the fp32 summation order) a function of n only; the minimum accepted is 2*c*ceil(n/512). */
+ * statistics around a shift point, additive over ranks for SyncBN).  Differences, products and sums are fp64 throughout, so
+ * the one-pass variance S2/n - (S1/n)^2 stays accurate whatever the shift (0 on a first step).  out and scratch must be
+ * 8-byte aligned; scratch holds fp64 partials: >= 4*c*max(1024, ceil(n/512)) floats makes the row blocking (and so the
+ * summation order) a function of n only; the minimum accepted is 4*c*ceil(n/512). */
 int egonn_col_stats(int mode, const float* a, const float* b, const float* mask, const float* mean, int64_t n, int c,
-                    float* out, float* scratch, int64_t scratch_floats, void* stream);
+                    double* out, float* scratch, int64_t scratch_floats, void* stream);
 /* Per-channel BatchNorm bookkeeping of nn.BatchNorm1d in train mode, on the device:
- * forward: sums (2,c) from mode 3 around shift_point (c) over `count` rows (whole batch) -> out (4,c) = mean, invstd,
+ * forward: fp64 sums (2,c) from mode 3 around shift_point (c) over `count` rows (whole batch) -> out (4,c) = mean, invstd,
  * scale = weight*invstd, shift = bias - mean*scale; running_mean/var (nullable) updated with `momentum` (unbiased var).
- * backward: local/global (2,c) sums from mode 2 -> out (5,c) = A, B, C of egonn_affine3, dgamma, dbeta. */
-int egonn_bn_train_finalize(const float* sums, const float* shift_point, double count, int c, const float* weight,
+ * backward: local/global fp64 (2,c) sums from mode 2 -> out (5,c) = A, B, C of egonn_affine3, dgamma, dbeta. */
+int egonn_bn_train_finalize(const double* sums, const float* shift_point, double count, int c, const float* weight,
                             const float* bias, float eps, float momentum, float* running_mean, float* running_var,
                             float* out_mean_invstd_scale_shift, void* stream);
-int egonn_bn_backward_finalize(const float* local_sums, const float* global_sums, double count, int c, const float* weight,
+int egonn_bn_backward_finalize(const double* local_sums, const double* global_sums, double count, int c, const float* weight,
                                const float* mean, const float* invstd, float* out_abc_dgamma_dbeta, void* stream);
 /* out = relu?(x*scale[c] + shift[c]) — BatchNorm application with batch statistics folded by the caller. */
 int egonn_affine_act(const float* x, const float* scale, const float* shift, int64_t n, int c, int relu, float* out,

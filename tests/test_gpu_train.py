@@ -257,10 +257,12 @@ def test_train_step_matches_reference_fixture(name):
                    float(np.abs(mine[2:] - ref[2:]).max()) / max(float(np.abs(ref[2:]).max()), 1e-12))
 
     # How well is this gradient DEFINED in fp32?  The same step on the plain one-thread-per-output kernels and on the exact fp32 MFMA
-    # kernels — two exact-fp32 summation orders of the same convolutions.  With the local-head terms in the loss the two disagree by
-    # up to 2e-2 on the first layers of the polar case (measured, tools/exp/r06_train_grad_sensitivity.py: a perturbation of 1e-7 at
-    # level 3 moves those entries by percent, whichever kernel causes it), so an entry is held to the reference within
-    # max(5e-3, 2 x that spread): 5e-3 wherever fp32 pins the value, the fp32 noise floor of the quantity where it does not.
+    # kernels — two exact-fp32 summation orders of the same convolutions.  With fp32 BatchNorm statistics the two disagreed by up to
+    # 2e-2 on the first layers of the polar case (the one-pass variance amplified a 1e-7 perturbation at level 3 to percent); with
+    # the fp64 statistics the largest spread measured on the MI355X is 6.4e-5 (polar, trunk.bn.6.bn.weight) and the largest error
+    # against the fixture 1.2e-4.  Every tensor is held to 5e-3; only a name in RELAXED may use max(5e-3, min(2 x spread, 2e-2)),
+    # and the spread itself must stay under 2.5e-3, or 5e-3 no longer sits above the fp32 noise of the quantity it gates.
+    RELAXED = {}      # name -> spread measured on the MI355X; none is needed with fp64 BatchNorm statistics
     def grads_under(setting):
         m2 = egonn_amd.model_factory(mp)
         m2.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()})
@@ -287,7 +289,8 @@ def test_train_step_matches_reference_fixture(name):
         mine, ref = _digest(k, grads[k].detach().cpu().numpy()), case["grad/" + k]
         err = digest_err(mine, ref)
         floor = digest_err(g_exact[k], g_plain[k])
-        if err > max(5e-3, 2.0 * floor):
+        gate = max(5e-3, min(2.0 * floor, 2e-2)) if k in RELAXED else 5e-3
+        if err > gate or (k not in RELAXED and floor > 2.5e-3):
             bad.append((k, err, floor))
     assert not bad, bad
     sd = model.state_dict()
