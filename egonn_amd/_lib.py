@@ -30,6 +30,7 @@ _SIGS = [
     ("egonn_debug_set_trace", C.c_int, [_P]),
     ("egonn_prepare_maps", C.c_int, [_P, C.c_int, _P]),
     ("egonn_debug_rowgroup_tables", C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+    ("egonn_debug_rowgroup_perm", C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
     ("egonn_voxelize", C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
     ("egonn_ctx_reserve", C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     ("egonn_voxelize_device", C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
@@ -338,6 +339,15 @@ class Context:
             check(self.lib.egonn_debug_rowgroup_tables(self.h, map_kind, level_out, gm.data_ptr(), sn.data_ptr() if with_rows else None,
                                                        ng, C.byref(n), _stream()))
         return gm, sn
+
+    def rowgroup_perm(self, map_kind: int, level_out: int):
+        """test hook: perm [groups, 16] int32 of a map's row-group tables, the output row of every slot (-1 = padding)."""
+        ng, _ = self.map_groups(map_kind, level_out)
+        pm = torch.empty((ng, 16), dtype=torch.int32, device=self.device)
+        n = C.c_int64()
+        with torch.cuda.device(self.device):
+            check(self.lib.egonn_debug_rowgroup_perm(self.h, map_kind, level_out, pm.data_ptr(), ng, C.byref(n), _stream()))
+        return pm
 
     def set_naive_conv(self, on: bool):
         """tests only: route this context's sparse convolutions through the plain (non-MFMA) kernel."""

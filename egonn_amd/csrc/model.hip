@@ -439,6 +439,25 @@ API int egonn_debug_rowgroup_tables(egonn_ctx* c, int map_kind, int level_out, u
   return EGONN_OK;
 }
 
+// Test hook (tests/test_gpu_maps.py): device copy of a map's perm table, [groups][16] i32, the output row of every slot (-1 =
+// padding) — with gmask and snbr of the hook above the whole row-group form.  [SYNC]
+API int egonn_debug_rowgroup_perm(egonn_ctx* c, int map_kind, int level_out, int32_t* perm_out, int64_t capacity_groups,
+                                  int64_t* n_groups, void* stream) {
+  REQUIRE_PLAN(c);
+  HIP_CHECK(hipSetDevice(c->device));
+  EGONN_REQUIRE(n_groups && perm_out, EGONN_ERR_INVALID, "rowgroup_perm: null argument");
+  EGONN_TRY(ensure_rowgroups(c, &map_kind, &level_out, 1, (hipStream_t)stream));
+  const Level& V = c->plan.lv[level_out];
+  const RowGroups& rg = map_kind == 0 ? V.rg27 : (map_kind == 1 ? V.rg8 : V.rgT);
+  int32_t ng = 0;
+  HIP_CHECK(hipMemcpyAsync(&ng, rg.meta, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  EGONN_REQUIRE(ng <= capacity_groups, EGONN_ERR_INVALID, "rowgroup_perm: %d groups, room for %lld", ng, (long long)capacity_groups);
+  HIP_CHECK(hipMemcpyAsync(perm_out, rg.perm, (size_t)ng * 16 * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  *n_groups = ng;
+  return EGONN_OK;
+}
+
 // Number of row groups (16 output rows each) of a map: rows of the `group_sums` output of egonn_sparse_conv; the groups of
 // sample b are [first_group[b], first_group[b+1]) (HOST copy, B+1 entries).  [SYNC]
 API int egonn_map_groups(egonn_ctx* c, int map_kind, int level_out, int64_t* n_groups, int64_t* first_group, void* stream) {

@@ -244,9 +244,10 @@ __global__ __launch_bounds__(RG_THREADS) void rowgroup_build_kernel(RGArgs a) {
   // ---- sorted table, one 64-byte line per (group, offset): thread = one 16-byte piece (4 consecutive slots of one
   // offset), its four values gathered from the LDS table (rows are random, the column is fixed: stride-27 rows spread
   // over the banks), written as the group's contiguous K x 64-byte block
-  const int ngr = (rows + 15) >> 4;                     // groups with real rows
+  // (every group of the window, the trailing empty ones of a partial window too: their slots are padding and read -1 like the
+  // padding slots of the last real group — the arena is reused between plans, so an unwritten line would hold a stale table)
   const int ppg = K * 4;                                // pieces per group
-  for (int e = tid; e < ngr * ppg; e += RG_THREADS) {
+  for (int e = tid; e < GPW * ppg; e += RG_THREADS) {
     const int gl = e / ppg, pc = e - gl * ppg;
     const int k = pc >> 2, s0 = (pc & 3) * 4;
     int32_t v[4];

@@ -68,6 +68,10 @@ int egonn_debug_set_trace(void* device_buffer);
 /* measurement hook: device copies of a map's row-group tables (gmask [groups], snbr [groups][K][16], nullable).  [SYNC] */
 int egonn_debug_rowgroup_tables(egonn_ctx* ctx, int map_kind, int level_out, uint32_t* gmask_out, int32_t* snbr_out,
                                 int64_t capacity_groups, int64_t* n_groups, void* stream);
+/* test hook: device copy of the same map's perm table ([groups][16] int32: the output row of every slot, -1 = padding); with
+ * the two tables above it is the whole row-group form.  Never called by the product path.  [SYNC] */
+int egonn_debug_rowgroup_perm(egonn_ctx* ctx, int map_kind, int level_out, int32_t* perm_out, int64_t capacity_groups,
+                              int64_t* n_groups, void* stream);
 
 /* ------------------------------------------------------------------ coordinate plan
  * replaces ME.utils.sparse_quantize      datasets/quantization.py:42,83   (Cartesian/Polar quantizer __call__)

@@ -30,15 +30,16 @@ from __future__ import annotations
 
 import numpy as np
 
-_M = 1 << 16          # per-axis key radix
-_O = 1 << 15          # per-axis offset so that negative coordinates encode
+_M = 1 << 18          # per-axis key radix: every coordinate of coord_bits = 16 ([-2^15, 2^15)) and one kernel step beyond it at
+_O = 1 << 17          # level 7 (2 * 128 for k=5) encodes; 3 x 18 bits leave 9 bits of an int64 for the batch index
 
 
 def encode_rows(c4: np.ndarray) -> np.ndarray:
     """(N,4) int [b,x,y,z] -> int64 key, monotone in (b,x,y,z) lexicographic order."""
     c = np.asarray(c4, dtype=np.int64)
     assert c.ndim == 2 and c.shape[1] == 4
-    assert (np.abs(c[:, 1:]) < _O).all(), "coordinate out of oracle key range"
+    assert ((c[:, 1:] >= -_O) & (c[:, 1:] < _O)).all(), "coordinate out of oracle key range"
+    assert ((c[:, 0] >= 0) & (c[:, 0] < (1 << 9))).all(), "batch index out of oracle key range"
     return ((c[:, 0] * _M + (c[:, 1] + _O)) * _M + (c[:, 2] + _O)) * _M + (c[:, 3] + _O)
 
 
@@ -142,7 +143,7 @@ def kernel_map(in_c4: np.ndarray, out_c4: np.ndarray, k: int, in_stride: int):
         q = out_c4.copy()
         q[:, 1:] += off
         # guard the oracle key range (queries one step outside are simply misses)
-        ok = (np.abs(q[:, 1:]) < _O).all(axis=1)
+        ok = ((q[:, 1:] >= -_O) & (q[:, 1:] < _O)).all(axis=1)
         j = np.full(len(q), -1, dtype=np.int64)
         if ok.any():
             j[ok] = index.lookup(q[ok])

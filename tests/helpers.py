@@ -87,3 +87,255 @@ def sparse_conv_f64(levels, kind, level_out, x, w):
         if len(j):
             out[o] += x[j] @ w[k]        # every output row appears at most once per offset
     return out
+
+
+# --------------------------------------------------------------------------------------
+# Edge geometries for the plan tests (tests/test_oracle.py pins the oracle on them, tests/test_gpu_maps.py the HIP plan).
+# Plain seeded functions, no GPU.  A scan is an (n, 3) int64 array of distinct voxel coordinates.
+# --------------------------------------------------------------------------------------
+def _grid(n):
+    a = np.arange(n, dtype=np.int64)
+    return np.stack(np.meshgrid(a, a, a, indexing="ij"), axis=-1).reshape(-1, 3)
+
+
+def corner_clusters(cb):
+    """the eight 3x3x3 clusters in the corners of the coord_bits = cb range [-2^(cb-1), 2^(cb-1) - 1]^3: (216, 3)"""
+    lo, hi = -(1 << (cb - 1)), (1 << (cb - 1)) - 1
+    out = []
+    for s in range(8):
+        base = np.array([lo if (s >> a) & 1 == 0 else hi - 2 for a in range(3)], dtype=np.int64)
+        out.append(base + _grid(3))
+    return np.concatenate(out)
+
+
+def face_pairs(cb):
+    """(6, 3): per axis one voxel on the low face and one on the high face, the other two coordinates equal (0): were a key to
+    wrap at the range's edge, the two would be neighbours.  Rows 2a, 2a+1 are the pair of axis a."""
+    lo, hi = -(1 << (cb - 1)), (1 << (cb - 1)) - 1
+    out = np.zeros((6, 3), dtype=np.int64)
+    for a in range(3):
+        out[2 * a, a], out[2 * a + 1, a] = lo, hi
+    return out
+
+
+def corners(cb):
+    """corner_clusters(cb) followed by face_pairs(cb): (222, 3).  For cb >= 10 every face voxel is isolated from every other voxel
+    at every level 0..7 (the nearest other cell is 2^(cb-1) >= 512 away on some axis, a level-7 step is 128)."""
+    return np.concatenate([corner_clusters(cb), face_pairs(cb)])
+
+
+def solid_cube(n, origin=(-3, -7, -33)):
+    """all n^3 voxels of origin + [0, n)^3.  The default origin puts zero and a 4-, a 16- and a 64-block boundary inside the cube
+    for n >= 8 (x: -3..: crosses 0 and 4; y: -7..: crosses -4 and 0; z: -33..: crosses -32 = a 16 and 32 boundary; n >= 34
+    crosses 0 = a 64 boundary on z too)."""
+    return np.asarray(origin, dtype=np.int64) + _grid(n)
+
+
+def checkerboard(n, origin=(-16, -16, -16)):
+    """one voxel of every 2x2x2 cell of a cube of n cells per axis (period-2 checkerboard, origin + 2 * [0, n)^3): no two voxels are
+    k=3 neighbours at level 0 (only the centre offset is present), level 1 is a solid n-cube of cells."""
+    return np.asarray(origin, dtype=np.int64) + 2 * _grid(n)
+
+
+def axis_lines(n, origin=(-5, -5, -5)):
+    """seven scans: straight lines of n voxels from `origin` along x, y, z and the four space diagonals (+,+,+), (+,+,-), (+,-,+),
+    (+,-,-).  Every interior voxel of a line has exactly 3 k=3 entries at level 0 (itself and the two along the line)."""
+    o = np.asarray(origin, dtype=np.int64)
+    t = np.arange(n, dtype=np.int64)[:, None]
+    dirs = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1), (1, 1, -1), (1, -1, 1), (1, -1, -1)]
+    return [o + t * np.asarray(d, dtype=np.int64) for d in dirs]
+
+
+def pow2_pairs(cb):
+    """cb - 1 scans of two voxels each, scan k = voxels 2^k apart along axis k % 3, placed so that they are k=3 neighbours at level
+    k and at no other level (below: further than one step apart; above: one cell — the first sits on a multiple of 2^(k+1),
+    alternately at 0 and at -2^(k+1), so that the pairs sit on either side of zero).  Pairs with k >= 8 are never neighbours at
+    levels 0..7.  One pair per scan: a batch of many two-row scans."""
+    out = []
+    for k in range(cb - 1):
+        p = 0 if k % 2 == 0 else -(1 << (k + 1))
+        a = np.zeros((2, 3), dtype=np.int64)
+        a[0, k % 3], a[1, k % 3] = p, p + (1 << k)
+        out.append(a)
+    return out
+
+
+def row_count_scan(level, n_rows, seed=0):
+    """a scan with exactly n_rows distinct level-`level` cells: a seeded random subset of a cube of cells centred on zero (about
+    two thirds full, so that the masks vary), one or two voxels per cell."""
+    rng = np.random.default_rng(1000 * level + n_rows + 7919 * seed)
+    m = 1
+    while m ** 3 * 2 < n_rows * 3:
+        m += 1
+    cells = _grid(m)[np.sort(rng.choice(m ** 3, size=n_rows, replace=False))] - m // 2
+    s = 1 << level
+    vox = [cells * s + rng.integers(0, s, size=(n_rows, 3))]
+    if s > 1:
+        twice = rng.random(n_rows) < 0.5
+        vox.append(cells[twice] * s + (vox[0][twice] - cells[twice] * s + 1 + rng.integers(0, s - 1, size=(int(twice.sum()), 3))) % s)
+    v = np.unique(np.concatenate(vox), axis=0)
+    assert len(np.unique(np.floor_divide(v, s), axis=0)) == n_rows
+    return v
+
+
+def batch_of(scans):
+    """scans: list whose entries are an (n, 3) array, None (an empty scan) or an int (a duplicate of that earlier entry under this
+    batch index).  Returns ((N, 4) int32 [b, x, y, z] rows in scan order, batch_size)."""
+    rows = []
+    for b, s in enumerate(scans):
+        if isinstance(s, (int, np.integer)):
+            s = scans[int(s)]
+        if s is None or len(s) == 0:
+            continue
+        c = np.empty((len(s), 4), dtype=np.int32)
+        c[:, 0] = b
+        c[:, 1:] = s
+        rows.append(c)
+    return (np.concatenate(rows) if rows else np.zeros((0, 4), dtype=np.int32)), len(scans)
+
+
+# --------------------------------------------------------------------------------------
+# Kernel maps as sets of (output voxel, weight slot, input voxel), the row-group form of a map, and the comparisons between them.
+# --------------------------------------------------------------------------------------
+MAP_K = {0: 27, 1: 8, 2: 8}
+
+
+def map_levels(kind, level_out):
+    """(input level, output level) of map kind 0 (k=3 on level_out), 1 (k=2,s=2 into level_out), 2 (transposed onto level_out)"""
+    return (level_out, level_out - 1, level_out + 1)[kind], level_out
+
+
+def oracle_pairs(levels, kind, level_out):
+    """(P, 3) int64 rows (out row, slot k, in row) of the oracle's map, rows numbered as in `levels` (oracle.egonn_ref.SparseLevels)"""
+    if kind == 0:
+        maps = levels.kmap(level_out, level_out, 3)
+    elif kind == 1:
+        maps = levels.kmap(level_out - 1, level_out, 2)
+    else:
+        maps = [(o, j) for j, o in levels.kmap(level_out, level_out + 1, 2)]
+    out = [np.stack([o, np.full(len(o), k, dtype=np.int64), j], axis=1) for k, (j, o) in enumerate(maps)]
+    return np.concatenate(out).astype(np.int64) if out else np.zeros((0, 3), dtype=np.int64)
+
+
+def triples_by_coord(pairs, c_out, c_in):
+    """(out row, k, in row) -> (out key, k, in key), sorted: the row-order-free form of a map (a set, as a sorted array)"""
+    p = np.asarray(pairs, dtype=np.int64).reshape(-1, 3)
+    if len(p):
+        assert p[:, 0].min() >= 0 and p[:, 0].max() < len(c_out), "output row outside the level"
+        assert p[:, 2].min() >= 0 and p[:, 2].max() < len(c_in), "input row outside the level"
+    t = np.stack([rowkey(c_out)[p[:, 0]], p[:, 1], rowkey(c_in)[p[:, 2]]], axis=1) if len(p) else np.zeros((0, 3), dtype=np.int64)
+    t = t[np.lexsort((t[:, 2], t[:, 1], t[:, 0]))]
+    assert len(t) < 2 or (np.diff(t, axis=0) != 0).any(axis=1).all(), "a (output, slot, input) entry appears twice"
+    return t
+
+
+def decode_rowgroups(perm, snbr):
+    """perm [G, 16], snbr [G, K, 16] -> (P, 3) rows (out row, slot k, in row) of every entry >= 0 in a slot that holds a row"""
+    perm, snbr = np.asarray(perm, dtype=np.int64), np.asarray(snbr, dtype=np.int64)
+    g, k, s = np.nonzero((snbr >= 0) & (perm[:, None, :] >= 0))
+    return np.stack([perm[g, s], k, snbr[g, k, s]], axis=1)
+
+
+def check_rowgroup_form(perm, snbr, gmask, n_rows, first_group, batch_offsets):
+    """The invariants of the row-group form (csrc/rowgroup.hip) that do not need the reference map; AssertionError on a breach.
+    gmask bit order, read from rowgroup.hip: bit k (k < K) is kernel offset k itself — the OR of `(row[k] >= 0) << k` over the
+    group's rows; the sort key is remapped (remap27), the stored mask is not — and bit 31 says that the group holds a real row."""
+    perm, snbr = np.asarray(perm, dtype=np.int64), np.asarray(snbr, dtype=np.int64)
+    gmask = np.asarray(gmask).astype(np.int64) & 0xFFFFFFFF
+    G, K, _ = snbr.shape
+    assert perm.shape == (G, 16) and gmask.shape == (G,)
+    real = perm >= 0
+    assert perm.min(initial=0) >= -1 and perm.max(initial=-1) < n_rows, "perm names a row outside the level"
+    assert np.array_equal(np.sort(perm[real]), np.arange(n_rows)), "every output row must appear in perm exactly once"
+    assert (snbr[~np.broadcast_to(real[:, None, :], snbr.shape)] == -1).all(), "a padding slot has an snbr entry other than -1"
+    want = (real.any(axis=1).astype(np.int64) << 31)
+    for k in range(K):
+        want |= (snbr[:, k, :] >= 0).any(axis=1).astype(np.int64) << k
+    assert np.array_equal(gmask, want), "gmask differs from the OR of its group's slots"
+    B = len(batch_offsets) - 1
+    assert len(first_group) == B + 1 and first_group[0] == 0 and first_group[B] == G
+    for b in range(B):
+        lo, hi = batch_offsets[b], batch_offsets[b + 1]
+        rows = perm[first_group[b]:first_group[b + 1]]
+        rows = rows[rows >= 0]
+        assert first_group[b] <= first_group[b + 1]
+        assert ((rows >= lo) & (rows < hi)).all(), f"the groups of scan {b} hold rows of another scan"
+        assert len(rows) == hi - lo, f"scan {b}: {len(rows)} rows in its groups, {hi - lo} in the level"
+        if hi == lo:
+            assert first_group[b] == first_group[b + 1], f"the empty scan {b} owns groups"
+
+
+def encode_rowgroups(pairs, K, batch_offsets, win=64):
+    """Row-group form of a map given as (out row, k, in row) rows, built on the host the plain way (per scan: windows of `win`
+    rows, groups of 16 in row order, no mask sort): the synthetic CORRECT table set of the CPU tests.
+    Returns perm, snbr, gmask (uint32 values in int64), first_group."""
+    gpw = win // 16
+    first, perm = [0], []
+    for b in range(len(batch_offsets) - 1):
+        lo, hi = int(batch_offsets[b]), int(batch_offsets[b + 1])
+        for w0 in range(lo, hi, win):
+            p = np.full(win, -1, dtype=np.int64)
+            p[:min(win, hi - w0)] = np.arange(w0, min(w0 + win, hi))
+            perm.append(p.reshape(gpw, 16))
+        first.append(sum(len(p) for p in perm))
+    perm = np.concatenate(perm) if perm else np.zeros((0, 16), dtype=np.int64)
+    G = len(perm)
+    n_rows = int(batch_offsets[-1])
+    slot = np.full(n_rows, -1, dtype=np.int64)
+    g, s = np.nonzero(perm >= 0)
+    slot[perm[g, s]] = g * 16 + s
+    snbr = np.full((G, K, 16), -1, dtype=np.int64)
+    p = np.asarray(pairs, dtype=np.int64).reshape(-1, 3)
+    snbr[slot[p[:, 0]] // 16, p[:, 1], slot[p[:, 0]] % 16] = p[:, 2]
+    gmask = ((perm >= 0).any(axis=1).astype(np.int64) << 31)
+    for k in range(K):
+        gmask |= (snbr[:, k, :] >= 0).any(axis=1).astype(np.int64) << k
+    return perm, snbr, gmask, first
+
+
+def assert_same_map(got_triples, want_triples, what=""):
+    """set equality of two maps in the sorted (out key, k, in key) form"""
+    got, want = np.asarray(got_triples), np.asarray(want_triples)
+    assert got.shape == want.shape, f"{what}: {len(got)} map entries, the reference has {len(want)}"
+    assert np.array_equal(got, want), f"{what}: map entries differ from the reference"
+
+
+# the first layer: W[k, 0, k // 4] = 2^(k % 4) makes output channel c of a unit-feature k=5 convolution the presence bits of
+# offsets 4c .. 4c+3
+def k5_probe_kernel():
+    w = np.zeros((125, 1, 32), dtype=np.float32)
+    k = np.arange(125)
+    w[k, 0, k // 4] = 2.0 ** (k % 4)
+    return w
+
+
+def decode_k5_presence(out):
+    """(N, 32) output of the probe convolution on unit features -> (N, 125) bool presence of every 5x5x5 offset"""
+    out = np.asarray(out)
+    v = np.rint(out).astype(np.int64)
+    assert np.array_equal(v.astype(out.dtype), out) and v.min(initial=0) >= 0 and v.max(initial=0) <= 15, "not a 4-bit presence code"
+    k = np.arange(125)
+    return ((v[:, k // 4] >> (k % 4)) & 1).astype(bool)
+
+
+def oracle_k5_presence(maps, n_rows):
+    """kernel_map(c0, c0, 5, 1) -> (N, 125) bool, rows in the oracle's order"""
+    p = np.zeros((n_rows, 125), dtype=bool)
+    for k, (j, o) in enumerate(maps):
+        p[o, k] = True
+    return p
+
+
+def int_conv_reference(pairs, x, w, n_out):
+    """exact integer convolution out[o] = sum over (o, k, j) of x[j] @ w[k]: float64 arithmetic on integer data (every product
+    and partial sum an integer far below 2^53, so float64 is exact), returned as int64"""
+    x, w = np.asarray(x, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    out = np.zeros((n_out, w.shape[-1]), dtype=np.float64)
+    p = np.asarray(pairs, dtype=np.int64).reshape(-1, 3)
+    for k in range(w.shape[0]):
+        sel = p[p[:, 1] == k]
+        if len(sel):
+            np.add.at(out, sel[:, 0], x[sel[:, 2]] @ w[k])
+    r = np.rint(out).astype(np.int64)
+    assert np.array_equal(r.astype(np.float64), out)
+    return r

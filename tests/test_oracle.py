@@ -336,3 +336,241 @@ def test_c_oracle_under_sanitizers(tmp_path):
         tok = r.stdout.split()
         assert int(tok[1]) == len(kp) and [int(t) for t in tok[3:11]] == cnt.tolist(), (name, r.stdout)
         assert np.isclose(float(tok[12]), float(g.astype(np.float64).sum()), rtol=1e-4, atol=1e-4), (name, r.stdout)
+
+
+# ------------------------------------------------------------------ (4) the reference map on the edge geometries
+# tests/test_gpu_maps.py holds the HIP plan against oracle.me_ops.kernel_map on the geometries of tests/helpers.py; the counts
+# below are derivable by hand and pin the oracle itself there.  A solid block of m cells per axis has (3m - 2)^3 k=3 entries:
+# per axis, m centre pairs + (m - 1) pairs each way.
+def _levels(scan_list):
+    c4, _ = H.batch_of(scan_list)
+    return ref.SparseLevels(c4)
+
+
+def _n_pairs(lv, level):
+    return sum(len(j) for j, _ in lv.kmap(level, level, 3))
+
+
+def test_oracle_key_range_covers_coord_bits_16_and_one_step_beyond():
+    lo, hi = -(1 << 15), (1 << 15) - 1
+    c = np.array([[0, lo, lo, lo], [0, hi, hi, hi], [511, lo, hi, 0]], dtype=np.int64)
+    k = ops.encode_rows(c)
+    assert (np.diff(k) > 0).all() and k.dtype == np.int64
+    # one k=5 step of level 7 beyond either end still encodes, without meeting another voxel's key
+    far = np.array([[0, lo - 256, lo - 256, lo - 256], [0, hi + 256, hi + 256, hi + 256]], dtype=np.int64)
+    assert len(np.unique(np.concatenate([k, ops.encode_rows(far)]))) == 5
+    for c4 in (np.array([[0, 1 << 17, 0, 0]]), np.array([[0, 0, -(1 << 17) - 1, 0]]), np.array([[512, 0, 0, 0]])):
+        with pytest.raises(AssertionError):
+            ops.encode_rows(c4)
+
+
+@pytest.mark.parametrize("n", [1, 2, 5, 20])
+def test_solid_cube_pair_count(n):
+    lv = _levels([H.solid_cube(n)])
+    assert lv.n(0) == n ** 3
+    assert _n_pairs(lv, 0) == (3 * n - 2) ** 3
+    if n == 20:
+        assert _n_pairs(lv, 0) == 195112
+        # interior rows carry all 27 offsets
+        per_row = np.zeros(lv.n(0), dtype=np.int64)
+        for _, o in lv.kmap(0, 0, 3):
+            per_row[o] += 1
+        assert (per_row == 27).sum() == 18 ** 3
+    # an origin on the block boundaries gives the same count: the map does not see alignment
+    assert _n_pairs(_levels([H.solid_cube(n, origin=(-64, 0, 60))]), 0) == (3 * n - 2) ** 3
+
+
+def test_checkerboard_pair_counts():
+    lv = _levels([H.checkerboard(16)])
+    assert lv.n(0) == 4096 and lv.n(1) == 4096
+    assert _n_pairs(lv, 0) == 4096                      # the centre offset only
+    assert all(len(j) == (4096 if k == 13 else 0) for k, (j, _) in enumerate(lv.kmap(0, 0, 3)))
+    assert _n_pairs(lv, 1) == 46 ** 3 == 97336          # a solid 16-cube of level-1 cells
+    assert _n_pairs(lv, 2) == (3 * 8 - 2) ** 3          # ... of 8 level-2 cells per axis (origin -16 is a multiple of 4)
+
+
+@pytest.mark.parametrize("cb", [10, 11, 12, 13, 14, 15, 16])
+def test_corner_clusters_pair_counts_and_no_wrap(cb):
+    """The eight corner clusters: 8 x 343 = 2 744 entries at level 0, 8 x 64 = 512 at level 1 (two cells per axis), 8 from level 2
+    on (one cell per corner); each of the six isolated face voxels of corners(cb) adds its centre entry and nothing else; no entry
+    at any level links a cell on a low face with a cell on the high face of the same axis."""
+    lo, hi = -(1 << (cb - 1)), (1 << (cb - 1)) - 1
+    cl = _levels([H.corner_clusters(cb)])
+    lv = _levels([H.corners(cb)])
+    assert lv.n(0) == 222 and lv.coords[0][:, 1:].min() == lo and lv.coords[0][:, 1:].max() == hi
+    for level in range(8):
+        want = 2744 if level == 0 else (512 if level == 1 else 8)
+        assert _n_pairs(cl, level) == want, (cb, level)
+        assert _n_pairs(lv, level) == want + 6, (cb, level)
+        c = lv.coords[level].astype(np.int64)
+        far = 0
+        for j, o in lv.kmap(level, level, 3):
+            far = max(far, int(np.abs(c[j, 1:] - c[o, 1:]).max(initial=0)))
+        assert far <= (1 << level), (cb, level, far)            # an entry never spans more than one step: nothing wraps
+        for kind in (1, 2):
+            if level + (kind == 2) > 7 or level - (kind == 1) < 0:
+                continue
+            lin, _ = H.map_levels(kind, level)
+            p = H.oracle_pairs(lv, kind, level)
+            d = np.abs(lv.coords[lin].astype(np.int64)[p[:, 2], 1:] - c[p[:, 0], 1:])
+            assert d.max() < (1 << max(lin, level)), (cb, level, kind)
+    # the face voxels of one axis are never each other's neighbour
+    fp = H.face_pairs(cb)
+    assert all(np.abs(fp[2 * a] - fp[2 * a + 1]).max() == hi - lo for a in range(3))
+
+
+def test_axis_lines_and_pow2_pairs_known_answers():
+    lines = H.axis_lines(9)
+    lv = _levels(lines)
+    assert lv.batch_size == 7 and lv.n(0) == 63
+    assert _n_pairs(lv, 0) == 7 * (9 + 2 * 8)           # per line: 9 centres + 8 pairs each way; scans never pair up
+    offs = ops.kernel_offsets(3, 1)
+    dirs = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1), (1, 1, -1), (1, -1, 1), (1, -1, -1)]
+    for k, (j, o) in enumerate(lv.kmap(0, 0, 3)):
+        b = lv.coords[0][o, 0]
+        assert np.array_equal(b, lv.coords[0][j, 0])
+        for bb in np.unique(b):
+            assert tuple(offs[k]) in ((0, 0, 0), dirs[bb], tuple(-np.array(dirs[bb])))
+    for cb in (10, 12, 16):
+        pairs = H.pow2_pairs(cb)
+        lv = _levels(pairs)
+        assert lv.batch_size == cb - 1 and lv.n(0) == 2 * (cb - 1)
+        for level in range(8):
+            c = lv.coords[level]
+            for k in range(cb - 1):
+                n_cells = int((c[:, 0] == k).sum())
+                linked = sum(int(((c[o, 0] == k) & (j != o)).sum()) for j, o in lv.kmap(level, level, 3))
+                assert n_cells == (1 if level > k else 2), (cb, level, k)
+                assert linked == (2 if level == k else 0), (cb, level, k)      # neighbours at level k only
+
+
+@pytest.mark.parametrize("level,n_rows", [(0, 1), (1, 17), (1, 513), (4, 1025), (7, 16)])
+def test_row_count_scan_has_the_rows_it_promises(level, n_rows):
+    v = H.row_count_scan(level, n_rows)
+    c4, B = H.batch_of([None, v, None, 1])
+    assert B == 4 and sorted(np.unique(c4[:, 0]).tolist()) == [1, 3]
+    lv = ref.SparseLevels(c4)
+    assert lv.n(level) == 2 * n_rows
+    assert np.array_equal(lv.coords[0][c4[:, 0] == 1][:, 1:], lv.coords[0][c4[:, 0] == 3][:, 1:])
+    for j, o in lv.kmap(level, level, 3):                # duplicates of a scan under another batch index never pair up
+        assert np.array_equal(lv.coords[level][j, 0], lv.coords[level][o, 0])
+
+
+# ------------------------------------------------------------------ (5) the comparisons of tests/test_gpu_maps.py can fail
+def _synthetic_tables(kind=0, level=1):
+    """a correct row-group table set, built on the host from the oracle's own map of a two-scan geometry with opposite faces"""
+    cb = 10
+    c4, B = H.batch_of([H.corners(cb), None, H.solid_cube(5)])
+    lv = ref.SparseLevels(c4)
+    lin, lout = H.map_levels(kind, level)
+    c_out, c_in = lv.coords[lout], lv.coords[lin]
+    boff = [int((c_out[:, 0] < b).sum()) for b in range(B + 1)]
+    assert (np.diff(c_out[:, 0]) >= 0).all()                    # rows are batch-contiguous, as the row-group form needs
+    pairs = H.oracle_pairs(lv, kind, level)
+    perm, snbr, gmask, first = H.encode_rowgroups(pairs, H.MAP_K[kind], boff)
+    return lv, c_out, c_in, boff, pairs, perm, snbr, gmask, first
+
+
+def _compare(lv, c_out, c_in, boff, pairs, perm, snbr, gmask, first):
+    H.check_rowgroup_form(perm, snbr, gmask, len(c_out), first, boff)
+    H.assert_same_map(H.triples_by_coord(H.decode_rowgroups(perm, snbr), c_out, c_in), H.triples_by_coord(pairs, c_out, c_in), "synthetic")
+
+
+@pytest.mark.parametrize("kind,level", [(0, 0), (0, 1), (1, 1), (2, 0), (0, 3)])
+def test_table_comparison_accepts_a_correct_table_set(kind, level):
+    t = _synthetic_tables(kind, level)
+    assert t[7].shape[0] > 0 and (t[5] == -1).any() and t[8][1] == t[8][2]      # padding slots exist; the empty scan owns no group
+    _compare(*t)
+
+
+def test_table_comparison_rejects_a_neighbour_moved_to_the_opposite_face():
+    lv, c_out, c_in, boff, pairs, perm, snbr, gmask, first = _synthetic_tables(0, 0)
+    lo, hi = -512, 511
+    row = {tuple(c): i for i, c in enumerate(c_out.tolist())}
+    a, b, wrapped = row[(0, hi, hi, hi)], row[(0, hi - 1, hi, hi)], row[(0, lo, hi, hi)]
+    g, s = np.argwhere(perm == b)[0]
+    assert snbr[g, 14, s] == a                                   # slot 14 = (+1, 0, 0)
+    g2, s2 = np.argwhere(perm == a)[0]
+    assert snbr[g2, 14, s2] == -1                                # the corner voxel has no +x neighbour ...
+    bad = snbr.copy()
+    bad[g2, 14, s2] = wrapped                                    # ... a wrapped key would find the opposite face
+    gm = gmask.copy()
+    gm[g2] |= 1 << 14
+    with pytest.raises(AssertionError, match="map entries"):
+        _compare(lv, c_out, c_in, boff, pairs, perm, bad, gm, first)
+    bad = snbr.copy()
+    bad[g, 14, s] = wrapped                                      # an existing entry moved to the opposite-face row
+    with pytest.raises(AssertionError, match="map entries differ"):
+        _compare(lv, c_out, c_in, boff, pairs, perm, bad, gmask, first)
+
+
+def test_table_comparison_rejects_a_cleared_gmask_bit_and_a_missing_row():
+    lv, c_out, c_in, boff, pairs, perm, snbr, gmask, first = _synthetic_tables(0, 1)
+    g = int(np.argmax(gmask & (1 << 13) != 0))
+    for bit in (13, 31):
+        gm = gmask.copy()
+        gm[g] &= ~(1 << bit)
+        with pytest.raises(AssertionError, match="gmask"):
+            _compare(lv, c_out, c_in, boff, pairs, perm, snbr, gm, first)
+    gm = gmask.copy()
+    g_abs, k_abs = [(gi, k) for gi in range(len(gmask)) for k in range(27) if gmask[gi] >> 31 and not (gmask[gi] >> k) & 1][0]
+    gm[g_abs] |= 1 << k_abs                                     # a bit set for an offset that no slot of the group has
+    with pytest.raises(AssertionError, match="gmask"):
+        _compare(lv, c_out, c_in, boff, pairs, perm, snbr, gm, first)
+    # one output row missing from perm (its slot turned into padding), with and without its snbr column
+    gg, ss = np.argwhere(perm >= 0)[3]
+    pm = perm.copy()
+    pm[gg, ss] = -1
+    with pytest.raises(AssertionError, match="exactly once"):
+        _compare(lv, c_out, c_in, boff, pairs, pm, snbr, gmask, first)
+    sn = snbr.copy()
+    sn[gg, :, ss] = -1
+    with pytest.raises(AssertionError, match="exactly once"):
+        _compare(lv, c_out, c_in, boff, pairs, pm, sn, gmask, first)
+    # a row listed twice, a padding slot with an entry, a group of the wrong scan
+    pm = perm.copy()
+    pm[gg, ss] = perm[np.argwhere(perm >= 0)[4][0], np.argwhere(perm >= 0)[4][1]]
+    with pytest.raises(AssertionError, match="exactly once"):
+        _compare(lv, c_out, c_in, boff, pairs, pm, snbr, gmask, first)
+    gp, sp = np.argwhere(perm < 0)[0]
+    sn = snbr.copy()
+    sn[gp, 13, sp] = 0
+    with pytest.raises(AssertionError, match="padding slot"):
+        _compare(lv, c_out, c_in, boff, pairs, perm, sn, gmask, first)
+    f = list(first)
+    f[1] = f[2] = int(np.nonzero((perm[:first[1]] >= 0).any(axis=1))[0][-1])      # scan 0's last real group handed to scan 2
+    with pytest.raises(AssertionError, match="scan"):
+        _compare(lv, c_out, c_in, boff, pairs, perm, snbr, gmask, f)
+
+
+def test_k5_decode_rejects_a_flipped_presence_bit():
+    c4, _ = H.batch_of([H.corners(10), H.solid_cube(6)])
+    lv = ref.SparseLevels(c4)
+    want = H.oracle_k5_presence(lv.kmap(0, 0, 5), lv.n(0))
+    assert want[:, 62].all() and want.sum() == sum(len(j) for j, _ in lv.kmap(0, 0, 5))
+    w = H.k5_probe_kernel()
+    out = ops.conv_forward(np.ones((lv.n(0), 1), dtype=np.float32), w, lv.kmap(0, 0, 5), lv.n(0))
+    assert np.array_equal(H.decode_k5_presence(out), want)
+    for k in (0, 62, 124):
+        bad = out.copy()
+        bit = np.float32(2.0 ** (k % 4))
+        bad[5, k // 4] += -bit if want[5, k] else bit
+        assert not np.array_equal(H.decode_k5_presence(bad), want)
+    bad = out.copy()
+    bad[0, 0] += 0.5
+    with pytest.raises(AssertionError, match="presence code"):
+        H.decode_k5_presence(bad)
+
+
+def test_integer_conv_reference_matches_the_oracle_convolution():
+    c4, _ = H.batch_of([H.solid_cube(4), H.checkerboard(3)])
+    lv = ref.SparseLevels(c4)
+    rng = np.random.default_rng(3)
+    for kind, level in [(0, 0), (0, 1), (1, 1), (2, 0)]:
+        lin, lout = H.map_levels(kind, level)
+        K = H.MAP_K[kind]
+        x = rng.integers(-8, 9, size=(lv.n(lin), 5))
+        w = rng.integers(-8, 9, size=(K, 5, 3))
+        got = H.int_conv_reference(H.oracle_pairs(lv, kind, level), x, w, lv.n(lout))
+        want = H.sparse_conv_f64(lv, kind, level, x, w)
+        assert np.array_equal(got, want.astype(np.int64)) and np.array_equal(want, np.rint(want))
