@@ -339,3 +339,219 @@ def int_conv_reference(pairs, x, w, n_out):
     r = np.rint(out).astype(np.int64)
     assert np.array_equal(r.astype(np.float64), out)
     return r
+
+
+# --------------------------------------------------------------------------------------
+# Edge batches and the stage comparison of tests/test_forward_f64_host.py / tests/test_gpu_forward_stages.py
+# --------------------------------------------------------------------------------------
+_REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+POLAR_STEP = [1.0, 0.3, 0.2]            # the polar fixture's steps (tests/golden/make_golden.py): 360 azimuth bins
+EDGE_WEIGHT_SEED = 23
+
+
+def kernel_constant(name):
+    """the value of `constexpr int <name> = N;` in egonn_amd/csrc (LH_WAVES, SEG_CHUNKS): the tiles the edge batches straddle"""
+    import re
+    for f in ("dense.hip", "kernels.h"):
+        with open(os.path.join(_REPO, "egonn_amd", "csrc", f)) as fh:
+            m = re.search(r"constexpr\s+int\s+" + name + r"\s*=\s*(\d+)\s*;", fh.read())
+        if m:
+            return int(m.group(1))
+    raise KeyError(name)
+
+
+def head_tile_counts():
+    """level-3 row counts on each side of a wave's 16 rows, of 64 rows and of a workgroup's 16 * LH_WAVES rows"""
+    wg = 16 * kernel_constant("LH_WAVES")
+    return sorted({1, 15, 16, 17, 63, 64, 65, wg - 1, wg, wg + 1})
+
+
+def pool_chunk_counts():
+    """level-5 row counts: fewer rows than SEG_CHUNKS chunks (chunks with zero rows and with one row), one on each side of it,
+    and one more than a 256-row window"""
+    ch = kernel_constant("SEG_CHUNKS")
+    return [1, ch - 1, ch, ch + 1, 257]
+
+
+def lidar_voxels(seed, n_points, step=0.1):
+    from egonn_amd.synth import lidar_scan
+    return np.unique(np.floor(lidar_scan(seed, n_points) / np.float32(step)).astype(np.int64), axis=0)
+
+
+def _many_tiny_scans():
+    """64 scans of 1-5 voxels with empty scans inside (the geometry of tests/test_gpu_maps.py:_many_scans)"""
+    rng = np.random.default_rng(64)
+    return [None if b in (0, 13, 14, 40, 63) else row_count_scan(0, 1 + b % 5, seed=b) + rng.integers(-200, 200, size=3)
+            for b in range(64)]
+
+
+def _seam_scan():
+    """polar voxels (azimuth bin, ring, z) in the first and the last azimuth bins of POLAR_STEP: next to the +-180 degree seam"""
+    nb = int(360.0 // POLAR_STEP[0])
+    return np.array([(t, r, z) for t in (0, 1, nb - 2, nb - 1) for r in (3, 40, 200) for z in (-5, 0)], dtype=np.int64)
+
+
+# name -> (coord_bits, coordinates, scans)
+EDGE_BATCHES = {
+    "ragged": (12, "cartesian", lambda: [np.array([[3, -2, 5]]), np.array([[-900, 0, 0], [900, 0, 0]]), lidar_voxels(9, 40), None,
+                                         lidar_voxels(8, 3000), None]),
+    "head_tiles": (12, "cartesian", lambda: [row_count_scan(3, n) for n in head_tile_counts()]),
+    "pool_chunks": (12, "cartesian", lambda: [row_count_scan(5, n) for n in pool_chunk_counts()]),
+    "many_scans": (10, "cartesian", _many_tiny_scans),
+    "corners_cb10_cart": (10, "cartesian", lambda: [corners(10)]),
+    "corners_cb16_cart": (16, "cartesian", lambda: [corners(16)]),
+    "corners_cb10_polar": (10, "polar", lambda: [corners(10), _seam_scan()]),
+    "corners_cb16_polar": (16, "polar", lambda: [corners(16), _seam_scan()]),
+    "lidar10k": (12, "cartesian", lambda: [lidar_voxels(77, 10000)]),
+}
+RANGE_CORNER_BATCHES = [n for n in EDGE_BATCHES if n.startswith("corners")]
+_EDGE_CACHE = {}
+
+
+class EdgeBatch:
+    """an edge batch: c4 (N, 4) int32, B scans, coord_bits, the quantizer (mode, step), the oracle's pyramid lv (batch_size = B,
+    trailing empty scans included) and seeded non-constant level-0 features"""
+
+    def __init__(self, name):
+        from oracle import egonn_ref as ref
+        self.name = name
+        self.cb, coordinates, make = EDGE_BATCHES[name]
+        self.c4, self.B = batch_of(make())
+        lo, hi = -(1 << (self.cb - 1)), (1 << (self.cb - 1)) - 1
+        assert self.c4[:, 1:].min() >= lo and self.c4[:, 1:].max() <= hi and len(self.c4) <= 9100, name        # "about 8 500": the 10 k-point scan has 9 015 voxels
+        self.coordinates = coordinates
+        self.mode = 0 if coordinates == "cartesian" else 1
+        self.step = [0.1] if self.mode == 0 else list(POLAR_STEP)
+        self.lv = ref.SparseLevels(self.c4)
+        self.lv.batch_size = self.B
+        self.scan = {l: self.lv.coords[l][:, 0].astype(np.int64) for l in range(8)}
+
+    def features(self):
+        """non-constant level-0 features in (0.5, 1.5), one per row of lv.coords[0], a function of the coordinate"""
+        k = rowkey(self.lv.coords[0]).astype(np.uint64)
+        h = (k * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(40)
+        return (0.5 + h.astype(np.float64) / float(1 << 24)).astype(np.float32).reshape(-1, 1)
+
+
+def edge_batch(name):
+    if name not in _EDGE_CACHE:
+        _EDGE_CACHE[name] = EdgeBatch(name)
+    return _EDGE_CACHE[name]
+
+
+def edge_weights():
+    return seeded_weights(EDGE_WEIGHT_SEED)
+
+
+# ---- the comparison: e = max |got - want| / max |want|, over a stage's output and per scan of the batch
+FP32_FLOOR = 16 * 2.0 ** -24           # floor of a bound whose e_ref happens to be tiny
+SPLIT_CONV = 3e-6                      # README / include/egonn_hip.h / test_split_conv_matches_exact_fp32: one split-pipe convolution
+SPLIT_HEADS = 3e-6                     # test_local_heads_input_beyond_fp16_range_is_reported: the split heads against exact
+SPARSE_CONVS = {"conv0": 0, "block": 3, "local": 1, "global": 2}       # sparse convolutions per stage (conv0 is exact: bf16 x 3)
+BF16_ROUNDINGS = {"conv0": 1, "block": 4, "local": 2, "global": 4}     # bf16 stores between a stage's observed input and output
+
+
+def stage_kind(stage):
+    return "block" if stage.startswith("block") else stage.split(".")[0]
+
+
+def rel_err(got, want):
+    """max |got - want| / max |want| in float64; 0 for two all-zero arrays, inf for a non-zero got against an all-zero want"""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    if got.size == 0:
+        return 0.0
+    d, m = float(np.abs(got - want).max()), float(np.abs(want).max())
+    if not np.isfinite(d):
+        return float("inf")
+    return d / m if m > 0 else (0.0 if d == 0 else float("inf"))
+
+
+def scan_errs(got, want, scan, B):
+    """rel_err per scan (rows with scan[row] == b): each scan held to its own scale; None for a scan without rows"""
+    return [rel_err(got[scan == b], want[scan == b]) if (scan == b).any() else None for b in range(B)]
+
+
+def stage_bound(stage, config, e_ref):
+    """config 'exact': 8 x e_ref (another summation order, not another algorithm), floor 16 x 2^-24; 'product': plus 3e-6 per split
+    sparse convolution of the stage and 3e-6 for the split heads; 'bf16': roundings x 2^-8 (a derived count)"""
+    kind = stage_kind(stage)
+    if config == "bf16":
+        return BF16_ROUNDINGS[kind] * 2.0 ** -8
+    b = max(8.0 * e_ref, FP32_FLOOR)
+    if config == "product":
+        b += SPLIT_CONV * SPARSE_CONVS[kind] + (SPLIT_HEADS if kind == "local" else 0.0)
+    return b
+
+
+def worst_entry(got, want, rows=None):
+    """(row, channel, got, want) of the largest |got - want| (row an index into `rows` if given)"""
+    d = np.abs(np.asarray(got, dtype=np.float64) - np.asarray(want, dtype=np.float64))
+    d = d.reshape(len(d), -1)
+    r, c = np.unravel_index(int(np.argmax(d)), d.shape)
+    g, w = np.asarray(got).reshape(len(d), -1)[r, c], np.asarray(want).reshape(len(d), -1)[r, c]
+    return (int(rows[r]) if rows is not None else int(r)), int(c), float(g), float(w)
+
+
+def check_stage(table, batch, config, stage, got, want, ref32, scan, B, gate=None, exact_zero=(), min_share=1.0):
+    """One stage of one forward against float64.  got: the GPU's output (None on the host: only e_ref is recorded), want: the float64
+    stage on the same input, ref32: the fp32 oracle's stage on that input (None for bf16).  The whole output and every scan (in its
+    own scale; bound from the larger of the batch's and the scan's own e_ref: a scan of a few rows samples the stage's rounding
+    poorly) must stay inside stage_bound; the scans listed in exact_zero have an all-zero float64 output and must be exactly zero.
+    min_share < 1 (bf16 keypoints / sigma only, the rule of test_local_heads_range_bf16_maps): instead, that share of the rows lies
+    within bound x max |want|.  Appends (batch, config, stage, e_ref, e_gpu, bound) to `table`; returns the failure messages."""
+    want = np.asarray(want, dtype=np.float64)
+    e_ref = rel_err(ref32, want) if ref32 is not None else 0.0
+    bound = stage_bound(stage, config, e_ref)
+    if got is None:
+        table.append((batch, config, stage, e_ref, None, bound))
+        return []
+    got = np.asarray(got, dtype=np.float64)
+    fails = []
+    if not np.isfinite(got).all():
+        fails.append(f"{batch}/{config}/{stage}: NaN or Inf in the output")
+    e_gpu = rel_err(got, want)
+    table.append((batch, config, stage, e_ref, e_gpu, bound))
+
+    def describe(rows_mask, b):
+        rows = np.nonzero(rows_mask)[0]
+        r, c, g, w = worst_entry(got[rows_mask], want[rows_mask], rows)
+        s = f"worst row {r} channel {c}: got {g!r}, float64 {w!r}"
+        if gate is not None and b is not None and c < gate.shape[1]:
+            s += f", float64 gate[{b}][{c}] = {gate[b, c]:.6f}"
+        return s
+
+    if min_share < 1.0:
+        ok = np.abs(got - want).reshape(len(got), -1).max(axis=1) <= bound * np.abs(want).max()
+        if ok.mean() < min_share:
+            fails.append(f"{batch}/{config}/{stage}: {ok.mean():.4f} of the rows within {bound:.3e} x max|want|, {min_share} required")
+        return fails
+    if not e_gpu <= bound:
+        r, c, _, _ = worst_entry(got, want)
+        fails.append(f"{batch}/{config}/{stage}: e_gpu {e_gpu:.3e} > bound {bound:.3e} (e_ref {e_ref:.3e}); "
+                     + describe(np.ones(len(got), dtype=bool), int(scan[r]) if len(scan) == len(got) else None))
+    if len(scan) == len(got):
+        eg = scan_errs(got, want, scan, B)
+        er = scan_errs(ref32, want, scan, B) if ref32 is not None else [0.0] * B
+        for b in range(B):
+            if eg[b] is None:
+                continue
+            m = scan == b
+            if b in exact_zero:
+                assert not want[m].any()
+                if got[m].any():
+                    fails.append(f"{batch}/{config}/{stage} scan {b}: float64 output is all zero, the GPU's is not; " + describe(m, b))
+                continue
+            bb = stage_bound(stage, config, max(e_ref, er[b]))
+            if not eg[b] <= bb:
+                fails.append(f"{batch}/{config}/{stage} scan {b} ({int(m.sum())} rows): e_gpu {eg[b]:.3e} > bound {bb:.3e} "
+                             f"(e_ref of the scan {er[b]:.3e}, of the batch {e_ref:.3e}); " + describe(m, b))
+    return fails
+
+
+def format_table(table):
+    """stage x configuration x batch: e_ref, e_gpu, bound — one line per entry"""
+    out = [f"{'batch':<20}{'config':<10}{'stage':<14}{'e_ref':>11}{'e_gpu':>11}{'bound':>11}"]
+    for batch, config, stage, e_ref, e_gpu, bound in table:
+        g = "-" if e_gpu is None else f"{e_gpu:.2e}"
+        out.append(f"{batch:<20}{config:<10}{stage:<14}{e_ref:>11.2e}{g:>11}{bound:>11.2e}")
+    return "\n".join(out)
