@@ -96,6 +96,12 @@ _SIGS = [
                                       C.c_int64, _P]),
     ("egonn_knn", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P]),
     ("egonn_recall_counts", C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
+    ("egonn_registration_scratch_bytes", C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    ("egonn_match_mutual", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ("egonn_ransac_pairs", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, _P,
+                                     C.c_int64, _P, _P, _P]),
+    ("egonn_registration_finish", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, _P,
+                                            C.c_int64, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("egonn_profile_enable", C.c_int, [_P, C.c_int, C.c_char_p]),
     ("egonn_profile_fetch", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),

@@ -1,0 +1,603 @@
+// 6-DoF registration of two keypoint sets on the device: the consumer of the LOCAL half of the descriptor path
+// (reference eval/evaluate.py: get_ransac_result :381-399, ransac_fn :296-306, calculate_repeatability :402-411 and the
+// RRE / RTE / success bookkeeping :239-259).  The reference hands the step to Open3D's
+// registration_ransac_based_on_feature_matching (mutual_filter, max distance 0.5, point-to-point without scale,
+// ransac_n = 3, checkers EdgeLength(0.8) + Distance(0.5), criteria (10000, 0.999)).  Open3D is not part of the reference
+// tree, so what follows restates its documented behaviour [recall], batched over P independent (query, candidate) pairs:
+//
+//   1. reg_match_kernel   d2[i][j] = sum_k (a_ik - b_jk)^2 in fp64 over exactly converted fp32 descriptors, k ascending, one
+//                         fma per term; j(i) = row argmin, i(j) = column argmin, ties: lowest index; keep (i, j(i)) with
+//                         i(j(i)) == i; fewer than 3 such pairs: keep every (i, j(i)).  Compacted in ascending i.
+//   2. reg_ransac_kernel  hypothesis t = 0 .. H-1, one lane each (see reg_hypothesis below); per workgroup the best
+//                         (inliers, err2, t) goes to scratch.
+//   3. reg_finish_kernel  best over the workgroups' records, the winner's transform again (same code, same bits), the
+//                         final evaluation over ALL source keypoints, and the metrics against a caller's T_gt.
+//
+// Two deliberate differences from Open3D: (a) Open3D stops early by its 0.999 confidence rule, here every one of the H
+// hypotheses is evaluated (a superset of what Open3D tries); (b) Open3D draws from a thread-dependent generator, here a
+// draw is a pure function of (seed, pair id, t, slot), so the result is reproducible bit for bit and does not depend on the
+// batch a pair sits in nor on how the hypotheses are spread over workgroups.
+//
+// The draw (reg_draw): with 64-bit wrapping arithmetic
+//       ctr = (pair_id << 34) | (t << 2) | slot                     pair_id < 2^30, t < 2^31, slot in {0, 1, 2}
+//       z   = seed + 0x9E3779B97F4A7C15 * (ctr + 1)                 (the state of splitmix64(seed) after ctr + 1 steps)
+//       z   = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+//       z   = (z ^ (z >> 27)) * 0x94D049BB133111EB
+//       z   =  z ^ (z >> 31)
+//       draw = ((z >> 32) * n_corr) >> 32                           (multiply-high of the upper word, in [0, n_corr))
+//
+// Best rule: most inliers (= highest fitness, n_corr is common), then smallest sum of squared inlier distances err2
+// (= lowest rmse at equal inliers; compared before the square root, which is the finer order), then lowest t.  It is a
+// total order, so the two-stage reduction gives the same winner under every chunking; there are no float atomics.
+//
+// All geometry is fp64 with contraction off: every operation below is the IEEE operation that is written, so the
+// transform the finish kernel recomputes is the one the hot loop scored.
+#include "../../include/egonn_hip.h"
+#include "common.h"
+
+#pragma clang fp contract(off)
+
+#define API extern "C" __attribute__((visibility("default")))
+
+namespace egonn {
+
+static constexpr int REG_MAX_N = 256;    // keypoints per side (the reference evaluates n_k = 128 and 256)
+static constexpr int REG_MAX_D = 256;    // descriptor width
+static constexpr int REG_TJ = 32;        // rows of the other side per LDS tile of the matching kernel
+static constexpr int REG_WG = 256;       // lanes = hypotheses per workgroup of the hot loop
+static constexpr double REG_EDGE2 = 0.8 * 0.8;   // CorrespondenceCheckerBasedOnEdgeLength(0.8), on squared lengths
+static constexpr double REG_DEGEN2 = 1e-6;       // |e1 x e2|^2 <= 1e-6 |e1|^2 |e2|^2  <=>  |e1 x e2| <= 1e-3 |e1| |e2|
+
+struct RegPartial {   // one workgroup's best hypothesis
+  int32_t cnt;        // inliers, -1 = none accepted in the chunk
+  int32_t t;
+  double err2;
+};
+
+__host__ __device__ static inline uint32_t reg_draw(uint64_t seed, uint32_t pair_id, uint32_t t, uint32_t slot, uint32_t n) {
+  const uint64_t ctr = ((uint64_t)pair_id << 34) | ((uint64_t)t << 2) | (uint64_t)slot;
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (ctr + 1ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z = z ^ (z >> 31);
+  return (uint32_t)(((z >> 32) * (uint64_t)n) >> 32);
+}
+
+__device__ static inline bool reg_better(int c1, double e1, int t1, int c2, double e2, int t2) {
+  return c1 > c2 || (c1 == c2 && (e1 < e2 || (e1 == e2 && t1 < t2)));
+}
+
+__device__ static inline int reg_clip(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// ------------------------------------------------------------------ 1. mutual nearest-neighbour matching
+// argmin over the rows of `other` of the fp64 squared distance to this thread's row of `own`.  The tile of `other` sits in
+// LDS and every lane reads the same address (broadcast); the own row comes from global memory as float4 (L1 / L2 resident).
+// Both directions run this same code, and (a - b)^2 == (b - a)^2 exactly, so d2[i][j] has the same bits in both passes.
+__device__ static int reg_argmin_pass(const float* __restrict__ own, int n_own, const float* __restrict__ other, int n_other,
+                                      int D, float4* s_tile) {
+  const int t = threadIdx.x, d4 = D >> 2;
+  const float4* own4 = reinterpret_cast<const float4*>(own) + (size_t)t * d4;
+  const float4* other4 = reinterpret_cast<const float4*>(other);
+  double best = INFINITY;
+  int bi = 0;
+  for (int j0 = 0; j0 < n_other; j0 += REG_TJ) {
+    const int nrow = min(REG_TJ, n_other - j0);
+    __syncthreads();
+    for (int e = t; e < nrow * d4; e += REG_WG) s_tile[e] = other4[(size_t)j0 * d4 + e];
+    __syncthreads();
+    if (t < n_own) {
+      double acc[REG_TJ];
+#pragma unroll
+      for (int j = 0; j < REG_TJ; ++j) acc[j] = 0.0;
+      for (int k = 0; k < d4; ++k) {
+        const float4 a = own4[k];
+        const double ax = (double)a.x, ay = (double)a.y, az = (double)a.z, aw = (double)a.w;
+#pragma unroll
+        for (int j = 0; j < REG_TJ; ++j) {
+          const float4 b = s_tile[j * d4 + k];   // rows >= nrow hold stale data: computed, never compared
+          double d = ax - (double)b.x;
+          acc[j] = fma(d, d, acc[j]);
+          d = ay - (double)b.y;
+          acc[j] = fma(d, d, acc[j]);
+          d = az - (double)b.z;
+          acc[j] = fma(d, d, acc[j]);
+          d = aw - (double)b.w;
+          acc[j] = fma(d, d, acc[j]);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < REG_TJ; ++j)
+        if (j < nrow && acc[j] < best) {
+          best = acc[j];
+          bi = j0 + j;
+        }
+    }
+  }
+  return bi;
+}
+
+__global__ __launch_bounds__(REG_WG) void reg_match_kernel(const float* __restrict__ feat1, const float* __restrict__ feat2,
+                                                           const int32_t* __restrict__ n1, const int32_t* __restrict__ n2,
+                                                           int n_max, int D, int32_t* __restrict__ corr,
+                                                           int32_t* __restrict__ n_corr) {
+  __shared__ float4 s_tile[REG_TJ * REG_MAX_D / 4];   // 32 KB
+  __shared__ int s_j[REG_MAX_N], s_i[REG_MAX_N];
+  __shared__ int s_wave[4];
+  const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int m1 = reg_clip(n1[p], n_max), m2 = reg_clip(n2[p], n_max);
+  const float* f1 = feat1 + (size_t)p * n_max * D;
+  const float* f2 = feat2 + (size_t)p * n_max * D;
+  int32_t* out = corr + (size_t)p * n_max * 2;
+  if (m1 == 0 || m2 == 0) {
+    for (int c = t; c < n_max; c += REG_WG) out[2 * c] = out[2 * c + 1] = -1;
+    if (t == 0) n_corr[p] = 0;
+    return;
+  }
+  s_j[t] = reg_argmin_pass(f1, m1, f2, m2, D, s_tile);
+  s_i[t] = reg_argmin_pass(f2, m2, f1, m1, D, s_tile);
+  __syncthreads();
+  const bool mutual = t < m1 && s_i[s_j[t]] == t;
+  unsigned long long bal = __ballot(mutual);
+  if (lane == 0) s_wave[w] = __popcll(bal);
+  __syncthreads();
+  const int n_mutual = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  __syncthreads();
+  const bool keep = n_mutual >= 3 ? mutual : (t < m1);
+  bal = __ballot(keep);
+  if (lane == 0) s_wave[w] = __popcll(bal);
+  __syncthreads();
+  int pos = __popcll(bal & ((1ull << lane) - 1ull));
+  for (int k = 0; k < w; ++k) pos += s_wave[k];
+  const int total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  if (keep) {
+    out[2 * pos] = t;
+    out[2 * pos + 1] = s_j[t];
+  }
+  for (int c = total + t; c < n_max; c += REG_WG) out[2 * c] = out[2 * c + 1] = -1;
+  if (t == 0) n_corr[p] = total;
+}
+
+// ------------------------------------------------------------------ shared geometry
+// Correspondence coordinates of one pair into LDS as fp64, centred on the centroids of the correspondences' source / target
+// points (sums in ascending correspondence order by one lane per coordinate: a fixed order).  s_c[0..2] = source x, y, z,
+// s_c[3..5] = target; s_cent[0..5] the centroids.  Indices are clamped: nothing is read by an unchecked index.
+__device__ static int reg_load_corr(const float* __restrict__ kp1, const float* __restrict__ kp2, int m1, int m2,
+                                    const int32_t* __restrict__ corr, int nc_raw, int n_max, double (*s_c)[REG_MAX_N],
+                                    double* s_cent) {
+  const int t = threadIdx.x;
+  const int nc = (m1 == 0 || m2 == 0) ? 0 : reg_clip(nc_raw, n_max);
+  if (t < nc) {
+    const int i = reg_clip(corr[2 * t], m1 - 1), j = reg_clip(corr[2 * t + 1], m2 - 1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      s_c[k][t] = (double)kp1[i * 3 + k];
+      s_c[3 + k][t] = (double)kp2[j * 3 + k];
+    }
+  }
+  __syncthreads();
+  if (t < 6) {
+    double s = 0.0;
+    for (int c = 0; c < nc; ++c) s += s_c[t][c];
+    s_cent[t] = nc > 0 ? s / (double)nc : 0.0;
+  }
+  __syncthreads();
+  if (t < nc) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s_c[k][t] -= s_cent[k];
+  }
+  __syncthreads();
+  return nc;
+}
+
+__device__ static inline void reg_cross(const double* a, const double* b, double* o) {
+  o[0] = a[1] * b[2] - a[2] * b[1];
+  o[1] = a[2] * b[0] - a[0] * b[2];
+  o[2] = a[0] * b[1] - a[1] * b[0];
+}
+__device__ static inline double reg_dot(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+// |R s + tv - q|^2
+__device__ static inline double reg_res2(const double* R, const double* tv, double sx, double sy, double sz, double qx,
+                                         double qy, double qz) {
+  const double dx = R[0] * sx + R[1] * sy + R[2] * sz + tv[0] - qx;
+  const double dy = R[3] * sx + R[4] * sy + R[5] * sz + tv[1] - qy;
+  const double dz = R[6] * sx + R[7] * sy + R[8] * sz + tv[2] - qz;
+  return dx * dx + dy * dy + dz * dz;
+}
+
+// One hypothesis on the centred correspondences in LDS.  Returns 0 = accepted (R row-major and tv, in centred coordinates),
+// -1 = degenerate draw (a repeated correspondence, or a source or target triangle with |e1 x e2| <= 1e-3 |e1| |e2|),
+// -2 = edge-length check (every edge: |s_a - s_b| >= 0.8 |t_a - t_b| and the converse; on squared lengths),
+// -3 = distance check (a transformed sample point farther than dist_th from its target).
+//
+// The rigid transform of three point pairs in closed form: the centred triples span a plane each, so the cross-covariance
+// has rank 2 and the least-squares rotation (Kabsch / Umeyama with the reflection correction) maps the source plane onto
+// the target plane.  In orthonormal frames (f1, f2, ns) / (g1, g2, nt) of the two planes it is the 2 x 2 orthogonal factor
+// O of A = sum_k p_k q_k^T (p, q = in-plane coordinates) that maximises tr(O A^T): the rotation by atan2(a12 - a21, a11 + a22)
+// when det A >= 0, else the reflection by atan2(a12 + a21, a11 - a22), and the normal maps to det(O) times the normal, which
+// makes det R = +1.  No iteration, no square root of a small difference.
+__device__ static int reg_hypothesis(const double (*s_c)[REG_MAX_N], int nc, uint64_t seed, uint32_t pid, uint32_t t,
+                                     double th2, double* R, double* tv) {
+  const int ia = (int)reg_draw(seed, pid, t, 0, (uint32_t)nc), ib = (int)reg_draw(seed, pid, t, 1, (uint32_t)nc),
+            ic = (int)reg_draw(seed, pid, t, 2, (uint32_t)nc);
+  if (ia == ib || ia == ic || ib == ic) return -1;
+  const int idx[3] = {ia, ib, ic};
+  double S[3][3], Q[3][3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      S[k][c] = s_c[c][idx[k]];
+      Q[k][c] = s_c[3 + c][idx[k]];
+    }
+  double e1[3], e2[3], e3[3], f1[3], f2[3], f3[3], ns[3], nt[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    e1[c] = S[1][c] - S[0][c];
+    e2[c] = S[2][c] - S[0][c];
+    e3[c] = S[2][c] - S[1][c];
+    f1[c] = Q[1][c] - Q[0][c];
+    f2[c] = Q[2][c] - Q[0][c];
+    f3[c] = Q[2][c] - Q[1][c];
+  }
+  reg_cross(e1, e2, ns);
+  reg_cross(f1, f2, nt);
+  const double le1 = reg_dot(e1, e1), le2 = reg_dot(e2, e2), le3 = reg_dot(e3, e3);
+  const double lf1 = reg_dot(f1, f1), lf2 = reg_dot(f2, f2), lf3 = reg_dot(f3, f3);
+  const double ns2 = reg_dot(ns, ns), nt2 = reg_dot(nt, nt);
+  if (!(ns2 > REG_DEGEN2 * le1 * le2) || !(nt2 > REG_DEGEN2 * lf1 * lf2)) return -1;
+  if (!(le1 >= REG_EDGE2 * lf1 && lf1 >= REG_EDGE2 * le1 && le2 >= REG_EDGE2 * lf2 && lf2 >= REG_EDGE2 * le2 &&
+        le3 >= REG_EDGE2 * lf3 && lf3 >= REG_EDGE2 * le3))
+    return -2;
+  // plane frames
+  double fs1[3], fs2[3], gt1[3], gt2[3];
+  const double ie = 1.0 / sqrt(le1), ig = 1.0 / sqrt(lf1), ins = 1.0 / sqrt(ns2), int_ = 1.0 / sqrt(nt2);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    fs1[c] = e1[c] * ie;
+    gt1[c] = f1[c] * ig;
+    ns[c] *= ins;
+    nt[c] *= int_;
+  }
+  reg_cross(ns, fs1, fs2);
+  reg_cross(nt, gt1, gt2);
+  double cs[3], ct[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    cs[c] = (S[0][c] + S[1][c] + S[2][c]) / 3.0;
+    ct[c] = (Q[0][c] + Q[1][c] + Q[2][c]) / 3.0;
+  }
+  double a11 = 0.0, a12 = 0.0, a21 = 0.0, a22 = 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    double ps[3], qs[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      ps[c] = S[k][c] - cs[c];
+      qs[c] = Q[k][c] - ct[c];
+    }
+    const double p0 = reg_dot(ps, fs1), p1 = reg_dot(ps, fs2), q0 = reg_dot(qs, gt1), q1 = reg_dot(qs, gt2);
+    a11 += p0 * q0;
+    a12 += p0 * q1;
+    a21 += p1 * q0;
+    a22 += p1 * q1;
+  }
+  const double cr = a11 + a22, sr = a12 - a21, cf = a11 - a22, sf = a12 + a21;
+  const double vr = cr * cr + sr * sr, vf = cf * cf + sf * sf;
+  double o11, o12, o21, o22, det;
+  if (vr >= vf) {
+    if (!(vr > 0.0)) return -1;
+    const double h = 1.0 / sqrt(vr), c = cr * h, s = sr * h;
+    o11 = c, o12 = -s, o21 = s, o22 = c, det = 1.0;
+  } else {
+    const double h = 1.0 / sqrt(vf), c = cf * h, s = sf * h;
+    o11 = c, o12 = s, o21 = s, o22 = -c, det = -1.0;
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      R[r * 3 + c] = o11 * gt1[r] * fs1[c] + o12 * gt1[r] * fs2[c] + o21 * gt2[r] * fs1[c] + o22 * gt2[r] * fs2[c] +
+                     det * nt[r] * ns[c];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) tv[r] = ct[r] - (R[r * 3] * cs[0] + R[r * 3 + 1] * cs[1] + R[r * 3 + 2] * cs[2]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (!(reg_res2(R, tv, S[k][0], S[k][1], S[k][2], Q[k][0], Q[k][1], Q[k][2]) <= th2)) return -3;
+  return 0;
+}
+
+// workgroup-wide best of (cnt, err2, t) under reg_better; the result is valid in every lane
+__device__ static void reg_block_best(int& cnt, double& err2, int& bt, int* s_cnt, int* s_t, double* s_e) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int oc = __shfl_xor(cnt, o, 64), ot = __shfl_xor(bt, o, 64);
+    const double oe = __shfl_xor(err2, o, 64);
+    if (reg_better(oc, oe, ot, cnt, err2, bt)) cnt = oc, err2 = oe, bt = ot;
+  }
+  __syncthreads();
+  if (lane == 0) s_cnt[w] = cnt, s_t[w] = bt, s_e[w] = err2;
+  __syncthreads();
+  cnt = s_cnt[0], bt = s_t[0], err2 = s_e[0];
+#pragma unroll
+  for (int k = 1; k < 4; ++k)
+    if (reg_better(s_cnt[k], s_e[k], s_t[k], cnt, err2, bt)) cnt = s_cnt[k], err2 = s_e[k], bt = s_t[k];
+}
+
+// ------------------------------------------------------------------ 2. the hot loop: one lane = one hypothesis
+__global__ __launch_bounds__(REG_WG) void reg_ransac_kernel(const float* __restrict__ kp1, const float* __restrict__ kp2,
+                                                            const int32_t* __restrict__ n1, const int32_t* __restrict__ n2,
+                                                            const int32_t* __restrict__ corr,
+                                                            const int32_t* __restrict__ n_corr,
+                                                            const int32_t* __restrict__ pair_id, int n_max, int H, int chunks,
+                                                            uint64_t seed, double th2, RegPartial* __restrict__ partial,
+                                                            int32_t* __restrict__ hyp_count, double* __restrict__ hyp_err2) {
+  __shared__ double s_c[6][REG_MAX_N];   // 12 KB
+  __shared__ double s_cent[6];
+  __shared__ int s_cnt[4], s_t[4];
+  __shared__ double s_e[4];
+  const int p = blockIdx.x / chunks, chunk = blockIdx.x % chunks, t = chunk * REG_WG + (int)threadIdx.x;
+  const int m1 = reg_clip(n1[p], n_max), m2 = reg_clip(n2[p], n_max);
+  const int nc = reg_load_corr(kp1 + (size_t)p * n_max * 3, kp2 + (size_t)p * n_max * 3, m1, m2, corr + (size_t)p * n_max * 2,
+                               n_corr[p], n_max, s_c, s_cent);
+  const uint32_t pid = pair_id ? (uint32_t)pair_id[p] & 0x3fffffffu : (uint32_t)p;
+  int cnt = -1, code = -1;
+  double err2 = 0.0;
+  if (t < H && nc >= 3) {
+    double R[9], tv[3];
+    code = reg_hypothesis(s_c, nc, seed, pid, (uint32_t)t, th2, R, tv);
+    if (code == 0) {
+      cnt = 0;
+      for (int c = 0; c < nc; ++c) {   // every lane reads the same correspondence: LDS broadcast
+        const double d2 = reg_res2(R, tv, s_c[0][c], s_c[1][c], s_c[2][c], s_c[3][c], s_c[4][c], s_c[5][c]);
+        if (d2 < th2) {
+          ++cnt;
+          err2 += d2;
+        }
+      }
+    }
+  }
+  if (t < H) {
+    if (hyp_count) hyp_count[(size_t)p * H + t] = code == 0 ? cnt : code;
+    if (hyp_err2) hyp_err2[(size_t)p * H + t] = err2;
+  }
+  int bt = t < H ? t : 0x7fffffff;
+  reg_block_best(cnt, err2, bt, s_cnt, s_t, s_e);
+  if (threadIdx.x == 0) {
+    RegPartial r;
+    r.cnt = cnt, r.t = bt, r.err2 = err2;
+    partial[(size_t)p * chunks + chunk] = r;
+  }
+}
+
+// ------------------------------------------------------------------ 3. best hypothesis, final evaluation, metrics
+__global__ __launch_bounds__(REG_WG) void reg_finish_kernel(
+    const float* __restrict__ kp1, const float* __restrict__ kp2, const int32_t* __restrict__ n1, const int32_t* __restrict__ n2,
+    const int32_t* __restrict__ corr, const int32_t* __restrict__ n_corr, const int32_t* __restrict__ pair_id, int n_max, int H,
+    int chunks, uint64_t seed, double th2, const RegPartial* __restrict__ partial, const double* __restrict__ T_gt, double rth2,
+    double* __restrict__ T_out, int32_t* __restrict__ inliers, double* __restrict__ fitness, double* __restrict__ rmse,
+    int32_t* __restrict__ corr_set, int32_t* __restrict__ best_t, double* __restrict__ rte, double* __restrict__ rre,
+    int32_t* __restrict__ success, double* __restrict__ repeatability, int32_t* __restrict__ status) {
+  __shared__ double s_c[6][REG_MAX_N];
+  __shared__ double s_cent[6];
+  __shared__ int s_cnt[4], s_t[4];
+  __shared__ double s_e[4];
+  __shared__ double s_q[3][REG_MAX_N];   // target keypoints, fp64
+  __shared__ double s_d2[REG_MAX_N];
+  __shared__ int s_nn[REG_MAX_N];
+  const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int r1 = n1[p], r2 = n2[p];
+  const int m1 = reg_clip(r1, n_max), m2 = reg_clip(r2, n_max);
+  const float* k1 = kp1 + (size_t)p * n_max * 3;
+  const float* k2 = kp2 + (size_t)p * n_max * 3;
+  int st = (r1 != m1 || r2 != m2) ? EGONN_REG_STATUS_CLIPPED : 0;
+
+  // T = identity unless a hypothesis was accepted (Open3D returns the identity result when nothing beats fitness 0)
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tf[3] = {0, 0, 0};
+  int bt = -1;
+  if (corr) {
+    const int32_t* cp = corr + (size_t)p * n_max * 2;
+    const int nc_raw = n_corr[p];
+    const int nc = reg_load_corr(k1, k2, m1, m2, cp, nc_raw, n_max, s_c, s_cent);
+    if (nc_raw != nc) st |= EGONN_REG_STATUS_CLIPPED;
+    bool bad = false;
+    if (t < nc) bad = cp[2 * t] < 0 || cp[2 * t] >= m1 || cp[2 * t + 1] < 0 || cp[2 * t + 1] >= m2;
+    if (__syncthreads_or(bad)) st |= EGONN_REG_STATUS_BAD_INDEX;
+    if (nc < 3) st |= EGONN_REG_STATUS_FEW_CORR;
+    int cnt = -1, ct = 0x7fffffff;
+    double e = 0.0;
+    for (int c = t; c < chunks; c += REG_WG) {
+      const RegPartial r = partial[(size_t)p * chunks + c];
+      if (reg_better(r.cnt, r.err2, r.t, cnt, e, ct)) cnt = r.cnt, e = r.err2, ct = r.t;
+    }
+    reg_block_best(cnt, e, ct, s_cnt, s_t, s_e);
+    if (nc >= 3 && cnt > 0 && ct >= 0 && ct < H) {
+      const uint32_t pid = pair_id ? (uint32_t)pair_id[p] & 0x3fffffffu : (uint32_t)p;
+      double tv[3];
+      if (reg_hypothesis(s_c, nc, seed, pid, (uint32_t)ct, th2, R, tv) == 0) {   // every lane: the same bits
+        bt = ct;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)   // centred -> caller's coordinates
+          tf[r] = s_cent[3 + r] + tv[r] - (R[r * 3] * s_cent[0] + R[r * 3 + 1] * s_cent[1] + R[r * 3 + 2] * s_cent[2]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+      }
+    }
+    if (bt < 0) st |= EGONN_REG_STATUS_NO_MODEL;
+  }
+
+  if (t < m2) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s_q[k][t] = (double)k2[t * 3 + k];
+  }
+  __syncthreads();
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  if (t < m1) sx = (double)k1[t * 3], sy = (double)k1[t * 3 + 1], sz = (double)k1[t * 3 + 2];
+
+  if (corr) {
+    // final evaluation: every source keypoint under T, nearest target keypoint (ties: lowest index) closer than dist_th
+    double bd = INFINITY;
+    int bj = -1;
+    if (t < m1 && bt >= 0) {
+      const double px = R[0] * sx + R[1] * sy + R[2] * sz + tf[0], py = R[3] * sx + R[4] * sy + R[5] * sz + tf[1],
+                   pz = R[6] * sx + R[7] * sy + R[8] * sz + tf[2];
+      for (int j = 0; j < m2; ++j) {
+        const double dx = px - s_q[0][j], dy = py - s_q[1][j], dz = pz - s_q[2][j];
+        const double d2 = dx * dx + dy * dy + dz * dz;
+        if (d2 < bd) bd = d2, bj = j;
+      }
+    }
+    s_d2[t] = bd;
+    s_nn[t] = bj;
+    __syncthreads();
+    if (t == 0) {
+      int k = 0;
+      double e2 = 0.0;
+      int32_t* cs = corr_set ? corr_set + (size_t)p * n_max * 2 : nullptr;
+      for (int i = 0; i < m1; ++i)   // ascending i: a fixed summation order
+        if (s_nn[i] >= 0 && s_d2[i] < th2) {
+          if (cs) cs[2 * k] = i, cs[2 * k + 1] = s_nn[i];
+          e2 += s_d2[i];
+          ++k;
+        }
+      if (cs)
+        for (int c = k; c < n_max; ++c) cs[2 * c] = cs[2 * c + 1] = -1;
+      inliers[p] = k;
+      fitness[p] = m1 > 0 ? (double)k / (double)m1 : 0.0;
+      rmse[p] = k > 0 ? sqrt(e2 / (double)k) : 0.0;
+      if (best_t) best_t[p] = bt;
+      double* To = T_out + (size_t)p * 16;
+      for (int r = 0; r < 3; ++r) {
+        To[r * 4] = R[r * 3], To[r * 4 + 1] = R[r * 3 + 1], To[r * 4 + 2] = R[r * 3 + 2], To[r * 4 + 3] = tf[r];
+      }
+      To[12] = To[13] = To[14] = 0.0, To[15] = 1.0;
+    }
+  }
+
+  if (T_gt) {
+    const double* G = T_gt + (size_t)p * 16;
+    // calculate_repeatability: share of source keypoints with a target keypoint within the threshold under T_gt (fp64)
+    bool rep = false;
+    if (t < m1) {
+      const double px = G[0] * sx + G[1] * sy + G[2] * sz + G[3], py = G[4] * sx + G[5] * sy + G[6] * sz + G[7],
+                   pz = G[8] * sx + G[9] * sy + G[10] * sz + G[11];
+      double bd = INFINITY;
+      for (int j = 0; j < m2; ++j) {
+        const double dx = px - s_q[0][j], dy = py - s_q[1][j], dz = pz - s_q[2][j];
+        const double d2 = dx * dx + dy * dy + dz * dz;
+        if (d2 < bd) bd = d2;
+      }
+      rep = bd <= rth2;
+    }
+    const unsigned long long bal = __ballot(rep);
+    __syncthreads();
+    if (lane == 0) s_cnt[w] = __popcll(bal);
+    __syncthreads();
+    if (t == 0) {
+      const int nrep = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+      if (repeatability) repeatability[p] = m1 > 0 ? (double)nrep / (double)m1 : 0.0;
+      if (corr) {
+        const double dx = tf[0] - G[3], dy = tf[1] - G[7], dz = tf[2] - G[11];
+        const double e_t = sqrt(dx * dx + dy * dy + dz * dz);
+        double tr = 0.0;   // trace(R_est^T R_gt) = sum of the elementwise products
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 3; ++c) tr += R[r * 3 + c] * G[r * 4 + c];
+        double cosv = (tr - 1.0) / 2.0;
+        cosv = cosv < -1.0 ? -1.0 : (cosv > 1.0 ? 1.0 : cosv);
+        const double e_r = acos(cosv) * 180.0 / 3.14159265358979323846;
+        if (rte) rte[p] = e_t;
+        if (rre) rre[p] = e_r;
+        if (success) success[p] = (e_t > 2.0 || e_r > 5.0) ? 0 : 1;
+      }
+    }
+  }
+  if (t == 0 && status) status[p] = st;
+}
+
+static int reg_check_shape(const char* who, int P, int n_max) {
+  EGONN_REQUIRE(P >= 0 && P <= (1 << 20) && n_max >= 1 && n_max <= REG_MAX_N, EGONN_ERR_INVALID,
+                "%s: bad shape (P=%d, n_max=%d; n_max <= %d)", who, P, n_max, REG_MAX_N);
+  return EGONN_OK;
+}
+
+}  // namespace egonn
+
+using namespace egonn;
+
+API int64_t egonn_registration_scratch_bytes(int n_pairs, int n_max, int n_hypotheses) {
+  if (n_pairs < 0 || n_max < 1 || n_max > REG_MAX_N || n_hypotheses <= 0) return -1;
+  return (int64_t)n_pairs * cdiv(n_hypotheses, REG_WG) * (int64_t)sizeof(RegPartial);
+}
+
+API int egonn_match_mutual(const float* feat1, const float* feat2, const int32_t* n1, const int32_t* n2, int n_pairs, int n_max,
+                           int dim, int32_t* corr, int32_t* n_corr, void* stream) {
+  EGONN_TRY(reg_check_shape("match_mutual", n_pairs, n_max));
+  EGONN_REQUIRE(dim >= 4 && dim <= REG_MAX_D && dim % 4 == 0, EGONN_ERR_INVALID,
+                "match_mutual: descriptor width %d must be a multiple of 4 in [4, %d]", dim, REG_MAX_D);
+  EGONN_REQUIRE(feat1 && feat2 && n1 && n2 && corr && n_corr, EGONN_ERR_INVALID, "match_mutual: null pointer");
+  EGONN_REQUIRE(((uintptr_t)feat1 & 15) == 0 && ((uintptr_t)feat2 & 15) == 0, EGONN_ERR_INVALID,
+                "match_mutual: descriptors must be 16-byte aligned");
+  if (n_pairs == 0) return EGONN_OK;
+  hipLaunchKernelGGL(reg_match_kernel, dim3((unsigned)n_pairs), dim3(REG_WG), 0, (hipStream_t)stream, feat1, feat2, n1, n2, n_max,
+                     dim, corr, n_corr);
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}
+
+API int egonn_ransac_pairs(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2, const int32_t* corr,
+                           const int32_t* n_corr, const int32_t* pair_id, int n_pairs, int n_max, int n_hypotheses,
+                           uint64_t seed, double dist_th, void* scratch, int64_t scratch_bytes, int32_t* hyp_count,
+                           double* hyp_err2, void* stream) {
+  EGONN_TRY(reg_check_shape("ransac_pairs", n_pairs, n_max));
+  EGONN_REQUIRE(n_hypotheses > 0, EGONN_ERR_INVALID, "ransac_pairs: n_hypotheses %d must be positive", n_hypotheses);
+  EGONN_REQUIRE(kp1 && kp2 && n1 && n2 && corr && n_corr && scratch, EGONN_ERR_INVALID, "ransac_pairs: null pointer");
+  EGONN_REQUIRE(dist_th > 0.0 && dist_th < 1e18, EGONN_ERR_INVALID, "ransac_pairs: bad distance threshold");
+  const int64_t chunks = cdiv(n_hypotheses, REG_WG);
+  EGONN_REQUIRE(scratch_bytes >= egonn_registration_scratch_bytes(n_pairs, n_max, n_hypotheses) &&
+                    ((uintptr_t)scratch & 7) == 0,
+                EGONN_ERR_INVALID, "ransac_pairs: scratch needs %lld bytes, 8-byte aligned",
+                (long long)egonn_registration_scratch_bytes(n_pairs, n_max, n_hypotheses));
+  EGONN_REQUIRE((int64_t)n_pairs * chunks < (1ll << 31), EGONN_ERR_INVALID, "ransac_pairs: %d pairs x %d hypotheses is too large a grid",
+                n_pairs, n_hypotheses);
+  if (n_pairs == 0) return EGONN_OK;
+  hipLaunchKernelGGL(reg_ransac_kernel, dim3((unsigned)(n_pairs * chunks)), dim3(REG_WG), 0, (hipStream_t)stream, kp1, kp2, n1, n2,
+                     corr, n_corr, pair_id, n_max, n_hypotheses, (int)chunks, seed, dist_th * dist_th, (RegPartial*)scratch,
+                     hyp_count, hyp_err2);
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}
+
+API int egonn_registration_finish(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2, const int32_t* corr,
+                                  const int32_t* n_corr, const int32_t* pair_id, int n_pairs, int n_max, int n_hypotheses,
+                                  uint64_t seed, double dist_th, const void* scratch, int64_t scratch_bytes, const double* T_gt,
+                                  double repeat_th, double* T, int32_t* inliers, double* fitness, double* inlier_rmse,
+                                  int32_t* corr_set, int32_t* best_t, double* rte, double* rre, int32_t* success,
+                                  double* repeatability, int32_t* status, void* stream) {
+  EGONN_TRY(reg_check_shape("registration_finish", n_pairs, n_max));
+  EGONN_REQUIRE(kp1 && kp2 && n1 && n2, EGONN_ERR_INVALID, "registration_finish: null pointer");
+  int chunks = 0;
+  if (corr) {
+    EGONN_REQUIRE(n_hypotheses > 0, EGONN_ERR_INVALID, "registration_finish: n_hypotheses %d must be positive", n_hypotheses);
+    EGONN_REQUIRE(n_corr && scratch && T && inliers && fitness && inlier_rmse, EGONN_ERR_INVALID,
+                  "registration_finish: null pointer");
+    EGONN_REQUIRE(dist_th > 0.0 && dist_th < 1e18, EGONN_ERR_INVALID, "registration_finish: bad distance threshold");
+    EGONN_REQUIRE(scratch_bytes >= egonn_registration_scratch_bytes(n_pairs, n_max, n_hypotheses) &&
+                      ((uintptr_t)scratch & 7) == 0,
+                  EGONN_ERR_INVALID, "registration_finish: scratch needs %lld bytes, 8-byte aligned",
+                  (long long)egonn_registration_scratch_bytes(n_pairs, n_max, n_hypotheses));
+    chunks = (int)cdiv(n_hypotheses, REG_WG);
+  } else {
+    EGONN_REQUIRE(T_gt && repeatability, EGONN_ERR_INVALID,
+                  "registration_finish: without correspondences only the T_gt metrics are computed: T_gt and repeatability needed");
+  }
+  EGONN_REQUIRE(!T_gt || (repeat_th >= 0.0 && repeat_th < 1e18), EGONN_ERR_INVALID, "registration_finish: bad repeatability threshold");
+  if (n_pairs == 0) return EGONN_OK;
+  hipLaunchKernelGGL(reg_finish_kernel, dim3((unsigned)n_pairs), dim3(REG_WG), 0, (hipStream_t)stream, kp1, kp2, n1, n2, corr, n_corr,
+                     pair_id, n_max, n_hypotheses, chunks, seed, dist_th * dist_th, (const RegPartial*)scratch, T_gt,
+                     repeat_th * repeat_th, T, inliers, fitness, inlier_rmse, corr_set, best_t, rte, rre, success, repeatability,
+                     status);
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}

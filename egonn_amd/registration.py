@@ -1,0 +1,241 @@
+"""6-DoF registration of keypoint sets on the device: the consumer of the local half of the descriptor path.
+
+Mirrors the reference's names (eval/evaluate.py): `get_ransac_result` (:381-399), `calculate_repeatability` (:402-411),
+plus `register_pairs` (batched) and `evaluate_local`, the per-n_k metric bookkeeping of
+`MinkLocGLEvaluator.evaluate` (:188-292).  Matching, RANSAC, the final evaluation and the metrics run in libegonn_hip
+(egonn_match_mutual / egonn_ransac_pairs / egonn_registration_finish); there is no torch or numpy fallback for the
+arithmetic.  ICP refinement is out of scope (it needs the full clouds): the `*_refined` family is reduced to
+`repeatability_refined`, computed with the caller's `T_refined`.
+"""
+from __future__ import annotations
+
+from typing import Dict, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+
+N_MAX = 256
+STATUS_CLIPPED, STATUS_FEW_CORR, STATUS_NO_MODEL, STATUS_BAD_INDEX = 1, 2, 4, 8
+
+
+class RegistrationResult:
+    """one pair's result with the attribute names of Open3D's RegistrationResult"""
+
+    def __init__(self, transformation, correspondence_set, fitness, inlier_rmse, status):
+        self.transformation = transformation            # (4,4) numpy float64
+        self.correspondence_set = correspondence_set    # (inliers, 2) numpy int32
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.status = status
+
+    def __repr__(self):
+        return (f"RegistrationResult(fitness={self.fitness:.6f}, inlier_rmse={self.inlier_rmse:.6f}, "
+                f"correspondence_set={len(self.correspondence_set)}, status={self.status})")
+
+
+def _dev(x, dev, dtype):
+    return torch.as_tensor(x).to(device=dev, dtype=dtype).contiguous()
+
+
+def _counts(n, P, n_rows, dev):
+    if n is None:
+        return torch.full((P,), n_rows, dtype=torch.int32, device=dev)
+    n = _dev(n, dev, torch.int32)
+    assert n.shape == (P,), "per-pair counts must have shape (P,)"
+    return n
+
+
+def match_mutual(feat1: torch.Tensor, feat2: torch.Tensor, n1=None, n2=None):
+    """(P, n_max, D) x 2 -> corr (P, n_max, 2) int32 compacted in ascending source index (unused rows -1), n_corr (P,)."""
+    dev = feat1.device if feat1.is_cuda else _lib.require_gpu()
+    lib = _lib.load()
+    f1, f2 = _dev(feat1, dev, torch.float32), _dev(feat2, dev, torch.float32)
+    assert f1.dim() == 3 and f1.shape == f2.shape, "descriptors: (P, n_max, D), both sides padded alike"
+    P, n_max, D = f1.shape
+    c1, c2 = _counts(n1, P, n_max, dev), _counts(n2, P, n_max, dev)
+    corr = torch.empty((P, n_max, 2), dtype=torch.int32, device=dev)
+    n_corr = torch.empty((P,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.egonn_match_mutual(f1.data_ptr(), f2.data_ptr(), c1.data_ptr(), c2.data_ptr(), P, n_max, D,
+                                          corr.data_ptr(), n_corr.data_ptr(), _lib._stream()))
+    return corr, n_corr
+
+
+def register_pairs(feat1, feat2, kp1, kp2, n1=None, n2=None, T_gt=None, ransac_dist_th: float = 0.5,
+                   ransac_max_it: int = 10000, seed: int = 0, pair_ids=None, repeat_dist_th: float = 0.5,
+                   debug: bool = False) -> Dict[str, torch.Tensor]:
+    """P pairs at once.  feat (P, n_max, D), kp (P, n_max, 3), n1 / n2 (P,) row counts (None = n_max), T_gt (P,4,4) or None.
+    Returns device tensors: T (P,4,4) f64, inliers (P,) i32, fitness, inlier_rmse (P,) f64, correspondence_set
+    (P, n_max, 2) i32 (rows beyond `inliers` are -1), best_t, status (P,) i32, corr, n_corr; with T_gt also rte, rre (f64),
+    success (i32), repeatability (f64); with debug the per-hypothesis tables hyp_count (P,H) i32 and hyp_err2 (P,H) f64.
+    pair_ids (P,) int32: the id that enters the draws, its low 30 bits (None = position in the batch).
+    No host synchronisation when every array argument is a device tensor (host arrays or lists are copied over first); such a
+    call can be captured into a graph."""
+    dev = feat1.device if torch.is_tensor(feat1) and feat1.is_cuda else _lib.require_gpu()
+    lib = _lib.load()
+    f1 = _dev(feat1, dev, torch.float32)
+    assert f1.dim() == 3, "descriptors: (P, n_max, D)"
+    P, n_max = f1.shape[0], f1.shape[1]
+    c1, c2 = _counts(n1, P, n_max, dev), _counts(n2, P, n_max, dev)          # converted once: host counts cost one copy each
+    corr, n_corr = match_mutual(f1, _dev(feat2, dev, torch.float32), c1, c2)
+    k1, k2 = _dev(kp1, dev, torch.float32), _dev(kp2, dev, torch.float32)
+    assert k1.shape == (P, n_max, 3) and k2.shape == (P, n_max, 3), "keypoints: (P, n_max, 3), padded like the descriptors"
+    H = int(ransac_max_it)
+    pid = None if pair_ids is None else _dev(pair_ids, dev, torch.int32)
+    gt = None if T_gt is None else _dev(T_gt, dev, torch.float64).reshape(P, 4, 4)
+    nbytes = int(lib.egonn_registration_scratch_bytes(P, n_max, H))      # -1 on bad arguments: the launch call below raises
+    scratch = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
+    out = {"T": f64(P, 4, 4), "inliers": i32(P), "fitness": f64(P), "inlier_rmse": f64(P),
+           "correspondence_set": i32(P, n_max, 2), "best_t": i32(P), "status": i32(P), "corr": corr, "n_corr": n_corr}
+    if gt is not None:
+        out.update({"rte": f64(P), "rre": f64(P), "success": i32(P), "repeatability": f64(P)})
+    if debug:
+        out.update({"hyp_count": i32(P, max(H, 0)), "hyp_err2": f64(P, max(H, 0))})
+    p = lambda k: _lib._ptr(out.get(k))                                       # noqa: E731
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    with torch.cuda.device(dev):
+        st = _lib._stream()
+        _lib.check(lib.egonn_ransac_pairs(k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(),
+                                          n_corr.data_ptr(), _lib._ptr(pid), P, n_max, H, seed, float(ransac_dist_th),
+                                          scratch.data_ptr(), scratch.numel() * 8, p("hyp_count"), p("hyp_err2"), st))
+        _lib.check(lib.egonn_registration_finish(k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(),
+                                                 n_corr.data_ptr(), _lib._ptr(pid), P, n_max, H, seed, float(ransac_dist_th),
+                                                 scratch.data_ptr(), scratch.numel() * 8, _lib._ptr(gt), float(repeat_dist_th),
+                                                 p("T"), p("inliers"), p("fitness"), p("inlier_rmse"), p("correspondence_set"),
+                                                 p("best_t"), p("rte"), p("rre"), p("success"), p("repeatability"),
+                                                 p("status"), st))
+    out["_keep"] = (k1, k2, c1, c2, pid, gt, scratch)      # inputs of enqueued work stay alive with the result
+    return out
+
+
+def get_ransac_result(feat1, feat2, kp1, kp2, ransac_dist_th: float = 0.5, ransac_max_it: int = 10000, seed: int = 0):
+    """eval/evaluate.py:381-399 for one pair: feat (n, D), kp (n, 3); n1 != n2 allowed.  [SYNC] copies the result back."""
+    dev = _lib.require_gpu() if not (torch.is_tensor(feat1) and feat1.is_cuda) else feat1.device
+    f1, f2 = torch.as_tensor(feat1), torch.as_tensor(feat2)
+    k1, k2 = torch.as_tensor(kp1), torch.as_tensor(kp2)
+    assert f1.dim() == 2 and f2.dim() == 2 and f1.shape[1] == f2.shape[1] and k1.shape == (f1.shape[0], 3) \
+        and k2.shape == (f2.shape[0], 3), "feat (n, D) and kp (n, 3) per side"
+    n_max = max(f1.shape[0], f2.shape[0], 1)
+    if n_max > N_MAX:
+        raise ValueError(f"get_ransac_result: at most {N_MAX} keypoints per side, got {n_max}")
+
+    def pad(x, w):
+        o = torch.zeros((1, n_max, w), dtype=torch.float32, device=dev)
+        o[0, :x.shape[0]] = x.to(device=dev, dtype=torch.float32)
+        return o
+
+    r = register_pairs(pad(f1, f1.shape[1]), pad(f2, f1.shape[1]), pad(k1, 3), pad(k2, 3), n1=[f1.shape[0]], n2=[f2.shape[0]],
+                       ransac_dist_th=ransac_dist_th, ransac_max_it=ransac_max_it, seed=seed)
+    n_in = int(r["inliers"][0])
+    return RegistrationResult(r["T"][0].cpu().numpy(), r["correspondence_set"][0, :n_in].cpu().numpy(), float(r["fitness"][0]),
+                              float(r["inlier_rmse"][0]), int(r["status"][0]))
+
+
+def repeatability_pairs(kp1, kp2, T, threshold: float, n1=None, n2=None) -> torch.Tensor:
+    """batched calculate_repeatability: kp (P, n_max, 3), T (P,4,4) -> (P,) f64 on the device"""
+    dev = kp1.device if torch.is_tensor(kp1) and kp1.is_cuda else _lib.require_gpu()
+    lib = _lib.load()
+    k1, k2 = _dev(kp1, dev, torch.float32), _dev(kp2, dev, torch.float32)
+    P, n_max = k1.shape[0], k1.shape[1]
+    assert k1.dim() == 3 and k1.shape == k2.shape and k1.shape[2] == 3
+    c1, c2 = _counts(n1, P, n_max, dev), _counts(n2, P, n_max, dev)
+    gt = _dev(T, dev, torch.float64).reshape(P, 4, 4)
+    rep = torch.empty((P,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.egonn_registration_finish(k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), None, None, None, P,
+                                                 n_max, 0, 0, 0.0, None, 0, gt.data_ptr(), float(threshold), None, None, None,
+                                                 None, None, None, None, None, None, rep.data_ptr(), None, _lib._stream()))
+    return rep
+
+
+def calculate_repeatability(kp1, kp2, T_gt, threshold: float) -> float:
+    """eval/evaluate.py:402-411 for one pair (kp1 (n1,3), kp2 (n2,3)); the transform is applied in float64 on the device."""
+    dev = _lib.require_gpu() if not (torch.is_tensor(kp1) and kp1.is_cuda) else kp1.device
+    k1, k2 = torch.as_tensor(kp1), torch.as_tensor(kp2)
+    n_max = max(k1.shape[0], k2.shape[0], 1)
+    if n_max > N_MAX:
+        raise ValueError(f"calculate_repeatability: at most {N_MAX} keypoints per side, got {n_max}")
+    a = torch.zeros((1, n_max, 3), dtype=torch.float32, device=dev)
+    b = torch.zeros((1, n_max, 3), dtype=torch.float32, device=dev)
+    a[0, :k1.shape[0]] = k1.to(device=dev, dtype=torch.float32)
+    b[0, :k2.shape[0]] = k2.to(device=dev, dtype=torch.float32)
+    rep = repeatability_pairs(a, b, np.asarray(T_gt, dtype=np.float64).reshape(1, 4, 4), threshold, [k1.shape[0]], [k2.shape[0]])
+    return float(rep[0])
+
+
+def _stack(items, idx, key, n_k, width, dev):
+    """pad the first n_k rows of items[i][key] for i in idx to (len(idx), n_k, width) + counts"""
+    out = torch.zeros((len(idx), n_k, width), dtype=torch.float32, device=dev)
+    cnt = []
+    for r, i in enumerate(idx):
+        x = torch.as_tensor(items[i][key])[:n_k]
+        out[r, :x.shape[0]] = x.to(device=dev, dtype=torch.float32)
+        cnt.append(x.shape[0])
+    return out, cnt
+
+
+def evaluate_local(local_query: Sequence[dict], local_map: Sequence[dict], nn_index, T_gt, n_k: Sequence[int] = (128,),
+                   euclid_dist=None, T_refined=None, ransac_dist_th: float = 0.5, ransac_max_it: int = 10000,
+                   repeat_dist_th: float = 0.5, seed: int = 0) -> Dict[int, Dict[str, float]]:
+    """The local-descriptor half of MinkLocGLEvaluator.evaluate (eval/evaluate.py:188-292) for all queries at once.
+
+    local_query / local_map: per scan {'keypoints': (n,3), 'features': (n,D)} (compute_embeddings, :323); nn_index (Q,) or
+    (Q,k): the retrieved map element per query (column 0 is used, :197); T_gt (Q,4,4): relative pose of query and that
+    element; euclid_dist (Q,) or (Q,k): when given, queries whose first neighbour is farther than 20 m are skipped (:192).
+    Returns {n_k: {'rre', 'rte', 'repeatability', 'success', 'success_inliers', 'failure_inliers', 'repeatability_refined',
+    't_ransac', 't_ransac_sd'}} with the reference's conventions (rre / rte averaged over successes, empty lists -> 0.;
+    t_ransac = the device time of the batched call divided by its pairs: ONE measurement, so 't_ransac_sd' is reported as 0.
+    rather than computed).  The pair id of the draws is the query index."""
+    dev = _lib.require_gpu()
+    nn = torch.as_tensor(nn_index).reshape(len(local_query), -1)[:, 0].tolist()
+    sel = list(range(len(local_query)))
+    if euclid_dist is not None:
+        ed = torch.as_tensor(euclid_dist, dtype=torch.float64).reshape(len(local_query), -1)[:, 0].tolist()
+        sel = [q for q in sel if not ed[q] > 20]
+    gt_all = torch.as_tensor(np.asarray(T_gt, dtype=np.float64)).reshape(-1, 4, 4)
+    ref_all = None if T_refined is None else torch.as_tensor(np.asarray(T_refined, dtype=np.float64)).reshape(-1, 4, 4)
+    keys = ('rre', 'rte', 'repeatability', 'success', 'success_inliers', 'failure_inliers', 'repeatability_refined')
+    mean_metrics = {}
+    for nk in n_k:
+        if nk > N_MAX:
+            raise ValueError(f"evaluate_local: n_k {nk} exceeds {N_MAX}")
+        m = {k: [] for k in keys}
+        t_pair = 0.
+        if sel:
+            D = int(torch.as_tensor(local_query[sel[0]]['features']).shape[1])
+            f1, c1 = _stack(local_query, sel, 'features', nk, D, dev)
+            k1, _ = _stack(local_query, sel, 'keypoints', nk, 3, dev)
+            mi = [nn[q] for q in sel]
+            f2, c2 = _stack(local_map, mi, 'features', nk, D, dev)
+            k2, _ = _stack(local_map, mi, 'keypoints', nk, 3, dev)
+            gt = gt_all[sel]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = register_pairs(f1, f2, k1, k2, n1=c1, n2=c2, T_gt=gt, ransac_dist_th=ransac_dist_th, ransac_max_it=ransac_max_it,
+                               seed=seed, pair_ids=sel, repeat_dist_th=repeat_dist_th)
+            e1.record()
+            ref = gt if ref_all is None else ref_all[sel]
+            rep_ref = r["repeatability"] if ref_all is None else repeatability_pairs(k1, k2, ref, repeat_dist_th, c1, c2)
+            e1.synchronize()
+            t_pair = e0.elapsed_time(e1) * 1e-3 / len(sel)
+            rte, rre, suc, inl = (r[k].cpu().tolist() for k in ("rte", "rre", "success", "inliers"))
+            m['repeatability'] = r["repeatability"].cpu().tolist()
+            m['repeatability_refined'] = rep_ref.cpu().tolist()
+            for i in range(len(sel)):
+                if suc[i]:
+                    m['success'].append(1.)
+                    m['rte'].append(rte[i])
+                    m['rre'].append(rre[i])
+                    m['success_inliers'].append(inl[i])
+                else:
+                    m['success'].append(0.)
+                    m['failure_inliers'].append(inl[i])
+        mean_metrics[nk] = {k: (float(np.mean(v)) if len(v) else 0.) for k, v in m.items()}
+        mean_metrics[nk]['t_ransac'] = t_pair
+        if sel:
+            mean_metrics[nk]['t_ransac_sd'] = 0.
+    return mean_metrics

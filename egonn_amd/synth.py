@@ -114,3 +114,54 @@ def seeded_tensor(seed: int, key: str, shape: Tuple[int, ...]) -> np.ndarray:
 
 def seeded_state_dict(seed: int, shapes: Dict[str, Tuple[int, ...]]) -> Dict[str, np.ndarray]:
     return {k: seeded_tensor(seed, k, s) for k, s in shapes.items()}
+
+
+# ------------------------------------------------------------------ keypoint sets with a planted pose (registration tests / timing)
+def _unit(x):
+    return x / np.linalg.norm(x, axis=-1, keepdims=True)
+
+
+def rot_zyx(yaw, pitch, roll):
+    cy, sy, cp, sp, cr, sr = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
+    Rz = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1.0]])
+    Ry = np.array([[cp, 0, sp], [0, 1.0, 0], [-sp, 0, cp]])
+    Rx = np.array([[1.0, 0, 0], [0, cr, -sr], [0, sr, cr]])
+    return Rz @ Ry @ Rx
+
+
+def planted_keypoint_pair(n, seed, outliers, noise=0.05, D=128, n2=None, desc_noise=0.02):
+    """source keypoints in a +-80 m box (z +-10), target = T_gt source + noise, a share `outliers` of the target replaced by
+    unrelated points with unrelated descriptors, the target order shuffled.  -> f1, f2, k1, k2 (float32), T_gt (4,4) float64"""
+    rng = np.random.default_rng(seed)
+    src = rng.uniform([-80, -80, -10], [80, 80, 10], size=(n, 3))
+    R = rot_zyx(rng.uniform(-np.pi, np.pi), np.deg2rad(rng.uniform(-3, 3)), np.deg2rad(rng.uniform(-3, 3)))
+    t = _unit(rng.standard_normal(3)) * rng.uniform(0, 20)
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, t
+    tgt = src @ R.T + t + noise * rng.standard_normal((n, 3))
+    base = _unit(rng.standard_normal((n, D)))
+    d1 = _unit(base + desc_noise * rng.standard_normal((n, D)))
+    d2 = _unit(base + desc_noise * rng.standard_normal((n, D)))
+    out = rng.choice(n, size=int(round(outliers * n)), replace=False)
+    tgt[out] = rng.uniform([-80, -80, -10], [80, 80, 10], size=(len(out), 3))
+    d2[out] = _unit(rng.standard_normal((len(out), D)))
+    perm = rng.permutation(n)
+    tgt, d2 = tgt[perm], d2[perm]
+    if n2 is not None:
+        tgt, d2 = tgt[:n2], d2[:n2]
+    f32 = lambda x: np.ascontiguousarray(x, dtype=np.float32)      # noqa: E731
+    return f32(d1), f32(d2), f32(src), f32(tgt), T
+
+
+def pad_keypoint_pairs(pairs, n_max=None, D=None):
+    """list of (f1, f2, k1, k2, ...) -> padded float32 arrays (P, n_max, .) and int32 counts"""
+    n_max = n_max or max(max(len(p[0]), len(p[1])) for p in pairs)
+    D = D or pairs[0][0].shape[1]
+    P = len(pairs)
+    F1, F2 = np.zeros((P, n_max, D), np.float32), np.zeros((P, n_max, D), np.float32)
+    K1, K2 = np.zeros((P, n_max, 3), np.float32), np.zeros((P, n_max, 3), np.float32)
+    n1, n2 = np.zeros(P, np.int32), np.zeros(P, np.int32)
+    for i, p in enumerate(pairs):
+        n1[i], n2[i] = len(p[0]), len(p[1])
+        F1[i, :n1[i]], F2[i, :n2[i]], K1[i, :n1[i]], K2[i, :n2[i]] = p[0], p[1], p[2], p[3]
+    return F1, F2, K1, K2, n1, n2

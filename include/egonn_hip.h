@@ -391,6 +391,59 @@ int egonn_recall_counts(const int32_t* nn_index, const float* query_positions, c
                         int64_t n_query, int k, int position_dim, const float* radius, int n_radius,
                         int32_t* out_true_positives, void* stream);
 
+/* ------------------------------------------------------------------ 6-DoF registration of keypoint sets (local evaluation)
+ * replaces get_ransac_result (eval/evaluate.py:381-399; called by ransac_fn :296-306), calculate_repeatability (:402-411)
+ * and the RRE / RTE / success arithmetic (:245-252).  The reference hands the estimation to Open3D's
+ * registration_ransac_based_on_feature_matching, which is not part of the reference tree: its behaviour is restated from
+ * its documentation [recall] (egonn_amd/csrc/registration.hip spells out every rule, the draw function included).
+ * Two deliberate differences: all n_hypotheses hypotheses are evaluated (Open3D stops early by its 0.999 confidence rule),
+ * and a draw is a pure function of (seed, pair id, hypothesis, slot) (Open3D's generator depends on its threads), so
+ * results are bitwise reproducible, independent of the batch a pair sits in and of the launch geometry.
+ *
+ * Batched over n_pairs independent (source = query, target = candidate) pairs, padded to n_max <= 256 rows per side:
+ * feat (n_pairs, n_max, dim) f32 with dim a multiple of 4 up to 256 (16-byte aligned), kp (n_pairs, n_max, 3) f32, per-pair
+ * row counts n1 / n2 (n_pairs) DEVICE int32 (clipped to [0, n_max] on the device and reported).  No host synchronisation.
+ * pair_id (n_pairs) DEVICE int32, nullable: the id that enters the draws (null = the pair's index in the batch).  Only its
+ * low 30 bits are used (0 <= pair_id < 2^30; n_hypotheses < 2^31): ids that agree in them draw the same samples.
+ * Geometry is fp64 throughout. */
+enum { EGONN_REG_STATUS_CLIPPED = 1,      /* a count was outside [0, n_max] and was clipped */
+       EGONN_REG_STATUS_FEW_CORR = 2,     /* fewer than 3 correspondences */
+       EGONN_REG_STATUS_NO_MODEL = 4,     /* no hypothesis passed the checks with an inlier: T = identity, 0 inliers */
+       EGONN_REG_STATUS_BAD_INDEX = 8 };  /* a correspondence index outside its set (clamped) */
+/* bytes of the scratch that carries the per-workgroup bests from egonn_ransac_pairs to egonn_registration_finish
+ * (-1 on bad arguments) */
+int64_t egonn_registration_scratch_bytes(int n_pairs, int n_max, int n_hypotheses);
+/* correspondences by mutual nearest neighbours in descriptor space (fp64 squared L2 of the exactly converted fp32 inputs):
+ * j(i) = nearest target of source i, i(j) = nearest source of target j, ties: lowest index; keep (i, j(i)) iff
+ * i(j(i)) == i; fewer than 3 such pairs: every (i, j(i)).  corr (n_pairs, n_max, 2) int32 compacted in ascending i
+ * (unused rows -1), n_corr (n_pairs). */
+int egonn_match_mutual(const float* feat1, const float* feat2, const int32_t* n1, const int32_t* n2, int n_pairs, int n_max,
+                       int dim, int32_t* corr, int32_t* n_corr, void* stream);
+/* hypotheses t = 0 .. n_hypotheses-1 of every pair: 3 drawn correspondences, degeneracy / edge-length (0.8) / distance
+ * (dist_th) checks, the rigid transform of the 3 pairs (no scale, reflection corrected), then over all correspondences
+ * inlier iff |T s_i - t_j| < dist_th.  Writes each workgroup's best (inliers, sum of squared inlier distances, t) to scratch.
+ * Optional debug tables (null = not written): hyp_count (n_pairs, n_hypotheses) int32 = inliers, or -1 degenerate draw,
+ * -2 edge check, -3 distance check; hyp_err2 (n_pairs, n_hypotheses) f64 = sum of squared inlier distances. */
+int egonn_ransac_pairs(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2, const int32_t* corr,
+                       const int32_t* n_corr, const int32_t* pair_id, int n_pairs, int n_max, int n_hypotheses, uint64_t seed,
+                       double dist_th, void* scratch, int64_t scratch_bytes, int32_t* hyp_count, double* hyp_err2, void* stream);
+/* best hypothesis = most inliers, then smallest squared-distance sum (lowest rmse), then lowest t; its transform T
+ * (n_pairs,4,4) f64 row-major in the caller's coordinates; then the final evaluation, which is what the reference's
+ * len(correspondence_set) counts: every source keypoint under T whose nearest target keypoint is closer than dist_th ->
+ * inliers (n_pairs) int32, fitness = inliers / n1, inlier_rmse (f64), corr_set (n_pairs, n_max, 2) int32 (nullable; unused
+ * rows -1), best_t (nullable; -1 = none).  Same corr / pair_id / n_hypotheses / seed / dist_th / scratch as the
+ * egonn_ransac_pairs call before it.  With T_gt (n_pairs,4,4) f64 (nullable): rte = |t_est - t_gt|, rre in degrees =
+ * acos(clip((trace(R_est^T R_gt) - 1) / 2)), success = rte <= 2 and rre <= 5, repeatability = share of source keypoints with a
+ * target keypoint within repeat_th under T_gt (the transform applied in fp64; the reference applies it in fp32).  status
+ * (n_pairs) int32 of EGONN_REG_STATUS_* bits (nullable); a pair without a model is not an error of the call.
+ * corr == NULL: nothing is estimated, only repeatability under T_gt is written (calculate_repeatability on its own). */
+int egonn_registration_finish(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2, const int32_t* corr,
+                              const int32_t* n_corr, const int32_t* pair_id, int n_pairs, int n_max, int n_hypotheses,
+                              uint64_t seed, double dist_th, const void* scratch, int64_t scratch_bytes, const double* T_gt,
+                              double repeat_th, double* T, int32_t* inliers, double* fitness, double* inlier_rmse,
+                              int32_t* corr_set, int32_t* best_t, double* rte, double* rre, int32_t* success,
+                              double* repeatability, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ launch timing (bench.py roofline leg)
  * mode 0: off; 1: time every tagged sparse-conv launch (event records around it); 2: only launches whose tag contains
  * `filter`, with the events attached to the kernel dispatch itself (the kernel's own begin..end, also when other streams

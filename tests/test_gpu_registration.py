@@ -1,0 +1,368 @@
+"""GPU tests of the keypoint-set registration (run with -m gpu on an MI355X) against the float64 restatement of
+tests/test_registration_host.py: matching entry by entry, the RANSAC table hypothesis by hypothesis, the selection, the
+planted poses, determinism / batch / chunking / graph invariances, the descriptor path end to end and the argument checks.
+
+Measured difference between the device's and the restatement's transformed coordinates (test_band_measurement: the device
+returns one transform per pair and run, the winner's, so the measurement covers the winning hypothesis of every pair of
+every committed case under BAND_SEEDS different seeds; the device transform and the restatement's SVD transform of the
+same triple are applied to every source keypoint): MEASURED_COORD_DIFF below.  BAND (1e-9 m, tests/test_registration_host.py) must
+be >= 100 x that and <= 1e-6 m; the test asserts both."""
+import numpy as np
+import pytest
+import torch
+
+from tests.test_registration_host import (BAND, PLANTED_CASES, STATUS_CLIPPED, STATUS_FEW_CORR, STATUS_NO_MODEL, best_rule,
+                                          edge_pairs, final_eval, hypothesis_transform_f64, match_band, match_f64,
+                                          metrics_f64, pad_batch, planted_case, planted_pair, ransac_f64, repeatability_f64)
+
+pytestmark = pytest.mark.gpu
+
+BAND_SEEDS = 8
+MEASURED_COORD_DIFF = 5.791e-13   # metres, as printed by test_band_measurement on an MI355X (28 pairs x BAND_SEEDS = 224 winners)
+BOX_RADIUS = 114.0            # metres: farthest corner of the +-80 m x +-80 m x +-10 m box from its centre
+ROT_TOL = BAND / BOX_RADIUS   # radians: a rotation difference that moves no point of the box by more than BAND
+EXCUSED_HYP_CAP = 1e-4        # share of P x H per case
+EXCUSED_ROW_CAP = 0.01        # share of matching rows per case
+# rre goes through acos near 1: at angle a its error is eps / sin(a), and an exact identity gives sqrt(2 eps) = 1.5e-8 rad
+RRE_ATOL_DEG = 1e-5
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    import __graft_entry__ as g
+    g.build()
+    import egonn_amd
+    return egonn_amd
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _cu(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return t if dtype is None else t.to(dtype)
+
+
+def _run(gpu, pairs, H, seed=0, pids=None, n_max=None, debug=True, with_gt=True):
+    F1, F2, K1, K2, n1, n2 = pad_batch(pairs, n_max)
+    gt = np.stack([p[4] for p in pairs]) if with_gt else None
+    out = gpu.register_pairs(_cu(F1), _cu(F2), _cu(K1), _cu(K2), n1=_cu(n1), n2=_cu(n2), T_gt=None if gt is None else _cu(gt),
+                             ransac_max_it=H, seed=seed, pair_ids=None if pids is None else _cu(np.asarray(pids, np.int32)),
+                             debug=debug)
+    torch.cuda.synchronize()
+    return {k: _np(v) for k, v in out.items() if k != "_keep"}
+
+
+_CACHE = {}
+
+
+def _case(gpu, name):
+    """device outputs of a planted case + the restatement's table of every pair on the device's correspondences"""
+    if name not in _CACHE:
+        pairs, H = planted_case(name), PLANTED_CASES[name]["H"]
+        out = _run(gpu, pairs, H)
+        tabs = [ransac_f64(p[2], p[3], out["corr"][i, :out["n_corr"][i]], 0, i, H) for i, p in enumerate(pairs)]
+        _CACHE[name] = (pairs, H, out, tabs)
+    return _CACHE[name]
+
+
+def _check_matching(pairs, corr, n_corr):
+    """-> excused rows, rows, unchecked pairs.  Rows whose best and second-best float64 squared distances lie within match_band
+    may pick either; a pair is unchecked when such a row put the device and the restatement on different sides of the
+    fewer-than-3 fallback (the sets then differ wholesale).  Callers assert or print the last figure: it must not hide."""
+    excused = total = unchecked = 0
+    for i, p in enumerate(pairs):
+        want, g1, g2 = match_f64(p[0], p[1])
+        band = match_band(p[0], p[1])
+        # a gap of exactly 0 is a tie of duplicated descriptors: identical bits on both sides, the lowest-index rule decides
+        e1, e2 = np.nonzero((g1 > 0) & (g1 < band))[0], np.nonzero((g2 > 0) & (g2 < band))[0]
+        excused += len(e1) + len(e2)
+        total += len(g1) + len(g2)
+        got = corr[i, :n_corr[i]]
+        assert (corr[i, n_corr[i]:] == -1).all()
+        if len(e1) + len(e2) == 0:
+            assert n_corr[i] == len(want) and np.array_equal(got, want), i
+        else:       # entries that touch no excused row must agree (the < 3 fallback may flip with an excused row)
+            skip = lambda c: np.isin(c[:, 0], e1) | np.isin(c[:, 1], e2)       # noqa: E731
+            a, b = got[~skip(got)], want[~skip(want)]
+            # all-rows output = the fewer-than-3 fallback (or every row mutual); on different sides nothing can be compared
+            if (n_corr[i] == len(p[0])) != (len(want) == len(p[0])):
+                unchecked += 1
+            else:
+                assert np.array_equal(a, b), i
+                # an excused row changes at most its own entry and the entry of the row it displaces
+                assert abs(int(n_corr[i]) - len(want)) <= 2 * (len(e1) + len(e2)), i
+    return excused, total, unchecked
+
+
+def _check_table(name, out, tabs, H):
+    """hyp_count equal and hyp_err2 close for every hypothesis the restatement does not mark near a decision"""
+    excused = 0
+    for i, tab in enumerate(tabs):
+        ok = ~tab["near"]
+        excused += int(tab["near"].sum())
+        bad = np.nonzero(ok & (out["hyp_count"][i] != tab["count"]))[0]
+        assert len(bad) == 0, (name, i, bad[:8], out["hyp_count"][i][bad[:8]], tab["count"][bad[:8]])
+        # each inlier's d^2 moves by at most 2 * 0.5 * BAND when the transformed point moves by BAND
+        tol = np.maximum(tab["count"], 0) * BAND + 1e-12 * tab["err2"]
+        assert (np.abs(out["hyp_err2"][i] - tab["err2"])[ok] <= tol[ok]).all(), (name, i)
+    share = excused / (len(tabs) * H)
+    print(f"[registration] {name}: excused hypotheses {excused} of {len(tabs) * H} ({share:.2e})")
+    assert share <= EXCUSED_HYP_CAP
+    return excused
+
+
+def _check_selection(pairs, out, tabs):
+    for i, (p, tab) in enumerate(zip(pairs, tabs)):
+        bt = best_rule(out["hyp_count"][i], out["hyp_err2"][i])          # of the DEVICE's own table: exact
+        assert out["best_t"][i] == bt, i
+        T = out["T"][i]
+        assert np.array_equal(T[3], [0, 0, 0, 1])
+        if bt < 0:
+            assert np.array_equal(T, np.eye(4)) and out["inliers"][i] == 0 and out["fitness"][i] == 0 and out["inlier_rmse"][i] == 0
+            assert out["status"][i] & STATUS_NO_MODEL and (out["correspondence_set"][i] == -1).all()
+            continue
+        assert not out["status"][i] & STATUS_NO_MODEL
+        if not tab["near"][bt]:
+            assert np.linalg.norm(T[:3, :3] - tab["R"][bt]) / np.sqrt(2) <= ROT_TOL, i       # = the angle, for small angles
+            assert np.abs(T[:3, 3] - tab["t"][bt]).max() <= BAND, i
+        assert abs(np.linalg.det(T[:3, :3]) - 1) < 1e-12
+        # the final evaluation, restated at the device's T
+        a = p[2].astype(np.float64) @ T[:3, :3].T + T[:3, 3]
+        d = np.sqrt(((a[:, None] - p[3].astype(np.float64)[None]) ** 2).sum(-1).min(1)) if len(p[3]) else np.ones(len(a))
+        if len(a) and np.abs(d - 0.5).min() <= BAND:
+            continue                                                      # a keypoint on the threshold: either count is right
+        inl, fit, rmse, cset = final_eval(p[2], p[3], T)
+        assert out["inliers"][i] == inl and out["fitness"][i] == fit, i
+        assert abs(out["inlier_rmse"][i] - rmse) <= 1e-9 * max(rmse, 1e-3)
+        assert np.array_equal(out["correspondence_set"][i, :inl], cset) and (out["correspondence_set"][i, inl:] == -1).all()
+
+
+def _check_metrics(pairs, out):
+    for i, p in enumerate(pairs):
+        rte, rre, suc = metrics_f64(out["T"][i], p[4])
+        assert abs(out["rte"][i] - rte) <= 1e-9 and abs(out["rre"][i] - rre) <= RRE_ATOL_DEG, i
+        if abs(rte - 2.0) > 1e-9 and abs(rre - 5.0) > RRE_ATOL_DEG:
+            assert out["success"][i] == suc
+        assert abs(out["repeatability"][i] - repeatability_f64(p[2], p[3], p[4], 0.5)) <= 1e-12, i
+
+
+# ------------------------------------------------------------------ 1. matching
+@pytest.mark.parametrize("name", list(PLANTED_CASES))
+def test_matching_equals_restatement(gpu, name):
+    pairs = planted_case(name)
+    F1, F2, _, _, n1, n2 = pad_batch(pairs)
+    corr, n_corr = gpu.match_mutual(_cu(F1), _cu(F2), _cu(n1), _cu(n2))
+    assert corr.dtype == torch.int32 and n_corr.dtype == torch.int32
+    excused, total, unchecked = _check_matching(pairs, _np(corr), _np(n_corr))
+    print(f"[registration] {name}: excused matching rows {excused} of {total}, unchecked pairs {unchecked}")
+    assert excused <= EXCUSED_ROW_CAP * total and unchecked == 0
+
+
+# ------------------------------------------------------------------ 2. per-hypothesis parity, and the band it rests on
+def test_band_measurement(gpu):
+    worst, n = 0.0, 0
+    for name in PLANTED_CASES:
+        pairs, H = planted_case(name), PLANTED_CASES[name]["H"]
+        for seed in range(BAND_SEEDS):
+            out = _case(gpu, name)[2] if seed == 0 else _run(gpu, pairs, H, seed=seed, debug=False)
+            for i, p in enumerate(pairs):
+                bt = int(out["best_t"][i])
+                assert bt >= 0
+                R, t = hypothesis_transform_f64(p[2], p[3], out["corr"][i, :out["n_corr"][i]], seed, i, bt)
+                s = p[2].astype(np.float64)
+                dev = s @ out["T"][i][:3, :3].T + out["T"][i][:3, 3]
+                worst = max(worst, float(np.abs(dev - (s @ R.T + t)).max()))
+                n += 1
+    print(f"[registration] largest device-vs-restatement transformed-coordinate difference over {n} winning hypotheses: "
+          f"{worst:.3e} m")
+    assert 100 * worst <= BAND <= 1e-6
+    assert 100 * MEASURED_COORD_DIFF <= BAND
+
+
+@pytest.mark.parametrize("name", list(PLANTED_CASES))
+def test_every_hypothesis_equals_restatement(gpu, name):
+    pairs, H, out, tabs = _case(gpu, name)
+    assert out["hyp_count"].shape == (len(pairs), H) and out["hyp_err2"].dtype == np.float64
+    _check_table(name, out, tabs, H)
+    assert (out["hyp_count"] >= 3).any() and (out["hyp_count"] == -2).any() and (out["hyp_count"] == -3).any()
+
+
+# ------------------------------------------------------------------ 3. selection and final evaluation
+@pytest.mark.parametrize("name", list(PLANTED_CASES))
+def test_selection_and_final_evaluation(gpu, name):
+    pairs, H, out, tabs = _case(gpu, name)
+    _check_selection(pairs, out, tabs)
+
+
+# ------------------------------------------------------------------ 4. planted poses
+@pytest.mark.parametrize("name", list(PLANTED_CASES))
+def test_planted_poses_are_recovered(gpu, name):
+    pairs, H, out, tabs = _case(gpu, name)
+    assert (out["status"] == 0).all()
+    assert (out["success"] == 1).all() and (out["rte"] <= 2.0).all() and (out["rre"] <= 5.0).all(), (out["rte"], out["rre"])
+    _check_metrics(pairs, out)
+
+
+def test_edge_cases(gpu):
+    E = edge_pairs()
+    names = list(E)
+    pairs = [E[k] for k in names]
+    H = 2000
+    out = _run(gpu, pairs, H, n_max=128)
+    excused, _, unchecked = _check_matching(pairs, out["corr"], out["n_corr"])
+    assert excused == 0 and unchecked == 0
+    tabs = [ransac_f64(p[2], p[3], out["corr"][i, :out["n_corr"][i]], 0, i, H) for i, p in enumerate(pairs)]
+    _check_table("edge cases", out, tabs, H)
+    _check_selection(pairs, out, tabs)
+    _check_metrics(pairs, out)
+    st = dict(zip(names, out["status"].tolist()))
+    for m in (0, 1, 2):
+        assert st[f"n_corr_{m}"] == STATUS_FEW_CORR | STATUS_NO_MODEL and out["n_corr"][names.index(f"n_corr_{m}")] == m
+    assert st["n_corr_3"] == 0 and out["success"][names.index("n_corr_3")] == 1
+    for k in ("identical_keypoints", "collinear", "no_accepted_hypothesis"):
+        assert st[k] == STATUS_NO_MODEL
+    assert st["n1_ne_n2"] == 0 and st["duplicate_descriptors"] == 0
+    # counts outside [0, n_max] are clipped on the device and reported
+    F1, F2, K1, K2, n1, n2 = pad_batch(pairs[-2:], 128)
+    big = gpu.register_pairs(_cu(F1), _cu(F2), _cu(K1), _cu(K2), n1=_cu(np.array([1000, -4], np.int32)), n2=_cu(n2),
+                             ransac_max_it=500)
+    torch.cuda.synchronize()
+    assert (_np(big["status"]) & STATUS_CLIPPED).all() and _np(big["n_corr"])[1] == 0 and np.isfinite(_np(big["T"])).all()
+
+
+# ------------------------------------------------------------------ 5. determinism and invariances
+def test_determinism_and_invariances(gpu):
+    pairs = [planted_pair(128, 700 + i, 0.2 + 0.05 * (i % 7)) for i in range(64)]
+    H = 2000
+    keys = ("T", "inliers", "fitness", "inlier_rmse", "correspondence_set", "best_t", "status", "corr", "n_corr", "rte", "rre",
+            "success", "repeatability", "hyp_count", "hyp_err2")
+    a, b = _run(gpu, pairs, H), _run(gpu, pairs, H)
+    for k in keys:
+        assert np.array_equal(a[k], b[k]), k                               # bitwise-equal reruns
+    # a pair alone equals the pair inside the batch of 64 (the draws take the pair's id, not its position)
+    for i in (0, 17, 63):
+        one = _run(gpu, [pairs[i]], H, pids=[i])
+        for k in keys:
+            assert np.array_equal(one[k][0], a[k][i]), (k, i)
+    # another chunking of the hypotheses (grid of 4 instead of 8 workgroups per pair): the same prefix table
+    half = _run(gpu, pairs[:8], H // 2)
+    assert np.array_equal(half["hyp_count"], a["hyp_count"][:8, :H // 2])
+    assert np.array_equal(half["hyp_err2"], a["hyp_err2"][:8, :H // 2])
+    # H not a multiple of the workgroup: the tail lanes stay out of the table and of the selection
+    odd = _run(gpu, pairs[:8], 777)
+    assert np.array_equal(odd["hyp_count"], a["hyp_count"][:8, :777])
+    assert [best_rule(c, e) for c, e in zip(odd["hyp_count"], odd["hyp_err2"])] == odd["best_t"].tolist()
+    # another seed: another table
+    other = _run(gpu, pairs[:8], H, seed=1)
+    assert (other["hyp_count"] != a["hyp_count"][:8]).mean() > 0.2
+    # replay inside a captured graph (one stream, no parallel branches) equals the eager result
+    F1, F2, K1, K2, n1, n2 = (_cu(x) for x in pad_batch(pairs))
+    gt = _cu(np.stack([p[4] for p in pairs]))
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = gpu.register_pairs(F1, F2, K1, K2, n1=n1, n2=n2, T_gt=gt, ransac_max_it=H, debug=True)
+    for k in keys:
+        out[k].zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    for k in keys:
+        assert np.array_equal(_np(out[k]), a[k]), k
+
+
+# ------------------------------------------------------------------ 6. end to end behind the descriptor path
+def test_end_to_end_from_scans(gpu):
+    from egonn_amd.synth import lidar_scan, seeded_state_dict
+    from tests.test_registration_host import rot_zyx
+    mp = gpu.ModelParams(model="egonn", coordinates="cartesian", quantization_step=0.1)
+    model = gpu.model_factory(mp)
+    sd = seeded_state_dict(7, {k: tuple(v.shape) for k, v in model.state_dict().items()})
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    model = model.to("cuda:0").eval()
+    pc = lidar_scan(2, n_points=20000).astype(np.float64)
+    T_gt = np.eye(4)
+    T_gt[:3, :3], T_gt[:3, 3] = rot_zyx(np.deg2rad(10.0), 0.0, 0.0), [2.0, 1.0, 0.0]
+    pc2 = pc @ T_gt[:3, :3].T + T_gt[:3, 3]
+    ex = gpu.DescriptorExtractor(model, n_k=128)
+    y = ex.extract([torch.from_numpy(pc.astype(np.float32)), torch.from_numpy(pc2.astype(np.float32))])
+    kp, desc, cnt = y["keypoints"], y["descriptors"], y["count"].to(torch.int32)
+    H = 4000
+    out = gpu.register_pairs(desc[0:1], desc[1:2], kp[0:1], kp[1:2], n1=cnt[0:1], n2=cnt[1:2], T_gt=_cu(T_gt[None]),
+                             ransac_max_it=H, debug=True)
+    torch.cuda.synchronize()
+    assert out["T"].shape == (1, 4, 4) and out["T"].dtype == torch.float64 and out["inliers"].dtype == torch.int32
+    assert out["fitness"].dtype == torch.float64 and out["correspondence_set"].shape == (1, 128, 2)
+    assert out["hyp_count"].shape == (1, H) and out["success"].dtype == torch.int32
+    o = {k: _np(v) for k, v in out.items() if k != "_keep"}
+    for k in ("T", "fitness", "inlier_rmse", "rte", "rre", "repeatability", "hyp_err2"):
+        assert np.isfinite(o[k]).all(), k
+    assert not o["status"][0] & (STATUS_CLIPPED | STATUS_FEW_CORR)
+    n1, n2 = int(cnt[0]), int(cnt[1])
+    pair = (_np(desc[0])[:n1], _np(desc[1])[:n2], _np(kp[0])[:n1], _np(kp[1])[:n2], T_gt)
+    excused, total, unchecked = _check_matching([pair], o["corr"], o["n_corr"])
+    print(f"[registration] end to end: excused matching rows {excused} of {total}, unchecked pairs {unchecked}")
+    tabs = [ransac_f64(pair[2], pair[3], o["corr"][0, :o["n_corr"][0]], 0, 0, H)]
+    _check_table("end to end", o, tabs, H)
+    _check_selection([pair], o, tabs)
+    _check_metrics([pair], o)
+    print(f"[registration] end to end (seeded weights): n_corr {o['n_corr'][0]}, inliers {o['inliers'][0]}, "
+          f"rte {o['rte'][0]:.3f} m, rre {o['rre'][0]:.3f} deg, repeatability {o['repeatability'][0]:.3f}")
+    # the one-pair surface with the reference's names gives the same answer
+    r = gpu.get_ransac_result(desc[0, :n1], desc[1, :n2], kp[0, :n1], kp[1, :n2], ransac_max_it=H)
+    assert np.array_equal(r.transformation, o["T"][0]) and len(r.correspondence_set) == o["inliers"][0]
+    assert r.fitness == o["fitness"][0] and r.inlier_rmse == o["inlier_rmse"][0]
+    assert gpu.calculate_repeatability(kp[0, :n1], kp[1, :n2], T_gt, 0.5) == o["repeatability"][0]
+
+
+def test_evaluate_local_bookkeeping(gpu):
+    """evaluate_local against the same bookkeeping done by hand on register_pairs' outputs; the 20 m gate drops a query"""
+    pairs = planted_case("n128_out30")
+    q = [{"keypoints": torch.from_numpy(p[2]), "features": torch.from_numpy(p[0])} for p in pairs]
+    m = [{"keypoints": torch.from_numpy(p[3]), "features": torch.from_numpy(p[1])} for p in pairs][::-1]
+    nn = np.arange(len(pairs))[::-1].copy()[:, None]
+    gt = np.stack([p[4] for p in pairs])
+    gt[1, :3, 3] += 10.0                                                   # one failure by construction
+    dist = np.full((len(pairs), 1), 5.0)
+    dist[2] = 25.0                                                         # beyond the 20 m gate: skipped
+    res = gpu.evaluate_local(q, m, nn, gt, n_k=(128, 64), euclid_dist=dist, ransac_max_it=3000)
+    assert set(res) == {128, 64}
+    keep = [i for i in range(len(pairs)) if i != 2]
+    out = _run(gpu, [pairs[i][:4] + (gt[i],) for i in keep], 3000, pids=keep)
+    suc = out["success"].astype(bool)
+    r = res[128]
+    assert suc.sum() == len(keep) - 1 and r["success"] == suc.mean()
+    assert r["rte"] == out["rte"][suc].mean() and r["rre"] == out["rre"][suc].mean()
+    assert r["success_inliers"] == out["inliers"][suc].mean() and r["failure_inliers"] == out["inliers"][~suc].mean()
+    assert r["repeatability"] == out["repeatability"].mean() == r["repeatability_refined"]
+    # one batched device measurement divided by the pairs: a positive time, and by definition no per-pair spread
+    assert r["t_ransac"] > 0 and r["t_ransac_sd"] == 0.0
+    assert 0.0 <= res[64]["success"] <= 1.0 and set(res[64]) == set(r)
+
+
+# ------------------------------------------------------------------ 7. argument checks
+def test_argument_checks(gpu):
+    from egonn_amd._lib import EgonnError, load
+    z = lambda *s: torch.zeros(s, device="cuda")                           # noqa: E731
+    for f, k, kw in ((z(1, 257, 128), z(1, 257, 3), {}), (z(1, 64, 30), z(1, 64, 3), {}),
+                     (z(1, 64, 128), z(1, 64, 3), {"ransac_max_it": 0}), (z(1, 64, 128), z(1, 64, 3), {"ransac_max_it": -7})):
+        with pytest.raises(EgonnError) as e:
+            gpu.register_pairs(f, f, k, k, **kw)
+        assert e.value.code == 1                                           # EGONN_STATUS_INVALID, nothing launched
+    lib = load()
+    f, k, n = z(1, 64, 128), z(1, 64, 3), torch.zeros(1, dtype=torch.int32, device="cuda")
+    c = torch.zeros((1, 64, 2), dtype=torch.int32, device="cuda")
+    s = torch.zeros(64, dtype=torch.int64, device="cuda")
+    P = lambda t: t.data_ptr()                                             # noqa: E731
+    assert lib.egonn_match_mutual(P(f), None, P(n), P(n), 1, 64, 128, P(c), P(n), None) == 1
+    assert lib.egonn_match_mutual(P(f), P(f), P(n), P(n), 1, 64, 128, None, P(n), None) == 1
+    assert lib.egonn_ransac_pairs(P(k), P(k), P(n), P(n), None, P(n), None, 1, 64, 100, 0, 0.5, P(s), 512, None, None, None) == 1
+    assert lib.egonn_ransac_pairs(P(k), P(k), P(n), P(n), P(c), P(n), None, 1, 64, 100, 0, 0.5, None, 512, None, None, None) == 1
+    assert lib.egonn_ransac_pairs(P(k), P(k), P(n), P(n), P(c), P(n), None, 1, 64, 10000, 0, 0.5, P(s), 512, None, None, None) == 1
+    assert lib.egonn_registration_finish(P(k), P(k), P(n), P(n), P(c), P(n), None, 1, 64, 100, 0, 0.5, P(s), 512, None, 0.5, None,
+                                         P(n), P(s), P(s), None, None, None, None, None, None, None, None) == 1
+    assert lib.egonn_registration_finish(P(k), P(k), P(n), P(n), None, None, None, 1, 64, 0, 0, 0.5, None, 0, None, 0.5, None,
+                                         None, None, None, None, None, None, None, None, None, None, None) == 1
+    torch.cuda.synchronize()
