@@ -129,7 +129,7 @@ size_t ingest_scratch_ints(int64_t n) { return (size_t)cdiv(n, ING_BLOCK) + 2; }
 int ingest_filter(const float* raw, int64_t n, int stride, const int64_t* raw_off_dev, int batch, int remove_zero,
                   int remove_ground, float ground, float* out_xyz, int64_t* new_off_dev, int32_t* scratch,
                   size_t scratch_ints, hipStream_t stream) {
-  EGONN_REQUIRE(raw && out_xyz && raw_off_dev && new_off_dev && scratch && n >= 0 && n < (1ll << 31) && batch >= 1 &&
+  EGONN_REQUIRE((raw || n == 0) && out_xyz && raw_off_dev && new_off_dev && scratch && n >= 0 && n < (1ll << 31) && batch >= 1 &&
                     (stride == 3 || stride == 4),
                 EGONN_ERR_INVALID, "ingest: bad arguments (n=%lld stride=%d)", (long long)n, stride);
   const int64_t nblk = cdiv(n, ING_BLOCK);

@@ -5,6 +5,9 @@
 // knn_dist_kernel: one workgroup per query, one wave per database row at a time (a 256-float row is one
 // float4 per lane), exact difference form (not the |a|^2+|b|^2-2ab expansion) like the reference.
 // knn_select_kernel: k rounds of a workgroup-wide arg-min over the query's distance row (ties: lower index).
+// Non-finite distances: +inf (an overflowing or infinite element) is a distance like any other, after every finite one
+// and in index order; a NaN distance is never a neighbour, the list then ends early with (-1, +inf).  A taken entry is
+// marked NaN, which no comparison selects, so that a genuine +inf is returned once and only once.
 #include "common.h"
 #include "kernels.h"
 
@@ -65,10 +68,10 @@ __global__ __launch_bounds__(256) void knn_select_kernel(float* __restrict__ dis
           s_v[0] = s_v[j];
           s_i[0] = s_i[j];
         }
-      const bool ok = s_i[0] != 0x7fffffff && round < m;
+      const bool ok = s_i[0] != 0x7fffffff;       // nothing left to take: every entry taken (round >= m) or NaN
       out_idx[(int64_t)q * k + round] = ok ? s_i[0] : -1;
       out_dist[(int64_t)q * k + round] = ok ? s_v[0] : INFINITY;
-      if (ok) row[s_i[0]] = INFINITY;             // taken
+      if (ok) row[s_i[0]] = NAN;                  // taken: never compares below or equal to anything
     }
     __syncthreads();
   }
@@ -111,8 +114,8 @@ __global__ void recall_kernel(const int32_t* __restrict__ nn_idx, const float* _
 
 int recall_counts(const int32_t* nn_idx, const float* qpos, const float* mpos, int32_t nq, int k, int pd,
                   const float* radius, int nr, int32_t* tp, hipStream_t stream) {
-  EGONN_REQUIRE(nn_idx && qpos && mpos && radius && tp && k >= 1 && nr >= 1 && pd >= 1, EGONN_ERR_INVALID,
-                "recall: bad arguments");
+  EGONN_REQUIRE(radius && tp && k >= 1 && nr >= 1 && pd >= 1 && nq >= 0 && (nq == 0 || (nn_idx && qpos && mpos)),
+                EGONN_ERR_INVALID, "recall: bad arguments");       // an empty query set has no buffers to point at
   HIP_CHECK(hipMemsetAsync(tp, 0, (size_t)nr * k * 4, stream));
   if (nq == 0) return EGONN_OK;
   hipLaunchKernelGGL(recall_kernel, dim3((unsigned)cdiv(nq, 128)), dim3(128), 0, stream, nn_idx, qpos, mpos, nq, k, pd,

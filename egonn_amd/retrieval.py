@@ -11,7 +11,8 @@ from . import _lib
 
 
 def knn(query: torch.Tensor, database: torch.Tensor, k: int, chunk: int = 4096):
-    """(Q,D), (M,D) -> indices (Q,k) int32 ascending by L2 distance (ties: lower index), distances (Q,k)."""
+    """(Q,D), (M,D) -> indices (Q,k) int32 ascending by L2 distance (ties: lower index), distances (Q,k); -1 / inf beyond
+    M.  +inf distances come after every finite one; a NaN distance is never a neighbour (the list then ends early)."""
     dev = _lib.require_gpu() if not query.is_cuda else query.device
     lib = _lib.load()
     q = query.to(device=dev, dtype=torch.float32).contiguous()

@@ -370,9 +370,10 @@ int egonn_gem_backward(egonn_ctx* ctx, int level, const float* x, const float* c
  * [scan_offsets[b], scan_offsets[b+1]), DEVICE int64, batch_size+1 entries); drops all-zero points (|v| <= 1e-8) and
  * points with z <= ground_plane_level; survivors keep their order.  out_points (n,3) f32 (first out_scan_offsets[B]
  * rows valid), out_scan_offsets (batch_size+1) DEVICE int64.  scratch: egonn_filter_points_scratch_ints(n) int32.
- * n is a CAPACITY (>= scan_offsets[batch_size]; rows beyond scan_offsets[batch_size] are never read), so that a fixed-size
- * launch sequence serves every batch (hipGraph capture).  No host sync: out_scan_offsets can be handed to
- * egonn_voxelize_device as they are (egonn_amd/stream.py), or copied back for egonn_voxelize. */
+ * n is a CAPACITY (>= scan_offsets[batch_size]; rows beyond scan_offsets[batch_size] are never read; with n == 0 raw
+ * may be NULL), so that a fixed-size launch sequence serves every batch (hipGraph capture).  No host sync:
+ * out_scan_offsets can be handed to egonn_voxelize_device as they are (egonn_amd/stream.py), or copied back for
+ * egonn_voxelize. */
 int64_t egonn_filter_points_scratch_ints(int64_t n);
 int egonn_filter_points(const float* raw, int64_t n, int floats_per_point, const int64_t* scan_offsets, int batch_size,
                         int remove_zero_points, int remove_ground_plane, float ground_plane_level, float* out_points,
@@ -382,7 +383,8 @@ int egonn_filter_points(const float* raw, int64_t n, int floats_per_point, const
  * replaces the per-query NumPy search of Evaluator.evaluate, eval/evaluate.py:80-82 and :175-176:
  *   embed_dist = np.linalg.norm(map_embeddings - query_embedding, axis=1);  nn_ndx = np.argsort(embed_dist)[:k]
  * out_index (n_query,k) int32 ascending by distance (ties: lower index; -1 beyond n_database), out_distance (n_query,k).
- * scratch >= n_query*n_database floats. */
+ * +inf distances (an infinite or overflowing element) sort after every finite one, in index order; a NaN distance is never
+ * a neighbour: such rows are left out and the list ends with (-1, +inf).  scratch >= n_query*n_database floats. */
 int egonn_knn(const float* query, int64_t n_query, const float* database, int64_t n_database, int dim, int k,
               int32_t* out_index, float* out_distance, float* scratch, int64_t scratch_floats, void* stream);
 /* eval/evaluate.py:84-88 / :181-184: out_true_positives (n_radius,k) int32, [r][nn] = number of queries with a

@@ -365,14 +365,23 @@ class MinkLocOracle:
 
 
 # ----------------------------------------------------------------------------- batch-hard triplet loss
+def pdist64(emb, block=32):
+    """(n, n) float64 L2 distances in the difference form, row blocks at a time (n = 1024, d = 256 stays small)."""
+    e = np.asarray(emb, dtype=np.float64)
+    D = np.empty((len(e), len(e)))
+    for lo in range(0, len(e), block):
+        diff = e[lo:lo + block, None, :] - e[None, :, :]
+        D[lo:lo + block] = np.sqrt(np.einsum("ijd,ijd->ij", diff, diff))
+    return D
+
+
 def batch_hard_triplet_loss(emb: np.ndarray, pos_mask: np.ndarray, neg_mask: np.ndarray, margin: float):
     """reference models/loss.py:114-172 — miner (in-tree: get_max_per_row / get_min_per_row :132-143) + the
     pytorch_metric_learning pieces it calls, restated per SURVEY.md Appendix A.9 (parity unpinned for those):
     LpDistance(p=2), TripletMarginLoss(margin, swap=True), AvgNonZeroReducer.  Returns (loss, stats, (a, p, n))."""
     e = np.asarray(emb, dtype=np.float64)
     n = len(e)
-    diff = e[:, None, :] - e[None, :, :]
-    D = np.sqrt((diff * diff).sum(-1))
+    D = pdist64(e)
     pm, nm = np.asarray(pos_mask, bool), np.asarray(neg_mask, bool)
     mp = np.where(pm, D, 0.0)
     mn = np.where(nm, D, np.inf)
@@ -391,3 +400,148 @@ def batch_hard_triplet_loss(emb: np.ndarray, pos_mask: np.ndarray, neg_mask: np.
              "min_pos_pair_dist": float(hp.min()), "mean_neg_pair_dist": float(hn.mean()),
              "max_neg_pair_dist": float(hn.max()), "min_neg_pair_dist": float(hn.min())}
     return loss, stats, (a, p, q)
+
+
+U32 = 2.0 ** -24                                                                # unit roundoff of fp32
+
+
+def triplet_tol(d):
+    """Relative error bound of one fp32 entry of pdist_kernel (egonn_amd/csrc/loss.hip), first order in u = 2^-24:
+    ei[c] - ej[c] rounds once (2u on its square), ONE thread chains d fmaf on non-negative terms (d u), sqrtf halves
+    the sum and rounds once: ((d + 2) / 2 + 1) u = (d / 2 + 2) u;  7.7e-6 at d = 256."""
+    return (d / 2.0 + 2.0) * U32
+
+
+def triplet_gaps(emb, pos_mask, neg_mask, margin, allow_ties=False):
+    """How far the inputs are from every decision fp32 could flip, each as a multiple of its floor (> 1 = fp32 cannot
+    flip it), over the anchors that are kept, with t = triplet_tol(d) and D in float64:
+      pos   hardest vs second-hardest positive of a row:  (D1 - D2) / (2 t D1)
+      neg   hardest vs second-hardest negative:           (D2 - D1) / (2 t D2)
+      kink  |d_ap - d_an + margin| / (2 t (d_ap + d_an + margin))       (relu, and the l > 0 filter of the gradient)
+      swap  |D[a][n] - D[p][n]| / (2 t max of the two)                   (swap=True picks the smaller)
+    allow_ties: gaps that are exactly 0 (duplicated rows, integer data) are left out: there the first-index rule
+    decides, not the arithmetic.  Also returns the shares of active triplets and of swapped ones."""
+    e = np.asarray(emb, np.float64)
+    t = triplet_tol(e.shape[1])
+    D = pdist64(e)
+    pm, nm = np.asarray(pos_mask, bool), np.asarray(neg_mask, bool)
+    keep = pm.any(1) & nm.any(1)
+    out = {"pos": np.inf, "neg": np.inf, "kink": np.inf, "swap": np.inf, "active": 0.0, "swapped": 0.0,
+           "triplets": int(keep.sum())}
+    if not keep.any():
+        return out
+
+    def ratio(gap, floor):
+        gap, floor = np.asarray(gap), np.asarray(floor)
+        sel = gap > 0 if allow_ties else np.ones(gap.shape, bool)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = gap[sel] / floor[sel]
+        return float(np.nan_to_num(r, nan=0.0).min(initial=np.inf))
+
+    rows = keep & (pm.sum(1) >= 2)
+    if rows.any():
+        top = -np.sort(-np.where(pm, D, -np.inf)[rows], axis=1)[:, :2]               # two largest positives
+        out["pos"] = ratio(top[:, 0] - top[:, 1], 2 * t * top[:, 0])
+    rows = keep & (nm.sum(1) >= 2)
+    if rows.any():
+        low = np.sort(np.where(nm, D, np.inf)[rows], axis=1)[:, :2]                  # two smallest negatives
+        out["neg"] = ratio(low[:, 1] - low[:, 0], 2 * t * low[:, 1])
+    a = np.flatnonzero(keep)
+    p, q = np.where(pm, D, 0.0).argmax(1)[a], np.where(nm, D, np.inf).argmin(1)[a]
+    d_ap, d_an = D[a, p], np.minimum(D[a, q], D[p, q])
+    l = d_ap - d_an + margin
+    out["kink"] = float((np.abs(l) / (2 * t * (d_ap + d_an + margin))).min())
+    out["swap"] = ratio(np.abs(D[a, q] - D[p, q]), 2 * t * np.maximum(D[a, q], D[p, q]))
+    out["active"] = float((l > 0).mean())
+    out["swapped"] = float((D[p, q] < D[a, q]).mean())
+    return out
+
+
+def triplet_grad(emb, D, a, p, q, margin, dtype=np.float64):
+    """dLoss/dE of the batch-hard loss for given triplets, in `dtype`, with the conventions of triplet_grad_kernel: only
+    l > 0 triplets, weight 1 / num_non_zero, the negative distance is d(x, n) with x = p where D[p][n] < D[a][n] and
+    x = a otherwise (ties: the anchor), and a zero distance contributes nothing.  Returns (grad, S, T): S[r][c] = sum of
+    the |terms| that land on grad[r][c] and T[r] = their number (for the error bound of the fp32 kernel)."""
+    e, D = np.asarray(emb, dtype), np.asarray(D, dtype)
+    n, d = e.shape
+    grad, S, T = np.zeros((n, d), dtype), np.zeros((n, d), np.float64), np.zeros(n, np.int64)
+    a, p, q = (np.asarray(v, np.int64) for v in (a, p, q))
+    if len(a) == 0:
+        return grad, S, T
+    li = np.maximum(D[a, p] - np.minimum(D[a, q], D[p, q]) + dtype(margin), dtype(0))
+    act = li > 0
+    if not act.any():
+        return grad, S, T
+    a, p, q = a[act], p[act], q[act]
+    w = dtype(1) / dtype(act.sum())
+    x = np.where(D[p, q] < D[a, q], p, a)
+    for rows_plus, rows_minus, dist, diff in ((a, p, D[a, p], e[a] - e[p]), (q, x, D[x, q], e[x] - e[q])):
+        ok = dist > 0
+        term = (w * diff[ok] / dist[ok][:, None]).astype(dtype)
+        np.add.at(grad, rows_plus[ok], term)
+        np.add.at(grad, rows_minus[ok], -term)
+        for rows in (rows_plus[ok], rows_minus[ok]):
+            np.add.at(S, rows, np.abs(term).astype(np.float64))
+            np.add.at(T, rows, 1)
+    return grad, S, T
+
+
+def triplet_bounds(emb, pos_mask, neg_mask, margin):
+    """float64 reference of everything egonn_triplet_loss returns, with the absolute error allowed to the fp32 kernel
+    for each quantity, derived from t = triplet_tol(d), u = 2^-24 and the kernel's fixed summation orders
+    (s = ceil(n / 256) + 8 + 1: a thread's strided partial sum, the 8-level tree, one division):
+      loss         (t + 4u) max(d_ap + d_an + margin) + s u loss       each l_i: two D entries, two roundings; mean of l_i
+      mean_*_dist  (t + s u) mean          max_* / min_*: t value      avg_embedding_norm: (t + s u) value
+      grad[r][c]   (t + (T[r] + 4) u) S[r][c]   every term w * (e_x - e_y) / D: one D entry, three roundings, then T[r]
+                   sequential additions; S = sum of |terms| (triplet_grad); capped by 1e-6 + 1e-3 |grad|, the bound of
+                   the older test, which cancellation between terms at d >= 1000 could otherwise exceed
+    Returns (loss, stats, (a, p, n), grad, tol) with tol = {'loss', each stats key, 'grad' (n, d)}."""
+    e = np.asarray(emb, np.float64)
+    n, d = e.shape
+    t = triplet_tol(d)
+    s = -(-n // 256) + 9
+    loss, stats, (a, p, q) = batch_hard_triplet_loss(e, pos_mask, neg_mask, margin)
+    D = pdist64(e)
+    grad, S, T = triplet_grad(e, D, a, p, q, margin)
+    tol = {}
+    dsum = (D[a, p] + np.minimum(D[a, q], D[p, q]) + margin).max(initial=0.0)
+    tol["loss"] = (t + 4 * U32) * dsum + s * U32 * loss
+    for k, v in stats.items():
+        if k.startswith("mean_") or k == "avg_embedding_norm":
+            tol[k] = (t + s * U32) * abs(v) if np.isfinite(v) else 0.0
+        elif k.startswith(("max_", "min_")):
+            tol[k] = t * abs(v) if np.isfinite(v) else 0.0
+        else:
+            tol[k] = 0.0 if k != "loss" else tol["loss"]
+    tol["grad"] = np.minimum((t + (T[:, None] + 4) * U32) * S, 1e-6 + 1e-3 * np.abs(grad))
+    return loss, stats, (a, p, q), grad, tol
+
+
+def triplet_fp32(emb, pos_mask, neg_mask, margin):
+    """numpy fp32 restatement of the arithmetic of loss.hip: D by a serial fmaf chain over the d columns and sqrtf, mining
+    with first-index ties, l_i, the AvgNonZero mean and the gather gradient, all in float32 (numpy's summation order,
+    not the kernel's).  Returns (loss, stats, (a, p, n), grad)."""
+    e = np.asarray(emb, np.float32)
+    n, d = e.shape
+    s = np.zeros((n, n), np.float32)
+    for c in range(d):
+        df = e[:, None, c] - e[None, :, c]
+        s = (df.astype(np.float64) * df.astype(np.float64) + s.astype(np.float64)).astype(np.float32)   # fmaf
+    D = np.sqrt(s)
+    pm, nm = np.asarray(pos_mask, bool), np.asarray(neg_mask, bool)
+    mp, mn = np.where(pm, D, np.float32(0)), np.where(nm, D, np.float32(np.inf))
+    keep = pm.any(1) & nm.any(1)
+    a = np.arange(n)[keep]
+    p, q = mp.argmax(1)[keep], mn.argmin(1)[keep]
+    li = np.maximum(D[a, p] - np.minimum(D[a, q], D[p, q]) + np.float32(margin), np.float32(0))
+    nz = int((li > 0).sum())
+    loss = float(li[li > 0].sum(dtype=np.float32) / np.float32(nz)) if nz else 0.0
+    hp, hn = mp.max(1), mn.min(1)
+    with np.errstate(invalid="ignore"):
+        stats = {"loss": loss, "num_triplets": int(len(a)), "num_non_zero_triplets": nz,
+                 "avg_embedding_norm": float(np.sqrt((e * e).sum(1, dtype=np.float32)).mean(dtype=np.float32)),
+                 "mean_pos_pair_dist": float(hp.mean(dtype=np.float32)), "max_pos_pair_dist": float(hp.max()),
+                 "min_pos_pair_dist": float(hp.min()), "mean_neg_pair_dist": float(hn.mean(dtype=np.float32)),
+                 "max_neg_pair_dist": float(hn.max()), "min_neg_pair_dist": float(hn.min())}
+    grad, _, _ = triplet_grad(e, D, a, p, q, margin, dtype=np.float32)
+    return loss, stats, (a, p, q), grad

@@ -734,7 +734,7 @@ def test_streaming_pipeline_equals_extract(gpu, tmp_path):
 
 
 def test_knn_and_recall_match_oracle():
-    """on-device kNN + recall@k (eval/evaluate.py:80-88) vs the numpy restatement: indices bit-exact (ties by index)."""
+    """on-device kNN + recall@k (eval/evaluate.py:80-88) vs the numpy restatement: a certified k-nearest list (ties by index)."""
     from egonn_amd import retrieval, _lib
     from oracle import retrieval_ref as R
     dev = _lib.require_gpu()
@@ -748,9 +748,9 @@ def test_knn_and_recall_match_oracle():
     idx, dist = retrieval.knn(torch.from_numpy(qs).to(dev), torch.from_numpy(db).to(dev), k)
     ridx, rdist = R.knn(qs, db, k)
     assert idx.cpu().numpy()[0, :3].tolist() == [7, 100, 4000]
-    same = idx.cpu().numpy() == ridx
-    # fp32 summation order can swap two neighbours whose distances agree to the last ulp
-    assert same.mean() > 0.999
+    # fp32 summation order can swap two neighbours whose distances agree to the last ulp, so the answer is certified
+    # instead of compared index by index: a valid k-nearest list up to the derived fp32 bound (retrieval_ref.knn_tol)
+    assert R.knn_certificate(qs, db, idx.cpu().numpy(), dist.cpu().numpy(), R.knn_tol(d)) == []
     assert np.allclose(dist.cpu().numpy(), rdist, rtol=1e-5, atol=1e-5)
     mpos = rng.uniform(0, 500, (m, 2)).astype(np.float32)
     qpos = (mpos[ridx[:, 0]] + rng.normal(0, 8, (nq, 2))).astype(np.float32)
