@@ -102,6 +102,12 @@ _SIGS = [
                                      C.c_int64, _P, _P, _P]),
     ("egonn_registration_finish", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, _P,
                                             C.c_int64, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("egonn_voxel_downsample_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_voxel_downsample", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_double, C.POINTER(C.c_float), _P, _P, _P, _P, _P,
+                                         C.c_int64, _P]),
+    ("egonn_icp_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
+    ("egonn_icp_pairs", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_double, C.c_int, C.c_double, C.c_double,
+                                  _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     ("egonn_profile_enable", C.c_int, [_P, C.c_int, C.c_char_p]),
     ("egonn_profile_fetch", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),

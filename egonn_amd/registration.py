@@ -4,8 +4,12 @@ Mirrors the reference's names (eval/evaluate.py): `get_ransac_result` (:381-399)
 plus `register_pairs` (batched) and `evaluate_local`, the per-n_k metric bookkeeping of
 `MinkLocGLEvaluator.evaluate` (:188-292).  Matching, RANSAC, the final evaluation and the metrics run in libegonn_hip
 (egonn_match_mutual / egonn_ransac_pairs / egonn_registration_finish); there is no torch or numpy fallback for the
-arithmetic.  ICP refinement is out of scope (it needs the full clouds): the `*_refined` family is reduced to
-`repeatability_refined`, computed with the caller's `T_refined`.
+arithmetic.
+
+ICP refinement (misc/point_clouds.py:31-62: `icp`) runs on the full clouds in libegonn_hip as well (egonn_voxel_downsample /
+egonn_icp_pairs, csrc/icp.hip): `voxel_downsample`, `icp_pairs` (batched) and `icp` (the reference's signature).  With
+`query_clouds` / `map_clouds`, `evaluate_local` computes `T_refined` from `T_gt` on the device and reports the whole
+`*_refined` family (:261-275); without them only `repeatability_refined`, computed with the caller's `T_refined`.
 """
 from __future__ import annotations
 
@@ -18,6 +22,9 @@ from . import _lib
 
 N_MAX = 256
 STATUS_CLIPPED, STATUS_FEW_CORR, STATUS_NO_MODEL, STATUS_BAD_INDEX = 1, 2, 4, 8
+ICP_FEW_CORR, ICP_MAX_ITER, ICP_EMPTY, ICP_RANGE = 1, 2, 4, 8
+ICP_VOXEL_SIZE = 0.1                       # misc/point_clouds.py:37
+ICP_EPS_FITNESS = ICP_EPS_RMSE = 1e-6      # Open3D's ICPConvergenceCriteria defaults [recall]
 
 
 class RegistrationResult:
@@ -167,6 +174,170 @@ def calculate_repeatability(kp1, kp2, T_gt, threshold: float) -> float:
     return float(rep[0])
 
 
+# ------------------------------------------------------------------ ICP refinement on the full clouds
+def _check_cloud(name, x):
+    shape = tuple(getattr(x, "shape", ()))
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{name}: expected (n, 3) points, got shape {shape}")
+
+
+def _check_offsets(name, off, n_rows):
+    shape = tuple(getattr(off, "shape", (len(off),) if hasattr(off, "__len__") else ()))
+    if len(shape) != 1 or shape[0] < 2:
+        raise ValueError(f"{name}: offsets must be a 1-D sequence of n_clouds + 1 entries, got shape {shape}")
+    return shape[0] - 1
+
+
+def _check_crop(crop):
+    if crop is None:
+        return None
+    c = [float("nan") if v is None else float(v) for v in crop]
+    if len(c) != 6:
+        raise ValueError("crop: (min_x, max_x, min_y, max_y, min_z, max_z), None or NaN = no bound")
+    import ctypes
+    return (ctypes.c_float * 6)(*c)
+
+
+def voxel_downsample(points, offsets, voxel_size: float = ICP_VOXEL_SIZE, crop=None) -> Dict[str, torch.Tensor]:
+    """Voxel-grid downsample (Open3D voxel_down_sample, restated in csrc/icp.hip) of concatenated clouds: points (n,3),
+    cloud c = rows [offsets[c], offsets[c+1]).  crop = (min_x, max_x, min_y, max_y, min_z, max_z) with None / NaN = no bound,
+    applied first by the rules of preprocess_pointcloud (> min, <= max).  Returns device tensors: points (n,3) f64 (the first
+    offsets[-1] rows valid, ascending voxel index inside a cloud), offsets (n_clouds+1,) int64, counts (n,) int32 points per
+    voxel, status (n_clouds,) int32 (ICP_RANGE: a voxel index beyond 21 bits, nothing written for the cloud).
+    No host synchronisation when points and offsets are device tensors."""
+    _check_cloud("voxel_downsample", points)
+    C = _check_offsets("voxel_downsample", offsets, None)
+    if not float(voxel_size) > 0.0:
+        raise ValueError("voxel_downsample: voxel_size must be positive")
+    cr = _check_crop(crop)
+    dev = points.device if torch.is_tensor(points) and points.is_cuda else _lib.require_gpu()
+    lib = _lib.load()
+    pts, off = _dev(points, dev, torch.float32), _dev(offsets, dev, torch.int64)
+    n = pts.shape[0]
+    nbytes = int(lib.egonn_voxel_downsample_scratch_bytes(n, C))
+    scratch = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    out = {"points": torch.empty((n, 3), dtype=torch.float64, device=dev),
+           "offsets": torch.empty((C + 1,), dtype=torch.int64, device=dev),
+           "counts": torch.zeros((n,), dtype=torch.int32, device=dev),
+           "status": torch.empty((C,), dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        _lib.check(lib.egonn_voxel_downsample(_lib._ptr(pts) if n else None, n, off.data_ptr(), C, float(voxel_size), cr,
+                                              out["points"].data_ptr() if n else None, out["offsets"].data_ptr(),
+                                              out["counts"].data_ptr() if n else None, out["status"].data_ptr(),
+                                              scratch.data_ptr(), scratch.numel() * 8, _lib._stream()))
+    out["_keep"] = (pts, off, scratch)
+    return out
+
+
+def icp_pairs(src, src_offsets, tgt, tgt_offsets, T_init=None, inlier_dist_threshold: float = 1.2, max_iteration: int = 200,
+              debug: bool = False) -> Dict[str, torch.Tensor]:
+    """Point-to-point ICP of P (source, target) pairs (Open3D registration_icp, restated in csrc/icp.hip): src / tgt (n,3)
+    float64 concatenated clouds (what `voxel_downsample` returns) with (P+1,) offsets, T_init (P,4,4) or None = identity.
+    Returns device tensors T (P,4,4) f64, fitness, inlier_rmse (P,) f64, iterations, status (P,) int32 (ICP_* bits); with
+    debug also T_trace (P, max_iteration+1, 4, 4), eval_trace (P, max_iteration+1, 3) = (n_corr, sum d2, stop) and corr
+    (n_src,) int32 = j(i) of the last evaluation or -1.  No host synchronisation when the arguments are device tensors: the
+    call enqueues a fixed launch sequence and can be captured into a graph."""
+    _check_cloud("icp_pairs: src", src)
+    _check_cloud("icp_pairs: tgt", tgt)
+    P = _check_offsets("icp_pairs: src_offsets", src_offsets, None)
+    if _check_offsets("icp_pairs: tgt_offsets", tgt_offsets, None) != P:
+        raise ValueError("icp_pairs: src_offsets and tgt_offsets must describe the same number of pairs")
+    if T_init is not None and tuple(T_init.shape) != (P, 4, 4):
+        raise ValueError(f"icp_pairs: T_init must have shape ({P}, 4, 4), got {tuple(T_init.shape)}")
+    if int(max_iteration) < 0 or not float(inlier_dist_threshold) > 0.0:
+        raise ValueError("icp_pairs: max_iteration >= 0 and inlier_dist_threshold > 0 required")
+    dev = src.device if torch.is_tensor(src) and src.is_cuda else _lib.require_gpu()
+    lib = _lib.load()
+    s, t = _dev(src, dev, torch.float64), _dev(tgt, dev, torch.float64)       # fp32 inputs convert exactly
+    so, to = _dev(src_offsets, dev, torch.int64), _dev(tgt_offsets, dev, torch.int64)
+    ti = None if T_init is None else _dev(T_init, dev, torch.float64)
+    ns, nt, K = s.shape[0], t.shape[0], int(max_iteration)
+    nbytes = int(lib.egonn_icp_scratch_bytes(ns, nt, P))
+    scratch = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)        # noqa: E731
+    i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)          # noqa: E731
+    out = {"T": f64(P, 4, 4), "fitness": f64(P), "inlier_rmse": f64(P), "iterations": i32(P), "status": i32(P)}
+    if debug:
+        out.update({"T_trace": f64(P, K + 1, 4, 4), "eval_trace": f64(P, K + 1, 3), "corr": i32(ns)})
+    p = lambda k: _lib._ptr(out.get(k))                                       # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(lib.egonn_icp_pairs(s.data_ptr() if ns else None, ns, so.data_ptr(), t.data_ptr() if nt else None, nt,
+                                       to.data_ptr(), P, _lib._ptr(ti), float(inlier_dist_threshold), K, ICP_EPS_FITNESS,
+                                       ICP_EPS_RMSE, p("T"), p("fitness"), p("inlier_rmse"), p("iterations"), p("status"),
+                                       p("T_trace"), p("eval_trace"), p("corr") if ns else None, scratch.data_ptr(),
+                                       scratch.numel() * 8, _lib._stream()))
+    out["_keep"] = (s, t, so, to, ti, scratch)
+    return out
+
+
+def _concat_clouds(clouds, dev):
+    """per-scan (n,3) arrays -> (points (sum n, 3) f32 on the device, (len+1,) int64 offsets)"""
+    ts = [torch.as_tensor(c) for c in clouds]
+    for c in ts:
+        _check_cloud("cloud", c)
+    off = np.zeros(len(ts) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([c.shape[0] for c in ts])
+    pts = torch.cat([c.to(device=dev, dtype=torch.float32) for c in ts]) if ts else torch.zeros((0, 3), device=dev)
+    return pts, torch.from_numpy(off).to(dev)
+
+
+def refine_pairs(src_clouds, tgt_clouds, T_init=None, crop=None, inlier_dist_threshold: float = 1.2, max_iteration: int = 200,
+                 debug: bool = False) -> Dict[str, torch.Tensor]:
+    """icp() for P pairs of full clouds (lists of (n,3) arrays): crop, downsample both sides, ICP.  The `icp_pairs` result."""
+    if len(src_clouds) != len(tgt_clouds):
+        raise ValueError("refine_pairs: as many source as target clouds")
+    for c in list(src_clouds) + list(tgt_clouds):
+        _check_cloud("refine_pairs", c)
+    dev = _lib.require_gpu()
+    a = voxel_downsample(*_concat_clouds(src_clouds, dev), crop=crop)
+    b = voxel_downsample(*_concat_clouds(tgt_clouds, dev), crop=crop)
+    r = icp_pairs(a["points"], a["offsets"], b["points"], b["offsets"], T_init, inlier_dist_threshold, max_iteration, debug)
+    r["_clouds"] = (a, b)
+    return r
+
+
+def icp(anchor_pc, positive_pc, transform=None, point2plane: bool = False, inlier_dist_threshold: float = 1.2,
+        max_iteration: int = 200):
+    """misc/point_clouds.py:31-62 for one pair: -> (T (4,4) numpy float64, fitness, inlier_rmse).  [SYNC] copies the result
+    back.  Point-to-plane is not implemented."""
+    if point2plane:
+        raise NotImplementedError("icp: only the point-to-point estimation is implemented")
+    _check_cloud("icp: anchor_pc", anchor_pc)
+    _check_cloud("icp: positive_pc", positive_pc)
+    ti = None
+    if transform is not None:
+        ti = torch.as_tensor(np.asarray(transform, dtype=np.float64))
+        if tuple(ti.shape) != (4, 4):
+            raise ValueError(f"icp: transform must be (4, 4), got {tuple(ti.shape)}")
+        ti = ti.reshape(1, 4, 4)
+    r = refine_pairs([anchor_pc], [positive_pc], ti, None, inlier_dist_threshold, max_iteration)
+    return r["T"][0].cpu().numpy(), float(r["fitness"][0]), float(r["inlier_rmse"][0])
+
+
+def _metrics_against(r, T_ref, n_max, ransac_max_it, seed, ransac_dist_th, repeat_dist_th):
+    """rte / rre / success / repeatability of a `register_pairs` result against another pose T_ref (P,4,4) on the device:
+    egonn_registration_finish again, on the scratch the result still holds (same winner, same bits)."""
+    lib = _lib.load()
+    k1, k2, c1, c2, pid, _, scratch = r["_keep"]
+    dev, P = k1.device, k1.shape[0]
+    ref = _dev(T_ref, dev, torch.float64).reshape(P, 4, 4)
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
+    out = {"T": f64(P, 4, 4), "inliers": i32(P), "fitness": f64(P), "inlier_rmse": f64(P), "rte": f64(P), "rre": f64(P),
+           "success": i32(P), "repeatability": f64(P)}
+    with torch.cuda.device(dev):
+        _lib.check(lib.egonn_registration_finish(k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), r["corr"].data_ptr(),
+                                                 r["n_corr"].data_ptr(), _lib._ptr(pid), P, n_max, int(ransac_max_it),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, float(ransac_dist_th), scratch.data_ptr(),
+                                                 scratch.numel() * 8, ref.data_ptr(), float(repeat_dist_th), out["T"].data_ptr(),
+                                                 out["inliers"].data_ptr(), out["fitness"].data_ptr(),
+                                                 out["inlier_rmse"].data_ptr(), None, None, out["rte"].data_ptr(),
+                                                 out["rre"].data_ptr(), out["success"].data_ptr(),
+                                                 out["repeatability"].data_ptr(), None, _lib._stream()))
+    out["_keep"] = (ref,)
+    return out
+
+
 def _stack(items, idx, key, n_k, width, dev):
     """pad the first n_k rows of items[i][key] for i in idx to (len(idx), n_k, width) + counts"""
     out = torch.zeros((len(idx), n_k, width), dtype=torch.float32, device=dev)
@@ -180,7 +351,8 @@ def _stack(items, idx, key, n_k, width, dev):
 
 def evaluate_local(local_query: Sequence[dict], local_map: Sequence[dict], nn_index, T_gt, n_k: Sequence[int] = (128,),
                    euclid_dist=None, T_refined=None, ransac_dist_th: float = 0.5, ransac_max_it: int = 10000,
-                   repeat_dist_th: float = 0.5, seed: int = 0) -> Dict[int, Dict[str, float]]:
+                   repeat_dist_th: float = 0.5, seed: int = 0, query_clouds=None, map_clouds=None, crop=None,
+                   icp_dist_th: float = 1.2, icp_max_it: int = 200) -> Dict[int, Dict[str, float]]:
     """The local-descriptor half of MinkLocGLEvaluator.evaluate (eval/evaluate.py:188-292) for all queries at once.
 
     local_query / local_map: per scan {'keypoints': (n,3), 'features': (n,D)} (compute_embeddings, :323); nn_index (Q,) or
@@ -189,7 +361,15 @@ def evaluate_local(local_query: Sequence[dict], local_map: Sequence[dict], nn_in
     Returns {n_k: {'rre', 'rte', 'repeatability', 'success', 'success_inliers', 'failure_inliers', 'repeatability_refined',
     't_ransac', 't_ransac_sd'}} with the reference's conventions (rre / rte averaged over successes, empty lists -> 0.;
     t_ransac = the device time of the batched call divided by its pairs: ONE measurement, so 't_ransac_sd' is reported as 0.
-    rather than computed).  The pair id of the draws is the query index."""
+    rather than computed).  The pair id of the draws is the query index.
+
+    query_clouds / map_clouds (per-scan (n,3) arrays, indexed like local_query / local_map) switch the ICP refinement on
+    (icp_refine, :215-236): T_refined = icp(query cloud, map cloud, T_gt) on the device, after the optional `crop` (min_x,
+    max_x, min_y, max_y, min_z, max_z) on both clouds; a caller's T_refined is then not used.  The dict then also carries
+    'rre_refined', 'rte_refined', 'success_refined', 'success_inliers_refined', 'failure_inliers_refined' (:261-275)."""
+    if (query_clouds is None) != (map_clouds is None):
+        raise ValueError("evaluate_local: query_clouds and map_clouds go together")
+    refine = query_clouds is not None
     dev = _lib.require_gpu()
     nn = torch.as_tensor(nn_index).reshape(len(local_query), -1)[:, 0].tolist()
     sel = list(range(len(local_query)))
@@ -199,7 +379,13 @@ def evaluate_local(local_query: Sequence[dict], local_map: Sequence[dict], nn_in
     gt_all = torch.as_tensor(np.asarray(T_gt, dtype=np.float64)).reshape(-1, 4, 4)
     ref_all = None if T_refined is None else torch.as_tensor(np.asarray(T_refined, dtype=np.float64)).reshape(-1, 4, 4)
     keys = ('rre', 'rte', 'repeatability', 'success', 'success_inliers', 'failure_inliers', 'repeatability_refined')
+    if refine:
+        keys += ('rre_refined', 'rte_refined', 'success_refined', 'success_inliers_refined', 'failure_inliers_refined')
     mean_metrics = {}
+    icp_res = None
+    if refine and sel:                                    # one batched call for every n_k: the clouds do not depend on it
+        icp_res = refine_pairs([query_clouds[q] for q in sel], [map_clouds[nn[q]] for q in sel], gt_all[sel], crop,
+                               icp_dist_th, icp_max_it)
     for nk in n_k:
         if nk > N_MAX:
             raise ValueError(f"evaluate_local: n_k {nk} exceeds {N_MAX}")
@@ -218,8 +404,13 @@ def evaluate_local(local_query: Sequence[dict], local_map: Sequence[dict], nn_in
             r = register_pairs(f1, f2, k1, k2, n1=c1, n2=c2, T_gt=gt, ransac_dist_th=ransac_dist_th, ransac_max_it=ransac_max_it,
                                seed=seed, pair_ids=sel, repeat_dist_th=repeat_dist_th)
             e1.record()
-            ref = gt if ref_all is None else ref_all[sel]
-            rep_ref = r["repeatability"] if ref_all is None else repeatability_pairs(k1, k2, ref, repeat_dist_th, c1, c2)
+            rr = None
+            if refine:       # the estimate against T_refined: the finish kernel once more on the same hypotheses' bests
+                rr = _metrics_against(r, icp_res["T"], nk, ransac_max_it, seed, ransac_dist_th, repeat_dist_th)
+                rep_ref = rr["repeatability"]
+            else:
+                ref = gt if ref_all is None else ref_all[sel]
+                rep_ref = r["repeatability"] if ref_all is None else repeatability_pairs(k1, k2, ref, repeat_dist_th, c1, c2)
             e1.synchronize()
             t_pair = e0.elapsed_time(e1) * 1e-3 / len(sel)
             rte, rre, suc, inl = (r[k].cpu().tolist() for k in ("rte", "rre", "success", "inliers"))
@@ -234,6 +425,17 @@ def evaluate_local(local_query: Sequence[dict], local_map: Sequence[dict], nn_in
                 else:
                     m['success'].append(0.)
                     m['failure_inliers'].append(inl[i])
+            if refine:
+                rte_r, rre_r, suc_r = (rr[k].cpu().tolist() for k in ("rte", "rre", "success"))
+                for i in range(len(sel)):
+                    if suc_r[i]:
+                        m['rte_refined'].append(rte_r[i])
+                        m['rre_refined'].append(rre_r[i])
+                        m['success_refined'].append(1.)
+                        m['success_inliers_refined'].append(inl[i])
+                    else:
+                        m['success_refined'].append(0.)
+                        m['failure_inliers_refined'].append(inl[i])
         mean_metrics[nk] = {k: (float(np.mean(v)) if len(v) else 0.) for k, v in m.items()}
         mean_metrics[nk]['t_ransac'] = t_pair
         if sel:

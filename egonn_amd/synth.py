@@ -165,3 +165,25 @@ def pad_keypoint_pairs(pairs, n_max=None, D=None):
         n1[i], n2[i] = len(p[0]), len(p[1])
         F1[i, :n1[i]], F2[i, :n2[i]], K1[i, :n1[i]], K2[i, :n2[i]] = p[0], p[1], p[2], p[3]
     return F1, F2, K1, K2, n1, n2
+
+
+# ------------------------------------------------------------------ scan pairs with a planted pose (ICP tests / timing)
+def planted_scan_pair(seed, n_points, translation=(1.0, 0.5, 0.1), yaw_pitch_roll=(0.05, 0.01, 0.01), noise=0.02,
+                      init_translation=(0.3, -0.2, 0.1), init_yaw_pitch_roll=(0.01, 0.0, 0.0)):
+    """Two different subsamples of one `lidar_scan` scene: src = subsample A + noise, tgt = T_planted (subsample B) + noise
+    (independent N(0, noise) per coordinate).  n_points: int or (n_src, n_tgt).  translation (m) and yaw_pitch_roll (rad)
+    make T_planted; T_init = D T_planted with D the rigid motion of init_translation (m) / init_yaw_pitch_roll (rad) — the
+    stated perturbation (zeros: T_init = T_planted).  -> src, tgt (float32), T_planted, T_init (4,4) float64."""
+    n_src, n_tgt = (n_points, n_points) if np.isscalar(n_points) else n_points
+    scene = lidar_scan(seed, n_points=int(1.6 * max(n_src, n_tgt))).astype(np.float64)
+    rng = np.random.default_rng([seed, 0x1C9])
+    a = scene[rng.choice(len(scene), size=n_src, replace=False)]
+    b = scene[rng.choice(len(scene), size=n_tgt, replace=False)]
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = rot_zyx(*yaw_pitch_roll), np.asarray(translation, dtype=np.float64)
+    D = np.eye(4)
+    D[:3, :3], D[:3, 3] = rot_zyx(*init_yaw_pitch_roll), np.asarray(init_translation, dtype=np.float64)
+    src = a + noise * rng.standard_normal(a.shape)
+    tgt = b @ T[:3, :3].T + T[:3, 3] + noise * rng.standard_normal(b.shape)
+    f32 = lambda x: np.ascontiguousarray(x, dtype=np.float32)      # noqa: E731
+    return f32(src), f32(tgt), T, D @ T

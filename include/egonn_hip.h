@@ -446,6 +446,51 @@ int egonn_registration_finish(const float* kp1, const float* kp2, const int32_t*
                               int32_t* corr_set, int32_t* best_t, double* rte, double* rre, int32_t* success,
                               double* repeatability, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ ICP refinement of scan pairs (local evaluation, tuples)
+ * replaces icp() of misc/point_clouds.py:31-62 (voxel_down_sample(0.1) of both clouds, then Open3D's registration_icp,
+ * point-to-point, ICPConvergenceCriteria(max_iteration)); called by eval/evaluate.py:215-236 and
+ * datasets/mulran/generate_training_tuples.py:83.  Open3D is not part of the reference tree: the rules are restated from
+ * its documentation [recall] (egonn_amd/csrc/icp.hip).  Deliberate differences: the downsampled order is fixed
+ * (ascending voxel index), and the source is always transformed from the original points by the cumulative transform.
+ * All geometry is fp64; results are bitwise reproducible and independent of the batch a pair sits in. */
+enum { EGONN_ICP_STATUS_FEW_CORR = 1,     /* a round met fewer than 3 correspondences: the loop stopped with T unchanged */
+       EGONN_ICP_STATUS_MAX_ITER = 2,     /* stopped by the round limit */
+       EGONN_ICP_STATUS_EMPTY = 4,        /* a side has no points: T = init, fitness 0 */
+       EGONN_ICP_STATUS_RANGE = 8 };      /* downsample: a voxel index needs more than 21 bits (or a non-finite point) */
+/* Voxel-grid downsample of n_clouds clouds: points (n,3) f32 concatenated, cloud c = rows [offsets[c], offsets[c+1]) (DEVICE
+ * int64, n_clouds+1; n is a CAPACITY as in egonn_filter_points).  crop: 6 HOST floats min_x, max_x, min_y, max_y, min_z,
+ * max_z (nullable; NaN = no bound): keep x > min_x and x <= max_x, likewise y, z (preprocess_pointcloud,
+ * datasets/dataset_utils.py:235-265).  mb = min over the kept points - voxel_size/2 per axis; idx = floor((p - mb) /
+ * voxel_size); one output point per occupied voxel = fp64 mean of its points summed in input order, in ascending (ix, iy,
+ * iz).  out_points (n,3) f64 (first out_offsets[n_clouds] rows valid), out_offsets (n_clouds+1) DEVICE int64, out_counts (n)
+ * int32 points per voxel (nullable), status (n_clouds) DEVICE int32: EGONN_ICP_STATUS_RANGE = nothing written for that
+ * cloud.  scratch: egonn_voxel_downsample_scratch_bytes(n, n_clouds) bytes (-1 on bad arguments), 256-byte aligned.
+ * No host synchronisation. */
+int64_t egonn_voxel_downsample_scratch_bytes(int64_t n, int n_clouds);
+int egonn_voxel_downsample(const float* points, int64_t n, const int64_t* offsets, int n_clouds, double voxel_size,
+                           const float* crop, double* out_points, int64_t* out_offsets, int32_t* out_counts, int32_t* status,
+                           void* scratch, int64_t scratch_bytes, void* stream);
+/* Point-to-point ICP of n_pairs independent (source, target) pairs: src (n_src,3) / tgt (n_tgt,3) f64 with DEVICE int64
+ * offsets (n_pairs+1 each; n_src / n_tgt are capacities), T_init (n_pairs,4,4) f64 (nullable = identity).
+ * Evaluation under T: j(i) = nearest target point of T s_i (fp64 squared distance, ties: lowest index), a correspondence iff
+ * the distance is < max_dist; fitness = n_corr / n_source; inlier_rmse = sqrt(sum d2 / n_corr) (0 without correspondences).
+ * T_0 = init is evaluated; round k: U = least-squares rigid transform (no scale, det +1) of {T_k s_i} onto {t_j(i)},
+ * T_k+1 = U T_k, evaluated; the loop stops after that evaluation if |d fitness| < eps_fitness and |d rmse| < eps_rmse, after
+ * max_iteration rounds (MAX_ITER), or before a round with fewer than 3 correspondences (FEW_CORR, T unchanged).
+ * Outputs: T (n_pairs,4,4) f64, fitness, inlier_rmse (n_pairs) f64 of the last evaluation, iterations (rounds run), status
+ * (EGONN_ICP_STATUS_* bits), all (n_pairs).  Nullable debug tables: T_trace (n_pairs, max_iteration+1, 4, 4) = T_k (zero
+ * beyond the last), eval_trace (n_pairs, max_iteration+1, 3) = (n_corr, sum d2, stop flag) of evaluation k, corr (n_src)
+ * int32 = j(i) of the last evaluation (index inside the pair's target) or -1.
+ * The call enqueues a fixed launch sequence for max_iteration rounds; a stopped pair's later launches return at once: no host
+ * synchronisation, capturable.  scratch: egonn_icp_scratch_bytes(n_src, n_tgt, n_pairs) bytes (-1 on bad arguments),
+ * 256-byte aligned. */
+int64_t egonn_icp_scratch_bytes(int64_t n_src, int64_t n_tgt, int n_pairs);
+int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_offsets, const double* tgt, int64_t n_tgt,
+                    const int64_t* tgt_offsets, int n_pairs, const double* T_init, double max_dist, int max_iteration,
+                    double eps_fitness, double eps_rmse, double* T, double* fitness, double* inlier_rmse, int32_t* iterations,
+                    int32_t* status, double* T_trace, double* eval_trace, int32_t* corr, void* scratch, int64_t scratch_bytes,
+                    void* stream);
+
 /* ------------------------------------------------------------------ launch timing (bench.py roofline leg)
  * mode 0: off; 1: time every tagged sparse-conv launch (event records around it); 2: only launches whose tag contains
  * `filter`, with the events attached to the kernel dispatch itself (the kernel's own begin..end, also when other streams
