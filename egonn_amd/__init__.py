@@ -14,9 +14,13 @@ from .stream import StreamingExtractor
 from .local_loss import KeypointLoss, CorrespondenceLoss, KeypointCorrLoss, make_local_loss
 from .registration import (get_ransac_result, calculate_repeatability, register_pairs, evaluate_local, match_mutual,
                            RegistrationResult, voxel_downsample, icp_pairs, refine_pairs, icp)
+from .augment import (TrainTransform, TrainSetTransform, TrainBatcher, JitterPoints, RemoveRandomPoints, RandomTranslation,
+                      RandomRotation, RemoveRandomBlock, RandomFlip, RigidPerturbation, AugmentParams, augment_points)
 
 __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "MinkHead", "MinkTrunk",
            "CartesianQuantizer", "PolarQuantizer", "Quantizer", "DescriptorExtractor", "GraphExtractor", "StreamingExtractor", "MinkFPN", "MinkLoc", "MinkLoc3D",
            "KeypointLoss", "CorrespondenceLoss", "KeypointCorrLoss", "make_local_loss",
            "get_ransac_result", "calculate_repeatability", "register_pairs", "evaluate_local", "match_mutual", "RegistrationResult",
-           "voxel_downsample", "icp_pairs", "refine_pairs", "icp"]
+           "voxel_downsample", "icp_pairs", "refine_pairs", "icp",
+           "TrainTransform", "TrainSetTransform", "TrainBatcher", "JitterPoints", "RemoveRandomPoints", "RandomTranslation",
+           "RandomRotation", "RemoveRandomBlock", "RandomFlip", "RigidPerturbation", "AugmentParams", "augment_points"]

@@ -491,6 +491,47 @@ int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_offsets
                     int32_t* status, double* T_trace, double* eval_trace, int32_t* corr, void* scratch, int64_t scratch_bytes,
                     void* stream);
 
+/* ------------------------------------------------------------------ training augmentation of a resident scan batch
+ * replaces TrainTransform (datasets/augmentation.py:10-30, called per scan by datasets/base_datasets.py:70-76),
+ * TrainSetTransform (:33-48, called per batch by datasets/dataset_utils.py:67-72) and the rigid perturbation of the local
+ * phase (datasets/mulran/mulran_train.py:41-50) for scans that are already on the device.  Capacity-based and free of host
+ * synchronisation like egonn_filter_points, so it can sit in front of egonn_voxelize_device inside a captured graph.
+ * egonn_amd/csrc/augment.hip spells out every rule, the deliberate differences and the draw: a draw is a pure function of
+ * (seed, draw, scan id, point index, slot) through splitmix64, so a scan's augmentation does not depend on its batch. */
+enum { EGONN_AUG_JITTER = 1, EGONN_AUG_REMOVE_POINTS = 2, EGONN_AUG_TRANSLATE = 4, EGONN_AUG_ROTATE = 8, EGONN_AUG_BLOCK = 16,
+       EGONN_AUG_SET_ROTATE = 32, EGONN_AUG_FLIP = 64, EGONN_AUG_RIGID = 128, EGONN_AUG_JITTER_CLIP = 256, EGONN_AUG_ALL = 511 };
+enum { EGONN_AUG_STATUS_BAD_ID = 1 };     /* scan id outside [0, 2^22) (or a scan of 2^24 - 2 points or more): its points are NaN */
+typedef struct egonn_augment_params {
+  uint64_t seed;
+  uint32_t draw;            /* draw counter, e.g. the epoch: < 2^14 */
+  uint32_t set_id;          /* id of the batch's own draw (stage 2): < 2^22 */
+  uint32_t stages;          /* EGONN_AUG_* bits: every stage is switched on its own */
+  uint32_t reserved;
+  double sigma, clip;                 /* JitterPoints (clip used with EGONN_AUG_JITTER_CLIP) */
+  double r_min, r_max;                /* RemoveRandomPoints */
+  double max_delta;                   /* RandomTranslation */
+  double max_theta;                   /* RandomRotation about z, degrees (stage 1) */
+  double block_p, scale_lo, scale_hi, ratio_lo, ratio_hi;   /* RemoveRandomBlock */
+  double set_max_theta;               /* RandomRotation about z, degrees (stage 2) */
+  double flip_cum[3];                 /* RandomFlip: cumulative sums of p */
+  double rot_max, trans_max;          /* rigid perturbation: radians, metres */
+} egonn_augment_params;
+/* points (n,3) f32, scan b = rows [scan_offsets[b], scan_offsets[b+1]) (DEVICE int64, batch_size+1; n < 2^24 is a CAPACITY:
+ * rows beyond scan_offsets[batch_size] are neither read nor written); scan_ids (batch_size) DEVICE int32, nullable = the
+ * position in the batch; out_points (n,3) f32 (may be points itself).  T_in / T_out (batch_size,4,4) f32 row-major, both
+ * nullable: T_out = m @ T_in with m the rigid perturbation of the scan (T_in null = identity).  Optional outputs (null =
+ * not written): rec_i (batch_size,8) int32 = n, k removed, block drawn, flip axis (-1 none), status bits, scan id, low and
+ * high word of the removal threshold key; rec_d (batch_size,32) f64 = [0] r, [1..3] translation, [4..6] theta, cos, sin
+ * of stage 1, [7] block u, [8..13] box min xyz, max xyz, [14..19] block x, y, w, h, x + w, y + h, [20..23] set theta, cos,
+ * sin, flip u, [24..28] rigid angle, cos, sin, tx, ty, [29] erase area, [30] aspect ratio (fields of stages that are off
+ * or not drawn are 0; translation, cos and sin are the fp64 values BEFORE their one rounding to fp32, the box and the block
+ * are fp32 values); flags (n) uint8: bit 0 = removed by RemoveRandomPoints, bit 1 = erased by RemoveRandomBlock.
+ * scratch: egonn_augment_scratch_bytes(n, batch_size) bytes (-1 on bad arguments), 256-byte aligned. */
+int64_t egonn_augment_scratch_bytes(int64_t n, int batch_size);
+int egonn_augment_points(const float* points, int64_t n, const int64_t* scan_offsets, int batch_size, const int32_t* scan_ids,
+                         const egonn_augment_params* params, const float* T_in, float* out_points, float* T_out,
+                         int32_t* rec_i, double* rec_d, uint8_t* flags, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ launch timing (bench.py roofline leg)
  * mode 0: off; 1: time every tagged sparse-conv launch (event records around it); 2: only launches whose tag contains
  * `filter`, with the events attached to the kernel dispatch itself (the kernel's own begin..end, also when other streams
