@@ -57,6 +57,13 @@ _SIGS = [
     ("egonn_gem", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P]),
     ("egonn_global_max_pool", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
     ("egonn_netvlad", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    ("egonn_netvlad_train_forward", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, C.c_float, _P, _P,
+                                              _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    ("egonn_netvlad_train_backward", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P,
+                                               _P, _P, _P, _P, _P, _P, _P]),
+    ("egonn_global_max_pool_argmax", C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P]),
+    ("egonn_global_max_pool_backward", C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P, _P]),
+    ("egonn_sigmoid_gate", C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     ("egonn_add", C.c_int, [_P, _P, C.c_int64, _P, _P]),
     ("egonn_gather_input", C.c_int, [_P, _P, C.c_int, _P, _P]),
     ("egonn_model_create", C.c_int, [C.POINTER(_P)]),
@@ -494,6 +501,70 @@ class Context:
         self._call(self.lib.egonn_dense, x.data_ptr(), x.shape[0], cin, weight.data_ptr(), int(out_in), _ptr(b), cout,
                    act, out.data_ptr())
         return out
+
+    def netvlad_train_forward(self, level: int, x: torch.Tensor, nmax: int, cluster_weights, cluster_weights2,
+                              bn1: torch.nn.BatchNorm1d, hidden1_weights):
+        """egonn_netvlad_train_forward: (y (B, D) before bn2, saved tensors for netvlad_train_backward); updates bn1's running
+        statistics in place (num_batches_tracked is the caller's)."""
+        x = _dev_f32(x, self.device)
+        n, c = x.shape
+        assert n == self.level_count(level), "netvlad: x must hold exactly the rows of the level"
+        B, d = self.batch_size, hidden1_weights.shape[-1]
+        f = dict(dtype=torch.float32, device=self.device)
+        out = torch.empty((B, d), **f)
+        saved = (torch.empty((n, 64), **f), torch.empty((4, 64), **f), torch.empty((B, c, 64), **f),
+                 torch.empty((B, c // 16, 64), **f), torch.empty((B, 64), **f))
+        mom = bn1.momentum if bn1.momentum is not None else 1.0 / float(int(bn1.num_batches_tracked) + 1)
+        self._call(self.lib.egonn_netvlad_train_forward, self.h, level, x.data_ptr(), c, int(nmax), cluster_weights.data_ptr(),
+                   cluster_weights2.data_ptr(), bn1.weight.data_ptr(), bn1.bias.data_ptr(), float(bn1.eps), float(mom),
+                   bn1.running_mean.data_ptr(), bn1.running_var.data_ptr(), hidden1_weights.data_ptr(), d, out.data_ptr(),
+                   *[t.data_ptr() for t in saved])
+        return out, saved
+
+    def netvlad_train_backward(self, level: int, x, nmax: int, cluster_weights, cluster_weights2, bn1_weight, hidden1_weights,
+                               grad_out, saved):
+        """egonn_netvlad_train_backward: (grad x, grad cluster_weights, grad cluster_weights2, grad bn1 weight, grad bn1 bias,
+        grad hidden1_weights)"""
+        x, g = _dev_f32(x, self.device), _dev_f32(grad_out, self.device)
+        n, c = x.shape
+        d = hidden1_weights.shape[-1]
+        f = dict(dtype=torch.float32, device=self.device)
+        dx, dwc, dw2 = torch.empty((n, c), **f), torch.empty((c, 64), **f), torch.empty((c, 64), **f)
+        bn5, dh = torch.empty((5, 64), **f), torch.empty((c * 64, d), **f)
+        self._call(self.lib.egonn_netvlad_train_backward, self.h, level, x.data_ptr(), c, int(nmax), cluster_weights.data_ptr(),
+                   cluster_weights2.data_ptr(), bn1_weight.data_ptr(), hidden1_weights.data_ptr(), d, g.data_ptr(),
+                   *[t.data_ptr() for t in saved], dx.data_ptr(), dwc.data_ptr(), dw2.data_ptr(), bn5.data_ptr(), dh.data_ptr())
+        return dx, dwc, dw2, bn5[3], bn5[4], dh
+
+    def global_max_pool_argmax(self, level: int, x: torch.Tensor):
+        """MAC and the plan row of every maximum (ties: lowest row; -1 for an empty scan): ((B, C) f32, (B, C) int32)"""
+        x = _dev_f32(x, self.device)
+        assert x.shape[0] == self.level_count(level)
+        out = torch.empty((self.batch_size, x.shape[1]), dtype=torch.float32, device=self.device)
+        rows = torch.empty((self.batch_size, x.shape[1]), dtype=torch.int32, device=self.device)
+        self._call(self.lib.egonn_global_max_pool_argmax, self.h, level, x.data_ptr(), x.shape[1], out.data_ptr(),
+                   rows.data_ptr())
+        return out, rows
+
+    def global_max_pool_backward(self, level: int, grad_out, rows):
+        g = _dev_f32(grad_out, self.device)
+        dx = torch.empty((self.level_count(level), g.shape[1]), dtype=torch.float32, device=self.device)
+        self._call(self.lib.egonn_global_max_pool_backward, self.h, level, g.data_ptr(), rows.data_ptr(), g.shape[1],
+                   dx.data_ptr())
+        return dx
+
+    def sigmoid_gate(self, y, t, grad_out=None):
+        """y * sigmoid(t), or with grad_out its backward (grad y, grad t)"""
+        y, t = _dev_f32(y, self.device), _dev_f32(t, self.device)
+        if grad_out is None:
+            out = torch.empty_like(y)
+            self._call(self.lib.egonn_sigmoid_gate, y.data_ptr(), t.data_ptr(), None, y.numel(), out.data_ptr(), None, None)
+            return out
+        g = _dev_f32(grad_out, self.device)
+        dy, dt = torch.empty_like(y), torch.empty_like(y)
+        self._call(self.lib.egonn_sigmoid_gate, y.data_ptr(), t.data_ptr(), g.data_ptr(), y.numel(), None, dy.data_ptr(),
+                   dt.data_ptr())
+        return dy, dt
 
     def dense_backward_weight(self, a, b):
         """a^T b over the rows: (ca, cb)."""

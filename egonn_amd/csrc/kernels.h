@@ -123,10 +123,39 @@ int select_topk(const float* sigma, const int32_t* boff_dev, int B, int k, const
 // netvlad.hip ------------------------------------------------------------------------------------
 // NetVLAD(-GC) pooling of MinkLoc (layers/netvlad.py:18-112) over the scans of boff (DEVICE, B+1): out (B, D).  Four launches;
 // weights in reference layout, bn scale/shift folded (bn_fold); ws: netvlad_workspace_floats(B, C, D) floats.
+static constexpr int NV_K = 64;             // clusters (NetVLADWrapper fixes cluster_size = 64)
+static constexpr int NV_MAX_CHUNKS = 32;    // row chunks per scan of the row passes
+static constexpr int NV_CHUNK_ROWS = 128;   // target rows per chunk
+// chunks of a scan: a function of the scan's own row count only (the summation orders of every row pass follow it)
+__host__ __device__ static inline int nv_chunks(int32_t len) {
+  if (len <= 0) return 0;
+  const int n = (len + NV_CHUNK_ROWS - 1) / NV_CHUNK_ROWS;
+  return n < NV_MAX_CHUNKS ? n : NV_MAX_CHUNKS;
+}
 size_t netvlad_workspace_floats(int B, int C, int D);
+// the carve-outs of that workspace: per-chunk partials (X^T A | a_sum), V (B, C, 64), squared-norm partials, projection partials
+void netvlad_workspace_carve(float* ws, int B, int C, float** part, float** vraw, float** sq, float** pp);
 int netvlad_forward(const float* x, const int32_t* boff, int B, int C, const float* wc, const float* w2, const float* sc1,
                     const float* sh1, const float* H, int D, const float* sc2, const float* sh2, const float* wg,
                     const float* scg, const float* shg, int gating, float* out, float* ws, hipStream_t stream);
+
+// netvlad_train.hip ------------------------------------------------------------------------------
+// Train-mode NetVLAD core (bn1 on batch statistics over M = B * nmax rows, pad rows included; y = vlad @ H before bn2) and its
+// backward; MAC with its argmax and the scatter that is its backward; y * sigmoid(t) of the context gating.
+size_t netvlad_train_forward_floats(int B, int64_t N, int C, int D);
+int netvlad_train_forward(const float* x, const int32_t* boff, int B, int64_t N, int C, int nmax, const float* wc,
+                          const float* w2, const float* bn1_w, const float* bn1_b, float eps, float momentum,
+                          float* running_mean, float* running_var, const float* H, int D, float* out, float* save_z,
+                          float* save_bn4, float* save_vraw, float* save_sq, float* save_asum, float* ws, hipStream_t stream);
+size_t netvlad_train_backward_floats(int B, int64_t N, int C, int D);
+int netvlad_train_backward(const float* x, const float* z, const int32_t* boff, int B, int64_t N, int C, int nmax,
+                           const float* wc, const float* w2, const float* bn1_w, const float* bn4, const float* H, int D,
+                           const float* dy, const float* vraw, const float* sq, const float* asum, float* dx, float* dwc,
+                           float* dw2, float* bn5, float* dH, float* ws, hipStream_t stream);
+int global_max_argmax(const float* in, const int32_t* boff, int B, int c, float* out, int32_t* rows, hipStream_t stream);
+int global_max_backward(const float* grad, const int32_t* rows, int B, int64_t n, int c, float* dx, hipStream_t stream);
+int sigmoid_gate(const float* y, const float* t, const float* grad, int64_t n, float* out, float* dy, float* dt,
+                 hipStream_t stream);
 
 // loss.hip ---------------------------------------------------------------------------------------
 size_t triplet_loss_scratch_floats(int n);

@@ -613,6 +613,101 @@ API int egonn_netvlad(egonn_ctx* c, int level, const float* x, int channels, con
                          ws, (hipStream_t)stream);
 }
 
+// Train-mode NetVLAD core over the rows of `level` (netvlad_train.hip): bn1 on the statistics of the M = B * nmax zero-padded
+// rows, y = vlad @ H (B, out_dim) BEFORE bn2; what the backward needs goes to the caller's save_* buffers
+static int netvlad_train_check(egonn_ctx* c, int level, int channels, int out_dim, int nmax) {
+  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS, EGONN_ERR_INVALID, "netvlad_train: level %d out of range", level);
+  EGONN_REQUIRE(channels >= 16 && channels <= 512 && channels % 16 == 0, EGONN_ERR_INVALID,
+                "netvlad_train: %d channels unsupported (multiple of 16, 16..512)", channels);
+  EGONN_REQUIRE(out_dim >= 16 && out_dim <= 1024 && out_dim % 16 == 0, EGONN_ERR_INVALID,
+                "netvlad_train: output_dim %d unsupported (multiple of 16, 16..1024)", out_dim);
+  EGONN_REQUIRE(c->plan.batch >= 2, EGONN_ERR_INVALID, "netvlad_train: batch statistics need at least 2 scans");
+  EGONN_REQUIRE(c->plan.lv[level].n >= 1 && nmax >= 1 && (int64_t)nmax * c->plan.batch >= c->plan.lv[level].n,
+                EGONN_ERR_INVALID, "netvlad_train: nmax %d is not the largest scan of the level", nmax);
+  return EGONN_OK;
+}
+
+API int egonn_netvlad_train_forward(egonn_ctx* c, int level, const float* x, int channels, int nmax,
+                                    const float* cluster_weights, const float* cluster_weights2, const float* bn1_weight,
+                                    const float* bn1_bias, float bn1_eps, float bn1_momentum, float* bn1_running_mean,
+                                    float* bn1_running_var, const float* hidden1_weights, int out_dim, float* out, float* save_z,
+                                    float* save_bn1, float* save_v, float* save_sq, float* save_asum, void* stream) {
+  REQUIRE_PLAN(c);
+  EGONN_TRY(netvlad_train_check(c, level, channels, out_dim, nmax));
+  EGONN_REQUIRE(x && cluster_weights && cluster_weights2 && bn1_weight && bn1_bias && bn1_running_mean && bn1_running_var &&
+                    hidden1_weights && out && save_z && save_bn1 && save_v && save_sq && save_asum,
+                EGONN_ERR_INVALID, "netvlad_train_forward: null argument");
+  EGONN_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)save_z & 15) == 0, EGONN_ERR_INVALID,
+                "netvlad_train_forward: x and save_z must be 16-byte aligned");
+  HIP_CHECK(hipSetDevice(c->device));
+  const int B = c->plan.batch;
+  const int64_t N = c->plan.lv[level].n;
+  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
+  const size_t nws = netvlad_train_forward_floats(B, N, channels, out_dim);
+  EGONN_TRY(c->work_arena.ensure(nws * 4 + 4096));
+  c->work_arena.reset();
+  float* ws = c->work_arena.alloc<float>(nws);
+  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
+  return netvlad_train_forward(x, c->plan.lv[level].boff, B, N, channels, nmax, cluster_weights, cluster_weights2, bn1_weight,
+                               bn1_bias, bn1_eps, bn1_momentum, bn1_running_mean, bn1_running_var, hidden1_weights, out_dim, out,
+                               save_z, save_bn1, save_v, save_sq, save_asum, ws, (hipStream_t)stream);
+}
+
+API int egonn_netvlad_train_backward(egonn_ctx* c, int level, const float* x, int channels, int nmax,
+                                     const float* cluster_weights, const float* cluster_weights2, const float* bn1_weight,
+                                     const float* hidden1_weights, int out_dim, const float* grad_out, const float* save_z,
+                                     const float* save_bn1, const float* save_v, const float* save_sq, const float* save_asum,
+                                     float* grad_x, float* grad_cluster_weights, float* grad_cluster_weights2, float* out_bn1,
+                                     float* grad_hidden1_weights, void* stream) {
+  REQUIRE_PLAN(c);
+  EGONN_TRY(netvlad_train_check(c, level, channels, out_dim, nmax));
+  EGONN_REQUIRE(x && cluster_weights && cluster_weights2 && bn1_weight && hidden1_weights && grad_out && save_z && save_bn1 &&
+                    save_v && save_sq && save_asum && grad_x && grad_cluster_weights && grad_cluster_weights2 && out_bn1 &&
+                    grad_hidden1_weights,
+                EGONN_ERR_INVALID, "netvlad_train_backward: null argument");
+  EGONN_REQUIRE(((uintptr_t)x & 15) == 0, EGONN_ERR_INVALID, "netvlad_train_backward: x must be 16-byte aligned");
+  HIP_CHECK(hipSetDevice(c->device));
+  const int B = c->plan.batch;
+  const int64_t N = c->plan.lv[level].n;
+  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
+  const size_t nws = netvlad_train_backward_floats(B, N, channels, out_dim);
+  EGONN_TRY(c->work_arena.ensure(nws * 4 + 4096));
+  c->work_arena.reset();
+  float* ws = c->work_arena.alloc<float>(nws);
+  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
+  return netvlad_train_backward(x, save_z, c->plan.lv[level].boff, B, N, channels, nmax, cluster_weights, cluster_weights2,
+                                bn1_weight, save_bn1, hidden1_weights, out_dim, grad_out, save_v, save_sq, save_asum, grad_x,
+                                grad_cluster_weights, grad_cluster_weights2, out_bn1, grad_hidden1_weights, ws,
+                                (hipStream_t)stream);
+}
+
+// MAC with the winning plan row of every (scan, channel) (ties: lowest row; empty scan: 0 and row -1), and its backward
+API int egonn_global_max_pool_argmax(egonn_ctx* c, int level, const float* in, int channels, float* out, int32_t* out_rows,
+                                     void* stream) {
+  REQUIRE_PLAN(c);
+  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && in && out && out_rows && channels >= 1, EGONN_ERR_INVALID,
+                "global_max_pool_argmax: bad argument");
+  HIP_CHECK(hipSetDevice(c->device));
+  return global_max_argmax(in, c->plan.lv[level].boff, c->plan.batch, channels, out, out_rows, (hipStream_t)stream);
+}
+
+API int egonn_global_max_pool_backward(egonn_ctx* c, int level, const float* grad_out, const int32_t* rows, int channels,
+                                       float* grad_in, void* stream) {
+  REQUIRE_PLAN(c);
+  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && grad_out && rows && grad_in && channels >= 1, EGONN_ERR_INVALID,
+                "global_max_pool_backward: bad argument");
+  HIP_CHECK(hipSetDevice(c->device));
+  return global_max_backward(grad_out, rows, c->plan.batch, c->plan.lv[level].n, channels, grad_in, (hipStream_t)stream);
+}
+
+// out = y * sigmoid(t) (grad_out NULL), or its backward: grad_y = grad_out * s, grad_t = grad_out * y * s * (1 - s)
+API int egonn_sigmoid_gate(const float* y, const float* t, const float* grad_out, int64_t n, float* out, float* grad_y,
+                           float* grad_t, void* stream) {
+  EGONN_REQUIRE(y && t && n >= 0 && (grad_out ? (grad_y && grad_t) : out != nullptr), EGONN_ERR_INVALID,
+                "sigmoid_gate: bad argument");
+  return sigmoid_gate(y, t, grad_out, n, out, grad_y, grad_t, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------ model
 API int egonn_model_create(egonn_model** m) {
   EGONN_REQUIRE(m, EGONN_ERR_INVALID, "model_create: null out pointer");

@@ -26,16 +26,7 @@ namespace egonn {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-static constexpr int NV_K = 64;             // clusters (NetVLADWrapper fixes cluster_size = 64)
-static constexpr int NV_MAX_CHUNKS = 32;    // row chunks per scan in launch 1
-static constexpr int NV_CHUNK_ROWS = 128;   // target rows per chunk
 static constexpr int NV_BB = 16;            // scans per workgroup of launch 3
-
-__host__ __device__ static inline int nv_chunks(int32_t len) {
-  if (len <= 0) return 0;
-  const int n = (len + NV_CHUNK_ROWS - 1) / NV_CHUNK_ROWS;
-  return n < NV_MAX_CHUNKS ? n : NV_MAX_CHUNKS;
-}
 
 // ------------------------------------------------------------------ 1. assign + aggregate
 // Workgroup = 4 waves; wave w owns clusters 16w..16w+15.  Per tile of R = 16*RB rows (staged in LDS, row stride C+4 so that
@@ -337,15 +328,20 @@ static int launch_assign(const float* x, const int32_t* boff, int B, int C, cons
   return EGONN_OK;
 }
 
+void netvlad_workspace_carve(float* ws, int B, int C, float** part, float** vraw, float** sq, float** pp) {
+  *part = ws;
+  *vraw = *part + align_up((size_t)B * NV_MAX_CHUNKS * ((size_t)C * NV_K + NV_K), 64);
+  *sq = *vraw + align_up((size_t)B * C * NV_K, 64);
+  *pp = *sq + align_up((size_t)B * (C / 16) * NV_K, 64);
+}
+
 int netvlad_forward(const float* x, const int32_t* boff, int B, int C, const float* wc, const float* w2, const float* sc1,
                     const float* sh1, const float* H, int D, const float* sc2, const float* sh2, const float* wg,
                     const float* scg, const float* shg, int gating, float* out, float* ws, hipStream_t stream) {
   EGONN_REQUIRE(C >= 16 && C <= 512 && C % 16 == 0 && D >= 16 && D <= 1024 && D % 16 == 0 && B >= 1, EGONN_ERR_INVALID,
                 "netvlad: unsupported sizes C=%d D=%d B=%d", C, D, B);
-  float* part = ws;
-  float* vraw = part + align_up((size_t)B * NV_MAX_CHUNKS * ((size_t)C * NV_K + NV_K), 64);
-  float* sq = vraw + align_up((size_t)B * C * NV_K, 64);
-  float* pp = sq + align_up((size_t)B * (C / 16) * NV_K, 64);
+  float *part, *vraw, *sq, *pp;
+  netvlad_workspace_carve(ws, B, C, &part, &vraw, &sq, &pp);
   if (C <= 64) EGONN_TRY((launch_assign<4, 4>(x, boff, B, C, wc, sc1, sh1, part, stream)));
   else if (C <= 128) EGONN_TRY((launch_assign<8, 4>(x, boff, B, C, wc, sc1, sh1, part, stream)));
   else if (C <= 256) EGONN_TRY((launch_assign<16, 4>(x, boff, B, C, wc, sc1, sh1, part, stream)));

@@ -2,7 +2,7 @@
 per-operator entry points of libegonn_hip (reference: models/minkfpn.py, models/minkloc.py,
 third_party/minkloc3d/minkloc.py, models/resnet.py:81-117).  Same kernels as EgoNN, second graph; the module
 tree only holds parameters (identical state_dict keys/shapes), there is no PyTorch fallback.  MinkLoc's pooling
-(layers/pooling.py:13-43) is GeM, MAC, SPoC, netvlad or netvladgc; train mode implements GeM only.
+(layers/pooling.py:13-43) is GeM, MAC, SPoC, netvlad or netvladgc, in eval and in train mode (egonn_amd/train.py: pool).
 """
 from __future__ import annotations
 
@@ -136,9 +136,10 @@ class _MinkLocBase(nn.Module):
         raise NotImplementedError(f'Unknown pooling method: {method}')
 
     def _forward(self, batch: Dict[str, torch.Tensor], gem_p: torch.Tensor = None):
-        if self.training and self.pooling_method != 'GeM':
-            raise NotImplementedError(f"train mode implements GeM pooling only: pooling method {self.pooling_method!r} "
-                                      f"has no backward here (use the model in eval mode)")
+        method = self.pooling_method
+        if self.training and method != 'GeM' and next(self.parameters()).device.type != 'cuda':
+            raise NotImplementedError(f"pooling method {method!r} in train mode runs on the HIP device only; there is no "
+                                      f"CPU fallback")
         dev = self._device()
         ctx = self.context()
         coords = batch['coords'].to(device=dev, dtype=torch.int32).contiguous()
@@ -154,7 +155,9 @@ class _MinkLocBase(nn.Module):
                 raise NotImplementedError("train mode supports the reference's all-ones input features only")
             level, x = train.minkfpn_forward(self.backbone, ctx, self.sync_bn_group)
             assert x.shape[1] == self.feature_size
-            return {'global': train.GeMFn.apply(x, gem_p, ctx, level)}
+            if method == 'GeM':
+                return {'global': train.GeMFn.apply(x, gem_p, ctx, level)}
+            return {'global': train.pool(ctx, level, x, self.pooling.pooling, method, self.sync_bn_group)}
         with torch.no_grad():
             level, x = self.backbone.run(ctx, ctx.gather_input(feats))
             assert x.shape[1] == self.feature_size
@@ -176,7 +179,8 @@ class MinkLoc(_MinkLocBase):
         self.pooling = PoolingWrapper(pool_method=pooling_method, in_dim=feature_size, output_dim=output_dim)
         self.pooled_feature_size = self.pooling.output_dim
 
-    def forward(self, batch):
+    def forward(self, batch, disable_local_head: bool = True):
+        assert disable_local_head, "MinkLoc model has only the global head"
         return self._forward(batch, self.pooling.pooling.p if self.pooling_method == 'GeM' else None)
 
     def print_info(self):

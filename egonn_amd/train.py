@@ -327,6 +327,122 @@ class GeMFn(Function):
         return dx, dp, None, None
 
 
+# ----------------------------------------------------------------------------- MAC / NetVLAD pooling (layers/pooling.py)
+class GlobalMaxFn(Function):
+    """ME.MinkowskiGlobalMaxPooling (MAC, layers/pooling.py:46-56) -> (B, C); the gradient of (b, c) goes to the one plan
+    row that holds the maximum (ties: the lowest row; an empty scan gets none)."""
+
+    @staticmethod
+    def forward(fctx, x, ctx: _lib.Context, level: int):
+        out, rows = ctx.global_max_pool_argmax(level, _c(x))
+        fctx.save_for_backward(rows)
+        fctx.meta = (ctx, level)
+        return out
+
+    @staticmethod
+    def backward(fctx, g):
+        (rows,) = fctx.saved_tensors
+        ctx, level = fctx.meta
+        return ctx.global_max_pool_backward(level, _c(g), rows), None, None
+
+
+class MatmulFn(Function):
+    """rows @ W with W (in, out): GatingContext's gating_weights (layers/netvlad.py:101)."""
+
+    @staticmethod
+    def forward(fctx, x, weight, ctx: _lib.Context):
+        fctx.save_for_backward(x, weight)
+        fctx.meta = ctx
+        return ctx.dense(x, _c(weight.detach()), out_in=False)
+
+    @staticmethod
+    def backward(fctx, g):
+        x, weight = fctx.saved_tensors
+        ctx = fctx.meta
+        g = _c(g)
+        dx = ctx.dense(g, _c(weight.detach()), out_in=True) if fctx.needs_input_grad[0] else None     # g @ W^T
+        dw = ctx.dense_backward_weight(x, g) if fctx.needs_input_grad[1] else None
+        return dx, dw, None
+
+
+class SigmoidGateFn(Function):
+    """y * sigmoid(t) (GatingContext, layers/netvlad.py:108-110)."""
+
+    @staticmethod
+    def forward(fctx, y, t, ctx: _lib.Context):
+        fctx.save_for_backward(y, t)
+        fctx.meta = ctx
+        return ctx.sigmoid_gate(y, t)
+
+    @staticmethod
+    def backward(fctx, g):
+        y, t = fctx.saved_tensors
+        dy, dt = fctx.meta.sigmoid_gate(y, t, _c(g))
+        return dy, dt, None
+
+
+class NetVLADFn(Function):
+    """The row part of NetVLADLoupe.forward in train mode (layers/netvlad.py:44-73 under NetVLADWrapper's zero padding to the
+    largest scan): bn1 on the statistics of all B * Nmax rows (pad rows included), soft assignment, aggregation, the two
+    normalisations and the projection: (B, D) before bn2.  Forward and backward are egonn_netvlad_train_forward /
+    _backward; Nmax comes from the host offsets of the plan."""
+
+    @staticmethod
+    def forward(fctx, x, cluster_weights, cluster_weights2, bn1_weight, bn1_bias, hidden1_weights, ctx: _lib.Context,
+                level: int, bn1: torch.nn.BatchNorm1d):
+        off = ctx.level_batch_offsets(level)
+        nmax = max(off[b + 1] - off[b] for b in range(ctx.batch_size))
+        x = _c(x)
+        y, saved = ctx.netvlad_train_forward(level, x, nmax, cluster_weights, cluster_weights2, bn1, hidden1_weights)
+        bn1.num_batches_tracked += 1
+        fctx.save_for_backward(x, cluster_weights, cluster_weights2, bn1_weight, hidden1_weights, *saved)
+        fctx.meta = (ctx, level, nmax)
+        return y
+
+    @staticmethod
+    def backward(fctx, g):
+        x, wc, w2, g1, H, *saved = fctx.saved_tensors
+        ctx, level, nmax = fctx.meta
+        dx, dwc, dw2, dg1, db1, dH = ctx.netvlad_train_backward(level, x, nmax, wc, w2, g1, H, _c(g), saved)
+        return dx, dwc, dw2.reshape(w2.shape), dg1, db1, dH, None, None, None
+
+
+def netvlad_pool(ctx, level: int, x: torch.Tensor, nv, group=None) -> torch.Tensor:
+    """NetVLADLoupe (+ GatingContext) in train mode over the rows of `level`: NetVLADFn, then bn2 and the gating on the
+    (B, D) descriptors through the differentiable row operators (batch statistics over the B descriptors)."""
+    if group is not None:
+        raise NotImplementedError("NetVLAD pooling with a SyncBN process group: Nmax and the B-row statistics would have to "
+                                  "span the ranks")
+    if ctx.batch_size < 2:            # nn.BatchNorm1d's own rule for bn2, before any device work
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                         f"torch.Size([{ctx.batch_size}, {nv.output_dim}])")
+    for w in (nv.cluster_weights, nv.cluster_weights2, nv.hidden1_weights):
+        assert w.is_contiguous() and w.dtype == torch.float32
+    y = NetVLADFn.apply(x, nv.cluster_weights, nv.cluster_weights2, nv.bn1.weight, nv.bn1.bias, nv.hidden1_weights, ctx, level,
+                        nv.bn1)
+    y = BatchNormFn.apply(y, nv.bn2.weight, nv.bn2.bias, ctx, nv.bn2, False, None, None)
+    if nv.gating:
+        cg = nv.context_gating
+        t = MatmulFn.apply(y, cg.gating_weights, ctx)
+        t = BatchNormFn.apply(t, cg.bn1.weight, cg.bn1.bias, ctx, cg.bn1, False, None, None)
+        y = SigmoidGateFn.apply(y, t, ctx)
+    return y
+
+
+def pool(ctx, level: int, x: torch.Tensor, pooling, method: str, group=None) -> torch.Tensor:
+    """PoolingWrapper.forward in train mode (layers/pooling.py:13-43): `pooling` is the GeM / MAC / SPoC / NetVLADWrapper
+    module, `method` its name."""
+    if method == 'GeM':
+        return GeMFn.apply(x, pooling.p, ctx, level)
+    if method == 'MAC':
+        return GlobalMaxFn.apply(x, ctx, level)
+    if method == 'SPoC':
+        return SegmentMeanFn.apply(x, ctx, level)
+    if method in ('netvlad', 'netvladgc'):
+        return netvlad_pool(ctx, level, x, pooling.net_vlad, group)
+    raise NotImplementedError(f'Unknown pooling method: {method}')
+
+
 # ----------------------------------------------------------------------------- the graph
 def trunk_forward(model, ctx, group=None) -> Dict[int, torch.Tensor]:
     """MinkTrunk.forward (reference models/minkgl.py:136-153) with all-ones input features."""
@@ -363,18 +479,14 @@ def head_forward(head, ctx, levels: Dict[int, torch.Tensor]):
 
 
 def global_branch(model, ctx, group=None, levels=None) -> torch.Tensor:
-    """trunk -> global head -> descriptor decoder -> GeM  (reference models/minkgl.py:269-287)."""
+    """trunk -> global head -> descriptor decoder -> GeM / MAC / SPoC  (reference models/minkgl.py:269-287)."""
     if levels is None:
         levels = trunk_forward(model, ctx, group)
     lvl, x = head_forward(model.global_head, ctx, levels)
     net = model.global_descriptor_decoder.net
     x = LinearFn.apply(x, net[0].linear.weight, net[0].linear.bias, ctx, True)
     x = LinearFn.apply(x, net[2].linear.weight, net[2].linear.bias, ctx, False)
-    method = getattr(model, "global_pool_method", "GeM")
-    if method != "GeM":          # MAC / SPoC (layers/pooling.py:46-69) exist for eval-mode forwards only
-        raise NotImplementedError(f"train-mode forward is implemented for GeM pooling; this model pools with {method!r} "
-                                  "(use model.eval(), or train with pool_method='GeM' as config_egonn.txt does)")
-    return GeMFn.apply(x, model.global_pooling.pooling.p, ctx, lvl)
+    return pool(ctx, lvl, x, model.global_pooling.pooling, getattr(model, "global_pool_method", "GeM"), group)
 
 
 def minkfpn_forward(fpn, ctx, group=None):

@@ -220,6 +220,50 @@ int egonn_netvlad(egonn_ctx* ctx, int level, const float* x, int channels, const
                   const float* hidden1_weights, const float* bn2_scale, const float* bn2_shift,
                   const float* gating_weights, const float* gate_scale, const float* gate_shift, int out_dim, int gating,
                   float* out, void* stream);
+/* NetVLAD / NetVLAD-GC in TRAIN mode, the part of NetVLADLoupe.forward (layers/netvlad.py:44-73, under NetVLADWrapper's
+ * pad_sequence, layers/pooling.py:97-109) that works on rows: out (B, out_dim) = normalize(normalize_c(V)) @ hidden1_weights,
+ * BEFORE bn2 (bn2 and the context gating are (B, out_dim) row operators: egonn_col_stats / egonn_bn_train_finalize /
+ * egonn_affine_act, egonn_dense, egonn_sigmoid_gate).  Layouts and limits as egonn_netvlad; B >= 2 (batch statistics).
+ * bn1 / pad rule: bn1 normalises the logits Z = X @ cluster_weights of all M = B * nmax rows of the zero-padded batch, nmax =
+ * the largest scan of the level (HOST value, from egonn_level_batch_offsets).  A pad row has Z = 0, so mean = (sum_real z) / M
+ * and the biased variance (sum_real z^2) / M - mean^2, formed in fp64 around bn1_running_mean; every pad row then has the logits
+ * beta - mean * gamma * invstd, the folded shift, and adds softmax(shift) to the cluster mass exactly as in eval mode.  The
+ * running statistics are updated in place (momentum, unbiased factor M / (M - 1)); num_batches_tracked is the caller's.
+ * Saved for the backward (caller-owned): save_z (N_l, 64) = Z, save_bn1 (4, 64) = mean, invstd, scale, shift, save_v
+ * (B, channels, 64) = V before the normalisations, save_sq (B, channels / 16, 64) its squared-norm partials, save_asum (B, 64).
+ * Exact fp32 (f32 MFMA / FMA), fp64 BatchNorm sums, no atomics, no host synchronisation, workspace from the context. */
+int egonn_netvlad_train_forward(egonn_ctx* ctx, int level, const float* x, int channels, int nmax,
+                                const float* cluster_weights, const float* cluster_weights2, const float* bn1_weight,
+                                const float* bn1_bias, float bn1_eps, float bn1_momentum, float* bn1_running_mean,
+                                float* bn1_running_var, const float* hidden1_weights, int out_dim, float* out, float* save_z,
+                                float* save_bn1, float* save_v, float* save_sq, float* save_asum, void* stream);
+/* Its backward: grad_out (B, out_dim) -> grad_x (N_l, channels), grad_cluster_weights (channels, 64), grad_cluster_weights2
+ * (channels, 64), grad_hidden1_weights (channels * 64, out_dim) and out_bn1 (5, 64) whose rows 3 and 4 are the gradients of
+ * bn1's weight and bias (rows 0-2: the coefficients of dZ = a dL + b Z + c).  The (nmax - n_b) pad rows of every scan are
+ * added analytically to bn1's sums (assignment softmax(shift), dA = da_sum_b, z - mean = -mean): they carry gradient into
+ * gamma, beta, the mean and the variance.  The two F.normalize backwards keep the reference's eps 1e-12 clamps.
+ * Summation orders: rows in chunks that are a function of the scan's own row count (128-row target, at most 32), chunks in
+ * order, scans in batch order; bitwise reproducible; a scan's rows of grad_x depend on the other scans only through the
+ * bn1 vectors and nmax.  Same limits, same arithmetic and workspace rules as the forward. */
+int egonn_netvlad_train_backward(egonn_ctx* ctx, int level, const float* x, int channels, int nmax,
+                                 const float* cluster_weights, const float* cluster_weights2, const float* bn1_weight,
+                                 const float* hidden1_weights, int out_dim, const float* grad_out, const float* save_z,
+                                 const float* save_bn1, const float* save_v, const float* save_sq, const float* save_asum,
+                                 float* grad_x, float* grad_cluster_weights, float* grad_cluster_weights2, float* out_bn1,
+                                 float* grad_hidden1_weights, void* stream);
+/* MAC pooling with its argmax: out (B, channels) as egonn_global_max_pool, out_rows (B, channels) int32 = the plan row that
+ * holds the maximum (-1 for an empty sample).  Tie rule: the LOWEST plan row wins.  [ME-recall, unpinned]: which of two tied
+ * rows MinkowskiGlobalMaxPooling routes the gradient to is not checked against MinkowskiEngine (absent from the build); the
+ * fixtures hold no tie.  Any channels >= 1. */
+int egonn_global_max_pool_argmax(egonn_ctx* ctx, int level, const float* in, int channels, float* out, int32_t* out_rows,
+                                 void* stream);
+/* Its backward: grad_in (N_l, channels) = 0 except grad_in[rows[b][c]][c] = grad_out[b][c]; an empty sample gets nothing. */
+int egonn_global_max_pool_backward(egonn_ctx* ctx, int level, const float* grad_out, const int32_t* rows, int channels,
+                                   float* grad_in, void* stream);
+/* GatingContext's product (layers/netvlad.py:108-110) on n values: grad_out NULL: out = y * sigmoid(t); else
+ * grad_y = grad_out * s and grad_t = grad_out * y * s * (1 - s), s = sigmoid(t). */
+int egonn_sigmoid_gate(const float* y, const float* t, const float* grad_out, int64_t n, float* out, float* grad_y,
+                       float* grad_t, void* stream);
 
 /* ------------------------------------------------------------------ model
  * replaces model_factory(...) / MinkGL.forward: models/model_factory.py:31-76, models/minkgl.py:267-315       */
