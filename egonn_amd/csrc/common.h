@@ -187,6 +187,31 @@ struct Profiler {
   hipEvent_t get();
 };
 
+// ------------------------------------------------------------------ measurement switches (coords.hip)
+// Environment variables for tests and A/B measurements, read ONCE per process on first use; the product sets none of them
+// (DESIGN.md "Measurement switches": which change arithmetic, which only scheduling).
+struct Switches {
+  bool debug_sync;         // EGONN_DEBUG_SYNC=1         egonn_forward synchronises after every stage and prints its name (never in captures)
+  bool no_presplit;        // EGONN_NO_PRESPLIT          conv2 splits its operands in its step loop instead of reading conv1's split-form output
+  bool no_fused_down;      // EGONN_NO_FUSED_DOWN        1x1 downsample branch + BatchNorm and the gated residual + ReLU as two launches
+  bool no_fused_lateral;   // EGONN_NO_FUSED_LATERAL     the local head's level-3 lateral 1x1 convolution as its own launch
+  bool no_gated_k2s2;      // EGONN_NO_GATED_K2S2        level 1's block tail as its own launch instead of inside level 2's strided convolution
+  bool no_fused_ghead;     // EGONN_NO_FUSED_GHEAD       the global head as five launches instead of three
+  bool no_split_heads;     // EGONN_NO_SPLIT_HEADS       the local heads' Linear layers on the exact fp32 kernel instead of the fp16 matrix pipe
+  bool no_tail_split;      // EGONN_NO_TAIL_SPLIT        128->128 maps above the split level limit on the exact per-tile kernel
+  bool no_task_order;      // EGONN_NO_TASK_ORDER        sparse-conv tasks in table order instead of longest-first (RowGroups::order4)
+  bool flat_sort, sort_pairs;   // EGONN_FLAT_SORT / EGONN_SORT_PAIRS  plan sort on flat (batch | Morton) keys / on (key, value) pairs
+  bool no_search67;        // EGONN_NO_SEARCH67          k=3 maps of levels 6-7 derived from levels 8-9 instead of searched
+  int split_max_level;     // EGONN_SPLIT_MAX_LEVEL=l    replaces a context's split level limit (unless that is -1: exact fp32); -1 = unset
+  int split_max_level_k8;  // EGONN_SPLIT_MAX_LEVEL_K8=l the limit of the 8-slot maps (k=2,s=2 and transposed) alone; -1 = unset
+  int split_cfg;           // EGONN_SPLIT_CFG=cfg        workgroup shape of the lock-step split kernel (sconv_split_forward); 0 = unset
+  int rg_first_pass;       // EGONN_RG_FIRST_PASS=0..2   variant of the first pass of the row-group build (rowgroup.hip)
+  // EGONN_KSPLIT, EGONN_KSPLIT8, EGONN_KSPLIT_KW, EGONN_KSPLIT_KW8, EGONN_KSPLIT_PARTS: comma lists indexed by the output level that
+  // replace the offset-split rule below (kparts and kw of the k=3 / 8-slot maps, column parts per task); null = unset
+  const char* ksplit[5];
+};
+const Switches& switches();
+
 // Offset-split rule of the fp32 lock-step kernels (sconv_ksplit_rule): [0] = k=3 maps, [1] = 8-slot maps, indexed by output level
 struct KsRule {
   int8_t kparts[2][EGONN_NUM_LEVELS];   // offset parts as separate workgroups + reducer launch (1 = none)
@@ -204,15 +229,10 @@ struct Ctx {
   int split_max_level = 5;    // fp32 sparse convs whose output level is <= this run on the fp16-split kernels (sconv_split.hip);
                               // round 5: 4 -> 5 (profiles/r05b_tail_kernel.txt: 25.2 k -> 26.4 k scans/s with four batches in flight; the
                               // level-5 launches alone get slower, one-batch graph latency 1.17 -> 1.23 ms — the headline metric is scans/s)
-  int split_io = 0;           // set by egonn_forward around ONE sconv_map call: bit 0 = the input map is in split form (fp16 hi | lo
-                              // per 32-channel block, sconv_split.hip), bit 1 = write the output in split form
-  const float* gated_in2 = nullptr;   // set by egonn_forward around ONE sconv_map call: the convolution's input row r is
-  const float* gated_gate = nullptr;  // relu(in[r] * gate[scan] + in2[r]) — the tail of the ECA block below, never materialised
   float* ks_part = nullptr;   // scratch for the partial tiles of the offset-split launches (sconv_split.hip): carved from the work arena
   size_t ks_part_floats = 0;  // by egonn_forward / the stand-alone operator entry points (sconv_ksplit_scratch_floats)
   const void* sort_prezeroed = nullptr;   // the per-scan histograms of the segmented sort were zeroed by the kernel in front of it
   int keep_level_features = 0;   // egonn_debug_keep_level_features: no fusion that leaves a level's block output unmaterialised
-  const float* conv_residual = nullptr;   // set by egonn_forward around ONE sconv_map call (fp32 maps): out += residual in the epilogue
   int operand_autoscale = 0;  // egonn_ctx_set_operand_autoscale: the fp16-split convolutions scale their INPUT by a power of two per launch
                               // (max |in| -> [2^13, 2^14), undone in the epilogue): the input-gradient convolutions of a training step
   int conv_variant = 0;       // tests / A-B measurements only (egonn_debug_set_naive_conv): 0 = product choice, 1 = per-wave

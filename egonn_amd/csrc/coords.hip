@@ -26,6 +26,24 @@ void set_error(const char* fmt, ...) {
 }
 const char* last_error() { return g_err; }
 
+const Switches& switches() {
+  static const Switches sw = [] {
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+    const char* ds = getenv("EGONN_DEBUG_SYNC");
+    return Switches{.debug_sync = ds && ds[0] == '1', .no_presplit = on("EGONN_NO_PRESPLIT"), .no_fused_down = on("EGONN_NO_FUSED_DOWN"),
+                    .no_fused_lateral = on("EGONN_NO_FUSED_LATERAL"), .no_gated_k2s2 = on("EGONN_NO_GATED_K2S2"),
+                    .no_fused_ghead = on("EGONN_NO_FUSED_GHEAD"), .no_split_heads = on("EGONN_NO_SPLIT_HEADS"),
+                    .no_tail_split = on("EGONN_NO_TAIL_SPLIT"), .no_task_order = on("EGONN_NO_TASK_ORDER"),
+                    .flat_sort = on("EGONN_FLAT_SORT"), .sort_pairs = on("EGONN_SORT_PAIRS"), .no_search67 = on("EGONN_NO_SEARCH67"),
+                    .split_max_level = num("EGONN_SPLIT_MAX_LEVEL", -1), .split_max_level_k8 = num("EGONN_SPLIT_MAX_LEVEL_K8", -1),
+                    .split_cfg = num("EGONN_SPLIT_CFG", 0), .rg_first_pass = num("EGONN_RG_FIRST_PASS", 0),
+                    .ksplit = {getenv("EGONN_KSPLIT"), getenv("EGONN_KSPLIT8"), getenv("EGONN_KSPLIT_KW"), getenv("EGONN_KSPLIT_KW8"),
+                               getenv("EGONN_KSPLIT_PARTS")}};
+  }();
+  return sw;
+}
+
 int Arena::ensure(size_t bytes) {
   if (bytes <= cap) return EGONN_OK;
   size_t want = align_up(bytes + bytes / 4, size_t(1) << 20);
@@ -811,13 +829,10 @@ int plan_sync(Ctx* ctx, hipStream_t stream) {
 // are the exact row counts (one host sync right after the pyramid); true: ctx->reserve_cap[] (no host sync at all).
 // seg_off (nullable): DEVICE scan offsets (B+1) when the rows arrive scan by scan (plans built from points)
 // measurement switch: the round-3 flat sort of (batch | Morton) keys also for plans built from points
-static bool plan_flat_sort() {
-  static const bool v = getenv("EGONN_FLAT_SORT") != nullptr;
-  return v;
-}
+static bool plan_flat_sort() { return switches().flat_sort; }
 // bits of the point index inside its scan that a packed sort element can carry next to the 3 * cb Morton bits (0 = pairs)
 static int plan_packed_idx_bits(int cb, int64_t n) {
-  static const bool off = getenv("EGONN_SORT_PAIRS") != nullptr;          // measurement switch: (key, value) pairs as in round 4
+  const bool off = switches().sort_pairs;                 // measurement switch: (key, value) pairs as in round 4
   const int room = std::min(64 - 3 * cb, 30);
   if (off || plan_flat_sort() || room < 1 || n >= (int64_t(1) << room)) return 0;
   return room;
@@ -919,7 +934,7 @@ static int build_plan_from_sorted_input(Ctx* ctx, uint64_t* keys_raw, uint32_t* 
   }
   // levels 6 and 7 (1 488 + 682 rows at batch 16) by search too: bitwise the tables nbr27_kernel derives from levels 8 / 9, and the
   // chain of dependent nbr27 launches is three instead of four.  (Capped: a level beyond 8 192 rows keeps the derived path.)
-  static const bool search67_ok = getenv("EGONN_NO_SEARCH67") == nullptr;              // measurement switch
+  const bool search67_ok = !switches().no_search67;       // measurement switch
   const int search_from = (search67_ok && P.cap[NL - 4] <= 8192 && P.cap[NL - 3] <= 8192) ? NL - 4 : NL - 2;
   ta.b_adj2 = 0;
   ta.adj2 = ta.adj;

@@ -14,44 +14,71 @@ bool sconv_rg_supported(int cin, int cout);
 int pack_rg_weights(const float* W, int K, int cin, int cout, int bf16, int flip, int transpose, void* out,
                     hipStream_t stream);
 extern unsigned long long* g_sconv_trace;
-// name of the kernel sconv_map dispatches for (map kind, output level, channel plan) under this context's settings
+// One sparse-convolution kernel in the forms the kernels read (egonn_model_finalize packs every kernel of the graph once)
+struct PackedKernel {
+  const void* rg32 = nullptr;    // pack_rg_weights, fp32
+  const void* rg16 = nullptr;    // pack_rg_weights, bf16
+  const void* split = nullptr;   // pack_split_weights: the fp16-split path of fp32 maps (null: sconv_split_supported says no)
+};
+// One convolution over a map of the plan.  kind 0: k=3 on `level`; 1: k=2,s=2 from level-1 into `level`; 2: transposed from
+// level+1 onto `level`.  bf16: feature maps in/out and weights are bf16.
+struct ConvCall {
+  int kind = 0, level = 0;
+  const void* in = nullptr; void* out = nullptr;
+  int cin = 0, cout = 0, bf16 = 0;
+  const float *scale = nullptr, *shift = nullptr;   // folded BatchNorm (nullable)
+  int relu = 0;
+  float* psum = nullptr;                 // (nullable) [groups][cout] per-group column sums of the output
+  // the kernel: packed at finalize, or (stand-alone operators) W [K][cin][cout] in reference layout + scratch to pack it into
+  const PackedKernel* packed = nullptr;
+  const float* W = nullptr; float* scratch = nullptr; size_t scratch_floats = 0;
+  // extras of this one call (the split kernel; the residual also in the per-tile kernel of fp32 maps, levels >= 5)
+  int split_io = 0;                      // bit 0 = the input map is in split form (fp16 hi | lo per 32-channel block), bit 1 = write split form
+  const float *in2 = nullptr, *gate = nullptr;   // input row r = relu(in[r] * gate[scan] + in2[r]): the tail of an ECA block, never materialised
+  const float* residual = nullptr;       // out += residual ([n_out][cout] fp32) in the epilogue
+};
+// Kernel family a layer runs on: a function of the LAYER and the context's settings, never of the batch.  sconv_route alone decides it.
+enum SconvRoute {
+  ROUTE_PLAIN,        // one thread per output (conv.hip): debug variant 3, channel plans without an MFMA instantiation
+  ROUTE_SPLIT,        // lock-step fp16-split kernel (sconv_split.hip)
+  ROUTE_TAIL_SPLIT,   // per-tile kernel on fp16-split arithmetic: 128->128 fp32 maps above the split level limit
+  ROUTE_WG,           // workgroup-cooperative exact kernel
+  ROUTE_DMA,          // LDS-DMA exact kernel (fp32 maps)
+  ROUTE_RG            // per-tile exact kernel
+};
+SconvRoute sconv_route(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16);
+bool sconv_split_arithmetic(const Ctx* ctx);   // the product rule with fp16-split arithmetic allowed (no exact-fp32 / debug variant)
+// name of that kernel (the profiler tags carry it: bench.py's roofline leg keys on it)
 const char* sconv_kernel_name(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16);
-// level: output level of the map (selects the prefetch depth / kernel family: a function of the LAYER, never of a capacity)
-int sconv_rg_forward(const void* in, int64_t n_in_cap, const RowGroups& rg, int64_t groups_hint, const void* Wp, int cin,
-                     int cout, int bf16, const float* scale, const float* shift, int relu, void* out, float* psum,
-                     hipStream_t stream, int variant = 0, int level = 0,
-                     int split = 0, int32_t* flags = nullptr,    // split: Wp = pack_split_weights form, fp16-split arithmetic (128->128 fp32 maps)
-                     const float* residual = nullptr);           // out += residual (fp32 maps) in the epilogue
+// What sconv_map chose for one launch of sconv_rg_forward / sconv_split_forward
+struct SconvLaunch {
+  SconvRoute route = ROUTE_RG;
+  const RowGroups* rg = nullptr;         // row-group form of the map
+  int64_t n_in_cap = 0;                  // rows the input map can hold
+  int64_t groups_hint = 0;               // host upper bound of the groups in use (sizes the grid only; the kernels read rg->meta[0])
+  const void* Wp = nullptr;              // the kernel in the form the route reads
+  int variant = 0;                       // rg: ctx->conv_variant (A/B choice among the exact kernels); split: cfg, 0 = product choice
+  bool small = false;                    // rg: a level that never fills the chip (deeper prefetch)
+  int32_t* flags = nullptr;              // the plan's flag word (bit 3: fp16 range guard); split arithmetic only
+  int B = 0;                             // split, gated input: scans of the batch
+  int kparts = 1, kw = 0, col_parts = 0; // split: offset parts as workgroups / inside a workgroup (0, 1: none), column parts per task (0 = automatic)
+  float* part = nullptr; size_t part_floats = 0;           // split: scratch for the partial tiles of an offset-split launch
+  uint32_t* in_absmax = nullptr; int64_t in_elems = 0;     // split, operand autoscale: 8 bytes of scratch, the elements of `in`
+};
+int sconv_rg_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream);
 // three independent (n_i, 128) @ (128, 128) products in one launch (dense.hip)
 int dense_small_group3(const float* const* in, const int64_t* n, const int32_t* const* n_dev, const float* const* W, float* const* out,
                        hipStream_t stream);
-// Convolution over a map of the plan.  kind 0: k=3 on `level`; 1: k=2,s=2 from level-1 into `level`; 2: transposed from
-// level+1 onto `level`.  Wp: kernel already packed for this precision (or null: W is packed into `scratch` first).
-// bf16: feature maps in/out and weights are bf16.  psum (nullable): [groups][cout] per-group column sums of the output.
-// Wsp: the kernel packed for the split-bf16 path (pack_split_weights; fp32 maps only, nullable like Wp).
-int sconv_map(Ctx* ctx, int kind, int level, const void* in, const float* W, const void* Wp, const void* Wsp, int cin, int cout,
-              int bf16, const float* scale, const float* shift, int relu, void* out, float* psum, float* scratch,
-              size_t scratch_floats, hipStream_t stream);
-bool sconv_uses_split(int cin, int cout, int bf16, int level, int variant, int split_max_level, int kind = 0);
+int sconv_map(Ctx* ctx, const ConvCall& c, hipStream_t stream);
 // sconv_split.hip: fp32 maps on the fp16 matrix pipe (two-way split operands, three products, fp32 accumulate)
 bool sconv_split_supported(int cin, int cout);
 int pack_split_weights(const float* W, int K, int cin, int cout, int flip, int transpose, void* out, hipStream_t stream);
 size_t split_weights_bytes(int K, int cin, int cout);   // fragments + 16 bytes (inverse of the pack scale)
-int sconv_split_default_cfg(int cin, int cout, int64_t groups_hint);
-int sconv_split_forward(const float* in, int64_t n_in_cap, const RowGroups& rg, int64_t groups_hint, const void* Wsp, int cin,
-                        int cout, const float* scale, const float* shift, int relu, float* out, float* psum, hipStream_t stream,
-                        int cfg = 0, int split_io = 0,       // split_io: bit 0 = input map in split form, bit 1 = write split form
-                        const float* gated_in2 = nullptr, const float* gated_gate = nullptr, int B = 0,    // input row = relu(in * gate[scan] + in2)
-                        int kparts = 1, float* part = nullptr, size_t part_floats = 0,   // offset-split launch: parts, scratch for the partial tiles
-                        int col_parts = 0,                                                // column parts per task (0 = automatic)
-                        int kw = 0,                                                       // offset parts INSIDE a workgroup (0 / 1: none; 2, 3, 4)
-                        int32_t* flags = nullptr,                                         // the plan's flag word (bit 3: fp16 range guard)
-                        uint32_t* in_absmax = nullptr, int64_t in_elems = 0,              // operand autoscale: 8 bytes of scratch, elements of `in`
-                        const float* residual = nullptr);                                 // out += residual ([n_out][cout] fp32) in the epilogue
+int sconv_split_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream);
 size_t sconv_split_part_floats(const RowGroups& rg, int cout, int kparts);
 // Offset-split rule of the fp32 lock-step kernels: parts of the map's K offsets (1 = unsplit) and column parts per task for
 // (map kind, output level) — a function of the LAYER only (the partition changes the summation order of a row)
-void sconv_ksplit_rule(const Ctx* ctx, int kind, int level, int* kparts, int* col_parts, int* kw = nullptr);
+void sconv_ksplit_rule(const Ctx* ctx, int kind, int level, int* kparts, int* col_parts, int* kw);
 void sconv_ksplit_defaults(KsRule* r);                  // the product rule (+ the EGONN_KSPLIT* measurement overrides)
 size_t sconv_ksplit_scratch_floats(const Ctx* ctx);    // partial-tile scratch that covers every map of the context's plan
 static constexpr size_t SCONV_SCRATCH_FLOATS = (size_t)2 << 20;   // 8 MB: one packed kernel (27 x 256 x 256 fp32 = 7 MB)

@@ -10,7 +10,6 @@
 #include "../../include/egonn_hip.h"
 #include "common.h"
 #include "kernels.h"
-#include <stdlib.h>
 
 using namespace egonn;
 
@@ -74,11 +73,7 @@ struct egonn_model {
   void* conv0_unit = nullptr;   // conv0_pack_unit(conv0): 24 KB
   void* lh_pack = nullptr;      // local_heads_pack: the heads' six Linear kernels as fp16 hi | lo fragments (92 KB)
   const float** lh_ptrs = nullptr;   // device array of the six weight pointers (the packer's input)
-  const float *p_convs[8] = {}, *p_c1[8] = {}, *p_c2[8] = {}, *p_gt[8] = {}, *p_lt[8] = {};
-  // the same kernels packed as bf16 (EGONN_FLAG_BF16): [0] = fp32 set, [1] = bf16 set
-  const float *q_convs[8] = {}, *q_c1[8] = {}, *q_c2[8] = {}, *q_gt[8] = {}, *q_lt[8] = {};
-  // the same kernels as hi|mid|lo bf16 fragments for the split-bf16 fp32 path (sconv_split.hip)
-  const float *s_convs[8] = {}, *s_c1[8] = {}, *s_c2[8] = {}, *s_gt[8] = {}, *s_lt[8] = {};
+  PackedKernel pk_convs[8], pk_c1[8], pk_c2[8], pk_gt[8], pk_lt[8];   // fp32, bf16 (EGONN_FLAG_BF16) and fp16-split forms
 };
 
 // ------------------------------------------------------------------------------------------ lifecycle
@@ -343,6 +338,14 @@ static float* op_scratch(egonn_ctx* c) {
   return scratch;
 }
 
+// a convolution of a stand-alone operator entry point: the kernel in reference layout, packed into the work arena per call
+static int op_conv(egonn_ctx* c, int kind, int level, const void* in, int cin, const float* kernel, int cout, int bf16,
+                   const float* scale, const float* shift, int relu, void* out, float* psum, void* stream) {
+  const ConvCall cc{.kind = kind, .level = level, .in = in, .out = out, .cin = cin, .cout = cout, .bf16 = bf16, .scale = scale,
+                    .shift = shift, .relu = relu, .psum = psum, .W = kernel, .scratch = op_scratch(c), .scratch_floats = SCONV_SCRATCH_FLOATS};
+  return sconv_map(c, cc, (hipStream_t)stream);
+}
+
 API int egonn_conv(egonn_ctx* c, int level_in, int level_out, int ks, const float* in, int cin, const float* kernel,
                    int cout, const float* scale, const float* shift, int relu, float* out, void* stream) {
   REQUIRE_PLAN(c);
@@ -364,13 +367,11 @@ API int egonn_conv(egonn_ctx* c, int level_in, int level_out, int ks, const floa
   if (ks == 3) {
     EGONN_REQUIRE(level_in == level_out && level_in >= 1, EGONN_ERR_INVALID,
                   "k=3 convolution is implemented for levels 1..7 (same in/out level)");
-    return sconv_map(c, 0, level_out, in, kernel, nullptr, nullptr, cin, cout, 0, scale, shift, relu, out, nullptr, op_scratch(c),
-                     SCONV_SCRATCH_FLOATS, st);
+    return op_conv(c, 0, level_out, in, cin, kernel, cout, 0, scale, shift, relu, out, nullptr, st);
   }
   if (ks == 2) {
     EGONN_REQUIRE(level_out == level_in + 1, EGONN_ERR_INVALID, "k=2,s=2 convolution maps level l to l+1");
-    return sconv_map(c, 1, level_out, in, kernel, nullptr, nullptr, cin, cout, 0, scale, shift, relu, out, nullptr, op_scratch(c),
-                     SCONV_SCRATCH_FLOATS, st);
+    return op_conv(c, 1, level_out, in, cin, kernel, cout, 0, scale, shift, relu, out, nullptr, st);
   }
   set_error("conv: kernel_size %d not supported (1, 2, 3, 5)", ks);
   return EGONN_ERR_INVALID;
@@ -383,8 +384,7 @@ API int egonn_conv_transpose(egonn_ctx* c, int level_in, const float* in, int ci
   EGONN_REQUIRE(level_in >= 1 && level_in < EGONN_NUM_LEVELS, EGONN_ERR_INVALID,
                 "transposed conv: input level %d out of range [1,7]", level_in);
   if (level_in == 1) EGONN_TRY(ensure_level0_parent_table(c, (hipStream_t)stream));
-  return sconv_map(c, 2, level_in - 1, in, kernel, nullptr, nullptr, cin, cout, 0, nullptr, nullptr, 0, out, nullptr, op_scratch(c),
-                   SCONV_SCRATCH_FLOATS, (hipStream_t)stream);
+  return op_conv(c, 2, level_in - 1, in, cin, kernel, cout, 0, nullptr, nullptr, 0, out, nullptr, stream);
 }
 
 // Sparse convolution on a map of the plan with explicit precision (the operator behind egonn_conv / egonn_conv_transpose).
@@ -394,8 +394,7 @@ API int egonn_sparse_conv(egonn_ctx* c, int map_kind, int level_out, const void*
   REQUIRE_PLAN(c);
   HIP_CHECK(hipSetDevice(c->device));
   EGONN_REQUIRE(in && kernel && out, EGONN_ERR_INVALID, "sparse_conv: null argument");
-  return sconv_map(c, map_kind, level_out, in, kernel, nullptr, nullptr, cin, cout, bf16, scale, shift, relu, out, group_sums,
-                   op_scratch(c), SCONV_SCRATCH_FLOATS, (hipStream_t)stream);
+  return op_conv(c, map_kind, level_out, in, cin, kernel, cout, bf16, scale, shift, relu, out, group_sums, stream);
 }
 // Row-group tables of every kernel map of the plan a training step (or a sequence of stand-alone operator calls) uses, in ONE
 // launch: k=3 and k=2,s=2 maps of levels 1..7, transposed maps onto levels 0..6 (with_level0_transpose: the input gradient of the
@@ -856,15 +855,13 @@ API int egonn_model_finalize(egonn_model* m, void* stream) {
     float* pc = m->packed;
     uint16_t* qc = reinterpret_cast<uint16_t*>(m->packed + need_p);      // bf16 copies behind the fp32 ones
     uint16_t* sc = reinterpret_cast<uint16_t*>(m->packed + need_p + need_p / 2 + 16);   // split fragments behind the bf16 ones
-    auto pack2 = [&](const float* w, int K, int ci, int co, const float** dst32, const float** dst16, const float** dsts) -> int {
+    auto pack2 = [&](const float* w, int K, int ci, int co, PackedKernel* dst) -> int {
       EGONN_TRY(pack_rg_weights(w, K, ci, co, 0, 0, 0, pc, st));
       EGONN_TRY(pack_rg_weights(w, K, ci, co, 1, 0, 0, qc, st));
-      *dst32 = pc;
-      *dst16 = reinterpret_cast<const float*>(qc);
-      *dsts = nullptr;
+      *dst = PackedKernel{pc, qc, nullptr};
       if (sconv_split_supported(ci, co)) {
         EGONN_TRY(pack_split_weights(w, K, ci, co, 0, 0, sc, st));
-        *dsts = reinterpret_cast<const float*>(sc);
+        dst->split = sc;
         sc += split_weights_bytes(K, ci, co) / 2;
       }
       pc += (size_t)K * ci * co;
@@ -873,13 +870,13 @@ API int egonn_model_finalize(egonn_model* m, void* stream) {
     };
     for (int i = 1; i <= 7; ++i) {
       const BlockRef& b = m->blk[i];
-      EGONN_TRY(pack2(m->convs[i], 8, b.cin, b.cin, &m->p_convs[i], &m->q_convs[i], &m->s_convs[i]));
-      EGONN_TRY(pack2(b.conv1, 27, b.cin, b.cout, &m->p_c1[i], &m->q_c1[i], &m->s_c1[i]));
-      EGONN_TRY(pack2(b.conv2, 27, b.cout, b.cout, &m->p_c2[i], &m->q_c2[i], &m->s_c2[i]));
+      EGONN_TRY(pack2(m->convs[i], 8, b.cin, b.cin, &m->pk_convs[i]));
+      EGONN_TRY(pack2(b.conv1, 27, b.cin, b.cout, &m->pk_c1[i]));
+      EGONN_TRY(pack2(b.conv2, 27, b.cout, b.cout, &m->pk_c2[i]));
     }
-    EGONN_TRY(pack2(m->gt[6], 8, GLOBAL_CH, GLOBAL_CH, &m->p_gt[6], &m->q_gt[6], &m->s_gt[6]));
-    EGONN_TRY(pack2(m->gt[7], 8, GLOBAL_CH, GLOBAL_CH, &m->p_gt[7], &m->q_gt[7], &m->s_gt[7]));
-    EGONN_TRY(pack2(m->lt[4], 8, LOCAL_CH, LOCAL_CH, &m->p_lt[4], &m->q_lt[4], &m->s_lt[4]));
+    EGONN_TRY(pack2(m->gt[6], 8, GLOBAL_CH, GLOBAL_CH, &m->pk_gt[6]));
+    EGONN_TRY(pack2(m->gt[7], 8, GLOBAL_CH, GLOBAL_CH, &m->pk_gt[7]));
+    EGONN_TRY(pack2(m->lt[4], 8, LOCAL_CH, LOCAL_CH, &m->pk_lt[4]));
   }
   if (!m->conv0_unit) HIP_CHECK(hipMalloc(&m->conv0_unit, 2 * 4 * 3 * 64 * 16));
   EGONN_TRY(conv0_pack_unit(m->conv0, m->conv0_unit, st));
@@ -908,13 +905,9 @@ namespace {
 
 // EGONN_DEBUG_SYNC=1: synchronise after every stage of egonn_forward and print its name (a GPU fault aborts the process at
 // the next synchronisation: the last name printed is the stage that faulted).  Debug aid only; never set in captures.
-bool debug_sync_on() {
-  static const bool on = [] { const char* e = getenv("EGONN_DEBUG_SYNC"); return e && e[0] == '1'; }();
-  return on;
-}
 #define DBG_SYNC(...)                                                 \
   do {                                                                \
-    if (debug_sync_on()) {                                            \
+    if (switches().debug_sync) {                                            \
       fprintf(stderr, "[egonn] " __VA_ARGS__);                        \
       fprintf(stderr, "\n");                                          \
       fflush(stderr);                                                 \
@@ -926,6 +919,22 @@ int run_mlp(const MlpRef& r, const float* x, int64_t n, int act_out, float* hidd
             const int32_t* n_dev) {
   EGONN_TRY(dense_forward_ex(x, 0, n, r.cin, r.w0, 1, r.mid, r.b0, nullptr, nullptr, ACT_RELU, nullptr, 0, hidden, 0, st, n_dev));
   return dense_forward_ex(hidden, 0, n, r.mid, r.w1, 1, r.cout, r.b1, nullptr, nullptr, act_out, nullptr, 0, out, 0, st, n_dev);
+}
+
+// One sparse convolution of the graph: the profiler tag "<kernel><cin,cout>/L<level>/<what>" (the kernel sconv_map will dispatch,
+// so that bench.py's roofline leg names what rocprofv3 names), the timing scope, the launch
+int conv_layer(egonn_ctx* c, hipStream_t st, const ConvCall& cc, const char* what) {
+  static const int pk[3] = {PK_K3, PK_K2S2, PK_TCONV};
+  char tag[64];
+  snprintf(tag, sizeof(tag), "%s<%d,%d>/L%d/%s", sconv_kernel_name(c, cc.kind, cc.level, cc.cin, cc.cout, cc.bf16), cc.cin, cc.cout,
+           cc.level, what);
+  ProfScope ps(c, st, tag, pk[cc.kind], cc.level, cc.kind == 0 ? 27 : 8, cc.cin, cc.cout, cc.bf16 ? 2 : 4);
+  return sconv_map(c, cc, st);
+}
+ConvCall conv_call(int kind, int level, const void* in, const PackedKernel& pk, int cin, int cout, int bf16, const BnRef* bn, int relu,
+                   void* out) {
+  return ConvCall{.kind = kind, .level = level, .in = in, .out = out, .cin = cin, .cout = cout, .bf16 = bf16,
+                  .scale = bn ? bn->scale : nullptr, .shift = bn ? bn->shift : nullptr, .relu = relu, .packed = &pk};
 }
 
 }  // namespace
@@ -1009,23 +1018,14 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
     EGONN_TRY(dense_forward_ex(x[4], bf16, n4, 128, m->l1x1[4], 0, LOCAL_CH, nullptr, nullptr, nullptr, ACT_NONE, nullptr, 0, l4,
                                bf16, st, cnt + 4));
     FALLOC(u3, n3 * LOCAL_CH);
-    {
-      char tag[64];
-      snprintf(tag, sizeof(tag), "%s<%d,%d>/L3/tconv", sconv_kernel_name(c, 2, 3, LOCAL_CH, LOCAL_CH, bf16),
-               LOCAL_CH, LOCAL_CH);
-      ProfScope ps(c, st, tag, PK_TCONV, 3, 8, LOCAL_CH, LOCAL_CH, (int)es);
-      EGONN_TRY(sconv_map(c, 2, 3, l4, nullptr, bf16 ? m->q_lt[4] : m->p_lt[4], m->s_lt[4], LOCAL_CH, LOCAL_CH, bf16, nullptr, nullptr, 0, u3,
-                          nullptr, nullptr, 0, st));
-    }
+    EGONN_TRY(conv_layer(c, st, conv_call(2, 3, l4, m->pk_lt[4], LOCAL_CH, LOCAL_CH, bf16, nullptr, 0, u3), "tconv"));
     EGONN_REQUIRE(m->ldec.cin == 64 && m->ldec.mid == 96 && m->ldec.cout == 128 && m->kp.mid == 32 && m->sg.mid == 32,
                   EGONN_ERR_STATE, "local heads: unexpected layer sizes");
     const float* hw[12] = {m->ldec.w0, m->ldec.b0, m->ldec.w1, m->ldec.b1, m->kp.w0, m->kp.b0, m->kp.w1, m->kp.b1,
                            m->sg.w0, m->sg.b0, m->sg.w1, m->sg.b1};
-    static const bool fuse_lateral = getenv("EGONN_NO_FUSED_LATERAL") == nullptr;      // measurement switch
-    static const bool heads_split_ok = getenv("EGONN_NO_SPLIT_HEADS") == nullptr;      // measurement switch
     // the heads' Linear layers on the fp16 matrix pipe (dense.hip), unless this context asked for exact fp32 arithmetic
-    const void* lh_pack = (heads_split_ok && m->lh_pack && c->split_max_level >= 0 && c->conv_variant == 0) ? m->lh_pack : nullptr;
-    if (fuse_lateral && LOCAL_CH == 64) {
+    const void* lh_pack = (!switches().no_split_heads && sconv_split_arithmetic(c)) ? m->lh_pack : nullptr;
+    if (!switches().no_fused_lateral && LOCAL_CH == 64) {
       // the level-3 lateral 1x1 convolution + the transposed convolution's output are the first layer of the heads' kernel — the
       // 64-channel map they read is never written (bitwise the rows of the dense launch this replaces; bf16 maps are widened on load)
       EGONN_TRY(local_heads_forward(reinterpret_cast<const float*>(x[3]), n3, cnt + 3, hw, P.lv[3].keys, 3, P.coord_bits, quant_mode,
@@ -1040,65 +1040,48 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
                                   lh_pack, c->dev_fp16_flag));
     return EGONN_OK;
   };
-  static const bool presplit_ok = getenv("EGONN_NO_PRESPLIT") == nullptr;     // measurement switch: conv2 splits in its loop
   const float *gated_t2 = nullptr, *gated_res = nullptr, *gated_gate = nullptr;     // level 1's block tail, evaluated by level 2's k=2 conv
   for (int i = 1; i <= 7; ++i) {
     const BlockRef& b = m->blk[i];
     const Level& L = P.lv[i];
     const int64_t n = P.cap[i];
     FALLOC(y, n * b.cin);
-    char tag[64];
     {
-      snprintf(tag, sizeof(tag), "%s<%d,%d>/L%d/k2s2", sconv_kernel_name(c, 1, i, b.cin, b.cin, bf16), b.cin,
-               b.cin, i);
-      ProfScope ps(c, st, tag, PK_K2S2, i, 8, b.cin, b.cin, (int)es);
-      // (level 2 with a gated input: the block output of level 1 is evaluated on the gathered rows — see below)
-      const bool gin = gated_t2 != nullptr && i == 2;
-      c->gated_in2 = gin ? gated_res : nullptr;
-      c->gated_gate = gin ? gated_gate : nullptr;
-      const int rc = sconv_map(c, 1, i, gin ? gated_t2 : x[i - 1], nullptr, bf16 ? m->q_convs[i] : m->p_convs[i], m->s_convs[i], b.cin, b.cin, bf16,
-                               m->bn[i].scale, m->bn[i].shift, 1, y, nullptr, nullptr, 0, st);
-      c->gated_in2 = nullptr;
-      c->gated_gate = nullptr;
-      EGONN_TRY(rc);
+      ConvCall cc = conv_call(1, i, x[i - 1], m->pk_convs[i], b.cin, b.cin, bf16, &m->bn[i], 1, y);
+      if (gated_t2 && i == 2) {      // the block output of level 1 is evaluated on the gathered rows — see below
+        cc.in = gated_t2;
+        cc.in2 = gated_res;
+        cc.gate = gated_gate;
+      }
+      EGONN_TRY(conv_layer(c, st, cc, "k2s2"));
     }
     DBG_SYNC("L%d k2s2", i);
     // ECABasicBlock (layers/eca_block.py:56-73)
     FALLOC(t1, n * b.cout);
     // conv1's output has ONE reader, conv2: when both run on the split kernel, conv1's epilogue writes it in split form (the
     // fp16 hi | lo operands conv2 would otherwise make of every gathered fragment in its step loop; sconv_split.hip)
-    const bool t1_split = presplit_ok && sconv_uses_split(b.cin, b.cout, bf16, i, c->conv_variant, c->split_max_level) &&
-                          sconv_uses_split(b.cout, b.cout, bf16, i, c->conv_variant, c->split_max_level);
+    const bool t1_split = !switches().no_presplit && sconv_route(c, 0, i, b.cin, b.cout, bf16) == ROUTE_SPLIT &&
+                          sconv_route(c, 0, i, b.cout, b.cout, bf16) == ROUTE_SPLIT;
     {
-      snprintf(tag, sizeof(tag), "%s<%d,%d>/L%d/k3.conv1", sconv_kernel_name(c, 0, i, b.cin, b.cout, bf16),
-               b.cin, b.cout, i);
-      ProfScope ps(c, st, tag, PK_K3, i, 27, b.cin, b.cout, (int)es);
-      c->split_io = t1_split ? 2 : 0;
-      const int rc = sconv_map(c, 0, i, y, nullptr, bf16 ? m->q_c1[i] : m->p_c1[i], m->s_c1[i], b.cin, b.cout, bf16, b.n1.scale, b.n1.shift, 1, t1,
-                               nullptr, nullptr, 0, st);
-      c->split_io = 0;
-      EGONN_TRY(rc);
+      ConvCall cc = conv_call(0, i, y, m->pk_c1[i], b.cin, b.cout, bf16, &b.n1, 1, t1);
+      cc.split_io = t1_split ? 2 : 0;
+      EGONN_TRY(conv_layer(c, st, cc, "k3.conv1"));
     }
     FALLOC(t2, n * b.cout);
     WALLOC(psum, (size_t)L.rg27.cap_groups * b.cout);
     {
-      snprintf(tag, sizeof(tag), "%s<%d,%d>/L%d/k3.conv2", sconv_kernel_name(c, 0, i, b.cout, b.cout, bf16),
-               b.cout, b.cout, i);
-      ProfScope ps(c, st, tag, PK_K3, i, 27, b.cout, b.cout, (int)es);
-      c->split_io = t1_split ? 1 : 0;
-      const int rc = sconv_map(c, 0, i, t1, nullptr, bf16 ? m->q_c2[i] : m->p_c2[i], m->s_c2[i], b.cout, b.cout, bf16, b.n2.scale, b.n2.shift, 0, t2,
-                               psum, nullptr, 0, st);
-      c->split_io = 0;
-      EGONN_TRY(rc);
+      ConvCall cc = conv_call(0, i, t1, m->pk_c2[i], b.cout, b.cout, bf16, &b.n2, 0, t2);
+      cc.split_io = t1_split ? 1 : 0;
+      cc.psum = psum;
+      EGONN_TRY(conv_layer(c, st, cc, "k3.conv2"));
     }
     WALLOC(gate, (size_t)B * b.cout);
     DBG_SYNC("L%d convs", i);
     EGONN_TRY(eca_gate_groups(psum, L.rg27, L.boff, B, b.cout, b.eca, b.eca_k, gate, st));
     DBG_SYNC("L%d eca gate", i);
     const void* res = y;
-    static const bool gated_ok = getenv("EGONN_NO_GATED_K2S2") == nullptr;        // measurement switch
-    if (i == 1 && gated_ok && !c->keep_level_features && !bf16 && !b.down && c->conv_variant == 0 && b.cout == 32 && m->blk[2].cin == 32 &&
-        sconv_uses_split(32, 32, 0, 2, c->conv_variant, c->split_max_level, 1)) {
+    if (i == 1 && !switches().no_gated_k2s2 && !c->keep_level_features && !bf16 && !b.down && c->conv_variant == 0 && b.cout == 32 &&
+        m->blk[2].cin == 32 && sconv_route(c, 1, 2, 32, 32, 0) == ROUTE_SPLIT) {
       // level 1's block output has ONE reader, the strided convolution into level 2, which reads every row exactly once: it
       // evaluates relu(t2 * gate[scan] + y) on the rows it gathers (sconv_split_kernel<32,32,...,GATED>) — the 23 MB map is neither
       // written nor read back and the element-wise launch is gone; bitwise the same level-2 input.  egonn_forward_level_features(1)
@@ -1112,8 +1095,7 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
       continue;
     }
     FALLOC(xo, n * b.cout);
-    static const bool fuse_down = getenv("EGONN_NO_FUSED_DOWN") == nullptr;      // measurement switch
-    if (b.down && fuse_down && dense_gate_fusable(n, b.cin, b.cout)) {
+    if (b.down && !switches().no_fused_down && dense_gate_fusable(n, b.cin, b.cout)) {
       // blocks with a 1x1 downsample branch (levels 2 and 4): the branch, its BatchNorm and the gated residual + ReLU of the block's
       // tail in ONE launch — out = relu(t2 * gate[scan] + bn(y @ Wd)); the branch output never goes to memory (bitwise the result
       // of the two launches it replaces)
@@ -1140,9 +1122,8 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
   DBG_SYNC("local head");
 
   // ---- global head + decoder + GeM (models/minkgl.py:46-60, 207-225; layers/pooling.py:82-86)
-  static const bool fuse_ghead = getenv("EGONN_NO_FUSED_GHEAD") == nullptr;      // measurement switch
   void* g5_fused = nullptr;
-  if (do_global && fuse_ghead && !bf16 && c->conv_variant == 0 && P.cap[5] < 8192 && P.cap[6] < 8192 && P.cap[7] < 8192) {
+  if (do_global && !switches().no_fused_ghead && !bf16 && c->conv_variant == 0 && P.cap[5] < 8192 && P.cap[6] < 8192 && P.cap[7] < 8192) {
     // MinkHead (models/minkgl.py:46-60) in three launches instead of five: the three lateral 1x1 convolutions depend on the trunk
     // only — ONE grouped launch — and every FPN step `tconv(y) + lateral` is the transposed convolution with the lateral as its
     // epilogue residual.  a + b = b + a: bitwise the five-launch result (tools/check_bitwise_switches.py).
@@ -1158,14 +1139,9 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
     float* gout[3] = {l7, l6, l5};
     EGONN_TRY(dense_small_group3(gin, gn, gnd, gw, gout, st));
     for (int lv = 6; lv >= 5; --lv) {
-      char tag[64];
-      snprintf(tag, sizeof(tag), "%s<%d,%d>/L%d/tconv", sconv_kernel_name(c, 2, lv, GLOBAL_CH, GLOBAL_CH, 0), GLOBAL_CH, GLOBAL_CH, lv);
-      ProfScope ps(c, st, tag, PK_TCONV, lv, 8, GLOBAL_CH, GLOBAL_CH, 4);
-      c->conv_residual = lv == 6 ? l6 : l5;
-      const int rc = sconv_map(c, 2, lv, lv == 6 ? l7 : g6f, nullptr, m->p_gt[lv + 1], m->s_gt[lv + 1], GLOBAL_CH, GLOBAL_CH, 0, nullptr, nullptr, 0,
-                               lv == 6 ? g6f : g5f, nullptr, nullptr, 0, st);
-      c->conv_residual = nullptr;
-      EGONN_TRY(rc);
+      ConvCall cc = conv_call(2, lv, lv == 6 ? l7 : g6f, m->pk_gt[lv + 1], GLOBAL_CH, GLOBAL_CH, 0, nullptr, 0, lv == 6 ? g6f : g5f);
+      cc.residual = lv == 6 ? l6 : l5;
+      EGONN_TRY(conv_layer(c, st, cc, "tconv"));
     }
     g5_fused = g5f;
     DBG_SYNC("global head (fused)");
@@ -1177,26 +1153,12 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
     EGONN_TRY(dense_forward_ex(x[7], bf16, P.cap[7], 128, m->g1x1[7], 0, GLOBAL_CH, nullptr, nullptr, nullptr, ACT_NONE, nullptr, 0,
                                g7, bf16, st, cnt + 7));
     FALLOC(u6, P.cap[6] * GLOBAL_CH);
-    {
-      char tag[64];
-      snprintf(tag, sizeof(tag), "%s<%d,%d>/L6/tconv", sconv_kernel_name(c, 2, 6, GLOBAL_CH, GLOBAL_CH, bf16),
-               GLOBAL_CH, GLOBAL_CH);
-      ProfScope ps(c, st, tag, PK_TCONV, 6, 8, GLOBAL_CH, GLOBAL_CH, (int)es);
-      EGONN_TRY(sconv_map(c, 2, 6, g7, nullptr, bf16 ? m->q_gt[7] : m->p_gt[7], m->s_gt[7], GLOBAL_CH, GLOBAL_CH, bf16, nullptr, nullptr, 0, u6,
-                          nullptr, nullptr, 0, st));
-    }
+    EGONN_TRY(conv_layer(c, st, conv_call(2, 6, g7, m->pk_gt[7], GLOBAL_CH, GLOBAL_CH, bf16, nullptr, 0, u6), "tconv"));
     FALLOC(g6, P.cap[6] * GLOBAL_CH);
     EGONN_TRY(dense_forward_ex(x[6], bf16, P.cap[6], 128, m->g1x1[6], 0, GLOBAL_CH, nullptr, nullptr, nullptr, ACT_NONE, u6, bf16,
                                g6, bf16, st, cnt + 6));
     FALLOC(u5, P.cap[5] * GLOBAL_CH);
-    {
-      char tag[64];
-      snprintf(tag, sizeof(tag), "%s<%d,%d>/L5/tconv", sconv_kernel_name(c, 2, 5, GLOBAL_CH, GLOBAL_CH, bf16),
-               GLOBAL_CH, GLOBAL_CH);
-      ProfScope ps(c, st, tag, PK_TCONV, 5, 8, GLOBAL_CH, GLOBAL_CH, (int)es);
-      EGONN_TRY(sconv_map(c, 2, 5, g6, nullptr, bf16 ? m->q_gt[6] : m->p_gt[6], m->s_gt[6], GLOBAL_CH, GLOBAL_CH, bf16, nullptr, nullptr, 0, u5,
-                          nullptr, nullptr, 0, st));
-    }
+    EGONN_TRY(conv_layer(c, st, conv_call(2, 5, g6, m->pk_gt[6], GLOBAL_CH, GLOBAL_CH, bf16, nullptr, 0, u5), "tconv"));
     WALLOC(g5u, P.cap[5] * GLOBAL_CH);
     EGONN_TRY(dense_forward_ex(x[5], bf16, P.cap[5], 128, m->g1x1[5], 0, GLOBAL_CH, nullptr, nullptr, nullptr, ACT_NONE, u5, bf16,
                                g5u, 0, st, cnt + 5));

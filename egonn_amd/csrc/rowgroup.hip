@@ -377,8 +377,7 @@ int rowgroup_build(const RGBuild* jobs, int njobs, int B, hipStream_t stream) {
     nb += b.rg->cap_groups / (b.rg->win / 16);
   }
   a.nblocks = nb;
-  static const int env_first = [] { const char* e = getenv("EGONN_RG_FIRST_PASS"); return e ? atoi(e) : 0; }();   // measurement switch
-  a.first_pass = std::min(std::max(env_first, 0), 2);
+  a.first_pass = std::min(std::max(switches().rg_first_pass, 0), 2);   // measurement switch
   a.trace = g_sconv_trace;
   if (nb == 0) return EGONN_OK;
   static AttrOnce attr_done;

@@ -1130,26 +1130,22 @@ static int launch_rg_d(const SconvArgs& a, int64_t groups_hint, hipStream_t stre
 // sel (tests / A-B measurements; every choice gives bitwise-identical results): 0 = product choice, 1 = register-ring
 // kernel, 2 = register-ring kernel with two groups per wave, 3 = LDS-DMA kernel (fp32 maps; split-phase LDS fetch, 4 ring slots), 4 = LDS-DMA kernel with the fetch inside the item (3 slots), 9 = traced build
 template <int CIN, int COUT, bool BF16>
-static int launch_rg(const SconvArgs& a, int64_t groups_hint, hipStream_t stream, int sel, int level, int split) {
+static int launch_rg(const SconvArgs& a, int64_t groups_hint, hipStream_t stream, int sel, SconvRoute route, bool small) {
   constexpr int NS = COUT / 32, NCB = CIN / 32;
   // the input-channel blocks are always split over the waves of a workgroup (a function of the shape only, so results
   // never depend on launch sizes): measured faster at every level, 12 % on the 84 k-row 64->64 layer, 40 % on level 4.
   // Splitting the kernel offsets as well measured neutral to 50 % slower.
   constexpr int KSP = NCB >= 4 ? 4 : NCB;
-  // prefetch depth (does not touch the arithmetic): few waves per SIMD => nothing else hides the gather latency, keep
-  // 5 items in flight; a full chip prefers the smaller register footprint
-  // levels >= 5 never fill the chip (batch 16: <= 240 groups): few waves per SIMD.  A function of the LAYER, not of a
-  // capacity: eager plans, reserved (graph) plans, the per-layer table and rocprof all see the same kernel.  bf16 maps are the
-  // batch-64 configuration (BASELINE configs[2]): level 5 still fills the chip there
-  const bool small = level >= (BF16 ? 6 : 5);
+  // prefetch depth (does not touch the arithmetic): few waves per SIMD (`small`, sconv_small_level) => nothing else hides the
+  // gather latency, keep 5 items in flight; a full chip prefers the smaller register footprint
   if constexpr (!BF16 && CIN == 128 && COUT == 128) {      // the tail levels' plan on split arithmetic (a.Wp = the split pack)
     // (ring depth 9 / 12 instead of 6: L6 k=3 21.7 / 22.5 vs 18.1 us, L6 k2s2 13.2 / 14.7 vs 8.8 — profiles/r06c_kw_sweep.txt)
-    if (split) return launch_rg_d<CIN, COUT, false, KSP, 6, 1, true>(a, groups_hint, stream);
+    if (route == ROUTE_TAIL_SPLIT) return launch_rg_d<CIN, COUT, false, KSP, 6, 1, true>(a, groups_hint, stream);
   }
-  EGONN_REQUIRE(!split, EGONN_ERR_INVALID, "sconv: the per-tile kernel has split arithmetic for fp32 128->128 maps only");
+  EGONN_REQUIRE(route != ROUTE_TAIL_SPLIT, EGONN_ERR_INVALID, "sconv: the per-tile kernel has split arithmetic for fp32 128->128 maps only");
   if constexpr (!BF16) {
-    {
-      if (sel == 3 || (sel == 0 && !small)) return launch_dma_d<CIN, COUT, KSP, 4, false, true>(a, groups_hint, stream);
+    if (route == ROUTE_DMA) {
+      if (sel == 3 || sel == 0) return launch_dma_d<CIN, COUT, KSP, 4, false, true>(a, groups_hint, stream);
       if (sel == 4) return launch_dma_d<CIN, COUT, KSP, 3>(a, groups_hint, stream);
       if constexpr ((CIN == 32 && COUT == 32) || (CIN == 64 && COUT == 64)) {
         if (sel == 9) return launch_dma_d<CIN, COUT, KSP, 4, true, true>(a, groups_hint, stream);
@@ -1173,40 +1169,35 @@ bool sconv_rg_supported(int cin, int cout) {
   return ok(cin) && ok(cout);
 }
 
-// in: [n_in][cin]; rg: row-group tables of the map; Wp: pack_rg_weights(bf16 matching); groups_hint: host upper bound of
-// the groups in use (sizes the persistent grid only; the kernel reads the true count from rg.meta[0]).
-int sconv_rg_forward(const void* in, int64_t n_in_cap, const RowGroups& rg, int64_t groups_hint, const void* Wp, int cin,
-                     int cout, int bf16, const float* scale, const float* shift, int relu, void* out, float* psum,
-                     hipStream_t stream, int variant, int level, int split, int32_t* flags, const float* residual) {
+// c.in: [n_in][cin]; l.rg: row-group tables of the map; l.Wp: pack_rg_weights(bf16 matching), or the split pack (tail split)
+int sconv_rg_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream) {
+  const RowGroups& rg = *l.rg;
+  const int cin = c.cin, cout = c.cout, bf16 = c.bf16, variant = l.variant;
+  const int64_t groups_hint = l.groups_hint;
   EGONN_REQUIRE(rg.built, EGONN_ERR_STATE, "sconv: row-group tables not built");
   EGONN_REQUIRE(sconv_rg_supported(cin, cout), EGONN_ERR_INVALID, "sconv: channel plan %d->%d not supported (32/64/128/256)", cin, cout);
-  const uint64_t ib = (uint64_t)n_in_cap * cin * (bf16 ? 2 : 4);
+  const uint64_t ib = (uint64_t)l.n_in_cap * cin * (bf16 ? 2 : 4);
   EGONN_REQUIRE(ib < (1ull << 32) - (1ull << 20), EGONN_ERR_INVALID,
-                "sconv: input feature map of %lld rows exceeds the 4 GiB buffer-resource range", (long long)n_in_cap);
+                "sconv: input feature map of %lld rows exceeds the 4 GiB buffer-resource range", (long long)l.n_in_cap);
   if (groups_hint <= 0) return EGONN_OK;
   SconvArgs a;
-  a.in = in; a.snbr = rg.snbr; a.gmask = rg.gmask; a.perm = rg.perm; a.meta = rg.meta; a.Wp = Wp;
-  a.scale = scale; a.shift = shift; a.out = out; a.psum = psum;
+  a.in = c.in; a.snbr = rg.snbr; a.gmask = rg.gmask; a.perm = rg.perm; a.meta = rg.meta; a.Wp = l.Wp;
+  a.scale = c.scale; a.shift = c.shift; a.out = c.out; a.psum = c.psum;
   a.in_bytes = (uint32_t)ib;
   a.w_bytes = (uint32_t)((uint64_t)rg.K * cin * cout * (bf16 ? 2 : 4));
-  a.K = rg.K; a.relu = relu ? 1 : 0; a.cap_groups = rg.cap_groups;
-  static const bool no_order = getenv("EGONN_NO_TASK_ORDER") != nullptr;   // (measurement switch)
-  a.order4 = no_order ? nullptr : rg.order4;
+  a.K = rg.K; a.relu = c.relu ? 1 : 0; a.cap_groups = rg.cap_groups;
+  a.order4 = switches().no_task_order ? nullptr : rg.order4;
   a.trace = variant == 9 ? g_sconv_trace : nullptr;
-  a.flags = flags;
-  a.res = residual;
-  EGONN_REQUIRE(!residual || (!bf16 && level >= 5 && (variant == 0 || variant == 1)), EGONN_ERR_INVALID,
+  a.flags = l.flags;
+  a.res = c.residual;
+  EGONN_REQUIRE(!c.residual || (!bf16 && c.level >= 5 && (variant == 0 || variant == 1)), EGONN_ERR_INVALID,
                 "sconv: the epilogue residual exists in the per-tile kernel of fp32 maps (levels >= 5) and in the split kernel");
-
-  // Measured (profiles/r02b_sconv.json, batch 16): in fp32 the per-wave kernel wins everywhere (the lock-step of the
-  // cooperative kernel costs more than its saved W traffic when an item is 16-64 MFMAs of 32 cycles); with bf16 maps the
-  // items are load-bound and the cooperative kernel wins on the big layers with >= 64 input or output channels.
   const int gsel = variant == 1 ? 1 : (variant == 4 ? 2 : (variant == 5 ? 3 : (variant == 6 ? 4 : (variant == 9 ? 9 : 0))));
-  const bool coop = variant == 2 || (variant == 0 && bf16 && level <= 4 && cin * cout >= 32 * 64);   // (a function of the layer)
+  const bool coop = l.route == ROUTE_WG;
 #define EGONN_RG_CASE(CI, CO)                                                                      \
   if (cin == CI && cout == CO) {                                                                   \
     if (coop) return bf16 ? launch_wg<CI, CO, true>(a, groups_hint, stream) : launch_wg<CI, CO, false>(a, groups_hint, stream); \
-    return bf16 ? launch_rg<CI, CO, true>(a, groups_hint, stream, gsel, level, split) : launch_rg<CI, CO, false>(a, groups_hint, stream, gsel, level, split); \
+    return bf16 ? launch_rg<CI, CO, true>(a, groups_hint, stream, gsel, l.route, l.small) : launch_rg<CI, CO, false>(a, groups_hint, stream, gsel, l.route, l.small); \
   }
   EGONN_RG_CASE(32, 32)
   EGONN_RG_CASE(32, 64)
@@ -1229,18 +1220,6 @@ int sconv_rg_forward(const void* in, int64_t n_in_cap, const RowGroups& rg, int6
   return EGONN_ERR_INVALID;
 }
 
-// Name of the kernel sconv_map dispatches for this layer (the profiler tags carry it, so that bench.py's dominant kernel is
-// the kernel rocprofv3 names).  Mirrors the choices in sconv_map / sconv_rg_forward / launch_rg.
-const char* sconv_kernel_name(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16) {
-  const int variant = ctx->conv_variant;
-  if (sconv_uses_split(cin, cout, bf16, level, variant, ctx->split_max_level, kind)) return "sconv_split_kernel";
-  const bool small = level >= (bf16 ? 6 : 5);
-  const bool coop = variant == 2 || (variant == 0 && bf16 && level <= 4 && cin * cout >= 32 * 64);
-  if (coop) return "sconv_wg_kernel";
-  if (!bf16 && (variant == 5 || variant == 6 || variant == 9 || (variant == 0 && !small))) return "sconv_dma_kernel";
-  return "sconv_rg_kernel";
-}
-
 // Arithmetic of an fp32 sparse convolution (ctx->conv_variant; egonn_debug_set_naive_conv):
 //   0           product choice: split-bf16 kernel (sconv_split.hip) on the maps of levels <= ctx->split_max_level where it is
 //               instantiated, exact fp32 MFMA kernels elsewhere
@@ -1252,23 +1231,39 @@ const char* sconv_kernel_name(const Ctx* ctx, int kind, int level, int cin, int 
 // kernel wins from ~4 000 row groups up (L1 k3 60 -> 54 us, L2 64->64 89 -> 79) and loses below; with batches in flight it
 // pays much earlier because it leaves the matrix pipe to the other batches: scans/s with the split kernel on launches of
 // >= inf / 4096 / 2000 / 700 / 200 groups = 21.8 k / 23.3 k / 24.3 k / 24.8 k / 23.6 k, i.e. levels <= 0 / 2 / 3 / 4 / 6.
-static int split_level_limit(int split_max_level) {      // the context's limit, or EGONN_SPLIT_MAX_LEVEL (measurement override)
-  static const int env_level = [] {
-    const char* e = getenv("EGONN_SPLIT_MAX_LEVEL");
-    return e ? atoi(e) : -1;
-  }();
-  return (env_level >= 0 && split_max_level >= 0) ? env_level : split_max_level;
+//
+// The exact kernels, measured (profiles/r02b_sconv.json, batch 16): in fp32 the per-wave kernels win everywhere (the lock-step of the
+// cooperative kernel costs more than its saved W traffic when an item is 16-64 MFMAs of 32 cycles); with bf16 maps the items are
+// load-bound and the cooperative kernel wins on the big layers with >= 64 input or output channels.  Levels >= 5 never fill
+// the chip (batch 16: <= 240 groups); bf16 maps are the batch-64 configuration (BASELINE configs[2]): level 5 still fills it there.
+static bool sconv_small_level(int level, int bf16) { return level >= (bf16 ? 6 : 5); }
+bool sconv_split_arithmetic(const Ctx* ctx) { return ctx->conv_variant == 0 && ctx->split_max_level >= 0; }
+SconvRoute sconv_route(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16) {
+  const int variant = ctx->conv_variant;
+  const Switches& sw = switches();
+  if (variant == 3 || !sconv_rg_supported(cin, cout)) return ROUTE_PLAIN;
+  // the context's split level limit, or EGONN_SPLIT_MAX_LEVEL; EGONN_SPLIT_MAX_LEVEL_K8 for the 8-slot maps (measurement overrides)
+  const int limit = (sw.split_max_level >= 0 && ctx->split_max_level >= 0) ? sw.split_max_level : ctx->split_max_level;
+  if (!bf16 && sconv_split_supported(cin, cout)) {
+    if (variant >= 1000) return ROUTE_SPLIT;
+    if (variant == 0 && level <= ((kind != 0 && sw.split_max_level_k8 >= 0) ? sw.split_max_level_k8 : limit)) return ROUTE_SPLIT;
+  }
+  if (!sw.no_tail_split && !bf16 && cin == 128 && cout == 128 && sconv_split_arithmetic(ctx) && level > limit && !ctx->operand_autoscale)
+    return ROUTE_TAIL_SPLIT;
+  if (variant == 2 || (variant == 0 && bf16 && level <= 4 && cin * cout >= 32 * 64)) return ROUTE_WG;
+  // (variants 1 and 4 ask for the register-ring kernels; every other one leaves the big fp32 launches on the LDS-DMA kernel)
+  if (!bf16 && variant != 1 && variant != 4 && (variant == 5 || variant == 6 || variant == 9 || !sconv_small_level(level, bf16)))
+    return ROUTE_DMA;
+  return ROUTE_RG;
 }
-bool sconv_uses_split(int cin, int cout, int bf16, int level, int variant, int split_max_level, int kind) {
-  if (bf16 || !sconv_split_supported(cin, cout)) return false;
-  if (variant >= 1000) return true;
-  if (variant != 0) return false;
-  static const int env_k8 = [] {                          // EGONN_SPLIT_MAX_LEVEL_K8: measurement override for the 8-slot maps
-    const char* e = getenv("EGONN_SPLIT_MAX_LEVEL_K8");
-    return e ? atoi(e) : -1;
-  }();
-  if (kind != 0 && env_k8 >= 0) return level <= env_k8;
-  return level <= split_level_limit(split_max_level);
+// (the plain kernel runs under a debug variant only and has no tag of its own)
+const char* sconv_kernel_name(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16) {
+  switch (sconv_route(ctx, kind, level, cin, cout, bf16)) {
+    case ROUTE_SPLIT: return "sconv_split_kernel";
+    case ROUTE_WG: return "sconv_wg_kernel";
+    case ROUTE_DMA: return "sconv_dma_kernel";
+    default: return "sconv_rg_kernel";
+  }
 }
 
 // Offset-split rule (see kernels.h): a function of (map kind, output level) only.
@@ -1288,19 +1283,15 @@ bool sconv_uses_split(int cin, int cout, int bf16, int level, int variant, int s
 void sconv_ksplit_defaults(KsRule* r) {
   static const KsRule rule = [] {
     KsRule q = {{{1, 1, 1, 1, 1, 1, 1, 1}, {1, 1, 1, 1, 1, 1, 1, 1}}, {{0, 0, 0, 2, 2, 2, 0, 0}, {0, 0, 0, 2, 2, 2, 0, 0}}, {0, 0, 0, 0, 0, 0, 0, 0}};
-    auto parse = [](const char* name, int8_t* dst) {
-      const char* e = getenv(name);
+    auto parse = [](const char* e, int8_t* dst) {
       for (int l = 0; e && *e && l < EGONN_NUM_LEVELS; ++l) {
         dst[l] = (int8_t)atoi(e);
         e = strchr(e, ',');
         if (e) ++e;
       }
     };
-    parse("EGONN_KSPLIT", q.kparts[0]);
-    parse("EGONN_KSPLIT8", q.kparts[1]);
-    parse("EGONN_KSPLIT_KW", q.kw[0]);
-    parse("EGONN_KSPLIT_KW8", q.kw[1]);
-    parse("EGONN_KSPLIT_PARTS", q.col_parts);
+    int8_t* const dst[5] = {q.kparts[0], q.kparts[1], q.kw[0], q.kw[1], q.col_parts};
+    for (int i = 0; i < 5; ++i) parse(switches().ksplit[i], dst[i]);
     return q;
   }();
   *r = rule;
@@ -1311,23 +1302,33 @@ void sconv_ksplit_rule(const Ctx* ctx, int kind, int level, int* kparts, int* co
   const int K = kind == 0 ? 27 : 8, mc = kind == 0 ? 0 : 1;
   *kparts = std::min(std::max((int)rule.kparts[mc][l], 1), K);
   *col_parts = rule.col_parts[l];
-  if (kw) *kw = rule.kw[mc][l];
+  *kw = rule.kw[mc][l];
 }
 size_t sconv_ksplit_scratch_floats(const Ctx* ctx) {
   size_t need = 0;
   for (int kind = 0; kind <= 2; ++kind)
     for (int l = (kind == 2 ? 0 : 1); l < EGONN_NUM_LEVELS - (kind == 2 ? 1 : 0); ++l) {
-      int kp, cp;
-      sconv_ksplit_rule(ctx, kind, l, &kp, &cp);
+      int kp, cp, kw;
+      sconv_ksplit_rule(ctx, kind, l, &kp, &cp, &kw);
       if (kp > 1) need = std::max(need, (size_t)kp * rowgroup_cap_groups(ctx->plan, l) * 16 * 128);
     }
   return need;
 }
 
-int sconv_map(Ctx* ctx, int kind, int level, const void* in, const float* W, const void* Wp, const void* Wsp, int cin, int cout,
-              int bf16, const float* scale, const float* shift, int relu, void* out, float* psum, float* scratch,
-              size_t scratch_floats, hipStream_t stream) {
+// The kernel in the form the route reads: the model's pack, or (stand-alone operator call) W packed into the caller's scratch
+static int route_kernel(const ConvCall& c, int K, bool split, hipStream_t stream, const void** Wp) {
+  *Wp = !c.packed ? nullptr : (split ? c.packed->split : (c.bf16 ? c.packed->rg16 : c.packed->rg32));
+  if (*Wp) return EGONN_OK;
+  const size_t wn = split ? (split_weights_bytes(K, c.cin, c.cout) + 3) / 4 : (size_t)K * c.cin * c.cout;
+  EGONN_REQUIRE(c.W && c.scratch && c.scratch_floats >= wn, EGONN_ERR_STATE, "sconv: no scratch to pack the kernel into");
+  *Wp = c.scratch;
+  return split ? pack_split_weights(c.W, K, c.cin, c.cout, 0, 0, c.scratch, stream)
+               : pack_rg_weights(c.W, K, c.cin, c.cout, c.bf16, 0, 0, c.scratch, stream);
+}
+
+int sconv_map(Ctx* ctx, const ConvCall& c, hipStream_t stream) {
   Plan& P = ctx->plan;
+  const int kind = c.kind, level = c.level;
   EGONN_REQUIRE(kind >= 0 && kind <= 2, EGONN_ERR_INVALID, "sconv: map kind %d", kind);
   const int lin = kind == 0 ? level : (kind == 1 ? level - 1 : level + 1);
   EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && lin >= 0 && lin < EGONN_NUM_LEVELS, EGONN_ERR_INVALID,
@@ -1335,58 +1336,41 @@ int sconv_map(Ctx* ctx, int kind, int level, const void* in, const float* W, con
   Level& V = P.lv[level];
   if (V.n == 0) return EGONN_OK;
   const int K = kind == 0 ? 27 : 8;
-  if (ctx->conv_variant == 3 || !sconv_rg_supported(cin, cout)) {
-    EGONN_REQUIRE(!bf16, EGONN_ERR_INVALID, "sconv: bf16 feature maps need a 32/64/128/256-channel plan (%d->%d)", cin, cout);
-    EGONN_REQUIRE(W, EGONN_ERR_INVALID, "sconv: the plain kernel needs the reference-layout kernel");
+  SconvLaunch l;
+  l.route = sconv_route(ctx, kind, level, c.cin, c.cout, c.bf16);
+  if (l.route == ROUTE_PLAIN) {
+    EGONN_REQUIRE(!c.bf16, EGONN_ERR_INVALID, "sconv: bf16 feature maps need a 32/64/128/256-channel plan (%d->%d)", c.cin, c.cout);
+    EGONN_REQUIRE(c.W, EGONN_ERR_INVALID, "sconv: the plain kernel needs the reference-layout kernel");
     if (kind == 2 && level == 0) EGONN_TRY(ensure_level0_parent_table(ctx, stream));
     const int32_t* nbr = kind == 0 ? V.nbr27 : (kind == 1 ? V.nbr8 : V.nbrT);
-    EGONN_REQUIRE(!psum && !ctx->conv_residual, EGONN_ERR_INVALID, "sconv: group sums / epilogue residuals are produced by the MFMA kernels only");
-    return sconv_naive(reinterpret_cast<const float*>(in), nbr, W, scale, shift, relu, reinterpret_cast<float*>(out), V.n, K,
-                       cin, cout, stream);
+    EGONN_REQUIRE(!c.psum && !c.residual, EGONN_ERR_INVALID, "sconv: group sums / epilogue residuals are produced by the MFMA kernels only");
+    return sconv_naive(reinterpret_cast<const float*>(c.in), nbr, c.W, c.scale, c.shift, c.relu, reinterpret_cast<float*>(c.out), V.n, K,
+                       c.cin, c.cout, stream);
   }
   EGONN_TRY(ensure_rowgroups(ctx, &kind, &level, 1, stream));
-  const RowGroups& rg = kind == 0 ? V.rg27 : (kind == 1 ? V.rg8 : V.rgT);
-  if (sconv_uses_split(cin, cout, bf16, level, ctx->conv_variant, ctx->split_max_level, kind)) {
-    if (!Wsp) {   // stand-alone operator call: pack into the caller's scratch
-      const size_t wn = (split_weights_bytes(K, cin, cout) + 3) / 4;
-      EGONN_REQUIRE(W && scratch && scratch_floats >= wn, EGONN_ERR_STATE, "sconv: no scratch to pack the kernel into");
-      EGONN_TRY(pack_split_weights(W, K, cin, cout, 0, 0, scratch, stream));
-      Wsp = scratch;
-    }
-    int kparts = 1, col_parts = 0, kw = 0;
-    sconv_ksplit_rule(ctx, kind, level, &kparts, &col_parts, &kw);
-    if (ctx->gated_in2) { kparts = 1; kw = 0; }
-    if (cin < 64) kw = 0;
-    return sconv_split_forward(reinterpret_cast<const float*>(in), P.cap[lin], rg, rg.cap_groups, Wsp, cin, cout, scale, shift,
-                               relu, reinterpret_cast<float*>(out), psum, stream,
-                               ctx->conv_variant >= 1000 ? ctx->conv_variant - 1000 : 0, ctx->split_io, ctx->gated_in2, ctx->gated_gate,
-                               P.batch, kparts, ctx->ks_part, ctx->ks_part_floats, col_parts, kw, ctx->dev_fp16_flag,
-                               ctx->operand_autoscale ? reinterpret_cast<uint32_t*>(ctx->dev_counts + 24) : nullptr,
-                               ctx->operand_autoscale ? P.lv[lin].n * cin : 0, ctx->conv_residual);
+  l.rg = kind == 0 ? &V.rg27 : (kind == 1 ? &V.rg8 : &V.rgT);
+  l.n_in_cap = P.cap[lin]; l.groups_hint = l.rg->cap_groups;
+  const bool split = l.route == ROUTE_SPLIT || l.route == ROUTE_TAIL_SPLIT;   // fp16-split arithmetic: the split pack, the range guard
+  if (split) l.flags = ctx->dev_fp16_flag;
+  if (l.route != ROUTE_SPLIT)
+    EGONN_REQUIRE(c.split_io == 0 && !c.in2, EGONN_ERR_STATE,
+                  "sconv: split-form maps and gated inputs are read and written by the split kernel only");
+  EGONN_TRY(route_kernel(c, K, split, stream, &l.Wp));
+  if (l.route != ROUTE_SPLIT) {
+    l.variant = ctx->conv_variant;
+    l.small = sconv_small_level(level, c.bf16);
+    return sconv_rg_forward(c, l, stream);
   }
-  EGONN_REQUIRE(ctx->split_io == 0 && !ctx->gated_in2, EGONN_ERR_STATE,
-                "sconv: split-form maps and gated inputs are read and written by the split kernel only");
-  // fp32 maps of the tail levels (above split_max_level): the per-tile kernel on split arithmetic (a function of the layer)
-  static const bool tail_split_ok = getenv("EGONN_NO_TAIL_SPLIT") == nullptr;          // measurement switch
-  if (tail_split_ok && !bf16 && cin == 128 && cout == 128 && ctx->conv_variant == 0 && ctx->split_max_level >= 0 &&
-      level > split_level_limit(ctx->split_max_level) && !ctx->operand_autoscale) {
-    if (!Wsp) {
-      const size_t wn = (split_weights_bytes(K, cin, cout) + 3) / 4;
-      EGONN_REQUIRE(W && scratch && scratch_floats >= wn, EGONN_ERR_STATE, "sconv: no scratch to pack the kernel into");
-      EGONN_TRY(pack_split_weights(W, K, cin, cout, 0, 0, scratch, stream));
-      Wsp = scratch;
-    }
-    return sconv_rg_forward(in, P.cap[lin], rg, rg.cap_groups, Wsp, cin, cout, 0, scale, shift, relu, out, psum, stream, 0, level, 1,
-                            ctx->dev_fp16_flag, ctx->conv_residual);
+  sconv_ksplit_rule(ctx, kind, level, &l.kparts, &l.col_parts, &l.kw);
+  if (c.in2) { l.kparts = 1; l.kw = 0; }
+  if (c.cin < 64) l.kw = 0;
+  l.variant = ctx->conv_variant >= 1000 ? ctx->conv_variant - 1000 : 0;
+  l.B = P.batch; l.part = ctx->ks_part; l.part_floats = ctx->ks_part_floats;
+  if (ctx->operand_autoscale) {
+    l.in_absmax = reinterpret_cast<uint32_t*>(ctx->dev_counts + 24);
+    l.in_elems = P.lv[lin].n * c.cin;
   }
-  if (!Wp) {      // stand-alone operator call: pack into the caller's scratch
-    const size_t wn = (size_t)K * cin * cout;
-    EGONN_REQUIRE(W && scratch && scratch_floats >= wn, EGONN_ERR_STATE, "sconv: no scratch to pack the kernel into");
-    EGONN_TRY(pack_rg_weights(W, K, cin, cout, bf16, 0, 0, scratch, stream));
-    Wp = scratch;
-  }
-  return sconv_rg_forward(in, P.cap[lin], rg, rg.cap_groups, Wp, cin, cout, bf16, scale, shift, relu, out, psum, stream,
-                          ctx->conv_variant, level, 0, nullptr, ctx->conv_residual);
+  return sconv_split_forward(c, l, stream);
 }
 
 }  // namespace egonn

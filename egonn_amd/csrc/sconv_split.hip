@@ -712,41 +712,41 @@ bool sconv_split_supported(int cin, int cout) {
 }
 
 // cfg = 100 + NW * 10 + 2 [+ 400 * (1 + log2(column parts))]; 0 = product choice (142: workgroups of 4 waves, automatic parts)
-int sconv_split_forward(const float* in, int64_t n_in_cap, const RowGroups& rg, int64_t groups_hint, const void* Wsp, int cin,
-                        int cout, const float* scale, const float* shift, int relu, float* out, float* psum, hipStream_t stream,
-                        int cfg, int split_io, const float* gated_in2, const float* gated_gate, int B, int kparts, float* part,
-                        size_t part_floats, int col_parts, int kw, int32_t* flags, uint32_t* in_absmax, int64_t in_elems, const float* residual) {
+int sconv_split_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream) {
+  const RowGroups& rg = *l.rg;
+  const int cin = c.cin, cout = c.cout, kw = l.kw;
+  const int64_t groups_hint = l.groups_hint;
   EGONN_REQUIRE(rg.built, EGONN_ERR_STATE, "sconv: row-group tables not built");
   EGONN_REQUIRE(sconv_split_supported(cin, cout), EGONN_ERR_INVALID, "sconv(split): channel plan %d->%d not supported", cin, cout);
-  EGONN_REQUIRE((uint64_t)n_in_cap * cin * 4 < (1ull << 32) - (1ull << 20), EGONN_ERR_INVALID,
-                "sconv: input feature map of %lld rows exceeds the 4 GiB buffer-resource range", (long long)n_in_cap);
+  EGONN_REQUIRE((uint64_t)l.n_in_cap * cin * 4 < (1ull << 32) - (1ull << 20), EGONN_ERR_INVALID,
+                "sconv: input feature map of %lld rows exceeds the 4 GiB buffer-resource range", (long long)l.n_in_cap);
   if (groups_hint <= 0) return EGONN_OK;
   SplitArgs a;
-  a.in = in; a.snbr = rg.snbr; a.gmask = rg.gmask; a.perm = rg.perm; a.meta = rg.meta; a.Wsp = Wsp;
-  static const bool no_order = getenv("EGONN_NO_TASK_ORDER") != nullptr;   // (measurement switch)
-  a.order = no_order ? nullptr : rg.order4;
-  a.scale = scale; a.shift = shift; a.out = out; a.psum = psum;
-  a.in_rows = (uint32_t)n_in_cap;
+  a.in = reinterpret_cast<const float*>(c.in); a.snbr = rg.snbr; a.gmask = rg.gmask; a.perm = rg.perm; a.meta = rg.meta; a.Wsp = l.Wp;
+  a.order = switches().no_task_order ? nullptr : rg.order4;
+  a.scale = c.scale; a.shift = c.shift; a.out = reinterpret_cast<float*>(c.out); a.psum = c.psum;
+  a.in_rows = (uint32_t)l.n_in_cap;
   a.w_bytes = (uint32_t)((uint64_t)rg.K * cin * cout * 4);           // the fragments; the pack scale's inverse sits right behind them
-  a.K = rg.K; a.relu = relu ? 1 : 0; a.cap_groups = rg.cap_groups;
-  a.flags = flags;
-  a.res = residual;
-  a.in_split = (split_io & 1) ? 1 : 0;
-  if (in_absmax) {                                       // operand autoscale: max |in| -> in_absmax[1] (one memset + one launch)
-    EGONN_REQUIRE(!(split_io & 1) && !gated_in2 && in_elems > 0, EGONN_ERR_INVALID, "sconv(split): operand scale on a plain fp32 input only");
-    HIP_CHECK(hipMemsetAsync(in_absmax, 0, 8, stream));
-    hipLaunchKernelGGL(split_absmax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(in_elems, 1024), 1024)), dim3(256), 0, stream, in, in_elems, in_absmax);
-    a.in_maxbits = in_absmax + 1;
+  a.K = rg.K; a.relu = c.relu ? 1 : 0; a.cap_groups = rg.cap_groups;
+  a.flags = l.flags;
+  a.res = c.residual;
+  a.in_split = (c.split_io & 1) ? 1 : 0;
+  if (l.in_absmax) {                                     // operand autoscale: max |in| -> in_absmax[1] (one memset + one launch)
+    EGONN_REQUIRE(!(c.split_io & 1) && !c.in2 && l.in_elems > 0, EGONN_ERR_INVALID, "sconv(split): operand scale on a plain fp32 input only");
+    HIP_CHECK(hipMemsetAsync(l.in_absmax, 0, 8, stream));
+    hipLaunchKernelGGL(split_absmax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(l.in_elems, 1024), 1024)), dim3(256), 0, stream, a.in, l.in_elems, l.in_absmax);
+    a.in_maxbits = l.in_absmax + 1;
   }
-  a.out_split = (split_io & 2) ? 1 : 0;
-  if (kparts > 1) {
-    EGONN_REQUIRE(kparts <= rg.K && !gated_in2, EGONN_ERR_INVALID, "sconv(split): %d offset parts on a %d-slot map", kparts, rg.K);
-    EGONN_REQUIRE(part && part_floats >= sconv_split_part_floats(rg, cout, kparts), EGONN_ERR_STATE,
+  a.out_split = (c.split_io & 2) ? 1 : 0;
+  if (l.kparts > 1) {
+    EGONN_REQUIRE(l.kparts <= rg.K && !c.in2, EGONN_ERR_INVALID, "sconv(split): %d offset parts on a %d-slot map", l.kparts, rg.K);
+    EGONN_REQUIRE(l.part && l.part_floats >= sconv_split_part_floats(rg, cout, l.kparts), EGONN_ERR_STATE,
                   "sconv(split): no scratch for the partial tiles of an offset-split launch");
-    a.part = part;
-    a.kp_n = kparts;
+    a.part = l.part;
+    a.kp_n = l.kparts;
   }
-  if (cfg == 0) cfg = sconv_split_default_cfg(cin, cout, groups_hint);
+  // 0 = product choice: 142, the lock-step kernel on workgroups of 4 waves (EGONN_SPLIT_CFG: measurement override)
+  const int cfg = l.variant ? l.variant : (switches().split_cfg ? switches().split_cfg : 142);
   const bool trace = cfg >= 9000;                        // 9000 + shape: the s_memtime build (tools/split_trace.py)
   int shape = trace ? cfg - 9000 : cfg;
   int parts_sel = 0;
@@ -754,7 +754,7 @@ int sconv_split_forward(const float* in, int64_t n_in_cap, const RowGroups& rg, 
   const int ns_tot = cout / 32;
   int parts = 1;
   if (parts_sel > 0) parts = std::min(ns_tot, 1 << (parts_sel - 1));
-  else if (col_parts > 0) parts = std::min(ns_tot, col_parts);      // the layer's rule (offset-split launches)
+  else if (l.col_parts > 0) parts = std::min(ns_tot, l.col_parts);      // the layer's rule (offset-split launches)
   else if (kw > 1) parts = std::max(1, ns_tot / 2);                 // in-workgroup offset parts: 64 columns per workgroup, whatever the
                                                                     // capacity (the choice of KW must not depend on the batch)
   else if (ns_tot >= 2 && cdiv(groups_hint, 4) < 700) {  // less than one round of the chip: two column parts per task
@@ -762,10 +762,10 @@ int sconv_split_forward(const float* in, int64_t n_in_cap, const RowGroups& rg, 
   }                                                      //  with 1 / 2 / 4 parts, 64->128 56 / 45 / 51, L3 64->64 43 / 41; round 5, fp16 kernels:
                                                          //  4 parts change neither the layers (profiles/r05g_parts4.txt) nor scans/s)
   const int nsw = ns_tot / parts;
-  if (gated_in2) {
-    EGONN_REQUIRE(cin == 32 && cout == 32 && gated_gate && B >= 1 && !a.in_split && cfg == 142, EGONN_ERR_INVALID,
+  if (c.in2) {
+    EGONN_REQUIRE(cin == 32 && cout == 32 && c.gate && l.B >= 1 && !a.in_split && cfg == 142, EGONN_ERR_INVALID,
                   "sconv(split): the gated input exists for the 32->32 plan only");
-    a.in2 = gated_in2; a.gate = gated_gate; a.B = B;
+    a.in2 = c.in2; a.gate = c.gate; a.B = l.B;
     return launch_split<32, 32, 4, 1, false, true>(a, groups_hint, stream);
   }
 #define EGONN_SP_KW(CI, CO, NWW, NSWW, KWW)                                                               \
@@ -810,15 +810,6 @@ int sconv_split_forward(const float* in, int64_t n_in_cap, const RowGroups& rg, 
 #undef EGONN_SP_LOCK_TRACE
   set_error("sconv(split): no instantiation for %d->%d cfg %d", cin, cout, cfg);
   return EGONN_ERR_INVALID;
-}
-
-int sconv_split_default_cfg(int cin, int cout, int64_t groups_hint) {
-  (void)cin; (void)cout; (void)groups_hint;
-  static const int env_cfg = [] {                        // EGONN_SPLIT_CFG: measurement override
-    const char* e = getenv("EGONN_SPLIT_CFG");
-    return e ? atoi(e) : 0;
-  }();
-  return env_cfg ? env_cfg : 142;                        // lock-step kernel, workgroups of 4 waves
 }
 
 }  // namespace egonn
