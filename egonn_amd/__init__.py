@@ -16,6 +16,7 @@ from .registration import (get_ransac_result, calculate_repeatability, register_
                            RegistrationResult, voxel_downsample, icp_pairs, refine_pairs, icp)
 from .augment import (TrainTransform, TrainSetTransform, TrainBatcher, JitterPoints, RemoveRandomPoints, RandomTranslation,
                       RandomRotation, RemoveRandomBlock, RandomFlip, RigidPerturbation, AugmentParams, augment_points)
+from .scan_context import ScanContext, ScanContextManager, sc2rk, distance_sc, evaluate as evaluate_scan_context
 
 __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "MinkHead", "MinkTrunk",
            "CartesianQuantizer", "PolarQuantizer", "Quantizer", "DescriptorExtractor", "GraphExtractor", "StreamingExtractor", "MinkFPN", "MinkLoc", "MinkLoc3D",
@@ -23,4 +24,5 @@ __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "Mink
            "get_ransac_result", "calculate_repeatability", "register_pairs", "evaluate_local", "match_mutual", "RegistrationResult",
            "voxel_downsample", "icp_pairs", "refine_pairs", "icp",
            "TrainTransform", "TrainSetTransform", "TrainBatcher", "JitterPoints", "RemoveRandomPoints", "RandomTranslation",
-           "RandomRotation", "RemoveRandomBlock", "RandomFlip", "RigidPerturbation", "AugmentParams", "augment_points"]
+           "RandomRotation", "RemoveRandomBlock", "RandomFlip", "RigidPerturbation", "AugmentParams", "augment_points",
+           "ScanContext", "ScanContextManager", "sc2rk", "distance_sc", "evaluate_scan_context"]

@@ -117,6 +117,10 @@ _SIGS = [
                                   _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     ("egonn_augment_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
     ("egonn_augment_points", C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("egonn_scan_context", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _P]),
+    ("egonn_scan_context_ringkey", C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P]),
+    ("egonn_scan_context_distance", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
+    ("egonn_scan_context_rerank", C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P]),
     ("egonn_profile_enable", C.c_int, [_P, C.c_int, C.c_char_p]),
     ("egonn_profile_fetch", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),

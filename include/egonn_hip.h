@@ -576,6 +576,36 @@ int egonn_augment_points(const float* points, int64_t n, const int64_t* scan_off
                          const egonn_augment_params* params, const float* T_in, float* out_points, float* T_out,
                          int32_t* rec_i, double* rec_d, uint8_t* flags, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ ScanContext baseline (hand-crafted descriptor)
+ * replaces third_party/scan_context/scan_context.py: ScanContext.__call__ (:9-55), sc2rk (:86-88), distance_sc (:58-83) and the
+ * rerank of ScanContextManager.query (:145-154); evaluate_scan_context.py:24-84 is built on these plus egonn_knn over the ring
+ * keys and egonn_recall_counts (egonn_amd/scan_context.py).  Supported shapes: 1 <= num_ring <= 40, 2 <= num_sector <= 128,
+ * rerank 1 <= k <= 128.  No host synchronisation, no float atomics: every result is bitwise reproducible and independent of
+ * the batch an item sits in; every call can be captured into a graph.
+ *
+ * Descriptor: points (n,3) f32, scan b = rows [scan_offsets[b], scan_offsets[b+1]) (DEVICE int64, batch_size+1; n is a
+ * CAPACITY as in egonn_filter_points).  In float32, as the reference computes on float32 arrays: theta = clip(atan2(y,x) +
+ * pi, 0, 2pi - 1e-6), ring = floor(|(x,y)| / (max_length / num_ring)), sector = floor(theta / (2pi / num_sector)) (both the
+ * floor of the exact quotient of the float32 operands, which is what numpy's floor-division gives); points with ring >=
+ * num_ring or a NaN coordinate are dropped; cell = max(0, max over its points of z + lidar_height), an empty cell +0.0.
+ * out_sc (batch_size, num_ring, num_sector) f32, out_ringkey (batch_size, num_ring) f32 (nullable) = the row means. */
+int egonn_scan_context(const float* points, int64_t n, const int64_t* scan_offsets, int batch_size, int num_sector,
+                       int num_ring, double max_length, double lidar_height, float* out_sc, float* out_ringkey, void* stream);
+/* sc2rk on its own: sc (n, num_ring, num_sector) f32 -> out_ringkey (n, num_ring), the mean over sectors in a fixed order */
+int egonn_scan_context_ringkey(const float* sc, int64_t n, int num_ring, int num_sector, float* out_ringkey, void* stream);
+/* distance_sc(map_sc[c], query_sc[q]) for c = candidates[q][j] (DEVICE int32 (n_query, k); NULL = every map element, k =
+ * n_map): for shift i = 1..S, a = roll(candidate, i) along the sectors, sim_i = mean over the columns whose norm exceeds 1e-8
+ * on both sides of the column cosine; out_dist = 1 - max_i sim_i, out_yaw = (argmax_i + 1) % S with the first maximum in
+ * shift order 1..S (the identity shift i = S loses ties) and, as np.argmax / np.max have it, NaN as the maximum: a pair with
+ * an all-zero descriptor gives (NaN, 1).  A candidate outside [0, n_map) gives (+inf, -1).  fp32 arithmetic. */
+int egonn_scan_context_distance(const float* query_sc, int64_t n_query, const float* map_sc, int64_t n_map, int num_ring,
+                                int num_sector, const int32_t* candidates, int k, float* out_dist, int32_t* out_yaw,
+                                void* stream);
+/* every query's k entries ascending by distance, NaN after every number (np.argsort), equal distances by lower candidate
+ * index then lower position.  candidates nullable (= the position).  Outputs must not alias inputs. */
+int egonn_scan_context_rerank(const float* dist, const int32_t* yaw, const int32_t* candidates, int64_t n_query, int k,
+                              int32_t* out_index, float* out_dist, int32_t* out_yaw, void* stream);
+
 /* ------------------------------------------------------------------ launch timing (bench.py roofline leg)
  * mode 0: off; 1: time every tagged sparse-conv launch (event records around it); 2: only launches whose tag contains
  * `filter`, with the events attached to the kernel dispatch itself (the kernel's own begin..end, also when other streams
