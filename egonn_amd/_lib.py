@@ -89,6 +89,10 @@ _SIGS = [
     ("egonn_affine_act", C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     ("egonn_affine3", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int, _P, _P]),
     ("egonn_relu_backward", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P]),
+    ("egonn_contrastive_loss_scratch_floats", C.c_int64, [C.c_int]),
+    ("egonn_contrastive_loss", C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P]),
+    ("egonn_se_gate", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ("egonn_se_gate_backward", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("egonn_eca_gate", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     ("egonn_eca_gate_backward", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     ("egonn_act_backward", C.c_int, [C.c_int, _P, _P, C.c_int64, C.c_int, _P, _P]),
@@ -423,6 +427,21 @@ class Context:
             check(self.lib.egonn_block_tail(self.h, level, x.data_ptr(), residual.data_ptr(), x.shape[1], _ptr(ew),
                                             0 if ew is None else ew.numel(), out.data_ptr(), _stream()))
         return out
+
+    def se_gate(self, mean: torch.Tensor, fc, want_hidden: bool = False):
+        """SELayer.fc on the (B, C) per-sample means: sigmoid(W2 relu(W1 mean + b1) + b2) -> gate (B, C) [, hidden (B, C/16)].
+        `fc`: the SELayer's Sequential (fc[0].linear, fc[2].linear)."""
+        mean = _dev_f32(mean, self.device)
+        w1, b1, w2, b2 = (_dev_f32(t.detach(), self.device) for t in (fc[0].linear.weight, fc[0].linear.bias,
+                                                                       fc[2].linear.weight, fc[2].linear.bias))
+        B, c = mean.shape
+        h = w1.shape[0]
+        assert w1.shape == (h, c) and w2.shape == (c, h) and b1.shape == (h,) and b2.shape == (c,)
+        gate = torch.empty_like(mean)
+        hid = torch.empty((B, h), dtype=torch.float32, device=self.device) if want_hidden else None
+        self._call(self.lib.egonn_se_gate, mean.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, c, h,
+                   gate.data_ptr(), _ptr(hid))
+        return (gate, hid) if want_hidden else gate
 
     def add(self, a: torch.Tensor, b: torch.Tensor):
         a, b = _dev_f32(a, self.device), _dev_f32(b, self.device)

@@ -185,6 +185,10 @@ int sigmoid_gate(const float* y, const float* t, const float* grad, int64_t n, f
                  hipStream_t stream);
 
 // loss.hip ---------------------------------------------------------------------------------------
+size_t contrastive_loss_scratch_floats(int n);
+int contrastive_loss_forward(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float pos_margin,
+                             float neg_margin, float* out13, int32_t* triplets, float* grad, float* scratch,
+                             hipStream_t stream);
 size_t triplet_loss_scratch_floats(int n);
 int triplet_loss_forward(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float margin,
                          float* out10, int32_t* triplets, float* grad, float* scratch, hipStream_t stream);
@@ -223,6 +227,12 @@ int seg_sums2(int mode, const float* a, const float* b, const float* x2, const f
 int gem_backward_rows(const float* x, const float* coef, const float* p, const int32_t* boff, int B, int64_t n, int c,
                       float* dx, hipStream_t stream);
 
+// SELayer.fc on the (B, c) per-sample means (layers/senet_block.py:39-49): gate = sigmoid(W2 relu(W1 mean + b1) + b2), h = c / 16
+int se_gate_forward(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, int B, int c, int h,
+                    float* gate, float* hidden_out, hipStream_t stream);
+int se_gate_backward(const float* dgate, const float* gate, const float* hid, const float* mean, const float* w1,
+                     const float* w2, int B, int c, int h, float* dmean, float* dw1, float* db1, float* dw2, float* db2,
+                     hipStream_t stream);
 int eca_gate_forward(const float* mean, const float* w, int ks, int B, int c, float* gate, hipStream_t stream);
 int eca_gate_backward(const float* dgate, const float* gate, const float* mean, const float* w, int ks, int B, int c,
                       float* dmean, float* dw, hipStream_t stream);

@@ -194,6 +194,124 @@ int triplet_loss_forward(const float* emb, int n, int d, const uint8_t* pos, con
   return EGONN_OK;
 }
 
+// ------------------------------------------------------------------ batch-hard contrastive loss
+// Reference: models/loss.py:175-204 (BatchHardContrastiveLossWithMasks) on the miner above (:114-143).  The loss class lives in
+// pytorch_metric_learning (absent from the image) and is restated from its documentation [recall], like the triplet loss:
+// ContrastiveLoss(pos_margin, neg_margin, distance=LpDistance(p=2, power=1, normalize_embeddings=False), AvgNonZeroReducer) on
+// the mined triplets read as the pairs (a, p) and (a, n):
+//   pos_i = relu(D[a][p] - pos_margin)      neg_i = relu(neg_margin - D[a][n])      (plain Euclidean distance, no swap)
+//   loss  = mean of the pos_i > 0 (0 if none) + mean of the neg_i > 0 (0 if none)
+// out[0] loss, [1] num_triplets, [2] pos_pairs_above_threshold, [3] neg_pairs_above_threshold, [4] pos_loss, [5] neg_loss,
+// [6] avg_embedding_norm, [7..9] mean/max/min hardest-positive distance, [10..12] mean/max/min hardest-negative distance
+__global__ __launch_bounds__(256) void contrastive_loss_kernel(const float* __restrict__ D, const int32_t* __restrict__ trip,
+                                                               const float* __restrict__ hp, const float* __restrict__ hn,
+                                                               const float* __restrict__ norms, int n, float pos_margin,
+                                                               float neg_margin, float* __restrict__ lp,
+                                                               float* __restrict__ ln, float* __restrict__ out) {
+  __shared__ float red[256];
+  const int t = threadIdx.x;
+  float sp_l = 0.f, sn_l = 0.f, nt = 0.f, cp = 0.f, cn = 0.f, sn = 0.f, sp = 0.f, mxp = -INFINITY, mnp = INFINITY, sng = 0.f,
+        mxn = -INFINITY, mnn = INFINITY;
+  for (int i = t; i < n; i += 256) {
+    float a = 0.f, b = 0.f;
+    if (trip[3 * i] >= 0) {
+      a = fmaxf(D[(int64_t)i * n + trip[3 * i + 1]] - pos_margin, 0.f);
+      b = fmaxf(neg_margin - D[(int64_t)i * n + trip[3 * i + 2]], 0.f);
+      nt += 1.f;
+      if (a > 0.f) { cp += 1.f; sp_l += a; }
+      if (b > 0.f) { cn += 1.f; sn_l += b; }
+    }
+    lp[i] = a;
+    ln[i] = b;
+    sn += norms[i];
+    sp += hp[i]; mxp = fmaxf(mxp, hp[i]); mnp = fminf(mnp, hp[i]);
+    sng += hn[i]; mxn = fmaxf(mxn, hn[i]); mnn = fminf(mnn, hn[i]);
+  }
+  float v[12] = {sp_l, sn_l, nt, cp, cn, sn, sp, mxp, mnp, sng, mxn, mnn};
+  // fixed-order tree reductions (deterministic); max: 7, 10; min: 8, 11; the rest sums
+  for (int k = 0; k < 12; ++k) {
+    __syncthreads();
+    red[t] = v[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (t < o) {
+        const float a = red[t], b = red[t + o];
+        red[t] = (k == 7 || k == 10) ? fmaxf(a, b) : ((k == 8 || k == 11) ? fminf(a, b) : a + b);
+      }
+      __syncthreads();
+    }
+    v[k] = red[0];
+  }
+  if (t == 0) {
+    const float pl = v[3] > 0.f ? v[0] / v[3] : 0.f, nl = v[4] > 0.f ? v[1] / v[4] : 0.f;
+    out[0] = pl + nl;
+    out[1] = v[2];
+    out[2] = v[3];
+    out[3] = v[4];
+    out[4] = pl;
+    out[5] = nl;
+    out[6] = v[5] / (float)n;
+    out[7] = v[6] / (float)n; out[8] = v[7]; out[9] = v[8];
+    out[10] = v[9] / (float)n; out[11] = v[10]; out[12] = v[11];
+  }
+}
+
+// dLoss/dE[r][:], gathered per row in fixed anchor order like triplet_grad_kernel: + d(i,p) / #pos for an active positive
+// hinge, - d(i,n) / #neg for an active negative hinge; a zero distance contributes nothing.
+__global__ __launch_bounds__(256) void contrastive_grad_kernel(const float* __restrict__ e, const float* __restrict__ D,
+                                                               const int32_t* __restrict__ trip,
+                                                               const float* __restrict__ lp, const float* __restrict__ ln,
+                                                               const float* __restrict__ out, int n, int d,
+                                                               float* __restrict__ grad) {
+  const int r = blockIdx.x;
+  const float wp = out[2] > 0.f ? 1.f / out[2] : 0.f, wn = out[3] > 0.f ? 1.f / out[3] : 0.f;
+  for (int c = threadIdx.x; c < d; c += blockDim.x) {
+    float g = 0.f;
+    const float er = e[(int64_t)r * d + c];
+    for (int i = 0; i < n; ++i) {
+      if (trip[3 * i] < 0) continue;
+      const int p = trip[3 * i + 1], q = trip[3 * i + 2];
+      if (lp[i] > 0.f && (r == i || r == p)) {
+        const float dap = D[(int64_t)i * n + p];
+        if (dap > 0.f) {
+          if (r == i) g += wp * (er - e[(int64_t)p * d + c]) / dap;
+          if (r == p) g -= wp * (e[(int64_t)i * d + c] - er) / dap;
+        }
+      }
+      if (ln[i] > 0.f && (r == i || r == q)) {
+        const float dan = D[(int64_t)i * n + q];
+        if (dan > 0.f) {
+          if (r == i) g -= wn * (er - e[(int64_t)q * d + c]) / dan;
+          if (r == q) g += wn * (e[(int64_t)i * d + c] - er) / dan;
+        }
+      }
+    }
+    grad[(int64_t)r * d + c] = g;
+  }
+}
+
+size_t contrastive_loss_scratch_floats(int n) { return (size_t)n * n + 5 * (size_t)n + 64; }
+
+int contrastive_loss_forward(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float pos_margin,
+                             float neg_margin, float* out13, int32_t* triplets, float* grad, float* scratch,
+                             hipStream_t stream) {
+  EGONN_REQUIRE(n >= 1 && d >= 1 && d <= 4096, EGONN_ERR_INVALID, "contrastive loss: n=%d d=%d out of range", n, d);
+  float* D = scratch;
+  float* norms = D + (size_t)n * n;
+  float* hp = norms + n;
+  float* hn = hp + n;
+  float* lp = hn + n;
+  float* ln = lp + n;
+  hipLaunchKernelGGL(pdist_kernel, dim3(n), dim3(256), d * sizeof(float), stream, emb, n, d, D, norms);
+  hipLaunchKernelGGL(mine_kernel, dim3(n), dim3(256), 0, stream, D, pos, neg, n, triplets, hp, hn);
+  hipLaunchKernelGGL(contrastive_loss_kernel, dim3(1), dim3(256), 0, stream, D, triplets, hp, hn, norms, n, pos_margin,
+                     neg_margin, lp, ln, out13);
+  if (grad)
+    hipLaunchKernelGGL(contrastive_grad_kernel, dim3(n), dim3(256), 0, stream, emb, D, triplets, lp, ln, out13, n, d, grad);
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}
+
 // ------------------------------------------------------------------ local-head losses (models/loss_utils.py)
 // KeypointLoss (:23-95) and CorrespondenceLoss (:108-139), driven per pair of scans by KeypointCorrLoss
 // (models/loss.py:43-92), need three searches that the reference does on dense torch.cdist matrices:

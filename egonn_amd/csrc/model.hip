@@ -1282,6 +1282,18 @@ API int egonn_profile_fetch(egonn_ctx* c, int cap, int* n, char* names, float* m
 }
 
 
+// ------------------------------------------------------------------------------------------ batch-hard contrastive loss
+API int64_t egonn_contrastive_loss_scratch_floats(int n) { return (int64_t)contrastive_loss_scratch_floats(n); }
+
+API int egonn_contrastive_loss(const float* embeddings, int n, int d, const uint8_t* positives_mask,
+                               const uint8_t* negatives_mask, float pos_margin, float neg_margin, float* out_stats,
+                               int32_t* out_triplets, float* out_grad, float* scratch, void* stream) {
+  EGONN_REQUIRE(embeddings && positives_mask && negatives_mask && out_stats && out_triplets && scratch, EGONN_ERR_INVALID,
+                "contrastive_loss: null argument");
+  return contrastive_loss_forward(embeddings, n, d, positives_mask, negatives_mask, pos_margin, neg_margin, out_stats,
+                                  out_triplets, out_grad, scratch, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------ batch-hard triplet loss
 API int64_t egonn_triplet_loss_scratch_floats(int n) { return (int64_t)triplet_loss_scratch_floats(n); }
 
@@ -1424,6 +1436,19 @@ API int egonn_eca_gate_backward(const float* grad_gate, const float* gate, const
                 "eca_gate_backward: null argument");
   return eca_gate_backward(grad_gate, gate, mean, conv_weight, kernel_size, batch_size, channels, grad_mean, grad_weight,
                            (hipStream_t)stream);
+}
+API int egonn_se_gate(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, int batch_size,
+                      int channels, int hidden, float* gate, float* hidden_out, void* stream) {
+  EGONN_REQUIRE(mean && w1 && b1 && w2 && b2 && gate, EGONN_ERR_INVALID, "se_gate: null argument");
+  return se_gate_forward(mean, w1, b1, w2, b2, batch_size, channels, hidden, gate, hidden_out, (hipStream_t)stream);
+}
+API int egonn_se_gate_backward(const float* grad_gate, const float* gate, const float* hidden_act, const float* mean,
+                               const float* w1, const float* w2, int batch_size, int channels, int hidden, float* grad_mean,
+                               float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, void* stream) {
+  EGONN_REQUIRE(grad_gate && gate && hidden_act && mean && w1 && w2 && grad_mean && grad_w1 && grad_b1 && grad_w2 && grad_b2,
+                EGONN_ERR_INVALID, "se_gate_backward: null argument");
+  return se_gate_backward(grad_gate, gate, hidden_act, mean, w1, w2, batch_size, channels, hidden, grad_mean, grad_w1, grad_b1,
+                          grad_w2, grad_b2, (hipStream_t)stream);
 }
 API int egonn_act_backward(int act, const float* grad_out, const float* out, int64_t n, int c, float* grad_in, void* stream) {
   EGONN_REQUIRE(grad_out && out && grad_in && act >= 0 && act <= 4, EGONN_ERR_INVALID, "act_backward: bad arguments");

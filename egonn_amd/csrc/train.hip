@@ -1154,6 +1154,140 @@ int eca_gate_backward(const float* dgate, const float* gate, const float* mean, 
   return EGONN_OK;
 }
 
+// ------------------------------------------------------------------------------------------ SE gate on (B, C) means
+// gate = sigmoid(W2 relu(W1 mean_b + b1) + b2): SELayer.fc on the pooled means (layers/senet_block.py:39-43,48-49), W1 (H, C) and
+// W2 (C, H) in nn.Linear layout, H = C / 16 (reduction = 16), 16 <= C <= 256.  One workgroup per sample forward.  Every sum has
+// an order that depends on C and H alone: 16 lanes share a hidden unit (lane l takes the channels l, l + 16, ... in turn, then a
+// 4-level butterfly), the output layer is one serial chain of H terms per channel.
+static constexpr int SE_MAX_C = 256, SE_MAX_H = 16;
+__global__ __launch_bounds__(256) void se_gate_fwd_kernel(const float* __restrict__ mean, const float* __restrict__ w1,
+                                                         const float* __restrict__ b1, const float* __restrict__ w2,
+                                                         const float* __restrict__ b2, int c, int h, float* __restrict__ gate,
+                                                         float* __restrict__ hidden_out) {
+  __shared__ float s_mean[SE_MAX_C];
+  __shared__ float s_h[SE_MAX_H];
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (t < c) s_mean[t] = mean[(int64_t)b * c + t];
+  __syncthreads();
+  const int j = t >> 4, l = t & 15;
+  float s = 0.f;
+  if (j < h)
+    for (int k = l; k < c; k += 16) s = fmaf(w1[j * c + k], s_mean[k], s);
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
+  if (j < h && l == 0) {
+    const float a = fmaxf(s + b1[j], 0.f);
+    s_h[j] = a;
+    if (hidden_out) hidden_out[(int64_t)b * h + j] = a;
+  }
+  __syncthreads();
+  if (t < c) {
+    float z = b2[t];
+    for (int q = 0; q < h; ++q) z = fmaf(w2[t * h + q], s_h[q], z);
+    gate[(int64_t)b * c + t] = 1.f / (1.f + expf(-z));
+  }
+}
+// Backward in ONE workgroup, thread = channel.  The samples are walked in order, four per round (one wave each for the hidden
+// gradient), so every parameter gradient is a serial sum over b = 0, 1, ... whatever B is: bitwise reproducible, no atomics.
+//   dz2 = dgate g (1 - g);  db2[c] = sum_b dz2;  dW2[c][j] = sum_b dz2 h[b][j];  dz1[b][j] = [h > 0] sum_c dz2 W2[c][j]
+//   db1[j] = sum_b dz1;  dW1[j][c] = sum_b dz1[b][j] mean[b][c];  dmean[b][c] = sum_j dz1[b][j] W1[j][c]
+__global__ __launch_bounds__(256) void se_gate_bwd_kernel(const float* __restrict__ dgate, const float* __restrict__ gate,
+                                                         const float* __restrict__ hid, const float* __restrict__ mean,
+                                                         const float* __restrict__ w1, const float* __restrict__ w2, int B, int c,
+                                                         int h, float* __restrict__ dmean, float* __restrict__ dw1,
+                                                         float* __restrict__ db1, float* __restrict__ dw2,
+                                                         float* __restrict__ db2) {
+  __shared__ float s_w2[SE_MAX_C * SE_MAX_H];
+  __shared__ float s_dz2[4][SE_MAX_C];
+  __shared__ float s_dz1[4][SE_MAX_H];
+  __shared__ float s_hid[4][SE_MAX_H];
+  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  for (int e = t; e < c * h; e += 256) s_w2[e] = w2[e];
+  float w1c[SE_MAX_H], a_w1[SE_MAX_H], a_w2[SE_MAX_H];
+#pragma unroll
+  for (int j = 0; j < SE_MAX_H; ++j) {
+    w1c[j] = (t < c && j < h) ? w1[j * c + t] : 0.f;
+    a_w1[j] = a_w2[j] = 0.f;
+  }
+  float a_b2 = 0.f, a_b1 = 0.f;                   // a_b1: thread j < h
+  for (int b0 = 0; b0 < B; b0 += 4) {
+    const int nb = min(4, B - b0);
+    __syncthreads();                              // the previous round is consumed (first round: s_w2 is complete)
+    for (int s = 0; s < nb; ++s) {
+      if (t < c) {
+        const int64_t e = (int64_t)(b0 + s) * c + t;
+        const float g = gate[e];
+        s_dz2[s][t] = dgate[e] * g * (1.f - g);
+      }
+      if (t < h) s_hid[s][t] = hid[(int64_t)(b0 + s) * h + t];
+    }
+    __syncthreads();
+    {                                             // wave s: dz1 of sample b0 + s; 4 lanes share a hidden unit
+      const int j = lane >> 2, l = lane & 3;
+      float v = 0.f;
+      if (wave < nb && j < h)
+        for (int k = l; k < c; k += 4) v = fmaf(s_dz2[wave][k], s_w2[k * h + j], v);
+      v += __shfl_xor(v, 1, 4);
+      v += __shfl_xor(v, 2, 4);
+      if (wave < nb && j < h && l == 0) s_dz1[wave][j] = s_hid[wave][j] > 0.f ? v : 0.f;
+    }
+    __syncthreads();
+    for (int s = 0; s < nb; ++s) {
+      if (t < c) {
+        const int64_t e = (int64_t)(b0 + s) * c + t;
+        const float dz2 = s_dz2[s][t], m = mean[e];
+        float dm = 0.f;
+        a_b2 += dz2;
+#pragma unroll
+        for (int j = 0; j < SE_MAX_H; ++j) {
+          if (j < h) {
+            const float dz1 = s_dz1[s][j];
+            a_w2[j] = fmaf(dz2, s_hid[s][j], a_w2[j]);
+            a_w1[j] = fmaf(dz1, m, a_w1[j]);
+            dm = fmaf(dz1, w1c[j], dm);
+          }
+        }
+        dmean[e] = dm;
+      }
+      if (t < h) a_b1 += s_dz1[s][t];
+    }
+  }
+  if (t < c) {
+    db2[t] = a_b2;
+#pragma unroll
+    for (int j = 0; j < SE_MAX_H; ++j) {
+      if (j < h) {
+        dw2[t * h + j] = a_w2[j];
+        dw1[j * c + t] = a_w1[j];
+      }
+    }
+  }
+  if (t < h) db1[t] = a_b1;
+}
+static int se_check(int B, int c, int h) {
+  EGONN_REQUIRE(B >= 0 && c >= 16 && c <= SE_MAX_C && c % 16 == 0 && h == c / 16, EGONN_ERR_INVALID,
+                "se_gate: B=%d channels=%d hidden=%d unsupported (channels a multiple of 16 in 16..256, hidden = channels/16)",
+                B, c, h);
+  return EGONN_OK;
+}
+int se_gate_forward(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, int B, int c, int h,
+                    float* gate, float* hidden_out, hipStream_t stream) {
+  EGONN_TRY(se_check(B, c, h));
+  if (B == 0) return EGONN_OK;
+  hipLaunchKernelGGL(se_gate_fwd_kernel, dim3((unsigned)B), dim3(256), 0, stream, mean, w1, b1, w2, b2, c, h, gate, hidden_out);
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}
+int se_gate_backward(const float* dgate, const float* gate, const float* hid, const float* mean, const float* w1,
+                     const float* w2, int B, int c, int h, float* dmean, float* dw1, float* db1, float* dw2, float* db2,
+                     hipStream_t stream) {
+  EGONN_TRY(se_check(B, c, h));
+  hipLaunchKernelGGL(se_gate_bwd_kernel, dim3(1), dim3(256), 0, stream, dgate, gate, hid, mean, w1, w2, B, c, h, dmean, dw1, db1,
+                     dw2, db2);
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}
+
 // ------------------------------------------------------------------------------------------ activations / L2 normalisation
 // grad_in = grad_out * act'(.) expressed through the activation's OUTPUT y:
 //   relu: [y > 0]   tanh: 1 - y^2   softplus: 1 - exp(-y)  (= sigmoid(x))   sigmoid: y (1 - y)

@@ -1,6 +1,7 @@
 """MinkLoc / MinkLoc3D (MinkFPN backbone + GeM) with the reference's Python surface, executed through the
 per-operator entry points of libegonn_hip (reference: models/minkfpn.py, models/minkloc.py,
-third_party/minkloc3d/minkloc.py, models/resnet.py:81-117).  Same kernels as EgoNN, second graph; the module
+third_party/minkloc3d/minkloc.py, models/resnet.py:81-117; blocks: ME BasicBlock, layers/eca_block.py ECABasicBlock,
+layers/senet_block.py SEBasicBlock).  Same kernels as EgoNN, second graph; the module
 tree only holds parameters (identical state_dict keys/shapes), there is no PyTorch fallback.  MinkLoc's pooling
 (layers/pooling.py:13-43) is GeM, MAC, SPoC, netvlad or netvladgc, in eval and in train mode (egonn_amd/train.py: pool).
 """
@@ -12,14 +13,28 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .model import SparseConv, BatchNorm, ECALayer, PoolingWrapper, GeM
+from .model import SparseConv, BatchNorm, ECALayer, Linear, _NoParams, PoolingWrapper, GeM
+
+
+class SELayer(nn.Module):
+    """reference layers/senet_block.py:34-50: fc = MinkowskiLinear(C, C/r), ReLU, MinkowskiLinear(C/r, C), Sigmoid on the
+    per-sample means (keys se.fc.0.linear.*, se.fc.2.linear.*); evaluated by egonn_se_gate."""
+
+    def __init__(self, channel, reduction=16):
+        super().__init__()
+        if reduction != 16 or channel % 16 or not 16 <= channel <= 256:
+            raise NotImplementedError(f'SELayer({channel}, reduction={reduction}): egonn_se_gate covers reduction 16 and a '
+                                      f'multiple of 16 channels in 16..256')
+        self.fc = nn.Sequential(Linear(channel, channel // reduction), _NoParams(), Linear(channel // reduction, channel),
+                                _NoParams())
 
 
 class BasicBlock(nn.Module):
-    """ME modules.resnet_block.BasicBlock parameters (conv1 norm1 conv2 norm2 [downsample])."""
+    """ME modules.resnet_block.BasicBlock parameters (conv1 norm1 conv2 norm2 [downsample]); with `eca` the reference's
+    ECABasicBlock (layers/eca_block.py:39-54), with `se` its SEBasicBlock (layers/senet_block.py:53-70)."""
     expansion = 1
 
-    def __init__(self, inplanes, planes, downsample=None, eca: bool = False):
+    def __init__(self, inplanes, planes, downsample=None, eca: bool = False, se: bool = False):
         super().__init__()
         self.conv1 = SparseConv(inplanes, planes, 3)
         self.norm1 = BatchNorm(planes)
@@ -28,6 +43,8 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
         if eca:
             self.eca = ECALayer(planes, gamma=2, b=1)      # reference layers/eca_block.py:54
+        if se:
+            self.se = SELayer(planes, reduction=16)        # reference layers/senet_block.py:70
 
 
 class MinkFPN(nn.Module):
@@ -37,11 +54,16 @@ class MinkFPN(nn.Module):
                  layers: Sequence[int] = (1, 1, 1), planes: Sequence[int] = (32, 64, 64)):
         super().__init__()
         assert len(layers) == len(planes) and 1 <= len(layers) and 0 <= num_top_down <= len(layers)
-        if block not in ('BasicBlock', 'ECABasicBlock'):
-            raise NotImplementedError(f'block {block!r}: the MI355X path implements BasicBlock and ECABasicBlock')
+        if block == 'Bottleneck':
+            raise NotImplementedError(
+                "block 'Bottleneck': the reference cannot run it either, so there is nothing to match: a Bottleneck layer emits "
+                "planes[-1] * 4 channels (models/resnet.py:107) while MinkFPN builds its lateral conv1x1[0] for planes[-1] input "
+                "channels (models/minkfpn.py:49)")
+        if block not in ('BasicBlock', 'ECABasicBlock', 'SEBasicBlock'):
+            raise NotImplementedError(f'block {block!r}: the MI355X path implements BasicBlock, ECABasicBlock and SEBasicBlock')
         self.num_bottom_up, self.num_top_down = len(layers), num_top_down
         self.layers, self.planes, self.lateral_dim = list(layers), list(planes), out_channels
-        eca = block == 'ECABasicBlock'
+        eca, se = block == 'ECABasicBlock', block == 'SEBasicBlock'
         self.convs, self.bn, self.blocks = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
         self.tconvs, self.conv1x1 = nn.ModuleList(), nn.ModuleList()
         inplanes = planes[0]
@@ -53,9 +75,9 @@ class MinkFPN(nn.Module):
             down = None
             if inplanes != plane:
                 down = nn.Sequential(SparseConv(inplanes, plane, 1), BatchNorm(plane))
-            blocks = [BasicBlock(inplanes, plane, down, eca)]
+            blocks = [BasicBlock(inplanes, plane, down, eca, se)]
             inplanes = plane
-            blocks += [BasicBlock(inplanes, plane, None, eca) for _ in range(1, layer)]
+            blocks += [BasicBlock(inplanes, plane, None, eca, se) for _ in range(1, layer)]
             self.blocks.append(nn.Sequential(*blocks))
         for i in range(num_top_down):
             self.conv1x1.append(SparseConv(planes[-1 - i], out_channels, 1))
@@ -77,6 +99,9 @@ class MinkFPN(nn.Module):
             t = conv_bn(level, level, 3, x, b.conv1, b.norm1, True)
             t = conv_bn(level, level, 3, t, b.conv2, b.norm2, False)
             res = x if b.downsample is None else conv_bn(level, level, 1, x, b.downsample[0], b.downsample[1], False)
+            if hasattr(b, 'se'):      # SEBasicBlock tail (layers/senet_block.py:81-87): pool -> fc gate -> relu(t * gate + res)
+                gate = ctx.se_gate(ctx.global_avg_pool(level, t), b.se.fc)
+                return ctx.gate_residual(level, t, gate, res, relu=True)
             return ctx.block_tail(level, t, res, b.eca.conv.weight if hasattr(b, 'eca') else None)
 
         x = conv_bn(0, 0, self.conv0.kernel_size, feats0, self.conv0, self.bn0, True)

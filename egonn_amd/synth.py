@@ -69,7 +69,8 @@ def seeded_tensor(seed: int, key: str, shape: Tuple[int, ...]) -> np.ndarray:
     """Deterministic fp32 tensor for a state_dict entry.  Distribution by key suffix:
     conv kernels / linear weights ~ N(0, sqrt(2/fan)), BN weight ~ U(0.5,1.5), BN bias and
     running_mean ~ N(0,0.1), running_var ~ U(0.5,1.5), linear bias ~ N(0,0.05), GeM p = 3; NetVLAD cluster / hidden
-    matrices ~ N(0,1)/sqrt(C), gate ~ N(0,1)/sqrt(D), its bn1 / bn2 weight ~ U(0.5,1.5) and bias ~ N(0,0.1)."""
+    matrices ~ N(0,1)/sqrt(C), gate ~ N(0,1)/sqrt(D), its bn1 / bn2 weight ~ U(0.5,1.5) and bias ~ N(0,0.1); SELayer.fc
+    weights ~ N(0, 3 sqrt(2/fan)) and biases ~ N(0,0.3)."""
     rng = np.random.default_rng(_key_seed(seed, key))
     shape = tuple(int(s) for s in shape)
     if key.endswith("num_batches_tracked"):
@@ -105,6 +106,12 @@ def seeded_tensor(seed: int, key: str, shape: Tuple[int, ...]) -> np.ndarray:
         return rng.uniform(0.5, 1.5, size=shape).astype(np.float32)
     if key.endswith(("bn1.bias", "bn2.bias")):
         return (rng.standard_normal(shape) * 0.1).astype(np.float32)
+    # SELayer.fc (layers/senet_block.py:39-43): three times the linear rule and biases of 0.3, so that the sigmoid gates of a
+    # seeded model spread over 0.3 .. 0.7 and beyond instead of sitting at 0.5 (tests/golden/make_golden_se.py checks it)
+    if ".se.fc." in key and key.endswith("linear.weight"):
+        return (rng.standard_normal(shape) * 3.0 * np.sqrt(2.0 / shape[1])).astype(np.float32)
+    if ".se.fc." in key and key.endswith("linear.bias"):
+        return (rng.standard_normal(shape) * 0.3).astype(np.float32)
     if key.endswith("linear.weight"):
         return (rng.standard_normal(shape) * np.sqrt(2.0 / shape[1])).astype(np.float32)
     if key.endswith("linear.bias"):

@@ -240,6 +240,51 @@ def eca_tail(ctx, level, x, residual, eca_module):
     return GateResidualFn.apply(x, gate, residual, ctx, level)
 
 
+class SeGateFn(Function):
+    """sigmoid(W2 relu(W1 mean + b1) + b2) on the (B, C) per-sample means (SELayer.fc, layers/senet_block.py:39-43,49):
+    egonn_se_gate / egonn_se_gate_backward, one launch each.  The parameter gradients are serial sums over the samples in
+    order, so two runs agree bitwise."""
+
+    @staticmethod
+    def forward(fctx, mean, w1, b1, w2, b2, ctx: _lib.Context):
+        mean = _c(mean)
+        B, c = mean.shape
+        h = w1.shape[0]
+        assert w1.shape == (h, c) and w2.shape == (c, h) and all(t.is_contiguous() and t.dtype == torch.float32
+                                                                 for t in (w1, b1, w2, b2))
+        gate = torch.empty_like(mean)
+        hid = torch.empty((B, h), dtype=torch.float32, device=mean.device)
+        ctx._call(ctx.lib.egonn_se_gate, mean.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, c, h,
+                  gate.data_ptr(), hid.data_ptr())
+        fctx.save_for_backward(mean, w1, w2, gate, hid)
+        fctx.meta = ctx
+        return gate
+
+    @staticmethod
+    def backward(fctx, g):
+        mean, w1, w2, gate, hid = fctx.saved_tensors
+        ctx = fctx.meta
+        B, c = mean.shape
+        h = w1.shape[0]
+        g = _c(g)
+        dmean, dw1, dw2 = torch.empty_like(mean), torch.empty_like(w1), torch.empty_like(w2)
+        db1 = torch.empty(h, dtype=torch.float32, device=mean.device)
+        db2 = torch.empty(c, dtype=torch.float32, device=mean.device)
+        ctx._call(ctx.lib.egonn_se_gate_backward, g.data_ptr(), gate.data_ptr(), hid.data_ptr(), mean.data_ptr(), w1.data_ptr(),
+                  w2.data_ptr(), B, c, h, dmean.data_ptr(), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr())
+        return dmean, dw1, db1, dw2, db2, None
+
+
+def se_tail(ctx, level, x, residual, se_module):
+    """layers/senet_block.py:47-50,81-87: gate = sigmoid(fc(mean_b(x))), out = relu(x * gate + residual).  The gate is a
+    function of ONE sample's rows, which one rank holds whole, so under a SyncBN process group it needs no collective; the
+    gradients of the four fc tensors are summed over the ranks with every other parameter's (all_reduce_gradients)."""
+    fc = se_module.fc
+    m = SegmentMeanFn.apply(x, ctx, level)                                       # (B, C)
+    gate = SeGateFn.apply(m, fc[0].linear.weight, fc[0].linear.bias, fc[2].linear.weight, fc[2].linear.bias, ctx)
+    return GateResidualFn.apply(x, gate, residual, ctx, level)
+
+
 class AddFn(Function):
     @staticmethod
     def forward(fctx, a, b, ctx: _lib.Context):
@@ -490,7 +535,7 @@ def global_branch(model, ctx, group=None, levels=None) -> torch.Tensor:
 
 
 def minkfpn_forward(fpn, ctx, group=None):
-    """MinkFPN.forward in train mode (reference models/minkfpn.py:65-93; BasicBlock / ECABasicBlock, all-ones input
+    """MinkFPN.forward in train mode (reference models/minkfpn.py:65-93; BasicBlock / ECABasicBlock / SEBasicBlock, all-ones input
     features): the same graph as egonn_amd.minkloc.MinkFPN.run, on the differentiable operators."""
     tot = level_totals(ctx, group)
 
@@ -505,6 +550,8 @@ def minkfpn_forward(fpn, ctx, group=None):
             res = batch_norm(ctx, res, b.downsample[1], False, group, tot[level])
         if hasattr(b, 'eca'):
             return eca_tail(ctx, level, y, res, b.eca)
+        if hasattr(b, 'se'):
+            return se_tail(ctx, level, y, res, b.se)
         return GateResidualFn.apply(y, None, res, ctx, level)
 
     assert fpn.conv0.kernel_size == 5 and fpn.conv0.kernel.shape[1] == 1, "train mode: k=5, 1-channel input layer"
@@ -578,16 +625,19 @@ class TrainStep:
         forward of this rank's scans (SyncBN statistics over the whole batch: one all-reduce of C+1 and one of C
         values per BatchNorm layer and direction)
         -> RCCL all-gather of the (b_local, 256) global descriptors (differentiable, distributed.py)
-        -> batch-hard triplet loss on the gathered (B, 256) matrix with the (B, B) masks every rank holds
+        -> batch-hard triplet (or, with `loss_fn`, contrastive) loss on the gathered (B, 256) matrix with the (B, B) masks
+           every rank holds
         -> backward (each rank back-propagates the rows it produced)
         -> ONE flat SUM all-reduce of the parameter gradients -> optimizer.step()
 
     With a single process it is exactly the reference's step."""
 
-    def __init__(self, model, optimizer, margin: float = 0.2):
+    def __init__(self, model, optimizer, margin: float = 0.2, loss_fn=None):
+        """loss_fn: a global loss with the call (embeddings, positives_mask, negatives_mask) -> (loss, stats, hard_triplets),
+        e.g. loss.BatchHardContrastiveLossWithMasks(0.2, 0.65); None = the batch-hard triplet loss with `margin`."""
         from .loss import BatchHardTripletLossWithMasks
         self.model, self.optimizer = model, optimizer
-        self.loss_fn = BatchHardTripletLossWithMasks(margin)
+        self.loss_fn = BatchHardTripletLossWithMasks(margin) if loss_fn is None else loss_fn
 
     def __call__(self, batch: Dict[str, torch.Tensor], positives_mask: torch.Tensor, negatives_mask: torch.Tensor,
                  step_optimizer: bool = True, shard_sizes=None):

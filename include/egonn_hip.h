@@ -316,6 +316,22 @@ int egonn_triplet_loss(const float* embeddings, int n, int d, const uint8_t* pos
                        const uint8_t* negatives_mask, float margin, float* out_stats, int32_t* out_triplets,
                        float* out_grad, float* scratch, void* stream);
 
+/* ------------------------------------------------------------------ batch-hard contrastive loss (training)
+ * replaces BatchHardContrastiveLossWithMasks.__call__ (models/loss.py:175-204; selected by `loss = BatchHardContrastiveLoss`,
+ * models/loss.py:17-18, margins misc/utils.py:158-160) on the same distances and the same miner as egonn_triplet_loss
+ * (models/loss.py:114-143).  The loss it calls is pytorch_metric_learning's ContrastiveLoss(pos_margin, neg_margin,
+ * LpDistance(p=2, power=1), AvgNonZeroReducer), restated from its documentation [recall]: the mined triplets are read as the
+ * pairs (a,p) and (a,n); pos_i = relu(D[a][p] - pos_margin), neg_i = relu(neg_margin - D[a][n]) on the plain (not squared)
+ * Euclidean distance; each set is averaged over its entries > 0 (0 if none) and the two means are added.  No swap.
+ * out_stats (13 f32, device): loss, num_triplets, pos_pairs_above_threshold, neg_pairs_above_threshold, pos_loss, neg_loss,
+ * avg_embedding_norm, mean/max/min hardest positive distance, mean/max/min hardest negative distance.  out_triplets,
+ * out_grad (nullable; a zero distance contributes no gradient) and scratch (egonn_contrastive_loss_scratch_floats(n) device
+ * floats) as in egonn_triplet_loss.  No host sync. */
+int64_t egonn_contrastive_loss_scratch_floats(int n);
+int egonn_contrastive_loss(const float* embeddings, int n, int d, const uint8_t* positives_mask,
+                           const uint8_t* negatives_mask, float pos_margin, float neg_margin, float* out_stats,
+                           int32_t* out_triplets, float* out_grad, float* scratch, void* stream);
+
 /* ------------------------------------------------------------------ local-head losses (training)
  * replaces the dense torch.cdist / torch.min / CrossEntropyLoss work of KeypointLoss (models/loss_utils.py:23-95) and
  * CorrespondenceLoss (:108-139), driven per pair of scans by KeypointCorrLoss (models/loss.py:43-92).  The kernels return
@@ -391,6 +407,18 @@ int egonn_eca_gate(const float* mean, const float* conv_weight, int kernel_size,
 int egonn_eca_gate_backward(const float* grad_gate, const float* gate, const float* mean, const float* conv_weight,
                             int kernel_size, int batch_size, int channels, float* grad_mean, float* grad_weight,
                             void* stream);
+/* SELayer gate on the (B, channels) per-sample means (layers/senet_block.py:34-50, block :53-89, selected by
+ * `block = SEBasicBlock`, models/minkloc.py:30-31): gate = sigmoid(W2 relu(W1 mean_b + b1) + b2), the fc Sequential of two
+ * MinkowskiLinear layers (:39-43) with w1 (hidden,channels), w2 (channels,hidden) in nn.Linear layout.  channels a multiple
+ * of 16 in 16..256, hidden = channels/16 (reduction = 16); anything else is EGONN_STATUS_INVALID.  hidden_out (nullable):
+ * (B,hidden) post-ReLU activations, what the backward needs.  Backward: ReLU by hidden_act > 0; grad_mean (B,channels),
+ * grad_w1/b1/w2/b2 in the parameters' shapes, each a serial sum over the samples in order (bitwise reproducible, no atomics).
+ * One launch each, no host sync.  The block tail around it is egonn_global_avg_pool + egonn_gate_residual(relu = 1). */
+int egonn_se_gate(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, int batch_size,
+                  int channels, int hidden, float* gate, float* hidden_out, void* stream);
+int egonn_se_gate_backward(const float* grad_gate, const float* gate, const float* hidden_act, const float* mean,
+                           const float* w1, const float* w2, int batch_size, int channels, int hidden, float* grad_mean,
+                           float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, void* stream);
 /* out = relu?(x * gate[sample] + residual): MinkowskiBroadcastMultiplication + residual add + MinkowskiReLU
  * (layers/eca_block.py:69-73) with an explicit (B,c) gate (nullable = 1); backward: d = grad_out*[out>0],
  * grad_residual = d (nullable), grad_x = d*gate. */
