@@ -11,7 +11,9 @@ from .model import MinkGL, MinkHead, MinkTrunk, model_factory, create_egonn_mode
 from .minkloc import MinkFPN, MinkLoc, MinkLoc3D
 from .evaluator import DescriptorExtractor, GraphExtractor
 from .stream import StreamingExtractor
-from .local_loss import KeypointLoss, CorrespondenceLoss, KeypointCorrLoss, make_local_loss
+from .local_loss import (KeypointLoss, CorrespondenceLoss, KeypointCorrLoss, make_local_loss, BatchedKeypointCorrLoss,
+                         local_loss_packed)
+from .train import EgoNNTrainStep
 from .registration import (get_ransac_result, calculate_repeatability, register_pairs, evaluate_local, match_mutual,
                            RegistrationResult, voxel_downsample, icp_pairs, refine_pairs, icp)
 from .augment import (TrainTransform, TrainSetTransform, TrainBatcher, JitterPoints, RemoveRandomPoints, RandomTranslation,
@@ -21,6 +23,7 @@ from .scan_context import ScanContext, ScanContextManager, sc2rk, distance_sc, e
 __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "MinkHead", "MinkTrunk",
            "CartesianQuantizer", "PolarQuantizer", "Quantizer", "DescriptorExtractor", "GraphExtractor", "StreamingExtractor", "MinkFPN", "MinkLoc", "MinkLoc3D",
            "KeypointLoss", "CorrespondenceLoss", "KeypointCorrLoss", "make_local_loss",
+           "BatchedKeypointCorrLoss", "local_loss_packed", "EgoNNTrainStep",
            "get_ransac_result", "calculate_repeatability", "register_pairs", "evaluate_local", "match_mutual", "RegistrationResult",
            "voxel_downsample", "icp_pairs", "refine_pairs", "icp",
            "TrainTransform", "TrainSetTransform", "TrainBatcher", "JitterPoints", "RemoveRandomPoints", "RandomTranslation",

@@ -201,6 +201,26 @@ int matrix_min(const float* d, int64_t n, int64_t m, float* row_min, int32_t* ro
 int softmax_ce(const float* logits, int64_t n, int64_t m, const int32_t* target, float* loss, int32_t* argmax, float* dlogits,
                hipStream_t stream);
 
+// local_loss.hip ---------------------------------------------------------------------------------
+// the whole KeypointCorrLoss of a batch of pairs (loss, metrics, six input gradients) in one fixed launch sequence
+constexpr int LL_CLOUD_CHUNK = 1024;     // cloud points per workgroup of the keypoint -> cloud search
+constexpr int LL_STATS = 16;             // floats per row of out_pair / out_batch (= EGONN_LOCAL_LOSS_STATS)
+struct LocalLossArgs {
+  int pairs;
+  int64_t n_cloud1, n_cloud2, n_kp1, n_kp2;                       // totals over the batch (launch sizes)
+  const float *clouds1, *clouds2;                                 // (M,3)
+  const int32_t *cloud_off1, *cloud_off2, *kp_off1, *kp_off2;     // device (pairs+1)
+  const float *kp1, *sigma1, *desc1, *kp2, *sigma2, *desc2;       // (N,3) (N) (N,128)
+  const float* transforms;                                        // device (pairs,16)
+  const float* params;                                            // host: gamma_chamfer, gamma_p2p, gamma_c, gamma_k, beta, dist_th
+  float *out_pair, *out_batch;                                    // (pairs, LL_STATS), (LL_STATS)
+  float *g_kp1, *g_sigma1, *g_desc1, *g_kp2, *g_sigma2, *g_desc2; // all null: loss and metrics only
+  void* scratch;
+};
+bool local_loss_dim_supported(int dim);
+size_t local_loss_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2);
+int local_loss_forward(const LocalLossArgs& args, hipStream_t stream);
+
 // train.hip --------------------------------------------------------------------------------------
 // dW[k][ci][co] = sum_o in[nbr[o][k]][ci] * dout[o][co]; nbr == nullptr: identity map (K = 1, dense layer)
 // rg (nullable): the row-group form of the same map when it is built (the pair source of the MFMA kernel)

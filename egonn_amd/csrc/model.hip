@@ -1323,6 +1323,47 @@ API int egonn_softmax_cross_entropy(const float* logits, int64_t n, int64_t m, c
   EGONN_REQUIRE(logits && target && out_loss && out_argmax, EGONN_ERR_INVALID, "softmax_cross_entropy: null argument");
   return softmax_ce(logits, n, m, target, out_loss, out_argmax, out_dlogits, (hipStream_t)stream);
 }
+static_assert(EGONN_LOCAL_LOSS_STATS == LL_STATS, "header and kernels disagree on the stats row");
+API int64_t egonn_local_loss_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2, int dim) {
+  (void)dim;
+  return (int64_t)local_loss_scratch_bytes(pairs, n_kp1, n_kp2);
+}
+API int egonn_local_loss(int pairs, int64_t n_cloud1, int64_t n_cloud2, int64_t n_kp1, int64_t n_kp2, int dim,
+                         const float* clouds1, const int32_t* cloud_off1, const float* clouds2, const int32_t* cloud_off2,
+                         const float* kp1, const float* sigma1, const float* desc1, const int32_t* kp_off1,
+                         const float* kp2, const float* sigma2, const float* desc2, const int32_t* kp_off2,
+                         const float* transforms, const float* params, float* out_pair, float* out_batch,
+                         float* g_kp1, float* g_sigma1, float* g_desc1, float* g_kp2, float* g_sigma2, float* g_desc2,
+                         void* scratch, int64_t scratch_bytes, void* stream) {
+  // every check runs before anything touches the device
+  EGONN_REQUIRE(pairs >= 1 && pairs <= 4096, EGONN_ERR_INVALID, "local_loss: pairs=%d outside [1, 4096]", pairs);
+  EGONN_REQUIRE(local_loss_dim_supported(dim), EGONN_ERR_INVALID, "local_loss: descriptor width %d not supported (128)", dim);
+  const int64_t lim = (1ll << 31) / 128;       // row * 128 and cloud row * 3 stay inside int32 / the packed key
+  EGONN_REQUIRE(n_cloud1 >= 1 && n_cloud2 >= 1 && n_kp1 >= 1 && n_kp2 >= 1 && n_kp1 < lim && n_kp2 < lim &&
+                    n_cloud1 < (1ll << 31) / 3 && n_cloud2 < (1ll << 31) / 3 && n_kp1 + n_kp2 < (1ll << 31) - 256,
+                EGONN_ERR_INVALID, "local_loss: totals out of range (clouds %lld %lld, keypoints %lld %lld)",
+                (long long)n_cloud1, (long long)n_cloud2, (long long)n_kp1, (long long)n_kp2);
+  EGONN_REQUIRE(clouds1 && cloud_off1 && clouds2 && cloud_off2 && kp1 && sigma1 && desc1 && kp_off1 && kp2 && sigma2 && desc2 &&
+                    kp_off2 && transforms && params && out_pair && out_batch && scratch,
+                EGONN_ERR_INVALID, "local_loss: null argument");
+  const int ng = (g_kp1 != nullptr) + (g_sigma1 != nullptr) + (g_desc1 != nullptr) + (g_kp2 != nullptr) + (g_sigma2 != nullptr) +
+                 (g_desc2 != nullptr);
+  EGONN_REQUIRE(ng == 0 || ng == 6, EGONN_ERR_INVALID, "local_loss: the six gradient outputs are given together or not at all");
+  EGONN_REQUIRE((((uintptr_t)desc1 | (uintptr_t)desc2 | (uintptr_t)g_desc1 | (uintptr_t)g_desc2) & 15) == 0 &&
+                    ((uintptr_t)scratch & 255) == 0,
+                EGONN_ERR_INVALID, "local_loss: descriptors must be 16-byte aligned, scratch 256-byte aligned");
+  const int64_t need = (int64_t)local_loss_scratch_bytes(pairs, n_kp1, n_kp2);
+  EGONN_REQUIRE(scratch_bytes >= need, EGONN_ERR_INVALID, "local_loss: scratch of %lld bytes, %lld needed",
+                (long long)scratch_bytes, (long long)need);
+  LocalLossArgs a;
+  a.pairs = pairs; a.n_cloud1 = n_cloud1; a.n_cloud2 = n_cloud2; a.n_kp1 = n_kp1; a.n_kp2 = n_kp2;
+  a.clouds1 = clouds1; a.clouds2 = clouds2; a.cloud_off1 = cloud_off1; a.cloud_off2 = cloud_off2; a.kp_off1 = kp_off1;
+  a.kp_off2 = kp_off2; a.kp1 = kp1; a.sigma1 = sigma1; a.desc1 = desc1; a.kp2 = kp2; a.sigma2 = sigma2; a.desc2 = desc2;
+  a.transforms = transforms; a.params = params; a.out_pair = out_pair; a.out_batch = out_batch;
+  a.g_kp1 = g_kp1; a.g_sigma1 = g_sigma1; a.g_desc1 = g_desc1; a.g_kp2 = g_kp2; a.g_sigma2 = g_sigma2; a.g_desc2 = g_desc2;
+  a.scratch = scratch;
+  return local_loss_forward(a, (hipStream_t)stream);
+}
 
 // ------------------------------------------------------------------------------------------ training-mode operators
 #define REQUIRE_LEVEL(c, level)                                                                              \

@@ -15,6 +15,7 @@ Golden vectors: tests/golden/local_losses_*.npz, produced by importing the refer
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import Dict, List
 
@@ -266,8 +267,128 @@ class KeypointCorrLoss:
         return torch.stack(batch_loss).mean(), metrics_mean(batch_metrics)
 
 
-def make_local_loss(loss_gammas=None) -> KeypointCorrLoss:
+# ----------------------------------------------------------------------------- the whole batch in one library call
+# columns of the stats rows of egonn_local_loss (include/egonn_hip.h EGONN_LL_*): the metric keys of KeypointCorrLoss
+LOCAL_LOSS_STATS = 16
+STAT_KEYS = ('loss', 'kp_per_cloud', 'repeatability', 'chamfer_pure', 'chamfer_weighted', 'mean_sigma', 'loss_chamfer', 'loss_p2p',
+             'keypoint_loss', 'correspondence_loss', 'matching_keypoints', 'matching_descriptors', 'pos_similarity',
+             'neg_similarity')
+
+
+def _packed(t: torch.Tensor, cols: int, what: str) -> torch.Tensor:
+    t = _dev(t).detach()
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError(f"local_loss_packed: {what} must be float32 (n, {cols}), got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _offsets(t: torch.Tensor, pairs: int, what: str) -> torch.Tensor:
+    if not (t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.numel() == pairs + 1 and t.is_contiguous()):
+        raise ValueError(f"local_loss_packed: {what} must be a contiguous int32 device vector of pairs + 1 = {pairs + 1} offsets")
+    return t
+
+
+class _LocalLossPacked(torch.autograd.Function):
+    """egonn_local_loss: one call yields the batch loss, the stats and d loss / d input; backward only scales."""
+
+    @staticmethod
+    def forward(ctx, clouds1, cloud_off1, kp1, sigma1, desc1, kp_off1, clouds2, cloud_off2, kp2, sigma2, desc2, kp_off2,
+                transforms, gammas):
+        lib = _lib.load()
+        pairs = kp_off1.numel() - 1
+        c1, c2 = _packed(clouds1, 3, "clouds1"), _packed(clouds2, 3, "clouds2")
+        k1, k2 = _packed(kp1, 3, "kp1"), _packed(kp2, 3, "kp2")
+        s1, s2 = _packed(sigma1, 1, "sigma1"), _packed(sigma2, 1, "sigma2")
+        dim = desc1.shape[1]
+        d1, d2 = _packed(desc1, dim, "desc1"), _packed(desc2, dim, "desc2")
+        if not (s1.shape[0] == d1.shape[0] == k1.shape[0] and s2.shape[0] == d2.shape[0] == k2.shape[0]):
+            raise ValueError("local_loss_packed: keypoints, sigma and descriptors of a side must have the same rows")
+        offs = [_offsets(o, pairs, n) for o, n in ((cloud_off1, "cloud_off1"), (cloud_off2, "cloud_off2"), (kp_off1, "kp_off1"),
+                                                   (kp_off2, "kp_off2"))]
+        dev = k1.device
+        T = _dev(transforms).detach().to(dtype=torch.float32).reshape(-1).contiguous()
+        if T.numel() != 16 * pairs:
+            raise ValueError(f"local_loss_packed: transforms must be (pairs, 4, 4) = {pairs} matrices")
+        params = (C.c_float * 6)(*[float(g) for g in gammas])
+        f = dict(dtype=torch.float32, device=dev)
+        out_pair, out_batch = torch.empty((pairs, LOCAL_LOSS_STATS), **f), torch.empty(LOCAL_LOSS_STATS, **f)
+        grads = [torch.empty_like(t) for t in (k1, s1, d1, k2, s2, d2)]
+        nbytes = int(lib.egonn_local_loss_scratch_bytes(pairs, k1.shape[0], k2.shape[0], dim))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.egonn_local_loss(pairs, c1.shape[0], c2.shape[0], k1.shape[0], k2.shape[0], dim,
+                                            c1.data_ptr(), offs[0].data_ptr(), c2.data_ptr(), offs[1].data_ptr(),
+                                            k1.data_ptr(), s1.data_ptr(), d1.data_ptr(), offs[2].data_ptr(),
+                                            k2.data_ptr(), s2.data_ptr(), d2.data_ptr(), offs[3].data_ptr(),
+                                            T.data_ptr(), params, out_pair.data_ptr(), out_batch.data_ptr(),
+                                            *[g.data_ptr() for g in grads], scratch.data_ptr(), nbytes, _lib._stream()))
+        ctx.save_for_backward(*grads)
+        ctx.mark_non_differentiable(out_batch, out_pair)
+        return out_batch[0].clone(), out_batch, out_pair
+
+    @staticmethod
+    def backward(ctx, g, _gb, _gp):
+        gk1, gs1, gd1, gk2, gs2, gd2 = ctx.saved_tensors
+        return (None, None, gk1 * g, gs1 * g, gd1 * g, None, None, None, gk2 * g, gs2 * g, gd2 * g, None, None, None)
+
+
+def local_loss_packed(clouds1, cloud_off1, kp1, sigma1, desc1, kp_off1, clouds2, cloud_off2, kp2, sigma2, desc2, kp_off2,
+                      transforms, gammas, return_pair_stats: bool = False):
+    """KeypointCorrLoss of a whole batch of pairs in ONE library call (`egonn_local_loss`), without a host synchronisation.
+
+    clouds (M,3), kp (N,3), sigma (N,1), desc (N,128): the rows of all pairs, packed; *_off: int32 DEVICE vectors of pairs + 1
+    row offsets; transforms (pairs,4,4) on the device; gammas = (gamma_chamfer, gamma_p2p, gamma_c, gamma_k, beta, dist_th).
+    Returns (loss, stats): the 0-dim batch loss (differentiable w.r.t. kp, sigma and desc of both sides) and the
+    (LOCAL_LOSS_STATS,) vector of batch means, columns STAT_KEYS.  return_pair_stats: also the (pairs, LOCAL_LOSS_STATS) rows."""
+    loss, stats, pair_stats = _LocalLossPacked.apply(clouds1, cloud_off1, kp1, sigma1, desc1, kp_off1, clouds2, cloud_off2, kp2,
+                                                     sigma2, desc2, kp_off2, transforms, tuple(gammas))
+    return (loss, stats, pair_stats) if return_pair_stats else (loss, stats)
+
+
+class BatchedKeypointCorrLoss:
+    """`KeypointCorrLoss` with the same constructor and call, evaluated by `local_loss_packed`: the lists are packed (one
+    concatenation per kind), one library call computes the batch.  Every metric is a 0-dim DEVICE tensor viewing one stats
+    vector (the reference's `tensors_to_numbers`, training/trainer.py:46-48, turns them into numbers), so the call never
+    synchronises.  The offset vectors are built from the list lengths and kept per length signature."""
+
+    def __init__(self, gamma_c=1., gamma_k=1., gamma_chamfer=1., gamma_p2p=1., beta=1., dist_th=0.5):
+        self.gammas = (gamma_chamfer, gamma_p2p, gamma_c, gamma_k, beta, dist_th)
+        self._off = {}
+
+    def _offsets(self, lens, device) -> torch.Tensor:
+        key = (tuple(int(n) for n in lens), str(device))
+        off = self._off.get(key)
+        if off is None:
+            if len(self._off) > 64:
+                self._off.clear()
+            off = torch.tensor(np.concatenate([[0], np.cumsum(key[0])]), dtype=torch.int32, device=device)
+            self._off[key] = off
+        return off
+
+    def __call__(self, clouds1, keypoints1, sigma1, descriptors1, clouds2, keypoints2, sigma2, descriptors2, M_gt, len_batch):
+        assert clouds1.dim() == 2 and clouds2.dim() == 2
+        pairs = len(keypoints1)
+        assert pairs == len(sigma1) == len(descriptors1) == len(keypoints2) == len(sigma2) == len(descriptors2) == len(len_batch)
+        assert pairs >= 1 and all(len(k) > 0 for k in keypoints1) and all(len(k) > 0 for k in keypoints2)
+        assert sum(e[0] for e in len_batch) == len(clouds1) and sum(e[1] for e in len_batch) == len(clouds2)
+        assert all(e[0] > 0 and e[1] > 0 for e in len_batch)
+        dev = _dev(keypoints1[0]).device
+        if torch.is_tensor(M_gt):
+            T = M_gt
+        else:
+            T = torch.stack([torch.as_tensor(m) for m in M_gt])
+        T = T.to(device=dev, dtype=torch.float32)
+        loss, stats = local_loss_packed(
+            clouds1.to(dev), self._offsets([e[0] for e in len_batch], dev), torch.cat(list(keypoints1)), torch.cat(list(sigma1)),
+            torch.cat(list(descriptors1)), self._offsets([len(k) for k in keypoints1], dev),
+            clouds2.to(dev), self._offsets([e[1] for e in len_batch], dev), torch.cat(list(keypoints2)), torch.cat(list(sigma2)),
+            torch.cat(list(descriptors2)), self._offsets([len(k) for k in keypoints2], dev), T, self.gammas)
+        return loss, {k: stats[i] for i, k in enumerate(STAT_KEYS)}
+
+
+def make_local_loss(loss_gammas=None, batched: bool = False):
     """the `loc_loss_fn` of reference models/loss.py:12-29 (`make_losses`): loss_gammas = [gamma_chamfer, gamma_p2p, gamma_c,
-    beta], default [1, 1, 1, 2]."""
+    beta], default [1, 1, 1, 2].  batched: the one-call `BatchedKeypointCorrLoss` instead of the per-pair `KeypointCorrLoss`."""
     gamma_chamfer, gamma_p2p, gamma_c, beta = loss_gammas if loss_gammas is not None else [1., 1., 1., 2.]
-    return KeypointCorrLoss(gamma_c=gamma_c, gamma_chamfer=gamma_chamfer, gamma_p2p=gamma_p2p, beta=beta)
+    cls = BatchedKeypointCorrLoss if batched else KeypointCorrLoss
+    return cls(gamma_c=gamma_c, gamma_chamfer=gamma_chamfer, gamma_p2p=gamma_p2p, beta=beta)

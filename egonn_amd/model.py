@@ -315,9 +315,12 @@ class MinkGL(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, batch: Dict[str, torch.Tensor], disable_global_head: bool = False,
-                disable_local_head: bool = False):
+                disable_local_head: bool = False, context_slot: int = 0):
+        """context_slot: the egonn_ctx the plan of this batch lives in.  A train-mode graph back-propagates through the plan of
+        its context, so two forwards whose backward comes later (the anchor and the positive batch of the local phase,
+        training/trainer.py:183-192) need a slot each."""
         dev = self._device()
-        ctx = self.context()
+        ctx = self.context(context_slot)
         coords, feats = batch['coords'], batch['features']
         coords = coords.to(device=dev, dtype=torch.int32).contiguous()
         feats = feats.to(device=dev, dtype=torch.float32).contiguous()

@@ -662,3 +662,48 @@ class TrainStep:
         if step_optimizer:
             self.optimizer.step()
         return loss.detach(), stats
+
+
+class EgoNNTrainStep:
+    """One full optimisation step of the reference (training/trainer.py:160-193), both phases:
+
+        zero the gradients
+        -> the global phase exactly as `TrainStep` runs it (forward, batch-hard loss, backward; no optimizer step)
+        -> forward of the anchor batch and of the positive batch in train mode (:183-184)
+        -> the local loss of the (anchor, positive) pairs in one library call (`BatchedKeypointCorrLoss`, :186-189)
+        -> backward, accumulating onto the gradients of the global phase (:192)
+        -> ONE optimizer step (:193)
+
+    Single process only: sharding the pairs over ranks is not implemented."""
+
+    def __init__(self, model, optimizer, margin: float = 0.2, loss_fn=None, local_loss_fn=None):
+        """loss_fn: the global loss as in `TrainStep`; local_loss_fn: a local loss with the call of `KeypointCorrLoss`
+        (None = `make_local_loss(batched=True)`)."""
+        from .local_loss import make_local_loss
+        self.model, self.optimizer = model, optimizer
+        self.global_step = TrainStep(model, optimizer, margin, loss_fn)
+        self.local_loss_fn = make_local_loss(batched=True) if local_loss_fn is None else local_loss_fn
+
+    def __call__(self, batch: Dict[str, torch.Tensor], positives_mask: torch.Tensor, negatives_mask: torch.Tensor,
+                 local_batch: Dict):
+        """local_batch: the dict of the reference's make_collate_fn_6DOF (datasets/dataset_utils.py:98-151): anc_batch,
+        pos_batch, anc_pcd, pos_pcd, T_gt, len_batch.  Returns (global_loss, local_loss, stats): device tensors; stats holds
+        the global loss's stats and the local metrics (the local ones win a name clash, e.g. 'loss')."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("EgoNNTrainStep runs in a single process: the local phase is not sharded over ranks")
+        model = self.model
+        global_loss, stats = self.global_step(batch, positives_mask, negatives_mask, step_optimizer=False)   # zeroes the gradients
+        dev = global_loss.device
+        # two graphs are alive until the backward: each forward gets a context (plan + kernel maps) of its own.  The global
+        # head runs too, as in the reference (its output is unused, its gradient zero).
+        y1 = model(local_batch['anc_batch'], context_slot=1)
+        y2 = model(local_batch['pos_batch'], context_slot=2)
+        local_loss, local_stats = self.local_loss_fn(local_batch['anc_pcd'].to(dev), y1['keypoints'], y1['sigma'], y1['descriptors'],
+                                                     local_batch['pos_pcd'].to(dev), y2['keypoints'], y2['sigma'], y2['descriptors'],
+                                                     local_batch['T_gt'], local_batch['len_batch'])
+        local_loss.backward()
+        self.optimizer.step()
+        out = dict(stats)
+        out.update(local_stats)
+        return global_loss, local_loss.detach(), out

@@ -348,6 +348,37 @@ int egonn_matrix_min(const float* d, int64_t n, int64_t m, float* row_min, int32
 int egonn_softmax_cross_entropy(const float* logits, int64_t n, int64_t m, const int32_t* target, float* out_loss,
                                 int32_t* out_argmax, float* out_dlogits, void* stream);
 
+/* The whole KeypointCorrLoss (models/loss.py:32-92) of a batch of (anchor, positive) pairs in ONE call: the second half of the
+ * training step (training/trainer.py:186-190).  Loss, every metric and d out_batch[0] / d input for the six keypoint, sigma and
+ * descriptor arrays, with the arithmetic of the per-pair driver (egonn_amd/local_loss.py): searches on exact differences (ties:
+ * lowest index), probabilistic chamfer + point-to-point terms (a zero distance has a zero gradient), row-wise softmax
+ * cross-entropy over exp(beta) * desc1 . desc2^T on the rows whose nearest kp2 lies within dist_th, in exact fp32 FMAs.  No
+ * (n1 x n2) matrix is stored: the logits are evaluated tile by tile in LDS.  No host sync, no float atomics: two calls agree
+ * bitwise, and a pair's row of out_pair does not depend on its position in the batch.
+ * Argument order differs from a plain list of arrays in one way: the totals come first, BY VALUE (they size the launches).
+ *   pairs >= 1; n_cloud1/2, n_kp1/2 >= 1: rows of the packed arrays; dim: descriptor width, 128 only.
+ *   clouds (M,3), kp (N,3), sigma (N), desc (N,dim; 16-byte aligned), *_off (pairs+1) int32 DEVICE offsets of every pair's rows
+ *   (every pair needs at least one keypoint on both sides and one point in both clouds), transforms (pairs,16) DEVICE row-major
+ *   4x4 taking scan 1 into scan 2's frame, params HOST 6 floats: gamma_chamfer, gamma_p2p, gamma_c, gamma_k, beta, dist_th.
+ *   out_pair (pairs, EGONN_LOCAL_LOSS_STATS), out_batch (EGONN_LOCAL_LOSS_STATS) = mean over the pairs; columns
+ *   EGONN_LL_*.  A pair without a keypoint within dist_th has a NaN correspondence_loss and loss (CrossEntropyLoss over no
+ *   rows), so the batch loss is NaN, and NaN descriptor gradients — and nothing else of it is NaN.
+ *   g_*: same shapes as the inputs, all six or none (NULL = loss and metrics only).
+ *   scratch: egonn_local_loss_scratch_bytes(pairs, n_kp1, n_kp2, dim) DEVICE bytes, 256-byte aligned. */
+#define EGONN_LOCAL_LOSS_STATS 16
+enum { EGONN_LL_LOSS = 0, EGONN_LL_KP_PER_CLOUD = 1, EGONN_LL_REPEATABILITY = 2, EGONN_LL_CHAMFER_PURE = 3,
+       EGONN_LL_CHAMFER_WEIGHTED = 4, EGONN_LL_MEAN_SIGMA = 5, EGONN_LL_LOSS_CHAMFER = 6, EGONN_LL_LOSS_P2P = 7,
+       EGONN_LL_KEYPOINT_LOSS = 8, EGONN_LL_CORRESPONDENCE_LOSS = 9, EGONN_LL_MATCHING_KEYPOINTS = 10,
+       EGONN_LL_MATCHING_DESCRIPTORS = 11, EGONN_LL_POS_SIMILARITY = 12, EGONN_LL_NEG_SIMILARITY = 13 /* 14, 15: zero */ };
+int64_t egonn_local_loss_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2, int dim);
+int egonn_local_loss(int pairs, int64_t n_cloud1, int64_t n_cloud2, int64_t n_kp1, int64_t n_kp2, int dim,
+                     const float* clouds1, const int32_t* cloud_off1, const float* clouds2, const int32_t* cloud_off2,
+                     const float* kp1, const float* sigma1, const float* desc1, const int32_t* kp_off1,
+                     const float* kp2, const float* sigma2, const float* desc2, const int32_t* kp_off2,
+                     const float* transforms, const float* params, float* out_pair, float* out_batch,
+                     float* g_kp1, float* g_sigma1, float* g_desc1, float* g_kp2, float* g_sigma2, float* g_desc2,
+                     void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ training-mode operators (configs[3])
  * The reference trains through MinkowskiEngine's autograd (training/trainer.py:160-175: model.train(); y = model(batch);
  * loss.backward()).  Backward of a sparse convolution w.r.t. its input is again a sparse convolution on the cached
