@@ -193,6 +193,19 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def call(device: torch.device, fn, *args):
+    """The one way into the library for every entry point that ends in a stream: `fn(*args, stream)` on `device`'s current
+    stream, raising on a non-zero status.  The device is switched only when it is not the current one already."""
+    idx = device.index
+    if idx is None or torch.cuda.current_device() == idx:       # common case: no device switch needed
+        rc = fn(*args, _stream())
+    else:
+        with torch.cuda.device(device):
+            rc = fn(*args, _stream())
+    if rc != 0:
+        check(rc)
+
+
 def _dev_f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
@@ -235,8 +248,7 @@ class Context:
         B = len(scan_offsets) - 1
         off = (C.c_int64 * (B + 1))(*[int(o) for o in scan_offsets])
         st = (C.c_float * 3)(*([float(s) for s in step] + [0.0, 0.0])[:3])
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_voxelize(self.h, points.data_ptr(), off, B, mode, st, _stream()))
+        self._call(self.lib.egonn_voxelize, self.h, points.data_ptr(), off, B, mode, st)
         self.batch_size = B
 
     def reserve(self, max_points: int, batch_size: int, level_capacity: Optional[Sequence[int]] = None):
@@ -255,15 +267,13 @@ class Context:
         assert points.is_cuda and points.dtype == torch.float32 and points.is_contiguous() and points.shape[1] == 3
         assert scan_offsets.is_cuda and scan_offsets.dtype == torch.int64 and scan_offsets.numel() == batch_size + 1
         st = (C.c_float * 3)(*([float(s) for s in step] + [0.0, 0.0])[:3])
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_voxelize_device(self.h, points.data_ptr(), points.shape[0], scan_offsets.data_ptr(),
-                                                 int(batch_size), mode, st, _stream()))
+        self._call(self.lib.egonn_voxelize_device, self.h, points.data_ptr(), points.shape[0], scan_offsets.data_ptr(),
+                   int(batch_size), mode, st)
         self.batch_size = int(batch_size)
 
     def plan_status(self):
         """[SYNC] raises if the latest (replayed) plan left the coordinate range or the reserved capacities."""
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_plan_status(self.h, _stream()))
+        self._call(self.lib.egonn_plan_status, self.h)
 
     def level_capacity(self, level: int) -> int:
         n = C.c_int64()
@@ -273,8 +283,7 @@ class Context:
     def coords_set(self, coords: torch.Tensor, batch_size: int):
         assert coords.is_cuda and coords.dtype == torch.int32 and coords.is_contiguous()
         assert coords.dim() == 2 and coords.shape[1] == 4
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_coords_set(self.h, coords.data_ptr(), coords.shape[0], int(batch_size), _stream()))
+        self._call(self.lib.egonn_coords_set, self.h, coords.data_ptr(), coords.shape[0], int(batch_size))
         self.batch_size = int(batch_size)
 
     def level_count(self, level: int) -> int:
@@ -289,14 +298,12 @@ class Context:
 
     def level_coords(self, level: int) -> torch.Tensor:
         out = torch.empty((self.level_count(level), 4), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_level_coords(self.h, level, out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_level_coords, self.h, level, out.data_ptr())
         return out
 
     def input_index(self) -> torch.Tensor:
         out = torch.empty((self.level_count(0),), dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_input_index(self.h, out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_input_index, self.h, out.data_ptr())
         return out
 
     # ------------------------------------------------------------------ operators
@@ -312,9 +319,8 @@ class Context:
         out = torch.empty((self.level_count(level_out), cout), dtype=torch.float32, device=self.device)
         sc = None if scale is None else _dev_f32(scale, self.device)
         sh = None if shift is None else _dev_f32(shift, self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_conv(self.h, level_in, level_out, kernel_size, _ptr(x), cin, kernel.data_ptr(),
-                                      cout, _ptr(sc), _ptr(sh), int(relu), out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_conv, self.h, level_in, level_out, kernel_size, _ptr(x), cin, kernel.data_ptr(), cout,
+                   _ptr(sc), _ptr(sh), int(relu), out.data_ptr())
         return out
 
     def conv_transpose(self, level_in: int, x: torch.Tensor, kernel: torch.Tensor):
@@ -323,9 +329,7 @@ class Context:
         cin, cout = kernel.shape[-2], kernel.shape[-1]
         assert x.shape == (self.level_count(level_in), cin)
         out = torch.empty((self.level_count(level_in - 1), cout), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_conv_transpose(self.h, level_in, x.data_ptr(), cin, kernel.data_ptr(), cout,
-                                                out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_conv_transpose, self.h, level_in, x.data_ptr(), cin, kernel.data_ptr(), cout, out.data_ptr())
         return out
 
     def sparse_conv(self, map_kind: int, level_out: int, x: torch.Tensor, kernel: torch.Tensor, scale=None, shift=None,
@@ -342,22 +346,18 @@ class Context:
         sums = None
         if group_sums:
             sums = torch.zeros((self.map_groups(map_kind, level_out)[0], cout), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_sparse_conv(self.h, map_kind, level_out, x.data_ptr(), cin, kernel.data_ptr(), cout,
-                                             int(x.dtype == torch.bfloat16), _ptr(sc), _ptr(sh), int(relu), out.data_ptr(),
-                                             _ptr(sums), _stream()))
+        self._call(self.lib.egonn_sparse_conv, self.h, map_kind, level_out, x.data_ptr(), cin, kernel.data_ptr(), cout,
+                   int(x.dtype == torch.bfloat16), _ptr(sc), _ptr(sh), int(relu), out.data_ptr(), _ptr(sums))
         return (out, sums) if group_sums else out
 
     def prepare_maps(self, with_level0_transpose: bool = False):
         """row-group tables of every kernel map of the plan in ONE launch (training steps, operator sequences)"""
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_prepare_maps(self.h, int(with_level0_transpose), _stream()))
+        self._call(self.lib.egonn_prepare_maps, self.h, int(with_level0_transpose))
 
     def map_groups(self, map_kind: int, level_out: int):
         n = C.c_int64()
         first = (C.c_int64 * (self.batch_size + 1))()
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_map_groups(self.h, map_kind, level_out, C.byref(n), first, _stream()))
+        self._call(self.lib.egonn_map_groups, self.h, map_kind, level_out, C.byref(n), first)
         return n.value, list(first)
 
     def rowgroup_tables(self, map_kind: int, level_out: int, with_rows: bool = True):
@@ -367,9 +367,8 @@ class Context:
         gm = torch.empty(ng, dtype=torch.int32, device=self.device)
         sn = torch.empty((ng, K, 16), dtype=torch.int32, device=self.device) if with_rows else None
         n = C.c_int64()
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_debug_rowgroup_tables(self.h, map_kind, level_out, gm.data_ptr(), sn.data_ptr() if with_rows else None,
-                                                       ng, C.byref(n), _stream()))
+        self._call(self.lib.egonn_debug_rowgroup_tables, self.h, map_kind, level_out, gm.data_ptr(),
+                   sn.data_ptr() if with_rows else None, ng, C.byref(n))
         return gm, sn
 
     def rowgroup_perm(self, map_kind: int, level_out: int):
@@ -377,8 +376,7 @@ class Context:
         ng, _ = self.map_groups(map_kind, level_out)
         pm = torch.empty((ng, 16), dtype=torch.int32, device=self.device)
         n = C.c_int64()
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_debug_rowgroup_perm(self.h, map_kind, level_out, pm.data_ptr(), ng, C.byref(n), _stream()))
+        self._call(self.lib.egonn_debug_rowgroup_perm, self.h, map_kind, level_out, pm.data_ptr(), ng, C.byref(n))
         return pm
 
     def set_naive_conv(self, on: bool):
@@ -406,8 +404,7 @@ class Context:
     def global_avg_pool(self, level: int, x: torch.Tensor):
         x = _dev_f32(x, self.device)
         out = torch.empty((self.batch_size, x.shape[1]), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_global_avg_pool(self.h, level, x.data_ptr(), x.shape[1], out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_global_avg_pool, self.h, level, x.data_ptr(), x.shape[1], out.data_ptr())
         return out
 
     def bn_fold(self, bn: torch.nn.BatchNorm1d):
@@ -416,9 +413,8 @@ class Context:
         w, b, rm, rv = (_dev_f32(t.detach(), self.device) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
         scale = torch.empty(c, dtype=torch.float32, device=self.device)
         shift = torch.empty(c, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_bn_fold(w.data_ptr(), b.data_ptr(), rm.data_ptr(), rv.data_ptr(), float(bn.eps), c,
-                                         scale.data_ptr(), shift.data_ptr(), _stream()))
+        self._call(self.lib.egonn_bn_fold, w.data_ptr(), b.data_ptr(), rm.data_ptr(), rv.data_ptr(), float(bn.eps), c,
+                   scale.data_ptr(), shift.data_ptr())
         return scale, shift
 
     def block_tail(self, level: int, x: torch.Tensor, residual: torch.Tensor, eca_weight: Optional[torch.Tensor] = None):
@@ -426,17 +422,15 @@ class Context:
         assert x.shape == residual.shape == (self.level_count(level), x.shape[1])
         out = torch.empty_like(x)
         ew = None if eca_weight is None else _dev_f32(eca_weight.detach().reshape(-1), self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_block_tail(self.h, level, x.data_ptr(), residual.data_ptr(), x.shape[1], _ptr(ew),
-                                            0 if ew is None else ew.numel(), out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_block_tail, self.h, level, x.data_ptr(), residual.data_ptr(), x.shape[1], _ptr(ew),
+                   0 if ew is None else ew.numel(), out.data_ptr())
         return out
 
-    def se_gate(self, mean: torch.Tensor, fc, want_hidden: bool = False):
+    def se_gate(self, mean: torch.Tensor, w1, b1, w2, b2, want_hidden: bool = False):
         """SELayer.fc on the (B, C) per-sample means: sigmoid(W2 relu(W1 mean + b1) + b2) -> gate (B, C) [, hidden (B, C/16)].
-        `fc`: the SELayer's Sequential (fc[0].linear, fc[2].linear)."""
+        w1 (C/16, C), b1, w2 (C, C/16), b2: the weights and biases of fc[0].linear and fc[2].linear."""
         mean = _dev_f32(mean, self.device)
-        w1, b1, w2, b2 = (_dev_f32(t.detach(), self.device) for t in (fc[0].linear.weight, fc[0].linear.bias,
-                                                                       fc[2].linear.weight, fc[2].linear.bias))
+        w1, b1, w2, b2 = (_dev_f32(t.detach(), self.device) for t in (w1, b1, w2, b2))
         B, c = mean.shape
         h = w1.shape[0]
         assert w1.shape == (h, c) and w2.shape == (c, h) and b1.shape == (h,) and b2.shape == (c,)
@@ -450,30 +444,26 @@ class Context:
         a, b = _dev_f32(a, self.device), _dev_f32(b, self.device)
         assert a.shape == b.shape
         out = torch.empty_like(a)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_add(a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_add, a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr())
         return out
 
     def gather_input(self, feats: torch.Tensor):
         feats = _dev_f32(feats, self.device)
         out = torch.empty((self.level_count(0), feats.shape[1]), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_gather_input(self.h, feats.data_ptr(), feats.shape[1], out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_gather_input, self.h, feats.data_ptr(), feats.shape[1], out.data_ptr())
         return out
 
     def gem(self, level: int, x: torch.Tensor, p: torch.Tensor):
         x = _dev_f32(x, self.device)
         pp = _dev_f32(p.detach().reshape(-1), self.device)
         out = torch.empty((self.batch_size, x.shape[1]), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_gem(self.h, level, x.data_ptr(), x.shape[1], pp.data_ptr(), out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_gem, self.h, level, x.data_ptr(), x.shape[1], pp.data_ptr(), out.data_ptr())
         return out
 
     def global_max_pool(self, level: int, x: torch.Tensor):
         x = _dev_f32(x, self.device)
         out = torch.empty((self.batch_size, x.shape[1]), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_global_max_pool(self.h, level, x.data_ptr(), x.shape[1], out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_global_max_pool, self.h, level, x.data_ptr(), x.shape[1], out.data_ptr())
         return out
 
     def netvlad(self, level: int, x: torch.Tensor, cluster_weights: torch.Tensor, cluster_weights2: torch.Tensor,
@@ -493,10 +483,9 @@ class Context:
             gw = _dev_f32(gating_weights.detach(), self.device)
             scg, shg = self.bn_fold(gate_bn)
         out = torch.empty((self.batch_size, d), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_netvlad(self.h, level, x.data_ptr(), x.shape[1], w[0].data_ptr(), w[1].data_ptr(),
-                                         sc1.data_ptr(), sh1.data_ptr(), w[2].data_ptr(), sc2.data_ptr(), sh2.data_ptr(),
-                                         _ptr(gw), _ptr(scg), _ptr(shg), d, int(gating), out.data_ptr(), _stream()))
+        self._call(self.lib.egonn_netvlad, self.h, level, x.data_ptr(), x.shape[1], w[0].data_ptr(), w[1].data_ptr(),
+                   sc1.data_ptr(), sh1.data_ptr(), w[2].data_ptr(), sc2.data_ptr(), sh2.data_ptr(), _ptr(gw), _ptr(scg),
+                   _ptr(shg), d, int(gating), out.data_ptr())
         return out
 
     # ------------------------------------------------------------------ training-mode operators (egonn_amd/train.py)
@@ -509,14 +498,7 @@ class Context:
         return buf
 
     def _call(self, fn, *args):
-        idx = self.device.index
-        if idx is None or torch.cuda.current_device() == idx:       # common case: no device switch needed
-            rc = fn(*args, torch.cuda.current_stream().cuda_stream)
-        else:
-            with torch.cuda.device(self.device):
-                rc = fn(*args, torch.cuda.current_stream().cuda_stream)
-        if rc != 0:
-            check(rc)
+        call(self.device, fn, *args)
 
     def dense(self, x, weight, out_in: bool, bias=None, act: int = 0):
         x, weight = _dev_f32(x, self.device), _dev_f32(weight, self.device)
@@ -693,10 +675,56 @@ class Context:
                    dx.data_ptr())
         return dx
 
+    # the operators below take their tensors as the train graph holds them (fp32, contiguous, on the device): raw pointers
+    def eca_gate(self, mean, w):
+        """sigmoid(Conv1d_k(mean)) over the channel axis of the (B, C) per-sample means; w (k,)"""
+        B, c = mean.shape
+        gate = torch.empty_like(mean)
+        self._call(self.lib.egonn_eca_gate, mean.data_ptr(), w.data_ptr(), w.numel(), B, c, gate.data_ptr())
+        return gate
+
+    def eca_gate_backward(self, grad_out, gate, mean, w):
+        """(grad mean, grad w (k,))"""
+        B, c = mean.shape
+        dmean = torch.empty_like(mean)
+        dw = torch.empty(w.numel(), dtype=torch.float32, device=mean.device)
+        self._call(self.lib.egonn_eca_gate_backward, grad_out.data_ptr(), gate.data_ptr(), mean.data_ptr(), w.data_ptr(),
+                   w.numel(), B, c, dmean.data_ptr(), dw.data_ptr())
+        return dmean, dw
+
+    def se_gate_backward(self, grad_out, gate, hid, mean, w1, w2):
+        """(grad mean, grad w1, grad b1, grad w2, grad b2) of se_gate"""
+        B, c = mean.shape
+        h = w1.shape[0]
+        dmean, dw1, dw2 = torch.empty_like(mean), torch.empty_like(w1), torch.empty_like(w2)
+        db1 = torch.empty(h, dtype=torch.float32, device=mean.device)
+        db2 = torch.empty(c, dtype=torch.float32, device=mean.device)
+        self._call(self.lib.egonn_se_gate_backward, grad_out.data_ptr(), gate.data_ptr(), hid.data_ptr(), mean.data_ptr(),
+                   w1.data_ptr(), w2.data_ptr(), B, c, h, dmean.data_ptr(), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(),
+                   db2.data_ptr())
+        return dmean, dw1, db1, dw2, db2
+
+    def bn_train_finalize(self, sums, shift, total: float, weight, bias, eps: float, momentum: float, running_mean=None,
+                          running_var=None):
+        """(2, C) fp64 shifted sums of col_stats(3) -> (4, C): mean, invstd, folded scale, folded shift; updates the running
+        statistics in place when given."""
+        c = weight.numel()
+        out4 = torch.empty((4, c), dtype=torch.float32, device=sums.device)
+        self._call(self.lib.egonn_bn_train_finalize, sums.data_ptr(), shift.data_ptr(), total, c, weight.data_ptr(),
+                   bias.data_ptr(), float(eps), float(momentum), _ptr(running_mean), _ptr(running_var), out4.data_ptr())
+        return out4
+
+    def bn_backward_finalize(self, sums, sums_all, total: float, weight, mean, invstd):
+        """this rank's and the whole batch's (2, C) fp64 sums of col_stats(2) -> (5, C): A, B, C of affine3, dgamma, dbeta"""
+        c = weight.numel()
+        out5 = torch.empty((5, c), dtype=torch.float32, device=sums.device)
+        self._call(self.lib.egonn_bn_backward_finalize, sums.data_ptr(), sums_all.data_ptr(), total, c, weight.data_ptr(),
+                   mean.data_ptr(), invstd.data_ptr(), out5.data_ptr())
+        return out5
+
     def forward_level_features(self, level: int, channels: int) -> torch.Tensor:
         out = torch.empty((self.level_count(level), channels), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_forward_level_features(self.h, level, out.data_ptr(), channels, _stream()))
+        self._call(self.lib.egonn_forward_level_features, self.h, level, out.data_ptr(), channels)
         return out
 
     def select_keypoints(self, sigma: torch.Tensor, keypoints: torch.Tensor, descriptors: torch.Tensor, n_k: int):
@@ -706,12 +734,9 @@ class Context:
         sel_desc = torch.empty((B, n_k, descriptors.shape[1]), dtype=torch.float32, device=dev)
         sel_rows = torch.empty((B, n_k), dtype=torch.int32, device=dev)
         sel_count = torch.empty((B,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            check(self.lib.egonn_select_keypoints(self.h, sigma.data_ptr(), keypoints.data_ptr(),
-                                                  descriptors.data_ptr(), n_k, sel_kp.data_ptr(), sel_desc.data_ptr(),
-                                                  sel_rows.data_ptr(), sel_count.data_ptr(), _stream()))
+        self._call(self.lib.egonn_select_keypoints, self.h, sigma.data_ptr(), keypoints.data_ptr(), descriptors.data_ptr(), n_k,
+                   sel_kp.data_ptr(), sel_desc.data_ptr(), sel_rows.data_ptr(), sel_count.data_ptr())
         return sel_kp, sel_desc, sel_rows, sel_count
-
 
     # ------------------------------------------------------------------ launch timing
     def profile_enable(self, mode: int, filt: str = ""):
@@ -723,8 +748,7 @@ class Context:
         ms = (C.c_float * cap)()
         by = (C.c_double * cap)()
         fl = (C.c_double * cap)()
-        with torch.cuda.device(self.device):
-            check(self.lib.egonn_profile_fetch(self.h, cap, C.byref(n), names, ms, by, fl, _stream()))
+        self._call(self.lib.egonn_profile_fetch, self.h, cap, C.byref(n), names, ms, by, fl)
         out = []
         for i in range(n.value):
             nm = names.raw[i * 64:(i + 1) * 64].split(b"\0", 1)[0].decode()

@@ -127,10 +127,9 @@ def augment_points(points: torch.Tensor, offsets: torch.Tensor, scan_ids: Option
     ri = torch.zeros((B, REC_I), dtype=torch.int32, device=dev) if record else None
     rd = torch.zeros((B, REC_D), dtype=torch.float64, device=dev) if record else None
     fl = torch.zeros((N,), dtype=torch.uint8, device=dev) if flags else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_augment_points(points.data_ptr(), N, offsets.data_ptr(), B, _lib._ptr(scan_ids), C.byref(cp),
-                                            _lib._ptr(T_in) if T_out is not None else None, out.data_ptr(), _lib._ptr(T_out),
-                                            _lib._ptr(ri), _lib._ptr(rd), _lib._ptr(fl), sp, need, _lib._stream()))
+    _lib.call(dev, lib.egonn_augment_points, points.data_ptr(), N, offsets.data_ptr(), B, _lib._ptr(scan_ids), C.byref(cp),
+              _lib._ptr(T_in) if T_out is not None else None, out.data_ptr(), _lib._ptr(T_out), _lib._ptr(ri), _lib._ptr(rd),
+              _lib._ptr(fl), sp, need)
     return AugmentResult(out, T_out, ri, rd, fl)
 
 

@@ -48,9 +48,7 @@ class DescriptorExtractor:
         rows = torch.empty((1, n_k), dtype=torch.int32, device=dev)
         cnt = torch.empty((1,), dtype=torch.int32, device=dev)
         boff = torch.tensor([0, n], dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(ctx.lib.egonn_topk_rows(sg.data_ptr(), boff.data_ptr(), 1, n_k, rows.data_ptr(), cnt.data_ptr(),
-                                               _lib._stream()))
+        _lib.call(dev, ctx.lib.egonn_topk_rows, sg.data_ptr(), boff.data_ptr(), 1, n_k, rows.data_ptr(), cnt.data_ptr())
         return rows[0, :int(cnt[0].item())].long().cpu()
 
     # ------------------------------------------------------------------ batched device pipeline
@@ -199,11 +197,9 @@ class GraphExtractor:
             }
         o = self.out
         model._forward_on_plan(ctx, None, outputs=(o['global'], o['all_descriptors'], o['all_keypoints'], o['all_sigma']))
-        with torch.cuda.device(ctx.device):
-            _lib.check(ctx.lib.egonn_select_keypoints(ctx.h, o['all_sigma'].data_ptr(), o['all_keypoints'].data_ptr(),
-                                                      o['all_descriptors'].data_ptr(), self.ex.n_k,
-                                                      o['keypoints'].data_ptr(), o['descriptors'].data_ptr(),
-                                                      o['rows'].data_ptr(), o['count'].data_ptr(), _lib._stream()))
+        _lib.call(ctx.device, ctx.lib.egonn_select_keypoints, ctx.h, o['all_sigma'].data_ptr(), o['all_keypoints'].data_ptr(),
+                  o['all_descriptors'].data_ptr(), self.ex.n_k, o['keypoints'].data_ptr(), o['descriptors'].data_ptr(),
+                  o['rows'].data_ptr(), o['count'].data_ptr())
 
     def _load(self, points: torch.Tensor, offsets):
         n = int(offsets[-1])

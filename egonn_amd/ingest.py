@@ -58,11 +58,9 @@ class ScanIngest:
         out = torch.empty((max(n, 1), 3), dtype=torch.float32, device=dev)
         new_off = torch.empty(B + 1, dtype=torch.int64, device=dev)
         scratch = torch.empty(lib.egonn_filter_points_scratch_ints(n), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.egonn_filter_points(raw.data_ptr(), n, stride, raw_off.data_ptr(), B,
-                                               int(self.remove_zero_points), int(self.remove_ground_plane), self.ground,
-                                               out.data_ptr(), new_off.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                               _lib._stream()))
+        _lib.call(dev, lib.egonn_filter_points, raw.data_ptr(), n, stride, raw_off.data_ptr(), B, int(self.remove_zero_points),
+                  int(self.remove_ground_plane), self.ground, out.data_ptr(), new_off.data_ptr(), scratch.data_ptr(),
+                  scratch.numel())
         offs = new_off.tolist()                                   # the one host sync of the ingest step (B+1 values)
         return out[: offs[-1]], offs
 

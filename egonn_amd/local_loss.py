@@ -47,9 +47,8 @@ def nn_search(a: torch.Tensor, b: torch.Tensor):
     dist = torch.empty(a.shape[0], dtype=torch.float32, device=a.device)
     idx = torch.empty(a.shape[0], dtype=torch.int32, device=a.device)
     if a.shape[0]:
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.load().egonn_nn_search(a.data_ptr(), a.shape[0], None, b.data_ptr(), b.shape[0], dist.data_ptr(),
-                                                   idx.data_ptr(), _lib._stream()))
+        _lib.call(a.device, _lib.load().egonn_nn_search, a.data_ptr(), a.shape[0], None, b.data_ptr(), b.shape[0],
+                  dist.data_ptr(), idx.data_ptr())
     return dist, idx.long()
 
 
@@ -61,9 +60,8 @@ def matrix_min(d: torch.Tensor):
     ri = torch.empty(n, dtype=torch.int32, device=d.device)
     cv = torch.empty(m, dtype=torch.float32, device=d.device)
     ci = torch.empty(m, dtype=torch.int32, device=d.device)
-    with torch.cuda.device(d.device):
-        _lib.check(_lib.load().egonn_matrix_min(d.data_ptr(), n, m, rv.data_ptr(), ri.data_ptr(), cv.data_ptr(), ci.data_ptr(),
-                                                _lib._stream()))
+    _lib.call(d.device, _lib.load().egonn_matrix_min, d.data_ptr(), n, m, rv.data_ptr(), ri.data_ptr(), cv.data_ptr(),
+              ci.data_ptr())
     return rv, ri.long(), cv, ci.long()
 
 
@@ -98,12 +96,11 @@ class _SimilarityCE(torch.autograd.Function):
         rows = torch.empty(n1, dtype=torch.float32, device=dev)
         amax = torch.empty(n1, dtype=torch.int32, device=dev)
         dlog = torch.empty((n1, n2), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            # similarity = desc1 @ desc2.T : desc2 is an (out, in) "Linear weight"
-            _lib.check(lib.egonn_dense(d1.data_ptr(), n1, c, d2.data_ptr(), 1, None, n2, 0, logits.data_ptr(), _lib._stream()))
-            logits.mul_(scale)
-            _lib.check(lib.egonn_softmax_cross_entropy(logits.data_ptr(), n1, n2, tg.data_ptr(), rows.data_ptr(), amax.data_ptr(),
-                                                       dlog.data_ptr(), _lib._stream()))
+        # similarity = desc1 @ desc2.T : desc2 is an (out, in) "Linear weight"
+        _lib.call(dev, lib.egonn_dense, d1.data_ptr(), n1, c, d2.data_ptr(), 1, None, n2, 0, logits.data_ptr())
+        logits.mul_(scale)
+        _lib.call(dev, lib.egonn_softmax_cross_entropy, logits.data_ptr(), n1, n2, tg.data_ptr(), rows.data_ptr(),
+                  amax.data_ptr(), dlog.data_ptr())
         ctx.save_for_backward(d1, d2, dlog)
         ctx.scale = scale
         ctx.mark_non_differentiable(logits, amax)
@@ -120,12 +117,11 @@ class _SimilarityCE(torch.autograd.Function):
         g1 = torch.empty((n1, c), dtype=torch.float32, device=dev)
         g2 = torch.empty((n2, c), dtype=torch.float32, device=dev)
         scratch = torch.empty(max(64 * n2 * c, 1 << 20), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            # grad_desc1 = dS @ desc2 : desc2 as a (cin = n2, cout = c) kernel
-            _lib.check(lib.egonn_dense(ds.data_ptr(), n1, n2, d2.data_ptr(), 0, None, c, 0, g1.data_ptr(), _lib._stream()))
-            # grad_desc2 = dS.T @ desc1 : a^T b over the n1 rows
-            _lib.check(lib.egonn_dense_backward_weight(ds.data_ptr(), n2, d1.data_ptr(), c, n1, g2.data_ptr(),
-                                                       scratch.data_ptr(), scratch.numel(), _lib._stream()))
+        # grad_desc1 = dS @ desc2 : desc2 as a (cin = n2, cout = c) kernel
+        _lib.call(dev, lib.egonn_dense, ds.data_ptr(), n1, n2, d2.data_ptr(), 0, None, c, 0, g1.data_ptr())
+        # grad_desc2 = dS.T @ desc1 : a^T b over the n1 rows
+        _lib.call(dev, lib.egonn_dense_backward_weight, ds.data_ptr(), n2, d1.data_ptr(), c, n1, g2.data_ptr(),
+                  scratch.data_ptr(), scratch.numel())
         return g1, g2, None, None
 
 
@@ -315,13 +311,10 @@ class _LocalLossPacked(torch.autograd.Function):
         grads = [torch.empty_like(t) for t in (k1, s1, d1, k2, s2, d2)]
         nbytes = int(lib.egonn_local_loss_scratch_bytes(pairs, k1.shape[0], k2.shape[0], dim))
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.egonn_local_loss(pairs, c1.shape[0], c2.shape[0], k1.shape[0], k2.shape[0], dim,
-                                            c1.data_ptr(), offs[0].data_ptr(), c2.data_ptr(), offs[1].data_ptr(),
-                                            k1.data_ptr(), s1.data_ptr(), d1.data_ptr(), offs[2].data_ptr(),
-                                            k2.data_ptr(), s2.data_ptr(), d2.data_ptr(), offs[3].data_ptr(),
-                                            T.data_ptr(), params, out_pair.data_ptr(), out_batch.data_ptr(),
-                                            *[g.data_ptr() for g in grads], scratch.data_ptr(), nbytes, _lib._stream()))
+        _lib.call(dev, lib.egonn_local_loss, pairs, c1.shape[0], c2.shape[0], k1.shape[0], k2.shape[0], dim, c1.data_ptr(),
+                  offs[0].data_ptr(), c2.data_ptr(), offs[1].data_ptr(), k1.data_ptr(), s1.data_ptr(), d1.data_ptr(),
+                  offs[2].data_ptr(), k2.data_ptr(), s2.data_ptr(), d2.data_ptr(), offs[3].data_ptr(), T.data_ptr(), params,
+                  out_pair.data_ptr(), out_batch.data_ptr(), *[g.data_ptr() for g in grads], scratch.data_ptr(), nbytes)
         ctx.save_for_backward(*grads)
         ctx.mark_non_differentiable(out_batch, out_pair)
         return out_batch[0].clone(), out_batch, out_pair

@@ -31,10 +31,8 @@ class _TripletLossFn(torch.autograd.Function):
         trip = torch.empty((n, 3), dtype=torch.int32, device=e.device)
         grad = torch.empty_like(e)
         scratch = torch.empty(lib.egonn_triplet_loss_scratch_floats(n), dtype=torch.float32, device=e.device)
-        with torch.cuda.device(e.device):
-            _lib.check(lib.egonn_triplet_loss(e.data_ptr(), n, d, pm.data_ptr(), nm.data_ptr(), float(margin),
-                                              stats.data_ptr(), trip.data_ptr(), grad.data_ptr(), scratch.data_ptr(),
-                                              _lib._stream()))
+        _lib.call(e.device, lib.egonn_triplet_loss, e.data_ptr(), n, d, pm.data_ptr(), nm.data_ptr(), float(margin),
+                  stats.data_ptr(), trip.data_ptr(), grad.data_ptr(), scratch.data_ptr())
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(stats, trip)
         return stats[0].clone(), stats, trip
@@ -75,10 +73,8 @@ class _ContrastiveLossFn(torch.autograd.Function):
         trip = torch.empty((n, 3), dtype=torch.int32, device=e.device)
         grad = torch.empty_like(e)
         scratch = torch.empty(lib.egonn_contrastive_loss_scratch_floats(n), dtype=torch.float32, device=e.device)
-        with torch.cuda.device(e.device):
-            _lib.check(lib.egonn_contrastive_loss(e.data_ptr(), n, d, pm.data_ptr(), nm.data_ptr(), float(pos_margin),
-                                                  float(neg_margin), stats.data_ptr(), trip.data_ptr(), grad.data_ptr(),
-                                                  scratch.data_ptr(), _lib._stream()))
+        _lib.call(e.device, lib.egonn_contrastive_loss, e.data_ptr(), n, d, pm.data_ptr(), nm.data_ptr(), float(pos_margin),
+                  float(neg_margin), stats.data_ptr(), trip.data_ptr(), grad.data_ptr(), scratch.data_ptr())
         ctx.save_for_backward(grad)
         ctx.mark_non_differentiable(stats, trip)
         return stats[0].clone(), stats, trip

@@ -73,18 +73,47 @@ class ECALayer(nn.Module):
         self.conv = nn.Conv1d(1, 1, kernel_size=k_size, padding=(k_size - 1) // 2, bias=False)
 
 
-class ECABasicBlock(nn.Module):
-    """reference layers/eca_block.py:39-54 + ME BasicBlock ctor"""
+class SELayer(nn.Module):
+    """reference layers/senet_block.py:34-50: fc = MinkowskiLinear(C, C/r), ReLU, MinkowskiLinear(C/r, C), Sigmoid on the
+    per-sample means (keys se.fc.0.linear.*, se.fc.2.linear.*); evaluated by egonn_se_gate."""
+
+    def __init__(self, channel, reduction=16):
+        super().__init__()
+        if reduction != 16 or channel % 16 or not 16 <= channel <= 256:
+            raise NotImplementedError(f'SELayer({channel}, reduction={reduction}): egonn_se_gate covers reduction 16 and a '
+                                      f'multiple of 16 channels in 16..256')
+        self.fc = nn.Sequential(Linear(channel, channel // reduction), _NoParams(), Linear(channel // reduction, channel),
+                                _NoParams())
+
+    def tensors(self):
+        """(W1, b1, W2, b2) as egonn_se_gate takes them"""
+        return self.fc[0].linear.weight, self.fc[0].linear.bias, self.fc[2].linear.weight, self.fc[2].linear.bias
+
+
+class BasicBlock(nn.Module):
+    """ME modules.resnet_block.BasicBlock parameters (conv1 norm1 conv2 norm2 [downsample]); with `eca` the reference's
+    ECABasicBlock (layers/eca_block.py:39-54), with `se` its SEBasicBlock (layers/senet_block.py:53-70).  The graph of all
+    three is graph.residual_block."""
     expansion = 1
 
-    def __init__(self, inplanes, planes, downsample=None):
+    def __init__(self, inplanes, planes, downsample=None, eca: bool = False, se: bool = False):
         super().__init__()
         self.conv1 = SparseConv(inplanes, planes, 3)
         self.norm1 = BatchNorm(planes)
         self.conv2 = SparseConv(planes, planes, 3)
         self.norm2 = BatchNorm(planes)
         self.downsample = downsample
-        self.eca = ECALayer(planes, gamma=2, b=1)
+        if eca:
+            self.eca = ECALayer(planes, gamma=2, b=1)      # reference layers/eca_block.py:54
+        if se:
+            self.se = SELayer(planes, reduction=16)        # reference layers/senet_block.py:70
+
+
+class ECABasicBlock(BasicBlock):
+    """the EgoNN trunk's block: BasicBlock with the ECA gate"""
+
+    def __init__(self, inplanes, planes, downsample=None):
+        super().__init__(inplanes, planes, downsample, eca=True)
 
 
 class MinkTrunk(nn.Module):
@@ -232,7 +261,44 @@ class PoolingWrapper(nn.Module):        # reference layers/pooling.py:13-43
 
 
 # ----------------------------------------------------------------------------- the model
-class MinkGL(nn.Module):
+class PlanModule(nn.Module):
+    """What MinkGL and the MinkLoc models share: the device rule, the egonn_ctx slots and the batch dict -> plan step."""
+    coord_bits = 16
+
+    def _device(self) -> torch.device:
+        dev = next(self.parameters()).device
+        if dev.type != 'cuda':
+            raise RuntimeError(f"egonn_amd.{type(self).__name__} runs on MI355X only: move the model to a HIP device "
+                               f"(`model.to('cuda')`); there is no CPU fallback.")
+        return dev
+
+    def context(self, slot: int = 0) -> _lib.Context:
+        """egonn_ctx number `slot` of this model's device (one per batch in flight: each owns its plan+workspace)."""
+        dev = self._device()
+        if not isinstance(getattr(self, '_ctx', None), dict):
+            self._ctx = {}
+        c = self._ctx.get(slot)
+        if c is None or c.device != dev:
+            c = _lib.Context(dev, coord_bits=self.coord_bits)
+            self._ctx[slot] = c
+        return c
+
+    def _plan(self, batch: Dict[str, torch.Tensor], slot: int = 0):
+        """{'coords': (N,4) [b,x,y,z], 'features': (N,C) [, 'batch_size']} -> (the context of `slot`, holding the plan of the
+        coordinates; the features as fp32 on the device)"""
+        dev = self._device()
+        ctx = self.context(slot)
+        coords = batch['coords'].to(device=dev, dtype=torch.int32).contiguous()
+        feats = batch['features'].to(device=dev, dtype=torch.float32).contiguous()
+        assert coords.dim() == 2 and coords.shape[1] == 4 and feats.shape[0] == coords.shape[0]
+        bs = batch.get('batch_size', None)
+        if bs is None:
+            bs = int(coords[:, 0].max().item()) + 1
+        ctx.coords_set(coords, bs)
+        return ctx, feats
+
+
+class MinkGL(PlanModule):
     """reference models/minkgl.py:228-334"""
 
     def __init__(self, trunk: MinkTrunk, local_head: MinkHead = None, local_descriptor_size: int = None,
@@ -267,29 +333,9 @@ class MinkGL(nn.Module):
                                       "(global_normalize=False, local_normalize=True, with local head)")
         # --- HIP side
         self._handle = None
-        self._ctx = None
         self._registered = None
-        self.coord_bits = 16
 
     # ------------------------------------------------------------------ HIP plumbing
-    def _device(self) -> torch.device:
-        dev = next(self.parameters()).device
-        if dev.type != 'cuda':
-            raise RuntimeError("egonn_amd.MinkGL runs on MI355X only: move the model to a HIP device "
-                               "(`model.to('cuda')`); there is no CPU fallback.")
-        return dev
-
-    def context(self, slot: int = 0) -> _lib.Context:
-        """egonn_ctx number `slot` of this model's device (one per batch in flight: each owns its plan+workspace)."""
-        dev = self._device()
-        if self._ctx is None or not isinstance(self._ctx, dict):
-            self._ctx = {}
-        c = self._ctx.get(slot)
-        if c is None or c.device != dev:
-            c = _lib.Context(dev, coord_bits=self.coord_bits)
-            self._ctx[slot] = c
-        return c
-
     def _float_state(self):
         for k, v in self.state_dict(keep_vars=True).items():
             if v.dtype == torch.float32:
@@ -319,16 +365,8 @@ class MinkGL(nn.Module):
         """context_slot: the egonn_ctx the plan of this batch lives in.  A train-mode graph back-propagates through the plan of
         its context, so two forwards whose backward comes later (the anchor and the positive batch of the local phase,
         training/trainer.py:183-192) need a slot each."""
-        dev = self._device()
-        ctx = self.context(context_slot)
-        coords, feats = batch['coords'], batch['features']
-        coords = coords.to(device=dev, dtype=torch.int32).contiguous()
-        feats = feats.to(device=dev, dtype=torch.float32).contiguous()
-        assert coords.dim() == 2 and coords.shape[1] == 4 and feats.shape == (coords.shape[0], 1)
-        bs = batch.get('batch_size', None)
-        if bs is None:
-            bs = int(coords[:, 0].max().item()) + 1
-        ctx.coords_set(coords, bs)
+        assert batch['features'].dim() == 2 and batch['features'].shape[1] == 1
+        ctx, feats = self._plan(batch, context_slot)
         if self.training:
             return self._forward_train(ctx, feats, disable_global_head, disable_local_head)
         return self._forward_on_plan(ctx, feats, disable_global_head, disable_local_head)
@@ -378,9 +416,11 @@ class MinkGL(nn.Module):
         B = ctx.batch_size
         lvl = min(LOCAL_LEVELS)
         if outputs is not None:
-            return self._forward_reserved(ctx, feats, outputs, disable_global_head, disable_local_head)
+            out_g, out_d, out_k, out_s = outputs
+            self._egonn_forward(ctx, feats, disable_global_head, disable_local_head, outputs)
+            self._last_local = (out_d, out_k, out_s)
+            return {'global': out_g, 'descriptors': out_d, 'keypoints': out_k, 'sigma': out_s}
         n3 = ctx.level_count(lvl)
-        flags = self._flags(disable_global_head, disable_local_head)
         out_g = out_d = out_k = out_s = None
         if not disable_global_head:
             out_g = torch.empty((B, self.global_descriptor_size), dtype=torch.float32, device=dev)
@@ -388,12 +428,7 @@ class MinkGL(nn.Module):
             out_d = torch.empty((n3, self.local_descriptor_size), dtype=torch.float32, device=dev)
             out_k = torch.empty((n3, 3), dtype=torch.float32, device=dev)
             out_s = torch.empty((n3, 1), dtype=torch.float32, device=dev)
-        q = self.quantizer
-        step = (_lib.C.c_float * 3)(*([float(s) for s in q.step] + [0.0, 0.0])[:3])
-        with torch.cuda.device(dev):
-            _lib.check(ctx.lib.egonn_forward(ctx.h, self._handle.h, _lib._ptr(feats), q.mode, step, flags,
-                                             _lib._ptr(out_g), _lib._ptr(out_d), _lib._ptr(out_k), _lib._ptr(out_s),
-                                             _lib._stream()))
+        self._egonn_forward(ctx, feats, disable_global_head, disable_local_head, (out_g, out_d, out_k, out_s))
         y = {}
         if out_g is not None:
             assert out_g.dim() == 2 and out_g.shape[1] == self.global_descriptor_size
@@ -421,17 +456,12 @@ class MinkGL(nn.Module):
         flags |= {'GeM': 0, 'SPoC': _lib.FLAG_POOL_SPOC, 'MAC': _lib.FLAG_POOL_MAC}[self.global_pool_method]
         return flags
 
-    def _forward_reserved(self, ctx, feats, outputs, disable_global_head=False, disable_local_head=False):
-        out_g, out_d, out_k, out_s = outputs
+    def _egonn_forward(self, ctx, feats, disable_global_head, disable_local_head, outputs):
+        """the one egonn_forward call: the whole eval graph on the plan of `ctx` into (global, descriptors, keypoints, sigma)"""
         q = self.quantizer
         step = (_lib.C.c_float * 3)(*([float(s) for s in q.step] + [0.0, 0.0])[:3])
-        with torch.cuda.device(ctx.device):
-            _lib.check(ctx.lib.egonn_forward(ctx.h, self._handle.h, _lib._ptr(feats), q.mode, step,
-                                             self._flags(disable_global_head, disable_local_head),
-                                             _lib._ptr(out_g), _lib._ptr(out_d), _lib._ptr(out_k), _lib._ptr(out_s),
-                                             _lib._stream()))
-        self._last_local = (out_d, out_k, out_s)
-        return {'global': out_g, 'descriptors': out_d, 'keypoints': out_k, 'sigma': out_s}
+        _lib.call(ctx.device, ctx.lib.egonn_forward, ctx.h, self._handle.h, _lib._ptr(feats), q.mode, step,
+                  self._flags(disable_global_head, disable_local_head), *[_lib._ptr(t) for t in outputs])
 
     def keypoint_coords(self) -> List[torch.Tensor]:
         """(n_b,4) int32 super-voxel coordinates of the rows of the last forward's local outputs, per sample

@@ -64,9 +64,8 @@ def match_mutual(feat1: torch.Tensor, feat2: torch.Tensor, n1=None, n2=None):
     c1, c2 = _counts(n1, P, n_max, dev), _counts(n2, P, n_max, dev)
     corr = torch.empty((P, n_max, 2), dtype=torch.int32, device=dev)
     n_corr = torch.empty((P,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_match_mutual(f1.data_ptr(), f2.data_ptr(), c1.data_ptr(), c2.data_ptr(), P, n_max, D,
-                                          corr.data_ptr(), n_corr.data_ptr(), _lib._stream()))
+    _lib.call(dev, lib.egonn_match_mutual, f1.data_ptr(), f2.data_ptr(), c1.data_ptr(), c2.data_ptr(), P, n_max, D,
+              corr.data_ptr(), n_corr.data_ptr())
     return corr, n_corr
 
 
@@ -104,17 +103,13 @@ def register_pairs(feat1, feat2, kp1, kp2, n1=None, n2=None, T_gt=None, ransac_d
         out.update({"hyp_count": i32(P, max(H, 0)), "hyp_err2": f64(P, max(H, 0))})
     p = lambda k: _lib._ptr(out.get(k))                                       # noqa: E731
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    with torch.cuda.device(dev):
-        st = _lib._stream()
-        _lib.check(lib.egonn_ransac_pairs(k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(),
-                                          n_corr.data_ptr(), _lib._ptr(pid), P, n_max, H, seed, float(ransac_dist_th),
-                                          scratch.data_ptr(), scratch.numel() * 8, p("hyp_count"), p("hyp_err2"), st))
-        _lib.check(lib.egonn_registration_finish(k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(),
-                                                 n_corr.data_ptr(), _lib._ptr(pid), P, n_max, H, seed, float(ransac_dist_th),
-                                                 scratch.data_ptr(), scratch.numel() * 8, _lib._ptr(gt), float(repeat_dist_th),
-                                                 p("T"), p("inliers"), p("fitness"), p("inlier_rmse"), p("correspondence_set"),
-                                                 p("best_t"), p("rte"), p("rre"), p("success"), p("repeatability"),
-                                                 p("status"), st))
+    _lib.call(dev, lib.egonn_ransac_pairs, k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(),
+              n_corr.data_ptr(), _lib._ptr(pid), P, n_max, H, seed, float(ransac_dist_th), scratch.data_ptr(),
+              scratch.numel() * 8, p("hyp_count"), p("hyp_err2"))
+    _lib.call(dev, lib.egonn_registration_finish, k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(),
+              n_corr.data_ptr(), _lib._ptr(pid), P, n_max, H, seed, float(ransac_dist_th), scratch.data_ptr(),
+              scratch.numel() * 8, _lib._ptr(gt), float(repeat_dist_th), p("T"), p("inliers"), p("fitness"), p("inlier_rmse"),
+              p("correspondence_set"), p("best_t"), p("rte"), p("rre"), p("success"), p("repeatability"), p("status"))
     out["_keep"] = (k1, k2, c1, c2, pid, gt, scratch)      # inputs of enqueued work stay alive with the result
     return out
 
@@ -152,10 +147,9 @@ def repeatability_pairs(kp1, kp2, T, threshold: float, n1=None, n2=None) -> torc
     c1, c2 = _counts(n1, P, n_max, dev), _counts(n2, P, n_max, dev)
     gt = _dev(T, dev, torch.float64).reshape(P, 4, 4)
     rep = torch.empty((P,), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_registration_finish(k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), None, None, None, P,
-                                                 n_max, 0, 0, 0.0, None, 0, gt.data_ptr(), float(threshold), None, None, None,
-                                                 None, None, None, None, None, None, rep.data_ptr(), None, _lib._stream()))
+    _lib.call(dev, lib.egonn_registration_finish, k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), None, None, None,
+              P, n_max, 0, 0, 0.0, None, 0, gt.data_ptr(), float(threshold), None, None, None, None, None, None, None, None,
+              None, rep.data_ptr(), None)
     return rep
 
 
@@ -220,11 +214,9 @@ def voxel_downsample(points, offsets, voxel_size: float = ICP_VOXEL_SIZE, crop=N
            "offsets": torch.empty((C + 1,), dtype=torch.int64, device=dev),
            "counts": torch.zeros((n,), dtype=torch.int32, device=dev),
            "status": torch.empty((C,), dtype=torch.int32, device=dev)}
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_voxel_downsample(_lib._ptr(pts) if n else None, n, off.data_ptr(), C, float(voxel_size), cr,
-                                              out["points"].data_ptr() if n else None, out["offsets"].data_ptr(),
-                                              out["counts"].data_ptr() if n else None, out["status"].data_ptr(),
-                                              scratch.data_ptr(), scratch.numel() * 8, _lib._stream()))
+    _lib.call(dev, lib.egonn_voxel_downsample, _lib._ptr(pts) if n else None, n, off.data_ptr(), C, float(voxel_size), cr,
+              out["points"].data_ptr() if n else None, out["offsets"].data_ptr(), out["counts"].data_ptr() if n else None,
+              out["status"].data_ptr(), scratch.data_ptr(), scratch.numel() * 8)
     out["_keep"] = (pts, off, scratch)
     return out
 
@@ -260,12 +252,10 @@ def icp_pairs(src, src_offsets, tgt, tgt_offsets, T_init=None, inlier_dist_thres
     if debug:
         out.update({"T_trace": f64(P, K + 1, 4, 4), "eval_trace": f64(P, K + 1, 3), "corr": i32(ns)})
     p = lambda k: _lib._ptr(out.get(k))                                       # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_icp_pairs(s.data_ptr() if ns else None, ns, so.data_ptr(), t.data_ptr() if nt else None, nt,
-                                       to.data_ptr(), P, _lib._ptr(ti), float(inlier_dist_threshold), K, ICP_EPS_FITNESS,
-                                       ICP_EPS_RMSE, p("T"), p("fitness"), p("inlier_rmse"), p("iterations"), p("status"),
-                                       p("T_trace"), p("eval_trace"), p("corr") if ns else None, scratch.data_ptr(),
-                                       scratch.numel() * 8, _lib._stream()))
+    _lib.call(dev, lib.egonn_icp_pairs, s.data_ptr() if ns else None, ns, so.data_ptr(), t.data_ptr() if nt else None, nt,
+              to.data_ptr(), P, _lib._ptr(ti), float(inlier_dist_threshold), K, ICP_EPS_FITNESS, ICP_EPS_RMSE, p("T"),
+              p("fitness"), p("inlier_rmse"), p("iterations"), p("status"), p("T_trace"), p("eval_trace"),
+              p("corr") if ns else None, scratch.data_ptr(), scratch.numel() * 8)
     out["_keep"] = (s, t, so, to, ti, scratch)
     return out
 
@@ -325,15 +315,12 @@ def _metrics_against(r, T_ref, n_max, ransac_max_it, seed, ransac_dist_th, repea
     i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
     out = {"T": f64(P, 4, 4), "inliers": i32(P), "fitness": f64(P), "inlier_rmse": f64(P), "rte": f64(P), "rre": f64(P),
            "success": i32(P), "repeatability": f64(P)}
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_registration_finish(k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), r["corr"].data_ptr(),
-                                                 r["n_corr"].data_ptr(), _lib._ptr(pid), P, n_max, int(ransac_max_it),
-                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, float(ransac_dist_th), scratch.data_ptr(),
-                                                 scratch.numel() * 8, ref.data_ptr(), float(repeat_dist_th), out["T"].data_ptr(),
-                                                 out["inliers"].data_ptr(), out["fitness"].data_ptr(),
-                                                 out["inlier_rmse"].data_ptr(), None, None, out["rte"].data_ptr(),
-                                                 out["rre"].data_ptr(), out["success"].data_ptr(),
-                                                 out["repeatability"].data_ptr(), None, _lib._stream()))
+    _lib.call(dev, lib.egonn_registration_finish, k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(),
+              r["corr"].data_ptr(), r["n_corr"].data_ptr(), _lib._ptr(pid), P, n_max, int(ransac_max_it),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, float(ransac_dist_th), scratch.data_ptr(), scratch.numel() * 8, ref.data_ptr(),
+              float(repeat_dist_th), out["T"].data_ptr(), out["inliers"].data_ptr(), out["fitness"].data_ptr(),
+              out["inlier_rmse"].data_ptr(), None, None, out["rte"].data_ptr(), out["rre"].data_ptr(),
+              out["success"].data_ptr(), out["repeatability"].data_ptr(), None)
     out["_keep"] = (ref,)
     return out
 

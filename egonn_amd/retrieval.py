@@ -22,12 +22,10 @@ def knn(query: torch.Tensor, database: torch.Tensor, k: int, chunk: int = 4096):
     idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
     dist = torch.empty((nq, k), dtype=torch.float32, device=dev)
     scratch = torch.empty(min(max(nq, 1), chunk) * m, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        for lo in range(0, nq, chunk):
-            hi = min(nq, lo + chunk)
-            _lib.check(lib.egonn_knn(q[lo:hi].data_ptr(), hi - lo, db.data_ptr(), m, q.shape[1], k,
-                                     idx[lo:hi].data_ptr(), dist[lo:hi].data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                     _lib._stream()))
+    for lo in range(0, nq, chunk):
+        hi = min(nq, lo + chunk)
+        _lib.call(dev, lib.egonn_knn, q[lo:hi].data_ptr(), hi - lo, db.data_ptr(), m, q.shape[1], k, idx[lo:hi].data_ptr(),
+                  dist[lo:hi].data_ptr(), scratch.data_ptr(), scratch.numel())
     return idx, dist
 
 
@@ -54,9 +52,8 @@ def recall_at_k(map_embeddings: torch.Tensor, query_embeddings: torch.Tensor, ma
     idx, _ = knn(qe, map_embeddings.to(dev), k)
     rad = torch.tensor([float(r) for r in radius], dtype=torch.float32, device=dev)
     tp = torch.empty((len(radius), k), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_recall_counts(idx.data_ptr(), qp.data_ptr(), mp.data_ptr(), qe.shape[0], k, qp.shape[1],
-                                           rad.data_ptr(), len(radius), tp.data_ptr(), _lib._stream()))
+    _lib.call(dev, lib.egonn_recall_counts, idx.data_ptr(), qp.data_ptr(), mp.data_ptr(), qe.shape[0], k, qp.shape[1],
+              rad.data_ptr(), len(radius), tp.data_ptr())
     n = max(int(qe.shape[0]), 1)
     tpl = tp.cpu().tolist()
     return {'recall': {r: [c / n for c in tpl[i]] for i, r in enumerate(radius)}, 'nn_index': idx}

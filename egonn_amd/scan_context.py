@@ -100,9 +100,8 @@ class ScanContext:
         n = pts.shape[0]
         sc = torch.empty((B, self.num_ring, self.num_sector), dtype=torch.float32, device=dev)
         rk = torch.empty((B, self.num_ring), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.egonn_scan_context(pts.data_ptr() if n else None, n, off.data_ptr(), B, self.num_sector, self.num_ring,
-                                              self.max_length, self.lidar_height, sc.data_ptr(), rk.data_ptr(), _lib._stream()))
+        _lib.call(dev, lib.egonn_scan_context, pts.data_ptr() if n else None, n, off.data_ptr(), B, self.num_sector,
+                  self.num_ring, self.max_length, self.lidar_height, sc.data_ptr(), rk.data_ptr())
         return sc, rk
 
     def __call__(self, pc):
@@ -117,9 +116,8 @@ def sc2rk(sc):
     lib = _lib.load()
     x = _dev(sc, dev, torch.float32).reshape(-1, shape[-2], shape[-1])
     rk = torch.empty((x.shape[0], shape[-2]), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_scan_context_ringkey(x.data_ptr() if x.shape[0] else None, x.shape[0], shape[-2], shape[-1],
-                                                  rk.data_ptr() if x.shape[0] else None, _lib._stream()))
+    _lib.call(dev, lib.egonn_scan_context_ringkey, x.data_ptr() if x.shape[0] else None, x.shape[0], shape[-2], shape[-1],
+              rk.data_ptr() if x.shape[0] else None)
     return rk[0] if len(shape) == 2 else rk
 
 
@@ -142,10 +140,8 @@ def distance_pairs(query_sc, map_sc, candidates=None):
     c = None if candidates is None else _dev(candidates, dev, torch.int32)
     dist = torch.empty((Q, k), dtype=torch.float32, device=dev)
     yaw = torch.empty((Q, k), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_scan_context_distance(q.data_ptr() if Q else None, Q, m.data_ptr() if M else None, M, qs[1], qs[2],
-                                                   _lib._ptr(c) if k else None, k, dist.data_ptr(), yaw.data_ptr(),
-                                                   _lib._stream()))
+    _lib.call(dev, lib.egonn_scan_context_distance, q.data_ptr() if Q else None, Q, m.data_ptr() if M else None, M, qs[1],
+              qs[2], _lib._ptr(c) if k else None, k, dist.data_ptr(), yaw.data_ptr())
     return dist, yaw
 
 
@@ -160,9 +156,8 @@ def rerank(dist, yaw, candidates):
     lib = _lib.load()
     d, y, c = _dev(dist, dev, torch.float32), _dev(yaw, dev, torch.int32), _dev(candidates, dev, torch.int32)
     oi, od, oy = torch.empty_like(c), torch.empty_like(d), torch.empty_like(y)
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_scan_context_rerank(d.data_ptr(), y.data_ptr(), c.data_ptr(), ds[0], ds[1], oi.data_ptr(),
-                                                 od.data_ptr(), oy.data_ptr(), _lib._stream()))
+    _lib.call(dev, lib.egonn_scan_context_rerank, d.data_ptr(), y.data_ptr(), c.data_ptr(), ds[0], ds[1], oi.data_ptr(),
+              od.data_ptr(), oy.data_ptr())
     return oi, od, oy
 
 
@@ -293,9 +288,8 @@ def evaluate(map_clouds: Sequence, query_clouds: Sequence, map_positions, query_
     qp = (qp64 - origin)[sel].to(device=dev, dtype=torch.float32).contiguous()
     rad = torch.tensor([float(r) for r in radius], dtype=torch.float32, device=dev)
     tp = torch.empty((len(radius), k), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.egonn_recall_counts(idx.data_ptr() if len(sel) else None, qp.data_ptr(), mp.data_ptr(), len(sel), k,
-                                           mp.shape[1], rad.data_ptr(), len(radius), tp.data_ptr(), _lib._stream()))
+    _lib.call(dev, lib.egonn_recall_counts, idx.data_ptr() if len(sel) else None, qp.data_ptr(), mp.data_ptr(), len(sel), k,
+              mp.shape[1], rad.data_ptr(), len(radius), tp.data_ptr())
     n = max(len(sel), 1)
     tpl = tp.cpu().tolist()
     return {'recall1': {r: [c / n for c in tpl[i]] for i, r in enumerate(radius)}, 'nn_index': idx}

@@ -61,11 +61,9 @@ class _Slot(GraphExtractor):
     # the captured step starts with the device filter: raw rows -> self.points / self.offsets (the graph's static inputs)
     def _enqueue(self):
         o, ctx = self.owner, self.ctx
-        with torch.cuda.device(ctx.device):
-            _lib.check(ctx.lib.egonn_filter_points(self.d_raw.data_ptr(), o.max_points, o.floats_per_point, self.d_raw_off.data_ptr(),
-                                                   self.B, int(o.remove_zero_points), int(o.remove_ground_plane), o.ground,
-                                                   self.points.data_ptr(), self.offsets.data_ptr(), self.scratch.data_ptr(),
-                                                   self.scratch.numel(), _lib._stream()))
+        _lib.call(ctx.device, ctx.lib.egonn_filter_points, self.d_raw.data_ptr(), o.max_points, o.floats_per_point,
+                  self.d_raw_off.data_ptr(), self.B, int(o.remove_zero_points), int(o.remove_ground_plane), o.ground,
+                  self.points.data_ptr(), self.offsets.data_ptr(), self.scratch.data_ptr(), self.scratch.numel())
         super()._enqueue()
 
     def submit(self, n_rows: int, n_real: int):

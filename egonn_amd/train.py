@@ -18,15 +18,12 @@ quantiser's keypoint_position, sigma regressor + softplus) so that the reference
 """
 from __future__ import annotations
 
-import os
-
 from typing import Dict, List, Optional
 
 import torch
-import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, graph
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SOFTPLUS = 0, 1, 2, 3
 
@@ -126,20 +123,17 @@ class BatchNormFn(Function):
     @staticmethod
     def forward(fctx, x, weight, bias, ctx: _lib.Context, bn: torch.nn.BatchNorm1d, relu: bool, group, total):
         n, c = x.shape
-        lib = ctx.lib
         track = bn.track_running_stats and bn.running_mean is not None
         shift_pt = bn.running_mean if track else torch.zeros(c, dtype=torch.float32, device=x.device)
         s = ctx.col_stats(3, x, mean=shift_pt)
         _all_reduce(s, group)
         total = float(total if total is not None else n)
-        out4 = torch.empty((4, c), dtype=torch.float32, device=x.device)
         if track:
             mom = bn.momentum if bn.momentum is not None else 1.0 / float(int(bn.num_batches_tracked) + 1)
         else:
             mom = 0.0
-        ctx._call(lib.egonn_bn_train_finalize, s.data_ptr(), shift_pt.data_ptr(), total, c, weight.data_ptr(),
-                  bias.data_ptr(), float(bn.eps), float(mom), _lib._ptr(bn.running_mean if track else None),
-                  _lib._ptr(bn.running_var if track else None), out4.data_ptr())
+        out4 = ctx.bn_train_finalize(s, shift_pt, total, weight, bias, bn.eps, mom, bn.running_mean if track else None,
+                                     bn.running_var if track else None)
         if track:
             bn.num_batches_tracked += 1
         y = ctx.affine_act(x, out4[2], out4[3], relu)
@@ -151,15 +145,12 @@ class BatchNormFn(Function):
     def backward(fctx, g):
         x, y, out4, weight = fctx.saved_tensors
         ctx, group, total = fctx.meta
-        c = x.shape[1]
         g = _c(g)
         s = ctx.col_stats(2, g, b=x, mask=y, mean=out4[0])          # sum g', sum g' (x - mean)   (this rank's rows)
         sg = s
         if group is not None:
             sg = _all_reduce(s.clone(), group)                      # whole-batch sums for the input gradient
-        out5 = torch.empty((5, c), dtype=torch.float32, device=x.device)
-        ctx._call(ctx.lib.egonn_bn_backward_finalize, s.data_ptr(), sg.data_ptr(), total, c, weight.data_ptr(),
-                  out4[0].data_ptr(), out4[1].data_ptr(), out5.data_ptr())
+        out5 = ctx.bn_backward_finalize(s, sg, total, weight, out4[0], out4[1])
         dx = ctx.affine3(g, y, x, out5[0], out5[1], out5[2])
         return dx, out5[3], out5[4], None, None, None, None, None
 
@@ -211,10 +202,7 @@ class EcaGateFn(Function):
 
     @staticmethod
     def forward(fctx, mean, weight, ctx: _lib.Context):
-        w = _c(weight.detach().reshape(-1))
-        B, c = mean.shape
-        gate = torch.empty_like(mean)
-        ctx._call(ctx.lib.egonn_eca_gate, mean.data_ptr(), w.data_ptr(), w.numel(), B, c, gate.data_ptr())
+        gate = ctx.eca_gate(mean, _c(weight.detach().reshape(-1)))
         fctx.save_for_backward(mean, weight, gate)
         fctx.meta = ctx
         return gate
@@ -223,13 +211,7 @@ class EcaGateFn(Function):
     def backward(fctx, g):
         mean, weight, gate = fctx.saved_tensors
         ctx = fctx.meta
-        w = _c(weight.detach().reshape(-1))
-        B, c = mean.shape
-        g = _c(g)
-        dmean = torch.empty_like(mean)
-        dw = torch.empty(w.numel(), dtype=torch.float32, device=mean.device)
-        ctx._call(ctx.lib.egonn_eca_gate_backward, g.data_ptr(), gate.data_ptr(), mean.data_ptr(), w.data_ptr(), w.numel(),
-                  B, c, dmean.data_ptr(), dw.data_ptr())
+        dmean, dw = ctx.eca_gate_backward(_c(g), gate, mean, _c(weight.detach().reshape(-1)))
         return dmean, dw.reshape(weight.shape), None
 
 
@@ -248,14 +230,8 @@ class SeGateFn(Function):
     @staticmethod
     def forward(fctx, mean, w1, b1, w2, b2, ctx: _lib.Context):
         mean = _c(mean)
-        B, c = mean.shape
-        h = w1.shape[0]
-        assert w1.shape == (h, c) and w2.shape == (c, h) and all(t.is_contiguous() and t.dtype == torch.float32
-                                                                 for t in (w1, b1, w2, b2))
-        gate = torch.empty_like(mean)
-        hid = torch.empty((B, h), dtype=torch.float32, device=mean.device)
-        ctx._call(ctx.lib.egonn_se_gate, mean.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), B, c, h,
-                  gate.data_ptr(), hid.data_ptr())
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (w1, b1, w2, b2))
+        gate, hid = ctx.se_gate(mean, w1, b1, w2, b2, want_hidden=True)
         fctx.save_for_backward(mean, w1, w2, gate, hid)
         fctx.meta = ctx
         return gate
@@ -263,25 +239,15 @@ class SeGateFn(Function):
     @staticmethod
     def backward(fctx, g):
         mean, w1, w2, gate, hid = fctx.saved_tensors
-        ctx = fctx.meta
-        B, c = mean.shape
-        h = w1.shape[0]
-        g = _c(g)
-        dmean, dw1, dw2 = torch.empty_like(mean), torch.empty_like(w1), torch.empty_like(w2)
-        db1 = torch.empty(h, dtype=torch.float32, device=mean.device)
-        db2 = torch.empty(c, dtype=torch.float32, device=mean.device)
-        ctx._call(ctx.lib.egonn_se_gate_backward, g.data_ptr(), gate.data_ptr(), hid.data_ptr(), mean.data_ptr(), w1.data_ptr(),
-                  w2.data_ptr(), B, c, h, dmean.data_ptr(), dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr())
-        return dmean, dw1, db1, dw2, db2, None
+        return (*fctx.meta.se_gate_backward(_c(g), gate, hid, mean, w1, w2), None)
 
 
 def se_tail(ctx, level, x, residual, se_module):
     """layers/senet_block.py:47-50,81-87: gate = sigmoid(fc(mean_b(x))), out = relu(x * gate + residual).  The gate is a
     function of ONE sample's rows, which one rank holds whole, so under a SyncBN process group it needs no collective; the
     gradients of the four fc tensors are summed over the ranks with every other parameter's (all_reduce_gradients)."""
-    fc = se_module.fc
     m = SegmentMeanFn.apply(x, ctx, level)                                       # (B, C)
-    gate = SeGateFn.apply(m, fc[0].linear.weight, fc[0].linear.bias, fc[2].linear.weight, fc[2].linear.bias, ctx)
+    gate = SeGateFn.apply(m, *se_module.tensors(), ctx)
     return GateResidualFn.apply(x, gate, residual, ctx, level)
 
 
@@ -474,53 +440,71 @@ def netvlad_pool(ctx, level: int, x: torch.Tensor, nv, group=None) -> torch.Tens
     return y
 
 
+class TrainOps:
+    """train mode: the op set of graph.py on the differentiable operators.  `totals`: level_totals of the plan, the N of every
+    BatchNorm (needed by conv_bn only)."""
+
+    def __init__(self, ctx: _lib.Context, group=None, totals: Optional[List[float]] = None):
+        self.ctx, self.group, self.totals = ctx, group, totals
+
+    def conv_bn(self, level_in, level_out, x, conv, bn, relu):
+        y = sparse_conv(self.ctx, x, conv, level_in, level_out)
+        return batch_norm(self.ctx, y, bn, relu, self.group, self.totals[level_out])
+
+    def conv(self, level_in, level_out, x, conv):
+        return sparse_conv(self.ctx, x, conv, level_in, level_out)
+
+    def tail(self, level, t, residual, block):
+        if hasattr(block, 'eca'):
+            return eca_tail(self.ctx, level, t, residual, block.eca)
+        if hasattr(block, 'se'):
+            return se_tail(self.ctx, level, t, residual, block.se)
+        return GateResidualFn.apply(t, None, residual, self.ctx, level)
+
+    def add(self, a, b):
+        return AddFn.apply(a, b, self.ctx)
+
+    def gem(self, level, x, p):
+        return GeMFn.apply(x, p, self.ctx, level)
+
+    def max_pool(self, level, x):
+        return GlobalMaxFn.apply(x, self.ctx, level)
+
+    def avg_pool(self, level, x):
+        return SegmentMeanFn.apply(x, self.ctx, level)
+
+    def netvlad(self, level, x, wrapper):
+        return netvlad_pool(self.ctx, level, x, wrapper.net_vlad, self.group)
+
+
 def pool(ctx, level: int, x: torch.Tensor, pooling, method: str, group=None) -> torch.Tensor:
     """PoolingWrapper.forward in train mode (layers/pooling.py:13-43): `pooling` is the GeM / MAC / SPoC / NetVLADWrapper
     module, `method` its name."""
-    if method == 'GeM':
-        return GeMFn.apply(x, pooling.p, ctx, level)
-    if method == 'MAC':
-        return GlobalMaxFn.apply(x, ctx, level)
-    if method == 'SPoC':
-        return SegmentMeanFn.apply(x, ctx, level)
-    if method in ('netvlad', 'netvladgc'):
-        return netvlad_pool(ctx, level, x, pooling.net_vlad, group)
-    raise NotImplementedError(f'Unknown pooling method: {method}')
+    return graph.pool(TrainOps(ctx, group), level, x, pooling, method)
 
 
 # ----------------------------------------------------------------------------- the graph
 def trunk_forward(model, ctx, group=None) -> Dict[int, torch.Tensor]:
     """MinkTrunk.forward (reference models/minkgl.py:136-153) with all-ones input features."""
     t = model.trunk
-    tot = level_totals(ctx, group)
-    x = SparseConvFn.apply(None, t.convs['0'].kernel, ctx, 0, 0, t.convs['0'].kernel_size, False)
-    x = batch_norm(ctx, x, t.bn['0'], True, group, tot[0])
+    ops = TrainOps(ctx, group, level_totals(ctx, group))
+    x = ops.conv_bn(0, 0, None, t.convs['0'], t.bn['0'], True)
     levels = {}
     for i in range(1, len(t.planes) + 1):
-        x = sparse_conv(ctx, x, t.convs[str(i)], i - 1, i)
-        x = batch_norm(ctx, x, t.bn[str(i)], True, group, tot[i])
+        x = ops.conv_bn(i - 1, i, x, t.convs[str(i)], t.bn[str(i)], True)
         for blk in t.blocks[str(i)]:
-            y = sparse_conv(ctx, x, blk.conv1, i, i)
-            y = batch_norm(ctx, y, blk.norm1, True, group, tot[i])
-            y = sparse_conv(ctx, y, blk.conv2, i, i)
-            y = batch_norm(ctx, y, blk.norm2, False, group, tot[i])
-            res = x
-            if blk.downsample is not None:
-                res = sparse_conv(ctx, x, blk.downsample[0], i, i)
-                res = batch_norm(ctx, res, blk.downsample[1], False, group, tot[i])
-            x = eca_tail(ctx, i, y, res, blk.eca)
+            x = graph.residual_block(ops, i, x, blk)
         levels[i] = x
     return levels
 
 
 def head_forward(head, ctx, levels: Dict[int, torch.Tensor]):
     """MinkHead.forward (reference models/minkgl.py:46-60)."""
-    y = sparse_conv(ctx, levels[head.max_level], head.conv1x1[str(head.max_level)], head.max_level, head.max_level)
-    for level in range(head.max_level - 1, head.min_level - 1, -1):
-        y = sparse_conv(ctx, y, head.tconv[str(level + 1)], level + 1, level)
-        if level in head.in_levels:
-            y = AddFn.apply(y, sparse_conv(ctx, levels[level], head.conv1x1[str(level)], level, level), ctx)
-    return head.min_level, y
+    ops, top = TrainOps(ctx), head.max_level
+    y = ops.conv(top, top, levels[top], head.conv1x1[str(top)])
+    return graph.top_down(ops, top, y, [(head.tconv[str(l + 1)],) + ((levels[l], head.conv1x1[str(l)]) if l in head.in_levels
+                                                                     else (None, None))
+                                        for l in range(top - 1, head.min_level - 1, -1)])
 
 
 def global_branch(model, ctx, group=None, levels=None) -> torch.Tensor:
@@ -535,48 +519,9 @@ def global_branch(model, ctx, group=None, levels=None) -> torch.Tensor:
 
 
 def minkfpn_forward(fpn, ctx, group=None):
-    """MinkFPN.forward in train mode (reference models/minkfpn.py:65-93; BasicBlock / ECABasicBlock / SEBasicBlock, all-ones input
-    features): the same graph as egonn_amd.minkloc.MinkFPN.run, on the differentiable operators."""
-    tot = level_totals(ctx, group)
-
-    def block(level, x, b):
-        y = sparse_conv(ctx, x, b.conv1, level, level)
-        y = batch_norm(ctx, y, b.norm1, True, group, tot[level])
-        y = sparse_conv(ctx, y, b.conv2, level, level)
-        y = batch_norm(ctx, y, b.norm2, False, group, tot[level])
-        res = x
-        if b.downsample is not None:
-            res = sparse_conv(ctx, x, b.downsample[0], level, level)
-            res = batch_norm(ctx, res, b.downsample[1], False, group, tot[level])
-        if hasattr(b, 'eca'):
-            return eca_tail(ctx, level, y, res, b.eca)
-        if hasattr(b, 'se'):
-            return se_tail(ctx, level, y, res, b.se)
-        return GateResidualFn.apply(y, None, res, ctx, level)
-
+    """MinkFPN.forward in train mode (all-ones input features): graph.minkfpn on the differentiable operators."""
     assert fpn.conv0.kernel_size == 5 and fpn.conv0.kernel.shape[1] == 1, "train mode: k=5, 1-channel input layer"
-    x = SparseConvFn.apply(None, fpn.conv0.kernel, ctx, 0, 0, 5, False)
-    x = batch_norm(ctx, x, fpn.bn0, True, group, tot[0])
-    fmaps = []
-    if fpn.num_top_down == fpn.num_bottom_up:
-        fmaps.append((0, x))
-    level = 0
-    for ndx, (conv, bn, blocks) in enumerate(zip(fpn.convs, fpn.bn, fpn.blocks)):
-        x = sparse_conv(ctx, x, conv, level, level + 1)
-        level += 1
-        x = batch_norm(ctx, x, bn, True, group, tot[level])
-        for b in blocks:
-            x = block(level, x, b)
-        if fpn.num_bottom_up - 1 - fpn.num_top_down <= ndx < len(fpn.convs) - 1:
-            fmaps.append((level, x))
-    x = sparse_conv(ctx, x, fpn.conv1x1[0], level, level)
-    for ndx, tconv in enumerate(fpn.tconvs):
-        x = sparse_conv(ctx, x, tconv, level, level - 1)
-        level -= 1
-        flevel, f = fmaps[-ndx - 1]
-        assert flevel == level
-        x = AddFn.apply(x, sparse_conv(ctx, f, fpn.conv1x1[ndx + 1], level, level), ctx)
-    return level, x
+    return graph.minkfpn(TrainOps(ctx, group, level_totals(ctx, group)), fpn, None)
 
 
 def local_branch(model, ctx, levels: Dict[int, torch.Tensor]):
