@@ -9,7 +9,8 @@ from .params import ModelParams
 from .quantization import CartesianQuantizer, PolarQuantizer, Quantizer
 from .model import MinkGL, MinkHead, MinkTrunk, model_factory, create_egonn_model
 from .minkloc import MinkFPN, MinkLoc, MinkLoc3D
-from .evaluator import DescriptorExtractor, GraphExtractor
+from .evaluator import DescriptorExtractor, GraphExtractor, GlobalExtractor, GlobalGraphExtractor
+from .rotations import evaluate_with_rotations
 from .stream import StreamingExtractor
 from .local_loss import (KeypointLoss, CorrespondenceLoss, KeypointCorrLoss, make_local_loss, BatchedKeypointCorrLoss,
                          local_loss_packed)
@@ -21,7 +22,8 @@ from .augment import (TrainTransform, TrainSetTransform, TrainBatcher, JitterPoi
 from .scan_context import ScanContext, ScanContextManager, sc2rk, distance_sc, evaluate as evaluate_scan_context
 
 __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "MinkHead", "MinkTrunk",
-           "CartesianQuantizer", "PolarQuantizer", "Quantizer", "DescriptorExtractor", "GraphExtractor", "StreamingExtractor", "MinkFPN", "MinkLoc", "MinkLoc3D",
+           "CartesianQuantizer", "PolarQuantizer", "Quantizer", "DescriptorExtractor", "GraphExtractor", "GlobalExtractor", "GlobalGraphExtractor",
+           "evaluate_with_rotations", "StreamingExtractor", "MinkFPN", "MinkLoc", "MinkLoc3D",
            "KeypointLoss", "CorrespondenceLoss", "KeypointCorrLoss", "make_local_loss",
            "BatchedKeypointCorrLoss", "local_loss_packed", "EgoNNTrainStep",
            "get_ransac_result", "calculate_repeatability", "register_pairs", "evaluate_local", "match_mutual", "RegistrationResult",

@@ -17,6 +17,9 @@ LIB_PATH = os.path.join(_HERE, "lib", "libegonn_hip.so")
 QUANT_CARTESIAN, QUANT_POLAR = 0, 1
 FLAG_DISABLE_GLOBAL, FLAG_DISABLE_LOCAL, FLAG_IGNORE_KP_REGRESSOR, FLAG_BF16 = 1, 2, 4, 8
 FLAG_POOL_SPOC, FLAG_POOL_MAC = 16, 32
+MINKFPN_SPLIT_TOPDOWN = 1                 # egonn_minkfpn_forward: every top-down step as one launch on the fp16 matrix pipe
+MINKFPN_BLOCKS = {'BasicBlock': 0, 'ECABasicBlock': 1}
+MINKFPN_POOLING = {None: 0, 'GeM': 1, 'MAC': 2, 'SPoC': 3}
 
 # every symbol include/egonn_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
@@ -72,6 +75,10 @@ _SIGS = [
     ("egonn_model_finalize", C.c_int, [_P, _P]),
     ("egonn_forward", C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_float), C.c_int, _P, _P, _P, _P, _P]),
     ("egonn_forward_level_features", C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    ("egonn_minkfpn_finalize", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    ("egonn_minkfpn_out_level", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    ("egonn_minkfpn_forward", C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
+    ("egonn_topdown_step", C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     ("egonn_select_keypoints", C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     ("egonn_topk_rows", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     ("egonn_triplet_loss_scratch_floats", C.c_int64, [C.c_int]),
@@ -447,6 +454,22 @@ class Context:
         self._call(self.lib.egonn_add, a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr())
         return out
 
+    def topdown_step(self, level_out: int, x_coarse: torch.Tensor, w_tconv: torch.Tensor, x_lateral: Optional[torch.Tensor] = None,
+                     w_lateral: Optional[torch.Tensor] = None, rows: Optional[int] = None):
+        """egonn_topdown_step: x_coarse[parent] @ w_tconv[slot] (+ x_lateral @ w_lateral) onto `level_out`; `rows`: rows of the
+        output (default: the level's count — a host synchronisation on a reserved plan; pass the capacity there)."""
+        x_coarse, w_tconv = _dev_f32(x_coarse, self.device), _dev_f32(w_tconv, self.device)
+        c = w_tconv.shape[-1]
+        cl = 0
+        if x_lateral is not None:
+            x_lateral, w_lateral = _dev_f32(x_lateral, self.device), _dev_f32(w_lateral, self.device)
+            cl = w_lateral.shape[0]
+        n = self.level_count(level_out) if rows is None else int(rows)
+        out = torch.empty((n, c), dtype=torch.float32, device=self.device)
+        self._call(self.lib.egonn_topdown_step, self.h, level_out, x_coarse.data_ptr(), w_tconv.data_ptr(), _ptr(x_lateral),
+                   _ptr(w_lateral), c, cl, out.data_ptr())
+        return out
+
     def gather_input(self, feats: torch.Tensor):
         feats = _dev_f32(feats, self.device)
         out = torch.empty((self.level_count(0), feats.shape[1]), dtype=torch.float32, device=self.device)
@@ -782,3 +805,17 @@ class ModelHandle:
 
     def finalize(self):
         check(self.lib.egonn_model_finalize(self.h, _stream()))
+
+    def finalize_minkfpn(self, planes: Sequence[int], layers: Sequence[int], num_top_down: int, feature_size: int, block: int,
+                         pooling: int):
+        """egonn_minkfpn_finalize: the registered tensors as a MinkFPN + pooling model (folds and packs once)"""
+        n = len(planes)
+        assert len(layers) == n
+        check(self.lib.egonn_minkfpn_finalize(self.h, n, (C.c_int * max(n, 1))(*planes), (C.c_int * max(n, 1))(*layers),
+                                              int(num_top_down), int(feature_size), int(block), int(pooling), _stream()))
+
+
+def minkfpn_out_level(n_levels: int, num_top_down: int) -> int:
+    lv = C.c_int()
+    check(load().egonn_minkfpn_out_level(int(n_levels), int(num_top_down), C.byref(lv)))
+    return lv.value

@@ -4,77 +4,18 @@
 // MinkGL.forward in eval mode (models/minkgl.py:267-315): MinkTrunk (:136-153), ECABasicBlock
 // (layers/eca_block.py:56-73), MinkHead (:46-60), DescriptorDecoder / KeypointRegressor / SigmaRegressor
 // (:175-225), GeM (layers/pooling.py:82-86).  Weights are addressed by the reference's state_dict keys.
-#include <map>
-#include <string>
-
-#include "../../include/egonn_hip.h"
-#include "common.h"
-#include "kernels.h"
+#include "model.h"
 
 using namespace egonn;
 
 #define API extern "C" __attribute__((visibility("default")))
 
-struct egonn_ctx : public Ctx {
-  // scratch kept between egonn_forward and its readers
-  hipStream_t plan_stream = nullptr; // stream the current plan was enqueued on (lazy size queries synchronise it)
-
-  void* level_feat[EGONN_NUM_LEVELS] = {};
-  int level_ch[EGONN_NUM_LEVELS] = {};
-  int level_bf16 = 0;                // precision of level_feat (last forward)
-  bool from_points = false;
-};
-
 namespace {
-
-struct TensorRef {
-  const float* p = nullptr;
-  std::vector<int64_t> shape;
-};
-
-struct BnRef {
-  const float *w = nullptr, *b = nullptr, *rm = nullptr, *rv = nullptr;
-  float *scale = nullptr, *shift = nullptr;
-  int c = 0;
-};
-
-struct BlockRef {
-  const float *conv1 = nullptr, *conv2 = nullptr, *down = nullptr, *eca = nullptr;
-  BnRef n1, n2, dn;
-  int cin = 0, cout = 0, eca_k = 0;
-};
-
-struct MlpRef {
-  const float *w0 = nullptr, *b0 = nullptr, *w1 = nullptr, *b1 = nullptr;
-  int cin = 0, mid = 0, cout = 0;
-};
 
 const int PLANES[7] = {32, 64, 64, 128, 128, 128, 128};   // models/model_factory.py:40
 const int GLOBAL_CH = 128, GLOBAL_DIM = 256, LOCAL_CH = 64, LOCAL_DIM = 128;
 
 }  // namespace
-
-struct egonn_model {
-  std::map<std::string, TensorRef> t;
-  bool ready = false;
-  float* folded = nullptr;      // scale/shift storage
-  size_t folded_cap = 0;
-  // resolved views
-  const float* conv0 = nullptr;
-  BnRef bn[8];
-  const float* convs[8] = {};
-  BlockRef blk[8];
-  const float *g1x1[8] = {}, *gt[8] = {}, *l1x1[8] = {}, *lt[8] = {};
-  const float* gem_p = nullptr;
-  MlpRef gdec, ldec, kp, sg;
-  // sparse-conv kernels repacked into MFMA fragment order (one buffer, carved in finalize)
-  float* packed = nullptr;
-  size_t packed_cap = 0;
-  void* conv0_unit = nullptr;   // conv0_pack_unit(conv0): 24 KB
-  void* lh_pack = nullptr;      // local_heads_pack: the heads' six Linear kernels as fp16 hi | lo fragments (92 KB)
-  const float** lh_ptrs = nullptr;   // device array of the six weight pointers (the packer's input)
-  PackedKernel pk_convs[8], pk_c1[8], pk_c2[8], pk_gt[8], pk_lt[8];   // fp32, bf16 (EGONN_FLAG_BF16) and fp16-split forms
-};
 
 // ------------------------------------------------------------------------------------------ lifecycle
 API const char* egonn_last_error(void) { return last_error(); }
@@ -721,6 +662,7 @@ API void egonn_model_destroy(egonn_model* m) {
   if (m->conv0_unit) (void)hipFree(m->conv0_unit);
   if (m->lh_pack) (void)hipFree(m->lh_pack);
   if (m->lh_ptrs) (void)hipFree(m->lh_ptrs);
+  if (m->fpn) minkfpn_model_free(m->fpn);
   delete m;
 }
 
@@ -731,10 +673,11 @@ API int egonn_model_set_tensor(egonn_model* m, const char* key, const float* dat
   r.shape.assign(shape, shape + ndim);
   m->t[key] = r;
   m->ready = false;
+  if (m->fpn) minkfpn_model_invalidate(m->fpn);
   return EGONN_OK;
 }
 
-namespace {
+namespace egonn {
 
 int get_tensor(egonn_model* m, const std::string& key, std::initializer_list<int64_t> want, const float** out) {
   auto it = m->t.find(key);
@@ -769,6 +712,10 @@ int get_bn(egonn_model* m, const std::string& prefix, int c, BnRef* bn, float** 
   return EGONN_OK;
 }
 
+}  // namespace egonn
+
+namespace {
+
 int get_mlp(egonn_model* m, const std::string& prefix, int cin, int mid, int cout, MlpRef* r) {
   r->cin = cin; r->mid = mid; r->cout = cout;
   EGONN_TRY(get_tensor(m, prefix + ".net.0.linear.weight", {mid, cin}, &r->w0));
@@ -778,9 +725,11 @@ int get_mlp(egonn_model* m, const std::string& prefix, int cin, int mid, int cou
   return EGONN_OK;
 }
 
-int fold(const BnRef& bn, hipStream_t st) { return bn_fold(bn.w, bn.b, bn.rm, bn.rv, 1e-5f, bn.c, bn.scale, bn.shift, st); }
-
 }  // namespace
+
+namespace egonn {
+int fold(const BnRef& bn, hipStream_t st) { return bn_fold(bn.w, bn.b, bn.rm, bn.rv, 1e-5f, bn.c, bn.scale, bn.shift, st); }
+}  // namespace egonn
 
 API int egonn_model_finalize(egonn_model* m, void* stream) {
   EGONN_REQUIRE(m, EGONN_ERR_INVALID, "model_finalize: null model");
@@ -921,6 +870,10 @@ int run_mlp(const MlpRef& r, const float* x, int64_t n, int act_out, float* hidd
   return dense_forward_ex(hidden, 0, n, r.mid, r.w1, 1, r.cout, r.b1, nullptr, nullptr, act_out, nullptr, 0, out, 0, st, n_dev);
 }
 
+}  // namespace
+
+namespace egonn {
+
 // One sparse convolution of the graph: the profiler tag "<kernel><cin,cout>/L<level>/<what>" (the kernel sconv_map will dispatch,
 // so that bench.py's roofline leg names what rocprofv3 names), the timing scope, the launch
 int conv_layer(egonn_ctx* c, hipStream_t st, const ConvCall& cc, const char* what) {
@@ -937,7 +890,7 @@ ConvCall conv_call(int kind, int level, const void* in, const PackedKernel& pk, 
                   .scale = bn ? bn->scale : nullptr, .shift = bn ? bn->shift : nullptr, .relu = relu, .packed = &pk};
 }
 
-}  // namespace
+}  // namespace egonn
 
 API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int quant_mode, const float* step, int flags,
                       float* out_global, float* out_desc, float* out_kp, float* out_sigma, void* stream) {

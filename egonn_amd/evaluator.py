@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .model import MinkGL
+from .minkloc import _MinkLocBase
 
 
 class DescriptorExtractor:
@@ -261,3 +262,123 @@ class GraphExtractor:
                 self.graph = None
         except Exception:
             pass
+
+
+class GlobalExtractor:
+    """Global-only descriptor extraction — what the reference's global evaluators do per scan (eval/evaluate_with_rotations.py:
+    110-124: quantise, unit features, `model(batch)['global']`) as the batched device pipeline of `DescriptorExtractor`:
+    voxelise -> ONE library call.  MinkLoc / MinkLoc3D run `egonn_minkfpn_forward`, MinkGL runs `egonn_forward` with the local
+    head disabled.  A model the one-call path does not cover (SEBasicBlock, netvlad pooling) raises NotImplementedError here;
+    `model(batch)` still runs it.  `quantizer`: the voxeliser (default: the one model_factory attached to the model)."""
+
+    def __init__(self, model, quantizer=None):
+        if isinstance(model, _MinkLocBase):
+            model.minkfpn_spec()                       # NotImplementedError for a model outside the one-call path
+            self.dim = model.feature_size
+        elif isinstance(model, MinkGL):
+            self.dim = model.global_descriptor_size
+        else:
+            raise NotImplementedError(f"GlobalExtractor: {type(model).__name__} is neither a MinkLoc-type model nor MinkGL")
+        self.model = model
+        self.quantizer = quantizer if quantizer is not None else getattr(model, 'quantizer', None)
+        if self.quantizer is None:
+            raise ValueError("GlobalExtractor: the model carries no quantizer (model_factory attaches one): pass quantizer=")
+
+    def _forward(self, ctx: _lib.Context, out: Dict[str, torch.Tensor]):
+        """the one call on the plan of `ctx` into the preallocated tensors of `out` ('global' [, 'map'])"""
+        m = self.model
+        if isinstance(m, MinkGL):
+            if 'map' in out:
+                raise NotImplementedError("GlobalExtractor: the feature map is an output of the MinkLoc-type models only")
+            m._forward_on_plan(ctx, None, disable_local_head=True, outputs=(out['global'], None, None, None))
+        else:
+            m.forward_on_plan(ctx, outputs=(out['global'], out.get('map')))
+        return out
+
+    def _outputs(self, ctx: _lib.Context, batch_size: int, want_map: bool):
+        out = {'global': torch.empty((batch_size, self.dim), dtype=torch.float32, device=ctx.device)}
+        if want_map:
+            if isinstance(self.model, MinkGL):
+                raise NotImplementedError("GlobalExtractor: the feature map is an output of the MinkLoc-type models only")
+            out['map'] = torch.empty((ctx.level_capacity(self.model.out_level), self.dim), dtype=torch.float32, device=ctx.device)
+        return out
+
+    @torch.no_grad()
+    def extract(self, scans: Sequence[torch.Tensor], want_map: bool = False) -> Dict[str, torch.Tensor]:
+        """scans: list of (n_i,3) float32 tensors (any device) -> {'global': (B, D)} on the device.  Like
+        `DescriptorExtractor.extract` it never returns a batch the fp16 range guard flagged: it reads the plan's status (one
+        host synchronisation) and on `Fp16RangeError` runs the plan again on the exact fp32 kernels."""
+        dev = self.model.context().device
+        pts = [torch.as_tensor(s, dtype=torch.float32).to(dev) for s in scans]
+        offsets = [0]
+        for p in pts:
+            offsets.append(offsets[-1] + p.shape[0])
+        allpts = pts[0].contiguous() if len(pts) == 1 else torch.cat(pts, dim=0)
+        return self.extract_checked(allpts, offsets, want_map=want_map)
+
+    @torch.no_grad()
+    def extract_checked(self, points: torch.Tensor, offsets: List[int], slot: int = 0, want_map: bool = False):
+        """`extract` on a packed batch that is already on the device"""
+        ctx = self.model.context(slot)
+        out = self.extract_packed(points, offsets, slot, want_map=want_map)
+        try:
+            ctx.plan_status()
+        except _lib.Fp16RangeError:
+            ctx.set_exact_fp32(True)
+            try:
+                out = self._forward(ctx, out)
+                ctx.plan_status()
+            finally:
+                ctx.set_exact_fp32(False)
+        return out
+
+    @torch.no_grad()
+    def extract_packed(self, points: torch.Tensor, offsets: List[int], slot: int = 0, want_map: bool = False):
+        """points (sum n_i, 3) float32 on the device, offsets: host list of B+1 scan bounds; `slot` selects the egonn_ctx.
+        Throughput path: the fp16 range flag is NOT read (see `DescriptorExtractor.extract_packed`)."""
+        ctx = self.model.context(slot)
+        q = self.quantizer
+        ctx.voxelize(points, offsets, q.mode, q.step)
+        return self._forward(ctx, self._outputs(ctx, len(offsets) - 1, want_map))
+
+    @torch.no_grad()
+    def calibrate(self, points: torch.Tensor, offsets: List[int], margin: float = 1.3):
+        """Level capacities for `graph` from one representative batch (eager run): margin x the observed rows."""
+        ctx = self.model.context(0)
+        q = self.quantizer
+        ctx.voxelize(points, offsets, q.mode, q.step)
+        return [int(ctx.level_count(l) * margin) + 1024 for l in range(8)]
+
+    def graph(self, batch_size: int, max_points: int, level_capacity=None, slot: int = 0, stream=None, want_map: bool = False):
+        return GlobalGraphExtractor(self, batch_size, max_points, level_capacity, slot, stream, want_map)
+
+    @torch.no_grad()
+    def extract_stream(self, batches, n_streams: int = 2):
+        """Throughput mode, as `DescriptorExtractor.extract_stream`: batch i runs on HIP stream i % n_streams with its own
+        egonn_ctx; yields the per-batch dicts in order, valid after a synchronisation of the batch's stream."""
+        dev = self.model.context(0).device
+        self.model._sync_weights()
+        if getattr(self, '_streams', None) is None or len(self._streams) != n_streams:
+            self._streams = [torch.cuda.Stream(device=dev) for _ in range(n_streams)]
+        torch.cuda.current_stream(dev).synchronize()
+        for i, (points, offsets) in enumerate(batches):
+            slot = i % n_streams
+            with torch.cuda.stream(self._streams[slot]):
+                yield self.extract_packed(points, offsets, slot=slot)
+
+
+class GlobalGraphExtractor(GraphExtractor):
+    """`GraphExtractor` for the global-only path: voxelise -> the one forward call, captured once and replayed per batch.
+    `run` / `replay` return the static {'global': (B, D)} (and 'map': (capacity of the out level, D) with want_map)."""
+
+    def __init__(self, extractor: GlobalExtractor, batch_size: int, max_points: int, level_capacity=None, slot: int = 0,
+                 stream=None, want_map: bool = False):
+        super().__init__(extractor, batch_size, max_points, level_capacity, slot, stream)
+        self.want_map = want_map
+
+    def _enqueue(self):
+        ctx, q = self.ctx, self.ex.quantizer
+        ctx.voxelize_device(self.points, self.offsets, self.B, q.mode, q.step)
+        if self.out is None:
+            self.out = {k: v.zero_() for k, v in self.ex._outputs(ctx, self.B, self.want_map).items()}
+        self.ex._forward(ctx, self.out)

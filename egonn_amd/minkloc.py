@@ -66,6 +66,75 @@ class _MinkLocBase(PlanModule):
     sync_bn_group = None          # process group of the SyncBN statistics in train mode (None = this process)
 
     pooling_method = 'GeM'
+    block = 'BasicBlock'
+    quantizer = None              # model_factory attaches the configuration's quantizer (what GlobalExtractor voxelises with)
+    # egonn_minkfpn_forward: run every top-down step as one launch on the fp16 matrix pipe (egonn_topdown_step's split arithmetic)
+    # instead of the exact sequence.  Off: tools/time_minkloc.py did not measure it faster.
+    split_topdown = False
+    _handle = None
+    _registered = None
+
+    # ------------------------------------------------------------------ the one-call path (egonn_minkfpn_forward)
+    def minkfpn_spec(self):
+        """(planes, layers, num_top_down, feature_size, block, pooling) as egonn_minkfpn_finalize takes them; raises
+        NotImplementedError for a model the one-call path does not cover (the per-operator `forward` runs those)."""
+        fpn = self.backbone
+        if self.block not in _lib.MINKFPN_BLOCKS:
+            raise NotImplementedError(f"block {self.block!r}: the one-call MinkFPN forward covers BasicBlock and ECABasicBlock; "
+                                      f"model(batch) runs this model on the per-operator path")
+        if self.pooling_method not in _lib.MINKFPN_POOLING:
+            raise NotImplementedError(f"pooling {self.pooling_method!r}: the one-call MinkFPN forward covers GeM, MAC and SPoC; "
+                                      f"model(batch) runs this model on the per-operator path")
+        if fpn.conv0.kernel.shape[1] != 1 or fpn.conv0.kernel_size != 5:
+            raise NotImplementedError("the one-call MinkFPN forward assumes the k=5 input layer on unit (one-channel) features")
+        return (tuple(fpn.planes), tuple(fpn.layers), fpn.num_top_down, fpn.lateral_dim, _lib.MINKFPN_BLOCKS[self.block],
+                _lib.MINKFPN_POOLING[self.pooling_method])
+
+    @property
+    def out_level(self) -> int:
+        """level of the feature map the pooling reads"""
+        return self.backbone.num_bottom_up - self.backbone.num_top_down
+
+    def _sync_weights(self):
+        """(Re)register the weights with the HIP model and fold / pack them when any tensor moved or was written to
+        (as MinkGL._sync_weights: num_batches_tracked carries the version of the running statistics)."""
+        spec = self.minkfpn_spec()
+        sig = tuple((k, v.data_ptr(), v._version) for k, v in self.state_dict(keep_vars=True).items())
+        if self._handle is not None and sig == self._registered:
+            return
+        if self._handle is None:
+            self._handle = _lib.ModelHandle()
+        for k, v in self.state_dict(keep_vars=True).items():
+            if v.dtype != torch.float32:
+                continue
+            t = v.detach()
+            if not t.is_contiguous():
+                raise RuntimeError(f"parameter {k} is not contiguous")
+            self._handle.set_tensor(k, t)
+        self._handle.finalize_minkfpn(*spec)
+        self._registered = sig
+
+    @torch.no_grad()
+    def forward_on_plan(self, ctx: _lib.Context, outputs=None, want_map: bool = False):
+        """The whole eval graph on the plan `ctx` holds (egonn_voxelize / egonn_coords_set, eager or reserved) as ONE library
+        call on unit features.  outputs: preallocated (global (B, D), map or None) for a reserved (capturable) plan — the map
+        holds `ctx.level_capacity(self.out_level)` rows; no host synchronisation either way.  Returns {'global': (B, D)} and,
+        when a map was asked for, 'map': (capacity of the out level, D) whose first level_count(out_level) rows are valid."""
+        self._sync_weights()
+        if outputs is not None:
+            out_g, out_m = outputs
+        else:
+            dev = ctx.device
+            out_g = torch.empty((ctx.batch_size, self.feature_size), dtype=torch.float32, device=dev)
+            out_m = None
+            if want_map:
+                out_m = torch.empty((ctx.level_capacity(self.out_level), self.feature_size), dtype=torch.float32, device=dev)
+        flags = _lib.MINKFPN_SPLIT_TOPDOWN if self.split_topdown else 0
+        _lib.call(ctx.device, ctx.lib.egonn_minkfpn_forward, ctx.h, self._handle.h, flags, _lib._ptr(out_g), _lib._ptr(out_m))
+        y = {'global': out_g}
+        if out_m is not None:
+            y['map'] = out_m
+        return y
 
     def _forward(self, batch: Dict[str, torch.Tensor], pooling: nn.Module):
         """pooling: the GeM / MAC / SPoC / NetVLADWrapper module of `pooling_method`"""

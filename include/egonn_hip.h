@@ -291,6 +291,43 @@ int egonn_forward(egonn_ctx* ctx, egonn_model* model, const float* features, int
  * strided convolution into level 2 (EGONN_NO_GATED_K2S2=1 in the environment materialises it again). */
 int egonn_forward_level_features(egonn_ctx* ctx, int level, float* out, int channels, void* stream);
 
+/* ------------------------------------------------------------------ MinkLoc / MinkLoc3D: MinkFPN + pooling in one call
+ * replaces MinkFPN.forward (models/minkfpn.py:65-93) + PoolingWrapper.forward (layers/pooling.py:13-43) in eval mode.
+ *
+ * The second kind an egonn_model can be finalized as.  The tensors are registered with egonn_model_set_tensor under the
+ * reference's state_dict keys: backbone.conv0.kernel, backbone.bn0.bn.*, backbone.convs.i.kernel, backbone.bn.i.bn.*,
+ * backbone.blocks.i.j.{conv1,norm1,conv2,norm2,downsample.0,downsample.1,eca.conv}, backbone.conv1x1.i.kernel,
+ * backbone.tconvs.i.kernel and, for GeM, pooling.pooling.p (MinkLoc) or pooling.p (MinkLoc3D).  Checks every shape (the error
+ * names the key), folds every BatchNorm and packs every sparse-conv kernel ONCE.  Supported: n_levels 1..7; planes[i] and
+ * feature_size in {32, 64, 128, 256} with planes[0] = 32 (the k=5 one-channel input layer); layers[i] >= 1;
+ * num_top_down 0..n_levels; block 0 = BasicBlock, 1 = ECABasicBlock; pooling 0 = none (feature map only), 1 = GeM, 2 = MAC,
+ * 3 = SPoC.  Anything else returns EGONN_STATUS_INVALID before any device work.  Call again whenever weights change. */
+int egonn_minkfpn_finalize(egonn_model* model, int n_levels, const int* planes, const int* layers, int num_top_down,
+                           int feature_size, int block, int pooling, void* stream);
+/* Level of the feature map the top-down pass ends on (n_levels - num_top_down): out_map of the forward below holds
+ * egonn_level_capacity of that level rows. */
+int egonn_minkfpn_out_level(int n_levels, int num_top_down, int* level);
+/* The whole eval graph on the current plan (eager or reserved) as one fixed launch sequence; unit input features (what the
+ * reference always feeds).  out_global (B, feature_size): the pooled descriptor (required unless pooling = 0); out_map
+ * (nullable; capacity of the out level x feature_size): the feature map the pooling reads, rows in plan order (only the rows
+ * in use are written).  flags: EGONN_MINKFPN_SPLIT_TOPDOWN runs every top-down step as ONE launch on the fp16 matrix pipe
+ * (egonn_topdown_step's split arithmetic; ignored on an exact-fp32 context); 0 keeps the exact sequence transposed
+ * convolution + 1x1 + add.  Clears the fp16 range flag at its start like egonn_forward; no allocation after the first
+ * call on a plan size, no host synchronisation: capturable on a reserved context.  The result of a scan does not depend on
+ * the capacities, on the other scans of the batch or on eager versus replayed execution. */
+enum { EGONN_MINKFPN_SPLIT_TOPDOWN = 1 };
+int egonn_minkfpn_forward(egonn_ctx* ctx, egonn_model* model, int flags, float* out_global, float* out_map, void* stream);
+/* One top-down step of a feature pyramid (models/minkfpn.py:86-91) onto level_out, rows in plan order:
+ *   out[o] = x_coarse[parent(o)] @ w_tconv[key(o) & 7]  (+ x_lateral[o] @ w_lateral)
+ * x_coarse (N_{level_out+1}, C), w_tconv (8, C, C), x_lateral (N_level_out, Cl) nullable, w_lateral (Cl, C), out (N_level_out, C);
+ * C in {64, 128, 256}, Cl a multiple of 32 up to C; feature maps 16-byte aligned.  Default context: both products on
+ * v_mfma_f32_16x16x32_f16 with split operands (fp16 hi + lo, three products, fp32 accumulate): |out - exact| <=
+ * 3e-6 max |out|; a non-finite accumulator (an operand beyond the fp16 range) raises EGONN_STATUS_FP16_RANGE in
+ * egonn_plan_status.  After egonn_ctx_set_exact_fp32(ctx, 1): bitwise egonn_conv_transpose, the 1x1 egonn_conv and
+ * egonn_add in that order. */
+int egonn_topdown_step(egonn_ctx* ctx, int level_out, const float* x_coarse, const float* w_tconv, const float* x_lateral,
+                       const float* w_lateral, int C, int Cl, float* out, void* stream);
+
 /* Keypoint selection — MinkLocGLEvaluator.get_keypoints_idxes, eval/evaluate.py:352-361: per sample the n_k
  * keypoints with the lowest sigma in increasing order (ties: Z-order of the super-voxel).  Padded outputs:
  *   sel_keypoints (B,n_k,3), sel_descriptors (B,n_k,128), sel_rows (B,n_k) level-3 row or -1, sel_count (B,). */
