@@ -19,6 +19,9 @@ from .registration import (get_ransac_result, calculate_repeatability, register_
                            RegistrationResult, voxel_downsample, icp_pairs, refine_pairs, icp)
 from .augment import (TrainTransform, TrainSetTransform, TrainBatcher, JitterPoints, RemoveRandomPoints, RandomTranslation,
                       RandomRotation, RemoveRandomBlock, RandomFlip, RigidPerturbation, AugmentParams, augment_points)
+from .tuples import (TrainingTuple, EvaluationTuple, EvaluationSet, save_training_tuples, load_training_tuples, radius_neighbors,
+                     count_within, relative_poses, CloudBank, generate_training_tuples, filter_query_elements,
+                     generate_evaluation_set, TupleIndex, BatchSampler, TrainingSet)
 from .scan_context import ScanContext, ScanContextManager, sc2rk, distance_sc, evaluate as evaluate_scan_context
 
 __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "MinkHead", "MinkTrunk",
@@ -30,4 +33,7 @@ __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "Mink
            "voxel_downsample", "icp_pairs", "refine_pairs", "icp",
            "TrainTransform", "TrainSetTransform", "TrainBatcher", "JitterPoints", "RemoveRandomPoints", "RandomTranslation",
            "RandomRotation", "RemoveRandomBlock", "RandomFlip", "RigidPerturbation", "AugmentParams", "augment_points",
+           "TrainingTuple", "EvaluationTuple", "EvaluationSet", "save_training_tuples", "load_training_tuples", "radius_neighbors",
+           "count_within", "relative_poses", "CloudBank", "generate_training_tuples", "filter_query_elements",
+           "generate_evaluation_set", "TupleIndex", "BatchSampler", "TrainingSet",
            "ScanContext", "ScanContextManager", "sc2rk", "distance_sc", "evaluate_scan_context"]

@@ -135,6 +135,11 @@ _SIGS = [
     ("egonn_scan_context_ringkey", C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P, _P]),
     ("egonn_scan_context_distance", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     ("egonn_scan_context_rerank", C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P]),
+    ("egonn_radius_count", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int, _P, _P]),
+    ("egonn_radius_fill", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_double, C.c_int, _P, _P, C.c_int64, _P, _P]),
+    ("egonn_pair_masks", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    ("egonn_relative_poses", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
+    ("egonn_gather_clouds", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int, _P, C.c_int64, _P, _P, _P]),
     ("egonn_profile_enable", C.c_int, [_P, C.c_int, C.c_char_p]),
     ("egonn_profile_fetch", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),

@@ -702,6 +702,55 @@ int egonn_scan_context_distance(const float* query_sc, int64_t n_query, const fl
 int egonn_scan_context_rerank(const float* dist, const int32_t* yaw, const int32_t* candidates, int64_t n_query, int k,
                               int32_t* out_index, float* out_dist, int32_t* out_yaw, void* stream);
 
+/* ------------------------------------------------------------------ training tuples (egonn_amd/csrc/tuples.hip)
+ * What datasets/mulran/generate_training_tuples.py, filter_query_elements (datasets/dataset_utils.py:210-232) and the mask
+ * loops of make_collate_fn (:83-88) do around the ICP, on the device.  All geometry is fp64 with contraction off, there are no
+ * float atomics, every result is bitwise reproducible, and no entry synchronises with the host. */
+enum { EGONN_TUPLES_STATUS_CAPACITY = 1,     /* an output did not fit its capacity: nothing was written past it */
+       EGONN_TUPLES_STATUS_BAD_OFFSETS = 2,  /* row offsets that are not the exclusive scan of the counts / not inside their table */
+       EGONN_TUPLES_STATUS_BAD_INDEX = 4 };  /* a label or a pick outside its table */
+enum { EGONN_POSE_STATUS_BAD_ROW = 1,        /* a pose whose last row is not exactly 0 0 0 1 */
+       EGONN_POSE_STATUS_SINGULAR = 2,       /* det R_b is zero or not finite */
+       EGONN_POSE_STATUS_BAD_INDEX = 4 };    /* idx_a or idx_b outside [0, n_poses) */
+/* Radius join of 2-D positions: query (nq,2) and ref (nm,2) f64 on the DEVICE, nq, nm <= 2^24.  j is a neighbour of i iff
+ *     dx = qx_i - mx_j;  dy = qy_i - my_j;  dx*dx + dy*dy <= r*r        (each operation rounded to fp64)
+ * which is what sklearn's KDTree.query_radius returns on the same positions (tests/golden/make_golden_tuples.py asserts it
+ * row by row).  A NaN coordinate is never a neighbour and has none.  radii: 1 to 4 HOST doubles, finite, >= 0.
+ * exclude_self (bit r of exclude_self_mask = radius r) drops j == i and nothing else; it is legal only when query and ref are
+ * the same array (same pointer, nq == nm).
+ * count: counts (n_radius, nq) int32.  fill: one radius; offsets (nq+1) DEVICE int64 = the exclusive scan of that radius'
+ * counts; writes the neighbours of row i to indices[offsets[i] .. offsets[i+1]) in ASCENDING order (no sort: the order is by
+ * construction).  capacity = entries `indices` can hold: a hit whose slot is beyond it is dropped and sets
+ * EGONN_TUPLES_STATUS_CAPACITY in the DEVICE int32 *status (cleared by the call); offsets that disagree with the counts set
+ * EGONN_TUPLES_STATUS_BAD_OFFSETS and nothing is written outside a row. */
+int egonn_radius_count(const double* query, int64_t nq, const double* ref, int64_t nm, const double* radii, int n_radius,
+                       int exclude_self_mask, int32_t* counts, void* stream);
+int egonn_radius_fill(const double* query, int64_t nq, const double* ref, int64_t nm, double radius, int exclude_self,
+                      const int64_t* offsets, int32_t* indices, int64_t capacity, int32_t* status, void* stream);
+/* The (B,B) masks of a batch from the two CSR tables of the tuples (offsets (n_tuples+1) DEVICE int64, indices DEVICE int32
+ * sorted inside a row, n_pos / n_non = entries of the index arrays): with l = labels (B) DEVICE int32,
+ *     positives_mask[i][j] = l[j] in positives[l[i]],   negatives_mask[i][j] = l[j] not in non_negatives[l[i]]
+ * as uint8 0/1, each membership a binary search (in_sorted_array, datasets/dataset_utils.py:270-275).  A label outside
+ * [0, n_tuples) sets EGONN_TUPLES_STATUS_BAD_INDEX in *status (DEVICE int32, cleared by the call) and its row and column are 0
+ * in both masks.  batch_size <= 4096.  One memset + one launch: capturable. */
+int egonn_pair_masks(const int32_t* labels, int batch_size, const int64_t* pos_offsets, const int32_t* pos_indices, int64_t n_pos,
+                     const int64_t* non_offsets, const int32_t* non_indices, int64_t n_non, int64_t n_tuples,
+                     uint8_t* positives_mask, uint8_t* negatives_mask, int32_t* status, void* stream);
+/* out[p] = inv(m_b) @ m_a for a = idx_a[p], b = idx_b[p] (poses (n_poses,4,4) f64 row-major, indices DEVICE int32), evaluated
+ * as the affine inverse: R_b^-1 = adjugate / determinant, rotation R_b^-1 R_a, translation R_b^-1 (t_a - t_b) with the
+ * difference taken FIRST (np.linalg.inv(m_b) @ m_a cancels digits at UTM-sized translations), three-term dot products summed
+ * left to right, last row 0 0 0 1.  negate_translation: the translation is negated afterwards (datasets/mulran/utils.py:
+ * 122-124); off: misc/poses.py:89.  status (n_pairs) DEVICE int32: a non-zero EGONN_POSE_STATUS_* pair gets the identity. */
+int egonn_relative_poses(const double* poses, int64_t n_poses, const int32_t* idx_a, const int32_t* idx_b, int64_t n_pairs,
+                         int negate_translation, double* out, int32_t* status, void* stream);
+/* Copies clouds pick[0..n_pick) (DEVICE int32) of a bank (bank (n_bank,3) f64, bank_offsets (n_clouds+1) DEVICE int64: the
+ * layout egonn_voxel_downsample returns) back to back into out (capacity,3) and writes out_offsets (n_pick+1) DEVICE int64:
+ * the src / src_offsets of egonn_icp_pairs.  n_pick <= 4096 (the scan runs in one workgroup).  A pick outside the bank
+ * (EGONN_TUPLES_STATUS_BAD_INDEX) or more than `capacity` points (EGONN_TUPLES_STATUS_CAPACITY) is written to *status (DEVICE
+ * int32) and leaves ALL offsets zero and nothing copied: the ICP then sees empty clouds (EGONN_ICP_STATUS_EMPTY). */
+int egonn_gather_clouds(const double* bank, int64_t n_bank, const int64_t* bank_offsets, int64_t n_clouds, const int32_t* pick,
+                        int n_pick, double* out, int64_t capacity, int64_t* out_offsets, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ launch timing (bench.py roofline leg)
  * mode 0: off; 1: time every tagged sparse-conv launch (event records around it); 2: only launches whose tag contains
  * `filter`, with the events attached to the kernel dispatch itself (the kernel's own begin..end, also when other streams
