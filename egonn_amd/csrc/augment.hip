@@ -55,8 +55,6 @@
 
 #pragma clang fp contract(off)
 
-#define API extern "C" __attribute__((visibility("default")))
-
 namespace egonn {
 
 static constexpr int AUG_TILE = 256;        // points per workgroup of the apply pass (one per lane)

@@ -22,6 +22,9 @@
 #define EGONN_NUM_LEVELS 8       // levels that carry features: 0..7
 #define EGONN_MAX_BATCH 4096
 
+// an entry point of the C ABI (include/egonn_hip.h): defined in the file that holds its kernels
+#define API extern "C" __attribute__((visibility("default")))
+
 namespace egonn {
 
 // ------------------------------------------------------------------ error plumbing
@@ -72,11 +75,36 @@ struct AttrOnce {
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ------------------------------------------------------------------ device arena (grow-only)
+// An owning arena grows by hipFree + hipMalloc.  A borrowed one (Arena::view) is a window onto memory someone else owns — the
+// scratch a caller handed to an entry point: it never synchronises, allocates or frees, and a request beyond it is an error.
 struct Arena {
   char* base = nullptr;
   size_t cap = 0;
   size_t off = 0;
-  int ensure(size_t bytes);                 // may hipFree + hipMalloc (only legal when nothing is live)
+  bool borrowed = false;
+  static Arena view(void* span, size_t bytes) {
+    Arena a;
+    a.base = static_cast<char*>(span);
+    a.cap = bytes;
+    a.borrowed = true;
+    return a;
+  }
+  int ensure(size_t bytes) {                // owning: may hipFree + hipMalloc (only legal when nothing is live)
+    if (bytes <= cap) return EGONN_OK;
+    EGONN_REQUIRE(!borrowed, EGONN_ERR_INVALID, "scratch span of %zu bytes is %zu bytes short of the %zu needed", cap, bytes - cap,
+                  bytes);
+    size_t want = align_up(bytes + bytes / 4, size_t(1) << 20);
+    if (base) {
+      HIP_CHECK(hipDeviceSynchronize());
+      HIP_CHECK(hipFree(base));
+      base = nullptr;
+      cap = 0;
+    }
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&base), want));
+    cap = want;
+    off = 0;
+    return EGONN_OK;
+  }
   void reset() { off = 0; }
   template <typename T>
   T* alloc(size_t n) {
@@ -86,7 +114,12 @@ struct Arena {
     off = end;
     return reinterpret_cast<T*>(base + o);
   }
-  void release();
+  void release() {
+    if (borrowed) return;
+    if (base) (void)hipFree(base);
+    base = nullptr;
+    cap = off = 0;
+  }
 };
 
 // ------------------------------------------------------------------ Morton helpers (host + device)
@@ -232,6 +265,7 @@ struct Ctx {
   float* ks_part = nullptr;   // scratch for the partial tiles of the offset-split launches (sconv_split.hip): carved from the work arena
   size_t ks_part_floats = 0;  // by egonn_forward / the stand-alone operator entry points (sconv_ksplit_scratch_floats)
   const void* sort_prezeroed = nullptr;   // the per-scan histograms of the segmented sort were zeroed by the kernel in front of it
+                                          // (coords.hip: set by the key kernel's launcher, handed to the sort, cleared after it)
   int keep_level_features = 0;   // egonn_debug_keep_level_features: no fusion that leaves a level's block output unmaterialised
   int operand_autoscale = 0;  // egonn_ctx_set_operand_autoscale: the fp16-split convolutions scale their INPUT by a power of two per launch
                               // (max |in| -> [2^13, 2^14), undone in the epilogue): the input-gradient convolutions of a training step
@@ -280,19 +314,23 @@ int rowgroup_cap_groups(const Plan& P, int level);   // groups the row-group tab
 // ------------------------------------------------------------------ sort.hip
 // LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits).  Result lands in (keys_out, vals_out) — or, when the caller
 // passes keys_res / vals_res, in whichever of the two buffer pairs the last pass wrote (an even number of passes ends in the
-// "in" pair: no copy; the pointers are returned).  Stable.  Both pairs are clobbered.  Scratch comes from ctx->sort_arena.
+// "in" pair: no copy; the pointers are returned).  Stable.  Both pairs are clobbered.  Scratch comes from `ws`: a context's
+// sort arena (grown on demand) or a borrowed span of at least radix_sort_scratch_bytes(n) + 512 bytes (Arena::alloc aligns
+// every carve to 256).
 // n_dev (nullable): device-resident element count (<= n); n then only sizes the grid and the scratch.
-int radix_sort_pairs(Ctx* ctx, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out,
+int radix_sort_pairs(Arena& ws, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out,
                      int64_t n, int nbits, hipStream_t stream, const int64_t* n_dev = nullptr, uint64_t** keys_res = nullptr,
                      uint32_t** vals_res = nullptr);
 size_t radix_sort_scratch_bytes(int64_t n);
 // Per-scan variant: every segment [off[b], off[b+1]) (DEVICE int64 offsets, B+1) is sorted on its own on bits [0, nbits), 9 bits
 // per pass — no pass is spent on the batch index of contiguous scans.  The result lands in whichever pair the last pass wrote.
-int radix_sort_segments(Ctx* ctx, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n,
+// prezeroed (nullable): the per-scan histograms radix_sort_segments_layout(ws, n, B) returns, when the launch in front of the
+// sort has zeroed them already (one memset node less); anything else and the sort zeroes them itself.
+int radix_sort_segments(Arena& ws, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n,
                         const int64_t* off_dev, int B, int nbits, hipStream_t stream, uint64_t** keys_res, uint32_t** vals_res,
-                        int idx_bits = 0);
+                        int idx_bits = 0, const void* prezeroed = nullptr);
 size_t radix_sort_segments_scratch_bytes(int64_t n, int B);
-int radix_sort_segments_layout(Ctx* ctx, int64_t n, int B, int32_t** tilehist, int32_t** scanhist);
+int radix_sort_segments_layout(Arena& ws, int64_t n, int B, int32_t** tilehist, int32_t** scanhist);
 int radix_sort_segments_passes(int nbits);
 int radix_sort_segments_digits();
 

@@ -16,7 +16,7 @@
 
 namespace egonn {
 
-// ------------------------------------------------------------------ error + arena
+// ------------------------------------------------------------------ error
 static thread_local char g_err[1024] = "";
 void set_error(const char* fmt, ...) {
   va_list ap;
@@ -42,26 +42,6 @@ const Switches& switches() {
                                getenv("EGONN_KSPLIT_PARTS")}};
   }();
   return sw;
-}
-
-int Arena::ensure(size_t bytes) {
-  if (bytes <= cap) return EGONN_OK;
-  size_t want = align_up(bytes + bytes / 4, size_t(1) << 20);
-  if (base) {
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipFree(base));
-    base = nullptr;
-    cap = 0;
-  }
-  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&base), want));
-  cap = want;
-  off = 0;
-  return EGONN_OK;
-}
-void Arena::release() {
-  if (base) (void)hipFree(base);
-  base = nullptr;
-  cap = off = 0;
 }
 
 hipEvent_t Profiler::get() {
@@ -848,11 +828,13 @@ static int build_plan_from_sorted_input(Ctx* ctx, uint64_t* keys_raw, uint32_t* 
   const bool flat_sort = plan_flat_sort();
   if (seg_off && !flat_sort) {
     // plans built from points: the scans are contiguous, each is sorted on its Morton bits (packed elements when they fit)
-    EGONN_TRY(radix_sort_segments(ctx, keys_raw, vals_raw, keys_sorted, vals_sorted, n, seg_off, B, 3 * cb, stream, &keys_sorted,
-                                  &vals_sorted, idx_bits));
+    const void* prezeroed = ctx->sort_prezeroed;
+    ctx->sort_prezeroed = nullptr;
+    EGONN_TRY(radix_sort_segments(ctx->sort_arena, keys_raw, vals_raw, keys_sorted, vals_sorted, n, seg_off, B, 3 * cb, stream,
+                                  &keys_sorted, &vals_sorted, idx_bits, prezeroed));
   } else {
-    EGONN_TRY(radix_sort_pairs(ctx, keys_raw, vals_raw, keys_sorted, vals_sorted, n, 3 * cb + batch_bits(B), stream, n_dev, &keys_sorted,
-                               &vals_sorted));
+    EGONN_TRY(radix_sort_pairs(ctx->sort_arena, keys_raw, vals_raw, keys_sorted, vals_sorted, n, 3 * cb + batch_bits(B), stream, n_dev,
+                               &keys_sorted, &vals_sorted));
   }
 
   const int ntiles = (int)cdiv(n, PYR_TILE);
@@ -1144,7 +1126,7 @@ int plan_from_points(Ctx* ctx, const float* points, const int64_t* scan_offsets,
   int zero_words = 0;
   ctx->sort_prezeroed = nullptr;
   if (!plan_flat_sort()) {       // the segmented sort follows: its per-scan histograms are zeroed by the key kernel
-    EGONN_TRY(radix_sort_segments_layout(ctx, n, B, &tilehist, &scanhist));
+    EGONN_TRY(radix_sort_segments_layout(ctx->sort_arena, n, B, &tilehist, &scanhist));
     zero_words = radix_sort_segments_passes(3 * ctx->coord_bits) * B * radix_sort_segments_digits();
     ctx->sort_prezeroed = scanhist;
   }

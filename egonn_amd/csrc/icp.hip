@@ -36,8 +36,6 @@
 
 #pragma clang fp contract(off)
 
-#define API extern "C" __attribute__((visibility("default")))
-
 namespace egonn {
 
 static constexpr int ICP_WG = 256;
@@ -250,6 +248,7 @@ static DsLayout ds_layout(int64_t n, int C) {
   L.keys0 = take(m * 8), L.keys1 = take(m * 8), L.vals0 = take(m * 4), L.vals1 = take(m * 4);
   L.mins = take((size_t)C * 3 * 8);
   L.blockcnt = take((size_t)(cdiv((int64_t)m, ICP_WG) + 1) * 4);
+  // + 512: the sort carves two arrays out of this span and Arena::alloc aligns each carve to 256
   L.sort_bytes = align_up(radix_sort_segments_scratch_bytes((int64_t)m, C) + 512, 256);
   L.sort = take(L.sort_bytes);
   L.total = o;
@@ -705,17 +704,11 @@ static IcpLayout icp_layout(int64_t ns, int64_t nt, int P) {
   L.tq = take(b * 24), L.tj = take(b * 4), L.tkey = take(b * 8);
   L.sq = take(a * 24), L.si = take(a * 4);
   L.partial = take((size_t)L.n_wg * ICP_NPART * 8);
+  // + 512: the sort carves two arrays out of this span and Arena::alloc aligns each carve to 256
   L.sort_bytes = align_up(radix_sort_segments_scratch_bytes((int64_t)m, P) + 512, 256);
   L.sort = take(L.sort_bytes);
   L.total = o;
   return L;
-}
-
-// the segmented sort of sort.hip takes its scratch from a context's arena: a context whose arena IS the caller's scratch
-static void icp_sort_ctx(Ctx* shim, char* base, size_t bytes) {
-  shim->sort_arena.base = base;
-  shim->sort_arena.cap = bytes;
-  shim->sort_arena.off = 0;
 }
 
 }  // namespace egonn
@@ -752,10 +745,9 @@ API int egonn_voxel_downsample(const float* points, int64_t n, const int64_t* of
   if (n > 0) {
     hipLaunchKernelGGL(ds_key_kernel, dim3((unsigned)nb), dim3(ICP_WG), 0, st, points, n, offsets, n_clouds, cr, voxel_size, mins, keys,
                        vals, status);
-    Ctx shim;
-    icp_sort_ctx(&shim, base + L.sort, L.sort_bytes);
-    EGONN_TRY(radix_sort_segments(&shim, keys, vals, (uint64_t*)(base + L.keys1), (uint32_t*)(base + L.vals1), n, offsets, n_clouds,
-                                  64, st, &keys, &vals, 0));
+    Arena sort_ws = Arena::view(base + L.sort, L.sort_bytes);
+    EGONN_TRY(radix_sort_segments(sort_ws, keys, vals, (uint64_t*)(base + L.keys1), (uint32_t*)(base + L.vals1), n, offsets, n_clouds,
+                                  64, st, &keys, &vals));
     hipLaunchKernelGGL(ds_count_kernel, dim3((unsigned)nb), dim3(ICP_WG), 0, st, keys, offsets, n_clouds, n, status, blockcnt);
   }
   hipLaunchKernelGGL(ds_scan_kernel, dim3(1), dim3(ICP_WG), 0, st, keys, offsets, n_clouds, n, status, blockcnt, nb, out_offsets);
@@ -807,7 +799,7 @@ API int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_off
   double* sq = (double*)(base + L.sq);
   int32_t* si = (int32_t*)(base + L.si);
   double* partial = (double*)(base + L.partial);
-  Ctx shim;
+  Arena sort_ws = Arena::view(base + L.sort, L.sort_bytes);
   for (int side = 0; side < 2; ++side) {
     const double* pts = side == 0 ? tgt : src;
     const int64_t n = side == 0 ? n_tgt : n_src;
@@ -816,9 +808,8 @@ API int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_off
     uint32_t* vals = (uint32_t*)(base + L.vals0);
     const unsigned nb = (unsigned)cdiv(n, ICP_WG);
     hipLaunchKernelGGL(icp_key_kernel, dim3(nb), dim3(ICP_WG), 0, st, pts, n, off, n_pairs, pairs, side, keys, vals);
-    icp_sort_ctx(&shim, base + L.sort, L.sort_bytes);
-    EGONN_TRY(radix_sort_segments(&shim, keys, vals, (uint64_t*)(base + L.keys1), (uint32_t*)(base + L.vals1), n, off, n_pairs, 48, st,
-                                  &keys, &vals, 0));
+    EGONN_TRY(radix_sort_segments(sort_ws, keys, vals, (uint64_t*)(base + L.keys1), (uint32_t*)(base + L.vals1), n, off, n_pairs, 48,
+                                  st, &keys, &vals));
     hipLaunchKernelGGL(icp_gather_kernel, dim3(nb), dim3(ICP_WG), 0, st, pts, n, off, n_pairs, keys, vals, side == 0 ? tq : sq,
                        side == 0 ? tj : si, side == 0 ? tkey : (uint64_t*)nullptr);
   }

@@ -5,8 +5,7 @@
 //     pc = pc[pc[:, 2] > ground_plane_level]                             (NaN z fails the test, as in numpy)
 // and compacted in the original point order (stable) into the (n, 3) array egonn_voxelize consumes, together with
 // the per-scan offsets of the survivors.  Three small launches: per-block counts, one-block scan, scatter.
-#include "common.h"
-#include "kernels.h"
+#include "model.h"
 
 namespace egonn {
 
@@ -124,25 +123,26 @@ __global__ __launch_bounds__(64) void ingest_offsets_kernel(const float* __restr
   if (lane == 0) new_off[b] = (int64_t)block_pre[blk] + c;
 }
 
-size_t ingest_scratch_ints(int64_t n) { return (size_t)cdiv(n, ING_BLOCK) + 2; }
+API int64_t egonn_filter_points_scratch_ints(int64_t n) { return cdiv(n, ING_BLOCK) + 2; }
 
-int ingest_filter(const float* raw, int64_t n, int stride, const int64_t* raw_off_dev, int batch, int remove_zero,
-                  int remove_ground, float ground, float* out_xyz, int64_t* new_off_dev, int32_t* scratch,
-                  size_t scratch_ints, hipStream_t stream) {
+API int egonn_filter_points(const float* raw, int64_t n, int stride, const int64_t* raw_off_dev, int batch, int remove_zero,
+                            int remove_ground, float ground, float* out_xyz, int64_t* new_off_dev, int32_t* scratch,
+                            int64_t scratch_ints, void* stream) {
   EGONN_REQUIRE((raw || n == 0) && out_xyz && raw_off_dev && new_off_dev && scratch && n >= 0 && n < (1ll << 31) && batch >= 1 &&
                     (stride == 3 || stride == 4),
                 EGONN_ERR_INVALID, "ingest: bad arguments (n=%lld stride=%d)", (long long)n, stride);
   const int64_t nblk = cdiv(n, ING_BLOCK);
-  EGONN_REQUIRE(scratch_ints >= (size_t)nblk + 2, EGONN_ERR_INVALID, "ingest: scratch too small");
+  EGONN_REQUIRE((size_t)scratch_ints >= (size_t)nblk + 2, EGONN_ERR_INVALID, "ingest: scratch too small");
+  hipStream_t st = (hipStream_t)stream;
   if (nblk > 0) {
-    hipLaunchKernelGGL(ingest_count_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, raw, n, stride, remove_zero,
+    hipLaunchKernelGGL(ingest_count_kernel, dim3((unsigned)nblk), dim3(256), 0, st, raw, n, stride, remove_zero,
                        remove_ground, ground, raw_off_dev, batch, scratch);
   }
-  hipLaunchKernelGGL(ingest_scan_kernel, dim3(1), dim3(1024), 0, stream, scratch, (int32_t)nblk);
+  hipLaunchKernelGGL(ingest_scan_kernel, dim3(1), dim3(1024), 0, st, scratch, (int32_t)nblk);
   if (nblk > 0)
-    hipLaunchKernelGGL(ingest_scatter_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, raw, n, stride, remove_zero,
+    hipLaunchKernelGGL(ingest_scatter_kernel, dim3((unsigned)nblk), dim3(256), 0, st, raw, n, stride, remove_zero,
                        remove_ground, ground, scratch, raw_off_dev, batch, out_xyz);
-  hipLaunchKernelGGL(ingest_offsets_kernel, dim3((unsigned)(batch + 1)), dim3(64), 0, stream, raw, n, stride,
+  hipLaunchKernelGGL(ingest_offsets_kernel, dim3((unsigned)(batch + 1)), dim3(64), 0, st, raw, n, stride,
                      remove_zero, remove_ground, ground, scratch, raw_off_dev, batch + 1, new_off_dev);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;

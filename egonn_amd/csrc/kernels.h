@@ -1,4 +1,6 @@
-// Internal kernel-launcher declarations shared between the .hip translation units.
+// Internal kernel-launcher declarations shared between the .hip translation units: only what a second translation unit calls.
+// An operator that is an entry point of the C ABI and nothing else is defined beside its kernels and declared in
+// include/egonn_hip.h alone (loss.hip, local_loss.hip, train.hip, netvlad_train.hip, retrieval.hip, ingest.hip, ...).
 #pragma once
 #include "common.h"
 
@@ -166,110 +168,9 @@ int netvlad_forward(const float* x, const int32_t* boff, int B, int C, const flo
                     const float* sh1, const float* H, int D, const float* sc2, const float* sh2, const float* wg,
                     const float* scg, const float* shg, int gating, float* out, float* ws, hipStream_t stream);
 
-// netvlad_train.hip ------------------------------------------------------------------------------
-// Train-mode NetVLAD core (bn1 on batch statistics over M = B * nmax rows, pad rows included; y = vlad @ H before bn2) and its
-// backward; MAC with its argmax and the scatter that is its backward; y * sigmoid(t) of the context gating.
-size_t netvlad_train_forward_floats(int B, int64_t N, int C, int D);
-int netvlad_train_forward(const float* x, const int32_t* boff, int B, int64_t N, int C, int nmax, const float* wc,
-                          const float* w2, const float* bn1_w, const float* bn1_b, float eps, float momentum,
-                          float* running_mean, float* running_var, const float* H, int D, float* out, float* save_z,
-                          float* save_bn4, float* save_vraw, float* save_sq, float* save_asum, float* ws, hipStream_t stream);
-size_t netvlad_train_backward_floats(int B, int64_t N, int C, int D);
-int netvlad_train_backward(const float* x, const float* z, const int32_t* boff, int B, int64_t N, int C, int nmax,
-                           const float* wc, const float* w2, const float* bn1_w, const float* bn4, const float* H, int D,
-                           const float* dy, const float* vraw, const float* sq, const float* asum, float* dx, float* dwc,
-                           float* dw2, float* bn5, float* dH, float* ws, hipStream_t stream);
-int global_max_argmax(const float* in, const int32_t* boff, int B, int c, float* out, int32_t* rows, hipStream_t stream);
-int global_max_backward(const float* grad, const int32_t* rows, int B, int64_t n, int c, float* dx, hipStream_t stream);
-int sigmoid_gate(const float* y, const float* t, const float* grad, int64_t n, float* out, float* dy, float* dt,
-                 hipStream_t stream);
-
-// loss.hip ---------------------------------------------------------------------------------------
-size_t contrastive_loss_scratch_floats(int n);
-int contrastive_loss_forward(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float pos_margin,
-                             float neg_margin, float* out13, int32_t* triplets, float* grad, float* scratch,
-                             hipStream_t stream);
-size_t triplet_loss_scratch_floats(int n);
-int triplet_loss_forward(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float margin,
-                         float* out10, int32_t* triplets, float* grad, float* scratch, hipStream_t stream);
-
-// local-head losses (models/loss_utils.py): searches + softmax cross-entropy rows
-int nn_search(const float* a, int64_t n, const float* M, const float* b, int64_t m, float* out_dist, int32_t* out_idx,
-              hipStream_t stream);
-int matrix_min(const float* d, int64_t n, int64_t m, float* row_min, int32_t* row_idx, float* col_min, int32_t* col_idx,
-               hipStream_t stream);
-int softmax_ce(const float* logits, int64_t n, int64_t m, const int32_t* target, float* loss, int32_t* argmax, float* dlogits,
-               hipStream_t stream);
-
 // local_loss.hip ---------------------------------------------------------------------------------
-// the whole KeypointCorrLoss of a batch of pairs (loss, metrics, six input gradients) in one fixed launch sequence
+// tile constants of egonn_local_loss that the tests read from here (tests/helpers.py: kernel_constant) to build their edge batches
 constexpr int LL_CLOUD_CHUNK = 1024;     // cloud points per workgroup of the keypoint -> cloud search
 constexpr int LL_STATS = 16;             // floats per row of out_pair / out_batch (= EGONN_LOCAL_LOSS_STATS)
-struct LocalLossArgs {
-  int pairs;
-  int64_t n_cloud1, n_cloud2, n_kp1, n_kp2;                       // totals over the batch (launch sizes)
-  const float *clouds1, *clouds2;                                 // (M,3)
-  const int32_t *cloud_off1, *cloud_off2, *kp_off1, *kp_off2;     // device (pairs+1)
-  const float *kp1, *sigma1, *desc1, *kp2, *sigma2, *desc2;       // (N,3) (N) (N,128)
-  const float* transforms;                                        // device (pairs,16)
-  const float* params;                                            // host: gamma_chamfer, gamma_p2p, gamma_c, gamma_k, beta, dist_th
-  float *out_pair, *out_batch;                                    // (pairs, LL_STATS), (LL_STATS)
-  float *g_kp1, *g_sigma1, *g_desc1, *g_kp2, *g_sigma2, *g_desc2; // all null: loss and metrics only
-  void* scratch;
-};
-bool local_loss_dim_supported(int dim);
-size_t local_loss_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2);
-int local_loss_forward(const LocalLossArgs& args, hipStream_t stream);
-
-// train.hip --------------------------------------------------------------------------------------
-// dW[k][ci][co] = sum_o in[nbr[o][k]][ci] * dout[o][co]; nbr == nullptr: identity map (K = 1, dense layer)
-// rg (nullable): the row-group form of the same map when it is built (the pair source of the MFMA kernel)
-int conv_wgrad(const float* in, const float* dout, const int32_t* nbr, int64_t n_out, int K, int cin, int cout,
-               float* dW, float* scratch, size_t scratch_floats, hipStream_t stream, const RowGroups* rg = nullptr);
-int conv0_wgrad(Ctx* ctx, const float* feat, const float* dout, float* dW, float* scratch, size_t scratch_floats,
-                hipStream_t stream);
-int col_stats(int mode, const float* a, const float* b, const float* mask, const float* m, int64_t n, int c, double* out2c,
-              float* scratch, size_t scratch_floats, hipStream_t stream);
-int bn_fwd_finalize(const double* sums, const float* m, double n, int c, const float* w, const float* b, float eps,
-                    float momentum, float* running_mean, float* running_var, float* out4, hipStream_t stream);
-int bn_bwd_finalize(const double* local, const double* global, double n, int c, const float* w, const float* mean,
-                    const float* invstd, float* out5, hipStream_t stream);
-int affine_act(const float* x, const float* A, const float* B, int64_t n, int c, int relu, float* out, hipStream_t stream);
-int affine3(const float* g, const float* mask, const float* x, const float* A, const float* B, const float* C, int64_t n,
-            int c, float* out, hipStream_t stream);
-int gate_residual_forward(const float* x, const float* gate, const float* res, const int32_t* boff, int B, int64_t n, int c,
-                          int relu, float* out, hipStream_t stream);
-int gate_residual_backward(const float* dout, const float* out, const float* gate, const int32_t* boff, int B, int64_t n,
-                           int c, float* dx, float* dres, hipStream_t stream);
-int seg_broadcast(const float* v, const int32_t* boff, int B, int64_t n, int c, int mean, float* out, hipStream_t stream);
-int seg_sums2(int mode, const float* a, const float* b, const float* x2, const float* p, const int32_t* boff, int B, int c,
-              float* out_bc, float* scratch, size_t scratch_floats, hipStream_t stream);
-int gem_backward_rows(const float* x, const float* coef, const float* p, const int32_t* boff, int B, int64_t n, int c,
-                      float* dx, hipStream_t stream);
-
-// SELayer.fc on the (B, c) per-sample means (layers/senet_block.py:39-49): gate = sigmoid(W2 relu(W1 mean + b1) + b2), h = c / 16
-int se_gate_forward(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, int B, int c, int h,
-                    float* gate, float* hidden_out, hipStream_t stream);
-int se_gate_backward(const float* dgate, const float* gate, const float* hid, const float* mean, const float* w1,
-                     const float* w2, int B, int c, int h, float* dmean, float* dw1, float* db1, float* dw2, float* db2,
-                     hipStream_t stream);
-int eca_gate_forward(const float* mean, const float* w, int ks, int B, int c, float* gate, hipStream_t stream);
-int eca_gate_backward(const float* dgate, const float* gate, const float* mean, const float* w, int ks, int B, int c,
-                      float* dmean, float* dw, hipStream_t stream);
-int act_backward(int act, const float* g, const float* y, int64_t n, int c, float* out, hipStream_t stream);
-// g == nullptr: out = normalize(x) ; else out = d normalize / dx applied to g
-int l2norm_rows(const float* x, const float* g, int64_t n, int c, float* out, hipStream_t stream);
-
-// retrieval.hip ----------------------------------------------------------------------------------
-int knn_search(const float* query, int32_t nq, const float* db, int32_t m, int d, int k, int32_t* out_idx, float* out_dist,
-               float* scratch, size_t scratch_floats, hipStream_t stream);
-int recall_counts(const int32_t* nn_idx, const float* qpos, const float* mpos, int32_t nq, int k, int pd,
-                  const float* radius, int nr, int32_t* tp, hipStream_t stream);
-
-// ingest.hip -------------------------------------------------------------------------------------
-size_t ingest_scratch_ints(int64_t n);
-int ingest_filter(const float* raw, int64_t n, int stride, const int64_t* raw_off_dev, int batch, int remove_zero,
-                  int remove_ground, float ground, float* out_xyz, int64_t* new_off_dev, int32_t* scratch,
-                  size_t scratch_ints, hipStream_t stream);
 
 }  // namespace egonn

@@ -14,8 +14,7 @@
 // Launches: prepare (kp1' = R kp1 + t, key / flag init) -> keypoint searches both ways -> keypoint -> cloud search, cloud
 // side split into LL_CLOUD_CHUNK-point chunks over workgroups -> logit row statistics -> per-pair finish (loss + metrics) ->
 // batch mean -> [gradients] d/d desc1, d/d desc2, d/d keypoints and sigmas (gathers in fixed partner order).
-#include "common.h"
-#include "kernels.h"
+#include "model.h"
 
 namespace egonn {
 
@@ -26,6 +25,7 @@ constexpr int LL_OWN = 32;               // descriptor rows a workgroup owns (8 
 constexpr int LL_OTH = 64;               // rows of the other side per step (one per lane)
 constexpr int LL_LD = LL_DIM + 4;        // LDS row stride in floats: 16-byte aligned, b128 reads of 16 consecutive rows hit 64 banks
 constexpr int LL_KP_SPLIT = 4;           // keypoint tiles of a pair are dealt over this many workgroups per cloud chunk
+static_assert(EGONN_LOCAL_LOSS_STATS == LL_STATS, "header and kernels disagree on the stats row");
 
 __device__ __forceinline__ int ll_segment(const int32_t* __restrict__ off, int pairs, int i) {   // off[p] <= i < off[p+1]
   int lo = 0, hi = pairs;
@@ -532,17 +532,49 @@ LLScratch ll_layout(int pairs, int64_t n1, int64_t n2) {
 
 }  // namespace
 
-bool local_loss_dim_supported(int dim) { return dim == LL_DIM; }
-
-size_t local_loss_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2) {
+static size_t ll_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2) {
   return ll_layout(pairs < 1 ? 1 : pairs, n_kp1 < 0 ? 0 : n_kp1, n_kp2 < 0 ? 0 : n_kp2).total;
 }
 
-int local_loss_forward(const LocalLossArgs& x, hipStream_t stream) {
-  const int pairs = x.pairs;
-  const int32_t N1 = (int32_t)x.n_kp1, N2 = (int32_t)x.n_kp2;
+API int64_t egonn_local_loss_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2, int dim) {
+  (void)dim;
+  return (int64_t)ll_scratch_bytes(pairs, n_kp1, n_kp2);
+}
+
+// clouds (M,3), keypoints (N,3) (N) (N,128) and their offsets (pairs+1) on the device, transforms (pairs,16); params on the HOST:
+// gamma_chamfer, gamma_p2p, gamma_c, gamma_k, beta, dist_th; out_pair (pairs, LL_STATS), out_batch (LL_STATS); the six gradient
+// outputs all null: loss and metrics only
+API int egonn_local_loss(int pairs, int64_t n_cloud1, int64_t n_cloud2, int64_t n_kp1, int64_t n_kp2, int dim,
+                         const float* clouds1, const int32_t* cloud_off1, const float* clouds2, const int32_t* cloud_off2,
+                         const float* kp1, const float* sigma1, const float* desc1, const int32_t* kp_off1,
+                         const float* kp2, const float* sigma2, const float* desc2, const int32_t* kp_off2,
+                         const float* transforms, const float* params, float* out_pair, float* out_batch,
+                         float* g_kp1, float* g_sigma1, float* g_desc1, float* g_kp2, float* g_sigma2, float* g_desc2,
+                         void* scratch, int64_t scratch_bytes, void* stream) {
+  // every check runs before anything touches the device
+  EGONN_REQUIRE(pairs >= 1 && pairs <= 4096, EGONN_ERR_INVALID, "local_loss: pairs=%d outside [1, 4096]", pairs);
+  EGONN_REQUIRE(dim == LL_DIM, EGONN_ERR_INVALID, "local_loss: descriptor width %d not supported (128)", dim);
+  const int64_t lim = (1ll << 31) / 128;       // row * 128 and cloud row * 3 stay inside int32 / the packed key
+  EGONN_REQUIRE(n_cloud1 >= 1 && n_cloud2 >= 1 && n_kp1 >= 1 && n_kp2 >= 1 && n_kp1 < lim && n_kp2 < lim &&
+                    n_cloud1 < (1ll << 31) / 3 && n_cloud2 < (1ll << 31) / 3 && n_kp1 + n_kp2 < (1ll << 31) - 256,
+                EGONN_ERR_INVALID, "local_loss: totals out of range (clouds %lld %lld, keypoints %lld %lld)",
+                (long long)n_cloud1, (long long)n_cloud2, (long long)n_kp1, (long long)n_kp2);
+  EGONN_REQUIRE(clouds1 && cloud_off1 && clouds2 && cloud_off2 && kp1 && sigma1 && desc1 && kp_off1 && kp2 && sigma2 && desc2 &&
+                    kp_off2 && transforms && params && out_pair && out_batch && scratch,
+                EGONN_ERR_INVALID, "local_loss: null argument");
+  const int ng = (g_kp1 != nullptr) + (g_sigma1 != nullptr) + (g_desc1 != nullptr) + (g_kp2 != nullptr) + (g_sigma2 != nullptr) +
+                 (g_desc2 != nullptr);
+  EGONN_REQUIRE(ng == 0 || ng == 6, EGONN_ERR_INVALID, "local_loss: the six gradient outputs are given together or not at all");
+  EGONN_REQUIRE((((uintptr_t)desc1 | (uintptr_t)desc2 | (uintptr_t)g_desc1 | (uintptr_t)g_desc2) & 15) == 0 &&
+                    ((uintptr_t)scratch & 255) == 0,
+                EGONN_ERR_INVALID, "local_loss: descriptors must be 16-byte aligned, scratch 256-byte aligned");
+  const int64_t need = (int64_t)ll_scratch_bytes(pairs, n_kp1, n_kp2);
+  EGONN_REQUIRE(scratch_bytes >= need, EGONN_ERR_INVALID, "local_loss: scratch of %lld bytes, %lld needed",
+                (long long)scratch_bytes, (long long)need);
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t N1 = (int32_t)n_kp1, N2 = (int32_t)n_kp2;
   const LLScratch L = ll_layout(pairs, N1, N2);
-  char* sc = (char*)x.scratch;
+  char* sc = (char*)scratch;
   float* kp1t = (float*)(sc + L.kp1t);
   auto* ckey1 = (unsigned long long*)(sc + L.ckey1);
   auto* ckey2 = (unsigned long long*)(sc + L.ckey2);
@@ -557,37 +589,37 @@ int local_loss_forward(const LocalLossArgs& x, hipStream_t stream) {
   float* md2 = (float*)(sc + L.md2);
   int32_t* iscls = (int32_t*)(sc + L.iscls);
   float* pairK = (float*)(sc + L.pairK);
-  const float gamma_chamfer = x.params[0], gamma_p2p = x.params[1], gamma_c = x.params[2], gamma_k = x.params[3];
-  const float scale = expf(x.params[4]), dist_th = x.params[5];
+  const float gamma_chamfer = params[0], gamma_p2p = params[1], gamma_c = params[2], gamma_k = params[3];
+  const float scale = expf(params[4]), dist_th = params[5];
 
   const unsigned flat = (unsigned)cdiv((int64_t)N1 + N2, 256);
-  hipLaunchKernelGGL(ll_prepare_kernel, dim3(flat), dim3(256), 0, stream, pairs, x.kp1, x.kp_off1, N1, N2, x.transforms, kp1t,
+  hipLaunchKernelGGL(ll_prepare_kernel, dim3(flat), dim3(256), 0, st, pairs, kp1, kp_off1, N1, N2, transforms, kp1t,
                      ckey1, ckey2, iscls);
-  hipLaunchKernelGGL(ll_kp_search_kernel, dim3(flat), dim3(256), 0, stream, pairs, kp1t, x.kp_off1, x.kp2, x.kp_off2, N1, N2,
+  hipLaunchKernelGGL(ll_kp_search_kernel, dim3(flat), dim3(256), 0, st, pairs, kp1t, kp_off1, kp2, kp_off2, N1, N2,
                      dist_th, ndx1, md1, tgt, ndx2, md2, iscls);
   // chunks of a side <= total / chunk + one partial chunk per pair
-  const int64_t chunks = cdiv(x.n_cloud1 > x.n_cloud2 ? x.n_cloud1 : x.n_cloud2, LL_CLOUD_CHUNK) + pairs;
-  hipLaunchKernelGGL(ll_cloud_search_kernel, dim3((unsigned)chunks, LL_KP_SPLIT, 2), dim3(256), 0, stream, pairs, x.clouds1,
-                     x.cloud_off1, x.clouds2, x.cloud_off2, x.kp1, x.kp_off1, x.kp2, x.kp_off2, ckey1, ckey2);
+  const int64_t chunks = cdiv(n_cloud1 > n_cloud2 ? n_cloud1 : n_cloud2, LL_CLOUD_CHUNK) + pairs;
+  hipLaunchKernelGGL(ll_cloud_search_kernel, dim3((unsigned)chunks, LL_KP_SPLIT, 2), dim3(256), 0, st, pairs, clouds1,
+                     cloud_off1, clouds2, cloud_off2, kp1, kp_off1, kp2, kp_off2, ckey1, ckey2);
   const unsigned tiles1 = (unsigned)(cdiv(N1, LL_OWN) + pairs), tiles2 = (unsigned)(cdiv(N2, LL_OWN) + pairs);
-  hipLaunchKernelGGL(ll_corr_kernel<0>, dim3(tiles1), dim3(256), 0, stream, pairs, x.desc1, x.desc2, x.kp_off1, x.kp_off2, tgt,
+  hipLaunchKernelGGL(ll_corr_kernel<0>, dim3(tiles1), dim3(256), 0, st, pairs, desc1, desc2, kp_off1, kp_off2, tgt,
                      iscls, scale, 0.f, lse, rowloss, amax, negmax, (const float*)nullptr, (float*)nullptr);
   LLArgs a;
-  a.pairs = pairs; a.N1 = N1; a.N2 = N2; a.M1 = (int32_t)x.n_cloud1; a.M2 = (int32_t)x.n_cloud2;
-  a.c1 = x.clouds1; a.c2 = x.clouds2; a.kp1 = x.kp1; a.kp2 = x.kp2; a.s1 = x.sigma1; a.s2 = x.sigma2; a.T = x.transforms;
-  a.coff1 = x.cloud_off1; a.coff2 = x.cloud_off2; a.off1 = x.kp_off1; a.off2 = x.kp_off2;
+  a.pairs = pairs; a.N1 = N1; a.N2 = N2; a.M1 = (int32_t)n_cloud1; a.M2 = (int32_t)n_cloud2;
+  a.c1 = clouds1; a.c2 = clouds2; a.kp1 = kp1; a.kp2 = kp2; a.s1 = sigma1; a.s2 = sigma2; a.T = transforms;
+  a.coff1 = cloud_off1; a.coff2 = cloud_off2; a.off1 = kp_off1; a.off2 = kp_off2;
   a.kp1t = kp1t; a.ndx1 = ndx1; a.ndx2 = ndx2; a.tgt = tgt; a.amax = amax;
   a.md1 = md1; a.md2 = md2; a.rowloss = rowloss; a.negmax = negmax; a.ckey1 = ckey1; a.ckey2 = ckey2;
   a.gamma_chamfer = gamma_chamfer; a.gamma_p2p = gamma_p2p; a.gamma_c = gamma_c; a.gamma_k = gamma_k; a.dist_th = dist_th;
-  hipLaunchKernelGGL(ll_finish_kernel, dim3(pairs), dim3(256), 0, stream, a, x.out_pair, pairK);
-  hipLaunchKernelGGL(ll_batch_mean_kernel, dim3(1), dim3(64), 0, stream, pairs, (const float*)x.out_pair, x.out_batch);
-  if (x.g_kp1) {
+  hipLaunchKernelGGL(ll_finish_kernel, dim3(pairs), dim3(256), 0, st, a, out_pair, pairK);
+  hipLaunchKernelGGL(ll_batch_mean_kernel, dim3(1), dim3(64), 0, st, pairs, (const float*)out_pair, out_batch);
+  if (g_kp1) {
     const float coef = gamma_c * scale / (float)pairs;
-    hipLaunchKernelGGL(ll_corr_kernel<1>, dim3(tiles1), dim3(256), 0, stream, pairs, x.desc1, x.desc2, x.kp_off1, x.kp_off2, tgt,
-                       iscls, scale, coef, lse, rowloss, amax, negmax, (const float*)pairK, x.g_desc1);
-    hipLaunchKernelGGL(ll_corr_kernel<2>, dim3(tiles2), dim3(256), 0, stream, pairs, x.desc1, x.desc2, x.kp_off1, x.kp_off2, tgt,
-                       iscls, scale, coef, lse, rowloss, amax, negmax, (const float*)pairK, x.g_desc2);
-    hipLaunchKernelGGL(ll_point_grad_kernel, dim3(flat), dim3(256), 0, stream, a, x.g_kp1, x.g_sigma1, x.g_kp2, x.g_sigma2);
+    hipLaunchKernelGGL(ll_corr_kernel<1>, dim3(tiles1), dim3(256), 0, st, pairs, desc1, desc2, kp_off1, kp_off2, tgt,
+                       iscls, scale, coef, lse, rowloss, amax, negmax, (const float*)pairK, g_desc1);
+    hipLaunchKernelGGL(ll_corr_kernel<2>, dim3(tiles2), dim3(256), 0, st, pairs, desc1, desc2, kp_off1, kp_off2, tgt,
+                       iscls, scale, coef, lse, rowloss, amax, negmax, (const float*)pairK, g_desc2);
+    hipLaunchKernelGGL(ll_point_grad_kernel, dim3(flat), dim3(256), 0, st, a, g_kp1, g_sigma1, g_kp2, g_sigma2);
   }
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;

@@ -12,8 +12,7 @@
 //   l_i       = relu(D[i][p] - min(D[i][n], D[p][n]) + margin)          (swap=True)
 //   loss      = mean of the l_i > 0  (0 if none)                         (AvgNonZeroReducer)
 // Also returns dLoss/dE (deterministic gather formulation) so that each rank can back-propagate its own rows.
-#include "common.h"
-#include "kernels.h"
+#include "model.h"
 
 namespace egonn {
 
@@ -174,22 +173,24 @@ __global__ __launch_bounds__(256) void triplet_grad_kernel(const float* __restri
   }
 }
 
-size_t triplet_loss_scratch_floats(int n) { return (size_t)n * n + 4 * (size_t)n + 64; }
+API int64_t egonn_triplet_loss_scratch_floats(int n) { return (int64_t)((size_t)n * n + 4 * (size_t)n + 64); }
 
-int triplet_loss_forward(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float margin,
-                         float* out10, int32_t* triplets, float* grad, float* scratch, hipStream_t stream) {
+API int egonn_triplet_loss(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float margin, float* out10,
+                           int32_t* triplets, float* grad, float* scratch, void* stream) {
+  EGONN_REQUIRE(emb && pos && neg && out10 && triplets && scratch, EGONN_ERR_INVALID, "triplet_loss: null argument");
   EGONN_REQUIRE(n >= 1 && d >= 1 && d <= 4096, EGONN_ERR_INVALID, "triplet loss: n=%d d=%d out of range", n, d);
+  hipStream_t st = (hipStream_t)stream;
   float* D = scratch;
   float* norms = D + (size_t)n * n;
   float* hp = norms + n;
   float* hn = hp + n;
   float* li = hn + n;
-  hipLaunchKernelGGL(pdist_kernel, dim3(n), dim3(256), d * sizeof(float), stream, emb, n, d, D, norms);
-  hipLaunchKernelGGL(mine_kernel, dim3(n), dim3(256), 0, stream, D, pos, neg, n, triplets, hp, hn);
-  hipLaunchKernelGGL(triplet_loss_kernel, dim3(1), dim3(256), 0, stream, D, triplets, hp, hn, norms, n, margin, li,
+  hipLaunchKernelGGL(pdist_kernel, dim3(n), dim3(256), d * sizeof(float), st, emb, n, d, D, norms);
+  hipLaunchKernelGGL(mine_kernel, dim3(n), dim3(256), 0, st, D, pos, neg, n, triplets, hp, hn);
+  hipLaunchKernelGGL(triplet_loss_kernel, dim3(1), dim3(256), 0, st, D, triplets, hp, hn, norms, n, margin, li,
                      out10);
   if (grad)
-    hipLaunchKernelGGL(triplet_grad_kernel, dim3(n), dim3(256), 0, stream, emb, D, triplets, li, out10, n, d, grad);
+    hipLaunchKernelGGL(triplet_grad_kernel, dim3(n), dim3(256), 0, st, emb, D, triplets, li, out10, n, d, grad);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -290,24 +291,25 @@ __global__ __launch_bounds__(256) void contrastive_grad_kernel(const float* __re
   }
 }
 
-size_t contrastive_loss_scratch_floats(int n) { return (size_t)n * n + 5 * (size_t)n + 64; }
+API int64_t egonn_contrastive_loss_scratch_floats(int n) { return (int64_t)((size_t)n * n + 5 * (size_t)n + 64); }
 
-int contrastive_loss_forward(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float pos_margin,
-                             float neg_margin, float* out13, int32_t* triplets, float* grad, float* scratch,
-                             hipStream_t stream) {
+API int egonn_contrastive_loss(const float* emb, int n, int d, const uint8_t* pos, const uint8_t* neg, float pos_margin,
+                               float neg_margin, float* out13, int32_t* triplets, float* grad, float* scratch, void* stream) {
+  EGONN_REQUIRE(emb && pos && neg && out13 && triplets && scratch, EGONN_ERR_INVALID, "contrastive_loss: null argument");
   EGONN_REQUIRE(n >= 1 && d >= 1 && d <= 4096, EGONN_ERR_INVALID, "contrastive loss: n=%d d=%d out of range", n, d);
+  hipStream_t st = (hipStream_t)stream;
   float* D = scratch;
   float* norms = D + (size_t)n * n;
   float* hp = norms + n;
   float* hn = hp + n;
   float* lp = hn + n;
   float* ln = lp + n;
-  hipLaunchKernelGGL(pdist_kernel, dim3(n), dim3(256), d * sizeof(float), stream, emb, n, d, D, norms);
-  hipLaunchKernelGGL(mine_kernel, dim3(n), dim3(256), 0, stream, D, pos, neg, n, triplets, hp, hn);
-  hipLaunchKernelGGL(contrastive_loss_kernel, dim3(1), dim3(256), 0, stream, D, triplets, hp, hn, norms, n, pos_margin,
+  hipLaunchKernelGGL(pdist_kernel, dim3(n), dim3(256), d * sizeof(float), st, emb, n, d, D, norms);
+  hipLaunchKernelGGL(mine_kernel, dim3(n), dim3(256), 0, st, D, pos, neg, n, triplets, hp, hn);
+  hipLaunchKernelGGL(contrastive_loss_kernel, dim3(1), dim3(256), 0, st, D, triplets, hp, hn, norms, n, pos_margin,
                      neg_margin, lp, ln, out13);
   if (grad)
-    hipLaunchKernelGGL(contrastive_grad_kernel, dim3(n), dim3(256), 0, stream, emb, D, triplets, lp, ln, out13, n, d, grad);
+    hipLaunchKernelGGL(contrastive_grad_kernel, dim3(n), dim3(256), 0, st, emb, D, triplets, lp, ln, out13, n, d, grad);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -359,11 +361,13 @@ __global__ __launch_bounds__(256) void nn_search_kernel(const float* __restrict_
     out_idx[i] = bi;
   }
 }
-int nn_search(const float* a, int64_t n, const float* M, const float* b, int64_t m, float* out_dist, int32_t* out_idx,
-              hipStream_t stream) {
+API int egonn_nn_search(const float* a, int64_t n, const float* M, const float* b, int64_t m, float* out_dist, int32_t* out_idx,
+                        void* stream) {
+  EGONN_REQUIRE(a && b && out_dist && out_idx, EGONN_ERR_INVALID, "nn_search: null argument");
   EGONN_REQUIRE(n >= 0 && m >= 1 && n < (1ll << 31) && m < (1ll << 31), EGONN_ERR_INVALID, "nn_search: bad sizes");
+  hipStream_t st = (hipStream_t)stream;
   if (n == 0) return EGONN_OK;
-  hipLaunchKernelGGL(nn_search_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, a, (int32_t)n, M, b, (int32_t)m,
+  hipLaunchKernelGGL(nn_search_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, a, (int32_t)n, M, b, (int32_t)m,
                      out_dist, out_idx);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
@@ -403,12 +407,14 @@ __global__ void matrix_min_cols_kernel(const float* __restrict__ d, int32_t n, i
   vmin[c] = best;
   imin[c] = bi;
 }
-int matrix_min(const float* d, int64_t n, int64_t m, float* row_min, int32_t* row_idx, float* col_min, int32_t* col_idx,
-               hipStream_t stream) {
+API int egonn_matrix_min(const float* d, int64_t n, int64_t m, float* row_min, int32_t* row_idx, float* col_min, int32_t* col_idx,
+                         void* stream) {
+  EGONN_REQUIRE(d && row_min && row_idx && col_min && col_idx, EGONN_ERR_INVALID, "matrix_min: null argument");
   EGONN_REQUIRE(n >= 1 && m >= 1 && n < (1ll << 31) && m < (1ll << 31), EGONN_ERR_INVALID, "matrix_min: bad sizes");
-  hipLaunchKernelGGL(matrix_min_rows_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, stream, d, (int32_t)n, (int32_t)m,
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(matrix_min_rows_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, d, (int32_t)n, (int32_t)m,
                      row_min, row_idx);
-  hipLaunchKernelGGL(matrix_min_cols_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, stream, d, (int32_t)n, (int32_t)m,
+  hipLaunchKernelGGL(matrix_min_cols_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, st, d, (int32_t)n, (int32_t)m,
                      col_min, col_idx);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
@@ -452,11 +458,13 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict
       dlogits[(int64_t)r * m + j] = (t >= 0) ? (expf(row[j] - mx) * inv - (j == t ? 1.f : 0.f)) : 0.f;
   }
 }
-int softmax_ce(const float* logits, int64_t n, int64_t m, const int32_t* target, float* loss, int32_t* argmax, float* dlogits,
-               hipStream_t stream) {
+API int egonn_softmax_cross_entropy(const float* logits, int64_t n, int64_t m, const int32_t* target, float* loss,
+                                    int32_t* argmax, float* dlogits, void* stream) {
+  EGONN_REQUIRE(logits && target && loss && argmax, EGONN_ERR_INVALID, "softmax_cross_entropy: null argument");
   EGONN_REQUIRE(n >= 0 && m >= 1 && n < (1ll << 31) && m < (1ll << 31), EGONN_ERR_INVALID, "softmax_ce: bad sizes");
+  hipStream_t st = (hipStream_t)stream;
   if (n == 0) return EGONN_OK;
-  hipLaunchKernelGGL(softmax_ce_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, stream, logits, (int32_t)n, (int32_t)m,
+  hipLaunchKernelGGL(softmax_ce_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, st, logits, (int32_t)n, (int32_t)m,
                      target, loss, argmax, dlogits);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;

@@ -10,8 +10,6 @@
 
 using namespace egonn;
 
-#define API extern "C" __attribute__((visibility("default")))
-
 namespace egonn {
 
 static constexpr int FPN_MAX_LEVELS = 7;

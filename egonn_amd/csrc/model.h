@@ -1,5 +1,6 @@
 // What the translation units behind the model entry points share (model.hip: EgoNN, minkfpn.hip: MinkLoc / MinkLoc3D): the
 // context and model objects of the C ABI, the state_dict lookups and the one way a graph launches a sparse convolution.
+// Every file that defines an entry point includes it: the C header, the context behind egonn_ctx and its opening checks.
 #pragma once
 #include <map>
 #include <string>
@@ -18,6 +19,15 @@ struct egonn_ctx : public egonn::Ctx {
   int level_bf16 = 0;                // precision of level_feat (last forward)
   bool from_points = false;
 };
+
+// the checks every entry point that reads the plan of a context starts with
+#define REQUIRE_PLAN(c)                                                                               \
+  EGONN_REQUIRE((c) && (c)->plan.valid, EGONN_ERR_STATE, "no coordinate plan (call egonn_voxelize / " \
+                                                         "egonn_coords_set first)")
+#define REQUIRE_LEVEL(c, level)                                                                              \
+  REQUIRE_PLAN(c);                                                                                           \
+  HIP_CHECK(hipSetDevice((c)->device));                                                                      \
+  EGONN_REQUIRE((level) >= 0 && (level) < EGONN_NUM_LEVELS, EGONN_ERR_INVALID, "level %d out of range", (level))
 
 namespace egonn {
 

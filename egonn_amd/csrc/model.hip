@@ -8,8 +8,6 @@
 
 using namespace egonn;
 
-#define API extern "C" __attribute__((visibility("default")))
-
 namespace {
 
 const int PLANES[7] = {32, 64, 64, 128, 128, 128, 128};   // models/model_factory.py:40
@@ -213,10 +211,6 @@ API int egonn_coords_set(egonn_ctx* c, const int32_t* coords, int64_t n, int B, 
   c->from_points = false;
   return EGONN_OK;
 }
-
-#define REQUIRE_PLAN(c)                                                                               \
-  EGONN_REQUIRE((c) && (c)->plan.valid, EGONN_ERR_STATE, "no coordinate plan (call egonn_voxelize / " \
-                                                         "egonn_coords_set first)")
 
 API int egonn_level_count(egonn_ctx* c, int level, int64_t* n) {
   REQUIRE_PLAN(c);
@@ -481,6 +475,15 @@ API int egonn_add(const float* a, const float* b, int64_t n, float* out, void* s
   return add_act(a, b, n, 0, out, (hipStream_t)stream);
 }
 
+// out = act(x @ W + bias) of a stand-alone Linear / 1x1 layer (W in ME kernel or nn.Linear layout)
+API int egonn_dense(const float* x, int64_t n, int cin, const float* weight, int weight_out_in, const float* bias, int cout,
+                    int act, float* out, void* stream) {
+  EGONN_REQUIRE(x && weight && out && n >= 0 && cin >= 1 && cout >= 1 && act >= 0 && act <= 4, EGONN_ERR_INVALID,
+                "dense: bad arguments");
+  return dense_forward(x, n, cin, weight, weight_out_in ? 1 : 0, cout, bias, nullptr, nullptr, act, nullptr, out,
+                       (hipStream_t)stream);
+}
+
 // Features handed in in the caller's row order -> plan (Z-order) row order: out[i] = features[input_index[i]]
 API int egonn_gather_input(egonn_ctx* c, const float* features, int channels, float* out, void* stream) {
   REQUIRE_PLAN(c);
@@ -551,101 +554,6 @@ API int egonn_netvlad(egonn_ctx* c, int level, const float* x, int channels, con
   return netvlad_forward(x, c->plan.lv[level].boff, B, channels, cluster_weights, cluster_weights2, bn1_scale, bn1_shift,
                          hidden1_weights, out_dim, bn2_scale, bn2_shift, gating_weights, gate_scale, gate_shift, gating, out,
                          ws, (hipStream_t)stream);
-}
-
-// Train-mode NetVLAD core over the rows of `level` (netvlad_train.hip): bn1 on the statistics of the M = B * nmax zero-padded
-// rows, y = vlad @ H (B, out_dim) BEFORE bn2; what the backward needs goes to the caller's save_* buffers
-static int netvlad_train_check(egonn_ctx* c, int level, int channels, int out_dim, int nmax) {
-  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS, EGONN_ERR_INVALID, "netvlad_train: level %d out of range", level);
-  EGONN_REQUIRE(channels >= 16 && channels <= 512 && channels % 16 == 0, EGONN_ERR_INVALID,
-                "netvlad_train: %d channels unsupported (multiple of 16, 16..512)", channels);
-  EGONN_REQUIRE(out_dim >= 16 && out_dim <= 1024 && out_dim % 16 == 0, EGONN_ERR_INVALID,
-                "netvlad_train: output_dim %d unsupported (multiple of 16, 16..1024)", out_dim);
-  EGONN_REQUIRE(c->plan.batch >= 2, EGONN_ERR_INVALID, "netvlad_train: batch statistics need at least 2 scans");
-  EGONN_REQUIRE(c->plan.lv[level].n >= 1 && nmax >= 1 && (int64_t)nmax * c->plan.batch >= c->plan.lv[level].n,
-                EGONN_ERR_INVALID, "netvlad_train: nmax %d is not the largest scan of the level", nmax);
-  return EGONN_OK;
-}
-
-API int egonn_netvlad_train_forward(egonn_ctx* c, int level, const float* x, int channels, int nmax,
-                                    const float* cluster_weights, const float* cluster_weights2, const float* bn1_weight,
-                                    const float* bn1_bias, float bn1_eps, float bn1_momentum, float* bn1_running_mean,
-                                    float* bn1_running_var, const float* hidden1_weights, int out_dim, float* out, float* save_z,
-                                    float* save_bn1, float* save_v, float* save_sq, float* save_asum, void* stream) {
-  REQUIRE_PLAN(c);
-  EGONN_TRY(netvlad_train_check(c, level, channels, out_dim, nmax));
-  EGONN_REQUIRE(x && cluster_weights && cluster_weights2 && bn1_weight && bn1_bias && bn1_running_mean && bn1_running_var &&
-                    hidden1_weights && out && save_z && save_bn1 && save_v && save_sq && save_asum,
-                EGONN_ERR_INVALID, "netvlad_train_forward: null argument");
-  EGONN_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)save_z & 15) == 0, EGONN_ERR_INVALID,
-                "netvlad_train_forward: x and save_z must be 16-byte aligned");
-  HIP_CHECK(hipSetDevice(c->device));
-  const int B = c->plan.batch;
-  const int64_t N = c->plan.lv[level].n;
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
-  const size_t nws = netvlad_train_forward_floats(B, N, channels, out_dim);
-  EGONN_TRY(c->work_arena.ensure(nws * 4 + 4096));
-  c->work_arena.reset();
-  float* ws = c->work_arena.alloc<float>(nws);
-  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
-  return netvlad_train_forward(x, c->plan.lv[level].boff, B, N, channels, nmax, cluster_weights, cluster_weights2, bn1_weight,
-                               bn1_bias, bn1_eps, bn1_momentum, bn1_running_mean, bn1_running_var, hidden1_weights, out_dim, out,
-                               save_z, save_bn1, save_v, save_sq, save_asum, ws, (hipStream_t)stream);
-}
-
-API int egonn_netvlad_train_backward(egonn_ctx* c, int level, const float* x, int channels, int nmax,
-                                     const float* cluster_weights, const float* cluster_weights2, const float* bn1_weight,
-                                     const float* hidden1_weights, int out_dim, const float* grad_out, const float* save_z,
-                                     const float* save_bn1, const float* save_v, const float* save_sq, const float* save_asum,
-                                     float* grad_x, float* grad_cluster_weights, float* grad_cluster_weights2, float* out_bn1,
-                                     float* grad_hidden1_weights, void* stream) {
-  REQUIRE_PLAN(c);
-  EGONN_TRY(netvlad_train_check(c, level, channels, out_dim, nmax));
-  EGONN_REQUIRE(x && cluster_weights && cluster_weights2 && bn1_weight && hidden1_weights && grad_out && save_z && save_bn1 &&
-                    save_v && save_sq && save_asum && grad_x && grad_cluster_weights && grad_cluster_weights2 && out_bn1 &&
-                    grad_hidden1_weights,
-                EGONN_ERR_INVALID, "netvlad_train_backward: null argument");
-  EGONN_REQUIRE(((uintptr_t)x & 15) == 0, EGONN_ERR_INVALID, "netvlad_train_backward: x must be 16-byte aligned");
-  HIP_CHECK(hipSetDevice(c->device));
-  const int B = c->plan.batch;
-  const int64_t N = c->plan.lv[level].n;
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
-  const size_t nws = netvlad_train_backward_floats(B, N, channels, out_dim);
-  EGONN_TRY(c->work_arena.ensure(nws * 4 + 4096));
-  c->work_arena.reset();
-  float* ws = c->work_arena.alloc<float>(nws);
-  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
-  return netvlad_train_backward(x, save_z, c->plan.lv[level].boff, B, N, channels, nmax, cluster_weights, cluster_weights2,
-                                bn1_weight, save_bn1, hidden1_weights, out_dim, grad_out, save_v, save_sq, save_asum, grad_x,
-                                grad_cluster_weights, grad_cluster_weights2, out_bn1, grad_hidden1_weights, ws,
-                                (hipStream_t)stream);
-}
-
-// MAC with the winning plan row of every (scan, channel) (ties: lowest row; empty scan: 0 and row -1), and its backward
-API int egonn_global_max_pool_argmax(egonn_ctx* c, int level, const float* in, int channels, float* out, int32_t* out_rows,
-                                     void* stream) {
-  REQUIRE_PLAN(c);
-  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && in && out && out_rows && channels >= 1, EGONN_ERR_INVALID,
-                "global_max_pool_argmax: bad argument");
-  HIP_CHECK(hipSetDevice(c->device));
-  return global_max_argmax(in, c->plan.lv[level].boff, c->plan.batch, channels, out, out_rows, (hipStream_t)stream);
-}
-
-API int egonn_global_max_pool_backward(egonn_ctx* c, int level, const float* grad_out, const int32_t* rows, int channels,
-                                       float* grad_in, void* stream) {
-  REQUIRE_PLAN(c);
-  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && grad_out && rows && grad_in && channels >= 1, EGONN_ERR_INVALID,
-                "global_max_pool_backward: bad argument");
-  HIP_CHECK(hipSetDevice(c->device));
-  return global_max_backward(grad_out, rows, c->plan.batch, c->plan.lv[level].n, channels, grad_in, (hipStream_t)stream);
-}
-
-// out = y * sigmoid(t) (grad_out NULL), or its backward: grad_y = grad_out * s, grad_t = grad_out * y * s * (1 - s)
-API int egonn_sigmoid_gate(const float* y, const float* t, const float* grad_out, int64_t n, float* out, float* grad_y,
-                           float* grad_t, void* stream) {
-  EGONN_REQUIRE(y && t && n >= 0 && (grad_out ? (grad_y && grad_t) : out != nullptr), EGONN_ERR_INVALID,
-                "sigmoid_gate: bad argument");
-  return sigmoid_gate(y, t, grad_out, n, out, grad_y, grad_t, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------ model
@@ -1232,283 +1140,4 @@ API int egonn_profile_fetch(egonn_ctx* c, int cap, int* n, char* names, float* m
   c->prof.recs.clear();
   *n = w;
   return EGONN_OK;
-}
-
-
-// ------------------------------------------------------------------------------------------ batch-hard contrastive loss
-API int64_t egonn_contrastive_loss_scratch_floats(int n) { return (int64_t)contrastive_loss_scratch_floats(n); }
-
-API int egonn_contrastive_loss(const float* embeddings, int n, int d, const uint8_t* positives_mask,
-                               const uint8_t* negatives_mask, float pos_margin, float neg_margin, float* out_stats,
-                               int32_t* out_triplets, float* out_grad, float* scratch, void* stream) {
-  EGONN_REQUIRE(embeddings && positives_mask && negatives_mask && out_stats && out_triplets && scratch, EGONN_ERR_INVALID,
-                "contrastive_loss: null argument");
-  return contrastive_loss_forward(embeddings, n, d, positives_mask, negatives_mask, pos_margin, neg_margin, out_stats,
-                                  out_triplets, out_grad, scratch, (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------------------------------ batch-hard triplet loss
-API int64_t egonn_triplet_loss_scratch_floats(int n) { return (int64_t)triplet_loss_scratch_floats(n); }
-
-API int egonn_triplet_loss(const float* embeddings, int n, int d, const uint8_t* positives_mask,
-                           const uint8_t* negatives_mask, float margin, float* out_stats, int32_t* out_triplets,
-                           float* out_grad, float* scratch, void* stream) {
-  EGONN_REQUIRE(embeddings && positives_mask && negatives_mask && out_stats && out_triplets && scratch, EGONN_ERR_INVALID,
-                "triplet_loss: null argument");
-  return triplet_loss_forward(embeddings, n, d, positives_mask, negatives_mask, margin, out_stats, out_triplets, out_grad,
-                              scratch, (hipStream_t)stream);
-}
-
-
-// ------------------------------------------------------------------------------------------ local-head losses
-API int egonn_nn_search(const float* a, int64_t n, const float* transform, const float* b, int64_t m, float* out_dist,
-                        int32_t* out_index, void* stream) {
-  EGONN_REQUIRE(a && b && out_dist && out_index, EGONN_ERR_INVALID, "nn_search: null argument");
-  return nn_search(a, n, transform, b, m, out_dist, out_index, (hipStream_t)stream);
-}
-API int egonn_matrix_min(const float* d, int64_t n, int64_t m, float* row_min, int32_t* row_index, float* col_min,
-                         int32_t* col_index, void* stream) {
-  EGONN_REQUIRE(d && row_min && row_index && col_min && col_index, EGONN_ERR_INVALID, "matrix_min: null argument");
-  return matrix_min(d, n, m, row_min, row_index, col_min, col_index, (hipStream_t)stream);
-}
-API int egonn_softmax_cross_entropy(const float* logits, int64_t n, int64_t m, const int32_t* target, float* out_loss,
-                                    int32_t* out_argmax, float* out_dlogits, void* stream) {
-  EGONN_REQUIRE(logits && target && out_loss && out_argmax, EGONN_ERR_INVALID, "softmax_cross_entropy: null argument");
-  return softmax_ce(logits, n, m, target, out_loss, out_argmax, out_dlogits, (hipStream_t)stream);
-}
-static_assert(EGONN_LOCAL_LOSS_STATS == LL_STATS, "header and kernels disagree on the stats row");
-API int64_t egonn_local_loss_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2, int dim) {
-  (void)dim;
-  return (int64_t)local_loss_scratch_bytes(pairs, n_kp1, n_kp2);
-}
-API int egonn_local_loss(int pairs, int64_t n_cloud1, int64_t n_cloud2, int64_t n_kp1, int64_t n_kp2, int dim,
-                         const float* clouds1, const int32_t* cloud_off1, const float* clouds2, const int32_t* cloud_off2,
-                         const float* kp1, const float* sigma1, const float* desc1, const int32_t* kp_off1,
-                         const float* kp2, const float* sigma2, const float* desc2, const int32_t* kp_off2,
-                         const float* transforms, const float* params, float* out_pair, float* out_batch,
-                         float* g_kp1, float* g_sigma1, float* g_desc1, float* g_kp2, float* g_sigma2, float* g_desc2,
-                         void* scratch, int64_t scratch_bytes, void* stream) {
-  // every check runs before anything touches the device
-  EGONN_REQUIRE(pairs >= 1 && pairs <= 4096, EGONN_ERR_INVALID, "local_loss: pairs=%d outside [1, 4096]", pairs);
-  EGONN_REQUIRE(local_loss_dim_supported(dim), EGONN_ERR_INVALID, "local_loss: descriptor width %d not supported (128)", dim);
-  const int64_t lim = (1ll << 31) / 128;       // row * 128 and cloud row * 3 stay inside int32 / the packed key
-  EGONN_REQUIRE(n_cloud1 >= 1 && n_cloud2 >= 1 && n_kp1 >= 1 && n_kp2 >= 1 && n_kp1 < lim && n_kp2 < lim &&
-                    n_cloud1 < (1ll << 31) / 3 && n_cloud2 < (1ll << 31) / 3 && n_kp1 + n_kp2 < (1ll << 31) - 256,
-                EGONN_ERR_INVALID, "local_loss: totals out of range (clouds %lld %lld, keypoints %lld %lld)",
-                (long long)n_cloud1, (long long)n_cloud2, (long long)n_kp1, (long long)n_kp2);
-  EGONN_REQUIRE(clouds1 && cloud_off1 && clouds2 && cloud_off2 && kp1 && sigma1 && desc1 && kp_off1 && kp2 && sigma2 && desc2 &&
-                    kp_off2 && transforms && params && out_pair && out_batch && scratch,
-                EGONN_ERR_INVALID, "local_loss: null argument");
-  const int ng = (g_kp1 != nullptr) + (g_sigma1 != nullptr) + (g_desc1 != nullptr) + (g_kp2 != nullptr) + (g_sigma2 != nullptr) +
-                 (g_desc2 != nullptr);
-  EGONN_REQUIRE(ng == 0 || ng == 6, EGONN_ERR_INVALID, "local_loss: the six gradient outputs are given together or not at all");
-  EGONN_REQUIRE((((uintptr_t)desc1 | (uintptr_t)desc2 | (uintptr_t)g_desc1 | (uintptr_t)g_desc2) & 15) == 0 &&
-                    ((uintptr_t)scratch & 255) == 0,
-                EGONN_ERR_INVALID, "local_loss: descriptors must be 16-byte aligned, scratch 256-byte aligned");
-  const int64_t need = (int64_t)local_loss_scratch_bytes(pairs, n_kp1, n_kp2);
-  EGONN_REQUIRE(scratch_bytes >= need, EGONN_ERR_INVALID, "local_loss: scratch of %lld bytes, %lld needed",
-                (long long)scratch_bytes, (long long)need);
-  LocalLossArgs a;
-  a.pairs = pairs; a.n_cloud1 = n_cloud1; a.n_cloud2 = n_cloud2; a.n_kp1 = n_kp1; a.n_kp2 = n_kp2;
-  a.clouds1 = clouds1; a.clouds2 = clouds2; a.cloud_off1 = cloud_off1; a.cloud_off2 = cloud_off2; a.kp_off1 = kp_off1;
-  a.kp_off2 = kp_off2; a.kp1 = kp1; a.sigma1 = sigma1; a.desc1 = desc1; a.kp2 = kp2; a.sigma2 = sigma2; a.desc2 = desc2;
-  a.transforms = transforms; a.params = params; a.out_pair = out_pair; a.out_batch = out_batch;
-  a.g_kp1 = g_kp1; a.g_sigma1 = g_sigma1; a.g_desc1 = g_desc1; a.g_kp2 = g_kp2; a.g_sigma2 = g_sigma2; a.g_desc2 = g_desc2;
-  a.scratch = scratch;
-  return local_loss_forward(a, (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------------------------------ training-mode operators
-#define REQUIRE_LEVEL(c, level)                                                                              \
-  REQUIRE_PLAN(c);                                                                                           \
-  HIP_CHECK(hipSetDevice((c)->device));                                                                      \
-  EGONN_REQUIRE((level) >= 0 && (level) < EGONN_NUM_LEVELS, EGONN_ERR_INVALID, "level %d out of range", (level))
-
-API int egonn_dense(const float* x, int64_t n, int cin, const float* weight, int weight_out_in, const float* bias, int cout,
-                    int act, float* out, void* stream) {
-  EGONN_REQUIRE(x && weight && out && n >= 0 && cin >= 1 && cout >= 1 && act >= 0 && act <= 4, EGONN_ERR_INVALID,
-                "dense: bad arguments");
-  return dense_forward(x, n, cin, weight, weight_out_in ? 1 : 0, cout, bias, nullptr, nullptr, act, nullptr, out,
-                       (hipStream_t)stream);
-}
-
-API int egonn_dense_backward_weight(const float* a, int ca, const float* b, int cb, int64_t n, float* out, float* scratch,
-                                    int64_t scratch_floats, void* stream) {
-  EGONN_REQUIRE(a && b && out && ca >= 1 && cb >= 1 && n >= 0, EGONN_ERR_INVALID, "dense_backward_weight: bad arguments");
-  return conv_wgrad(a, b, nullptr, n, 1, ca, cb, out, scratch, (size_t)scratch_floats, (hipStream_t)stream);
-}
-
-API int egonn_conv_backward_weight(egonn_ctx* c, int level_in, int level_out, int ks, int transposed, const float* in,
-                                   int cin, const float* grad_out, int cout, float* grad_kernel, float* scratch,
-                                   int64_t scratch_floats, void* stream) {
-  REQUIRE_LEVEL(c, level_in);
-  EGONN_REQUIRE(level_out >= 0 && level_out < EGONN_NUM_LEVELS, EGONN_ERR_INVALID, "level %d out of range", level_out);
-  EGONN_REQUIRE(grad_out && grad_kernel, EGONN_ERR_INVALID, "conv_backward_weight: null argument");
-  hipStream_t st = (hipStream_t)stream;
-  const Plan& P = c->plan;
-  if (ks == 5) {
-    EGONN_REQUIRE(level_in == 0 && level_out == 0 && cin == 1 && cout == 32 && !transposed, EGONN_ERR_INVALID,
-                  "conv_backward_weight: k=5 is the 1->32 input layer only");
-    return conv0_wgrad(c, in, grad_out, grad_kernel, scratch, (size_t)scratch_floats, st);   // in == NULL: all ones
-  }
-  EGONN_REQUIRE(in, EGONN_ERR_INVALID, "conv_backward_weight: null input");
-  // the MFMA channel plans take their (input row, output row) pairs from the row-group form of the map: built here if no forward
-  // call did it before, so that the pair source — and with it the fp32 summation order — never depends on the call history
-  if ((ks == 3 || ks == 2) && ((cin == 32 && (cout == 32 || cout == 64)) || (cin == 64 && (cout == 64 || cout == 128)) ||
-                               (cin == 128 && cout == 128))) {
-    const int kind = ks == 3 ? 0 : (transposed ? 2 : 1);
-    if (level_out >= (kind == 2 ? 0 : 1) && level_out < EGONN_NUM_LEVELS - (kind == 2 ? 1 : 0))
-      EGONN_TRY(ensure_rowgroups(c, &kind, &level_out, 1, st));
-  }
-  if (ks == 1) {
-    EGONN_REQUIRE(level_in == level_out && !transposed, EGONN_ERR_INVALID, "1x1 conv cannot change the level");
-    return conv_wgrad(in, grad_out, nullptr, P.lv[level_in].n, 1, cin, cout, grad_kernel, scratch, (size_t)scratch_floats, st);
-  }
-  if (ks == 3) {
-    EGONN_REQUIRE(level_in == level_out && level_in >= 1 && !transposed, EGONN_ERR_INVALID,
-                  "k=3 convolution: levels 1..7, same in/out level");
-    return conv_wgrad(in, grad_out, P.lv[level_in].nbr27, P.lv[level_in].n, 27, cin, cout, grad_kernel, scratch,
-                      (size_t)scratch_floats, st, &P.lv[level_in].rg27);
-  }
-  if (ks == 2 && !transposed) {
-    EGONN_REQUIRE(level_out == level_in + 1, EGONN_ERR_INVALID, "k=2,s=2 convolution maps level l to l+1");
-    return conv_wgrad(in, grad_out, P.lv[level_out].nbr8, P.lv[level_out].n, 8, cin, cout, grad_kernel, scratch,
-                      (size_t)scratch_floats, st, &P.lv[level_out].rg8);
-  }
-  if (ks == 2 && transposed) {
-    EGONN_REQUIRE(level_out == level_in - 1 && level_out >= 0, EGONN_ERR_INVALID, "transposed conv maps level l to l-1");
-    if (level_out == 0) EGONN_TRY(ensure_level0_parent_table(c, st));
-    return conv_wgrad(in, grad_out, P.lv[level_out].nbrT, P.lv[level_out].n, 8, cin, cout, grad_kernel, scratch,
-                      (size_t)scratch_floats, st, &P.lv[level_out].rgT);
-  }
-  set_error("conv_backward_weight: kernel_size %d not supported", ks);
-  return EGONN_ERR_INVALID;
-}
-
-API int egonn_col_stats(int mode, const float* a, const float* b, const float* mask, const float* mean, int64_t n, int c,
-                        double* out, float* scratch, int64_t scratch_floats, void* stream) {
-  return col_stats(mode, a, b, mask, mean, n, c, out, scratch, (size_t)scratch_floats, (hipStream_t)stream);
-}
-API int egonn_bn_train_finalize(const double* sums, const float* shift_point, double count, int c, const float* weight,
-                                const float* bias, float eps, float momentum, float* running_mean, float* running_var,
-                                float* out_mean_invstd_scale_shift, void* stream) {
-  EGONN_REQUIRE(sums && shift_point && weight && bias && out_mean_invstd_scale_shift && count >= 1.0 && c >= 1,
-                EGONN_ERR_INVALID, "bn_train_finalize: bad arguments");
-  return bn_fwd_finalize(sums, shift_point, count, c, weight, bias, eps, momentum, running_mean, running_var,
-                         out_mean_invstd_scale_shift, (hipStream_t)stream);
-}
-API int egonn_bn_backward_finalize(const double* local_sums, const double* global_sums, double count, int c,
-                                   const float* weight, const float* mean, const float* invstd, float* out_abc_dgamma_dbeta,
-                                   void* stream) {
-  EGONN_REQUIRE(local_sums && global_sums && weight && mean && invstd && out_abc_dgamma_dbeta && count >= 1.0,
-                EGONN_ERR_INVALID, "bn_backward_finalize: bad arguments");
-  return bn_bwd_finalize(local_sums, global_sums, count, c, weight, mean, invstd, out_abc_dgamma_dbeta, (hipStream_t)stream);
-}
-API int egonn_affine_act(const float* x, const float* scale, const float* shift, int64_t n, int c, int relu, float* out,
-                         void* stream) {
-  EGONN_REQUIRE(x && scale && shift && out, EGONN_ERR_INVALID, "affine_act: null argument");
-  return affine_act(x, scale, shift, n, c, relu, out, (hipStream_t)stream);
-}
-API int egonn_affine3(const float* g, const float* mask, const float* x, const float* A, const float* B, const float* C,
-                      int64_t n, int c, float* out, void* stream) {
-  EGONN_REQUIRE(g && x && A && B && C && out, EGONN_ERR_INVALID, "affine3: null argument");
-  return affine3(g, mask, x, A, B, C, n, c, out, (hipStream_t)stream);
-}
-API int egonn_relu_backward(const float* grad_out, const float* out, int64_t n, int c, float* grad_in, void* stream) {
-  EGONN_REQUIRE(grad_out && out && grad_in, EGONN_ERR_INVALID, "relu_backward: null argument");
-  return gate_residual_backward(grad_out, out, nullptr, nullptr, 0, n, c, grad_in, nullptr, (hipStream_t)stream);
-}
-API int egonn_eca_gate(const float* mean, const float* conv_weight, int kernel_size, int batch_size, int channels,
-                       float* gate, void* stream) {
-  EGONN_REQUIRE(mean && conv_weight && gate, EGONN_ERR_INVALID, "eca_gate: null argument");
-  return eca_gate_forward(mean, conv_weight, kernel_size, batch_size, channels, gate, (hipStream_t)stream);
-}
-API int egonn_eca_gate_backward(const float* grad_gate, const float* gate, const float* mean, const float* conv_weight,
-                                int kernel_size, int batch_size, int channels, float* grad_mean, float* grad_weight,
-                                void* stream) {
-  EGONN_REQUIRE(grad_gate && gate && mean && conv_weight && grad_mean && grad_weight, EGONN_ERR_INVALID,
-                "eca_gate_backward: null argument");
-  return eca_gate_backward(grad_gate, gate, mean, conv_weight, kernel_size, batch_size, channels, grad_mean, grad_weight,
-                           (hipStream_t)stream);
-}
-API int egonn_se_gate(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, int batch_size,
-                      int channels, int hidden, float* gate, float* hidden_out, void* stream) {
-  EGONN_REQUIRE(mean && w1 && b1 && w2 && b2 && gate, EGONN_ERR_INVALID, "se_gate: null argument");
-  return se_gate_forward(mean, w1, b1, w2, b2, batch_size, channels, hidden, gate, hidden_out, (hipStream_t)stream);
-}
-API int egonn_se_gate_backward(const float* grad_gate, const float* gate, const float* hidden_act, const float* mean,
-                               const float* w1, const float* w2, int batch_size, int channels, int hidden, float* grad_mean,
-                               float* grad_w1, float* grad_b1, float* grad_w2, float* grad_b2, void* stream) {
-  EGONN_REQUIRE(grad_gate && gate && hidden_act && mean && w1 && w2 && grad_mean && grad_w1 && grad_b1 && grad_w2 && grad_b2,
-                EGONN_ERR_INVALID, "se_gate_backward: null argument");
-  return se_gate_backward(grad_gate, gate, hidden_act, mean, w1, w2, batch_size, channels, hidden, grad_mean, grad_w1, grad_b1,
-                          grad_w2, grad_b2, (hipStream_t)stream);
-}
-API int egonn_act_backward(int act, const float* grad_out, const float* out, int64_t n, int c, float* grad_in, void* stream) {
-  EGONN_REQUIRE(grad_out && out && grad_in && act >= 0 && act <= 4, EGONN_ERR_INVALID, "act_backward: bad arguments");
-  return act_backward(act, grad_out, out, n, c, grad_in, (hipStream_t)stream);
-}
-API int egonn_l2_normalize(const float* x, const float* grad_out, int64_t n, int c, float* out, void* stream) {
-  EGONN_REQUIRE(x && out && c >= 1, EGONN_ERR_INVALID, "l2_normalize: bad arguments");
-  return l2norm_rows(x, grad_out, n, c, out, (hipStream_t)stream);
-}
-API int egonn_gate_residual(egonn_ctx* c, int level, const float* x, const float* gate, const float* residual, int ch,
-                            int relu, float* out, void* stream) {
-  REQUIRE_LEVEL(c, level);
-  EGONN_REQUIRE(x && out, EGONN_ERR_INVALID, "gate_residual: null argument");
-  return gate_residual_forward(x, gate, residual, c->plan.lv[level].boff, c->plan.batch, c->plan.lv[level].n, ch, relu, out,
-                               (hipStream_t)stream);
-}
-API int egonn_gate_residual_backward(egonn_ctx* c, int level, const float* grad_out, const float* out, const float* gate,
-                                     int ch, float* grad_x, float* grad_residual, void* stream) {
-  REQUIRE_LEVEL(c, level);
-  EGONN_REQUIRE(grad_out && grad_x, EGONN_ERR_INVALID, "gate_residual_backward: null argument");
-  return gate_residual_backward(grad_out, out, gate, c->plan.lv[level].boff, c->plan.batch, c->plan.lv[level].n, ch, grad_x,
-                                grad_residual, (hipStream_t)stream);
-}
-API int egonn_segment_sums(egonn_ctx* c, int level, int mode, const float* a, const float* b, const float* x2, const float* p,
-                           int ch, float* out, float* scratch, int64_t scratch_floats, void* stream) {
-  REQUIRE_LEVEL(c, level);
-  EGONN_REQUIRE(a && out && mode >= 0 && mode <= 2 && (mode == 1 || b) && (mode != 2 || x2) && (mode != 1 || p),
-                EGONN_ERR_INVALID, "segment_sums: bad arguments");
-  return seg_sums2(mode, a, b, x2, p, c->plan.lv[level].boff, c->plan.batch, ch, out, scratch, (size_t)scratch_floats,
-                   (hipStream_t)stream);
-}
-API int egonn_segment_broadcast(egonn_ctx* c, int level, const float* v, int ch, int mean, float* out, void* stream) {
-  REQUIRE_LEVEL(c, level);
-  EGONN_REQUIRE(v && out, EGONN_ERR_INVALID, "segment_broadcast: null argument");
-  return seg_broadcast(v, c->plan.lv[level].boff, c->plan.batch, c->plan.lv[level].n, ch, mean, out, (hipStream_t)stream);
-}
-API int egonn_gem_backward(egonn_ctx* c, int level, const float* x, const float* coef, const float* p, int ch, float* grad_x,
-                           void* stream) {
-  REQUIRE_LEVEL(c, level);
-  EGONN_REQUIRE(x && coef && p && grad_x, EGONN_ERR_INVALID, "gem_backward: null argument");
-  return gem_backward_rows(x, coef, p, c->plan.lv[level].boff, c->plan.batch, c->plan.lv[level].n, ch, grad_x,
-                           (hipStream_t)stream);
-}
-
-
-// ------------------------------------------------------------------------------------------ retrieval (eval/evaluate.py)
-API int egonn_knn(const float* query, int64_t n_query, const float* database, int64_t n_database, int dim, int k,
-                  int32_t* out_index, float* out_distance, float* scratch, int64_t scratch_floats, void* stream) {
-  EGONN_REQUIRE(n_query < (1ll << 31) && n_database < (1ll << 31), EGONN_ERR_INVALID, "knn: too many rows");
-  return knn_search(query, (int32_t)n_query, database, (int32_t)n_database, dim, k, out_index, out_distance, scratch,
-                    (size_t)scratch_floats, (hipStream_t)stream);
-}
-API int egonn_recall_counts(const int32_t* nn_index, const float* query_positions, const float* map_positions,
-                            int64_t n_query, int k, int position_dim, const float* radius, int n_radius,
-                            int32_t* out_true_positives, void* stream) {
-  return recall_counts(nn_index, query_positions, map_positions, (int32_t)n_query, k, position_dim, radius, n_radius,
-                       out_true_positives, (hipStream_t)stream);
-}
-
-
-// ------------------------------------------------------------------------------------------ scan ingest
-API int64_t egonn_filter_points_scratch_ints(int64_t n) { return (int64_t)ingest_scratch_ints(n); }
-API int egonn_filter_points(const float* raw, int64_t n, int floats_per_point, const int64_t* scan_offsets, int batch_size,
-                            int remove_zero_points, int remove_ground_plane, float ground_plane_level, float* out_points,
-                            int64_t* out_scan_offsets, int32_t* scratch, int64_t scratch_ints, void* stream) {
-  return ingest_filter(raw, n, floats_per_point, scan_offsets, batch_size, remove_zero_points, remove_ground_plane,
-                       ground_plane_level, out_points, out_scan_offsets, scratch, (size_t)scratch_ints,
-                       (hipStream_t)stream);
 }

@@ -25,8 +25,7 @@
 //   7. dWc = sum of the partials in (scan, chunk) order
 // No atomics; every summation order is a function of the scan's own row count (nv_chunks) and, for the sums over scans, of the
 // batch order.  A scan's rows of dX depend on the other scans only through the (64,) bn1 vectors and Nmax.
-#include "common.h"
-#include "kernels.h"
+#include "model.h"
 
 namespace egonn {
 
@@ -69,19 +68,46 @@ __global__ void nvt_fill_kernel(float* __restrict__ p, int n, float v) {
 
 static size_t nvt_stats_scratch_floats(int64_t N) { return (size_t)4 * NV_K * (size_t)std::max<int64_t>(1024, N / 512 + 2); }
 
-size_t netvlad_train_forward_floats(int B, int64_t N, int C, int D) {
+static size_t netvlad_train_forward_floats(int B, int64_t N, int C, int D) {
   return netvlad_workspace_floats(B, C, D) + nvt_stats_scratch_floats(N) + 2 * (size_t)D + 4 * NV_K + 8 * 64;
 }
 
-int netvlad_train_forward(const float* x, const int32_t* boff, int B, int64_t N, int C, int nmax, const float* wc,
-                          const float* w2, const float* bn1_w, const float* bn1_b, float eps, float momentum,
-                          float* running_mean, float* running_var, const float* H, int D, float* out, float* save_z,
-                          float* save_bn4, float* save_vraw, float* save_sq, float* save_asum, float* ws, hipStream_t stream) {
-  EGONN_REQUIRE(C >= 16 && C <= 512 && C % 16 == 0 && D >= 16 && D <= 1024 && D % 16 == 0, EGONN_ERR_INVALID,
-                "netvlad_train: unsupported sizes C=%d D=%d", C, D);
-  EGONN_REQUIRE(B >= 2 && N >= 1 && nmax >= 1 && (int64_t)B * nmax >= N, EGONN_ERR_INVALID,
-                "netvlad_train: B=%d rows=%lld nmax=%d (batch statistics need B >= 2 and nmax = the largest scan)", B,
-                (long long)N, nmax);
+static int netvlad_train_check(egonn_ctx* ctx, int level, int C, int D, int nmax) {
+  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS, EGONN_ERR_INVALID, "netvlad_train: level %d out of range", level);
+  EGONN_REQUIRE(C >= 16 && C <= 512 && C % 16 == 0, EGONN_ERR_INVALID,
+                "netvlad_train: %d channels unsupported (multiple of 16, 16..512)", C);
+  EGONN_REQUIRE(D >= 16 && D <= 1024 && D % 16 == 0, EGONN_ERR_INVALID,
+                "netvlad_train: output_dim %d unsupported (multiple of 16, 16..1024)", D);
+  EGONN_REQUIRE(ctx->plan.batch >= 2, EGONN_ERR_INVALID, "netvlad_train: batch statistics need at least 2 scans");
+  EGONN_REQUIRE(ctx->plan.lv[level].n >= 1 && nmax >= 1 && (int64_t)nmax * ctx->plan.batch >= ctx->plan.lv[level].n,
+                EGONN_ERR_INVALID, "netvlad_train: nmax %d is not the largest scan of the level", nmax);
+  return EGONN_OK;
+}
+
+// Train-mode NetVLAD core over the rows of `level`: bn1 on the statistics of the M = B * nmax zero-padded rows, y = vlad @ H
+// (B, D) BEFORE bn2; what the backward needs goes to the caller's save_* buffers
+API int egonn_netvlad_train_forward(egonn_ctx* ctx, int level, const float* x, int C, int nmax, const float* wc, const float* w2,
+                                    const float* bn1_w, const float* bn1_b, float eps, float momentum, float* running_mean,
+                                    float* running_var, const float* H, int D, float* out, float* save_z, float* save_bn4,
+                                    float* save_vraw, float* save_sq, float* save_asum, void* stream) {
+  REQUIRE_PLAN(ctx);
+  EGONN_TRY(netvlad_train_check(ctx, level, C, D, nmax));
+  EGONN_REQUIRE(x && wc && w2 && bn1_w && bn1_b && running_mean && running_var && H && out && save_z && save_bn4 && save_vraw &&
+                    save_sq && save_asum,
+                EGONN_ERR_INVALID, "netvlad_train_forward: null argument");
+  EGONN_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)save_z & 15) == 0, EGONN_ERR_INVALID,
+                "netvlad_train_forward: x and save_z must be 16-byte aligned");
+  HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int B = ctx->plan.batch;
+  const int64_t N = ctx->plan.lv[level].n;
+  const int32_t* boff = ctx->plan.lv[level].boff;
+  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) ctx->level_feat[l] = nullptr;
+  const size_t nws = netvlad_train_forward_floats(B, N, C, D);
+  EGONN_TRY(ctx->work_arena.ensure(nws * 4 + 4096));
+  ctx->work_arena.reset();
+  float* ws = ctx->work_arena.alloc<float>(nws);
+  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
   float* nvws = ws;
   float* cs = nvws + align_up(netvlad_workspace_floats(B, C, D), 64);
   const size_t csn = nvt_stats_scratch_floats(N);
@@ -89,24 +115,24 @@ int netvlad_train_forward(const float* x, const int32_t* boff, int B, int64_t N,
   float* ones = reinterpret_cast<float*>(sums + 2 * NV_K);
   float* zeros = ones + D;
   const double M = (double)B * (double)nmax;
-  EGONN_TRY(dense_forward(x, N, C, wc, 0, NV_K, nullptr, nullptr, nullptr, ACT_NONE, nullptr, save_z, stream));
-  EGONN_TRY(col_stats(3, save_z, nullptr, nullptr, running_mean, N, NV_K, sums, cs, csn, stream));
-  hipLaunchKernelGGL(nvt_pad_stats_kernel, dim3(1), dim3(NV_K), 0, stream, sums, running_mean, M - (double)N);
+  EGONN_TRY(dense_forward(x, N, C, wc, 0, NV_K, nullptr, nullptr, nullptr, ACT_NONE, nullptr, save_z, st));
+  EGONN_TRY(egonn_col_stats(3, save_z, nullptr, nullptr, running_mean, N, NV_K, sums, cs, (int64_t)csn, st));
+  hipLaunchKernelGGL(nvt_pad_stats_kernel, dim3(1), dim3(NV_K), 0, st, sums, running_mean, M - (double)N);
   HIP_CHECK(hipGetLastError());
-  EGONN_TRY(bn_fwd_finalize(sums, running_mean, M, NV_K, bn1_w, bn1_b, eps, momentum, running_mean, running_var, save_bn4,
-                            stream));
-  hipLaunchKernelGGL(nvt_fill_kernel, dim3((unsigned)cdiv(D, 256)), dim3(256), 0, stream, ones, D, 1.f);
-  hipLaunchKernelGGL(nvt_fill_kernel, dim3((unsigned)cdiv(D, 256)), dim3(256), 0, stream, zeros, D, 0.f);
+  EGONN_TRY(egonn_bn_train_finalize(sums, running_mean, M, NV_K, bn1_w, bn1_b, eps, momentum, running_mean, running_var,
+                                    save_bn4, st));
+  hipLaunchKernelGGL(nvt_fill_kernel, dim3((unsigned)cdiv(D, 256)), dim3(256), 0, st, ones, D, 1.f);
+  hipLaunchKernelGGL(nvt_fill_kernel, dim3((unsigned)cdiv(D, 256)), dim3(256), 0, st, zeros, D, 0.f);
   HIP_CHECK(hipGetLastError());
   const float* sc1 = save_bn4 + 2 * NV_K;
   const float* sh1 = save_bn4 + 3 * NV_K;
   EGONN_TRY(netvlad_forward(x, boff, B, C, wc, w2, sc1, sh1, H, D, ones, zeros, nullptr, nullptr, nullptr, 0, out, nvws,
-                            stream));
+                            st));
   float *part, *vraw, *sq, *pp;
   netvlad_workspace_carve(nvws, B, C, &part, &vraw, &sq, &pp);
-  HIP_CHECK(hipMemcpyAsync(save_vraw, vraw, (size_t)B * C * NV_K * 4, hipMemcpyDeviceToDevice, stream));
-  HIP_CHECK(hipMemcpyAsync(save_sq, sq, (size_t)B * (C / 16) * NV_K * 4, hipMemcpyDeviceToDevice, stream));
-  hipLaunchKernelGGL(nvt_asum_kernel, dim3(B), dim3(64), 0, stream, part, boff, C, nmax, sh1, save_asum);
+  HIP_CHECK(hipMemcpyAsync(save_vraw, vraw, (size_t)B * C * NV_K * 4, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(save_sq, sq, (size_t)B * (C / 16) * NV_K * 4, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(nvt_asum_kernel, dim3(B), dim3(64), 0, st, part, boff, C, nmax, sh1, save_asum);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -549,20 +575,32 @@ static int launch_rows(const float* x, const float* z, const int32_t* boff, int 
   return EGONN_OK;
 }
 
-size_t netvlad_train_backward_floats(int B, int64_t N, int C, int D) {
+static size_t netvlad_train_backward_floats(int B, int64_t N, int C, int D) {
   const size_t CK = (size_t)C * NV_K;
   return 2 * align_up((size_t)B * CK, 64) + 3 * align_up((size_t)B * NV_K, 64) + 2 * align_up((size_t)N * NV_K, 64) +
          2 * ((size_t)B * NV_MAX_CHUNKS * 2 * NV_K + 2 * NV_K) + (size_t)B * NV_MAX_CHUNKS * CK + 8 * 64;
 }
 
-int netvlad_train_backward(const float* x, const float* z, const int32_t* boff, int B, int64_t N, int C, int nmax,
-                           const float* wc, const float* w2, const float* bn1_w, const float* bn4, const float* H, int D,
-                           const float* dy, const float* vraw, const float* sq, const float* asum, float* dx, float* dwc,
-                           float* dw2, float* bn5, float* dH, float* ws, hipStream_t stream) {
-  EGONN_REQUIRE(C >= 16 && C <= 512 && C % 16 == 0 && D >= 16 && D <= 1024 && D % 16 == 0, EGONN_ERR_INVALID,
-                "netvlad_train: unsupported sizes C=%d D=%d", C, D);
-  EGONN_REQUIRE(B >= 2 && N >= 1 && nmax >= 1 && (int64_t)B * nmax >= N, EGONN_ERR_INVALID,
-                "netvlad_train: B=%d rows=%lld nmax=%d", B, (long long)N, nmax);
+API int egonn_netvlad_train_backward(egonn_ctx* ctx, int level, const float* x, int C, int nmax, const float* wc, const float* w2,
+                                     const float* bn1_w, const float* H, int D, const float* dy, const float* z, const float* bn4,
+                                     const float* vraw, const float* sq, const float* asum, float* dx, float* dwc, float* dw2,
+                                     float* bn5, float* dH, void* stream) {
+  REQUIRE_PLAN(ctx);
+  EGONN_TRY(netvlad_train_check(ctx, level, C, D, nmax));
+  EGONN_REQUIRE(x && wc && w2 && bn1_w && H && dy && z && bn4 && vraw && sq && asum && dx && dwc && dw2 && bn5 && dH,
+                EGONN_ERR_INVALID, "netvlad_train_backward: null argument");
+  EGONN_REQUIRE(((uintptr_t)x & 15) == 0, EGONN_ERR_INVALID, "netvlad_train_backward: x must be 16-byte aligned");
+  HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int B = ctx->plan.batch;
+  const int64_t N = ctx->plan.lv[level].n;
+  const int32_t* boff = ctx->plan.lv[level].boff;
+  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) ctx->level_feat[l] = nullptr;
+  const size_t nws = netvlad_train_backward_floats(B, N, C, D);
+  EGONN_TRY(ctx->work_arena.ensure(nws * 4 + 4096));
+  ctx->work_arena.reset();
+  float* ws = ctx->work_arena.alloc<float>(nws);
+  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
   const int64_t CK = (int64_t)C * NV_K;
   float* dvl = ws;
   float* dV = dvl + align_up((size_t)B * CK, 64);
@@ -574,35 +612,36 @@ int netvlad_train_backward(const float* x, const float* z, const int32_t* boff, 
   double* partd = reinterpret_cast<double*>(dLs + align_up((size_t)N * NV_K, 64));
   double* sums = partd + (size_t)B * NV_MAX_CHUNKS * 2 * NV_K;
   float* pwc = reinterpret_cast<float*>(sums + 2 * NV_K);
-  hipLaunchKernelGGL(nvt_dvlad_kernel, dim3((unsigned)cdiv(CK, 4)), dim3(256), 0, stream, dy, H, B, (int)CK, D, dvl);
+  hipLaunchKernelGGL(nvt_dvlad_kernel, dim3((unsigned)cdiv(CK, 4)), dim3(256), 0, st, dy, H, B, (int)CK, D, dvl);
   HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(nvt_norm_bwd_kernel, dim3(B), dim3(1024), 0, stream, vraw, sq, dvl, w2, C, dV, dasum, sinv, sG);
+  hipLaunchKernelGGL(nvt_norm_bwd_kernel, dim3(B), dim3(1024), 0, st, vraw, sq, dvl, w2, C, dV, dasum, sinv, sG);
   HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(nvt_dh_kernel, dim3((unsigned)CK, (unsigned)cdiv(D, 256)), dim3(256), 0, stream, vraw, sinv, sG, dy, B, CK,
+  hipLaunchKernelGGL(nvt_dh_kernel, dim3((unsigned)CK, (unsigned)cdiv(D, 256)), dim3(256), 0, st, vraw, sinv, sG, dy, B, CK,
                      D, dH);
-  hipLaunchKernelGGL(nvt_dw2_kernel, dim3((unsigned)cdiv(CK, 256)), dim3(256), 0, stream, asum, dV, B, CK, dw2);
+  hipLaunchKernelGGL(nvt_dw2_kernel, dim3((unsigned)cdiv(CK, 256)), dim3(256), 0, st, asum, dV, B, CK, dw2);
   HIP_CHECK(hipGetLastError());
   for (int pass = 1; pass <= 2; ++pass) {
     if (C <= 64)
-      EGONN_TRY((launch_rows<4, 4>(x, z, boff, B, C, dV, dasum, bn4, As, dLs, partd, pass, wc, bn5, dx, pwc, stream)));
+      EGONN_TRY((launch_rows<4, 4>(x, z, boff, B, C, dV, dasum, bn4, As, dLs, partd, pass, wc, bn5, dx, pwc, st)));
     else if (C <= 128)
-      EGONN_TRY((launch_rows<8, 4>(x, z, boff, B, C, dV, dasum, bn4, As, dLs, partd, pass, wc, bn5, dx, pwc, stream)));
+      EGONN_TRY((launch_rows<8, 4>(x, z, boff, B, C, dV, dasum, bn4, As, dLs, partd, pass, wc, bn5, dx, pwc, st)));
     else if (C <= 256)
-      EGONN_TRY((launch_rows<16, 4>(x, z, boff, B, C, dV, dasum, bn4, As, dLs, partd, pass, wc, bn5, dx, pwc, stream)));
+      EGONN_TRY((launch_rows<16, 4>(x, z, boff, B, C, dV, dasum, bn4, As, dLs, partd, pass, wc, bn5, dx, pwc, st)));
     else
-      EGONN_TRY((launch_rows<32, 2>(x, z, boff, B, C, dV, dasum, bn4, As, dLs, partd, pass, wc, bn5, dx, pwc, stream)));
+      EGONN_TRY((launch_rows<32, 2>(x, z, boff, B, C, dV, dasum, bn4, As, dLs, partd, pass, wc, bn5, dx, pwc, st)));
     if (pass == 1) {
-      hipLaunchKernelGGL(nvt_bn1_sums_kernel, dim3(1), dim3(64), 0, stream, partd, boff, B, nmax, bn4, dasum, sums);
+      hipLaunchKernelGGL(nvt_bn1_sums_kernel, dim3(1), dim3(64), 0, st, partd, boff, B, nmax, bn4, dasum, sums);
       HIP_CHECK(hipGetLastError());
-      EGONN_TRY(bn_bwd_finalize(sums, sums, (double)B * (double)nmax, NV_K, bn1_w, bn4, bn4 + NV_K, bn5, stream));
+      EGONN_TRY(egonn_bn_backward_finalize(sums, sums, (double)B * (double)nmax, NV_K, bn1_w, bn4, bn4 + NV_K, bn5, st));
     }
   }
-  hipLaunchKernelGGL(nvt_dwc_kernel, dim3((unsigned)cdiv(CK, 256)), dim3(256), 0, stream, pwc, boff, B, CK, dwc);
+  hipLaunchKernelGGL(nvt_dwc_kernel, dim3((unsigned)cdiv(CK, 256)), dim3(256), 0, st, pwc, boff, B, CK, dwc);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
 
 // ------------------------------------------------------------------ MAC with its argmax, and its backward
+// (the winning plan row of every (scan, channel); ties: lowest row; empty scan: 0 and row -1)
 // workgroup (64 channels, scan): 4 row quarters in ascending order, strict > inside and between them: a tie goes to the lowest row
 __global__ __launch_bounds__(256) void max_argmax_kernel(const float* __restrict__ in, const int32_t* __restrict__ boff, int C,
                                                          float* __restrict__ out, int32_t* __restrict__ rows) {
@@ -644,18 +683,31 @@ __global__ void max_scatter_kernel(const float* __restrict__ grad, const int32_t
   if (r >= 0 && r < n) dx[(int64_t)r * C + (int)(i % C)] = grad[i];
 }
 
-int global_max_argmax(const float* in, const int32_t* boff, int B, int c, float* out, int32_t* rows, hipStream_t stream) {
+API int egonn_global_max_pool_argmax(egonn_ctx* ctx, int level, const float* in, int c, float* out, int32_t* rows, void* stream) {
+  REQUIRE_PLAN(ctx);
+  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && in && out && rows && c >= 1, EGONN_ERR_INVALID,
+                "global_max_pool_argmax: bad argument");
+  HIP_CHECK(hipSetDevice(ctx->device));
+  const int B = ctx->plan.batch;
   if (B == 0) return EGONN_OK;
-  hipLaunchKernelGGL(max_argmax_kernel, dim3((unsigned)cdiv(c, 64), B), dim3(256), 0, stream, in, boff, c, out, rows);
+  hipLaunchKernelGGL(max_argmax_kernel, dim3((unsigned)cdiv(c, 64), B), dim3(256), 0, (hipStream_t)stream, in,
+                     ctx->plan.lv[level].boff, c, out, rows);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
 
-int global_max_backward(const float* grad, const int32_t* rows, int B, int64_t n, int c, float* dx, hipStream_t stream) {
-  HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)n * c * 4, stream));
-  const int64_t total = (int64_t)B * c;
+API int egonn_global_max_pool_backward(egonn_ctx* ctx, int level, const float* grad, const int32_t* rows, int c, float* dx,
+                                       void* stream) {
+  REQUIRE_PLAN(ctx);
+  EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && grad && rows && dx && c >= 1, EGONN_ERR_INVALID,
+                "global_max_pool_backward: bad argument");
+  HIP_CHECK(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = ctx->plan.lv[level].n;
+  HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)n * c * 4, st));
+  const int64_t total = (int64_t)ctx->plan.batch * c;
   if (total == 0 || n == 0) return EGONN_OK;
-  hipLaunchKernelGGL(max_scatter_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, grad, rows, total, c, n, dx);
+  hipLaunchKernelGGL(max_scatter_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, grad, rows, total, c, n, dx);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -676,10 +728,12 @@ __global__ void sigmoid_gate_kernel(const float* __restrict__ y, const float* __
   dt[i] = g * y[i] * s * (1.f - s);
 }
 
-int sigmoid_gate(const float* y, const float* t, const float* grad, int64_t n, float* out, float* dy, float* dt,
-                 hipStream_t stream) {
+API int egonn_sigmoid_gate(const float* y, const float* t, const float* grad, int64_t n, float* out, float* dy, float* dt,
+                           void* stream) {
+  EGONN_REQUIRE(y && t && n >= 0 && (grad ? (dy && dt) : out != nullptr), EGONN_ERR_INVALID, "sigmoid_gate: bad argument");
   if (n == 0) return EGONN_OK;
-  hipLaunchKernelGGL(sigmoid_gate_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, y, t, grad, n, out, dy, dt);
+  hipLaunchKernelGGL(sigmoid_gate_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, y, t, grad, n, out, dy,
+                     dt);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }

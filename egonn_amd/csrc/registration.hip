@@ -37,8 +37,6 @@
 
 #pragma clang fp contract(off)
 
-#define API extern "C" __attribute__((visibility("default")))
-
 namespace egonn {
 
 static constexpr int REG_MAX_N = 256;    // keypoints per side (the reference evaluates n_k = 128 and 256)

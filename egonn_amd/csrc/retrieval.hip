@@ -8,8 +8,7 @@
 // Non-finite distances: +inf (an overflowing or infinite element) is a distance like any other, after every finite one
 // and in index order; a NaN distance is never a neighbour, the list then ends early with (-1, +inf).  A taken entry is
 // marked NaN, which no comparison selects, so that a genuine +inf is returned once and only once.
-#include "common.h"
-#include "kernels.h"
+#include "model.h"
 
 namespace egonn {
 
@@ -77,15 +76,18 @@ __global__ __launch_bounds__(256) void knn_select_kernel(float* __restrict__ dis
   }
 }
 
-int knn_search(const float* query, int32_t nq, const float* db, int32_t m, int d, int k, int32_t* out_idx, float* out_dist,
-               float* scratch, size_t scratch_floats, hipStream_t stream) {
+API int egonn_knn(const float* query, int64_t n_query, const float* db, int64_t n_database, int d, int k, int32_t* out_idx,
+                  float* out_dist, float* scratch, int64_t scratch_floats, void* stream) {
+  EGONN_REQUIRE(n_query < (1ll << 31) && n_database < (1ll << 31), EGONN_ERR_INVALID, "knn: too many rows");
+  const int32_t nq = (int32_t)n_query, m = (int32_t)n_database;
   EGONN_REQUIRE(query && db && out_idx && out_dist && nq >= 0 && m >= 1 && d >= 1 && d <= 4096 && k >= 1, EGONN_ERR_INVALID,
                 "knn: bad arguments (nq=%d m=%d d=%d k=%d)", nq, m, d, k);
   if (nq == 0) return EGONN_OK;
-  EGONN_REQUIRE(scratch && scratch_floats >= (size_t)nq * m, EGONN_ERR_INVALID,
+  EGONN_REQUIRE(scratch && (size_t)scratch_floats >= (size_t)nq * m, EGONN_ERR_INVALID,
                 "knn: scratch needs %lld floats", (long long)nq * m);
-  hipLaunchKernelGGL(knn_dist_kernel, dim3((unsigned)nq), dim3(256), (size_t)d * 4, stream, query, db, m, d, scratch);
-  hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)nq), dim3(256), 0, stream, scratch, m, k, out_idx, out_dist);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(knn_dist_kernel, dim3((unsigned)nq), dim3(256), (size_t)d * 4, st, query, db, m, d, scratch);
+  hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)nq), dim3(256), 0, st, scratch, m, k, out_idx, out_dist);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -112,13 +114,15 @@ __global__ void recall_kernel(const int32_t* __restrict__ nn_idx, const float* _
   }
 }
 
-int recall_counts(const int32_t* nn_idx, const float* qpos, const float* mpos, int32_t nq, int k, int pd,
-                  const float* radius, int nr, int32_t* tp, hipStream_t stream) {
+API int egonn_recall_counts(const int32_t* nn_idx, const float* qpos, const float* mpos, int64_t n_query, int k, int pd,
+                            const float* radius, int nr, int32_t* tp, void* stream) {
+  const int32_t nq = (int32_t)n_query;
+  hipStream_t st = (hipStream_t)stream;
   EGONN_REQUIRE(radius && tp && k >= 1 && nr >= 1 && pd >= 1 && nq >= 0 && (nq == 0 || (nn_idx && qpos && mpos)),
                 EGONN_ERR_INVALID, "recall: bad arguments");       // an empty query set has no buffers to point at
-  HIP_CHECK(hipMemsetAsync(tp, 0, (size_t)nr * k * 4, stream));
+  HIP_CHECK(hipMemsetAsync(tp, 0, (size_t)nr * k * 4, st));
   if (nq == 0) return EGONN_OK;
-  hipLaunchKernelGGL(recall_kernel, dim3((unsigned)cdiv(nq, 128)), dim3(128), 0, stream, nn_idx, qpos, mpos, nq, k, pd,
+  hipLaunchKernelGGL(recall_kernel, dim3((unsigned)cdiv(nq, 128)), dim3(128), 0, st, nn_idx, qpos, mpos, nq, k, pd,
                      radius, nr, tp);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;

@@ -38,8 +38,6 @@
 
 #pragma clang fp contract(off)
 
-#define API extern "C" __attribute__((visibility("default")))
-
 namespace egonn {
 
 static constexpr int SC_MAX_RING = 40, SC_MAX_SECTOR = 128, SC_MAX_K = 128;

@@ -227,7 +227,7 @@ size_t radix_sort_scratch_bytes(int64_t n) {
   return (size_t)(tiles * 256 + 8 * (supers + 1) * 256) * sizeof(int32_t) + 1024;
 }
 
-int radix_sort_pairs(Ctx* ctx, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out,
+int radix_sort_pairs(Arena& ws, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out,
                      int64_t n, int nbits, hipStream_t stream, const int64_t* n_dev, uint64_t** keys_res, uint32_t** vals_res) {
   EGONN_REQUIRE(n >= 0 && n < (int64_t(1) << 31), EGONN_ERR_INVALID, "radix_sort: n=%lld out of range", (long long)n);
   EGONN_REQUIRE(nbits >= 1 && nbits <= 64, EGONN_ERR_INVALID, "radix_sort: nbits=%d", nbits);
@@ -237,10 +237,10 @@ int radix_sort_pairs(Ctx* ctx, uint64_t* keys_in, uint32_t* vals_in, uint64_t* k
   if (n == 0) return EGONN_OK;
   const int64_t tiles = cdiv(n, SORT_TILE);
   const int64_t supers = cdiv(tiles, SORT_SUPER);
-  EGONN_TRY(ctx->sort_arena.ensure(radix_sort_scratch_bytes(n)));
-  ctx->sort_arena.reset();
-  int32_t* tilehist = ctx->sort_arena.alloc<int32_t>(tiles * 256);
-  int32_t* slabs = ctx->sort_arena.alloc<int32_t>(8 * (supers + 1) * 256);
+  EGONN_TRY(ws.ensure(radix_sort_scratch_bytes(n)));
+  ws.reset();
+  int32_t* tilehist = ws.alloc<int32_t>(tiles * 256);
+  int32_t* slabs = ws.alloc<int32_t>(8 * (supers + 1) * 256);
   EGONN_REQUIRE(tilehist && slabs, EGONN_ERR_STATE, "radix_sort: scratch arena too small");
   HIP_CHECK(hipMemsetAsync(slabs, 0, sizeof(int32_t) * passes * (supers + 1) * 256, stream));
 
@@ -507,13 +507,13 @@ __global__ __launch_bounds__(SORT_BLOCK) void sort_seg_scatter_kernel(
   }
 }
 
-// scratch of the segmented sort inside ctx->sort_arena (deterministic for (n, B)): per-tile and per-scan digit histograms
-int radix_sort_segments_layout(Ctx* ctx, int64_t n, int B, int32_t** tilehist, int32_t** scanhist) {
+// scratch of the segmented sort inside `ws` (deterministic for (n, B)): per-tile and per-scan digit histograms
+int radix_sort_segments_layout(Arena& ws, int64_t n, int B, int32_t** tilehist, int32_t** scanhist) {
   const int64_t tiles = cdiv(n > 0 ? n : 1, SORT_TILE) + B;
-  EGONN_TRY(ctx->sort_arena.ensure(radix_sort_segments_scratch_bytes(n, B)));
-  ctx->sort_arena.reset();
-  *tilehist = ctx->sort_arena.alloc<int32_t>(tiles * SEG_DIGITS);
-  *scanhist = ctx->sort_arena.alloc<int32_t>((size_t)8 * B * SEG_DIGITS);
+  EGONN_TRY(ws.ensure(radix_sort_segments_scratch_bytes(n, B)));
+  ws.reset();
+  *tilehist = ws.alloc<int32_t>(tiles * SEG_DIGITS);
+  *scanhist = ws.alloc<int32_t>((size_t)8 * B * SEG_DIGITS);
   EGONN_REQUIRE(*tilehist && *scanhist, EGONN_ERR_STATE, "radix_sort: scratch arena too small");
   return EGONN_OK;
 }
@@ -529,9 +529,9 @@ size_t radix_sort_segments_scratch_bytes(int64_t n, int B) {
 // to n (the capacity the buffers and the grid are sized for).  Result: as radix_sort_pairs (keys_res / vals_res).
 // idx_bits > 0: keys_in holds PACKED elements (Morton bits << idx_bits | index inside the scan; vals_in is not read): every pass
 // but the last moves 8 bytes per element, the last one writes the (key | scan, value) pairs described above.
-int radix_sort_segments(Ctx* ctx, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n,
+int radix_sort_segments(Arena& ws, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n,
                         const int64_t* off_dev, int B, int nbits, hipStream_t stream, uint64_t** keys_res, uint32_t** vals_res,
-                        int idx_bits) {
+                        int idx_bits, const void* prezeroed) {
   EGONN_REQUIRE(n >= 0 && n < (int64_t(1) << 31), EGONN_ERR_INVALID, "radix_sort: n=%lld out of range", (long long)n);
   EGONN_REQUIRE(nbits >= 1 && nbits <= 64 && off_dev && B >= 1 && idx_bits >= 0 && nbits + idx_bits <= 64, EGONN_ERR_INVALID,
                 "radix_sort_segments: bad arguments");
@@ -542,10 +542,9 @@ int radix_sort_segments(Ctx* ctx, uint64_t* keys_in, uint32_t* vals_in, uint64_t
   if (n == 0) return EGONN_OK;
   const int64_t tiles = cdiv(n, SORT_TILE) + B;
   int32_t *tilehist = nullptr, *scanhist = nullptr;
-  EGONN_TRY(radix_sort_segments_layout(ctx, n, B, &tilehist, &scanhist));
+  EGONN_TRY(radix_sort_segments_layout(ws, n, B, &tilehist, &scanhist));
   // (plans built from points: the key kernel in front of the sort has zeroed the per-scan histograms already — one memset node less)
-  if (ctx->sort_prezeroed != scanhist) HIP_CHECK(hipMemsetAsync(scanhist, 0, sizeof(int32_t) * passes * B * SEG_DIGITS, stream));
-  ctx->sort_prezeroed = nullptr;
+  if (prezeroed != scanhist) HIP_CHECK(hipMemsetAsync(scanhist, 0, sizeof(int32_t) * passes * B * SEG_DIGITS, stream));
   uint64_t* kb[2] = {keys_in, keys_out};
   uint32_t* vb[2] = {vals_in, vals_out};
   int src = 0;

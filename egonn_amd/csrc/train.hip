@@ -15,8 +15,7 @@
 // SyncBN the (sum, count) vectors are all-reduced over RCCL between the reduction and the element-wise kernel.
 #include <algorithm>
 
-#include "common.h"
-#include "kernels.h"
+#include "model.h"
 
 namespace egonn {
 
@@ -264,8 +263,10 @@ static void launch_sum_partials(const float* partial, int chunks, int64_t size, 
     hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)cdiv(size, 256)), dim3(256), 0, stream, partial, chunks, size, out);
 }
 
-int conv_wgrad(const float* in, const float* dout, const int32_t* nbr, int64_t n_out, int K, int cin, int cout,
-               float* dW, float* scratch, size_t scratch_floats, hipStream_t stream, const RowGroups* rg) {
+// dW[k][ci][co] = sum_o in[nbr[o][k]][ci] * dout[o][co]; nbr == nullptr: identity map (K = 1, dense layer)
+// rg (nullable): the row-group form of the same map when it is built (the pair source of the MFMA kernel)
+static int conv_wgrad(const float* in, const float* dout, const int32_t* nbr, int64_t n_out, int K, int cin, int cout, float* dW,
+                      float* scratch, size_t scratch_floats, hipStream_t stream, const RowGroups* rg = nullptr) {
   const int64_t size = (int64_t)K * cin * cout;
   if (n_out == 0) {
     HIP_CHECK(hipMemsetAsync(dW, 0, (size_t)size * 4, stream));
@@ -557,8 +558,8 @@ __global__ __launch_bounds__(256) void conv0_wgrad_unit_kernel(const float* __re
   for (int e = tid; e < 125 * 32; e += 256) partial[(int64_t)blockIdx.x * (125 * 32) + e] = red[e];
 }
 
-int conv0_wgrad(Ctx* ctx, const float* feat, const float* dout, float* dW, float* scratch, size_t scratch_floats,
-                hipStream_t stream) {
+static int conv0_wgrad(Ctx* ctx, const float* feat, const float* dout, float* dW, float* scratch, size_t scratch_floats,
+                       hipStream_t stream) {
   const Plan& P = ctx->plan;
   const int64_t n0 = P.lv[0].n, size = 125 * 32;
   if (n0 == 0) {
@@ -586,6 +587,59 @@ int conv0_wgrad(Ctx* ctx, const float* feat, const float* dout, float* dW, float
   launch_sum_partials(scratch, (int)chunks, size, dW, stream);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
+}
+
+API int egonn_dense_backward_weight(const float* a, int ca, const float* b, int cb, int64_t n, float* out, float* scratch,
+                                    int64_t scratch_floats, void* stream) {
+  EGONN_REQUIRE(a && b && out && ca >= 1 && cb >= 1 && n >= 0, EGONN_ERR_INVALID, "dense_backward_weight: bad arguments");
+  return conv_wgrad(a, b, nullptr, n, 1, ca, cb, out, scratch, (size_t)scratch_floats, (hipStream_t)stream);
+}
+
+API int egonn_conv_backward_weight(egonn_ctx* c, int level_in, int level_out, int ks, int transposed, const float* in,
+                                   int cin, const float* grad_out, int cout, float* grad_kernel, float* scratch,
+                                   int64_t scratch_floats, void* stream) {
+  REQUIRE_LEVEL(c, level_in);
+  EGONN_REQUIRE(level_out >= 0 && level_out < EGONN_NUM_LEVELS, EGONN_ERR_INVALID, "level %d out of range", level_out);
+  EGONN_REQUIRE(grad_out && grad_kernel, EGONN_ERR_INVALID, "conv_backward_weight: null argument");
+  hipStream_t st = (hipStream_t)stream;
+  const Plan& P = c->plan;
+  if (ks == 5) {
+    EGONN_REQUIRE(level_in == 0 && level_out == 0 && cin == 1 && cout == 32 && !transposed, EGONN_ERR_INVALID,
+                  "conv_backward_weight: k=5 is the 1->32 input layer only");
+    return conv0_wgrad(c, in, grad_out, grad_kernel, scratch, (size_t)scratch_floats, st);   // in == NULL: all ones
+  }
+  EGONN_REQUIRE(in, EGONN_ERR_INVALID, "conv_backward_weight: null input");
+  // the MFMA channel plans take their (input row, output row) pairs from the row-group form of the map: built here if no forward
+  // call did it before, so that the pair source — and with it the fp32 summation order — never depends on the call history
+  if ((ks == 3 || ks == 2) && ((cin == 32 && (cout == 32 || cout == 64)) || (cin == 64 && (cout == 64 || cout == 128)) ||
+                               (cin == 128 && cout == 128))) {
+    const int kind = ks == 3 ? 0 : (transposed ? 2 : 1);
+    if (level_out >= (kind == 2 ? 0 : 1) && level_out < EGONN_NUM_LEVELS - (kind == 2 ? 1 : 0))
+      EGONN_TRY(ensure_rowgroups(c, &kind, &level_out, 1, st));
+  }
+  if (ks == 1) {
+    EGONN_REQUIRE(level_in == level_out && !transposed, EGONN_ERR_INVALID, "1x1 conv cannot change the level");
+    return conv_wgrad(in, grad_out, nullptr, P.lv[level_in].n, 1, cin, cout, grad_kernel, scratch, (size_t)scratch_floats, st);
+  }
+  if (ks == 3) {
+    EGONN_REQUIRE(level_in == level_out && level_in >= 1 && !transposed, EGONN_ERR_INVALID,
+                  "k=3 convolution: levels 1..7, same in/out level");
+    return conv_wgrad(in, grad_out, P.lv[level_in].nbr27, P.lv[level_in].n, 27, cin, cout, grad_kernel, scratch,
+                      (size_t)scratch_floats, st, &P.lv[level_in].rg27);
+  }
+  if (ks == 2 && !transposed) {
+    EGONN_REQUIRE(level_out == level_in + 1, EGONN_ERR_INVALID, "k=2,s=2 convolution maps level l to l+1");
+    return conv_wgrad(in, grad_out, P.lv[level_out].nbr8, P.lv[level_out].n, 8, cin, cout, grad_kernel, scratch,
+                      (size_t)scratch_floats, st, &P.lv[level_out].rg8);
+  }
+  if (ks == 2 && transposed) {
+    EGONN_REQUIRE(level_out == level_in - 1 && level_out >= 0, EGONN_ERR_INVALID, "transposed conv maps level l to l-1");
+    if (level_out == 0) EGONN_TRY(ensure_level0_parent_table(c, st));
+    return conv_wgrad(in, grad_out, P.lv[level_out].nbrT, P.lv[level_out].n, 8, cin, cout, grad_kernel, scratch,
+                      (size_t)scratch_floats, st, &P.lv[level_out].rgT);
+  }
+  set_error("conv_backward_weight: kernel_size %d not supported", ks);
+  return EGONN_ERR_INVALID;
 }
 
 // ------------------------------------------------------------------------------------------- column statistics
@@ -771,18 +825,19 @@ __global__ __launch_bounds__(256) void sum_partials_block_kernel(const double* _
   if (t == 0) out[i] = red[0];
 }
 
-int col_stats(int mode, const float* a, const float* b, const float* mask, const float* m, int64_t n, int c, double* out2c,
-              float* scratch_f, size_t scratch_floats, hipStream_t stream) {
+API int egonn_col_stats(int mode, const float* a, const float* b, const float* mask, const float* m, int64_t n, int c, double* out2c,
+                        float* scratch_f, int64_t scratch_floats, void* stream) {
   EGONN_REQUIRE(c >= 1 && c <= 256, EGONN_ERR_INVALID, "col_stats: %d channels unsupported (1..256)", c);
   EGONN_REQUIRE(mode >= 0 && mode <= 3 && a && (mode != 2 || b), EGONN_ERR_INVALID, "col_stats: bad arguments");
   EGONN_REQUIRE((reinterpret_cast<uintptr_t>(out2c) & 7u) == 0 && (reinterpret_cast<uintptr_t>(scratch_f) & 7u) == 0,
                 EGONN_ERR_INVALID, "col_stats: out and scratch hold doubles (8-byte alignment)");
+  hipStream_t st = (hipStream_t)stream;
   if (n == 0) {
-    HIP_CHECK(hipMemsetAsync(out2c, 0, (size_t)2 * c * sizeof(double), stream));
+    HIP_CHECK(hipMemsetAsync(out2c, 0, (size_t)2 * c * sizeof(double), st));
     return EGONN_OK;
   }
   double* scratch = reinterpret_cast<double*>(scratch_f);
-  const size_t scratch_doubles = scratch_floats / 2;
+  const size_t scratch_doubles = (size_t)scratch_floats / 2;
   const bool aligned16 = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(mask) |
                            reinterpret_cast<uintptr_t>(m)) & 15u) == 0;
   if (c % 4 == 0 && c >= 32 && 256 % (c / 4) == 0 && aligned16) {      // 32 / 64 / 128 / 256 channels: 16-byte accesses
@@ -794,13 +849,13 @@ int col_stats(int mode, const float* a, const float* b, const float* mask, const
     while (rpb < CS4_ROWS && (size_t)cdiv(n, rpb) * 2 * c > scratch_doubles) rpb <<= 1;
     const int64_t blocks4 = cdiv(n, rpb);
     EGONN_REQUIRE(scratch && scratch_doubles >= (size_t)blocks4 * 2 * c, EGONN_ERR_INVALID,
-                  "col_stats: scratch too small (%zu < %lld floats)", scratch_floats, (long long)(blocks4 * 4 * c));
-    hipLaunchKernelGGL(col_stats4_kernel, dim3((unsigned)blocks4), dim3(256), 0, stream, mode, a, b, mask, m, n, c, rpb, scratch);
+                  "col_stats: scratch too small (%zu < %lld floats)", (size_t)scratch_floats, (long long)(blocks4 * 4 * c));
+    hipLaunchKernelGGL(col_stats4_kernel, dim3((unsigned)blocks4), dim3(256), 0, st, mode, a, b, mask, m, n, c, rpb, scratch);
     if (blocks4 >= 256)
-      hipLaunchKernelGGL(sum_partials_block_kernel, dim3((unsigned)(2 * c)), dim3(256), 0, stream, scratch, (int)blocks4,
+      hipLaunchKernelGGL(sum_partials_block_kernel, dim3((unsigned)(2 * c)), dim3(256), 0, st, scratch, (int)blocks4,
                          (int64_t)2 * c, out2c);
     else
-      hipLaunchKernelGGL(sum_partials_wave_kernel, dim3((unsigned)(2 * c)), dim3(64), 0, stream, scratch, (int)blocks4,
+      hipLaunchKernelGGL(sum_partials_wave_kernel, dim3((unsigned)(2 * c)), dim3(64), 0, st, scratch, (int)blocks4,
                          (int64_t)2 * c, out2c);
     HIP_CHECK(hipGetLastError());
     return EGONN_OK;
@@ -809,10 +864,10 @@ int col_stats(int mode, const float* a, const float* b, const float* mask, const
   while (cp < c) cp <<= 1;
   const int64_t blocks = cdiv(n, CS_ROWS);
   EGONN_REQUIRE(scratch && scratch_doubles >= (size_t)blocks * 2 * c, EGONN_ERR_INVALID,
-                "col_stats: scratch too small (%zu < %lld floats)", scratch_floats, (long long)(blocks * 4 * c));
-  hipLaunchKernelGGL(col_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, mode, a, b, mask, m, n, c, cp,
+                "col_stats: scratch too small (%zu < %lld floats)", (size_t)scratch_floats, (long long)(blocks * 4 * c));
+  hipLaunchKernelGGL(col_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, mode, a, b, mask, m, n, c, cp,
                      scratch);
-  hipLaunchKernelGGL(sum_partials_wave_kernel, dim3((unsigned)(2 * c)), dim3(64), 0, stream, scratch, (int)blocks,
+  hipLaunchKernelGGL(sum_partials_wave_kernel, dim3((unsigned)(2 * c)), dim3(64), 0, st, scratch, (int)blocks,
                      (int64_t)2 * c, out2c);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
@@ -862,17 +917,20 @@ __global__ void bn_bwd_finalize_kernel(const double* __restrict__ local, const d
   out5[3 * c + i] = (float)(local[c + i] * inv);
   out5[4 * c + i] = (float)local[i];
 }
-int bn_fwd_finalize(const double* sums, const float* m, double n, int c, const float* w, const float* b, float eps,
-                    float momentum, float* running_mean, float* running_var, float* out4, hipStream_t stream) {
-  hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((unsigned)cdiv(c, 64)), dim3(64), 0, stream, sums, m, n, c, w, b, eps,
-                     momentum, running_mean, running_var, out4);
+API int egonn_bn_train_finalize(const double* sums, const float* m, double n, int c, const float* w, const float* b, float eps,
+                                float momentum, float* running_mean, float* running_var, float* out4, void* stream) {
+  EGONN_REQUIRE(sums && m && w && b && out4 && n >= 1.0 && c >= 1, EGONN_ERR_INVALID, "bn_train_finalize: bad arguments");
+  hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((unsigned)cdiv(c, 64)), dim3(64), 0, (hipStream_t)stream, sums, m, n, c, w, b,
+                     eps, momentum, running_mean, running_var, out4);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
-int bn_bwd_finalize(const double* local, const double* global, double n, int c, const float* w, const float* mean,
-                    const float* invstd, float* out5, hipStream_t stream) {
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(c, 64)), dim3(64), 0, stream, local, global, n, c, w, mean,
-                     invstd, out5);
+API int egonn_bn_backward_finalize(const double* local, const double* global, double n, int c, const float* w, const float* mean,
+                                   const float* invstd, float* out5, void* stream) {
+  EGONN_REQUIRE(local && global && w && mean && invstd && out5 && n >= 1.0, EGONN_ERR_INVALID,
+                "bn_backward_finalize: bad arguments");
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)cdiv(c, 64)), dim3(64), 0, (hipStream_t)stream, local, global, n, c, w,
+                     mean, invstd, out5);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -898,19 +956,22 @@ __global__ void affine3_kernel(const float* __restrict__ g, const float* __restr
   const float gq = (mask && !(mask[i] > 0.f)) ? 0.f : g[i];
   out[i] = fmaf(A[ci], gq, fmaf(Bv[ci], x[i], Cv[ci]));
 }
-int affine_act(const float* x, const float* A, const float* B, int64_t n, int c, int relu, float* out, hipStream_t stream) {
+API int egonn_affine_act(const float* x, const float* A, const float* B, int64_t n, int c, int relu, float* out, void* stream) {
+  EGONN_REQUIRE(x && A && B && out, EGONN_ERR_INVALID, "affine_act: null argument");
   const int64_t total = n * c;
   if (total == 0) return EGONN_OK;
-  hipLaunchKernelGGL(affine_act_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, x, A, B, total, c, relu, out);
+  hipLaunchKernelGGL(affine_act_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, A, B, total, c,
+                     relu, out);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
-int affine3(const float* g, const float* mask, const float* x, const float* A, const float* B, const float* C, int64_t n,
-            int c, float* out, hipStream_t stream) {
+API int egonn_affine3(const float* g, const float* mask, const float* x, const float* A, const float* B, const float* C, int64_t n,
+                      int c, float* out, void* stream) {
+  EGONN_REQUIRE(g && x && A && B && C && out, EGONN_ERR_INVALID, "affine3: null argument");
   const int64_t total = n * c;
   if (total == 0) return EGONN_OK;
-  hipLaunchKernelGGL(affine3_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, g, mask, x, A, B, C, total, c,
-                     out);
+  hipLaunchKernelGGL(affine3_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, g, mask, x, A, B, C,
+                     total, c, out);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -1004,28 +1065,38 @@ __global__ void seg_finish_kernel(const float* __restrict__ partial, int64_t bc,
   for (int ch = 0; ch < SEG_CHUNKS; ++ch) s += partial[(b * SEG_CHUNKS + ch) * c + ci];
   out[i] = s;
 }
-int seg_sums2(int mode, const float* a, const float* b, const float* x2, const float* p, const int32_t* boff, int B, int c,
-              float* out_bc, float* scratch, size_t scratch_floats, hipStream_t stream) {
+API int egonn_segment_sums(egonn_ctx* ctx, int level, int mode, const float* a, const float* b, const float* x2, const float* p,
+                           int c, float* out_bc, float* scratch, int64_t scratch_floats, void* stream) {
+  REQUIRE_LEVEL(ctx, level);
+  EGONN_REQUIRE(a && out_bc && mode >= 0 && mode <= 2 && (mode == 1 || b) && (mode != 2 || x2) && (mode != 1 || p),
+                EGONN_ERR_INVALID, "segment_sums: bad arguments");
+  const int B = ctx->plan.batch;
   EGONN_REQUIRE(c >= 1 && c <= 256 && 256 % c == 0, EGONN_ERR_INVALID, "segment sums: %d channels unsupported", c);
-  EGONN_REQUIRE(scratch && scratch_floats >= (size_t)B * SEG_CHUNKS * c, EGONN_ERR_INVALID, "segment sums: scratch too small");
-  hipLaunchKernelGGL(seg_sums2_kernel, dim3(SEG_CHUNKS, B), dim3(256), 0, stream, mode, a, b, x2, p, boff, c, scratch);
-  hipLaunchKernelGGL(seg_finish_kernel, dim3((unsigned)cdiv((int64_t)B * c, 256)), dim3(256), 0, stream, scratch,
-                     (int64_t)B * c, c, out_bc);
+  EGONN_REQUIRE(scratch && (size_t)scratch_floats >= (size_t)B * SEG_CHUNKS * c, EGONN_ERR_INVALID,
+                "segment sums: scratch too small");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(seg_sums2_kernel, dim3(SEG_CHUNKS, B), dim3(256), 0, st, mode, a, b, x2, p, ctx->plan.lv[level].boff, c,
+                     scratch);
+  hipLaunchKernelGGL(seg_finish_kernel, dim3((unsigned)cdiv((int64_t)B * c, 256)), dim3(256), 0, st, scratch, (int64_t)B * c, c,
+                     out_bc);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
 
-int gate_residual_forward(const float* x, const float* gate, const float* res, const int32_t* boff, int B, int64_t n, int c,
-                          int relu, float* out, hipStream_t stream) {
-  const int64_t total = n * c;
+API int egonn_gate_residual(egonn_ctx* ctx, int level, const float* x, const float* gate, const float* res, int c, int relu,
+                            float* out, void* stream) {
+  REQUIRE_LEVEL(ctx, level);
+  EGONN_REQUIRE(x && out, EGONN_ERR_INVALID, "gate_residual: null argument");
+  const int64_t total = ctx->plan.lv[level].n * c;
   if (total == 0) return EGONN_OK;
-  hipLaunchKernelGGL(gate_res_fwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, x, gate, res, boff, B,
-                     total, c, relu, out);
+  hipLaunchKernelGGL(gate_res_fwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, gate, res,
+                     ctx->plan.lv[level].boff, ctx->plan.batch, total, c, relu, out);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
-int gate_residual_backward(const float* dout, const float* out, const float* gate, const int32_t* boff, int B, int64_t n,
-                           int c, float* dx, float* dres, hipStream_t stream) {
+// gate == nullptr: the plain ReLU backward (boff is then not read)
+static int gate_residual_backward(const float* dout, const float* out, const float* gate, const int32_t* boff, int B, int64_t n,
+                                  int c, float* dx, float* dres, hipStream_t stream) {
   const int64_t total = n * c;
   if (total == 0) return EGONN_OK;
   hipLaunchKernelGGL(gate_res_bwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, dout, out, gate, boff, B,
@@ -1033,11 +1104,24 @@ int gate_residual_backward(const float* dout, const float* out, const float* gat
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
-int seg_broadcast(const float* v, const int32_t* boff, int B, int64_t n, int c, int mean, float* out, hipStream_t stream) {
-  const int64_t total = n * c;
+API int egonn_gate_residual_backward(egonn_ctx* ctx, int level, const float* dout, const float* out, const float* gate, int c,
+                                     float* dx, float* dres, void* stream) {
+  REQUIRE_LEVEL(ctx, level);
+  EGONN_REQUIRE(dout && dx, EGONN_ERR_INVALID, "gate_residual_backward: null argument");
+  return gate_residual_backward(dout, out, gate, ctx->plan.lv[level].boff, ctx->plan.batch, ctx->plan.lv[level].n, c, dx, dres,
+                                (hipStream_t)stream);
+}
+API int egonn_relu_backward(const float* dout, const float* out, int64_t n, int c, float* dx, void* stream) {
+  EGONN_REQUIRE(dout && out && dx, EGONN_ERR_INVALID, "relu_backward: null argument");
+  return gate_residual_backward(dout, out, nullptr, nullptr, 0, n, c, dx, nullptr, (hipStream_t)stream);
+}
+API int egonn_segment_broadcast(egonn_ctx* ctx, int level, const float* v, int c, int mean, float* out, void* stream) {
+  REQUIRE_LEVEL(ctx, level);
+  EGONN_REQUIRE(v && out, EGONN_ERR_INVALID, "segment_broadcast: null argument");
+  const int64_t total = ctx->plan.lv[level].n * c;
   if (total == 0) return EGONN_OK;
-  hipLaunchKernelGGL(seg_broadcast_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, v, boff, B, total, c,
-                     mean, out);
+  hipLaunchKernelGGL(seg_broadcast_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, v,
+                     ctx->plan.lv[level].boff, ctx->plan.batch, total, c, mean, out);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -1055,12 +1139,14 @@ __global__ void gem_bwd_kernel(const float* __restrict__ x, const float* __restr
   if (v >= 1e-6f) o = coef[(int64_t)sample_of(boff, B, r) * c + ci] * powf(v, pexp[0] - 1.f);
   dx[i] = o;
 }
-int gem_backward_rows(const float* x, const float* coef, const float* p, const int32_t* boff, int B, int64_t n, int c,
-                      float* dx, hipStream_t stream) {
-  const int64_t total = n * c;
+API int egonn_gem_backward(egonn_ctx* ctx, int level, const float* x, const float* coef, const float* p, int c, float* dx,
+                           void* stream) {
+  REQUIRE_LEVEL(ctx, level);
+  EGONN_REQUIRE(x && coef && p && dx, EGONN_ERR_INVALID, "gem_backward: null argument");
+  const int64_t total = ctx->plan.lv[level].n * c;
   if (total == 0) return EGONN_OK;
-  hipLaunchKernelGGL(gem_bwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, x, coef, p, boff, B, total, c,
-                     dx);
+  hipLaunchKernelGGL(gem_bwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, coef, p,
+                     ctx->plan.lv[level].boff, ctx->plan.batch, total, c, dx);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -1139,17 +1225,19 @@ __global__ __launch_bounds__(256) void eca_gate_bwd_kernel(const float* __restri
     __syncthreads();
   }
 }
-int eca_gate_forward(const float* mean, const float* w, int ks, int B, int c, float* gate, hipStream_t stream) {
+API int egonn_eca_gate(const float* mean, const float* w, int ks, int B, int c, float* gate, void* stream) {
+  EGONN_REQUIRE(mean && w && gate, EGONN_ERR_INVALID, "eca_gate: null argument");
   EGONN_REQUIRE(c >= 1 && c <= 256 && ks >= 1 && ks <= 15 && (ks & 1), EGONN_ERR_INVALID, "eca_gate: bad shape");
   if (B == 0) return EGONN_OK;
-  hipLaunchKernelGGL(eca_gate_fwd_kernel, dim3((unsigned)B), dim3(256), 0, stream, mean, w, ks, c, gate);
+  hipLaunchKernelGGL(eca_gate_fwd_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, mean, w, ks, c, gate);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
-int eca_gate_backward(const float* dgate, const float* gate, const float* mean, const float* w, int ks, int B, int c,
-                      float* dmean, float* dw, hipStream_t stream) {
+API int egonn_eca_gate_backward(const float* dgate, const float* gate, const float* mean, const float* w, int ks, int B, int c,
+                                float* dmean, float* dw, void* stream) {
+  EGONN_REQUIRE(dgate && gate && mean && w && dmean && dw, EGONN_ERR_INVALID, "eca_gate_backward: null argument");
   EGONN_REQUIRE(c >= 1 && c <= 256 && ks >= 1 && ks <= 15 && (ks & 1), EGONN_ERR_INVALID, "eca_gate: bad shape");
-  hipLaunchKernelGGL(eca_gate_bwd_kernel, dim3(1), dim3(256), 0, stream, dgate, gate, mean, w, ks, B, c, dmean, dw);
+  hipLaunchKernelGGL(eca_gate_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, dgate, gate, mean, w, ks, B, c, dmean, dw);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -1270,20 +1358,24 @@ static int se_check(int B, int c, int h) {
                 B, c, h);
   return EGONN_OK;
 }
-int se_gate_forward(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, int B, int c, int h,
-                    float* gate, float* hidden_out, hipStream_t stream) {
+API int egonn_se_gate(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, int B, int c, int h,
+                      float* gate, float* hidden_out, void* stream) {
+  EGONN_REQUIRE(mean && w1 && b1 && w2 && b2 && gate, EGONN_ERR_INVALID, "se_gate: null argument");
   EGONN_TRY(se_check(B, c, h));
   if (B == 0) return EGONN_OK;
-  hipLaunchKernelGGL(se_gate_fwd_kernel, dim3((unsigned)B), dim3(256), 0, stream, mean, w1, b1, w2, b2, c, h, gate, hidden_out);
+  hipLaunchKernelGGL(se_gate_fwd_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, mean, w1, b1, w2, b2, c, h, gate,
+                     hidden_out);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
-int se_gate_backward(const float* dgate, const float* gate, const float* hid, const float* mean, const float* w1,
-                     const float* w2, int B, int c, int h, float* dmean, float* dw1, float* db1, float* dw2, float* db2,
-                     hipStream_t stream) {
+API int egonn_se_gate_backward(const float* dgate, const float* gate, const float* hid, const float* mean, const float* w1,
+                               const float* w2, int B, int c, int h, float* dmean, float* dw1, float* db1, float* dw2, float* db2,
+                               void* stream) {
+  EGONN_REQUIRE(dgate && gate && hid && mean && w1 && w2 && dmean && dw1 && db1 && dw2 && db2, EGONN_ERR_INVALID,
+                "se_gate_backward: null argument");
   EGONN_TRY(se_check(B, c, h));
-  hipLaunchKernelGGL(se_gate_bwd_kernel, dim3(1), dim3(256), 0, stream, dgate, gate, hid, mean, w1, w2, B, c, h, dmean, dw1, db1,
-                     dw2, db2);
+  hipLaunchKernelGGL(se_gate_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, dgate, gate, hid, mean, w1, w2, B, c, h, dmean,
+                     dw1, db1, dw2, db2);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -1303,10 +1395,11 @@ __global__ void act_bwd_kernel(int act, const float* __restrict__ g, const float
   else if (act == ACT_SIGMOID) d = yv * (1.f - yv);
   out[i] = g[i] * d;
 }
-int act_backward(int act, const float* g, const float* y, int64_t n, int c, float* out, hipStream_t stream) {
+API int egonn_act_backward(int act, const float* g, const float* y, int64_t n, int c, float* out, void* stream) {
+  EGONN_REQUIRE(g && y && out && act >= 0 && act <= 4, EGONN_ERR_INVALID, "act_backward: bad arguments");
   const int64_t total = n * c;
   if (total == 0) return EGONN_OK;
-  hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, stream, act, g, y, total, out);
+  hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, act, g, y, total, out);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -1336,9 +1429,11 @@ __global__ __launch_bounds__(256) void l2norm_fwd_bwd_kernel(const float* __rest
   const bool clamped = !(nrm > 1e-12f);
   for (int i = lane; i < c; i += 64) out[row * c + i] = clamped ? q[i] * inv : (q[i] - p[i] * inv * gy) * inv;
 }
-int l2norm_rows(const float* x, const float* g, int64_t n, int c, float* out, hipStream_t stream) {
+// g == nullptr: out = normalize(x) ; else out = d normalize / dx applied to g
+API int egonn_l2_normalize(const float* x, const float* g, int64_t n, int c, float* out, void* stream) {
+  EGONN_REQUIRE(x && out && c >= 1, EGONN_ERR_INVALID, "l2_normalize: bad arguments");
   if (n == 0) return EGONN_OK;
-  hipLaunchKernelGGL(l2norm_fwd_bwd_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, stream, x, g, n, c, out);
+  hipLaunchKernelGGL(l2norm_fwd_bwd_kernel, dim3((unsigned)cdiv(n, 4)), dim3(256), 0, (hipStream_t)stream, x, g, n, c, out);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }

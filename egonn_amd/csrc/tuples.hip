@@ -21,8 +21,6 @@
 
 #pragma clang fp contract(off)
 
-#define API extern "C" __attribute__((visibility("default")))
-
 namespace egonn {
 
 static constexpr int RJ_WG = 256;                 // 4 waves
