@@ -22,6 +22,7 @@ from .augment import (TrainTransform, TrainSetTransform, TrainBatcher, JitterPoi
 from .tuples import (TrainingTuple, EvaluationTuple, EvaluationSet, save_training_tuples, load_training_tuples, radius_neighbors,
                      count_within, relative_poses, CloudBank, generate_training_tuples, filter_query_elements,
                      generate_evaluation_set, TupleIndex, BatchSampler, TrainingSet)
+from .relocalize import KeypointMap, verify_candidates, Relocalizer, evaluate_relocalization
 from .scan_context import ScanContext, ScanContextManager, sc2rk, distance_sc, evaluate as evaluate_scan_context
 
 __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "MinkHead", "MinkTrunk",
@@ -36,4 +37,5 @@ __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "Mink
            "TrainingTuple", "EvaluationTuple", "EvaluationSet", "save_training_tuples", "load_training_tuples", "radius_neighbors",
            "count_within", "relative_poses", "CloudBank", "generate_training_tuples", "filter_query_elements",
            "generate_evaluation_set", "TupleIndex", "BatchSampler", "TrainingSet",
+           "KeypointMap", "verify_candidates", "Relocalizer", "evaluate_relocalization",
            "ScanContext", "ScanContextManager", "sc2rk", "distance_sc", "evaluate_scan_context"]

@@ -140,6 +140,11 @@ _SIGS = [
     ("egonn_pair_masks", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     ("egonn_relative_poses", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     ("egonn_gather_clouds", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int, _P, C.c_int64, _P, _P, _P]),
+    ("egonn_match_candidates_scratch_bytes", C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    ("egonn_match_candidates", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                                         C.c_int64, _P]),
+    ("egonn_gather_candidates", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    ("egonn_pick_candidates", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int] + [_P] * 12),
     ("egonn_profile_enable", C.c_int, [_P, C.c_int, C.c_char_p]),
     ("egonn_profile_fetch", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),

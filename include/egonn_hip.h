@@ -751,6 +751,52 @@ int egonn_relative_poses(const double* poses, int64_t n_poses, const int32_t* id
 int egonn_gather_clouds(const double* bank, int64_t n_bank, const int64_t* bank_offsets, int64_t n_clouds, const int32_t* pick,
                         int n_pick, double* out, int64_t capacity, int64_t* out_offsets, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ relocalisation against a keypoint map (csrc/relocalize.hip)
+ * A query scan is placed in the map frame by registering it against its top-k retrieved map entries (egonn_knn) and keeping
+ * the entry with the most inliers: P_query = P_map[best] @ T, T = the transform of egonn_registration_finish, which maps query
+ * keypoints into the candidate's frame (misc/poses.py: T_gt = inv(P_map) @ P_query).  The map is resident: descriptors
+ * bank_feat (n_bank, n_max, dim) f32, keypoints bank_kp (n_bank, n_max, 3) f32, counts bank_n (n_bank) int32, poses
+ * map_pose (n_bank,4,4) f64.  Queries: q_feat (n_queries, n_max, dim), q_kp, q_n; nn_index (n_queries, k) DEVICE int32 map
+ * entries per query, -1 = none (what egonn_knn writes beyond the map).  Pair p = q * k + c.  1 <= k <= 1024, n_queries * k <=
+ * 2^20, n_bank >= 1, n_max <= 256.  The sequence egonn_match_candidates, egonn_gather_candidates, egonn_ransac_pairs,
+ * egonn_registration_finish, egonn_pick_candidates has no host synchronisation and can be captured. */
+enum { EGONN_RELOC_NO_CANDIDATE = 1,     /* candidate index -1 (or outside the map): an empty pair */
+       EGONN_RELOC_BAD_INDEX = 2,        /* candidate index < -1 or >= n_bank: an empty pair, nothing read */
+       EGONN_RELOC_UNVERIFIED = 4 };     /* per query: no candidate with a model and min_inliers inliers */
+/* bytes of the scratch of egonn_match_candidates (-1 on bad arguments) */
+int64_t egonn_match_candidates_scratch_bytes(int n_queries, int k, int n_max);
+/* egonn_match_mutual of every (query, candidate) pair with the candidate's descriptors read from the bank by index: the
+ * same rules and the same bits (fp64 squared L2, k ascending, one fma per term; ties: lowest index; (i, j(i)) kept iff
+ * i(j(i)) == i; fewer than 3: every (i, j(i)); ascending i; counts clipped to [0, n_max]).  Each distance is computed once,
+ * by workgroups of 64 query rows x 32 candidate rows whose partial minima go to scratch and are merged in ascending tile
+ * order.  dim a multiple of 4 up to 256, descriptors 16-byte aligned, scratch 8-byte aligned.  corr (n_queries * k, n_max, 2)
+ * int32, n_corr (n_queries * k), status (n_queries * k) int32 of EGONN_RELOC_* bits (nullable).  An invalid index gives
+ * n_corr = 0 and all rows -1. */
+int egonn_match_candidates(const float* q_feat, const int32_t* q_n, const float* bank_feat, const int32_t* bank_n,
+                           const int32_t* nn_index, int n_queries, int k, int n_bank, int n_max, int dim, int32_t* corr,
+                           int32_t* n_corr, int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);
+/* the keypoint operands of egonn_ransac_pairs / egonn_registration_finish for the same pairs: kp1 (P, n_max, 3) = the
+ * query's keypoints repeated, kp2 = the candidate's (zeros for an invalid index), n1 = q_n[q], n2 = bank_n[index] (0 for an
+ * invalid index), pair_id = (query_id[q] * 1000003 + index) mod 2^30 with query_id (n_queries) DEVICE int32, null = q: a
+ * pair's draws depend on the query's id and the map entry, not on the candidate's rank nor on the batch. */
+int egonn_gather_candidates(const float* q_kp, const int32_t* q_n, const float* bank_kp, const int32_t* bank_n,
+                            const int32_t* nn_index, const int32_t* query_id, int n_queries, int k, int n_bank, int n_max,
+                            float* kp1, float* kp2, int32_t* n1, int32_t* n2, int32_t* pair_id, void* stream);
+/* per query over the k results of egonn_registration_finish (T (P,4,4) f64, inliers, inlier_rmse, reg_status (P); rte, rre,
+ * success (P) nullable): candidates ordered by most inliers, then lowest inlier_rmse, then lowest rank; invalid candidates
+ * last in rank order.  reranked (n_queries, k) = the map indices in that order (-1 for invalid ones).  The head of the order
+ * wins if it is valid, has a model (no EGONN_REG_STATUS_NO_MODEL) and inliers >= min_inliers: best_rank, best_index, best_inliers
+ * (n_queries), T_rel (n_queries,4,4) = its T, pose = map_pose[best] @ T_rel as the affine product (three-term dot products
+ * summed left to right, then the translation added; last row 0 0 0 1), best_rte / best_rre / best_success (nullable) = its
+ * metrics.  Otherwise EGONN_RELOC_UNVERIFIED: best_rank = best_index = -1, best_inliers = 0, T_rel = pose = identity, best_rte =
+ * best_rre = -1, best_success = 0.  safe_pick (n_queries) = best_index when verified, else nn_index[q][0] clamped to
+ * [0, n_bank): a pick egonn_gather_clouds accepts.  status (n_queries) = OR of the candidates' EGONN_RELOC_* bits. */
+int egonn_pick_candidates(const int32_t* nn_index, int n_queries, int k, int n_bank, const double* map_pose, const double* T,
+                          const int32_t* inliers, const double* inlier_rmse, const int32_t* reg_status, const double* rte,
+                          const double* rre, const int32_t* success, int min_inliers, int32_t* best_rank, int32_t* best_index,
+                          int32_t* reranked, double* T_rel, double* pose, int32_t* safe_pick, int32_t* best_inliers,
+                          int32_t* status, double* best_rte, double* best_rre, int32_t* best_success, void* stream);
+
 /* ------------------------------------------------------------------ launch timing (bench.py roofline leg)
  * mode 0: off; 1: time every tagged sparse-conv launch (event records around it); 2: only launches whose tag contains
  * `filter`, with the events attached to the kernel dispatch itself (the kernel's own begin..end, also when other streams
