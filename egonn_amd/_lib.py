@@ -118,7 +118,8 @@ _SIGS = [
     ("egonn_knn", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P]),
     ("egonn_recall_counts", C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     ("egonn_registration_scratch_bytes", C.c_int64, [C.c_int, C.c_int, C.c_int]),
-    ("egonn_match_mutual", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    ("egonn_match_mutual_scratch_bytes", C.c_int64, [C.c_int, C.c_int]),
+    ("egonn_match_mutual", C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P]),
     ("egonn_ransac_pairs", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, _P,
                                      C.c_int64, _P, _P, _P]),
     ("egonn_registration_finish", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, _P,
@@ -225,6 +226,44 @@ def call(device: torch.device, fn, *args):
 
 def _dev_f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def as_dev(x, dev, dtype) -> torch.Tensor:
+    """anything array-like as a contiguous tensor of `dtype` on `dev` (no copy when it is one already)"""
+    return torch.as_tensor(x).to(device=dev, dtype=dtype).contiguous()
+
+
+def scratch(nbytes: int, dev) -> torch.Tensor:
+    """caller-owned scratch of at least `nbytes` (8 at the least: a *_scratch_bytes of -1 still yields a pointer, and the call
+    it is handed to raises), 8-byte aligned: int64 elements, so `numel() * 8` is its size"""
+    return torch.empty((max(int(nbytes), 8) + 7) // 8, dtype=torch.int64, device=dev)
+
+
+# concatenated clouds: points (n, 3), cloud c = rows [offsets[c], offsets[c + 1])
+def check_cloud(name, x):
+    shape = tuple(getattr(x, "shape", ()))
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{name}: expected (n, 3) points, got shape {shape}")
+
+
+def check_offsets(name, off) -> int:
+    """-> the number of clouds"""
+    shape = tuple(getattr(off, "shape", (len(off),) if hasattr(off, "__len__") else ()))
+    if len(shape) != 1 or shape[0] < 2:
+        raise ValueError(f"{name}: offsets must be a 1-D sequence of n_clouds + 1 entries, got shape {shape}")
+    return shape[0] - 1
+
+
+def concat_clouds(clouds, dev):
+    """per-scan (n,3) arrays -> (points (sum n, 3) f32 on the device, (len+1,) int64 offsets)"""
+    ts = [torch.as_tensor(c) for c in clouds]
+    for c in ts:
+        check_cloud("cloud", c)
+    off = [0]
+    for c in ts:
+        off.append(off[-1] + c.shape[0])
+    pts = torch.cat([c.to(device=dev, dtype=torch.float32) for c in ts]) if ts else torch.zeros((0, 3), device=dev)
+    return pts, torch.tensor(off, dtype=torch.int64, device=dev)
 
 
 def require_gpu() -> torch.device:

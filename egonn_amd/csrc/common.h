@@ -63,6 +63,8 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+__host__ __device__ static inline int clipi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }   // v clamped to [0, hi]
+__host__ __device__ static inline int64_t clipi(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // "set this kernel's dynamic-LDS attribute once" — once per (kernel, DEVICE), safe from several host threads (a process may
 // hold contexts on several GPUs; a racing second call only repeats an idempotent setting)
@@ -310,6 +312,14 @@ int ensure_level0_parent_table(Ctx* ctx, hipStream_t stream);   // coords.hip
 // 2 = transposed map onto `level`; every missing table of the request is built in one launch
 int ensure_rowgroups(Ctx* ctx, const int* kinds, const int* levels, int count, hipStream_t stream);
 int rowgroup_cap_groups(const Plan& P, int level);   // groups the row-group tables of a map onto `level` hold (a function of P.cap, P.batch)
+
+// ------------------------------------------------------------------ keypoint sets (match.hip, registration.hip, relocalize.hip)
+static constexpr int KP_MAX_N = 256;             // keypoints per side (the reference evaluates n_k = 128 and 256)
+static constexpr int KP_MAX_D = 256;             // descriptor width
+static constexpr int KP_MAX_PAIRS = 1 << 20;     // pairs per call
+static constexpr int REL_MAX_K = 1024;           // candidates per query
+int reg_check_shape(const char* who, int P, int n_max);                     // registration.hip
+int rel_check_shape(const char* who, int Q, int k, int M, int n_max);       // relocalize.hip
 
 // ------------------------------------------------------------------ sort.hip
 // LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits).  Result lands in (keys_out, vals_out) — or, when the caller

@@ -44,15 +44,14 @@ static constexpr int DS_BITS = 21;                // voxel index bits per axis
 static constexpr int ICP_CELL_MAX = 65535;        // cell index bits per axis: 16
 static constexpr uint64_t DS_INVALID = ~0ull;     // key of a dropped / out-of-cloud point (valid keys have bit 63 clear)
 
-__device__ static inline int64_t icp_clip(int64_t v, int64_t n) { return v < 0 ? 0 : (v > n ? n : v); }
 
 // segment of position i: the largest c in [0, C) with clip(off[c]) <= i, or -1 when i is beyond the last segment
 __device__ static inline int icp_segment(const int64_t* __restrict__ off, int C, int64_t n, int64_t i) {
-  if (i >= icp_clip(off[C], n)) return -1;
+  if (i >= clipi(off[C], n)) return -1;
   int lo = 0, hi = C - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
-    if (icp_clip(off[mid], n) <= i) lo = mid; else hi = mid - 1;
+    if (clipi(off[mid], n) <= i) lo = mid; else hi = mid - 1;
   }
   return lo;
 }
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(ICP_WG) void ds_min_kernel(const float* __restrict_
                                                         int32_t* __restrict__ status) {
   __shared__ double s_m[3][ICP_WG];
   const int c = blockIdx.x, t = threadIdx.x;
-  const int64_t lo = icp_clip(off[c], n), hi = icp_clip(off[c + 1], n);
+  const int64_t lo = clipi(off[c], n), hi = clipi(off[c + 1], n);
   double m[3] = {INFINITY, INFINITY, INFINITY};
   for (int64_t i = lo + t; i < hi; i += ICP_WG) {
     const float* p = pts + i * 3;
@@ -139,7 +138,7 @@ __device__ static inline bool ds_is_head(const uint64_t* __restrict__ keys, cons
   if (c < 0 || (status[c] & EGONN_ICP_STATUS_RANGE)) return false;
   const uint64_t k = keys[i];
   if (k == DS_INVALID) return false;
-  return i == icp_clip(off[c], n) || keys[i - 1] != k;
+  return i == clipi(off[c], n) || keys[i - 1] != k;
 }
 
 __global__ __launch_bounds__(ICP_WG) void ds_count_kernel(const uint64_t* __restrict__ keys, const int64_t* __restrict__ off, int C,
@@ -185,7 +184,7 @@ __global__ __launch_bounds__(ICP_WG) void ds_scan_kernel(const uint64_t* __restr
   __threadfence_block();
   __syncthreads();
   for (int c = t; c <= C; c += ICP_WG) {
-    const int64_t pos = icp_clip(off[c], n);
+    const int64_t pos = clipi(off[c], n);
     const int64_t b = pos / ICP_WG;
     int64_t cnt = 0;
     if (b < nb) {
@@ -218,7 +217,7 @@ __global__ __launch_bounds__(ICP_WG) void ds_write_kernel(const float* __restric
   int64_t o = blockpre[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
   for (int k = 0; k < w; ++k) o += s_w[k];
   if (o >= n) return;                         // cannot happen (heads <= points); keeps the store in bounds regardless
-  const int64_t hi = icp_clip(off[c + 1], n);
+  const int64_t hi = clipi(off[c + 1], n);
   const uint64_t key = keys[i];
   double sx = 0.0, sy = 0.0, sz = 0.0;
   int cnt = 0;
@@ -279,8 +278,8 @@ __global__ __launch_bounds__(ICP_WG) void icp_setup_kernel(const double* __restr
                                                            int32_t* __restrict__ status, double* __restrict__ T_trace, int max_it) {
   __shared__ double s_lo[3][ICP_WG], s_hi[3][ICP_WG];
   const int p = blockIdx.x, t = threadIdx.x;
-  const int64_t so = icp_clip(soff[p], ns_cap), se = icp_clip(soff[p + 1], ns_cap);
-  const int64_t to = icp_clip(toff[p], nt_cap), te = icp_clip(toff[p + 1], nt_cap);
+  const int64_t so = clipi(soff[p], ns_cap), se = clipi(soff[p + 1], ns_cap);
+  const int64_t to = clipi(toff[p], nt_cap), te = clipi(toff[p + 1], nt_cap);
   const int64_t ns = se > so ? se - so : 0, nt = te > to ? te - to : 0;
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int64_t i = to + t; i < to + nt; i += ICP_WG) {
@@ -342,7 +341,7 @@ __global__ __launch_bounds__(ICP_WG) void icp_setup_kernel(const double* __restr
   // first workgroup of the pair in the flat search grid: a function of the sizes of the pairs before it only
   int64_t w = 0;
   for (int b = 0; b < p; ++b) {
-    const int64_t a = icp_clip(soff[b], ns_cap), e = icp_clip(soff[b + 1], ns_cap);
+    const int64_t a = clipi(soff[b], ns_cap), e = clipi(soff[b + 1], ns_cap);
     w += e > a ? (e - a + ICP_WG - 1) / ICP_WG : 0;
   }
   wg0[p] = (int32_t)w;
@@ -387,9 +386,9 @@ __global__ __launch_bounds__(ICP_WG) void icp_gather_kernel(const double* __rest
   if (i >= n) return;
   const int p = icp_segment(off, P, n, i);
   if (p < 0) return;
-  const int64_t first = icp_clip(off[p], n);
+  const int64_t first = clipi(off[p], n);
   int64_t v = (int64_t)vals[i];
-  if (v < first || v >= icp_clip(off[p + 1], n)) v = first;      // cannot happen after a sort of the segment; keeps reads in bounds
+  if (v < first || v >= clipi(off[p + 1], n)) v = first;      // cannot happen after a sort of the segment; keeps reads in bounds
   out_pts[i * 3] = pts[v * 3], out_pts[i * 3 + 1] = pts[v * 3 + 1], out_pts[i * 3 + 2] = pts[v * 3 + 2];
   out_idx[i] = (int32_t)(v - first);
   if (out_keys) out_keys[i] = keys[i];

@@ -5,9 +5,7 @@
 // ransac_n = 3, checkers EdgeLength(0.8) + Distance(0.5), criteria (10000, 0.999)).  Open3D is not part of the reference
 // tree, so what follows restates its documented behaviour [recall], batched over P independent (query, candidate) pairs:
 //
-//   1. reg_match_kernel   d2[i][j] = sum_k (a_ik - b_jk)^2 in fp64 over exactly converted fp32 descriptors, k ascending, one
-//                         fma per term; j(i) = row argmin, i(j) = column argmin, ties: lowest index; keep (i, j(i)) with
-//                         i(j(i)) == i; fewer than 3 such pairs: keep every (i, j(i)).  Compacted in ascending i.
+//   1. egonn_match_mutual (match.hip)  the mutual nearest neighbours of the two descriptor sets, compacted in ascending i.
 //   2. reg_ransac_kernel  hypothesis t = 0 .. H-1, one lane each (see reg_hypothesis below); per workgroup the best
 //                         (inliers, err2, t) goes to scratch.
 //   3. reg_finish_kernel  best over the workgroups' records, the winner's transform again (same code, same bits), the
@@ -39,9 +37,6 @@
 
 namespace egonn {
 
-static constexpr int REG_MAX_N = 256;    // keypoints per side (the reference evaluates n_k = 128 and 256)
-static constexpr int REG_MAX_D = 256;    // descriptor width
-static constexpr int REG_TJ = 32;        // rows of the other side per LDS tile of the matching kernel
 static constexpr int REG_WG = 256;       // lanes = hypotheses per workgroup of the hot loop
 static constexpr double REG_EDGE2 = 0.8 * 0.8;   // CorrespondenceCheckerBasedOnEdgeLength(0.8), on squared lengths
 static constexpr double REG_DEGEN2 = 1e-6;       // |e1 x e2|^2 <= 1e-6 |e1|^2 |e2|^2  <=>  |e1 x e2| <= 1e-3 |e1| |e2|
@@ -65,107 +60,17 @@ __device__ static inline bool reg_better(int c1, double e1, int t1, int c2, doub
   return c1 > c2 || (c1 == c2 && (e1 < e2 || (e1 == e2 && t1 < t2)));
 }
 
-__device__ static inline int reg_clip(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// ------------------------------------------------------------------ 1. mutual nearest-neighbour matching
-// argmin over the rows of `other` of the fp64 squared distance to this thread's row of `own`.  The tile of `other` sits in
-// LDS and every lane reads the same address (broadcast); the own row comes from global memory as float4 (L1 / L2 resident).
-// Both directions run this same code, and (a - b)^2 == (b - a)^2 exactly, so d2[i][j] has the same bits in both passes.
-__device__ static int reg_argmin_pass(const float* __restrict__ own, int n_own, const float* __restrict__ other, int n_other,
-                                      int D, float4* s_tile) {
-  const int t = threadIdx.x, d4 = D >> 2;
-  const float4* own4 = reinterpret_cast<const float4*>(own) + (size_t)t * d4;
-  const float4* other4 = reinterpret_cast<const float4*>(other);
-  double best = INFINITY;
-  int bi = 0;
-  for (int j0 = 0; j0 < n_other; j0 += REG_TJ) {
-    const int nrow = min(REG_TJ, n_other - j0);
-    __syncthreads();
-    for (int e = t; e < nrow * d4; e += REG_WG) s_tile[e] = other4[(size_t)j0 * d4 + e];
-    __syncthreads();
-    if (t < n_own) {
-      double acc[REG_TJ];
-#pragma unroll
-      for (int j = 0; j < REG_TJ; ++j) acc[j] = 0.0;
-      for (int k = 0; k < d4; ++k) {
-        const float4 a = own4[k];
-        const double ax = (double)a.x, ay = (double)a.y, az = (double)a.z, aw = (double)a.w;
-#pragma unroll
-        for (int j = 0; j < REG_TJ; ++j) {
-          const float4 b = s_tile[j * d4 + k];   // rows >= nrow hold stale data: computed, never compared
-          double d = ax - (double)b.x;
-          acc[j] = fma(d, d, acc[j]);
-          d = ay - (double)b.y;
-          acc[j] = fma(d, d, acc[j]);
-          d = az - (double)b.z;
-          acc[j] = fma(d, d, acc[j]);
-          d = aw - (double)b.w;
-          acc[j] = fma(d, d, acc[j]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < REG_TJ; ++j)
-        if (j < nrow && acc[j] < best) {
-          best = acc[j];
-          bi = j0 + j;
-        }
-    }
-  }
-  return bi;
-}
-
-__global__ __launch_bounds__(REG_WG) void reg_match_kernel(const float* __restrict__ feat1, const float* __restrict__ feat2,
-                                                           const int32_t* __restrict__ n1, const int32_t* __restrict__ n2,
-                                                           int n_max, int D, int32_t* __restrict__ corr,
-                                                           int32_t* __restrict__ n_corr) {
-  __shared__ float4 s_tile[REG_TJ * REG_MAX_D / 4];   // 32 KB
-  __shared__ int s_j[REG_MAX_N], s_i[REG_MAX_N];
-  __shared__ int s_wave[4];
-  const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int m1 = reg_clip(n1[p], n_max), m2 = reg_clip(n2[p], n_max);
-  const float* f1 = feat1 + (size_t)p * n_max * D;
-  const float* f2 = feat2 + (size_t)p * n_max * D;
-  int32_t* out = corr + (size_t)p * n_max * 2;
-  if (m1 == 0 || m2 == 0) {
-    for (int c = t; c < n_max; c += REG_WG) out[2 * c] = out[2 * c + 1] = -1;
-    if (t == 0) n_corr[p] = 0;
-    return;
-  }
-  s_j[t] = reg_argmin_pass(f1, m1, f2, m2, D, s_tile);
-  s_i[t] = reg_argmin_pass(f2, m2, f1, m1, D, s_tile);
-  __syncthreads();
-  const bool mutual = t < m1 && s_i[s_j[t]] == t;
-  unsigned long long bal = __ballot(mutual);
-  if (lane == 0) s_wave[w] = __popcll(bal);
-  __syncthreads();
-  const int n_mutual = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-  __syncthreads();
-  const bool keep = n_mutual >= 3 ? mutual : (t < m1);
-  bal = __ballot(keep);
-  if (lane == 0) s_wave[w] = __popcll(bal);
-  __syncthreads();
-  int pos = __popcll(bal & ((1ull << lane) - 1ull));
-  for (int k = 0; k < w; ++k) pos += s_wave[k];
-  const int total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-  if (keep) {
-    out[2 * pos] = t;
-    out[2 * pos + 1] = s_j[t];
-  }
-  for (int c = total + t; c < n_max; c += REG_WG) out[2 * c] = out[2 * c + 1] = -1;
-  if (t == 0) n_corr[p] = total;
-}
-
 // ------------------------------------------------------------------ shared geometry
 // Correspondence coordinates of one pair into LDS as fp64, centred on the centroids of the correspondences' source / target
 // points (sums in ascending correspondence order by one lane per coordinate: a fixed order).  s_c[0..2] = source x, y, z,
 // s_c[3..5] = target; s_cent[0..5] the centroids.  Indices are clamped: nothing is read by an unchecked index.
 __device__ static int reg_load_corr(const float* __restrict__ kp1, const float* __restrict__ kp2, int m1, int m2,
-                                    const int32_t* __restrict__ corr, int nc_raw, int n_max, double (*s_c)[REG_MAX_N],
+                                    const int32_t* __restrict__ corr, int nc_raw, int n_max, double (*s_c)[KP_MAX_N],
                                     double* s_cent) {
   const int t = threadIdx.x;
-  const int nc = (m1 == 0 || m2 == 0) ? 0 : reg_clip(nc_raw, n_max);
+  const int nc = (m1 == 0 || m2 == 0) ? 0 : clipi(nc_raw, n_max);
   if (t < nc) {
-    const int i = reg_clip(corr[2 * t], m1 - 1), j = reg_clip(corr[2 * t + 1], m2 - 1);
+    const int i = clipi(corr[2 * t], m1 - 1), j = clipi(corr[2 * t + 1], m2 - 1);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       s_c[k][t] = (double)kp1[i * 3 + k];
@@ -214,7 +119,7 @@ __device__ static inline double reg_res2(const double* R, const double* tv, doub
 // O of A = sum_k p_k q_k^T (p, q = in-plane coordinates) that maximises tr(O A^T): the rotation by atan2(a12 - a21, a11 + a22)
 // when det A >= 0, else the reflection by atan2(a12 + a21, a11 - a22), and the normal maps to det(O) times the normal, which
 // makes det R = +1.  No iteration, no square root of a small difference.
-__device__ static int reg_hypothesis(const double (*s_c)[REG_MAX_N], int nc, uint64_t seed, uint32_t pid, uint32_t t,
+__device__ static int reg_hypothesis(const double (*s_c)[KP_MAX_N], int nc, uint64_t seed, uint32_t pid, uint32_t t,
                                      double th2, double* R, double* tv) {
   const int ia = (int)reg_draw(seed, pid, t, 0, (uint32_t)nc), ib = (int)reg_draw(seed, pid, t, 1, (uint32_t)nc),
             ic = (int)reg_draw(seed, pid, t, 2, (uint32_t)nc);
@@ -331,12 +236,12 @@ __global__ __launch_bounds__(REG_WG) void reg_ransac_kernel(const float* __restr
                                                             const int32_t* __restrict__ pair_id, int n_max, int H, int chunks,
                                                             uint64_t seed, double th2, RegPartial* __restrict__ partial,
                                                             int32_t* __restrict__ hyp_count, double* __restrict__ hyp_err2) {
-  __shared__ double s_c[6][REG_MAX_N];   // 12 KB
+  __shared__ double s_c[6][KP_MAX_N];   // 12 KB
   __shared__ double s_cent[6];
   __shared__ int s_cnt[4], s_t[4];
   __shared__ double s_e[4];
   const int p = blockIdx.x / chunks, chunk = blockIdx.x % chunks, t = chunk * REG_WG + (int)threadIdx.x;
-  const int m1 = reg_clip(n1[p], n_max), m2 = reg_clip(n2[p], n_max);
+  const int m1 = clipi(n1[p], n_max), m2 = clipi(n2[p], n_max);
   const int nc = reg_load_corr(kp1 + (size_t)p * n_max * 3, kp2 + (size_t)p * n_max * 3, m1, m2, corr + (size_t)p * n_max * 2,
                                n_corr[p], n_max, s_c, s_cent);
   const uint32_t pid = pair_id ? (uint32_t)pair_id[p] & 0x3fffffffu : (uint32_t)p;
@@ -377,16 +282,16 @@ __global__ __launch_bounds__(REG_WG) void reg_finish_kernel(
     double* __restrict__ T_out, int32_t* __restrict__ inliers, double* __restrict__ fitness, double* __restrict__ rmse,
     int32_t* __restrict__ corr_set, int32_t* __restrict__ best_t, double* __restrict__ rte, double* __restrict__ rre,
     int32_t* __restrict__ success, double* __restrict__ repeatability, int32_t* __restrict__ status) {
-  __shared__ double s_c[6][REG_MAX_N];
+  __shared__ double s_c[6][KP_MAX_N];
   __shared__ double s_cent[6];
   __shared__ int s_cnt[4], s_t[4];
   __shared__ double s_e[4];
-  __shared__ double s_q[3][REG_MAX_N];   // target keypoints, fp64
-  __shared__ double s_d2[REG_MAX_N];
-  __shared__ int s_nn[REG_MAX_N];
+  __shared__ double s_q[3][KP_MAX_N];   // target keypoints, fp64
+  __shared__ double s_d2[KP_MAX_N];
+  __shared__ int s_nn[KP_MAX_N];
   const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int r1 = n1[p], r2 = n2[p];
-  const int m1 = reg_clip(r1, n_max), m2 = reg_clip(r2, n_max);
+  const int m1 = clipi(r1, n_max), m2 = clipi(r2, n_max);
   const float* k1 = kp1 + (size_t)p * n_max * 3;
   const float* k2 = kp2 + (size_t)p * n_max * 3;
   int st = (r1 != m1 || r2 != m2) ? EGONN_REG_STATUS_CLIPPED : 0;
@@ -514,9 +419,9 @@ __global__ __launch_bounds__(REG_WG) void reg_finish_kernel(
   if (t == 0 && status) status[p] = st;
 }
 
-static int reg_check_shape(const char* who, int P, int n_max) {
-  EGONN_REQUIRE(P >= 0 && P <= (1 << 20) && n_max >= 1 && n_max <= REG_MAX_N, EGONN_ERR_INVALID,
-                "%s: bad shape (P=%d, n_max=%d; n_max <= %d)", who, P, n_max, REG_MAX_N);
+int reg_check_shape(const char* who, int P, int n_max) {
+  EGONN_REQUIRE(P >= 0 && P <= KP_MAX_PAIRS && n_max >= 1 && n_max <= KP_MAX_N, EGONN_ERR_INVALID,
+                "%s: bad shape (P=%d, n_max=%d; n_max <= %d)", who, P, n_max, KP_MAX_N);
   return EGONN_OK;
 }
 
@@ -525,23 +430,8 @@ static int reg_check_shape(const char* who, int P, int n_max) {
 using namespace egonn;
 
 API int64_t egonn_registration_scratch_bytes(int n_pairs, int n_max, int n_hypotheses) {
-  if (n_pairs < 0 || n_max < 1 || n_max > REG_MAX_N || n_hypotheses <= 0) return -1;
+  if (n_pairs < 0 || n_max < 1 || n_max > KP_MAX_N || n_hypotheses <= 0) return -1;
   return (int64_t)n_pairs * cdiv(n_hypotheses, REG_WG) * (int64_t)sizeof(RegPartial);
-}
-
-API int egonn_match_mutual(const float* feat1, const float* feat2, const int32_t* n1, const int32_t* n2, int n_pairs, int n_max,
-                           int dim, int32_t* corr, int32_t* n_corr, void* stream) {
-  EGONN_TRY(reg_check_shape("match_mutual", n_pairs, n_max));
-  EGONN_REQUIRE(dim >= 4 && dim <= REG_MAX_D && dim % 4 == 0, EGONN_ERR_INVALID,
-                "match_mutual: descriptor width %d must be a multiple of 4 in [4, %d]", dim, REG_MAX_D);
-  EGONN_REQUIRE(feat1 && feat2 && n1 && n2 && corr && n_corr, EGONN_ERR_INVALID, "match_mutual: null pointer");
-  EGONN_REQUIRE(((uintptr_t)feat1 & 15) == 0 && ((uintptr_t)feat2 & 15) == 0, EGONN_ERR_INVALID,
-                "match_mutual: descriptors must be 16-byte aligned");
-  if (n_pairs == 0) return EGONN_OK;
-  hipLaunchKernelGGL(reg_match_kernel, dim3((unsigned)n_pairs), dim3(REG_WG), 0, (hipStream_t)stream, feat1, feat2, n1, n2, n_max,
-                     dim, corr, n_corr);
-  HIP_CHECK(hipGetLastError());
-  return EGONN_OK;
 }
 
 API int egonn_ransac_pairs(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2, const int32_t* corr,

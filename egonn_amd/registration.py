@@ -19,8 +19,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import as_dev as _dev, check_cloud as _check_cloud, check_offsets as _check_offsets, concat_clouds as _concat_clouds
 
 N_MAX = 256
+MAX_PAIRS = 4096          # pairs per matching call (and per call sequence of relocalize.verify_candidates): the matching scratch
+                          # is 9-36 KB per pair, and pairs are independent, so chunking cannot change a bit
 STATUS_CLIPPED, STATUS_FEW_CORR, STATUS_NO_MODEL, STATUS_BAD_INDEX = 1, 2, 4, 8
 ICP_FEW_CORR, ICP_MAX_ITER, ICP_EMPTY, ICP_RANGE = 1, 2, 4, 8
 ICP_VOXEL_SIZE = 0.1                       # misc/point_clouds.py:37
@@ -42,10 +45,6 @@ class RegistrationResult:
                 f"correspondence_set={len(self.correspondence_set)}, status={self.status})")
 
 
-def _dev(x, dev, dtype):
-    return torch.as_tensor(x).to(device=dev, dtype=dtype).contiguous()
-
-
 def _counts(n, P, n_rows, dev):
     if n is None:
         return torch.full((P,), n_rows, dtype=torch.int32, device=dev)
@@ -54,8 +53,9 @@ def _counts(n, P, n_rows, dev):
     return n
 
 
-def match_mutual(feat1: torch.Tensor, feat2: torch.Tensor, n1=None, n2=None):
-    """(P, n_max, D) x 2 -> corr (P, n_max, 2) int32 compacted in ascending source index (unused rows -1), n_corr (P,)."""
+def match_mutual(feat1: torch.Tensor, feat2: torch.Tensor, n1=None, n2=None, chunk_pairs: int = MAX_PAIRS):
+    """(P, n_max, D) x 2 -> corr (P, n_max, 2) int32 compacted in ascending source index (unused rows -1), n_corr (P,).
+    Issued in chunks of at most `chunk_pairs` (<= 4096) pairs on one scratch buffer."""
     dev = feat1.device if feat1.is_cuda else _lib.require_gpu()
     lib = _lib.load()
     f1, f2 = _dev(feat1, dev, torch.float32), _dev(feat2, dev, torch.float32)
@@ -64,9 +64,27 @@ def match_mutual(feat1: torch.Tensor, feat2: torch.Tensor, n1=None, n2=None):
     c1, c2 = _counts(n1, P, n_max, dev), _counts(n2, P, n_max, dev)
     corr = torch.empty((P, n_max, 2), dtype=torch.int32, device=dev)
     n_corr = torch.empty((P,), dtype=torch.int32, device=dev)
-    _lib.call(dev, lib.egonn_match_mutual, f1.data_ptr(), f2.data_ptr(), c1.data_ptr(), c2.data_ptr(), P, n_max, D,
-              corr.data_ptr(), n_corr.data_ptr())
+    pc = max(1, min(int(chunk_pairs), MAX_PAIRS, P))
+    scratch = _lib.scratch(lib.egonn_match_mutual_scratch_bytes(pc, n_max), dev)     # -1 on bad arguments: the call raises
+    for lo in range(0, max(P, 1), pc):                                               # (P = 0: one call, for its checks)
+        s = slice(lo, min(P, lo + pc))
+        _lib.call(dev, lib.egonn_match_mutual, f1[s].data_ptr(), f2[s].data_ptr(), c1[s].data_ptr(), c2[s].data_ptr(),
+                  s.stop - s.start, n_max, D, corr[s].data_ptr(), n_corr[s].data_ptr(), scratch.data_ptr(), scratch.numel() * 8)
     return corr, n_corr
+
+
+def enqueue_ransac(dev, operands, P, n_max, H, seed, dist_th, scratch, T_gt, repeat_th, out):
+    """egonn_ransac_pairs + egonn_registration_finish of P pairs.  operands: the pointers (kp1, kp2, n1, n2, corr, n_corr,
+    pair_id) both calls start with; scratch: `_lib.scratch` of egonn_registration_scratch_bytes; T_gt: (P,4,4) f64 tensor or
+    None; out: the outputs by the names of `register_pairs` (an absent one is not computed).  Nothing is allocated and
+    nothing synchronises, so the pair can be captured; the caller keeps the operands alive."""
+    lib = _lib.load()
+    p = lambda k: _lib._ptr(out.get(k))                                       # noqa: E731
+    head = (*operands, P, n_max, H, int(seed) & 0xFFFFFFFFFFFFFFFF, float(dist_th), scratch.data_ptr(), scratch.numel() * 8)
+    _lib.call(dev, lib.egonn_ransac_pairs, *head, p("hyp_count"), p("hyp_err2"))
+    _lib.call(dev, lib.egonn_registration_finish, *head, _lib._ptr(T_gt), float(repeat_th), p("T"), p("inliers"), p("fitness"),
+              p("inlier_rmse"), p("correspondence_set"), p("best_t"), p("rte"), p("rre"), p("success"), p("repeatability"),
+              p("status"))
 
 
 def register_pairs(feat1, feat2, kp1, kp2, n1=None, n2=None, T_gt=None, ransac_dist_th: float = 0.5,
@@ -91,8 +109,7 @@ def register_pairs(feat1, feat2, kp1, kp2, n1=None, n2=None, T_gt=None, ransac_d
     H = int(ransac_max_it)
     pid = None if pair_ids is None else _dev(pair_ids, dev, torch.int32)
     gt = None if T_gt is None else _dev(T_gt, dev, torch.float64).reshape(P, 4, 4)
-    nbytes = int(lib.egonn_registration_scratch_bytes(P, n_max, H))      # -1 on bad arguments: the launch call below raises
-    scratch = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _lib.scratch(lib.egonn_registration_scratch_bytes(P, n_max, H), dev)   # -1 on bad arguments: the call raises
     f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
     i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
     out = {"T": f64(P, 4, 4), "inliers": i32(P), "fitness": f64(P), "inlier_rmse": f64(P),
@@ -101,15 +118,8 @@ def register_pairs(feat1, feat2, kp1, kp2, n1=None, n2=None, T_gt=None, ransac_d
         out.update({"rte": f64(P), "rre": f64(P), "success": i32(P), "repeatability": f64(P)})
     if debug:
         out.update({"hyp_count": i32(P, max(H, 0)), "hyp_err2": f64(P, max(H, 0))})
-    p = lambda k: _lib._ptr(out.get(k))                                       # noqa: E731
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    _lib.call(dev, lib.egonn_ransac_pairs, k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(),
-              n_corr.data_ptr(), _lib._ptr(pid), P, n_max, H, seed, float(ransac_dist_th), scratch.data_ptr(),
-              scratch.numel() * 8, p("hyp_count"), p("hyp_err2"))
-    _lib.call(dev, lib.egonn_registration_finish, k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(),
-              n_corr.data_ptr(), _lib._ptr(pid), P, n_max, H, seed, float(ransac_dist_th), scratch.data_ptr(),
-              scratch.numel() * 8, _lib._ptr(gt), float(repeat_dist_th), p("T"), p("inliers"), p("fitness"), p("inlier_rmse"),
-              p("correspondence_set"), p("best_t"), p("rte"), p("rre"), p("success"), p("repeatability"), p("status"))
+    enqueue_ransac(dev, (k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(), n_corr.data_ptr(),
+                         _lib._ptr(pid)), P, n_max, H, seed, ransac_dist_th, scratch, gt, repeat_dist_th, out)
     out["_keep"] = (k1, k2, c1, c2, pid, gt, scratch)      # inputs of enqueued work stay alive with the result
     return out
 
@@ -169,19 +179,6 @@ def calculate_repeatability(kp1, kp2, T_gt, threshold: float) -> float:
 
 
 # ------------------------------------------------------------------ ICP refinement on the full clouds
-def _check_cloud(name, x):
-    shape = tuple(getattr(x, "shape", ()))
-    if len(shape) != 2 or shape[1] != 3:
-        raise ValueError(f"{name}: expected (n, 3) points, got shape {shape}")
-
-
-def _check_offsets(name, off, n_rows):
-    shape = tuple(getattr(off, "shape", (len(off),) if hasattr(off, "__len__") else ()))
-    if len(shape) != 1 or shape[0] < 2:
-        raise ValueError(f"{name}: offsets must be a 1-D sequence of n_clouds + 1 entries, got shape {shape}")
-    return shape[0] - 1
-
-
 def _check_crop(crop):
     if crop is None:
         return None
@@ -200,7 +197,7 @@ def voxel_downsample(points, offsets, voxel_size: float = ICP_VOXEL_SIZE, crop=N
     voxel, status (n_clouds,) int32 (ICP_RANGE: a voxel index beyond 21 bits, nothing written for the cloud).
     No host synchronisation when points and offsets are device tensors."""
     _check_cloud("voxel_downsample", points)
-    C = _check_offsets("voxel_downsample", offsets, None)
+    C = _check_offsets("voxel_downsample", offsets)
     if not float(voxel_size) > 0.0:
         raise ValueError("voxel_downsample: voxel_size must be positive")
     cr = _check_crop(crop)
@@ -208,8 +205,7 @@ def voxel_downsample(points, offsets, voxel_size: float = ICP_VOXEL_SIZE, crop=N
     lib = _lib.load()
     pts, off = _dev(points, dev, torch.float32), _dev(offsets, dev, torch.int64)
     n = pts.shape[0]
-    nbytes = int(lib.egonn_voxel_downsample_scratch_bytes(n, C))
-    scratch = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _lib.scratch(lib.egonn_voxel_downsample_scratch_bytes(n, C), dev)
     out = {"points": torch.empty((n, 3), dtype=torch.float64, device=dev),
            "offsets": torch.empty((C + 1,), dtype=torch.int64, device=dev),
            "counts": torch.zeros((n,), dtype=torch.int32, device=dev),
@@ -231,8 +227,8 @@ def icp_pairs(src, src_offsets, tgt, tgt_offsets, T_init=None, inlier_dist_thres
     call enqueues a fixed launch sequence and can be captured into a graph."""
     _check_cloud("icp_pairs: src", src)
     _check_cloud("icp_pairs: tgt", tgt)
-    P = _check_offsets("icp_pairs: src_offsets", src_offsets, None)
-    if _check_offsets("icp_pairs: tgt_offsets", tgt_offsets, None) != P:
+    P = _check_offsets("icp_pairs: src_offsets", src_offsets)
+    if _check_offsets("icp_pairs: tgt_offsets", tgt_offsets) != P:
         raise ValueError("icp_pairs: src_offsets and tgt_offsets must describe the same number of pairs")
     if T_init is not None and tuple(T_init.shape) != (P, 4, 4):
         raise ValueError(f"icp_pairs: T_init must have shape ({P}, 4, 4), got {tuple(T_init.shape)}")
@@ -244,8 +240,7 @@ def icp_pairs(src, src_offsets, tgt, tgt_offsets, T_init=None, inlier_dist_thres
     so, to = _dev(src_offsets, dev, torch.int64), _dev(tgt_offsets, dev, torch.int64)
     ti = None if T_init is None else _dev(T_init, dev, torch.float64)
     ns, nt, K = s.shape[0], t.shape[0], int(max_iteration)
-    nbytes = int(lib.egonn_icp_scratch_bytes(ns, nt, P))
-    scratch = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _lib.scratch(lib.egonn_icp_scratch_bytes(ns, nt, P), dev)
     f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)        # noqa: E731
     i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)          # noqa: E731
     out = {"T": f64(P, 4, 4), "fitness": f64(P), "inlier_rmse": f64(P), "iterations": i32(P), "status": i32(P)}
@@ -258,17 +253,6 @@ def icp_pairs(src, src_offsets, tgt, tgt_offsets, T_init=None, inlier_dist_thres
               p("corr") if ns else None, scratch.data_ptr(), scratch.numel() * 8)
     out["_keep"] = (s, t, so, to, ti, scratch)
     return out
-
-
-def _concat_clouds(clouds, dev):
-    """per-scan (n,3) arrays -> (points (sum n, 3) f32 on the device, (len+1,) int64 offsets)"""
-    ts = [torch.as_tensor(c) for c in clouds]
-    for c in ts:
-        _check_cloud("cloud", c)
-    off = np.zeros(len(ts) + 1, dtype=np.int64)
-    off[1:] = np.cumsum([c.shape[0] for c in ts])
-    pts = torch.cat([c.to(device=dev, dtype=torch.float32) for c in ts]) if ts else torch.zeros((0, 3), device=dev)
-    return pts, torch.from_numpy(off).to(dev)
 
 
 def refine_pairs(src_clouds, tgt_clouds, T_init=None, crop=None, inlier_dist_threshold: float = 1.2, max_iteration: int = 200,

@@ -19,14 +19,11 @@ import numpy as np
 import torch
 
 from . import _lib, registration as _reg, retrieval as _ret
+from ._lib import as_dev as _dev
 from .tuples import CloudBank, relative_poses
 
 RELOC_NO_CANDIDATE, RELOC_BAD_INDEX, RELOC_UNVERIFIED = 1, 2, 4
-MAX_PAIRS = 4096          # pairs per call sequence of verify_candidates
-
-
-def _dev(x, dev, dtype):
-    return torch.as_tensor(x).to(device=dev, dtype=dtype).contiguous()
+MAX_PAIRS = _reg.MAX_PAIRS     # pairs per call sequence of verify_candidates
 
 
 class KeypointMap:
@@ -153,9 +150,13 @@ def _verify_buffers(dev, Q, k, n_max, Pc, with_gt, nb_match, nb_reg):
                     "best_success": i32(Q)})
     out["_work"] = {"kp1": torch.empty((Pc, n_max, 3), dtype=torch.float32, device=dev),
                     "kp2": torch.empty((Pc, n_max, 3), dtype=torch.float32, device=dev), "n1": i32(Pc), "n2": i32(Pc),
-                    "match": torch.empty((max(nb_match, 8) + 7) // 8, dtype=torch.int64, device=dev),
-                    "reg": torch.empty((max(nb_reg, 8) + 7) // 8, dtype=torch.int64, device=dev)}
+                    "match": _lib.scratch(nb_match, dev), "reg": _lib.scratch(nb_reg, dev)}
     return out
+
+
+# outputs of egonn_registration_finish by the names of `register_pairs` -> the per-pair keys of `verify_candidates`
+_FINISH_OUT = (("T", "T"), ("inliers", "inliers"), ("fitness", "fitness"), ("inlier_rmse", "inlier_rmse"), ("best_t", "best_t"),
+               ("rte", "rte"), ("rre", "rre"), ("success", "success"), ("status", "pair_status"))
 
 
 def verify_candidates(q_desc, q_kp, q_count, kmap: KeypointMap, nn_index, query_ids=None, T_gt=None, min_inliers: int = 0,
@@ -225,7 +226,6 @@ def verify_candidates(q_desc, q_kp, q_count, kmap: KeypointMap, nn_index, query_
             raise ValueError("verify_candidates: `out` was made by a call with other shapes")
     w = out["_work"]
     km = (kmap.descriptors, kmap.keypoints, kmap.counts, kmap.poses)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     for lo in range(0, Q, qc):
         hi = min(Q, lo + qc)
         n, P = hi - lo, (hi - lo) * k
@@ -236,12 +236,10 @@ def verify_candidates(q_desc, q_kp, q_count, kmap: KeypointMap, nn_index, query_
         _lib.call(dev, lib.egonn_gather_candidates, qk[lo:hi].data_ptr(), qn[lo:hi].data_ptr(), km[1].data_ptr(), km[2].data_ptr(),
                   nn[lo:hi].data_ptr(), None if qid is None else qid[lo:hi].data_ptr(), n, k, M, n_max, w["kp1"].data_ptr(),
                   w["kp2"].data_ptr(), w["n1"].data_ptr(), w["n2"].data_ptr(), s("pair_ids"))
-        reg_in = (w["kp1"].data_ptr(), w["kp2"].data_ptr(), w["n1"].data_ptr(), w["n2"].data_ptr(), s("corr"), s("n_corr"),
-                  s("pair_ids"), P, n_max, H, seed, float(ransac_dist_th), w["reg"].data_ptr(), w["reg"].numel() * 8)
-        _lib.call(dev, lib.egonn_ransac_pairs, *reg_in, None, None)
-        _lib.call(dev, lib.egonn_registration_finish, *reg_in, None if gt is None else gt[lo:hi].data_ptr(), 0.5, s("T"),
-                  s("inliers"), s("fitness"), s("inlier_rmse"), None, s("best_t"), s("rte"), s("rre"), s("success"), None,
-                  s("pair_status"))
+        _reg.enqueue_ransac(dev, (w["kp1"].data_ptr(), w["kp2"].data_ptr(), w["n1"].data_ptr(), w["n2"].data_ptr(), s("corr"),
+                                  s("n_corr"), s("pair_ids")), P, n_max, H, seed, ransac_dist_th, w["reg"],
+                            None if gt is None else gt[lo:hi], 0.5,
+                            {name: out[key][lo:hi] for name, key in _FINISH_OUT if key in out})
         _lib.call(dev, lib.egonn_pick_candidates, nn[lo:hi].data_ptr(), n, k, M, km[3].data_ptr(), s("T"), s("inliers"),
                   s("inlier_rmse"), s("pair_status"), s("rte"), s("rre"), s("success"), int(min_inliers), s("best_rank"),
                   s("best_index"), s("reranked"), s("T_rel"), s("pose"), s("safe_pick"), s("best_inliers"), s("status"),

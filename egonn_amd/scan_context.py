@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import as_dev as _dev, check_cloud as _check_cloud, check_offsets as _check_offsets, concat_clouds as _concat_clouds
 from .retrieval import knn
 
 MAX_RING, MAX_SECTOR, MAX_K = 40, 128, 128
@@ -34,19 +35,6 @@ def _check_k(k):
         raise ValueError(f"scan context: k must be in [1, {MAX_K}], got {k}")
 
 
-def _check_cloud(name, x):
-    shape = tuple(getattr(x, "shape", ()))
-    if len(shape) != 2 or shape[1] != 3:
-        raise ValueError(f"{name}: expected (n, 3) points, got shape {shape}")
-
-
-def _check_offsets(name, off, n_rows):
-    shape = tuple(getattr(off, "shape", (len(off),) if hasattr(off, "__len__") else ()))
-    if len(shape) != 1 or shape[0] < 2:
-        raise ValueError(f"{name}: offsets must be a 1-D sequence of n_scans + 1 entries, got shape {shape}")
-    return shape[0] - 1
-
-
 def _check_sc(name, sc, lead_dims=(2, 3)):
     shape = tuple(getattr(sc, "shape", ()))
     if len(shape) not in lead_dims:
@@ -55,23 +43,11 @@ def _check_sc(name, sc, lead_dims=(2, 3)):
     return shape
 
 
-def _dev(x, dev, dtype):
-    return torch.as_tensor(x).to(device=dev, dtype=dtype).contiguous()
-
-
 def _device_of(*xs):
     for x in xs:
         if torch.is_tensor(x) and x.is_cuda:
             return x.device
     return _lib.require_gpu()
-
-
-def _concat_clouds(clouds, dev):
-    ts = [torch.as_tensor(c) for c in clouds]
-    off = np.zeros(len(ts) + 1, dtype=np.int64)
-    off[1:] = np.cumsum([c.shape[0] for c in ts])
-    pts = torch.cat([c.to(device=dev, dtype=torch.float32) for c in ts]) if ts else torch.zeros((0, 3), device=dev)
-    return pts, torch.from_numpy(off).to(dev)
 
 
 class ScanContext:
@@ -91,7 +67,7 @@ class ScanContext:
 
     def batch(self, points, offsets):
         _check_cloud("ScanContext.batch", points)
-        B = _check_offsets("ScanContext.batch", offsets, None)
+        B = _check_offsets("ScanContext.batch", offsets)
         if B > 65535:
             raise ValueError("ScanContext.batch: at most 65535 scans per call")
         dev = _device_of(points)
@@ -200,7 +176,7 @@ class ScanContextManager:
 
     def add_nodes(self, points, offsets):
         _check_cloud("ScanContextManager.add_nodes", points)
-        B = _check_offsets("ScanContextManager.add_nodes", offsets, None)
+        B = _check_offsets("ScanContextManager.add_nodes", offsets)
         self._reserve(B)
         sc, rk = self.sc.batch(points, offsets)
         self._sc_parts.append(sc)
@@ -244,7 +220,7 @@ class ScanContextManager:
 
     def query_batch(self, points, offsets, k=1, reranking=True):
         _check_cloud("ScanContextManager.query_batch", points)
-        _check_offsets("ScanContextManager.query_batch", offsets, None)
+        _check_offsets("ScanContextManager.query_batch", offsets)
         self._eligible(k)
         qsc, qrk = self.sc.batch(points, offsets)
         return self.query_descriptors(qsc, qrk, k, reranking)

@@ -143,14 +143,6 @@ def _check_exclude(exclude_self, n_radius: int, same: bool) -> List[bool]:
     return ex
 
 
-def _f64(x, dev):
-    return torch.as_tensor(x).to(device=dev, dtype=torch.float64).contiguous()
-
-
-def _i32(x, dev):
-    return torch.as_tensor(x).to(device=dev, dtype=torch.int32).contiguous()
-
-
 # ------------------------------------------------------------------ radius join
 def _radius_counts(q, m, radii, ex) -> torch.Tensor:
     lib = _lib.load()
@@ -179,8 +171,8 @@ def radius_neighbors(query_xy, ref_xy=None, radius: Union[float, Sequence[float]
     ex = _check_exclude(exclude_self, len(radii), ref_xy is None)
     dev = query_xy.device if torch.is_tensor(query_xy) and query_xy.is_cuda else _lib.require_gpu()
     lib = _lib.load()
-    q = _f64(query_xy, dev)
-    m = q if ref_xy is None else _f64(ref_xy, dev)
+    q = _lib.as_dev(query_xy, dev, torch.float64)
+    m = q if ref_xy is None else _lib.as_dev(ref_xy, dev, torch.float64)
     Q = q.shape[0]
     counts = _radius_counts(q, m, radii, ex)
     offsets = torch.zeros((len(radii), Q + 1), dtype=torch.int64, device=dev)
@@ -210,7 +202,7 @@ def count_within(query_xy, ref_xy, radius: float) -> torch.Tensor:
     if len(radii) != 1:
         raise ValueError("count_within: one radius")
     dev = query_xy.device if torch.is_tensor(query_xy) and query_xy.is_cuda else _lib.require_gpu()
-    return _radius_counts(_f64(query_xy, dev), _f64(ref_xy, dev), radii, [False])[0]
+    return _radius_counts(_lib.as_dev(query_xy, dev, torch.float64), _lib.as_dev(ref_xy, dev, torch.float64), radii, [False])[0]
 
 
 # ------------------------------------------------------------------ relative poses
@@ -232,7 +224,7 @@ def relative_poses(poses, idx_a, idx_b, negate_translation: bool = True, return_
         raise ValueError(f"relative_poses: idx_a and idx_b must be 1-D and equally long, got {la} and {lb}")
     dev = poses.device if torch.is_tensor(poses) and poses.is_cuda else _lib.require_gpu()
     lib = _lib.load()
-    ps, a, b = _f64(poses, dev), _i32(idx_a, dev), _i32(idx_b, dev)
+    ps, a, b = _lib.as_dev(poses, dev, torch.float64), _lib.as_dev(idx_a, dev, torch.int32), _lib.as_dev(idx_b, dev, torch.int32)
     P = a.shape[0]
     out = torch.empty((P, 4, 4), dtype=torch.float64, device=dev)
     status = torch.empty((P,), dtype=torch.int32, device=dev)
@@ -366,7 +358,7 @@ class CloudBank:
             raise ValueError("CloudBank.gather: negative capacity")
         lib = _lib.load()
         dev = self._dev()
-        pk = _i32(pick, dev)
+        pk = _lib.as_dev(pick, dev, torch.int32)
         out = torch.empty((max(int(capacity), 1), 3), dtype=torch.float64, device=dev)
         off = torch.empty((n_pick + 1,), dtype=torch.int64, device=dev)
         status = torch.empty((), dtype=torch.int32, device=dev)
@@ -511,7 +503,7 @@ class TupleIndex:
             raise ValueError(f"TupleIndex.masks: batch size in [1, {MAX_BATCH}], got {B}")
         t = self._tables()
         dev = self.device
-        lab = _i32(labels, dev)
+        lab = _lib.as_dev(labels, dev, torch.int32)
         if lab.dim() != 1:
             raise ValueError("TupleIndex.masks: labels are 1-D")
         if out is None:

@@ -555,12 +555,18 @@ enum { EGONN_REG_STATUS_CLIPPED = 1,      /* a count was outside [0, n_max] and 
 /* bytes of the scratch that carries the per-workgroup bests from egonn_ransac_pairs to egonn_registration_finish
  * (-1 on bad arguments) */
 int64_t egonn_registration_scratch_bytes(int n_pairs, int n_max, int n_hypotheses);
-/* correspondences by mutual nearest neighbours in descriptor space (fp64 squared L2 of the exactly converted fp32 inputs):
- * j(i) = nearest target of source i, i(j) = nearest source of target j, ties: lowest index; keep (i, j(i)) iff
- * i(j(i)) == i; fewer than 3 such pairs: every (i, j(i)).  corr (n_pairs, n_max, 2) int32 compacted in ascending i
- * (unused rows -1), n_corr (n_pairs). */
+/* correspondences by mutual nearest neighbours in descriptor space (csrc/match.hip): ONE operator with two addressings,
+ * egonn_match_mutual (dense: pair p = block p of both sides) and egonn_match_candidates below (indexed: side 2 of pair p is
+ * the bank block nn_index names).  Both run the same two kernels and give the same bits on the same operands.  fp64 squared
+ * L2 of the exactly converted fp32 inputs, k ascending, one fma per term: j(i) = nearest target of source i, i(j) = nearest
+ * source of target j, ties: lowest index; keep (i, j(i)) iff i(j(i)) == i; fewer than 3 such pairs: every (i, j(i)).
+ * corr (n_pairs, n_max, 2) int32 compacted in ascending i (unused rows -1), n_corr (n_pairs).  Each distance is computed
+ * once, by workgroups of 64 source rows x 32 target rows whose partial minima go to the caller's scratch (8-byte aligned,
+ * egonn_match_mutual_scratch_bytes: (cdiv(n_max, 64) + cdiv(n_max, 32)) * n_max * 12 bytes per pair, -1 on bad arguments)
+ * and are merged in ascending tile order. */
+int64_t egonn_match_mutual_scratch_bytes(int n_pairs, int n_max);
 int egonn_match_mutual(const float* feat1, const float* feat2, const int32_t* n1, const int32_t* n2, int n_pairs, int n_max,
-                       int dim, int32_t* corr, int32_t* n_corr, void* stream);
+                       int dim, int32_t* corr, int32_t* n_corr, void* scratch, int64_t scratch_bytes, void* stream);
 /* hypotheses t = 0 .. n_hypotheses-1 of every pair: 3 drawn correspondences, degeneracy / edge-length (0.8) / distance
  * (dist_th) checks, the rigid transform of the 3 pairs (no scale, reflection corrected), then over all correspondences
  * inlier iff |T s_i - t_j| < dist_th.  Writes each workgroup's best (inliers, sum of squared inlier distances, t) to scratch.
@@ -751,7 +757,7 @@ int egonn_relative_poses(const double* poses, int64_t n_poses, const int32_t* id
 int egonn_gather_clouds(const double* bank, int64_t n_bank, const int64_t* bank_offsets, int64_t n_clouds, const int32_t* pick,
                         int n_pick, double* out, int64_t capacity, int64_t* out_offsets, int32_t* status, void* stream);
 
-/* ------------------------------------------------------------------ relocalisation against a keypoint map (csrc/relocalize.hip)
+/* ------------------------------------------------------------------ relocalisation against a keypoint map (csrc/relocalize.hip, csrc/match.hip)
  * A query scan is placed in the map frame by registering it against its top-k retrieved map entries (egonn_knn) and keeping
  * the entry with the most inliers: P_query = P_map[best] @ T, T = the transform of egonn_registration_finish, which maps query
  * keypoints into the candidate's frame (misc/poses.py: T_gt = inv(P_map) @ P_query).  The map is resident: descriptors
@@ -765,13 +771,12 @@ enum { EGONN_RELOC_NO_CANDIDATE = 1,     /* candidate index -1 (or outside the m
        EGONN_RELOC_UNVERIFIED = 4 };     /* per query: no candidate with a model and min_inliers inliers */
 /* bytes of the scratch of egonn_match_candidates (-1 on bad arguments) */
 int64_t egonn_match_candidates_scratch_bytes(int n_queries, int k, int n_max);
-/* egonn_match_mutual of every (query, candidate) pair with the candidate's descriptors read from the bank by index: the
- * same rules and the same bits (fp64 squared L2, k ascending, one fma per term; ties: lowest index; (i, j(i)) kept iff
- * i(j(i)) == i; fewer than 3: every (i, j(i)); ascending i; counts clipped to [0, n_max]).  Each distance is computed once,
- * by workgroups of 64 query rows x 32 candidate rows whose partial minima go to scratch and are merged in ascending tile
- * order.  dim a multiple of 4 up to 256, descriptors 16-byte aligned, scratch 8-byte aligned.  corr (n_queries * k, n_max, 2)
- * int32, n_corr (n_queries * k), status (n_queries * k) int32 of EGONN_RELOC_* bits (nullable).  An invalid index gives
- * n_corr = 0 and all rows -1. */
+/* the indexed addressing of the matching operator (see egonn_match_mutual; csrc/match.hip): pair p = q * k + c matches
+ * query q against bank entry nn_index[q][c], read by index: nothing is gathered, and the result has the bits
+ * egonn_match_mutual gives on gathered operands (counts clipped to [0, n_max]).  dim a multiple of 4 up to 256, descriptors
+ * 16-byte aligned, scratch 8-byte aligned.  corr (n_queries * k, n_max, 2) int32, n_corr (n_queries * k), status
+ * (n_queries * k) int32 of EGONN_RELOC_* bits (nullable).  An invalid index gives n_corr = 0 and all rows -1; nothing is
+ * read by it. */
 int egonn_match_candidates(const float* q_feat, const int32_t* q_n, const float* bank_feat, const int32_t* bank_n,
                            const int32_t* nn_index, int n_queries, int k, int n_bank, int n_max, int dim, int32_t* corr,
                            int32_t* n_corr, int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);

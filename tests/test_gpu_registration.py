@@ -11,9 +11,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests.match_data import EXCUSED_ROW_CAP, check_matching as _check_matching, dense_sets, recorded
 from tests.test_registration_host import (BAND, PLANTED_CASES, STATUS_CLIPPED, STATUS_FEW_CORR, STATUS_NO_MODEL, best_rule,
-                                          edge_pairs, final_eval, hypothesis_transform_f64, match_band, match_f64,
-                                          metrics_f64, pad_batch, planted_case, planted_pair, ransac_f64, repeatability_f64)
+                                          edge_pairs, final_eval, hypothesis_transform_f64, metrics_f64, pad_batch,
+                                          planted_case, planted_pair, ransac_f64, repeatability_f64)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +23,6 @@ MEASURED_COORD_DIFF = 5.791e-13   # metres, as printed by test_band_measurement 
 BOX_RADIUS = 114.0            # metres: farthest corner of the +-80 m x +-80 m x +-10 m box from its centre
 ROT_TOL = BAND / BOX_RADIUS   # radians: a rotation difference that moves no point of the box by more than BAND
 EXCUSED_HYP_CAP = 1e-4        # share of P x H per case
-EXCUSED_ROW_CAP = 0.01        # share of matching rows per case
 # rre goes through acos near 1: at angle a its error is eps / sin(a), and an exact identity gives sqrt(2 eps) = 1.5e-8 rad
 RRE_ATOL_DEG = 1e-5
 
@@ -66,35 +66,6 @@ def _case(gpu, name):
         tabs = [ransac_f64(p[2], p[3], out["corr"][i, :out["n_corr"][i]], 0, i, H) for i, p in enumerate(pairs)]
         _CACHE[name] = (pairs, H, out, tabs)
     return _CACHE[name]
-
-
-def _check_matching(pairs, corr, n_corr):
-    """-> excused rows, rows, unchecked pairs.  Rows whose best and second-best float64 squared distances lie within match_band
-    may pick either; a pair is unchecked when such a row put the device and the restatement on different sides of the
-    fewer-than-3 fallback (the sets then differ wholesale).  Callers assert or print the last figure: it must not hide."""
-    excused = total = unchecked = 0
-    for i, p in enumerate(pairs):
-        want, g1, g2 = match_f64(p[0], p[1])
-        band = match_band(p[0], p[1])
-        # a gap of exactly 0 is a tie of duplicated descriptors: identical bits on both sides, the lowest-index rule decides
-        e1, e2 = np.nonzero((g1 > 0) & (g1 < band))[0], np.nonzero((g2 > 0) & (g2 < band))[0]
-        excused += len(e1) + len(e2)
-        total += len(g1) + len(g2)
-        got = corr[i, :n_corr[i]]
-        assert (corr[i, n_corr[i]:] == -1).all()
-        if len(e1) + len(e2) == 0:
-            assert n_corr[i] == len(want) and np.array_equal(got, want), i
-        else:       # entries that touch no excused row must agree (the < 3 fallback may flip with an excused row)
-            skip = lambda c: np.isin(c[:, 0], e1) | np.isin(c[:, 1], e2)       # noqa: E731
-            a, b = got[~skip(got)], want[~skip(want)]
-            # all-rows output = the fewer-than-3 fallback (or every row mutual); on different sides nothing can be compared
-            if (n_corr[i] == len(p[0])) != (len(want) == len(p[0])):
-                unchecked += 1
-            else:
-                assert np.array_equal(a, b), i
-                # an excused row changes at most its own entry and the entry of the row it displaces
-                assert abs(int(n_corr[i]) - len(want)) <= 2 * (len(e1) + len(e2)), i
-    return excused, total, unchecked
 
 
 def _check_table(name, out, tabs, H):
@@ -159,6 +130,44 @@ def test_matching_equals_restatement(gpu, name):
     excused, total, unchecked = _check_matching(pairs, _np(corr), _np(n_corr))
     print(f"[registration] {name}: excused matching rows {excused} of {total}, unchecked pairs {unchecked}")
     assert excused <= EXCUSED_ROW_CAP * total and unchecked == 0
+    # what the parent commit's one-workgroup-per-pair kernel gave on these inputs (tests/golden/match_parent.npz)
+    gold, gold_n = recorded(name, dense_sets()[name])
+    assert np.array_equal(_np(n_corr), gold_n) and np.array_equal(_np(corr), gold)
+
+
+def test_edge_pairs_equal_recorded_parent(gpu):
+    F1, F2, n1, n2 = dense_sets()["edge_pairs"]
+    corr, n_corr = gpu.match_mutual(_cu(F1), _cu(F2), _cu(n1), _cu(n2))
+    gold, gold_n = recorded("edge_pairs", (F1, F2, n1, n2))
+    assert np.array_equal(_np(n_corr), gold_n) and np.array_equal(_np(corr), gold)
+
+
+# the dense addressing at the smallest shapes where its index arithmetic can go wrong: P = 3 pairs, two row tiles / two column
+# tiles with a one-row remainder (n_max = 65 = 64 + 1 with D = 4, n_max = 33 = 32 + 1 with D = 8)
+@pytest.mark.parametrize("n_max,D", [(65, 4), (33, 8)])
+def test_dense_addressing_small_shapes(gpu, n_max, D):
+    rng = np.random.default_rng(n_max)
+    F1, F2 = (rng.standard_normal((3, n_max, D)).astype(np.float32) for _ in range(2))
+    for counts in ((65, 33), (1, 65), (0, 5)):
+        n1 = np.array([min(counts[0], n_max)] * 3, np.int32)
+        n2 = np.array([min(counts[1], n_max)] * 3, np.int32)
+        n1[1], n2[1] = n2[1], n1[1]                                        # the middle pair the other way round
+        corr, n_corr = (_np(x) for x in gpu.match_mutual(_cu(F1), _cu(F2), _cu(n1), _cu(n2)))
+        pairs = [(F1[p, :n1[p]], F2[p, :n2[p]]) for p in range(3)]
+        excused, total, unchecked = _check_matching(pairs, corr, n_corr)
+        assert excused == 0 and unchecked == 0, (counts, excused, total, unchecked)
+        # pair 1 of the batch equals the same pair run alone: the p / k and p addressing cannot cross pairs
+        one, one_n = (_np(x) for x in gpu.match_mutual(_cu(F1[1:2]), _cu(F2[1:2]), _cu(n1[1:2]), _cu(n2[1:2])))
+        assert np.array_equal(one[0], corr[1]) and one_n[0] == n_corr[1]
+
+
+def test_match_mutual_chunks_change_no_bit(gpu):
+    """registration.match_mutual issues at most `chunk_pairs` pairs per call on one scratch buffer: P = 5 in chunks of 2"""
+    pairs = planted_case("n128_out30")[:5]
+    F1, F2, _, _, n1, n2 = (_cu(x) for x in pad_batch(pairs))
+    whole, whole_n = gpu.match_mutual(F1, F2, n1, n2)
+    parts, parts_n = gpu.match_mutual(F1, F2, n1, n2, chunk_pairs=2)
+    assert torch.equal(whole, parts) and torch.equal(whole_n, parts_n) and int(whole_n.min()) >= 3
 
 
 # ------------------------------------------------------------------ 2. per-hypothesis parity, and the band it rests on
@@ -356,8 +365,13 @@ def test_argument_checks(gpu):
     c = torch.zeros((1, 64, 2), dtype=torch.int32, device="cuda")
     s = torch.zeros(64, dtype=torch.int64, device="cuda")
     P = lambda t: t.data_ptr()                                             # noqa: E731
-    assert lib.egonn_match_mutual(P(f), None, P(n), P(n), 1, 64, 128, P(c), P(n), None) == 1
-    assert lib.egonn_match_mutual(P(f), P(f), P(n), P(n), 1, 64, 128, None, P(n), None) == 1
+    nb = lib.egonn_match_mutual_scratch_bytes(1, 64)
+    ms = torch.zeros(nb // 8, dtype=torch.int64, device="cuda")
+    assert nb == (1 + 2) * 64 * 12
+    assert lib.egonn_match_mutual(P(f), None, P(n), P(n), 1, 64, 128, P(c), P(n), P(ms), nb, None) == 1
+    assert lib.egonn_match_mutual(P(f), P(f), P(n), P(n), 1, 64, 128, None, P(n), P(ms), nb, None) == 1
+    assert lib.egonn_match_mutual(P(f), P(f), P(n), P(n), 1, 64, 128, P(c), P(n), None, nb, None) == 1
+    assert lib.egonn_match_mutual(P(f), P(f), P(n), P(n), 1, 64, 128, P(c), P(n), P(ms), nb - 1, None) == 1
     assert lib.egonn_ransac_pairs(P(k), P(k), P(n), P(n), None, P(n), None, 1, 64, 100, 0, 0.5, P(s), 512, None, None, None) == 1
     assert lib.egonn_ransac_pairs(P(k), P(k), P(n), P(n), P(c), P(n), None, 1, 64, 100, 0, 0.5, None, 512, None, None, None) == 1
     assert lib.egonn_ransac_pairs(P(k), P(k), P(n), P(n), P(c), P(n), None, 1, 64, 10000, 0, 0.5, P(s), 512, None, None, None) == 1

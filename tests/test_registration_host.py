@@ -1,7 +1,8 @@
 """CPU tests of the keypoint-set registration (egonn_match_mutual / egonn_ransac_pairs / egonn_registration_finish) and the
 home of its float64 restatement, which tests/test_gpu_registration.py imports.
 
-Restated contract (egonn_amd/csrc/registration.hip; the reference delegates to Open3D, eval/evaluate.py:381-399 [recall]):
+Restated contract (egonn_amd/csrc/match.hip, egonn_amd/csrc/registration.hip; the reference delegates to Open3D,
+eval/evaluate.py:381-399 [recall]):
   correspondences  d2[i][j] = |a_i - b_j|^2 in float64; j(i) = argmin_j, i(j) = argmin_i, ties lowest index; keep (i, j(i))
                    iff i(j(i)) == i; fewer than 3 kept -> every (i, j(i)); ascending i.
   draw             splitmix64 of (seed, pair id, t, slot), multiply-high onto [0, n_corr)            (draw() below)
@@ -25,7 +26,8 @@ from egonn_amd.synth import pad_keypoint_pairs as pad_batch, planted_keypoint_pa
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MASK = (1 << 64) - 1
 STATUS_CLIPPED, STATUS_FEW_CORR, STATUS_NO_MODEL, STATUS_BAD_INDEX = 1, 2, 4, 8
-NEW_SYMBOLS = ["egonn_match_mutual", "egonn_ransac_pairs", "egonn_registration_finish", "egonn_registration_scratch_bytes"]
+NEW_SYMBOLS = ["egonn_match_mutual_scratch_bytes", "egonn_match_mutual", "egonn_ransac_pairs", "egonn_registration_finish",
+               "egonn_registration_scratch_bytes"]
 
 # Hypotheses within BAND of a decision threshold are excused from the per-hypothesis parity of the GPU test.  The issue
 # asks for a band >= 100 x the largest measured difference between the device's and this restatement's transformed
@@ -289,6 +291,10 @@ def test_new_symbols_declared_and_exported(built):
         assert name in declared and name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name), name
     assert lib.egonn_registration_scratch_bytes(4, 256, 10000) == 4 * 40 * 16
     assert lib.egonn_registration_scratch_bytes(4, 257, 10000) == -1 and lib.egonn_registration_scratch_bytes(4, 128, 0) == -1
+    # 64-row x 32-column tiles: (cdiv(n, 64) + cdiv(n, 32)) * n partial minima per pair, a double and an int32 each
+    assert lib.egonn_match_mutual_scratch_bytes(3, 200) == 3 * (4 + 7) * 200 * 12
+    assert lib.egonn_match_mutual_scratch_bytes(3, 200) == lib.egonn_match_candidates_scratch_bytes(3, 1, 200)
+    assert lib.egonn_match_mutual_scratch_bytes(3, 257) == -1 and lib.egonn_match_mutual_scratch_bytes(-1, 128) == -1
 
 
 def test_argument_checks_need_no_gpu(built):
@@ -296,10 +302,22 @@ def test_argument_checks_need_no_gpu(built):
     from egonn_amd import _lib
     lib = _lib.load()
     one = 16        # non-null, aligned, never dereferenced: every call below fails its argument check first
-    assert lib.egonn_match_mutual(one, one, one, one, 1, 257, 128, one, one, None) == 1
-    assert b"n_max" in lib.egonn_last_error()
-    assert lib.egonn_match_mutual(one, one, one, one, 1, 128, 30, one, one, None) == 1
-    assert lib.egonn_match_mutual(None, one, one, one, 1, 128, 128, one, one, None) == 1
+    need = lib.egonn_match_mutual_scratch_bytes(1, 128)
+    assert need == (2 + 4) * 128 * 12
+
+    def match(feat1=one, feat2=one, n_max=128, dim=128, corr=one, scratch=one, nbytes=need):
+        return lib.egonn_match_mutual(feat1, feat2, one, one, 1, n_max, dim, corr, one, scratch, nbytes, None)
+    # shape, width, null pointers, 16-byte alignment, then scratch size and 8-byte alignment: all before the first HIP call
+    for kw, word in ((dict(n_max=257), b"n_max"), (dict(dim=30), b"width 30"), (dict(feat1=None), b"null"),
+                     (dict(feat2=None), b"null"), (dict(corr=None), b"null"), (dict(scratch=None), b"null"),
+                     (dict(feat1=one + 4), b"16-byte aligned"), (dict(feat2=one + 8), b"16-byte aligned"),
+                     (dict(nbytes=need - 1), b"scratch needs"), (dict(scratch=one + 4), b"8-byte aligned")):
+        assert match(**kw) == 1, kw
+        assert word in lib.egonn_last_error() and b"match_mutual" in lib.egonn_last_error(), (kw, lib.egonn_last_error())
+    assert match(n_max=257, dim=30, feat1=None, scratch=None) == 1 and b"n_max" in lib.egonn_last_error()     # the order
+    assert match(dim=30, feat1=None, scratch=None) == 1 and b"width" in lib.egonn_last_error()
+    assert match(feat1=one + 4, scratch=None) == 1 and b"null" in lib.egonn_last_error()
+    assert match(feat1=one + 4, nbytes=0) == 1 and b"16-byte" in lib.egonn_last_error()
     assert lib.egonn_ransac_pairs(one, one, one, one, one, one, None, 1, 128, 0, 0, 0.5, one, 1 << 20, None, None, None) == 1
     assert lib.egonn_ransac_pairs(one, one, one, one, one, one, None, 1, 128, 100, 0, 0.5, None, 0, None, None, None) == 1
     assert lib.egonn_ransac_pairs(one, one, one, one, one, one, None, 1, 128, 1000, 0, 0.5, one, 8, None, None, None) == 1
@@ -352,6 +370,28 @@ def test_kabsch_recovers_planted_transforms():
     Qm = Q * np.array([1.0, 1.0, -1.0])
     Rm, _ = kabsch(S, Qm)
     assert np.allclose(np.linalg.det(Rm), 1.0)
+
+
+def test_matching_sets_are_recorded_and_inside_the_restatement_cap():
+    """every operand set of tests/match_data.py: its regenerated inputs hash to what tests/golden/match_parent.npz recorded,
+    the recorded result (the parent commit's kernel on an MI355X) passes the float64 restatement's check, and the restatement
+    alone stays inside the cap of the GPU tests (rows within match_band of a tie <= 1 %; exact duplicates have gap 0 and are
+    decided by the lowest-index rule, not excused)"""
+    from tests import match_data as D
+    sets = [(name, D.dense_of(*s), s) for name, s in D.index_sets().items()] + [(n, s, s) for n, s in D.dense_sets().items()]
+    assert len(sets) == 15
+    for name, (F1, F2, n1, n2), hashed in sets:
+        corr, n_corr = D.recorded(name, hashed)
+        assert corr.shape == (len(F1), F1.shape[1], 2) and n_corr.shape == (len(F1),)
+        excused, total, unchecked = D.check_matching(D.rows_of(F1, F2, n1, n2), corr, n_corr)
+        assert excused <= D.EXCUSED_ROW_CAP * total and unchecked == 0, (name, excused, total, unchecked)
+
+
+def test_one_distance_loop_in_the_library():
+    """the fp64 distance loop of the matching operator exists in one kernel file"""
+    csrc = os.path.join(REPO, "egonn_amd", "csrc")
+    holders = [f for f in sorted(os.listdir(csrc)) if f.endswith(".hip") and "fma(d, d, acc" in open(os.path.join(csrc, f)).read()]
+    assert holders == ["match.hip"]
 
 
 def test_mutual_matching_rules():

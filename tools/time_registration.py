@@ -66,8 +66,11 @@ def main():
             st = _lib._stream()
             p = lambda t: t.data_ptr()                                     # noqa: E731
 
+            mscratch = _lib.scratch(lib.egonn_match_mutual_scratch_bytes(P, nk), "cuda")
+
             def match():
-                _lib.check(lib.egonn_match_mutual(p(F1), p(F2), p(n1), p(n2), P, nk, F1.shape[2], p(corr), p(ncorr), st))
+                _lib.check(lib.egonn_match_mutual(p(F1), p(F2), p(n1), p(n2), P, nk, F1.shape[2], p(corr), p(ncorr), p(mscratch),
+                                                  mscratch.numel() * 8, st))
 
             def ransac():
                 _lib.check(lib.egonn_ransac_pairs(p(K1), p(K2), p(n1), p(n2), p(corr), p(ncorr), p(pid), P, nk, H, 0, 0.5,

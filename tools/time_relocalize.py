@@ -2,8 +2,12 @@
 back-to-back calls, median of the windows after warm-up; two forms that are compared are ALTERNATED window by window in the
 same run, so both see the same machine).
 
-  1. matching  egonn_match_candidates (candidates read from the resident map by index) against the parent commit's way,
-               torch gather of both operands + egonn_match_mutual, at (Q, k) = (1, 20), (16, 20), (256, 20), n_k = 128, D = 128
+  1. matching  egonn_match_candidates (candidates read from the resident map by index) against torch gather of both
+               operands + egonn_match_mutual, at (Q, k) = (1, 20), (16, 20), (256, 20), n_k = 128, D = 128.  Both entry points
+               run the same tile / merge kernels (csrc/match.hip), so the "gather + match_mutual" column now times those
+               kernels on gathered operands: the difference is the cost of the gather alone.  (Up to commit a2c5576
+               egonn_match_mutual ran a kernel of its own, one workgroup per pair; DESIGN.md 3.14 keeps those figures.)
+               The two forms must agree bit for bit.
   2. the whole verify_candidates call at the same points (default call, and with its buffers reused through out=)
   3. Relocalizer.localize at batch 1 and 16 on 50 k-point synthetic scans (seeded weights, a map of --map_scans scans)
 
@@ -86,7 +90,8 @@ def main():
         ncorr, stat = torch.empty(P, dtype=torch.int32, device="cuda"), torch.empty(P, dtype=torch.int32, device="cuda")
         corr2, ncorr2 = torch.empty_like(corr), torch.empty_like(ncorr)
         nb = lib.egonn_match_candidates_scratch_bytes(Q, k, nk)
-        scratch = torch.empty(nb // 8 + 1, dtype=torch.int64, device="cuda")
+        assert nb == lib.egonn_match_mutual_scratch_bytes(P, nk)
+        scratch, scratch2 = _lib.scratch(nb, "cuda"), _lib.scratch(nb, "cuda")
         bank_f, bank_n = km.descriptors, km.counts
         st = _lib._stream()
         flat = nn.reshape(-1).long()
@@ -99,7 +104,7 @@ def main():
         def gathered():
             f1, f2 = qf[qidx], bank_f[flat]                        # (P, n_k, D) copies of both operands, as a host-side glue does
             n1, n2 = qn[qidx], bank_n[flat]
-            _lib.check(lib.egonn_match_mutual(p(f1), p(f2), p(n1), p(n2), P, nk, D, p(corr2), p(ncorr2), st))
+            _lib.check(lib.egonn_match_mutual(p(f1), p(f2), p(n1), p(n2), P, nk, D, p(corr2), p(ncorr2), p(scratch2), nb, st))
 
         reps, burst = (7, 2) if P >= 1024 else (10, 40)
         row = {"queries": Q, "k": k, "pairs": P, "n_k": nk, "dim": D, "map_entries": M}
