@@ -34,6 +34,9 @@ _SIGS = [
     ("egonn_prepare_maps", C.c_int, [_P, C.c_int, _P]),
     ("egonn_debug_rowgroup_tables", C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
     ("egonn_debug_rowgroup_perm", C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+    ("egonn_debug_radix_sort_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_debug_radix_sort", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(C.c_int32), _P, C.c_int64, _P]),
     ("egonn_voxelize", C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
     ("egonn_ctx_reserve", C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     ("egonn_voxelize_device", C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
@@ -264,6 +267,23 @@ def concat_clouds(clouds, dev):
         off.append(off[-1] + c.shape[0])
     pts = torch.cat([c.to(device=dev, dtype=torch.float32) for c in ts]) if ts else torch.zeros((0, 3), device=dev)
     return pts, torch.tensor(off, dtype=torch.int64, device=dev)
+
+
+def debug_radix_sort(keys_in, vals_in, keys_out, vals_out, n: int, nbits: int, n_dev=None, seg_offsets=None, idx_bits: int = 0,
+                     either_pair: bool = False, scratch_buf=None, scratch_bytes: Optional[int] = None) -> int:
+    """test hook (egonn_debug_radix_sort): the flat radix sort of the first n (u64 key as int64, u32 value as int32) pairs,
+    or with seg_offsets (device int64, segments + 1) the segmented one.  -> 0: the result is in (keys_in, vals_in), 1: in
+    (keys_out, vals_out).  scratch_buf / scratch_bytes: a scratch of the caller's (default: one of the reported size)."""
+    lib = load()
+    B = 0 if seg_offsets is None else seg_offsets.numel() - 1
+    need = lib.egonn_debug_radix_sort_scratch_bytes(int(n), B)
+    if scratch_buf is None:
+        scratch_buf = scratch(need, keys_in.device)
+    pair = C.c_int32(-1)
+    call(keys_in.device, lib.egonn_debug_radix_sort, keys_in.data_ptr(), vals_in.data_ptr(), keys_out.data_ptr(),
+         vals_out.data_ptr(), int(n), int(nbits), _ptr(n_dev), _ptr(seg_offsets), B, int(idx_bits), int(bool(either_pair)),
+         C.byref(pair), scratch_buf.data_ptr(), need if scratch_bytes is None else int(scratch_bytes))
+    return pair.value
 
 
 def require_gpu() -> torch.device:

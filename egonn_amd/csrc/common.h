@@ -322,18 +322,24 @@ int reg_check_shape(const char* who, int P, int n_max);                     // r
 int rel_check_shape(const char* who, int Q, int k, int M, int n_max);       // relocalize.hip
 
 // ------------------------------------------------------------------ sort.hip
-// LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits).  Result lands in (keys_out, vals_out) — or, when the caller
-// passes keys_res / vals_res, in whichever of the two buffer pairs the last pass wrote (an even number of passes ends in the
-// "in" pair: no copy; the pointers are returned).  Stable.  Both pairs are clobbered.  Scratch comes from `ws`: a context's
-// sort arena (grown on demand) or a borrowed span of at least radix_sort_scratch_bytes(n) + 512 bytes (Arena::alloc aligns
-// every carve to 256).
-// n_dev (nullable): device-resident element count (<= n); n then only sizes the grid and the scratch.
+// LSD radix sort of (u64 key, u32 value) pairs, 8 bits per pass, ceil(nbits / 8) passes.  The sort reads WHOLE DIGITS: the last
+// digit is not masked, so it orders the pairs on bits [0, 8 * ceil(nbits / 8)) of the key, not on [0, nbits) — a caller leaves
+// the bits between nbits and that end zero (every call site does) or accepts that they take part.  Bits from that end on are
+// never read.  Keys are carried whole.  Result lands in (keys_out, vals_out) — or, when the caller passes keys_res / vals_res, in
+// whichever of the two buffer pairs the last pass wrote (an even number of passes ends in the "in" pair: no copy; the pointers
+// are returned).  Stable.  Both pairs are clobbered below the element count, nothing is written from it on.  Scratch comes from
+// `ws`: a context's sort arena (grown on demand) or a borrowed span of at least radix_sort_scratch_bytes(n) + 512 bytes
+// (Arena::alloc aligns every carve to 256).  tests/test_gpu_sort.py pins all of this through egonn_debug_radix_sort.
+// n_dev (nullable): device-resident element count (clipped to n); n then only sizes the grid and the scratch.
 int radix_sort_pairs(Arena& ws, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out,
                      int64_t n, int nbits, hipStream_t stream, const int64_t* n_dev = nullptr, uint64_t** keys_res = nullptr,
                      uint32_t** vals_res = nullptr);
 size_t radix_sort_scratch_bytes(int64_t n);
-// Per-scan variant: every segment [off[b], off[b+1]) (DEVICE int64 offsets, B+1) is sorted on its own on bits [0, nbits), 9 bits
-// per pass — no pass is spent on the batch index of contiguous scans.  The result lands in whichever pair the last pass wrote.
+// Per-scan variant: every segment [off[b], off[b+1]) (DEVICE int64 offsets, B+1, clipped to n) is sorted on its own, 9 bits per
+// pass, ceil(nbits / 9) passes (8 at most) — no pass is spent on the batch index of contiguous scans.  Whole digits here too: the
+// order is on bits [idx_bits, min(64, idx_bits + 9 * ceil(nbits / 9))) of the element, the same rule for the bits between
+// idx_bits + nbits and that end.  The result lands in whichever pair the last pass wrote; rows outside the segments are not
+// written.  idx_bits > 0: packed elements (see sort.hip): the index field is carried, never sorted on.
 // prezeroed (nullable): the per-scan histograms radix_sort_segments_layout(ws, n, B) returns, when the launch in front of the
 // sort has zeroed them already (one memset node less); anything else and the sort zeroes them itself.
 int radix_sort_segments(Arena& ws, uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n,

@@ -11,6 +11,9 @@
 //
 // HBM traffic per pass: 12 B read (hist: 8) + 12 B written per pair; the sort is launch/latency bound at
 // the sizes of this path (<= a few M keys), not bandwidth bound.
+//
+// Both sorts read whole digits (the last one is not masked; the contract is stated in common.h).  They are tested on their
+// own, bit for bit against numpy, through the hook at the end of this file: tests/test_gpu_sort.py.
 #include "common.h"
 
 namespace egonn {
@@ -220,6 +223,17 @@ __global__ __launch_bounds__(SORT_BLOCK) void sort_scatter_kernel(
   }
 }
 
+// even number of passes and a caller that wants (keys_out, vals_out): the passes start from a copy of the input in the "out" pair
+__global__ __launch_bounds__(SORT_BLOCK) void sort_copy_kernel(const uint64_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+                                                               uint64_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
+                                                               int64_t n_cap, const int64_t* __restrict__ n_dev) {
+  const int64_t i = (int64_t)blockIdx.x * SORT_BLOCK + threadIdx.x;
+  if (i < sort_count(n_cap, n_dev)) {
+    keys_out[i] = keys_in[i];
+    vals_out[i] = vals_in[i];
+  }
+}
+
 size_t radix_sort_scratch_bytes(int64_t n) {
   const int64_t tiles = cdiv(n > 0 ? n : 1, SORT_TILE);
   const int64_t supers = cdiv(tiles, SORT_SUPER);
@@ -253,8 +267,9 @@ int radix_sort_pairs(Arena& ws, uint64_t* keys_in, uint32_t* vals_in, uint64_t* 
     *keys_res = keys_in;
     *vals_res = vals_in;
   } else if (src == 1) {                    // even number of passes: start from the "out" buffers
-    HIP_CHECK(hipMemcpyAsync(keys_out, keys_in, sizeof(uint64_t) * n, hipMemcpyDeviceToDevice, stream));
-    HIP_CHECK(hipMemcpyAsync(vals_out, vals_in, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, stream));
+    // (a kernel, not two hipMemcpyAsync of the capacity: with n_dev the rows from *n_dev on are not the sort's to write)
+    hipLaunchKernelGGL(sort_copy_kernel, dim3((unsigned)cdiv(n, SORT_BLOCK)), dim3(SORT_BLOCK), 0, stream, keys_in, vals_in, keys_out,
+                       vals_out, n, n_dev);
   }
   for (int p = 0; p < passes; ++p) {
     int32_t* superhist = slabs + (int64_t)p * (supers + 1) * 256;
@@ -570,3 +585,53 @@ int radix_sort_segments(Arena& ws, uint64_t* keys_in, uint32_t* vals_in, uint64_
 }
 
 }  // namespace egonn
+
+using namespace egonn;
+
+// ------------------------------------------------------------------ test hook (tests/test_gpu_sort.py; no product path calls it)
+// + 512: either sort carves two arrays out of the span and Arena::alloc aligns each carve to 256
+static size_t debug_sort_span(int64_t n, int n_segments) {
+  return align_up((n_segments ? radix_sort_segments_scratch_bytes(n, n_segments) : radix_sort_scratch_bytes(n)) + 512, 256);
+}
+
+API int64_t egonn_debug_radix_sort_scratch_bytes(int64_t n, int n_segments) {
+  if (n < 0 || n >= (1ll << 31) || n_segments < 0 || n_segments > EGONN_MAX_BATCH) return -1;
+  return (int64_t)debug_sort_span(n, n_segments);
+}
+
+API int egonn_debug_radix_sort(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n, int nbits,
+                               const int64_t* n_dev, const int64_t* seg_offsets, int n_segments, int idx_bits, int either_pair,
+                               int32_t* result_pair, void* scratch, int64_t scratch_bytes, void* stream) {
+  EGONN_REQUIRE(keys_in && vals_in && keys_out && vals_out && result_pair && scratch, EGONN_ERR_INVALID,
+                "debug_radix_sort: null pointer");
+  EGONN_REQUIRE(n >= 0 && n < (1ll << 31), EGONN_ERR_INVALID, "debug_radix_sort: n=%lld outside [0, 2^31)", (long long)n);
+  EGONN_REQUIRE(nbits >= 1 && nbits <= 64, EGONN_ERR_INVALID, "debug_radix_sort: nbits=%d outside [1, 64]", nbits);
+  if (seg_offsets) {
+    EGONN_REQUIRE(n_segments >= 1 && n_segments <= EGONN_MAX_BATCH, EGONN_ERR_INVALID,
+                  "debug_radix_sort: n_segments=%d outside [1, %d]", n_segments, EGONN_MAX_BATCH);
+    EGONN_REQUIRE(!n_dev, EGONN_ERR_INVALID, "debug_radix_sort: the segmented sort takes no n_dev");
+    EGONN_REQUIRE(idx_bits >= 0 && nbits + idx_bits <= 64, EGONN_ERR_INVALID,
+                  "debug_radix_sort: nbits=%d + idx_bits=%d outside [nbits, 64]", nbits, idx_bits);
+    EGONN_REQUIRE(radix_sort_segments_passes(nbits) <= 8, EGONN_ERR_INVALID, "debug_radix_sort: %d segmented passes (8 at most)",
+                  radix_sort_segments_passes(nbits));
+  } else {
+    EGONN_REQUIRE(n_segments == 0 && idx_bits == 0, EGONN_ERR_INVALID,
+                  "debug_radix_sort: n_segments=%d idx_bits=%d without seg_offsets (the flat sort takes neither)", n_segments, idx_bits);
+  }
+  const size_t need = debug_sort_span(n, n_segments);
+  EGONN_REQUIRE(scratch_bytes >= (int64_t)need && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
+                "debug_radix_sort: scratch needs %lld bytes, 256-byte aligned", (long long)need);
+  Arena ws = Arena::view(scratch, need);
+  uint64_t* kres = keys_out;
+  uint32_t* vres = vals_out;
+  if (seg_offsets)
+    EGONN_TRY(radix_sort_segments(ws, keys_in, vals_in, keys_out, vals_out, n, seg_offsets, n_segments, nbits, (hipStream_t)stream,
+                                  &kres, &vres, idx_bits));
+  else if (either_pair)
+    EGONN_TRY(radix_sort_pairs(ws, keys_in, vals_in, keys_out, vals_out, n, nbits, (hipStream_t)stream, n_dev, &kres, &vres));
+  else
+    EGONN_TRY(radix_sort_pairs(ws, keys_in, vals_in, keys_out, vals_out, n, nbits, (hipStream_t)stream, n_dev));
+  EGONN_REQUIRE((kres == keys_in) == (vres == vals_in), EGONN_ERR_STATE, "debug_radix_sort: keys and values ended in different pairs");
+  *result_pair = kres == keys_in ? 0 : 1;
+  return EGONN_OK;
+}

@@ -72,6 +72,24 @@ int egonn_debug_rowgroup_tables(egonn_ctx* ctx, int map_kind, int level_out, uin
  * the two tables above it is the whole row-group form.  Never called by the product path.  [SYNC] */
 int egonn_debug_rowgroup_perm(egonn_ctx* ctx, int map_kind, int level_out, int32_t* perm_out, int64_t capacity_groups,
                               int64_t* n_groups, void* stream);
+/* test hook: the two radix sorts of egonn_amd/csrc/sort.hip on their own, with every argument their call sites use.  Never
+ * called by the product path; needs no context: the sort's histograms live in a borrowed span of the caller's scratch.
+ * seg_offsets NULL: the flat sort of the first n pairs (n_dev nullable: DEVICE int64 count, clipped to n; n_segments =
+ * idx_bits = 0).  either_pair = 0: the result is in (keys_out, vals_out); 1: in whichever pair the last pass wrote.
+ * seg_offsets given (DEVICE int64, n_segments + 1, clipped to n): every segment [seg_offsets[b], seg_offsets[b+1]) is sorted
+ * on its own, rows outside the segments are not touched; idx_bits = 0: (key, value) pairs; idx_bits > 0: keys_in holds packed
+ * elements (sort bits << idx_bits | index inside the segment; vals_in is not read) and the result is key = (segment << nbits) |
+ * (packed >> idx_bits), value = clipped seg_offsets[segment] + index.  n_dev must be NULL, either_pair is ignored.
+ * Both sorts are stable and carry keys whole.  They read WHOLE DIGITS above the first sorted bit (bit 0, or idx_bits): 8 bits
+ * per pass and ceil(nbits / 8) passes flat, 9 bits per pass and ceil(nbits / 9) passes (8 at most) segmented, so key bits
+ * between nbits and the end of the last digit take part in the order; bits from there on are carried and never read.
+ * result_pair (HOST): 0 = the result is in (keys_in, vals_in), 1 = in (keys_out, vals_out); the other pair is clobbered
+ * below the count.  scratch: egonn_debug_radix_sort_scratch_bytes(n, n_segments) bytes (n_segments = 0: the flat sort;
+ * -1 on bad arguments), 256-byte aligned.  No host synchronisation. */
+int64_t egonn_debug_radix_sort_scratch_bytes(int64_t n, int n_segments);
+int egonn_debug_radix_sort(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n, int nbits,
+                           const int64_t* n_dev, const int64_t* seg_offsets, int n_segments, int idx_bits, int either_pair,
+                           int32_t* result_pair, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------ coordinate plan
  * replaces ME.utils.sparse_quantize      datasets/quantization.py:42,83   (Cartesian/Polar quantizer __call__)

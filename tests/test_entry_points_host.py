@@ -4,7 +4,9 @@ in one place, and the library must answer with the recorded status and message b
 EXPECTED was recorded from the library as it stood before the entry points moved out of model.hip into the files that hold their
 kernels (`python tests/test_entry_points_host.py [path/to/libegonn_hip.so]` prints the table of the library it is given); a change
 of an entry point keeps it unless it means to change the C ABI's behaviour.  A case whose broken argument is not caught by a
-check reaches a HIP call (status 2 on a machine without a device) and has no row here.
+check reaches a HIP call (status 2 on a machine without a device) and has no row here.  The rows of egonn_debug_radix_sort were
+recorded when that hook was added.  Its check of the segmented pass count (8 at most) has no row: nbits <= 64 is checked first and
+64 bits are 8 passes of 9, so no argument set reaches it.
 
 The borrowed (non-owning) Arena that the ICP entry points sort on is a host-side object: tests/arena_view_main.cpp is a program
 of its own that this file compiles for the host and runs."""
@@ -51,6 +53,9 @@ def _base(lib):
         "egonn_voxel_downsample": [P, 10, P, 1, 0.1, None, P, P, P, P, P, lib.egonn_voxel_downsample_scratch_bytes(10, 1), None],
         "egonn_icp_pairs": [P, 10, P, P, 10, P, 1, None, 1.2, 200, 1e-6, 1e-6] + [P] * 5 + [None] * 3 +
                            [P, lib.egonn_icp_scratch_bytes(10, 10, 1), None],
+        # keys_in, vals_in, keys_out, vals_out, n, nbits, n_dev, seg_offsets, n_segments, idx_bits, either_pair, result_pair | scratch
+        "egonn_debug_radix_sort": [P, P, P, P, 100, 16, None, None, 0, 0, 0, C.pointer(C.c_int32(-1)), P,
+                                   lib.egonn_debug_radix_sort_scratch_bytes(100, 0), None],
     }
 
 
@@ -58,6 +63,7 @@ def _base(lib):
 # The last two: the ICP entry points sort on a borrowed span of the caller's scratch, so one byte less than
 # egonn_*_scratch_bytes reports must be refused up front (tests/test_icp_host.py covers a scratch of 8 bytes).
 LESS = "one less"
+SEG = {7: P, 8: 2, 13: 1 << 20}
 CASES = [
     ("egonn_triplet_loss", "null embeddings", {0: None}),
     ("egonn_triplet_loss", "null scratch", {9: None}),
@@ -129,6 +135,25 @@ CASES = [
     ("egonn_filter_points", "scratch too small", {11: LESS}),
     ("egonn_voxel_downsample", "scratch one byte short", {11: LESS}),
     ("egonn_icp_pairs", "scratch one byte short", {21: LESS}),
+    # the sort hook: flat without seg_offsets; SEG turns the base into a segmented call of two segments with scratch to spare
+    ("egonn_debug_radix_sort", "null keys_in", {0: None}),
+    ("egonn_debug_radix_sort", "null vals_out", {3: None}),
+    ("egonn_debug_radix_sort", "null result_pair", {11: None}),
+    ("egonn_debug_radix_sort", "null scratch", {12: None}),
+    ("egonn_debug_radix_sort", "n = -1", {4: -1}),
+    ("egonn_debug_radix_sort", "n = 2^31", {4: 1 << 31}),
+    ("egonn_debug_radix_sort", "nbits = 0", {5: 0}),
+    ("egonn_debug_radix_sort", "nbits = 65", {5: 65}),
+    ("egonn_debug_radix_sort", "idx_bits without offsets", {9: 16}),
+    ("egonn_debug_radix_sort", "segments without offsets", {8: 2}),
+    ("egonn_debug_radix_sort", "nbits + idx_bits = 65", {**SEG, 5: 37, 9: 28}),
+    ("egonn_debug_radix_sort", "idx_bits = -1", {**SEG, 9: -1}),
+    ("egonn_debug_radix_sort", "n_segments = 0", {**SEG, 8: 0}),
+    ("egonn_debug_radix_sort", "n_segments = 4097", {**SEG, 8: 4097}),
+    ("egonn_debug_radix_sort", "n_dev with segments", {**SEG, 6: P}),
+    ("egonn_debug_radix_sort", "misaligned scratch", {12: P + 8}),
+    ("egonn_debug_radix_sort", "scratch one byte short", {13: LESS}),
+    ("egonn_debug_radix_sort", "segmented scratch one byte short", {**SEG, 13: 40447}),
 ]
 
 # (status, egonn_last_error()) of every case above
@@ -203,6 +228,24 @@ EXPECTED = {
     ('egonn_filter_points', 'scratch too small'): (1, 'ingest: scratch too small'),
     ('egonn_voxel_downsample', 'scratch one byte short'): (1, 'voxel_downsample: scratch needs 23552 bytes, 256-byte aligned'),
     ('egonn_icp_pairs', 'scratch one byte short'): (1, 'icp_pairs: scratch needs 25344 bytes, 256-byte aligned'),
+    ('egonn_debug_radix_sort', 'null keys_in'): (1, 'debug_radix_sort: null pointer'),
+    ('egonn_debug_radix_sort', 'null vals_out'): (1, 'debug_radix_sort: null pointer'),
+    ('egonn_debug_radix_sort', 'null result_pair'): (1, 'debug_radix_sort: null pointer'),
+    ('egonn_debug_radix_sort', 'null scratch'): (1, 'debug_radix_sort: null pointer'),
+    ('egonn_debug_radix_sort', 'n = -1'): (1, 'debug_radix_sort: n=-1 outside [0, 2^31)'),
+    ('egonn_debug_radix_sort', 'n = 2^31'): (1, 'debug_radix_sort: n=2147483648 outside [0, 2^31)'),
+    ('egonn_debug_radix_sort', 'nbits = 0'): (1, 'debug_radix_sort: nbits=0 outside [1, 64]'),
+    ('egonn_debug_radix_sort', 'nbits = 65'): (1, 'debug_radix_sort: nbits=65 outside [1, 64]'),
+    ('egonn_debug_radix_sort', 'idx_bits without offsets'): (1, 'debug_radix_sort: n_segments=0 idx_bits=16 without seg_offsets (the flat sort takes neither)'),
+    ('egonn_debug_radix_sort', 'segments without offsets'): (1, 'debug_radix_sort: n_segments=2 idx_bits=0 without seg_offsets (the flat sort takes neither)'),
+    ('egonn_debug_radix_sort', 'nbits + idx_bits = 65'): (1, 'debug_radix_sort: nbits=37 + idx_bits=28 outside [nbits, 64]'),
+    ('egonn_debug_radix_sort', 'idx_bits = -1'): (1, 'debug_radix_sort: nbits=16 + idx_bits=-1 outside [nbits, 64]'),
+    ('egonn_debug_radix_sort', 'n_segments = 0'): (1, 'debug_radix_sort: n_segments=0 outside [1, 4096]'),
+    ('egonn_debug_radix_sort', 'n_segments = 4097'): (1, 'debug_radix_sort: n_segments=4097 outside [1, 4096]'),
+    ('egonn_debug_radix_sort', 'n_dev with segments'): (1, 'debug_radix_sort: the segmented sort takes no n_dev'),
+    ('egonn_debug_radix_sort', 'misaligned scratch'): (1, 'debug_radix_sort: scratch needs 18944 bytes, 256-byte aligned'),
+    ('egonn_debug_radix_sort', 'scratch one byte short'): (1, 'debug_radix_sort: scratch needs 18944 bytes, 256-byte aligned'),
+    ('egonn_debug_radix_sort', 'segmented scratch one byte short'): (1, 'debug_radix_sort: scratch needs 40448 bytes, 256-byte aligned'),
 }
 
 

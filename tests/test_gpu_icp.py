@@ -107,6 +107,27 @@ def test_downsample_matches_restatement(gpu):
     assert np.array_equal(alone[0], pts[2]) and np.array_equal(cnt_alone[0], cnt[2])
 
 
+def test_downsample_where_the_sort_loops_wrap(gpu):
+    """clouds of exactly one tile of the 64-bit segmented sort (2048 keys) less one, one tile, one tile and a key, and of 9 and
+    11 tiles (16 385 and 20 481 points: the scatter kernel sums the histogram rows of a cloud's earlier tiles eight at a time,
+    8 rows fill one round, 10 need a second), many points per voxel, and a crop that drops a share of every cloud: the
+    dropped points carry the key ~0 and must sort behind every kept point of their own cloud.  The voxel means are sums in
+    input order: a sort that was not stable would move them beyond the bound of _check_downsample."""
+    rng = np.random.default_rng(16385)
+    sizes = (2047, 2048, 2049, 16385, 20481)
+    clouds = [rng.uniform(-2, 2, size=(n, 3)).astype(np.float32) for n in sizes]
+    crop = (-1.2, 1.6, None, 1.5, float("nan"), None)
+    pts, cnt, status, off = _downsample(gpu, clouds, 0.5, crop)
+    assert (status == 0).all() and off[0] == 0 and off[-1] == sum(len(p) for p in pts)
+    for i, n in enumerate(sizes):
+        _check_downsample(pts[i], cnt[i], clouds[i], 0.5, crop)
+        assert 0.3 * n < cnt[i].sum() < 0.7 * n                  # a share of the cloud is cropped away, a share is kept
+    assert cnt[0].max() > 3 and cnt[3].max() > 30                # many points per voxel
+    for i in (3, 4):                                             # in the batch = alone, bit for bit
+        alone, cnt_alone, st, _ = _downsample(gpu, clouds[i:i + 1], 0.5, crop)
+        assert st.tolist() == [0] and np.array_equal(alone[0], pts[i]) and np.array_equal(cnt_alone[0], cnt[i])
+
+
 def test_downsample_edges(gpu):
     p = np.array([[0.0, 0, 0], [0.04, 0.04, 0.04], [0.06, 0, 0], [1.0, 1.0, 1.0], [-0.3, 5, 5], [0.5, 0.2, 0.1]], np.float32)
     # crop: the point exactly on min_x (0.0) is dropped, the one exactly on max_x (1.0) is kept; NaN / None = no bound
