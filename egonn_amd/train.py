@@ -111,6 +111,9 @@ def level_totals(ctx: _lib.Context, group=None) -> List[float]:
     return t.tolist()
 
 
+BN_MAX_COLUMNS = 256       # egonn_col_stats: 1..256 channels
+
+
 class BatchNormFn(Function):
     """nn.BatchNorm1d over all rows in train mode (MinkowskiBatchNorm), optional fused ReLU, optional SyncBN.
     Statistics: ONE pass of shifted sums (sum d, sum d^2 with d = x - running_mean: additive over ranks), formed and kept
@@ -427,6 +430,10 @@ def netvlad_pool(ctx, level: int, x: torch.Tensor, nv, group=None) -> torch.Tens
     if ctx.batch_size < 2:            # nn.BatchNorm1d's own rule for bn2, before any device work
         raise ValueError(f"Expected more than 1 value per channel when training, got input size "
                          f"torch.Size([{ctx.batch_size}, {nv.output_dim}])")
+    if nv.output_dim > BN_MAX_COLUMNS:
+        # bn2 and the gating's BatchNorm would refuse only after NetVLADFn had stepped bn1's running statistics
+        raise _lib.EgonnError(f"netvlad_pool: output_dim {nv.output_dim} unsupported in train mode (BatchNormFn holds at most "
+                              f"{BN_MAX_COLUMNS} columns)", 1)
     for w in (nv.cluster_weights, nv.cluster_weights2, nv.hidden1_weights):
         assert w.is_contiguous() and w.dtype == torch.float32
     y = NetVLADFn.apply(x, nv.cluster_weights, nv.cluster_weights2, nv.bn1.weight, nv.bn1.bias, nv.hidden1_weights, ctx, level,

@@ -12,9 +12,12 @@ B. End-to-end fixtures `minkloc_{netvlad,netvladgc,mac,spoc}_train_cart03.npz`: 
    FIVE scans of unequal size (with B = 2 the B-row bn2 maps every descriptor to +-gamma + beta and the gradients
    upstream of it collapse to the order of eps).
 
+C. Clamp fixture `netvlad_train_edges.npz` (mode `edges`, see main_edges): the recipe of A on the two eps-clamp cases of
+   tests/netvlad_edges_data.py.
+
 No reference source text is stored — only arrays the reference code computed.
 
-    python tests/golden/make_golden_pooling_train.py [ops|e2e]
+    python tests/golden/make_golden_pooling_train.py [ops|e2e|edges]
 """
 from __future__ import annotations
 
@@ -173,8 +176,62 @@ def main_e2e():
         assert size <= LIMIT, (name, size)
 
 
+def main_edges():
+    """C. `netvlad_train_edges.npz`: main_ops' recipe on the two clamp cases of tests/netvlad_edges_data.py (one scan all zero;
+    one column, or all, of cluster_weights2 zero, so that a per-cluster norm, or the whole descriptor's, is exactly 0 and
+    F.normalize divides by its eps).  Writes this file only."""
+    bootstrap_reference()
+    import numpy as np
+    import torch
+    from layers.netvlad import NetVLADLoupe
+    from egonn_amd.synth import seeded_tensor
+    from tests import netvlad_edges_data as E
+
+    out = {}
+    for name in E.CLAMP_CASES:
+        case = E.BY_NAME[name]
+        rows, state = E.features(case, "train"), E.state(case, "train")
+        torch.manual_seed(0)
+        m = NetVLADLoupe(feature_size=case.C, cluster_size=64, output_dim=case.D, gating=case.gating, add_batch_norm=True)
+        sd = {k: torch.from_numpy(state[k] if k in state else seeded_tensor(case.seed, k, tuple(v.shape)))
+              for k, v in m.state_dict().items()}
+        assert all(k in sd for k in state)
+        m.load_state_dict(sd)
+        m = m.double().train()
+        xs = [torch.from_numpy(r).double().requires_grad_(True) for r in rows]
+        padded = torch.nn.utils.rnn.pad_sequence(xs, batch_first=True)
+        y = m(padded)
+        g = E.upstream(case)
+        (y * torch.from_numpy(g).double()).sum().backward()
+        p = name + "/"
+        out[p + "C"], out[p + "D"], out[p + "gating"] = np.int64(case.C), np.int64(case.D), np.int64(case.gating)
+        out[p + "seed"] = np.int64(case.seed)
+        out[p + "offsets"] = E.offsets(case)
+        out[p + "x"] = np.concatenate(rows, axis=0)
+        out[p + "cluster_weights2"] = state["cluster_weights2"]                  # the edited tensor, as the module held it
+        out[p + "out"] = y.detach().numpy()
+        out[p + "upstream"] = g
+        out[p + "grad_x"] = np.concatenate([x.grad.numpy() for x in xs], axis=0)
+        params = dict(m.named_parameters())
+        for k in PARAM_KEYS:
+            if k in params:
+                out[p + "grad/" + k] = params[k].grad.numpy()
+        for k, v in m.state_dict().items():
+            if "running" in k or k.endswith("num_batches_tracked"):
+                out[p + "buf/" + k] = v.numpy()
+        print(name, "M =", padded.shape[0] * padded.shape[1], "out", tuple(y.shape),
+              "|grad x| max", float(np.abs(out[p + "grad_x"]).max()))
+    path = os.path.join(HERE, "netvlad_train_edges.npz")
+    np.savez_compressed(path, **out)
+    size = os.path.getsize(path)
+    print("netvlad_train_edges.npz", len(out), "arrays", f"{size / 1e6:.3f} MB")
+    assert size <= LIMIT, size
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
+    if what == "edges":                 # a mode of its own: `all` regenerates the earlier fixtures only
+        main_edges()
     if what in ("all", "ops"):
         main_ops()
     if what in ("all", "e2e"):

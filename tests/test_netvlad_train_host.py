@@ -48,7 +48,7 @@ def op_state(case):
     return {k: seeded_tensor(seed, k, s) for k, s in shapes.items()}
 
 
-def netvlad_train_f64(x, offsets, p, buf, gating, eps=1e-5, momentum=0.1):
+def netvlad_train_f64(x, offsets, p, buf, gating, eps=1e-5, momentum=0.1, head=True):
     """Train-mode NetVLADLoupe under NetVLADWrapper's zero padding, float64 torch, differentiable, from the rows x (N, C) and
     the scan offsets (B + 1).  p: parameters, buf: running statistics (both dicts of float64 tensors, reference key names).
     The (Nmax - n_b) pad rows of scan b are never built: a pad row has the logits 0 before bn1, so
@@ -56,6 +56,7 @@ def netvlad_train_f64(x, offsets, p, buf, gating, eps=1e-5, momentum=0.1):
       * every pad row has the assignment softmax(shift), shift = beta - mean * gamma * invstd, and adds it to a_sum_b;
       * pad rows add nothing to X^T A (x = 0).
     Autograd through these expressions carries the pad rows' share of the gradients of gamma, beta, mean and variance.
+    head=False stops before bn2 and the gating: what NetVLADFn (egonn_netvlad_train_forward) returns.
     Returns (y (B, D), {buffer name: value after the step})."""
     off = [int(o) for o in offsets]
     B = len(off) - 1
@@ -81,6 +82,8 @@ def netvlad_train_f64(x, offsets, p, buf, gating, eps=1e-5, momentum=0.1):
         V = F.normalize(V, dim=0, p=2)
         rows.append(F.normalize(V.reshape(1, -1), dim=1, p=2)[0])
     y = torch.stack(rows) @ hid
+    if not head:
+        return y, new
 
     def bn_rows(t, name):
         rm, rv = buf[name + ".running_mean"].clone(), buf[name + ".running_var"].clone()
