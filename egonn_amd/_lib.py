@@ -29,6 +29,7 @@ _SIGS = [
     ("egonn_last_error", C.c_char_p, []),
     ("egonn_debug_set_naive_conv", C.c_int, [_P, C.c_int]),
     ("egonn_debug_set_ksplit", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("egonn_debug_set_resident", C.c_int, [_P, C.c_int, C.c_int]),
     ("egonn_debug_keep_level_features", C.c_int, [_P, C.c_int]),
     ("egonn_debug_set_trace", C.c_int, [_P]),
     ("egonn_prepare_maps", C.c_int, [_P, C.c_int, _P]),
@@ -476,6 +477,11 @@ class Context:
     def set_ksplit(self, map_class: int, level: int, kparts: int = -1, kw: int = -1, col_parts: int = -1):
         """tests / A-B only: offset-split rule of the fp32 sparse convolutions (map_class 0: k=3 maps, 1: 8-slot maps); -1 keeps a field."""
         check(self.lib.egonn_debug_set_ksplit(self.h, int(map_class), int(level), int(kparts), int(kw), int(col_parts)))
+
+    def set_resident(self, mask: int = -1, max_workgroups: int = 0):
+        """tests / A-B only: 32->32 split convolutions on the weight-resident form (bit 0: k=3 of level 1, bit 1: k=2,s=2 into
+        level 1, bit 2: gated k=2,s=2 into level 2; -1: the product rule); workgroups per resident launch, 0 = default."""
+        check(self.lib.egonn_debug_set_resident(self.h, int(mask), int(max_workgroups)))
 
     def global_avg_pool(self, level: int, x: torch.Tensor):
         x = _dev_f32(x, self.device)

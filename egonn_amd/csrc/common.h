@@ -254,6 +254,11 @@ struct KsRule {
   int8_t col_parts[EGONN_NUM_LEVELS];   // column parts per task (0 = automatic)
 };
 
+// Product rule of the weight-resident 32->32 split convolutions: bits of sconv_resident_bit (kernels.h) that are on by default.
+// 6 = the two strided convolutions (into level 1; gated, into level 2), which read every input row once; the k=3 convolutions
+// of level 1 stay on the lock-step kernel (measured: DESIGN.md §3.1, §3.5, profiles/r07a_*)
+static constexpr int SCONV_RESIDENT_DEFAULT = 6;
+
 struct Ctx {
   Profiler prof;
   KsRule ks_rule;             // set at context creation (sconv_ksplit_defaults); egonn_debug_set_ksplit
@@ -268,6 +273,8 @@ struct Ctx {
   size_t ks_part_floats = 0;  // by egonn_forward / the stand-alone operator entry points (sconv_ksplit_scratch_floats)
   const void* sort_prezeroed = nullptr;   // the per-scan histograms of the segmented sort were zeroed by the kernel in front of it
                                           // (coords.hip: set by the key kernel's launcher, handed to the sort, cleared after it)
+  int resident_mask = SCONV_RESIDENT_DEFAULT;   // 32->32 split convolutions on the weight-resident form (sconv_resident_bit;
+  int resident_wgs = 0;                         // egonn_debug_set_resident); its workgroups per launch, 0 = default
   int keep_level_features = 0;   // egonn_debug_keep_level_features: no fusion that leaves a level's block output unmaterialised
   int operand_autoscale = 0;  // egonn_ctx_set_operand_autoscale: the fp16-split convolutions scale their INPUT by a power of two per launch
                               // (max |in| -> [2^13, 2^14), undone in the epilogue): the input-gradient convolutions of a training step

@@ -64,6 +64,7 @@ struct SconvLaunch {
   int32_t* flags = nullptr;              // the plan's flag word (bit 3: fp16 range guard); split arithmetic only
   int B = 0;                             // split, gated input: scans of the batch
   int kparts = 1, kw = 0, col_parts = 0; // split: offset parts as workgroups / inside a workgroup (0, 1: none), column parts per task (0 = automatic)
+  int resident = 0, resident_wgs = 0;    // split, 32->32: the weight-resident form (sconv_resident_rule); workgroups, 0 = default
   float* part = nullptr; size_t part_floats = 0;           // split: scratch for the partial tiles of an offset-split launch
   uint32_t* in_absmax = nullptr; int64_t in_elems = 0;     // split, operand autoscale: 8 bytes of scratch, the elements of `in`
 };
@@ -83,6 +84,10 @@ size_t sconv_split_part_floats(const RowGroups& rg, int cout, int kparts);
 void sconv_ksplit_rule(const Ctx* ctx, int kind, int level, int* kparts, int* col_parts, int* kw);
 void sconv_ksplit_defaults(KsRule* r);                  // the product rule (+ the EGONN_KSPLIT* measurement overrides)
 size_t sconv_ksplit_scratch_floats(const Ctx* ctx);    // partial-tile scratch that covers every map of the context's plan
+// Weight-resident form of the 32->32 split convolutions (sconv_split_resident_kernel): bit of Ctx::resident_mask that covers
+// (map kind, output level, gated input), 0 = none — a function of the LAYER only.  bit 0: k=3 of level 1, bit 1: k=2,s=2 into
+// level 1, bit 2: gated k=2,s=2 into level 2
+int sconv_resident_bit(int kind, int level, int cin, int cout, bool gated);
 static constexpr size_t SCONV_SCRATCH_FLOATS = (size_t)2 << 20;   // 8 MB: one packed kernel (27 x 256 x 256 fp32 = 7 MB)
 // conv.hip -------------------------------------------------------------------------------------
 int sconv_naive(const float* in, const int32_t* nbr, const float* W, const float* scale, const float* shift, int relu,

@@ -38,6 +38,16 @@ API int egonn_debug_set_ksplit(egonn_ctx* c, int map_class, int level, int kpart
   return EGONN_OK;
 }
 
+// Weight-resident form of the 32->32 split convolutions (sconv_resident_bit): layers it runs on, -1 = the product rule; workgroups
+// per resident launch, 0 = default
+API int egonn_debug_set_resident(egonn_ctx* c, int mask, int max_workgroups) {
+  EGONN_REQUIRE(c && mask >= -1 && mask <= 7 && max_workgroups >= 0 && max_workgroups <= 65536, EGONN_ERR_INVALID,
+                "debug_set_resident: mask in [-1, 7], max_workgroups in [0, 65536]");
+  c->resident_mask = mask < 0 ? SCONV_RESIDENT_DEFAULT : mask;
+  c->resident_wgs = max_workgroups;
+  return EGONN_OK;
+}
+
 API int egonn_ctx_create(egonn_ctx** out, int device, int coord_bits) {
   EGONN_REQUIRE(out != nullptr, EGONN_ERR_INVALID, "ctx_create: null out pointer");
   EGONN_REQUIRE(coord_bits >= 10 && coord_bits <= 16, EGONN_ERR_INVALID, "coord_bits=%d outside [10,16]", coord_bits);

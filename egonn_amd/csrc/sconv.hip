@@ -1304,6 +1304,14 @@ void sconv_ksplit_rule(const Ctx* ctx, int kind, int level, int* kparts, int* co
   *col_parts = rule.col_parts[l];
   *kw = rule.kw[mc][l];
 }
+// Layers the weight-resident form exists for in the forward (see kernels.h): the 32->32 plan at output levels 1 and 2
+int sconv_resident_bit(int kind, int level, int cin, int cout, bool gated) {
+  if (cin != 32 || cout != 32) return 0;
+  if (kind == 0 && level == 1 && !gated) return 1;
+  if (kind == 1 && level == 1 && !gated) return 2;
+  if (kind == 1 && level == 2 && gated) return 4;
+  return 0;
+}
 size_t sconv_ksplit_scratch_floats(const Ctx* ctx) {
   size_t need = 0;
   for (int kind = 0; kind <= 2; ++kind)
@@ -1365,6 +1373,9 @@ int sconv_map(Ctx* ctx, const ConvCall& c, hipStream_t stream) {
   if (c.in2) { l.kparts = 1; l.kw = 0; }
   if (c.cin < 64) l.kw = 0;
   l.variant = ctx->conv_variant >= 1000 ? ctx->conv_variant - 1000 : 0;
+  l.resident = (ctx->conv_variant == 0 && !ctx->operand_autoscale &&
+                (ctx->resident_mask & sconv_resident_bit(kind, level, c.cin, c.cout, c.in2 != nullptr)) != 0) ? 1 : 0;
+  l.resident_wgs = ctx->resident_wgs;
   l.B = P.batch; l.part = ctx->ks_part; l.part_floats = ctx->ks_part_floats;
   if (ctx->operand_autoscale) {
     l.in_absmax = reinterpret_cast<uint32_t*>(ctx->dev_counts + 24);

@@ -665,6 +665,290 @@ __global__ __launch_bounds__(NW * KW * 64) void sconv_split_kernel(const SplitAr
   }
 }
 
+// ------------------------------------------------------------------ the weight-resident form (CIN = COUT = 32)
+// The 32->32 plans of levels 1-2 gather 2 KB of rows per (group, offset) and, in the lock-step kernel above, 4 KB of W[k] per
+// workgroup and step: the same K * 4 KB (108 KB for k=3, 32 KB for the 8-slot maps) fetched again by every task.  Here a workgroup
+// stages the WHOLE packed kernel into LDS once (LDS-DMA, 1 KB pieces, one wait, one barrier) and then nothing is shared any more:
+//   * every wave owns one row group at a time and walks the set bits of that group's OWN mask in ascending k — no union padding,
+//     no s_barrier and no vmcnt(0) in the offset loop; the waits on the wave's two-slot ring are counted (the DMA of offset j + 2
+//     is requested as soon as offset j's operands are in registers, so two gathers per wave are in flight);
+//   * per offset the six MFMAs run in the lock-step kernel's order (lo*hi, hi*lo, hi*hi; column tile 0 then 1) on the same
+//     accumulators: per output row the same operations in the same order — results are bitwise those of cfg 142;
+//   * the next group's header (mask, table, output rows, gate) is requested while the current group computes and held in registers;
+//   * groups are dealt statically: the XCD slice of the lock-step kernel (block b -> contiguous eighth b % 8 of the task slots, a
+//     grid that is no multiple of 8: one slice), inside it the group slots — RowGroups::order4's longest-first tasks x 4 groups —
+//     round-robin over the slice's waves.  No workgroup waits for another one; a row's result does not depend on the dealing.
+template <int NW, bool GATED>
+struct ResidentGeom {
+  static constexpr int TBL = GATED ? 512 : 2048;         // one group's table (padded); the gated form exists for the 8-slot maps
+  static constexpr int WAVE_LDS = TBL + 2 * 2048 + (GATED ? 2 * 2048 : 0);   // table + two ring slots (+ two of the second operand)
+  static constexpr int lds_bytes(int K) { return K * 4096 + NW * WAVE_LDS; }
+};
+static_assert(ResidentGeom<8, false>::lds_bytes(27) <= 160 * 1024, "resident k=3 workgroup: LDS budget");
+static_assert(ResidentGeom<8, false>::lds_bytes(8) <= 80 * 1024, "resident 8-slot workgroups: two per CU");
+static_assert(ResidentGeom<12, true>::lds_bytes(8) <= 160 * 1024, "resident gated workgroup: LDS budget");
+
+template <int NW, bool GATED>
+__global__ __launch_bounds__(NW * 64) void sconv_split_resident_kernel(const SplitArgs p) {
+  using GEO = ResidentGeom<NW, GATED>;
+  constexpr int CIN = 32, COUT = 32, NOPS = GATED ? 4 : 2;   // NOPS: vector-memory requests of one offset
+  extern __shared__ __attribute__((aligned(1024))) char smem[];
+  typedef __attribute__((address_space(3))) char lds_char;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int l15 = lane & 15, g4 = lane >> 4;
+  const int K = p.K;
+  const float in_sc = p.in_maxbits ? split_scale_of(__builtin_amdgcn_readfirstlane((int)p.in_maxbits[0])) : 1.f;
+  char* const wl = smem + K * 4096 + wave * GEO::WAVE_LDS;
+  int32_t* const tbl = reinterpret_cast<int32_t*>(wl);
+  char* const ring = wl + GEO::TBL;
+  const uint32_t smem_addr = (uint32_t)(uintptr_t)(lds_char*)smem;
+  const uint32_t wl_addr = (uint32_t)(uintptr_t)(lds_char*)wl;
+  const uint32_t rd0 = wl_addr + GEO::TBL + (uint32_t)(l15 * 128 + ((g4 ^ (l15 & 7)) * 16));
+  const uint32_t rd1 = wl_addr + GEO::TBL + (uint32_t)(l15 * 128 + (((4 + g4) ^ (l15 & 7)) * 16));
+  const uint32_t tb0 = wl_addr + (uint32_t)((lane >> 3) * 4);
+  const uint32_t wrd = smem_addr + (uint32_t)(lane * 16);
+  const int dma_chunk = ((lane & 7) ^ (lane >> 3)) * 16;
+  const int w_lane = lane * 16;
+
+  const __amdgpu_buffer_rsrc_t a_rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), (short)(CIN * 4), (int)p.in_rows, 0x00020000);
+  const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.Wsp), 0, (int)p.w_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t a2_rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(GATED ? p.in2 : p.in), (short)(CIN * 4), (int)p.in_rows, 0x00020000);
+
+  const int ngroups = __builtin_amdgcn_readfirstlane(min(p.meta[0], p.cap_groups));
+  const int ntask = (ngroups + 3) >> 2;
+  const int nx = (gridDim.x & 7) ? 1 : 8;
+  const int xcd = (int)blockIdx.x % nx, lb = (int)blockIdx.x / nx, nper = (int)gridDim.x / nx;
+  const int cpx = (ntask + nx - 1) / nx;
+  const int nslot = 4 * cpx, stride = nper * NW;         // group slots of the slice; the slice's waves
+  if (lb * NW >= nslot || xcd * cpx + ((lb * NW) >> 2) >= ntask) return;   // (workgroup-uniform) no group for any wave of it
+
+  // ---- the packed kernel -> LDS, all pieces requested before one wait
+  for (int pc = wave; pc < K * 4; pc += NW)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (lds_char*)(smem + pc * 1024), 16, w_lane, pc * 1024, 0, 0);
+
+  struct Hdr {
+    int4 hv0, hv1;
+    int32_t orow;
+    uint32_t gm;
+    int gw;
+    f32x4 gq0, gq1;
+  };
+  // task of group slot s (looked up one group ahead of its use: nothing waits for it); -1: past the slice
+  auto task_at = [&](int s) {
+    const int tslot = xcd * cpx + (s >> 2);
+    if (s >= nslot || tslot >= ntask) return -1;
+    return p.order ? __builtin_amdgcn_readfirstlane(p.order[tslot]) : tslot;
+  };
+  int task_nx = task_at(lb * NW + wave);
+  // the next group of this wave from slot s on (s: past it), header requested and nothing of it waited for; gw = -1: none left
+  auto fetch = [&](int& s, Hdr& h) {
+    h.gw = -1;
+    h.gm = 0;
+    for (; s < nslot; s += stride) {
+      const int task = task_nx;
+      task_nx = task_at(s + stride);
+      if (task < 0) { s = nslot; break; }
+      const int gw = task * 4 + (s & 3);
+      if (gw >= ngroups) continue;
+      h.gw = gw;
+      h.gm = p.gmask[gw];                                // (bit 31 clear: a padding group, skipped when its turn comes)
+      const int n16 = K * 4;
+      const int4* src = reinterpret_cast<const int4*>(p.snbr + (int64_t)gw * K * 16);
+      h.hv0 = h.hv1 = make_int4(-1, -1, -1, -1);
+      if (lane < n16) h.hv0 = src[lane];
+      if (lane + 64 < n16) h.hv1 = src[lane + 64];
+      h.orow = p.perm[(int64_t)gw * 16 + l15];
+      if constexpr (GATED) {
+        int lo = 0, hi = p.B;                            // scan of the group: last b with meta[1 + b] <= gw
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (p.meta[1 + mid] <= gw) lo = mid; else hi = mid;
+        }
+        h.gq0 = *reinterpret_cast<const f32x4*>(p.gate + (int64_t)lo * CIN + 4 * g4);
+        h.gq1 = *reinterpret_cast<const f32x4*>(p.gate + (int64_t)lo * CIN + 16 + 4 * g4);
+      }
+      s += stride;
+      return;
+    }
+  };
+
+  int s = lb * NW + wave;
+  Hdr cur, nxt;
+  fetch(s, cur);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();                          // the kernel is resident: the only barrier of the workgroup
+
+  auto mfma = [](const f32x4& wf, const f16x8_t& af, f32x4& c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, wf), af, c, 0, 0, 0);
+  };
+  // the group in work: its remaining offsets, output rows, gate, the offsets in ring slots `slot` (kA) and `slot ^ 1` (kB)
+  uint32_t mk = 0;
+  int gw = -1, kA = 27, kB = 27, slot = 0;
+  int32_t orow = -1, i0 = -1, i1 = -1;
+  f32x4 gq0 = {0.f, 0.f, 0.f, 0.f}, gq1 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  {
+    auto next_k = [&]() {                                // 27: past the end
+      const int k = mk ? __builtin_ctz(mk) : 27;
+      mk &= mk - 1;
+      return k;
+    };
+    auto idx_read = [&](int k, int32_t& i0, int32_t& i1) {
+      if (k < 27) {
+        const uint32_t tb = tb0 + (uint32_t)(k * 64);
+        asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:32" : "=&v"(i0), "=&v"(i1) : "v"(tb) : "memory");
+      }
+    };
+    auto issue = [&](int slot, int k, int32_t i0, int32_t i1) {
+      if (k >= 27) return;
+      __builtin_amdgcn_struct_ptr_buffer_load_lds(a_rsrc, (lds_char*)(ring + slot * 2048), 16, i0, dma_chunk, 0, 0, 0);
+      __builtin_amdgcn_struct_ptr_buffer_load_lds(a_rsrc, (lds_char*)(ring + slot * 2048 + 1024), 16, i1, dma_chunk, 0, 0, 0);
+      if constexpr (GATED) {
+        __builtin_amdgcn_struct_ptr_buffer_load_lds(a2_rsrc, (lds_char*)(ring + 4096 + slot * 2048), 16, i0, dma_chunk, 0, 0, 0);
+        __builtin_amdgcn_struct_ptr_buffer_load_lds(a2_rsrc, (lds_char*)(ring + 4096 + slot * 2048 + 1024), 16, i1, dma_chunk, 0, 0, 0);
+      }
+    };
+    // ---- one offset: rows of ring slot x W[k] of the resident image (the lock-step kernel's compute at NS = 1)
+    auto compute = [&](int slot, int k) {
+      f32x4 ra0, ra1, rb0, rb1, w[4];
+      const uint32_t r0 = rd0 + (uint32_t)(slot * 2048), r1 = rd1 + (uint32_t)(slot * 2048);
+      asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3" : "=&v"(ra0), "=&v"(ra1) : "v"(r0), "v"(r1) : "memory");
+      if constexpr (GATED) {
+        const uint32_t q0 = r0 + 4096u, q1 = r1 + 4096u;
+        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3" : "=&v"(rb0), "=&v"(rb1) : "v"(q0), "v"(q1) : "memory");
+      }
+      const uint32_t wa = wrd + (uint32_t)(k * 4096);
+      asm volatile(
+          "ds_read_b128 %0, %4\n\t"
+          "ds_read_b128 %1, %4 offset:1024\n\t"
+          "ds_read_b128 %2, %4 offset:2048\n\t"
+          "ds_read_b128 %3, %4 offset:3072"
+          : "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3])
+          : "v"(wa)
+          : "memory");
+      if constexpr (GATED) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ra0), "+v"(ra1), "+v"(rb0), "+v"(rb1)::"memory");
+      else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ra0), "+v"(ra1)::"memory");
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3])::"memory");
+      f16x8_t ah, al;
+      if constexpr (GATED) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          ra0[u] = fmaxf(ra0[u] * gq0[u] + rb0[u], 0.f);        // eca_apply_kernel's expression
+          ra1[u] = fmaxf(ra1[u] * gq1[u] + rb1[u], 0.f);
+        }
+        split8h(ra0, ra1, ah, al);
+      } else if (p.in_split) { ah = __builtin_bit_cast(f16x8_t, ra0); al = __builtin_bit_cast(f16x8_t, ra1); }   // (uniform branch)
+      else {
+        if (in_sc != 1.f) { ra0 *= in_sc; ra1 *= in_sc; }                                                       // (uniform branch)
+        split8h(ra0, ra1, ah, al);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      mfma(w[2], ah, acc0); mfma(w[3], ah, acc1);        // w lo * a hi
+      mfma(w[0], al, acc0); mfma(w[1], al, acc1);        // w hi * a lo
+      mfma(w[0], ah, acc0); mfma(w[1], ah, acc1);        // hi * hi
+      __builtin_amdgcn_sched_barrier(0);
+    };
+
+    // ---- a group begins: padding groups skipped, its table -> wave-private LDS (the ring is drained: a group's last wait is
+    // vmcnt(0), and its indices have been read), the header after it requested, its first two offsets in flight.  false: none left
+    auto begin = [&]() {
+      while (cur.gw >= 0 && !((uint32_t)__builtin_amdgcn_readfirstlane((int)cur.gm) >> 31)) {
+        fetch(s, nxt);
+        cur = nxt;
+      }
+      if (cur.gw < 0) return false;
+      gw = cur.gw;
+      orow = cur.orow;
+      mk = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur.gm) & 0x07FFFFFFu;
+      if constexpr (GATED) { gq0 = cur.gq0; gq1 = cur.gq1; }
+      {
+        int4* dst = reinterpret_cast<int4*>(tbl);
+        if (lane < K * 4) dst[lane] = cur.hv0;
+        if (lane + 64 < K * 4) dst[lane + 64] = cur.hv1;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      fetch(s, nxt);                                     // (older than every gather of this group)
+      kA = next_k();
+      kB = next_k();
+      slot = 0;
+      idx_read(kA, i0, i1);
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(i0), "+v"(i1)::"memory");
+      issue(0, kA, i0, i1);
+      idx_read(kB, i0, i1);
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(i0), "+v"(i1)::"memory");
+      issue(1, kB, i0, i1);
+      return true;
+    };
+
+    bool have = begin();
+    while (have) {
+      const int e_gw = gw;
+      const int32_t e_orow = orow;
+      acc0 = acc1 = (f32x4){0.f, 0.f, 0.f, 0.f};
+      // ---- offsets: wait for offset j, compute it, request offset j + 2 into its slot.  Counted waits: what may still be in
+      // flight is offset j + 1 (NOPS requests).  (The previous group's epilogue — issued behind this group's first two gathers —
+      // may be younger still: the count then waits for a little more than it needs, never for less; loads and stores of one
+      // wave retire in order.)
+      while (kA < 27) {
+        const int kC = next_k();
+        idx_read(kC, i0, i1);                            // (awaited by the operand wait of compute)
+        if (kB < 27) {
+          if constexpr (GATED) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+          else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        } else {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        static_assert(NOPS == (GATED ? 4 : 2), "the counted waits above");
+        __builtin_amdgcn_sched_barrier(0);
+        compute(slot, kA);
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(i0), "+v"(i1)::"memory");
+        issue(slot, kC, i0, i1);                         // (the slot's operands are in registers)
+        __builtin_amdgcn_sched_barrier(0);
+        kA = kB; kB = kC; slot ^= 1;
+      }
+      // ---- the next group's first gathers go out in front of this group's epilogue (its loads and stores run under them)
+      const f32x4 e0 = acc0, e1 = acc1;
+      cur = nxt;
+      have = begin();
+      split_epilogue<COUT>(p, e0, e1, 0, e_orow, e_gw, l15, g4);
+    }
+  }
+}
+
+template <int NW, bool GATED>
+static int launch_split_resident(const SplitArgs& a, int64_t groups_hint, int max_workgroups, hipStream_t stream) {
+  using GEO = ResidentGeom<NW, GATED>;
+  const int lds = GEO::lds_bytes(a.K);
+  EGONN_REQUIRE(lds <= 160 * 1024 && a.K * 64 <= GEO::TBL, EGONN_ERR_INVALID, "sconv(split, resident): K = %d, %d bytes of LDS", a.K, lds);
+  static AttrOnce attr_done;
+  if (attr_done.need()) {
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sconv_split_resident_kernel<NW, GATED>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_done.mark();
+  }
+  // one workgroup lifetime per CU slot (256 CUs; a k=3 workgroup fills a CU's LDS, two 8-slot workgroups share one), clipped to
+  // what the capacity can feed; max_workgroups > 0: measurement / test override (any count; no multiple of 8 = one slice)
+  int64_t gridx = (a.K > 8 || GATED) ? 256 : 512;
+  gridx = std::min<int64_t>(gridx, (std::max<int64_t>(cdiv(groups_hint, NW), 8) + 7) / 8 * 8);
+  if (max_workgroups > 0) gridx = std::min<int64_t>(max_workgroups, 1 << 16);
+  const dim3 grid((unsigned)gridx);
+  hipEvent_t* pev = prof_kernel_events();
+  if (pev[0]) {
+    hipExtLaunchKernelGGL((sconv_split_resident_kernel<NW, GATED>), grid, dim3(NW * 64), lds, stream, pev[0], pev[1], 0, a);
+    pev[0] = pev[1] = nullptr;
+  } else {
+    hipLaunchKernelGGL((sconv_split_resident_kernel<NW, GATED>), grid, dim3(NW * 64), lds, stream, a);
+  }
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}
+
 template <int COUT>
 static int launch_split_reduce(const SplitArgs& a, int64_t groups_hint, hipStream_t stream, hipEvent_t ev_stop) {
   const dim3 grid((unsigned)groups_hint);
@@ -711,7 +995,8 @@ bool sconv_split_supported(int cin, int cout) {
   return false;
 }
 
-// cfg = 100 + NW * 10 + 2 [+ 400 * (1 + log2(column parts))]; 0 = product choice (142: workgroups of 4 waves, automatic parts)
+// cfg = 100 + NW * 10 + 2 [+ 400 * (1 + log2(column parts))]; 0 = product choice (142: workgroups of 4 waves, automatic parts);
+// 100 + NW * 10 + 3 = 183: the weight-resident form (32->32 only)
 int sconv_split_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream) {
   const RowGroups& rg = *l.rg;
   const int cin = c.cin, cout = c.cout, kw = l.kw;
@@ -762,12 +1047,22 @@ int sconv_split_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t str
   }                                                      //  with 1 / 2 / 4 parts, 64->128 56 / 45 / 51, L3 64->64 43 / 41; round 5, fp16 kernels:
                                                          //  4 parts change neither the layers (profiles/r05g_parts4.txt) nor scans/s)
   const int nsw = ns_tot / parts;
+  // 183: the weight-resident form (workgroups of 8 waves; 32->32 only) — the layer's rule (l.resident) or the explicit cfg
+  const bool resident = !trace && (shape == 183 || (l.resident && cfg == 142));
+  if (resident)
+    EGONN_REQUIRE(cin == 32 && cout == 32 && a.kp_n == 1 && kw <= 1 && (rg.K == 27 || rg.K == 8), EGONN_ERR_INVALID,
+                  "sconv(split): the weight-resident form exists for the unsplit 32->32 plan only (%d->%d, K %d)", cin, cout, rg.K);
   if (c.in2) {
-    EGONN_REQUIRE(cin == 32 && cout == 32 && c.gate && l.B >= 1 && !a.in_split && cfg == 142, EGONN_ERR_INVALID,
+    EGONN_REQUIRE(cin == 32 && cout == 32 && c.gate && l.B >= 1 && !a.in_split && (cfg == 142 || resident), EGONN_ERR_INVALID,
                   "sconv(split): the gated input exists for the 32->32 plan only");
     a.in2 = c.in2; a.gate = c.gate; a.B = l.B;
+    if (resident) {
+      EGONN_REQUIRE(rg.K == 8, EGONN_ERR_INVALID, "sconv(split): the gated resident form exists for the 8-slot maps");
+      return launch_split_resident<12, true>(a, groups_hint, l.resident_wgs, stream);
+    }
     return launch_split<32, 32, 4, 1, false, true>(a, groups_hint, stream);
   }
+  if (resident) return launch_split_resident<8, false>(a, groups_hint, l.resident_wgs, stream);
 #define EGONN_SP_KW(CI, CO, NWW, NSWW, KWW)                                                               \
   if constexpr (SplitGeom<NSWW, NWW, false, KWW>::LDS_BYTES <= 160 * 1024) {                              \
     if (kw == KWW && a.kp_n > 1) return launch_split<CI, CO, NWW, NSWW, false, false, true, KWW>(a, groups_hint, stream);  \

@@ -59,6 +59,13 @@ int egonn_debug_set_naive_conv(egonn_ctx* ctx, int on);
  * row's offsets in a fixed partition and order: results are deterministic and batch-invariant under each, and differ between
  * settings by summation order only (<= 3e-6 of the largest output; tests/test_gpu_ksplit.py). */
 int egonn_debug_set_ksplit(egonn_ctx* ctx, int map_class, int level, int kparts, int kw, int col_parts);
+/* tests / measurements only: which 32->32 fp16-split convolutions of this context run on the weight-resident form of the split
+ * kernel (the whole packed kernel staged into LDS once per workgroup, no barrier in the offset loop).  mask bit 0 = the k=3
+ * convolutions of level 1, bit 1 = the k=2,s=2 convolution into level 1, bit 2 = the gated k=2,s=2 convolution into level 2;
+ * -1 = the product rule.  max_workgroups: workgroups per resident launch, 0 = default (also applies to the explicit
+ * configuration egonn_debug_set_naive_conv(ctx, 1183)).  Every setting computes bitwise the same results
+ * (tests/test_gpu_resident_conv.py). */
+int egonn_debug_set_resident(egonn_ctx* ctx, int mask, int max_workgroups);
 /* tests only: on = 1 makes egonn_forward materialise the block output of every level, so that egonn_forward_level_features(ctx, 1, ...)
  * has a map to return (by default level 1's block tail of fp32 maps is evaluated inside level 2's strided convolution and its
  * 23 MB output never exists; bitwise the same results either way) */
