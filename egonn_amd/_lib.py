@@ -134,6 +134,11 @@ _SIGS = [
     ("egonn_icp_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
     ("egonn_icp_pairs", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int, _P, C.c_double, C.c_int, C.c_double, C.c_double,
                                   _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("egonn_estimate_normals_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_estimate_normals", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("egonn_icp_plane_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
+    ("egonn_icp_plane_pairs", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int, _P, C.c_double, C.c_int, C.c_double,
+                                        C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     ("egonn_augment_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
     ("egonn_augment_points", C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     ("egonn_scan_context", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _P]),

@@ -31,6 +31,11 @@
 // schedule are fixed, there are no floating-point atomics: a pair's result has the same bits alone, in any batch and at any
 // batch position.  The launch sequence is fixed by max_iteration; a stopped pair sets a flag and its later workgroups
 // return at once: no host synchronisation, capturable.
+//
+// Point-to-plane (icp(..., point2plane=True) of the reference) is the same loop with another estimator, a template parameter of
+// the search and finish kernels: surface normals of the target by an exact k-nearest-neighbour search on the same grid
+// (nrm_knn_kernel, further down), 29 partials per workgroup (A = sum J J^T, b = sum J r) and a 6 x 6 LDL^T solve per round
+// (icp_plane_step).  The point-to-point instantiation is the code above, operation for operation.
 #include "../../include/egonn_hip.h"
 #include "common.h"
 
@@ -40,7 +45,10 @@ namespace egonn {
 
 static constexpr int ICP_WG = 256;
 static constexpr int ICP_NPART = 17;              // n_corr, sum d2, sum p (3), sum q (3), sum p q^T (9)
-static constexpr int DS_BITS = 21;                // voxel index bits per axis
+static constexpr int ICP_NPART_PLANE = 29;        // n_corr, sum d2, sum J J^T (21 upper entries), sum J r (6)
+static constexpr int NRM_KNN_MIN = 3, NRM_KNN_MAX = 32;
+static constexpr double NRM_CELL = 0.5;           // start radius and cell edge of the normals' grid: 5 voxels of the 0.1 m downsample
+static constexpr int DS_BITS = 21;               // voxel index bits per axis
 static constexpr int ICP_CELL_MAX = 65535;        // cell index bits per axis: 16
 static constexpr uint64_t DS_INVALID = ~0ull;     // key of a dropped / out-of-cloud point (valid keys have bit 63 clear)
 
@@ -394,88 +402,78 @@ __global__ __launch_bounds__(ICP_WG) void icp_gather_kernel(const double* __rest
   if (out_keys) out_keys[i] = keys[i];
 }
 
-__global__ __launch_bounds__(ICP_WG) void icp_search_kernel(const IcpPair* __restrict__ pairs, const int32_t* __restrict__ wg0, int P,
-                                                            const double* __restrict__ sq, const int32_t* __restrict__ si,
-                                                            const double* __restrict__ tq, const int32_t* __restrict__ tj,
-                                                            const uint64_t* __restrict__ tkey, double max_dist,
-                                                            double* __restrict__ partial, int32_t* __restrict__ corr) {
+struct IcpRange { int lo[3], hi[3]; };      // a clamped range of target cells, inclusive; hi < lo on an axis = empty
+
+// pair (or cloud) of workgroup `flat` of the flat search grid: the largest p with wg0[p] <= flat
+__device__ static inline int icp_pair_of(const int32_t* __restrict__ wg0, int P, int flat) {
+  int lo = 0, hi = P - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (wg0[mid] <= flat) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// bounding box of the workgroup's points (lanes with !valid have none): per-wave minima / maxima into s_box; a barrier follows
+__device__ static inline void icp_wave_box(double (*s_box)[4], bool valid, double px, double py, double pz) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  double b[6] = {valid ? px : INFINITY, valid ? py : INFINITY, valid ? pz : INFINITY,
+                 valid ? px : -INFINITY, valid ? py : -INFINITY, valid ? pz : -INFINITY};
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      b[k] = fmin(b[k], __shfl_xor(b[k], o, 64));
+      b[3 + k] = fmax(b[3 + k], __shfl_xor(b[3 + k], o, 64));
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s_box[k][w] = b[k];
+  }
+}
+
+// the cells of pair q that the box of s_box, padded by `reach`, touches.  The pad is the reach and a little more: the roundings
+// of the box, of the cell function and of d2 are ~1e-14 m
+__device__ static inline IcpRange icp_cell_range(const IcpPair* __restrict__ q, const double (*s_box)[4], double reach) {
+  IcpRange rg;
+  const double pad = reach * (1.0 + 0x1p-20) + 0x1p-20;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double lo = fmin(fmin(s_box[k][0], s_box[k][1]), fmin(s_box[k][2], s_box[k][3]));
+    const double hi = fmax(fmax(s_box[3 + k][0], s_box[3 + k][1]), fmax(s_box[3 + k][2], s_box[3 + k][3]));
+    const double flo = floor((lo - pad - q->org[k]) / q->h), fhi = floor((hi + pad - q->org[k]) / q->h);
+    // a box wholly outside the grid gets an empty range: its cells hold nothing
+    rg.lo[k] = flo > (double)(q->dim[k] - 1) ? q->dim[k] : icp_cell(flo, q->dim[k]);
+    rg.hi[k] = fhi < 0.0 ? -1 : icp_cell(fhi, q->dim[k]);
+    if (!(lo <= hi)) rg.lo[k] = 0, rg.hi[k] = -1;         // no finite point
+  }
+  return rg;
+}
+
+// Streams the target points of the cell range rg through LDS in tiles of 256 points and hands every one of them, in the
+// order of the sorted cell keys, to visit(qx, qy, qz, j) of every lane with `take`.  Per (x, y) column of the range the run
+// of target points is found by binary search in the sorted cell keys (a column's z range is one contiguous run).  Every
+// barrier is workgroup-uniform: rg must be.  keys / nt: the sorted cell keys of the pair's target; to: its first point in
+// tq / tj.
+template <class Visit>
+__device__ __forceinline__ void icp_stream_cells(const uint64_t* __restrict__ keys, int nt, const double* __restrict__ tq,
+                                                 const int32_t* __restrict__ tj, int64_t to, const IcpRange& rg, bool take,
+                                                 Visit&& visit) {
   __shared__ double s_q[3][ICP_WG];
   __shared__ int s_j[ICP_WG];
   __shared__ int s_start[ICP_WG], s_pre[ICP_WG + 1];
-  __shared__ double s_red[ICP_NPART][4];
-  __shared__ double s_box[6][4];
   __shared__ int s_wsum[4];
-  const int flat = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  // pair of this workgroup: the largest p with wg0[p] <= flat
-  int p = 0;
-  {
-    int lo = 0, hi = P - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (wg0[mid] <= flat) lo = mid; else hi = mid - 1;
-    }
-    p = lo;
-  }
-  const IcpPair* q = pairs + p;
-  const int chunk = flat - wg0[p];
-  const int ns = q->ns, nt = q->nt;
-  if (q->done || chunk < 0 || (int64_t)chunk * ICP_WG >= ns) return;          // workgroup-uniform
-  const int row = chunk * ICP_WG + t;
-  const bool valid = row < ns;
-  const int64_t so = q->so, to = q->to;
-  double px = 0.0, py = 0.0, pz = 0.0;
-  if (valid) {
-    const double x = sq[(so + row) * 3], y = sq[(so + row) * 3 + 1], z = sq[(so + row) * 3 + 2];
-    px = q->R[0] * x + q->R[1] * y + q->R[2] * z + q->t[0];
-    py = q->R[3] * x + q->R[4] * y + q->R[5] * z + q->t[1];
-    pz = q->R[6] * x + q->R[7] * y + q->R[8] * z + q->t[2];
-  }
-  // bounding box of the workgroup's transformed points
-  {
-    double b[6] = {valid ? px : INFINITY, valid ? py : INFINITY, valid ? pz : INFINITY,
-                   valid ? px : -INFINITY, valid ? py : -INFINITY, valid ? pz : -INFINITY};
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        b[k] = fmin(b[k], __shfl_xor(b[k], o, 64));
-        b[3 + k] = fmax(b[3 + k], __shfl_xor(b[3 + k], o, 64));
-      }
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) s_box[k][w] = b[k];
-    }
-  }
-  __syncthreads();
-  int clo[3], chi[3];
-  {
-    // the pad is max_dist and a little more: the roundings of the box, of the cell function and of d2 are ~1e-14 m
-    const double pad = max_dist * (1.0 + 0x1p-20) + 0x1p-20;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double lo = fmin(fmin(s_box[k][0], s_box[k][1]), fmin(s_box[k][2], s_box[k][3]));
-      const double hi = fmax(fmax(s_box[3 + k][0], s_box[3 + k][1]), fmax(s_box[3 + k][2], s_box[3 + k][3]));
-      const double flo = floor((lo - pad - q->org[k]) / q->h), fhi = floor((hi + pad - q->org[k]) / q->h);
-      // a box wholly outside the grid gets an empty range: its cells hold nothing
-      clo[k] = flo > (double)(q->dim[k] - 1) ? q->dim[k] : icp_cell(flo, q->dim[k]);
-      chi[k] = fhi < 0.0 ? -1 : icp_cell(fhi, q->dim[k]);
-      if (!(lo <= hi)) clo[k] = 0, chi[k] = -1;         // no finite point
-    }
-  }
-  const double md2 = max_dist * max_dist;
-  double best = INFINITY, bqx = 0.0, bqy = 0.0, bqz = 0.0;
-  int bj = -1;
-  const int ny = chi[1] - clo[1] + 1, nx = chi[0] - clo[0] + 1;
-  const int64_t ncol = (nx > 0 && ny > 0 && chi[2] >= clo[2]) ? (int64_t)nx * ny : 0;
-  const uint64_t* keys = tkey + to;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int ny = rg.hi[1] - rg.lo[1] + 1, nx = rg.hi[0] - rg.lo[0] + 1;
+  const int64_t ncol = (nx > 0 && ny > 0 && rg.hi[2] >= rg.lo[2]) ? (int64_t)nx * ny : 0;
   for (int64_t c0 = 0; c0 < ncol; c0 += ICP_WG) {
     // runs of target points of up to 256 (x, y) columns of the cell range: one contiguous run per column
     const int64_t c = c0 + t;
     int start = 0, len = 0;
     if (c < ncol) {
-      const uint64_t x = (uint64_t)(clo[0] + (int)(c / ny)), y = (uint64_t)(clo[1] + (int)(c % ny));
-      const uint64_t k0 = (x << 32) | (y << 16) | (uint64_t)clo[2], k1 = (x << 32) | (y << 16) | (uint64_t)chi[2];
+      const uint64_t x = (uint64_t)(rg.lo[0] + (int)(c / ny)), y = (uint64_t)(rg.lo[1] + (int)(c % ny));
+      const uint64_t k0 = (x << 32) | (y << 16) | (uint64_t)rg.lo[2], k1 = (x << 32) | (y << 16) | (uint64_t)rg.hi[2];
       start = icp_lower_bound(keys, 0, nt, k0);
       len = icp_lower_bound(keys, start, nt, k1 + 1) - start;
     }
@@ -510,42 +508,100 @@ __global__ __launch_bounds__(ICP_WG) void icp_search_kernel(const IcpPair* __res
       }
       __syncthreads();
       const int cnt = min(ICP_WG, total - e0);
-      if (valid) {
-        for (int k = 0; k < cnt; ++k) {                // every lane reads the same address: LDS broadcast
-          const double qx = s_q[0][k], qy = s_q[1][k], qz = s_q[2][k];
-          const double dx = px - qx, dy = py - qy, dz = pz - qz;
-          const double d2 = dx * dx + dy * dy + dz * dz;
-          const int j = s_j[k];
-          if (d2 < best || (d2 == best && j < bj)) best = d2, bj = j, bqx = qx, bqy = qy, bqz = qz;
-        }
+      if (take) {
+        for (int k = 0; k < cnt; ++k) visit(s_q[0][k], s_q[1][k], s_q[2][k], s_j[k]);      // one address for all lanes: LDS broadcast
       }
       __syncthreads();
     }
   }
+}
+
+// EST 0: point-to-point, 17 partials (n_corr, sum d2, sum p, sum q, sum p q^T).  EST 1: point-to-plane, 29 partials (n_corr,
+// sum d2, the 21 upper entries of sum J J^T row by row, the 6 of sum J r) with r = (p - q) . n, J = [p x n, n], n = the normal
+// of the final nearest target, fetched once after the tile loop.
+template <int EST>
+__global__ __launch_bounds__(ICP_WG) void icp_search_kernel(const IcpPair* __restrict__ pairs, const int32_t* __restrict__ wg0, int P,
+                                                            const double* __restrict__ sq, const int32_t* __restrict__ si,
+                                                            const double* __restrict__ tq, const int32_t* __restrict__ tj,
+                                                            const uint64_t* __restrict__ tkey, const double* __restrict__ tnrm,
+                                                            double max_dist, double* __restrict__ partial,
+                                                            int32_t* __restrict__ corr) {
+  constexpr int NP = EST ? ICP_NPART_PLANE : ICP_NPART;
+  __shared__ double s_red[NP][4];
+  __shared__ double s_box[6][4];
+  const int flat = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int p = icp_pair_of(wg0, P, flat);
+  const IcpPair* q = pairs + p;
+  const int chunk = flat - wg0[p];
+  const int ns = q->ns, nt = q->nt;
+  if (q->done || chunk < 0 || (int64_t)chunk * ICP_WG >= ns) return;          // workgroup-uniform
+  const int row = chunk * ICP_WG + t;
+  const bool valid = row < ns;
+  const int64_t so = q->so, to = q->to;
+  double px = 0.0, py = 0.0, pz = 0.0;
+  if (valid) {
+    const double x = sq[(so + row) * 3], y = sq[(so + row) * 3 + 1], z = sq[(so + row) * 3 + 2];
+    px = q->R[0] * x + q->R[1] * y + q->R[2] * z + q->t[0];
+    py = q->R[3] * x + q->R[4] * y + q->R[5] * z + q->t[1];
+    pz = q->R[6] * x + q->R[7] * y + q->R[8] * z + q->t[2];
+  }
+  icp_wave_box(s_box, valid, px, py, pz);              // of the workgroup's transformed points
+  __syncthreads();
+  const IcpRange rg = icp_cell_range(q, s_box, max_dist);
+  const double md2 = max_dist * max_dist;
+  double best = INFINITY, bqx = 0.0, bqy = 0.0, bqz = 0.0;
+  int bj = -1;
+  icp_stream_cells(tkey + to, nt, tq, tj, to, rg, valid, [&](double qx, double qy, double qz, int j) {
+    const double dx = px - qx, dy = py - qy, dz = pz - qz;
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    if (d2 < best || (d2 == best && j < bj)) best = d2, bj = j, bqx = qx, bqy = qy, bqz = qz;
+  });
   const bool is_corr = valid && bj >= 0 && best < md2;
   if (corr && valid) {
     const int32_t orig = si[so + row];
     if (orig >= 0 && orig < ns) corr[so + orig] = is_corr ? bj : -1;
   }
-  double v[ICP_NPART];
+  double v[NP];
   v[0] = is_corr ? 1.0 : 0.0;
   v[1] = is_corr ? best : 0.0;
-  const double a[3] = {is_corr ? px : 0.0, is_corr ? py : 0.0, is_corr ? pz : 0.0};
-  const double b[3] = {is_corr ? bqx : 0.0, is_corr ? bqy : 0.0, is_corr ? bqz : 0.0};
+  if constexpr (EST == 0) {
+    const double a[3] = {is_corr ? px : 0.0, is_corr ? py : 0.0, is_corr ? pz : 0.0};
+    const double b[3] = {is_corr ? bqx : 0.0, is_corr ? bqy : 0.0, is_corr ? bqz : 0.0};
 #pragma unroll
-  for (int k = 0; k < 3; ++k) v[2 + k] = a[k], v[5 + k] = b[k];
+    for (int k = 0; k < 3; ++k) v[2 + k] = a[k], v[5 + k] = b[k];
 #pragma unroll
-  for (int r = 0; r < 3; ++r)
+    for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[8 + r * 3 + c] = a[r] * b[c];
+      for (int c = 0; c < 3; ++c) v[8 + r * 3 + c] = a[r] * b[c];
+  } else {
+    double nx = 0.0, ny = 0.0, nz = 0.0;
+    if (is_corr) {                                       // bj is an index inside the pair's target (icp_gather_kernel)
+      const int64_t j = to + (bj < nt ? bj : nt - 1);
+      nx = tnrm[j * 3], ny = tnrm[j * 3 + 1], nz = tnrm[j * 3 + 2];
+    }
+    const double dx = px - bqx, dy = py - bqy, dz = pz - bqz;
+    const double r = is_corr ? (dx * nx + dy * ny) + dz * nz : 0.0;
+    double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+    if (!is_corr) {
 #pragma unroll
-  for (int k = 0; k < ICP_NPART; ++k) {
+      for (int k = 0; k < 6; ++k) J[k] = 0.0;
+    }
+    int e = 2;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = a; b < 6; ++b) v[e++] = J[a] * J[b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) v[23 + a] = J[a] * r;
+  }
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);      // a fixed tree
     if (lane == 0) s_red[k][w] = v[k];
   }
   __syncthreads();
-  if (t < ICP_NPART) partial[(size_t)flat * ICP_NPART + t] = ((s_red[t][0] + s_red[t][1]) + s_red[t][2]) + s_red[t][3];
+  if (t < NP) partial[(size_t)flat * NP + t] = ((s_red[t][0] + s_red[t][1]) + s_red[t][2]) + s_red[t][3];
 }
 
 // largest eigenvector of the symmetric 4 x 4 matrix A (cyclic Jacobi, fixed schedule): the unit quaternion (w, x, y, z)
@@ -611,20 +667,78 @@ __device__ static void icp_top_eigenvector(double A[4][4], double* qv) {
   for (int k = 0; k < 4; ++k) qv[k] *= nrm;
 }
 
+// Point-to-plane step: solves A x = -b (A = sum J J^T from its 21 upper entries row by row, b = sum J r) by LDL^T without
+// pivoting and returns U = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)] as (U[9], ut[3]).  False, with nothing to rely on in U, when
+// a pivot d_i is not > 2^-40 A_ii (A's own diagonal: fp64 leaves ~2^-52 relative rounding in a pivot, twelve bits above that
+// separate a rank-deficient scene from rounding noise) or x is not finite.
+__device__ static bool icp_plane_step(const double* __restrict__ s, double* U, double* ut) {
+  double A[6][6], L[6][6], d[6], x[6];
+  {
+    int e = 2;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = a; b < 6; ++b) A[a][b] = A[b][a] = s[e++];
+  }
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double dj = A[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) dj -= (L[j][k] * L[j][k]) * d[k];
+    ok = ok && dj > 0x1p-40 * A[j][j];                  // false for NaN as well
+    d[j] = ok ? dj : 1.0;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double l = A[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) l -= (L[i][k] * L[j][k]) * d[k];
+      L[i][j] = l / d[j];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {                          // L y = -b
+    double y = -s[23 + i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) y -= L[i][k] * x[k];
+    x[i] = y;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) x[i] = x[i] / d[i];
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {                         // L^T x = z
+    double y = x[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) y -= L[k][i] * x[k];
+    x[i] = y;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) ok = ok && fabs(x[i]) < INFINITY;
+  const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sc = sin(x[2]), cc = cos(x[2]);
+  U[0] = cb * cc, U[1] = (sa * sb) * cc - ca * sc, U[2] = (ca * sb) * cc + sa * sc;
+  U[3] = cb * sc, U[4] = (sa * sb) * sc + ca * cc, U[5] = (ca * sb) * sc - sa * cc;
+  U[6] = -sb, U[7] = sa * cb, U[8] = ca * cb;
+  ut[0] = x[3], ut[1] = x[4], ut[2] = x[5];
+  return ok;
+}
+
+// EST as in icp_search_kernel.  One loop, two estimators: the evaluation, the stop rule and the traces are the same code.
+template <int EST>
 __global__ __launch_bounds__(64) void icp_finish_kernel(IcpPair* __restrict__ pairs, const int32_t* __restrict__ wg0,
                                                         const double* __restrict__ partial, int round, int max_it, double eps_fit,
                                                         double eps_rmse, double* __restrict__ T_out, double* __restrict__ fitness,
                                                         double* __restrict__ rmse, int32_t* __restrict__ iterations,
                                                         int32_t* __restrict__ status, double* __restrict__ T_trace,
                                                         double* __restrict__ eval_trace) {
-  __shared__ double s[ICP_NPART];
+  constexpr int NP = EST ? ICP_NPART_PLANE : ICP_NPART;
+  __shared__ double s[NP];
   const int p = blockIdx.x, t = threadIdx.x;
   IcpPair* q = pairs + p;
   if (q->done) return;
   const int nwg = (q->ns + ICP_WG - 1) / ICP_WG, first = wg0[p];
-  if (t < ICP_NPART) {
+  if (t < NP) {
     double acc = 0.0;
-    for (int c = 0; c < nwg; ++c) acc += partial[(size_t)(first + c) * ICP_NPART + t];     // ascending workgroups
+    for (int c = 0; c < nwg; ++c) acc += partial[(size_t)(first + c) * NP + t];     // ascending workgroups
     s[t] = acc;
   }
   __syncthreads();
@@ -632,9 +746,13 @@ __global__ __launch_bounds__(64) void icp_finish_kernel(IcpPair* __restrict__ pa
   const double n = s[0];
   const double fit = n / (double)q->ns, e_rmse = n > 0.0 ? sqrt(s[1] / n) : 0.0;
   int stop = 0, st = q->status;
+  double U[9], ut[3];
   if (round >= 1 && fabs(fit - q->prev_fit) < eps_fit && fabs(e_rmse - q->prev_rmse) < eps_rmse) stop = 1;
   else if (round >= max_it) stop = 1, st |= EGONN_ICP_STATUS_MAX_ITER;
-  else if (n < 3.0) stop = 1, st |= EGONN_ICP_STATUS_FEW_CORR;
+  else if (n < (EST ? 6.0 : 3.0)) stop = 1, st |= EGONN_ICP_STATUS_FEW_CORR;
+  else if constexpr (EST == 1) {
+    if (!icp_plane_step(s, U, ut)) stop = 1, st |= EGONN_ICP_STATUS_SINGULAR;
+  }
   if (eval_trace) {
     double* e = eval_trace + ((size_t)p * (max_it + 1) + round) * 3;
     e[0] = n, e[1] = s[1], e[2] = (double)stop;
@@ -648,31 +766,32 @@ __global__ __launch_bounds__(64) void icp_finish_kernel(IcpPair* __restrict__ pa
     q->done = 1;
     return;
   }
-  // Horn: S = sum (p - pm)(q - qm)^T, the 4 x 4 matrix N, its largest eigenvector
-  double pm[3], qm[3], S[3][3];
-  for (int k = 0; k < 3; ++k) pm[k] = s[2 + k] / n, qm[k] = s[5 + k] / n;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) S[r][c] = s[8 + r * 3 + c] - n * pm[r] * qm[c];
-  double N[4][4];
-  N[0][0] = S[0][0] + S[1][1] + S[2][2];
-  N[1][1] = S[0][0] - S[1][1] - S[2][2];
-  N[2][2] = -S[0][0] + S[1][1] - S[2][2];
-  N[3][3] = -S[0][0] - S[1][1] + S[2][2];
-  N[0][1] = N[1][0] = S[1][2] - S[2][1];
-  N[0][2] = N[2][0] = S[2][0] - S[0][2];
-  N[0][3] = N[3][0] = S[0][1] - S[1][0];
-  N[1][2] = N[2][1] = S[0][1] + S[1][0];
-  N[1][3] = N[3][1] = S[2][0] + S[0][2];
-  N[2][3] = N[3][2] = S[1][2] + S[2][1];
-  double qv[4];
-  icp_top_eigenvector(N, qv);
-  const double qw = qv[0], qx = qv[1], qy = qv[2], qz = qv[3];
-  double U[9];
-  U[0] = 1.0 - 2.0 * (qy * qy + qz * qz), U[1] = 2.0 * (qx * qy - qw * qz), U[2] = 2.0 * (qx * qz + qw * qy);
-  U[3] = 2.0 * (qx * qy + qw * qz), U[4] = 1.0 - 2.0 * (qx * qx + qz * qz), U[5] = 2.0 * (qy * qz - qw * qx);
-  U[6] = 2.0 * (qx * qz - qw * qy), U[7] = 2.0 * (qy * qz + qw * qx), U[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
-  double ut[3], Rn[9], tn[3];
-  for (int r = 0; r < 3; ++r) ut[r] = qm[r] - (U[r * 3] * pm[0] + U[r * 3 + 1] * pm[1] + U[r * 3 + 2] * pm[2]);
+  if constexpr (EST == 0) {
+    // Horn: S = sum (p - pm)(q - qm)^T, the 4 x 4 matrix N, its largest eigenvector
+    double pm[3], qm[3], S[3][3];
+    for (int k = 0; k < 3; ++k) pm[k] = s[2 + k] / n, qm[k] = s[5 + k] / n;
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) S[r][c] = s[8 + r * 3 + c] - n * pm[r] * qm[c];
+    double N[4][4];
+    N[0][0] = S[0][0] + S[1][1] + S[2][2];
+    N[1][1] = S[0][0] - S[1][1] - S[2][2];
+    N[2][2] = -S[0][0] + S[1][1] - S[2][2];
+    N[3][3] = -S[0][0] - S[1][1] + S[2][2];
+    N[0][1] = N[1][0] = S[1][2] - S[2][1];
+    N[0][2] = N[2][0] = S[2][0] - S[0][2];
+    N[0][3] = N[3][0] = S[0][1] - S[1][0];
+    N[1][2] = N[2][1] = S[0][1] + S[1][0];
+    N[1][3] = N[3][1] = S[2][0] + S[0][2];
+    N[2][3] = N[3][2] = S[1][2] + S[2][1];
+    double qv[4];
+    icp_top_eigenvector(N, qv);
+    const double qw = qv[0], qx = qv[1], qy = qv[2], qz = qv[3];
+    U[0] = 1.0 - 2.0 * (qy * qy + qz * qz), U[1] = 2.0 * (qx * qy - qw * qz), U[2] = 2.0 * (qx * qz + qw * qy);
+    U[3] = 2.0 * (qx * qy + qw * qz), U[4] = 1.0 - 2.0 * (qx * qx + qz * qz), U[5] = 2.0 * (qy * qz - qw * qx);
+    U[6] = 2.0 * (qx * qz - qw * qy), U[7] = 2.0 * (qy * qz + qw * qx), U[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
+    for (int r = 0; r < 3; ++r) ut[r] = qm[r] - (U[r * 3] * pm[0] + U[r * 3 + 1] * pm[1] + U[r * 3 + 2] * pm[2]);
+  }
+  double Rn[9], tn[3];
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) Rn[r * 3 + c] = U[r * 3] * q->R[c] + U[r * 3 + 1] * q->R[3 + c] + U[r * 3 + 2] * q->R[6 + c];
     tn[r] = U[r * 3] * q->t[0] + U[r * 3 + 1] * q->t[1] + U[r * 3 + 2] * q->t[2] + ut[r];
@@ -687,12 +806,246 @@ __global__ __launch_bounds__(64) void icp_finish_kernel(IcpPair* __restrict__ pa
   }
 }
 
+// ------------------------------------------------------------------ surface normals: exact k nearest neighbours, PCA
+// Open3D's estimate_normals(KDTreeSearchParamKNN(knn)) [recall], restated (DESIGN.md "Point-to-plane ICP"):
+//   neighbours   all points of the same cloud, the query itself included, by (d2, index) ascending with
+//                d2 = (dx*dx + dy*dy) + dz*dz; the first m = min(knn, cloud size).
+//   covariance   mean = (sum q) / m, C = sum (q - mean)(q - mean)^T / m, both summed in neighbour order.
+//   normal       unit eigenvector of C's smallest eigenvalue (cyclic Jacobi, fixed schedule), flipped so that n . p <= 0
+//                (toward the sensor at the origin); with n . p == 0 its first non-zero component is positive.
+//                m < 3, a largest eigenvalue that is not > 0 or a non-finite value: (0, 0, 1).
+// The grid is the ICP's with target = the cloud itself (icp_setup_kernel with T = identity, icp_key_kernel, the sorts,
+// icp_gather_kernel).  A workgroup owns 256 Morton-consecutive points, pads their box by r and streams that cell range
+// (icp_stream_cells); a lane is finished when it holds m entries and its m-th d2 is <= r^2: every closer point lay in the
+// padded box, so the list is exact and a larger pass cannot change it.  While a lane is unfinished and the range does not
+// cover the grid, r doubles and the unfinished lanes start over.  (d2, index) is a total order: the radius schedule, and
+// with it the partition into workgroups, cannot change a result.
+
+// one workgroup per cloud: RANGE if a coordinate is not finite, FEW_POINTS if the cloud has fewer than knn points
+__global__ __launch_bounds__(ICP_WG) void nrm_status_kernel(const double* __restrict__ pts, int64_t n, const int64_t* __restrict__ off,
+                                                            int knn, int32_t* __restrict__ status) {
+  const int c = blockIdx.x, t = threadIdx.x;
+  const int64_t lo = clipi(off[c], n), hi = clipi(off[c + 1], n);
+  int bad = 0;
+  for (int64_t i = lo + t; i < hi; i += ICP_WG)
+    if (!(fabs(pts[i * 3]) < INFINITY && fabs(pts[i * 3 + 1]) < INFINITY && fabs(pts[i * 3 + 2]) < INFINITY)) bad = 1;
+  bad = __syncthreads_or(bad);
+  if (t == 0)
+    status[c] = (bad ? EGONN_NORMALS_STATUS_RANGE : 0) | ((hi > lo ? hi - lo : 0) < knn ? EGONN_NORMALS_STATUS_FEW_POINTS : 0);
+}
+
+// eigen-decomposition of the symmetric 3 x 3 matrix A by cyclic Jacobi, the schedule of icp_top_eigenvector: A's diagonal
+// becomes the eigenvalues, the columns of V the eigenvectors
+__device__ static inline void nrm_jacobi3(double A[3][3], double V[3][3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    if (fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]) == 0.0) break;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = i + 1; j < 3; ++j) {
+        const double apq = A[i][j];
+        if (apq != 0.0) {
+          const double theta = (A[j][j] - A[i][i]) / (2.0 * apq);
+          const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+          const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {              // A <- A J
+            const double aki = A[k][i], akj = A[k][j];
+            A[k][i] = c * aki - s * akj;
+            A[k][j] = s * aki + c * akj;
+          }
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {              // A <- J^T A
+            const double aik = A[i][k], ajk = A[j][k];
+            A[i][k] = c * aik - s * ajk;
+            A[j][k] = s * aik + c * ajk;
+          }
+          A[i][j] = A[j][i] = 0.0;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            const double vki = V[k][i], vkj = V[k][j];
+            V[k][i] = c * vki - s * vkj;
+            V[k][j] = s * vki + c * vkj;
+          }
+        }
+      }
+  }
+}
+
+// K: the capacity of a lane's sorted list, kept in registers (every index below is a compile-time constant after unrolling)
+template <int K>
+__global__ __launch_bounds__(ICP_WG) void nrm_knn_kernel(const IcpPair* __restrict__ pairs, const int32_t* __restrict__ wg0, int P,
+                                                         const double* __restrict__ pts, const double* __restrict__ sq,
+                                                         const int32_t* __restrict__ si, const double* __restrict__ tq,
+                                                         const int32_t* __restrict__ tj, const uint64_t* __restrict__ tkey, int knn,
+                                                         const int32_t* __restrict__ status, double* __restrict__ normals,
+                                                         int32_t* __restrict__ neighbors, double* __restrict__ eigenvalues) {
+  __shared__ double s_box[6][4];
+  const int flat = blockIdx.x, t = threadIdx.x;
+  const int p = icp_pair_of(wg0, P, flat);
+  const IcpPair* q = pairs + p;
+  const int chunk = flat - wg0[p];
+  const int ns = q->ns;                                   // source = target = the cloud
+  if (chunk < 0 || (int64_t)chunk * ICP_WG >= ns) return;  // workgroup-uniform; an empty cloud has no workgroup
+  const int row = chunk * ICP_WG + t;
+  const bool valid = row < ns;
+  const int64_t so = q->so;
+  int orig = valid ? si[so + row] : 0;
+  orig = orig < 0 ? 0 : (orig >= ns ? ns - 1 : orig);
+  double* nout = normals + (so + orig) * 3;
+  if (status[p] & EGONN_NORMALS_STATUS_RANGE) {           // workgroup-uniform
+    if (valid) {
+      nout[0] = 0.0, nout[1] = 0.0, nout[2] = 1.0;
+      if (neighbors)
+        for (int s = 0; s < knn; ++s) neighbors[(so + orig) * knn + s] = -1;
+      if (eigenvalues)
+        for (int k = 0; k < 3; ++k) eigenvalues[(so + orig) * 3 + k] = 0.0;
+    }
+    return;
+  }
+  const int m = knn < ns ? knn : ns;
+  double px = 0.0, py = 0.0, pz = 0.0;
+  if (valid) px = sq[(so + row) * 3], py = sq[(so + row) * 3 + 1], pz = sq[(so + row) * 3 + 2];
+  icp_wave_box(s_box, valid, px, py, pz);
+  __syncthreads();
+  double ld[K];
+  int lj[K];
+  bool fin = !valid;
+  // start radius: the cell edge, or an eighth of the box's longest side where the workgroup's points are sparse (256 points
+  // of a surface at spacing s span ~16 s and their 20th neighbour lies ~2.5 s away).  Any start gives the same lists.
+  double r = q->h;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double lo = fmin(fmin(s_box[k][0], s_box[k][1]), fmin(s_box[k][2], s_box[k][3]));
+    const double hi = fmax(fmax(s_box[3 + k][0], s_box[3 + k][1]), fmax(s_box[3 + k][2], s_box[3 + k][3]));
+    const double e = (hi - lo) * 0.125;
+    if (e > r) r = e;                                      // false for NaN
+  }
+  for (int pass = 0; pass < 64; ++pass) {                  // r doubles: the grid has at most 2^16 cells per axis
+    const IcpRange rg = icp_cell_range(q, s_box, r);
+    const bool covers = rg.lo[0] == 0 && rg.lo[1] == 0 && rg.lo[2] == 0 && rg.hi[0] == q->dim[0] - 1 &&
+                        rg.hi[1] == q->dim[1] - 1 && rg.hi[2] == q->dim[2] - 1;
+    if (!fin) {
+#pragma unroll
+      for (int s = 0; s < K; ++s) ld[s] = INFINITY, lj[s] = 0x7fffffff;     // an empty slot: behind every point
+    }
+    icp_stream_cells(tkey + so, ns, tq, tj, so, rg, !fin, [&](double qx, double qy, double qz, int j) {
+      const double dx = px - qx, dy = py - qy, dz = pz - qz;
+      const double d2 = (dx * dx + dy * dy) + dz * dz;
+      if (d2 < ld[K - 1] || (d2 == ld[K - 1] && j < lj[K - 1])) {
+        bool here = true;                                  // the candidate sorts before slot s
+#pragma unroll
+        for (int s = K - 1; s >= 1; --s) {                 // compare and shift: slot s from slot s - 1, not yet touched
+          const bool prev = d2 < ld[s - 1] || (d2 == ld[s - 1] && j < lj[s - 1]);
+          ld[s] = prev ? ld[s - 1] : (here ? d2 : ld[s]);
+          lj[s] = prev ? lj[s - 1] : (here ? j : lj[s]);
+          here = prev;
+        }
+        if (here) ld[0] = d2, lj[0] = j;
+      }
+    });
+    if (!fin) {
+      double dm = INFINITY;
+#pragma unroll
+      for (int s = 0; s < K; ++s)
+        if (s == m - 1) dm = ld[s];
+      fin = dm <= r * r;
+    }
+    const int open = __syncthreads_or(fin ? 0 : 1);
+    if (!open || covers) break;
+    r = r + r;
+  }
+  if (!valid) return;
+  // mean and covariance in neighbour order
+  int cnt = 0;
+  double mx = 0.0, my = 0.0, mz = 0.0;
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    if (s < m && lj[s] < ns) {
+      const double* g = pts + (so + lj[s]) * 3;
+      mx += g[0], my += g[1], mz += g[2];
+      ++cnt;
+    }
+  }
+  const double dm = (double)(cnt > 0 ? cnt : 1);
+  mx = mx / dm, my = my / dm, mz = mz / dm;
+  double c00 = 0.0, c01 = 0.0, c02 = 0.0, c11 = 0.0, c12 = 0.0, c22 = 0.0;
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    if (s < m && lj[s] < ns) {
+      const double* g = pts + (so + lj[s]) * 3;
+      const double ax = g[0] - mx, ay = g[1] - my, az = g[2] - mz;
+      c00 += ax * ax, c01 += ax * ay, c02 += ax * az, c11 += ay * ay, c12 += ay * az, c22 += az * az;
+    }
+  }
+  double A[3][3], V[3][3];
+  A[0][0] = c00 / dm, A[1][1] = c11 / dm, A[2][2] = c22 / dm;
+  A[0][1] = A[1][0] = c01 / dm, A[0][2] = A[2][0] = c02 / dm, A[1][2] = A[2][1] = c12 / dm;
+  nrm_jacobi3(A, V);
+  int lo = 0, hi = 0;
+#pragma unroll
+  for (int i = 1; i < 3; ++i) {
+    if (A[i][i] < (lo == 0 ? A[0][0] : (lo == 1 ? A[1][1] : A[2][2]))) lo = i;
+    if (A[i][i] > (hi == 0 ? A[0][0] : (hi == 1 ? A[1][1] : A[2][2]))) hi = i;
+  }
+  const double e0 = lo == 0 ? A[0][0] : (lo == 1 ? A[1][1] : A[2][2]), e2 = hi == 0 ? A[0][0] : (hi == 1 ? A[1][1] : A[2][2]);
+  const int mid = lo == hi ? lo : 3 - lo - hi;
+  const double e1 = mid == 0 ? A[0][0] : (mid == 1 ? A[1][1] : A[2][2]);
+  double nx = lo == 0 ? V[0][0] : (lo == 1 ? V[0][1] : V[0][2]);
+  double ny = lo == 0 ? V[1][0] : (lo == 1 ? V[1][1] : V[1][2]);
+  double nz = lo == 0 ? V[2][0] : (lo == 1 ? V[2][1] : V[2][2]);
+  const double len = sqrt((nx * nx + ny * ny) + nz * nz);
+  nx = nx / len, ny = ny / len, nz = nz / len;
+  const double dot = (nx * px + ny * py) + nz * pz;
+  const double lead = nx != 0.0 ? nx : (ny != 0.0 ? ny : nz);
+  if (dot > 0.0 || (dot == 0.0 && lead < 0.0)) nx = -nx, ny = -ny, nz = -nz;
+  const bool good = cnt >= 3 && e2 > 0.0 && fabs(e2) < INFINITY && fabs(nx) < 2.0 && fabs(ny) < 2.0 && fabs(nz) < 2.0;     // false for NaN
+  nout[0] = good ? nx : 0.0, nout[1] = good ? ny : 0.0, nout[2] = good ? nz : 1.0;
+  if (neighbors) {
+#pragma unroll
+    for (int s = 0; s < K; ++s)
+      if (s < knn) neighbors[(so + orig) * knn + s] = (s < m && lj[s] < ns) ? lj[s] : -1;
+  }
+  if (eigenvalues) {
+    double* ev = eigenvalues + (so + orig) * 3;
+    ev[0] = e0, ev[1] = e1, ev[2] = e2;
+  }
+}
+
+struct NrmLayout {
+  size_t pairs, wg0, keys0, keys1, vals0, vals1, tq, tj, tkey, sq, si, outs, sort, sort_bytes, total;
+  int64_t n_wg;
+};
+static NrmLayout nrm_layout(int64_t n, int C) {
+  NrmLayout L;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+  const size_t m = (size_t)(n > 0 ? n : 1);
+  L.n_wg = cdiv((int64_t)m, ICP_WG) + C;
+  L.pairs = take((size_t)C * sizeof(IcpPair));
+  L.wg0 = take((size_t)(C + 1) * 4);
+  L.keys0 = take(m * 8), L.keys1 = take(m * 8), L.vals0 = take(m * 4), L.vals1 = take(m * 4);
+  L.tq = take(m * 24), L.tj = take(m * 4), L.tkey = take(m * 8);
+  L.sq = take(m * 24), L.si = take(m * 4);
+  L.outs = take((size_t)C * 20 * 8);      // what icp_setup_kernel writes for an empty pair: T (16), fitness, rmse, iterations, status
+  L.sort_bytes = align_up(radix_sort_segments_scratch_bytes((int64_t)m, C) + 512, 256);
+  L.sort = take(L.sort_bytes);
+  L.total = o;
+  return L;
+}
+
 struct IcpLayout {
   size_t pairs, wg0, keys0, keys1, vals0, vals1, tq, tj, tkey, sq, si, partial, sort, sort_bytes, total;
   int64_t n_wg;
+  int estimator;            // 0: point-to-point, 1: point-to-plane; the one thing that tells the two calls apart
 };
-static IcpLayout icp_layout(int64_t ns, int64_t nt, int P) {
+static IcpLayout icp_layout(int64_t ns, int64_t nt, int P, int estimator) {
   IcpLayout L;
+  L.estimator = estimator;
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
   const size_t a = (size_t)(ns > 0 ? ns : 1), b = (size_t)(nt > 0 ? nt : 1), m = a > b ? a : b;
@@ -702,7 +1055,7 @@ static IcpLayout icp_layout(int64_t ns, int64_t nt, int P) {
   L.keys0 = take(m * 8), L.keys1 = take(m * 8), L.vals0 = take(m * 4), L.vals1 = take(m * 4);
   L.tq = take(b * 24), L.tj = take(b * 4), L.tkey = take(b * 8);
   L.sq = take(a * 24), L.si = take(a * 4);
-  L.partial = take((size_t)L.n_wg * ICP_NPART * 8);
+  L.partial = take((size_t)L.n_wg * (estimator ? ICP_NPART_PLANE : ICP_NPART) * 8);
   // + 512: the sort carves two arrays out of this span and Arena::alloc aligns each carve to 256
   L.sort_bytes = align_up(radix_sort_segments_scratch_bytes((int64_t)m, P) + 512, 256);
   L.sort = take(L.sort_bytes);
@@ -757,29 +1110,39 @@ API int egonn_voxel_downsample(const float* points, int64_t n, const int64_t* of
   return EGONN_OK;
 }
 
-API int64_t egonn_icp_scratch_bytes(int64_t n_src, int64_t n_tgt, int n_pairs) {
-  if (n_src < 0 || n_tgt < 0 || n_src >= (1ll << 31) || n_tgt >= (1ll << 31) || n_pairs < 1 || n_pairs > EGONN_MAX_BATCH) return -1;
-  return (int64_t)icp_layout(n_src, n_tgt, n_pairs).total;
+
+// cell order of the targets (side 0: tq, tj, tkey) or Morton order of the sources under T_0 (side 1: sq, si) of every pair
+static int icp_order_side(int side, const double* pts, int64_t n, const int64_t* off, int P, const IcpPair* pairs, Arena sort_ws,
+                          uint64_t* keys0, uint32_t* vals0, uint64_t* keys1, uint32_t* vals1, double* out_pts, int32_t* out_idx,
+                          uint64_t* out_keys, hipStream_t st) {
+  uint64_t* keys = keys0;
+  uint32_t* vals = vals0;
+  const unsigned nb = (unsigned)cdiv(n, ICP_WG);
+  hipLaunchKernelGGL(icp_key_kernel, dim3(nb), dim3(ICP_WG), 0, st, pts, n, off, P, pairs, side, keys, vals);
+  EGONN_TRY(radix_sort_segments(sort_ws, keys, vals, keys1, vals1, n, off, P, 48, st, &keys, &vals));
+  hipLaunchKernelGGL(icp_gather_kernel, dim3(nb), dim3(ICP_WG), 0, st, pts, n, off, P, keys, vals, out_pts, out_idx, out_keys);
+  return EGONN_OK;
 }
 
-API int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_offsets, const double* tgt, int64_t n_tgt,
-                        const int64_t* tgt_offsets, int n_pairs, const double* T_init, double max_dist, int max_iteration,
-                        double eps_fitness, double eps_rmse, double* T, double* fitness, double* inlier_rmse, int32_t* iterations,
-                        int32_t* status, double* T_trace, double* eval_trace, int32_t* corr, void* scratch, int64_t scratch_bytes,
-                        void* stream) {
+// the ICP loop of both entry points; L.estimator picks the instantiation of the two per-round kernels
+static int icp_run(const IcpLayout& L, const char* who, const double* src, int64_t n_src, const int64_t* src_offsets,
+                   const double* tgt, int64_t n_tgt, const int64_t* tgt_offsets, const double* tgt_normals, int n_pairs,
+                   const double* T_init, double max_dist, int max_iteration, double eps_fitness, double eps_rmse, double* T,
+                   double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* status, double* T_trace, double* eval_trace,
+                   int32_t* corr, void* scratch, int64_t scratch_bytes, void* stream) {
   EGONN_REQUIRE(n_src >= 0 && n_tgt >= 0 && n_src < (1ll << 31) && n_tgt < (1ll << 31) && n_pairs >= 1 && n_pairs <= EGONN_MAX_BATCH,
-                EGONN_ERR_INVALID, "icp_pairs: bad shape (n_src=%lld, n_tgt=%lld, n_pairs=%d; n_pairs <= %d)", (long long)n_src,
+                EGONN_ERR_INVALID, "%s: bad shape (n_src=%lld, n_tgt=%lld, n_pairs=%d; n_pairs <= %d)", who, (long long)n_src,
                 (long long)n_tgt, n_pairs, EGONN_MAX_BATCH);
-  EGONN_REQUIRE(max_dist > 0.0 && max_dist < 1e18, EGONN_ERR_INVALID, "icp_pairs: bad distance threshold");
-  EGONN_REQUIRE(max_iteration >= 0 && max_iteration <= 100000, EGONN_ERR_INVALID, "icp_pairs: max_iteration %d outside [0, 100000]",
+  EGONN_REQUIRE(max_dist > 0.0 && max_dist < 1e18, EGONN_ERR_INVALID, "%s: bad distance threshold", who);
+  EGONN_REQUIRE(max_iteration >= 0 && max_iteration <= 100000, EGONN_ERR_INVALID, "%s: max_iteration %d outside [0, 100000]", who,
                 max_iteration);
-  EGONN_REQUIRE(eps_fitness >= 0.0 && eps_rmse >= 0.0, EGONN_ERR_INVALID, "icp_pairs: negative convergence threshold");
+  EGONN_REQUIRE(eps_fitness >= 0.0 && eps_rmse >= 0.0, EGONN_ERR_INVALID, "%s: negative convergence threshold", who);
   EGONN_REQUIRE(src_offsets && tgt_offsets && T && fitness && inlier_rmse && iterations && status && scratch &&
                     (n_src == 0 || src) && (n_tgt == 0 || tgt),
-                EGONN_ERR_INVALID, "icp_pairs: null pointer");
-  const IcpLayout L = icp_layout(n_src, n_tgt, n_pairs);
+                EGONN_ERR_INVALID, "%s: null pointer", who);
+  EGONN_REQUIRE(!L.estimator || n_tgt == 0 || tgt_normals, EGONN_ERR_INVALID, "%s: null tgt_normals", who);
   EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "icp_pairs: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+                "%s: scratch needs %lld bytes, 256-byte aligned", who, (long long)L.total);
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)scratch;
   IcpPair* pairs = (IcpPair*)(base + L.pairs);
@@ -799,25 +1162,112 @@ API int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_off
   int32_t* si = (int32_t*)(base + L.si);
   double* partial = (double*)(base + L.partial);
   Arena sort_ws = Arena::view(base + L.sort, L.sort_bytes);
-  for (int side = 0; side < 2; ++side) {
-    const double* pts = side == 0 ? tgt : src;
-    const int64_t n = side == 0 ? n_tgt : n_src;
-    const int64_t* off = side == 0 ? tgt_offsets : src_offsets;
-    uint64_t* keys = (uint64_t*)(base + L.keys0);
-    uint32_t* vals = (uint32_t*)(base + L.vals0);
-    const unsigned nb = (unsigned)cdiv(n, ICP_WG);
-    hipLaunchKernelGGL(icp_key_kernel, dim3(nb), dim3(ICP_WG), 0, st, pts, n, off, n_pairs, pairs, side, keys, vals);
-    EGONN_TRY(radix_sort_segments(sort_ws, keys, vals, (uint64_t*)(base + L.keys1), (uint32_t*)(base + L.vals1), n, off, n_pairs, 48,
-                                  st, &keys, &vals));
-    hipLaunchKernelGGL(icp_gather_kernel, dim3(nb), dim3(ICP_WG), 0, st, pts, n, off, n_pairs, keys, vals, side == 0 ? tq : sq,
-                       side == 0 ? tj : si, side == 0 ? tkey : (uint64_t*)nullptr);
-  }
+  uint64_t *k0 = (uint64_t*)(base + L.keys0), *k1 = (uint64_t*)(base + L.keys1);
+  uint32_t *v0 = (uint32_t*)(base + L.vals0), *v1 = (uint32_t*)(base + L.vals1);
+  EGONN_TRY(icp_order_side(0, tgt, n_tgt, tgt_offsets, n_pairs, pairs, sort_ws, k0, v0, k1, v1, tq, tj, tkey, st));
+  EGONN_TRY(icp_order_side(1, src, n_src, src_offsets, n_pairs, pairs, sort_ws, k0, v0, k1, v1, sq, si, nullptr, st));
+  const dim3 grid((unsigned)L.n_wg), one((unsigned)n_pairs);
   for (int k = 0; k <= max_iteration; ++k) {
-    hipLaunchKernelGGL(icp_search_kernel, dim3((unsigned)L.n_wg), dim3(ICP_WG), 0, st, pairs, wg0, n_pairs, sq, si, tq, tj, tkey,
-                       max_dist, partial, corr);
-    hipLaunchKernelGGL(icp_finish_kernel, dim3((unsigned)n_pairs), dim3(64), 0, st, pairs, wg0, partial, k, max_iteration, eps_fitness,
-                       eps_rmse, T, fitness, inlier_rmse, iterations, status, T_trace, eval_trace);
+    if (L.estimator) {
+      hipLaunchKernelGGL(icp_search_kernel<1>, grid, dim3(ICP_WG), 0, st, pairs, wg0, n_pairs, sq, si, tq, tj, tkey, tgt_normals,
+                         max_dist, partial, corr);
+      hipLaunchKernelGGL(icp_finish_kernel<1>, one, dim3(64), 0, st, pairs, wg0, partial, k, max_iteration, eps_fitness, eps_rmse, T,
+                         fitness, inlier_rmse, iterations, status, T_trace, eval_trace);
+    } else {
+      hipLaunchKernelGGL(icp_search_kernel<0>, grid, dim3(ICP_WG), 0, st, pairs, wg0, n_pairs, sq, si, tq, tj, tkey,
+                         (const double*)nullptr, max_dist, partial, corr);
+      hipLaunchKernelGGL(icp_finish_kernel<0>, one, dim3(64), 0, st, pairs, wg0, partial, k, max_iteration, eps_fitness, eps_rmse, T,
+                         fitness, inlier_rmse, iterations, status, T_trace, eval_trace);
+    }
   }
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}
+
+static bool icp_shape_ok(int64_t n_src, int64_t n_tgt, int n_pairs) {
+  return n_src >= 0 && n_tgt >= 0 && n_src < (1ll << 31) && n_tgt < (1ll << 31) && n_pairs >= 1 && n_pairs <= EGONN_MAX_BATCH;
+}
+
+API int64_t egonn_icp_scratch_bytes(int64_t n_src, int64_t n_tgt, int n_pairs) {
+  if (!icp_shape_ok(n_src, n_tgt, n_pairs)) return -1;
+  return (int64_t)icp_layout(n_src, n_tgt, n_pairs, 0).total;
+}
+
+API int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_offsets, const double* tgt, int64_t n_tgt,
+                        const int64_t* tgt_offsets, int n_pairs, const double* T_init, double max_dist, int max_iteration,
+                        double eps_fitness, double eps_rmse, double* T, double* fitness, double* inlier_rmse, int32_t* iterations,
+                        int32_t* status, double* T_trace, double* eval_trace, int32_t* corr, void* scratch, int64_t scratch_bytes,
+                        void* stream) {
+  // the layout is computed on sanitised capacities: icp_run refuses bad ones before it looks at it
+  const bool ok = icp_shape_ok(n_src, n_tgt, n_pairs);
+  return icp_run(icp_layout(ok ? n_src : 0, ok ? n_tgt : 0, ok ? n_pairs : 1, 0), "icp_pairs", src, n_src, src_offsets, tgt, n_tgt,
+                 tgt_offsets, nullptr, n_pairs, T_init, max_dist, max_iteration, eps_fitness, eps_rmse, T, fitness, inlier_rmse,
+                 iterations, status, T_trace, eval_trace, corr, scratch, scratch_bytes, stream);
+}
+
+API int64_t egonn_icp_plane_scratch_bytes(int64_t n_src, int64_t n_tgt, int n_pairs) {
+  if (!icp_shape_ok(n_src, n_tgt, n_pairs)) return -1;
+  return (int64_t)icp_layout(n_src, n_tgt, n_pairs, 1).total;
+}
+
+API int egonn_icp_plane_pairs(const double* src, int64_t n_src, const int64_t* src_offsets, const double* tgt, int64_t n_tgt,
+                              const int64_t* tgt_offsets, const double* tgt_normals, int n_pairs, const double* T_init,
+                              double max_dist, int max_iteration, double eps_fitness, double eps_rmse, double* T, double* fitness,
+                              double* inlier_rmse, int32_t* iterations, int32_t* status, double* T_trace, double* eval_trace,
+                              int32_t* corr, void* scratch, int64_t scratch_bytes, void* stream) {
+  const bool ok = icp_shape_ok(n_src, n_tgt, n_pairs);
+  return icp_run(icp_layout(ok ? n_src : 0, ok ? n_tgt : 0, ok ? n_pairs : 1, 1), "icp_plane_pairs", src, n_src, src_offsets, tgt,
+                 n_tgt, tgt_offsets, tgt_normals, n_pairs, T_init, max_dist, max_iteration, eps_fitness, eps_rmse, T, fitness,
+                 inlier_rmse, iterations, status, T_trace, eval_trace, corr, scratch, scratch_bytes, stream);
+}
+
+API int64_t egonn_estimate_normals_scratch_bytes(int64_t n, int n_clouds) {
+  if (n < 0 || n >= (1ll << 31) || n_clouds < 1 || n_clouds > EGONN_MAX_BATCH) return -1;
+  return (int64_t)nrm_layout(n, n_clouds).total;
+}
+
+API int egonn_estimate_normals(const double* points, int64_t n, const int64_t* offsets, int n_clouds, int knn, double* normals,
+                               int32_t* status, int32_t* neighbors, double* eigenvalues, void* scratch, int64_t scratch_bytes,
+                               void* stream) {
+  EGONN_REQUIRE(n >= 0 && n < (1ll << 31) && n_clouds >= 1 && n_clouds <= EGONN_MAX_BATCH, EGONN_ERR_INVALID,
+                "estimate_normals: bad shape (n=%lld, n_clouds=%d; n_clouds <= %d)", (long long)n, n_clouds, EGONN_MAX_BATCH);
+  EGONN_REQUIRE(knn >= NRM_KNN_MIN && knn <= NRM_KNN_MAX, EGONN_ERR_INVALID, "estimate_normals: knn %d outside [%d, %d]", knn,
+                NRM_KNN_MIN, NRM_KNN_MAX);
+  EGONN_REQUIRE(offsets && status && scratch && (n == 0 || (points && normals)), EGONN_ERR_INVALID, "estimate_normals: null pointer");
+  const NrmLayout L = nrm_layout(n, n_clouds);
+  EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
+                "estimate_normals: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)scratch;
+  IcpPair* pairs = (IcpPair*)(base + L.pairs);
+  int32_t* wg0 = (int32_t*)(base + L.wg0);
+  hipLaunchKernelGGL(nrm_status_kernel, dim3((unsigned)n_clouds), dim3(ICP_WG), 0, st, points, n, offsets, knn, status);
+  HIP_CHECK(hipGetLastError());
+  if (n == 0) return EGONN_OK;
+  // the ICP's grid with source = target = the cloud, T = identity and the cell edge as the search radius; what the setup
+  // writes for an empty cloud lands in scratch
+  double* outs = (double*)(base + L.outs);
+  double *o_T = outs, *o_fit = outs + (size_t)n_clouds * 16, *o_rmse = o_fit + n_clouds;
+  int32_t *o_it = (int32_t*)(o_rmse + n_clouds), *o_st = (int32_t*)(o_rmse + 2 * (size_t)n_clouds);
+  hipLaunchKernelGGL(icp_setup_kernel, dim3((unsigned)n_clouds), dim3(ICP_WG), 0, st, points, n, offsets, offsets, n, n_clouds,
+                     (const double*)nullptr, NRM_CELL, pairs, wg0, o_T, o_fit, o_rmse, o_it, o_st, (double*)nullptr, 0);
+  double* tq = (double*)(base + L.tq);
+  int32_t* tj = (int32_t*)(base + L.tj);
+  uint64_t* tkey = (uint64_t*)(base + L.tkey);
+  double* sq = (double*)(base + L.sq);
+  int32_t* si = (int32_t*)(base + L.si);
+  Arena sort_ws = Arena::view(base + L.sort, L.sort_bytes);
+  uint64_t *k0 = (uint64_t*)(base + L.keys0), *k1 = (uint64_t*)(base + L.keys1);
+  uint32_t *v0 = (uint32_t*)(base + L.vals0), *v1 = (uint32_t*)(base + L.vals1);
+  EGONN_TRY(icp_order_side(0, points, n, offsets, n_clouds, pairs, sort_ws, k0, v0, k1, v1, tq, tj, tkey, st));
+  EGONN_TRY(icp_order_side(1, points, n, offsets, n_clouds, pairs, sort_ws, k0, v0, k1, v1, sq, si, nullptr, st));
+  const dim3 grid((unsigned)L.n_wg);
+  if (knn <= 20)
+    hipLaunchKernelGGL(nrm_knn_kernel<20>, grid, dim3(ICP_WG), 0, st, pairs, wg0, n_clouds, points, sq, si, tq, tj, tkey, knn, status,
+                       normals, neighbors, eigenvalues);
+  else
+    hipLaunchKernelGGL(nrm_knn_kernel<32>, grid, dim3(ICP_WG), 0, st, pairs, wg0, n_clouds, points, sq, si, tq, tj, tkey, knn, status,
+                       normals, neighbors, eigenvalues);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }

@@ -26,6 +26,9 @@ MAX_PAIRS = 4096          # pairs per matching call (and per call sequence of re
                           # is 9-36 KB per pair, and pairs are independent, so chunking cannot change a bit
 STATUS_CLIPPED, STATUS_FEW_CORR, STATUS_NO_MODEL, STATUS_BAD_INDEX = 1, 2, 4, 8
 ICP_FEW_CORR, ICP_MAX_ITER, ICP_EMPTY, ICP_RANGE = 1, 2, 4, 8
+ICP_SINGULAR = 16                          # point-to-plane: the 6 x 6 solve met a pivot at rounding level (one plane, a corridor)
+NORMALS_FEW_POINTS, NORMALS_RANGE = 1, 2
+NORMALS_KNN = 20                           # misc/point_clouds.py:44-45: KDTreeSearchParamKNN(knn=20)
 ICP_VOXEL_SIZE = 0.1                       # misc/point_clouds.py:37
 ICP_EPS_FITNESS = ICP_EPS_RMSE = 1e-6      # Open3D's ICPConvergenceCriteria defaults [recall]
 
@@ -217,14 +220,45 @@ def voxel_downsample(points, offsets, voxel_size: float = ICP_VOXEL_SIZE, crop=N
     return out
 
 
+def estimate_normals(points, offsets, knn: int = NORMALS_KNN, debug: bool = False) -> Dict[str, torch.Tensor]:
+    """Surface normals of concatenated clouds (Open3D estimate_normals(KDTreeSearchParamKNN(knn)), restated in csrc/icp.hip):
+    points (n,3) float64 (what `voxel_downsample` returns) with (n_clouds+1,) offsets, knn in [3, 32].  Per point the exact
+    min(knn, cloud size) nearest points of its cloud (itself included, by (d2, index)), their covariance, the unit eigenvector
+    of its smallest eigenvalue, oriented toward the origin of the cloud's frame.  Returns device tensors normals (n,3) f64 and
+    status (n_clouds,) int32 (NORMALS_* bits); with debug also neighbors (n, knn) int32 (index inside the cloud, -1 beyond
+    the count) and eigenvalues (n,3) ascending.  No host synchronisation when the arguments are device tensors."""
+    _check_cloud("estimate_normals", points)
+    C = _check_offsets("estimate_normals", offsets)
+    knn = int(knn)
+    if not 3 <= knn <= 32:
+        raise ValueError(f"estimate_normals: knn must be in [3, 32], got {knn}")
+    dev = points.device if torch.is_tensor(points) and points.is_cuda else _lib.require_gpu()
+    lib = _lib.load()
+    pts, off = _dev(points, dev, torch.float64), _dev(offsets, dev, torch.int64)
+    n = pts.shape[0]
+    scratch = _lib.scratch(lib.egonn_estimate_normals_scratch_bytes(n, C), dev)
+    out = {"normals": torch.empty((n, 3), dtype=torch.float64, device=dev), "status": torch.empty((C,), dtype=torch.int32, device=dev)}
+    if debug:
+        out.update({"neighbors": torch.empty((n, knn), dtype=torch.int32, device=dev),
+                    "eigenvalues": torch.empty((n, 3), dtype=torch.float64, device=dev)})
+    _lib.call(dev, lib.egonn_estimate_normals, pts.data_ptr() if n else None, n, off.data_ptr(), C, knn,
+              out["normals"].data_ptr() if n else None, out["status"].data_ptr(), _lib._ptr(out.get("neighbors")) if n else None,
+              _lib._ptr(out.get("eigenvalues")) if n else None, scratch.data_ptr(), scratch.numel() * 8)
+    out["_keep"] = (pts, off, scratch)
+    return out
+
+
 def icp_pairs(src, src_offsets, tgt, tgt_offsets, T_init=None, inlier_dist_threshold: float = 1.2, max_iteration: int = 200,
-              debug: bool = False) -> Dict[str, torch.Tensor]:
+              debug: bool = False, tgt_normals=None) -> Dict[str, torch.Tensor]:
     """Point-to-point ICP of P (source, target) pairs (Open3D registration_icp, restated in csrc/icp.hip): src / tgt (n,3)
     float64 concatenated clouds (what `voxel_downsample` returns) with (P+1,) offsets, T_init (P,4,4) or None = identity.
     Returns device tensors T (P,4,4) f64, fitness, inlier_rmse (P,) f64, iterations, status (P,) int32 (ICP_* bits); with
     debug also T_trace (P, max_iteration+1, 4, 4), eval_trace (P, max_iteration+1, 3) = (n_corr, sum d2, stop) and corr
     (n_src,) int32 = j(i) of the last evaluation or -1.  No host synchronisation when the arguments are device tensors: the
-    call enqueues a fixed launch sequence and can be captured into a graph."""
+    call enqueues a fixed launch sequence and can be captured into a graph.
+    tgt_normals (n_tgt,3) float64 (`estimate_normals` of tgt) switches to the point-to-plane estimator (egonn_icp_plane_pairs):
+    same evaluation, stop rule and tables; fewer than 6 correspondences give ICP_FEW_CORR, a rank-deficient scene
+    ICP_SINGULAR.  None is the point-to-point call, unchanged."""
     _check_cloud("icp_pairs: src", src)
     _check_cloud("icp_pairs: tgt", tgt)
     P = _check_offsets("icp_pairs: src_offsets", src_offsets)
@@ -234,30 +268,39 @@ def icp_pairs(src, src_offsets, tgt, tgt_offsets, T_init=None, inlier_dist_thres
         raise ValueError(f"icp_pairs: T_init must have shape ({P}, 4, 4), got {tuple(T_init.shape)}")
     if int(max_iteration) < 0 or not float(inlier_dist_threshold) > 0.0:
         raise ValueError("icp_pairs: max_iteration >= 0 and inlier_dist_threshold > 0 required")
+    if tgt_normals is not None and tuple(tgt_normals.shape) != (tgt.shape[0], 3):
+        raise ValueError(f"icp_pairs: tgt_normals must have shape ({tgt.shape[0]}, 3), got {tuple(tgt_normals.shape)}")
     dev = src.device if torch.is_tensor(src) and src.is_cuda else _lib.require_gpu()
     lib = _lib.load()
     s, t = _dev(src, dev, torch.float64), _dev(tgt, dev, torch.float64)       # fp32 inputs convert exactly
     so, to = _dev(src_offsets, dev, torch.int64), _dev(tgt_offsets, dev, torch.int64)
     ti = None if T_init is None else _dev(T_init, dev, torch.float64)
     ns, nt, K = s.shape[0], t.shape[0], int(max_iteration)
-    scratch = _lib.scratch(lib.egonn_icp_scratch_bytes(ns, nt, P), dev)
+    tn = None if tgt_normals is None else _dev(tgt_normals, dev, torch.float64)
+    scratch = _lib.scratch((lib.egonn_icp_scratch_bytes if tn is None else lib.egonn_icp_plane_scratch_bytes)(ns, nt, P), dev)
     f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)        # noqa: E731
     i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)          # noqa: E731
     out = {"T": f64(P, 4, 4), "fitness": f64(P), "inlier_rmse": f64(P), "iterations": i32(P), "status": i32(P)}
     if debug:
         out.update({"T_trace": f64(P, K + 1, 4, 4), "eval_trace": f64(P, K + 1, 3), "corr": i32(ns)})
     p = lambda k: _lib._ptr(out.get(k))                                       # noqa: E731
-    _lib.call(dev, lib.egonn_icp_pairs, s.data_ptr() if ns else None, ns, so.data_ptr(), t.data_ptr() if nt else None, nt,
-              to.data_ptr(), P, _lib._ptr(ti), float(inlier_dist_threshold), K, ICP_EPS_FITNESS, ICP_EPS_RMSE, p("T"),
-              p("fitness"), p("inlier_rmse"), p("iterations"), p("status"), p("T_trace"), p("eval_trace"),
-              p("corr") if ns else None, scratch.data_ptr(), scratch.numel() * 8)
-    out["_keep"] = (s, t, so, to, ti, scratch)
+    head = (s.data_ptr() if ns else None, ns, so.data_ptr(), t.data_ptr() if nt else None, nt, to.data_ptr())
+    tail = (P, _lib._ptr(ti), float(inlier_dist_threshold), K, ICP_EPS_FITNESS, ICP_EPS_RMSE, p("T"), p("fitness"),
+            p("inlier_rmse"), p("iterations"), p("status"), p("T_trace"), p("eval_trace"), p("corr") if ns else None,
+            scratch.data_ptr(), scratch.numel() * 8)
+    if tn is None:
+        _lib.call(dev, lib.egonn_icp_pairs, *head, *tail)
+    else:
+        _lib.call(dev, lib.egonn_icp_plane_pairs, *head, tn.data_ptr() if nt else None, *tail)
+    out["_keep"] = (s, t, so, to, ti, tn, scratch)
     return out
 
 
 def refine_pairs(src_clouds, tgt_clouds, T_init=None, crop=None, inlier_dist_threshold: float = 1.2, max_iteration: int = 200,
-                 debug: bool = False) -> Dict[str, torch.Tensor]:
-    """icp() for P pairs of full clouds (lists of (n,3) arrays): crop, downsample both sides, ICP.  The `icp_pairs` result."""
+                 debug: bool = False, point2plane: bool = False, knn: int = NORMALS_KNN) -> Dict[str, torch.Tensor]:
+    """icp() for P pairs of full clouds (lists of (n,3) arrays): crop, downsample both sides, ICP.  The `icp_pairs` result.
+    point2plane: normals of the downsampled target side (`estimate_normals`, knn neighbours), then the point-to-plane
+    estimator.  (The reference estimates the source's normals as well; point-to-plane never reads them.)"""
     if len(src_clouds) != len(tgt_clouds):
         raise ValueError("refine_pairs: as many source as target clouds")
     for c in list(src_clouds) + list(tgt_clouds):
@@ -265,26 +308,44 @@ def refine_pairs(src_clouds, tgt_clouds, T_init=None, crop=None, inlier_dist_thr
     dev = _lib.require_gpu()
     a = voxel_downsample(*_concat_clouds(src_clouds, dev), crop=crop)
     b = voxel_downsample(*_concat_clouds(tgt_clouds, dev), crop=crop)
-    r = icp_pairs(a["points"], a["offsets"], b["points"], b["offsets"], T_init, inlier_dist_threshold, max_iteration, debug)
-    r["_clouds"] = (a, b)
+    nrm = estimate_normals(b["points"], b["offsets"], knn) if point2plane else None
+    r = icp_pairs(a["points"], a["offsets"], b["points"], b["offsets"], T_init, inlier_dist_threshold, max_iteration, debug,
+                  None if nrm is None else nrm["normals"])
+    r["_clouds"] = (a, b, nrm)
     return r
 
 
 def icp(anchor_pc, positive_pc, transform=None, point2plane: bool = False, inlier_dist_threshold: float = 1.2,
         max_iteration: int = 200):
     """misc/point_clouds.py:31-62 for one pair: -> (T (4,4) numpy float64, fitness, inlier_rmse).  [SYNC] copies the result
-    back.  Point-to-plane is not implemented."""
+    back.  point2plane=True still raises NotImplementedError: the tests of the point-to-point pull request pin that refusal
+    (tests/test_icp_host.py, tests/test_gpu_icp.py).  The point-to-plane estimator is `icp_point_to_plane`; a change that may
+    touch those tests can route the flag there."""
     if point2plane:
-        raise NotImplementedError("icp: only the point-to-point estimation is implemented")
-    _check_cloud("icp: anchor_pc", anchor_pc)
-    _check_cloud("icp: positive_pc", positive_pc)
+        raise NotImplementedError("icp: point2plane=True is refused here; call icp_point_to_plane for the point-to-plane estimation")
+    return _icp_one("icp", anchor_pc, positive_pc, transform, inlier_dist_threshold, max_iteration, False, NORMALS_KNN)
+
+
+def icp_point_to_plane(anchor_pc, positive_pc, transform=None, inlier_dist_threshold: float = 1.2, max_iteration: int = 200,
+                       knn: int = NORMALS_KNN):
+    """icp(..., point2plane=True) of misc/point_clouds.py:31-62 for one pair: normals of the downsampled target from its knn
+    nearest neighbours, then point-to-plane ICP -> (T (4,4) numpy float64, fitness, inlier_rmse).  [SYNC] copies the result
+    back.  The one-pair form of `refine_pairs(point2plane=True)`."""
+    return _icp_one("icp_point_to_plane", anchor_pc, positive_pc, transform, inlier_dist_threshold, max_iteration, True, knn)
+
+
+def _icp_one(who, anchor_pc, positive_pc, transform, inlier_dist_threshold, max_iteration, point2plane, knn):
+    _check_cloud(f"{who}: anchor_pc", anchor_pc)
+    _check_cloud(f"{who}: positive_pc", positive_pc)
+    if not 3 <= int(knn) <= 32:
+        raise ValueError(f"{who}: knn must be in [3, 32], got {knn}")
     ti = None
     if transform is not None:
         ti = torch.as_tensor(np.asarray(transform, dtype=np.float64))
         if tuple(ti.shape) != (4, 4):
-            raise ValueError(f"icp: transform must be (4, 4), got {tuple(ti.shape)}")
+            raise ValueError(f"{who}: transform must be (4, 4), got {tuple(ti.shape)}")
         ti = ti.reshape(1, 4, 4)
-    r = refine_pairs([anchor_pc], [positive_pc], ti, None, inlier_dist_threshold, max_iteration)
+    r = refine_pairs([anchor_pc], [positive_pc], ti, None, inlier_dist_threshold, max_iteration, False, point2plane, knn)
     return r["T"][0].cpu().numpy(), float(r["fitness"][0]), float(r["inlier_rmse"][0])
 
 
@@ -323,7 +384,7 @@ def _stack(items, idx, key, n_k, width, dev):
 def evaluate_local(local_query: Sequence[dict], local_map: Sequence[dict], nn_index, T_gt, n_k: Sequence[int] = (128,),
                    euclid_dist=None, T_refined=None, ransac_dist_th: float = 0.5, ransac_max_it: int = 10000,
                    repeat_dist_th: float = 0.5, seed: int = 0, query_clouds=None, map_clouds=None, crop=None,
-                   icp_dist_th: float = 1.2, icp_max_it: int = 200) -> Dict[int, Dict[str, float]]:
+                   icp_dist_th: float = 1.2, icp_max_it: int = 200, icp_point2plane: bool = False) -> Dict[int, Dict[str, float]]:
     """The local-descriptor half of MinkLocGLEvaluator.evaluate (eval/evaluate.py:188-292) for all queries at once.
 
     local_query / local_map: per scan {'keypoints': (n,3), 'features': (n,D)} (compute_embeddings, :323); nn_index (Q,) or
@@ -337,7 +398,8 @@ def evaluate_local(local_query: Sequence[dict], local_map: Sequence[dict], nn_in
     query_clouds / map_clouds (per-scan (n,3) arrays, indexed like local_query / local_map) switch the ICP refinement on
     (icp_refine, :215-236): T_refined = icp(query cloud, map cloud, T_gt) on the device, after the optional `crop` (min_x,
     max_x, min_y, max_y, min_z, max_z) on both clouds; a caller's T_refined is then not used.  The dict then also carries
-    'rre_refined', 'rte_refined', 'success_refined', 'success_inliers_refined', 'failure_inliers_refined' (:261-275)."""
+    'rre_refined', 'rte_refined', 'success_refined', 'success_inliers_refined', 'failure_inliers_refined' (:261-275).
+    icp_point2plane refines with the point-to-plane estimator (`refine_pairs(point2plane=True)`)."""
     if (query_clouds is None) != (map_clouds is None):
         raise ValueError("evaluate_local: query_clouds and map_clouds go together")
     refine = query_clouds is not None
@@ -356,7 +418,7 @@ def evaluate_local(local_query: Sequence[dict], local_map: Sequence[dict], nn_in
     icp_res = None
     if refine and sel:                                    # one batched call for every n_k: the clouds do not depend on it
         icp_res = refine_pairs([query_clouds[q] for q in sel], [map_clouds[nn[q]] for q in sel], gt_all[sel], crop,
-                               icp_dist_th, icp_max_it)
+                               icp_dist_th, icp_max_it, point2plane=bool(icp_point2plane))
     for nk in n_k:
         if nk > N_MAX:
             raise ValueError(f"evaluate_local: n_k {nk} exceeds {N_MAX}")

@@ -270,11 +270,12 @@ class Relocalizer:
 
     extractor: a `DescriptorExtractor` (or any object whose `extract(scans)` returns its dict); kmap: a `KeypointMap` on the
     extractor's device; k: candidates per query.  refine=True needs `kmap.clouds` and polishes the winner's T_rel by
-    point-to-point ICP of the query's downsampled cloud against the winner's cloud of the bank."""
+    point-to-point ICP of the query's downsampled cloud against the winner's cloud of the bank; icp_point2plane=True uses the
+    point-to-plane estimator instead, on normals of the gathered winners' clouds."""
 
     def __init__(self, extractor, kmap: KeypointMap, k: int = 20, min_inliers: int = 0, ransac_dist_th: float = 0.5,
                  ransac_max_it: int = 10000, seed: int = 0, refine: bool = False, icp_dist_th: float = 1.2,
-                 icp_max_it: int = 200, chunk_pairs: int = MAX_PAIRS):
+                 icp_max_it: int = 200, chunk_pairs: int = MAX_PAIRS, icp_point2plane: bool = False):
         if int(k) < 1:
             raise ValueError("Relocalizer: k must be positive")
         if refine and kmap.clouds is None:
@@ -282,6 +283,7 @@ class Relocalizer:
         self.extractor, self.kmap, self.k = extractor, kmap, int(k)
         self.min_inliers, self.ransac_dist_th, self.ransac_max_it, self.seed = int(min_inliers), ransac_dist_th, ransac_max_it, seed
         self.refine, self.icp_dist_th, self.icp_max_it, self.chunk_pairs = bool(refine), icp_dist_th, icp_max_it, chunk_pairs
+        self.icp_point2plane = bool(icp_point2plane)
 
     def _extract(self, scans):
         """-> (extractor dict, deferred status check or None)"""
@@ -320,8 +322,9 @@ class Relocalizer:
             off[1:] = np.cumsum([p.shape[0] for p in pts])
             qd = _reg.voxel_downsample(torch.cat(pts).contiguous(), torch.from_numpy(off).to(dev), bank.voxel_size, bank.crop)
             g = bank.gather(r["safe_pick"], capacity=Q * int(bank.sizes().max()) if len(bank) else 0)
+            nrm = _reg.estimate_normals(g["points"], g["offsets"])["normals"] if self.icp_point2plane else None
             icp = _reg.icp_pairs(qd["points"], qd["offsets"], g["points"], g["offsets"], r["T_rel"], self.icp_dist_th,
-                                 self.icp_max_it)
+                                 self.icp_max_it, tgt_normals=nrm)
             r.update({"T_icp": icp["T"], "icp_fitness": icp["fitness"], "icp_inlier_rmse": icp["inlier_rmse"],
                       "icp_status": icp["status"], "pose_refined": _pose_product(km.poses, r["safe_pick"], icp["T"]),
                       "_refine": (qd, g, icp)})

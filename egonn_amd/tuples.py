@@ -375,7 +375,8 @@ def _csr_to_host(nb) -> Tuple[np.ndarray, np.ndarray]:
 
 def generate_training_tuples(poses, scans, pos_threshold: float = 2., neg_threshold: float = 10., refine: bool = True,
                              pairs_per_call: int = 16, negate_translation: bool = True, inlier_dist_threshold: float = 1.2,
-                             max_iteration: int = 200, timestamps=None, rel_scan_filepaths=None):
+                             max_iteration: int = 200, timestamps=None, rel_scan_filepaths=None, point2plane: bool = False,
+                             knn: int = 20):
     """datasets/mulran/generate_training_tuples.py:41-100 for poses (n,4,4) float64 and scans = a `CloudBank` that holds the n
     scans, or a callable i -> (n_i, 3 | 4) float32 raw scan (a bank is then filled from it).  positives: other scans within
     pos_threshold of the anchor's (x, y) = poses[:, :2, 3]; non_negatives: scans within neg_threshold, the anchor included;
@@ -383,7 +384,9 @@ def generate_training_tuples(poses, scans, pos_threshold: float = 2., neg_thresh
     positives_poses[j] = ICP(cloud i -> cloud j) started at relative_poses(i, j); refine=False: that start itself (the
     reference's DEBUG branch).  Returns ({ndx: TrainingTuple}, stats): stats has 'pairs', 'fitness' / 'inlier_rmse' as
     {'min', 'mean', 'max'} (1. without refinement, as the reference reports), 'status_counts' {ICP status: pairs} and
-    'pose_status_counts'.  T, fitness, rmse and status of all pairs come back in ONE device-to-host copy at the end."""
+    'pose_status_counts'.  T, fitness, rmse and status of all pairs come back in ONE device-to-host copy at the end.
+    point2plane: the point-to-plane estimator, on normals of each chunk's gathered target clouds (`estimate_normals`, knn
+    neighbours); the normals of a cloud do not depend on the chunk it is gathered into."""
     _check_poses("generate_training_tuples", poses)
     n = int(poses.shape[0])
     if not 1 <= int(pairs_per_call) <= MAX_BATCH:
@@ -419,8 +422,9 @@ def generate_training_tuples(poses, scans, pos_threshold: float = 2., neg_thresh
         for lo in range(0, n_pairs, int(pairs_per_call)):
             hi = min(lo + int(pairs_per_call), n_pairs)
             src, tgt = bank.gather(idx_a[lo:hi]), bank.gather(idx_b[lo:hi])
+            nrm = _reg.estimate_normals(tgt["points"], tgt["offsets"], knn)["normals"] if point2plane else None
             r = _reg.icp_pairs(src["points"], src["offsets"], tgt["points"], tgt["offsets"], T_init[lo:hi],
-                               inlier_dist_threshold, max_iteration)
+                               inlier_dist_threshold, max_iteration, tgt_normals=nrm)
             result[lo:hi, :16] = r["T"].reshape(hi - lo, 16)
             result[lo:hi, 16] = r["fitness"]
             result[lo:hi, 17] = r["inlier_rmse"]

@@ -662,6 +662,47 @@ int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_offsets
                     int32_t* status, double* T_trace, double* eval_trace, int32_t* corr, void* scratch, int64_t scratch_bytes,
                     void* stream);
 
+/* ------------------------------------------------------------------ point-to-plane ICP: surface normals and the 6-DoF solve
+ * the other estimator of icp() (misc/point_clouds.py:31-62, point2plane=True): estimate_normals(KDTreeSearchParamKNN(knn=20))
+ * on the downsampled clouds, then registration_icp with TransformationEstimationPointToPlane.  Restated from Open3D's
+ * documentation [recall] like the block above.  Deliberate difference: only the TARGET's normals are computed, point-to-plane
+ * never reads the source's.  fp64, no floating-point atomics, fixed summation orders: a cloud's or pair's result has the same
+ * bits alone, in any batch and at any batch position. */
+enum { EGONN_ICP_STATUS_SINGULAR = 16 };  /* plane: a pivot of the 6 x 6 solve is not > 2^-40 of A's diagonal entry, or the
+                                           * step is not finite (one plane, a corridor): the loop stopped with T unchanged */
+enum { EGONN_NORMALS_STATUS_FEW_POINTS = 1,   /* the cloud has fewer than knn points: every list holds the whole cloud */
+       EGONN_NORMALS_STATUS_RANGE = 2 };      /* a non-finite coordinate: every normal of the cloud is (0,0,1) */
+/* Surface normals of n_clouds resident clouds: points (n,3) f64 concatenated (the layout egonn_voxel_downsample returns; n is
+ * a CAPACITY), DEVICE int64 offsets (n_clouds+1), knn in [3, 32].
+ * Neighbours of a point: all points of the same cloud, itself included, ordered by (d2, index) ascending with
+ * d2 = (dx*dx + dy*dy) + dz*dz; the first m = min(knn, cloud size) are taken (an exact search).  mean = (sum q) / m and
+ * C = sum (q - mean)(q - mean)^T / m, both summed in neighbour order.  The normal is the unit eigenvector of C's smallest
+ * eigenvalue (cyclic Jacobi, fixed schedule), flipped so that n . p <= 0 (toward the sensor at the origin of the cloud's
+ * frame); if n . p == 0 its first non-zero component is positive.  m < 3, a largest eigenvalue that is not > 0 or a non-finite
+ * value gives (0,0,1).
+ * Outputs: normals (n,3) f64, status (n_clouds) DEVICE int32 (EGONN_NORMALS_STATUS_* bits).  Nullable debug tables: neighbors
+ * (n, knn) int32 = index inside the cloud in the order above, -1 beyond m (all -1 in a RANGE cloud); eigenvalues (n,3)
+ * ascending (0 in a RANGE cloud).  Rows outside every cloud are not written.
+ * scratch: egonn_estimate_normals_scratch_bytes(n, n_clouds) bytes (-1 on bad arguments), 256-byte aligned.  No host
+ * synchronisation, capturable. */
+int64_t egonn_estimate_normals_scratch_bytes(int64_t n, int n_clouds);
+int egonn_estimate_normals(const double* points, int64_t n, const int64_t* offsets, int n_clouds, int knn, double* normals,
+                           int32_t* status, int32_t* neighbors, double* eigenvalues, void* scratch, int64_t scratch_bytes,
+                           void* stream);
+/* Point-to-plane ICP: the arguments of egonn_icp_pairs plus tgt_normals (n_tgt,3) f64 (required; what egonn_estimate_normals
+ * returns for tgt).  The evaluation (nearest target by POINT distance, strict < max_dist, fitness and rmse from point
+ * distances), the stop rule and the trace tables are those of egonn_icp_pairs.  Round k: for each correspondence (i, j)
+ * vs = T_k s_i, r = (vs - t_j) . n_j, J = [vs x n_j, n_j]; A = sum J J^T, b = sum J r; A x = -b by LDL^T without pivoting;
+ * U = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)]; T_k+1 = U T_k.  Before a round: fewer than 6 correspondences stop the loop with
+ * FEW_CORR, a pivot d_i that is not > 2^-40 A_ii or a non-finite x with SINGULAR, T unchanged in both cases.
+ * scratch: egonn_icp_plane_scratch_bytes(n_src, n_tgt, n_pairs) bytes (-1 on bad arguments), 256-byte aligned. */
+int64_t egonn_icp_plane_scratch_bytes(int64_t n_src, int64_t n_tgt, int n_pairs);
+int egonn_icp_plane_pairs(const double* src, int64_t n_src, const int64_t* src_offsets, const double* tgt, int64_t n_tgt,
+                          const int64_t* tgt_offsets, const double* tgt_normals, int n_pairs, const double* T_init, double max_dist,
+                          int max_iteration, double eps_fitness, double eps_rmse, double* T, double* fitness, double* inlier_rmse,
+                          int32_t* iterations, int32_t* status, double* T_trace, double* eval_trace, int32_t* corr, void* scratch,
+                          int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ training augmentation of a resident scan batch
  * replaces TrainTransform (datasets/augmentation.py:10-30, called per scan by datasets/base_datasets.py:70-76),
  * TrainSetTransform (:33-48, called per batch by datasets/dataset_utils.py:67-72) and the rigid perturbation of the local
