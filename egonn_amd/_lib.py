@@ -9,6 +9,7 @@ import ctypes as C
 import os
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -94,6 +95,10 @@ _SIGS = [
     ("egonn_local_loss", C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int] + [_P] * 13 +
                                   [C.POINTER(C.c_float)] + [_P] * 9 + [C.c_int64, _P]),
     ("egonn_dense", C.c_int, [_P, C.c_int64, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    ("egonn_dense_pack_fragments", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    ("egonn_dense_pack_fragments_host", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
+    ("egonn_debug_dense", C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int,
+                                    _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     ("egonn_dense_backward_weight", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, _P, _P, C.c_int64, _P]),
     ("egonn_conv_backward_weight", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P,
                                              C.c_int64, _P]),
@@ -273,6 +278,38 @@ def concat_clouds(clouds, dev):
         off.append(off[-1] + c.shape[0])
     pts = torch.cat([c.to(device=dev, dtype=torch.float32) for c in ts]) if ts else torch.zeros((0, 3), device=dev)
     return pts, torch.tensor(off, dtype=torch.int64, device=dev)
+
+
+def dense_pack_fragments(weight, out_in: bool):
+    """egonn_dense_pack_fragments(_host): a 1x1 kernel ((cin, cout), or (cout, cin) with out_in) in the dense kernels' LDS fragment
+    order, cin * cout floats.  A numpy array is packed on the host (no device needed), a device tensor on the device."""
+    lib = load()
+    co, ci = (weight.shape if out_in else weight.shape[::-1])
+    if isinstance(weight, np.ndarray):
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        out = np.empty(ci * co, dtype=np.float32)
+        check(lib.egonn_dense_pack_fragments_host(w.ctypes.data, int(bool(out_in)), int(ci), int(co), out.ctypes.data))
+        return out
+    w = weight.contiguous()
+    out = torch.empty(ci * co, dtype=torch.float32, device=w.device)
+    call(w.device, lib.egonn_dense_pack_fragments, w.data_ptr(), int(bool(out_in)), int(ci), int(co), out.data_ptr())
+    return out
+
+
+def debug_dense(x, weight, out_in: bool, out, form: int, n_dev=None, packed=None, bias=None, scale=None, shift=None, act: int = 0,
+                residual=None, gate=None, boff=None):
+    """test hook (egonn_debug_dense): the forward's dense launcher on device tensors.  x (capacity, cin) and residual / out
+    (capacity, cout) are fp32 or bf16 maps (by dtype); rows from n_dev[0] on are left as they are in `out`.  form 0 = the
+    persistent LDS kernel, 1 = the streaming form (with `packed` from dense_pack_fragments, or gathering the weights)."""
+    lib = load()
+    cap, cin = x.shape
+    cout = out.shape[1]
+    B = 0 if boff is None else boff.numel() - 1
+    bf = lambda t: int(t is not None and t.dtype == torch.bfloat16)
+    call(x.device, lib.egonn_debug_dense, x.data_ptr(), bf(x), int(cap), _ptr(n_dev), int(cin), int(cout), weight.data_ptr(),
+         int(bool(out_in)), _ptr(packed), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(residual), bf(residual), _ptr(gate),
+         _ptr(boff), B, out.data_ptr(), bf(out), int(form))
+    return out
 
 
 def debug_radix_sort(keys_in, vals_in, keys_out, vals_out, n: int, nbits: int, n_dev=None, seg_offsets=None, idx_bits: int = 0,

@@ -237,6 +237,7 @@ struct Switches {
   bool no_task_order;      // EGONN_NO_TASK_ORDER        sparse-conv tasks in table order instead of longest-first (RowGroups::order4)
   bool flat_sort, sort_pairs;   // EGONN_FLAT_SORT / EGONN_SORT_PAIRS  plan sort on flat (batch | Morton) keys / on (key, value) pairs
   bool no_search67;        // EGONN_NO_SEARCH67          k=3 maps of levels 6-7 derived from levels 8-9 instead of searched
+  bool no_dense_stream;    // EGONN_NO_DENSE_STREAM      1x1 convolutions on >= 8192 rows on the persistent LDS kernel instead of its streaming form
   int split_max_level;     // EGONN_SPLIT_MAX_LEVEL=l    replaces a context's split level limit (unless that is -1: exact fp32); -1 = unset
   int split_max_level_k8;  // EGONN_SPLIT_MAX_LEVEL_K8=l the limit of the 8-slot maps (k=2,s=2 and transposed) alone; -1 = unset
   int split_cfg;           // EGONN_SPLIT_CFG=cfg        workgroup shape of the lock-step split kernel (sconv_split_forward); 0 = unset

@@ -36,6 +36,7 @@ const Switches& switches() {
                     .no_fused_ghead = on("EGONN_NO_FUSED_GHEAD"), .no_split_heads = on("EGONN_NO_SPLIT_HEADS"),
                     .no_tail_split = on("EGONN_NO_TAIL_SPLIT"), .no_task_order = on("EGONN_NO_TASK_ORDER"),
                     .flat_sort = on("EGONN_FLAT_SORT"), .sort_pairs = on("EGONN_SORT_PAIRS"), .no_search67 = on("EGONN_NO_SEARCH67"),
+                    .no_dense_stream = on("EGONN_NO_DENSE_STREAM"),
                     .split_max_level = num("EGONN_SPLIT_MAX_LEVEL", -1), .split_max_level_k8 = num("EGONN_SPLIT_MAX_LEVEL_K8", -1),
                     .split_cfg = num("EGONN_SPLIT_CFG", 0), .rg_first_pass = num("EGONN_RG_FIRST_PASS", 0),
                     .ksplit = {getenv("EGONN_KSPLIT"), getenv("EGONN_KSPLIT8"), getenv("EGONN_KSPLIT_KW"), getenv("EGONN_KSPLIT_KW8"),

@@ -415,6 +415,184 @@ __global__ __launch_bounds__(256) void dense_lds_kernel(const void* __restrict__
   }
 }
 
+// Float j of a 1x1 kernel's packed fragment buffer (the LDS image of the two kernels around this comment, whole kernel, cb0 = 0):
+//   packed[((nt * cin/16 + t) * 64 + lane) * 4 + u] = W(ci = 16 t + 4 (lane >> 4) + u, col = 16 nt + (lane & 15))
+// -> its index in the caller's weights.  One function behind the device packer, the host packer and the on-the-fly staging.
+__host__ __device__ static inline int64_t dense_frag_src(int64_t j, int w_out_in, int cin, int cout) {
+  const int u = (int)(j & 3), ln = (int)((j >> 2) & 63), ft = (int)(j >> 8), ks = cin / 16;
+  const int nt = ft / ks, t = ft - nt * ks;
+  const int ci = 16 * t + 4 * (ln >> 4) + u, col = 16 * nt + (ln & 15);
+  return w_out_in ? (int64_t)col * cin + ci : (int64_t)ci * cout + col;
+}
+__global__ void dense_pack_kernel(const float* __restrict__ W, int w_out_in, int cin, int cout, float* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < (int64_t)cin * cout) out[j] = W[dense_frag_src(j, w_out_in, cin, cout)];
+}
+int dense_pack_frags(const float* W, int w_out_in, int cin, int cout, float* out, hipStream_t stream) {
+  EGONN_REQUIRE(W && out && cin >= 16 && cin % 16 == 0 && cout >= 16 && cout % 16 == 0, EGONN_ERR_INVALID,
+                "dense pack: %d->%d (multiples of 16 expected)", cin, cout);
+  hipLaunchKernelGGL(dense_pack_kernel, dim3((unsigned)cdiv((int64_t)cin * cout, 256)), dim3(256), 0, stream, W, w_out_in ? 1 : 0, cin,
+                     cout, out);
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}
+
+// Streaming form of dense_lds_kernel: ONE 16-row tile per wave, the grid sized from the capacity alone, and every request of the
+// tile — the staged weights (packed at egonn_model_finalize: coalesced 16-byte loads; else gathered from the caller's layout), the
+// epilogue vectors, the scan offsets, the input rows and the residual rows of all COUT/16 column tiles — issued before the first
+// wait.  The scan of a row is searched in an LDS copy of boff, and the gate rows are requested before the first MFMA.  dense_lds_kernel
+// keeps 2 waves per SIMD with 2 KB each in flight and walks a chain of dependent round trips per tile (rows -> search in global
+// memory -> residual -> gate -> store); here a CU holds 16 waves with 6-12 KB each in flight.  Same MFMA sequence per tile, same
+// epilogue expression => bitwise the results of dense_lds_kernel.  Rows between the live count and the capacity are neither read
+// nor written.
+// ACT_ANY = false: act is ACT_NONE or ACT_RELU (every 1x1 convolution of the forward) — the unrolled epilogue then carries no
+// COUT/4 copies of tanhf / log1pf / expf.
+template <int CIN, int COUT, bool IN_BF16, bool ACT_ANY>
+__global__ __launch_bounds__(256, 4) void dense_stream_kernel(const void* __restrict__ in_v, int64_t n, const float* __restrict__ W,
+                                                           int w_out_in, const float* __restrict__ wfrag,
+                                                           const float* __restrict__ bias, const float* __restrict__ scale,
+                                                           const float* __restrict__ shift, int act,
+                                                           const void* __restrict__ residual_v, void* __restrict__ out_v, int io,
+                                                           const int32_t* __restrict__ n_dev, const float* __restrict__ gate,
+                                                           const int32_t* __restrict__ boff, int B) {
+  extern __shared__ __attribute__((aligned(16))) f32x4 ds_frags[];
+  constexpr int KS = CIN / 16, NT = COUT / 16, NFRAG = NT * KS * 64, PER = NFRAG / 256;
+  static_assert(NFRAG % 256 == 0, "whole fragments per thread");
+  float* const s_vec = reinterpret_cast<float*>(ds_frags + NFRAG);           // [3][COUT]: bias, scale, shift
+  int32_t* const s_boff = reinterpret_cast<int32_t*>(s_vec + 3 * COUT);      // [B + 1]
+  if (n_dev) n = min((int64_t)*n_dev, n);
+  if (!gate) B = 0;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, g4 = lane >> 4;
+  // Every load below is unconditional — null pointers are replaced by W (cin * cout floats: every dummy index stays inside it) and
+  // rows past the live count by the last live row — so that the requests are one straight line followed by one wait (guarded
+  // loads compiled into a branch, a wait and, under the register bound, a spill per load: see dense_small_body).
+  // ---- requests: weights (without a packed copy the same bytes of W, overwritten below), vectors, scan offsets
+  f32x4 st[PER];
+  {
+    const f32x4* src = reinterpret_cast<const f32x4*>(wfrag ? wfrag : W);
+#pragma unroll
+    for (int u = 0; u < PER; ++u) st[u] = src[tid + u * 256];
+  }
+  const int vi = min(tid, COUT - 1);
+  float vb = (bias ? bias : W)[vi], vs = (scale ? scale : W)[vi], vh = (scale ? shift : W)[vi];
+  const int32_t vo = (gate ? boff : reinterpret_cast<const int32_t*>(W))[gate ? min(tid, B) : 0];
+  // ---- requests: this wave's tile (raw bits; bf16 rows are widened after the barrier)
+  const int64_t row = ((int64_t)blockIdx.x * 4 + wave) * 16 + l15;
+  const bool ok = row < n;
+  const int64_t rowc = min(row, max(n, (int64_t)1) - 1);
+  f32x4 a[KS], r[NT];
+#pragma unroll
+  for (int t = 0; t < KS; ++t) {
+    if constexpr (IN_BF16) {
+      const uint2 h = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(in_v) + rowc * CIN + 16 * t + 4 * g4);
+      a[t] = (f32x4){__uint_as_float(h.x), __uint_as_float(h.y), 0.f, 0.f};
+    } else {
+      a[t] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(in_v) + rowc * CIN + 16 * t + 4 * g4);
+    }
+  }
+  {
+    const void* rp = residual_v ? residual_v : static_cast<const void*>(W);
+    const int64_t r0 = (residual_v ? rowc * COUT : 0) + 4 * g4;
+    if (io & 1) {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const uint2 h = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(rp) + r0 + 16 * nt);
+        r[nt] = (f32x4){__uint_as_float(h.x), __uint_as_float(h.y), 0.f, 0.f};
+      }
+    } else {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) r[nt] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(rp) + r0 + 16 * nt);
+    }
+  }
+  // ---- LDS image
+#pragma unroll
+  for (int u = 0; u < PER; ++u) ds_frags[tid + u * 256] = st[u];
+  if (!wfrag) {      // no packed copy (stand-alone callers): gathered from the caller's layout, one fragment per thread at a time
+#pragma unroll 1
+    for (int i = tid; i < NFRAG; i += 256) {
+      f32x4 v;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = W[dense_frag_src((int64_t)i * 4 + k, w_out_in, CIN, COUT)];
+      ds_frags[i] = v;
+    }
+  }
+  if (tid < COUT) {
+    s_vec[tid] = bias ? vb : 0.f;
+    s_vec[COUT + tid] = scale ? vs : 1.f;
+    s_vec[2 * COUT + tid] = scale ? vh : 0.f;
+  }
+  if (tid <= B) s_boff[tid] = vo;
+  for (int i = tid + 256; i <= B; i += 256) s_boff[i] = boff[i];     // (batches of 256 scans and more; B = 0 without a gate)
+  __syncthreads();
+  if (((int64_t)blockIdx.x * 4 + wave) * 16 >= n) return;
+  // ---- scan of the row (last b with boff[b] <= row) from the LDS copy, then the gate rows: L2 hits, in flight under the MFMAs' operands
+  f32x4 gq[NT];
+  {
+    int lo = 0, hi = gate ? B : 0;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (s_boff[mid] <= (int32_t)row) lo = mid; else hi = mid;
+    }
+    const float* gp = (gate ? gate : W) + ((gate && ok) ? (int64_t)lo * COUT : 0) + 4 * g4;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) gq[nt] = *reinterpret_cast<const f32x4*>(gp + 16 * nt);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (IN_BF16) {
+#pragma unroll
+    for (int t = 0; t < KS; ++t) {
+      const uint32_t hx = __float_as_uint(a[t][0]), hy = __float_as_uint(a[t][1]);
+      a[t] = (f32x4){bf2f(hx & 0xFFFFu), bf2f(hx >> 16), bf2f(hy & 0xFFFFu), bf2f(hy >> 16)};
+    }
+  }
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const f32x4* fr = ds_frags + nt * KS * 64 + lane;
+#pragma unroll
+    for (int t = 0; t < KS; ++t) {
+      const f32x4 wf = fr[t * 64];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[u], a[t][u], acc, 0, 0, 0);
+    }
+    if (ok) {
+      const int c0 = 16 * nt + 4 * g4;
+      f32x4 v = acc + *reinterpret_cast<const f32x4*>(s_vec + c0);
+      v = v * *reinterpret_cast<const f32x4*>(s_vec + COUT + c0) + *reinterpret_cast<const f32x4*>(s_vec + 2 * COUT + c0);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = ACT_ANY ? apply_act(v[u], act) : (act == ACT_RELU ? fmaxf(v[u], 0.f) : v[u]);
+      if (residual_v) {
+        f32x4 rr = r[nt];
+        if (io & 1) {
+          const uint32_t hx = __float_as_uint(rr[0]), hy = __float_as_uint(rr[1]);
+          rr = (f32x4){bf2f(hx & 0xFFFFu), bf2f(hx >> 16), bf2f(hy & 0xFFFFu), bf2f(hy >> 16)};
+        }
+        if (gate) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float d = (io & 2) ? bf2f(f2bf_rn(v[u])) : v[u];     // (see dense_lds_kernel)
+            v[u] = fmaxf(rr[u] * gq[nt][u] + d, 0.f);
+          }
+        } else {
+          v += rr;
+        }
+      }
+      if (io & 2) {
+        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out_v) + row * COUT + c0) =
+            make_uint2(f2bf_rn(v[0]) | (f2bf_rn(v[1]) << 16), f2bf_rn(v[2]) | (f2bf_rn(v[3]) << 16));
+      } else {
+        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out_v) + row * COUT + c0) = v;
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// shapes of the streaming form: whole fragments per thread, all of a tile's requests in registers, four workgroups to a CU
+static bool dense_stream_shape(int64_t n, int cin, int cout) {
+  return n >= 8192 && (cin == 32 || cin == 64 || cin == 128) && (cout == 64 || cout == 128) && (size_t)cin * cout * sizeof(float) <= 32 * 1024;
+}
+
 __global__ void dense_any_kernel(const float* __restrict__ in, int64_t total, int cin, const float* __restrict__ W,
                                  int w_out_in, int cout, const float* __restrict__ bias, int act, float* __restrict__ out,
                                  const int32_t* __restrict__ n_dev) {
@@ -437,12 +615,40 @@ bool dense_gate_fusable(int64_t n, int cin, int cout) {
 int dense_forward_ex(const void* in, int in_bf16, int64_t n, int cin, const float* W, int w_out_in, int cout,
                      const float* bias, const float* scale, const float* shift, int act, const void* residual, int res_bf16,
                      void* out, int out_bf16, hipStream_t stream, const int32_t* n_dev, const float* gate, const int32_t* boff,
-                     int B) {
+                     int B, const float* wfrag, int form) {
   if (n == 0) return EGONN_OK;
   EGONN_REQUIRE(!gate || (residual && boff && B >= 1 && dense_gate_fusable(n, cin, cout)), EGONN_ERR_INVALID,
                 "dense: the fused gated residual needs the LDS-staged kernel (%lld rows, %d->%d)", (long long)n, cin, cout);
+  EGONN_REQUIRE(form != 1 || dense_stream_shape(n, cin, cout), EGONN_ERR_INVALID, "dense: no streaming form for %lld rows, %d->%d",
+                (long long)n, cin, cout);
   const dim3 grid((unsigned)cdiv(n, 64), (unsigned)cdiv(cout, 64));
   const int io = (res_bf16 ? 1 : 0) | (out_bf16 ? 2 : 0);
+  // the streaming form: a function of (rows, cin, cout) alone (form -1 = this rule, 0 / 1 = tests and measurements)
+  if (form == 1 || (form < 0 && !switches().no_dense_stream && dense_stream_shape(n, cin, cout))) {
+    const unsigned g1 = (unsigned)cdiv(cdiv(n, 16), 4);                   // one tile per wave: from the capacity alone
+    const size_t lds = (size_t)cin * cout * sizeof(float) + 3 * (size_t)cout * sizeof(float) + ((size_t)(gate ? B : 0) + 1) * sizeof(int32_t);
+    const bool act_any = act != ACT_NONE && act != ACT_RELU;
+#define EGONN_DENSE_STREAM_LAUNCH(CI, CO, INB, ANY)                                                                                  \
+  if ((in_bf16 != 0) == INB && act_any == ANY)                                                                                       \
+    hipLaunchKernelGGL((dense_stream_kernel<CI, CO, INB, ANY>), dim3(g1), dim3(256), lds, stream, in, n, W, w_out_in, wfrag, bias,  \
+                       scale, shift, act, residual, out, io, n_dev, gate, boff, B);
+#define EGONN_DENSE_STREAM_CASE(CI, CO)                                                                                              \
+  if (cin == CI && cout == CO) {                                                                                                     \
+    EGONN_DENSE_STREAM_LAUNCH(CI, CO, true, true)                                                                                    \
+    EGONN_DENSE_STREAM_LAUNCH(CI, CO, true, false)                                                                                   \
+    EGONN_DENSE_STREAM_LAUNCH(CI, CO, false, true)                                                                                   \
+    EGONN_DENSE_STREAM_LAUNCH(CI, CO, false, false)                                                                                  \
+    HIP_CHECK(hipGetLastError());                                                                                                    \
+    return EGONN_OK;                                                                                                                 \
+  }
+    EGONN_DENSE_STREAM_CASE(32, 64)
+    EGONN_DENSE_STREAM_CASE(32, 128)
+    EGONN_DENSE_STREAM_CASE(64, 64)
+    EGONN_DENSE_STREAM_CASE(64, 128)
+    EGONN_DENSE_STREAM_CASE(128, 64)
+#undef EGONN_DENSE_STREAM_CASE
+#undef EGONN_DENSE_STREAM_LAUNCH
+  }
   const size_t frag_bytes = (size_t)cin * cout * sizeof(float);
   // weights resident in LDS, workgroups persistent over the row tiles; weight sets above 96 KB (the 192 -> 256 layer of the
   // global decoder) are split over grid.y into column blocks that fit
@@ -1536,3 +1742,26 @@ int select_topk(const float* sigma, const int32_t* boff_dev, int B, int k, const
 }
 
 }  // namespace egonn
+
+using namespace egonn;
+
+// ------------------------------------------------------------------ 1x1 kernels in fragment order; the dense launcher with everything explicit
+API int egonn_dense_pack_fragments(const float* weight, int weight_out_in, int cin, int cout, float* packed, void* stream) {
+  return dense_pack_frags(weight, weight_out_in, cin, cout, packed, (hipStream_t)stream);
+}
+API int egonn_dense_pack_fragments_host(const float* weight, int weight_out_in, int cin, int cout, float* packed) {
+  EGONN_REQUIRE(weight && packed && cin >= 16 && cin % 16 == 0 && cout >= 16 && cout % 16 == 0, EGONN_ERR_INVALID,
+                "dense pack: %d->%d (multiples of 16 expected)", cin, cout);
+  for (int64_t j = 0; j < (int64_t)cin * cout; ++j) packed[j] = weight[dense_frag_src(j, weight_out_in ? 1 : 0, cin, cout)];
+  return EGONN_OK;
+}
+API int egonn_debug_dense(const void* in, int in_bf16, int64_t rows_capacity, const int32_t* n_dev, int cin, int cout, const float* weight,
+                          int weight_out_in, const float* packed, const float* bias, const float* scale, const float* shift, int act,
+                          const void* residual, int res_bf16, const float* gate, const int32_t* boff, int B, void* out, int out_bf16,
+                          int form, void* stream) {
+  EGONN_REQUIRE(in && weight && out && rows_capacity >= 0 && cin >= 1 && cout >= 1 && act >= 0 && act <= 4 && (form == 0 || form == 1) &&
+                    (!scale == !shift) && (form == 1 || !packed),
+                EGONN_ERR_INVALID, "debug_dense: bad arguments");
+  return dense_forward_ex(in, in_bf16 ? 1 : 0, rows_capacity, cin, weight, weight_out_in ? 1 : 0, cout, bias, scale, shift, act, residual,
+                          res_bf16 ? 1 : 0, out, out_bf16 ? 1 : 0, (hipStream_t)stream, n_dev, gate, boff, B, packed, form);
+}

@@ -109,7 +109,12 @@ bool dense_gate_fusable(int64_t n, int cin, int cout);
 int dense_forward_ex(const void* in, int in_bf16, int64_t n, int cin, const float* W, int w_out_in, int cout,
                      const float* bias, const float* scale, const float* shift, int act, const void* residual, int res_bf16,
                      void* out, int out_bf16, hipStream_t stream, const int32_t* n_dev = nullptr, const float* gate = nullptr,
-                     const int32_t* boff = nullptr, int B = 0);   // gate: out = relu(residual * gate[sample][col] + layer output)
+                     const int32_t* boff = nullptr, int B = 0,    // gate: out = relu(residual * gate[sample][col] + layer output)
+                     const float* wfrag = nullptr, int form = -1);
+// wfrag (nullable): the kernel in fragment order (dense_pack_frags), read by the streaming form instead of gathering W per workgroup.
+// form: -1 = the product rule (streaming form for >= 8192 rows, cin in {32, 64, 128}, cout in {64, 128}, cin * cout * 4 <= 32 KB,
+// unless EGONN_NO_DENSE_STREAM), 0 = never the streaming form, 1 = the streaming form (an error for other shapes): bitwise the same
+int dense_pack_frags(const float* W, int w_out_in, int cin, int cout, float* out, hipStream_t stream);   // cin * cout floats
 int bn_fold(const float* w, const float* b, const float* rm, const float* rv, float eps, int c, float* scale,
             float* shift, hipStream_t stream);
 // n_dev (nullable, here and below): device-resident row count (<= n); n then only sizes the grid

@@ -79,6 +79,7 @@ struct egonn_model {
   void* lh_pack = nullptr;      // local_heads_pack: the heads' six Linear kernels as fp16 hi | lo fragments (92 KB)
   const float** lh_ptrs = nullptr;   // device array of the six weight pointers (the packer's input)
   egonn::PackedKernel pk_convs[8], pk_c1[8], pk_c2[8], pk_gt[8], pk_lt[8];   // fp32, bf16 (EGONN_FLAG_BF16) and fp16-split forms
+  const float *pk_down[8] = {}, *pk_l1x1[8] = {};   // blk[i].down / l1x1[l] in the dense kernels' fragment order (dense_pack_frags), in `packed`
   egonn::MinkFpnModel* fpn = nullptr;   // egonn_minkfpn_finalize: the MinkFPN view of the same tensors (minkfpn.hip)
 };
 

@@ -714,6 +714,10 @@ API int egonn_model_finalize(egonn_model* m, void* stream) {
       need_p += (size_t)8 * b.cin * b.cin + (size_t)27 * b.cin * b.cout + (size_t)27 * b.cout * b.cout;
     }
     need_p += (size_t)2 * 8 * GLOBAL_CH * GLOBAL_CH + (size_t)8 * LOCAL_CH * LOCAL_CH;
+    // + the 1x1 kernels the forward runs through the streaming dense kernel, in its LDS fragment order (fp32 only)
+    for (int i = 1; i <= 7; ++i)
+      if (m->blk[i].down) need_p += (size_t)m->blk[i].cin * m->blk[i].cout;
+    for (int l : {3, 4}) need_p += (size_t)PLANES[l - 1] * LOCAL_CH;
     if (m->packed_cap < need_p) {
       if (m->packed) HIP_CHECK(hipFree(m->packed));
       HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->packed), (3 * need_p + 512) * sizeof(float)));
@@ -744,6 +748,19 @@ API int egonn_model_finalize(egonn_model* m, void* stream) {
     EGONN_TRY(pack2(m->gt[6], 8, GLOBAL_CH, GLOBAL_CH, &m->pk_gt[6]));
     EGONN_TRY(pack2(m->gt[7], 8, GLOBAL_CH, GLOBAL_CH, &m->pk_gt[7]));
     EGONN_TRY(pack2(m->lt[4], 8, LOCAL_CH, LOCAL_CH, &m->pk_lt[4]));
+    auto pack1 = [&](const float* w, int ci, int co, const float** dst) -> int {
+      *dst = nullptr;
+      if (ci % 16 || co % 16) return EGONN_OK;
+      EGONN_TRY(dense_pack_frags(w, 0, ci, co, pc, st));
+      *dst = pc;
+      pc += (size_t)ci * co;
+      return EGONN_OK;
+    };
+    for (int i = 1; i <= 7; ++i) {
+      m->pk_down[i] = nullptr;
+      if (m->blk[i].down) EGONN_TRY(pack1(m->blk[i].down, m->blk[i].cin, m->blk[i].cout, &m->pk_down[i]));
+    }
+    for (int l : {3, 4}) EGONN_TRY(pack1(m->l1x1[l], PLANES[l - 1], LOCAL_CH, &m->pk_l1x1[l]));
   }
   if (!m->conv0_unit) HIP_CHECK(hipMalloc(&m->conv0_unit, 2 * 4 * 3 * 64 * 16));
   EGONN_TRY(conv0_pack_unit(m->conv0, m->conv0_unit, st));
@@ -887,7 +904,7 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
     const int64_t n3 = P.cap[3], n4 = P.cap[4];
     FALLOC(l4, n4 * LOCAL_CH);
     EGONN_TRY(dense_forward_ex(x[4], bf16, n4, 128, m->l1x1[4], 0, LOCAL_CH, nullptr, nullptr, nullptr, ACT_NONE, nullptr, 0, l4,
-                               bf16, st, cnt + 4));
+                               bf16, st, cnt + 4, nullptr, nullptr, 0, m->pk_l1x1[4]));
     FALLOC(u3, n3 * LOCAL_CH);
     EGONN_TRY(conv_layer(c, st, conv_call(2, 3, l4, m->pk_lt[4], LOCAL_CH, LOCAL_CH, bf16, nullptr, 0, u3), "tconv"));
     EGONN_REQUIRE(m->ldec.cin == 64 && m->ldec.mid == 96 && m->ldec.cout == 128 && m->kp.mid == 32 && m->sg.mid == 32,
@@ -905,7 +922,8 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
       return EGONN_OK;
     }
     WALLOC(l3, n3 * LOCAL_CH);
-    EGONN_TRY(dense_forward_ex(x[3], bf16, n3, 64, m->l1x1[3], 0, LOCAL_CH, nullptr, nullptr, nullptr, ACT_NONE, u3, bf16, l3, 0, st, cnt + 3));
+    EGONN_TRY(dense_forward_ex(x[3], bf16, n3, 64, m->l1x1[3], 0, LOCAL_CH, nullptr, nullptr, nullptr, ACT_NONE, u3, bf16, l3, 0, st, cnt + 3,
+                               nullptr, nullptr, 0, m->pk_l1x1[3]));
     EGONN_TRY(local_heads_forward(l3, n3, cnt + 3, hw, P.lv[3].keys, 3, P.coord_bits, quant_mode, step,
                                   (flags & EGONN_FLAG_IGNORE_KP_REGRESSOR) ? 1 : 0, out_desc, out_kp, out_sigma, st, nullptr, nullptr, 0,
                                   lh_pack, c->dev_fp16_flag));
@@ -971,12 +989,12 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
       // tail in ONE launch — out = relu(t2 * gate[scan] + bn(y @ Wd)); the branch output never goes to memory (bitwise the result
       // of the two launches it replaces)
       EGONN_TRY(dense_forward_ex(y, bf16, n, b.cin, b.down, 0, b.cout, nullptr, b.dn.scale, b.dn.shift, ACT_NONE, t2, bf16, xo,
-                                 bf16, st, cnt + i, gate, L.boff, B));
+                                 bf16, st, cnt + i, gate, L.boff, B, m->pk_down[i]));
     } else {
       if (b.down) {
         FALLOC(rd, n * b.cout);
         EGONN_TRY(dense_forward_ex(y, bf16, n, b.cin, b.down, 0, b.cout, nullptr, b.dn.scale, b.dn.shift, ACT_NONE, nullptr, 0, rd,
-                                   bf16, st, cnt + i));
+                                   bf16, st, cnt + i, nullptr, nullptr, 0, m->pk_down[i]));
         res = rd;
       }
       EGONN_TRY(eca_apply_gate(t2, res, gate, L.boff, B, n, b.cout, xo, bf16, st));

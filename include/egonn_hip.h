@@ -453,6 +453,23 @@ enum { EGONN_ACT_NONE = 0, EGONN_ACT_RELU = 1, EGONN_ACT_TANH = 2, EGONN_ACT_SOF
  * layout (swap the flag). */
 int egonn_dense(const float* x, int64_t n, int cin, const float* weight, int weight_out_in, const float* bias, int cout,
                 int act, float* out, void* stream);
+/* A 1x1 kernel (cin, cout multiples of 16; either layout) in the MFMA fragment order the dense kernels keep in LDS:
+ *   packed[((nt * cin/16 + t) * 64 + lane) * 4 + u] = Wmat[16 t + 4 (lane >> 4) + u][16 nt + (lane & 15)]      (cin * cout floats)
+ * egonn_model_finalize makes these once per model for the 1x1 convolutions of the forward; _host is the same function on host
+ * memory (no device needed). */
+int egonn_dense_pack_fragments(const float* weight, int weight_out_in, int cin, int cout, float* packed, void* stream);
+int egonn_dense_pack_fragments_host(const float* weight, int weight_out_in, int cin, int cout, float* packed);
+/* tests / measurements only: the dense launcher of the forward with everything explicit.  out[r] = act((in[r] @ Wmat + bias) * scale
+ * + shift) (+ residual[r]), or with gate (B, cout) and boff (B + 1 int32 row offsets of the scans): relu(residual[r] * gate[scan of
+ * r] + that).  rows_capacity sizes the grid; n_dev (nullable, device int32) is the live row count, rows from it on are not
+ * written.  in / residual / out are bf16 maps where their flag is set.  form 0 = the persistent LDS kernel, 1 = its streaming
+ * form (>= 8192 rows, cin in {32, 64, 128}, cout in {64, 128}, cin * cout <= 8192), which reads `packed` (nullable:
+ * egonn_dense_pack_fragments of the same kernel) instead of gathering the weights.  All three compute bitwise the same rows
+ * (tests/test_gpu_dense_stream.py). */
+int egonn_debug_dense(const void* in, int in_bf16, int64_t rows_capacity, const int32_t* n_dev, int cin, int cout, const float* weight,
+                      int weight_out_in, const float* packed, const float* bias, const float* scale, const float* shift, int act,
+                      const void* residual, int res_bf16, const float* gate, const int32_t* boff, int B, void* out, int out_bf16,
+                      int form, void* stream);
 /* out (ca,cb) = a^T b over n rows: weight gradient of a dense layer (a = input, b = grad_out for the (cin,cout) layout). */
 int egonn_dense_backward_weight(const float* a, int ca, const float* b, int cb, int64_t n, float* out, float* scratch,
                                 int64_t scratch_floats, void* stream);

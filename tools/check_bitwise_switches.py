@@ -5,6 +5,8 @@
   EGONN_NO_GATED_K2S2=1  level 1's block tail as its own launch + a 23 MB map instead of being evaluated by level 2's strided convolution
   EGONN_NO_FUSED_GHEAD=1  MinkHead's three lateral 1x1 convolutions as three launches and every FPN add inside the next lateral (round 5) instead of
                           one grouped launch + the lateral as the transposed convolution's epilogue residual (fp32 maps)
+  EGONN_NO_DENSE_STREAM=1  the 1x1 convolutions on >= 8192 rows (block tails of levels 2 and 4, level-4 lateral) on the persistent LDS
+                          kernel instead of its streaming form on fragments packed at egonn_model_finalize (dense.hip)
 fp32 maps (4 scans) and bf16 maps."""
 import os, subprocess, sys, hashlib
 import numpy as np
@@ -42,7 +44,8 @@ else:
     ok = True
     for prec in ("fp32", "bf16"):
         d = []
-        for env in ({}, {"EGONN_NO_PRESPLIT": "1"}, {"EGONN_NO_FUSED_DOWN": "1"}, {"EGONN_NO_FUSED_LATERAL": "1"}, {"EGONN_NO_GATED_K2S2": "1"}, {"EGONN_NO_FUSED_GHEAD": "1"}):
+        for env in ({}, {"EGONN_NO_PRESPLIT": "1"}, {"EGONN_NO_FUSED_DOWN": "1"}, {"EGONN_NO_FUSED_LATERAL": "1"}, {"EGONN_NO_GATED_K2S2": "1"}, {"EGONN_NO_FUSED_GHEAD": "1"},
+                    {"EGONN_NO_DENSE_STREAM": "1"}):
             r = subprocess.run([sys.executable, __file__, "child"], capture_output=True, text=True,
                                env=dict(os.environ, CHECK_PRECISION=prec, **env))
             line = [l for l in r.stdout.splitlines() if l.startswith("DIGEST")]
