@@ -99,6 +99,7 @@ _SIGS = [
     ("egonn_dense_pack_fragments_host", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     ("egonn_debug_dense", C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int,
                                     _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    ("egonn_debug_dense_route", C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     ("egonn_dense_backward_weight", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, _P, _P, C.c_int64, _P]),
     ("egonn_conv_backward_weight", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P,
                                              C.c_int64, _P]),
@@ -310,6 +311,17 @@ def debug_dense(x, weight, out_in: bool, out, form: int, n_dev=None, packed=None
          int(bool(out_in)), _ptr(packed), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(residual), bf(residual), _ptr(gate),
          _ptr(boff), B, out.data_ptr(), bf(out), int(form))
     return out
+
+
+DENSE_ROUTES = ("none", "stream", "lds", "small", "tile", "plain")      # DenseRoute of egonn_amd/csrc/kernels.h, from 0
+
+
+def debug_dense_route(rows: int, cin: int, cout: int, form: int = -1, gate_scans: int = 0):
+    """test hook (egonn_debug_dense_route, no device needed): -> (route name, grid x, grid y, dynamic LDS bytes, colblk) of the
+    launch the dense launcher picks; raises its error for a form or a gate the shape does not have"""
+    out = (C.c_int32 * 5)()
+    check(load().egonn_debug_dense_route(int(rows), int(cin), int(cout), int(form), int(gate_scans), out))
+    return (DENSE_ROUTES[out[0]],) + tuple(out[1:])
 
 
 def debug_radix_sort(keys_in, vals_in, keys_out, vals_out, n: int, nbits: int, n_dev=None, seg_offsets=None, idx_bits: int = 0,

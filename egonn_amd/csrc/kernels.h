@@ -69,9 +69,6 @@ struct SconvLaunch {
   uint32_t* in_absmax = nullptr; int64_t in_elems = 0;     // split, operand autoscale: 8 bytes of scratch, the elements of `in`
 };
 int sconv_rg_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream);
-// three independent (n_i, 128) @ (128, 128) products in one launch (dense.hip)
-int dense_small_group3(const float* const* in, const int64_t* n, const int32_t* const* n_dev, const float* const* W, float* const* out,
-                       hipStream_t stream);
 int sconv_map(Ctx* ctx, const ConvCall& c, hipStream_t stream);
 // sconv_split.hip: fp32 maps on the fp16 matrix pipe (two-way split operands, three products, fp32 accumulate)
 bool sconv_split_supported(int cin, int cout);
@@ -99,22 +96,63 @@ int conv0_pack_unit(const float* W, void* wpk, hipStream_t stream);   // 24 KB: 
 
 // dense.hip ------------------------------------------------------------------------------------
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_SOFTPLUS = 3, ACT_SIGMOID = 4 };
-// out[r][:] = act( (in[r] @ Wmat + bias) * scale + shift ) (+ residual[r])
-//   w_out_in = 0: Wmat = W[cin][cout] (ME 1x1 kernel layout) ; 1: Wmat = W[cout][cin]^T (nn.Linear layout)
-int dense_forward(const float* in, int64_t n, int cin, const float* W, int w_out_in, int cout, const float* bias,
-                  const float* scale, const float* shift, int act, const float* residual, float* out,
-                  hipStream_t stream);
-// the same with bf16 feature maps on any of the three row operands (weights and arithmetic stay fp32)
+// One 1x1 convolution / Linear layer: out[r][:] = act( (in[r] @ Wmat + bias) * scale + shift ) (+ residual[r]).  Weights and
+// arithmetic are fp32; each of the three row operands may be a bf16 feature map.  Fields in the order of a designated initialiser.
+struct DenseCall {
+  // rows
+  const void* in = nullptr; int in_bf16 = 0;
+  int64_t n = 0;                         // rows the buffers hold (the capacity): sizes the grid
+  const int32_t* n_dev = nullptr;        // (nullable) device-resident live row count <= n: rows from it on are not written
+  // kernel
+  int cin = 0, cout = 0;
+  const float* W = nullptr;
+  int w_out_in = 0;                      // 0: Wmat = W[cin][cout] (ME 1x1 kernel layout); 1: Wmat = W[cout][cin]^T (nn.Linear layout)
+  const float* wfrag = nullptr;          // (nullable) the kernel in fragment order (dense_pack_frags): the streaming form reads it
+                                         // instead of gathering W per workgroup
+  // epilogue
+  const float* bias = nullptr;
+  const float *scale = nullptr, *shift = nullptr;   // folded BatchNorm (nullable, together)
+  int act = 0;                           // Act
+  const void* residual = nullptr; int res_bf16 = 0;
+  const float* gate = nullptr;           // (nullable) [B][cout]: the tail of an ECA block fused into the launch,
+  const int32_t* boff = nullptr;         // out = relu(residual[r] * gate[scan of r] + layer output); boff = the B + 1 row offsets
+  int B = 0;                             // of the scans.  Needs dense_gate_fusable(n, cin, cout)
+  // output
+  void* out = nullptr; int out_bf16 = 0;
+  // measurement: -1 = the product rule, 0 = never the streaming form, 1 = the streaming form (an error for other shapes);
+  // the forms are bitwise the same
+  int form = -1;
+};
+// Kernel a layer runs on: a function of (rows, cin, cout, form) and EGONN_NO_DENSE_STREAM.  dense_route alone decides it (the
+// rule and its thresholds: dense.hip).
+enum DenseRoute {
+  DENSE_INVALID = -1,  // form 1 on a shape without a streaming form
+  DENSE_NONE = 0,      // no rows: nothing to launch
+  DENSE_STREAM,        // dense_stream_kernel: one 16-row tile per wave, weights from the packed fragments
+  DENSE_LDS,           // dense_lds_kernel: weights resident in LDS, persistent workgroups, column blocks over grid.y
+  DENSE_SMALL,         // dense_small_kernel: one memory round trip per wave
+  DENSE_TILE,          // dense_kernel: 64 x 64 tiles
+  DENSE_PLAIN          // dense_any_kernel: thread per output; bias + activation only, fp32 rows
+};
+struct DenseLaunch {   // what the route implies
+  DenseRoute route = DENSE_NONE;
+  unsigned gx = 0, gy = 0;
+  size_t lds = 0;      // dynamic LDS bytes
+  int colblk = 0;      // DENSE_LDS: output columns per block of grid.y
+};
+DenseRoute dense_route(int64_t n, int cin, int cout, int form);
+DenseLaunch dense_launch(int64_t n, int cin, int cout, int form, int gate_scans);   // gate_scans: DenseCall::B of a gated call, else 0
+int dense_forward(const DenseCall& c, hipStream_t stream);
+// true: a DenseCall with a gate can run on this shape (form 0 takes the persistent LDS kernel with a single column block)
 bool dense_gate_fusable(int64_t n, int cin, int cout);
-int dense_forward_ex(const void* in, int in_bf16, int64_t n, int cin, const float* W, int w_out_in, int cout,
-                     const float* bias, const float* scale, const float* shift, int act, const void* residual, int res_bf16,
-                     void* out, int out_bf16, hipStream_t stream, const int32_t* n_dev = nullptr, const float* gate = nullptr,
-                     const int32_t* boff = nullptr, int B = 0,    // gate: out = relu(residual * gate[sample][col] + layer output)
-                     const float* wfrag = nullptr, int form = -1);
-// wfrag (nullable): the kernel in fragment order (dense_pack_frags), read by the streaming form instead of gathering W per workgroup.
-// form: -1 = the product rule (streaming form for >= 8192 rows, cin in {32, 64, 128}, cout in {64, 128}, cin * cout * 4 <= 32 KB,
-// unless EGONN_NO_DENSE_STREAM), 0 = never the streaming form, 1 = the streaming form (an error for other shapes): bitwise the same
+// three independent (n_i, 128) @ (128, 128) products in one launch of the small kernel: fp32 rows, no epilogue.  Every n_i must
+// pass dense_group3_rows (the small kernel is what dense_route gives the product alone, or there are no rows)
+bool dense_group3_rows(int64_t n);
+int dense_small_group3(const float* const* in, const int64_t* n, const int32_t* const* n_dev, const float* const* W, float* const* out,
+                       hipStream_t stream);
 int dense_pack_frags(const float* W, int w_out_in, int cin, int cout, float* out, hipStream_t stream);   // cin * cout floats
+
+// rowwise.hip ----------------------------------------------------------------------------------
 int bn_fold(const float* w, const float* b, const float* rm, const float* rv, float eps, int c, float* scale,
             float* shift, hipStream_t stream);
 // n_dev (nullable, here and below): device-resident row count (<= n); n then only sizes the grid
@@ -141,6 +179,11 @@ int gem_finish(const float* partial, const int32_t* boff, int B, int c, const fl
 int pool_finish(const float* partial, const int32_t* boff, int B, int c, int mode, float* out, hipStream_t stream);
 int l2_normalize_rows(float* x, int64_t n, int c, hipStream_t stream, const int32_t* n_dev = nullptr);
 int add_act(const float* a, const float* b, int64_t n, int relu, float* out, hipStream_t stream);
+
+// heads.hip ------------------------------------------------------------------------------------
+// waves (16-row tiles) per workgroup of the local-heads kernels; the tests read it from here (tests/helpers.py: kernel_constant) to
+// build their edge batches
+constexpr int LH_WAVES = 8;
 // keypoint positions (reference datasets/quantization.py:60-72, 93-103)
 int keypoint_positions(const uint64_t* keys, int64_t n, int level, int cb, const float* offsets, int mode,
                        const float* step, int ignore_offsets, float* out, hipStream_t stream, const int32_t* n_dev = nullptr);

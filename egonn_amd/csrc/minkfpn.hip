@@ -349,7 +349,9 @@ API int egonn_minkfpn_forward(egonn_ctx* c, egonn_model* m, int flags, float* ou
       const float* res = x;
       if (b.down) {
         WALLOC(rd, n * b.cout);
-        EGONN_TRY(dense_forward_ex(x, 0, n, b.cin, b.down, 0, b.cout, nullptr, b.dn.scale, b.dn.shift, ACT_NONE, nullptr, 0, rd, 0, st, cnt + lv));
+        EGONN_TRY(dense_forward({.in = x, .n = n, .n_dev = cnt + lv, .cin = b.cin, .cout = b.cout, .W = b.down, .scale = b.dn.scale,
+                                 .shift = b.dn.shift, .out = rd},
+                                st));
         res = rd;
       }
       WALLOC(xo, n * b.cout);
@@ -371,8 +373,7 @@ API int egonn_minkfpn_forward(egonn_ctx* c, egonn_model* m, int flags, float* ou
   {
     float* dst = (T == 0 && out_map) ? out_map : nullptr;
     if (!dst) { WALLOC(gL, P.cap[L] * F); dst = gL; }
-    EGONN_TRY(dense_forward_ex(feat[L], 0, P.cap[L], f.c1x1_cin[0], f.c1x1[0], 0, F, nullptr, nullptr, nullptr, ACT_NONE, nullptr, 0, dst, 0,
-                               st, cnt + L));
+    EGONN_TRY(dense_forward({.in = feat[L], .n = P.cap[L], .n_dev = cnt + L, .cin = f.c1x1_cin[0], .cout = F, .W = f.c1x1[0], .out = dst}, st));
     g = dst;
   }
   const bool split_step = (flags & EGONN_MINKFPN_SPLIT_TOPDOWN) && sconv_split_arithmetic(c);
@@ -386,8 +387,9 @@ API int egonn_minkfpn_forward(egonn_ctx* c, egonn_model* m, int flags, float* ou
       WALLOC(u, P.cap[lo] * F);
       EGONN_TRY(conv_layer(c, st, conv_call(2, lo, g, f.pk_t[ndx], F, F, 0, nullptr, 0, u), "tconv"));
       // (the sum is commutative: bitwise `tconv + lateral`)
-      EGONN_TRY(dense_forward_ex(feat[lo], 0, P.cap[lo], cl, f.c1x1[ndx + 1], 0, F, nullptr, nullptr, nullptr, ACT_NONE, u, 0, dst, 0, st,
-                                 cnt + lo));
+      EGONN_TRY(dense_forward({.in = feat[lo], .n = P.cap[lo], .n_dev = cnt + lo, .cin = cl, .cout = F, .W = f.c1x1[ndx + 1], .residual = u,
+                               .out = dst},
+                              st));
     }
     DBG_SYNC("minkfpn top-down onto L%d", lo);
     g = dst;
@@ -454,6 +456,6 @@ API int egonn_topdown_step(egonn_ctx* c, int level_out, const float* x_coarse, c
   if (!x_lateral) return EGONN_OK;
   float* v = c->work_arena.alloc<float>(rows * C);
   EGONN_REQUIRE(v, EGONN_ERR_STATE, "work arena too small");
-  EGONN_TRY(dense_forward(x_lateral, P.lv[level_out].n, Cl, w_lateral, 0, C, nullptr, nullptr, nullptr, ACT_NONE, nullptr, v, st));
+  EGONN_TRY(dense_forward({.in = x_lateral, .n = P.lv[level_out].n, .cin = Cl, .cout = C, .W = w_lateral, .out = v}, st));
   return add_act(u, v, P.lv[level_out].n * C, 0, out, st);
 }

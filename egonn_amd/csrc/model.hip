@@ -301,8 +301,9 @@ API int egonn_conv(egonn_ctx* c, int level_in, int level_out, int ks, const floa
   const Plan& P = c->plan;
   if (ks == 1) {
     EGONN_REQUIRE(level_in == level_out, EGONN_ERR_INVALID, "1x1 conv cannot change the level");
-    return dense_forward(in, P.lv[level_in].n, cin, kernel, 0, cout, nullptr, scale, shift, relu ? ACT_RELU : ACT_NONE,
-                         nullptr, out, st);
+    return dense_forward({.in = in, .n = P.lv[level_in].n, .cin = cin, .cout = cout, .W = kernel, .scale = scale, .shift = shift,
+                          .act = relu ? ACT_RELU : ACT_NONE, .out = out},
+                         st);
   }
   if (ks == 5) {
     EGONN_REQUIRE(level_in == 0 && level_out == 0 && cin == 1, EGONN_ERR_INVALID,
@@ -483,15 +484,6 @@ API int egonn_block_tail(egonn_ctx* c, int level, const float* x, const float* r
 API int egonn_add(const float* a, const float* b, int64_t n, float* out, void* stream) {
   EGONN_REQUIRE(a && b && out && n >= 0, EGONN_ERR_INVALID, "add: bad argument");
   return add_act(a, b, n, 0, out, (hipStream_t)stream);
-}
-
-// out = act(x @ W + bias) of a stand-alone Linear / 1x1 layer (W in ME kernel or nn.Linear layout)
-API int egonn_dense(const float* x, int64_t n, int cin, const float* weight, int weight_out_in, const float* bias, int cout,
-                    int act, float* out, void* stream) {
-  EGONN_REQUIRE(x && weight && out && n >= 0 && cin >= 1 && cout >= 1 && act >= 0 && act <= 4, EGONN_ERR_INVALID,
-                "dense: bad arguments");
-  return dense_forward(x, n, cin, weight, weight_out_in ? 1 : 0, cout, bias, nullptr, nullptr, act, nullptr, out,
-                       (hipStream_t)stream);
 }
 
 // Features handed in in the caller's row order -> plan (Z-order) row order: out[i] = features[input_index[i]]
@@ -801,8 +793,12 @@ namespace {
 
 int run_mlp(const MlpRef& r, const float* x, int64_t n, int act_out, float* hidden, float* out, hipStream_t st,
             const int32_t* n_dev) {
-  EGONN_TRY(dense_forward_ex(x, 0, n, r.cin, r.w0, 1, r.mid, r.b0, nullptr, nullptr, ACT_RELU, nullptr, 0, hidden, 0, st, n_dev));
-  return dense_forward_ex(hidden, 0, n, r.mid, r.w1, 1, r.cout, r.b1, nullptr, nullptr, act_out, nullptr, 0, out, 0, st, n_dev);
+  EGONN_TRY(dense_forward({.in = x, .n = n, .n_dev = n_dev, .cin = r.cin, .cout = r.mid, .W = r.w0, .w_out_in = 1, .bias = r.b0,
+                           .act = ACT_RELU, .out = hidden},
+                          st));
+  return dense_forward({.in = hidden, .n = n, .n_dev = n_dev, .cin = r.mid, .cout = r.cout, .W = r.w1, .w_out_in = 1, .bias = r.b1,
+                        .act = act_out, .out = out},
+                       st);
 }
 
 }  // namespace
@@ -903,15 +899,16 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
   auto local_head = [&](hipStream_t st) -> int {
     const int64_t n3 = P.cap[3], n4 = P.cap[4];
     FALLOC(l4, n4 * LOCAL_CH);
-    EGONN_TRY(dense_forward_ex(x[4], bf16, n4, 128, m->l1x1[4], 0, LOCAL_CH, nullptr, nullptr, nullptr, ACT_NONE, nullptr, 0, l4,
-                               bf16, st, cnt + 4, nullptr, nullptr, 0, m->pk_l1x1[4]));
+    EGONN_TRY(dense_forward({.in = x[4], .in_bf16 = bf16, .n = n4, .n_dev = cnt + 4, .cin = 128, .cout = LOCAL_CH, .W = m->l1x1[4],
+                             .wfrag = m->pk_l1x1[4], .out = l4, .out_bf16 = bf16},
+                            st));
     FALLOC(u3, n3 * LOCAL_CH);
     EGONN_TRY(conv_layer(c, st, conv_call(2, 3, l4, m->pk_lt[4], LOCAL_CH, LOCAL_CH, bf16, nullptr, 0, u3), "tconv"));
     EGONN_REQUIRE(m->ldec.cin == 64 && m->ldec.mid == 96 && m->ldec.cout == 128 && m->kp.mid == 32 && m->sg.mid == 32,
                   EGONN_ERR_STATE, "local heads: unexpected layer sizes");
     const float* hw[12] = {m->ldec.w0, m->ldec.b0, m->ldec.w1, m->ldec.b1, m->kp.w0, m->kp.b0, m->kp.w1, m->kp.b1,
                            m->sg.w0, m->sg.b0, m->sg.w1, m->sg.b1};
-    // the heads' Linear layers on the fp16 matrix pipe (dense.hip), unless this context asked for exact fp32 arithmetic
+    // the heads' Linear layers on the fp16 matrix pipe (heads.hip), unless this context asked for exact fp32 arithmetic
     const void* lh_pack = (!switches().no_split_heads && sconv_split_arithmetic(c)) ? m->lh_pack : nullptr;
     if (!switches().no_fused_lateral && LOCAL_CH == 64) {
       // the level-3 lateral 1x1 convolution + the transposed convolution's output are the first layer of the heads' kernel — the
@@ -922,8 +919,9 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
       return EGONN_OK;
     }
     WALLOC(l3, n3 * LOCAL_CH);
-    EGONN_TRY(dense_forward_ex(x[3], bf16, n3, 64, m->l1x1[3], 0, LOCAL_CH, nullptr, nullptr, nullptr, ACT_NONE, u3, bf16, l3, 0, st, cnt + 3,
-                               nullptr, nullptr, 0, m->pk_l1x1[3]));
+    EGONN_TRY(dense_forward({.in = x[3], .in_bf16 = bf16, .n = n3, .n_dev = cnt + 3, .cin = 64, .cout = LOCAL_CH, .W = m->l1x1[3],
+                             .wfrag = m->pk_l1x1[3], .residual = u3, .res_bf16 = bf16, .out = l3},
+                            st));
     EGONN_TRY(local_heads_forward(l3, n3, cnt + 3, hw, P.lv[3].keys, 3, P.coord_bits, quant_mode, step,
                                   (flags & EGONN_FLAG_IGNORE_KP_REGRESSOR) ? 1 : 0, out_desc, out_kp, out_sigma, st, nullptr, nullptr, 0,
                                   lh_pack, c->dev_fp16_flag));
@@ -984,17 +982,24 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
       continue;
     }
     FALLOC(xo, n * b.cout);
+    // the 1x1 downsample branch with its BatchNorm (levels 2 and 4); its output and what rides on it follow
+    const DenseCall down{.in = y, .in_bf16 = bf16, .n = n, .n_dev = cnt + i, .cin = b.cin, .cout = b.cout, .W = b.down,
+                         .wfrag = m->pk_down[i], .scale = b.dn.scale, .shift = b.dn.shift, .out_bf16 = bf16};
     if (b.down && !switches().no_fused_down && dense_gate_fusable(n, b.cin, b.cout)) {
       // blocks with a 1x1 downsample branch (levels 2 and 4): the branch, its BatchNorm and the gated residual + ReLU of the block's
       // tail in ONE launch — out = relu(t2 * gate[scan] + bn(y @ Wd)); the branch output never goes to memory (bitwise the result
       // of the two launches it replaces)
-      EGONN_TRY(dense_forward_ex(y, bf16, n, b.cin, b.down, 0, b.cout, nullptr, b.dn.scale, b.dn.shift, ACT_NONE, t2, bf16, xo,
-                                 bf16, st, cnt + i, gate, L.boff, B, m->pk_down[i]));
+      DenseCall dc = down;
+      dc.residual = t2; dc.res_bf16 = bf16;
+      dc.gate = gate; dc.boff = L.boff; dc.B = B;
+      dc.out = xo;
+      EGONN_TRY(dense_forward(dc, st));
     } else {
       if (b.down) {
         FALLOC(rd, n * b.cout);
-        EGONN_TRY(dense_forward_ex(y, bf16, n, b.cin, b.down, 0, b.cout, nullptr, b.dn.scale, b.dn.shift, ACT_NONE, nullptr, 0, rd,
-                                   bf16, st, cnt + i, nullptr, nullptr, 0, m->pk_down[i]));
+        DenseCall dc = down;
+        dc.out = rd;
+        EGONN_TRY(dense_forward(dc, st));
         res = rd;
       }
       EGONN_TRY(eca_apply_gate(t2, res, gate, L.boff, B, n, b.cout, xo, bf16, st));
@@ -1012,7 +1017,8 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
 
   // ---- global head + decoder + GeM (models/minkgl.py:46-60, 207-225; layers/pooling.py:82-86)
   void* g5_fused = nullptr;
-  if (do_global && !switches().no_fused_ghead && !bf16 && c->conv_variant == 0 && P.cap[5] < 8192 && P.cap[6] < 8192 && P.cap[7] < 8192) {
+  if (do_global && !switches().no_fused_ghead && !bf16 && c->conv_variant == 0 && dense_group3_rows(P.cap[5]) &&
+      dense_group3_rows(P.cap[6]) && dense_group3_rows(P.cap[7])) {
     // MinkHead (models/minkgl.py:46-60) in three launches instead of five: the three lateral 1x1 convolutions depend on the trunk
     // only — ONE grouped launch — and every FPN step `tconv(y) + lateral` is the transposed convolution with the lateral as its
     // epilogue residual.  a + b = b + a: bitwise the five-launch result (tools/check_bitwise_switches.py).
@@ -1038,19 +1044,22 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
   if (do_global) {
     const float* g5 = reinterpret_cast<const float*>(g5_fused);
     if (!g5) {
+    // lateral 1x1 convolution of level l (+ the transposed convolution's output as its residual)
+    auto lateral = [&](int l, const void* up, void* out, int out_bf16) {
+      return dense_forward({.in = x[l], .in_bf16 = bf16, .n = P.cap[l], .n_dev = cnt + l, .cin = 128, .cout = GLOBAL_CH, .W = m->g1x1[l],
+                            .residual = up, .res_bf16 = up ? bf16 : 0, .out = out, .out_bf16 = out_bf16},
+                           st);
+    };
     FALLOC(g7, P.cap[7] * GLOBAL_CH);
-    EGONN_TRY(dense_forward_ex(x[7], bf16, P.cap[7], 128, m->g1x1[7], 0, GLOBAL_CH, nullptr, nullptr, nullptr, ACT_NONE, nullptr, 0,
-                               g7, bf16, st, cnt + 7));
+    EGONN_TRY(lateral(7, nullptr, g7, bf16));
     FALLOC(u6, P.cap[6] * GLOBAL_CH);
     EGONN_TRY(conv_layer(c, st, conv_call(2, 6, g7, m->pk_gt[7], GLOBAL_CH, GLOBAL_CH, bf16, nullptr, 0, u6), "tconv"));
     FALLOC(g6, P.cap[6] * GLOBAL_CH);
-    EGONN_TRY(dense_forward_ex(x[6], bf16, P.cap[6], 128, m->g1x1[6], 0, GLOBAL_CH, nullptr, nullptr, nullptr, ACT_NONE, u6, bf16,
-                               g6, bf16, st, cnt + 6));
+    EGONN_TRY(lateral(6, u6, g6, bf16));
     FALLOC(u5, P.cap[5] * GLOBAL_CH);
     EGONN_TRY(conv_layer(c, st, conv_call(2, 5, g6, m->pk_gt[6], GLOBAL_CH, GLOBAL_CH, bf16, nullptr, 0, u5), "tconv"));
     WALLOC(g5u, P.cap[5] * GLOBAL_CH);
-    EGONN_TRY(dense_forward_ex(x[5], bf16, P.cap[5], 128, m->g1x1[5], 0, GLOBAL_CH, nullptr, nullptr, nullptr, ACT_NONE, u5, bf16,
-                               g5u, 0, st, cnt + 5));
+    EGONN_TRY(lateral(5, u5, g5u, 0));
     g5 = g5u;
     DBG_SYNC("global head");
     }

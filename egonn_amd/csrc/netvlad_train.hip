@@ -115,7 +115,7 @@ API int egonn_netvlad_train_forward(egonn_ctx* ctx, int level, const float* x, i
   float* ones = reinterpret_cast<float*>(sums + 2 * NV_K);
   float* zeros = ones + D;
   const double M = (double)B * (double)nmax;
-  EGONN_TRY(dense_forward(x, N, C, wc, 0, NV_K, nullptr, nullptr, nullptr, ACT_NONE, nullptr, save_z, st));
+  EGONN_TRY(dense_forward({.in = x, .n = N, .cin = C, .cout = NV_K, .W = wc, .out = save_z}, st));
   EGONN_TRY(egonn_col_stats(3, save_z, nullptr, nullptr, running_mean, N, NV_K, sums, cs, (int64_t)csn, st));
   hipLaunchKernelGGL(nvt_pad_stats_kernel, dim3(1), dim3(NV_K), 0, st, sums, running_mean, M - (double)N);
   HIP_CHECK(hipGetLastError());

@@ -470,6 +470,12 @@ int egonn_debug_dense(const void* in, int in_bf16, int64_t rows_capacity, const 
                       int weight_out_in, const float* packed, const float* bias, const float* scale, const float* shift, int act,
                       const void* residual, int res_bf16, const float* gate, const int32_t* boff, int B, void* out, int out_bf16,
                       int form, void* stream);
+/* tests only, no device call: what the dense launcher picks for a layer of `rows` (capacity) x cin -> cout.  form -1 = the product
+ * rule, 0 / 1 as above; gate_scans = B of a gated call, 0 = no gate.  out[0] = the kernel (0 nothing to launch, 1 streaming form,
+ * 2 persistent LDS kernel, 3 small kernel, 4 64-column tile kernel, 5 thread per output), out[1], out[2] = grid x, y, out[3] =
+ * dynamic LDS bytes, out[4] = output columns per block of grid y (persistent LDS kernel, else 0).  A form or a gate the shape
+ * does not have is the launcher's own error. */
+int egonn_debug_dense_route(int64_t rows, int cin, int cout, int form, int gate_scans, int32_t out[5]);
 /* out (ca,cb) = a^T b over n rows: weight gradient of a dense layer (a = input, b = grad_out for the (cin,cout) layout). */
 int egonn_dense_backward_weight(const float* a, int ca, const float* b, int cb, int64_t n, float* out, float* scratch,
                                 int64_t scratch_floats, void* stream);
