@@ -267,27 +267,14 @@ API int egonn_input_index(egonn_ctx* c, int64_t* out, void* stream) {
 }
 
 // ------------------------------------------------------------------------------------------ operators
-// scratch for the stand-alone operator entry points (the forward carves its own from the work arena)
-static float* op_scratch(egonn_ctx* c) {
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
-  const size_t ks = sconv_ksplit_scratch_floats(c);
-  c->ks_part = nullptr;
-  c->ks_part_floats = 0;
-  if (c->work_arena.ensure((SCONV_SCRATCH_FLOATS + ks) * sizeof(float) + 8192) != EGONN_OK) return nullptr;
-  c->work_arena.reset();
-  float* scratch = c->work_arena.alloc<float>(SCONV_SCRATCH_FLOATS);
-  if (ks) {
-    c->ks_part = c->work_arena.alloc<float>(ks);
-    c->ks_part_floats = c->ks_part ? ks : 0;
-  }
-  return scratch;
-}
-
 // a convolution of a stand-alone operator entry point: the kernel in reference layout, packed into the work arena per call
 static int op_conv(egonn_ctx* c, int kind, int level, const void* in, int cin, const float* kernel, int cout, int bf16,
                    const float* scale, const float* shift, int relu, void* out, float* psum, void* stream) {
+  Arena* A;
+  EGONN_TRY(claim_work(c, (SCONV_SCRATCH_FLOATS + sconv_ksplit_scratch_floats(c)) * sizeof(float) + 8192, true, &A));
+  WALLOC(float, scratch, SCONV_SCRATCH_FLOATS);
   const ConvCall cc{.kind = kind, .level = level, .in = in, .out = out, .cin = cin, .cout = cout, .bf16 = bf16, .scale = scale,
-                    .shift = shift, .relu = relu, .psum = psum, .W = kernel, .scratch = op_scratch(c), .scratch_floats = SCONV_SCRATCH_FLOATS};
+                    .shift = shift, .relu = relu, .psum = psum, .W = kernel, .scratch = scratch, .scratch_floats = SCONV_SCRATCH_FLOATS};
   return sconv_map(c, cc, (hipStream_t)stream);
 }
 
@@ -349,11 +336,8 @@ API int egonn_sparse_conv(egonn_ctx* c, int map_kind, int level_out, const void*
 API int egonn_prepare_maps(egonn_ctx* c, int with_level0_transpose, void* stream) {
   REQUIRE_PLAN(c);
   HIP_CHECK(hipSetDevice(c->device));
-  int kinds[RG_MAX_JOBS], levels[RG_MAX_JOBS], n = 0;
-  for (int l = 1; l < EGONN_NUM_LEVELS; ++l) { kinds[n] = 0; levels[n++] = l; }
-  for (int l = 1; l < EGONN_NUM_LEVELS; ++l) { kinds[n] = 1; levels[n++] = l; }
-  for (int l = with_level0_transpose ? 0 : 1; l < EGONN_NUM_LEVELS - 1; ++l) { kinds[n] = 2; levels[n++] = l; }
-  return ensure_rowgroups(c, kinds, levels, n, (hipStream_t)stream);
+  const int tlevels[EGONN_NUM_LEVELS - 1] = {0, 1, 2, 3, 4, 5, 6}, skip = with_level0_transpose ? 0 : 1;
+  return ensure_graph_rowgroups(c, EGONN_NUM_LEVELS - 1, tlevels + skip, EGONN_NUM_LEVELS - 1 - skip, (hipStream_t)stream);
 }
 
 // Measurement hook (tools/sconv_trace.py): device buffer the traced conv build (debug variant 128) writes its per-task
@@ -421,30 +405,21 @@ API int egonn_map_groups(egonn_ctx* c, int map_kind, int level_out, int64_t* n_g
   return EGONN_OK;
 }
 
-__global__ void avg_finish_kernel(const float* __restrict__ partial, const int32_t* __restrict__ boff, int c,
-                                  float* __restrict__ out) {
-  const int b = blockIdx.x, t = threadIdx.x;
-  if (t >= c) return;
-  const int32_t n = boff[b + 1] - boff[b];
-  float s = 0.f;
-  for (int ch = 0; ch < SEG_CHUNKS; ++ch) s += partial[((int64_t)b * SEG_CHUNKS + ch) * c + t];
-  out[(int64_t)b * c + t] = n > 0 ? s / (float)n : 0.f;
+// the pooling operators: `method` over the rows of level `level`, out (B, channels)
+static int op_pool(egonn_ctx* c, Pooling method, int level, const float* x, int channels, const float* p, float* out, void* stream) {
+  const int B = c->plan.batch;
+  Arena* A;
+  EGONN_TRY(claim_work(c, (size_t)B * SEG_CHUNKS * channels * 4 + 4096, false, &A));
+  WALLOC(float, partial, (size_t)B * SEG_CHUNKS * channels);
+  return global_pool(method, x, c->plan.lv[level].boff, B, channels, p, partial, out, (hipStream_t)stream);
 }
 
+// SPoC pooling over the rows of level `level` (MinkowskiGlobalAvgPooling, layers/pooling.py:59-69): out (B, ch)
 API int egonn_global_avg_pool(egonn_ctx* c, int level, const float* in, int ch, float* out, void* stream) {
   REQUIRE_PLAN(c);
   HIP_CHECK(hipSetDevice(c->device));
   EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS, EGONN_ERR_INVALID, "level %d out of range", level);
-  const int B = c->plan.batch;
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
-  EGONN_TRY(c->work_arena.ensure((size_t)B * SEG_CHUNKS * ch * 4 + 4096));
-  c->work_arena.reset();
-  float* partial = c->work_arena.alloc<float>((size_t)B * SEG_CHUNKS * ch);
-  EGONN_TRY(segment_partial_sums(in, c->plan.lv[level].boff, B, ch, 0, nullptr, partial, (hipStream_t)stream));
-  hipLaunchKernelGGL(avg_finish_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, partial, c->plan.lv[level].boff, ch,
-                     out);
-  HIP_CHECK(hipGetLastError());
-  return EGONN_OK;
+  return op_pool(c, POOL_SPOC, level, in, ch, nullptr, out, stream);
 }
 
 // eval-mode MinkowskiBatchNorm folded to scale/shift (nn.BatchNorm1d eps as given): scale = w / sqrt(var + eps)
@@ -463,21 +438,12 @@ API int egonn_block_tail(egonn_ctx* c, int level, const float* x, const float* r
   REQUIRE_PLAN(c);
   EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && x && residual && out, EGONN_ERR_INVALID, "block_tail: bad argument");
   HIP_CHECK(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
   const int B = c->plan.batch;
   const Level& L = c->plan.lv[level];
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
-  EGONN_TRY(c->work_arena.ensure(((size_t)B * SEG_CHUNKS * channels + (size_t)B * channels + 64) * 4 + 4096));
-  c->work_arena.reset();
-  float* partial = c->work_arena.alloc<float>((size_t)B * SEG_CHUNKS * channels + (size_t)B * channels);
-  EGONN_REQUIRE(partial, EGONN_ERR_STATE, "work arena too small");
-  float ones[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  (void)ones;
-  if (eca_weight) {
-    EGONN_TRY(segment_partial_sums(x, L.boff, B, channels, 0, nullptr, partial, st));
-    return eca_apply(x, residual, partial, L.boff, B, L.n, channels, eca_weight, eca_ksize, out, st);
-  }
-  return add_act(x, residual, L.n * channels, 1, out, st);
+  Arena* A;
+  EGONN_TRY(claim_work(c, ((size_t)B * SEG_CHUNKS * channels + (size_t)B * channels + 64) * 4 + 4096, false, &A));
+  WALLOC(float, partial, (size_t)B * SEG_CHUNKS * channels + (size_t)B * channels);
+  return block_tail(x, residual, L.boff, B, L.n, channels, eca_weight, eca_ksize, partial, out, (hipStream_t)stream);
 }
 
 // SparseTensor + SparseTensor on the same coordinate map (models/minkfpn.py:91, minkgl.py:56): out = a + b
@@ -500,15 +466,7 @@ API int egonn_gem(egonn_ctx* c, int level, const float* x, int channels, const f
   REQUIRE_PLAN(c);
   EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && x && p && out, EGONN_ERR_INVALID, "gem: bad argument");
   HIP_CHECK(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int B = c->plan.batch;
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
-  EGONN_TRY(c->work_arena.ensure((size_t)B * SEG_CHUNKS * channels * 4 + 4096));
-  c->work_arena.reset();
-  float* partial = c->work_arena.alloc<float>((size_t)B * SEG_CHUNKS * channels);
-  EGONN_REQUIRE(partial, EGONN_ERR_STATE, "work arena too small");
-  EGONN_TRY(segment_partial_sums(x, c->plan.lv[level].boff, B, channels, 1, p, partial, st));
-  return gem_finish(partial, c->plan.lv[level].boff, B, channels, p, out, st);
+  return op_pool(c, POOL_GEM, level, x, channels, p, out, stream);
 }
 
 // MAC pooling over the rows of level `level` (MinkowskiGlobalMaxPooling, layers/pooling.py:46-56): out (B, channels)
@@ -516,15 +474,7 @@ API int egonn_global_max_pool(egonn_ctx* c, int level, const float* in, int chan
   REQUIRE_PLAN(c);
   EGONN_REQUIRE(level >= 0 && level < EGONN_NUM_LEVELS && in && out, EGONN_ERR_INVALID, "global_max_pool: bad argument");
   HIP_CHECK(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int B = c->plan.batch;
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
-  EGONN_TRY(c->work_arena.ensure((size_t)B * SEG_CHUNKS * channels * 4 + 4096));
-  c->work_arena.reset();
-  float* partial = c->work_arena.alloc<float>((size_t)B * SEG_CHUNKS * channels);
-  EGONN_REQUIRE(partial, EGONN_ERR_STATE, "work arena too small");
-  EGONN_TRY(segment_partial_sums(in, c->plan.lv[level].boff, B, channels, 2, nullptr, partial, st));
-  return pool_finish(partial, c->plan.lv[level].boff, B, channels, 2, out, st);
+  return op_pool(c, POOL_MAC, level, in, channels, nullptr, out, stream);
 }
 
 // NetVLAD / NetVLAD-GC pooling over the rows of level `level` (layers/netvlad.py:18-112, netvlad.hip): out (B, out_dim)
@@ -547,12 +497,10 @@ API int egonn_netvlad(egonn_ctx* c, int level, const float* x, int channels, con
   EGONN_REQUIRE(((uintptr_t)x & 15) == 0, EGONN_ERR_INVALID, "netvlad: x must be 16-byte aligned");
   HIP_CHECK(hipSetDevice(c->device));
   const int B = c->plan.batch;
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
   const size_t nws = netvlad_workspace_floats(B, channels, out_dim);
-  EGONN_TRY(c->work_arena.ensure(nws * 4 + 4096));
-  c->work_arena.reset();
-  float* ws = c->work_arena.alloc<float>(nws);
-  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
+  Arena* A;
+  EGONN_TRY(claim_work(c, nws * 4 + 4096, false, &A));
+  WALLOC(float, ws, nws);
   return netvlad_forward(x, c->plan.lv[level].boff, B, channels, cluster_weights, cluster_weights2, bn1_scale, bn1_shift,
                          hidden1_weights, out_dim, bn2_scale, bn2_shift, gating_weights, gate_scale, gate_shift, gating, out,
                          ws, (hipStream_t)stream);
@@ -567,8 +515,7 @@ API int egonn_model_create(egonn_model** m) {
 
 API void egonn_model_destroy(egonn_model* m) {
   if (!m) return;
-  if (m->folded) (void)hipFree(m->folded);
-  if (m->packed) (void)hipFree(m->packed);
+  m->store.release();
   if (m->conv0_unit) (void)hipFree(m->conv0_unit);
   if (m->lh_pack) (void)hipFree(m->lh_pack);
   if (m->lh_ptrs) (void)hipFree(m->lh_ptrs);
@@ -610,16 +557,98 @@ int get_tensor(egonn_model* m, const std::string& key, std::initializer_list<int
   return EGONN_OK;
 }
 
-int get_bn(egonn_model* m, const std::string& prefix, int c, BnRef* bn, float** cursor) {
+int get_bn(egonn_model* m, const std::string& prefix, int c, BnRef* bn, ModelStore* store) {
   bn->c = c;
   EGONN_TRY(get_tensor(m, prefix + ".bn.weight", {c}, &bn->w));
   EGONN_TRY(get_tensor(m, prefix + ".bn.bias", {c}, &bn->b));
   EGONN_TRY(get_tensor(m, prefix + ".bn.running_mean", {c}, &bn->rm));
   EGONN_TRY(get_tensor(m, prefix + ".bn.running_var", {c}, &bn->rv));
-  bn->scale = *cursor;
-  bn->shift = *cursor + c;
-  *cursor += 2 * c;
+  store->add_bn(bn);
   return EGONN_OK;
+}
+
+int eca_ksize(int c) {
+  int lg = 0;
+  while ((1 << lg) < c) ++lg;
+  const int t = (lg + 1) / 2;
+  return (t % 2) ? t : t + 1;
+}
+
+int get_block(egonn_model* m, const std::string& prefix, int ci, int co, bool eca, BlockRef* b, ModelStore* store) {
+  *b = BlockRef();
+  b->cin = ci;
+  b->cout = co;
+  EGONN_TRY(get_tensor(m, prefix + ".conv1.kernel", {27, ci, co}, &b->conv1));
+  EGONN_TRY(get_bn(m, prefix + ".norm1", co, &b->n1, store));
+  EGONN_TRY(get_tensor(m, prefix + ".conv2.kernel", {27, co, co}, &b->conv2));
+  EGONN_TRY(get_bn(m, prefix + ".norm2", co, &b->n2, store));
+  if (ci != co) {
+    EGONN_TRY(get_tensor(m, prefix + ".downsample.0.kernel", {ci, co}, &b->down));
+    EGONN_TRY(get_bn(m, prefix + ".downsample.1", co, &b->dn, store));
+  }
+  if (eca) {
+    b->eca_k = eca_ksize(co);
+    EGONN_TRY(get_tensor(m, prefix + ".eca.conv.weight", {1, 1, b->eca_k}, &b->eca));
+  }
+  return EGONN_OK;
+}
+
+void ModelStore::begin() {
+  bns.clear();
+  packs.clear();
+  bn_bytes = pack_bytes = 0;
+}
+void ModelStore::add_bn(BnRef* bn) {
+  bns.push_back(bn);
+  bn_bytes += align_up((size_t)2 * bn->c * sizeof(float), 256);
+}
+void ModelStore::add_pack(Form form, const float* w, int K, int ci, int co, const void** dst) {
+  packs.push_back({form, w, K, ci, co, pack_bytes, dst});
+  const size_t n = (size_t)K * ci * co;
+  pack_bytes += align_up(form == SPLIT ? split_weights_bytes(K, ci, co) : form == RG16 ? n * 2 : n * 4, 256);
+}
+void ModelStore::add_kernel(const float* w, int K, int ci, int co, bool bf16, PackedKernel* dst) {
+  *dst = PackedKernel();
+  add_pack(RG32, w, K, ci, co, &dst->rg32);
+  if (bf16) add_pack(RG16, w, K, ci, co, &dst->rg16);
+  if (sconv_split_supported(ci, co)) add_pack(SPLIT, w, K, ci, co, &dst->split);
+}
+int ModelStore::commit(hipStream_t st) {
+  auto grow = [](char** buf, size_t* cap, size_t need) -> int {
+    if (*cap >= need) return EGONN_OK;
+    if (*buf) HIP_CHECK(hipFree(*buf));
+    *buf = nullptr;
+    *cap = 0;
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(buf), need));
+    *cap = need;
+    return EGONN_OK;
+  };
+  EGONN_TRY(grow(&folded, &folded_cap, bn_bytes));
+  EGONN_TRY(grow(&packed, &packed_cap, pack_bytes));
+  for (const Pack& k : packs) {
+    char* out = packed + k.off;
+    switch (k.form) {
+      case RG32: EGONN_TRY(pack_rg_weights(k.w, k.K, k.ci, k.co, 0, 0, 0, out, st)); break;
+      case RG16: EGONN_TRY(pack_rg_weights(k.w, k.K, k.ci, k.co, 1, 0, 0, out, st)); break;
+      case SPLIT: EGONN_TRY(pack_split_weights(k.w, k.K, k.ci, k.co, 0, 0, out, st)); break;
+      case DENSE: EGONN_TRY(dense_pack_frags(k.w, 0, k.ci, k.co, reinterpret_cast<float*>(out), st)); break;
+    }
+    *k.dst = out;
+  }
+  char* cur = folded;
+  for (BnRef* bn : bns) {   // eval-mode BatchNorm folded to scale / shift, eps of nn.BatchNorm1d
+    bn->scale = reinterpret_cast<float*>(cur);
+    bn->shift = bn->scale + bn->c;
+    cur += align_up((size_t)2 * bn->c * sizeof(float), 256);
+    EGONN_TRY(bn_fold(bn->w, bn->b, bn->rm, bn->rv, 1e-5f, bn->c, bn->scale, bn->shift, st));
+  }
+  return EGONN_OK;
+}
+void ModelStore::release() {
+  if (folded) (void)hipFree(folded);
+  if (packed) (void)hipFree(packed);
+  folded = packed = nullptr;
+  folded_cap = packed_cap = 0;
 }
 
 }  // namespace egonn
@@ -637,60 +666,47 @@ int get_mlp(egonn_model* m, const std::string& prefix, int cin, int mid, int cou
 
 }  // namespace
 
-namespace egonn {
-int fold(const BnRef& bn, hipStream_t st) { return bn_fold(bn.w, bn.b, bn.rm, bn.rv, 1e-5f, bn.c, bn.scale, bn.shift, st); }
-}  // namespace egonn
-
 API int egonn_model_finalize(egonn_model* m, void* stream) {
   EGONN_REQUIRE(m, EGONN_ERR_INVALID, "model_finalize: null model");
   hipStream_t st = (hipStream_t)stream;
-  const size_t need = 2 * 128 * 32;   // generous: 24 BN layers x <=128 ch x (scale, shift)
-  if (m->folded_cap < need) {
-    if (m->folded) HIP_CHECK(hipFree(m->folded));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->folded), need * sizeof(float)));
-    m->folded_cap = need;
-  }
-  float* cur = m->folded;
+  ModelStore& S = m->store;
+  S.begin();
+  // ---- resolve every tensor (shapes checked, the offending key named) and register what the store folds and packs: every
+  // sparse-conv kernel in item-major MFMA fragment order (sconv.hip), fp32, bf16 and split; the 1x1 kernels the forward runs
+  // through the streaming dense kernel in its fragment order (fp32 only).  No device work before the last lookup.
+  auto dense = [&](const float* w, int ci, int co, const void** dst) {
+    *dst = nullptr;
+    if (ci % 16 == 0 && co % 16 == 0) S.add_pack(ModelStore::DENSE, w, 1, ci, co, dst);
+  };
   EGONN_TRY(get_tensor(m, "trunk.convs.0.kernel", {125, 1, 32}, &m->conv0));
-  EGONN_TRY(get_bn(m, "trunk.bn.0", 32, &m->bn[0], &cur));
+  EGONN_TRY(get_bn(m, "trunk.bn.0", 32, &m->bn[0], &S));
   int inpl = PLANES[0];
   for (int i = 1; i <= 7; ++i) {
     const std::string si = std::to_string(i);
     const int cout = PLANES[i - 1];
     EGONN_TRY(get_tensor(m, "trunk.convs." + si + ".kernel", {8, inpl, inpl}, &m->convs[i]));
-    EGONN_TRY(get_bn(m, "trunk.bn." + si, inpl, &m->bn[i], &cur));
+    EGONN_TRY(get_bn(m, "trunk.bn." + si, inpl, &m->bn[i], &S));
     BlockRef& b = m->blk[i];
-    b.cin = inpl;
-    b.cout = cout;
-    const std::string pre = "trunk.blocks." + si + ".0";
-    EGONN_TRY(get_tensor(m, pre + ".conv1.kernel", {27, inpl, cout}, &b.conv1));
-    EGONN_TRY(get_bn(m, pre + ".norm1", cout, &b.n1, &cur));
-    EGONN_TRY(get_tensor(m, pre + ".conv2.kernel", {27, cout, cout}, &b.conv2));
-    EGONN_TRY(get_bn(m, pre + ".norm2", cout, &b.n2, &cur));
-    if (inpl != cout) {
-      EGONN_TRY(get_tensor(m, pre + ".downsample.0.kernel", {inpl, cout}, &b.down));
-      EGONN_TRY(get_bn(m, pre + ".downsample.1", cout, &b.dn, &cur));
-    } else {
-      b.down = nullptr;
-    }
-    // ECALayer kernel size (layers/eca_block.py:14-15): t = int(|log2(C)+1| / 2), odd
-    int tt = 0;
-    {
-      int lg = 0;
-      while ((1 << lg) < cout) ++lg;
-      tt = (lg + 1) / 2;
-    }
-    b.eca_k = (tt % 2) ? tt : tt + 1;
-    EGONN_TRY(get_tensor(m, pre + ".eca.conv.weight", {1, 1, b.eca_k}, &b.eca));
+    EGONN_TRY(get_block(m, "trunk.blocks." + si + ".0", inpl, cout, true, &b, &S));
+    S.add_kernel(m->convs[i], 8, inpl, inpl, true, &m->pk_convs[i]);
+    S.add_kernel(b.conv1, 27, inpl, cout, true, &m->pk_c1[i]);
+    S.add_kernel(b.conv2, 27, cout, cout, true, &m->pk_c2[i]);
+    m->pk_down[i] = nullptr;
+    if (b.down) dense(b.down, inpl, cout, &m->pk_down[i]);
     inpl = cout;
   }
   for (int l : {5, 6, 7})
     EGONN_TRY(get_tensor(m, "global_head.conv1x1." + std::to_string(l) + ".kernel", {PLANES[l - 1], GLOBAL_CH}, &m->g1x1[l]));
-  for (int l : {6, 7})
+  for (int l : {6, 7}) {
     EGONN_TRY(get_tensor(m, "global_head.tconv." + std::to_string(l) + ".kernel", {8, GLOBAL_CH, GLOBAL_CH}, &m->gt[l]));
-  for (int l : {3, 4})
+    S.add_kernel(m->gt[l], 8, GLOBAL_CH, GLOBAL_CH, true, &m->pk_gt[l]);
+  }
+  for (int l : {3, 4}) {
     EGONN_TRY(get_tensor(m, "local_head.conv1x1." + std::to_string(l) + ".kernel", {PLANES[l - 1], LOCAL_CH}, &m->l1x1[l]));
+    dense(m->l1x1[l], PLANES[l - 1], LOCAL_CH, &m->pk_l1x1[l]);
+  }
   EGONN_TRY(get_tensor(m, "local_head.tconv.4.kernel", {8, LOCAL_CH, LOCAL_CH}, &m->lt[4]));
+  S.add_kernel(m->lt[4], 8, LOCAL_CH, LOCAL_CH, true, &m->pk_lt[4]);
   m->gem_p = nullptr;                  // GeM exponent; MAC / SPoC pooling (layers/pooling.py:46-69) has no parameter
   if (m->t.count("global_pooling.pooling.p")) EGONN_TRY(get_tensor(m, "global_pooling.pooling.p", {1}, &m->gem_p));
   EGONN_TRY(get_mlp(m, "global_descriptor_decoder", GLOBAL_CH, GLOBAL_DIM + (GLOBAL_CH - GLOBAL_DIM) / 2, GLOBAL_DIM, &m->gdec));
@@ -698,62 +714,8 @@ API int egonn_model_finalize(egonn_model* m, void* stream) {
   EGONN_TRY(get_mlp(m, "local_keypoint_regressor", LOCAL_CH, LOCAL_CH / 2, 3, &m->kp));
   EGONN_TRY(get_mlp(m, "local_sigma_regressor", LOCAL_CH, LOCAL_CH / 2, 1, &m->sg));
 
-  // ---- repack every sparse-conv kernel into item-major MFMA fragment order (sconv.hip), fp32 and bf16
-  {
-    size_t need_p = 0;
-    for (int i = 1; i <= 7; ++i) {
-      const BlockRef& b = m->blk[i];
-      need_p += (size_t)8 * b.cin * b.cin + (size_t)27 * b.cin * b.cout + (size_t)27 * b.cout * b.cout;
-    }
-    need_p += (size_t)2 * 8 * GLOBAL_CH * GLOBAL_CH + (size_t)8 * LOCAL_CH * LOCAL_CH;
-    // + the 1x1 kernels the forward runs through the streaming dense kernel, in its LDS fragment order (fp32 only)
-    for (int i = 1; i <= 7; ++i)
-      if (m->blk[i].down) need_p += (size_t)m->blk[i].cin * m->blk[i].cout;
-    for (int l : {3, 4}) need_p += (size_t)PLANES[l - 1] * LOCAL_CH;
-    if (m->packed_cap < need_p) {
-      if (m->packed) HIP_CHECK(hipFree(m->packed));
-      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->packed), (3 * need_p + 512) * sizeof(float)));
-      m->packed_cap = need_p;
-    }
-    float* pc = m->packed;
-    uint16_t* qc = reinterpret_cast<uint16_t*>(m->packed + need_p);      // bf16 copies behind the fp32 ones
-    uint16_t* sc = reinterpret_cast<uint16_t*>(m->packed + need_p + need_p / 2 + 16);   // split fragments behind the bf16 ones
-    auto pack2 = [&](const float* w, int K, int ci, int co, PackedKernel* dst) -> int {
-      EGONN_TRY(pack_rg_weights(w, K, ci, co, 0, 0, 0, pc, st));
-      EGONN_TRY(pack_rg_weights(w, K, ci, co, 1, 0, 0, qc, st));
-      *dst = PackedKernel{pc, qc, nullptr};
-      if (sconv_split_supported(ci, co)) {
-        EGONN_TRY(pack_split_weights(w, K, ci, co, 0, 0, sc, st));
-        dst->split = sc;
-        sc += split_weights_bytes(K, ci, co) / 2;
-      }
-      pc += (size_t)K * ci * co;
-      qc += (size_t)K * ci * co;
-      return EGONN_OK;
-    };
-    for (int i = 1; i <= 7; ++i) {
-      const BlockRef& b = m->blk[i];
-      EGONN_TRY(pack2(m->convs[i], 8, b.cin, b.cin, &m->pk_convs[i]));
-      EGONN_TRY(pack2(b.conv1, 27, b.cin, b.cout, &m->pk_c1[i]));
-      EGONN_TRY(pack2(b.conv2, 27, b.cout, b.cout, &m->pk_c2[i]));
-    }
-    EGONN_TRY(pack2(m->gt[6], 8, GLOBAL_CH, GLOBAL_CH, &m->pk_gt[6]));
-    EGONN_TRY(pack2(m->gt[7], 8, GLOBAL_CH, GLOBAL_CH, &m->pk_gt[7]));
-    EGONN_TRY(pack2(m->lt[4], 8, LOCAL_CH, LOCAL_CH, &m->pk_lt[4]));
-    auto pack1 = [&](const float* w, int ci, int co, const float** dst) -> int {
-      *dst = nullptr;
-      if (ci % 16 || co % 16) return EGONN_OK;
-      EGONN_TRY(dense_pack_frags(w, 0, ci, co, pc, st));
-      *dst = pc;
-      pc += (size_t)ci * co;
-      return EGONN_OK;
-    };
-    for (int i = 1; i <= 7; ++i) {
-      m->pk_down[i] = nullptr;
-      if (m->blk[i].down) EGONN_TRY(pack1(m->blk[i].down, m->blk[i].cin, m->blk[i].cout, &m->pk_down[i]));
-    }
-    for (int l : {3, 4}) EGONN_TRY(pack1(m->l1x1[l], PLANES[l - 1], LOCAL_CH, &m->pk_l1x1[l]));
-  }
+  // ---- device work from here on
+  EGONN_TRY(S.commit(st));
   if (!m->conv0_unit) HIP_CHECK(hipMalloc(&m->conv0_unit, 2 * 4 * 3 * 64 * 16));
   EGONN_TRY(conv0_pack_unit(m->conv0, m->conv0_unit, st));
   if (m->ldec.cin == 64 && m->ldec.mid == 96 && m->ldec.cout == 128 && m->kp.mid == 32 && m->sg.mid == 32 && m->kp.cin == 64 &&
@@ -765,31 +727,12 @@ API int egonn_model_finalize(egonn_model* m, void* stream) {
     HIP_CHECK(hipStreamSynchronize(st));                    // (hp lives on this stack frame)
     EGONN_TRY(local_heads_pack(m->lh_ptrs, m->lh_pack, st));
   }
-  EGONN_TRY(fold(m->bn[0], st));
-  for (int i = 1; i <= 7; ++i) {
-    EGONN_TRY(fold(m->bn[i], st));
-    EGONN_TRY(fold(m->blk[i].n1, st));
-    EGONN_TRY(fold(m->blk[i].n2, st));
-    if (m->blk[i].down) EGONN_TRY(fold(m->blk[i].dn, st));
-  }
   m->ready = true;
   return EGONN_OK;
 }
 
 // ------------------------------------------------------------------------------------------ forward
 namespace {
-
-// EGONN_DEBUG_SYNC=1: synchronise after every stage of egonn_forward and print its name (a GPU fault aborts the process at
-// the next synchronisation: the last name printed is the stage that faulted).  Debug aid only; never set in captures.
-#define DBG_SYNC(...)                                                 \
-  do {                                                                \
-    if (switches().debug_sync) {                                            \
-      fprintf(stderr, "[egonn] " __VA_ARGS__);                        \
-      fprintf(stderr, "\n");                                          \
-      fflush(stderr);                                                 \
-      HIP_CHECK(hipStreamSynchronize(st));                            \
-    }                                                                 \
-  } while (0)
 
 int run_mlp(const MlpRef& r, const float* x, int64_t n, int act_out, float* hidden, float* out, hipStream_t st,
             const int32_t* n_dev) {
@@ -805,6 +748,24 @@ int run_mlp(const MlpRef& r, const float* x, int64_t n, int act_out, float* hidd
 
 namespace egonn {
 
+int claim_work(egonn_ctx* c, size_t bytes, bool with_ksplit, Arena** A) {
+  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
+  c->ks_part = nullptr;
+  c->ks_part_floats = 0;
+  EGONN_TRY(c->work_arena.ensure(bytes));
+  c->work_arena.reset();
+  *A = &c->work_arena;
+  // partial tiles of the offset-split launches: ONE buffer, written by a convolution and consumed by its reducer before the
+  // next launch of the same stream writes it again
+  const size_t ks = with_ksplit ? sconv_ksplit_scratch_floats(c) : 0;
+  if (ks) {
+    c->ks_part = (*A)->alloc<float>(ks);
+    EGONN_REQUIRE(c->ks_part, EGONN_ERR_STATE, "work arena too small (ks_part)");
+    c->ks_part_floats = ks;
+  }
+  return EGONN_OK;
+}
+
 // One sparse convolution of the graph: the profiler tag "<kernel><cin,cout>/L<level>/<what>" (the kernel sconv_map will dispatch,
 // so that bench.py's roofline leg names what rocprofv3 names), the timing scope, the launch
 int conv_layer(egonn_ctx* c, hipStream_t st, const ConvCall& cc, const char* what) {
@@ -819,6 +780,55 @@ ConvCall conv_call(int kind, int level, const void* in, const PackedKernel& pk, 
                    void* out) {
   return ConvCall{.kind = kind, .level = level, .in = in, .out = out, .cin = cin, .cout = cout, .bf16 = bf16,
                   .scale = bn ? bn->scale : nullptr, .shift = bn ? bn->shift : nullptr, .relu = relu, .packed = &pk};
+}
+
+int ensure_graph_rowgroups(egonn_ctx* c, int L, const int* tlevels, int nt, hipStream_t st) {
+  int kinds[RG_MAX_JOBS], levels[RG_MAX_JOBS], n = 0;
+  for (int l = 1; l <= L; ++l) { kinds[n] = 0; levels[n++] = l; }
+  for (int l = 1; l <= L; ++l) { kinds[n] = 1; levels[n++] = l; }
+  for (int i = 0; i < nt; ++i) { kinds[n] = 2; levels[n++] = tlevels[i]; }
+  return ensure_rowgroups(c, kinds, levels, n, st);
+}
+
+int block_convs(egonn_ctx* c, hipStream_t st, Arena* A, int level, const BlockRef& b, const PackedKernel& pk1, const PackedKernel& pk2,
+                int bf16, const void* in, float* psum, void** t2_out) {
+  const size_t bytes = (size_t)c->plan.cap[level] * b.cout * (bf16 ? 2 : 4);
+  WALLOC(char, t1, bytes);
+  WALLOC(char, t2, bytes);
+  const bool t1_split = !switches().no_presplit && sconv_route(c, 0, level, b.cin, b.cout, bf16) == ROUTE_SPLIT &&
+                        sconv_route(c, 0, level, b.cout, b.cout, bf16) == ROUTE_SPLIT;
+  ConvCall c1 = conv_call(0, level, in, pk1, b.cin, b.cout, bf16, &b.n1, 1, t1);
+  c1.split_io = t1_split ? 2 : 0;
+  EGONN_TRY(conv_layer(c, st, c1, "k3.conv1"));
+  ConvCall c2 = conv_call(0, level, t1, pk2, b.cout, b.cout, bf16, &b.n2, 0, t2);
+  c2.split_io = t1_split ? 1 : 0;
+  c2.psum = psum;
+  EGONN_TRY(conv_layer(c, st, c2, "k3.conv2"));
+  *t2_out = t2;
+  return EGONN_OK;
+}
+
+DenseCall down_call(const BlockRef& b, const void* in, int bf16, int64_t n, const int32_t* n_dev, const void* wfrag) {
+  return DenseCall{.in = in, .in_bf16 = bf16, .n = n, .n_dev = n_dev, .cin = b.cin, .cout = b.cout, .W = b.down,
+                   .wfrag = static_cast<const float*>(wfrag), .scale = b.dn.scale, .shift = b.dn.shift, .out_bf16 = bf16};
+}
+
+int global_pool(Pooling method, const float* x, const int32_t* boff, int B, int C, const float* p, float* partial, float* out,
+                hipStream_t st) {
+  if (method == POOL_GEM) {       // GeM (layers/pooling.py:72-86)
+    EGONN_TRY(segment_partial_sums(x, boff, B, C, 1, p, partial, st));
+    return gem_finish(partial, boff, B, C, p, out, st);
+  }
+  const int mode = method == POOL_MAC ? 2 : 0;     // MAC = max (:46-56), SPoC = average (:59-69)
+  EGONN_TRY(segment_partial_sums(x, boff, B, C, mode, nullptr, partial, st));
+  return pool_finish(partial, boff, B, C, mode, out, st);
+}
+
+int block_tail(const float* x, const float* res, const int32_t* boff, int B, int64_t n, int ch, const float* eca, int eca_k,
+               float* partial, float* out, hipStream_t st) {
+  if (!eca) return add_act(x, res, n * ch, 1, out, st);
+  EGONN_TRY(segment_partial_sums(x, boff, B, ch, 0, nullptr, partial, st));
+  return eca_apply(x, res, partial, boff, B, n, ch, eca, eca_k, out, st);
 }
 
 }  // namespace egonn
@@ -845,12 +855,8 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
 
   // ---- row-group tables of every map the graph uses: one launch per plan
   {
-    int kinds[RG_MAX_JOBS], levels[RG_MAX_JOBS], nreq = 0;
-    for (int l = 1; l <= 7; ++l) { kinds[nreq] = 0; levels[nreq++] = l; }
-    for (int l = 1; l <= 7; ++l) { kinds[nreq] = 1; levels[nreq++] = l; }
-    if (do_global) { kinds[nreq] = 2; levels[nreq++] = 6; kinds[nreq] = 2; levels[nreq++] = 5; }
-    if (do_local) { kinds[nreq] = 2; levels[nreq++] = 3; }
-    EGONN_TRY(ensure_rowgroups(c, kinds, levels, nreq, st));
+    const int tlevels[3] = {6, 5, 3};      // the global head's transposed maps, the local head's
+    EGONN_TRY(ensure_graph_rowgroups(c, 7, tlevels + (do_global ? 0 : 2), (do_global ? 2 : 0) + (do_local ? 1 : 0), st));
     DBG_SYNC("row groups");
   }
 
@@ -859,33 +865,19 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
   for (int i = 1; i <= 7; ++i) need += (size_t)P.cap[i] * 128 * 4 * 6 + (size_t)P.lv[i].rg27.cap_groups * 128 * 4;
   need += (size_t)P.cap[5] * (192 + 256 + 128 * 2) * 4 + (size_t)P.cap[3] * (96 + 32 + 32 + 3 + 64 * 2) * 4;
   need += (size_t)B * SEG_CHUNKS * 256 * 4 * 10 + (size_t)P.cap[3] * 32 + (4u << 20);
-  const size_t ks_floats = sconv_ksplit_scratch_floats(c);
-  need += ks_floats * 4 + 4096;
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) c->level_feat[l] = nullptr;
-  EGONN_TRY(c->work_arena.ensure(need));
-  Arena& A = c->work_arena;
-  A.reset();
-  // partial tiles of the offset-split launches: ONE buffer, written by a convolution and consumed by its reducer before the
-  // next launch of the same stream writes it again
-  c->ks_part = ks_floats ? A.alloc<float>(ks_floats) : nullptr;
-  c->ks_part_floats = c->ks_part ? ks_floats : 0;
-#define WALLOC(var, count)                                                         \
-  float* var = A.alloc<float>((size_t)(count));                                    \
-  EGONN_REQUIRE(var != nullptr, EGONN_ERR_STATE, "work arena too small (" #var ")")
-  // feature maps: `count` elements of the map precision (bf16 maps use half of the fp32-sized slot)
-#define FALLOC(var, count)                                                         \
-  void* var = A.alloc<char>((size_t)(count) * es);                                 \
-  EGONN_REQUIRE(var != nullptr, EGONN_ERR_STATE, "work arena too small (" #var ")")
+  need += sconv_ksplit_scratch_floats(c) * 4 + 4096;
+  Arena* A;
+  EGONN_TRY(claim_work(c, need, true, &A));
 
   // ---- trunk (models/minkgl.py:136-153)
   const int64_t n0 = P.cap[0];
   const float* f0 = features;          // voxelize plans: features are already in level-0 row order; NULL = all ones
   if (features && !c->from_points) {
-    WALLOC(fg, n0);
+    WALLOC(float, fg, n0);
     EGONN_TRY(gather_rows(features, P.perm0, n0, 1, fg, st, cnt));
     f0 = fg;
   }
-  FALLOC(x0, n0 * 32);
+  WALLOC(char, x0, n0 * 32 * es);
   {
     ProfScope ps(c, st, "conv0_k5_kernel/L0", PK_CONV0, 0, 125, 1, 32, (int)es);
     EGONN_TRY(conv0_k5_forward(c, f0, m->conv0, 32, m->bn[0].scale, m->bn[0].shift, 1, x0, bf16, st, m->conv0_unit));
@@ -898,11 +890,11 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
   // ---- local head, descriptor / keypoint / sigma regressors (models/minkgl.py:287-308)
   auto local_head = [&](hipStream_t st) -> int {
     const int64_t n3 = P.cap[3], n4 = P.cap[4];
-    FALLOC(l4, n4 * LOCAL_CH);
+    WALLOC(char, l4, n4 * LOCAL_CH * es);
     EGONN_TRY(dense_forward({.in = x[4], .in_bf16 = bf16, .n = n4, .n_dev = cnt + 4, .cin = 128, .cout = LOCAL_CH, .W = m->l1x1[4],
-                             .wfrag = m->pk_l1x1[4], .out = l4, .out_bf16 = bf16},
+                             .wfrag = static_cast<const float*>(m->pk_l1x1[4]), .out = l4, .out_bf16 = bf16},
                             st));
-    FALLOC(u3, n3 * LOCAL_CH);
+    WALLOC(char, u3, n3 * LOCAL_CH * es);
     EGONN_TRY(conv_layer(c, st, conv_call(2, 3, l4, m->pk_lt[4], LOCAL_CH, LOCAL_CH, bf16, nullptr, 0, u3), "tconv"));
     EGONN_REQUIRE(m->ldec.cin == 64 && m->ldec.mid == 96 && m->ldec.cout == 128 && m->kp.mid == 32 && m->sg.mid == 32,
                   EGONN_ERR_STATE, "local heads: unexpected layer sizes");
@@ -918,9 +910,9 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
                                     m->l1x1[3], reinterpret_cast<const float*>(u3), bf16, lh_pack, c->dev_fp16_flag));
       return EGONN_OK;
     }
-    WALLOC(l3, n3 * LOCAL_CH);
+    WALLOC(float, l3, n3 * LOCAL_CH);
     EGONN_TRY(dense_forward({.in = x[3], .in_bf16 = bf16, .n = n3, .n_dev = cnt + 3, .cin = 64, .cout = LOCAL_CH, .W = m->l1x1[3],
-                             .wfrag = m->pk_l1x1[3], .residual = u3, .res_bf16 = bf16, .out = l3},
+                             .wfrag = static_cast<const float*>(m->pk_l1x1[3]), .residual = u3, .res_bf16 = bf16, .out = l3},
                             st));
     EGONN_TRY(local_heads_forward(l3, n3, cnt + 3, hw, P.lv[3].keys, 3, P.coord_bits, quant_mode, step,
                                   (flags & EGONN_FLAG_IGNORE_KP_REGRESSOR) ? 1 : 0, out_desc, out_kp, out_sigma, st, nullptr, nullptr, 0,
@@ -932,7 +924,7 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
     const BlockRef& b = m->blk[i];
     const Level& L = P.lv[i];
     const int64_t n = P.cap[i];
-    FALLOC(y, n * b.cin);
+    WALLOC(char, y, n * b.cin * es);
     {
       ConvCall cc = conv_call(1, i, x[i - 1], m->pk_convs[i], b.cin, b.cin, bf16, &m->bn[i], 1, y);
       if (gated_t2 && i == 2) {      // the block output of level 1 is evaluated on the gathered rows — see below
@@ -943,26 +935,11 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
       EGONN_TRY(conv_layer(c, st, cc, "k2s2"));
     }
     DBG_SYNC("L%d k2s2", i);
-    // ECABasicBlock (layers/eca_block.py:56-73)
-    FALLOC(t1, n * b.cout);
-    // conv1's output has ONE reader, conv2: when both run on the split kernel, conv1's epilogue writes it in split form (the
-    // fp16 hi | lo operands conv2 would otherwise make of every gathered fragment in its step loop; sconv_split.hip)
-    const bool t1_split = !switches().no_presplit && sconv_route(c, 0, i, b.cin, b.cout, bf16) == ROUTE_SPLIT &&
-                          sconv_route(c, 0, i, b.cout, b.cout, bf16) == ROUTE_SPLIT;
-    {
-      ConvCall cc = conv_call(0, i, y, m->pk_c1[i], b.cin, b.cout, bf16, &b.n1, 1, t1);
-      cc.split_io = t1_split ? 2 : 0;
-      EGONN_TRY(conv_layer(c, st, cc, "k3.conv1"));
-    }
-    FALLOC(t2, n * b.cout);
-    WALLOC(psum, (size_t)L.rg27.cap_groups * b.cout);
-    {
-      ConvCall cc = conv_call(0, i, t1, m->pk_c2[i], b.cout, b.cout, bf16, &b.n2, 0, t2);
-      cc.split_io = t1_split ? 1 : 0;
-      cc.psum = psum;
-      EGONN_TRY(conv_layer(c, st, cc, "k3.conv2"));
-    }
-    WALLOC(gate, (size_t)B * b.cout);
+    // ECABasicBlock (layers/eca_block.py:56-73); the gate comes from the column sums conv2's epilogue leaves behind
+    WALLOC(float, psum, (size_t)L.rg27.cap_groups * b.cout);
+    void* t2 = nullptr;
+    EGONN_TRY(block_convs(c, st, A, i, b, m->pk_c1[i], m->pk_c2[i], bf16, y, psum, &t2));
+    WALLOC(float, gate, (size_t)B * b.cout);
     DBG_SYNC("L%d convs", i);
     EGONN_TRY(eca_gate_groups(psum, L.rg27, L.boff, B, b.cout, b.eca, b.eca_k, gate, st));
     DBG_SYNC("L%d eca gate", i);
@@ -981,10 +958,9 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
       c->level_ch[i] = b.cout;
       continue;
     }
-    FALLOC(xo, n * b.cout);
+    WALLOC(char, xo, n * b.cout * es);
     // the 1x1 downsample branch with its BatchNorm (levels 2 and 4); its output and what rides on it follow
-    const DenseCall down{.in = y, .in_bf16 = bf16, .n = n, .n_dev = cnt + i, .cin = b.cin, .cout = b.cout, .W = b.down,
-                         .wfrag = m->pk_down[i], .scale = b.dn.scale, .shift = b.dn.shift, .out_bf16 = bf16};
+    const DenseCall down = down_call(b, y, bf16, n, cnt + i, m->pk_down[i]);
     if (b.down && !switches().no_fused_down && dense_gate_fusable(n, b.cin, b.cout)) {
       // blocks with a 1x1 downsample branch (levels 2 and 4): the branch, its BatchNorm and the gated residual + ReLU of the block's
       // tail in ONE launch — out = relu(t2 * gate[scan] + bn(y @ Wd)); the branch output never goes to memory (bitwise the result
@@ -996,7 +972,7 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
       EGONN_TRY(dense_forward(dc, st));
     } else {
       if (b.down) {
-        FALLOC(rd, n * b.cout);
+        WALLOC(char, rd, n * b.cout * es);
         DenseCall dc = down;
         dc.out = rd;
         EGONN_TRY(dense_forward(dc, st));
@@ -1022,11 +998,11 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
     // MinkHead (models/minkgl.py:46-60) in three launches instead of five: the three lateral 1x1 convolutions depend on the trunk
     // only — ONE grouped launch — and every FPN step `tconv(y) + lateral` is the transposed convolution with the lateral as its
     // epilogue residual.  a + b = b + a: bitwise the five-launch result (tools/check_bitwise_switches.py).
-    WALLOC(l7, P.cap[7] * GLOBAL_CH);
-    WALLOC(l6, P.cap[6] * GLOBAL_CH);
-    WALLOC(l5, P.cap[5] * GLOBAL_CH);
-    WALLOC(g6f, P.cap[6] * GLOBAL_CH);
-    WALLOC(g5f, P.cap[5] * GLOBAL_CH);
+    WALLOC(float, l7, P.cap[7] * GLOBAL_CH);
+    WALLOC(float, l6, P.cap[6] * GLOBAL_CH);
+    WALLOC(float, l5, P.cap[5] * GLOBAL_CH);
+    WALLOC(float, g6f, P.cap[6] * GLOBAL_CH);
+    WALLOC(float, g5f, P.cap[5] * GLOBAL_CH);
     const float* gin[3] = {reinterpret_cast<const float*>(x[7]), reinterpret_cast<const float*>(x[6]), reinterpret_cast<const float*>(x[5])};
     const int64_t gn[3] = {P.cap[7], P.cap[6], P.cap[5]};
     const int32_t* gnd[3] = {cnt + 7, cnt + 6, cnt + 5};
@@ -1050,38 +1026,30 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
                             .residual = up, .res_bf16 = up ? bf16 : 0, .out = out, .out_bf16 = out_bf16},
                            st);
     };
-    FALLOC(g7, P.cap[7] * GLOBAL_CH);
+    WALLOC(char, g7, P.cap[7] * GLOBAL_CH * es);
     EGONN_TRY(lateral(7, nullptr, g7, bf16));
-    FALLOC(u6, P.cap[6] * GLOBAL_CH);
+    WALLOC(char, u6, P.cap[6] * GLOBAL_CH * es);
     EGONN_TRY(conv_layer(c, st, conv_call(2, 6, g7, m->pk_gt[7], GLOBAL_CH, GLOBAL_CH, bf16, nullptr, 0, u6), "tconv"));
-    FALLOC(g6, P.cap[6] * GLOBAL_CH);
+    WALLOC(char, g6, P.cap[6] * GLOBAL_CH * es);
     EGONN_TRY(lateral(6, u6, g6, bf16));
-    FALLOC(u5, P.cap[5] * GLOBAL_CH);
+    WALLOC(char, u5, P.cap[5] * GLOBAL_CH * es);
     EGONN_TRY(conv_layer(c, st, conv_call(2, 5, g6, m->pk_gt[6], GLOBAL_CH, GLOBAL_CH, bf16, nullptr, 0, u5), "tconv"));
-    WALLOC(g5u, P.cap[5] * GLOBAL_CH);
+    WALLOC(float, g5u, P.cap[5] * GLOBAL_CH);
     EGONN_TRY(lateral(5, u5, g5u, 0));
     g5 = g5u;
     DBG_SYNC("global head");
     }
-    WALLOC(gh, P.cap[5] * m->gdec.mid);
-    WALLOC(gd, P.cap[5] * GLOBAL_DIM);
+    WALLOC(float, gh, P.cap[5] * m->gdec.mid);
+    WALLOC(float, gd, P.cap[5] * GLOBAL_DIM);
     EGONN_TRY(run_mlp(m->gdec, g5, P.cap[5], ACT_NONE, gh, gd, st, cnt + 5));
-    WALLOC(gp, (size_t)B * SEG_CHUNKS * GLOBAL_DIM);
+    WALLOC(float, gp, (size_t)B * SEG_CHUNKS * GLOBAL_DIM);
     // global pooling (layers/pooling.py:13-43): GeM (default, :72-86), SPoC = average (:59-69), MAC = max (:46-56)
-    if (flags & (EGONN_FLAG_POOL_SPOC | EGONN_FLAG_POOL_MAC)) {
-      const int mode = (flags & EGONN_FLAG_POOL_MAC) ? 2 : 0;
-      EGONN_TRY(segment_partial_sums(gd, P.lv[5].boff, B, GLOBAL_DIM, mode, nullptr, gp, st));
-      EGONN_TRY(pool_finish(gp, P.lv[5].boff, B, GLOBAL_DIM, mode, out_global, st));
-    } else {
-      EGONN_REQUIRE(m->gem_p, EGONN_ERR_STATE, "forward: GeM pooling needs the tensor 'global_pooling.pooling.p'");
-      EGONN_TRY(segment_partial_sums(gd, P.lv[5].boff, B, GLOBAL_DIM, 1, m->gem_p, gp, st));
-      EGONN_TRY(gem_finish(gp, P.lv[5].boff, B, GLOBAL_DIM, m->gem_p, out_global, st));
-    }
+    const Pooling pool = (flags & EGONN_FLAG_POOL_MAC) ? POOL_MAC : (flags & EGONN_FLAG_POOL_SPOC) ? POOL_SPOC : POOL_GEM;
+    EGONN_REQUIRE(pool != POOL_GEM || m->gem_p, EGONN_ERR_STATE, "forward: GeM pooling needs the tensor 'global_pooling.pooling.p'");
+    EGONN_TRY(global_pool(pool, gd, P.lv[5].boff, B, GLOBAL_DIM, m->gem_p, gp, out_global, st));
   }
 
   DBG_SYNC("global decoder + pooling");
-#undef WALLOC
-#undef FALLOC
   return EGONN_OK;
 }
 

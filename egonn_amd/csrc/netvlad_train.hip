@@ -102,12 +102,10 @@ API int egonn_netvlad_train_forward(egonn_ctx* ctx, int level, const float* x, i
   const int B = ctx->plan.batch;
   const int64_t N = ctx->plan.lv[level].n;
   const int32_t* boff = ctx->plan.lv[level].boff;
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) ctx->level_feat[l] = nullptr;
   const size_t nws = netvlad_train_forward_floats(B, N, C, D);
-  EGONN_TRY(ctx->work_arena.ensure(nws * 4 + 4096));
-  ctx->work_arena.reset();
-  float* ws = ctx->work_arena.alloc<float>(nws);
-  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
+  Arena* A;
+  EGONN_TRY(claim_work(ctx, nws * 4 + 4096, false, &A));
+  WALLOC(float, ws, nws);
   float* nvws = ws;
   float* cs = nvws + align_up(netvlad_workspace_floats(B, C, D), 64);
   const size_t csn = nvt_stats_scratch_floats(N);
@@ -595,12 +593,10 @@ API int egonn_netvlad_train_backward(egonn_ctx* ctx, int level, const float* x, 
   const int B = ctx->plan.batch;
   const int64_t N = ctx->plan.lv[level].n;
   const int32_t* boff = ctx->plan.lv[level].boff;
-  for (int l = 0; l < EGONN_NUM_LEVELS; ++l) ctx->level_feat[l] = nullptr;
   const size_t nws = netvlad_train_backward_floats(B, N, C, D);
-  EGONN_TRY(ctx->work_arena.ensure(nws * 4 + 4096));
-  ctx->work_arena.reset();
-  float* ws = ctx->work_arena.alloc<float>(nws);
-  EGONN_REQUIRE(ws, EGONN_ERR_STATE, "work arena too small");
+  Arena* A;
+  EGONN_TRY(claim_work(ctx, nws * 4 + 4096, false, &A));
+  WALLOC(float, ws, nws);
   const int64_t CK = (int64_t)C * NV_K;
   float* dvl = ws;
   float* dV = dvl + align_up((size_t)B * CK, 64);
