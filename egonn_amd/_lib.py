@@ -39,6 +39,9 @@ _SIGS = [
     ("egonn_debug_radix_sort_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
     ("egonn_debug_radix_sort", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(C.c_int32), _P, C.c_int64, _P]),
+    ("egonn_debug_dense_group3", C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    ("egonn_debug_global_tail_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("egonn_debug_global_tail", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P]),
     ("egonn_voxelize", C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
     ("egonn_ctx_reserve", C.c_int, [_P, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
     ("egonn_voxelize_device", C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
@@ -339,6 +342,42 @@ def debug_radix_sort(keys_in, vals_in, keys_out, vals_out, n: int, nbits: int, n
          vals_out.data_ptr(), int(n), int(nbits), _ptr(n_dev), _ptr(seg_offsets), B, int(idx_bits), int(bool(either_pair)),
          C.byref(pair), scratch_buf.data_ptr(), need if scratch_bytes is None else int(scratch_bytes))
     return pair.value
+
+
+def debug_dense_group3(xs, capacities, counts, ws, packed: bool):
+    """test hook (egonn_debug_dense_group3): three (capacity_q, 128) @ (128, 128) products in the grouped lateral launch, reading
+    packed fragments or the raw (cin, cout) kernels.  xs[q] holds at least max(capacity_q, 1) rows; counts[q] is the live count.
+    -> three (capacity_q, 128) outputs, -12345 in every row the launch did not write"""
+    lib = load()
+    dev = xs[0].device
+    arr = lambda ptrs: (C.c_void_p * 3)(*ptrs)  # noqa: E731
+    nds = [torch.tensor([int(c)], dtype=torch.int32, device=dev) for c in counts]
+    pks = [dense_pack_fragments(w, False) for w in ws] if packed else [None] * 3
+    bufs = [torch.full((max(int(c), 1), 128), -12345.0, dtype=torch.float32, device=dev) for c in capacities]
+    call(dev, lib.egonn_debug_dense_group3, arr([x.data_ptr() for x in xs]), (C.c_int64 * 3)(*[int(c) for c in capacities]),
+         arr([n.data_ptr() for n in nds]), arr([w.data_ptr() for w in ws]), arr([_ptr(p) for p in pks]),
+         arr([b.data_ptr() for b in bufs]))
+    return [b[:int(c)] for b, c in zip(bufs, capacities)]
+
+
+GLOBAL_TAIL_POOLING = {"GeM": 1, "MAC": 2, "SPoC": 3}
+
+
+def debug_global_tail(g5, row_offsets, n_dev, w0, b0, w1, b1, p, pooling: str, form: int):
+    """test hook (egonn_debug_global_tail): descriptor decoder + global pooling on the fp32 rows g5 (capacity, 128) of the scans
+    row_offsets (device int32, B + 1) below the live count n_dev (device int32).  form 0 = two dense launches + partial sums,
+    1 = the fused launch.  -> (partial (B, 32, 256), pooled (B, 256))"""
+    lib = load()
+    B = row_offsets.numel() - 1
+    cap = g5.shape[0]
+    need = lib.egonn_debug_global_tail_scratch_bytes(int(cap))
+    buf = scratch(need, g5.device)
+    partial = torch.empty((B, 32, 256), dtype=torch.float32, device=g5.device)
+    out = torch.empty((B, 256), dtype=torch.float32, device=g5.device)
+    call(g5.device, lib.egonn_debug_global_tail, g5.data_ptr(), row_offsets.data_ptr(), B, int(cap), n_dev.data_ptr(), w0.data_ptr(),
+         b0.data_ptr(), w1.data_ptr(), b1.data_ptr(), _ptr(p), GLOBAL_TAIL_POOLING[pooling], int(form), partial.data_ptr(),
+         out.data_ptr(), buf.data_ptr(), need)
+    return partial, out
 
 
 def require_gpu() -> torch.device:

@@ -232,6 +232,8 @@ struct Switches {
   bool no_fused_lateral;   // EGONN_NO_FUSED_LATERAL     the local head's level-3 lateral 1x1 convolution as its own launch
   bool no_gated_k2s2;      // EGONN_NO_GATED_K2S2        level 1's block tail as its own launch instead of inside level 2's strided convolution
   bool no_fused_ghead;     // EGONN_NO_FUSED_GHEAD       the global head as five launches instead of three
+  bool no_fused_gtail;     // EGONN_NO_FUSED_GTAIL       the global decoder and the pooling partial sums as three launches instead of one
+  bool no_packed_laterals; // EGONN_NO_PACKED_LATERALS   the global head's grouped lateral launch gathers the raw kernels instead of reading packed fragments
   bool no_split_heads;     // EGONN_NO_SPLIT_HEADS       the local heads' Linear layers on the exact fp32 kernel instead of the fp16 matrix pipe
   bool no_tail_split;      // EGONN_NO_TAIL_SPLIT        128->128 maps above the split level limit on the exact per-tile kernel
   bool no_task_order;      // EGONN_NO_TASK_ORDER        sparse-conv tasks in table order instead of longest-first (RowGroups::order4)

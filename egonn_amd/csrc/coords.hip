@@ -33,7 +33,8 @@ const Switches& switches() {
     const char* ds = getenv("EGONN_DEBUG_SYNC");
     return Switches{.debug_sync = ds && ds[0] == '1', .no_presplit = on("EGONN_NO_PRESPLIT"), .no_fused_down = on("EGONN_NO_FUSED_DOWN"),
                     .no_fused_lateral = on("EGONN_NO_FUSED_LATERAL"), .no_gated_k2s2 = on("EGONN_NO_GATED_K2S2"),
-                    .no_fused_ghead = on("EGONN_NO_FUSED_GHEAD"), .no_split_heads = on("EGONN_NO_SPLIT_HEADS"),
+                    .no_fused_ghead = on("EGONN_NO_FUSED_GHEAD"), .no_fused_gtail = on("EGONN_NO_FUSED_GTAIL"),
+                    .no_packed_laterals = on("EGONN_NO_PACKED_LATERALS"), .no_split_heads = on("EGONN_NO_SPLIT_HEADS"),
                     .no_tail_split = on("EGONN_NO_TAIL_SPLIT"), .no_task_order = on("EGONN_NO_TASK_ORDER"),
                     .flat_sort = on("EGONN_FLAT_SORT"), .sort_pairs = on("EGONN_SORT_PAIRS"), .no_search67 = on("EGONN_NO_SEARCH67"),
                     .no_dense_stream = on("EGONN_NO_DENSE_STREAM"),

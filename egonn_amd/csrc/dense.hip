@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void dense_kernel(const void* __restrict__ in_
 
 // dense_small_kernel: the same tile arithmetic for launches too small to hide latency (n < 8192 rows) — see its first comment.
 template <int W_OUT_IN, int CIN, bool IN_BF16>
-__device__ static inline void dense_small_body(const void* __restrict__ in_v, int64_t n,
+__device__ static inline __attribute__((always_inline)) void dense_small_body(const void* __restrict__ in_v, int64_t n,
                                                const float* __restrict__ W, int cout,
                                                const float* __restrict__ bias, const float* __restrict__ scale,
                                                const float* __restrict__ shift, int act,
@@ -152,26 +152,39 @@ __device__ static inline void dense_small_body(const void* __restrict__ in_v, in
   const float* bias_p = bias ? bias : W;
   const float* scale_p = scale ? scale : W;
   const float* shift_p = scale ? shift : W;
+  // W_OUT_IN = 2: W is the kernel in fragment order (dense_pack_frags; cout a multiple of 16) — the operand of a column tile is
+  // CIN / 16 16-byte loads per lane instead of CIN / 4 strided dword loads (W_OUT_IN = 0)
+  auto load_b = [&](int nt) {
+    const int col = min(ncol0 + nt * 16 + l15, cout - 1);
+#pragma unroll
+    for (int t = 0; t < KS; ++t) {
+      float4 v;
+      if (W_OUT_IN == 2) {
+        v = *reinterpret_cast<const float4*>(W + ((int64_t)((col >> 4) * KS + t) * 64 + lane) * 4);
+      } else if (W_OUT_IN == 1) {
+        v = *reinterpret_cast<const float4*>(W + (int64_t)col * CIN + 16 * t + 4 * g4);
+      } else {      // (32-bit unsigned offsets from one scalar base: one address register per load instead of two)
+        const uint32_t uc = (uint32_t)cout, o = (uint32_t)(16 * t + 4 * g4) * uc + (uint32_t)col;
+        v.x = W[o];
+        v.y = W[o + uc];
+        v.z = W[o + 2u * uc];
+        v.w = W[o + 3u * uc];
+      }
+      b[nt][t] = v;
+    }
+  };
+  // NUP column tiles' operands are requested up front: all four, except with 128 fp32 input channels and a raw (cin, cout)
+  // kernel — 128 strided dword loads, whose results and addresses beside the rows do not fit the 256 registers of two waves per
+  // SIMD.  There the operand of the fourth tile is requested after the first tile's MFMAs, into its registers, and lands behind
+  // the MFMAs of the second and third.  Same MFMA order per element.
+  constexpr int NUP = (CIN >= 128 && !IN_BF16 && W_OUT_IN == 0) ? 3 : 4;
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) {
     const int col = min(ncol0 + nt * 16 + l15, cout - 1);
     bi[nt] = bias_p[col];
     sc[nt] = scale_p[col];
     sh[nt] = shift_p[col];
-#pragma unroll
-    for (int t = 0; t < KS; ++t) {
-      float4 v;
-      if (W_OUT_IN) {
-        v = *reinterpret_cast<const float4*>(W + (int64_t)col * CIN + 16 * t + 4 * g4);
-      } else {
-        const float* wp = W + (int64_t)(16 * t + 4 * g4) * cout + col;
-        v.x = wp[0];
-        v.y = wp[cout];
-        v.z = wp[2 * (int64_t)cout];
-        v.w = wp[3 * (int64_t)cout];
-      }
-      b[nt][t] = v;
-    }
+    if (nt < NUP) load_b(nt);
   }
   float res[4][4];
   {
@@ -206,6 +219,10 @@ __device__ static inline void dense_small_body(const void* __restrict__ in_v, in
   for (int nt = 0; nt < 4; ++nt) {
     const int col = ncol0 + nt * 16 + l15;
     if (ncol0 + nt * 16 >= cout) break;
+    if constexpr (NUP < 4) {
+      if (nt >= 1 && nt + NUP - 1 < 4) load_b(nt + NUP - 1);
+      __builtin_amdgcn_sched_barrier(0);      // (the request stays between the first and the second tile's MFMAs)
+    }
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < KS; ++t) {
@@ -697,19 +714,22 @@ int dense_forward(const DenseCall& c, hipStream_t stream) {
 
 // Three (n_i, 128) @ (128, 128) products ((cin, cout) kernels, no bias / BN / activation) in ONE launch of dense_small3_kernel;
 // fp32 rows in and out.
+// wfrag (nullable, all three or none): the same kernels in fragment order (dense_pack_frags) — read instead of W.
 bool dense_group3_rows(int64_t n) { return n == 0 || dense_route(n, 128, 128, -1) == DENSE_SMALL; }
-int dense_small_group3(const float* const* in, const int64_t* n, const int32_t* const* n_dev, const float* const* W, float* const* out,
-                       hipStream_t stream) {
+int dense_small_group3(const float* const* in, const int64_t* n, const int32_t* const* n_dev, const float* const* W,
+                       const float* const* wfrag, float* const* out, hipStream_t stream) {
+  const bool packed = wfrag && wfrag[0] && wfrag[1] && wfrag[2];
   DenseGroup3 g;
   int bx = 0;
   for (int q = 0; q < 3; ++q) {
     EGONN_REQUIRE(dense_group3_rows(n[q]), EGONN_ERR_INVALID, "dense(group): %lld rows", (long long)n[q]);
-    g.in[q] = in[q]; g.W[q] = W[q]; g.out[q] = out[q]; g.n_dev[q] = n_dev[q]; g.n[q] = n[q];
+    g.in[q] = in[q]; g.W[q] = packed ? wfrag[q] : W[q]; g.out[q] = out[q]; g.n_dev[q] = n_dev[q]; g.n[q] = n[q];
     g.bx0[q] = bx;
     bx += (int)cdiv(std::max<int64_t>(n[q], 1), 64);
   }
   g.bx0[3] = bx;
-  hipLaunchKernelGGL((dense_small3_kernel<0, 128, false>), dim3((unsigned)bx, 2), dim3(256), 0, stream, g, 128, 0);
+  if (packed) hipLaunchKernelGGL((dense_small3_kernel<2, 128, false>), dim3((unsigned)bx, 2), dim3(256), 0, stream, g, 128, 0);
+  else hipLaunchKernelGGL((dense_small3_kernel<0, 128, false>), dim3((unsigned)bx, 2), dim3(256), 0, stream, g, 128, 0);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -751,6 +771,18 @@ API int egonn_debug_dense(const void* in, int in_bf16, int64_t rows_capacity, co
                         .residual = residual, .res_bf16 = res_bf16 ? 1 : 0, .gate = gate, .boff = boff, .B = B, .out = out,
                         .out_bf16 = out_bf16 ? 1 : 0, .form = form},
                        (hipStream_t)stream);
+}
+// the grouped lateral launch on the caller's three problems (tests/test_gpu_global_tail.py): packed = all NULL reads the raw kernels
+API int egonn_debug_dense_group3(const float* const in[3], const int64_t rows_capacity[3], const int32_t* const n_dev[3],
+                                 const float* const weight[3], const float* const packed[3], float* const out[3], void* stream) {
+  EGONN_REQUIRE(in && rows_capacity && n_dev && weight && packed && out, EGONN_ERR_INVALID, "debug_dense_group3: null argument");
+  for (int q = 0; q < 3; ++q) {
+    EGONN_REQUIRE(in[q] && n_dev[q] && weight[q] && out[q] && rows_capacity[q] >= 0 && !packed[q] == !packed[0], EGONN_ERR_INVALID,
+                  "debug_dense_group3: bad arguments of problem %d", q);
+    EGONN_REQUIRE(dense_group3_rows(rows_capacity[q]), EGONN_ERR_INVALID, "debug_dense_group3: %lld rows are not a small launch",
+                  (long long)rows_capacity[q]);
+  }
+  return dense_small_group3(in, rows_capacity, n_dev, weight, packed, out, (hipStream_t)stream);
 }
 // what dense_forward would launch for a shape — no device call: out = route (DenseRoute), grid x, grid y, dynamic LDS bytes, colblk
 API int egonn_debug_dense_route(int64_t rows, int cin, int cout, int form, int gate_scans, int32_t out[5]) {

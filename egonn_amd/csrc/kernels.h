@@ -148,9 +148,19 @@ bool dense_gate_fusable(int64_t n, int cin, int cout);
 // three independent (n_i, 128) @ (128, 128) products in one launch of the small kernel: fp32 rows, no epilogue.  Every n_i must
 // pass dense_group3_rows (the small kernel is what dense_route gives the product alone, or there are no rows)
 bool dense_group3_rows(int64_t n);
-int dense_small_group3(const float* const* in, const int64_t* n, const int32_t* const* n_dev, const float* const* W, float* const* out,
-                       hipStream_t stream);
+// wfrag (nullable; all three or none): the kernels in fragment order, read as 16-byte loads instead of W
+int dense_small_group3(const float* const* in, const int64_t* n, const int32_t* const* n_dev, const float* const* W,
+                       const float* const* wfrag, float* const* out, hipStream_t stream);
 int dense_pack_frags(const float* W, int w_out_in, int cin, int cout, float* out, hipStream_t stream);   // cin * cout floats
+
+// global_tail.hip ------------------------------------------------------------------------------
+// The global descriptor decoder in its shipped sizes (Linear 128 -> 192 + ReLU, Linear 192 -> 256) and the partial sums of the
+// global pooling in one launch: partial[b][chunk][256] of segment_partial_sums(decoder(g5), pow_mode), bitwise, without the hidden
+// map and the decoder output in memory.  wf0 / wf1: the two (out, in) kernels in fragment order (dense_pack_frags); rows of g5 are
+// read inside [boff[0], boff[B]) and below ncap only
+constexpr int GTAIL_CIN = 128, GTAIL_MID = 192, GTAIL_OUT = 256;
+int global_tail_fused(const float* g5, int64_t ncap, const int32_t* boff, int B, const float* wf0, const float* b0, const float* wf1,
+                      const float* b1, int pow_mode, const float* p, float* partial, hipStream_t stream);
 
 // rowwise.hip ----------------------------------------------------------------------------------
 int bn_fold(const float* w, const float* b, const float* rm, const float* rv, float eps, int c, float* scale,

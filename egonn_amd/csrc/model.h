@@ -83,7 +83,8 @@ struct MlpRef {
 // touches the device), then commit() sizes both buffers from the registrations, allocates each once (growing only), and carves,
 // packs and folds in registration order: no device call before the last state_dict lookup.
 struct ModelStore {
-  enum Form { RG32, RG16, SPLIT, DENSE };   // pack_rg_weights fp32 / bf16, pack_split_weights, dense_pack_frags
+  enum Form { RG32, RG16, SPLIT, DENSE, DENSE_OI };   // pack_rg_weights fp32 / bf16, pack_split_weights, dense_pack_frags of a
+                                                       // (cin, cout) 1x1 kernel / of an (out, in) nn.Linear kernel
   struct Pack { Form form; const float* w; int K, ci, co; size_t off; const void** dst; };
   std::vector<BnRef*> bns;                  // the registered objects must stay where they are until commit()
   std::vector<Pack> packs;
@@ -124,6 +125,7 @@ struct egonn_model {
   const float** lh_ptrs = nullptr;   // device array of the six weight pointers (the packer's input)
   egonn::PackedKernel pk_convs[8], pk_c1[8], pk_c2[8], pk_gt[8], pk_lt[8];   // fp32, bf16 (EGONN_FLAG_BF16) and fp16-split forms
   const void *pk_down[8] = {}, *pk_l1x1[8] = {};   // blk[i].down / l1x1[l] in the dense kernels' fragment order (dense_pack_frags; null: no such form)
+  const void *pk_g1x1[8] = {}, *pk_gdec[2] = {};   // global_head.conv1x1[l] and the global decoder's two Linear kernels, the same order
   egonn::MinkFpnModel* fpn = nullptr;   // egonn_minkfpn_finalize: the MinkFPN view of the same tensors (minkfpn.hip)
 };
 
@@ -160,6 +162,13 @@ int block_tail(const float* x, const float* res, const int32_t* boff, int B, int
 enum Pooling { POOL_GEM = 1, POOL_MAC = 2, POOL_SPOC = 3 };
 int global_pool(Pooling method, const float* x, const int32_t* boff, int B, int C, const float* p, float* partial, float* out,
                 hipStream_t st);   // p: the GeM exponent (device); partial: B * SEG_CHUNKS * C floats
+// The tail of the global head on the fp32 rows of g5 (capacity ncap, live count n_dev, scans boff): out[b] = pooling of
+// decoder(g5 rows of scan b).  fused: one launch leaves the pooling's partial sums (global_tail_fused; needs global_tail_fusable
+// and the decoder's packed kernels pk[0..1]); else the decoder's two dense launches write gh (ncap x mid) and gd (ncap x cout) and
+// the partial sums are a third.  Bitwise the same `partial` and `out` either way.
+bool global_tail_fusable(const MlpRef& r);
+int global_tail(const MlpRef& r, const void* const* pk, const float* g5, int64_t ncap, const int32_t* n_dev, const int32_t* boff, int B,
+                Pooling method, const float* p, bool fused, float* gh, float* gd, float* partial, float* out, hipStream_t st);
 
 // topdown.hip: one top-down step of an FPN on the fp16-split pipe,
 //   out[o] = x_coarse[parent(o)] @ W_t[key(o) & 7] (+ x_lateral[o] @ W_l)

@@ -632,6 +632,7 @@ int ModelStore::commit(hipStream_t st) {
       case RG16: EGONN_TRY(pack_rg_weights(k.w, k.K, k.ci, k.co, 1, 0, 0, out, st)); break;
       case SPLIT: EGONN_TRY(pack_split_weights(k.w, k.K, k.ci, k.co, 0, 0, out, st)); break;
       case DENSE: EGONN_TRY(dense_pack_frags(k.w, 0, k.ci, k.co, reinterpret_cast<float*>(out), st)); break;
+      case DENSE_OI: EGONN_TRY(dense_pack_frags(k.w, 1, k.ci, k.co, reinterpret_cast<float*>(out), st)); break;
     }
     *k.dst = out;
   }
@@ -673,10 +674,11 @@ API int egonn_model_finalize(egonn_model* m, void* stream) {
   S.begin();
   // ---- resolve every tensor (shapes checked, the offending key named) and register what the store folds and packs: every
   // sparse-conv kernel in item-major MFMA fragment order (sconv.hip), fp32, bf16 and split; the 1x1 kernels the forward runs
-  // through the streaming dense kernel in its fragment order (fp32 only).  No device work before the last lookup.
-  auto dense = [&](const float* w, int ci, int co, const void** dst) {
+  // through the streaming dense kernel, the global head's lateral 1x1 kernels and its decoder's two Linear kernels in the dense
+  // kernels' fragment order (fp32 only).  No device work before the last lookup.
+  auto dense = [&](const float* w, int ci, int co, const void** dst, ModelStore::Form form = ModelStore::DENSE) {
     *dst = nullptr;
-    if (ci % 16 == 0 && co % 16 == 0) S.add_pack(ModelStore::DENSE, w, 1, ci, co, dst);
+    if (ci % 16 == 0 && co % 16 == 0) S.add_pack(form, w, 1, ci, co, dst);
   };
   EGONN_TRY(get_tensor(m, "trunk.convs.0.kernel", {125, 1, 32}, &m->conv0));
   EGONN_TRY(get_bn(m, "trunk.bn.0", 32, &m->bn[0], &S));
@@ -695,8 +697,10 @@ API int egonn_model_finalize(egonn_model* m, void* stream) {
     if (b.down) dense(b.down, inpl, cout, &m->pk_down[i]);
     inpl = cout;
   }
-  for (int l : {5, 6, 7})
+  for (int l : {5, 6, 7}) {
     EGONN_TRY(get_tensor(m, "global_head.conv1x1." + std::to_string(l) + ".kernel", {PLANES[l - 1], GLOBAL_CH}, &m->g1x1[l]));
+    dense(m->g1x1[l], PLANES[l - 1], GLOBAL_CH, &m->pk_g1x1[l]);
+  }
   for (int l : {6, 7}) {
     EGONN_TRY(get_tensor(m, "global_head.tconv." + std::to_string(l) + ".kernel", {8, GLOBAL_CH, GLOBAL_CH}, &m->gt[l]));
     S.add_kernel(m->gt[l], 8, GLOBAL_CH, GLOBAL_CH, true, &m->pk_gt[l]);
@@ -710,6 +714,11 @@ API int egonn_model_finalize(egonn_model* m, void* stream) {
   m->gem_p = nullptr;                  // GeM exponent; MAC / SPoC pooling (layers/pooling.py:46-69) has no parameter
   if (m->t.count("global_pooling.pooling.p")) EGONN_TRY(get_tensor(m, "global_pooling.pooling.p", {1}, &m->gem_p));
   EGONN_TRY(get_mlp(m, "global_descriptor_decoder", GLOBAL_CH, GLOBAL_DIM + (GLOBAL_CH - GLOBAL_DIM) / 2, GLOBAL_DIM, &m->gdec));
+  m->pk_gdec[0] = m->pk_gdec[1] = nullptr;
+  if (global_tail_fusable(m->gdec)) {      // the fused tail of the global head reads both Linear kernels in fragment order
+    dense(m->gdec.w0, m->gdec.cin, m->gdec.mid, &m->pk_gdec[0], ModelStore::DENSE_OI);
+    dense(m->gdec.w1, m->gdec.mid, m->gdec.cout, &m->pk_gdec[1], ModelStore::DENSE_OI);
+  }
   EGONN_TRY(get_mlp(m, "local_descriptor_decoder", LOCAL_CH, LOCAL_DIM + (LOCAL_CH - LOCAL_DIM) / 2, LOCAL_DIM, &m->ldec));
   EGONN_TRY(get_mlp(m, "local_keypoint_regressor", LOCAL_CH, LOCAL_CH / 2, 3, &m->kp));
   EGONN_TRY(get_mlp(m, "local_sigma_regressor", LOCAL_CH, LOCAL_CH / 2, 1, &m->sg));
@@ -813,15 +822,31 @@ DenseCall down_call(const BlockRef& b, const void* in, int bf16, int64_t n, cons
                    .wfrag = static_cast<const float*>(wfrag), .scale = b.dn.scale, .shift = b.dn.shift, .out_bf16 = bf16};
 }
 
+// pow_mode of the partial sums: GeM = sum of clamp(x)^p (layers/pooling.py:72-86), MAC = max (:46-56), SPoC = average (:59-69)
+static int pool_pow_mode(Pooling method) { return method == POOL_GEM ? 1 : method == POOL_MAC ? 2 : 0; }
+static int global_pool_finish(Pooling method, const float* partial, const int32_t* boff, int B, int C, const float* p, float* out,
+                              hipStream_t st) {
+  if (method == POOL_GEM) return gem_finish(partial, boff, B, C, p, out, st);
+  return pool_finish(partial, boff, B, C, pool_pow_mode(method), out, st);
+}
 int global_pool(Pooling method, const float* x, const int32_t* boff, int B, int C, const float* p, float* partial, float* out,
                 hipStream_t st) {
-  if (method == POOL_GEM) {       // GeM (layers/pooling.py:72-86)
-    EGONN_TRY(segment_partial_sums(x, boff, B, C, 1, p, partial, st));
-    return gem_finish(partial, boff, B, C, p, out, st);
+  EGONN_TRY(segment_partial_sums(x, boff, B, C, pool_pow_mode(method), method == POOL_GEM ? p : nullptr, partial, st));
+  return global_pool_finish(method, partial, boff, B, C, p, out, st);
+}
+
+bool global_tail_fusable(const MlpRef& r) { return r.cin == GTAIL_CIN && r.mid == GTAIL_MID && r.cout == GTAIL_OUT; }
+int global_tail(const MlpRef& r, const void* const* pk, const float* g5, int64_t ncap, const int32_t* n_dev, const int32_t* boff, int B,
+                Pooling method, const float* p, bool fused, float* gh, float* gd, float* partial, float* out, hipStream_t st) {
+  if (fused) {
+    EGONN_REQUIRE(global_tail_fusable(r) && pk && pk[0] && pk[1], EGONN_ERR_STATE, "global tail: no fused form for %d->%d->%d", r.cin,
+                  r.mid, r.cout);
+    EGONN_TRY(global_tail_fused(g5, ncap, boff, B, static_cast<const float*>(pk[0]), r.b0, static_cast<const float*>(pk[1]), r.b1,
+                                pool_pow_mode(method), method == POOL_GEM ? p : nullptr, partial, st));
+    return global_pool_finish(method, partial, boff, B, r.cout, p, out, st);
   }
-  const int mode = method == POOL_MAC ? 2 : 0;     // MAC = max (:46-56), SPoC = average (:59-69)
-  EGONN_TRY(segment_partial_sums(x, boff, B, C, mode, nullptr, partial, st));
-  return pool_finish(partial, boff, B, C, mode, out, st);
+  EGONN_TRY(run_mlp(r, g5, ncap, ACT_NONE, gh, gd, st, n_dev));
+  return global_pool(method, gd, boff, B, r.cout, p, partial, out, st);
 }
 
 int block_tail(const float* x, const float* res, const int32_t* boff, int B, int64_t n, int ch, const float* eca, int eca_k,
@@ -1008,7 +1033,9 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
     const int32_t* gnd[3] = {cnt + 7, cnt + 6, cnt + 5};
     const float* gw[3] = {m->g1x1[7], m->g1x1[6], m->g1x1[5]};
     float* gout[3] = {l7, l6, l5};
-    EGONN_TRY(dense_small_group3(gin, gn, gnd, gw, gout, st));
+    const float* gpk[3] = {static_cast<const float*>(m->pk_g1x1[7]), static_cast<const float*>(m->pk_g1x1[6]),
+                           static_cast<const float*>(m->pk_g1x1[5])};
+    EGONN_TRY(dense_small_group3(gin, gn, gnd, gw, switches().no_packed_laterals ? nullptr : gpk, gout, st));
     for (int lv = 6; lv >= 5; --lv) {
       ConvCall cc = conv_call(2, lv, lv == 6 ? l7 : g6f, m->pk_gt[lv + 1], GLOBAL_CH, GLOBAL_CH, 0, nullptr, 0, lv == 6 ? g6f : g5f);
       cc.residual = lv == 6 ? l6 : l5;
@@ -1041,16 +1068,60 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
     }
     WALLOC(float, gh, P.cap[5] * m->gdec.mid);
     WALLOC(float, gd, P.cap[5] * GLOBAL_DIM);
-    EGONN_TRY(run_mlp(m->gdec, g5, P.cap[5], ACT_NONE, gh, gd, st, cnt + 5));
     WALLOC(float, gp, (size_t)B * SEG_CHUNKS * GLOBAL_DIM);
     // global pooling (layers/pooling.py:13-43): GeM (default, :72-86), SPoC = average (:59-69), MAC = max (:46-56)
     const Pooling pool = (flags & EGONN_FLAG_POOL_MAC) ? POOL_MAC : (flags & EGONN_FLAG_POOL_SPOC) ? POOL_SPOC : POOL_GEM;
     EGONN_REQUIRE(pool != POOL_GEM || m->gem_p, EGONN_ERR_STATE, "forward: GeM pooling needs the tensor 'global_pooling.pooling.p'");
-    EGONN_TRY(global_pool(pool, gd, P.lv[5].boff, B, GLOBAL_DIM, m->gem_p, gp, out_global, st));
+    // decoder + partial sums in ONE launch when the decoder has its shipped sizes (g5 is fp32 for both map precisions): the hidden
+    // map and the decoder output are never written; bitwise the partial sums of the three launches (tests/test_gpu_global_tail.py)
+    const bool fused_tail = !switches().no_fused_gtail && global_tail_fusable(m->gdec) && m->pk_gdec[0] && m->pk_gdec[1];
+    EGONN_TRY(global_tail(m->gdec, m->pk_gdec, g5, P.cap[5], cnt + 5, P.lv[5].boff, B, pool, m->gem_p, fused_tail, gh, gd, gp, out_global, st));
   }
 
   DBG_SYNC("global decoder + pooling");
   return EGONN_OK;
+}
+
+// ------------------------------------------------------------------ test hook (tests/test_gpu_global_tail.py; no product path calls it)
+// global_tail on the caller's rows and decoder, without a context or a model: scratch = hidden map | decoder output | the two
+// kernels in fragment order
+static size_t debug_tail_span(int64_t ncap) {
+  return align_up((size_t)ncap * GTAIL_MID * 4, 256) + align_up((size_t)ncap * GTAIL_OUT * 4, 256) +
+         align_up((size_t)GTAIL_CIN * GTAIL_MID * 4, 256) + align_up((size_t)GTAIL_MID * GTAIL_OUT * 4, 256) + 1024;
+}
+API int64_t egonn_debug_global_tail_scratch_bytes(int64_t rows_capacity) {
+  if (rows_capacity < 0 || rows_capacity >= (1ll << 31) / GTAIL_OUT) return -1;
+  return (int64_t)debug_tail_span(rows_capacity);
+}
+API int egonn_debug_global_tail(const float* g5, const int32_t* row_offsets, int batch_size, int64_t rows_capacity, const int32_t* n_dev,
+                                const float* w0, const float* b0, const float* w1, const float* b1, const float* p, int pooling, int form,
+                                float* partial, float* out, void* scratch, int64_t scratch_bytes, void* stream) {
+  EGONN_REQUIRE(g5 && row_offsets && n_dev && w0 && b0 && w1 && b1 && partial && out && scratch, EGONN_ERR_INVALID,
+                "debug_global_tail: null pointer");
+  EGONN_REQUIRE(batch_size >= 1 && batch_size <= EGONN_MAX_BATCH, EGONN_ERR_INVALID, "debug_global_tail: batch_size=%d outside [1, %d]",
+                batch_size, EGONN_MAX_BATCH);
+  EGONN_REQUIRE(rows_capacity >= 0 && rows_capacity < (1ll << 31) / GTAIL_OUT, EGONN_ERR_INVALID,
+                "debug_global_tail: rows_capacity=%lld outside [0, 2^31 / %d)", (long long)rows_capacity, GTAIL_OUT);
+  EGONN_REQUIRE(pooling >= POOL_GEM && pooling <= POOL_SPOC && (pooling != POOL_GEM || p), EGONN_ERR_INVALID,
+                "debug_global_tail: pooling=%d (1 GeM with its exponent, 2 MAC, 3 SPoC)", pooling);
+  EGONN_REQUIRE(form == 0 || form == 1, EGONN_ERR_INVALID, "debug_global_tail: form=%d (0 three launches, 1 the fused launch)", form);
+  const size_t need = debug_tail_span(rows_capacity);
+  EGONN_REQUIRE(scratch_bytes >= (int64_t)need && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
+                "debug_global_tail: scratch needs %lld bytes, 256-byte aligned", (long long)need);
+  hipStream_t st = (hipStream_t)stream;
+  Arena ws = Arena::view(scratch, need);
+  float* gh = ws.alloc<float>((size_t)rows_capacity * GTAIL_MID);
+  float* gd = ws.alloc<float>((size_t)rows_capacity * GTAIL_OUT);
+  float* pk0 = ws.alloc<float>((size_t)GTAIL_CIN * GTAIL_MID);
+  float* pk1 = ws.alloc<float>((size_t)GTAIL_MID * GTAIL_OUT);
+  EGONN_REQUIRE(gh && gd && pk0 && pk1, EGONN_ERR_STATE, "debug_global_tail: scratch span too small");
+  const MlpRef r{.w0 = w0, .b0 = b0, .w1 = w1, .b1 = b1, .cin = GTAIL_CIN, .mid = GTAIL_MID, .cout = GTAIL_OUT};
+  const void* pk[2] = {pk0, pk1};
+  if (form == 1) {
+    EGONN_TRY(dense_pack_frags(w0, 1, r.cin, r.mid, pk0, st));
+    EGONN_TRY(dense_pack_frags(w1, 1, r.mid, r.cout, pk1, st));
+  }
+  return global_tail(r, pk, g5, rows_capacity, n_dev, row_offsets, batch_size, (Pooling)pooling, p, form == 1, gh, gd, partial, out, st);
 }
 
 API int egonn_forward_level_features(egonn_ctx* c, int level, float* out, int channels, void* stream) {

@@ -97,6 +97,26 @@ int64_t egonn_debug_radix_sort_scratch_bytes(int64_t n, int n_segments);
 int egonn_debug_radix_sort(uint64_t* keys_in, uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n, int nbits,
                            const int64_t* n_dev, const int64_t* seg_offsets, int n_segments, int idx_bits, int either_pair,
                            int32_t* result_pair, void* scratch, int64_t scratch_bytes, void* stream);
+/* test hook: the tail of the global head (descriptor decoder Linear 128 -> 192 + ReLU, Linear 192 -> 256, then the global
+ * pooling) on the caller's rows, without a context or a model.  g5: DEVICE fp32 (rows_capacity, 128); row_offsets: DEVICE int32
+ * (batch_size + 1), the rows of scan b are [row_offsets[b], row_offsets[b+1]), all below the live count n_dev (DEVICE int32,
+ * <= rows_capacity); rows from the live count on are never read.  w0 (192, 128), b0, w1 (256, 192), b1: the decoder in nn.Linear
+ * layout; pooling: 1 = GeM with the exponent p (DEVICE), 2 = MAC, 3 = SPoC (p nullable).  form 0: the decoder as two dense
+ * launches, then the partial sums; form 1: one fused launch on the kernels in fragment order.  partial: DEVICE
+ * (batch_size, 32 chunks, 256) partial sums of the pooling; out: DEVICE (batch_size, 256).  Both forms give the same bits.
+ * scratch: egonn_debug_global_tail_scratch_bytes(rows_capacity) bytes (-1 on a bad capacity), 256-byte aligned.  No host
+ * synchronisation. */
+/* test hook: the grouped lateral launch of MinkHead — three independent (n_q, 128) @ (128, 128) products, fp32 rows, (cin, cout)
+ * kernels, no epilogue — on the caller's DEVICE buffers.  The arrays are HOST arrays of three entries: in[q] (rows_capacity[q], 128),
+ * n_dev[q] (DEVICE int32 live count <= rows_capacity[q]; rows from it on are not written), weight[q], out[q]; packed[q] = the
+ * kernel in fragment order (egonn_dense_pack_fragments) for all three, or NULL for all three: the raw kernels are gathered.  Every
+ * capacity must be one the dense launcher gives its small kernel (below 8192 rows).  Both forms give the bits of egonn_dense. */
+int egonn_debug_dense_group3(const float* const in[3], const int64_t rows_capacity[3], const int32_t* const n_dev[3],
+                             const float* const weight[3], const float* const packed[3], float* const out[3], void* stream);
+int64_t egonn_debug_global_tail_scratch_bytes(int64_t rows_capacity);
+int egonn_debug_global_tail(const float* g5, const int32_t* row_offsets, int batch_size, int64_t rows_capacity, const int32_t* n_dev,
+                            const float* w0, const float* b0, const float* w1, const float* b1, const float* p, int pooling, int form,
+                            float* partial, float* out, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------ coordinate plan
  * replaces ME.utils.sparse_quantize      datasets/quantization.py:42,83   (Cartesian/Polar quantizer __call__)
