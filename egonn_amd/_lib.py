@@ -103,6 +103,7 @@ _SIGS = [
     ("egonn_debug_dense", C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_int,
                                     _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     ("egonn_debug_dense_route", C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    ("egonn_debug_sconv_choice", C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int32)]),
     ("egonn_dense_backward_weight", C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int64, _P, _P, C.c_int64, _P]),
     ("egonn_conv_backward_weight", C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P,
                                              C.c_int64, _P]),
@@ -314,6 +315,30 @@ def debug_dense(x, weight, out_in: bool, out, form: int, n_dev=None, packed=None
          int(bool(out_in)), _ptr(packed), _ptr(bias), _ptr(scale), _ptr(shift), int(act), _ptr(residual), bf(residual), _ptr(gate),
          _ptr(boff), B, out.data_ptr(), bf(out), int(form))
     return out
+
+
+# codes of Context.set_naive_conv / egonn_debug_set_naive_conv (the table: include/egonn_hip.h)
+CONV_PRODUCT, CONV_PLAIN, CONV_RING, CONV_COOP, CONV_RING2, CONV_DMA, CONV_DMA3, CONV_TRACED = 0, 1, 2, 4, 8, 16, 32, 128
+CONV_SPLIT = 1000                      # + cfg: the split kernel in an explicit configuration
+CFG_NW4, CFG_NW8, CFG_RESIDENT = 142, 182, 183
+CFG_PARTS, CFG_TRACED = 400, 9000      # + CFG_PARTS * (1 + log2(column parts)), + CFG_TRACED
+SCONV_ROUTES = ("plain", "split", "tail_split", "wg", "dma", "rg")     # SconvRoute of egonn_amd/csrc/kernels.h, from 0
+SCONV_CHOICE_FIELDS = ("route", "kernel", "NW", "NSW", "KW", "KS", "GATED", "TRACE", "resident", "KSP", "D", "G", "SPLIT", "PIPE",
+                       "gx", "gy", "gz", "block", "lds", "kparts")
+
+
+def debug_sconv_choice(kind: int, level: int, cin: int, cout: int, cap_groups: int, *, code: int = 0, bf16: int = 0, gated: int = 0,
+                       split_io: int = 0, residual: int = 0, split_max_level: int = 5, autoscale: int = 0, resident_mask: int = -1,
+                       max_workgroups: int = 0, kparts: int = -1, kw: int = -1, col_parts: int = -1) -> dict:
+    """test hook (egonn_debug_sconv_choice, no device needed): the launch a sparse-convolution layer gets under a setting, as a dict
+    of SCONV_CHOICE_FIELDS (route and kernel by name)"""
+    arg = (C.c_int32 * 16)(int(code), kind, level, cin, cout, int(bf16), int(gated), split_io, int(residual), split_max_level,
+                           int(autoscale), resident_mask, max_workgroups, kparts, kw, col_parts)
+    out = (C.c_int32 * 20)()
+    check(load().egonn_debug_sconv_choice(arg, int(cap_groups), out))
+    d = dict(zip(SCONV_CHOICE_FIELDS, out))
+    d["route"], d["kernel"] = SCONV_ROUTES[d["route"]], SCONV_ROUTES[d["kernel"]]
+    return d
 
 
 DENSE_ROUTES = ("none", "stream", "lds", "small", "tile", "plain")      # DenseRoute of egonn_amd/csrc/kernels.h, from 0
@@ -549,8 +574,9 @@ class Context:
         self._call(self.lib.egonn_debug_rowgroup_perm, self.h, map_kind, level_out, pm.data_ptr(), ng, C.byref(n))
         return pm
 
-    def set_naive_conv(self, on: bool):
-        """tests only: route this context's sparse convolutions through the plain (non-MFMA) kernel."""
+    def set_naive_conv(self, on):
+        """tests / measurements only: True or CONV_PLAIN routes this context's sparse convolutions through the plain (non-MFMA)
+        kernel; any other CONV_* code (or CONV_SPLIT + cfg) forces that kernel; False / CONV_PRODUCT = the product choice."""
         check(self.lib.egonn_debug_set_naive_conv(self.h, int(on)))
 
     def keep_level_features(self, on: bool):

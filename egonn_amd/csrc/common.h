@@ -242,7 +242,7 @@ struct Switches {
   bool no_dense_stream;    // EGONN_NO_DENSE_STREAM      1x1 convolutions on >= 8192 rows on the persistent LDS kernel instead of its streaming form
   int split_max_level;     // EGONN_SPLIT_MAX_LEVEL=l    replaces a context's split level limit (unless that is -1: exact fp32); -1 = unset
   int split_max_level_k8;  // EGONN_SPLIT_MAX_LEVEL_K8=l the limit of the 8-slot maps (k=2,s=2 and transposed) alone; -1 = unset
-  int split_cfg;           // EGONN_SPLIT_CFG=cfg        workgroup shape of the lock-step split kernel (sconv_split_forward); 0 = unset
+  int split_cfg;           // EGONN_SPLIT_CFG=cfg        workgroup shape of the lock-step split kernel (sconv_decode_cfg); 0 = unset
   int rg_first_pass;       // EGONN_RG_FIRST_PASS=0..2   variant of the first pass of the row-group build (rowgroup.hip)
   // EGONN_KSPLIT, EGONN_KSPLIT8, EGONN_KSPLIT_KW, EGONN_KSPLIT_KW8, EGONN_KSPLIT_PARTS: comma lists indexed by the output level that
   // replace the offset-split rule below (kparts and kw of the k=3 / 8-slot maps, column parts per task); null = unset
@@ -250,39 +250,69 @@ struct Switches {
 };
 const Switches& switches();
 
-// Offset-split rule of the fp32 lock-step kernels (sconv_ksplit_rule): [0] = k=3 maps, [1] = 8-slot maps, indexed by output level
+// Offset-split rule of the fp32 lock-step kernels (sconv_choose): [0] = k=3 maps, [1] = 8-slot maps, indexed by output level
 struct KsRule {
   int8_t kparts[2][EGONN_NUM_LEVELS];   // offset parts as separate workgroups + reducer launch (1 = none)
   int8_t kw[2][EGONN_NUM_LEVELS];       // offset parts inside a workgroup (0 / 1 = none)
   int8_t col_parts[EGONN_NUM_LEVELS];   // column parts per task (0 = automatic)
 };
 
-// Product rule of the weight-resident 32->32 split convolutions: bits of sconv_resident_bit (kernels.h) that are on by default.
-// 6 = the two strided convolutions (into level 1; gated, into level 2), which read every input row once; the k=3 convolutions
-// of level 1 stay on the lock-step kernel (measured: DESIGN.md §3.1, §3.5, profiles/r07a_*)
+// Product rule of the weight-resident 32->32 split convolutions: bits of the layer's resident bit (sconv_choose) that are on by
+// default.  6 = the two strided convolutions (into level 1; gated, into level 2), which read every input row once; the k=3
+// convolutions of level 1 stay on the lock-step kernel (measured: DESIGN.md §3.1, §3.5, profiles/r07a_*)
 static constexpr int SCONV_RESIDENT_DEFAULT = 6;
+
+// What egonn_debug_set_naive_conv(code) asks for, decoded once (sconv_decode; the code table: include/egonn_hip.h).  Tests / A-B
+// measurements only: the product leaves it at its default.
+enum SconvFamily {
+  SCONV_AUTO = 0,     // no family forced: the product rule (or, with `split`, the split kernel wherever it exists)
+  SCONV_PLAIN,        // one thread per output (cross-check path)
+  SCONV_RING,         // register-ring per-tile kernel
+  SCONV_RING2,        // register-ring kernel, two groups per wave
+  SCONV_COOP,         // workgroup-cooperative kernel
+  SCONV_DMA,          // LDS-DMA kernel, split-phase LDS fetch, 4 ring slots
+  SCONV_DMA3,         // LDS-DMA kernel, fetch inside the item, 3 ring slots
+  SCONV_TRACED        // traced build of the LDS-DMA kernel (egonn_debug_set_trace)
+};
+// Explicit configuration of the split kernel (code 1000 + cfg, EGONN_SPLIT_CFG=cfg; sconv_decode_cfg)
+struct SplitCfg {
+  int code = 0;            // the cfg as given; 0 = none given
+  int nw = 0;              // waves per lock-step workgroup (4 / 8); 0 = a shape without an instantiation
+  int parts_sel = 0;       // column parts per task = 2^(parts_sel - 1), 0 = the layer's rule
+  bool trace = false;      // the traced build
+  bool resident = false;   // the weight-resident form (32->32 only)
+};
+struct SconvSetting {
+  SconvFamily family = SCONV_AUTO;
+  bool split = false;      // the split kernel on every fp32 map it is instantiated for, shaped by cfg
+  SplitCfg cfg;
+  bool product() const { return family == SCONV_AUTO && !split; }   // the product rule decides
+};
+// The context fields a sparse convolution's launch depends on (sconv_choose reads these and the layer, nothing else)
+struct SconvSettings {
+  SconvSetting set;           // egonn_debug_set_naive_conv
+  int split_max_level = 5;    // fp32 sparse convs whose output level is <= this run on the fp16-split kernels (sconv_split.hip);
+                              // round 5: 4 -> 5 (profiles/r05b_tail_kernel.txt: 25.2 k -> 26.4 k scans/s with four batches in flight; the
+                              // level-5 launches alone get slower, one-batch graph latency 1.17 -> 1.23 ms — the headline metric is scans/s)
+  int operand_autoscale = 0;  // egonn_ctx_set_operand_autoscale: the fp16-split convolutions scale their INPUT by a power of two per launch
+                              // (max |in| -> [2^13, 2^14), undone in the epilogue): the input-gradient convolutions of a training step
+  int resident_mask = SCONV_RESIDENT_DEFAULT;   // 32->32 split convolutions on the weight-resident form (egonn_debug_set_resident);
+  int resident_wgs = 0;                         // its workgroups per launch, 0 = default
+  KsRule ks_rule;             // set at context creation (sconv_ksplit_defaults); egonn_debug_set_ksplit
+};
 
 struct Ctx {
   Profiler prof;
-  KsRule ks_rule;             // set at context creation (sconv_ksplit_defaults); egonn_debug_set_ksplit
+  SconvSettings sconv;        // every setting the launch of a sparse convolution depends on
   uint16_t* conv0_lut = nullptr;             // first-layer lookup table (64 positions x 128 offsets), built on first use
   unsigned long long* dev_pairs = nullptr;   // [16] kernel-map pair counters: [0] conv0 k5, [l] k3 map of level l
   int device = 0;
   int coord_bits = 16;
-  int split_max_level = 5;    // fp32 sparse convs whose output level is <= this run on the fp16-split kernels (sconv_split.hip);
-                              // round 5: 4 -> 5 (profiles/r05b_tail_kernel.txt: 25.2 k -> 26.4 k scans/s with four batches in flight; the
-                              // level-5 launches alone get slower, one-batch graph latency 1.17 -> 1.23 ms — the headline metric is scans/s)
   float* ks_part = nullptr;   // scratch for the partial tiles of the offset-split launches (sconv_split.hip): carved from the work arena
   size_t ks_part_floats = 0;  // by egonn_forward / the stand-alone operator entry points (sconv_ksplit_scratch_floats)
   const void* sort_prezeroed = nullptr;   // the per-scan histograms of the segmented sort were zeroed by the kernel in front of it
                                           // (coords.hip: set by the key kernel's launcher, handed to the sort, cleared after it)
-  int resident_mask = SCONV_RESIDENT_DEFAULT;   // 32->32 split convolutions on the weight-resident form (sconv_resident_bit;
-  int resident_wgs = 0;                         // egonn_debug_set_resident); its workgroups per launch, 0 = default
   int keep_level_features = 0;   // egonn_debug_keep_level_features: no fusion that leaves a level's block output unmaterialised
-  int operand_autoscale = 0;  // egonn_ctx_set_operand_autoscale: the fp16-split convolutions scale their INPUT by a power of two per launch
-                              // (max |in| -> [2^13, 2^14), undone in the epilogue): the input-gradient convolutions of a training step
-  int conv_variant = 0;       // tests / A-B measurements only (egonn_debug_set_naive_conv): 0 = product choice, 1 = per-wave
-                              // MFMA kernel, 2 = workgroup-cooperative MFMA kernel, 3 = plain one-thread-per-output kernel
   Arena plan_arena;           // keys, maps (lives until the next plan)
   Arena work_arena;           // features & scratch of one forward
   Arena sort_arena;           // radix-sort scratch

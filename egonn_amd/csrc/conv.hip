@@ -471,7 +471,7 @@ int conv0_k5_forward(Ctx* ctx, const float* feat, const float* W, int cout, cons
                      ctx->dev_counts, (int32_t)P.cap[2], (int32_t)P.cap[0], W, scale, shift, relu, out, ctx->conv0_lut)
   if (feat) {
     if (out_bf16) EGONN_CONV0_LAUNCH(false, true); else EGONN_CONV0_LAUNCH(false, false);
-  } else if (ctx->conv_variant == 3) {                     // cross-check path (egonn_debug_set_naive_conv): fp32-MFMA kernel
+  } else if (ctx->sconv.set.family == SCONV_PLAIN) {                     // cross-check path (egonn_debug_set_naive_conv): fp32-MFMA kernel
     if (out_bf16) EGONN_CONV0_LAUNCH(true, true); else EGONN_CONV0_LAUNCH(true, false);
   } else {                                                 // unit features: exact bf16 x 3 split of the kernel
     if (out_bf16)

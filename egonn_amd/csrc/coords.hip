@@ -1160,7 +1160,7 @@ int plan_from_coords(Ctx* ctx, const int32_t* coords, int64_t n, int B, hipStrea
 // Fixes the sizes of everything a plan allocates, so that later plans neither allocate nor synchronise (capturable).
 int plan_reserve(Ctx* ctx, int64_t max_points, int B, const int64_t* level_caps) {
   EGONN_REQUIRE(max_points >= 1 && B >= 1 && B <= EGONN_MAX_BATCH, EGONN_ERR_INVALID, "reserve: bad sizes");
-  EGONN_REQUIRE(!ctx->operand_autoscale, EGONN_ERR_STATE,
+  EGONN_REQUIRE(!ctx->sconv.operand_autoscale, EGONN_ERR_STATE,
                 "reserve: operand autoscale is on — it reads the map's row count on the host (eager plans only)");
   ctx->plan.valid = false;
   for (int l = 0; l < NL; ++l) {

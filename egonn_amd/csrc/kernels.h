@@ -39,32 +39,73 @@ struct ConvCall {
   const float *in2 = nullptr, *gate = nullptr;   // input row r = relu(in[r] * gate[scan] + in2[r]): the tail of an ECA block, never materialised
   const float* residual = nullptr;       // out += residual ([n_out][cout] fp32) in the epilogue
 };
-// Kernel family a layer runs on: a function of the LAYER and the context's settings, never of the batch.  sconv_route alone decides it.
+// Kernel family a layer runs on: a function of the LAYER and the context's settings, never of the batch.  sconv_choose alone decides it.
 enum SconvRoute {
-  ROUTE_PLAIN,        // one thread per output (conv.hip): debug variant 3, channel plans without an MFMA instantiation
+  ROUTE_PLAIN,        // one thread per output (conv.hip): SCONV_PLAIN, channel plans without an MFMA instantiation
   ROUTE_SPLIT,        // lock-step fp16-split kernel (sconv_split.hip)
   ROUTE_TAIL_SPLIT,   // per-tile kernel on fp16-split arithmetic: 128->128 fp32 maps above the split level limit
   ROUTE_WG,           // workgroup-cooperative exact kernel
   ROUTE_DMA,          // LDS-DMA exact kernel (fp32 maps)
   ROUTE_RG            // per-tile exact kernel
 };
+// The layer of one sparse convolution, as far as the launch depends on it
+struct SconvLayer {
+  int kind = 0, level = 0, cin = 0, cout = 0, bf16 = 0;
+  bool gated = false;      // ConvCall::in2
+  int split_io = 0;        // ConvCall::split_io
+  bool residual = false;   // ConvCall::residual
+};
+// The whole launch of one layer: the kernel instantiation that runs (template parameters a kernel does not have stay 0), its grid,
+// block and dynamic LDS bytes.  sconv_choose is its only author; the instantiation tables of sconv_rg_forward /
+// sconv_split_forward and launch_sconv only read it.
+struct SconvChoice {
+  SconvRoute route = ROUTE_RG;   // the family (profiler tags, the pack the kernel reads)
+  SconvRoute kernel = ROUTE_RG;  // the kernel template: route, but ROUTE_RG for the tail split and for a traced layer on a plan
+                                 // without a traced instantiation
+  int NW = 0, NSW = 0, KW = 0, KS = 0, GATED = 0, TRACE = 0, resident = 0;   // split kernels (resident: sconv_split_resident_kernel<NW, GATED>)
+  int KSP = 0, D = 0, G = 0, SPLIT = 0, PIPE = 0;                            // exact kernels (and NW, TRACE)
+  unsigned gx = 0, gy = 1, gz = 1, block = 0;
+  size_t lds = 0;
+  int kparts = 1;                // split: offset parts as workgroups of grid.z (> 1: a reducer launch follows)
+  int err = 0;                   // != EGONN_OK: the combination is refused (the message: last_error())
+};
+// The one launch tail of the sparse-convolution kernels: the dynamic-LDS attribute once per (instantiation, device), the launch
+// with or without the profiler's event pair (bench.py roofline leg: time exactly this dispatch), the error check.  stop_later
+// (the offset-split launcher): the stop event is not attached here but handed back for the reducer launch behind it.
+template <auto Kernel, class Args>
+static int launch_sconv(const SconvChoice& ch, hipStream_t stream, const Args& a, hipEvent_t* stop_later = nullptr) {
+  static AttrOnce attr_done;                         // per instantiation; idempotent
+  if (ch.lds > 48 * 1024 && attr_done.need()) {
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    attr_done.mark();
+  }
+  const dim3 grid(ch.gx, ch.gy, ch.gz), block(ch.block);
+  hipEvent_t* pev = prof_kernel_events();
+  if (pev[0]) {
+    if (stop_later) *stop_later = pev[1];
+    hipExtLaunchKernelGGL(Kernel, grid, block, ch.lds, stream, pev[0], stop_later ? nullptr : pev[1], 0, a);
+    pev[0] = pev[1] = nullptr;
+  } else {
+    hipLaunchKernelGGL(Kernel, grid, block, ch.lds, stream, a);
+  }
+  HIP_CHECK(hipGetLastError());
+  return EGONN_OK;
+}
+SconvChoice sconv_choose(const SconvSettings& s, const SconvLayer& l, int64_t cap_groups);
+SconvSetting sconv_decode(int code);    // egonn_debug_set_naive_conv's public code
+SplitCfg sconv_decode_cfg(int cfg);     // the cfg of code 1000 + cfg and of EGONN_SPLIT_CFG
 SconvRoute sconv_route(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16);
-bool sconv_split_arithmetic(const Ctx* ctx);   // the product rule with fp16-split arithmetic allowed (no exact-fp32 / debug variant)
+bool sconv_split_arithmetic(const Ctx* ctx);   // the product rule with fp16-split arithmetic allowed (no exact-fp32 / debug setting)
 // name of that kernel (the profiler tags carry it: bench.py's roofline leg keys on it)
 const char* sconv_kernel_name(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16);
-// What sconv_map chose for one launch of sconv_rg_forward / sconv_split_forward
+// What a launch of sconv_rg_forward / sconv_split_forward needs besides the choice
 struct SconvLaunch {
-  SconvRoute route = ROUTE_RG;
+  SconvChoice ch;
   const RowGroups* rg = nullptr;         // row-group form of the map
   int64_t n_in_cap = 0;                  // rows the input map can hold
-  int64_t groups_hint = 0;               // host upper bound of the groups in use (sizes the grid only; the kernels read rg->meta[0])
   const void* Wp = nullptr;              // the kernel in the form the route reads
-  int variant = 0;                       // rg: ctx->conv_variant (A/B choice among the exact kernels); split: cfg, 0 = product choice
-  bool small = false;                    // rg: a level that never fills the chip (deeper prefetch)
   int32_t* flags = nullptr;              // the plan's flag word (bit 3: fp16 range guard); split arithmetic only
   int B = 0;                             // split, gated input: scans of the batch
-  int kparts = 1, kw = 0, col_parts = 0; // split: offset parts as workgroups / inside a workgroup (0, 1: none), column parts per task (0 = automatic)
-  int resident = 0, resident_wgs = 0;    // split, 32->32: the weight-resident form (sconv_resident_rule); workgroups, 0 = default
   float* part = nullptr; size_t part_floats = 0;           // split: scratch for the partial tiles of an offset-split launch
   uint32_t* in_absmax = nullptr; int64_t in_elems = 0;     // split, operand autoscale: 8 bytes of scratch, the elements of `in`
 };
@@ -78,13 +119,10 @@ int sconv_split_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t str
 size_t sconv_split_part_floats(const RowGroups& rg, int cout, int kparts);
 // Offset-split rule of the fp32 lock-step kernels: parts of the map's K offsets (1 = unsplit) and column parts per task for
 // (map kind, output level) — a function of the LAYER only (the partition changes the summation order of a row)
-void sconv_ksplit_rule(const Ctx* ctx, int kind, int level, int* kparts, int* col_parts, int* kw);
+struct KsChoice { int kparts, col_parts, kw; };
+KsChoice sconv_ksplit_rule(const KsRule& rule, int kind, int level);
 void sconv_ksplit_defaults(KsRule* r);                  // the product rule (+ the EGONN_KSPLIT* measurement overrides)
 size_t sconv_ksplit_scratch_floats(const Ctx* ctx);    // partial-tile scratch that covers every map of the context's plan
-// Weight-resident form of the 32->32 split convolutions (sconv_split_resident_kernel): bit of Ctx::resident_mask that covers
-// (map kind, output level, gated input), 0 = none — a function of the LAYER only.  bit 0: k=3 of level 1, bit 1: k=2,s=2 into
-// level 1, bit 2: gated k=2,s=2 into level 2
-int sconv_resident_bit(int kind, int level, int cin, int cout, bool gated);
 static constexpr size_t SCONV_SCRATCH_FLOATS = (size_t)2 << 20;   // 8 MB: one packed kernel (27 x 256 x 256 fp32 = 7 MB)
 // conv.hip -------------------------------------------------------------------------------------
 int sconv_naive(const float* in, const int32_t* nbr, const float* W, const float* scale, const float* shift, int relu,

@@ -20,31 +20,30 @@ API const char* egonn_last_error(void) { return last_error(); }
 
 API int egonn_debug_set_naive_conv(egonn_ctx* c, int on) {
   EGONN_REQUIRE(c, EGONN_ERR_INVALID, "debug_set_naive_conv: null context");
-  if (on >= 1000) { c->conv_variant = on; return EGONN_OK; }     // 1000 + cfg: the split kernel with an explicit configuration
-  c->conv_variant = (on == 1) ? 3 : (on == 2 ? 1 : (on == 4 ? 2 : (on == 8 ? 4 : (on == 16 ? 5 : (on == 32 ? 6 : (on == 128 ? 9 : 0))))));
+  c->sconv.set = sconv_decode(on);
   return EGONN_OK;
 }
 
-// Offset-split rule of this context's fp32 sparse convolutions (tests / A-B measurements; sconv_ksplit_rule): map_class 0 = the
+// Offset-split rule of this context's fp32 sparse convolutions (tests / A-B measurements; sconv_choose): map_class 0 = the
 // k=3 maps, 1 = the 8-slot maps (k=2,s=2 and transposed); kparts = offset parts as separate workgroups + reducer launch (1 = none),
 // kw = offset parts inside a workgroup (0 / 1 = none, 2..4), col_parts = column parts per task (0 = automatic).  -1 keeps a field.
 API int egonn_debug_set_ksplit(egonn_ctx* c, int map_class, int level, int kparts, int kw, int col_parts) {
   EGONN_REQUIRE(c && (map_class == 0 || map_class == 1) && level >= 0 && level < EGONN_NUM_LEVELS, EGONN_ERR_INVALID,
                 "debug_set_ksplit: bad argument");
   EGONN_REQUIRE(kparts <= 27 && kw <= 4 && col_parts <= 4, EGONN_ERR_INVALID, "debug_set_ksplit: kparts <= 27, kw <= 4, col_parts <= 4");
-  if (kparts >= 0) c->ks_rule.kparts[map_class][level] = (int8_t)std::max(kparts, 1);
-  if (kw >= 0) c->ks_rule.kw[map_class][level] = (int8_t)kw;
-  if (col_parts >= 0) c->ks_rule.col_parts[level] = (int8_t)col_parts;
+  if (kparts >= 0) c->sconv.ks_rule.kparts[map_class][level] = (int8_t)std::max(kparts, 1);
+  if (kw >= 0) c->sconv.ks_rule.kw[map_class][level] = (int8_t)kw;
+  if (col_parts >= 0) c->sconv.ks_rule.col_parts[level] = (int8_t)col_parts;
   return EGONN_OK;
 }
 
-// Weight-resident form of the 32->32 split convolutions (sconv_resident_bit): layers it runs on, -1 = the product rule; workgroups
+// Weight-resident form of the 32->32 split convolutions (sconv_choose): layers it runs on, -1 = the product rule; workgroups
 // per resident launch, 0 = default
 API int egonn_debug_set_resident(egonn_ctx* c, int mask, int max_workgroups) {
   EGONN_REQUIRE(c && mask >= -1 && mask <= 7 && max_workgroups >= 0 && max_workgroups <= 65536, EGONN_ERR_INVALID,
                 "debug_set_resident: mask in [-1, 7], max_workgroups in [0, 65536]");
-  c->resident_mask = mask < 0 ? SCONV_RESIDENT_DEFAULT : mask;
-  c->resident_wgs = max_workgroups;
+  c->sconv.resident_mask = mask < 0 ? SCONV_RESIDENT_DEFAULT : mask;
+  c->sconv.resident_wgs = max_workgroups;
   return EGONN_OK;
 }
 
@@ -73,7 +72,7 @@ API int egonn_ctx_create(egonn_ctx** out, int device, int coord_bits) {
   }
   c->dev_flags = c->dev_counts + 16;   // counts[0..11], flags at [16], the fp16 range flag at [17]: fetched by one copy
   c->dev_fp16_flag = c->dev_counts + 17;
-  sconv_ksplit_defaults(&c->ks_rule);
+  sconv_ksplit_defaults(&c->sconv.ks_rule);
   if (conv0_lut_init(c) != EGONN_OK) {
     egonn_ctx_destroy(c);
     return EGONN_ERR_HIP;
@@ -194,7 +193,7 @@ API int egonn_ctx_set_operand_autoscale(egonn_ctx* c, int on) {
   EGONN_REQUIRE(!on || !c->reserved, EGONN_ERR_STATE,
                 "ctx_set_operand_autoscale: eager plans only — the scale reads the map's row count on the host, which a reserved "
                 "(egonn_ctx_reserve) plan keeps on the device");
-  c->operand_autoscale = on;
+  c->sconv.operand_autoscale = on;
   return EGONN_OK;
 }
 
@@ -208,7 +207,7 @@ API int egonn_debug_keep_level_features(egonn_ctx* c, int on) {
 
 API int egonn_ctx_set_exact_fp32(egonn_ctx* c, int on) {
   EGONN_REQUIRE(c && (on == 0 || on == 1), EGONN_ERR_INVALID, "ctx_set_exact_fp32: bad argument");
-  c->split_max_level = on ? -1 : 5;
+  c->sconv.split_max_level = on ? -1 : 5;
   return EGONN_OK;
 }
 
@@ -969,7 +968,7 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
     EGONN_TRY(eca_gate_groups(psum, L.rg27, L.boff, B, b.cout, b.eca, b.eca_k, gate, st));
     DBG_SYNC("L%d eca gate", i);
     const void* res = y;
-    if (i == 1 && !switches().no_gated_k2s2 && !c->keep_level_features && !bf16 && !b.down && c->conv_variant == 0 && b.cout == 32 &&
+    if (i == 1 && !switches().no_gated_k2s2 && !c->keep_level_features && !bf16 && !b.down && c->sconv.set.product() && b.cout == 32 &&
         m->blk[2].cin == 32 && sconv_route(c, 1, 2, 32, 32, 0) == ROUTE_SPLIT) {
       // level 1's block output has ONE reader, the strided convolution into level 2, which reads every row exactly once: it
       // evaluates relu(t2 * gate[scan] + y) on the rows it gathers (sconv_split_kernel<32,32,...,GATED>) — the 23 MB map is neither
@@ -1018,7 +1017,7 @@ API int egonn_forward(egonn_ctx* c, egonn_model* m, const float* features, int q
 
   // ---- global head + decoder + GeM (models/minkgl.py:46-60, 207-225; layers/pooling.py:82-86)
   void* g5_fused = nullptr;
-  if (do_global && !switches().no_fused_ghead && !bf16 && c->conv_variant == 0 && dense_group3_rows(P.cap[5]) &&
+  if (do_global && !switches().no_fused_ghead && !bf16 && c->sconv.set.product() && dense_group3_rows(P.cap[5]) &&
       dense_group3_rows(P.cap[6]) && dense_group3_rows(P.cap[7])) {
     // MinkHead (models/minkgl.py:46-60) in three launches instead of five: the three lateral 1x1 convolutions depend on the trunk
     // only — ONE grouped launch — and every FPN step `tconv(y) + lateral` is the transposed convolution with the lateral as its

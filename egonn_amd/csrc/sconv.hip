@@ -818,36 +818,7 @@ __global__ __launch_bounds__(NW * 64) void sconv_dma_kernel(const SconvArgs p) {
 // 9 live waves of 16 (tools/sconv_trace.py).  The waves of a workgroup only have to be together when they split the input
 // channels of one tile (KSP > 1), so a workgroup is exactly those KSP waves; the dispatcher starts > 3000 workgroups/us
 // (tools/exp/dispatch_rate.hip), far more than these launches need.
-template <int CIN, int COUT, int KSP, int D, bool TRACE = false, bool PIPE = false>
-static int launch_dma_d(const SconvArgs& a, int64_t groups_hint, hipStream_t stream, int nw_sel = 0) {
-  constexpr int NS = COUT / 32;
-  auto go = [&](auto NWC) -> int {
-    constexpr int NW = decltype(NWC)::value;
-    const size_t lds = NW * ((2 * 256 + 32) * 4 + D * 2048);
-    static AttrOnce attr_done;                       // per instantiation (the lambda is instantiated per NW)
-    if (attr_done.need()) {
-      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sconv_dma_kernel<CIN, COUT, D, KSP, NW, TRACE, PIPE>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_done.mark(); 
-    }
-    const int64_t ntask = cdiv(groups_hint * NS * KSP, NW);
-    int64_t grid = std::min<int64_t>(std::max<int64_t>(ntask, 8), 65536);
-    grid = (grid + 7) / 8 * 8;
-    hipEvent_t* pev = prof_kernel_events();
-    if (pev[0]) {
-      hipExtLaunchKernelGGL((sconv_dma_kernel<CIN, COUT, D, KSP, NW, TRACE, PIPE>), dim3((unsigned)grid), dim3(NW * 64), lds, stream, pev[0], pev[1], 0, a);
-      pev[0] = pev[1] = nullptr;
-    } else {
-      hipLaunchKernelGGL((sconv_dma_kernel<CIN, COUT, D, KSP, NW, TRACE, PIPE>), dim3((unsigned)grid), dim3(NW * 64), lds, stream, a);
-    }
-    HIP_CHECK(hipGetLastError());
-    return EGONN_OK;
-  };
-  if constexpr (KSP < 4) {
-    if (nw_sel == 4) return go(std::integral_constant<int, 4>{});
-  }
-  return go(std::integral_constant<int, KSP>{});
-}
+// (sconv_choose sizes the launch: NW = KSP, one workgroup per task.)
 
 // ------------------------------------------------------------------ workgroup-cooperative variant
 // What the per-wave kernel above taught (profiles/r02a_pmc_sweep.txt): the texture-address unit is 71 % busy and the MFMA
@@ -1074,92 +1045,35 @@ __global__ __launch_bounds__(NW * 64) void sconv_wg_kernel(const SconvArgs p) {
   }
 }
 
-template <int CIN, int COUT, bool BF16>
-static int launch_wg(const SconvArgs& a, int64_t groups_hint, hipStream_t stream) {
-  constexpr int NW = 4;
-  constexpr int ES = BF16 ? 2 : 4;
-  const size_t lds = 2 * (size_t)(32 * COUT * ES) + NW * 28 * 16 * sizeof(int32_t);
-  static AttrOnce attr_done;                         // per instantiation; idempotent
-  if (attr_done.need()) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sconv_wg_kernel<CIN, COUT, BF16, NW>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done.mark(); 
-  }
-  const int64_t ntask = cdiv(groups_hint, NW);
-  int64_t grid = std::min<int64_t>(std::max<int64_t>(ntask, 8), 16384);
-  grid = (grid + 7) / 8 * 8;
-  hipEvent_t* pev = prof_kernel_events();
-  if (pev[0]) {      // bench.py roofline leg: time exactly this dispatch
-    hipExtLaunchKernelGGL((sconv_wg_kernel<CIN, COUT, BF16, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, stream, pev[0], pev[1], 0, a);
-    pev[0] = pev[1] = nullptr;
-  } else {
-    hipLaunchKernelGGL((sconv_wg_kernel<CIN, COUT, BF16, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, stream, a);
-  }
-  HIP_CHECK(hipGetLastError());
-  return EGONN_OK;
-}
-
 // ------------------------------------------------------------------ launcher
-template <int CIN, int COUT, bool BF16, int KSP, int D, int G, bool SPLIT = false>
-static int launch_rg_d(const SconvArgs& a, int64_t groups_hint, hipStream_t stream) {
-  constexpr int NS = COUT / 32;
-  constexpr int NW = KSP;                                // a workgroup = the waves that share a tile (see launch_dma_d)
-  constexpr int NPIECE = (G * 27 * 4 + 63) / 64;
-  const size_t lds = NW * (NPIECE * 256 + 16) * sizeof(int32_t) + (KSP > 1 ? 2 * NW * 2 * G * 64 * sizeof(f32x4) : 0);
-  static AttrOnce attr_done;                         // per instantiation; idempotent
-  if (attr_done.need() && lds > 48 * 1024) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sconv_rg_kernel<CIN, COUT, BF16, D, KSP, G, NW, SPLIT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done.mark(); 
-  }
-  const int64_t ntask = cdiv(cdiv(groups_hint, G) * NS * KSP, NW);
-  // one workgroup per task up to a cap: the hardware dispatcher then balances the uneven tasks (a grid of only the
-  // resident workgroups was 30 % slower: each loops over ~3 tasks and the slowest decides)
-  int64_t grid = std::min<int64_t>(std::max<int64_t>(ntask, 8), 65536);
-  grid = (grid + 7) / 8 * 8;
-  hipEvent_t* pev = prof_kernel_events();
-  if (pev[0]) {      // bench.py roofline leg: time exactly this dispatch
-    hipExtLaunchKernelGGL((sconv_rg_kernel<CIN, COUT, BF16, D, KSP, G, NW, SPLIT>), dim3((unsigned)grid), dim3(NW * 64), lds, stream, pev[0], pev[1], 0, a);
-    pev[0] = pev[1] = nullptr;
-  } else {
-    hipLaunchKernelGGL((sconv_rg_kernel<CIN, COUT, BF16, D, KSP, G, NW, SPLIT>), dim3((unsigned)grid), dim3(NW * 64), lds, stream, a);
-  }
-  HIP_CHECK(hipGetLastError());
-  return EGONN_OK;
-}
-// sel (tests / A-B measurements; every choice gives bitwise-identical results): 0 = product choice, 1 = register-ring
-// kernel, 2 = register-ring kernel with two groups per wave, 3 = LDS-DMA kernel (fp32 maps; split-phase LDS fetch, 4 ring slots), 4 = LDS-DMA kernel with the fetch inside the item (3 slots), 9 = traced build
+// The instantiation table of the exact kernels.  It switches on the fields of the choice (sconv_choose) and decides nothing.
 template <int CIN, int COUT, bool BF16>
-static int launch_rg(const SconvArgs& a, int64_t groups_hint, hipStream_t stream, int sel, SconvRoute route, bool small) {
-  constexpr int NS = COUT / 32, NCB = CIN / 32;
+static int launch_rg(const SconvArgs& a, const SconvChoice& ch, hipStream_t stream) {
   // the input-channel blocks are always split over the waves of a workgroup (a function of the shape only, so results
   // never depend on launch sizes): measured faster at every level, 12 % on the 84 k-row 64->64 layer, 40 % on level 4.
   // Splitting the kernel offsets as well measured neutral to 50 % slower.
-  constexpr int KSP = NCB >= 4 ? 4 : NCB;
-  // prefetch depth (does not touch the arithmetic): few waves per SIMD (`small`, sconv_small_level) => nothing else hides the
-  // gather latency, keep 5 items in flight; a full chip prefers the smaller register footprint
-  if constexpr (!BF16 && CIN == 128 && COUT == 128) {      // the tail levels' plan on split arithmetic (a.Wp = the split pack)
-    // (ring depth 9 / 12 instead of 6: L6 k=3 21.7 / 22.5 vs 18.1 us, L6 k2s2 13.2 / 14.7 vs 8.8 — profiles/r06c_kw_sweep.txt)
-    if (route == ROUTE_TAIL_SPLIT) return launch_rg_d<CIN, COUT, false, KSP, 6, 1, true>(a, groups_hint, stream);
+  constexpr int KSP = CIN / 32 >= 4 ? 4 : CIN / 32;
+  constexpr int NW = KSP;                                // a workgroup = the waves that share a tile (see above)
+  constexpr int DR = BF16 ? 4 : 3;                       // ring depth of a launch that fills the chip
+  if (ch.kernel == ROUTE_WG) return launch_sconv<sconv_wg_kernel<CIN, COUT, BF16, 4>>(ch, stream, a);
+  if constexpr (!BF16 && CIN == 128 && COUT == 128) {    // the tail levels' plan on split arithmetic (a.Wp = the split pack)
+    if (ch.SPLIT) return launch_sconv<sconv_rg_kernel<CIN, COUT, false, 6, KSP, 1, NW, true>>(ch, stream, a);
   }
-  EGONN_REQUIRE(route != ROUTE_TAIL_SPLIT, EGONN_ERR_INVALID, "sconv: the per-tile kernel has split arithmetic for fp32 128->128 maps only");
   if constexpr (!BF16) {
-    if (route == ROUTE_DMA) {
-      if (sel == 3 || sel == 0) return launch_dma_d<CIN, COUT, KSP, 4, false, true>(a, groups_hint, stream);
-      if (sel == 4) return launch_dma_d<CIN, COUT, KSP, 3>(a, groups_hint, stream);
+    if (ch.kernel == ROUTE_DMA) {
       if constexpr ((CIN == 32 && COUT == 32) || (CIN == 64 && COUT == 64)) {
-        if (sel == 9) return launch_dma_d<CIN, COUT, KSP, 4, true, true>(a, groups_hint, stream);
+        if (ch.TRACE) return launch_sconv<sconv_dma_kernel<CIN, COUT, 4, KSP, NW, true, true>>(ch, stream, a);
       }
+      if (ch.D == 3) return launch_sconv<sconv_dma_kernel<CIN, COUT, 3, KSP, NW, false, false>>(ch, stream, a);
+      return launch_sconv<sconv_dma_kernel<CIN, COUT, 4, KSP, NW, false, true>>(ch, stream, a);
     }
   }
-  // bf16 maps, big launches: two groups per wave share the W fragments (the items are load-bound: W is two thirds of the
-  // bytes an item moves) — 9-12 % on the 32-channel layers at batch 64; fp32 items are MFMA-bound and gain nothing
-  if constexpr (BF16) {      // very large launches (batch 64, levels 1-2): four groups per wave, another 4 %
-    if (sel == 0 && groups_hint * NS * KSP >= 32768) return launch_rg_d<CIN, COUT, BF16, KSP, 3, 4>(a, groups_hint, stream);
+  if constexpr (BF16) {
+    if (ch.G == 4) return launch_sconv<sconv_rg_kernel<CIN, COUT, BF16, 3, KSP, 4, NW, false>>(ch, stream, a);
   }
-  if ((sel == 2 || (BF16 && sel == 0)) && !small) return launch_rg_d<CIN, COUT, BF16, KSP, BF16 ? 4 : 3, 2>(a, groups_hint, stream);
-  if (small) return launch_rg_d<CIN, COUT, BF16, KSP, 6, 1>(a, groups_hint, stream);
-  return launch_rg_d<CIN, COUT, BF16, KSP, BF16 ? 4 : 3, 1>(a, groups_hint, stream);
+  if (ch.G == 2) return launch_sconv<sconv_rg_kernel<CIN, COUT, BF16, DR, KSP, 2, NW, false>>(ch, stream, a);
+  if (ch.D == 6) return launch_sconv<sconv_rg_kernel<CIN, COUT, BF16, 6, KSP, 1, NW, false>>(ch, stream, a);
+  return launch_sconv<sconv_rg_kernel<CIN, COUT, BF16, DR, KSP, 1, NW, false>>(ch, stream, a);
 }
 
 unsigned long long* g_sconv_trace = nullptr;              // measurement hook (egonn_debug_set_trace)
@@ -1172,14 +1086,13 @@ bool sconv_rg_supported(int cin, int cout) {
 // c.in: [n_in][cin]; l.rg: row-group tables of the map; l.Wp: pack_rg_weights(bf16 matching), or the split pack (tail split)
 int sconv_rg_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream) {
   const RowGroups& rg = *l.rg;
-  const int cin = c.cin, cout = c.cout, bf16 = c.bf16, variant = l.variant;
-  const int64_t groups_hint = l.groups_hint;
+  const int cin = c.cin, cout = c.cout, bf16 = c.bf16;
   EGONN_REQUIRE(rg.built, EGONN_ERR_STATE, "sconv: row-group tables not built");
   EGONN_REQUIRE(sconv_rg_supported(cin, cout), EGONN_ERR_INVALID, "sconv: channel plan %d->%d not supported (32/64/128/256)", cin, cout);
   const uint64_t ib = (uint64_t)l.n_in_cap * cin * (bf16 ? 2 : 4);
   EGONN_REQUIRE(ib < (1ull << 32) - (1ull << 20), EGONN_ERR_INVALID,
                 "sconv: input feature map of %lld rows exceeds the 4 GiB buffer-resource range", (long long)l.n_in_cap);
-  if (groups_hint <= 0) return EGONN_OK;
+  if (rg.cap_groups <= 0) return EGONN_OK;
   SconvArgs a;
   a.in = c.in; a.snbr = rg.snbr; a.gmask = rg.gmask; a.perm = rg.perm; a.meta = rg.meta; a.Wp = l.Wp;
   a.scale = c.scale; a.shift = c.shift; a.out = c.out; a.psum = c.psum;
@@ -1187,18 +1100,11 @@ int sconv_rg_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream
   a.w_bytes = (uint32_t)((uint64_t)rg.K * cin * cout * (bf16 ? 2 : 4));
   a.K = rg.K; a.relu = c.relu ? 1 : 0; a.cap_groups = rg.cap_groups;
   a.order4 = switches().no_task_order ? nullptr : rg.order4;
-  a.trace = variant == 9 ? g_sconv_trace : nullptr;
+  a.trace = l.ch.TRACE ? g_sconv_trace : nullptr;
   a.flags = l.flags;
   a.res = c.residual;
-  EGONN_REQUIRE(!c.residual || (!bf16 && c.level >= 5 && (variant == 0 || variant == 1)), EGONN_ERR_INVALID,
-                "sconv: the epilogue residual exists in the per-tile kernel of fp32 maps (levels >= 5) and in the split kernel");
-  const int gsel = variant == 1 ? 1 : (variant == 4 ? 2 : (variant == 5 ? 3 : (variant == 6 ? 4 : (variant == 9 ? 9 : 0))));
-  const bool coop = l.route == ROUTE_WG;
-#define EGONN_RG_CASE(CI, CO)                                                                      \
-  if (cin == CI && cout == CO) {                                                                   \
-    if (coop) return bf16 ? launch_wg<CI, CO, true>(a, groups_hint, stream) : launch_wg<CI, CO, false>(a, groups_hint, stream); \
-    return bf16 ? launch_rg<CI, CO, true>(a, groups_hint, stream, gsel, l.route, l.small) : launch_rg<CI, CO, false>(a, groups_hint, stream, gsel, l.route, l.small); \
-  }
+#define EGONN_RG_CASE(CI, CO) \
+  if (cin == CI && cout == CO) return bf16 ? launch_rg<CI, CO, true>(a, l.ch, stream) : launch_rg<CI, CO, false>(a, l.ch, stream);
   EGONN_RG_CASE(32, 32)
   EGONN_RG_CASE(32, 64)
   EGONN_RG_CASE(64, 64)
@@ -1220,11 +1126,33 @@ int sconv_rg_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream
   return EGONN_ERR_INVALID;
 }
 
-// Arithmetic of an fp32 sparse convolution (ctx->conv_variant; egonn_debug_set_naive_conv):
-//   0           product choice: split-bf16 kernel (sconv_split.hip) on the maps of levels <= ctx->split_max_level where it is
-//               instantiated, exact fp32 MFMA kernels elsewhere
-//   1..9        the exact fp32 kernels of this file (3 = plain one-thread-per-output kernel)
-//   1000 + cfg  split-bf16 kernel with an explicit configuration (cfg 0 = its default)
+// ------------------------------------------------------------------ the setting (egonn_debug_set_naive_conv; codes: egonn_hip.h)
+// cfg = 100 + NW * 10 + 2 [+ 400 * (1 + log2(column parts))] [+ 9000: the s_memtime build, tools/split_trace.py];
+// 100 + 8 * 10 + 3 = 183: the weight-resident form (32->32 only).  142 is the product's shape.
+SplitCfg sconv_decode_cfg(int cfg) {
+  SplitCfg q;
+  q.code = cfg;
+  q.trace = cfg >= 9000;
+  int shape = q.trace ? cfg - 9000 : cfg;
+  if (shape >= 500) { q.parts_sel = shape / 400; shape -= 400 * q.parts_sel; }
+  q.resident = shape == 183 && !q.trace;
+  q.nw = shape == 142 ? 4 : ((shape == 182 || q.resident) ? 8 : 0);
+  return q;
+}
+SconvSetting sconv_decode(int code) {
+  SconvSetting s;
+  static const struct { int code; SconvFamily family; } families[] = {{1, SCONV_PLAIN}, {2, SCONV_RING}, {4, SCONV_COOP}, {8, SCONV_RING2},
+                                                                      {16, SCONV_DMA}, {32, SCONV_DMA3}, {128, SCONV_TRACED}};
+  s.split = code >= 1000;
+  if (s.split) s.cfg = sconv_decode_cfg(code - 1000);
+  for (const auto& f : families)
+    if (f.code == code) s.family = f.family;             // every other code below 1000: the product choice
+  return s;
+}
+
+// ------------------------------------------------------------------ the choice
+// Arithmetic of an fp32 sparse convolution: the product rule puts the maps of levels <= the split level limit on the split-bf16 kernel
+// (sconv_split.hip) where it is instantiated and the others on the exact fp32 MFMA kernels of this file; a setting forces one.
 // The product choice is a function of the LAYER (output level, channel plan), never of the batch or of a capacity: a scan
 // gives bitwise the same descriptors alone, in any batch, and under eager or reserved (hipGraph) plans.
 // Measured (profiles/r03e_split_threshold.txt, batch 16, four batches in flight): one launch alone, the lock-step split
@@ -1236,27 +1164,31 @@ int sconv_rg_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream
 // cooperative kernel costs more than its saved W traffic when an item is 16-64 MFMAs of 32 cycles); with bf16 maps the items are
 // load-bound and the cooperative kernel wins on the big layers with >= 64 input or output channels.  Levels >= 5 never fill
 // the chip (batch 16: <= 240 groups); bf16 maps are the batch-64 configuration (BASELINE configs[2]): level 5 still fills it there.
-static bool sconv_small_level(int level, int bf16) { return level >= (bf16 ? 6 : 5); }
-bool sconv_split_arithmetic(const Ctx* ctx) { return ctx->conv_variant == 0 && ctx->split_max_level >= 0; }
-SconvRoute sconv_route(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16) {
-  const int variant = ctx->conv_variant;
+static bool small_level(int level, bool bf16) { return level >= (bf16 ? 6 : 5); }
+static bool split_arithmetic(const SconvSettings& s) { return s.set.product() && s.split_max_level >= 0; }
+static SconvRoute route_of(const SconvSettings& s, int kind, int level, int cin, int cout, bool bf16) {
+  const SconvSetting& set = s.set;
   const Switches& sw = switches();
-  if (variant == 3 || !sconv_rg_supported(cin, cout)) return ROUTE_PLAIN;
+  if (set.family == SCONV_PLAIN || !sconv_rg_supported(cin, cout)) return ROUTE_PLAIN;
   // the context's split level limit, or EGONN_SPLIT_MAX_LEVEL; EGONN_SPLIT_MAX_LEVEL_K8 for the 8-slot maps (measurement overrides)
-  const int limit = (sw.split_max_level >= 0 && ctx->split_max_level >= 0) ? sw.split_max_level : ctx->split_max_level;
+  const int limit = (sw.split_max_level >= 0 && s.split_max_level >= 0) ? sw.split_max_level : s.split_max_level;
   if (!bf16 && sconv_split_supported(cin, cout)) {
-    if (variant >= 1000) return ROUTE_SPLIT;
-    if (variant == 0 && level <= ((kind != 0 && sw.split_max_level_k8 >= 0) ? sw.split_max_level_k8 : limit)) return ROUTE_SPLIT;
+    if (set.split) return ROUTE_SPLIT;
+    if (set.product() && level <= ((kind != 0 && sw.split_max_level_k8 >= 0) ? sw.split_max_level_k8 : limit)) return ROUTE_SPLIT;
   }
-  if (!sw.no_tail_split && !bf16 && cin == 128 && cout == 128 && sconv_split_arithmetic(ctx) && level > limit && !ctx->operand_autoscale)
+  if (!sw.no_tail_split && !bf16 && cin == 128 && cout == 128 && split_arithmetic(s) && level > limit && !s.operand_autoscale)
     return ROUTE_TAIL_SPLIT;
-  if (variant == 2 || (variant == 0 && bf16 && level <= 4 && cin * cout >= 32 * 64)) return ROUTE_WG;
-  // (variants 1 and 4 ask for the register-ring kernels; every other one leaves the big fp32 launches on the LDS-DMA kernel)
-  if (!bf16 && variant != 1 && variant != 4 && (variant == 5 || variant == 6 || variant == 9 || !sconv_small_level(level, bf16)))
-    return ROUTE_DMA;
+  if (set.family == SCONV_COOP || (set.product() && bf16 && level <= 4 && cin * cout >= 32 * 64)) return ROUTE_WG;
+  // (the two register-ring families ask for the per-tile kernel; every other setting leaves the big fp32 launches on the LDS-DMA kernel)
+  const bool dma_family = set.family == SCONV_DMA || set.family == SCONV_DMA3 || set.family == SCONV_TRACED;
+  if (!bf16 && set.family != SCONV_RING && set.family != SCONV_RING2 && (dma_family || !small_level(level, bf16))) return ROUTE_DMA;
   return ROUTE_RG;
 }
-// (the plain kernel runs under a debug variant only and has no tag of its own)
+bool sconv_split_arithmetic(const Ctx* ctx) { return split_arithmetic(ctx->sconv); }
+SconvRoute sconv_route(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16) {
+  return route_of(ctx->sconv, kind, level, cin, cout, bf16 != 0);
+}
+// (the plain kernel runs under a debug setting only and has no tag of its own)
 const char* sconv_kernel_name(const Ctx* ctx, int kind, int level, int cin, int cout, int bf16) {
   switch (sconv_route(ctx, kind, level, cin, cout, bf16)) {
     case ROUTE_SPLIT: return "sconv_split_kernel";
@@ -1296,32 +1228,148 @@ void sconv_ksplit_defaults(KsRule* r) {
   }();
   *r = rule;
 }
-void sconv_ksplit_rule(const Ctx* ctx, int kind, int level, int* kparts, int* col_parts, int* kw) {
-  const KsRule& rule = ctx->ks_rule;
+KsChoice sconv_ksplit_rule(const KsRule& rule, int kind, int level) {
   const int l = std::min(std::max(level, 0), EGONN_NUM_LEVELS - 1);
   const int K = kind == 0 ? 27 : 8, mc = kind == 0 ? 0 : 1;
-  *kparts = std::min(std::max((int)rule.kparts[mc][l], 1), K);
-  *col_parts = rule.col_parts[l];
-  *kw = rule.kw[mc][l];
-}
-// Layers the weight-resident form exists for in the forward (see kernels.h): the 32->32 plan at output levels 1 and 2
-int sconv_resident_bit(int kind, int level, int cin, int cout, bool gated) {
-  if (cin != 32 || cout != 32) return 0;
-  if (kind == 0 && level == 1 && !gated) return 1;
-  if (kind == 1 && level == 1 && !gated) return 2;
-  if (kind == 1 && level == 2 && gated) return 4;
-  return 0;
+  return {std::min(std::max((int)rule.kparts[mc][l], 1), K), rule.col_parts[l], rule.kw[mc][l]};
 }
 size_t sconv_ksplit_scratch_floats(const Ctx* ctx) {
   size_t need = 0;
   for (int kind = 0; kind <= 2; ++kind)
     for (int l = (kind == 2 ? 0 : 1); l < EGONN_NUM_LEVELS - (kind == 2 ? 1 : 0); ++l) {
-      int kp, cp, kw;
-      sconv_ksplit_rule(ctx, kind, l, &kp, &cp, &kw);
+      const int kp = sconv_ksplit_rule(ctx->sconv.ks_rule, kind, l).kparts;
       if (kp > 1) need = std::max(need, (size_t)kp * rowgroup_cap_groups(ctx->plan, l) * 16 * 128);
     }
   return need;
 }
+
+// one workgroup per task up to a cap, rounded to the 8 XCDs: the hardware dispatcher then balances the uneven tasks (a grid of
+// only the resident workgroups was 30 % slower: each loops over ~3 tasks and the slowest decides)
+static unsigned task_grid(int64_t ntask, int64_t cap) { return (unsigned)((std::min(std::max<int64_t>(ntask, 8), cap) + 7) / 8 * 8); }
+
+#define SCONV_REFUSE_UNLESS(cond, code, ...) \
+  if (!(cond)) return set_error(__VA_ARGS__), ch.err = (code), ch
+
+// The launch of one layer under one setting: route, kernel instantiation, grid, block, LDS.  Pure: reads its arguments and the
+// process-wide measurement switches, makes no HIP call.  `groups`: the groups the map's row-group tables hold (it sizes grids and
+// picks among forms that compute the same bits; nothing that changes a row's arithmetic depends on it).
+SconvChoice sconv_choose(const SconvSettings& s, const SconvLayer& l, int64_t groups) {
+  SconvChoice ch;
+  const SconvSetting& set = s.set;
+  const int kind = l.kind, level = l.level, cin = l.cin, cout = l.cout;
+  const bool bf16 = l.bf16 != 0, small = small_level(level, bf16);
+  ch.route = ch.kernel = route_of(s, kind, level, cin, cout, bf16);
+  if (ch.route == ROUTE_PLAIN) return ch;
+  const int NS = cout / 32, K = kind == 0 ? 27 : 8;
+  if (ch.route != ROUTE_SPLIT) {
+    SCONV_REFUSE_UNLESS(l.split_io == 0 && !l.gated, EGONN_ERR_STATE,
+                        "sconv: split-form maps and gated inputs are read and written by the split kernel only");
+    SCONV_REFUSE_UNLESS(!l.residual || (!bf16 && level >= 5 && (set.product() || set.family == SCONV_RING)), EGONN_ERR_INVALID,
+                        "sconv: the epilogue residual exists in the per-tile kernel of fp32 maps (levels >= 5) and in the split kernel");
+    if (ch.route == ROUTE_WG) {
+      ch.NW = 4; ch.block = 256;
+      ch.lds = 2 * (size_t)(32 * cout * (bf16 ? 2 : 4)) + 4 * 28 * 16 * sizeof(int32_t);
+      ch.gx = task_grid(cdiv(groups, 4), 16384);
+      return ch;
+    }
+    const int KSP = std::min(cin / 32, 4);               // the waves of a workgroup split the input-channel blocks of one tile
+    ch.KSP = ch.NW = KSP; ch.block = KSP * 64;
+    const bool traced = set.family == SCONV_TRACED;      // its instantiations: 32->32 and 64->64; other plans run the per-tile kernel
+    if (ch.route == ROUTE_DMA && (!traced || (cin == cout && (cin == 32 || cin == 64)))) {
+      ch.D = set.family == SCONV_DMA3 ? 3 : 4; ch.PIPE = ch.D == 4; ch.TRACE = traced;
+      ch.lds = (size_t)KSP * ((2 * 256 + 32) * 4 + ch.D * 2048);
+      ch.gx = task_grid(groups * NS, 65536);
+      return ch;
+    }
+    ch.kernel = ROUTE_RG;
+    // prefetch depth (does not touch the arithmetic): few waves per SIMD (`small`) => nothing else hides the gather latency, keep 5
+    // items in flight; a full chip prefers the smaller register footprint.  bf16 maps, big launches: two groups per wave share the
+    // W fragments (the items are load-bound: W is two thirds of the bytes an item moves) — 9-12 % on the 32-channel layers at
+    // batch 64; fp32 items are MFMA-bound and gain nothing.  Very large launches (batch 64, levels 1-2): four groups, another 4 %
+    const bool free_bf16 = bf16 && set.family == SCONV_AUTO;
+    if (ch.route == ROUTE_TAIL_SPLIT) {                  // (ring depth 9 / 12 instead of 6: L6 k=3 21.7 / 22.5 vs 18.1 us, L6 k2s2
+      ch.D = 6; ch.G = 1; ch.SPLIT = 1;                  //  13.2 / 14.7 vs 8.8 — profiles/r06c_kw_sweep.txt)
+    } else if (free_bf16 && groups * NS * KSP >= 32768) {
+      ch.D = 3; ch.G = 4;
+    } else if ((set.family == SCONV_RING2 || free_bf16) && !small) {
+      ch.D = bf16 ? 4 : 3; ch.G = 2;
+    } else {
+      ch.D = small ? 6 : (bf16 ? 4 : 3); ch.G = 1;
+    }
+    const int npiece = (ch.G * 27 * 4 + 63) / 64;
+    ch.lds = KSP * (npiece * 256 + 16) * sizeof(int32_t) + (KSP > 1 ? (size_t)2 * KSP * 2 * ch.G * 64 * 16 : 0);
+    ch.gx = task_grid(cdiv(groups, ch.G) * NS, 65536);
+    return ch;
+  }
+
+  // ---- the split kernel (sconv_split.hip)
+  KsChoice ks = sconv_ksplit_rule(s.ks_rule, kind, level);
+  if (l.gated) { ks.kparts = 1; ks.kw = 0; }
+  if (cin < 64) ks.kw = 0;
+  const int kp = ks.kparts, kw = ks.kw;
+  ch.kparts = ch.gz = kp;
+  // the setting's explicit configuration, else EGONN_SPLIT_CFG (measurement override), else 142: workgroups of 4 waves
+  static const SplitCfg env_cfg = sconv_decode_cfg(switches().split_cfg ? switches().split_cfg : 142);
+  const SplitCfg& cfg = (set.split && set.cfg.code) ? set.cfg : env_cfg;
+  int parts = 1;
+  if (cfg.parts_sel > 0) parts = cfg.parts_sel > 3 ? NS : std::min(NS, 1 << (cfg.parts_sel - 1));
+  else if (ks.col_parts > 0) parts = std::min(NS, ks.col_parts);       // the layer's rule (offset-split launches)
+  else if (kw > 1) parts = std::max(1, NS / 2);                    // in-workgroup offset parts: 64 columns per workgroup, whatever the
+                                                                   // capacity (the choice of KW must not depend on the batch)
+  else if (NS >= 2 && cdiv(groups, 4) < 700) parts = 2;  // less than one round of the chip: two column parts per task
+                                                         // (measured, profiles/r03i_colparts.txt: L4 128->128 101 / 80 / 93 us
+                                                         //  with 1 / 2 / 4 parts, 64->128 56 / 45 / 51, L3 64->64 43 / 41; round 5, fp16 kernels:
+                                                         //  4 parts change neither the layers (profiles/r05g_parts4.txt) nor scans/s)
+  // Weight-resident form of the 32->32 plan (sconv_split_resident_kernel) — bit of SconvSettings::resident_mask that covers the
+  // layer: bit 0: k=3 of level 1, bit 1: k=2,s=2 into level 1, bit 2: gated k=2,s=2 into level 2.  The layer's rule, or cfg 183
+  const int rbit = (cin != 32 || cout != 32) ? 0 : (kind == 0 && level == 1 && !l.gated) ? 1 : (kind == 1 && level == 1 && !l.gated) ? 2
+                   : (kind == 1 && level == 2 && l.gated) ? 4 : 0;
+  const bool resident_rule = set.product() && !s.operand_autoscale && (s.resident_mask & rbit) != 0;
+  const bool resident = cfg.resident || (resident_rule && cfg.code == 142);
+  SCONV_REFUSE_UNLESS(!resident || (cin == 32 && cout == 32 && kp == 1 && kw <= 1), EGONN_ERR_INVALID,
+                        "sconv(split): the weight-resident form exists for the unsplit 32->32 plan only (%d->%d, K %d)", cin, cout, K);
+  if (l.gated) {
+    SCONV_REFUSE_UNLESS(cin == 32 && cout == 32 && !(l.split_io & 1) && (cfg.code == 142 || resident), EGONN_ERR_INVALID,
+                        "sconv(split): the gated input exists for the 32->32 plan only");
+    SCONV_REFUSE_UNLESS(!resident || K == 8, EGONN_ERR_INVALID, "sconv(split): the gated resident form exists for the 8-slot maps");
+    ch.GATED = 1;
+  }
+  if (resident) {
+    // one workgroup lifetime per CU slot (256 CUs; a k=3 workgroup fills a CU's LDS, two 8-slot workgroups share one), clipped to
+    // what the capacity can feed; resident_wgs > 0: measurement / test override (any count; no multiple of 8 = one slice)
+    ch.resident = 1; ch.NW = l.gated ? 12 : 8; ch.block = ch.NW * 64;
+    ch.lds = (size_t)K * 4096 + ch.NW * ((l.gated ? 512 : 2048) + 2 * 2048 + (l.gated ? 2 * 2048 : 0));
+    int64_t gx = (K > 8 || l.gated) ? 256 : 512;
+    gx = std::min<int64_t>(gx, (std::max<int64_t>(cdiv(groups, ch.NW), 8) + 7) / 8 * 8);
+    if (s.resident_wgs > 0) gx = std::min<int64_t>(s.resident_wgs, 1 << 16);
+    ch.gx = (unsigned)gx;
+    return ch;
+  }
+  // lock-step workgroups: LDS = KW * (two W slabs of NSW column slices) + NW * KW waves * (table + two ring slots (+ two of the gate operand))
+  auto lock_lds = [&](int nsw, int nw, int kwn) { return (size_t)kwn * 2 * nsw * 4096 + (size_t)nw * kwn * (2048 + 2 * 2048 + (l.gated ? 2 * 2048 : 0)); };
+  ch.KW = 1;
+  if (l.gated) {
+    ch.NW = 4; ch.NSW = 1;
+  } else if (cfg.trace) {                                // the traced instantiations: whole rows; 128->128 on the small maps' two column parts
+    const bool whole = (cin == 32 && cout == 32 && cfg.nw != 0) || (cin == 64 && cout == 64 && cfg.nw == 4);
+    SCONV_REFUSE_UNLESS(whole || (cin == 128 && cout == 128 && cfg.nw == 4), EGONN_ERR_INVALID,
+                        "sconv(split): no instantiation for %d->%d cfg %d", cin, cout, cfg.code);
+    ch.NW = cfg.nw; ch.NSW = whole ? NS : 2; ch.TRACE = 1;
+  } else {
+    SCONV_REFUSE_UNLESS(cfg.nw != 0, EGONN_ERR_INVALID, "sconv(split): no instantiation for %d->%d cfg %d", cin, cout, cfg.code);
+    ch.NW = cfg.nw; ch.NSW = NS / parts;
+    const bool parts_inst = ch.NW == 4 && cin >= 64;     // the plans with offset-part instantiations
+    if (parts_inst && kw >= 2 && kw <= 4 && lock_lds(ch.NSW, 4, kw) <= 160 * 1024) { ch.KW = kw; ch.KS = kp > 1; }
+    else if (parts_inst && kp > 1) ch.KS = 1;
+    else SCONV_REFUSE_UNLESS(kp == 1 && kw <= 1, EGONN_ERR_INVALID, "sconv(split): no offset-split instantiation for %d->%d (parts %d, kw %d)", cin, cout, kp, kw);
+  }
+  ch.block = ch.NW * ch.KW * 64;
+  ch.lds = lock_lds(ch.NSW, ch.NW, ch.KW);
+  ch.gx = task_grid(cdiv(groups, ch.NW), 1 << 20);
+  ch.gy = NS / ch.NSW;
+  return ch;
+}
+#undef SCONV_REFUSE_UNLESS
 
 // The kernel in the form the route reads: the model's pack, or (stand-alone operator call) W packed into the caller's scratch
 static int route_kernel(const ConvCall& c, int K, bool split, hipStream_t stream, const void** Wp) {
@@ -1345,8 +1393,11 @@ int sconv_map(Ctx* ctx, const ConvCall& c, hipStream_t stream) {
   if (V.n == 0) return EGONN_OK;
   const int K = kind == 0 ? 27 : 8;
   SconvLaunch l;
-  l.route = sconv_route(ctx, kind, level, c.cin, c.cout, c.bf16);
-  if (l.route == ROUTE_PLAIN) {
+  l.rg = kind == 0 ? &V.rg27 : (kind == 1 ? &V.rg8 : &V.rgT);
+  l.ch = sconv_choose(ctx->sconv, {kind, level, c.cin, c.cout, c.bf16, c.in2 != nullptr, c.split_io, c.residual != nullptr},
+                      l.rg->built ? l.rg->cap_groups : rowgroup_cap_groups(P, level));
+  const SconvRoute route = l.ch.route;
+  if (route == ROUTE_PLAIN) {
     EGONN_REQUIRE(!c.bf16, EGONN_ERR_INVALID, "sconv: bf16 feature maps need a 32/64/128/256-channel plan (%d->%d)", c.cin, c.cout);
     EGONN_REQUIRE(c.W, EGONN_ERR_INVALID, "sconv: the plain kernel needs the reference-layout kernel");
     if (kind == 2 && level == 0) EGONN_TRY(ensure_level0_parent_table(ctx, stream));
@@ -1355,29 +1406,15 @@ int sconv_map(Ctx* ctx, const ConvCall& c, hipStream_t stream) {
     return sconv_naive(reinterpret_cast<const float*>(c.in), nbr, c.W, c.scale, c.shift, c.relu, reinterpret_cast<float*>(c.out), V.n, K,
                        c.cin, c.cout, stream);
   }
+  if (l.ch.err != EGONN_OK) return l.ch.err;
   EGONN_TRY(ensure_rowgroups(ctx, &kind, &level, 1, stream));
-  l.rg = kind == 0 ? &V.rg27 : (kind == 1 ? &V.rg8 : &V.rgT);
-  l.n_in_cap = P.cap[lin]; l.groups_hint = l.rg->cap_groups;
-  const bool split = l.route == ROUTE_SPLIT || l.route == ROUTE_TAIL_SPLIT;   // fp16-split arithmetic: the split pack, the range guard
+  l.n_in_cap = P.cap[lin];
+  const bool split = route == ROUTE_SPLIT || route == ROUTE_TAIL_SPLIT;   // fp16-split arithmetic: the split pack, the range guard
   if (split) l.flags = ctx->dev_fp16_flag;
-  if (l.route != ROUTE_SPLIT)
-    EGONN_REQUIRE(c.split_io == 0 && !c.in2, EGONN_ERR_STATE,
-                  "sconv: split-form maps and gated inputs are read and written by the split kernel only");
   EGONN_TRY(route_kernel(c, K, split, stream, &l.Wp));
-  if (l.route != ROUTE_SPLIT) {
-    l.variant = ctx->conv_variant;
-    l.small = sconv_small_level(level, c.bf16);
-    return sconv_rg_forward(c, l, stream);
-  }
-  sconv_ksplit_rule(ctx, kind, level, &l.kparts, &l.col_parts, &l.kw);
-  if (c.in2) { l.kparts = 1; l.kw = 0; }
-  if (c.cin < 64) l.kw = 0;
-  l.variant = ctx->conv_variant >= 1000 ? ctx->conv_variant - 1000 : 0;
-  l.resident = (ctx->conv_variant == 0 && !ctx->operand_autoscale &&
-                (ctx->resident_mask & sconv_resident_bit(kind, level, c.cin, c.cout, c.in2 != nullptr)) != 0) ? 1 : 0;
-  l.resident_wgs = ctx->resident_wgs;
+  if (route != ROUTE_SPLIT) return sconv_rg_forward(c, l, stream);
   l.B = P.batch; l.part = ctx->ks_part; l.part_floats = ctx->ks_part_floats;
-  if (ctx->operand_autoscale) {
+  if (ctx->sconv.operand_autoscale) {
     l.in_absmax = reinterpret_cast<uint32_t*>(ctx->dev_counts + 24);
     l.in_elems = P.lv[lin].n * c.cin;
   }
@@ -1385,3 +1422,25 @@ int sconv_map(Ctx* ctx, const ConvCall& c, hipStream_t stream) {
 }
 
 }  // namespace egonn
+
+using namespace egonn;
+
+// what sconv_map would launch for a layer — no context, no device call (in / out: include/egonn_hip.h)
+API int egonn_debug_sconv_choice(const int32_t in[16], int64_t cap_groups, int32_t out[20]) {
+  EGONN_REQUIRE(in && out && cap_groups >= 0 && in[1] >= 0 && in[1] <= 2 && in[2] >= 0 && in[2] < EGONN_NUM_LEVELS && in[3] >= 1 && in[4] >= 1,
+                EGONN_ERR_INVALID, "debug_sconv_choice: bad arguments");
+  const int kind = in[1], level = in[2], mc = kind == 0 ? 0 : 1;
+  SconvSettings s;
+  s.set = sconv_decode(in[0]);
+  s.split_max_level = in[9]; s.operand_autoscale = in[10];
+  s.resident_mask = in[11] < 0 ? SCONV_RESIDENT_DEFAULT : in[11]; s.resident_wgs = in[12];
+  sconv_ksplit_defaults(&s.ks_rule);
+  if (in[13] >= 0) s.ks_rule.kparts[mc][level] = (int8_t)std::max(in[13], 1);
+  if (in[14] >= 0) s.ks_rule.kw[mc][level] = (int8_t)in[14];
+  if (in[15] >= 0) s.ks_rule.col_parts[level] = (int8_t)in[15];
+  const SconvChoice ch = sconv_choose(s, {kind, level, in[3], in[4], in[5], in[6] != 0, in[7], in[8] != 0}, cap_groups);
+  const int32_t v[20] = {ch.route, ch.kernel, ch.NW, ch.NSW, ch.KW, ch.KS, ch.GATED, ch.TRACE, ch.resident, ch.KSP, ch.D, ch.G, ch.SPLIT,
+                         ch.PIPE, (int32_t)ch.gx, (int32_t)ch.gy, (int32_t)ch.gz, (int32_t)ch.block, (int32_t)ch.lds, ch.kparts};
+  std::copy(v, v + 20, out);
+  return ch.err;
+}

@@ -921,34 +921,6 @@ __global__ __launch_bounds__(NW * 64) void sconv_split_resident_kernel(const Spl
   }
 }
 
-template <int NW, bool GATED>
-static int launch_split_resident(const SplitArgs& a, int64_t groups_hint, int max_workgroups, hipStream_t stream) {
-  using GEO = ResidentGeom<NW, GATED>;
-  const int lds = GEO::lds_bytes(a.K);
-  EGONN_REQUIRE(lds <= 160 * 1024 && a.K * 64 <= GEO::TBL, EGONN_ERR_INVALID, "sconv(split, resident): K = %d, %d bytes of LDS", a.K, lds);
-  static AttrOnce attr_done;
-  if (attr_done.need()) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sconv_split_resident_kernel<NW, GATED>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done.mark();
-  }
-  // one workgroup lifetime per CU slot (256 CUs; a k=3 workgroup fills a CU's LDS, two 8-slot workgroups share one), clipped to
-  // what the capacity can feed; max_workgroups > 0: measurement / test override (any count; no multiple of 8 = one slice)
-  int64_t gridx = (a.K > 8 || GATED) ? 256 : 512;
-  gridx = std::min<int64_t>(gridx, (std::max<int64_t>(cdiv(groups_hint, NW), 8) + 7) / 8 * 8);
-  if (max_workgroups > 0) gridx = std::min<int64_t>(max_workgroups, 1 << 16);
-  const dim3 grid((unsigned)gridx);
-  hipEvent_t* pev = prof_kernel_events();
-  if (pev[0]) {
-    hipExtLaunchKernelGGL((sconv_split_resident_kernel<NW, GATED>), grid, dim3(NW * 64), lds, stream, pev[0], pev[1], 0, a);
-    pev[0] = pev[1] = nullptr;
-  } else {
-    hipLaunchKernelGGL((sconv_split_resident_kernel<NW, GATED>), grid, dim3(NW * 64), lds, stream, a);
-  }
-  HIP_CHECK(hipGetLastError());
-  return EGONN_OK;
-}
-
 template <int COUT>
 static int launch_split_reduce(const SplitArgs& a, int64_t groups_hint, hipStream_t stream, hipEvent_t ev_stop) {
   const dim3 grid((unsigned)groups_hint);
@@ -958,32 +930,24 @@ static int launch_split_reduce(const SplitArgs& a, int64_t groups_hint, hipStrea
   return EGONN_OK;
 }
 
+template <int NW, bool GATED>
+static int launch_split_resident(const SplitArgs& a, const SconvChoice& ch, hipStream_t stream) {
+  using GEO = ResidentGeom<NW, GATED>;
+  EGONN_REQUIRE(ch.lds == (size_t)GEO::lds_bytes(a.K) && ch.block == NW * 64 && a.K * 64 <= GEO::TBL, EGONN_ERR_STATE,
+                "sconv(split, resident): the choice does not fit the instantiation (K = %d)", a.K);
+  return launch_sconv<sconv_split_resident_kernel<NW, GATED>>(ch, stream, a);
+}
+
+// an offset-split layer is timed from the begin of this launch to the end of its reducer (bench.py roofline leg)
 template <int CIN, int COUT, int NW, int NSW, bool TRACE = false, bool GATED = false, bool KS = false, int KW = 1>
-static int launch_split(const SplitArgs& a, int64_t groups_hint, hipStream_t stream) {
+static int launch_split(const SplitArgs& a, const SconvChoice& ch, hipStream_t stream) {
   using GEO = SplitGeom<NSW, NW, GATED, KW>;
-  static AttrOnce attr_done;
-  if (attr_done.need()) {
-    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sconv_split_kernel<CIN, COUT, NW, NSW, TRACE, GATED, KS, KW>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done.mark();
-  }
-  const int64_t ntask = cdiv(groups_hint, NW);
-  int64_t gridx = std::min<int64_t>(std::max<int64_t>(ntask, 8), 1 << 20);
-  gridx = (gridx + 7) / 8 * 8;
-  const dim3 grid((unsigned)gridx, (unsigned)(COUT / 32 / NSW), (unsigned)a.kp_n);
-  hipEvent_t* pev = prof_kernel_events();
+  static_assert(GEO::LDS_BYTES <= 160 * 1024, "lock-step workgroup: LDS budget");
+  EGONN_REQUIRE(ch.lds == (size_t)GEO::LDS_BYTES && ch.block == NW * KW * 64, EGONN_ERR_STATE,
+                "sconv(split): the choice does not fit the instantiation");
   hipEvent_t ev_stop = nullptr;
-  if (pev[0]) {      // bench.py roofline leg: time exactly this dispatch (an offset-split layer: begin of this one .. end of its reducer)
-    ev_stop = pev[1];
-    hipExtLaunchKernelGGL((sconv_split_kernel<CIN, COUT, NW, NSW, TRACE, GATED, KS, KW>), grid, dim3(NW * KW * 64), GEO::LDS_BYTES, stream,
-                          pev[0], a.kp_n > 1 ? nullptr : pev[1], 0, a);
-    pev[0] = pev[1] = nullptr;
-  } else {
-    hipLaunchKernelGGL((sconv_split_kernel<CIN, COUT, NW, NSW, TRACE, GATED, KS, KW>), grid, dim3(NW * KW * 64), GEO::LDS_BYTES, stream, a);
-  }
-  HIP_CHECK(hipGetLastError());
-  if (a.kp_n > 1) return launch_split_reduce<COUT>(a, groups_hint, stream, ev_stop);
-  return EGONN_OK;
+  EGONN_TRY((launch_sconv<sconv_split_kernel<CIN, COUT, NW, NSW, TRACE, GATED, KS, KW>>(ch, stream, a, a.kp_n > 1 ? &ev_stop : nullptr)));
+  return a.kp_n > 1 ? launch_split_reduce<COUT>(a, a.cap_groups, stream, ev_stop) : EGONN_OK;
 }
 
 // exactly the channel plans EGONN_SP_PLAN instantiates below (the forward plans of the trunk and heads + the two
@@ -995,17 +959,16 @@ bool sconv_split_supported(int cin, int cout) {
   return false;
 }
 
-// cfg = 100 + NW * 10 + 2 [+ 400 * (1 + log2(column parts))]; 0 = product choice (142: workgroups of 4 waves, automatic parts);
-// 100 + NW * 10 + 3 = 183: the weight-resident form (32->32 only)
+// The instantiation table of the split kernels: it switches on the fields of the choice (sconv_choose: kernels.h) and decides nothing
 int sconv_split_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream) {
   const RowGroups& rg = *l.rg;
-  const int cin = c.cin, cout = c.cout, kw = l.kw;
-  const int64_t groups_hint = l.groups_hint;
+  const SconvChoice& ch = l.ch;
+  const int cin = c.cin, cout = c.cout;
   EGONN_REQUIRE(rg.built, EGONN_ERR_STATE, "sconv: row-group tables not built");
   EGONN_REQUIRE(sconv_split_supported(cin, cout), EGONN_ERR_INVALID, "sconv(split): channel plan %d->%d not supported", cin, cout);
   EGONN_REQUIRE((uint64_t)l.n_in_cap * cin * 4 < (1ull << 32) - (1ull << 20), EGONN_ERR_INVALID,
                 "sconv: input feature map of %lld rows exceeds the 4 GiB buffer-resource range", (long long)l.n_in_cap);
-  if (groups_hint <= 0) return EGONN_OK;
+  if (rg.cap_groups <= 0) return EGONN_OK;
   SplitArgs a;
   a.in = reinterpret_cast<const float*>(c.in); a.snbr = rg.snbr; a.gmask = rg.gmask; a.perm = rg.perm; a.meta = rg.meta; a.Wsp = l.Wp;
   a.order = switches().no_task_order ? nullptr : rg.order4;
@@ -1023,74 +986,41 @@ int sconv_split_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t str
     a.in_maxbits = l.in_absmax + 1;
   }
   a.out_split = (c.split_io & 2) ? 1 : 0;
-  if (l.kparts > 1) {
-    EGONN_REQUIRE(l.kparts <= rg.K && !c.in2, EGONN_ERR_INVALID, "sconv(split): %d offset parts on a %d-slot map", l.kparts, rg.K);
-    EGONN_REQUIRE(l.part && l.part_floats >= sconv_split_part_floats(rg, cout, l.kparts), EGONN_ERR_STATE,
+  if (ch.kparts > 1) {
+    EGONN_REQUIRE(l.part && l.part_floats >= sconv_split_part_floats(rg, cout, ch.kparts), EGONN_ERR_STATE,
                   "sconv(split): no scratch for the partial tiles of an offset-split launch");
     a.part = l.part;
-    a.kp_n = l.kparts;
+    a.kp_n = ch.kparts;
   }
-  // 0 = product choice: 142, the lock-step kernel on workgroups of 4 waves (EGONN_SPLIT_CFG: measurement override)
-  const int cfg = l.variant ? l.variant : (switches().split_cfg ? switches().split_cfg : 142);
-  const bool trace = cfg >= 9000;                        // 9000 + shape: the s_memtime build (tools/split_trace.py)
-  int shape = trace ? cfg - 9000 : cfg;
-  int parts_sel = 0;
-  if (shape >= 500) { parts_sel = shape / 400; shape -= 400 * parts_sel; }
-  const int ns_tot = cout / 32;
-  int parts = 1;
-  if (parts_sel > 0) parts = std::min(ns_tot, 1 << (parts_sel - 1));
-  else if (l.col_parts > 0) parts = std::min(ns_tot, l.col_parts);      // the layer's rule (offset-split launches)
-  else if (kw > 1) parts = std::max(1, ns_tot / 2);                 // in-workgroup offset parts: 64 columns per workgroup, whatever the
-                                                                    // capacity (the choice of KW must not depend on the batch)
-  else if (ns_tot >= 2 && cdiv(groups_hint, 4) < 700) {  // less than one round of the chip: two column parts per task
-    parts = 2;                                           // (measured, profiles/r03i_colparts.txt: L4 128->128 101 / 80 / 93 us
-  }                                                      //  with 1 / 2 / 4 parts, 64->128 56 / 45 / 51, L3 64->64 43 / 41; round 5, fp16 kernels:
-                                                         //  4 parts change neither the layers (profiles/r05g_parts4.txt) nor scans/s)
-  const int nsw = ns_tot / parts;
-  // 183: the weight-resident form (workgroups of 8 waves; 32->32 only) — the layer's rule (l.resident) or the explicit cfg
-  const bool resident = !trace && (shape == 183 || (l.resident && cfg == 142));
-  if (resident)
-    EGONN_REQUIRE(cin == 32 && cout == 32 && a.kp_n == 1 && kw <= 1 && (rg.K == 27 || rg.K == 8), EGONN_ERR_INVALID,
-                  "sconv(split): the weight-resident form exists for the unsplit 32->32 plan only (%d->%d, K %d)", cin, cout, rg.K);
-  if (c.in2) {
-    EGONN_REQUIRE(cin == 32 && cout == 32 && c.gate && l.B >= 1 && !a.in_split && (cfg == 142 || resident), EGONN_ERR_INVALID,
-                  "sconv(split): the gated input exists for the 32->32 plan only");
+  if (ch.TRACE) a.trace = g_sconv_trace;
+  if (ch.GATED) {
+    EGONN_REQUIRE(c.gate && l.B >= 1, EGONN_ERR_INVALID, "sconv(split): the gated input exists for the 32->32 plan only");
     a.in2 = c.in2; a.gate = c.gate; a.B = l.B;
-    if (resident) {
-      EGONN_REQUIRE(rg.K == 8, EGONN_ERR_INVALID, "sconv(split): the gated resident form exists for the 8-slot maps");
-      return launch_split_resident<12, true>(a, groups_hint, l.resident_wgs, stream);
-    }
-    return launch_split<32, 32, 4, 1, false, true>(a, groups_hint, stream);
+    if (ch.resident) return launch_split_resident<12, true>(a, ch, stream);
+    return launch_split<32, 32, 4, 1, false, true>(a, ch, stream);
   }
-  if (resident) return launch_split_resident<8, false>(a, groups_hint, l.resident_wgs, stream);
+  if (ch.resident) return launch_split_resident<8, false>(a, ch, stream);
 #define EGONN_SP_KW(CI, CO, NWW, NSWW, KWW)                                                               \
   if constexpr (SplitGeom<NSWW, NWW, false, KWW>::LDS_BYTES <= 160 * 1024) {                              \
-    if (kw == KWW && a.kp_n > 1) return launch_split<CI, CO, NWW, NSWW, false, false, true, KWW>(a, groups_hint, stream);  \
-    if (kw == KWW) return launch_split<CI, CO, NWW, NSWW, false, false, false, KWW>(a, groups_hint, stream); \
+    if (ch.KW == KWW && ch.KS) return launch_split<CI, CO, NWW, NSWW, false, false, true, KWW>(a, ch, stream);  \
+    if (ch.KW == KWW) return launch_split<CI, CO, NWW, NSWW, false, false, false, KWW>(a, ch, stream);    \
   }
 #define EGONN_SP_LOCK1(CI, CO, NWW, NSWW)                                                                 \
-  if (cin == CI && cout == CO && shape == 100 + NWW * 10 + 2 && nsw == NSWW && !trace) {                  \
+  if (cin == CI && cout == CO && ch.NW == NWW && ch.NSW == NSWW && !ch.TRACE) {                           \
     if constexpr (NWW == 4 && CI >= 64) {                                                                 \
       EGONN_SP_KW(CI, CO, NWW, NSWW, 2) EGONN_SP_KW(CI, CO, NWW, NSWW, 3) EGONN_SP_KW(CI, CO, NWW, NSWW, 4) \
-      if (a.kp_n > 1) return launch_split<CI, CO, NWW, NSWW, false, false, true>(a, groups_hint, stream); \
+      if (ch.KS) return launch_split<CI, CO, NWW, NSWW, false, false, true>(a, ch, stream);               \
     }                                                                                                     \
-    EGONN_REQUIRE(a.kp_n == 1 && kw <= 1, EGONN_ERR_INVALID, "sconv(split): no offset-split instantiation for %d->%d (parts %d, kw %d)", cin, cout, a.kp_n, kw); \
-    return launch_split<CI, CO, NWW, NSWW>(a, groups_hint, stream);                                       \
+    return launch_split<CI, CO, NWW, NSWW>(a, ch, stream);                                                \
   }
 #define EGONN_SP_LOCK(CI, CO, NWW)                                                                        \
   EGONN_SP_LOCK1(CI, CO, NWW, (CO / 32))                                                                  \
   if constexpr (CO >= 64) { EGONN_SP_LOCK1(CI, CO, NWW, (CO / 64)) }                                      \
   if constexpr (CO >= 128) { EGONN_SP_LOCK1(CI, CO, NWW, (CO / 128)) }
-#define EGONN_SP_LOCK_TRACE(CI, CO, NWW)                                                                  \
-  if (cin == CI && cout == CO && shape == 100 + NWW * 10 + 2 && trace) {                                  \
-    a.trace = g_sconv_trace;                                                                              \
-    return launch_split<CI, CO, NWW, (CO / 32), true>(a, groups_hint, stream);                            \
-  }
-  EGONN_SP_LOCK_TRACE(32, 32, 4) EGONN_SP_LOCK_TRACE(32, 32, 8) EGONN_SP_LOCK_TRACE(64, 64, 4)
-  if (cin == 128 && cout == 128 && shape == 142 && trace) {              // the small maps' shape: two column parts
-    a.trace = g_sconv_trace;
-    return launch_split<128, 128, 4, 2, true>(a, groups_hint, stream);
-  }
+#define EGONN_SP_LOCK_TRACE(CI, CO, NWW, NSWW)                                                            \
+  if (cin == CI && cout == CO && ch.NW == NWW && ch.NSW == NSWW && ch.TRACE) return launch_split<CI, CO, NWW, NSWW, true>(a, ch, stream);
+  EGONN_SP_LOCK_TRACE(32, 32, 4, 1) EGONN_SP_LOCK_TRACE(32, 32, 8, 1) EGONN_SP_LOCK_TRACE(64, 64, 4, 2)
+  EGONN_SP_LOCK_TRACE(128, 128, 4, 2)                    // the small maps' shape: two column parts
 #define EGONN_SP_PLAN(CI, CO) EGONN_SP_LOCK(CI, CO, 8) EGONN_SP_LOCK(CI, CO, 4)
   EGONN_SP_PLAN(32, 32)
   EGONN_SP_PLAN(32, 64)
@@ -1102,8 +1032,9 @@ int sconv_split_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t str
 #undef EGONN_SP_PLAN
 #undef EGONN_SP_LOCK
 #undef EGONN_SP_LOCK1
+#undef EGONN_SP_KW
 #undef EGONN_SP_LOCK_TRACE
-  set_error("sconv(split): no instantiation for %d->%d cfg %d", cin, cout, cfg);
+  set_error("sconv(split): the choice for %d->%d (NW %d, NSW %d) has no instantiation", cin, cout, ch.NW, ch.NSW);
   return EGONN_ERR_INVALID;
 }
 

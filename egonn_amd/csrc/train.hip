@@ -569,7 +569,7 @@ static int conv0_wgrad(Ctx* ctx, const float* feat, const float* dout, float* dW
   EGONN_REQUIRE(ctx->conv0_lut && P.g0 && P.t2m && P.t2s, EGONN_ERR_STATE,
                 "conv0 wgrad: run the forward convolution of this plan first");
   EGONN_REQUIRE(scratch && scratch_floats >= (size_t)size, EGONN_ERR_INVALID, "conv0 wgrad: scratch too small");
-  if (!feat && ctx->conv_variant != 3) {                   // unit features: the MFMA kernel (variant 3 = cross-check path)
+  if (!feat && ctx->sconv.set.family != SCONV_PLAIN) {       // unit features: the MFMA kernel (SCONV_PLAIN = cross-check path)
     int64_t wgs = std::min<int64_t>(512, cdiv(cdiv(n0, 32), 4));
     wgs = std::max<int64_t>(1, std::min<int64_t>(wgs, (int64_t)(scratch_floats / (size_t)size)));
     hipLaunchKernelGGL(conv0_wgrad_unit_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, dout, P.lv[0].keys, P.g0, P.t2m,

@@ -48,9 +48,21 @@ enum { EGONN_FLAG_DISABLE_GLOBAL = 1, EGONN_FLAG_DISABLE_LOCAL = 2, EGONN_FLAG_I
 int egonn_ctx_create(egonn_ctx** ctx, int device, int coord_bits);
 void egonn_ctx_destroy(egonn_ctx* ctx);
 const char* egonn_last_error(void);
-/* tests / measurements only: on = 1 routes this context's sparse convolutions through the plain one-thread-per-output
- * HIP kernel (cross-check of the MFMA kernels), on = 2 / 4 force the per-wave / the workgroup-cooperative MFMA kernel (A/B
- * timing); 0 = product choice.  Never set by the product path. */
+/* tests / measurements only: which kernel this context's sparse convolutions run on.  Never set by the product path.  The codes:
+ *     0   the product choice (so is every other code below 1000 that is not listed here)
+ *     1   the plain one-thread-per-output HIP kernel, every layer: the cross-check of the MFMA kernels
+ *     2   the register-ring per-tile kernel (exact fp32 / bf16)
+ *     4   the workgroup-cooperative kernel
+ *     8   the register-ring kernel with two groups per wave
+ *    16   the LDS-DMA kernel, split-phase LDS fetch, 4 ring slots (fp32 maps; bf16 maps: the register-ring kernel)
+ *    32   the LDS-DMA kernel with the fetch inside the item, 3 ring slots
+ *   128   the traced build of the LDS-DMA kernel (egonn_debug_set_trace; 32->32 and 64->64, other plans untraced)
+ *   1000 + cfg   the fp16-split kernel on every fp32 map it is instantiated for, in the configuration cfg; cfg 0 = its default
+ *                (142, or EGONN_SPLIT_CFG).  cfg = shape [+ 400 * (1 + log2(column parts per task))] [+ 9000: the traced build],
+ *                shape = 100 + 10 * NW + 2: lock-step workgroups of NW = 4 or 8 waves (142, 182), or 183: the weight-resident
+ *                form (32->32 only).  Without the 400s term the layer's own rule picks the column parts.  A cfg whose shape has
+ *                no instantiation is an error of the convolution, not of this call.
+ * Codes 2 .. 128 compute bitwise the same results; the exact kernels and the split kernel differ by the split's rounding. */
 int egonn_debug_set_naive_conv(egonn_ctx* ctx, int on);
 /* tests / measurements only: the offset-split rule of this context's fp32 sparse convolutions on the small maps (the rule is
  * a function of (map class, output level), never of the batch).  map_class 0 = the k=3 maps, 1 = the 8-slot maps (k=2,s=2 and
@@ -70,7 +82,7 @@ int egonn_debug_set_resident(egonn_ctx* ctx, int mask, int max_workgroups);
  * has a map to return (by default level 1's block tail of fp32 maps is evaluated inside level 2's strided convolution and its
  * 23 MB output never exists; bitwise the same results either way) */
 int egonn_debug_keep_level_features(egonn_ctx* ctx, int on);
-/* measurement hook: buffer for the traced sparse-conv build (debug variant 128): 8 u64 per wave task; NULL = off */
+/* measurement hook: buffer for the traced sparse-conv builds (code 128, cfg 9000 + shape): 8 u64 per wave task; NULL = off */
 int egonn_debug_set_trace(void* device_buffer);
 /* measurement hook: device copies of a map's row-group tables (gmask [groups], snbr [groups][K][16], nullable).  [SYNC] */
 int egonn_debug_rowgroup_tables(egonn_ctx* ctx, int map_kind, int level_out, uint32_t* gmask_out, int32_t* snbr_out,
@@ -496,6 +508,15 @@ int egonn_debug_dense(const void* in, int in_bf16, int64_t rows_capacity, const 
  * dynamic LDS bytes, out[4] = output columns per block of grid y (persistent LDS kernel, else 0).  A form or a gate the shape
  * does not have is the launcher's own error. */
 int egonn_debug_dense_route(int64_t rows, int cin, int cout, int form, int gate_scans, int32_t out[5]);
+/* test hook, host only (no context, no device call): the whole launch sconv_map would make for one sparse-convolution layer
+ * under one setting — sconv_choose, DESIGN.md §3.1 "Host side of a convolution"; tests/test_sconv_choice_host.py.
+ * in = code (as egonn_debug_set_naive_conv), map kind, output level, cin, cout, bf16, gated input, split_io, epilogue residual,
+ *      split level limit (-1 = exact fp32), operand autoscale, resident mask (-1 = product rule), resident max_workgroups,
+ *      kparts, kw, col_parts (each -1 = the product offset-split rule; as egonn_debug_set_ksplit)
+ * cap_groups = the groups the map's row-group tables hold
+ * out = route, kernel (both SconvRoute of egonn_amd/csrc/kernels.h), NW, NSW, KW, KS, GATED, TRACE, resident, KSP, D, G, SPLIT,
+ *       PIPE, grid x, y, z, block size, dynamic LDS bytes, kparts.  A refused combination returns the convolution's own error. */
+int egonn_debug_sconv_choice(const int32_t in[16], int64_t cap_groups, int32_t out[20]);
 /* out (ca,cb) = a^T b over n rows: weight gradient of a dense layer (a = input, b = grad_out for the (cin,cout) layout). */
 int egonn_dense_backward_weight(const float* a, int ca, const float* b, int cb, int64_t n, float* out, float* scratch,
                                 int64_t scratch_floats, void* stream);

@@ -248,7 +248,7 @@ def test_sparse_conv_precisions_and_group_sums(gpu):
             assert ((v16.float() - got16.float()).abs().max() / scale) < 8e-3, (var, kind, lvl)
             if var == 2:
                 per_wave = (v32, s32)
-            if var in (16, 32):     # the LDS-DMA kernel (KSP-wave / 4-wave workgroups) runs the register-ring kernel's arithmetic
+            if var in (16, 32):     # the LDS-DMA kernel (split-phase fetch, 4 ring slots / fetch inside the item, 3 slots) runs the register-ring kernel's arithmetic
                 assert torch.equal(v32, per_wave[0]) and torch.equal(s32, per_wave[1]), (var, kind, lvl)
         ctx.lib.egonn_debug_set_naive_conv(ctx.h, 0)
 

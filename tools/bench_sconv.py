@@ -68,7 +68,7 @@ for (kind, lvl, ci, co) in cfgs:
         es = 4 if dt == torch.float32 else 2
         alg = P * ci * es + n_out * co * es + K * ci * co * es + 8 * P
         fl = 2 * P * ci * co
-        ctx.lib.egonn_debug_set_naive_conv(ctx.h, 0)
+        ctx.lib.egonn_debug_set_naive_conv(ctx.h, _lib.CONV_PRODUCT)
         rows.append(dict(kind=kind, level=lvl, cin=ci, cout=co, dtype=str(dt).split(".")[-1] + ("/v%d" % var if var else ""), us=us, pairs=P, n_out=n_out,
                          groups=ng, alg_MB=alg / 1e6, hbm_frac=alg / (us * 1e-6) / 8e12, tflops=fl / (us * 1e-6) / 1e12, rel_err=err))
         r = rows[-1]

@@ -29,7 +29,8 @@ ng = ctx.map_groups(kind, lvl)[0]
 ksp = min(ci // 32, 4)
 ntr = ng * (co // 32) * ksp
 buf = torch.zeros((ntr + 64, 8), dtype=torch.int64, device="cuda")
-ctx.lib.egonn_debug_set_naive_conv(ctx.h, 2009 if ci == 128 else 128)
+# (2009 predates the cfg grammar of include/egonn_hip.h and decodes to no instantiation: the 128->128 leg is stale)
+ctx.lib.egonn_debug_set_naive_conv(ctx.h, 2009 if ci == 128 else _lib.CONV_TRACED)
 for _ in range(3): ctx.sparse_conv(kind, lvl, x, w)
 buf.zero_()
 ctx.lib.egonn_debug_set_trace(buf.data_ptr())
@@ -37,7 +38,7 @@ torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); ctx.sparse_conv(kind, lvl, x, w); e1.record(); torch.cuda.synchronize()
 ctx.lib.egonn_debug_set_trace(None)
-ctx.lib.egonn_debug_set_naive_conv(ctx.h, 0)
+ctx.lib.egonn_debug_set_naive_conv(ctx.h, _lib.CONV_PRODUCT)
 t = buf.cpu().numpy()[:ntr]
 t = t[t[:, 4] > 0]
 t0 = t[:, 0].min()

@@ -25,7 +25,7 @@ x = torch.randn(ctx.level_count(lin), ci, device="cuda")
 w = torch.randn(K, ci, co, device="cuda") * 0.05
 ng = ctx.map_groups(kind, lvl)[0]
 buf = torch.zeros((ng + 64, 12), dtype=torch.int64, device="cuda")
-var = 1000 + 9000 + 100 + NW * 10 + 2
+var = _lib.CONV_SPLIT + _lib.CFG_TRACED + 100 + NW * 10 + 2     # the traced build of the lock-step shape (142 / 182)
 ctx.lib.egonn_debug_set_naive_conv(ctx.h, var)
 for _ in range(3): ctx.sparse_conv(kind, lvl, x, w)
 buf.zero_()
@@ -34,7 +34,7 @@ torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); ctx.sparse_conv(kind, lvl, x, w); e1.record(); torch.cuda.synchronize()
 ctx.lib.egonn_debug_set_trace(None)
-ctx.lib.egonn_debug_set_naive_conv(ctx.h, 0)
+ctx.lib.egonn_debug_set_naive_conv(ctx.h, _lib.CONV_PRODUCT)
 t = buf.cpu().numpy()[:ng].astype(np.float64)
 t = t[t[:, 10] > 0]
 t0 = t[:, 0].min(); span = t[:, 10].max() - t0
