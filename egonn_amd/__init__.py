@@ -24,6 +24,7 @@ from .tuples import (TrainingTuple, EvaluationTuple, EvaluationSet, save_trainin
                      count_within, relative_poses, CloudBank, generate_training_tuples, filter_query_elements,
                      generate_evaluation_set, TupleIndex, BatchSampler, TrainingSet)
 from .relocalize import KeypointMap, verify_candidates, Relocalizer, evaluate_relocalization
+from .loop_closure import knn_window, time_windows, detect_loops, LoopDetector, evaluate_loop_closure
 from .scan_context import ScanContext, ScanContextManager, sc2rk, distance_sc, evaluate as evaluate_scan_context
 
 __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "MinkHead", "MinkTrunk",
@@ -39,4 +40,5 @@ __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "Mink
            "count_within", "relative_poses", "CloudBank", "generate_training_tuples", "filter_query_elements",
            "generate_evaluation_set", "TupleIndex", "BatchSampler", "TrainingSet",
            "KeypointMap", "verify_candidates", "Relocalizer", "evaluate_relocalization",
+           "knn_window", "time_windows", "detect_loops", "LoopDetector", "evaluate_loop_closure",
            "ScanContext", "ScanContextManager", "sc2rk", "distance_sc", "evaluate_scan_context"]

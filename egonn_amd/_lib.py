@@ -165,6 +165,12 @@ _SIGS = [
                                          C.c_int64, _P]),
     ("egonn_gather_candidates", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     ("egonn_pick_candidates", C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int] + [_P] * 12),
+    ("egonn_time_windows", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_double, C.c_double, _P, _P, _P, _P]),
+    ("egonn_knn_window_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_knn_window", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("egonn_window_radius", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, _P, _P, C.c_float, _P, _P, _P, _P]),
+    ("egonn_pr_curve_scratch_bytes", C.c_int64, [C.c_int64]),
+    ("egonn_pr_curve", C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     ("egonn_profile_enable", C.c_int, [_P, C.c_int, C.c_char_p]),
     ("egonn_profile_fetch", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),

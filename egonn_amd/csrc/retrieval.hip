@@ -2,13 +2,15 @@
 // (BASELINE configs[4]; reference eval/evaluate.py:60-88 and :168-184):
 //     embed_dist = np.linalg.norm(map_embeddings - query_embedding, axis=1);  nn_ndx = np.argsort(embed_dist)[:k]
 //     euclid_dist = norm(query_pos - map_positions[nn_ndx]);  tp[r][nn] += any(euclid_dist[:nn+1] <= r)
-// knn_dist_kernel: one workgroup per query, one wave per database row at a time (a 256-float row is one
-// float4 per lane), exact difference form (not the |a|^2+|b|^2-2ab expansion) like the reference.
+// knn_dist_kernel: one workgroup per query, one wave per database row at a time, exact difference form (not the
+// |a|^2+|b|^2-2ab expansion) like the reference; the row distance is knn_row_distance (retrieval.h), shared with the
+// windowed search of loop_closure.hip, whose distances are these bit for bit.
 // knn_select_kernel: k rounds of a workgroup-wide arg-min over the query's distance row (ties: lower index).
 // Non-finite distances: +inf (an overflowing or infinite element) is a distance like any other, after every finite one
 // and in index order; a NaN distance is never a neighbour, the list then ends early with (-1, +inf).  A taken entry is
 // marked NaN, which no comparison selects, so that a genuine +inf is returned once and only once.
 #include "model.h"
+#include "retrieval.h"
 
 namespace egonn {
 
@@ -19,15 +21,9 @@ __global__ __launch_bounds__(256) void knn_dist_kernel(const float* __restrict__
   for (int i = t; i < d; i += 256) s_q[i] = query[(int64_t)q * d + i];
   __syncthreads();
   for (int32_t r = w; r < m; r += 4) {
-    const float* row = db + (int64_t)r * d;
-    float s = 0.f;
-    for (int i = lane; i < d; i += 64) {
-      const float df = row[i] - s_q[i];
-      s = fmaf(df, df, s);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) dist[(int64_t)q * m + r] = sqrtf(s);
+    float v[1];
+    knn_row_distance<1>(db + (int64_t)r * d, 0, s_q, d, lane, v);
+    if (lane == 0) dist[(int64_t)q * m + r] = v[0];
   }
 }
 

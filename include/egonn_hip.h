@@ -932,6 +932,47 @@ int egonn_pick_candidates(const int32_t* nn_index, int n_queries, int k, int n_b
                           int32_t* reranked, double* T_rel, double* pose, int32_t* safe_pick, int32_t* best_inliers,
                           int32_t* status, double* best_rte, double* best_rre, int32_t* best_success, void* stream);
 
+/* ------------------------------------------------------------------ loop closure inside one trajectory (csrc/loop_closure.hip)
+ * "Has the vehicle been here before?": every scan of a growing trajectory is searched against the scans that are old enough.
+ * Every entry point validates its arguments before any launch (EGONN_STATUS_INVALID), takes a stream and never synchronises.
+ *
+ * egonn_time_windows: the admissible window [win_lo[q], win_hi[q]) of every query from float64 time stamps (Unix-time stamps
+ * at 0.1 s spacing do not survive fp32), one binary search per bound: win_hi[q] = #{j : t_db[j] <= t_q[q] - min_gap} (the bound
+ * is inclusive), win_lo[q] = #{j : t_db[j] < t_q[q] - max_gap} (max_gap = +inf: 0).  t_db (m) must be non-decreasing; status
+ * (DEVICE, 1 int) bit 0 is set when it is not (a NaN stamp counts), the windows are then unspecified but inside [0, m].
+ *
+ * egonn_knn_window: egonn_knn of query q on database[lo:hi], lo = max(win_lo[q], 0) (win_lo NULL = 0), hi = min(win_hi[q],
+ * n_database), with lo added to the indices: ascending distance, ties to the lower index, (-1, +inf) where fewer than k rows are
+ * admissible (lo >= hi: the whole list), the +inf / NaN rules of egonn_knn, and distances bit-identical to egonn_knn's (the two
+ * kernels share the row-distance function).  win_lo / win_hi: DEVICE (n_query) int32.  1 <= k <= 64, 1 <= dim <= 4096,
+ * n_database >= 0 (0: every list is empty), n_query = 0 returns at once.  There is no n_query x n_database buffer: the k best
+ * are kept while the rows stream past, and the result of a query does not depend on the other queries of the call.  The
+ * scratch (8-byte aligned, 0 bytes for 512 queries or more: NULL is accepted then) depends on n_query and k only.
+ *
+ * egonn_window_radius: count[q] = rows j of the window with sqrtf(sum_c fmaf(d_c, d_c, .)) <= radius, d_c = qpos[q][c] -
+ * dbpos[j][c] (the form and component order of egonn_recall_counts; position_dim 2 or 3); with pred (n_query, nullable):
+ * pred_dist[q] = that distance to row pred[q], +inf when pred[q] < 0 or >= m.
+ *
+ * egonn_pr_curve: the precision/recall curve of n decisions.  A lower score is more confident; +inf or NaN = no prediction;
+ * -0.0 counts as +0.0; negative scores are legal.  order (n) = the stable ascending order by (score, index), predictions first
+ * (the flat radix sort on the monotone map of the float's bits); cum_tp / cum_fp / cum_rev (n) = inclusive counts over
+ * positions 0..i of correct != 0 / correct == 0 / revisit != 0 among the predictions (positions behind the last prediction
+ * repeat its counts); group_end[i] = 1 where position i is the last of a run of equal scores among the predictions: the points
+ * of the curve; totals (DEVICE, 2) = number of predictions, number of revisit != 0 over all n.  scratch: 256-byte aligned. */
+int egonn_time_windows(const double* t_db, int64_t m, const double* t_q, int64_t n_query, double min_gap, double max_gap,
+                       int32_t* win_lo, int32_t* win_hi, int32_t* status, void* stream);
+int64_t egonn_knn_window_scratch_bytes(int64_t n_query, int k);      /* -1 on bad arguments; no dependence on n_database */
+int egonn_knn_window(const float* query, int64_t n_query, const float* database, int64_t n_database, int dim, int k,
+                     const int32_t* win_lo, const int32_t* win_hi, int32_t* out_index, float* out_distance, void* scratch,
+                     int64_t scratch_bytes, void* stream);
+int egonn_window_radius(const float* query_positions, int64_t n_query, const float* db_positions, int64_t m, int position_dim,
+                        const int32_t* win_lo, const int32_t* win_hi, float radius, const int32_t* pred, int32_t* count,
+                        float* pred_dist, void* stream);
+int64_t egonn_pr_curve_scratch_bytes(int64_t n);                      /* -1 on bad arguments */
+int egonn_pr_curve(const float* score, const int32_t* correct, const int32_t* revisit, int64_t n, int32_t* order,
+                   int32_t* cum_tp, int32_t* cum_fp, int32_t* cum_rev, uint8_t* group_end, int32_t* totals, void* scratch,
+                   int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ launch timing (bench.py roofline leg)
  * mode 0: off; 1: time every tagged sparse-conv launch (event records around it); 2: only launches whose tag contains
  * `filter`, with the events attached to the kernel dispatch itself (the kernel's own begin..end, also when other streams
