@@ -25,6 +25,8 @@ from .tuples import (TrainingTuple, EvaluationTuple, EvaluationSet, save_trainin
                      generate_evaluation_set, TupleIndex, BatchSampler, TrainingSet)
 from .relocalize import KeypointMap, verify_candidates, Relocalizer, evaluate_relocalization
 from .loop_closure import knn_window, time_windows, detect_loops, LoopDetector, evaluate_loop_closure
+from .pose_graph import (pose_graph_cost, pose_graph_hessvec, optimize_pose_graph, odometry_edges, loop_edges,
+                         optimize_trajectory)
 from .scan_context import ScanContext, ScanContextManager, sc2rk, distance_sc, evaluate as evaluate_scan_context
 
 __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "MinkHead", "MinkTrunk",
@@ -41,4 +43,5 @@ __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "Mink
            "generate_evaluation_set", "TupleIndex", "BatchSampler", "TrainingSet",
            "KeypointMap", "verify_candidates", "Relocalizer", "evaluate_relocalization",
            "knn_window", "time_windows", "detect_loops", "LoopDetector", "evaluate_loop_closure",
+           "pose_graph_cost", "pose_graph_hessvec", "optimize_pose_graph", "odometry_edges", "loop_edges", "optimize_trajectory",
            "ScanContext", "ScanContextManager", "sc2rk", "distance_sc", "evaluate_scan_context"]

@@ -973,6 +973,64 @@ int egonn_pr_curve(const float* score, const int32_t* correct, const int32_t* re
                    int32_t* cum_tp, int32_t* cum_fp, int32_t* cum_rev, uint8_t* group_end, int32_t* totals, void* scratch,
                    int64_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ pose-graph optimisation (csrc/pose_graph.hip)
+ * The corrected trajectory behind the loop detector.  Unknowns: poses X_i = [R_i | t_i] as (n,4,4) float64; edge e = (a, b, Z,
+ * (w_rot, w_trans)) measures Z ~ X_a^-1 X_b, weights in 1/sigma^2, both 0 = off.  E = Z^-1 X_a^-1 X_b, r = [t_E ; Log_SO3 R_E],
+ * s = sqrt(w_trans |t_E|^2 + w_rot |Log R_E|^2), rho = 1 or, robust_delta > 0, min(1, delta / s) (Huber by IRLS: recomputed at
+ * every linearisation, fixed inside the linear solve), cost = sum rho (1 - rho / 2) s^2 (s^2 / 2, and delta s - delta^2 / 2 beyond
+ * delta: the Huber cost, whose gradient is sum J^T rho W r).  Retraction R <- R Exp(w), t <- t + R v for
+ * delta_i = (v, w), followed by one Newton-Schulz step on R; a node whose delta is exactly 0 is copied bit for bit.  Residual
+ * rotations up to pi - 1e-3; beyond, EGONN_PG_STATUS_ANGLE and weight 0 for that linearisation.
+ * Every entry point validates its arguments before any launch (EGONN_STATUS_INVALID), takes a stream, never synchronises and is
+ * deterministic (no floating-point atomics; sums in one fixed order).  All pointers are DEVICE pointers.  scratch: one span of
+ * egonn_pose_graph_scratch_bytes(n, E, pcg_iterations) bytes, 256-byte aligned, owned by the caller; egonn_pose_graph_plan
+ * fills its plan part and the other three calls need that plan of the same (n, E) in the same span.
+ *
+ * egonn_pose_graph_plan: validates the edges and builds the node -> (edge, side) lists, each in edge order.  edge_index (E,2)
+ * int32, Z (E,4,4), weights (E,2) or NULL (all 1), fixed (n) uint8 or NULL (node 0 only).  edge_status (E): BAD_INDEX (outside
+ * [0, n)), SELF_LOOP, NONFINITE (a non-finite entry of Z or the weights, or a last row of Z other than 0 0 0 1),
+ * NEGATIVE_WEIGHT; an edge with a bit set is off.  graph_status (1): ISOLATED when a free node has no live edge.
+ * egonn_pose_graph_cost: cost (1), residuals (E,6) = [t_E ; Log R_E], rho (E), s (E), gradient (n,6) = sum J^T W r in (v, w)
+ * order for EVERY node (the gauge is the solver's), edge_status (E) = the plan's bits | ANGLE.  An edge that is off (by the plan
+ * or by ANGLE) gives residual 0, s 0, rho 1.  Poses are not validated up front: an edge whose residual is not finite (a
+ * non-finite pose) is switched off with the ANGLE bit as well.
+ * egonn_pose_graph_odometry: the chain of a trajectory, edge_index (n-1,2) = (i, i + 1), Z (n-1,4,4) = X_i^-1 X_{i+1}.
+ * egonn_pose_graph_hessvec: out (n,6) = (J^T W J + lambda I) p on the free nodes, the product the solver iterates with: rows of
+ * fixed nodes are 0 and their p is ignored.
+ * egonn_pose_graph_optimize: max_iterations Levenberg-Marquardt steps, each a linearisation, exactly pcg_iterations iterations of
+ * block-Jacobi preconditioned conjugate gradients (two launches each; after |r| <= pcg_tol |r0| in the M^-1 norm or p.Hp <= 0
+ * they return at once) on (J^T W J + lambda I) delta = -J^T W r, the retraction into a candidate and its cost.  Accepted when the
+ * cost decreases (lambda <- max(lambda / 10, lambda_min)), otherwise the poses stay and lambda <- 10 lambda.  Stops (every later
+ * launch returns at once) on a relative decrease < rel_tol, lambda > lambda_max or a gradient max-norm <= grad_tol.  poses_out
+ * (n,4,4); cost_trace (max_iterations + 1): the cost of the start and after every step, NaN after the stop; accept_trace
+ * (max_iterations): 1 / 0 / -1 (not run); counters (2) = steps run, steps accepted; lambda_out (1); edge_status (E) = the plan's
+ * bits | ANGLE of any linearisation; graph_status (1) = the plan's | PIVOT (a diagonal block fell back to the identity). */
+enum {
+  EGONN_PG_STATUS_BAD_INDEX = 1,
+  EGONN_PG_STATUS_SELF_LOOP = 2,
+  EGONN_PG_STATUS_NONFINITE = 4,
+  EGONN_PG_STATUS_NEGATIVE_WEIGHT = 8,
+  EGONN_PG_STATUS_ANGLE = 16,
+  EGONN_PG_STATUS_ISOLATED = 32,
+  EGONN_PG_STATUS_PIVOT = 64
+};
+int64_t egonn_pose_graph_scratch_bytes(int64_t n, int64_t n_edges, int pcg_iterations);     /* -1 on bad arguments */
+int egonn_pose_graph_odometry(const double* poses, int64_t n, double* Z, int32_t* edge_index, void* stream);
+int egonn_pose_graph_plan(const int32_t* edge_index, const double* Z, const double* weights, const uint8_t* fixed, int64_t n,
+                          int64_t n_edges, int32_t* edge_status, int32_t* graph_status, void* scratch, int64_t scratch_bytes,
+                          void* stream);
+int egonn_pose_graph_cost(const double* poses, int64_t n, int64_t n_edges, const double* Z, double robust_delta, double* cost,
+                          double* residuals, double* rho, double* s, double* gradient, int32_t* edge_status, void* scratch,
+                          int64_t scratch_bytes, void* stream);
+int egonn_pose_graph_hessvec(const double* poses, int64_t n, int64_t n_edges, const double* Z, double robust_delta, double lambda,
+                             const double* p, double* out, int32_t* edge_status, void* scratch, int64_t scratch_bytes,
+                             void* stream);
+int egonn_pose_graph_optimize(const double* poses, int64_t n, int64_t n_edges, const double* Z, double robust_delta,
+                              int max_iterations, int pcg_iterations, double pcg_tol, double lambda_init, double lambda_min,
+                              double lambda_max, double rel_tol, double grad_tol, double* poses_out, double* cost_trace,
+                              int32_t* accept_trace, int32_t* counters, double* lambda_out, int32_t* edge_status,
+                              int32_t* graph_status, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ launch timing (bench.py roofline leg)
  * mode 0: off; 1: time every tagged sparse-conv launch (event records around it); 2: only launches whose tag contains
  * `filter`, with the events attached to the kernel dispatch itself (the kernel's own begin..end, also when other streams
