@@ -37,6 +37,8 @@ void set_error(const char* fmt, ...);
 #define EGONN_ERR_CAPACITY 5   // a batch did not fit the capacities of egonn_ctx_reserve (the eager path still works)
 #define EGONN_ERR_FP16_RANGE 6 // an fp32 sparse convolution on the fp16-split pipe met a non-finite accumulator (activation beyond
                                // +-65504 or non-finite input): rerun with egonn_ctx_set_exact_fp32(ctx, 1)
+// the bit of Ctx::dev_fp16_flag that the kernels on the fp16-split pipe raise (split16.h: split_raise) and egonn_plan_status tests
+constexpr int SPLIT_RANGE_BIT = 8;
 
 #define HIP_CHECK(expr)                                                                   \
   do {                                                                                    \
@@ -321,8 +323,8 @@ struct Ctx {
   int32_t* dev_counts = nullptr;
   int32_t* dev_flags = nullptr;      // bit 0 = out-of-range coordinate seen, bit 1 = batch larger than the reserved capacities
                                      // (the plan's bits: cleared by the plan builders only)
-  int32_t* dev_fp16_flag = nullptr;  // bit 3 = fp16 range guard of the split kernels (sconv_split.hip, the tail split of sconv.hip,
-                                     // the local heads): its own word, cleared by the plan builders and at the start of every
+  int32_t* dev_fp16_flag = nullptr;  // SPLIT_RANGE_BIT = fp16 range guard of the split kernels (sconv_split.hip, the tail split of sconv.hip,
+                                     // topdown.hip, the local heads): its own word, cleared by the plan builders and at the start of every
                                      // egonn_forward; egonn_plan_status reports the OR of both words
   bool reserved = false;             // egonn_ctx_reserve: fixed capacities, plans neither allocate nor synchronise
   int64_t reserve_points = 0;

@@ -11,10 +11,9 @@
 #include "common.h"
 #include <hip/hip_ext.h>
 #include "kernels.h"
+#include "rowmath.h"
 
 namespace egonn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------ naive reference kernel (bring-up / cross-check)
 __global__ void sconv_naive_kernel(const float* __restrict__ in, const int32_t* __restrict__ nbr,
@@ -234,11 +233,6 @@ __global__ __launch_bounds__(256) void conv0_k5_kernel(const float* __restrict__
 // MFMA (k = 32 j + 8 g + e): its 8 table entries are one 16-byte LDS read.  Everything else (per-block neighbourhood table,
 // software pipeline over the tiles, zero-mask slot for the padding offsets) is the fp32 kernel's.
 typedef short bf16x8_c0 __attribute__((ext_vector_type(8)));
-__device__ static inline uint32_t bf16_rne(float a) {
-  uint32_t u = __float_as_uint(a);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return u >> 16;
-}
 template <bool OUT_BF16>
 __global__ __launch_bounds__(256) void conv0_k5_unit_kernel(const uint64_t* __restrict__ vkeys,     // level 0
                                                              const int32_t* __restrict__ g0,         // level-2 block of row
@@ -286,7 +280,7 @@ __global__ __launch_bounds__(256) void conv0_k5_unit_kernel(const uint64_t* __re
         float w = (k < 125) ? W[k * COUT0 + nt * 16 + l15] : 0.f;
 #pragma unroll
         for (int sp = 0; sp < 3; ++sp) {
-          const uint32_t b = bf16_rne(w);
+          const uint32_t b = f2bf_rn(w);
           h[sp][e] = b;
           w -= __uint_as_float(b << 16);                   // exact: the residual has at most 16 (then 8) significant bits
         }
@@ -383,7 +377,7 @@ __global__ __launch_bounds__(256) void conv0_k5_unit_kernel(const uint64_t* __re
         }
         if constexpr (OUT_BF16) {
           *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out_v) + (int64_t)orow * COUT0 + nt * 16 + 4 * g4) =
-              make_uint2(bf16_rne(o[0]) | (bf16_rne(o[1]) << 16), bf16_rne(o[2]) | (bf16_rne(o[3]) << 16));
+              make_uint2(f2bf_rn(o[0]) | (f2bf_rn(o[1]) << 16), f2bf_rn(o[2]) | (f2bf_rn(o[3]) << 16));
         } else {
           *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out_v) + (int64_t)orow * COUT0 + nt * 16 + 4 * g4) = o;
         }
@@ -409,7 +403,7 @@ __global__ void conv0_pack_unit_kernel(const float* __restrict__ W, uint4* __res
     float w = (k < 125) ? W[k * COUT0 + nt * 16 + l15] : 0.f;
 #pragma unroll
     for (int sp = 0; sp < 3; ++sp) {
-      const uint32_t b = bf16_rne(w);
+      const uint32_t b = f2bf_rn(w);
       h[sp][e] = b;
       w -= __uint_as_float(b << 16);
     }

@@ -798,7 +798,7 @@ int plan_sync(Ctx* ctx, hipStream_t stream) {
   }
   P.n_input = ctx->host_counts[NL + 1];
   P.exact = true;
-  if (flags & 8) {             // (the plan itself is fine: the sizes above are valid; the feature maps of the forward are not)
+  if (flags & SPLIT_RANGE_BIT) {           // (the plan itself is fine: the sizes above are valid; the feature maps of the forward are not)
     set_error("a kernel on the fp16-split matrix pipe (fp32 sparse convolution or local heads) met an operand outside the fp16 "
               "range (|x| >= 65520, which fp16 rounds to Inf) or a non-finite input; the outputs of this batch are invalid — "
               "egonn_ctx_set_exact_fp32(ctx, 1) selects the exact fp32 kernels");

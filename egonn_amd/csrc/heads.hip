@@ -8,6 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "rowmath.h"
+#include "split16.h"
 
 namespace egonn {
 
@@ -230,18 +231,14 @@ __global__ __launch_bounds__(LH_WAVES * 64) void local_heads_kernel(const LocalH
 // ------------------------------------------------------------------ the three heads on the fp16 matrix pipe (round 6)
 // local_heads_kernel above is bound by v_mfma_f32_16x16x4_f32: 432 MFMAs of 32 cycles per 16-row tile, two waves per SIMD —
 // 1 831 tiles x 13.8 k cycles / 1 024 SIMDs = 10 us of the 36 us launch at best.  The heads' six Linear layers here run with
-// the two-way fp16 split of sconv_split.hip instead (weights packed ONCE per model as hi | lo fragments in the contraction
+// the two-way fp16 split of split16.h instead (weights packed ONCE per model as hi | lo fragments in the contraction
 // order of the register chain, one power-of-two scale per matrix; activations split in registers; three products on
 // v_mfma_f32_16x16x32_f16, small terms first): 138 MFMAs of 16 cycles.  The lateral 1x1 convolution in front stays on the exact
 // pipe in the accumulation order of the dense kernel (the fused / unfused switch stays bitwise).  Deviation of the outputs from
 // the exact kernel: < 3e-6 of the largest value per output (tests/test_gpu_fusions.py).  Range guard (the plan's fp16 range flag):
-// the heads' input tile (lateral + transposed convolution, exact fp32) is tested for |x| >= 65520 and non-finite elements before it
+// the heads' input tile (lateral + transposed convolution, exact fp32) is tested for |x| >= SPLIT_FP16_LIMIT and non-finite elements before it
 // is split — the first layers' ReLU would otherwise turn the NaN accumulators of such an input into 0 — and the outputs of the
 // second layers for non-finite values (a hidden activation beyond the range).  egonn_ctx_set_exact_fp32 selects the kernel above.
-typedef _Float16 lh_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 lh_f16x2 __attribute__((ext_vector_type(2)));
-typedef float lh_f32x2 __attribute__((ext_vector_type(2)));
-__host__ __device__ static inline int lh_chan(int g, int e) { return e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4); }
 // fragments (1 KB hi + 1 KB lo each) per matrix: NT * CIN / 32
 constexpr int LHS_DW0 = 0, LHS_DW1 = LHS_DW0 + 6 * 2, LHS_KW0 = LHS_DW1 + 8 * 3, LHS_KW1 = LHS_KW0 + 2 * 2, LHS_SW0 = LHS_KW1 + 1 * 1,
               LHS_SW1 = LHS_SW0 + 2 * 2, LHS_FRAGS = LHS_SW1 + 1 * 1;                                   // 46 fragment pairs = 92 KB
@@ -252,28 +249,17 @@ __global__ void lhs_absmax_kernel(const float* const* __restrict__ W, uint32_t* 
   const int mi = blockIdx.x;
   const LhsMat M = lhs_mats[mi];
   const float* w = W[mi];
-  float m = 0.f;
-  for (int i = threadIdx.x; i < M.cin * M.nout; i += blockDim.x) {
-    const float v = fabsf(w[i]);
-    m = (v == v && v < INFINITY) ? fmaxf(m, v) : m;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  const float m = split_finite_absmax(w, M.cin * M.nout, (int)threadIdx.x, blockDim.x);
   if ((threadIdx.x & 63) == 0) atomicMax(trailer + 8 + mi, __float_as_uint(m));
 }
-__device__ static inline float lhs_scale_of(uint32_t maxbits) {        // power of two s with s * max in [2^13, 2^14)
-  const int e = (int)(maxbits >> 23) - 127;
-  const int se = min(max(13 - e, -100), 100);
-  return __uint_as_float((uint32_t)(se + 127) << 23);
-}
-// out[(first + nt * KB + kb) * 2 + part][lane][e] = part(s * W[16 nt + (lane & 15)][32 kb + lh_chan(lane >> 4, e)]) (fp16),
+// out[(first + nt * KB + kb) * 2 + part][lane][e] = part(s * W[16 nt + (lane & 15)][32 kb + split_chan(lane >> 4, e)]) (fp16),
 // rows beyond nout: zeros; behind the fragments: float 1/s per matrix [0..5], max bits [8..13]
 __global__ void lhs_pack_kernel(const float* const* __restrict__ W, uint16_t* __restrict__ out, uint32_t* __restrict__ trailer) {
   const int mi = blockIdx.y;
   const LhsMat M = lhs_mats[mi];
   const int KB = M.cin / 32;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const float sc = lhs_scale_of(trailer[8 + mi]);
+  const float sc = split_scale_of(trailer[8 + mi]);
   if (t == 0) reinterpret_cast<float*>(trailer)[mi] = 1.f / sc;
   if (t >= M.nt * KB * 2 * 64 * 8) return;
   int r = t;
@@ -281,11 +267,9 @@ __global__ void lhs_pack_kernel(const float* const* __restrict__ W, uint16_t* __
   const int lane = r & 63; r >>= 6;
   const int part = r & 1; r >>= 1;
   const int kb = r % KB, nt = r / KB;
-  const int unit = 16 * nt + (lane & 15), k = 32 * kb + lh_chan(lane >> 4, e);
+  const int unit = 16 * nt + (lane & 15), k = 32 * kb + split_chan(lane >> 4, e);
   const float v = unit < M.nout ? sc * W[mi][(int64_t)unit * M.cin + k] : 0.f;
-  const _Float16 hi = (_Float16)v;
-  const _Float16 lo = (_Float16)(v - (float)hi);
-  out[(int64_t)M.first * 2 * 512 + t] = __builtin_bit_cast(uint16_t, part == 0 ? hi : lo);
+  out[(int64_t)M.first * 2 * 512 + t] = __builtin_bit_cast(uint16_t, split_part(v, part));
 }
 size_t local_heads_pack_bytes() { return (size_t)LHS_FRAGS * 2048 + 64; }
 int local_heads_pack(const float* const* w6_dev /*device array of the six weight pointers*/, void* out, hipStream_t stream) {
@@ -297,35 +281,22 @@ int local_heads_pack(const float* const* w6_dev /*device array of the six weight
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
-__device__ static inline void lhs_split8(const f32x4& a0, const f32x4& a1, lh_f16x8& hi, lh_f16x8& lo) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float x0 = q < 2 ? a0[2 * q] : a1[2 * q - 4], x1 = q < 2 ? a0[2 * q + 1] : a1[2 * q - 3];
-    const lh_f16x2 h = __builtin_convertvector((lh_f32x2){x0, x1}, lh_f16x2);
-    const lh_f32x2 hf = __builtin_convertvector(h, lh_f32x2);
-    const lh_f16x2 l = __builtin_convertvector((lh_f32x2){x0 - hf[0], x1 - hf[1]}, lh_f16x2);
-    hi[2 * q] = h[0]; hi[2 * q + 1] = h[1];
-    lo[2 * q] = l[0]; lo[2 * q + 1] = l[1];
-  }
-}
 // out[nt] = winv * sum_kb (W_lo ah + W_hi al + W_hi ah): in = f32x4 per 16 input channels (the register chain's layout)
 template <int CIN, int NT>
 __device__ static inline void lhs_layer(const f32x4* __restrict__ frags /* pairs: hi, lo */, const f32x4* __restrict__ in, int lane,
                                         float winv, f32x4* __restrict__ out) {
   constexpr int KB = CIN / 32;
-  lh_f16x8 ah[KB], al[KB];
+  f16x8_t ah[KB], al[KB];
 #pragma unroll
-  for (int kb = 0; kb < KB; ++kb) lhs_split8(in[2 * kb], in[2 * kb + 1], ah[kb], al[kb]);
+  for (int kb = 0; kb < KB; ++kb) split8h(in[2 * kb], in[2 * kb + 1], ah[kb], al[kb]);
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb) {
-      const lh_f16x8 wh = __builtin_bit_cast(lh_f16x8, frags[((nt * KB + kb) * 2) * 64 + lane]);
-      const lh_f16x8 wl = __builtin_bit_cast(lh_f16x8, frags[((nt * KB + kb) * 2 + 1) * 64 + lane]);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, ah[kb], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, al[kb], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, ah[kb], acc, 0, 0, 0);
+      const f16x8_t wh = __builtin_bit_cast(f16x8_t, frags[((nt * KB + kb) * 2) * 64 + lane]);
+      const f16x8_t wl = __builtin_bit_cast(f16x8_t, frags[((nt * KB + kb) * 2 + 1) * 64 + lane]);
+      split_mfma3(wh, wl, ah[kb], al[kb], acc);
     }
     out[nt] = acc * winv;
     __builtin_amdgcn_sched_barrier(0);
@@ -334,7 +305,7 @@ __device__ static inline void lhs_layer(const f32x4* __restrict__ frags /* pairs
 struct LocalHeadsSplitArgs {
   LocalHeadsArgs a;
   const void* pack;          // local_heads_pack
-  int32_t* flags;            // the plan's flag word (bit 3: non-finite head output)
+  int32_t* flags;            // the plan's flag word (split_raise: input beyond the fp16 range, non-finite head output)
 };
 __global__ __launch_bounds__(LH_WAVES * 64) void local_heads_split_kernel(const LocalHeadsSplitArgs q) {
   const LocalHeadsArgs& p = q.a;
@@ -375,15 +346,15 @@ __global__ __launch_bounds__(LH_WAVES * 64) void local_heads_split_kernel(const 
 #pragma unroll
       for (int t = 0; t < 4; ++t) x[t] = l[t] + r[t];
     }
-    float guard = 0.f;                                       // (v - v) is NaN for a non-finite v: sticky under addition
-    // the heads' input (fp32, or bf16 widened): an element fp16 cannot hold (|x| >= 65520 rounds to Inf; 65504 <= |x| < 65520 to
-    // 65504 with an exact low part) or a non-finite one turns the first layers' accumulators into NaN, which the bias + ReLU
+    float guard = 0.f;                                       // sum of split_nonfinite probes
+    // the heads' input (fp32, or bf16 widened): an element fp16 cannot hold (|x| >= SPLIT_FP16_LIMIT rounds to Inf; below it to
+    // a finite hi with an exact low part) or a non-finite one turns the first layers' accumulators into NaN, which the bias + ReLU
     // below (fmaxf) would turn into 0 — so the input tile itself is checked, before any of it enters the split
     bool outside = false;
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) outside |= !(fabsf(x[t][r]) < 65520.f);
+      for (int r = 0; r < 4; ++r) outside |= !(fabsf(x[t][r]) < SPLIT_FP16_LIMIT);
     // ---- descriptor decoder + L2 normalisation
     {
       f32x4 h[6], o[8];
@@ -407,7 +378,7 @@ __global__ __launch_bounds__(LH_WAVES * 64) void local_heads_split_kernel(const 
       }
       ss += __shfl_xor(ss, 16, 64);
       ss += __shfl_xor(ss, 32, 64);
-      guard += ss - ss;
+      guard += split_nonfinite(ss);
       const float inv = 1.f / fmaxf(sqrtf(ss), 1e-12f);
       if (ok) {
 #pragma unroll
@@ -427,7 +398,7 @@ __global__ __launch_bounds__(LH_WAVES * 64) void local_heads_split_kernel(const 
       }
       lhs_layer<32, 1>(lh_frags + LHS_KW1 * 2 * 64, h, lane, wi3, o);
       if (ok && g4 == 0) {
-        guard += (o[0][0] - o[0][0]) + (o[0][1] - o[0][1]) + (o[0][2] - o[0][2]);
+        guard += split_nonfinite(o[0][0]) + split_nonfinite(o[0][1]) + split_nonfinite(o[0][2]);
         const float ox = p.ignore_offsets ? 0.f : tanhf(o[0][0] + p.kb1[0]);
         const float oy = p.ignore_offsets ? 0.f : tanhf(o[0][1] + p.kb1[1]);
         const float oz = p.ignore_offsets ? 0.f : tanhf(o[0][2] + p.kb1[2]);
@@ -446,11 +417,11 @@ __global__ __launch_bounds__(LH_WAVES * 64) void local_heads_split_kernel(const 
       }
       lhs_layer<32, 1>(lh_frags + LHS_SW1 * 2 * 64, h, lane, wi5, o);
       if (ok && g4 == 0) {
-        guard += o[0][0] - o[0][0];
+        guard += split_nonfinite(o[0][0]);
         p.out_sigma[row] = apply_act(o[0][0] + p.sb1[0], ACT_SOFTPLUS);
       }
     }
-    if (ok && (outside || guard != 0.f) && q.flags) atomicOr(q.flags, 8);
+    if (ok && (outside || guard != 0.f) && q.flags) split_raise(q.flags);
   }
 }
 

@@ -173,7 +173,7 @@ int global_tail(const MlpRef& r, const void* const* pk, const float* g5, int64_t
 // topdown.hip: one top-down step of an FPN on the fp16-split pipe,
 //   out[o] = x_coarse[parent(o)] @ W_t[key(o) & 7] (+ x_lateral[o] @ W_l)
 // sp_tconv / sp_lateral: pack_split_weights of the (8, C, C) and (1, Cl, C) kernels.  Rows come from the transposed map's row-group
-// tables onto `level_out` (ensure_rowgroups kind 2); the epilogue raises bit 3 of `flags` on a non-finite accumulator.
+// tables onto `level_out` (ensure_rowgroups kind 2); the epilogue raises SPLIT_RANGE_BIT of the plan's fp16 flag word on a non-finite accumulator.
 bool topdown_split_supported(int C, int Cl);
 int topdown_split_forward(Ctx* ctx, int level_out, const float* x_coarse, const void* sp_tconv, const float* x_lateral,
                           const void* sp_lateral, int C, int Cl, float* out, hipStream_t stream);

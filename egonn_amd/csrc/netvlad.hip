@@ -21,10 +21,9 @@
 //   4. tail, grid B: sum of the C partials (four interleaved parts, combined in order), bn2, (gating GEMM, bn, sigmoid, product)
 #include "common.h"
 #include "kernels.h"
+#include "split16.h"
 
 namespace egonn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static constexpr int NV_BB = 16;            // scans per workgroup of launch 3
 

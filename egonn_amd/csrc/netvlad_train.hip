@@ -26,10 +26,9 @@
 // No atomics; every summation order is a function of the scan's own row count (nv_chunks) and, for the sums over scans, of the
 // batch order.  A scan's rows of dX depend on the other scans only through the (64,) bn1 vectors and Nmax.
 #include "model.h"
+#include "split16.h"
 
 namespace egonn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------ forward helpers
 // the pad rows' share of the shifted sums: d = 0 - m for each of `pads` rows

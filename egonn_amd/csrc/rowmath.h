@@ -1,12 +1,12 @@
-// Device helpers shared by the row-wise translation units (dense.hip, rowwise.hip, heads.hip): the activation of an epilogue,
-// the bf16 <-> fp32 conversions of bf16 feature maps and the scan of a row.  Defined once, here.
+// Device helpers shared by the translation units that work on rows of feature maps: the activation of an epilogue, the
+// bf16 <-> fp32 conversions of bf16 feature maps, the scan of a row and the sum over the 16 rows of an accumulator tile.
+// Defined once, here (f32x4 and the other vector types: split16.h).
 #pragma once
 #include "common.h"
 #include "kernels.h"
+#include "split16.h"
 
 namespace egonn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ static inline float apply_act(float v, int act) {
   switch (act) {
@@ -34,6 +34,18 @@ __device__ static inline int sample_of_row(const int32_t* __restrict__ boff, int
     if (boff[mid] <= r) lo = mid; else hi = mid;
   }
   return lo;
+}
+
+__device__ static inline float row16_sum(float v) {      // sum over the 16 lanes of a DPP row (= the 16 rows of a tile)
+  int x = __builtin_bit_cast(int, v);
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+  x = __builtin_bit_cast(int, v);
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+  x = __builtin_bit_cast(int, v);
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true));   // row_half_mirror
+  x = __builtin_bit_cast(int, v);
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true));   // row_mirror
+  return v;
 }
 
 }  // namespace egonn

@@ -40,17 +40,12 @@
 #include "common.h"
 #include <hip/hip_ext.h>
 #include "kernels.h"
+#include "rowmath.h"
+#include "split16.h"
 
 namespace egonn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-
-__device__ static inline uint32_t f2bf(float a) {       // round to nearest even
-  uint32_t u = __float_as_uint(a);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return u >> 16;
-}
 
 // ------------------------------------------------------------------ weight packing
 // W[k][ci][co] (reference layout: MinkowskiConvolution.kernel) -> item-major fragment order
@@ -90,7 +85,7 @@ __global__ void pack_rg_weights_kernel(const float* __restrict__ W, int K, int c
   const int ks = flip ? K - 1 - k : k;
   // source kernel is [K][cin_src][cout_src]; with transpose the packed (ci, co) reads W[ks][co][ci] of a [cout][cin] kernel
   const float v = transpose ? W[(int64_t)ks * per_k + (int64_t)co * cin + ci] : W[(int64_t)ks * per_k + (int64_t)ci * cout + co];
-  if (bf16) reinterpret_cast<uint16_t*>(out)[e] = (uint16_t)f2bf(v);
+  if (bf16) reinterpret_cast<uint16_t*>(out)[e] = (uint16_t)f2bf_rn(v);
   else reinterpret_cast<float*>(out)[e] = v;
 }
 
@@ -122,25 +117,9 @@ struct SconvArgs {
   const int32_t* order4 = nullptr;       // dispatch order of tasks of 4 consecutive groups (rowgroup.hip: longest first inside
                                          // every XCD's eighth); used by the kernels whose task is exactly such a quadruple
   unsigned long long* trace = nullptr;   // measurement builds only (tools/sconv_trace.py): 8 u64 per wave task
-  int32_t* flags = nullptr;              // SPLIT instantiation: the plan's flag word (bit 3: fp16 range guard, sconv_split.hip)
+  int32_t* flags = nullptr;              // SPLIT instantiation: the plan's flag word (fp16 range guard: split16.h)
   const float* res = nullptr;            // fp32 maps: out += res[row] in the epilogue (MinkHead's FPN step, models/minkgl.py:46-60)
 };
-
-// fp32 x 8 -> (hi, lo) fp16 x 8 (the two-way split of sconv_split.hip, same rounding)
-typedef _Float16 rg_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 rg_f16x2 __attribute__((ext_vector_type(2)));
-typedef float rg_f32x2 __attribute__((ext_vector_type(2)));
-__device__ static inline void rg_split8h(const f32x4& a0, const f32x4& a1, rg_f16x8& hi, rg_f16x8& lo) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float x0 = q < 2 ? a0[2 * q] : a1[2 * q - 4], x1 = q < 2 ? a0[2 * q + 1] : a1[2 * q - 3];
-    const rg_f16x2 h = __builtin_convertvector((rg_f32x2){x0, x1}, rg_f16x2);
-    const rg_f32x2 hf = __builtin_convertvector(h, rg_f32x2);
-    const rg_f16x2 l = __builtin_convertvector((rg_f32x2){x0 - hf[0], x1 - hf[1]}, rg_f16x2);
-    hi[2 * q] = h[0]; hi[2 * q + 1] = h[1];
-    lo[2 * q] = l[0]; lo[2 * q + 1] = l[1];
-  }
-}
 
 // KSP > 1 (layers with >= 64 input channels): the KSP waves of a workgroup that share one (group, 32-column) tile each
 // take 1/KSP of the input-channel blocks and the partial accumulators are summed through LDS in fixed order — shorter
@@ -152,7 +131,7 @@ __device__ static inline void rg_split8h(const f32x4& a0, const f32x4& a1, rg_f1
 // (6 loads x 16 cycles x 4 waves per 512 MFMA cycles); G = 2 makes it 8 loads per 1024 MFMA cycles.  A group that lacks
 // the offset skips the item's MFMAs (wave-uniform branch; its gather rows are "-1" and cost no memory traffic).  The sum
 // order of every output row is unchanged (ascending k, ascending channel) => results are bitwise identical for every G.
-// SPLIT (fp32 maps of levels 6-7, round 6): the item's arithmetic is the two-way fp16 split of sconv_split.hip — p.Wp is the
+// SPLIT (fp32 maps of levels 6-7, round 6): the item's arithmetic is the two-way fp16 split of split16.h — p.Wp is the
 // pack_split_weights form, whose 4 KB item (hi nt0 | hi nt1 | lo nt0 | lo nt1 fragments) sits where the fp32 item sat, the gathered
 // fragment is split in registers and six MFMAs of 16 cycles replace sixteen of 32: a wave's chain of 27 items was 5.8 of the launch's
 // 14.5 us in exact-fp32 MFMAs.  Same partition and order of the sum as the exact instantiation; epilogue * 1 / (pack scale); range guard.
@@ -199,9 +178,8 @@ __global__ __launch_bounds__(NW * 64) void sconv_rg_kernel(const SconvArgs p) {
       const int c0 = ns * 32 + nt * 16 + 4 * g4;
       f32x4 v = acc[nt];
       if constexpr (SPLIT) {
-        const f32x4 z = v - v;                               // NaN for a non-finite accumulator (range guard)
-        if (__builtin_expect((z[0] + z[1]) + (z[2] + z[3]) != 0.f, 0) && p.flags) atomicOr(p.flags, 8);
-        v = v * *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.Wp) + p.w_bytes);      // 1 / (pack scale)
+        if (__builtin_expect(split_nonfinite(v) != 0.f, 0) && p.flags) split_raise(p.flags);   // range guard
+        v = v * split_pack_winv(p.Wp, p.w_bytes);                                              // 1 / (pack scale)
       }
       if (p.scale) v = v * sc[nt] + sh[nt];
       if (p.relu) {
@@ -214,8 +192,8 @@ __global__ __launch_bounds__(NW * 64) void sconv_rg_kernel(const SconvArgs p) {
       if (row >= 0) {
         if constexpr (BF16) {
           uint2 o;
-          o.x = f2bf(v[0]) | (f2bf(v[1]) << 16);
-          o.y = f2bf(v[2]) | (f2bf(v[3]) << 16);
+          o.x = f2bf_rn(v[0]) | (f2bf_rn(v[1]) << 16);
+          o.y = f2bf_rn(v[2]) | (f2bf_rn(v[3]) << 16);
           *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.out) + (int64_t)row * COUT + c0) = o;
         } else {
           *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (int64_t)row * COUT + c0) = v;
@@ -356,16 +334,11 @@ __global__ __launch_bounds__(NW * 64) void sconv_rg_kernel(const SconvArgs p) {
         for (int j = 0; j < G; ++j) {
           if (G > 1 && !((gm[j] >> bitring[rs]) & 1u)) continue;        // wave-uniform
           if constexpr (SPLIT) {
-            rg_f16x8 ah, al;
-            rg_split8h(aring[rs][j][0], aring[rs][j][1], ah, al);
-            const rg_f16x8 w0 = __builtin_bit_cast(rg_f16x8, wring[rs][0]), w1 = __builtin_bit_cast(rg_f16x8, wring[rs][1]);
-            const rg_f16x8 w2 = __builtin_bit_cast(rg_f16x8, wring[rs][2]), w3 = __builtin_bit_cast(rg_f16x8, wring[rs][3]);
-            acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w2, ah, acc[j][0], 0, 0, 0);      // small terms first
-            acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w3, ah, acc[j][1], 0, 0, 0);
-            acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, al, acc[j][0], 0, 0, 0);
-            acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1, al, acc[j][1], 0, 0, 0);
-            acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, ah, acc[j][0], 0, 0, 0);
-            acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1, ah, acc[j][1], 0, 0, 0);
+            f16x8_t ah, al;
+            split8h(aring[rs][j][0], aring[rs][j][1], ah, al);
+            const f16x8_t w0 = __builtin_bit_cast(f16x8_t, wring[rs][0]), w1 = __builtin_bit_cast(f16x8_t, wring[rs][1]);
+            const f16x8_t w2 = __builtin_bit_cast(f16x8_t, wring[rs][2]), w3 = __builtin_bit_cast(f16x8_t, wring[rs][3]);
+            split_mfma3(w0, w1, w2, w3, ah, al, acc[j][0], acc[j][1]);      // hi nt0 | hi nt1 | lo nt0 | lo nt1
           } else if constexpr (BF16) {
             const bf16x8_t av = __builtin_bit_cast(bf16x8_t, aring[rs][j][0]);
 #pragma unroll
@@ -458,18 +431,6 @@ __global__ __launch_bounds__(NW * 64) void sconv_rg_kernel(const SconvArgs p) {
 // front of any LDS read it can see; every LDS read inside the item loop is therefore issued from one asm statement per
 // item that carries its own counted s_waitcnt vmcnt and its own lgkmcnt(0).
 // Arithmetic (MFMA order, channel permutation, W packing, epilogue) is identical to sconv_rg_kernel => bitwise equal.
-__device__ static inline float row16_sum(float v) {      // sum over the 16 lanes of a DPP row (= the 16 rows of a tile)
-  int x = __builtin_bit_cast(int, v);
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  x = __builtin_bit_cast(int, v);
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  x = __builtin_bit_cast(int, v);
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true));   // row_half_mirror
-  x = __builtin_bit_cast(int, v);
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
-
 template <int CIN, int COUT, int D, int KSP, int NW, bool TRACE = false, bool PIPE = false>
 __global__ __launch_bounds__(NW * 64) void sconv_dma_kernel(const SconvArgs p) {
   constexpr int NS = COUT / 32, NCB = CIN / 32;
@@ -1014,8 +975,8 @@ __global__ __launch_bounds__(NW * 64) void sconv_wg_kernel(const SconvArgs p) {
         if (row >= 0) {
           if constexpr (BF16) {
             uint2 o;
-            o.x = f2bf(v[0]) | (f2bf(v[1]) << 16);
-            o.y = f2bf(v[2]) | (f2bf(v[3]) << 16);
+            o.x = f2bf_rn(v[0]) | (f2bf_rn(v[1]) << 16);
+            o.y = f2bf_rn(v[2]) | (f2bf_rn(v[3]) << 16);
             *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.out) + (int64_t)row * COUT + c0) = o;
           } else {
             *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + (int64_t)row * COUT + c0) = v;
@@ -1097,7 +1058,7 @@ int sconv_rg_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t stream
   a.in = c.in; a.snbr = rg.snbr; a.gmask = rg.gmask; a.perm = rg.perm; a.meta = rg.meta; a.Wp = l.Wp;
   a.scale = c.scale; a.shift = c.shift; a.out = c.out; a.psum = c.psum;
   a.in_bytes = (uint32_t)ib;
-  a.w_bytes = (uint32_t)((uint64_t)rg.K * cin * cout * (bf16 ? 2 : 4));
+  a.w_bytes = (uint32_t)((uint64_t)rg.K * cin * cout * (bf16 ? 2 : 4));    // (a split pack: its fragments, = split_frag_bytes)
   a.K = rg.K; a.relu = c.relu ? 1 : 0; a.cap_groups = rg.cap_groups;
   a.order4 = switches().no_task_order ? nullptr : rg.order4;
   a.trace = l.ch.TRACE ? g_sconv_trace : nullptr;

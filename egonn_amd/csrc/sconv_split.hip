@@ -6,22 +6,8 @@
 //
 //   out[o] = act( (sum_k in[nbr[o][k]] @ W[k]) * scale + shift )
 //
-// Why.  v_mfma_f32_16x16x4_f32 runs at the fp32 VECTOR rate (157 TFLOP/s, 1/16 of the 16-bit matrix rate) and was the binding
-// roof of every fp32 layer with >= 64 channels.  Round 3 ran these layers on v_mfma_f32_16x16x32_bf16 with
-// both operands split EXACTLY into three bf16 parts and six products; the kernels then turned out to be bound by their own
-// instruction stream (44 of 68 vector instructions per group and step were the split, profiles/r03c_pmc_wide.txt).  Round 5: fp16 parts.
-// An fp16 number carries 11 significand bits, so  x = hi + lo + r  with hi = rn16(x), lo = rn16(x - hi), |r| <= 2^-22 |x|
-// (fp32 itself rounds at 2^-24), an fp16 x fp16 product is exact in fp32, and
-//     a * w = ah*wh + ah*wl + al*wh  (+ al*wl + cross terms with r: <= 3 * 2^-22 |a w|, dropped)
-// is THREE products on v_mfma_f32_16x16x32_f16 (same rate as bf16) instead of six, a 24-instruction split instead of 44, and
-// 4 bytes per weight instead of 6.  Range: fp16 holds |x| < 65504.  Weights are scaled by a power of two per kernel at pack
-// time (max |W| -> [2^13, 2^14); exact, undone exactly in the epilogue) so that their low parts stay normal numbers;
-// activations are used as they are: an fp32 activation beyond +-65504 becomes Inf in the split — every accumulator that gathers it
-// then is Inf / NaN and the epilogue raises the plan's range flag (SplitArgs::flags; egonn_plan_status: EGONN_STATUS_FP16_RANGE;
-// egonn_ctx_set_exact_fp32 selects the exact kernels of sconv.hip) — and the low part of an activation below 2^-3 is a subnormal
-// with an ABSOLUTE error <= 2^-25: nothing next to the rounding of the sums these layers produce (operands far below 1 — input
-// gradients — are scaled per launch: SplitArgs::in_maxbits).  Measured against the plain fp32 kernel
-// (tests/test_gpu_graph.py::test_split_conv_matches_exact_fp32, tests/test_gpu_range.py): DESIGN.md §3.1.
+// Arithmetic: the project's fp16 split (split16.h: error bound, range, why weights are scaled and activations are not, the order
+// of the three products, the range guard).  This file is the kernels around it.
 //
 // Decomposition (unchanged from round 3):
 //   * a WORKGROUP of NW waves owns NW consecutive row groups (rowgroup.hip: 16 output rows each, sorted by neighbour mask
@@ -49,39 +35,21 @@
 #include "common.h"
 #include <hip/hip_ext.h>
 #include "kernels.h"
+#include "rowmath.h"
+#include "split16.h"
 
 namespace egonn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-
-// channel of the 32-channel block that lane group g (= lane >> 4) holds in element e of its 8-element MFMA operand: the two
-// 16-byte chunks g and 4+g of the gathered 128-byte row (the conflict-free ds_read_b128 pattern of the swizzled image)
-__host__ __device__ static inline int sp_chan(int g, int e) { return e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4); }
-
 // ------------------------------------------------------------------ weight packing
 // W[k][ci][co] -> Wsp[k][cb][ns][f][lane][e] (fp16), f = 2*part + nt, part: 0 hi, 1 lo
-//   = part( s * W[k][32cb + sp_chan(lane>>4, e)][32ns + 16nt + (lane&15)] ),   s = 2^(13 - exponent(max |W|))
+//   = part( s * W[k][32cb + split_chan(lane>>4, e)][32ns + 16nt + (lane&15)] ),   s = 2^(13 - exponent(max |W|))
 // so that the slab of a step (k, cb) is one contiguous block of COUT/32 * 4 KB and every 1 KB piece is one lane-linear
-// MFMA A-operand fragment.  Behind the fragments (byte offset K*cin*cout*4): float 1/s, uint32 bits of max |W|.
+// MFMA A-operand fragment.  Behind the fragments (split16.h: split_frag_bytes, split_pack_winv): float 1/s, uint32 bits of max |W|.
 // flip / transpose: as pack_rg_weights (input-gradient kernels, k=2 <-> transposed pairs).
 __global__ void split_absmax_kernel(const float* __restrict__ W, int64_t n, uint32_t* __restrict__ trailer) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  float m = 0.f;
-  for (int64_t i = t; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float v = fabsf(W[i]);
-    m = (v == v && v < INFINITY) ? fmaxf(m, v) : m;       // NaN / Inf weights do not pick the scale
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  const float m = split_finite_absmax(W, n, t, (int64_t)gridDim.x * blockDim.x);
   if ((threadIdx.x & 63) == 0) atomicMax(trailer + 1, __float_as_uint(m));
-}
-__device__ static inline float split_scale_of(uint32_t maxbits) {     // power of two s with s * max in [2^13, 2^14)
-  const int e = (int)(maxbits >> 23) - 127;                            // max = 1.m * 2^e (0 / subnormal: e = -127 -> clamped)
-  const int se = min(max(13 - e, -100), 100);
-  return __uint_as_float((uint32_t)(se + 127) << 23);
 }
 __global__ void pack_split_weights_kernel(const float* __restrict__ W, int K, int cin, int cout, int flip, int transpose,
                                           uint16_t* __restrict__ out, uint32_t* __restrict__ trailer) {
@@ -99,16 +67,14 @@ __global__ void pack_split_weights_kernel(const float* __restrict__ W, int K, in
   const int cb = (int)(r % ncb); r /= ncb;
   const int k = (int)r;
   const int part = f >> 1, nt = f & 1;
-  const int ci = 32 * cb + sp_chan(lane >> 4, e);
+  const int ci = 32 * cb + split_chan(lane >> 4, e);
   const int co = 32 * ns + 16 * nt + (lane & 15);
   const int ks = flip ? K - 1 - k : k;
   const float v = sc * (transpose ? W[(int64_t)ks * per_k + (int64_t)co * cin + ci] : W[(int64_t)ks * per_k + (int64_t)ci * cout + co]);
-  const _Float16 hi = (_Float16)v;
-  const _Float16 lo = (_Float16)(v - (float)hi);
-  out[t] = __builtin_bit_cast(uint16_t, part == 0 ? hi : lo);
+  out[t] = __builtin_bit_cast(uint16_t, split_part(v, part));
 }
 
-size_t split_weights_bytes(int K, int cin, int cout) { return (size_t)K * cin * cout * 4 + 16; }
+size_t split_weights_bytes(int K, int cin, int cout) { return split_frag_bytes(K, cin, cout) + SPLIT_TRAILER_BYTES; }
 size_t sconv_split_part_floats(const RowGroups& rg, int cout, int kparts) {
   return kparts > 1 ? (size_t)kparts * rg.cap_groups * 16 * cout : 0;
 }
@@ -116,8 +82,8 @@ size_t sconv_split_part_floats(const RowGroups& rg, int cout, int kparts) {
 int pack_split_weights(const float* W, int K, int cin, int cout, int flip, int transpose, void* out, hipStream_t stream) {
   EGONN_REQUIRE(cin % 32 == 0 && cout % 32 == 0, EGONN_ERR_INVALID, "sconv: channel counts must be multiples of 32 (%d->%d)", cin, cout);
   const int64_t nw = (int64_t)K * cin * cout, n = nw * 2;
-  uint32_t* trailer = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(out) + nw * 4);
-  HIP_CHECK(hipMemsetAsync(trailer, 0, 16, stream));
+  uint32_t* trailer = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(out) + split_frag_bytes(K, cin, cout));
+  HIP_CHECK(hipMemsetAsync(trailer, 0, SPLIT_TRAILER_BYTES, stream));
   hipLaunchKernelGGL(split_absmax_kernel, dim3((unsigned)std::min<int64_t>(cdiv(nw, 256), 256)), dim3(256), 0, stream, W, nw, trailer);
   hipLaunchKernelGGL(pack_split_weights_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream, W, K, cin, cout, flip,
                      transpose, reinterpret_cast<uint16_t*>(out), trailer);
@@ -141,7 +107,7 @@ struct SplitArgs {
   uint32_t in_rows, w_bytes;
   int K, relu, cap_groups;
   int in_split, out_split;   // the input / output map is in SPLIT FORM: per row and 32-channel block the 128 bytes hold the fp16 hi
-                             // parts (chunk g = channels sp_chan(g, 0..7)) and lo parts (chunk 4 + g) the consumer's MFMA operands
+                             // parts (chunk g = channels split_chan(g, 0..7)) and lo parts (chunk 4 + g) the consumer's MFMA operands
                              // are made of, instead of 32 fp32 values.  Same size, same gather; the consumer's in-loop split
                              // (24 vector instructions per 16 x 32 fragment) moves into the producer's epilogue.  hi / lo are
                              // computed by the same split8h either way: results are bitwise those of fp32 maps.
@@ -158,10 +124,7 @@ struct SplitArgs {
   // boundary, nothing is synchronised in here.
   float* part = nullptr;
   int kp_n = 1;
-  // RANGE GUARD.  fp16 parts hold |x| < 65520: a finite fp32 activation beyond that becomes Inf in split8h, every accumulator
-  // that gathers it becomes Inf or NaN (Inf * 0, Inf - Inf), and the epilogue — which sees every accumulator before BN / ReLU can
-  // hide it — raises bit 3 of the plan's flag word (egonn_plan_status: EGONN_STATUS_FP16_RANGE; egonn_ctx_set_exact_fp32 selects
-  // the exact kernels).  Non-finite INPUTS raise it too: the flag says "this launch's fp32 semantics are not guaranteed".
+  // RANGE GUARD (split16.h): the plan's flag word; the epilogue sees every accumulator and raises SPLIT_RANGE_BIT on a non-finite one
   int32_t* flags = nullptr;
   // OPERAND SCALE (the input-gradient convolutions of a training step: gradients of 1e-6 .. 1e-8 would lose their low parts): the bits
   // of max |in| (split_absmax_kernel); the gathered rows are multiplied by the power of two that puts the maximum into
@@ -176,31 +139,6 @@ __host__ __device__ static inline uint32_t ks_range_mask(int kp, int kp_n, int K
   return ((1u << k1) - 1u) & ~((1u << k0) - 1u);
 }
 
-__device__ static inline float sp_row16_sum(float v) {   // sum over the 16 lanes of a DPP row (= the 16 rows of a tile)
-  int x = __builtin_bit_cast(int, v);
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  x = __builtin_bit_cast(int, v);
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  x = __builtin_bit_cast(int, v);
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true));   // row_half_mirror
-  x = __builtin_bit_cast(int, v);
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true));   // row_mirror
-  return v;
-}
-
-// fp32 x 8 -> (hi, lo) fp16 x 8, round to nearest even at both levels (v_cvt_pk_f16_f32): 24 VALU
-__device__ static inline void split8h(const f32x4& a0, const f32x4& a1, f16x8_t& hi, f16x8_t& lo) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const float x0 = p < 2 ? a0[2 * p] : a1[2 * p - 4], x1 = p < 2 ? a0[2 * p + 1] : a1[2 * p - 3];
-    const f16x2_t h = __builtin_convertvector((f32x2){x0, x1}, f16x2_t);
-    const f32x2 hf = __builtin_convertvector(h, f32x2);
-    const f16x2_t l = __builtin_convertvector((f32x2){x0 - hf[0], x1 - hf[1]}, f16x2_t);
-    hi[2 * p] = h[0]; hi[2 * p + 1] = h[1];
-    lo[2 * p] = l[0]; lo[2 * p + 1] = l[1];
-  }
-}
-
 // The epilogue of one 16-row x 32-column accumulator pair (tiles nt = 0, 1 of column slice ns): undo the weight pack scale, BN
 // scale/shift (+ReLU), one 16-byte store per tile (fp32 map) or the split-form chunks, optional per-group column sums.  Shared by
 // the convolution kernel and by the reducer of the offset-split launches (same expression, same order: the reducer's output for
@@ -208,16 +146,11 @@ __device__ static inline void split8h(const f32x4& a0, const f32x4& a1, f16x8_t&
 template <int COUT>
 __device__ static inline void split_epilogue(const SplitArgs& p, const f32x4& a0, const f32x4& a1, int ns, int32_t row, int gw,
                                              int l15, int g4) {
-  float winv = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.Wsp) + p.w_bytes);   // 1 / (pack scale): a power of two
+  float winv = split_pack_winv(p.Wsp, p.w_bytes);                                                       // 1 / (pack scale): a power of two
   if (p.in_maxbits) winv *= 1.f / split_scale_of(p.in_maxbits[0]);                                     // (uniform) 1 / (operand scale)
   float sums[2][4];
   f32x4 vv[2];
-  {
-    // range guard: (x - x) is 0 for finite x and NaN for Inf / NaN, and NaN is sticky under addition — one test for the eight values
-    const f32x4 z = (a0 - a0) + (a1 - a1);
-    const float zz = (z[0] + z[1]) + (z[2] + z[3]);
-    if (__builtin_expect(zz != 0.f, 0) && p.flags) atomicOr(p.flags, 8);
-  }
+  if (__builtin_expect(split_nonfinite(a0, a1) != 0.f, 0) && p.flags) split_raise(p.flags);   // range guard: one test for the eight values
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
     const int c0 = ns * 32 + nt * 16 + 4 * g4;
@@ -238,7 +171,7 @@ __device__ static inline void split_epilogue(const SplitArgs& p, const f32x4& a0
     for (int u = 0; u < 4; ++u) sums[nt][u] = row >= 0 ? v[u] : 0.f;
   }
   if (p.out_split && row >= 0) {
-    // this lane holds exactly the eight channels sp_chan(g4, 0..7) of its row: columns 4 g4.. of tile 0 and of tile 1
+    // this lane holds exactly the eight channels split_chan(g4, 0..7) of its row: columns 4 g4.. of tile 0 and of tile 1
     f16x8_t oh, ol;
     split8h(vv[0], vv[1], oh, ol);
     char* o = reinterpret_cast<char*>(p.out) + ((int64_t)row * COUT + ns * 32) * 4 + 16 * g4;
@@ -249,7 +182,7 @@ __device__ static inline void split_epilogue(const SplitArgs& p, const f32x4& a0
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-      for (int u = 0; u < 4; ++u) sums[nt][u] = sp_row16_sum(sums[nt][u]);
+      for (int u = 0; u < 4; ++u) sums[nt][u] = row16_sum(sums[nt][u]);
     if (l15 == 0) {
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
@@ -524,9 +457,7 @@ __global__ __launch_bounds__(NW * KW * 64) void sconv_split_kernel(const SplitAr
     auto wwait = [&](f32x4 (&w)[4]) {
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3])::"memory");
     };
-    auto mfma = [](const f32x4& wf, const f16x8_t& af, f32x4& c) {
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, wf), af, c, 0, 0, 0);
-    };
+    auto h8 = [](const f32x4& wf) { return __builtin_bit_cast(f16x8_t, wf); };
     // ---- one step of this wave's group: rows of ring slot x slab of the same slot
     auto compute = [&](int slot) {
       f32x4 ra0, ra1, rb0, rb1, w[4];
@@ -561,10 +492,7 @@ __global__ __launch_bounds__(NW * KW * 64) void sconv_split_kernel(const SplitAr
            f32x4 wn[4];
            if constexpr (NSI + 1 < NS) wread(wa, std::integral_constant<int, NSI + 1>{}, wn);
            __builtin_amdgcn_sched_barrier(0);
-           // small terms first; w[2*part + nt]
-           mfma(w[2], ah, acc[NSI][0]); mfma(w[3], ah, acc[NSI][1]);        // w lo * a hi
-           mfma(w[0], al, acc[NSI][0]); mfma(w[1], al, acc[NSI][1]);        // w hi * a lo
-           mfma(w[0], ah, acc[NSI][0]); mfma(w[1], ah, acc[NSI][1]);        // hi * hi
+           split_mfma3(h8(w[0]), h8(w[1]), h8(w[2]), h8(w[3]), ah, al, acc[NSI][0], acc[NSI][1]);   // w[2*part + nt]
            __builtin_amdgcn_sched_barrier(0);
            if constexpr (NSI + 1 < NS) {
              wwait(wn);
@@ -672,7 +600,7 @@ __global__ __launch_bounds__(NW * KW * 64) void sconv_split_kernel(const SplitAr
 //   * every wave owns one row group at a time and walks the set bits of that group's OWN mask in ascending k — no union padding,
 //     no s_barrier and no vmcnt(0) in the offset loop; the waits on the wave's two-slot ring are counted (the DMA of offset j + 2
 //     is requested as soon as offset j's operands are in registers, so two gathers per wave are in flight);
-//   * per offset the six MFMAs run in the lock-step kernel's order (lo*hi, hi*lo, hi*hi; column tile 0 then 1) on the same
+//   * per offset the six MFMAs run in the order of split16.h's two-tile split_mfma3 (lo*hi, hi*lo, hi*hi; column tile 0 then 1) on the same
 //     accumulators: per output row the same operations in the same order — results are bitwise those of cfg 142;
 //   * the next group's header (mask, table, output rows, gate) is requested while the current group computes and held in registers;
 //   * groups are dealt statically: the XCD slice of the lock-step kernel (block b -> contiguous eighth b % 8 of the task slots, a
@@ -846,6 +774,7 @@ __global__ __launch_bounds__(NW * 64) void sconv_split_resident_kernel(const Spl
         split8h(ra0, ra1, ah, al);
       }
       __builtin_amdgcn_sched_barrier(0);
+      // written out: the order of the two-tile split_mfma3 (split16.h); w[2*part + nt]
       mfma(w[2], ah, acc0); mfma(w[3], ah, acc1);        // w lo * a hi
       mfma(w[0], al, acc0); mfma(w[1], al, acc1);        // w hi * a lo
       mfma(w[0], ah, acc0); mfma(w[1], ah, acc1);        // hi * hi
@@ -974,7 +903,7 @@ int sconv_split_forward(const ConvCall& c, const SconvLaunch& l, hipStream_t str
   a.order = switches().no_task_order ? nullptr : rg.order4;
   a.scale = c.scale; a.shift = c.shift; a.out = reinterpret_cast<float*>(c.out); a.psum = c.psum;
   a.in_rows = (uint32_t)l.n_in_cap;
-  a.w_bytes = (uint32_t)((uint64_t)rg.K * cin * cout * 4);           // the fragments; the pack scale's inverse sits right behind them
+  a.w_bytes = (uint32_t)split_frag_bytes(rg.K, cin, cout);           // the fragments; the pack scale's inverse sits right behind them
   a.K = rg.K; a.relu = c.relu ? 1 : 0; a.cap_groups = rg.cap_groups;
   a.flags = l.flags;
   a.res = c.residual;

@@ -6,7 +6,7 @@
 // (reference models/minkfpn.py:86-91, graph.top_down).  For MinkLoc3D that is 256 -> 256 plus 64 -> 256 per level-2 row, which the
 // exact path runs on v_mfma_f32_16x16x4_f32 (sconv_rg / dense kernels) in three launches with two intermediate maps.
 //
-// Arithmetic: the project's split arithmetic (sconv_split.hip): every fp32 operand is hi + lo in fp16, a product is the three
+// Arithmetic: the project's split arithmetic (split16.h): every fp32 operand is hi + lo in fp16, a product is the three
 // v_mfma_f32_16x16x32_f16 products lo*hi, hi*lo, hi*hi accumulated in fp32, weights are scaled by a power of two at pack time
 // (pack_split_weights; undone exactly in the epilogue).  The two packs carry their own scales, so the two products keep their own
 // accumulators and the epilogue forms  acc_t / s_t + acc_l / s_l  — the order `tconv + lateral` of the exact sequence.
@@ -23,13 +23,9 @@
 #include <algorithm>
 
 #include "model.h"
+#include "split16.h"
 
 namespace egonn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -43,23 +39,10 @@ struct TopdownArgs {
   const int32_t* perm;
   const int32_t* meta;
   float* out;                // [n_out][C]
-  int32_t* flags;            // the plan's fp16 range word (bit 3)
+  int32_t* flags;            // the plan's fp16 range word (split16.h: split_raise)
   uint32_t n_in_cap, n_out_cap;
   int cap_groups, ncl;       // ncl = Cl / 32
 };
-
-// fp32 x 8 -> (hi, lo) fp16 x 8, round to nearest even at both levels: the split of sconv_split.hip
-__device__ inline void td_split8h(const f32x4& a0, const f32x4& a1, f16x8_t& hi, f16x8_t& lo) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const float x0 = p < 2 ? a0[2 * p] : a1[2 * p - 4], x1 = p < 2 ? a0[2 * p + 1] : a1[2 * p - 3];
-    const f16x2_t h = __builtin_convertvector((f32x2){x0, x1}, f16x2_t);
-    const f32x2 hf = __builtin_convertvector(h, f32x2);
-    const f16x2_t l = __builtin_convertvector((f32x2){x0 - hf[0], x1 - hf[1]}, f16x2_t);
-    hi[2 * p] = h[0]; hi[2 * p + 1] = h[1];
-    lo[2 * p] = l[0]; lo[2 * p + 1] = l[1];
-  }
-}
 
 constexpr int TD_NW = 4;     // waves (= row groups) per workgroup
 
@@ -170,7 +153,7 @@ __global__ __launch_bounds__(TD_NW * 64) void topdown_split_kernel(const Topdown
     if (s + 1 < n_steps) fetch(s + 1, true);             // in flight under the arithmetic of step s
     if (a_has) {                                         // wave-uniform
       f16x8_t ah, al;
-      td_split8h(a0, a1, ah, al);
+      split8h(a0, a1, ah, al);
       const uint4* w = slab + buf * SLAB16 + lane;
       auto product = [&](f32x4 (&acc)[NS][2]) {
 #pragma unroll
@@ -180,13 +163,7 @@ __global__ __launch_bounds__(TD_NW * 64) void topdown_split_kernel(const Topdown
           const f16x8_t wh1 = __builtin_bit_cast(f16x8_t, w[(ns * 4 + 1) * 64]);
           const f16x8_t wl0 = __builtin_bit_cast(f16x8_t, w[(ns * 4 + 2) * 64]);
           const f16x8_t wl1 = __builtin_bit_cast(f16x8_t, w[(ns * 4 + 3) * 64]);
-          // small terms first (the order of sconv_split_kernel)
-          acc[ns][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl0, ah, acc[ns][0], 0, 0, 0);
-          acc[ns][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl1, ah, acc[ns][1], 0, 0, 0);
-          acc[ns][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh0, al, acc[ns][0], 0, 0, 0);
-          acc[ns][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh1, al, acc[ns][1], 0, 0, 0);
-          acc[ns][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh0, ah, acc[ns][0], 0, 0, 0);
-          acc[ns][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh1, ah, acc[ns][1], 0, 0, 0);
+          split_mfma3(wh0, wh1, wl0, wl1, ah, al, acc[ns][0], acc[ns][1]);
         }
       };
       if (lateral) product(acc_l); else product(acc_t);  // (uniform: the two products keep their own accumulators)
@@ -198,23 +175,22 @@ __global__ __launch_bounds__(TD_NW * 64) void topdown_split_kernel(const Topdown
 
   // ---- epilogue: undo the pack scales, range guard, one 16-byte store per tile
   if (!live) return;
-  const float winv_t = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.wt) + (size_t)8 * C * C * 4);
-  const float winv_l = p.xl ? *reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.wl) + (size_t)p.ncl * 32 * C * 4) : 0.f;
+  const float winv_t = split_pack_winv(p.wt, 8, C, C);
+  const float winv_l = p.xl ? split_pack_winv(p.wl, p.ncl, 32, C) : 0.f;        // (the K = 1 pack of ncl 32-channel blocks)
   float guard = 0.f;
 #pragma unroll
   for (int ns = 0; ns < NS; ++ns)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       const f32x4 t = acc_t[ns][nt], l = acc_l[ns][nt];
-      const f32x4 z = (t - t) + (l - l);                 // 0 for finite values, NaN for Inf / NaN (sticky under addition)
-      guard += (z[0] + z[1]) + (z[2] + z[3]);
+      guard += split_nonfinite(t, l);
       if (orow >= 0) {
         f32x4 v = t * winv_t;
         if (p.xl) v = v + l * winv_l;
         *reinterpret_cast<f32x4*>(p.out + (int64_t)orow * C + (ns0 + ns) * 32 + nt * 16 + 4 * g4) = v;
       }
     }
-  if (__builtin_expect(guard != 0.f, 0) && p.flags) atomicOr(p.flags, 8);
+  if (__builtin_expect(guard != 0.f, 0) && p.flags) split_raise(p.flags);
 }
 
 template <int C, int NS>

@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "model.h"
+#include "rowmath.h"
 
 namespace egonn {
 
@@ -107,7 +108,6 @@ __global__ __launch_bounds__((TCI / 4) * (TCO / 4)) void wgrad_kernel(
 // waves tile the CIN x COUT output (WM x WN waves, each (TM/WM) x (TN/WN) tiles of 16 x 16, accumulators in registers);
 // pairs are compacted like in wgrad_kernel and staged 32 at a time in LDS (row stride +16 floats: the four
 // lane groups of a fragment read four consecutive rows -> bank offsets 0/16, conflict free).
-typedef float wg_f32x4 __attribute__((ext_vector_type(4)));
 template <int CIN, int COUT>
 __global__ __launch_bounds__(256) void wgrad_mfma_kernel(const float* __restrict__ in, const float* __restrict__ dout,
                                                         const int32_t* __restrict__ nbr, int32_t n_out, int K,
@@ -126,11 +126,11 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(const float* __restrict
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, k = blockIdx.y, chunk = blockIdx.x;
   const int wm = w / WN, wn = w % WN;
   const int l15 = lane & 15, g4 = lane >> 4;
-  wg_f32x4 acc[TMW][TNW];
+  f32x4 acc[TMW][TNW];
 #pragma unroll
   for (int i = 0; i < TMW; ++i)
 #pragma unroll
-    for (int j = 0; j < TNW; ++j) acc[i][j] = (wg_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < TNW; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   // rg_perm != null: the pairs come from the row-group form of the map (rowgroup.hip) — slot e = 16 g + s holds output row
   // perm[e] and input row snbr[(g K + k) 16 + s]: one 64-byte line per (group, offset) where the plain table costs every
   // (chunk, offset) workgroup a 108-byte-strided column (each line of the table fetched 27 times); n_out counts slots then
@@ -403,8 +403,6 @@ __global__ __launch_bounds__(256) void conv0_wgrad_kernel(const float* __restric
 //   * issues 8 (offset tiles) x 2 (channel tiles) x 3 (parts) MFMAs into 64 accumulator registers that live for the whole kernel.
 // 1.58 ms -> ~0.05 ms at the 830 k voxels of a 32-scan training step (the plain kernel did 3.3 G predicated FMAs).
 // Deterministic: tiles are dealt to the waves in a fixed order, the partials are summed in fixed order (sum_partials_kernel).
-typedef float f32x4_t4 __attribute__((ext_vector_type(4)));
-typedef float f32x2_t4 __attribute__((ext_vector_type(2)));
 typedef short bf16x8_t4 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t4 __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void conv0_wgrad_unit_kernel(const float* __restrict__ dout, const uint64_t* __restrict__ vkeys,
@@ -433,17 +431,17 @@ __global__ __launch_bounds__(256) void conv0_wgrad_unit_kernel(const float* __re
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint64_t*>(vkeys), 0, (int)((uint32_t)nvox * 8u), 0x00020000);
   const __amdgpu_buffer_rsrc_t d_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dout), 0, (int)((uint32_t)nvox * 128u), 0x00020000);
-  f32x4_t4 acc[8][2];
+  f32x4 acc[8][2];
 #pragma unroll
-  for (int t = 0; t < 8; ++t) acc[t][0] = acc[t][1] = (f32x4_t4){0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < 8; ++t) acc[t][0] = acc[t][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int32_t ntiles = (nvox + 31) >> 5;
   constexpr int NE = (16 * 27 + 63) / 64;
   for (int32_t tile = blockIdx.x * 4 + wave; tile < ntiles; tile += gridDim.x * 4) {
     // ---- dout tile -> LDS (4 coalesced 1 KB loads; rows beyond nvox read zeros)
-    f32x4_t4 dv[4];
+    f32x4 dv[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      dv[q] = __builtin_bit_cast(f32x4_t4, __builtin_amdgcn_raw_buffer_load_b128(d_rsrc, (tile * 32 + q * 8 + (lane >> 3)) * 128 + (lane & 7) * 16, 0, 0));
+      dv[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(d_rsrc, (tile * 32 + q * 8 + (lane >> 3)) * 128 + (lane & 7) * 16, 0, 0));
     // ---- occupancy vectors of the 32 voxels, 16 at a time (the forward kernel's operand construction)
 #pragma unroll 1
     for (int h = 0; h < 2; ++h) {
@@ -491,7 +489,7 @@ __global__ __launch_bounds__(256) void conv0_wgrad_unit_kernel(const float* __re
       }
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4_t4*>(&s_d[wave][q * 8 + (lane >> 3)][(lane & 7) * 4]) = dv[q];
+    for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4*>(&s_d[wave][q * 8 + (lane >> 3)][(lane & 7) * 4]) = dv[q];
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // ---- A operand: dout^T, lane (channel 16 nt + l15, voxels 8 g4 + e), split exactly into three bf16 parts
@@ -502,12 +500,12 @@ __global__ __launch_bounds__(256) void conv0_wgrad_unit_kernel(const float* __re
 #pragma unroll
       for (int pq = 0; pq < 4; ++pq) {
         const float x0 = s_d[wave][8 * g4 + 2 * pq][16 * nt + l15], x1 = s_d[wave][8 * g4 + 2 * pq + 1][16 * nt + l15];
-        const uint32_t hp = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t4){x0, x1}, bf16x2_t4));
+        const uint32_t hp = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){x0, x1}, bf16x2_t4));
         const float r0 = x0 - __uint_as_float(hp << 16), r1 = x1 - __uint_as_float(hp & 0xFFFF0000u);
-        const uint32_t mp = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t4){r0, r1}, bf16x2_t4));
+        const uint32_t mp = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){r0, r1}, bf16x2_t4));
         const float s0 = r0 - __uint_as_float(mp << 16), s1 = r1 - __uint_as_float(mp & 0xFFFF0000u);
         hh[pq] = hp; mm[pq] = mp;
-        ll[pq] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t4){s0, s1}, bf16x2_t4));
+        ll[pq] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){s0, s1}, bf16x2_t4));
       }
       dp[nt][0] = __builtin_bit_cast(bf16x8_t4, make_uint4(hh[0], hh[1], hh[2], hh[3]));
       dp[nt][1] = __builtin_bit_cast(bf16x8_t4, make_uint4(mm[0], mm[1], mm[2], mm[3]));
@@ -549,7 +547,7 @@ __global__ __launch_bounds__(256) void conv0_wgrad_unit_kernel(const float* __re
       for (int t = 0; t < 8; ++t)
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          f32x4_t4* dst = reinterpret_cast<f32x4_t4*>(red + (16 * t + l15) * 32 + 16 * nt + 4 * g4);
+          f32x4* dst = reinterpret_cast<f32x4*>(red + (16 * t + l15) * 32 + 16 * nt + 4 * g4);
           *dst = (w == 0) ? acc[t][nt] : (*dst + acc[t][nt]);
         }
     }
@@ -976,15 +974,6 @@ API int egonn_affine3(const float* g, const float* mask, const float* x, const f
   return EGONN_OK;
 }
 
-__device__ static inline int sample_of(const int32_t* __restrict__ boff, int B, int32_t r) {
-  int lo = 0, hi = B;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (boff[mid] <= r) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // out = relu(x * gate[b] + res)   (gate nullable -> 1; res nullable -> 0)
 __global__ void gate_res_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gate, const float* __restrict__ res,
                                     const int32_t* __restrict__ boff, int B, int64_t total, int c, int relu,
@@ -994,7 +983,7 @@ __global__ void gate_res_fwd_kernel(const float* __restrict__ x, const float* __
   const int32_t r = (int32_t)(i / c);
   const int ci = (int)(i - (int64_t)r * c);
   float v = x[i];
-  if (gate) v *= gate[(int64_t)sample_of(boff, B, r) * c + ci];
+  if (gate) v *= gate[(int64_t)sample_of_row(boff, B, r) * c + ci];
   if (res) v += res[i];
   out[i] = relu ? fmaxf(v, 0.f) : v;
 }
@@ -1008,7 +997,7 @@ __global__ void gate_res_bwd_kernel(const float* __restrict__ dout, const float*
   const int ci = (int)(i - (int64_t)r * c);
   const float d = (out && !(out[i] > 0.f)) ? 0.f : dout[i];
   if (dres) dres[i] = d;
-  dx[i] = gate ? d * gate[(int64_t)sample_of(boff, B, r) * c + ci] : d;
+  dx[i] = gate ? d * gate[(int64_t)sample_of_row(boff, B, r) * c + ci] : d;
 }
 // out[r][c] = v[b(r)][c] * (mean ? 1/n_b : 1)     (backward of the per-sample average pooling / broadcast)
 __global__ void seg_broadcast_kernel(const float* __restrict__ v, const int32_t* __restrict__ boff, int B, int64_t total,
@@ -1017,7 +1006,7 @@ __global__ void seg_broadcast_kernel(const float* __restrict__ v, const int32_t*
   if (i >= total) return;
   const int32_t r = (int32_t)(i / c);
   const int ci = (int)(i - (int64_t)r * c);
-  const int b = sample_of(boff, B, r);
+  const int b = sample_of_row(boff, B, r);
   float s = v[(int64_t)b * c + ci];
   if (mean) s /= (float)(boff[b + 1] - boff[b]);
   out[i] = s;
@@ -1136,7 +1125,7 @@ __global__ void gem_bwd_kernel(const float* __restrict__ x, const float* __restr
   const int ci = (int)(i - (int64_t)r * c);
   const float v = x[i];
   float o = 0.f;
-  if (v >= 1e-6f) o = coef[(int64_t)sample_of(boff, B, r) * c + ci] * powf(v, pexp[0] - 1.f);
+  if (v >= 1e-6f) o = coef[(int64_t)sample_of_row(boff, B, r) * c + ci] * powf(v, pexp[0] - 1.f);
   dx[i] = o;
 }
 API int egonn_gem_backward(egonn_ctx* ctx, int level, const float* x, const float* coef, const float* p, int c, float* dx,
