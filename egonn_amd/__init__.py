@@ -17,7 +17,7 @@ from .local_loss import (KeypointLoss, CorrespondenceLoss, KeypointCorrLoss, mak
 from .train import EgoNNTrainStep
 from .registration import (get_ransac_result, calculate_repeatability, register_pairs, evaluate_local, match_mutual,
                            RegistrationResult, voxel_downsample, icp_pairs, refine_pairs, icp, estimate_normals,
-                           icp_point_to_plane)
+                           icp_point_to_plane, spectral_verify)
 from .augment import (TrainTransform, TrainSetTransform, TrainBatcher, JitterPoints, RemoveRandomPoints, RandomTranslation,
                       RandomRotation, RemoveRandomBlock, RandomFlip, RigidPerturbation, AugmentParams, augment_points)
 from .tuples import (TrainingTuple, EvaluationTuple, EvaluationSet, save_training_tuples, load_training_tuples, radius_neighbors,
@@ -35,7 +35,7 @@ __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "Mink
            "KeypointLoss", "CorrespondenceLoss", "KeypointCorrLoss", "make_local_loss",
            "BatchedKeypointCorrLoss", "local_loss_packed", "EgoNNTrainStep",
            "get_ransac_result", "calculate_repeatability", "register_pairs", "evaluate_local", "match_mutual", "RegistrationResult",
-           "voxel_downsample", "icp_pairs", "refine_pairs", "icp", "estimate_normals", "icp_point_to_plane",
+           "voxel_downsample", "icp_pairs", "refine_pairs", "icp", "estimate_normals", "icp_point_to_plane", "spectral_verify",
            "TrainTransform", "TrainSetTransform", "TrainBatcher", "JitterPoints", "RemoveRandomPoints", "RandomTranslation",
            "RandomRotation", "RemoveRandomBlock", "RandomFlip", "RigidPerturbation", "AugmentParams", "augment_points",
            "TrainingTuple", "EvaluationTuple", "EvaluationSet", "save_training_tuples", "load_training_tuples", "radius_neighbors",

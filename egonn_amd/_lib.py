@@ -138,6 +138,9 @@ _SIGS = [
                                      C.c_int64, _P, _P, _P]),
     ("egonn_registration_finish", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double, _P,
                                             C.c_int64, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("egonn_spectral_verify_scratch_bytes", C.c_int64, [C.c_int, C.c_int]),
+    ("egonn_spectral_verify", C.c_int, [_P] * 6 + [C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, _P, C.c_double,
+                                        _P, C.c_int64] + [_P] * 15),
     ("egonn_voxel_downsample_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
     ("egonn_voxel_downsample", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_double, C.POINTER(C.c_float), _P, _P, _P, _P, _P,
                                          C.c_int64, _P]),

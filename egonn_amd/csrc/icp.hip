@@ -38,6 +38,7 @@
 // (icp_plane_step).  The point-to-point instantiation is the code above, operation for operation.
 #include "../../include/egonn_hip.h"
 #include "common.h"
+#include "horn.h"
 
 #pragma clang fp contract(off)
 
@@ -604,69 +605,6 @@ __global__ __launch_bounds__(ICP_WG) void icp_search_kernel(const IcpPair* __res
   if (t < NP) partial[(size_t)flat * NP + t] = ((s_red[t][0] + s_red[t][1]) + s_red[t][2]) + s_red[t][3];
 }
 
-// largest eigenvector of the symmetric 4 x 4 matrix A (cyclic Jacobi, fixed schedule): the unit quaternion (w, x, y, z)
-__device__ static void icp_top_eigenvector(double A[4][4], double* qv) {
-  double V[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 40; ++sweep) {
-    double offd = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = i + 1; j < 4; ++j) offd += fabs(A[i][j]);
-    if (offd == 0.0) break;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = i + 1; j < 4; ++j) {
-        const double apq = A[i][j];
-        if (apq == 0.0) continue;
-        const double theta = (A[j][j] - A[i][i]) / (2.0 * apq);
-        const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {              // A <- A J
-          const double aki = A[k][i], akj = A[k][j];
-          A[k][i] = c * aki - s * akj;
-          A[k][j] = s * aki + c * akj;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {              // A <- J^T A
-          const double aik = A[i][k], ajk = A[j][k];
-          A[i][k] = c * aik - s * ajk;
-          A[j][k] = s * aik + c * ajk;
-        }
-        A[i][j] = A[j][i] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double vki = V[k][i], vkj = V[k][j];
-          V[k][i] = c * vki - s * vkj;
-          V[k][j] = s * vki + c * vkj;
-        }
-      }
-  }
-  int m = 0;
-#pragma unroll
-  for (int i = 1; i < 4; ++i)
-    if (A[i][i] > A[m][m]) m = i;
-  double nrm = 0.0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    double e = V[k][0];
-    if (m == 1) e = V[k][1];
-    if (m == 2) e = V[k][2];
-    if (m == 3) e = V[k][3];
-    qv[k] = e;
-    nrm += e * e;
-  }
-  nrm = 1.0 / sqrt(nrm);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) qv[k] *= nrm;
-}
-
 // Point-to-plane step: solves A x = -b (A = sum J J^T from its 21 upper entries row by row, b = sum J r) by LDL^T without
 // pivoting and returns U = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)] as (U[9], ut[3]).  False, with nothing to rely on in U, when
 // a pivot d_i is not > 2^-40 A_ii (A's own diagonal: fp64 leaves ~2^-52 relative rounding in a pivot, twelve bits above that
@@ -772,23 +710,7 @@ __global__ __launch_bounds__(64) void icp_finish_kernel(IcpPair* __restrict__ pa
     for (int k = 0; k < 3; ++k) pm[k] = s[2 + k] / n, qm[k] = s[5 + k] / n;
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) S[r][c] = s[8 + r * 3 + c] - n * pm[r] * qm[c];
-    double N[4][4];
-    N[0][0] = S[0][0] + S[1][1] + S[2][2];
-    N[1][1] = S[0][0] - S[1][1] - S[2][2];
-    N[2][2] = -S[0][0] + S[1][1] - S[2][2];
-    N[3][3] = -S[0][0] - S[1][1] + S[2][2];
-    N[0][1] = N[1][0] = S[1][2] - S[2][1];
-    N[0][2] = N[2][0] = S[2][0] - S[0][2];
-    N[0][3] = N[3][0] = S[0][1] - S[1][0];
-    N[1][2] = N[2][1] = S[0][1] + S[1][0];
-    N[1][3] = N[3][1] = S[2][0] + S[0][2];
-    N[2][3] = N[3][2] = S[1][2] + S[2][1];
-    double qv[4];
-    icp_top_eigenvector(N, qv);
-    const double qw = qv[0], qx = qv[1], qy = qv[2], qz = qv[3];
-    U[0] = 1.0 - 2.0 * (qy * qy + qz * qz), U[1] = 2.0 * (qx * qy - qw * qz), U[2] = 2.0 * (qx * qz + qw * qy);
-    U[3] = 2.0 * (qx * qy + qw * qz), U[4] = 1.0 - 2.0 * (qx * qx + qz * qz), U[5] = 2.0 * (qy * qz - qw * qx);
-    U[6] = 2.0 * (qx * qz - qw * qy), U[7] = 2.0 * (qy * qz + qw * qx), U[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
+    horn_rotation(S, U);
     for (int r = 0; r < 3; ++r) ut[r] = qm[r] - (U[r * 3] * pm[0] + U[r * 3 + 1] * pm[1] + U[r * 3 + 2] * pm[2]);
   }
   double Rn[9], tn[3];
@@ -834,7 +756,7 @@ __global__ __launch_bounds__(ICP_WG) void nrm_status_kernel(const double* __rest
     status[c] = (bad ? EGONN_NORMALS_STATUS_RANGE : 0) | ((hi > lo ? hi - lo : 0) < knn ? EGONN_NORMALS_STATUS_FEW_POINTS : 0);
 }
 
-// eigen-decomposition of the symmetric 3 x 3 matrix A by cyclic Jacobi, the schedule of icp_top_eigenvector: A's diagonal
+// eigen-decomposition of the symmetric 3 x 3 matrix A by cyclic Jacobi, the schedule of horn_top_eigenvector (horn.h): A's diagonal
 // becomes the eigenvalues, the columns of V the eigenvectors
 __device__ static inline void nrm_jacobi3(double A[3][3], double V[3][3]) {
 #pragma unroll

@@ -113,7 +113,8 @@ class LoopDetector:
     kmap: a `KeypointMap` to adopt (None: one is made from n_k, dim, global_dim on `device`; a map that already holds
     entries needs their `times`); k: candidates per scan (<= 64); min_time_gap / max_time_gap: the admissible age in
     seconds; verify: register every candidate from its keypoints (`verify_candidates`) and keep the one with the most
-    inliers; min_inliers, ransac_dist_th, ransac_max_it, seed: passed on to it.
+    inliers; min_inliers, ransac_dist_th, ransac_max_it, seed: passed on to it, and verify_method as its `method` ("ransac" or
+    "spectral").
 
     min_inliers = 0 means: the best candidate with a model wins.  No threshold for real data can be derived here (there are
     neither trained weights nor a dataset in this project); pick one from the inlier counts of wrong candidates on your data,
@@ -125,8 +126,11 @@ class LoopDetector:
 
     def __init__(self, kmap: Optional[KeypointMap] = None, k: int = 20, min_time_gap: float = 30.0, max_time_gap: float = math.inf,
                  verify: bool = True, min_inliers: int = 0, ransac_dist_th: float = 0.5, ransac_max_it: int = 10000, seed: int = 0,
-                 n_k: int = 128, dim: int = 128, global_dim: int = 256, device=None, times=None):
+                 n_k: int = 128, dim: int = 128, global_dim: int = 256, device=None, times=None, verify_method: str = "ransac"):
         _check_gaps("LoopDetector", k, min_time_gap, max_time_gap)
+        if verify_method not in ("ransac", "spectral"):
+            raise ValueError(f"LoopDetector: verify_method must be 'ransac' or 'spectral', got {verify_method!r}")
+        self.verify_method = verify_method
         self.kmap = KeypointMap(n_k, dim, global_dim, device) if kmap is None else kmap
         self.k, self.min_time_gap, self.max_time_gap = int(k), float(min_time_gap), float(max_time_gap)
         self.verify, self.min_inliers = bool(verify), int(min_inliers)
@@ -182,7 +186,7 @@ class LoopDetector:
         if self.verify:
             r = verify_candidates(km.descriptors[start:], km.keypoints[start:], km.counts[start:], km, nn, query_ids=index,
                                   min_inliers=self.min_inliers, ransac_dist_th=self.ransac_dist_th,
-                                  ransac_max_it=self.ransac_max_it, seed=self.seed)
+                                  ransac_max_it=self.ransac_max_it, seed=self.seed, method=self.verify_method)
         r.update(nn_index=nn, nn_dist=dist, index=index, win_lo=lo, win_hi=hi,
                  loop=(r["best_index"] >= 0) if self.verify else (nn[:, 0] >= 0))
         return r

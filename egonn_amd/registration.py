@@ -90,16 +90,96 @@ def enqueue_ransac(dev, operands, P, n_max, H, seed, dist_th, scratch, T_gt, rep
               p("status"))
 
 
+METHODS = ("ransac", "spectral")
+SPECTRAL_D_THR, SPECTRAL_ITERATIONS, SPECTRAL_SEED_RATIO = 0.6, 32, 0.5      # choices, not tuned values (`spectral_verify`)
+_SPECTRAL_OUT = ("eigenvalue", "score", "weights", "n_seeds", "T", "inliers", "fitness", "inlier_rmse", "correspondence_set",
+                 "rte", "rre", "success", "repeatability", "status")
+
+
+def check_method(who, method):
+    if method not in METHODS:
+        raise ValueError(f"{who}: method must be one of {METHODS}, got {method!r}")
+    return method
+
+
+def enqueue_spectral(dev, operands, P, n_max, d_thr, iterations, seed_ratio, dist_th, scratch, T_gt, repeat_th, out):
+    """egonn_spectral_verify of P pairs.  operands: the pointers (kp1, kp2, n1, n2, corr, n_corr); scratch: `_lib.scratch` of
+    egonn_spectral_verify_scratch_bytes; T_gt: (P,4,4) f64 tensor or None; out: the outputs by the names of `spectral_verify`
+    (an absent one is not computed).  Nothing is allocated and nothing synchronises, so the call can be captured; the caller
+    keeps the operands alive."""
+    lib = _lib.load()
+    _lib.call(dev, lib.egonn_spectral_verify, *operands, P, n_max, float(d_thr), int(iterations), float(seed_ratio),
+              float(dist_th), _lib._ptr(T_gt), float(repeat_th), scratch.data_ptr(), scratch.numel() * 8,
+              *(_lib._ptr(out.get(k)) for k in _SPECTRAL_OUT))
+
+
+def _spectral_buffers(dev, P, n_max, with_gt):
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
+    out = {"eigenvalue": f64(P), "score": f64(P), "weights": f64(P, n_max), "n_seeds": i32(P), "T": f64(P, 4, 4),
+           "inliers": i32(P), "fitness": f64(P), "inlier_rmse": f64(P), "correspondence_set": i32(P, n_max, 2), "status": i32(P)}
+    if with_gt:
+        out.update({"rte": f64(P), "rre": f64(P), "success": i32(P), "repeatability": f64(P)})
+    out["_scratch"] = _lib.scratch(_lib.load().egonn_spectral_verify_scratch_bytes(P, n_max), dev)   # -1: the call raises
+    return out
+
+
+def spectral_verify(kp1, kp2, corr, n_corr, n1=None, n2=None, T_gt=None, d_thr: float = SPECTRAL_D_THR,
+                    iterations: int = SPECTRAL_ITERATIONS, seed_ratio: float = SPECTRAL_SEED_RATIO, dist_th: float = 0.5,
+                    out=None, repeat_dist_th: float = 0.5) -> Dict[str, torch.Tensor]:
+    """Spectral geometric verification of P pairs (egonn_spectral_verify, csrc/spectral.hip): no hypotheses, no seed.
+
+    kp (P, n_max, 3), corr (P, n_max, 2) int32 with n_corr (P,) valid rows (what `match_mutual` returns), n1 / n2 (P,) keypoint
+    counts (None = n_max), T_gt (P,4,4) or None.  The pairwise length-consistency matrix M_ij = max(0, 1 - d_ij^2 / d_thr^2)
+    of the correspondences, `iterations` power iterations from the uniform vector, eigenvalue = v^T M v (about the size of the
+    consistent set minus 1), score = eigenvalue / (n_max - 1), seeds = correspondences with v_i >= seed_ratio * max v, a rigid
+    fit on the seeds, its inliers under dist_th, a refit on them, then the final evaluation of `register_pairs`.
+
+    Returns device tensors: eigenvalue, score (P,) f64, weights (P, n_max) f64 (v, zero beyond n_corr), n_seeds (P,) i32, and
+    with the meaning they have in `register_pairs`: T, inliers, fitness, inlier_rmse, correspondence_set, status, with T_gt
+    also rte, rre, success, repeatability.
+
+    d_thr = 0.6 m, 32 iterations and seed_ratio = 0.5 are choices, not tuned values: there are neither trained weights nor
+    data to tune on in this project.
+
+    No host synchronisation when the inputs are device tensors.  `out`: the dict of an earlier call with the same shapes; its
+    buffers (scratch included) are used again and nothing is allocated, which a graph capture needs."""
+    dev = kp1.device if torch.is_tensor(kp1) and kp1.is_cuda else _lib.require_gpu()
+    k1, k2 = _dev(kp1, dev, torch.float32), _dev(kp2, dev, torch.float32)
+    if k1.dim() != 3 or k1.shape[2] != 3 or k1.shape != k2.shape:
+        raise ValueError(f"spectral_verify: keypoints must be (P, n_max, 3) on both sides, got {tuple(k1.shape)}, {tuple(k2.shape)}")
+    P, n_max = k1.shape[0], k1.shape[1]
+    c, nc = _dev(corr, dev, torch.int32), _dev(n_corr, dev, torch.int32)
+    if tuple(c.shape) != (P, n_max, 2) or tuple(nc.shape) != (P,):
+        raise ValueError(f"spectral_verify: corr must be ({P}, {n_max}, 2) and n_corr ({P},), got {tuple(c.shape)}, {tuple(nc.shape)}")
+    c1, c2 = _counts(n1, P, n_max, dev), _counts(n2, P, n_max, dev)
+    gt = None if T_gt is None else _dev(T_gt, dev, torch.float64).reshape(P, 4, 4)
+    if out is None:
+        out = _spectral_buffers(dev, P, n_max, gt is not None)
+    elif "weights" not in out or tuple(out["weights"].shape) != (P, n_max) or ("rte" in out) != (gt is not None) or \
+            out["weights"].device != dev:
+        raise ValueError("spectral_verify: `out` was made by a call with other shapes")
+    enqueue_spectral(dev, (k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), c.data_ptr(), nc.data_ptr()), P, n_max,
+                     d_thr, iterations, seed_ratio, dist_th, out["_scratch"], gt, repeat_dist_th, out)
+    out["_keep"] = (k1, k2, c1, c2, c, nc, gt)             # inputs of enqueued work stay alive with the result
+    return out
+
+
 def register_pairs(feat1, feat2, kp1, kp2, n1=None, n2=None, T_gt=None, ransac_dist_th: float = 0.5,
                    ransac_max_it: int = 10000, seed: int = 0, pair_ids=None, repeat_dist_th: float = 0.5,
-                   debug: bool = False) -> Dict[str, torch.Tensor]:
+                   debug: bool = False, method: str = "ransac", d_thr: float = SPECTRAL_D_THR,
+                   iterations: int = SPECTRAL_ITERATIONS, seed_ratio: float = SPECTRAL_SEED_RATIO) -> Dict[str, torch.Tensor]:
     """P pairs at once.  feat (P, n_max, D), kp (P, n_max, 3), n1 / n2 (P,) row counts (None = n_max), T_gt (P,4,4) or None.
     Returns device tensors: T (P,4,4) f64, inliers (P,) i32, fitness, inlier_rmse (P,) f64, correspondence_set
     (P, n_max, 2) i32 (rows beyond `inliers` are -1), best_t, status (P,) i32, corr, n_corr; with T_gt also rte, rre (f64),
     success (i32), repeatability (f64); with debug the per-hypothesis tables hyp_count (P,H) i32 and hyp_err2 (P,H) f64.
     pair_ids (P,) int32: the id that enters the draws, its low 30 bits (None = position in the batch).
     No host synchronisation when every array argument is a device tensor (host arrays or lists are copied over first); such a
-    call can be captured into a graph."""
+    call can be captured into a graph.
+    method="spectral": the same matching, then `spectral_verify` (d_thr, iterations, seed_ratio; ransac_dist_th is its
+    dist_th) instead of RANSAC: the same keys plus eigenvalue, score, weights and n_seeds, without best_t; ransac_max_it, seed,
+    pair_ids and debug are accepted and ignored."""
+    check_method("register_pairs", method)
     dev = feat1.device if torch.is_tensor(feat1) and feat1.is_cuda else _lib.require_gpu()
     lib = _lib.load()
     f1 = _dev(feat1, dev, torch.float32)
@@ -109,6 +189,11 @@ def register_pairs(feat1, feat2, kp1, kp2, n1=None, n2=None, T_gt=None, ransac_d
     corr, n_corr = match_mutual(f1, _dev(feat2, dev, torch.float32), c1, c2)
     k1, k2 = _dev(kp1, dev, torch.float32), _dev(kp2, dev, torch.float32)
     assert k1.shape == (P, n_max, 3) and k2.shape == (P, n_max, 3), "keypoints: (P, n_max, 3), padded like the descriptors"
+    if method == "spectral":
+        out = spectral_verify(k1, k2, corr, n_corr, c1, c2, T_gt, d_thr, iterations, seed_ratio, ransac_dist_th,
+                              repeat_dist_th=repeat_dist_th)
+        out.update(corr=corr, n_corr=n_corr)
+        return out
     H = int(ransac_max_it)
     pid = None if pair_ids is None else _dev(pair_ids, dev, torch.int32)
     gt = None if T_gt is None else _dev(T_gt, dev, torch.float64).reshape(P, 4, 4)

@@ -8,7 +8,8 @@ instead of trusting rank 0 is what turns recall@k into recall@1.
 
 `KeypointMap` holds the map resident on the device, `verify_candidates` is the sync-free call sequence
 egonn_match_candidates -> egonn_gather_candidates -> egonn_ransac_pairs -> egonn_registration_finish ->
-egonn_pick_candidates, `Relocalizer` is the product call from raw scans and `evaluate_relocalization` its metrics.
+egonn_pick_candidates (with method="spectral": egonn_spectral_verify, csrc/spectral.hip, in place of the two RANSAC
+calls), `Relocalizer` is the product call from raw scans and `evaluate_relocalization` its metrics.
 All arithmetic runs in libegonn_hip; there is no torch or numpy fallback.
 """
 from __future__ import annotations
@@ -137,10 +138,12 @@ class KeypointMap:
         return m
 
 
-def _verify_buffers(dev, Q, k, n_max, Pc, with_gt, nb_match, nb_reg):
+def _verify_buffers(dev, Q, k, n_max, Pc, with_gt, nb_match, nb_reg, method="ransac"):
     f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
     i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
-    out = {"T": f64(Q, k, 4, 4), "fitness": f64(Q, k), "inlier_rmse": f64(Q, k), "inliers": i32(Q, k), "best_t": i32(Q, k),
+    own = {"best_t": i32(Q, k)} if method == "ransac" else \
+        {"eigenvalue": f64(Q, k), "score": f64(Q, k), "weights": f64(Q, k, n_max), "n_seeds": i32(Q, k)}
+    out = {"T": f64(Q, k, 4, 4), "fitness": f64(Q, k), "inlier_rmse": f64(Q, k), "inliers": i32(Q, k), **own,
            "pair_status": i32(Q, k), "match_status": i32(Q, k), "corr": i32(Q, k, n_max, 2), "n_corr": i32(Q, k),
            "pair_ids": i32(Q, k),
            "best_rank": i32(Q), "best_index": i32(Q), "reranked": i32(Q, k), "T_rel": f64(Q, 4, 4), "pose": f64(Q, 4, 4),
@@ -157,11 +160,15 @@ def _verify_buffers(dev, Q, k, n_max, Pc, with_gt, nb_match, nb_reg):
 # outputs of egonn_registration_finish by the names of `register_pairs` -> the per-pair keys of `verify_candidates`
 _FINISH_OUT = (("T", "T"), ("inliers", "inliers"), ("fitness", "fitness"), ("inlier_rmse", "inlier_rmse"), ("best_t", "best_t"),
                ("rte", "rte"), ("rre", "rre"), ("success", "success"), ("status", "pair_status"))
+# the same for egonn_spectral_verify and `spectral_verify`
+_SPECTRAL_OUT = tuple(x for x in _FINISH_OUT if x[0] != "best_t") + tuple((n, n) for n in ("eigenvalue", "score", "weights", "n_seeds"))
 
 
 def verify_candidates(q_desc, q_kp, q_count, kmap: KeypointMap, nn_index, query_ids=None, T_gt=None, min_inliers: int = 0,
                       ransac_dist_th: float = 0.5, ransac_max_it: int = 10000, seed: int = 0, chunk_pairs: int = MAX_PAIRS,
-                      out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                      out: Optional[Dict[str, torch.Tensor]] = None, method: str = "ransac", d_thr: float = _reg.SPECTRAL_D_THR,
+                      iterations: int = _reg.SPECTRAL_ITERATIONS,
+                      seed_ratio: float = _reg.SPECTRAL_SEED_RATIO) -> Dict[str, torch.Tensor]:
     """Register Q queries against k map entries each and pick the best candidate per query.
 
     q_desc (Q, n_k, D), q_kp (Q, n_k, 3), q_count (Q,) or None (= n_k): what the extractors return; nn_index (Q, k) int32 map
@@ -179,9 +186,14 @@ def verify_candidates(q_desc, q_kp, q_count, kmap: KeypointMap, nn_index, query_
     min_inliers = 0 means: the best candidate with a model wins.  No threshold for real data can be derived here (there are
     neither trained weights nor a dataset in this project); pick one from the inlier counts of wrong candidates on your data.
 
+    method="spectral": egonn_spectral_verify (`registration.spectral_verify`: d_thr, iterations, seed_ratio; ransac_dist_th
+    is its dist_th) takes the place of the two RANSAC calls.  The pick order is the same; per pair eigenvalue, score (Q, k),
+    weights (Q, k, n_k) and n_seeds replace best_t; ransac_max_it and seed are ignored and pair_ids enter nothing.
+
     No host synchronisation when the inputs are device tensors.  Queries are chunked so that a call sequence covers at most
-    `chunk_pairs` (<= 4096) pairs.  `out`: the dict of an earlier call with the same shapes; its buffers (scratch included)
-    are used again and nothing is allocated, which a graph capture through egonn_graph_begin / egonn_graph_end needs."""
+    `chunk_pairs` (<= 4096) pairs.  `out`: the dict of an earlier call with the same shapes and method; its buffers (scratch
+    included) are used again and nothing is allocated, which a graph capture through egonn_graph_begin / egonn_graph_end needs."""
+    spectral = _reg.check_method("verify_candidates", method) == "spectral"
     dev = q_desc.device if torch.is_tensor(q_desc) and q_desc.is_cuda else _lib.require_gpu()
     lib = _lib.load()
     qf = _dev(q_desc, dev, torch.float32)
@@ -216,11 +228,14 @@ def verify_candidates(q_desc, q_kp, q_count, kmap: KeypointMap, nn_index, query_
         qid = torch.arange(Q, dtype=torch.int32, device=dev)
     H = int(ransac_max_it)
     nb_match = int(lib.egonn_match_candidates_scratch_bytes(qc, k, n_max))     # -1 on bad arguments: the calls below raise
-    nb_reg = int(lib.egonn_registration_scratch_bytes(qc * k, n_max, H))
+    nb_reg = int(lib.egonn_spectral_verify_scratch_bytes(qc * k, n_max) if spectral else
+                 lib.egonn_registration_scratch_bytes(qc * k, n_max, H))
     if out is None:
-        out = _verify_buffers(dev, Q, k, n_max, qc * k, gt is not None, nb_match, nb_reg)
+        out = _verify_buffers(dev, Q, k, n_max, qc * k, gt is not None, nb_match, nb_reg, method)
     else:
         w = out.get("_work", {})
+        if ("eigenvalue" in out) != spectral:
+            raise ValueError(f"verify_candidates: `out` was made by a call with the other method, not {method!r}")
         if tuple(out["corr"].shape) != (Q, k, n_max, 2) or ("rte" in out) != (gt is not None) or out["T"].device != dev or \
                 w["kp1"].shape[0] != qc * k or w["match"].numel() * 8 < nb_match or w["reg"].numel() * 8 < nb_reg:
             raise ValueError("verify_candidates: `out` was made by a call with other shapes")
@@ -236,10 +251,15 @@ def verify_candidates(q_desc, q_kp, q_count, kmap: KeypointMap, nn_index, query_
         _lib.call(dev, lib.egonn_gather_candidates, qk[lo:hi].data_ptr(), qn[lo:hi].data_ptr(), km[1].data_ptr(), km[2].data_ptr(),
                   nn[lo:hi].data_ptr(), None if qid is None else qid[lo:hi].data_ptr(), n, k, M, n_max, w["kp1"].data_ptr(),
                   w["kp2"].data_ptr(), w["n1"].data_ptr(), w["n2"].data_ptr(), s("pair_ids"))
-        _reg.enqueue_ransac(dev, (w["kp1"].data_ptr(), w["kp2"].data_ptr(), w["n1"].data_ptr(), w["n2"].data_ptr(), s("corr"),
-                                  s("n_corr"), s("pair_ids")), P, n_max, H, seed, ransac_dist_th, w["reg"],
-                            None if gt is None else gt[lo:hi], 0.5,
-                            {name: out[key][lo:hi] for name, key in _FINISH_OUT if key in out})
+        operands = (w["kp1"].data_ptr(), w["kp2"].data_ptr(), w["n1"].data_ptr(), w["n2"].data_ptr(), s("corr"), s("n_corr"))
+        if spectral:
+            _reg.enqueue_spectral(dev, operands, P, n_max, d_thr, iterations, seed_ratio, ransac_dist_th, w["reg"],
+                                  None if gt is None else gt[lo:hi], 0.5,
+                                  {name: out[key][lo:hi] for name, key in _SPECTRAL_OUT if key in out})
+        else:
+            _reg.enqueue_ransac(dev, (*operands, s("pair_ids")), P, n_max, H, seed, ransac_dist_th, w["reg"],
+                                None if gt is None else gt[lo:hi], 0.5,
+                                {name: out[key][lo:hi] for name, key in _FINISH_OUT if key in out})
         _lib.call(dev, lib.egonn_pick_candidates, nn[lo:hi].data_ptr(), n, k, M, km[3].data_ptr(), s("T"), s("inliers"),
                   s("inlier_rmse"), s("pair_status"), s("rte"), s("rre"), s("success"), int(min_inliers), s("best_rank"),
                   s("best_index"), s("reranked"), s("T_rel"), s("pose"), s("safe_pick"), s("best_inliers"), s("status"),
@@ -271,11 +291,14 @@ class Relocalizer:
     extractor: a `DescriptorExtractor` (or any object whose `extract(scans)` returns its dict); kmap: a `KeypointMap` on the
     extractor's device; k: candidates per query.  refine=True needs `kmap.clouds` and polishes the winner's T_rel by
     point-to-point ICP of the query's downsampled cloud against the winner's cloud of the bank; icp_point2plane=True uses the
-    point-to-plane estimator instead, on normals of the gathered winners' clouds."""
+    point-to-plane estimator instead, on normals of the gathered winners' clouds.  method, d_thr, iterations, seed_ratio: the
+    geometric check of `verify_candidates` ("ransac" or "spectral")."""
 
     def __init__(self, extractor, kmap: KeypointMap, k: int = 20, min_inliers: int = 0, ransac_dist_th: float = 0.5,
                  ransac_max_it: int = 10000, seed: int = 0, refine: bool = False, icp_dist_th: float = 1.2,
-                 icp_max_it: int = 200, chunk_pairs: int = MAX_PAIRS, icp_point2plane: bool = False):
+                 icp_max_it: int = 200, chunk_pairs: int = MAX_PAIRS, icp_point2plane: bool = False, method: str = "ransac",
+                 d_thr: float = _reg.SPECTRAL_D_THR, iterations: int = _reg.SPECTRAL_ITERATIONS,
+                 seed_ratio: float = _reg.SPECTRAL_SEED_RATIO):
         if int(k) < 1:
             raise ValueError("Relocalizer: k must be positive")
         if refine and kmap.clouds is None:
@@ -284,6 +307,8 @@ class Relocalizer:
         self.min_inliers, self.ransac_dist_th, self.ransac_max_it, self.seed = int(min_inliers), ransac_dist_th, ransac_max_it, seed
         self.refine, self.icp_dist_th, self.icp_max_it, self.chunk_pairs = bool(refine), icp_dist_th, icp_max_it, chunk_pairs
         self.icp_point2plane = bool(icp_point2plane)
+        self.method = _reg.check_method("Relocalizer", method)
+        self.d_thr, self.iterations, self.seed_ratio = d_thr, iterations, seed_ratio
 
     def _extract(self, scans):
         """-> (extractor dict, deferred status check or None)"""
@@ -313,7 +338,8 @@ class Relocalizer:
             b = nn.reshape(-1).clamp(0, len(km) - 1)
             gt = relative_poses(allp, a, b, negate_translation=False).reshape(Q, k, 4, 4)
         r = verify_candidates(y["descriptors"], y["keypoints"], y.get("count"), km, nn, query_ids, gt, self.min_inliers,
-                              self.ransac_dist_th, self.ransac_max_it, self.seed, self.chunk_pairs)
+                              self.ransac_dist_th, self.ransac_max_it, self.seed, self.chunk_pairs, method=self.method,
+                              d_thr=self.d_thr, iterations=self.iterations, seed_ratio=self.seed_ratio)
         r["nn_index"], r["global"] = nn, y["global"]
         if self.refine:
             bank = km.clouds

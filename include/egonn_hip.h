@@ -680,6 +680,35 @@ int egonn_registration_finish(const float* kp1, const float* kp2, const int32_t*
                               double repeat_th, double* T, int32_t* inliers, double* fitness, double* inlier_rmse,
                               int32_t* corr_set, int32_t* best_t, double* rte, double* rre, int32_t* success,
                               double* repeatability, int32_t* status, void* stream);
+/* Spectral geometric verification (csrc/spectral.hip): the hypothesis-free counterpart of egonn_ransac_pairs +
+ * egonn_registration_finish on the same operands (kp1, kp2, n1, n2, corr, n_corr as above; no pair id, no seed).  Per pair,
+ * with m = n_corr and (p_i, q_i) = (kp1[corr[i][0]], kp2[corr[i][1]]) converted exactly to fp64:
+ *   M_ij = max(0, 1 - d_ij^2 / d_thr^2), d_ij = | |p_i - p_j| - |q_i - q_j| |, M_ii = 0 (fp64, stored rounded to fp32);
+ *   v = 1 / sqrt(m) everywhere, then exactly `iterations` times u = M v; |u| = 0: stop; v = u / |u|;  eigenvalue = v^T M v
+ *   (about the size of the mutually consistent set minus 1; fp64 sums in a fixed order: a row in ascending j, the rows by a
+ *   64-lane butterfly and then ascending waves);  score = eigenvalue / (n_max - 1), the normaliser fixed so that a pair with
+ *   few correspondences cannot outrank one with many consistent ones (0 when n_max = 1);
+ *   seeds S = { i : v_i >= seed_ratio * max v };  T0 = least-squares rigid transform of S (no scale, det +1: Horn's closed form
+ *   with the fixed-schedule Jacobi of the ICP);  I = { i : |T0 p_i - q_i| < dist_th };  T = the rigid transform of I.
+ * inliers, fitness, inlier_rmse, corr_set and, with T_gt, rte / rre / success / repeatability are then those of
+ * egonn_registration_finish under T: same definitions, shapes and dtypes, so egonn_pick_candidates consumes them unchanged.
+ * status: CLIPPED / BAD_INDEX as the registration; FEW_CORR when m < 3; NO_MODEL when M = 0, |S| < 3, |I| < 3 or a fit is
+ * degenerate (coincident or collinear points: a scatter matrix C with e2(C) <= 1e-10 tr(C)^2, e2 = the sum of its principal
+ * 2 x 2 minors); in both cases T = identity and 0 inliers.  No output is ever NaN for finite keypoints inside the counts.
+ * eigenvalue, score (n_pairs) f64, weights (n_pairs, n_max) f64 = v, zero from m on, n_seeds (n_pairs) int32 = |S|.  Every
+ * output is nullable (null = not written).  Rows of corr from n_corr on and keypoints beyond the counts are never read.
+ * d_thr > 0, iterations >= 1, 0 < seed_ratio <= 1, dist_th > 0 (checked, with the shape and the pointers, before anything is
+ * launched).  One launch, no host synchronisation, no float atomics: deterministic, capturable, and a pair's result does not
+ * depend on n_pairs, on its position in the batch or on other pairs.  scratch: egonn_spectral_verify_scratch_bytes
+ * (n_pairs, n_max) bytes, 8-byte aligned: 0 (scratch may be null) up to n_max = 128, where M lives in LDS, else
+ * min(n_pairs, 512) * n_max^2 * 4 for the workgroups' slabs of M; -1 on bad arguments. */
+int64_t egonn_spectral_verify_scratch_bytes(int n_pairs, int n_max);
+int egonn_spectral_verify(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2, const int32_t* corr,
+                          const int32_t* n_corr, int n_pairs, int n_max, double d_thr, int iterations, double seed_ratio,
+                          double dist_th, const double* T_gt, double repeat_th, void* scratch, int64_t scratch_bytes,
+                          double* eigenvalue, double* score, double* weights, int32_t* n_seeds, double* T, int32_t* inliers,
+                          double* fitness, double* inlier_rmse, int32_t* corr_set, double* rte, double* rre, int32_t* success,
+                          double* repeatability, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------ ICP refinement of scan pairs (local evaluation, tuples)
  * replaces icp() of misc/point_clouds.py:31-62 (voxel_down_sample(0.1) of both clouds, then Open3D's registration_icp,

@@ -10,8 +10,13 @@ same run, so both see the same machine).
                The two forms must agree bit for bit.
   2. the whole verify_candidates call at the same points (default call, and with its buffers reused through out=)
   3. Relocalizer.localize at batch 1 and 16 on 50 k-point synthetic scans (seeded weights, a map of --map_scans scans)
+  4. --spectral: the two geometric checks at the same points, on the same operands (the matcher's correspondences and the
+               gathered keypoints of the call's pairs): egonn_ransac_pairs + egonn_registration_finish against
+               egonn_spectral_verify, and the whole verify_candidates (buffers reused) under method="ransac" and "spectral".
+               With this flag only these are measured, and the rows are APPENDED to the "spectral_rows" of an existing --out
+               file, whose other content is kept.
 
-    python tools/time_relocalize.py --out profiles/relocalize_timing.json [--commit HASH]
+    python tools/time_relocalize.py --out profiles/relocalize_timing.json [--commit HASH] [--spectral]
 """
 import argparse
 import json
@@ -48,6 +53,63 @@ def _time_alternated(forms, warmup, reps, burst):
                    "windows": reps, "calls_per_window": burst} for name, v in ms.items()}
 
 
+def _overlap(a, b):
+    return not (a["max"] < b["min"] or b["max"] < a["min"])
+
+
+def _spectral_row(ea, _lib, lib, km, qf, qk, qn, nn, H, row):
+    """the operator against RANSAC + finish on one set of operands, then verify_candidates under both methods"""
+    from egonn_amd import registration as reg
+    dev = qf.device
+    base = ea.verify_candidates(qf, qk, qn, km, nn, ransac_max_it=H)          # its buffers hold corr / n_corr / pair_ids
+    spec = ea.verify_candidates(qf, qk, qn, km, nn, method="spectral")
+    torch.cuda.synchronize()
+    Q, k = nn.shape
+    P, nk = Q * k, qf.shape[1]
+    # the keypoint operands of all P pairs at once (verify_candidates gathers them chunk by chunk)
+    kp1, kp2 = (torch.empty((P, nk, 3), dtype=torch.float32, device=dev) for _ in range(2))
+    n1, n2, pids = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
+    _lib.call(dev, lib.egonn_gather_candidates, qk.data_ptr(), qn.data_ptr(), km.keypoints.data_ptr(), km.counts.data_ptr(),
+              nn.data_ptr(), None, Q, k, len(km), nk, kp1.data_ptr(), kp2.data_ptr(), n1.data_ptr(), n2.data_ptr(), pids.data_ptr())
+    ops = (kp1.data_ptr(), kp2.data_ptr(), n1.data_ptr(), n2.data_ptr(), base["corr"].data_ptr(), base["n_corr"].data_ptr())
+    scr_r = _lib.scratch(lib.egonn_registration_scratch_bytes(P, nk, H), dev)
+    scr_s = _lib.scratch(lib.egonn_spectral_verify_scratch_bytes(P, nk), dev)
+    flat = lambda d, names: {n: d[key].reshape(P, *d[key].shape[2:]) for n, key in names if key in d}      # noqa: E731
+    out_r = flat(base, (("T", "T"), ("inliers", "inliers"), ("fitness", "fitness"), ("inlier_rmse", "inlier_rmse"),
+                        ("best_t", "best_t"), ("status", "pair_status")))
+    out_s = flat(spec, (("T", "T"), ("inliers", "inliers"), ("fitness", "fitness"), ("inlier_rmse", "inlier_rmse"),
+                        ("status", "pair_status"), ("eigenvalue", "eigenvalue"), ("score", "score"), ("weights", "weights"),
+                        ("n_seeds", "n_seeds")))
+    pid = pids.data_ptr()
+
+    def ransac():
+        reg.enqueue_ransac(dev, (*ops, pid), P, nk, H, 0, 0.5, scr_r, None, 0.5, out_r)
+
+    def spectral():
+        reg.enqueue_spectral(dev, ops, P, nk, reg.SPECTRAL_D_THR, reg.SPECTRAL_ITERATIONS, reg.SPECTRAL_SEED_RATIO, 0.5,
+                             scr_s, None, 0.5, out_s)
+
+    reps, burst = (7, 2) if P >= 1024 else (10, 40)
+    row["operator_us"] = t = _time_alternated({"ransac_plus_finish": ransac, "spectral_verify": spectral}, 3, reps, burst)
+    row["operator_ranges_overlap"] = _overlap(t["ransac_plus_finish"], t["spectral_verify"])
+
+    def verify_ransac():
+        ea.verify_candidates(qf, qk, qn, km, nn, ransac_max_it=H, out=base)
+
+    def verify_spectral():
+        ea.verify_candidates(qf, qk, qn, km, nn, method="spectral", out=spec)
+
+    reps, burst = (5, 2) if P >= 1024 else (8, 10)
+    row["verify_candidates_us"] = t = _time_alternated({"ransac": verify_ransac, "spectral": verify_spectral}, 2, reps, burst)
+    row["verify_candidates_ranges_overlap"] = _overlap(t["ransac"], t["spectral"])
+    torch.cuda.synchronize()
+    row["verified_share"] = {"ransac": float((base["best_index"] >= 0).float().mean()),
+                             "spectral": float((spec["best_index"] >= 0).float().mean())}
+    row["rank0_won"] = {"ransac": float((base["best_rank"] == 0).float().mean()),
+                               "spectral": float((spec["best_rank"] == 0).float().mean())}
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
@@ -60,6 +122,7 @@ def main():
     ap.add_argument("--map_scans", type=int, default=32)
     ap.add_argument("--scan_points", type=int, default=50000)
     ap.add_argument("--skip_localize", action="store_true")
+    ap.add_argument("--spectral", action="store_true", help="time only the spectral check against RANSAC and append the rows")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "timing needs an MI355X"
     import __graft_entry__ as g
@@ -94,6 +157,11 @@ def main():
         scratch, scratch2 = _lib.scratch(nb, "cuda"), _lib.scratch(nb, "cuda")
         bank_f, bank_n = km.descriptors, km.counts
         st = _lib._stream()
+        if args.spectral:
+            rows.append(_spectral_row(ea, _lib, lib, km, qf, qk, qn, nn, H, {"queries": Q, "k": k, "pairs": P, "n_k": nk, "dim": D,
+                                                                            "map_entries": M, "hypotheses": H}))
+            print(json.dumps(rows[-1]), flush=True)
+            continue
         flat = nn.reshape(-1).long()
         qidx = torch.arange(Q, device="cuda").repeat_interleave(k)
 
@@ -129,6 +197,16 @@ def main():
         row["hypotheses"] = H
         rows.append(row)
         print(json.dumps(row), flush=True)
+
+    if args.spectral:
+        out = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        for row in rows:
+            row.update(device=torch.cuda.get_device_name(0), commit=args.commit)
+        out.setdefault("spectral_rows", []).extend(rows)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+        return
 
     loc = []
     if not args.skip_localize:
