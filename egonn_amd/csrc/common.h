@@ -361,6 +361,7 @@ static constexpr int KP_MAX_D = 256;             // descriptor width
 static constexpr int KP_MAX_PAIRS = 1 << 20;     // pairs per call
 static constexpr int REL_MAX_K = 1024;           // candidates per query
 int reg_check_shape(const char* who, int P, int n_max);                     // registration.hip
+int reg_check_threshold(const char* who, const char* what, double th, bool zero_ok);   // registration.hip: "<who>: bad <what> threshold"
 int rel_check_shape(const char* who, int Q, int k, int M, int n_max);       // relocalize.hip
 
 // ------------------------------------------------------------------ sort.hip

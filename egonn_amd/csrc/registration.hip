@@ -8,8 +8,9 @@
 //   1. egonn_match_mutual (match.hip)  the mutual nearest neighbours of the two descriptor sets, compacted in ascending i.
 //   2. reg_ransac_kernel  hypothesis t = 0 .. H-1, one lane each (see reg_hypothesis below); per workgroup the best
 //                         (inliers, err2, t) goes to scratch.
-//   3. reg_finish_kernel  best over the workgroups' records, the winner's transform again (same code, same bits), the
-//                         final evaluation over ALL source keypoints, and the metrics against a caller's T_gt.
+//   3. reg_finish_kernel  best over the workgroups' records, the winner's transform again (same code, same bits), then
+//                         pair_tail (pair_eval.h, shared with spectral.hip): the final evaluation over ALL source
+//                         keypoints and the metrics against a caller's T_gt.
 //
 // Two deliberate differences from Open3D: (a) Open3D stops early by its 0.999 confidence rule, here every one of the H
 // hypotheses is evaluated (a superset of what Open3D tries); (b) Open3D draws from a thread-dependent generator, here a
@@ -32,6 +33,7 @@
 // transform the finish kernel recomputes is the one the hot loop scored.
 #include "../../include/egonn_hip.h"
 #include "common.h"
+#include "pair_eval.h"
 
 #pragma clang fp contract(off)
 
@@ -61,23 +63,11 @@ __device__ static inline bool reg_better(int c1, double e1, int t1, int c2, doub
 }
 
 // ------------------------------------------------------------------ shared geometry
-// Correspondence coordinates of one pair into LDS as fp64, centred on the centroids of the correspondences' source / target
-// points (sums in ascending correspondence order by one lane per coordinate: a fixed order).  s_c[0..2] = source x, y, z,
-// s_c[3..5] = target; s_cent[0..5] the centroids.  Indices are clamped: nothing is read by an unchecked index.
-__device__ static int reg_load_corr(const float* __restrict__ kp1, const float* __restrict__ kp2, int m1, int m2,
-                                    const int32_t* __restrict__ corr, int nc_raw, int n_max, double (*s_c)[KP_MAX_N],
-                                    double* s_cent) {
+// RANSAC works on centred coordinates: the correspondences' points that pair_load_corr (pair_eval.h) put into s_c, centred on
+// the centroids of their source / target points (sums in ascending correspondence order by one lane per coordinate: a fixed
+// order).  s_cent[0..2] = the source centroid, s_cent[3..5] = the target's.  Called behind the barrier that follows the load.
+__device__ static void reg_centre(double (*s_c)[KP_MAX_N], int nc, double* s_cent) {
   const int t = threadIdx.x;
-  const int nc = (m1 == 0 || m2 == 0) ? 0 : clipi(nc_raw, n_max);
-  if (t < nc) {
-    const int i = clipi(corr[2 * t], m1 - 1), j = clipi(corr[2 * t + 1], m2 - 1);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      s_c[k][t] = (double)kp1[i * 3 + k];
-      s_c[3 + k][t] = (double)kp2[j * 3 + k];
-    }
-  }
-  __syncthreads();
   if (t < 6) {
     double s = 0.0;
     for (int c = 0; c < nc; ++c) s += s_c[t][c];
@@ -89,7 +79,6 @@ __device__ static int reg_load_corr(const float* __restrict__ kp1, const float* 
     for (int k = 0; k < 6; ++k) s_c[k][t] -= s_cent[k];
   }
   __syncthreads();
-  return nc;
 }
 
 __device__ static inline void reg_cross(const double* a, const double* b, double* o) {
@@ -98,15 +87,6 @@ __device__ static inline void reg_cross(const double* a, const double* b, double
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
 __device__ static inline double reg_dot(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-// |R s + tv - q|^2
-__device__ static inline double reg_res2(const double* R, const double* tv, double sx, double sy, double sz, double qx,
-                                         double qy, double qz) {
-  const double dx = R[0] * sx + R[1] * sy + R[2] * sz + tv[0] - qx;
-  const double dy = R[3] * sx + R[4] * sy + R[5] * sz + tv[1] - qy;
-  const double dz = R[6] * sx + R[7] * sy + R[8] * sz + tv[2] - qz;
-  return dx * dx + dy * dy + dz * dz;
-}
 
 // One hypothesis on the centred correspondences in LDS.  Returns 0 = accepted (R row-major and tv, in centred coordinates),
 // -1 = degenerate draw (a repeated correspondence, or a source or target triangle with |e1 x e2| <= 1e-3 |e1| |e2|),
@@ -206,7 +186,7 @@ __device__ static int reg_hypothesis(const double (*s_c)[KP_MAX_N], int nc, uint
   for (int r = 0; r < 3; ++r) tv[r] = ct[r] - (R[r * 3] * cs[0] + R[r * 3 + 1] * cs[1] + R[r * 3 + 2] * cs[2]);
 #pragma unroll
   for (int k = 0; k < 3; ++k)
-    if (!(reg_res2(R, tv, S[k][0], S[k][1], S[k][2], Q[k][0], Q[k][1], Q[k][2]) <= th2)) return -3;
+    if (!(pair_res2(R, tv, S[k][0], S[k][1], S[k][2], Q[k][0], Q[k][1], Q[k][2]) <= th2)) return -3;
   return 0;
 }
 
@@ -242,8 +222,10 @@ __global__ __launch_bounds__(REG_WG) void reg_ransac_kernel(const float* __restr
   __shared__ double s_e[4];
   const int p = blockIdx.x / chunks, chunk = blockIdx.x % chunks, t = chunk * REG_WG + (int)threadIdx.x;
   const int m1 = clipi(n1[p], n_max), m2 = clipi(n2[p], n_max);
-  const int nc = reg_load_corr(kp1 + (size_t)p * n_max * 3, kp2 + (size_t)p * n_max * 3, m1, m2, corr + (size_t)p * n_max * 2,
-                               n_corr[p], n_max, s_c, s_cent);
+  const int nc = pair_nc(m1, m2, n_corr[p], n_max);
+  pair_load_corr(kp1 + (size_t)p * n_max * 3, kp2 + (size_t)p * n_max * 3, m1, m2, corr + (size_t)p * n_max * 2, nc, s_c);
+  __syncthreads();
+  reg_centre(s_c, nc, s_cent);
   const uint32_t pid = pair_id ? (uint32_t)pair_id[p] & 0x3fffffffu : (uint32_t)p;
   int cnt = -1, code = -1;
   double err2 = 0.0;
@@ -253,7 +235,7 @@ __global__ __launch_bounds__(REG_WG) void reg_ransac_kernel(const float* __restr
     if (code == 0) {
       cnt = 0;
       for (int c = 0; c < nc; ++c) {   // every lane reads the same correspondence: LDS broadcast
-        const double d2 = reg_res2(R, tv, s_c[0][c], s_c[1][c], s_c[2][c], s_c[3][c], s_c[4][c], s_c[5][c]);
+        const double d2 = pair_res2(R, tv, s_c[0][c], s_c[1][c], s_c[2][c], s_c[3][c], s_c[4][c], s_c[5][c]);
         if (d2 < th2) {
           ++cnt;
           err2 += d2;
@@ -274,51 +256,44 @@ __global__ __launch_bounds__(REG_WG) void reg_ransac_kernel(const float* __restr
   }
 }
 
-// ------------------------------------------------------------------ 3. best hypothesis, final evaluation, metrics
-__global__ __launch_bounds__(REG_WG) void reg_finish_kernel(
-    const float* __restrict__ kp1, const float* __restrict__ kp2, const int32_t* __restrict__ n1, const int32_t* __restrict__ n2,
-    const int32_t* __restrict__ corr, const int32_t* __restrict__ n_corr, const int32_t* __restrict__ pair_id, int n_max, int H,
-    int chunks, uint64_t seed, double th2, const RegPartial* __restrict__ partial, const double* __restrict__ T_gt, double rth2,
-    double* __restrict__ T_out, int32_t* __restrict__ inliers, double* __restrict__ fitness, double* __restrict__ rmse,
-    int32_t* __restrict__ corr_set, int32_t* __restrict__ best_t, double* __restrict__ rte, double* __restrict__ rre,
-    int32_t* __restrict__ success, double* __restrict__ repeatability, int32_t* __restrict__ status) {
+// ------------------------------------------------------------------ 3. best hypothesis, then the tail of pair_eval.h
+struct RegFinishArgs {
+  PairIn in;
+  const int32_t* pair_id;
+  int H, chunks;
+  uint64_t seed;
+  const RegPartial* partial;
+  int32_t* best_t;
+  PairOut out;
+};
+
+__global__ __launch_bounds__(REG_WG) void reg_finish_kernel(const RegFinishArgs a) {
   __shared__ double s_c[6][KP_MAX_N];
   __shared__ double s_cent[6];
   __shared__ int s_cnt[4], s_t[4];
   __shared__ double s_e[4];
-  __shared__ double s_q[3][KP_MAX_N];   // target keypoints, fp64
-  __shared__ double s_d2[KP_MAX_N];
-  __shared__ int s_nn[KP_MAX_N];
-  const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int r1 = n1[p], r2 = n2[p];
-  const int m1 = clipi(r1, n_max), m2 = clipi(r2, n_max);
-  const float* k1 = kp1 + (size_t)p * n_max * 3;
-  const float* k2 = kp2 + (size_t)p * n_max * 3;
-  int st = (r1 != m1 || r2 != m2) ? EGONN_REG_STATUS_CLIPPED : 0;
+  __shared__ alignas(16) PairTailShared<REG_WG> s_tail;   // the search reads two targets per 128-bit LDS load
+  const int p = blockIdx.x, t = threadIdx.x;
+  const PairView v = pair_view(a.in, p);
+  int st = v.st;
 
-  // T = identity unless a hypothesis was accepted (Open3D returns the identity result when nothing beats fitness 0)
-  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tf[3] = {0, 0, 0};
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tf[3] = {0, 0, 0};   // T = identity unless a hypothesis was accepted
   int bt = -1;
-  if (corr) {
-    const int32_t* cp = corr + (size_t)p * n_max * 2;
-    const int nc_raw = n_corr[p];
-    const int nc = reg_load_corr(k1, k2, m1, m2, cp, nc_raw, n_max, s_c, s_cent);
-    if (nc_raw != nc) st |= EGONN_REG_STATUS_CLIPPED;
-    bool bad = false;
-    if (t < nc) bad = cp[2 * t] < 0 || cp[2 * t] >= m1 || cp[2 * t + 1] < 0 || cp[2 * t + 1] >= m2;
-    if (__syncthreads_or(bad)) st |= EGONN_REG_STATUS_BAD_INDEX;
-    if (nc < 3) st |= EGONN_REG_STATUS_FEW_CORR;
+  if (v.cp) {
+    const int nc = v.nc;
+    st = pair_load_corr_status(v, s_c);   // ends in a barrier
+    reg_centre(s_c, nc, s_cent);
     int cnt = -1, ct = 0x7fffffff;
     double e = 0.0;
-    for (int c = t; c < chunks; c += REG_WG) {
-      const RegPartial r = partial[(size_t)p * chunks + c];
+    for (int c = t; c < a.chunks; c += REG_WG) {
+      const RegPartial r = a.partial[(size_t)p * a.chunks + c];
       if (reg_better(r.cnt, r.err2, r.t, cnt, e, ct)) cnt = r.cnt, e = r.err2, ct = r.t;
     }
     reg_block_best(cnt, e, ct, s_cnt, s_t, s_e);
-    if (nc >= 3 && cnt > 0 && ct >= 0 && ct < H) {
-      const uint32_t pid = pair_id ? (uint32_t)pair_id[p] & 0x3fffffffu : (uint32_t)p;
+    if (nc >= 3 && cnt > 0 && ct >= 0 && ct < a.H) {
+      const uint32_t pid = a.pair_id ? (uint32_t)a.pair_id[p] & 0x3fffffffu : (uint32_t)p;
       double tv[3];
-      if (reg_hypothesis(s_c, nc, seed, pid, (uint32_t)ct, th2, R, tv) == 0) {   // every lane: the same bits
+      if (reg_hypothesis(s_c, nc, a.seed, pid, (uint32_t)ct, a.in.th2, R, tv) == 0) {   // every lane: the same bits
         bt = ct;
 #pragma unroll
         for (int r = 0; r < 3; ++r)   // centred -> caller's coordinates
@@ -328,100 +303,20 @@ __global__ __launch_bounds__(REG_WG) void reg_finish_kernel(
         for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
       }
     }
-    if (bt < 0) st |= EGONN_REG_STATUS_NO_MODEL;
+    if (t == 0 && a.best_t) a.best_t[p] = bt;
   }
-
-  if (t < m2) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s_q[k][t] = (double)k2[t * 3 + k];
-  }
-  __syncthreads();
-  double sx = 0.0, sy = 0.0, sz = 0.0;
-  if (t < m1) sx = (double)k1[t * 3], sy = (double)k1[t * 3 + 1], sz = (double)k1[t * 3 + 2];
-
-  if (corr) {
-    // final evaluation: every source keypoint under T, nearest target keypoint (ties: lowest index) closer than dist_th
-    double bd = INFINITY;
-    int bj = -1;
-    if (t < m1 && bt >= 0) {
-      const double px = R[0] * sx + R[1] * sy + R[2] * sz + tf[0], py = R[3] * sx + R[4] * sy + R[5] * sz + tf[1],
-                   pz = R[6] * sx + R[7] * sy + R[8] * sz + tf[2];
-      for (int j = 0; j < m2; ++j) {
-        const double dx = px - s_q[0][j], dy = py - s_q[1][j], dz = pz - s_q[2][j];
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        if (d2 < bd) bd = d2, bj = j;
-      }
-    }
-    s_d2[t] = bd;
-    s_nn[t] = bj;
-    __syncthreads();
-    if (t == 0) {
-      int k = 0;
-      double e2 = 0.0;
-      int32_t* cs = corr_set ? corr_set + (size_t)p * n_max * 2 : nullptr;
-      for (int i = 0; i < m1; ++i)   // ascending i: a fixed summation order
-        if (s_nn[i] >= 0 && s_d2[i] < th2) {
-          if (cs) cs[2 * k] = i, cs[2 * k + 1] = s_nn[i];
-          e2 += s_d2[i];
-          ++k;
-        }
-      if (cs)
-        for (int c = k; c < n_max; ++c) cs[2 * c] = cs[2 * c + 1] = -1;
-      inliers[p] = k;
-      fitness[p] = m1 > 0 ? (double)k / (double)m1 : 0.0;
-      rmse[p] = k > 0 ? sqrt(e2 / (double)k) : 0.0;
-      if (best_t) best_t[p] = bt;
-      double* To = T_out + (size_t)p * 16;
-      for (int r = 0; r < 3; ++r) {
-        To[r * 4] = R[r * 3], To[r * 4 + 1] = R[r * 3 + 1], To[r * 4 + 2] = R[r * 3 + 2], To[r * 4 + 3] = tf[r];
-      }
-      To[12] = To[13] = To[14] = 0.0, To[15] = 1.0;
-    }
-  }
-
-  if (T_gt) {
-    const double* G = T_gt + (size_t)p * 16;
-    // calculate_repeatability: share of source keypoints with a target keypoint within the threshold under T_gt (fp64)
-    bool rep = false;
-    if (t < m1) {
-      const double px = G[0] * sx + G[1] * sy + G[2] * sz + G[3], py = G[4] * sx + G[5] * sy + G[6] * sz + G[7],
-                   pz = G[8] * sx + G[9] * sy + G[10] * sz + G[11];
-      double bd = INFINITY;
-      for (int j = 0; j < m2; ++j) {
-        const double dx = px - s_q[0][j], dy = py - s_q[1][j], dz = pz - s_q[2][j];
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        if (d2 < bd) bd = d2;
-      }
-      rep = bd <= rth2;
-    }
-    const unsigned long long bal = __ballot(rep);
-    __syncthreads();
-    if (lane == 0) s_cnt[w] = __popcll(bal);
-    __syncthreads();
-    if (t == 0) {
-      const int nrep = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-      if (repeatability) repeatability[p] = m1 > 0 ? (double)nrep / (double)m1 : 0.0;
-      if (corr) {
-        const double dx = tf[0] - G[3], dy = tf[1] - G[7], dz = tf[2] - G[11];
-        const double e_t = sqrt(dx * dx + dy * dy + dz * dz);
-        double tr = 0.0;   // trace(R_est^T R_gt) = sum of the elementwise products
-        for (int r = 0; r < 3; ++r)
-          for (int c = 0; c < 3; ++c) tr += R[r * 3 + c] * G[r * 4 + c];
-        double cosv = (tr - 1.0) / 2.0;
-        cosv = cosv < -1.0 ? -1.0 : (cosv > 1.0 ? 1.0 : cosv);
-        const double e_r = acos(cosv) * 180.0 / 3.14159265358979323846;
-        if (rte) rte[p] = e_t;
-        if (rre) rre[p] = e_r;
-        if (success) success[p] = (e_t > 2.0 || e_r > 5.0) ? 0 : 1;
-      }
-    }
-  }
-  if (t == 0 && status) status[p] = st;
+  pair_tail<REG_WG>(a.in, a.out, p, v, v.cp != nullptr, bt >= 0, R, tf, st, s_tail);
 }
 
 int reg_check_shape(const char* who, int P, int n_max) {
   EGONN_REQUIRE(P >= 0 && P <= KP_MAX_PAIRS && n_max >= 1 && n_max <= KP_MAX_N, EGONN_ERR_INVALID,
                 "%s: bad shape (P=%d, n_max=%d; n_max <= %d)", who, P, n_max, KP_MAX_N);
+  return EGONN_OK;
+}
+
+// dist_th in (0, 1e18), repeat_th in [0, 1e18): the kernels compare with the square
+int reg_check_threshold(const char* who, const char* what, double th, bool zero_ok) {
+  EGONN_REQUIRE((th > 0.0 || (zero_ok && th == 0.0)) && th < 1e18, EGONN_ERR_INVALID, "%s: bad %s threshold", who, what);
   return EGONN_OK;
 }
 
@@ -441,7 +336,7 @@ API int egonn_ransac_pairs(const float* kp1, const float* kp2, const int32_t* n1
   EGONN_TRY(reg_check_shape("ransac_pairs", n_pairs, n_max));
   EGONN_REQUIRE(n_hypotheses > 0, EGONN_ERR_INVALID, "ransac_pairs: n_hypotheses %d must be positive", n_hypotheses);
   EGONN_REQUIRE(kp1 && kp2 && n1 && n2 && corr && n_corr && scratch, EGONN_ERR_INVALID, "ransac_pairs: null pointer");
-  EGONN_REQUIRE(dist_th > 0.0 && dist_th < 1e18, EGONN_ERR_INVALID, "ransac_pairs: bad distance threshold");
+  EGONN_TRY(reg_check_threshold("ransac_pairs", "distance", dist_th, false));
   const int64_t chunks = cdiv(n_hypotheses, REG_WG);
   EGONN_REQUIRE(scratch_bytes >= egonn_registration_scratch_bytes(n_pairs, n_max, n_hypotheses) &&
                     ((uintptr_t)scratch & 7) == 0,
@@ -470,7 +365,7 @@ API int egonn_registration_finish(const float* kp1, const float* kp2, const int3
     EGONN_REQUIRE(n_hypotheses > 0, EGONN_ERR_INVALID, "registration_finish: n_hypotheses %d must be positive", n_hypotheses);
     EGONN_REQUIRE(n_corr && scratch && T && inliers && fitness && inlier_rmse, EGONN_ERR_INVALID,
                   "registration_finish: null pointer");
-    EGONN_REQUIRE(dist_th > 0.0 && dist_th < 1e18, EGONN_ERR_INVALID, "registration_finish: bad distance threshold");
+    EGONN_TRY(reg_check_threshold("registration_finish", "distance", dist_th, false));
     EGONN_REQUIRE(scratch_bytes >= egonn_registration_scratch_bytes(n_pairs, n_max, n_hypotheses) &&
                       ((uintptr_t)scratch & 7) == 0,
                   EGONN_ERR_INVALID, "registration_finish: scratch needs %lld bytes, 8-byte aligned",
@@ -480,12 +375,13 @@ API int egonn_registration_finish(const float* kp1, const float* kp2, const int3
     EGONN_REQUIRE(T_gt && repeatability, EGONN_ERR_INVALID,
                   "registration_finish: without correspondences only the T_gt metrics are computed: T_gt and repeatability needed");
   }
-  EGONN_REQUIRE(!T_gt || (repeat_th >= 0.0 && repeat_th < 1e18), EGONN_ERR_INVALID, "registration_finish: bad repeatability threshold");
+  if (T_gt) EGONN_TRY(reg_check_threshold("registration_finish", "repeatability", repeat_th, true));
   if (n_pairs == 0) return EGONN_OK;
-  hipLaunchKernelGGL(reg_finish_kernel, dim3((unsigned)n_pairs), dim3(REG_WG), 0, (hipStream_t)stream, kp1, kp2, n1, n2, corr, n_corr,
-                     pair_id, n_max, n_hypotheses, chunks, seed, dist_th * dist_th, (const RegPartial*)scratch, T_gt,
-                     repeat_th * repeat_th, T, inliers, fitness, inlier_rmse, corr_set, best_t, rte, rre, success, repeatability,
-                     status);
+  RegFinishArgs a;
+  a.in = PairIn{kp1, kp2, n1, n2, corr, n_corr, n_max, dist_th * dist_th, repeat_th * repeat_th, T_gt};
+  a.pair_id = pair_id, a.H = n_hypotheses, a.chunks = chunks, a.seed = seed, a.partial = (const RegPartial*)scratch, a.best_t = best_t;
+  a.out = PairOut{T, inliers, fitness, inlier_rmse, corr_set, rte, rre, success, repeatability, status};
+  hipLaunchKernelGGL(reg_finish_kernel, dim3((unsigned)n_pairs), dim3(REG_WG), 0, (hipStream_t)stream, a);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }

@@ -10,8 +10,9 @@
 //      a 64-lane xor butterfly (32, 16, .. 1) and then the waves' sums in ascending wave order.  No float atomics.
 //   3. score = eigenvalue / (n_max - 1) (0 when n_max = 1).
 //   4. seeds S = { i : v_i >= seed_ratio * max v }.
-//   5. T0 = rigid fit of S; I = { i : |T0 p_i - q_i| < dist_th }; T = rigid fit of I; then the final evaluation and the metrics
-//      of egonn_registration_finish under T (every source keypoint against its nearest target keypoint; registration.hip).
+//   5. T0 = rigid fit of S; I = { i : |T0 p_i - q_i| < dist_th }; T = rigid fit of I; then pair_tail (pair_eval.h), the text
+//      egonn_registration_finish ends with: the final evaluation under T (every source keypoint against its nearest target
+//      keypoint) and the metrics.
 //   6. m < 3: FEW_CORR.  M = 0 (|u| = 0 can only happen in the first iteration: M is symmetric, so M (M w) = 0 implies M w = 0),
 //      |S| < 3, |I| < 3 or a degenerate fit: NO_MODEL.  Both: T = identity, 0 inliers.
 //
@@ -29,6 +30,7 @@
 #include "../../include/egonn_hip.h"
 #include "common.h"
 #include "horn.h"
+#include "pair_eval.h"
 
 #pragma clang fp contract(off)
 
@@ -40,32 +42,21 @@ static constexpr int SPV_NRED = 21;        // widest reduction: 9 cross-covarian
 static constexpr double SPV_DEGEN = 1e-10;
 
 struct SpvArgs {
-  const float *kp1, *kp2;
-  const int32_t *n1, *n2, *corr, *n_corr;
-  int n_pairs, n_max, iterations;
-  double inv_thr2, seed_ratio, th2, rth2;
-  const double* T_gt;
+  PairIn in;
+  int n_pairs, iterations;
+  double inv_thr2, seed_ratio;
   float* slab;
   double *eigenvalue, *score, *weights;
   int32_t* n_seeds;
-  double* T;
-  int32_t* inliers;
-  double *fitness, *rmse;
-  int32_t* corr_set;
-  double *rte, *rre;
-  int32_t* success;
-  double* repeatability;
-  int32_t* status;
+  PairOut out;
 };
 
 template <int NT>
 struct SpvShared {
   double c[6][NT];             // the correspondences' points: source x, y, z, target x, y, z
-  double q[3][NT];             // every target keypoint (final evaluation, repeatability)
   double v[NT];
-  double d2[NT];
-  int nn[NT];
   double red[SPV_NRED][NT / 64];
+  PairTailShared<NT> tail;
 };
 
 // x[k] summed over the workgroup, for k < K: butterfly inside a wave, then the waves in ascending order.  Valid in every lane.
@@ -110,15 +101,6 @@ __device__ static inline bool spv_spread(const double* c) {
   const double tr = c[0] + c[3] + c[5];
   const double e2 = (c[0] * c[3] - c[1] * c[1]) + (c[0] * c[5] - c[2] * c[2]) + (c[3] * c[5] - c[4] * c[4]);
   return e2 > SPV_DEGEN * (tr * tr);
-}
-
-// |R s + tv - q|^2
-__device__ static inline double spv_res2(const double* R, const double* tv, double sx, double sy, double sz, double qx, double qy,
-                                         double qz) {
-  const double dx = R[0] * sx + R[1] * sy + R[2] * sz + tv[0] - qx;
-  const double dy = R[3] * sx + R[4] * sy + R[5] * sz + tv[1] - qy;
-  const double dz = R[6] * sx + R[7] * sy + R[8] * sz + tv[2] - qz;
-  return dx * dx + dy * dy + dz * dz;
 }
 
 // Least-squares rigid transform (no scale, det +1) of the correspondences whose lane passes `in`.  Called by the whole
@@ -166,36 +148,12 @@ __device__ static bool spv_fit(SpvShared<NT>& sh, bool in, double* R, double* tv
 // One pair by the whole workgroup.  row = this lane's row of M, element j at row[j * rs].
 template <int NT>
 __device__ static void spv_pair(const SpvArgs& a, int p, float* __restrict__ row, int rs, SpvShared<NT>& sh) {
-  const int t = threadIdx.x, n_max = a.n_max;
-  const int r1 = a.n1[p], r2 = a.n2[p];
-  const int m1 = clipi(r1, n_max), m2 = clipi(r2, n_max);
-  const float* k1 = a.kp1 + (size_t)p * n_max * 3;
-  const float* k2 = a.kp2 + (size_t)p * n_max * 3;
-  const int32_t* cp = a.corr + (size_t)p * n_max * 2;
-  const int nc_raw = a.n_corr[p];
-  const int nc = (m1 == 0 || m2 == 0) ? 0 : clipi(nc_raw, n_max);
-  int st = (r1 != m1 || r2 != m2 || nc_raw != nc) ? EGONN_REG_STATUS_CLIPPED : 0;
-
-  // the correspondences' points (indices clamped: nothing is read by an unchecked index) and every target keypoint
-  bool bad = false;
-  if (t < nc) {
-    const int ci = cp[2 * t], cj = cp[2 * t + 1];
-    bad = ci < 0 || ci >= m1 || cj < 0 || cj >= m2;
-    const int i = clipi(ci, m1 - 1), j = clipi(cj, m2 - 1);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      sh.c[k][t] = (double)k1[i * 3 + k];
-      sh.c[3 + k][t] = (double)k2[j * 3 + k];
-    }
-  }
-  if (t < m2) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sh.q[k][t] = (double)k2[t * 3 + k];
-  }
+  const int t = threadIdx.x, n_max = a.in.n_max;
+  const PairView pv = pair_view(a.in, p);
+  const int nc = pv.nc;
   const double v0 = nc > 0 ? 1.0 / sqrt((double)nc) : 0.0;
   sh.v[t] = t < nc ? v0 : 0.0;
-  if (__syncthreads_or(bad)) st |= EGONN_REG_STATUS_BAD_INDEX;
-  if (nc < 3) st |= EGONN_REG_STATUS_FEW_CORR;
+  const int st = pair_load_corr_status(pv, sh.c);   // the correspondences' points; its barrier covers v as well
 
   // 1. this lane's row of M
   double pc[6] = {0, 0, 0, 0, 0, 0};
@@ -241,7 +199,7 @@ __device__ static void spv_pair(const SpvArgs& a, int p, float* __restrict__ row
   if (nc >= 3 && !zero) {
     double R0[9], t0[3];
     if (spv_fit<NT>(sh, seed, R0, t0)) {
-      const bool in = t < nc && spv_res2(R0, t0, pc[0], pc[1], pc[2], pc[3], pc[4], pc[5]) < a.th2;
+      const bool in = t < nc && pair_res2(R0, t0, pc[0], pc[1], pc[2], pc[3], pc[4], pc[5]) < a.in.th2;
       model = spv_fit<NT>(sh, in, R0, t0);
       if (model) {
 #pragma unroll
@@ -251,83 +209,13 @@ __device__ static void spv_pair(const SpvArgs& a, int p, float* __restrict__ row
       }
     }
   }
-  if (!model) st |= EGONN_REG_STATUS_NO_MODEL;
-
-  // final evaluation, as egonn_registration_finish: every source keypoint under T, nearest target keypoint (ties: lowest
-  // index) closer than dist_th
-  double sx = 0.0, sy = 0.0, sz = 0.0;
-  if (t < m1) sx = (double)k1[t * 3], sy = (double)k1[t * 3 + 1], sz = (double)k1[t * 3 + 2];
-  double bd = INFINITY;
-  int bj = -1;
-  if (t < m1 && model) {
-    const double px = R[0] * sx + R[1] * sy + R[2] * sz + tf[0], py = R[3] * sx + R[4] * sy + R[5] * sz + tf[1],
-                 pz = R[6] * sx + R[7] * sy + R[8] * sz + tf[2];
-    for (int j = 0; j < m2; ++j) {
-      const double dx = px - sh.q[0][j], dy = py - sh.q[1][j], dz = pz - sh.q[2][j];
-      const double d2 = dx * dx + dy * dy + dz * dz;
-      if (d2 < bd) bd = d2, bj = j;
-    }
-  }
-  sh.d2[t] = bd;
-  sh.nn[t] = bj;
-  __syncthreads();
   if (t == 0) {
-    int k = 0;
-    double e2 = 0.0;
-    int32_t* cs = a.corr_set ? a.corr_set + (size_t)p * n_max * 2 : nullptr;
-    for (int i = 0; i < m1; ++i)   // ascending i: a fixed summation order
-      if (sh.nn[i] >= 0 && sh.d2[i] < a.th2) {
-        if (cs) cs[2 * k] = i, cs[2 * k + 1] = sh.nn[i];
-        e2 += sh.d2[i];
-        ++k;
-      }
-    if (cs)
-      for (int c = k; c < n_max; ++c) cs[2 * c] = cs[2 * c + 1] = -1;
-    if (a.inliers) a.inliers[p] = k;
-    if (a.fitness) a.fitness[p] = m1 > 0 ? (double)k / (double)m1 : 0.0;
-    if (a.rmse) a.rmse[p] = k > 0 ? sqrt(e2 / (double)k) : 0.0;
-    if (a.T) {
-      double* To = a.T + (size_t)p * 16;
-      for (int r = 0; r < 3; ++r) To[r * 4] = R[r * 3], To[r * 4 + 1] = R[r * 3 + 1], To[r * 4 + 2] = R[r * 3 + 2], To[r * 4 + 3] = tf[r];
-      To[12] = To[13] = To[14] = 0.0, To[15] = 1.0;
-    }
     if (a.eigenvalue) a.eigenvalue[p] = lam;
     if (a.score) a.score[p] = n_max > 1 ? lam / (double)(n_max - 1) : 0.0;
     if (a.n_seeds) a.n_seeds[p] = n_seeds;
-    if (a.status) a.status[p] = st;
   }
   if (a.weights && t < n_max) a.weights[(size_t)p * n_max + t] = vt;
-
-  if (a.T_gt) {   // the metrics of egonn_registration_finish against the caller's pose
-    const double* G = a.T_gt + (size_t)p * 16;
-    bool rep = false;
-    if (t < m1) {
-      const double px = G[0] * sx + G[1] * sy + G[2] * sz + G[3], py = G[4] * sx + G[5] * sy + G[6] * sz + G[7],
-                   pz = G[8] * sx + G[9] * sy + G[10] * sz + G[11];
-      double gd = INFINITY;
-      for (int j = 0; j < m2; ++j) {
-        const double dx = px - sh.q[0][j], dy = py - sh.q[1][j], dz = pz - sh.q[2][j];
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        if (d2 < gd) gd = d2;
-      }
-      rep = gd <= a.rth2;
-    }
-    const int nrep = __syncthreads_count(rep);
-    if (t == 0) {
-      if (a.repeatability) a.repeatability[p] = m1 > 0 ? (double)nrep / (double)m1 : 0.0;
-      const double dx = tf[0] - G[3], dy = tf[1] - G[7], dz = tf[2] - G[11];
-      const double e_t = sqrt(dx * dx + dy * dy + dz * dz);
-      double tr = 0.0;   // trace(R_est^T R_gt) = sum of the elementwise products
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) tr += R[r * 3 + c] * G[r * 4 + c];
-      double cosv = (tr - 1.0) / 2.0;
-      cosv = cosv < -1.0 ? -1.0 : (cosv > 1.0 ? 1.0 : cosv);
-      const double e_r = acos(cosv) * 180.0 / 3.14159265358979323846;
-      if (a.rte) a.rte[p] = e_t;
-      if (a.rre) a.rre[p] = e_r;
-      if (a.success) a.success[p] = (e_t > 2.0 || e_r > 5.0) ? 0 : 1;
-    }
-  }
+  pair_tail<NT>(a.in, a.out, p, pv, true, model, R, tf, st, sh.tail);
 }
 
 template <int NT, bool LDS_M>
@@ -335,8 +223,8 @@ __global__ __launch_bounds__(NT) void spectral_kernel(const SpvArgs a) {
   extern __shared__ float s_m[];   // LDS_M: NT rows of NT + 1 words
   __shared__ SpvShared<NT> sh;
   const int t = threadIdx.x;
-  float* row = LDS_M ? s_m + t * (NT + 1) : a.slab + (size_t)blockIdx.x * a.n_max * a.n_max + t;
-  const int rs = LDS_M ? 1 : a.n_max;
+  float* row = LDS_M ? s_m + t * (NT + 1) : a.slab + (size_t)blockIdx.x * a.in.n_max * a.in.n_max + t;
+  const int rs = LDS_M ? 1 : a.in.n_max;
   for (int p = blockIdx.x; p < a.n_pairs; p += gridDim.x) {
     spv_pair<NT>(a, p, row, rs, sh);
     __syncthreads();   // the next pair overwrites the shared arrays
@@ -364,20 +252,17 @@ API int egonn_spectral_verify(const float* kp1, const float* kp2, const int32_t*
   EGONN_REQUIRE(d_thr > 0.0 && d_thr < 1e18, EGONN_ERR_INVALID, "spectral_verify: bad consistency threshold d_thr");
   EGONN_REQUIRE(iterations >= 1, EGONN_ERR_INVALID, "spectral_verify: iterations %d must be positive", iterations);
   EGONN_REQUIRE(seed_ratio > 0.0 && seed_ratio <= 1.0, EGONN_ERR_INVALID, "spectral_verify: seed_ratio must be in (0, 1]");
-  EGONN_REQUIRE(dist_th > 0.0 && dist_th < 1e18, EGONN_ERR_INVALID, "spectral_verify: bad distance threshold");
-  EGONN_REQUIRE(!T_gt || (repeat_th >= 0.0 && repeat_th < 1e18), EGONN_ERR_INVALID, "spectral_verify: bad repeatability threshold");
+  EGONN_TRY(reg_check_threshold("spectral_verify", "distance", dist_th, false));
+  if (T_gt) EGONN_TRY(reg_check_threshold("spectral_verify", "repeatability", repeat_th, true));
   const int64_t need = egonn_spectral_verify_scratch_bytes(n_pairs, n_max);
   EGONN_REQUIRE(need == 0 || (scratch && scratch_bytes >= need && ((uintptr_t)scratch & 7) == 0), EGONN_ERR_INVALID,
                 "spectral_verify: scratch needs %lld bytes, 8-byte aligned", (long long)need);
   if (n_pairs == 0) return EGONN_OK;
   SpvArgs a;
-  a.kp1 = kp1, a.kp2 = kp2, a.n1 = n1, a.n2 = n2, a.corr = corr, a.n_corr = n_corr;
-  a.n_pairs = n_pairs, a.n_max = n_max, a.iterations = iterations;
-  a.inv_thr2 = 1.0 / (d_thr * d_thr), a.seed_ratio = seed_ratio, a.th2 = dist_th * dist_th, a.rth2 = repeat_th * repeat_th;
-  a.T_gt = T_gt, a.slab = (float*)scratch;
-  a.eigenvalue = eigenvalue, a.score = score, a.weights = weights, a.n_seeds = n_seeds, a.T = T, a.inliers = inliers;
-  a.fitness = fitness, a.rmse = inlier_rmse, a.corr_set = corr_set, a.rte = rte, a.rre = rre, a.success = success;
-  a.repeatability = repeatability, a.status = status;
+  a.in = PairIn{kp1, kp2, n1, n2, corr, n_corr, n_max, dist_th * dist_th, repeat_th * repeat_th, T_gt};
+  a.n_pairs = n_pairs, a.iterations = iterations, a.inv_thr2 = 1.0 / (d_thr * d_thr), a.seed_ratio = seed_ratio;
+  a.slab = (float*)scratch, a.eigenvalue = eigenvalue, a.score = score, a.weights = weights, a.n_seeds = n_seeds;
+  a.out = PairOut{T, inliers, fitness, inlier_rmse, corr_set, rte, rre, success, repeatability, status};
   if (n_max <= SPV_LDS_N) {
     constexpr size_t lds = (size_t)SPV_LDS_N * (SPV_LDS_N + 1) * sizeof(float);
     static AttrOnce attr;

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import as_dev as _dev
+from .registration import check_method
 from .relocalize import KeypointMap, verify_candidates
 
 MAX_K = 64        # one list entry per lane of a wave (csrc/loop_closure.hip)
@@ -128,9 +129,7 @@ class LoopDetector:
                  verify: bool = True, min_inliers: int = 0, ransac_dist_th: float = 0.5, ransac_max_it: int = 10000, seed: int = 0,
                  n_k: int = 128, dim: int = 128, global_dim: int = 256, device=None, times=None, verify_method: str = "ransac"):
         _check_gaps("LoopDetector", k, min_time_gap, max_time_gap)
-        if verify_method not in ("ransac", "spectral"):
-            raise ValueError(f"LoopDetector: verify_method must be 'ransac' or 'spectral', got {verify_method!r}")
-        self.verify_method = verify_method
+        self.verify_method = check_method("LoopDetector(verify_method)", verify_method)
         self.kmap = KeypointMap(n_k, dim, global_dim, device) if kmap is None else kmap
         self.k, self.min_time_gap, self.max_time_gap = int(k), float(min_time_gap), float(max_time_gap)
         self.verify, self.min_inliers = bool(verify), int(min_inliers)

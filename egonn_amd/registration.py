@@ -76,30 +76,51 @@ def match_mutual(feat1: torch.Tensor, feat2: torch.Tensor, n1=None, n2=None, chu
     return corr, n_corr
 
 
-def enqueue_ransac(dev, operands, P, n_max, H, seed, dist_th, scratch, T_gt, repeat_th, out):
-    """egonn_ransac_pairs + egonn_registration_finish of P pairs.  operands: the pointers (kp1, kp2, n1, n2, corr, n_corr,
-    pair_id) both calls start with; scratch: `_lib.scratch` of egonn_registration_scratch_bytes; T_gt: (P,4,4) f64 tensor or
-    None; out: the outputs by the names of `register_pairs` (an absent one is not computed).  Nothing is allocated and
-    nothing synchronises, so the pair can be captured; the caller keeps the operands alive."""
-    lib = _lib.load()
-    p = lambda k: _lib._ptr(out.get(k))                                       # noqa: E731
-    head = (*operands, P, n_max, H, int(seed) & 0xFFFFFFFFFFFFFFFF, float(dist_th), scratch.data_ptr(), scratch.numel() * 8)
-    _lib.call(dev, lib.egonn_ransac_pairs, *head, p("hyp_count"), p("hyp_err2"))
-    _lib.call(dev, lib.egonn_registration_finish, *head, _lib._ptr(T_gt), float(repeat_th), p("T"), p("inliers"), p("fitness"),
-              p("inlier_rmse"), p("correspondence_set"), p("best_t"), p("rte"), p("rre"), p("success"), p("repeatability"),
-              p("status"))
-
-
 METHODS = ("ransac", "spectral")
 SPECTRAL_D_THR, SPECTRAL_ITERATIONS, SPECTRAL_SEED_RATIO = 0.6, 32, 0.5      # choices, not tuned values (`spectral_verify`)
-_SPECTRAL_OUT = ("eigenvalue", "score", "weights", "n_seeds", "T", "inliers", "fitness", "inlier_rmse", "correspondence_set",
-                 "rte", "rre", "success", "repeatability", "status")
+# The per-pair outputs of egonn_registration_finish and egonn_spectral_verify, in the order of the C prototypes: name, dtype,
+# trailing shape ("n" = n_max), only with T_gt, the method that owns it (None = both: PairOut of csrc/pair_eval.h).
+_F, _I = torch.float64, torch.int32
+PAIR_OUTPUTS = (
+    ("eigenvalue", _F, (), False, "spectral"), ("score", _F, (), False, "spectral"), ("weights", _F, ("n",), False, "spectral"),
+    ("n_seeds", _I, (), False, "spectral"),
+    ("T", _F, (4, 4), False, None), ("inliers", _I, (), False, None), ("fitness", _F, (), False, None),
+    ("inlier_rmse", _F, (), False, None), ("correspondence_set", _I, ("n", 2), False, None),
+    ("best_t", _I, (), False, "ransac"),
+    ("rte", _F, (), True, None), ("rre", _F, (), True, None), ("success", _I, (), True, None), ("repeatability", _F, (), True, None),
+    ("status", _I, (), False, None))
 
 
 def check_method(who, method):
     if method not in METHODS:
         raise ValueError(f"{who}: method must be one of {METHODS}, got {method!r}")
     return method
+
+
+def pair_outputs(method, with_gt=True, skip=()):
+    """the rows of PAIR_OUTPUTS that `method` writes, in the order its C entry point takes them"""
+    return tuple(r for r in PAIR_OUTPUTS if r[4] in (None, method) and (with_gt or not r[3]) and r[0] not in skip)
+
+
+def pair_buffers(dev, lead, n_max, with_gt, method, skip=()):
+    """{name: empty tensor of shape lead + trailing shape} for those rows"""
+    return {name: torch.empty((*lead, *(n_max if s == "n" else s for s in shape)), dtype=dt, device=dev)
+            for name, dt, shape, _, _ in pair_outputs(method, with_gt, skip)}
+
+
+def _out_ptrs(method, out):
+    return [_lib._ptr(out.get(r[0])) for r in pair_outputs(method)]
+
+
+def enqueue_ransac(dev, operands, P, n_max, H, seed, dist_th, scratch, T_gt, repeat_th, out):
+    """egonn_ransac_pairs + egonn_registration_finish of P pairs.  operands: the pointers (kp1, kp2, n1, n2, corr, n_corr,
+    pair_id) both calls start with; scratch: `_lib.scratch` of egonn_registration_scratch_bytes; T_gt: (P,4,4) f64 tensor or
+    None; out: the outputs by the names of `register_pairs` (an absent one is not computed).  Nothing is allocated and
+    nothing synchronises, so the pair can be captured; the caller keeps the operands alive."""
+    lib = _lib.load()
+    head = (*operands, P, n_max, H, int(seed) & 0xFFFFFFFFFFFFFFFF, float(dist_th), scratch.data_ptr(), scratch.numel() * 8)
+    _lib.call(dev, lib.egonn_ransac_pairs, *head, _lib._ptr(out.get("hyp_count")), _lib._ptr(out.get("hyp_err2")))
+    _lib.call(dev, lib.egonn_registration_finish, *head, _lib._ptr(T_gt), float(repeat_th), *_out_ptrs("ransac", out))
 
 
 def enqueue_spectral(dev, operands, P, n_max, d_thr, iterations, seed_ratio, dist_th, scratch, T_gt, repeat_th, out):
@@ -110,18 +131,7 @@ def enqueue_spectral(dev, operands, P, n_max, d_thr, iterations, seed_ratio, dis
     lib = _lib.load()
     _lib.call(dev, lib.egonn_spectral_verify, *operands, P, n_max, float(d_thr), int(iterations), float(seed_ratio),
               float(dist_th), _lib._ptr(T_gt), float(repeat_th), scratch.data_ptr(), scratch.numel() * 8,
-              *(_lib._ptr(out.get(k)) for k in _SPECTRAL_OUT))
-
-
-def _spectral_buffers(dev, P, n_max, with_gt):
-    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
-    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
-    out = {"eigenvalue": f64(P), "score": f64(P), "weights": f64(P, n_max), "n_seeds": i32(P), "T": f64(P, 4, 4),
-           "inliers": i32(P), "fitness": f64(P), "inlier_rmse": f64(P), "correspondence_set": i32(P, n_max, 2), "status": i32(P)}
-    if with_gt:
-        out.update({"rte": f64(P), "rre": f64(P), "success": i32(P), "repeatability": f64(P)})
-    out["_scratch"] = _lib.scratch(_lib.load().egonn_spectral_verify_scratch_bytes(P, n_max), dev)   # -1: the call raises
-    return out
+              *_out_ptrs("spectral", out))
 
 
 def spectral_verify(kp1, kp2, corr, n_corr, n1=None, n2=None, T_gt=None, d_thr: float = SPECTRAL_D_THR,
@@ -155,7 +165,8 @@ def spectral_verify(kp1, kp2, corr, n_corr, n1=None, n2=None, T_gt=None, d_thr: 
     c1, c2 = _counts(n1, P, n_max, dev), _counts(n2, P, n_max, dev)
     gt = None if T_gt is None else _dev(T_gt, dev, torch.float64).reshape(P, 4, 4)
     if out is None:
-        out = _spectral_buffers(dev, P, n_max, gt is not None)
+        out = pair_buffers(dev, (P,), n_max, gt is not None, "spectral")
+        out["_scratch"] = _lib.scratch(_lib.load().egonn_spectral_verify_scratch_bytes(P, n_max), dev)   # -1: the call raises
     elif "weights" not in out or tuple(out["weights"].shape) != (P, n_max) or ("rte" in out) != (gt is not None) or \
             out["weights"].device != dev:
         raise ValueError("spectral_verify: `out` was made by a call with other shapes")
@@ -198,14 +209,11 @@ def register_pairs(feat1, feat2, kp1, kp2, n1=None, n2=None, T_gt=None, ransac_d
     pid = None if pair_ids is None else _dev(pair_ids, dev, torch.int32)
     gt = None if T_gt is None else _dev(T_gt, dev, torch.float64).reshape(P, 4, 4)
     scratch = _lib.scratch(lib.egonn_registration_scratch_bytes(P, n_max, H), dev)   # -1 on bad arguments: the call raises
-    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
-    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
-    out = {"T": f64(P, 4, 4), "inliers": i32(P), "fitness": f64(P), "inlier_rmse": f64(P),
-           "correspondence_set": i32(P, n_max, 2), "best_t": i32(P), "status": i32(P), "corr": corr, "n_corr": n_corr}
-    if gt is not None:
-        out.update({"rte": f64(P), "rre": f64(P), "success": i32(P), "repeatability": f64(P)})
+    out = pair_buffers(dev, (P,), n_max, gt is not None, "ransac")
+    out.update(corr=corr, n_corr=n_corr)
     if debug:
-        out.update({"hyp_count": i32(P, max(H, 0)), "hyp_err2": f64(P, max(H, 0))})
+        out.update({"hyp_count": torch.empty((P, max(H, 0)), dtype=torch.int32, device=dev),
+                    "hyp_err2": torch.empty((P, max(H, 0)), dtype=torch.float64, device=dev)})
     enqueue_ransac(dev, (k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), corr.data_ptr(), n_corr.data_ptr(),
                          _lib._ptr(pid)), P, n_max, H, seed, ransac_dist_th, scratch, gt, repeat_dist_th, out)
     out["_keep"] = (k1, k2, c1, c2, pid, gt, scratch)      # inputs of enqueued work stay alive with the result
@@ -246,8 +254,7 @@ def repeatability_pairs(kp1, kp2, T, threshold: float, n1=None, n2=None) -> torc
     gt = _dev(T, dev, torch.float64).reshape(P, 4, 4)
     rep = torch.empty((P,), dtype=torch.float64, device=dev)
     _lib.call(dev, lib.egonn_registration_finish, k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(), None, None, None,
-              P, n_max, 0, 0, 0.0, None, 0, gt.data_ptr(), float(threshold), None, None, None, None, None, None, None, None,
-              None, rep.data_ptr(), None)
+              P, n_max, 0, 0, 0.0, None, 0, gt.data_ptr(), float(threshold), *_out_ptrs("ransac", {"repeatability": rep}))
     return rep
 
 
@@ -441,16 +448,11 @@ def _metrics_against(r, T_ref, n_max, ransac_max_it, seed, ransac_dist_th, repea
     k1, k2, c1, c2, pid, _, scratch = r["_keep"]
     dev, P = k1.device, k1.shape[0]
     ref = _dev(T_ref, dev, torch.float64).reshape(P, 4, 4)
-    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
-    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
-    out = {"T": f64(P, 4, 4), "inliers": i32(P), "fitness": f64(P), "inlier_rmse": f64(P), "rte": f64(P), "rre": f64(P),
-           "success": i32(P), "repeatability": f64(P)}
+    out = pair_buffers(dev, (P,), n_max, True, "ransac", skip=("correspondence_set", "best_t", "status"))
     _lib.call(dev, lib.egonn_registration_finish, k1.data_ptr(), k2.data_ptr(), c1.data_ptr(), c2.data_ptr(),
               r["corr"].data_ptr(), r["n_corr"].data_ptr(), _lib._ptr(pid), P, n_max, int(ransac_max_it),
               int(seed) & 0xFFFFFFFFFFFFFFFF, float(ransac_dist_th), scratch.data_ptr(), scratch.numel() * 8, ref.data_ptr(),
-              float(repeat_dist_th), out["T"].data_ptr(), out["inliers"].data_ptr(), out["fitness"].data_ptr(),
-              out["inlier_rmse"].data_ptr(), None, None, out["rte"].data_ptr(), out["rre"].data_ptr(),
-              out["success"].data_ptr(), out["repeatability"].data_ptr(), None)
+              float(repeat_dist_th), *_out_ptrs("ransac", out))
     out["_keep"] = (ref,)
     return out
 

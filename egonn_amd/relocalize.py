@@ -138,30 +138,27 @@ class KeypointMap:
         return m
 
 
+_NOT_KEPT = ("correspondence_set", "repeatability")     # per-pair outputs of `registration.PAIR_OUTPUTS` not computed per candidate
+
+
+def pair_keys(method):
+    """{name in `registration.PAIR_OUTPUTS`: per-pair key of `verify_candidates`}: `status` is the per-query word here"""
+    return {r[0]: "pair_status" if r[0] == "status" else r[0] for r in _reg.pair_outputs(method, skip=_NOT_KEPT)}
+
+
 def _verify_buffers(dev, Q, k, n_max, Pc, with_gt, nb_match, nb_reg, method="ransac"):
     f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
     i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)            # noqa: E731
-    own = {"best_t": i32(Q, k)} if method == "ransac" else \
-        {"eigenvalue": f64(Q, k), "score": f64(Q, k), "weights": f64(Q, k, n_max), "n_seeds": i32(Q, k)}
-    out = {"T": f64(Q, k, 4, 4), "fitness": f64(Q, k), "inlier_rmse": f64(Q, k), "inliers": i32(Q, k), **own,
-           "pair_status": i32(Q, k), "match_status": i32(Q, k), "corr": i32(Q, k, n_max, 2), "n_corr": i32(Q, k),
-           "pair_ids": i32(Q, k),
-           "best_rank": i32(Q), "best_index": i32(Q), "reranked": i32(Q, k), "T_rel": f64(Q, 4, 4), "pose": f64(Q, 4, 4),
-           "safe_pick": i32(Q), "best_inliers": i32(Q), "status": i32(Q)}
+    keys, own = pair_keys(method), _reg.pair_buffers(dev, (Q, k), n_max, with_gt, method, skip=_NOT_KEPT)
+    out = {**{keys[n]: t for n, t in own.items()}, "match_status": i32(Q, k), "corr": i32(Q, k, n_max, 2), "n_corr": i32(Q, k),
+           "pair_ids": i32(Q, k), "best_rank": i32(Q), "best_index": i32(Q), "reranked": i32(Q, k), "T_rel": f64(Q, 4, 4),
+           "pose": f64(Q, 4, 4), "safe_pick": i32(Q), "best_inliers": i32(Q), "status": i32(Q)}
     if with_gt:
-        out.update({"rte": f64(Q, k), "rre": f64(Q, k), "success": i32(Q, k), "best_rte": f64(Q), "best_rre": f64(Q),
-                    "best_success": i32(Q)})
+        out.update({"best_rte": f64(Q), "best_rre": f64(Q), "best_success": i32(Q)})
     out["_work"] = {"kp1": torch.empty((Pc, n_max, 3), dtype=torch.float32, device=dev),
                     "kp2": torch.empty((Pc, n_max, 3), dtype=torch.float32, device=dev), "n1": i32(Pc), "n2": i32(Pc),
                     "match": _lib.scratch(nb_match, dev), "reg": _lib.scratch(nb_reg, dev)}
     return out
-
-
-# outputs of egonn_registration_finish by the names of `register_pairs` -> the per-pair keys of `verify_candidates`
-_FINISH_OUT = (("T", "T"), ("inliers", "inliers"), ("fitness", "fitness"), ("inlier_rmse", "inlier_rmse"), ("best_t", "best_t"),
-               ("rte", "rte"), ("rre", "rre"), ("success", "success"), ("status", "pair_status"))
-# the same for egonn_spectral_verify and `spectral_verify`
-_SPECTRAL_OUT = tuple(x for x in _FINISH_OUT if x[0] != "best_t") + tuple((n, n) for n in ("eigenvalue", "score", "weights", "n_seeds"))
 
 
 def verify_candidates(q_desc, q_kp, q_count, kmap: KeypointMap, nn_index, query_ids=None, T_gt=None, min_inliers: int = 0,
@@ -252,14 +249,13 @@ def verify_candidates(q_desc, q_kp, q_count, kmap: KeypointMap, nn_index, query_
                   nn[lo:hi].data_ptr(), None if qid is None else qid[lo:hi].data_ptr(), n, k, M, n_max, w["kp1"].data_ptr(),
                   w["kp2"].data_ptr(), w["n1"].data_ptr(), w["n2"].data_ptr(), s("pair_ids"))
         operands = (w["kp1"].data_ptr(), w["kp2"].data_ptr(), w["n1"].data_ptr(), w["n2"].data_ptr(), s("corr"), s("n_corr"))
+        pair_out = {name: out[key][lo:hi] for name, key in pair_keys(method).items() if key in out}
         if spectral:
             _reg.enqueue_spectral(dev, operands, P, n_max, d_thr, iterations, seed_ratio, ransac_dist_th, w["reg"],
-                                  None if gt is None else gt[lo:hi], 0.5,
-                                  {name: out[key][lo:hi] for name, key in _SPECTRAL_OUT if key in out})
+                                  None if gt is None else gt[lo:hi], 0.5, pair_out)
         else:
             _reg.enqueue_ransac(dev, (*operands, s("pair_ids")), P, n_max, H, seed, ransac_dist_th, w["reg"],
-                                None if gt is None else gt[lo:hi], 0.5,
-                                {name: out[key][lo:hi] for name, key in _FINISH_OUT if key in out})
+                                None if gt is None else gt[lo:hi], 0.5, pair_out)
         _lib.call(dev, lib.egonn_pick_candidates, nn[lo:hi].data_ptr(), n, k, M, km[3].data_ptr(), s("T"), s("inliers"),
                   s("inlier_rmse"), s("pair_status"), s("rte"), s("rre"), s("success"), int(min_inliers), s("best_rank"),
                   s("best_index"), s("reranked"), s("T_rel"), s("pose"), s("safe_pick"), s("best_inliers"), s("status"),

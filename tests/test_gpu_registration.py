@@ -380,3 +380,64 @@ def test_argument_checks(gpu):
     assert lib.egonn_registration_finish(P(k), P(k), P(n), P(n), None, None, None, 1, 64, 0, 0, 0.5, None, 0, None, 0.5, None,
                                          None, None, None, None, None, None, None, None, None, None, None) == 1
     torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------ 8. one tail behind both methods (csrc/pair_eval.h)
+TAIL_KEYS = ("T", "inliers", "fitness", "inlier_rmse", "correspondence_set", "rte", "rre", "success")
+TAIL_H = 500
+
+
+def _pad_clipped(pairs, n_max):
+    """pad_batch to n_max rows; a pair with more rows keeps its raw counts, which the device clips and reports"""
+    F1, F2, K1, K2, _, _ = pad_batch([tuple(x[:n_max] for x in p[:4]) for p in pairs], n_max)
+    return F1, F2, K1, K2, np.array([len(p[2]) for p in pairs], np.int32), np.array([len(p[3]) for p in pairs], np.int32)
+
+
+def _both_methods(gpu, pairs, n_max):
+    F1, F2, K1, K2, n1, n2 = (_cu(x) for x in _pad_clipped(pairs, n_max))
+    gt = _cu(np.stack([p[4] for p in pairs]))
+    out = {m: gpu.register_pairs(F1, F2, K1, K2, n1=n1, n2=n2, T_gt=gt, ransac_max_it=TAIL_H, method=m) for m in ("ransac", "spectral")}
+    rep = gpu.registration.repeatability_pairs(K1, K2, gt, 0.5, n1, n2)
+    torch.cuda.synchronize()
+    return {m: {k: _np(v) for k, v in o.items() if not k.startswith("_")} for m, o in out.items()}, _np(rep), _np(n1), _np(n2)
+
+
+@pytest.mark.parametrize("n_max", [128, 256])
+def test_repeatability_is_one_tail_behind_three_entry_points(gpu, n_max):
+    """register_pairs by RANSAC (256 lanes), by the spectral check (128 lanes at n_max 128, 256 beyond) and repeatability_pairs
+    (no correspondences) reach the same pair_tail: the same bits, counts of 0 and 1 and a count clipped at n_max included"""
+    pairs = list(edge_pairs().values()) + planted_case("n256_n2_200")
+    out, rep, n1, _ = _both_methods(gpu, pairs, n_max)
+    assert 0 in n1 and 1 in n1 and (n1 > n_max).any() == (n_max == 128)
+    assert ((out["ransac"]["status"] & STATUS_CLIPPED) != 0).tolist() == (n1 > n_max).tolist()
+    assert rep.dtype == np.float64 and rep.tobytes() == out["ransac"]["repeatability"].tobytes()
+    assert rep.tobytes() == out["spectral"]["repeatability"].tobytes()
+    want = [repeatability_f64(p[2][:n_max], p[3][:n_max], p[4], 0.5) for p in pairs]
+    assert np.abs(rep - want).max() <= 1e-12
+
+
+def _modelless_edge_pairs():
+    """names of the edge pairs that both float64 restatements end without a model (FEW_CORR or NO_MODEL): chosen on the CPU"""
+    from tests.spectral_ref import spectral_f64
+    from tests.test_registration_host import match_f64, register_f64
+    none = STATUS_FEW_CORR | STATUS_NO_MODEL
+    names = []
+    for name, (f1, f2, k1, k2, T) in edge_pairs().items():
+        a = register_f64(f1, f2, k1, k2, T, H=TAIL_H)
+        b = spectral_f64(k1, k2, match_f64(f1, f2)[0], 128, T)
+        if a["status"] & none and b["status"] & none:
+            names.append(name)
+    return names
+
+
+def test_modelless_pairs_end_alike_in_both_methods(gpu):
+    """without a model the shared outputs do not depend on the method: identity, 0 inliers, the metrics of the identity"""
+    E, names = edge_pairs(), _modelless_edge_pairs()
+    print(f"[registration] pairs without a model in both restatements: {names}")
+    assert len(names) >= 2
+    out, _, _, _ = _both_methods(gpu, [E[k] for k in names], 128)
+    for m in out:
+        assert ((out[m]["status"] & (STATUS_FEW_CORR | STATUS_NO_MODEL)) != 0).all(), m
+    for k in TAIL_KEYS:
+        assert out["ransac"][k].dtype == out["spectral"][k].dtype and out["ransac"][k].tobytes() == out["spectral"][k].tobytes(), k
+    assert np.array_equal(out["ransac"]["T"], np.broadcast_to(np.eye(4), (len(names), 4, 4))) and not out["ransac"]["inliers"].any()

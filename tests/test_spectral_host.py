@@ -79,6 +79,28 @@ def test_python_surface_refuses_unknown_methods(built):
     assert registration.check_method("x", "spectral") == "spectral" and registration.METHODS == ("ransac", "spectral")
 
 
+def test_output_table_follows_the_c_prototypes():
+    """registration.PAIR_OUTPUTS yields, per method, the pointer order of its entry point in include/egonn_hip.h from the first
+    output onwards, and verify_candidates' per-pair keys rename exactly the table's rows that it keeps"""
+    from egonn_amd import registration, relocalize
+    header = open(os.path.join(REPO, "include", "egonn_hip.h")).read()
+    c_name = {"correspondence_set": "corr_set"}         # the one name Python spells out (Open3D's attribute)
+    for method, entry, first in (("ransac", "egonn_registration_finish", "T"), ("spectral", "egonn_spectral_verify", "eigenvalue")):
+        args = re.search(r"\bint " + entry + r"\((.*?)\);", header, re.S).group(1)
+        params = [re.search(r"(\w+)\s*$", a).group(1) for a in args.split(",")]
+        assert params[-1] == "stream"
+        rows = registration.pair_outputs(method)
+        names = [r[0] for r in rows]
+        assert [c_name.get(n, n) for n in names] == params[params.index(first):-1], method
+        assert len(set(names)) == len(names) and all(r[4] in (None, method) for r in rows)
+        keys = relocalize.pair_keys(method)
+        assert set(keys) | set(relocalize._NOT_KEPT) == set(names) and not set(keys) & set(relocalize._NOT_KEPT)
+        assert {n: k for n, k in keys.items() if n != k} == {"status": "pair_status"} and len(set(keys.values())) == len(keys)
+    assert [r[0] for r in registration.PAIR_OUTPUTS if r[3]] == ["rte", "rre", "success", "repeatability"]
+    assert {r[0] for r in registration.PAIR_OUTPUTS if r[4] == "ransac"} == {"best_t"}
+    assert {r[0] for r in registration.PAIR_OUTPUTS if r[4] == "spectral"} == {"eigenvalue", "score", "weights", "n_seeds"}
+
+
 # ------------------------------------------------------------------ the restatement on numbers that can be written out
 def _identity_corr(m):
     return np.stack([np.arange(m), np.arange(m)], 1).astype(np.int32)

@@ -74,12 +74,9 @@ def _spectral_row(ea, _lib, lib, km, qf, qk, qn, nn, H, row):
     ops = (kp1.data_ptr(), kp2.data_ptr(), n1.data_ptr(), n2.data_ptr(), base["corr"].data_ptr(), base["n_corr"].data_ptr())
     scr_r = _lib.scratch(lib.egonn_registration_scratch_bytes(P, nk, H), dev)
     scr_s = _lib.scratch(lib.egonn_spectral_verify_scratch_bytes(P, nk), dev)
-    flat = lambda d, names: {n: d[key].reshape(P, *d[key].shape[2:]) for n, key in names if key in d}      # noqa: E731
-    out_r = flat(base, (("T", "T"), ("inliers", "inliers"), ("fitness", "fitness"), ("inlier_rmse", "inlier_rmse"),
-                        ("best_t", "best_t"), ("status", "pair_status")))
-    out_s = flat(spec, (("T", "T"), ("inliers", "inliers"), ("fitness", "fitness"), ("inlier_rmse", "inlier_rmse"),
-                        ("status", "pair_status"), ("eigenvalue", "eigenvalue"), ("score", "score"), ("weights", "weights"),
-                        ("n_seeds", "n_seeds")))
+    from egonn_amd.relocalize import pair_keys
+    flat = lambda d, m: {n: d[key].reshape(P, *d[key].shape[2:]) for n, key in pair_keys(m).items() if key in d}      # noqa: E731
+    out_r, out_s = flat(base, "ransac"), flat(spec, "spectral")
     pid = pids.data_ptr()
 
     def ransac():
