@@ -181,6 +181,10 @@ _SIGS = [
     ("egonn_pose_graph_hessvec", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_double, C.c_double, _P, _P, _P, _P, C.c_int64, _P]),
     ("egonn_pose_graph_optimize", C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_double, C.c_int, C.c_int] + [C.c_double] * 6 +
      [_P] * 8 + [C.c_int64, _P]),
+    ("egonn_loop_consistency_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_loop_consistency", C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int] + [C.c_double] * 4 + [C.c_int] * 3 +
+     [_P] * 8 + [C.c_int64, _P]),
+    ("egonn_loop_cycle_errors", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("egonn_profile_enable", C.c_int, [_P, C.c_int, C.c_char_p]),
     ("egonn_profile_fetch", C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.POINTER(C.c_float),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),

@@ -38,43 +38,19 @@
 #include <math.h>
 
 #include "../../include/egonn_hip.h"
+#include "pose_math.h"
 
 namespace egonn {
 
 static constexpr int PG_WG = 64;
 static constexpr int PG_LIN = 40;                    // doubles per linearised edge: 32 + the residual (6), padded to 64 bytes
-static constexpr double PG_SMALL = 0.05;             // series below this angle (see above)
+static constexpr double PG_SMALL = POSE_LOG_SMALL;   // series below this angle (see above)
 static constexpr double PG_MAX_ANGLE = 3.14159265358979323846 - 1e-3;
 
 struct PgState {
   double lambda, cost;
   int32_t cur, done, iter, accepted, flag_a, flag_b;
 };
-
-// ------------------------------------------------------------------ small 3x3 algebra (row-major)
-__device__ static inline void m3_mul(const double* A, const double* B, double* C) {            // C = A B
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
-__device__ static inline void m3_tmul(const double* A, const double* B, double* C) {           // C = A^T B
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) C[3 * i + j] = A[i] * B[j] + A[3 + i] * B[3 + j] + A[6 + i] * B[6 + j];
-}
-__device__ static inline void m3_vec(const double* A, const double* x, double* y) {            // y = A x
-#pragma unroll
-  for (int i = 0; i < 3; ++i) y[i] = A[3 * i] * x[0] + A[3 * i + 1] * x[1] + A[3 * i + 2] * x[2];
-}
-__device__ static inline void m3_tvec(const double* A, const double* x, double* y) {           // y = A^T x
-#pragma unroll
-  for (int i = 0; i < 3; ++i) y[i] = A[i] * x[0] + A[3 + i] * x[1] + A[6 + i] * x[2];
-}
-__device__ static inline void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1], c[1] = a[2] * b[0] - a[0] * b[2], c[2] = a[0] * b[1] - a[1] * b[0];
-}
 
 __device__ static inline double pg_wave_sum(double v) {
 #pragma unroll
@@ -103,16 +79,7 @@ __global__ __launch_bounds__(PG_WG) void pg_validate_kernel(const int32_t* __res
   if (e >= E) return;
   const int32_t a = edge_index[2 * e], b = edge_index[2 * e + 1];
   const double wr = w ? w[2 * e] : 1.0, wt = w ? w[2 * e + 1] : 1.0;
-  int st = 0;
-  if (a < 0 || a >= n || b < 0 || b >= n) st |= EGONN_PG_STATUS_BAD_INDEX;
-  else if (a == b) st |= EGONN_PG_STATUS_SELF_LOOP;
-  bool finite = fabs(wr) < INFINITY && fabs(wt) < INFINITY;              // false for NaN
-  const double* z = Z + e * 16;
-#pragma unroll
-  for (int j = 0; j < 12; ++j) finite = finite && fabs(z[j]) < INFINITY;
-  finite = finite && z[12] == 0.0 && z[13] == 0.0 && z[14] == 0.0 && z[15] == 1.0;
-  if (!finite) st |= EGONN_PG_STATUS_NONFINITE;
-  if (wr < 0.0 || wt < 0.0) st |= EGONN_PG_STATUS_NEGATIVE_WEIGHT;
+  const int st = pose_edge_status(a, b, n, Z + e * 16, wr, wt);
   const bool live = st == 0 && (wr > 0.0 || wt > 0.0);
   ab[2 * e] = live ? a : 0, ab[2 * e + 1] = live ? b : 0;
   weff[2 * e] = live ? wr : 0.0, weff[2 * e + 1] = live ? wt : 0.0;
@@ -155,15 +122,10 @@ __global__ __launch_bounds__(PG_WG) void pg_odometry_kernel(const double* __rest
   if (i >= m) return;
   const double* Xa = X + i * 16;
   const double* Xb = Xa + 16;
-  double Ra[9], Rb[9], d[3], RM[9], tM[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int b = 0; b < 3; ++b) Ra[3 * a + b] = Xa[4 * a + b], Rb[3 * a + b] = Xb[4 * a + b];
-    d[a] = Xb[4 * a + 3] - Xa[4 * a + 3];
-  }
-  m3_tmul(Ra, Rb, RM);
-  m3_tvec(Ra, d, tM);
+  double Ra[9], ta[3], Rb[9], tb[3], RM[9], tM[3];
+  se3_load(Xa, Ra, ta);
+  se3_load(Xb, Rb, tb);
+  se3_inv_mul(Ra, ta, Rb, tb, RM, tM);
   double* z = Z + i * 16;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -212,27 +174,17 @@ __global__ __launch_bounds__(PG_WG) void pg_linearize_kernel(const PgState* __re
     const double* Xa = X + (int64_t)ab[2 * e] * 16;
     const double* Xb = X + (int64_t)ab[2 * e + 1] * 16;
     const double* z = Z + e * 16;
-    double Ra[9], Rb[9], RZ[9], d[3], tZ[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Ra[3 * i + j] = Xa[4 * i + j], Rb[3 * i + j] = Xb[4 * i + j], RZ[3 * i + j] = z[4 * i + j];
-      d[i] = Xb[4 * i + 3] - Xa[4 * i + 3];                                // first, so UTM-scale offsets cancel exactly
-      tZ[i] = z[4 * i + 3];
-    }
-    double RM[9], tM[3], RE[9], u[3];
-    m3_tmul(Ra, Rb, RM);
-    m3_tvec(Ra, d, tM);
-    m3_tmul(RZ, RM, RE);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u[i] = tM[i] - tZ[i];
-    m3_tvec(RZ, u, r);
-    const double ax[3] = {0.5 * (RE[7] - RE[5]), 0.5 * (RE[2] - RE[6]), 0.5 * (RE[3] - RE[1])};
-    const double sn = sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]), cs = 0.5 * (RE[0] + RE[4] + RE[8] - 1.0);
-    const double th = atan2(sn, cs), th2 = th * th;
+    double Ra[9], ta[3], Rb[9], tb[3], RZ[9], tZ[3], RM[9], tM[3], RE[9];
+    se3_load(Xa, Ra, ta);
+    se3_load(Xb, Rb, tb);
+    se3_load(z, RZ, tZ);
+    se3_inv_mul(Ra, ta, Rb, tb, RM, tM);                                   // M = X_a^-1 X_b: the difference first, so UTM-scale offsets cancel exactly
+    se3_inv_mul(RZ, tZ, RM, tM, RE, r);                                    // E = Z^-1 M
+    double ax[3], sn, cs;
+    const double th = so3_log_angle(RE, ax, &sn, &cs), th2 = th * th;
     double k, c;
     if (th < PG_SMALL) {
-      k = 1.0 + th2 * (1.0 / 6.0 + th2 * (7.0 / 360.0 + th2 * (31.0 / 15120.0)));
+      k = so3_log_series(th2);
       c = 1.0 / 12.0 + th2 * (1.0 / 720.0 + th2 * (1.0 / 30240.0));
     } else {
       k = th / sn;
@@ -699,7 +651,7 @@ struct PgLayout {
   size_t ab, weff, pstat, fixed, row_start, inc, keys0, keys1, vals0, vals1, sort, sort_bytes;        // the plan
   size_t state, X0, X1, lin0, lin1, ecost, fac, x, r, z, q, p0, p1, pqp, rz0p, rzp0, rzp1, gmaxp, costp, total;
 };
-static bool pg_sizes_ok(int64_t n, int64_t E) { return n >= 1 && n < (1ll << 31) - 1 && E >= 0 && E < (1ll << 30); }
+static bool pg_sizes_ok(int64_t n, int64_t E) { return pose_sizes_ok(n, E); }
 static PgLayout pg_layout(int64_t n, int64_t E) {
   PgLayout L;
   const size_t nn = (size_t)n, ee = (size_t)(E > 0 ? E : 1), nwg = (size_t)cdiv(n, PG_WG);

@@ -223,12 +223,15 @@ def loop_edges(result: Dict[str, torch.Tensor], weight=(1.0, 1.0)) -> Dict[str, 
 
 
 def optimize_trajectory(poses, loops: Dict[str, torch.Tensor], odometry: Optional[Dict[str, torch.Tensor]] = None,
-                        odometry_weight=(1.0, 1.0), out: Optional[Dict] = None, **kw) -> Dict:
+                        odometry_weight=(1.0, 1.0), out: Optional[Dict] = None, consistency: Optional[Dict] = None, **kw) -> Dict:
     """poses (n,4,4): the drifting trajectory; loops: `loop_edges(...)` (or any dict of edge_index, Z, weights); odometry: such
     a dict too, e.g. ICP-refined relative poses of consecutive scans, default: the chain of `odometry_edges(poses,
     odometry_weight)`.  The two edge sets are written one behind the other into buffers the result owns ('edge_index', 'Z',
     'weights'; 'n_odometry' = the length of the first) and `optimize_pose_graph(**kw)` runs on them.  out = a result of this
-    function for the same shapes: the buffers are filled again by copies and nothing is allocated (see optimize_pose_graph)."""
+    function for the same shapes: the buffers are filled again by copies and nothing is allocated (see optimize_pose_graph).
+    consistency: a dict of `filter_loops` keywords ({} = its defaults): the loops go through the pairwise-consistency filter
+    first (loop_consistency.py), its result is kept under 'consistency' and its buffers are used again with out=; None: no
+    filter, and nothing of it runs."""
     who = "optimize_trajectory"
     shape = tuple(getattr(poses, "shape", ()))
     if len(shape) != 3 or shape[1:] != (4, 4) or shape[0] < 1:
@@ -248,6 +251,11 @@ def optimize_trajectory(poses, loops: Dict[str, torch.Tensor], odometry: Optiona
         Z = torch.empty((m, 4, 4), dtype=torch.float64, device=dev)
         w = torch.empty((m, 2), dtype=torch.float64, device=dev)
     X = _stage(who, "poses", poses, dev, torch.float64, store, reuse)
+    if consistency is not None:
+        from .loop_consistency import filter_loops
+        if reuse and "consistency" not in out:
+            raise ValueError(f"{who}: `out` was made without consistency=")
+        loops = filtered = filter_loops(X, loops, out=out["consistency"] if reuse else None, **consistency)
     if odometry is None:
         _odometry_into(X, Z, edges)
         w[:m_od, 0], w[:m_od, 1] = wr, wt
@@ -258,4 +266,6 @@ def optimize_trajectory(poses, loops: Dict[str, torch.Tensor], odometry: Optiona
             w[lo:hi].copy_(torch.as_tensor(part["weights"]))
     res = optimize_pose_graph(X, edges, Z, w, out=out, **kw)
     res.update(edge_index=edges, Z=Z, weights=w, n_odometry=m_od, _traj_in=store)
+    if consistency is not None:
+        res["consistency"] = filtered
     return res

@@ -1060,6 +1060,41 @@ int egonn_pose_graph_optimize(const double* poses, int64_t n, int64_t n_edges, c
                               int32_t* accept_trace, int32_t* counters, double* lambda_out, int32_t* edge_status,
                               int32_t* graph_status, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ loop-edge consistency filter (csrc/loop_consistency.hip)
+ * Between the loop edges and the pose graph: two loop closures taken close together in time must agree with each other through
+ * the odometry between them.  poses (n,4,4) float64, the drifting trajectory; edge_index (E,2) int32 = (a, b), Z (E,4,4) ~
+ * X_a^-1 X_b, weights (E,2), E static.  An edge is live when the pose-graph plan would leave it on (no BAD_INDEX, SELF_LOOP,
+ * NONFINITE, NEGATIVE_WEIGHT; a non-finite pose at either end also gives NONFINITE) and one of its weights is positive; a dead
+ * edge never votes, has support 0, keep 0, and leaves every other output bit-equal to a call without it.
+ * Cycle of live edges e, f: C = Z_e (X_be^-1 X_bf) Z_f^-1 (X_af^-1 X_ae), c_trans = |t_C|, c_rot = |Log_SO3 R_C|, always with the
+ * edge that comes first in the order of (b, row) in the role of e, so the relation is symmetric by construction.
+ * Comparable: |b_e - b_f| <= window, |a_e - a_f| <= window, and at most max_partners / 2 positions apart in the order of the live
+ * edges by (b, row); TRUNCATED when a live edge has a partner inside its b-window beyond that cap.  Consistent: comparable,
+ * c_trans <= trans_thr + trans_drift g, c_rot <= rot_thr + rot_drift g, g = |b_e - b_f| + |a_e - a_f|.  An edge never counts
+ * itself; duplicates count each other.  Selection: the min_support-core in synchronous rounds (count, then remove all below
+ * min_support at once); max_rounds rounds are enqueued, after one that removed nothing the rest return at once; ROUNDS when
+ * the last round still removed something.  Not a maximum clique: a coherent set of false loops survives.
+ * Outputs: keep (E) uint8, support0 (E) before any removal, support (E) among the survivors (0 for removed and dead edges),
+ * weights_out (E,2) = weights * keep, rounds (1) = rounds that removed something, edge_status (E) = EGONN_PG_STATUS_* bits,
+ * status (1) = EGONN_LC_STATUS_*.  scratch: egonn_loop_consistency_scratch_bytes(E, max_partners) bytes, 256-byte aligned
+ * (-1 for E outside [0, 2^30) or max_partners not a multiple of 64 in [64, 65536]).  Arguments are validated before any launch
+ * (null or misaligned pointers, n or E out of the plan's ranges, window < 0, thresholds negative or not finite, min_support < 1,
+ * max_rounds outside [1, 65536], max_partners, scratch); one stream, no synchronisation, deterministic, float64.
+ * egonn_loop_cycle_errors: the test seam of the arithmetic.  pairs (P,2) int32 rows of the edge arrays -> out (P,2) =
+ * (c_trans, c_rot) in the canonical role; a pair out of range or naming an edge with a status bit gives NaN (no weights here). */
+enum {
+  EGONN_LC_STATUS_TRUNCATED = 1,
+  EGONN_LC_STATUS_ROUNDS = 2
+};
+int64_t egonn_loop_consistency_scratch_bytes(int64_t n_edges, int max_partners);            /* -1 on bad arguments */
+int egonn_loop_consistency(const double* poses, int64_t n, const int32_t* edge_index, const double* Z, const double* weights,
+                           int64_t n_edges, int window, double trans_thr, double rot_thr, double trans_drift, double rot_drift,
+                           int min_support, int max_rounds, int max_partners, uint8_t* keep, int32_t* support0, int32_t* support,
+                           double* weights_out, int32_t* rounds, int32_t* edge_status, int32_t* status, void* scratch,
+                           int64_t scratch_bytes, void* stream);
+int egonn_loop_cycle_errors(const double* poses, int64_t n, const int32_t* edge_index, const double* Z, int64_t n_edges,
+                            const int32_t* pairs, int64_t n_pairs, double* out, void* stream);
+
 /* ------------------------------------------------------------------ launch timing (bench.py roofline leg)
  * mode 0: off; 1: time every tagged sparse-conv launch (event records around it); 2: only launches whose tag contains
  * `filter`, with the events attached to the kernel dispatch itself (the kernel's own begin..end, also when other streams
