@@ -60,9 +60,8 @@ __device__ static inline void lc_cycle(const double* __restrict__ Ze, const doub
   se3_inv_mul(R0, t0, R1, t1, R3, t3);                 // X_af^-1 X_ae
   se3_mul(R2, t2, R3, t3, R0, t0);                     // C
   double ax[3], sn, cs;
-  const double th = so3_log_angle(R0, ax, &sn, &cs);
+  *c_rot = so3_log_angle(R0, ax, &sn, &cs);            // theta itself, the length of Log R: no theta / sin(theta), which is 0 * inf at a half turn
   *c_trans = sqrt(t0[0] * t0[0] + t0[1] * t0[1] + t0[2] * t0[2]);
-  *c_rot = sn * so3_log_scale(th, th * th, sn);        // |ax| theta / sin(theta): the length of the pose graph's Log R
 }
 
 // the filter's status of an edge: the plan's bits, NONFINITE also for a pose that is not finite

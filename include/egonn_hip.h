@@ -738,6 +738,8 @@ int egonn_voxel_downsample(const float* points, int64_t n, const int64_t* offset
  * offsets (n_pairs+1 each; n_src / n_tgt are capacities), T_init (n_pairs,4,4) f64 (nullable = identity).
  * Evaluation under T: j(i) = nearest target point of T s_i (fp64 squared distance, ties: lowest index), a correspondence iff
  * the distance is < max_dist; fitness = n_corr / n_source; inlier_rmse = sqrt(sum d2 / n_corr) (0 without correspondences).
+ * A squared distance that is not finite never wins: a source or target row with a NaN or an infinite coordinate is never part
+ * of a correspondence and is never counted, and every other row is evaluated as if that row held no point.
  * T_0 = init is evaluated; round k: U = least-squares rigid transform (no scale, det +1) of {T_k s_i} onto {t_j(i)},
  * T_k+1 = U T_k, evaluated; the loop stops after that evaluation if |d fitness| < eps_fitness and |d rmse| < eps_rmse, after
  * max_iteration rounds (MAX_ITER), or before a round with fewer than 3 correspondences (FEW_CORR, T unchanged).

@@ -103,6 +103,14 @@ def pair_residuals(Xa, Xb, Z):
     return np.concatenate([np.einsum("eji,ej->ei", RZ, tM - Z[:, :3, 3]), log_so3_rows(RE)], axis=1)
 
 
+def pair_angles(Xa, Xb, Z):
+    """the rotation angle of E = Z^-1 X_a^-1 X_b in [0, pi] for every row: atan2 of the axial vector's length and the trace.
+    At a half turn the axial vector is 0 and Log R_E has no direction (log_so3_rows returns 0 there): the angle still is pi."""
+    RE = np.einsum("eji,ejk->eik", Z[:, :3, :3], np.einsum("eji,ejk->eik", Xa[:, :3, :3], Xb[:, :3, :3]))
+    ax = 0.5 * np.stack([RE[:, 2, 1] - RE[:, 1, 2], RE[:, 0, 2] - RE[:, 2, 0], RE[:, 1, 0] - RE[:, 0, 1]], axis=1)
+    return np.arctan2(np.linalg.norm(ax, axis=1), 0.5 * (np.trace(RE, axis1=1, axis2=2) - 1.0))
+
+
 def residuals(poses, edge_index, Z, weights=None, robust_delta=0.0, rho=None):
     """-> dict r (E,6), s (E,), rho (E,), terms (E,) = rho (1 - rho / 2) s^2, cost, status (E,), w (E,2) effective weights.
     rho given: held fixed and the terms are the quadratic 1/2 rho s^2 the linear solve sees; else recomputed here."""
@@ -112,7 +120,7 @@ def residuals(poses, edge_index, Z, weights=None, robust_delta=0.0, rho=None):
     r, st = np.zeros((E, 6)), st.copy()
     ok = np.flatnonzero(st == 0)
     r[ok] = pair_residuals(poses[ei[ok, 0]], poses[ei[ok, 1]], Z[ok])
-    far = ok[np.linalg.norm(r[ok, 3:], axis=1) > MAX_ANGLE]
+    far = ok[(np.linalg.norm(r[ok, 3:], axis=1) > MAX_ANGLE) | (pair_angles(poses[ei[ok, 0]], poses[ei[ok, 1]], Z[ok]) > MAX_ANGLE)]
     st[far] |= ANGLE
     w[far] = 0.0
     s = np.sqrt(w[:, 1] * (r[:, :3] ** 2).sum(axis=1) + w[:, 0] * (r[:, 3:] ** 2).sum(axis=1))

@@ -116,7 +116,7 @@ def _same(got, want, w):
 
 
 # ------------------------------------------------------------------ 1. the cycle arithmetic
-ANGLES = [0.0, 1e-9, 1e-4, 1.0, 3.0, math.pi - 2e-3]
+ANGLES = [0.0, 1e-9, 1e-4, 1.0, 3.0, math.pi - 2e-3, math.pi]
 
 
 def test_cycle_errors_against_the_restatement_in_longdouble(gpu):
@@ -124,14 +124,19 @@ def test_cycle_errors_against_the_restatement_in_longdouble(gpu):
     the origin.  The yardstick is the restatement evaluated in numpy.longdouble on the same float64 inputs; the device may be off
     by 4 x the float64 restatement's own error against it, and never has to be closer than 16 * 2^-53 times the largest
     coordinate (c_trans) or 16 * 2^-53 (c_rot): the margin covers another, equally valid operation order and FMA contraction.
-    Measured on the MI355X: c_trans error 2.2e-14 m (restatement 2.4e-14 m, floor 1.8e-9 m), c_rot error 7.6e-17 rad (restatement
-    1.3e-16 rad, floor 1.8e-15 rad).  (e, f) and (f, e) are equal bit for bit; out-of-range pairs and dead edges give NaN."""
+    Measured on the MI355X: c_trans error 2.2e-14 m (restatement 2.4e-14 m, floor 1.8e-9 m), c_rot error 1.3e-16 rad (restatement
+    1.3e-16 rad, floor 1.8e-15 rad).  (e, f) and (f, e) are equal bit for bit; out-of-range pairs and dead edges give NaN.
+    The last angle is an exact half turn, the yaw flip of a false loop: poses without rotation, Z_e = I and Z_f = diag(-1, -1, 1),
+    so the cycle's rotation is the half turn bit for bit, its axial vector is 0 and theta / sin(theta) is not a number.  c_rot is
+    theta itself there: pi to one ulp, never NaN."""
     assert np.finfo(np.longdouble).eps < 2.0 ** -60
     rng = np.random.default_rng(21)
     m = len(ANGLES)
-    X = np.stack([_rand_pose(rng, math.pi, 100.0, offset=1e6) for _ in range(4 * m + 1)])
+    assert ANGLES[-1] == math.pi
+    nan_pose = 4 * (m - 1)
+    X = np.stack([_rand_pose(rng, math.pi, 100.0, offset=1e6) for _ in range(nan_pose + 1)])
     ei, Z = [], []
-    for k, ang in enumerate(ANGLES):
+    for k, ang in enumerate(ANGLES[:-1]):
         a, b, a2, b2 = 4 * k, 4 * k + 1, 4 * k + 2, 4 * k + 3
         ax = rng.standard_normal(3)
         Err = np.eye(4)
@@ -139,12 +144,17 @@ def test_cycle_errors_against_the_restatement_in_longdouble(gpu):
         Err[:3, 3] = rng.uniform(-3, 3, 3) if k else 0.0
         ei += [[a, b], [a2, b2]]
         Z += [_rel(X[a], X[b]), _rel(X[a2], X[b2]) @ Err]               # the cycle is a conjugate of Err^-1: it turns by ang
+    flat = np.tile(np.eye(4), (4, 1, 1))                                  # the half turn: four poses that do not rotate
+    flat[:, :3, 3] = 1e6 + np.array([[3.0, -40.5, 7.25], [-12.0, 8.0, 0.5], [55.5, 1.0, -2.0], [-7.0, 66.0, 30.0]])
+    X = np.concatenate([X, flat])
+    ei += [[nan_pose + 1, nan_pose + 2], [nan_pose + 3, nan_pose + 4]]
+    Z += [np.eye(4), np.diag([-1.0, -1.0, 1.0, 1.0])]
     dead0 = len(ei)
-    ei += [[-1, 3], [5, 5], [2, 3], [1, 4 * m]]                           # bad index, self loop, NaN in Z, NaN pose
+    ei += [[-1, 3], [5, 5], [2, 3], [1, nan_pose]]                        # bad index, self loop, NaN in Z, NaN pose
     Z += [np.eye(4)] * 4
     ei, Z = np.array(ei, np.int32), np.stack(Z)
     Z[dead0 + 2, 0, 3] = np.nan
-    X[4 * m, 2, 2] = np.nan
+    X[nan_pose, 2, 2] = np.nan
     pairs = [[2 * k, 2 * k + 1] for k in range(m)] + [[2 * k + 1, 2 * k] for k in range(m)] + [[0, 3], [7, 2], [4, 4]]
     n_live = len(pairs)
     pairs += [[0, dead0 + j] for j in range(4)] + [[dead0 + 1, 2], [0, len(ei)], [-1, 0], [2 ** 31 - 1, 1]]
@@ -164,6 +174,7 @@ def test_cycle_errors_against_the_restatement_in_longdouble(gpu):
           f"restatement c_trans {own_err[:, 0].max():.2e} m, c_rot {own_err[:, 1].max():.2e} rad; floors {floor[0]:.2e} m, {floor[1]:.2e} rad")
     assert (err <= bound).all(), (err, bound)
     assert np.array_equal(_bits(got[:m]), _bits(got[m: 2 * m]))               # (e, f) and (f, e): the same bits
+    assert abs(float(want[m - 1, 1]) - math.pi) <= 2.0 ** -51 and abs(got[m - 1, 1] - math.pi) <= 2.0 ** -51 and got[2 * m - 1, 1] == got[m - 1, 1]
 
 
 # ------------------------------------------------------------------ 2. support, survivors and rounds exactly

@@ -79,7 +79,9 @@ ANGLES = [0.0, 1e-9, 1e-4, 1.0, 3.0, math.pi - 2e-3]
 
 def test_residuals_and_cost_at_the_edges_of_the_logarithm(gpu):
     """Residual rotations {0, 1e-9, 1e-4, 1, 3, pi - 2e-3} about random axes (both sides of the series switch at 0.05),
-    translation errors up to 100 m, poses at 1e6 m offsets.
+    translation errors up to 100 m, poses at 1e6 m offsets.  One more edge is an exact half turn (two poses that do not rotate,
+    Z = diag(-1, -1, 1)): the axial vector of E is 0, theta / sin(theta) is pi / 0; the edge is past the range like any other and
+    nothing it leaves behind is infinite or NaN.
     Tolerances.  A residual component is a few hundred fp64 operations on numbers of size <= 200 m after the translation
     difference (taken first in both implementations, the same IEEE subtraction, so the 1e6 offset leaves nothing behind):
     300 * 2^-53 * 200 = 7e-12 m, bar 1e-10 m.  An angle component loses the most at pi - 2e-3, where the axial vector has length
@@ -96,11 +98,16 @@ def test_residuals_and_cost_at_the_edges_of_the_logarithm(gpu):
         Err[:3, 3] = rng.uniform(-100, 100, 3) if k else 0.0
         edges.append([k, k + 1])
         Z.append(_rel(X[k], X[k + 1]) @ _inv(Err))                            # E = Z^-1 M = Err
+    flat = np.tile(np.eye(4), (2, 1, 1))                                      # the exact half turn, on two nodes of its own
+    flat[:, :3, 3] = 1e6 + np.array([[3.0, -40.5, 7.25], [-12.0, 8.0, 0.5]])
+    X = np.concatenate([X, flat])
+    edges.append([n, n + 1])
+    Z.append(np.diag([-1.0, -1.0, 1.0, 1.0]))
     edges, Z = np.array(edges, np.int32), np.stack(Z)
     w = rng.uniform(0.5, 2.0, (len(edges), 2))
     want = ref.residuals(X, edges, Z, w)
-    assert want["status"].tolist() == [0] * len(ANGLES) + [ref.ANGLE]
-    assert np.allclose(np.linalg.norm(want["r"][:-1, 3:], axis=1), ANGLES, rtol=0, atol=1e-9)
+    assert want["status"].tolist() == [0] * len(ANGLES) + [ref.ANGLE, ref.ANGLE]
+    assert np.allclose(np.linalg.norm(want["r"][:len(ANGLES), 3:], axis=1), ANGLES, rtol=0, atol=1e-9)
     got = gpu.pose_graph_cost(_cu(X), _cu(edges), _cu(Z), _cu(w))
     r, s, rho, st = _np(got["residuals"]), _np(got["s"]), _np(got["rho"]), _np(got["edge_status"])
     assert st.tolist() == want["status"].tolist() and int(got["status"].item()) == 0
@@ -108,15 +115,16 @@ def test_residuals_and_cost_at_the_edges_of_the_logarithm(gpu):
     dt, da = np.abs(r[live, :3] - want["r"][live, :3]).max(), np.abs(r[live, 3:] - want["r"][live, 3:]).max()
     print(f"[pose graph] residual error: translation {dt:.2e} m, angle {da:.2e} rad")
     assert dt <= 1e-10 and da <= 1e-9
-    assert s[-1] == 0.0 and (rho == 1.0).all() and (r[-1] == 0.0).all()        # the edge past the range contributes nothing
+    assert (s[-2:] == 0.0).all() and (rho == 1.0).all() and (r[-2:] == 0.0).all()    # the edges past the range contribute nothing
+    assert np.isfinite(r).all() and np.isfinite(s).all() and np.isfinite(float(got["cost"]))
     g0 = _np(got["gradient"])
-    assert np.isfinite(g0).all() and (g0[-1] == 0.0).all()                     # its far node has no other edge
+    assert np.isfinite(g0).all() and (g0[n - 1:] == 0.0).all()                 # their far nodes have no other edge
     # a pose that is not finite switches its edges off the same way and poisons nothing else
     Xn = X.copy()
     Xn[3, 1, 3] = np.nan
     bad = gpu.pose_graph_cost(_cu(Xn), _cu(edges), _cu(Z), _cu(w))
     bst, br, bg = _np(bad["edge_status"]), _np(bad["residuals"]), _np(bad["gradient"])
-    assert bst.tolist() == [0, 0, ref.ANGLE, ref.ANGLE, 0, 0, ref.ANGLE] and (br[[2, 3]] == 0.0).all()
+    assert bst.tolist() == [0, 0, ref.ANGLE, ref.ANGLE, 0, 0, ref.ANGLE, ref.ANGLE] and (br[[2, 3]] == 0.0).all()
     assert np.isfinite(bg).all() and np.isfinite(float(bad["cost"])) and np.array_equal(br[[0, 1, 4, 5]], r[[0, 1, 4, 5]])
     assert np.abs(s[live] - want["s"][live]).max() <= 1e-12 * want["s"].max()
     assert abs(float(got["cost"]) - want["cost"]) <= 1e-12 * np.abs(want["terms"]).sum()
