@@ -163,6 +163,15 @@ _SIGS = [
     ("egonn_pair_masks", C.c_int, [_P, C.c_int, _P, _P, C.c_int64, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     ("egonn_relative_poses", C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     ("egonn_gather_clouds", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int, _P, C.c_int64, _P, _P, _P]),
+    ("egonn_voxel_map_integrate_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_voxel_map_integrate", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_double,
+                                            C.c_int64, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
+    ("egonn_voxel_map_merge_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    ("egonn_voxel_map_merge", C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64,
+                                        _P, _P, _P, C.c_int64, _P]),
+    ("egonn_voxel_map_select_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_voxel_map_select", C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int, _P,
+                                         C.c_int, C.c_int, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
     ("egonn_match_candidates_scratch_bytes", C.c_int64, [C.c_int, C.c_int, C.c_int]),
     ("egonn_match_candidates", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                          C.c_int64, _P]),

@@ -1,0 +1,337 @@
+"""A resident global voxel map (csrc/voxel_map.hip): fuse the clouds of a `CloudBank` under a trajectory's
+poses into one map, grow it batch by batch, crop submaps out of it, and refine a scan's pose against it.
+
+A voxel record is (key, integer sums of the points' residuals, point count, observation count).  The sums are integers, so
+`insert` in any number of batches and in any order gives, bit for bit, the records of one call.  The centroid of a voxel is
+its output point; `observations` (how many scans put a point there) is the one filter against dynamic objects.  There is no
+torch or numpy fallback for the device arithmetic.
+
+Not here: removing observations again (the integer sums make it possible later), `Relocalizer(refine="map")`, normals or
+covariances per voxel, and cutting the sort's 63 key bits by a known extent."""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import registration as _reg
+
+MAX_OBS = 4096
+MAX_BOXES = 4096
+STATUS_RANGE, STATUS_CAPACITY, STATUS_BAD_INDEX = 1, 2, 4
+_FIELDS = ("keys", "sums", "count", "obs")
+
+
+def _check_poses(name, poses, n=None):
+    shape = tuple(getattr(poses, "shape", ()))
+    if len(shape) != 3 or shape[1:] != (4, 4) or (n is not None and shape[0] != n):
+        want = "(n, 4, 4)" if n is None else f"({n}, 4, 4)"
+        raise ValueError(f"{name}: expected {want} poses, got shape {shape}")
+
+
+def _check_filters(name, min_count, min_observations):
+    if int(min_count) < 1 or int(min_observations) < 1:
+        raise ValueError(f"{name}: min_count and min_observations are at least 1")
+
+
+def _check_boxes(name, centers, half_extent) -> np.ndarray:
+    """-> half extents (3,) float64"""
+    shape = tuple(getattr(centers, "shape", ()))
+    if len(shape) != 2 or shape[1] != 3 or not 1 <= shape[0] <= MAX_BOXES:
+        raise ValueError(f"{name}: centers must be (n, 3) with 1 <= n <= {MAX_BOXES}, got shape {shape}")
+    try:
+        half = np.broadcast_to(np.asarray(half_extent, dtype=np.float64), (3,))
+    except ValueError:
+        half = None
+    if half is None or not (np.isfinite(half).all() and (half > 0).all()):
+        raise ValueError(f"{name}: half_extent is one positive finite number or three")
+    return np.array(half, dtype=np.float64)          # a writable copy: torch.from_numpy wants one
+
+
+def _records(rows: int, dev) -> Dict[str, torch.Tensor]:
+    rows = max(int(rows), 1)
+    return {"keys": torch.empty((rows,), dtype=torch.int64, device=dev), "sums": torch.empty((rows, 3), dtype=torch.int64, device=dev),
+            "count": torch.empty((rows,), dtype=torch.int32, device=dev), "obs": torch.empty((rows,), dtype=torch.int32, device=dev),
+            "n": torch.zeros((), dtype=torch.int64, device=dev)}
+
+
+def _rec_ptrs(r):
+    return r["keys"].data_ptr(), r["sums"].data_ptr(), r["count"].data_ptr(), r["obs"].data_ptr()
+
+
+def _scratch256(nbytes: int, dev) -> torch.Tensor:
+    """scratch for the voxel-map calls: they want 256-byte alignment, which a fresh allocation of the caching allocator has"""
+    s = _lib.scratch(nbytes, dev)
+    assert s.data_ptr() % 256 == 0
+    return s
+
+
+class VoxelMap:
+    """The map: `voxel_size` (0.2 m by default: twice the bank's 0.1 m downsample, so a surface seen by one scan fills its
+    voxels), `origin` (3 floats; None = the translation of the first pose inserted, read on the host) and up to 2^21 voxels per
+    axis around it.  capacity=None: the record buffers grow as needed and `insert` takes one [SYNC] per chunk to size them, as
+    `CloudBank.add` does.  capacity=rows reserves two record buffers of that size: `insert` then has no host synchronisation
+    (device picks and poses, explicit points_capacity) and can be captured; a chunk that would overflow is dropped whole and
+    sets STATUS_CAPACITY, the map keeps what it holds."""
+
+    def __init__(self, voxel_size: float = 0.2, origin=None, capacity: Optional[int] = None, device=None,
+                 chunk_points: int = 4_000_000):
+        v = float(voxel_size)
+        if not (v > 0.0 and np.isfinite(v)):
+            raise ValueError("VoxelMap: voxel_size must be positive and finite")
+        if origin is not None:
+            origin = np.asarray(origin, dtype=np.float64)
+            if origin.shape != (3,) or not np.isfinite(origin).all():
+                raise ValueError("VoxelMap: origin is three finite numbers")
+        if capacity is not None and not 1 <= int(capacity) < 2 ** 31:
+            raise ValueError("VoxelMap: capacity in [1, 2^31)")
+        if int(chunk_points) < 1:
+            raise ValueError("VoxelMap: chunk_points must be positive")
+        self.voxel_size, self.origin, self.capacity = v, origin, None if capacity is None else int(capacity)
+        self.device, self.chunk_points = device, int(chunk_points)
+        self._buf = [None, None]          # ping-pong record buffers
+        self._cur = 0
+        self._status = None
+        self._work = {}                   # (points_capacity, n_obs) -> chunk records and scratch, kept for replays
+
+    # ------------------------------------------------------------------ state
+    def _dev(self):
+        if self.device is None:
+            self.device = _lib.require_gpu()
+        return self.device
+
+    def _ensure(self):
+        if self._status is None:
+            dev = self._dev()
+            self._status = torch.zeros((), dtype=torch.int32, device=dev)
+            rows = self.capacity if self.capacity is not None else 1
+            self._buf = [_records(rows, dev), _records(rows, dev)]
+
+    def _origin_c(self):
+        return (ctypes.c_double * 3)(*[float(v) for v in self.origin])
+
+    @property
+    def records(self) -> Dict[str, torch.Tensor]:
+        """the live buffer: keys (rows) int64 (the 63-bit key), sums (rows,3) int64, count, obs (rows) int32, n () int64"""
+        self._ensure()
+        return self._buf[self._cur]
+
+    @property
+    def n_voxels(self) -> int:
+        """[SYNC]"""
+        return 0 if self._status is None else int(self.records["n"].item())
+
+    @property
+    def status(self) -> int:
+        """[SYNC] OR of the STATUS_* bits of every call so far"""
+        return 0 if self._status is None else int(self._status.item())
+
+    def clear(self) -> "VoxelMap":
+        """empty map, status 0, buffers kept"""
+        if self._status is not None:
+            self._cur = 0
+            self._buf[0]["n"].zero_()
+            self._status.zero_()
+        return self
+
+    # ------------------------------------------------------------------ insert
+    def _chunk(self, bank, pk, ps, n_obs: int, points_capacity: int):
+        lib = _lib.load()
+        dev = self._dev()
+        key = (int(points_capacity), int(n_obs))
+        work = self._work.get(key)
+        if work is None:
+            work = {"rec": _records(points_capacity, dev),
+                    "s_int": _scratch256(lib.egonn_voxel_map_integrate_scratch_bytes(points_capacity, n_obs), dev)}
+            if self.capacity is not None:
+                self._work[key] = work
+        chunk = work["rec"]
+        rows_c = max(int(points_capacity), 1)
+        n_bank = bank.n_points
+        _lib.call(dev, lib.egonn_voxel_map_integrate, _lib._ptr(bank.points) if n_bank else None, n_bank, bank.offsets().data_ptr(),
+                  len(bank), pk.data_ptr(), ps.data_ptr(), n_obs, self._origin_c(), self.voxel_size, int(points_capacity),
+                  *_rec_ptrs(chunk), rows_c, chunk["n"].data_ptr(), self._status.data_ptr(), work["s_int"].data_ptr(),
+                  work["s_int"].numel() * 8)
+        A = self._buf[self._cur]
+        rows_a = A["keys"].shape[0]
+        if self.capacity is None:
+            n_a, n_c = torch.stack([A["n"], chunk["n"]]).tolist()            # [SYNC] one copy per chunk: sizes the next buffer
+            need = n_a + n_c
+            out = self._buf[1 - self._cur]
+            if out["keys"].shape[0] < max(need, rows_a):
+                out = self._buf[1 - self._cur] = _records(max(need + need // 2, rows_a), dev)
+        else:
+            out = self._buf[1 - self._cur]
+        rows_o = out["keys"].shape[0]
+        mkey = ("merge", rows_a, rows_c, rows_o)
+        s_mrg = self._work.get(mkey)
+        if s_mrg is None:
+            s_mrg = _scratch256(lib.egonn_voxel_map_merge_scratch_bytes(rows_a, rows_c, rows_o), dev)
+            if self.capacity is not None:
+                self._work[mkey] = s_mrg
+        _lib.call(dev, lib.egonn_voxel_map_merge, *_rec_ptrs(A), A["n"].data_ptr(), rows_a, *_rec_ptrs(chunk), chunk["n"].data_ptr(),
+                  rows_c, *_rec_ptrs(out), rows_o, out["n"].data_ptr(), self._status.data_ptr(), s_mrg.data_ptr(), s_mrg.numel() * 8)
+        out["_keep"] = (chunk, work, s_mrg, pk, ps)
+        self._cur = 1 - self._cur
+
+    def insert(self, bank, poses, pick=None, points_capacity: Optional[int] = None) -> "VoxelMap":
+        """Fuses clouds pick[k] of `bank` (a `CloudBank`; pick=None: all of them, in order) under poses[k] ((n,4,4) float64, scan
+        frame -> map frame) into the map.  Host picks are chunked to <= 4096 observations and about `chunk_points` points; each
+        chunk is integrated, then merged into the other record buffer.  Device picks (one chunk, <= 4096) need
+        points_capacity, a bound on their clouds' total.  Returns self."""
+        n_bank = len(bank)
+        on_dev = torch.is_tensor(pick) and pick.is_cuda
+        n = n_bank if pick is None else len(pick)
+        _check_poses("VoxelMap.insert", poses, n)
+        if n < 1:
+            raise ValueError("VoxelMap.insert: at least one observation")
+        if on_dev:
+            if points_capacity is None or not 0 <= int(points_capacity) < 2 ** 31:
+                raise ValueError("VoxelMap.insert: device picks need points_capacity in [0, 2^31)")
+            if n > MAX_OBS:
+                raise ValueError(f"VoxelMap.insert: at most {MAX_OBS} device picks per call, got {n}")
+        else:
+            p = np.arange(n_bank, dtype=np.int64) if pick is None else np.asarray(pick, dtype=np.int64).reshape(-1)
+            if p.size and (p.min() < 0 or p.max() >= n_bank):
+                raise ValueError(f"VoxelMap.insert: pick outside [0, {n_bank})")
+            sizes = bank.sizes()[p]
+        if self.origin is None:
+            if torch.is_tensor(poses) and poses.is_cuda:
+                raise ValueError("VoxelMap.insert: device poses need an explicit origin")
+            o = np.asarray(poses[0], dtype=np.float64)[:3, 3].copy()
+            if not np.isfinite(o).all():
+                raise ValueError("VoxelMap.insert: the first pose's translation is not finite; give an origin")
+            self.origin = o
+        self._ensure()
+        dev = self._dev()
+        ps = _lib.as_dev(poses, dev, torch.float64)
+        if on_dev:
+            self._chunk(bank, _lib.as_dev(pick, dev, torch.int32), ps, n, int(points_capacity))
+            return self
+        lo = 0
+        while lo < n:
+            hi, rows = lo + 1, int(sizes[lo])
+            while hi < n and hi - lo < MAX_OBS and rows + int(sizes[hi]) <= self.chunk_points:
+                rows += int(sizes[hi])
+                hi += 1
+            pk = torch.from_numpy(p[lo:hi].astype(np.int32)).to(dev)
+            self._chunk(bank, pk, ps[lo:hi].contiguous(), hi - lo, rows)
+            lo = hi
+        return self
+
+    # ------------------------------------------------------------------ read
+    def _select(self, boxes, n_boxes, relative, min_count, min_obs, capacity, with_counts):
+        lib = _lib.load()
+        dev = self._dev()
+        R = self.records
+        rows = R["keys"].shape[0]
+        n_seg = max(n_boxes, 1)
+        off = torch.empty((n_seg + 1,), dtype=torch.int64, device=dev)
+        status = torch.zeros((), dtype=torch.int32, device=dev)
+        scratch = _scratch256(lib.egonn_voxel_map_select_scratch_bytes(rows, n_boxes), dev)
+        head = (*_rec_ptrs(R), R["n"].data_ptr(), rows, self._origin_c(), self.voxel_size, int(min_count), int(min_obs),
+                _lib._ptr(boxes), n_boxes, int(bool(relative)))
+        if capacity is None:                                                 # the sizing call, then [SYNC] its total
+            _lib.call(dev, lib.egonn_voxel_map_select, *head, None, off.data_ptr(), None, None, 0, status.data_ptr(),
+                      scratch.data_ptr(), scratch.numel() * 8)
+            capacity = int(off[-1].item())
+        capacity = int(capacity)
+        pts = torch.empty((max(capacity, 1), 3), dtype=torch.float64, device=dev)
+        cnt = torch.empty((max(capacity, 1),), dtype=torch.int32, device=dev) if with_counts else None
+        obs = torch.empty((max(capacity, 1),), dtype=torch.int32, device=dev) if with_counts else None
+        _lib.call(dev, lib.egonn_voxel_map_select, *head, pts.data_ptr(), off.data_ptr(), _lib._ptr(cnt), _lib._ptr(obs), capacity,
+                  status.data_ptr(), scratch.data_ptr(), scratch.numel() * 8)
+        return {"points": pts[:capacity], "offsets": off, "count": cnt, "observations": obs, "status": status,
+                "_keep": (scratch, boxes, R)}
+
+    def points(self, min_count: int = 1, min_observations: int = 1) -> Dict[str, torch.Tensor]:
+        """The map as points: the centroids of the voxels with at least min_count points seen by at least min_observations
+        scans, ascending key order -> {'points' (m,3) f64, 'count' (m,) int32, 'observations' (m,) int32} on the device.
+        [SYNC] once, for m."""
+        _check_filters("VoxelMap.points", min_count, min_observations)
+        if self._status is None:
+            raise ValueError("VoxelMap.points: the map is empty (nothing inserted)")
+        r = self._select(None, 0, False, min_count, min_observations, None, True)
+        m = r["points"].shape[0]
+        return {"points": r["points"], "count": r["count"][:m], "observations": r["observations"][:m]}
+
+    def submaps(self, centers, half_extent, min_count: int = 1, min_observations: int = 1, relative: bool = True,
+                capacity: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """One submap per centre (n,3) in the map frame: the centroids c with centre - half <= c < centre + half per axis
+        (half_extent: one number or three), ascending key order, as c - centre when `relative` (what `icp_pairs` wants as tgt:
+        its search grid takes local coordinates) -> {'points' (capacity,3) f64, 'offsets' (n+1,) int64, 'status' () int32} on the
+        device.  capacity=None sizes the output exactly ([SYNC] once); with a capacity there is no host synchronisation, and more
+        points than it give STATUS_CAPACITY, all offsets zero."""
+        half = _check_boxes("VoxelMap.submaps", centers, half_extent)
+        _check_filters("VoxelMap.submaps", min_count, min_observations)
+        if capacity is not None and not 0 <= int(capacity) < 2 ** 31:
+            raise ValueError("VoxelMap.submaps: capacity in [0, 2^31)")
+        if self._status is None:
+            raise ValueError("VoxelMap.submaps: the map is empty (nothing inserted)")
+        dev = self._dev()
+        c = _lib.as_dev(centers, dev, torch.float64)
+        boxes = torch.cat([c, torch.from_numpy(half).to(dev).expand(c.shape[0], 3)], dim=1).contiguous()
+        r = self._select(boxes, c.shape[0], relative, min_count, min_observations, capacity, False)
+        return {"points": r["points"], "offsets": r["offsets"], "status": r["status"], "_keep": r["_keep"]}
+
+    # ------------------------------------------------------------------ files
+    def save(self, path: str) -> None:
+        """one .npz: the records, voxel_size, origin.  [SYNC]"""
+        if self._status is None:
+            raise ValueError("VoxelMap.save: the map is empty (nothing inserted)")
+        R, n = self.records, self.n_voxels
+        np.savez(path, voxel_size=np.float64(self.voxel_size), origin=np.asarray(self.origin, dtype=np.float64),
+                 status=np.int32(self.status), **{f: R[f][:n].cpu().numpy() for f in _FIELDS})
+
+    @classmethod
+    def load(cls, path: str, capacity: Optional[int] = None, device=None) -> "VoxelMap":
+        with np.load(path) as z:
+            missing = [k for k in _FIELDS + ("voxel_size", "origin") if k not in z.files]
+            if missing:
+                raise ValueError(f"{path}: not a voxel map (missing {missing})")
+            data = {k: z[k] for k in z.files}
+        n = len(data["keys"])
+        if capacity is not None and int(capacity) < n:
+            raise ValueError(f"VoxelMap.load: capacity {capacity} below the file's {n} voxels")
+        m = cls(float(data["voxel_size"]), data["origin"], capacity, device)
+        m._ensure()
+        if capacity is None:
+            m._buf[0] = _records(n, m._dev())
+        for f in _FIELDS:
+            m._buf[0][f][:n] = torch.from_numpy(data[f]).to(m._dev())
+        m._buf[0]["n"].fill_(n)
+        m._status.fill_(int(data.get("status", 0)))
+        return m
+
+
+def build_map(bank, poses, voxel_size: float = 0.2, **kw) -> VoxelMap:
+    """every cloud of `bank` under its pose: VoxelMap(voxel_size, **kw).insert(bank, poses)"""
+    return VoxelMap(voxel_size, **kw).insert(bank, poses)
+
+
+def refine_against_map(vmap: VoxelMap, bank, pick, poses_init, half_extent=30.0, min_count: int = 1, min_observations: int = 1,
+                       **icp_kw) -> Dict[str, torch.Tensor]:
+    """Scan-to-map ICP by composition: for scan pick[k] of `bank` with the initial pose poses_init[k] (scan -> map frame), the
+    source is its cloud (`bank.gather`), the target the submap of `vmap` around the pose's translation (`submaps`, relative),
+    T_init = translate(-centre) @ pose_init, `icp_pairs` runs on that and pose = translate(+centre) @ T.  Host picks.
+    -> {'poses' (n,4,4) f64, 'fitness', 'inlier_rmse' (n,) f64, 'status' (n,) int32 (ICP_* bits)} on the device.  [SYNC] once,
+    to size the submaps."""
+    n = len(pick)
+    _check_poses("refine_against_map", poses_init, n)
+    if not 1 <= n <= MAX_OBS:
+        raise ValueError(f"refine_against_map: 1 to {MAX_OBS} scans per call, got {n}")
+    dev = vmap._dev()
+    X = _lib.as_dev(poses_init, dev, torch.float64)
+    centre = X[:, :3, 3].contiguous()
+    tgt = vmap.submaps(centre, half_extent, min_count, min_observations, relative=True)
+    src = bank.gather(pick)
+    T0 = X.clone()
+    T0[:, :3, 3] = 0.0                                                       # t - centre with centre = t
+    r = _reg.icp_pairs(src["points"], src["offsets"], tgt["points"], tgt["offsets"], T0, **icp_kw)
+    poses = r["T"].clone()
+    poses[:, :3, 3] += centre
+    return {"poses": poses, "fitness": r["fitness"], "inlier_rmse": r["inlier_rmse"], "status": r["status"],
+            "_keep": (src, tgt, r)}

@@ -918,6 +918,60 @@ int egonn_relative_poses(const double* poses, int64_t n_poses, const int32_t* id
 int egonn_gather_clouds(const double* bank, int64_t n_bank, const int64_t* bank_offsets, int64_t n_clouds, const int32_t* pick,
                         int n_pick, double* out, int64_t capacity, int64_t* out_offsets, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ voxel map (csrc/voxel_map.hip)
+ * A resident global voxel map of posed scans.  The map is defined by `voxel` (fp64, finite, > 0), `origin` (3 HOST doubles,
+ * finite) and 21 index bits per axis with bias 2^20.  Observation k is the bank cloud pick[k] under the pose X_k ((4,4) fp64
+ * row-major, scan frame -> map frame); for a point p of it, per axis a and with every operation rounded to fp64 (no FMA):
+ *     t'_a = X_k[a][3] - origin_a                                   (first: poses may carry UTM-sized translations)
+ *     w_a  = ((X_k[a][0] p_0 + X_k[a][1] p_1) + X_k[a][2] p_2) + t'_a
+ *     s_a  = w_a / voxel;   i_a = floor(s_a);   the point is valid iff every i_a is finite and in [-2^20, 2^20)
+ *     key  = (i_x + 2^20) << 42 | (i_y + 2^20) << 21 | (i_z + 2^20)                                    (bit 63 clear)
+ *     q_a  = min((int64) floor((s_a - i_a) * 2^30), 2^30 - 1)       (s_a = -1e-20: i_a = -1 and s_a - i_a rounds to 1.0)
+ * A voxel record is key (uint64), sum_q[3] (int64: the sums of its points' q), count (int32: points) and obs (int32:
+ * observations that put at least one point in it), held as four arrays (keys (rows), sums (rows,3), count (rows), obs
+ * (rows): 40 bytes per voxel), sorted by ascending key, keys unique.  Its centroid is
+ *     c_a = ((double) i_a + (double) sum_q_a / ((double) count * 2^30)) * voxel + origin_a.
+ * The sums are integers: inserting observations in any number of batches and in any order gives the bits of one call, and the
+ * kernels reduce a voxel's run in whatever order the hardware takes (integer atomics only; no floating-point atomic).
+ * Every call: scratch 256-byte aligned and at least *_scratch_bytes (-1 on bad arguments), no host synchronisation,
+ * capturable; grids are sized from the capacities, the live counts (n_out, n_a, n_b, n_dev: DEVICE int64, clipped to their
+ * capacity) stay on the device.  *status (DEVICE int32) is OR-ed into, never cleared: the caller zeroes it. */
+enum { EGONN_VMAP_STATUS_RANGE = 1,       /* a point was dropped: an index outside 21 bits or a non-finite coordinate */
+       EGONN_VMAP_STATUS_CAPACITY = 2,    /* more points / voxels than the capacity: see each call */
+       EGONN_VMAP_STATUS_BAD_INDEX = 4 }; /* a pick outside the bank: that observation contributes nothing */
+/* The records of observations 0..n_obs) (1 <= n_obs <= 4096): bank (n_bank,3) f64 with bank_offsets (n_clouds+1) DEVICE int64
+ * (the layout egonn_voxel_downsample returns), pick (n_obs) DEVICE int32, poses (n_obs,4,4) DEVICE f64.  points_capacity
+ * (< 2^31) is a host bound on the picked clouds' total, as egonn_gather_clouds takes `capacity`; more points than that set
+ * CAPACITY and give n_out = 0.  out_* hold `capacity` rows; more voxels than that set CAPACITY, n_out = 0 and nothing is
+ * written.  A dropped point sets RANGE and every other point is fused as if it were absent.  obs of a voxel counts the distinct
+ * positions k among its points: the same cloud picked twice is two observations. */
+int64_t egonn_voxel_map_integrate_scratch_bytes(int64_t points_capacity, int n_obs);
+int egonn_voxel_map_integrate(const double* bank, int64_t n_bank, const int64_t* bank_offsets, int64_t n_clouds, const int32_t* pick,
+                              const double* poses, int n_obs, const double* origin, double voxel, int64_t points_capacity,
+                              uint64_t* out_keys, int64_t* out_sums, int32_t* out_count, int32_t* out_obs, int64_t capacity,
+                              int64_t* n_out, int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);
+/* out = the union of records A (n_a rows) and B (n_b rows) by key; for a key in both, sum_q, count and obs are added (the
+ * caller guarantees disjoint observation sets).  capacity_out >= capacity_a; out is neither A nor B.  A union beyond
+ * capacity_out sets CAPACITY, out becomes A unchanged (n_out = n_a) and B is dropped whole. */
+int64_t egonn_voxel_map_merge_scratch_bytes(int64_t capacity_a, int64_t capacity_b, int64_t capacity_out);
+int egonn_voxel_map_merge(const uint64_t* a_keys, const int64_t* a_sums, const int32_t* a_count, const int32_t* a_obs,
+                          const int64_t* n_a, int64_t capacity_a, const uint64_t* b_keys, const int64_t* b_sums,
+                          const int32_t* b_count, const int32_t* b_obs, const int64_t* n_b, int64_t capacity_b, uint64_t* out_keys,
+                          int64_t* out_sums, int32_t* out_count, int32_t* out_obs, int64_t capacity_out, int64_t* n_out,
+                          int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);
+/* Centroids of the voxels with count >= min_count and obs >= min_obs, in ascending key order, per box: boxes (n_boxes,6)
+ * DEVICE f64 = centre and half extents in the map frame (n_boxes <= 4096; null with n_boxes = 0: the whole map is one
+ * segment).  A voxel belongs to box b iff centre_a - half_a <= c_a < centre_a + half_a on every axis.  relative (needs boxes):
+ * the output point is c - centre, the local coordinates egonn_icp_pairs wants as tgt.  out_points (capacity,3),
+ * out_offsets (max(n_boxes,1)+1) DEVICE int64, out_count / out_obs (capacity) nullable.  More selected voxels than
+ * `capacity`: CAPACITY, all offsets zero, nothing written (egonn_gather_clouds' rule).  out_points = null is the sizing call:
+ * the offsets are written and nothing else. */
+int64_t egonn_voxel_map_select_scratch_bytes(int64_t capacity_map, int n_boxes);
+int egonn_voxel_map_select(const uint64_t* keys, const int64_t* sums, const int32_t* count, const int32_t* obs, const int64_t* n_dev,
+                           int64_t capacity_map, const double* origin, double voxel, int min_count, int min_obs, const double* boxes,
+                           int n_boxes, int relative, double* out_points, int64_t* out_offsets, int32_t* out_count, int32_t* out_obs,
+                           int64_t capacity, int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ relocalisation against a keypoint map (csrc/relocalize.hip, csrc/match.hip)
  * A query scan is placed in the map frame by registering it against its top-k retrieved map entries (egonn_knn) and keeping
  * the entry with the most inliers: P_query = P_map[best] @ T, T = the transform of egonn_registration_finish, which maps query
