@@ -28,7 +28,7 @@ from .loop_closure import knn_window, time_windows, detect_loops, LoopDetector, 
 from .pose_graph import (pose_graph_cost, pose_graph_hessvec, optimize_pose_graph, odometry_edges, loop_edges,
                          optimize_trajectory)
 from .loop_consistency import filter_loops, loop_cycle_errors
-from .mapping import VoxelMap, build_map, refine_against_map
+from .mapping import VoxelMap, build_map, refine_against_map, NDTMap, build_ndt_map
 from .scan_context import ScanContext, ScanContextManager, sc2rk, distance_sc, evaluate as evaluate_scan_context
 
 __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "MinkHead", "MinkTrunk",
@@ -46,5 +46,5 @@ __all__ = ["ModelParams", "model_factory", "create_egonn_model", "MinkGL", "Mink
            "KeypointMap", "verify_candidates", "Relocalizer", "evaluate_relocalization",
            "knn_window", "time_windows", "detect_loops", "LoopDetector", "evaluate_loop_closure",
            "pose_graph_cost", "pose_graph_hessvec", "optimize_pose_graph", "odometry_edges", "loop_edges", "optimize_trajectory",
-           "filter_loops", "loop_cycle_errors", "VoxelMap", "build_map", "refine_against_map",
+           "filter_loops", "loop_cycle_errors", "VoxelMap", "build_map", "refine_against_map", "NDTMap", "build_ndt_map",
            "ScanContext", "ScanContextManager", "sc2rk", "distance_sc", "evaluate_scan_context"]

@@ -172,6 +172,13 @@ _SIGS = [
     ("egonn_voxel_map_select_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
     ("egonn_voxel_map_select", C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int, _P,
                                          C.c_int, C.c_int, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
+    ("egonn_ndt_accumulate_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_ndt_accumulate", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int64,
+                                       _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("egonn_ndt_finalize", C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_double, C.c_int, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("egonn_ndt_register_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_ndt_register", C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_double, C.c_int, C.c_int,
+                                     C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     ("egonn_match_candidates_scratch_bytes", C.c_int64, [C.c_int, C.c_int, C.c_int]),
     ("egonn_match_candidates", C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                          C.c_int64, _P]),

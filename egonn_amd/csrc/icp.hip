@@ -39,6 +39,8 @@
 #include "../../include/egonn_hip.h"
 #include "common.h"
 #include "horn.h"
+#include "jacobi3.h"
+#include "plane_step.h"
 
 #pragma clang fp contract(off)
 
@@ -605,60 +607,7 @@ __global__ __launch_bounds__(ICP_WG) void icp_search_kernel(const IcpPair* __res
   if (t < NP) partial[(size_t)flat * NP + t] = ((s_red[t][0] + s_red[t][1]) + s_red[t][2]) + s_red[t][3];
 }
 
-// Point-to-plane step: solves A x = -b (A = sum J J^T from its 21 upper entries row by row, b = sum J r) by LDL^T without
-// pivoting and returns U = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)] as (U[9], ut[3]).  False, with nothing to rely on in U, when
-// a pivot d_i is not > 2^-40 A_ii (A's own diagonal: fp64 leaves ~2^-52 relative rounding in a pivot, twelve bits above that
-// separate a rank-deficient scene from rounding noise) or x is not finite.
-__device__ static bool icp_plane_step(const double* __restrict__ s, double* U, double* ut) {
-  double A[6][6], L[6][6], d[6], x[6];
-  {
-    int e = 2;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int b = a; b < 6; ++b) A[a][b] = A[b][a] = s[e++];
-  }
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double dj = A[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) dj -= (L[j][k] * L[j][k]) * d[k];
-    ok = ok && dj > 0x1p-40 * A[j][j];                  // false for NaN as well
-    d[j] = ok ? dj : 1.0;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double l = A[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) l -= (L[i][k] * L[j][k]) * d[k];
-      L[i][j] = l / d[j];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {                          // L y = -b
-    double y = -s[23 + i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) y -= L[i][k] * x[k];
-    x[i] = y;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) x[i] = x[i] / d[i];
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {                         // L^T x = z
-    double y = x[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) y -= L[k][i] * x[k];
-    x[i] = y;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) ok = ok && fabs(x[i]) < INFINITY;
-  const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sc = sin(x[2]), cc = cos(x[2]);
-  U[0] = cb * cc, U[1] = (sa * sb) * cc - ca * sc, U[2] = (ca * sb) * cc + sa * sc;
-  U[3] = cb * sc, U[4] = (sa * sb) * sc + ca * cc, U[5] = (ca * sb) * sc - sa * cc;
-  U[6] = -sb, U[7] = sa * cb, U[8] = ca * cb;
-  ut[0] = x[3], ut[1] = x[4], ut[2] = x[5];
-  return ok;
-}
+// icp_plane_step (plane_step.h): the 6 x 6 solve by LDL^T and the update it stands for, shared with ndt.hip
 
 // EST as in icp_search_kernel.  One loop, two estimators: the evaluation, the stop rule and the traces are the same code.
 template <int EST>
@@ -756,47 +705,7 @@ __global__ __launch_bounds__(ICP_WG) void nrm_status_kernel(const double* __rest
     status[c] = (bad ? EGONN_NORMALS_STATUS_RANGE : 0) | ((hi > lo ? hi - lo : 0) < knn ? EGONN_NORMALS_STATUS_FEW_POINTS : 0);
 }
 
-// eigen-decomposition of the symmetric 3 x 3 matrix A by cyclic Jacobi, the schedule of horn_top_eigenvector (horn.h): A's diagonal
-// becomes the eigenvalues, the columns of V the eigenvectors
-__device__ static inline void nrm_jacobi3(double A[3][3], double V[3][3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    if (fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]) == 0.0) break;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = i + 1; j < 3; ++j) {
-        const double apq = A[i][j];
-        if (apq != 0.0) {
-          const double theta = (A[j][j] - A[i][i]) / (2.0 * apq);
-          const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {              // A <- A J
-            const double aki = A[k][i], akj = A[k][j];
-            A[k][i] = c * aki - s * akj;
-            A[k][j] = s * aki + c * akj;
-          }
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {              // A <- J^T A
-            const double aik = A[i][k], ajk = A[j][k];
-            A[i][k] = c * aik - s * ajk;
-            A[j][k] = s * aik + c * ajk;
-          }
-          A[i][j] = A[j][i] = 0.0;
-#pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            const double vki = V[k][i], vkj = V[k][j];
-            V[k][i] = c * vki - s * vkj;
-            V[k][j] = s * vki + c * vkj;
-          }
-        }
-      }
-  }
-}
+// nrm_jacobi3 (jacobi3.h): cyclic Jacobi on a symmetric 3 x 3 matrix, shared with ndt.hip
 
 // K: the capacity of a lane's sorted list, kept in registers (every index below is a compile-time constant after unrolling)
 template <int K>

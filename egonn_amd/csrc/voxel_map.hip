@@ -21,22 +21,14 @@
 // No call synchronises with the host; grids are sized from capacities and the live counts stay on the device.
 #include "../../include/egonn_hip.h"
 #include "common.h"
+#include "voxel_key.h"                                   // the frame, the key and the residuals of a point; shared with ndt.hip
 
 #pragma clang fp contract(off)
 
 namespace egonn {
 
-static constexpr int VM_WG = 256;
-static constexpr int VM_BITS = 21;                       // index bits per axis
-static constexpr int64_t VM_BIAS = 1ll << 20;
-static constexpr int64_t VM_ONE = 1ll << 30;             // fixed-point one of a residual
-static constexpr uint64_t VM_MASK = (1ull << VM_BITS) - 1ull;
-static constexpr uint64_t VM_INVALID = ~0ull;            // key of a dropped point (valid keys have bit 63 clear): sorts last
-static constexpr int VM_MAX_OBS = 4096;
 static constexpr int VM_MAX_BOXES = 4096;
 static constexpr int VM_MAX_SLICE_ROWS = 65536;          // slice counters of one select call
-
-struct VmFrame { double org[3]; double voxel; };
 
 struct VmRec {                                           // struct-of-arrays view of records
   uint64_t* keys;
@@ -52,17 +44,6 @@ struct VmCRec {
 };
 
 __device__ static inline int64_t vm_min(int64_t a, int64_t b) { return a < b ? a : b; }
-__device__ static inline int64_t vm_live(const int64_t* __restrict__ n_dev, int64_t cap) { return clipi(*n_dev, cap); }
-
-// first position in [0, n) whose key is >= k
-__device__ static inline int64_t vm_lower_bound(const uint64_t* __restrict__ keys, int64_t n, uint64_t k) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 // one workgroup: exclusive scan of cnt[0..n) in place, the total to every thread
 __device__ static inline int64_t vm_block_scan(int32_t* __restrict__ cnt, int64_t n, int64_t* s_sum) {
@@ -93,56 +74,7 @@ __device__ static inline int64_t vm_block_scan(int32_t* __restrict__ cnt, int64_
 }
 
 // ------------------------------------------------------------------ integrate
-// picked cloud of observation k: [lo, hi) in the bank, empty for a pick outside it
-__device__ static inline bool vm_pick_range(const int64_t* __restrict__ off, int64_t n_bank, int64_t n_clouds, int32_t p, int64_t* lo,
-                                            int64_t* hi) {
-  *lo = *hi = 0;
-  if (p < 0 || (int64_t)p >= n_clouds) return false;
-  const int64_t a = clipi(off[p], n_bank), b = clipi(off[p + 1], n_bank);
-  *lo = a;
-  *hi = b > a ? b : a;
-  return true;
-}
-
-__global__ __launch_bounds__(VM_WG) void vm_offsets_kernel(const int64_t* __restrict__ off, int64_t n_bank, int64_t n_clouds,
-                                                           const int32_t* __restrict__ pick, int n_obs, int64_t points_capacity,
-                                                           int64_t* __restrict__ obs_off, int32_t* __restrict__ status) {
-  __shared__ int64_t s_sum[VM_WG + 1];
-  const int t = threadIdx.x;
-  const int per = (n_obs + VM_WG - 1) / VM_WG;
-  const int k0 = min(t * per, n_obs), k1 = min(k0 + per, n_obs);
-  int64_t s = 0;
-  bool bad = false;
-  for (int k = k0; k < k1; ++k) {
-    int64_t lo, hi;
-    bad = !vm_pick_range(off, n_bank, n_clouds, pick[k], &lo, &hi) || bad;
-    s += hi - lo;
-  }
-  if (bad) atomicOr(status, EGONN_VMAP_STATUS_BAD_INDEX);
-  s_sum[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int64_t acc = 0;
-    for (int k = 0; k < VM_WG; ++k) {
-      const int64_t v = s_sum[k];
-      s_sum[k] = acc;
-      acc += v;
-    }
-    s_sum[VM_WG] = acc;
-    if (acc > points_capacity) atomicOr(status, EGONN_VMAP_STATUS_CAPACITY);
-  }
-  __syncthreads();
-  const bool fail = s_sum[VM_WG] > points_capacity;      // more points than the caller made room for: no point at all
-  int64_t acc = s_sum[t];
-  for (int k = k0; k < k1; ++k) {
-    int64_t lo, hi;
-    vm_pick_range(off, n_bank, n_clouds, pick[k], &lo, &hi);
-    obs_off[k] = fail ? 0 : acc;
-    acc += hi - lo;
-  }
-  if (t == 0) obs_off[n_obs] = fail ? 0 : s_sum[VM_WG];
-}
-
+// vm_offsets_kernel (voxel_key.h): the picked clouds' offsets, BAD_INDEX, the point capacity
 __global__ __launch_bounds__(VM_WG) void vm_key_kernel(const double* __restrict__ bank, int64_t n_bank, const int64_t* __restrict__ off,
                                                        int64_t n_clouds, const int32_t* __restrict__ pick,
                                                        const double* __restrict__ poses, int n_obs, VmFrame F,
@@ -150,39 +82,13 @@ __global__ __launch_bounds__(VM_WG) void vm_key_kernel(const double* __restrict_
                                                        uint32_t* __restrict__ vals, int4* __restrict__ q4, int32_t* __restrict__ status) {
   const int64_t i = (int64_t)blockIdx.x * VM_WG + threadIdx.x;
   if (i >= clipi(obs_off[n_obs], cap)) return;
-  int lo = 0, hi = n_obs - 1;                             // the last k with obs_off[k] <= i: its cloud is not empty, i < total
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (obs_off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  const int k = lo;
-  int64_t c0, c1;
-  vm_pick_range(off, n_bank, n_clouds, pick[k], &c0, &c1);
-  const int64_t src = c0 + (i - obs_off[k]);
+  int64_t src;
+  const int k = vm_point_source(obs_off, n_obs, off, n_bank, n_clouds, pick, i, &src);
   uint64_t key = VM_INVALID;
   int4 q = make_int4(0, 0, 0, k);
-  if (src >= c0 && src < c1) {
-    const double* p = bank + src * 3;
-    const double* X = poses + (int64_t)k * 16;
-    const double p0 = p[0], p1 = p[1], p2 = p[2];
-    uint64_t idx[3];
+  if (src >= 0) {
     int r[3];
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double tt = X[a * 4 + 3] - F.org[a];
-      const double w = ((X[a * 4] * p0 + X[a * 4 + 1] * p1) + X[a * 4 + 2] * p2) + tt;
-      const double s = w / F.voxel;
-      const double f = floor(s);
-      ok = ok && f >= -(double)VM_BIAS && f < (double)VM_BIAS;             // false for NaN / inf as well
-      const int64_t qa = ok ? (int64_t)floor((s - f) * (double)VM_ONE) : 0;
-      idx[a] = ok ? (uint64_t)((int64_t)f + VM_BIAS) : 0ull;
-      r[a] = (int)(qa < VM_ONE - 1 ? qa : VM_ONE - 1);
-    }
-    if (ok) {
-      key = (idx[0] << (2 * VM_BITS)) | (idx[1] << VM_BITS) | idx[2];
-      q = make_int4(r[0], r[1], r[2], k);
-    }
+    if (vm_point_key(bank + src * 3, poses + (int64_t)k * 16, F, &key, r)) q = make_int4(r[0], r[1], r[2], k);
   }
   if (key == VM_INVALID) atomicOr(status, EGONN_VMAP_STATUS_RANGE);
   keys[i] = key;
@@ -322,14 +228,6 @@ static VmLayout vm_layout(int64_t points_capacity, int n_obs) {
   L.sort = take(L.sort_bytes);
   L.total = o;
   return L;
-}
-
-static bool vm_frame_ok(const double* origin, double voxel) {
-  auto fin = [](double x) { return x > -INFINITY && x < INFINITY; };       // false for NaN
-  return origin && voxel > 0.0 && fin(voxel) && fin(origin[0]) && fin(origin[1]) && fin(origin[2]);
-}
-static bool vm_integrate_shape_ok(int64_t points_capacity, int n_obs) {
-  return points_capacity >= 0 && points_capacity < (1ll << 31) && n_obs >= 1 && n_obs <= VM_MAX_OBS;
 }
 
 // ------------------------------------------------------------------ merge

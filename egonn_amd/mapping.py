@@ -6,8 +6,13 @@ A voxel record is (key, integer sums of the points' residuals, point count, obse
 its output point; `observations` (how many scans put a point there) is the one filter against dynamic objects.  There is no
 torch or numpy fallback for the device arithmetic.
 
-Not here: removing observations again (the integer sums make it possible later), `Relocalizer(refine="map")`, normals or
-covariances per voxel, and cutting the sort's 63 key bits by a known extent."""
+`NDTMap` is the NDT layer over a map's keys (csrc/ndt.hip): exact integer second moments per voxel, one
+Gaussian per voxel (mean, information matrix, eigenvalues, normal), and scan-to-map registration against them, which needs
+no submap, no per-call grid and no sort.  `refine_against_map(method="ndt")` and `Relocalizer(ndt_map=...)` run on it.
+
+Not here: removing observations again (the integer sums make it possible later), cutting the sort's 63 key bits by a known
+extent, moments carried through `insert` / merge for an incrementally growing NDT map (an `NDTMap` is a snapshot), the full
+Newton step of the NDT score with a line search, and distribution-to-distribution NDT."""
 from __future__ import annotations
 
 import ctypes
@@ -312,17 +317,223 @@ def build_map(bank, poses, voxel_size: float = 0.2, **kw) -> VoxelMap:
     return VoxelMap(voxel_size, **kw).insert(bank, poses)
 
 
+NDT_MIN_POINTS = 6            # a choice, not a tuned value: twice the three points a covariance needs at the least
+NDT_MIN_EIG_RATIO = 0.01      # a choice: a flat voxel is given a thickness of a tenth of its largest extent (in sigma)
+NDT_MAX_ITERATION, NDT_EPS_ROT, NDT_EPS_TRANS = 30, 1e-5, 1e-4      # choices: rounds, and a step of 1e-5 rad / 0.1 mm
+_NDT_FIELDS = ("keys", "cnt", "s1", "s2")
+
+
+class NDTMap:
+    """The NDT layer over the keys of `vmap` (a `VoxelMap` that holds something): a snapshot (a clone of the keys and one
+    [SYNC] for their number, `voxel_size`, `origin`); later inserts into `vmap` do not disturb it.  `accumulate` adds the exact
+    integer moments of posed clouds (any batching and order: the bits of one call), `finalize` turns them into one Gaussian per
+    voxel with at least `min_points` points, `register` runs the NDT against them."""
+
+    def __init__(self, vmap: VoxelMap, min_points: int = NDT_MIN_POINTS, min_eig_ratio: float = NDT_MIN_EIG_RATIO,
+                 chunk_points: int = 4_000_000):
+        self._check_rule(min_points, min_eig_ratio)
+        if int(chunk_points) < 1:
+            raise ValueError("NDTMap: chunk_points must be positive")
+        if not isinstance(vmap, VoxelMap) or vmap._status is None:
+            raise ValueError("NDTMap: the voxel map is empty (nothing inserted)")
+        n = vmap.n_voxels                                                     # [SYNC]
+        self._init(vmap.records["keys"][:n].clone(), vmap.voxel_size, vmap.origin, min_points, min_eig_ratio, chunk_points, vmap._dev())
+
+    @staticmethod
+    def _check_rule(min_points, min_eig_ratio):
+        if int(min_points) < 3:
+            raise ValueError("NDTMap: min_points is at least 3")
+        if not (float(min_eig_ratio) > 0.0 and np.isfinite(float(min_eig_ratio))):
+            raise ValueError("NDTMap: min_eig_ratio must be positive and finite")
+
+    def _init(self, keys, voxel_size, origin, min_points, min_eig_ratio, chunk_points, dev):
+        n = int(keys.shape[0])
+        rows = max(n, 1)
+        self.device, self.voxel_size, self.origin = dev, float(voxel_size), np.asarray(origin, dtype=np.float64).copy()
+        self.min_points, self.min_eig_ratio, self.chunk_points = int(min_points), float(min_eig_ratio), int(chunk_points)
+        self.n_voxels = n
+        self.keys = torch.zeros((rows,), dtype=torch.int64, device=dev)
+        self.keys[:n] = keys
+        self._n = torch.full((), n, dtype=torch.int64, device=dev)
+        self.cnt = torch.zeros((rows,), dtype=torch.int32, device=dev)
+        self.s1 = torch.zeros((rows, 3), dtype=torch.int64, device=dev)
+        self.s2 = torch.zeros((rows, 6), dtype=torch.int64, device=dev)
+        self._missed = torch.zeros((), dtype=torch.int64, device=dev)
+        self._status = torch.zeros((), dtype=torch.int32, device=dev)
+        self._origin_dev = torch.from_numpy(self.origin).to(dev)
+        self.gaussians = None
+
+    def _origin_c(self):
+        return (ctypes.c_double * 3)(*[float(v) for v in self.origin])
+
+    @property
+    def missed(self) -> int:
+        """[SYNC] valid points whose voxel is not among the keys"""
+        return int(self._missed.item())
+
+    @property
+    def status(self) -> int:
+        """[SYNC] OR of the STATUS_* bits of every `accumulate` so far"""
+        return int(self._status.item())
+
+    def accumulate(self, bank, poses, pick=None) -> "NDTMap":
+        """Adds the moments of clouds pick[k] of `bank` (host picks; None: all, in order) under poses[k] ((n,4,4) f64, scan frame ->
+        map frame), chunked as `VoxelMap.insert` chunks.  The Gaussians of an earlier `finalize` are dropped.  Returns self."""
+        n_bank = len(bank)
+        n = n_bank if pick is None else len(pick)
+        _check_poses("NDTMap.accumulate", poses, n)
+        if n < 1:
+            raise ValueError("NDTMap.accumulate: at least one observation")
+        p = np.arange(n_bank, dtype=np.int64) if pick is None else np.asarray(pick, dtype=np.int64).reshape(-1)
+        if p.size and (p.min() < 0 or p.max() >= n_bank):
+            raise ValueError(f"NDTMap.accumulate: pick outside [0, {n_bank})")
+        sizes = bank.sizes()[p]
+        lib, dev = _lib.load(), self.device
+        ps = _lib.as_dev(poses, dev, torch.float64)
+        rows_m, n_pts, keep = self.keys.shape[0], bank.n_points, []
+        lo = 0
+        while lo < n:
+            hi, rows = lo + 1, int(sizes[lo])
+            while hi < n and hi - lo < MAX_OBS and rows + int(sizes[hi]) <= self.chunk_points:
+                rows += int(sizes[hi])
+                hi += 1
+            pk = torch.from_numpy(p[lo:hi].astype(np.int32)).to(dev)
+            pc = ps[lo:hi].contiguous()
+            s = _scratch256(lib.egonn_ndt_accumulate_scratch_bytes(rows, hi - lo), dev)
+            _lib.call(dev, lib.egonn_ndt_accumulate, _lib._ptr(bank.points) if n_pts else None, n_pts, bank.offsets().data_ptr(), n_bank,
+                      pk.data_ptr(), pc.data_ptr(), hi - lo, self._origin_c(), self.voxel_size, rows, self.keys.data_ptr(),
+                      self._n.data_ptr(), rows_m, self.cnt.data_ptr(), self.s1.data_ptr(), self.s2.data_ptr(), self._missed.data_ptr(),
+                      self._status.data_ptr(), s.data_ptr(), s.numel() * 8)
+            keep.append((pk, pc, s))
+            lo = hi
+        self._keep, self.gaussians = keep, None
+        return self
+
+    def finalize(self, debug: bool = False) -> Dict[str, torch.Tensor]:
+        """One Gaussian per voxel -> `gaussians` = {'mean' (n,3) f64 relative to `origin` (add it for a world point), 'info' (n,6)
+        f64 (xx, xy, xz, yy, yz, zz), 'eigenvalues' (n,3) ascending, 'normal' (n,3), 'valid' (n,) uint8, 'n_valid' () int64} on
+        the device; debug adds 'cov' (n,6).  An invalid voxel (fewer than min_points points, no extent) is all zeros."""
+        lib, dev, rows = _lib.load(), self.device, self.keys.shape[0]
+        f64 = lambda *sh: torch.zeros(sh, dtype=torch.float64, device=dev)        # noqa: E731
+        g = {"mean": f64(rows, 3), "info": f64(rows, 6), "eigenvalues": f64(rows, 3), "normal": f64(rows, 3),
+             "valid": torch.zeros((rows,), dtype=torch.uint8, device=dev), "n_valid": torch.zeros((), dtype=torch.int64, device=dev)}
+        if debug:
+            g["cov"] = f64(rows, 6)
+        _lib.call(dev, lib.egonn_ndt_finalize, self.keys.data_ptr(), self._n.data_ptr(), rows, self.cnt.data_ptr(), self.s1.data_ptr(),
+                  self.s2.data_ptr(), self.voxel_size, self.min_points, self.min_eig_ratio, g["mean"].data_ptr(), g["info"].data_ptr(),
+                  g["eigenvalues"].data_ptr(), g["normal"].data_ptr(), g["valid"].data_ptr(), g["n_valid"].data_ptr(),
+                  _lib._ptr(g.get("cov")))
+        n = self.n_voxels
+        self._layer = g
+        self.gaussians = {k: (v if v.dim() == 0 else v[:n]) for k, v in g.items()}
+        return self.gaussians
+
+    def register(self, points, offsets, poses_init, neighbors: int = 1, max_iteration: int = NDT_MAX_ITERATION,
+                 eps_rot: float = NDT_EPS_ROT, eps_trans: float = NDT_EPS_TRANS, debug: bool = False) -> Dict[str, torch.Tensor]:
+        """NDT of P scans against the map: points (n,3) concatenated clouds with (P+1,) offsets (what `voxel_downsample` and
+        `CloudBank.gather` return), poses_init (P,4,4) scan frame -> world frame.  `origin` is subtracted before and added after
+        the library call, which works in the origin-relative frame.  neighbors: 1 (the voxel a point falls into) or 7 (and its
+        face neighbours).  -> {'poses' (P,4,4) f64, 'fitness' (points with a Gaussian / points), 'score' (mean of exp(-d^2/2)
+        over the points) (P,) f64, 'iterations', 'status' (P,) int32 (ICP_* bits)} on the device; debug adds T_trace
+        (P, max_iteration+1, 4, 4) in the origin-relative frame, eval_trace (P, max_iteration+1, 4) = n_term, n_pts, score, stop
+        and sums_trace (P, max_iteration+1, 30) = n_term, n_pts, A (21), b (6), score of every evaluation.  No host synchronisation with device arguments; capturable."""
+        _reg._check_cloud("NDTMap.register", points)
+        P = _reg._check_offsets("NDTMap.register", offsets)
+        _check_poses("NDTMap.register", poses_init, P)
+        if not 1 <= P <= MAX_OBS:
+            raise ValueError(f"NDTMap.register: 1 to {MAX_OBS} scans per call, got {P}")
+        if int(neighbors) not in (1, 7):
+            raise ValueError(f"NDTMap.register: neighbors is 1 or 7, got {neighbors}")
+        if int(max_iteration) < 0 or not all(float(e) > 0.0 and np.isfinite(float(e)) for e in (eps_rot, eps_trans)):
+            raise ValueError("NDTMap.register: max_iteration >= 0, eps_rot and eps_trans positive and finite")
+        if self.gaussians is None:
+            raise ValueError("NDTMap.register: call finalize() first")
+        lib, dev, g, K = _lib.load(), self.device, self._layer, int(max_iteration)
+        src, off = _lib.as_dev(points, dev, torch.float64), _lib.as_dev(offsets, dev, torch.int64)
+        T0 = _lib.as_dev(poses_init, dev, torch.float64).clone()
+        T0[:, :3, 3] -= self._origin_dev
+        ns = src.shape[0]
+        s = _scratch256(lib.egonn_ndt_register_scratch_bytes(ns, P), dev)
+        f64 = lambda *sh: torch.empty(sh, dtype=torch.float64, device=dev)        # noqa: E731
+        i32 = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)          # noqa: E731
+        out = {"T": f64(P, 4, 4), "fitness": f64(P), "score": f64(P), "iterations": i32(P), "status": i32(P)}
+        if debug:
+            out.update({"T_trace": f64(P, K + 1, 4, 4), "eval_trace": f64(P, K + 1, 4), "sums_trace": f64(P, K + 1, 30)})
+        _lib.call(dev, lib.egonn_ndt_register, src.data_ptr() if ns else None, ns, off.data_ptr(), P, T0.data_ptr(), self.keys.data_ptr(),
+                  self._n.data_ptr(), self.keys.shape[0], g["mean"].data_ptr(), g["info"].data_ptr(), g["valid"].data_ptr(),
+                  self.voxel_size, int(neighbors), K, float(eps_rot), float(eps_trans), out["T"].data_ptr(), out["fitness"].data_ptr(),
+                  out["score"].data_ptr(), out["iterations"].data_ptr(), out["status"].data_ptr(), _lib._ptr(out.get("T_trace")),
+                  _lib._ptr(out.get("eval_trace")), _lib._ptr(out.get("sums_trace")), s.data_ptr(), s.numel() * 8)
+        poses = out.pop("T").clone()
+        poses[:, :3, 3] += self._origin_dev
+        out["poses"] = poses
+        out["_keep"] = (src, off, T0, s, g)
+        return out
+
+    # ------------------------------------------------------------------ files
+    def save(self, path: str) -> None:
+        """one .npz: the keys, the moments, the rule, voxel_size, origin; `load` finalizes again where this one was.  [SYNC]"""
+        n = self.n_voxels
+        np.savez(path, voxel_size=np.float64(self.voxel_size), origin=self.origin, min_points=np.int32(self.min_points),
+                 min_eig_ratio=np.float64(self.min_eig_ratio), missed=np.int64(self.missed), status=np.int32(self.status),
+                 finalized=np.int32(self.gaussians is not None), ndt=np.int32(1),
+                 **{f: getattr(self, f)[:n].cpu().numpy() for f in _NDT_FIELDS})
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "NDTMap":
+        with np.load(path) as z:
+            missing = [k for k in _NDT_FIELDS + ("ndt", "voxel_size", "origin", "min_points", "min_eig_ratio") if k not in z.files]
+            if missing:
+                raise ValueError(f"{path}: not an NDT map (missing {missing})")
+            data = {k: z[k] for k in z.files}
+        cls._check_rule(int(data["min_points"]), float(data["min_eig_ratio"]))
+        dev = device if device is not None else _lib.require_gpu()
+        m = cls.__new__(cls)
+        m._init(torch.from_numpy(data["keys"]).to(dev), float(data["voxel_size"]), data["origin"], int(data["min_points"]),
+                float(data["min_eig_ratio"]), 4_000_000, dev)
+        n = m.n_voxels
+        for f in ("cnt", "s1", "s2"):
+            getattr(m, f)[:n] = torch.from_numpy(data[f]).to(dev)
+        m._missed.fill_(int(data.get("missed", 0)))
+        m._status.fill_(int(data.get("status", 0)))
+        if int(data.get("finalized", 0)):
+            m.finalize()
+        return m
+
+
+def build_ndt_map(bank, poses, voxel_size: float = 1.0, min_points: int = NDT_MIN_POINTS, min_eig_ratio: float = NDT_MIN_EIG_RATIO,
+                  **kw) -> NDTMap:
+    """every cloud of `bank` under its pose as an NDT map: build_map, NDTMap(...).accumulate(bank, poses), finalize().  1.0 m by
+    default, not the voxel map's 0.2 m: a Gaussian needs points (at 0.2 m a voxel of the 0.1 m downsample holds a handful)."""
+    NDTMap._check_rule(min_points, min_eig_ratio)
+    m = NDTMap(build_map(bank, poses, voxel_size, **kw), min_points, min_eig_ratio)
+    m.accumulate(bank, poses).finalize()
+    return m
+
+
 def refine_against_map(vmap: VoxelMap, bank, pick, poses_init, half_extent=30.0, min_count: int = 1, min_observations: int = 1,
-                       **icp_kw) -> Dict[str, torch.Tensor]:
+                       method: str = "icp", ndt: Optional[NDTMap] = None, **icp_kw) -> Dict[str, torch.Tensor]:
     """Scan-to-map ICP by composition: for scan pick[k] of `bank` with the initial pose poses_init[k] (scan -> map frame), the
     source is its cloud (`bank.gather`), the target the submap of `vmap` around the pose's translation (`submaps`, relative),
     T_init = translate(-centre) @ pose_init, `icp_pairs` runs on that and pose = translate(+centre) @ T.  Host picks.
     -> {'poses' (n,4,4) f64, 'fitness', 'inlier_rmse' (n,) f64, 'status' (n,) int32 (ICP_* bits)} on the device.  [SYNC] once,
-    to size the submaps."""
+    to size the submaps.
+    method="ndt" registers against `ndt` (an `NDTMap`, finalized) instead: the clouds are gathered and handed to `ndt.register`
+    with the keywords of that call; there is no submap and no sizing synchronisation (vmap, half_extent and the two filters
+    are not read) -> the dict of `NDTMap.register`."""
+    if method not in ("icp", "ndt"):
+        raise ValueError(f"refine_against_map: method is 'icp' or 'ndt', got {method!r}")
     n = len(pick)
     _check_poses("refine_against_map", poses_init, n)
     if not 1 <= n <= MAX_OBS:
         raise ValueError(f"refine_against_map: 1 to {MAX_OBS} scans per call, got {n}")
+    if method == "ndt":
+        if not isinstance(ndt, NDTMap):
+            raise ValueError("refine_against_map: method='ndt' needs ndt=NDTMap")
+        src = bank.gather(pick)
+        r = ndt.register(src["points"], src["offsets"], poses_init, **icp_kw)
+        r["_keep"] = (src, r["_keep"])
+        return r
     dev = vmap._dev()
     X = _lib.as_dev(poses_init, dev, torch.float64)
     centre = X[:, :3, 3].contiguous()

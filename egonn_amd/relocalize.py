@@ -288,15 +288,22 @@ class Relocalizer:
     extractor's device; k: candidates per query.  refine=True needs `kmap.clouds` and polishes the winner's T_rel by
     point-to-point ICP of the query's downsampled cloud against the winner's cloud of the bank; icp_point2plane=True uses the
     point-to-plane estimator instead, on normals of the gathered winners' clouds.  method, d_thr, iterations, seed_ratio: the
-    geometric check of `verify_candidates` ("ransac" or "spectral")."""
+    geometric check of `verify_candidates` ("ransac" or "spectral").  ndt_map: a finalized `NDTMap` in the frame of the map's
+    poses; the winner's pose `map_pose[best] @ T_rel` then starts an NDT registration of the query's downsampled cloud against
+    it (ndt_neighbors 1 or 7).  `refine` keeps its meaning and the two can be combined."""
 
     def __init__(self, extractor, kmap: KeypointMap, k: int = 20, min_inliers: int = 0, ransac_dist_th: float = 0.5,
                  ransac_max_it: int = 10000, seed: int = 0, refine: bool = False, icp_dist_th: float = 1.2,
                  icp_max_it: int = 200, chunk_pairs: int = MAX_PAIRS, icp_point2plane: bool = False, method: str = "ransac",
                  d_thr: float = _reg.SPECTRAL_D_THR, iterations: int = _reg.SPECTRAL_ITERATIONS,
-                 seed_ratio: float = _reg.SPECTRAL_SEED_RATIO):
+                 seed_ratio: float = _reg.SPECTRAL_SEED_RATIO, ndt_map=None, ndt_neighbors: int = 1):
         if int(k) < 1:
             raise ValueError("Relocalizer: k must be positive")
+        if int(ndt_neighbors) not in (1, 7):
+            raise ValueError("Relocalizer: ndt_neighbors is 1 or 7")
+        if ndt_map is not None and getattr(ndt_map, "gaussians", None) is None:
+            raise ValueError("Relocalizer: ndt_map must be a finalized NDTMap")
+        self.ndt_map, self.ndt_neighbors = ndt_map, int(ndt_neighbors)
         if refine and kmap.clouds is None:
             raise ValueError("Relocalizer: refine=True needs kmap.clouds (a CloudBank of the map's scans)")
         self.extractor, self.kmap, self.k = extractor, kmap, int(k)
@@ -337,12 +344,18 @@ class Relocalizer:
                               self.ransac_dist_th, self.ransac_max_it, self.seed, self.chunk_pairs, method=self.method,
                               d_thr=self.d_thr, iterations=self.iterations, seed_ratio=self.seed_ratio)
         r["nn_index"], r["global"] = nn, y["global"]
-        if self.refine:
-            bank = km.clouds
+        bank = km.clouds
+        if self.refine or self.ndt_map is not None:      # the query's downsampled cloud, by the bank's rule where there is one
             pts = [torch.as_tensor(s, dtype=torch.float32).to(dev)[:, :3] for s in scans]
             off = np.zeros(Q + 1, dtype=np.int64)
             off[1:] = np.cumsum([p.shape[0] for p in pts])
-            qd = _reg.voxel_downsample(torch.cat(pts).contiguous(), torch.from_numpy(off).to(dev), bank.voxel_size, bank.crop)
+            qd = _reg.voxel_downsample(torch.cat(pts).contiguous(), torch.from_numpy(off).to(dev),
+                                       bank.voxel_size if bank is not None else _reg.ICP_VOXEL_SIZE, bank.crop if bank is not None else None)
+        if self.ndt_map is not None:                     # the verified winner's pose starts a registration against the NDT map
+            ndt = self.ndt_map.register(qd["points"], qd["offsets"], r["pose"], neighbors=self.ndt_neighbors)
+            r.update({"pose_ndt": ndt["poses"], "ndt_fitness": ndt["fitness"], "ndt_score": ndt["score"],
+                      "ndt_iterations": ndt["iterations"], "ndt_status": ndt["status"], "_ndt": (qd, ndt)})
+        if self.refine:
             g = bank.gather(r["safe_pick"], capacity=Q * int(bank.sizes().max()) if len(bank) else 0)
             nrm = _reg.estimate_normals(g["points"], g["offsets"])["normals"] if self.icp_point2plane else None
             icp = _reg.icp_pairs(qd["points"], qd["offsets"], g["points"], g["offsets"], r["T_rel"], self.icp_dist_th,
@@ -358,7 +371,9 @@ class Relocalizer:
         global (Q, G); with query_poses (Q,4,4) the per-pair and the winner's rte / rre / success against
         inv(P_map[candidate]) @ P_query.  With refine also T_icp, pose_refined = map pose[best] @ T_icp, icp_fitness,
         icp_inlier_rmse (the per-pair registration already owns `fitness` / `inlier_rmse`) and icp_status, meaningful only
-        where best_index >= 0.  nn_index (Q, k): candidates from elsewhere instead of the global retrieval.
+        where best_index >= 0.  With ndt_map also pose_ndt (Q,4,4), ndt_fitness, ndt_score, ndt_iterations and ndt_status (the
+        result of `NDTMap.register` started at `pose`), meaningful under the same condition.  nn_index (Q, k): candidates from
+        elsewhere instead of the global retrieval.
 
         Everything is enqueued without host synchronisation; the ONE synchronisation is the extractor's range check at the
         end (a flagged batch is extracted again on the exact kernels and verified again), after which the results are valid."""

@@ -972,6 +972,65 @@ int egonn_voxel_map_select(const uint64_t* keys, const int64_t* sums, const int3
                            int n_boxes, int relative, double* out_points, int64_t* out_offsets, int32_t* out_count, int32_t* out_obs,
                            int64_t capacity, int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ NDT layer (csrc/ndt.hip)
+ * One Gaussian per voxel over the keys of a voxel map, and the normal-distributions transform against them.  The layer lies
+ * over a fixed, ascending, unique key array keys[0 .. n) (n = *n_dev clipped to capacity_map: a snapshot of a map's keys) and
+ * uses the map's `voxel` and `origin`.  The point arithmetic is the voxel map's, bit for bit (t', w, s, i, key, q above).
+ *
+ * Moments.  m_a = q_a >> 10 (20 bits: a voxel holds the squares of 2^23 points in an int64).  Three arrays over the rows:
+ *     cnt (rows) int32;   s1 (rows,3) int64 = sum m;   s2 (rows,6) int64 = sum m_a m_b in the order xx, xy, xz, yy, yz, zz.
+ * A valid point whose key is in keys adds to its row; one whose key is absent adds 1 to *missed (DEVICE int64); a dropped point
+ * sets EGONN_VMAP_STATUS_RANGE, a bad pick BAD_INDEX, more points than points_capacity CAPACITY and then nothing is added (the
+ * rules of egonn_voxel_map_integrate).  The call adds into arrays the caller zeroed.  Everything is an integer: any batching
+ * and any order of calls give the bits of one call; there is no floating-point atomic.
+ *
+ * Gaussians.  Every operation rounded to fp64 in the order written (no FMA):
+ *     nf = (double) cnt;   mu_a = (double) s1_a / nf;   mean_a = ((double) i_a + mu_a * 2^-20) * voxel    (relative to origin)
+ *     u = voxel * 2^-20;   C_ab = ((((double) s2_ab - ((double) s1_a * (double) s1_b) / nf) / (nf - 1.0)) * u) * u
+ *     C = V diag(l) V^T by cyclic Jacobi (the schedule of the surface normals), eigenvalues ascending, ties in column order
+ *     l'_i = max(l_i, min_eig_ratio * l_2);   info_ab = sum_i ((1 / l'_i) v_ai) v_bi, added in i = 0, 1, 2 from 0.0
+ *     normal = v_0, negated when its first non-zero component is negative (a map has no sensor to face)
+ *     valid iff cnt >= min_points and l_2 > 0 and every value is finite; an invalid row is all zeros, valid = 0.
+ * min_points = 6 and min_eig_ratio = 0.01 are the Python defaults: choices, not tuned values.  mean (rows,3), info (rows,6:
+ * xx, xy, xz, yy, yz, zz), eigenvalues (rows,3), normal (rows,3), valid (rows) uint8, *n_valid DEVICE int64 (set, not added to),
+ * cov (rows,6) nullable debug output.  Rows from n on are not written.
+ *
+ * Registration of a pair (a source cloud, T_init in the origin-relative map frame; null = identity).  Under T_k, for a source
+ * point p: vs_a = ((R_a0 p_0 + R_a1 p_1) + R_a2 p_2) + t_a, i_a = floor(vs_a / voxel).  Neighbour offsets in this order: (0,0,0),
+ * (+1,0,0), (-1,0,0), (0,+1,0), (0,-1,0), (0,0,+1), (0,0,-1); neighbors = 1 takes the first, 7 all.  A neighbour counts iff its
+ * index is in [-2^20, 2^20) on every axis, its key is in keys and its row is valid.  Per counted term:
+ *     r = vs - mean,  g = info r,  m = r . g,  w = exp(-0.5 m)  (a term with non-finite m is skipped)
+ *     n_term += 1,  score += w,  A += w J^T info J (21 upper entries),  b += w J^T g,  J = [-[vs]x | I]: J^T g = (vs x g, g)
+ * n_pts = points with at least one term, fitness = n_pts / n_source, the `score` output = score / n_source.
+ * Round k: A x = -b by the LDL^T of the point-to-plane ICP (pivot rule 2^-40), U = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)],
+ * T_k+1 = U T_k.  The loop stops, in this order of precedence at the evaluation of T_k: after a round whose step had
+ * max |x_0..2| < eps_rot and max |x_3..5| < eps_trans (the new T is evaluated and returned, no bit set); k = max_iteration
+ * (MAX_ITER); n_term < 6 (FEW_CORR); a failed pivot or a non-finite step (SINGULAR); T is unchanged by the last three.  A pair
+ * without source points: EMPTY, T = T_init.  iterations = steps taken.  This is the Gauss-Newton form of the NDT score: the
+ * Hessian sum w J^T info J is positive semi-definite and there is no line search; Magnusson's full Newton step with
+ * More-Thuente is not built.  Python's defaults max_iteration = 30, eps_rot = 1e-5, eps_trans = 1e-4 are choices.
+ * Summation order: a lane adds its terms in neighbour order, a workgroup of 256 consecutive source points of one pair reduces
+ * in a fixed tree, partials are added in ascending workgroup order: a pair has the same bits alone, in any batch, at any
+ * position.  Debug tables (nullable): T_trace (n_pairs, max_iteration+1, 4, 4) = T_k (zero beyond the stop), eval_trace
+ * (n_pairs, max_iteration+1, 4) = n_term, n_pts, score, stop of the evaluation of T_k, sums_trace (n_pairs, max_iteration+1,
+ * 30) = its sums: n_term, n_pts, A (21 upper entries row by row), b (6), score.  status reuses EGONN_ICP_STATUS_*.
+ * Every call: arguments are checked before the first HIP call; scratch 256-byte aligned, at least *_scratch_bytes (-1 on bad
+ * arguments); 1 <= n_obs, n_pairs <= 4096; sizes in [0, 2^31); no host synchronisation, capturable. */
+int64_t egonn_ndt_accumulate_scratch_bytes(int64_t points_capacity, int n_obs);
+int egonn_ndt_accumulate(const double* bank, int64_t n_bank, const int64_t* bank_offsets, int64_t n_clouds, const int32_t* pick,
+                         const double* poses, int n_obs, const double* origin, double voxel, int64_t points_capacity,
+                         const uint64_t* keys, const int64_t* n_dev, int64_t capacity_map, int32_t* cnt, int64_t* s1, int64_t* s2,
+                         int64_t* missed, int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);
+int egonn_ndt_finalize(const uint64_t* keys, const int64_t* n_dev, int64_t capacity_map, const int32_t* cnt, const int64_t* s1,
+                       const int64_t* s2, double voxel, int min_points, double min_eig_ratio, double* mean, double* info,
+                       double* eigenvalues, double* normal, uint8_t* valid, int64_t* n_valid, double* cov, void* stream);
+int64_t egonn_ndt_register_scratch_bytes(int64_t n_src, int n_pairs);
+int egonn_ndt_register(const double* src, int64_t n_src, const int64_t* src_offsets, int n_pairs, const double* T_init,
+                       const uint64_t* keys, const int64_t* n_dev, int64_t capacity_map, const double* mean, const double* info,
+                       const uint8_t* valid, double voxel, int neighbors, int max_iteration, double eps_rot, double eps_trans,
+                       double* T, double* fitness, double* score, int32_t* iterations, int32_t* status, double* T_trace,
+                       double* eval_trace, double* sums_trace, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ relocalisation against a keypoint map (csrc/relocalize.hip, csrc/match.hip)
  * A query scan is placed in the map frame by registering it against its top-k retrieved map entries (egonn_knn) and keeping
  * the entry with the most inliers: P_query = P_map[best] @ T, T = the transform of egonn_registration_finish, which maps query
