@@ -27,6 +27,8 @@
 //            closed form (largest eigenvector of the 4 x 4 matrix by cyclic Jacobi; a unit quaternion is a proper
 //            rotation, which is the reflection-corrected least-squares solution), T_k+1 = U T_k.
 //
+// The loop around it (per-pair state, the flat grid of workgroups, the reduction tree, the ascending gather, stop and advance)
+// is pair_loop.h, shared with ndt.hip; this file supplies the search, the two estimators' terms and steps, and the stop rule.
 // The partition (256 points per workgroup, counted from the pair's own first point), the summation order and the Jacobi
 // schedule are fixed, there are no floating-point atomics: a pair's result has the same bits alone, in any batch and at any
 // batch position.  The launch sequence is fixed by max_iteration; a stopped pair sets a flag and its later workgroups
@@ -40,13 +42,14 @@
 #include "common.h"
 #include "horn.h"
 #include "jacobi3.h"
+#include "pair_loop.h"
 #include "plane_step.h"
 
 #pragma clang fp contract(off)
 
 namespace egonn {
 
-static constexpr int ICP_WG = 256;
+static constexpr int ICP_WG = PAIR_WG;
 static constexpr int ICP_NPART = 17;              // n_corr, sum d2, sum p (3), sum q (3), sum p q^T (9)
 static constexpr int ICP_NPART_PLANE = 29;        // n_corr, sum d2, sum J J^T (21 upper entries), sum J r (6)
 static constexpr int NRM_KNN_MIN = 3, NRM_KNN_MAX = 32;
@@ -54,7 +57,6 @@ static constexpr double NRM_CELL = 0.5;           // start radius and cell edge 
 static constexpr int DS_BITS = 21;               // voxel index bits per axis
 static constexpr int ICP_CELL_MAX = 65535;        // cell index bits per axis: 16
 static constexpr uint64_t DS_INVALID = ~0ull;     // key of a dropped / out-of-cloud point (valid keys have bit 63 clear)
-
 
 // segment of position i: the largest c in [0, C) with clip(off[c]) <= i, or -1 when i is beyond the last segment
 __device__ static inline int icp_segment(const int64_t* __restrict__ off, int C, int64_t n, int64_t i) {
@@ -266,7 +268,7 @@ static DsLayout ds_layout(int64_t n, int C) {
 }
 
 // ------------------------------------------------------------------ ICP
-struct IcpPair {
+struct IcpPair {            // the members pair_loop.h asks for, and the target grid; the order is the kernels' (see there)
   double R[9], t[3];        // T_k
   double org[3], h;         // target grid: origin (min corner) and cell edge
   double prev_fit, prev_rmse;
@@ -289,9 +291,8 @@ __global__ __launch_bounds__(ICP_WG) void icp_setup_kernel(const double* __restr
                                                            int32_t* __restrict__ status, double* __restrict__ T_trace, int max_it) {
   __shared__ double s_lo[3][ICP_WG], s_hi[3][ICP_WG];
   const int p = blockIdx.x, t = threadIdx.x;
-  const int64_t so = clipi(soff[p], ns_cap), se = clipi(soff[p + 1], ns_cap);
   const int64_t to = clipi(toff[p], nt_cap), te = clipi(toff[p + 1], nt_cap);
-  const int64_t ns = se > so ? se - so : 0, nt = te > to ? te - to : 0;
+  const int64_t nt = te > to ? te - to : 0;
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int64_t i = to + t; i < to + nt; i += ICP_WG) {
 #pragma unroll
@@ -316,13 +317,7 @@ __global__ __launch_bounds__(ICP_WG) void icp_setup_kernel(const double* __restr
   }
   if (t != 0) return;
   IcpPair q;
-  double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  if (T_init)
-    for (int k = 0; k < 16; ++k) T[k] = T_init[(size_t)p * 16 + k];
-  for (int r = 0; r < 3; ++r) {
-    q.R[r * 3] = T[r * 4], q.R[r * 3 + 1] = T[r * 4 + 1], q.R[r * 3 + 2] = T[r * 4 + 2];
-    q.t[r] = T[r * 4 + 3];
-  }
+  pair_begin(&q, soff, ns_cap, P, p, T_init, T_trace, max_it, wg0);
   double ext = 0.0;
   for (int k = 0; k < 3; ++k) {
     q.org[k] = nt > 0 ? s_lo[k][0] : 0.0;
@@ -339,24 +334,12 @@ __global__ __launch_bounds__(ICP_WG) void icp_setup_kernel(const double* __restr
     q.dim[k] = icp_cell(f, ICP_CELL_MAX + 1) + 1;
   }
   q.prev_fit = q.prev_rmse = 0.0;
-  q.so = so, q.to = to, q.ns = (int32_t)ns, q.nt = (int32_t)nt;
-  q.done = 0, q.status = 0, q.pad = 0;
-  if (T_trace)
-    for (int k = 0; k < 16; ++k) T_trace[((size_t)p * (max_it + 1)) * 16 + k] = k < 12 ? T[k] : (k == 15 ? 1.0 : 0.0);
-  if (ns == 0 || nt == 0) {
-    q.done = 1, q.status = EGONN_ICP_STATUS_EMPTY;
-    for (int k = 0; k < 16; ++k) T_out[(size_t)p * 16 + k] = k < 12 ? T[k] : (k == 15 ? 1.0 : 0.0);
-    fitness[p] = 0.0, rmse[p] = 0.0, iterations[p] = 0, status[p] = q.status;
+  q.to = to, q.nt = (int32_t)nt, q.pad = 0;
+  if (T_out && (q.ns == 0 || nt == 0)) {                 // the normals have no pair outputs; an empty cloud has no workgroup
+    pair_stop(&q, p, 0, EGONN_ICP_STATUS_EMPTY, T_out, iterations, status);
+    fitness[p] = 0.0, rmse[p] = 0.0;
   }
   pairs[p] = q;
-  // first workgroup of the pair in the flat search grid: a function of the sizes of the pairs before it only
-  int64_t w = 0;
-  for (int b = 0; b < p; ++b) {
-    const int64_t a = clipi(soff[b], ns_cap), e = clipi(soff[b + 1], ns_cap);
-    w += e > a ? (e - a + ICP_WG - 1) / ICP_WG : 0;
-  }
-  wg0[p] = (int32_t)w;
-  if (p == P - 1) wg0[P] = (int32_t)(w + (ns + ICP_WG - 1) / ICP_WG);
 }
 
 // side 0: cell key of every target point; side 1: Morton key of every source point's cell under T_0 (order only)
@@ -376,12 +359,11 @@ __global__ __launch_bounds__(ICP_WG) void icp_key_kernel(const double* __restric
       const uint64_t cz = (uint64_t)icp_cell(floor((z - q->org[2]) / q->h), q->dim[2]);
       key = (cx << 32) | (cy << 16) | cz;
     } else {
-      const double px = q->R[0] * x + q->R[1] * y + q->R[2] * z + q->t[0];
-      const double py = q->R[3] * x + q->R[4] * y + q->R[5] * z + q->t[1];
-      const double pz = q->R[6] * x + q->R[7] * y + q->R[8] * z + q->t[2];
-      const uint32_t cx = (uint32_t)icp_cell(floor((px - q->org[0]) / q->h) + 16384.0, ICP_CELL_MAX + 1);
-      const uint32_t cy = (uint32_t)icp_cell(floor((py - q->org[1]) / q->h) + 16384.0, ICP_CELL_MAX + 1);
-      const uint32_t cz = (uint32_t)icp_cell(floor((pz - q->org[2]) / q->h) + 16384.0, ICP_CELL_MAX + 1);
+      double c[3];
+      pair_apply(q, pts + i * 3, c);
+      const uint32_t cx = (uint32_t)icp_cell(floor((c[0] - q->org[0]) / q->h) + 16384.0, ICP_CELL_MAX + 1);
+      const uint32_t cy = (uint32_t)icp_cell(floor((c[1] - q->org[1]) / q->h) + 16384.0, ICP_CELL_MAX + 1);
+      const uint32_t cz = (uint32_t)icp_cell(floor((c[2] - q->org[2]) / q->h) + 16384.0, ICP_CELL_MAX + 1);
       key = morton3(cx, cy, cz);
     }
   }
@@ -406,16 +388,6 @@ __global__ __launch_bounds__(ICP_WG) void icp_gather_kernel(const double* __rest
 }
 
 struct IcpRange { int lo[3], hi[3]; };      // a clamped range of target cells, inclusive; hi < lo on an axis = empty
-
-// pair (or cloud) of workgroup `flat` of the flat search grid: the largest p with wg0[p] <= flat
-__device__ static inline int icp_pair_of(const int32_t* __restrict__ wg0, int P, int flat) {
-  int lo = 0, hi = P - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (wg0[mid] <= flat) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // bounding box of the workgroup's points (lanes with !valid have none): per-wave minima / maxima into s_box; a barrier follows
 __device__ static inline void icp_wave_box(double (*s_box)[4], bool valid, double px, double py, double pz) {
@@ -533,7 +505,7 @@ __global__ __launch_bounds__(ICP_WG) void icp_search_kernel(const IcpPair* __res
   __shared__ double s_red[NP][4];
   __shared__ double s_box[6][4];
   const int flat = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int p = icp_pair_of(wg0, P, flat);
+  const int p = pair_of(wg0, P, flat);
   const IcpPair* q = pairs + p;
   const int chunk = flat - wg0[p];
   const int ns = q->ns, nt = q->nt;
@@ -597,14 +569,7 @@ __global__ __launch_bounds__(ICP_WG) void icp_search_kernel(const IcpPair* __res
 #pragma unroll
     for (int a = 0; a < 6; ++a) v[23 + a] = J[a] * r;
   }
-#pragma unroll
-  for (int k = 0; k < NP; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);      // a fixed tree
-    if (lane == 0) s_red[k][w] = v[k];
-  }
-  __syncthreads();
-  if (t < NP) partial[(size_t)flat * NP + t] = ((s_red[t][0] + s_red[t][1]) + s_red[t][2]) + s_red[t][3];
+  pair_reduce<NP>(v, s_red, partial, flat, lane, w);
 }
 
 // icp_plane_step (plane_step.h): the 6 x 6 solve by LDL^T and the update it stands for, shared with ndt.hip
@@ -622,13 +587,7 @@ __global__ __launch_bounds__(64) void icp_finish_kernel(IcpPair* __restrict__ pa
   const int p = blockIdx.x, t = threadIdx.x;
   IcpPair* q = pairs + p;
   if (q->done) return;
-  const int nwg = (q->ns + ICP_WG - 1) / ICP_WG, first = wg0[p];
-  if (t < NP) {
-    double acc = 0.0;
-    for (int c = 0; c < nwg; ++c) acc += partial[(size_t)(first + c) * NP + t];     // ascending workgroups
-    s[t] = acc;
-  }
-  __syncthreads();
+  pair_gather<NP>(q, wg0[p], partial, s);
   if (t != 0) return;
   const double n = s[0];
   const double fit = n / (double)q->ns, e_rmse = n > 0.0 ? sqrt(s[1] / n) : 0.0;
@@ -645,12 +604,8 @@ __global__ __launch_bounds__(64) void icp_finish_kernel(IcpPair* __restrict__ pa
     e[0] = n, e[1] = s[1], e[2] = (double)stop;
   }
   if (stop) {
-    double* To = T_out + (size_t)p * 16;
-    for (int r = 0; r < 3; ++r) To[r * 4] = q->R[r * 3], To[r * 4 + 1] = q->R[r * 3 + 1], To[r * 4 + 2] = q->R[r * 3 + 2], To[r * 4 + 3] = q->t[r];
-    To[12] = To[13] = To[14] = 0.0, To[15] = 1.0;
-    fitness[p] = fit, rmse[p] = e_rmse, iterations[p] = round, status[p] = st;
-    q->status = st;
-    q->done = 1;
+    fitness[p] = fit, rmse[p] = e_rmse;
+    pair_stop(q, p, round, st, T_out, iterations, status);
     return;
   }
   if constexpr (EST == 0) {
@@ -662,19 +617,8 @@ __global__ __launch_bounds__(64) void icp_finish_kernel(IcpPair* __restrict__ pa
     horn_rotation(S, U);
     for (int r = 0; r < 3; ++r) ut[r] = qm[r] - (U[r * 3] * pm[0] + U[r * 3 + 1] * pm[1] + U[r * 3 + 2] * pm[2]);
   }
-  double Rn[9], tn[3];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) Rn[r * 3 + c] = U[r * 3] * q->R[c] + U[r * 3 + 1] * q->R[3 + c] + U[r * 3 + 2] * q->R[6 + c];
-    tn[r] = U[r * 3] * q->t[0] + U[r * 3 + 1] * q->t[1] + U[r * 3 + 2] * q->t[2] + ut[r];
-  }
-  for (int k = 0; k < 9; ++k) q->R[k] = Rn[k];
-  for (int k = 0; k < 3; ++k) q->t[k] = tn[k];
   q->prev_fit = fit, q->prev_rmse = e_rmse;
-  if (T_trace) {
-    double* To = T_trace + ((size_t)p * (max_it + 1) + round + 1) * 16;
-    for (int r = 0; r < 3; ++r) To[r * 4] = Rn[r * 3], To[r * 4 + 1] = Rn[r * 3 + 1], To[r * 4 + 2] = Rn[r * 3 + 2], To[r * 4 + 3] = tn[r];
-    To[12] = To[13] = To[14] = 0.0, To[15] = 1.0;
-  }
+  pair_advance(q, p, round, max_it, U, ut, T_trace);
 }
 
 // ------------------------------------------------------------------ surface normals: exact k nearest neighbours, PCA
@@ -717,7 +661,7 @@ __global__ __launch_bounds__(ICP_WG) void nrm_knn_kernel(const IcpPair* __restri
                                                          int32_t* __restrict__ neighbors, double* __restrict__ eigenvalues) {
   __shared__ double s_box[6][4];
   const int flat = blockIdx.x, t = threadIdx.x;
-  const int p = icp_pair_of(wg0, P, flat);
+  const int p = pair_of(wg0, P, flat);
   const IcpPair* q = pairs + p;
   const int chunk = flat - wg0[p];
   const int ns = q->ns;                                   // source = target = the cloud
@@ -847,51 +791,44 @@ __global__ __launch_bounds__(ICP_WG) void nrm_knn_kernel(const IcpPair* __restri
   }
 }
 
-struct NrmLayout {
-  size_t pairs, wg0, keys0, keys1, vals0, vals1, tq, tj, tkey, sq, si, outs, sort, sort_bytes, total;
-  int64_t n_wg;
+// The search grid that the ICP and the normals both build, as carves of the caller's scratch: the pairs and their workgroup
+// table, the targets in cell order, the sources in Morton order under T_0, and what the two sorts need.  n_part: partial sums
+// per workgroup (0: the normals have no rounds).  With scratch = nullptr only `total` means anything.
+struct IcpGrid {
+  int64_t n_wg;             // workgroups of the flat grid
+  IcpPair* pairs;
+  int32_t* wg0;
+  double* partial;
+  double *tq, *sq;          // points of the targets / sources in their order
+  int32_t *tj, *si;         // their index inside the pair's own cloud
+  uint64_t* tkey;           // cell keys of the targets
+  uint64_t* keys[2];        // ping-pong buffers of the sorts
+  uint32_t* vals[2];
+  Arena sort_ws;
+  size_t total;
 };
-static NrmLayout nrm_layout(int64_t n, int C) {
-  NrmLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-  const size_t m = (size_t)(n > 0 ? n : 1);
-  L.n_wg = cdiv((int64_t)m, ICP_WG) + C;
-  L.pairs = take((size_t)C * sizeof(IcpPair));
-  L.wg0 = take((size_t)(C + 1) * 4);
-  L.keys0 = take(m * 8), L.keys1 = take(m * 8), L.vals0 = take(m * 4), L.vals1 = take(m * 4);
-  L.tq = take(m * 24), L.tj = take(m * 4), L.tkey = take(m * 8);
-  L.sq = take(m * 24), L.si = take(m * 4);
-  L.outs = take((size_t)C * 20 * 8);      // what icp_setup_kernel writes for an empty pair: T (16), fitness, rmse, iterations, status
-  L.sort_bytes = align_up(radix_sort_segments_scratch_bytes((int64_t)m, C) + 512, 256);
-  L.sort = take(L.sort_bytes);
-  L.total = o;
-  return L;
+static IcpGrid icp_grid(void* scratch, int64_t ns, int64_t nt, int P, int n_part) {
+  IcpGrid G;
+  Carve c;
+  const size_t a = (size_t)(ns > 0 ? ns : 1), b = (size_t)(nt > 0 ? nt : 1), m = a > b ? a : b;
+  auto at = [&](size_t off) { return (void*)((uintptr_t)scratch + off); };
+  auto take = [&](size_t bytes) { return at(c.take(bytes)); };
+  const PairLayout L = pair_layout(c, (int64_t)a, P, sizeof(IcpPair));
+  G.n_wg = L.n_wg, G.pairs = (IcpPair*)at(L.pairs), G.wg0 = (int32_t*)at(L.wg0);
+  for (int k = 0; k < 2; ++k) G.keys[k] = (uint64_t*)take(m * 8);
+  for (int k = 0; k < 2; ++k) G.vals[k] = (uint32_t*)take(m * 4);
+  G.tq = (double*)take(b * 24), G.tj = (int32_t*)take(b * 4), G.tkey = (uint64_t*)take(b * 8);
+  G.sq = (double*)take(a * 24), G.si = (int32_t*)take(a * 4);
+  G.partial = (double*)take((size_t)L.n_wg * n_part * 8);
+  // + 512: the sort carves two arrays out of this span and Arena::alloc aligns each carve to 256
+  const size_t sort_bytes = align_up(radix_sort_segments_scratch_bytes((int64_t)m, P) + 512, 256);
+  G.sort_ws = Arena::view(take(sort_bytes), sort_bytes);
+  G.total = c.o;
+  return G;
 }
 
-struct IcpLayout {
-  size_t pairs, wg0, keys0, keys1, vals0, vals1, tq, tj, tkey, sq, si, partial, sort, sort_bytes, total;
-  int64_t n_wg;
-  int estimator;            // 0: point-to-point, 1: point-to-plane; the one thing that tells the two calls apart
-};
-static IcpLayout icp_layout(int64_t ns, int64_t nt, int P, int estimator) {
-  IcpLayout L;
-  L.estimator = estimator;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-  const size_t a = (size_t)(ns > 0 ? ns : 1), b = (size_t)(nt > 0 ? nt : 1), m = a > b ? a : b;
-  L.n_wg = cdiv((int64_t)a, ICP_WG) + P;
-  L.pairs = take((size_t)P * sizeof(IcpPair));
-  L.wg0 = take((size_t)(P + 1) * 4);
-  L.keys0 = take(m * 8), L.keys1 = take(m * 8), L.vals0 = take(m * 4), L.vals1 = take(m * 4);
-  L.tq = take(b * 24), L.tj = take(b * 4), L.tkey = take(b * 8);
-  L.sq = take(a * 24), L.si = take(a * 4);
-  L.partial = take((size_t)L.n_wg * (estimator ? ICP_NPART_PLANE : ICP_NPART) * 8);
-  // + 512: the sort carves two arrays out of this span and Arena::alloc aligns each carve to 256
-  L.sort_bytes = align_up(radix_sort_segments_scratch_bytes((int64_t)m, P) + 512, 256);
-  L.sort = take(L.sort_bytes);
-  L.total = o;
-  return L;
+static bool icp_shape_ok(int64_t n_src, int64_t n_tgt, int n_pairs) {
+  return n_src >= 0 && n_tgt >= 0 && n_src < (1ll << 31) && n_tgt < (1ll << 31) && n_pairs >= 1 && n_pairs <= EGONN_MAX_BATCH;
 }
 
 }  // namespace egonn
@@ -941,28 +878,35 @@ API int egonn_voxel_downsample(const float* points, int64_t n, const int64_t* of
   return EGONN_OK;
 }
 
-
 // cell order of the targets (side 0: tq, tj, tkey) or Morton order of the sources under T_0 (side 1: sq, si) of every pair
-static int icp_order_side(int side, const double* pts, int64_t n, const int64_t* off, int P, const IcpPair* pairs, Arena sort_ws,
-                          uint64_t* keys0, uint32_t* vals0, uint64_t* keys1, uint32_t* vals1, double* out_pts, int32_t* out_idx,
-                          uint64_t* out_keys, hipStream_t st) {
-  uint64_t* keys = keys0;
-  uint32_t* vals = vals0;
+static int icp_order_side(int side, const double* pts, int64_t n, const int64_t* off, int P, const IcpGrid& G, double* out_pts,
+                          int32_t* out_idx, uint64_t* out_keys, hipStream_t st) {
+  uint64_t* keys = G.keys[0];
+  uint32_t* vals = G.vals[0];
+  Arena ws = G.sort_ws;                                   // a view: every sort carves from its start
   const unsigned nb = (unsigned)cdiv(n, ICP_WG);
-  hipLaunchKernelGGL(icp_key_kernel, dim3(nb), dim3(ICP_WG), 0, st, pts, n, off, P, pairs, side, keys, vals);
-  EGONN_TRY(radix_sort_segments(sort_ws, keys, vals, keys1, vals1, n, off, P, 48, st, &keys, &vals));
+  hipLaunchKernelGGL(icp_key_kernel, dim3(nb), dim3(ICP_WG), 0, st, pts, n, off, P, G.pairs, side, keys, vals);
+  EGONN_TRY(radix_sort_segments(ws, keys, vals, G.keys[1], G.vals[1], n, off, P, 48, st, &keys, &vals));
   hipLaunchKernelGGL(icp_gather_kernel, dim3(nb), dim3(ICP_WG), 0, st, pts, n, off, P, keys, vals, out_pts, out_idx, out_keys);
   return EGONN_OK;
 }
 
-// the ICP loop of both entry points; L.estimator picks the instantiation of the two per-round kernels
-static int icp_run(const IcpLayout& L, const char* who, const double* src, int64_t n_src, const int64_t* src_offsets,
+// both sides of the grid, after icp_setup_kernel has filled G.pairs
+static int icp_build_grid(const IcpGrid& G, const double* tgt, int64_t n_tgt, const int64_t* tgt_offsets, const double* src,
+                          int64_t n_src, const int64_t* src_offsets, int P, hipStream_t st) {
+  EGONN_TRY(icp_order_side(0, tgt, n_tgt, tgt_offsets, P, G, G.tq, G.tj, G.tkey, st));
+  return icp_order_side(1, src, n_src, src_offsets, P, G, G.sq, G.si, nullptr, st);
+}
+
+// the ICP loop of both entry points; estimator (0: point-to-point, 1: point-to-plane) picks the instantiation of the two
+// per-round kernels and is the one thing that tells the two calls apart
+static int icp_run(int estimator, const char* who, const double* src, int64_t n_src, const int64_t* src_offsets,
                    const double* tgt, int64_t n_tgt, const int64_t* tgt_offsets, const double* tgt_normals, int n_pairs,
                    const double* T_init, double max_dist, int max_iteration, double eps_fitness, double eps_rmse, double* T,
                    double* fitness, double* inlier_rmse, int32_t* iterations, int32_t* status, double* T_trace, double* eval_trace,
                    int32_t* corr, void* scratch, int64_t scratch_bytes, void* stream) {
-  EGONN_REQUIRE(n_src >= 0 && n_tgt >= 0 && n_src < (1ll << 31) && n_tgt < (1ll << 31) && n_pairs >= 1 && n_pairs <= EGONN_MAX_BATCH,
-                EGONN_ERR_INVALID, "%s: bad shape (n_src=%lld, n_tgt=%lld, n_pairs=%d; n_pairs <= %d)", who, (long long)n_src,
+  EGONN_REQUIRE(icp_shape_ok(n_src, n_tgt, n_pairs), EGONN_ERR_INVALID,
+                "%s: bad shape (n_src=%lld, n_tgt=%lld, n_pairs=%d; n_pairs <= %d)", who, (long long)n_src,
                 (long long)n_tgt, n_pairs, EGONN_MAX_BATCH);
   EGONN_REQUIRE(max_dist > 0.0 && max_dist < 1e18, EGONN_ERR_INVALID, "%s: bad distance threshold", who);
   EGONN_REQUIRE(max_iteration >= 0 && max_iteration <= 100000, EGONN_ERR_INVALID, "%s: max_iteration %d outside [0, 100000]", who,
@@ -971,57 +915,39 @@ static int icp_run(const IcpLayout& L, const char* who, const double* src, int64
   EGONN_REQUIRE(src_offsets && tgt_offsets && T && fitness && inlier_rmse && iterations && status && scratch &&
                     (n_src == 0 || src) && (n_tgt == 0 || tgt),
                 EGONN_ERR_INVALID, "%s: null pointer", who);
-  EGONN_REQUIRE(!L.estimator || n_tgt == 0 || tgt_normals, EGONN_ERR_INVALID, "%s: null tgt_normals", who);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "%s: scratch needs %lld bytes, 256-byte aligned", who, (long long)L.total);
+  EGONN_REQUIRE(!estimator || n_tgt == 0 || tgt_normals, EGONN_ERR_INVALID, "%s: null tgt_normals", who);
+  const IcpGrid G = icp_grid(scratch, n_src, n_tgt, n_pairs, estimator ? ICP_NPART_PLANE : ICP_NPART);
+  EGONN_REQUIRE(scratch_bytes >= (int64_t)G.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
+                "%s: scratch needs %lld bytes, 256-byte aligned", who, (long long)G.total);
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  IcpPair* pairs = (IcpPair*)(base + L.pairs);
-  int32_t* wg0 = (int32_t*)(base + L.wg0);
-  const size_t rounds = (size_t)max_iteration + 1;
-  if (T_trace) HIP_CHECK(hipMemsetAsync(T_trace, 0, (size_t)n_pairs * rounds * 16 * sizeof(double), st));
-  if (eval_trace) HIP_CHECK(hipMemsetAsync(eval_trace, 0, (size_t)n_pairs * rounds * 3 * sizeof(double), st));
+  EGONN_TRY(pair_clear_traces(T_trace, eval_trace, 3, n_pairs, max_iteration, st));
   if (corr && n_src > 0) HIP_CHECK(hipMemsetAsync(corr, 0xFF, (size_t)n_src * sizeof(int32_t), st));
   hipLaunchKernelGGL(icp_setup_kernel, dim3((unsigned)n_pairs), dim3(ICP_WG), 0, st, tgt, n_tgt, src_offsets, tgt_offsets, n_src,
-                     n_pairs, T_init, max_dist, pairs, wg0, T, fitness, inlier_rmse, iterations, status, T_trace, max_iteration);
+                     n_pairs, T_init, max_dist, G.pairs, G.wg0, T, fitness, inlier_rmse, iterations, status, T_trace, max_iteration);
   HIP_CHECK(hipGetLastError());
   if (n_src == 0 || n_tgt == 0) return EGONN_OK;         // every pair is EMPTY
-  double* tq = (double*)(base + L.tq);
-  int32_t* tj = (int32_t*)(base + L.tj);
-  uint64_t* tkey = (uint64_t*)(base + L.tkey);
-  double* sq = (double*)(base + L.sq);
-  int32_t* si = (int32_t*)(base + L.si);
-  double* partial = (double*)(base + L.partial);
-  Arena sort_ws = Arena::view(base + L.sort, L.sort_bytes);
-  uint64_t *k0 = (uint64_t*)(base + L.keys0), *k1 = (uint64_t*)(base + L.keys1);
-  uint32_t *v0 = (uint32_t*)(base + L.vals0), *v1 = (uint32_t*)(base + L.vals1);
-  EGONN_TRY(icp_order_side(0, tgt, n_tgt, tgt_offsets, n_pairs, pairs, sort_ws, k0, v0, k1, v1, tq, tj, tkey, st));
-  EGONN_TRY(icp_order_side(1, src, n_src, src_offsets, n_pairs, pairs, sort_ws, k0, v0, k1, v1, sq, si, nullptr, st));
-  const dim3 grid((unsigned)L.n_wg), one((unsigned)n_pairs);
+  EGONN_TRY(icp_build_grid(G, tgt, n_tgt, tgt_offsets, src, n_src, src_offsets, n_pairs, st));
+  const dim3 grid((unsigned)G.n_wg), one((unsigned)n_pairs);
   for (int k = 0; k <= max_iteration; ++k) {
-    if (L.estimator) {
-      hipLaunchKernelGGL(icp_search_kernel<1>, grid, dim3(ICP_WG), 0, st, pairs, wg0, n_pairs, sq, si, tq, tj, tkey, tgt_normals,
-                         max_dist, partial, corr);
-      hipLaunchKernelGGL(icp_finish_kernel<1>, one, dim3(64), 0, st, pairs, wg0, partial, k, max_iteration, eps_fitness, eps_rmse, T,
-                         fitness, inlier_rmse, iterations, status, T_trace, eval_trace);
+    if (estimator) {
+      hipLaunchKernelGGL(icp_search_kernel<1>, grid, dim3(ICP_WG), 0, st, G.pairs, G.wg0, n_pairs, G.sq, G.si, G.tq, G.tj, G.tkey,
+                         tgt_normals, max_dist, G.partial, corr);
+      hipLaunchKernelGGL(icp_finish_kernel<1>, one, dim3(64), 0, st, G.pairs, G.wg0, G.partial, k, max_iteration, eps_fitness, eps_rmse,
+                         T, fitness, inlier_rmse, iterations, status, T_trace, eval_trace);
     } else {
-      hipLaunchKernelGGL(icp_search_kernel<0>, grid, dim3(ICP_WG), 0, st, pairs, wg0, n_pairs, sq, si, tq, tj, tkey,
-                         (const double*)nullptr, max_dist, partial, corr);
-      hipLaunchKernelGGL(icp_finish_kernel<0>, one, dim3(64), 0, st, pairs, wg0, partial, k, max_iteration, eps_fitness, eps_rmse, T,
-                         fitness, inlier_rmse, iterations, status, T_trace, eval_trace);
+      hipLaunchKernelGGL(icp_search_kernel<0>, grid, dim3(ICP_WG), 0, st, G.pairs, G.wg0, n_pairs, G.sq, G.si, G.tq, G.tj, G.tkey,
+                         (const double*)nullptr, max_dist, G.partial, corr);
+      hipLaunchKernelGGL(icp_finish_kernel<0>, one, dim3(64), 0, st, G.pairs, G.wg0, G.partial, k, max_iteration, eps_fitness, eps_rmse,
+                         T, fitness, inlier_rmse, iterations, status, T_trace, eval_trace);
     }
   }
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
 
-static bool icp_shape_ok(int64_t n_src, int64_t n_tgt, int n_pairs) {
-  return n_src >= 0 && n_tgt >= 0 && n_src < (1ll << 31) && n_tgt < (1ll << 31) && n_pairs >= 1 && n_pairs <= EGONN_MAX_BATCH;
-}
-
 API int64_t egonn_icp_scratch_bytes(int64_t n_src, int64_t n_tgt, int n_pairs) {
   if (!icp_shape_ok(n_src, n_tgt, n_pairs)) return -1;
-  return (int64_t)icp_layout(n_src, n_tgt, n_pairs, 0).total;
+  return (int64_t)icp_grid(nullptr, n_src, n_tgt, n_pairs, ICP_NPART).total;
 }
 
 API int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_offsets, const double* tgt, int64_t n_tgt,
@@ -1029,16 +955,14 @@ API int egonn_icp_pairs(const double* src, int64_t n_src, const int64_t* src_off
                         double eps_fitness, double eps_rmse, double* T, double* fitness, double* inlier_rmse, int32_t* iterations,
                         int32_t* status, double* T_trace, double* eval_trace, int32_t* corr, void* scratch, int64_t scratch_bytes,
                         void* stream) {
-  // the layout is computed on sanitised capacities: icp_run refuses bad ones before it looks at it
-  const bool ok = icp_shape_ok(n_src, n_tgt, n_pairs);
-  return icp_run(icp_layout(ok ? n_src : 0, ok ? n_tgt : 0, ok ? n_pairs : 1, 0), "icp_pairs", src, n_src, src_offsets, tgt, n_tgt,
-                 tgt_offsets, nullptr, n_pairs, T_init, max_dist, max_iteration, eps_fitness, eps_rmse, T, fitness, inlier_rmse,
-                 iterations, status, T_trace, eval_trace, corr, scratch, scratch_bytes, stream);
+  return icp_run(0, "icp_pairs", src, n_src, src_offsets, tgt, n_tgt, tgt_offsets, nullptr, n_pairs, T_init, max_dist, max_iteration,
+                 eps_fitness, eps_rmse, T, fitness, inlier_rmse, iterations, status, T_trace, eval_trace, corr, scratch, scratch_bytes,
+                 stream);
 }
 
 API int64_t egonn_icp_plane_scratch_bytes(int64_t n_src, int64_t n_tgt, int n_pairs) {
   if (!icp_shape_ok(n_src, n_tgt, n_pairs)) return -1;
-  return (int64_t)icp_layout(n_src, n_tgt, n_pairs, 1).total;
+  return (int64_t)icp_grid(nullptr, n_src, n_tgt, n_pairs, ICP_NPART_PLANE).total;
 }
 
 API int egonn_icp_plane_pairs(const double* src, int64_t n_src, const int64_t* src_offsets, const double* tgt, int64_t n_tgt,
@@ -1046,59 +970,43 @@ API int egonn_icp_plane_pairs(const double* src, int64_t n_src, const int64_t* s
                               double max_dist, int max_iteration, double eps_fitness, double eps_rmse, double* T, double* fitness,
                               double* inlier_rmse, int32_t* iterations, int32_t* status, double* T_trace, double* eval_trace,
                               int32_t* corr, void* scratch, int64_t scratch_bytes, void* stream) {
-  const bool ok = icp_shape_ok(n_src, n_tgt, n_pairs);
-  return icp_run(icp_layout(ok ? n_src : 0, ok ? n_tgt : 0, ok ? n_pairs : 1, 1), "icp_plane_pairs", src, n_src, src_offsets, tgt,
-                 n_tgt, tgt_offsets, tgt_normals, n_pairs, T_init, max_dist, max_iteration, eps_fitness, eps_rmse, T, fitness,
-                 inlier_rmse, iterations, status, T_trace, eval_trace, corr, scratch, scratch_bytes, stream);
+  return icp_run(1, "icp_plane_pairs", src, n_src, src_offsets, tgt, n_tgt, tgt_offsets, tgt_normals, n_pairs, T_init, max_dist,
+                 max_iteration, eps_fitness, eps_rmse, T, fitness, inlier_rmse, iterations, status, T_trace, eval_trace, corr, scratch,
+                 scratch_bytes, stream);
 }
 
 API int64_t egonn_estimate_normals_scratch_bytes(int64_t n, int n_clouds) {
-  if (n < 0 || n >= (1ll << 31) || n_clouds < 1 || n_clouds > EGONN_MAX_BATCH) return -1;
-  return (int64_t)nrm_layout(n, n_clouds).total;
+  if (!icp_shape_ok(n, n, n_clouds)) return -1;
+  return (int64_t)icp_grid(nullptr, n, n, n_clouds, 0).total;
 }
 
 API int egonn_estimate_normals(const double* points, int64_t n, const int64_t* offsets, int n_clouds, int knn, double* normals,
                                int32_t* status, int32_t* neighbors, double* eigenvalues, void* scratch, int64_t scratch_bytes,
                                void* stream) {
-  EGONN_REQUIRE(n >= 0 && n < (1ll << 31) && n_clouds >= 1 && n_clouds <= EGONN_MAX_BATCH, EGONN_ERR_INVALID,
-                "estimate_normals: bad shape (n=%lld, n_clouds=%d; n_clouds <= %d)", (long long)n, n_clouds, EGONN_MAX_BATCH);
+  EGONN_REQUIRE(icp_shape_ok(n, n, n_clouds), EGONN_ERR_INVALID, "estimate_normals: bad shape (n=%lld, n_clouds=%d; n_clouds <= %d)",
+                (long long)n, n_clouds, EGONN_MAX_BATCH);
   EGONN_REQUIRE(knn >= NRM_KNN_MIN && knn <= NRM_KNN_MAX, EGONN_ERR_INVALID, "estimate_normals: knn %d outside [%d, %d]", knn,
                 NRM_KNN_MIN, NRM_KNN_MAX);
   EGONN_REQUIRE(offsets && status && scratch && (n == 0 || (points && normals)), EGONN_ERR_INVALID, "estimate_normals: null pointer");
-  const NrmLayout L = nrm_layout(n, n_clouds);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "estimate_normals: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  const IcpGrid G = icp_grid(scratch, n, n, n_clouds, 0);
+  EGONN_REQUIRE(scratch_bytes >= (int64_t)G.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
+                "estimate_normals: scratch needs %lld bytes, 256-byte aligned", (long long)G.total);
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  IcpPair* pairs = (IcpPair*)(base + L.pairs);
-  int32_t* wg0 = (int32_t*)(base + L.wg0);
   hipLaunchKernelGGL(nrm_status_kernel, dim3((unsigned)n_clouds), dim3(ICP_WG), 0, st, points, n, offsets, knn, status);
   HIP_CHECK(hipGetLastError());
   if (n == 0) return EGONN_OK;
-  // the ICP's grid with source = target = the cloud, T = identity and the cell edge as the search radius; what the setup
-  // writes for an empty cloud lands in scratch
-  double* outs = (double*)(base + L.outs);
-  double *o_T = outs, *o_fit = outs + (size_t)n_clouds * 16, *o_rmse = o_fit + n_clouds;
-  int32_t *o_it = (int32_t*)(o_rmse + n_clouds), *o_st = (int32_t*)(o_rmse + 2 * (size_t)n_clouds);
+  // the ICP's grid with source = target = the cloud, T = identity, the cell edge as the search radius and no pair outputs
   hipLaunchKernelGGL(icp_setup_kernel, dim3((unsigned)n_clouds), dim3(ICP_WG), 0, st, points, n, offsets, offsets, n, n_clouds,
-                     (const double*)nullptr, NRM_CELL, pairs, wg0, o_T, o_fit, o_rmse, o_it, o_st, (double*)nullptr, 0);
-  double* tq = (double*)(base + L.tq);
-  int32_t* tj = (int32_t*)(base + L.tj);
-  uint64_t* tkey = (uint64_t*)(base + L.tkey);
-  double* sq = (double*)(base + L.sq);
-  int32_t* si = (int32_t*)(base + L.si);
-  Arena sort_ws = Arena::view(base + L.sort, L.sort_bytes);
-  uint64_t *k0 = (uint64_t*)(base + L.keys0), *k1 = (uint64_t*)(base + L.keys1);
-  uint32_t *v0 = (uint32_t*)(base + L.vals0), *v1 = (uint32_t*)(base + L.vals1);
-  EGONN_TRY(icp_order_side(0, points, n, offsets, n_clouds, pairs, sort_ws, k0, v0, k1, v1, tq, tj, tkey, st));
-  EGONN_TRY(icp_order_side(1, points, n, offsets, n_clouds, pairs, sort_ws, k0, v0, k1, v1, sq, si, nullptr, st));
-  const dim3 grid((unsigned)L.n_wg);
+                     (const double*)nullptr, NRM_CELL, G.pairs, G.wg0, (double*)nullptr, (double*)nullptr, (double*)nullptr,
+                     (int32_t*)nullptr, (int32_t*)nullptr, (double*)nullptr, 0);
+  EGONN_TRY(icp_build_grid(G, points, n, offsets, points, n, offsets, n_clouds, st));
+  const dim3 grid((unsigned)G.n_wg);
   if (knn <= 20)
-    hipLaunchKernelGGL(nrm_knn_kernel<20>, grid, dim3(ICP_WG), 0, st, pairs, wg0, n_clouds, points, sq, si, tq, tj, tkey, knn, status,
-                       normals, neighbors, eigenvalues);
+    hipLaunchKernelGGL(nrm_knn_kernel<20>, grid, dim3(ICP_WG), 0, st, G.pairs, G.wg0, n_clouds, points, G.sq, G.si, G.tq, G.tj, G.tkey, knn,
+                       status, normals, neighbors, eigenvalues);
   else
-    hipLaunchKernelGGL(nrm_knn_kernel<32>, grid, dim3(ICP_WG), 0, st, pairs, wg0, n_clouds, points, sq, si, tq, tj, tkey, knn, status,
-                       normals, neighbors, eigenvalues);
+    hipLaunchKernelGGL(nrm_knn_kernel<32>, grid, dim3(ICP_WG), 0, st, G.pairs, G.wg0, n_clouds, points, G.sq, G.si, G.tq, G.tj, G.tkey, knn,
+                       status, normals, neighbors, eigenvalues);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }

@@ -13,10 +13,13 @@
 // register    ndt_setup (pairs, the workgroup table), then max_iteration + 1 rounds of ndt_eval (256 consecutive source points
 //             of one pair per workgroup: up to seven lookups per point, 30 partial sums in a fixed tree) and ndt_finish (one
 //             workgroup per pair: partials in ascending order, the stop rule, the 6 x 6 step of plane_step.h).  A stopped
-//             pair's workgroups return at once.  No call synchronises with the host.
+//             pair's workgroups return at once.  No call synchronises with the host.  The loop itself (per-pair state, the flat
+//             grid, the tree, the gather, stop and advance) is pair_loop.h, shared with icp.hip; this file supplies the terms
+//             of a point, the stop rule on the step's size and the step.
 #include "../../include/egonn_hip.h"
 #include "common.h"
 #include "jacobi3.h"
+#include "pair_loop.h"
 #include "plane_step.h"
 #include "voxel_key.h"
 
@@ -24,7 +27,7 @@
 
 namespace egonn {
 
-static constexpr int NDT_WG = 256;
+static constexpr int NDT_WG = PAIR_WG;
 static constexpr int NDT_NPART = 30;             // n_term, n_pts, A (21 upper entries row by row), b (6), score: the layout of
                                                  // icp_plane_solve at [2, 29)
 static constexpr int NDT_MOMENT_SHIFT = 10;      // m = q >> 10: 20 bits, so 2^23 squares fit an int64
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(NDT_WG) void ndt_finalize_kernel(const uint64_t* __
 }
 
 // ------------------------------------------------------------------ register
-struct NdtPair {
+struct NdtPair {            // the members pair_loop.h asks for, and conv
   double R[9], t[3];        // T_k
   int64_t so;               // first source point
   int32_t ns, done, status, conv;      // conv: the last step was below both epsilons
@@ -197,11 +200,6 @@ struct NdtLayer {
   const uint8_t* valid;
 };
 
-__device__ static inline void ndt_write_T(double* To, const double* R, const double* t) {
-  for (int r = 0; r < 3; ++r) To[r * 4] = R[r * 3], To[r * 4 + 1] = R[r * 3 + 1], To[r * 4 + 2] = R[r * 3 + 2], To[r * 4 + 3] = t[r];
-  To[12] = To[13] = To[14] = 0.0, To[15] = 1.0;
-}
-
 __global__ __launch_bounds__(NDT_WG) void ndt_setup_kernel(const int64_t* __restrict__ soff, int64_t ns_cap, int P,
                                                            const double* __restrict__ T_init, NdtPair* __restrict__ pairs,
                                                            int32_t* __restrict__ wg0, double* __restrict__ T_out,
@@ -210,42 +208,14 @@ __global__ __launch_bounds__(NDT_WG) void ndt_setup_kernel(const int64_t* __rest
                                                            double* __restrict__ T_trace, int max_it) {
   const int p = blockIdx.x * NDT_WG + threadIdx.x;
   if (p >= P) return;
-  const int64_t so = clipi(soff[p], ns_cap), se = clipi(soff[p + 1], ns_cap);
-  const int64_t ns = se > so ? se - so : 0;
   NdtPair q;
-  double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  if (T_init)
-    for (int k = 0; k < 16; ++k) T[k] = T_init[(size_t)p * 16 + k];
-  for (int r = 0; r < 3; ++r) {
-    q.R[r * 3] = T[r * 4], q.R[r * 3 + 1] = T[r * 4 + 1], q.R[r * 3 + 2] = T[r * 4 + 2];
-    q.t[r] = T[r * 4 + 3];
-  }
-  q.so = so, q.ns = (int32_t)ns, q.done = 0, q.status = 0, q.conv = 0;
-  if (T_trace) ndt_write_T(T_trace + ((size_t)p * (max_it + 1)) * 16, q.R, q.t);
-  if (ns == 0) {
-    q.done = 1, q.status = EGONN_ICP_STATUS_EMPTY;
-    ndt_write_T(T_out + (size_t)p * 16, q.R, q.t);
-    fitness[p] = 0.0, score[p] = 0.0, iterations[p] = 0, status[p] = q.status;
+  pair_begin(&q, soff, ns_cap, P, p, T_init, T_trace, max_it, wg0);
+  q.conv = 0;
+  if (q.ns == 0) {
+    pair_stop(&q, p, 0, EGONN_ICP_STATUS_EMPTY, T_out, iterations, status);
+    fitness[p] = 0.0, score[p] = 0.0;
   }
   pairs[p] = q;
-  // first workgroup of the pair in the flat grid: a function of the sizes of the pairs before it only
-  int64_t w = 0;
-  for (int b = 0; b < p; ++b) {
-    const int64_t a = clipi(soff[b], ns_cap), e = clipi(soff[b + 1], ns_cap);
-    w += e > a ? (e - a + NDT_WG - 1) / NDT_WG : 0;
-  }
-  wg0[p] = (int32_t)w;
-  if (p == P - 1) wg0[P] = (int32_t)(w + (ns + NDT_WG - 1) / NDT_WG);
-}
-
-// pair of workgroup `flat`: the largest p with wg0[p] <= flat
-__device__ static inline int ndt_pair_of(const int32_t* __restrict__ wg0, int P, int flat) {
-  int lo = 0, hi = P - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (wg0[mid] <= flat) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 // one term: the Gaussian of `row` seen from vs; adds into the lane's sums v
@@ -287,23 +257,20 @@ __global__ __launch_bounds__(NDT_WG) void ndt_eval_kernel(const NdtPair* __restr
                                                           double* __restrict__ partial) {
   __shared__ double s_red[NDT_NPART][4];
   const int flat = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int p = ndt_pair_of(wg0, P, flat);
+  const int p = pair_of(wg0, P, flat);
   const NdtPair* q = pairs + p;
-  const int chunk = flat - wg0[p];
-  const int ns = q->ns;
-  if (q->done || chunk < 0 || (int64_t)chunk * NDT_WG >= ns) return;          // workgroup-uniform
+  const int chunk = pair_chunk(q, wg0[p], flat);
+  if (chunk < 0) return;                                  // workgroup-uniform
   const int row = chunk * NDT_WG + t;
   double v[NDT_NPART];
 #pragma unroll
   for (int k = 0; k < NDT_NPART; ++k) v[k] = 0.0;
-  if (row < ns) {
-    const double* s = src + (q->so + row) * 3;
-    const double x = s[0], y = s[1], z = s[2];
+  if (row < q->ns) {
     double vs[3], f[3];
     bool ok = true;
+    pair_apply(q, src + (q->so + row) * 3, vs);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      vs[a] = ((q->R[a * 3] * x + q->R[a * 3 + 1] * y) + q->R[a * 3 + 2] * z) + q->t[a];
       f[a] = floor(vs[a] / voxel);
       ok = ok && f[a] >= -(double)VM_BIAS - 1.0 && f[a] <= (double)VM_BIAS;      // beyond: no neighbour is in range; false for NaN
     }
@@ -353,14 +320,7 @@ __global__ __launch_bounds__(NDT_WG) void ndt_eval_kernel(const NdtPair* __restr
       v[1] = any ? 1.0 : 0.0;
     }
   }
-#pragma unroll
-  for (int k = 0; k < NDT_NPART; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);      // a fixed tree
-    if (lane == 0) s_red[k][w] = v[k];
-  }
-  __syncthreads();
-  if (t < NDT_NPART) partial[(size_t)flat * NDT_NPART + t] = ((s_red[t][0] + s_red[t][1]) + s_red[t][2]) + s_red[t][3];
+  pair_reduce<NDT_NPART>(v, s_red, partial, flat, lane, w);
 }
 
 __global__ __launch_bounds__(64) void ndt_finish_kernel(NdtPair* __restrict__ pairs, const int32_t* __restrict__ wg0,
@@ -373,13 +333,7 @@ __global__ __launch_bounds__(64) void ndt_finish_kernel(NdtPair* __restrict__ pa
   const int p = blockIdx.x, t = threadIdx.x;
   NdtPair* q = pairs + p;
   if (q->done) return;
-  const int nwg = (q->ns + NDT_WG - 1) / NDT_WG, first = wg0[p];
-  if (t < NDT_NPART) {
-    double acc = 0.0;
-    for (int c = 0; c < nwg; ++c) acc += partial[(size_t)(first + c) * NDT_NPART + t];     // ascending workgroups
-    s[t] = acc;
-  }
-  __syncthreads();
+  pair_gather<NDT_NPART>(q, wg0[p], partial, s);
   if (t != 0) return;
   const double n_term = s[0], n_pts = s[1], sc = s[29];
   int stop = 0, st = q->status;
@@ -395,40 +349,17 @@ __global__ __launch_bounds__(64) void ndt_finish_kernel(NdtPair* __restrict__ pa
   if (sums_trace)
     for (int k = 0; k < NDT_NPART; ++k) sums_trace[((size_t)p * (max_it + 1) + round) * NDT_NPART + k] = s[k];
   if (stop) {
-    ndt_write_T(T_out + (size_t)p * 16, q->R, q->t);
-    fitness[p] = n_pts / (double)q->ns, score[p] = sc / (double)q->ns, iterations[p] = round, status[p] = st;
-    q->status = st;
-    q->done = 1;
+    fitness[p] = n_pts / (double)q->ns, score[p] = sc / (double)q->ns;
+    pair_stop(q, p, round, st, T_out, iterations, status);
     return;
   }
-  double U[9], ut[3], Rn[9], tn[3];
+  double U[9], ut[3];
   icp_plane_update(x, U, ut);
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) Rn[r * 3 + c] = U[r * 3] * q->R[c] + U[r * 3 + 1] * q->R[3 + c] + U[r * 3 + 2] * q->R[6 + c];
-    tn[r] = U[r * 3] * q->t[0] + U[r * 3 + 1] * q->t[1] + U[r * 3 + 2] * q->t[2] + ut[r];
-  }
-  for (int k = 0; k < 9; ++k) q->R[k] = Rn[k];
-  for (int k = 0; k < 3; ++k) q->t[k] = tn[k];
   const double mr = fmax(fmax(fabs(x[0]), fabs(x[1])), fabs(x[2])), mt = fmax(fmax(fabs(x[3]), fabs(x[4])), fabs(x[5]));
   q->conv = mr < eps_rot && mt < eps_trans ? 1 : 0;
-  if (T_trace) ndt_write_T(T_trace + ((size_t)p * (max_it + 1) + round + 1) * 16, Rn, tn);
+  pair_advance(q, p, round, max_it, U, ut, T_trace);
 }
 
-struct NdtLayout {
-  size_t pairs, wg0, partial, total;
-  int64_t n_wg;
-};
-static NdtLayout ndt_layout(int64_t n_src, int n_pairs) {
-  NdtLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
-  L.n_wg = cdiv(n_src, NDT_WG) + n_pairs;                 // every pair rounds its own workgroups up
-  L.pairs = take((size_t)n_pairs * sizeof(NdtPair));
-  L.wg0 = take((size_t)(n_pairs + 1) * 4);
-  L.partial = take((size_t)L.n_wg * NDT_NPART * 8);
-  L.total = o;
-  return L;
-}
 static bool ndt_register_shape_ok(int64_t n_src, int n_pairs) {
   return n_src >= 0 && n_src < (1ll << 31) && n_pairs >= 1 && n_pairs <= EGONN_MAX_BATCH;
 }
@@ -494,7 +425,9 @@ API int egonn_ndt_finalize(const uint64_t* keys, const int64_t* n_dev, int64_t c
 
 API int64_t egonn_ndt_register_scratch_bytes(int64_t n_src, int n_pairs) {
   if (!ndt_register_shape_ok(n_src, n_pairs)) return -1;
-  return (int64_t)ndt_layout(n_src, n_pairs).total;
+  Carve c;
+  c.take((size_t)pair_layout(c, n_src, n_pairs, sizeof(NdtPair)).n_wg * NDT_NPART * 8);
+  return (int64_t)c.o;
 }
 
 API int egonn_ndt_register(const double* src, int64_t n_src, const int64_t* src_offsets, int n_pairs, const double* T_init,
@@ -513,18 +446,19 @@ API int egonn_ndt_register(const double* src, int64_t n_src, const int64_t* src_
   EGONN_REQUIRE(src_offsets && n_dev && T && fitness && score && iterations && status && scratch && (n_src == 0 || src) &&
                     (capacity_map == 0 || (keys && mean && info && valid)),
                 EGONN_ERR_INVALID, "ndt_register: null pointer");
-  const NdtLayout L = ndt_layout(n_src, n_pairs);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "ndt_register: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  Carve c;
+  const PairLayout L = pair_layout(c, n_src, n_pairs, sizeof(NdtPair));
+  const size_t partial_at = c.take((size_t)L.n_wg * NDT_NPART * 8);
+  EGONN_REQUIRE(scratch_bytes >= (int64_t)c.o && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
+                "ndt_register: scratch needs %lld bytes, 256-byte aligned", (long long)c.o);
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)scratch;
   NdtPair* pairs = (NdtPair*)(base + L.pairs);
   int32_t* wg0 = (int32_t*)(base + L.wg0);
-  double* partial = (double*)(base + L.partial);
-  const size_t rounds = (size_t)max_iteration + 1;
-  if (T_trace) HIP_CHECK(hipMemsetAsync(T_trace, 0, (size_t)n_pairs * rounds * 16 * sizeof(double), st));
-  if (eval_trace) HIP_CHECK(hipMemsetAsync(eval_trace, 0, (size_t)n_pairs * rounds * 4 * sizeof(double), st));
-  if (sums_trace) HIP_CHECK(hipMemsetAsync(sums_trace, 0, (size_t)n_pairs * rounds * NDT_NPART * sizeof(double), st));
+  double* partial = (double*)(base + partial_at);
+  EGONN_TRY(pair_clear_traces(T_trace, eval_trace, 4, n_pairs, max_iteration, st));
+  if (sums_trace)
+    HIP_CHECK(hipMemsetAsync(sums_trace, 0, (size_t)n_pairs * ((size_t)max_iteration + 1) * NDT_NPART * sizeof(double), st));
   hipLaunchKernelGGL(ndt_setup_kernel, dim3((unsigned)cdiv(n_pairs, NDT_WG)), dim3(NDT_WG), 0, st, src_offsets, n_src, n_pairs, T_init,
                      pairs, wg0, T, fitness, score, iterations, status, T_trace, max_iteration);
   HIP_CHECK(hipGetLastError());

@@ -8,6 +8,7 @@
 
 #include "../../include/egonn_hip.h"
 #include "common.h"
+#include "pose_math.h"      // se3_store only: the arithmetic there is not this file's (contraction)
 
 #pragma clang fp contract(off)
 
@@ -147,11 +148,7 @@ __device__ static void pair_tail(const PairIn& in, const PairOut& o, int p, cons
       if (o.inliers) o.inliers[p] = k;
       if (o.fitness) o.fitness[p] = m1 > 0 ? (double)k / (double)m1 : 0.0;
       if (o.rmse) o.rmse[p] = k > 0 ? sqrt(e2 / (double)k) : 0.0;
-      if (o.T) {
-        double* To = o.T + (size_t)p * 16;
-        for (int r = 0; r < 3; ++r) To[r * 4] = R[r * 3], To[r * 4 + 1] = R[r * 3 + 1], To[r * 4 + 2] = R[r * 3 + 2], To[r * 4 + 3] = tf[r];
-        To[12] = To[13] = To[14] = 0.0, To[15] = 1.0;
-      }
+      if (o.T) se3_store(R, tf, o.T + (size_t)p * 16);
     }
     if (!model) st |= EGONN_REG_STATUS_NO_MODEL;
   }

@@ -1,6 +1,8 @@
 // Rigid-pose arithmetic in float64 shared by the pose graph (pose_graph.hip) and the loop-consistency filter
 // (loop_consistency.hip): 3x3 algebra, SE(3) products as (R, t) pairs, the SO(3) logarithm and the validity test of an edge.
 // Stated once here so that both files take the same logarithm (series threshold, atan2 form) and switch the same edges off.
+// This header sets no contraction mode: its arithmetic is for those two files only.  se3_load and se3_store move data and
+// nothing else, and are what the contraction-off code (pair_loop.h, pair_eval.h) takes from here.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -51,6 +53,16 @@ __device__ static inline void se3_load(const double* __restrict__ X, double* R, 
     for (int j = 0; j < 3; ++j) R[3 * i + j] = X[4 * i + j];
     t[i] = X[4 * i + 3];
   }
+}
+// (R, t) as a (4,4) row-major pose
+__device__ static inline void se3_store(const double* R, const double* t, double* __restrict__ X) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) X[4 * i + j] = R[3 * i + j];
+    X[4 * i + 3] = t[i];
+  }
+  X[12] = X[13] = X[14] = 0.0, X[15] = 1.0;
 }
 // (R, t) = A B
 __device__ static inline void se3_mul(const double* Ra, const double* ta, const double* Rb, const double* tb, double* R, double* t) {

@@ -263,6 +263,32 @@ def test_runs_and_batches_are_bitwise_equal(gpu):
     assert np.array_equal(dev["T"][0], a["T"][0]) and dev["iterations"][0] == a["iterations"][0]
 
 
+EDGE_SIZES = (300, 0, 256, 257, 1)     # source points: an empty pair between two others, exactly one workgroup, one point more, one point
+
+
+def edge_batch():
+    """One pair per EDGE_SIZES entry, the smallest shapes at which the flat grid's indexing can go wrong: 400 points spread over
+    the target of scan_8k, and as sources their first n points moved off by a small rigid motion (so every source point has its
+    correspondence and the loop runs)."""
+    tgt = icp_case("scan_8k")["tgt"][::20][:400]
+    a = 0.004
+    M = np.array([[np.cos(a), -np.sin(a), 0.0, 0.05], [np.sin(a), np.cos(a), 0.0, -0.03], [0.0, 0.0, 1.0, 0.02], [0.0, 0.0, 0.0, 1.0]])
+    T0 = np.stack([np.linalg.inv(M)] * len(EDGE_SIZES))
+    T0[3, :3, 3] += 0.01                                               # not every pair from the same start
+    return [tgt[:n] @ M[:3, :3].T + M[:3, 3] for n in EDGE_SIZES], [tgt] * len(EDGE_SIZES), T0
+
+
+def test_edge_sizes_in_one_batch_equal_the_pair_alone(gpu):
+    srcs, tgts, T0 = edge_batch()
+    a = _icp(gpu, srcs, tgts, T0)
+    assert a["status"][1] == ICP_EMPTY and a["status"][4] == ICP_FEW_CORR and (a["iterations"][[0, 2, 3]] >= 1).all()
+    for pos in range(len(srcs)):                                       # each alone is also the single-pair batch
+        one = _icp(gpu, srcs[pos:pos + 1], tgts[pos:pos + 1], T0[pos:pos + 1])
+        for k in KEYS:
+            assert np.array_equal(one[k][0], a[k][pos]), (k, pos)
+        assert np.array_equal(one["corr"][0], a["corr"][pos]), pos
+
+
 def test_graph_replay_equals_eager(gpu):
     _, srcs, tgts, T0 = _batch16()
     srcs, tgts, T0 = srcs[:4], tgts[:4], T0[:4]

@@ -319,6 +319,21 @@ def test_runs_and_batches_are_bitwise_equal(gpu):
     assert np.array_equal(_teacher_forced(gpu, names[0])["dev"]["T"][0], a["T"][0])
 
 
+def test_edge_sizes_in_one_batch_equal_the_pair_alone(gpu):
+    """the pairs of tests/test_gpu_icp.py:edge_batch (300, 0, 256, 257 and 1 source points) with the plane estimator"""
+    from tests.test_gpu_icp import edge_batch
+    srcs, tgts, T0 = edge_batch()
+    nrm = _normals(gpu, tgts[:1])["normals"] * len(tgts)
+    a = _plane(gpu, srcs, tgts, nrm, T0)
+    print("edge batch: iterations", a["iterations"].tolist(), "status", a["status"].tolist())
+    assert a["status"][1] == ICP_EMPTY and a["status"][4] == ICP_FEW_CORR and (a["iterations"][[0, 2, 3]] >= 1).all()
+    for pos in range(len(srcs)):                                       # each alone is also the single-pair batch
+        one = _plane(gpu, srcs[pos:pos + 1], tgts[pos:pos + 1], nrm[pos:pos + 1], T0[pos:pos + 1])
+        for k in KEYS:
+            assert np.array_equal(one[k][0], a[k][pos]), (k, pos)
+        assert np.array_equal(one["corr"][0], a["corr"][pos]), pos
+
+
 def test_graph_replay_equals_eager(gpu):
     cs = [icp_case(n) for n in SMALL[:3]]
     srcs, tgts, T0 = [c["src"] for c in cs], [c["tgt"] for c in cs], np.stack([c["T_init"] for c in cs])

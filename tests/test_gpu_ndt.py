@@ -476,6 +476,23 @@ def test_a_pair_has_the_same_bits_alone_and_in_any_batch(gpu, planted):
         assert int(alone["iterations"][0]) > 3
 
 
+def test_edge_sizes_in_one_batch_equal_the_pair_alone(gpu, planted):
+    """300, 0, 256, 257 and 1 source points in one batch: an empty pair between two others, exactly one workgroup, one point into a
+    second, a single point; each against the same pair run alone, which is also the single-pair batch"""
+    c, layers = planted
+    M, cloud = layers[0], c["clouds"][0][::3]                                  # every third point: spread over the whole scene
+    clouds = [cloud[:300], cloud[:0], cloud[7:263], cloud[7:264], cloud[50:51]]
+    assert [len(x) for x in clouds] == [300, 0, 256, 257, 1]
+    Ts = np.stack([c["T0"][0]] * 4 + [c["T_planted"][0]])
+    for nb in (1, 7):
+        a = _res(_register(M, clouds, Ts, nb))
+        assert int(a["status"][1]) == ref.EMPTY and (a["iterations"][[0, 2, 3]] >= 1).all()
+        for pos in range(len(clouds)):
+            one = _res(_register(M, clouds[pos:pos + 1], Ts[pos:pos + 1], nb))
+            for k in KEYS:
+                assert np.array_equal(one[k][0], a[k][pos], equal_nan=True), (nb, k, pos)
+
+
 def test_replayed_graph_is_bit_equal_after_the_scratch_was_overwritten(gpu, planted):
     from egonn_amd import _lib
     lib = _lib.load()

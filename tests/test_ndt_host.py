@@ -243,9 +243,25 @@ def test_symbols_declared_and_exported(lib):
     assert not re.search(r"atomicAdd\s*\(\s*\(?\s*(float|double)|unsafeAtomicAdd|atomicAdd_system", src), "integer atomics only"
     # the shared arithmetic is stated once
     csrc = os.path.join(REPO, "egonn_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
     for fn, home in (("nrm_jacobi3", "jacobi3.h"), ("icp_plane_solve", "plane_step.h"), ("vm_point_key", "voxel_key.h")):
-        defs = [f for f in sorted(os.listdir(csrc)) if re.search(r"\b(void|bool)\s+" + fn + r"\s*\(", open(os.path.join(csrc, f)).read())]
+        defs = [f for f in text if re.search(r"\b(void|bool)\s+" + fn + r"\s*\(", text[f])]
         assert defs == [home], (fn, defs)
+    # the loop around it as well (pair_loop.h): every piece is defined there and nowhere else, and the copies it replaced are gone
+    loop = ("pair_apply", "pair_begin", "pair_of", "pair_chunk", "pair_reduce", "pair_gather", "pair_stop", "pair_advance",
+            "pair_layout", "pair_clear_traces")
+    for fn, home in [(fn, "pair_loop.h") for fn in loop] + [("se3_load", "pose_math.h"), ("se3_store", "pose_math.h")]:
+        defs = [f for f in text if re.search(r"\b(void|bool|int|PairLayout)\s+" + fn + r"\s*\([^;{]*\)\s*\{", text[f])]
+        assert defs == [home], (fn, defs)
+    for fn in loop:
+        users = ("ndt.hip",) if fn == "pair_chunk" else ("icp.hip", "ndt.hip")      # icp.hip's hot kernels spell the early-out out
+        assert all(re.search(r"\b" + fn + r"(<[^>]*>)?\(", text[f]) for f in users), fn
+    for old in ("icp_pair_of", "ndt_pair_of", "ndt_write_T"):
+        assert not [f for f in text if re.search(r"\b" + old + r"\b", text[f])], old
+    for f in ("icp.hip", "ndt.hip"):
+        assert '#include "pair_loop.h"' in text[f] and '"pose_math.h"' not in text[f], f
+        assert not re.search(r"__shfl_xor\(v\[|\bm3_\w+\(|\bse3_(mul|inv_mul|mul_inv)\(", text[f]), f
+    assert "#pragma clang fp contract(off)" in text["pair_loop.h"]
 
 
 def _refused(lib, rc, needle):

@@ -51,7 +51,7 @@ def _device_rows(args, pairs):
             e1.record()
             e1.synchronize()
             ms.append(e0.elapsed_time(e1))
-        a, b = r["_clouds"]
+        a, b = r["_clouds"][:2]                     # (source, target, normals or None) since the point-to-plane estimator
         rows.append({"pairs": P, "raw_points_per_cloud": int(len(sel[0][0])), "max_iteration": args.max_iteration,
                      "downsampled_source_points": int(a["offsets"][-1]) // P, "downsampled_target_points": int(b["offsets"][-1]) // P,
                      "ms_per_call": {"median": float(np.median(ms)), "min": float(np.min(ms)), "max": float(np.max(ms)), "calls": len(ms)},
