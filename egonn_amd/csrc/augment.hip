@@ -421,17 +421,21 @@ __global__ __launch_bounds__(AUG_TILE) void aug_apply_kernel(const float* pts, c
   if (flags) flags[row] = (uint8_t)((removed ? 1 : 0) | (erased ? 2 : 0));
 }
 
-struct AugLayout {
-  size_t scans, set, partial, total;
+// the carves of the caller's scratch.  With scratch = nullptr only `total` means anything
+struct AugSpan {
+  AugScan* scans;
+  AugSet* set;
+  float* partial;
+  size_t total;
 };
-static AugLayout aug_layout(int B) {
-  AugLayout L;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  L.scans = 0;
-  L.set = up((size_t)B * sizeof(AugScan));
-  L.partial = L.set + 256;
-  L.total = L.partial + up((size_t)B * AUG_CHUNKS * 6 * sizeof(float));
-  return L;
+static AugSpan aug_span(void* scratch, int B) {
+  AugSpan S;
+  Carve c(scratch);
+  S.scans = c.take<AugScan>((size_t)B);
+  S.set = c.take<AugSet>(1);
+  S.partial = c.take<float>((size_t)B * AUG_CHUNKS * 6);
+  S.total = c.total();
+  return S;
 }
 
 }  // namespace egonn
@@ -440,7 +444,7 @@ using namespace egonn;
 
 API int64_t egonn_augment_scratch_bytes(int64_t n, int batch_size) {
   if (n < 0 || n >= (1ll << 24) || batch_size < 1 || batch_size > EGONN_MAX_BATCH) return -1;
-  return (int64_t)aug_layout(batch_size).total;
+  return (int64_t)aug_span(nullptr, batch_size).total;
 }
 
 API int egonn_augment_points(const float* points, int64_t n, const int64_t* scan_offsets, int batch_size, const int32_t* scan_ids,
@@ -474,14 +478,12 @@ API int egonn_augment_points(const float* points, int64_t n, const int64_t* scan
                 EGONN_ERR_INVALID, "augment: flip thresholds (%g, %g, %g)", c.flip_cum[0], c.flip_cum[1], c.flip_cum[2]);
   EGONN_REQUIRE(!on(EGONN_AUG_RIGID) || (c.rot_max >= 0.0 && c.rot_max < 1e6 && c.trans_max >= 0.0 && c.trans_max < 1e18),
                 EGONN_ERR_INVALID, "augment: rot_max %g, trans_max %g", c.rot_max, c.trans_max);
-  const AugLayout L = aug_layout(batch_size);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "augment: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  const AugSpan S = aug_span(scratch, batch_size);
+  EGONN_TRY(span_check("augment", scratch, scratch_bytes, S.total));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  AugScan* scans = (AugScan*)(base + L.scans);
-  AugSet* set = (AugSet*)(base + L.set);
-  float* partial = (float*)(base + L.partial);
+  AugScan* scans = S.scans;
+  AugSet* set = S.set;
+  float* partial = S.partial;
   hipLaunchKernelGGL(aug_select_kernel, dim3((unsigned)batch_size), dim3(AUG_SEL_WG), 0, st, scan_offsets, batch_size, n, scan_ids, c,
                      scans);
   if (c.stages & EGONN_AUG_BLOCK)

@@ -126,6 +126,37 @@ struct Arena {
   }
 };
 
+// ------------------------------------------------------------------ caller-owned scratch spans
+// The carves of a span that a caller hands to an entry point, in order, each aligned to 256 bytes.  Every file states its span
+// once, as a function from the shape and a nullable span to a struct of typed pointers plus total(): with a null span the
+// pointers mean nothing and only the total does (the *_scratch_bytes query).
+struct Carve {
+  explicit Carve(void* span = nullptr) : base((uintptr_t)span) {}
+  template <typename T>
+  T* take(size_t count) {
+    const size_t at = o;
+    o = align_up(o + count * sizeof(T), 256);
+    return reinterpret_cast<T*>(base + at);
+  }
+  // the radix sort's arena inside this span: radix_sort_scratch_bytes(n) (or the segmented variant) + 512, because the sort
+  // carves two arrays and Arena::alloc aligns each to 256
+  Arena sort_arena(size_t sort_scratch_bytes) {
+    const size_t bytes = align_up(sort_scratch_bytes + 512, 256);
+    return Arena::view(take<char>(bytes), bytes);
+  }
+  size_t total() const { return o; }
+
+ private:
+  uintptr_t base;
+  size_t o = 0;
+};
+// what every such entry point asks of the span it was handed
+static inline int span_check(const char* who, const void* scratch, int64_t scratch_bytes, size_t need) {
+  EGONN_REQUIRE(scratch && scratch_bytes >= (int64_t)need && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
+                "%s: scratch needs %lld bytes, 256-byte aligned", who, (long long)need);
+  return EGONN_OK;
+}
+
 // ------------------------------------------------------------------ Morton helpers (host + device)
 __host__ __device__ static inline uint64_t part1by2(uint32_t v) {   // 16 bits -> every 3rd bit
   uint64_t x = v & 0xFFFFull;

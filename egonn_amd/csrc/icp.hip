@@ -40,6 +40,7 @@
 // (icp_plane_step).  The point-to-point instantiation is the code above, operation for operation.
 #include "../../include/egonn_hip.h"
 #include "common.h"
+#include "compact.h"
 #include "horn.h"
 #include "jacobi3.h"
 #include "pair_loop.h"
@@ -157,46 +158,19 @@ __device__ static inline bool ds_is_head(const uint64_t* __restrict__ keys, cons
 __global__ __launch_bounds__(ICP_WG) void ds_count_kernel(const uint64_t* __restrict__ keys, const int64_t* __restrict__ off, int C,
                                                           int64_t n, const int32_t* __restrict__ status,
                                                           int32_t* __restrict__ blockcnt) {
-  __shared__ int s_w[4];
-  const int t = threadIdx.x;
   int c;
-  const bool head = ds_is_head(keys, off, C, n, status, (int64_t)blockIdx.x * ICP_WG + t, &c);
-  const unsigned long long bal = __ballot(head);
-  if ((t & 63) == 0) s_w[t >> 6] = __popcll(bal);
-  __syncthreads();
-  if (t == 0) blockcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  const int heads = wg_count<ICP_WG>(ds_is_head(keys, off, C, n, status, (int64_t)blockIdx.x * ICP_WG + threadIdx.x, &c));
+  if (threadIdx.x == 0) blockcnt[blockIdx.x] = heads;
 }
 
 // one workgroup: exclusive scan of the block counts (in place), then the output offsets of the clouds
 __global__ __launch_bounds__(ICP_WG) void ds_scan_kernel(const uint64_t* __restrict__ keys, const int64_t* __restrict__ off, int C,
                                                          int64_t n, const int32_t* __restrict__ status, int32_t* __restrict__ blockcnt,
                                                          int nb, int64_t* __restrict__ out_off) {
-  __shared__ int s_sum[ICP_WG];
-  const int t = threadIdx.x;
-  const int per = (nb + ICP_WG - 1) / ICP_WG;
-  const int b0 = min(t * per, nb), b1 = min(b0 + per, nb);
-  int s = 0;
-  for (int b = b0; b < b1; ++b) s += blockcnt[b];
-  s_sum[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int acc = 0;
-    for (int k = 0; k < ICP_WG; ++k) {
-      const int v = s_sum[k];
-      s_sum[k] = acc;
-      acc += v;
-    }
-  }
-  __syncthreads();
-  int acc = s_sum[t];
-  for (int b = b0; b < b1; ++b) {
-    const int v = blockcnt[b];
-    blockcnt[b] = acc;
-    acc += v;
-  }
+  wg_scan<ICP_WG>(blockcnt, nb);
   __threadfence_block();
   __syncthreads();
-  for (int c = t; c <= C; c += ICP_WG) {
+  for (int c = threadIdx.x; c <= C; c += ICP_WG) {
     const int64_t pos = clipi(off[c], n);
     const int64_t b = pos / ICP_WG;
     int64_t cnt = 0;
@@ -218,18 +192,12 @@ __global__ __launch_bounds__(ICP_WG) void ds_write_kernel(const float* __restric
                                                           int64_t n, const int32_t* __restrict__ status,
                                                           const int32_t* __restrict__ blockpre, double* __restrict__ out_pts,
                                                           int32_t* __restrict__ out_cnt) {
-  __shared__ int s_w[4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int64_t i = (int64_t)blockIdx.x * ICP_WG + t;
+  const int64_t i = (int64_t)blockIdx.x * ICP_WG + threadIdx.x;
   int c = -1;
   const bool head = ds_is_head(keys, off, C, n, status, i, &c);
-  const unsigned long long bal = __ballot(head);
-  if (lane == 0) s_w[w] = __popcll(bal);
-  __syncthreads();
+  const int64_t o = (int64_t)blockpre[blockIdx.x] + wg_rank<ICP_WG>(__ballot(head));
   if (!head) return;
-  int64_t o = blockpre[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-  for (int k = 0; k < w; ++k) o += s_w[k];
-  if (o >= n) return;                         // cannot happen (heads <= points); keeps the store in bounds regardless
+  if (o >= n) return;                        // cannot happen (heads <= points); keeps the store in bounds regardless
   const int64_t hi = clipi(off[c + 1], n);
   const uint64_t key = keys[i];
   double sx = 0.0, sy = 0.0, sz = 0.0;
@@ -249,22 +217,26 @@ __global__ __launch_bounds__(ICP_WG) void ds_write_kernel(const float* __restric
   if (out_cnt) out_cnt[o] = cnt;
 }
 
-struct DsLayout {
-  size_t keys0, keys1, vals0, vals1, mins, blockcnt, sort, sort_bytes, total;
+// the downsample's carves of the caller's scratch.  With scratch = nullptr only `total` means anything
+struct DsSpan {
+  uint64_t* keys[2];        // ping-pong buffers of the sort
+  uint32_t* vals[2];
+  double* mins;
+  int32_t* blockcnt;
+  Arena sort_ws;
+  size_t total;
 };
-static DsLayout ds_layout(int64_t n, int C) {
-  DsLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+static DsSpan ds_span(void* scratch, int64_t n, int C) {
+  DsSpan S;
+  Carve c(scratch);
   const size_t m = (size_t)(n > 0 ? n : 1);
-  L.keys0 = take(m * 8), L.keys1 = take(m * 8), L.vals0 = take(m * 4), L.vals1 = take(m * 4);
-  L.mins = take((size_t)C * 3 * 8);
-  L.blockcnt = take((size_t)(cdiv((int64_t)m, ICP_WG) + 1) * 4);
-  // + 512: the sort carves two arrays out of this span and Arena::alloc aligns each carve to 256
-  L.sort_bytes = align_up(radix_sort_segments_scratch_bytes((int64_t)m, C) + 512, 256);
-  L.sort = take(L.sort_bytes);
-  L.total = o;
-  return L;
+  for (int k = 0; k < 2; ++k) S.keys[k] = c.take<uint64_t>(m);
+  for (int k = 0; k < 2; ++k) S.vals[k] = c.take<uint32_t>(m);
+  S.mins = c.take<double>((size_t)C * 3);
+  S.blockcnt = c.take<int32_t>((size_t)cdiv((int64_t)m, ICP_WG) + 1);
+  S.sort_ws = c.sort_arena(radix_sort_segments_scratch_bytes((int64_t)m, C));
+  S.total = c.total();
+  return S;
 }
 
 // ------------------------------------------------------------------ ICP
@@ -809,21 +781,17 @@ struct IcpGrid {
 };
 static IcpGrid icp_grid(void* scratch, int64_t ns, int64_t nt, int P, int n_part) {
   IcpGrid G;
-  Carve c;
+  Carve c(scratch);
   const size_t a = (size_t)(ns > 0 ? ns : 1), b = (size_t)(nt > 0 ? nt : 1), m = a > b ? a : b;
-  auto at = [&](size_t off) { return (void*)((uintptr_t)scratch + off); };
-  auto take = [&](size_t bytes) { return at(c.take(bytes)); };
   const PairLayout L = pair_layout(c, (int64_t)a, P, sizeof(IcpPair));
-  G.n_wg = L.n_wg, G.pairs = (IcpPair*)at(L.pairs), G.wg0 = (int32_t*)at(L.wg0);
-  for (int k = 0; k < 2; ++k) G.keys[k] = (uint64_t*)take(m * 8);
-  for (int k = 0; k < 2; ++k) G.vals[k] = (uint32_t*)take(m * 4);
-  G.tq = (double*)take(b * 24), G.tj = (int32_t*)take(b * 4), G.tkey = (uint64_t*)take(b * 8);
-  G.sq = (double*)take(a * 24), G.si = (int32_t*)take(a * 4);
-  G.partial = (double*)take((size_t)L.n_wg * n_part * 8);
-  // + 512: the sort carves two arrays out of this span and Arena::alloc aligns each carve to 256
-  const size_t sort_bytes = align_up(radix_sort_segments_scratch_bytes((int64_t)m, P) + 512, 256);
-  G.sort_ws = Arena::view(take(sort_bytes), sort_bytes);
-  G.total = c.o;
+  G.n_wg = L.n_wg, G.pairs = (IcpPair*)L.pairs, G.wg0 = L.wg0;
+  for (int k = 0; k < 2; ++k) G.keys[k] = c.take<uint64_t>(m);
+  for (int k = 0; k < 2; ++k) G.vals[k] = c.take<uint32_t>(m);
+  G.tq = c.take<double>(b * 3), G.tj = c.take<int32_t>(b), G.tkey = c.take<uint64_t>(b);
+  G.sq = c.take<double>(a * 3), G.si = c.take<int32_t>(a);
+  G.partial = c.take<double>((size_t)L.n_wg * n_part);
+  G.sort_ws = c.sort_arena(radix_sort_segments_scratch_bytes((int64_t)m, P));
+  G.total = c.total();
   return G;
 }
 
@@ -837,7 +805,7 @@ using namespace egonn;
 
 API int64_t egonn_voxel_downsample_scratch_bytes(int64_t n, int n_clouds) {
   if (n < 0 || n >= (1ll << 31) || n_clouds < 1 || n_clouds > EGONN_MAX_BATCH) return -1;
-  return (int64_t)ds_layout(n, n_clouds).total;
+  return (int64_t)ds_span(nullptr, n, n_clouds).total;
 }
 
 API int egonn_voxel_downsample(const float* points, int64_t n, const int64_t* offsets, int n_clouds, double voxel_size,
@@ -848,32 +816,26 @@ API int egonn_voxel_downsample(const float* points, int64_t n, const int64_t* of
   EGONN_REQUIRE(voxel_size > 0.0 && voxel_size < 1e18, EGONN_ERR_INVALID, "voxel_downsample: bad voxel_size");
   EGONN_REQUIRE(offsets && out_offsets && status && scratch && (n == 0 || (points && out_points)), EGONN_ERR_INVALID,
                 "voxel_downsample: null pointer");
-  const DsLayout L = ds_layout(n, n_clouds);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "voxel_downsample: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  DsSpan S = ds_span(scratch, n, n_clouds);
+  EGONN_TRY(span_check("voxel_downsample", scratch, scratch_bytes, S.total));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
   DsCrop cr;
   for (int k = 0; k < 6; ++k) cr.b[k] = crop ? (double)crop[k] : (double)NAN;
-  double* mins = (double*)(base + L.mins);
-  int32_t* blockcnt = (int32_t*)(base + L.blockcnt);
-  hipLaunchKernelGGL(ds_min_kernel, dim3((unsigned)n_clouds), dim3(ICP_WG), 0, st, points, n, offsets, n_clouds, cr, voxel_size, mins,
+  hipLaunchKernelGGL(ds_min_kernel, dim3((unsigned)n_clouds), dim3(ICP_WG), 0, st, points, n, offsets, n_clouds, cr, voxel_size, S.mins,
                      status);
   const int nb = (int)cdiv(n, ICP_WG);
-  uint64_t* keys = (uint64_t*)(base + L.keys0);
-  uint32_t* vals = (uint32_t*)(base + L.vals0);
+  uint64_t* keys = S.keys[0];
+  uint32_t* vals = S.vals[0];
   if (n > 0) {
-    hipLaunchKernelGGL(ds_key_kernel, dim3((unsigned)nb), dim3(ICP_WG), 0, st, points, n, offsets, n_clouds, cr, voxel_size, mins, keys,
+    hipLaunchKernelGGL(ds_key_kernel, dim3((unsigned)nb), dim3(ICP_WG), 0, st, points, n, offsets, n_clouds, cr, voxel_size, S.mins, keys,
                        vals, status);
-    Arena sort_ws = Arena::view(base + L.sort, L.sort_bytes);
-    EGONN_TRY(radix_sort_segments(sort_ws, keys, vals, (uint64_t*)(base + L.keys1), (uint32_t*)(base + L.vals1), n, offsets, n_clouds,
-                                  64, st, &keys, &vals));
-    hipLaunchKernelGGL(ds_count_kernel, dim3((unsigned)nb), dim3(ICP_WG), 0, st, keys, offsets, n_clouds, n, status, blockcnt);
+    EGONN_TRY(radix_sort_segments(S.sort_ws, keys, vals, S.keys[1], S.vals[1], n, offsets, n_clouds, 64, st, &keys, &vals));
+    hipLaunchKernelGGL(ds_count_kernel, dim3((unsigned)nb), dim3(ICP_WG), 0, st, keys, offsets, n_clouds, n, status, S.blockcnt);
   }
-  hipLaunchKernelGGL(ds_scan_kernel, dim3(1), dim3(ICP_WG), 0, st, keys, offsets, n_clouds, n, status, blockcnt, nb, out_offsets);
+  hipLaunchKernelGGL(ds_scan_kernel, dim3(1), dim3(ICP_WG), 0, st, keys, offsets, n_clouds, n, status, S.blockcnt, nb, out_offsets);
   if (n > 0)
     hipLaunchKernelGGL(ds_write_kernel, dim3((unsigned)nb), dim3(ICP_WG), 0, st, points, keys, vals, offsets, n_clouds, n, status,
-                       blockcnt, out_points, out_counts);
+                       S.blockcnt, out_points, out_counts);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
@@ -917,8 +879,7 @@ static int icp_run(int estimator, const char* who, const double* src, int64_t n_
                 EGONN_ERR_INVALID, "%s: null pointer", who);
   EGONN_REQUIRE(!estimator || n_tgt == 0 || tgt_normals, EGONN_ERR_INVALID, "%s: null tgt_normals", who);
   const IcpGrid G = icp_grid(scratch, n_src, n_tgt, n_pairs, estimator ? ICP_NPART_PLANE : ICP_NPART);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)G.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "%s: scratch needs %lld bytes, 256-byte aligned", who, (long long)G.total);
+  EGONN_TRY(span_check(who, scratch, scratch_bytes, G.total));
   hipStream_t st = (hipStream_t)stream;
   EGONN_TRY(pair_clear_traces(T_trace, eval_trace, 3, n_pairs, max_iteration, st));
   if (corr && n_src > 0) HIP_CHECK(hipMemsetAsync(corr, 0xFF, (size_t)n_src * sizeof(int32_t), st));
@@ -989,8 +950,7 @@ API int egonn_estimate_normals(const double* points, int64_t n, const int64_t* o
                 NRM_KNN_MIN, NRM_KNN_MAX);
   EGONN_REQUIRE(offsets && status && scratch && (n == 0 || (points && normals)), EGONN_ERR_INVALID, "estimate_normals: null pointer");
   const IcpGrid G = icp_grid(scratch, n, n, n_clouds, 0);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)G.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "estimate_normals: scratch needs %lld bytes, 256-byte aligned", (long long)G.total);
+  EGONN_TRY(span_check("estimate_normals", scratch, scratch_bytes, G.total));
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(nrm_status_kernel, dim3((unsigned)n_clouds), dim3(ICP_WG), 0, st, points, n, offsets, knn, status);
   HIP_CHECK(hipGetLastError());

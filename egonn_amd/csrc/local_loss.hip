@@ -511,34 +511,34 @@ __global__ __launch_bounds__(256) void ll_point_grad_kernel(LLArgs a, float* __r
   }
 }
 
-// scratch layout: every array 256-byte aligned, in this order
-struct LLScratch {
-  size_t kp1t, ckey1, ckey2, ndx1, md1, tgt, lse, rowloss, amax, negmax, ndx2, md2, iscls, pairK, total;
+// the carves of the caller's scratch, in this order.  With scratch = nullptr only `total` means anything
+struct LLSpan {
+  float* kp1t;
+  unsigned long long *ckey1, *ckey2;
+  int32_t *ndx1, *tgt, *amax, *ndx2, *iscls;
+  float *md1, *lse, *rowloss, *negmax, *md2, *pairK;
+  size_t total;
 };
-LLScratch ll_layout(int pairs, int64_t n1, int64_t n2) {
-  LLScratch L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
-  L.kp1t = take(n1 * 3 * sizeof(float));
-  L.ckey1 = take(n1 * sizeof(unsigned long long));
-  L.ckey2 = take(n2 * sizeof(unsigned long long));
-  L.ndx1 = take(n1 * 4); L.md1 = take(n1 * 4); L.tgt = take(n1 * 4); L.lse = take(n1 * 4);
-  L.rowloss = take(n1 * 4); L.amax = take(n1 * 4); L.negmax = take(n1 * 4);
-  L.ndx2 = take(n2 * 4); L.md2 = take(n2 * 4); L.iscls = take(n2 * 4);
-  L.pairK = take((size_t)pairs * 4);
-  L.total = o;
-  return L;
+LLSpan ll_span(void* scratch, int pairs, int64_t n_kp1, int64_t n_kp2) {
+  LLSpan S;
+  Carve c(scratch);
+  const size_t n1 = (size_t)(n_kp1 < 0 ? 0 : n_kp1), n2 = (size_t)(n_kp2 < 0 ? 0 : n_kp2);
+  S.kp1t = c.take<float>(n1 * 3);
+  S.ckey1 = c.take<unsigned long long>(n1);
+  S.ckey2 = c.take<unsigned long long>(n2);
+  S.ndx1 = c.take<int32_t>(n1), S.md1 = c.take<float>(n1), S.tgt = c.take<int32_t>(n1), S.lse = c.take<float>(n1);
+  S.rowloss = c.take<float>(n1), S.amax = c.take<int32_t>(n1), S.negmax = c.take<float>(n1);
+  S.ndx2 = c.take<int32_t>(n2), S.md2 = c.take<float>(n2), S.iscls = c.take<int32_t>(n2);
+  S.pairK = c.take<float>((size_t)(pairs < 1 ? 1 : pairs));
+  S.total = c.total();
+  return S;
 }
 
 }  // namespace
 
-static size_t ll_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2) {
-  return ll_layout(pairs < 1 ? 1 : pairs, n_kp1 < 0 ? 0 : n_kp1, n_kp2 < 0 ? 0 : n_kp2).total;
-}
-
 API int64_t egonn_local_loss_scratch_bytes(int pairs, int64_t n_kp1, int64_t n_kp2, int dim) {
   (void)dim;
-  return (int64_t)ll_scratch_bytes(pairs, n_kp1, n_kp2);
+  return (int64_t)ll_span(nullptr, pairs, n_kp1, n_kp2).total;
 }
 
 // clouds (M,3), keypoints (N,3) (N) (N,128) and their offsets (pairs+1) on the device, transforms (pairs,16); params on the HOST:
@@ -568,57 +568,42 @@ API int egonn_local_loss(int pairs, int64_t n_cloud1, int64_t n_cloud2, int64_t 
   EGONN_REQUIRE((((uintptr_t)desc1 | (uintptr_t)desc2 | (uintptr_t)g_desc1 | (uintptr_t)g_desc2) & 15) == 0 &&
                     ((uintptr_t)scratch & 255) == 0,
                 EGONN_ERR_INVALID, "local_loss: descriptors must be 16-byte aligned, scratch 256-byte aligned");
-  const int64_t need = (int64_t)ll_scratch_bytes(pairs, n_kp1, n_kp2);
+  const LLSpan S = ll_span(scratch, pairs, n_kp1, n_kp2);
+  const int64_t need = (int64_t)S.total;
   EGONN_REQUIRE(scratch_bytes >= need, EGONN_ERR_INVALID, "local_loss: scratch of %lld bytes, %lld needed",
                 (long long)scratch_bytes, (long long)need);
   hipStream_t st = (hipStream_t)stream;
   const int32_t N1 = (int32_t)n_kp1, N2 = (int32_t)n_kp2;
-  const LLScratch L = ll_layout(pairs, N1, N2);
-  char* sc = (char*)scratch;
-  float* kp1t = (float*)(sc + L.kp1t);
-  auto* ckey1 = (unsigned long long*)(sc + L.ckey1);
-  auto* ckey2 = (unsigned long long*)(sc + L.ckey2);
-  int32_t* ndx1 = (int32_t*)(sc + L.ndx1);
-  float* md1 = (float*)(sc + L.md1);
-  int32_t* tgt = (int32_t*)(sc + L.tgt);
-  float* lse = (float*)(sc + L.lse);
-  float* rowloss = (float*)(sc + L.rowloss);
-  int32_t* amax = (int32_t*)(sc + L.amax);
-  float* negmax = (float*)(sc + L.negmax);
-  int32_t* ndx2 = (int32_t*)(sc + L.ndx2);
-  float* md2 = (float*)(sc + L.md2);
-  int32_t* iscls = (int32_t*)(sc + L.iscls);
-  float* pairK = (float*)(sc + L.pairK);
   const float gamma_chamfer = params[0], gamma_p2p = params[1], gamma_c = params[2], gamma_k = params[3];
   const float scale = expf(params[4]), dist_th = params[5];
 
   const unsigned flat = (unsigned)cdiv((int64_t)N1 + N2, 256);
-  hipLaunchKernelGGL(ll_prepare_kernel, dim3(flat), dim3(256), 0, st, pairs, kp1, kp_off1, N1, N2, transforms, kp1t,
-                     ckey1, ckey2, iscls);
-  hipLaunchKernelGGL(ll_kp_search_kernel, dim3(flat), dim3(256), 0, st, pairs, kp1t, kp_off1, kp2, kp_off2, N1, N2,
-                     dist_th, ndx1, md1, tgt, ndx2, md2, iscls);
+  hipLaunchKernelGGL(ll_prepare_kernel, dim3(flat), dim3(256), 0, st, pairs, kp1, kp_off1, N1, N2, transforms, S.kp1t,
+                     S.ckey1, S.ckey2, S.iscls);
+  hipLaunchKernelGGL(ll_kp_search_kernel, dim3(flat), dim3(256), 0, st, pairs, S.kp1t, kp_off1, kp2, kp_off2, N1, N2,
+                     dist_th, S.ndx1, S.md1, S.tgt, S.ndx2, S.md2, S.iscls);
   // chunks of a side <= total / chunk + one partial chunk per pair
   const int64_t chunks = cdiv(n_cloud1 > n_cloud2 ? n_cloud1 : n_cloud2, LL_CLOUD_CHUNK) + pairs;
   hipLaunchKernelGGL(ll_cloud_search_kernel, dim3((unsigned)chunks, LL_KP_SPLIT, 2), dim3(256), 0, st, pairs, clouds1,
-                     cloud_off1, clouds2, cloud_off2, kp1, kp_off1, kp2, kp_off2, ckey1, ckey2);
+                     cloud_off1, clouds2, cloud_off2, kp1, kp_off1, kp2, kp_off2, S.ckey1, S.ckey2);
   const unsigned tiles1 = (unsigned)(cdiv(N1, LL_OWN) + pairs), tiles2 = (unsigned)(cdiv(N2, LL_OWN) + pairs);
-  hipLaunchKernelGGL(ll_corr_kernel<0>, dim3(tiles1), dim3(256), 0, st, pairs, desc1, desc2, kp_off1, kp_off2, tgt,
-                     iscls, scale, 0.f, lse, rowloss, amax, negmax, (const float*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL(ll_corr_kernel<0>, dim3(tiles1), dim3(256), 0, st, pairs, desc1, desc2, kp_off1, kp_off2, S.tgt,
+                     S.iscls, scale, 0.f, S.lse, S.rowloss, S.amax, S.negmax, (const float*)nullptr, (float*)nullptr);
   LLArgs a;
   a.pairs = pairs; a.N1 = N1; a.N2 = N2; a.M1 = (int32_t)n_cloud1; a.M2 = (int32_t)n_cloud2;
   a.c1 = clouds1; a.c2 = clouds2; a.kp1 = kp1; a.kp2 = kp2; a.s1 = sigma1; a.s2 = sigma2; a.T = transforms;
   a.coff1 = cloud_off1; a.coff2 = cloud_off2; a.off1 = kp_off1; a.off2 = kp_off2;
-  a.kp1t = kp1t; a.ndx1 = ndx1; a.ndx2 = ndx2; a.tgt = tgt; a.amax = amax;
-  a.md1 = md1; a.md2 = md2; a.rowloss = rowloss; a.negmax = negmax; a.ckey1 = ckey1; a.ckey2 = ckey2;
+  a.kp1t = S.kp1t; a.ndx1 = S.ndx1; a.ndx2 = S.ndx2; a.tgt = S.tgt; a.amax = S.amax;
+  a.md1 = S.md1; a.md2 = S.md2; a.rowloss = S.rowloss; a.negmax = S.negmax; a.ckey1 = S.ckey1; a.ckey2 = S.ckey2;
   a.gamma_chamfer = gamma_chamfer; a.gamma_p2p = gamma_p2p; a.gamma_c = gamma_c; a.gamma_k = gamma_k; a.dist_th = dist_th;
-  hipLaunchKernelGGL(ll_finish_kernel, dim3(pairs), dim3(256), 0, st, a, out_pair, pairK);
+  hipLaunchKernelGGL(ll_finish_kernel, dim3(pairs), dim3(256), 0, st, a, out_pair, S.pairK);
   hipLaunchKernelGGL(ll_batch_mean_kernel, dim3(1), dim3(64), 0, st, pairs, (const float*)out_pair, out_batch);
   if (g_kp1) {
     const float coef = gamma_c * scale / (float)pairs;
-    hipLaunchKernelGGL(ll_corr_kernel<1>, dim3(tiles1), dim3(256), 0, st, pairs, desc1, desc2, kp_off1, kp_off2, tgt,
-                       iscls, scale, coef, lse, rowloss, amax, negmax, (const float*)pairK, g_desc1);
-    hipLaunchKernelGGL(ll_corr_kernel<2>, dim3(tiles2), dim3(256), 0, st, pairs, desc1, desc2, kp_off1, kp_off2, tgt,
-                       iscls, scale, coef, lse, rowloss, amax, negmax, (const float*)pairK, g_desc2);
+    hipLaunchKernelGGL(ll_corr_kernel<1>, dim3(tiles1), dim3(256), 0, st, pairs, desc1, desc2, kp_off1, kp_off2, S.tgt,
+                       S.iscls, scale, coef, S.lse, S.rowloss, S.amax, S.negmax, (const float*)S.pairK, g_desc1);
+    hipLaunchKernelGGL(ll_corr_kernel<2>, dim3(tiles2), dim3(256), 0, st, pairs, desc1, desc2, kp_off1, kp_off2, S.tgt,
+                       S.iscls, scale, coef, S.lse, S.rowloss, S.amax, S.negmax, (const float*)S.pairK, g_desc2);
     hipLaunchKernelGGL(ll_point_grad_kernel, dim3(flat), dim3(256), 0, st, a, g_kp1, g_sigma1, g_kp2, g_sigma2);
   }
   HIP_CHECK(hipGetLastError());

@@ -401,29 +401,29 @@ __global__ __launch_bounds__(LC_BLOCK) void pr_emit_kernel(const uint64_t* __res
   }
 }
 
-// the carves of the scratch span, every one 256-byte aligned
-struct PrLayout {
-  size_t keys0, keys1, vals0, vals1, sums, sort, sort_bytes, total;
+// the carves of the PR curve's scratch span.  With scratch = nullptr only `total` means anything
+struct PrSpan {
+  uint64_t* keys[2];        // ping-pong buffers of the sort
+  uint32_t* vals[2];
+  int32_t* sums;
+  Arena sort_ws;
+  size_t total;
 };
-static PrLayout pr_layout(int64_t n) {
-  PrLayout L;
+static PrSpan pr_span(void* scratch, int64_t n) {
+  PrSpan S;
+  Carve c(scratch);
   const size_t nn = (size_t)(n > 0 ? n : 1), tiles = (size_t)cdiv((int64_t)nn, PR_TILE);
-  size_t o = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  L.keys0 = carve(nn * 8), L.keys1 = carve(nn * 8), L.vals0 = carve(nn * 4), L.vals1 = carve(nn * 4), L.sums = carve(3 * tiles * 4);
-  L.sort_bytes = align_up(radix_sort_scratch_bytes(n) + 512, 256);        // + 512: the sort carves two arrays, each aligned to 256
-  L.sort = carve(L.sort_bytes);
-  L.total = o;
-  return L;
+  for (int k = 0; k < 2; ++k) S.keys[k] = c.take<uint64_t>(nn);
+  for (int k = 0; k < 2; ++k) S.vals[k] = c.take<uint32_t>(nn);
+  S.sums = c.take<int32_t>(3 * tiles);
+  S.sort_ws = c.sort_arena(radix_sort_scratch_bytes(n));
+  S.total = c.total();
+  return S;
 }
 
 API int64_t egonn_pr_curve_scratch_bytes(int64_t n) {
   if (n < 0 || n >= (1ll << 31)) return -1;
-  return (int64_t)pr_layout(n).total;
+  return (int64_t)pr_span(nullptr, n).total;
 }
 
 API int egonn_pr_curve(const float* score, const int32_t* correct, const int32_t* revisit, int64_t n, int32_t* order, int32_t* cum_tp,
@@ -432,22 +432,19 @@ API int egonn_pr_curve(const float* score, const int32_t* correct, const int32_t
   EGONN_REQUIRE(n >= 0 && n < (1ll << 31), EGONN_ERR_INVALID, "pr_curve: n=%lld outside [0, 2^31)", (long long)n);
   EGONN_REQUIRE(totals && (n == 0 || (score && correct && revisit && order && cum_tp && cum_fp && cum_rev && group_end)),
                 EGONN_ERR_INVALID, "pr_curve: null pointer");
-  const PrLayout L = pr_layout(n);
-  EGONN_REQUIRE(n == 0 || (scratch && scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0), EGONN_ERR_INVALID,
-                "pr_curve: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  PrSpan S = pr_span(scratch, n);
+  if (n > 0) EGONN_TRY(span_check("pr_curve", scratch, scratch_bytes, S.total));      // no row: no scratch, null is fine
   hipStream_t st = (hipStream_t)stream;
   HIP_CHECK(hipMemsetAsync(totals, 0, 2 * sizeof(int32_t), st));
   if (n == 0) return EGONN_OK;
-  char* base = (char*)scratch;
-  uint64_t *keys0 = (uint64_t*)(base + L.keys0), *keys1 = (uint64_t*)(base + L.keys1);
-  uint32_t *vals0 = (uint32_t*)(base + L.vals0), *vals1 = (uint32_t*)(base + L.vals1);
-  int32_t* sums = (int32_t*)(base + L.sums);
+  uint64_t *keys0 = S.keys[0], *keys1 = S.keys[1];
+  uint32_t *vals0 = S.vals[0], *vals1 = S.vals[1];
+  int32_t* sums = S.sums;
   const int32_t nn = (int32_t)n, tiles = (int32_t)cdiv(n, PR_TILE);
   hipLaunchKernelGGL(pr_key_kernel, dim3((unsigned)cdiv(n, LC_BLOCK)), dim3(LC_BLOCK), 0, st, score, revisit, nn, keys0, vals0, totals);
-  Arena ws = Arena::view(base + L.sort, L.sort_bytes);
   uint64_t* kres = keys1;
   uint32_t* vres = vals1;
-  EGONN_TRY(radix_sort_pairs(ws, keys0, vals0, keys1, vals1, n, 32, st, nullptr, &kres, &vres));
+  EGONN_TRY(radix_sort_pairs(S.sort_ws, keys0, vals0, keys1, vals1, n, 32, st, nullptr, &kres, &vres));
   hipLaunchKernelGGL(pr_tile_sums_kernel, dim3((unsigned)tiles), dim3(LC_BLOCK), 0, st, kres, vres, correct, revisit, nn, tiles, sums);
   hipLaunchKernelGGL(pr_scan_sums_kernel, dim3(1), dim3(LC_BLOCK), 0, st, tiles, sums);
   hipLaunchKernelGGL(pr_emit_kernel, dim3((unsigned)tiles), dim3(LC_BLOCK), 0, st, kres, vres, correct, revisit, nn, tiles, sums, order,

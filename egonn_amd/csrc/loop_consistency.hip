@@ -232,25 +232,28 @@ __global__ __launch_bounds__(LC_WG) void lc_pairs_kernel(const double* __restric
 }
 
 // ------------------------------------------------------------------ the scratch span
-struct LcLayout {
-  size_t keys0, keys1, vals0, vals1, sort, sort_bytes, rows, alive0, alive1, state, total;
+// With scratch = nullptr only `total` means anything
+struct LcSpan {
+  uint64_t* keys[2];        // ping-pong buffers of the sort
+  uint32_t* vals[2];
+  Arena sort_ws;
+  uint64_t *rows, *alive[2];
+  LcState* state;
+  size_t total;
 };
 static bool lc_partners_ok(int max_partners) { return max_partners >= 64 && max_partners <= LC_MAX_PARTNERS && max_partners % 64 == 0; }
-static LcLayout lc_layout(int64_t E, int max_partners) {
-  LcLayout L;
+static LcSpan lc_span(void* scratch, int64_t E, int max_partners) {
+  LcSpan S;
+  Carve c(scratch);
   const size_t ee = (size_t)(E > 0 ? E : 1), W = (size_t)max_partners / 64 + 1, nwords = (ee + 63) / 64;
-  size_t o = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  L.keys0 = carve(ee * 8), L.keys1 = carve(ee * 8), L.vals0 = carve(ee * 4), L.vals1 = carve(ee * 4);
-  L.sort_bytes = align_up(radix_sort_scratch_bytes((int64_t)ee) + 512, 256);
-  L.sort = carve(L.sort_bytes);
-  L.rows = carve(ee * W * 8), L.alive0 = carve(nwords * 8), L.alive1 = carve(nwords * 8), L.state = carve(sizeof(LcState));
-  L.total = o;
-  return L;
+  for (int k = 0; k < 2; ++k) S.keys[k] = c.take<uint64_t>(ee);
+  for (int k = 0; k < 2; ++k) S.vals[k] = c.take<uint32_t>(ee);
+  S.sort_ws = c.sort_arena(radix_sort_scratch_bytes((int64_t)ee));
+  S.rows = c.take<uint64_t>(ee * W);
+  for (int k = 0; k < 2; ++k) S.alive[k] = c.take<uint64_t>(nwords);
+  S.state = c.take<LcState>(1);
+  S.total = c.total();
+  return S;
 }
 static inline bool lc_thr_ok(double v) { return v >= 0.0 && v < INFINITY; }
 static inline bool lc_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
@@ -258,7 +261,7 @@ static inline unsigned lc_grid(int64_t items) { return (unsigned)cdiv(items > 0 
 
 API int64_t egonn_loop_consistency_scratch_bytes(int64_t E, int max_partners) {
   if (!pose_sizes_ok(1, E) || !lc_partners_ok(max_partners)) return -1;
-  return (int64_t)lc_layout(E, max_partners).total;
+  return (int64_t)lc_span(nullptr, E, max_partners).total;
 }
 
 API int egonn_loop_consistency(const double* poses, int64_t n, const int32_t* edge_index, const double* Z, const double* weights,
@@ -284,23 +287,20 @@ API int egonn_loop_consistency(const double* poses, int64_t n, const int32_t* ed
                 max_rounds, LC_MAX_ROUNDS);
   EGONN_REQUIRE(lc_partners_ok(max_partners), EGONN_ERR_INVALID,
                 "loop_consistency: max_partners=%d is not a positive multiple of 64 (up to %d)", max_partners, LC_MAX_PARTNERS);
-  const LcLayout L = lc_layout(E, max_partners);
-  EGONN_REQUIRE(scratch && scratch_bytes >= (int64_t)L.total && lc_aligned(scratch, 256), EGONN_ERR_INVALID,
-                "loop_consistency: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  LcSpan S = lc_span(scratch, E, max_partners);
+  EGONN_TRY(span_check("loop_consistency", scratch, scratch_bytes, S.total));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  uint64_t *keys0 = (uint64_t*)(base + L.keys0), *keys1 = (uint64_t*)(base + L.keys1), *kres = keys1;
-  uint32_t *vals0 = (uint32_t*)(base + L.vals0), *vals1 = (uint32_t*)(base + L.vals1), *vres = vals1;
-  uint64_t *rows = (uint64_t*)(base + L.rows), *alive[2] = {(uint64_t*)(base + L.alive0), (uint64_t*)(base + L.alive1)};
-  LcState* state = (LcState*)(base + L.state);
+  uint64_t *keys0 = S.keys[0], *keys1 = S.keys[1], *kres = keys1;
+  uint32_t *vals0 = S.vals[0], *vals1 = S.vals[1], *vres = vals1;
+  uint64_t *rows = S.rows, *const* alive = S.alive;
+  LcState* state = S.state;
   const int32_t nn = (int32_t)n, ee = (int32_t)E, H = max_partners / 2, W = max_partners / 64 + 1;
   hipLaunchKernelGGL(lc_validate_kernel, dim3(lc_grid(E)), dim3(LC_WG), 0, st, poses, nn, edge_index, Z, weights, ee, edge_status, keys0,
                      vals0, state, status);
   if (E > 0) {
     int nbits = 1;
     while ((n >> nbits) != 0) ++nbits;                       // keys are 0 .. n
-    Arena ws = Arena::view(base + L.sort, L.sort_bytes);
-    EGONN_TRY(radix_sort_pairs(ws, keys0, vals0, keys1, vals1, E, nbits, st, nullptr, &kres, &vres));
+    EGONN_TRY(radix_sort_pairs(S.sort_ws, keys0, vals0, keys1, vals1, E, nbits, st, nullptr, &kres, &vres));
     hipLaunchKernelGGL(lc_rows_kernel, dim3((unsigned)E), dim3(LC_WG), 0, st, poses, nn, edge_index, Z, ee, kres, vres, (int32_t)window,
                        trans_thr, rot_thr, trans_drift, rot_drift, H, W, rows, alive[0], support0, status);
     for (int r = 0; r < max_rounds; ++r)

@@ -7,8 +7,8 @@
 // gives the bits of one call.  There is no floating-point atomic in this file.
 //
 // accumulate  vm_offsets (voxel_key.h), ndt_accumulate: key, binary search, equal consecutive rows combined inside a wave by a
-//             segmented scan (the bank's clouds are in voxel order: consecutive lanes often share a row); the last lane of a
-//             run issues ten integer atomics.
+//             segmented scan (the bank's clouds are in voxel order: consecutive lanes often share a row; the run bounds are
+//             compact.h's wave_run); the last lane of a run issues ten integer atomics.
 // finalize    one lane per row: mean, covariance, cyclic Jacobi (jacobi3.h), the eigenvalue floor, the information matrix.
 // register    ndt_setup (pairs, the workgroup table), then max_iteration + 1 rounds of ndt_eval (256 consecutive source points
 //             of one pair per workgroup: up to seven lookups per point, 30 partial sums in a fixed tree) and ndt_finish (one
@@ -18,6 +18,7 @@
 //             of a point, the stop rule on the step's size and the step.
 #include "../../include/egonn_hip.h"
 #include "common.h"
+#include "compact.h"
 #include "jacobi3.h"
 #include "pair_loop.h"
 #include "plane_step.h"
@@ -74,9 +75,7 @@ __global__ __launch_bounds__(NDT_WG) void ndt_accumulate_kernel(const double* __
   const bool head = row >= 0 && (lane == 0 || prev != row);
   const unsigned long long bal = __ballot(head);
   if (__ballot(row >= 0) == 0ull) return;                                   // wave-uniform
-  const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);          // lanes <= this one
-  const unsigned long long hb = bal & upto;
-  const int start = hb ? 63 - __clzll((long long)hb) : 0;                   // first lane of this point's run
+  const WaveRun run = wave_run(bal);
   int c = row >= 0 ? 1 : 0;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(NDT_WG) void ndt_accumulate_kernel(const double* __
     long long a[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) a[k] = __shfl_up(v[k], d);
-    if (lane - d >= start) {
+    if (lane - d >= run.start) {
       c += ac;
 #pragma unroll
       for (int k = 0; k < 9; ++k) v[k] += a[k];
@@ -365,6 +364,24 @@ static bool ndt_register_shape_ok(int64_t n_src, int n_pairs) {
 }
 static bool ndt_pos(double x) { return x > 0.0 && x < INFINITY; }          // false for NaN
 
+// The carves of register's scratch (accumulate's is one array: obs_off).  With scratch = nullptr only `total` means anything
+struct NdtSpan {
+  int64_t n_wg;             // workgroups of the flat grid
+  NdtPair* pairs;
+  int32_t* wg0;
+  double* partial;
+  size_t total;
+};
+static NdtSpan ndt_register_span(void* scratch, int64_t n_src, int n_pairs) {
+  NdtSpan S;
+  Carve c(scratch);
+  const PairLayout L = pair_layout(c, n_src, n_pairs, sizeof(NdtPair));
+  S.n_wg = L.n_wg, S.pairs = (NdtPair*)L.pairs, S.wg0 = L.wg0;
+  S.partial = c.take<double>((size_t)L.n_wg * NDT_NPART);
+  S.total = c.total();
+  return S;
+}
+
 }  // namespace egonn
 
 using namespace egonn;
@@ -372,7 +389,9 @@ using namespace egonn;
 // ------------------------------------------------------------------ entry points
 API int64_t egonn_ndt_accumulate_scratch_bytes(int64_t points_capacity, int n_obs) {
   if (!vm_integrate_shape_ok(points_capacity, n_obs)) return -1;
-  return (int64_t)align_up((size_t)(n_obs + 1) * 8, 256);
+  Carve c;
+  c.take<int64_t>((size_t)n_obs + 1);
+  return (int64_t)c.total();
 }
 
 API int egonn_ndt_accumulate(const double* bank, int64_t n_bank, const int64_t* bank_offsets, int64_t n_clouds, const int32_t* pick,
@@ -388,11 +407,10 @@ API int egonn_ndt_accumulate(const double* bank, int64_t n_bank, const int64_t* 
   EGONN_REQUIRE(bank_offsets && pick && poses && n_dev && missed && status && scratch && (n_bank == 0 || bank) &&
                     (capacity_map == 0 || (keys && cnt && s1 && s2)),
                 EGONN_ERR_INVALID, "ndt_accumulate: null pointer");
-  const int64_t need = (int64_t)align_up((size_t)(n_obs + 1) * 8, 256);
-  EGONN_REQUIRE(scratch_bytes >= need && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "ndt_accumulate: scratch needs %lld bytes, 256-byte aligned", (long long)need);
+  Carve c(scratch);
+  int64_t* obs_off = c.take<int64_t>((size_t)n_obs + 1);
+  EGONN_TRY(span_check("ndt_accumulate", scratch, scratch_bytes, c.total()));
   hipStream_t st = (hipStream_t)stream;
-  int64_t* obs_off = (int64_t*)scratch;
   VmFrame F = {{origin[0], origin[1], origin[2]}, voxel};
   hipLaunchKernelGGL(vm_offsets_kernel, dim3(1), dim3(VM_WG), 0, st, bank_offsets, n_bank, n_clouds, pick, n_obs, points_capacity,
                      obs_off, status);
@@ -425,9 +443,7 @@ API int egonn_ndt_finalize(const uint64_t* keys, const int64_t* n_dev, int64_t c
 
 API int64_t egonn_ndt_register_scratch_bytes(int64_t n_src, int n_pairs) {
   if (!ndt_register_shape_ok(n_src, n_pairs)) return -1;
-  Carve c;
-  c.take((size_t)pair_layout(c, n_src, n_pairs, sizeof(NdtPair)).n_wg * NDT_NPART * 8);
-  return (int64_t)c.o;
+  return (int64_t)ndt_register_span(nullptr, n_src, n_pairs).total;
 }
 
 API int egonn_ndt_register(const double* src, int64_t n_src, const int64_t* src_offsets, int n_pairs, const double* T_init,
@@ -446,16 +462,12 @@ API int egonn_ndt_register(const double* src, int64_t n_src, const int64_t* src_
   EGONN_REQUIRE(src_offsets && n_dev && T && fitness && score && iterations && status && scratch && (n_src == 0 || src) &&
                     (capacity_map == 0 || (keys && mean && info && valid)),
                 EGONN_ERR_INVALID, "ndt_register: null pointer");
-  Carve c;
-  const PairLayout L = pair_layout(c, n_src, n_pairs, sizeof(NdtPair));
-  const size_t partial_at = c.take((size_t)L.n_wg * NDT_NPART * 8);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)c.o && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "ndt_register: scratch needs %lld bytes, 256-byte aligned", (long long)c.o);
+  const NdtSpan S = ndt_register_span(scratch, n_src, n_pairs);
+  EGONN_TRY(span_check("ndt_register", scratch, scratch_bytes, S.total));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  NdtPair* pairs = (NdtPair*)(base + L.pairs);
-  int32_t* wg0 = (int32_t*)(base + L.wg0);
-  double* partial = (double*)(base + partial_at);
+  NdtPair* pairs = S.pairs;
+  int32_t* wg0 = S.wg0;
+  double* partial = S.partial;
   EGONN_TRY(pair_clear_traces(T_trace, eval_trace, 4, n_pairs, max_iteration, st));
   if (sums_trace)
     HIP_CHECK(hipMemsetAsync(sums_trace, 0, (size_t)n_pairs * ((size_t)max_iteration + 1) * NDT_NPART * sizeof(double), st));
@@ -464,7 +476,7 @@ API int egonn_ndt_register(const double* src, int64_t n_src, const int64_t* src_
   HIP_CHECK(hipGetLastError());
   if (n_src == 0) return EGONN_OK;                       // every pair is EMPTY
   const NdtLayer M = {keys, n_dev, capacity_map, mean, info, valid};
-  const dim3 grid((unsigned)L.n_wg), one((unsigned)n_pairs);
+  const dim3 grid((unsigned)S.n_wg), one((unsigned)n_pairs);
   for (int k = 0; k <= max_iteration; ++k) {
     if (neighbors == 7) hipLaunchKernelGGL(ndt_eval_kernel<7>, grid, dim3(NDT_WG), 0, st, pairs, wg0, n_pairs, src, M, voxel, partial);
     else hipLaunchKernelGGL(ndt_eval_kernel<1>, grid, dim3(NDT_WG), 0, st, pairs, wg0, n_pairs, src, M, voxel, partial);

@@ -128,21 +128,16 @@ __device__ static inline void pair_advance(Pair* q, int p, int round, int max_it
 }
 
 // ------------------------------------------------------------------ host side
-// carves of a scratch span, each aligned to 256 bytes
-struct Carve {
-  size_t o = 0;
-  size_t take(size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; }
-};
-
 struct PairLayout {         // the caller carves its partial sums, n_wg * NP doubles, where it wants them
-  size_t pairs, wg0;
+  void* pairs;              // n_pairs of the estimator's pair struct
+  int32_t* wg0;
   int64_t n_wg;             // workgroups of the flat grid: every pair rounds its own up
 };
 static inline PairLayout pair_layout(Carve& c, int64_t n_src, int n_pairs, size_t pair_bytes) {
   PairLayout L;
   L.n_wg = cdiv(n_src, PAIR_WG) + n_pairs;
-  L.pairs = c.take((size_t)n_pairs * pair_bytes);
-  L.wg0 = c.take((size_t)(n_pairs + 1) * 4);
+  L.pairs = c.take<char>((size_t)n_pairs * pair_bytes);
+  L.wg0 = c.take<int32_t>((size_t)n_pairs + 1);
   return L;
 }
 

@@ -647,62 +647,43 @@ __global__ __launch_bounds__(PG_WG) void pg_finish_kernel(const PgState* __restr
 }
 
 // ------------------------------------------------------------------ the scratch span
-struct PgLayout {
-  size_t ab, weff, pstat, fixed, row_start, inc, keys0, keys1, vals0, vals1, sort, sort_bytes;        // the plan
-  size_t state, X0, X1, lin0, lin1, ecost, fac, x, r, z, q, p0, p1, pqp, rz0p, rzp0, rzp1, gmaxp, costp, total;
-};
-static bool pg_sizes_ok(int64_t n, int64_t E) { return pose_sizes_ok(n, E); }
-static PgLayout pg_layout(int64_t n, int64_t E) {
-  PgLayout L;
-  const size_t nn = (size_t)n, ee = (size_t)(E > 0 ? E : 1), nwg = (size_t)cdiv(n, PG_WG);
-  size_t o = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  L.ab = carve(ee * 8), L.weff = carve(ee * 16), L.pstat = carve(ee * 4), L.fixed = carve(nn), L.row_start = carve((nn + 1) * 4);
-  L.inc = carve(ee * 8), L.keys0 = carve(ee * 16), L.keys1 = carve(ee * 16), L.vals0 = carve(ee * 8), L.vals1 = carve(ee * 8);
-  L.sort_bytes = align_up(radix_sort_scratch_bytes(2 * (int64_t)ee) + 512, 256);
-  L.sort = carve(L.sort_bytes);
-  L.state = carve(sizeof(PgState));
-  L.X0 = carve(nn * 128), L.X1 = carve(nn * 128), L.lin0 = carve(ee * PG_LIN * 8), L.lin1 = carve(ee * PG_LIN * 8);
-  L.ecost = carve(ee * 8), L.fac = carve(nn * 21 * 8);
-  L.x = carve(nn * 48), L.r = carve(nn * 48), L.z = carve(nn * 48), L.q = carve(nn * 48), L.p0 = carve(nn * 48), L.p1 = carve(nn * 48);
-  L.pqp = carve(nwg * 8), L.rz0p = carve(nwg * 8), L.rzp0 = carve(nwg * 8), L.rzp1 = carve(nwg * 8), L.gmaxp = carve(nwg * 8);
-  L.costp = carve(nwg * 8);
-  L.total = o;
-  return L;
-}
-
-struct PgPtrs {
-  int32_t *ab, *pstat, *row_start;
-  double *weff, *X0, *X1, *lin0, *lin1, *ecost, *fac, *x, *r, *z, *q, *p[2], *pqp, *rz0p, *rzp[2], *gmaxp, *costp;
+// Every array of the plan and of the optimiser's state, carved in this order.  With scratch = nullptr only `total` means anything
+struct PgSpan {
+  int32_t *ab, *pstat, *row_start;                            // the plan
+  double* weff;
   uint8_t* fixed;
   uint32_t* inc;
-  PgState* state;
+  uint64_t* keys[2];                                          // ping-pong buffers of the plan's sort
+  uint32_t* vals[2];
+  Arena sort_ws;
+  PgState* state;                                             // the optimiser
+  double *X0, *X1, *lin0, *lin1, *ecost, *fac, *x, *r, *z, *q, *p[2], *pqp, *rz0p, *rzp[2], *gmaxp, *costp;
+  size_t total;
 };
-static PgPtrs pg_ptrs(void* scratch, const PgLayout& L) {
-  char* b = (char*)scratch;
-  PgPtrs P;
-  P.ab = (int32_t*)(b + L.ab), P.pstat = (int32_t*)(b + L.pstat), P.row_start = (int32_t*)(b + L.row_start);
-  P.weff = (double*)(b + L.weff), P.X0 = (double*)(b + L.X0), P.X1 = (double*)(b + L.X1);
-  P.lin0 = (double*)(b + L.lin0), P.lin1 = (double*)(b + L.lin1), P.ecost = (double*)(b + L.ecost);
-  P.fac = (double*)(b + L.fac), P.x = (double*)(b + L.x), P.r = (double*)(b + L.r);
-  P.z = (double*)(b + L.z), P.q = (double*)(b + L.q), P.p[0] = (double*)(b + L.p0), P.p[1] = (double*)(b + L.p1);
-  P.pqp = (double*)(b + L.pqp), P.rz0p = (double*)(b + L.rz0p), P.rzp[0] = (double*)(b + L.rzp0), P.rzp[1] = (double*)(b + L.rzp1);
-  P.gmaxp = (double*)(b + L.gmaxp), P.costp = (double*)(b + L.costp);
-  P.fixed = (uint8_t*)(b + L.fixed), P.inc = (uint32_t*)(b + L.inc), P.state = (PgState*)(b + L.state);
+static bool pg_sizes_ok(int64_t n, int64_t E) { return pose_sizes_ok(n, E); }
+static PgSpan pg_span(void* scratch, int64_t n, int64_t E) {
+  PgSpan P;
+  Carve c(scratch);
+  const size_t nn = (size_t)n, ee = (size_t)(E > 0 ? E : 1), nwg = (size_t)cdiv(n, PG_WG);
+  P.ab = c.take<int32_t>(ee * 2), P.weff = c.take<double>(ee * 2), P.pstat = c.take<int32_t>(ee), P.fixed = c.take<uint8_t>(nn);
+  P.row_start = c.take<int32_t>(nn + 1), P.inc = c.take<uint32_t>(ee * 2);
+  for (int k = 0; k < 2; ++k) P.keys[k] = c.take<uint64_t>(ee * 2);
+  for (int k = 0; k < 2; ++k) P.vals[k] = c.take<uint32_t>(ee * 2);
+  P.sort_ws = c.sort_arena(radix_sort_scratch_bytes(2 * (int64_t)ee));
+  P.state = c.take<PgState>(1);
+  P.X0 = c.take<double>(nn * 16), P.X1 = c.take<double>(nn * 16), P.lin0 = c.take<double>(ee * PG_LIN), P.lin1 = c.take<double>(ee * PG_LIN);
+  P.ecost = c.take<double>(ee), P.fac = c.take<double>(nn * 21);
+  for (double** v : {&P.x, &P.r, &P.z, &P.q, &P.p[0], &P.p[1]}) *v = c.take<double>(nn * 6);
+  for (double** v : {&P.pqp, &P.rz0p, &P.rzp[0], &P.rzp[1], &P.gmaxp, &P.costp}) *v = c.take<double>(nwg);
+  P.total = c.total();
   return P;
 }
 
-static int pg_check_span(const char* who, int64_t n, int64_t E, const void* scratch, int64_t scratch_bytes, PgLayout* L) {
+static int pg_check_span(const char* who, int64_t n, int64_t E, void* scratch, int64_t scratch_bytes, PgSpan* P) {
   EGONN_REQUIRE(pg_sizes_ok(n, E), EGONN_ERR_INVALID, "%s: n=%lld E=%lld outside 1 <= n < 2^31 - 1, 0 <= E < 2^30", who, (long long)n,
                 (long long)E);
-  *L = pg_layout(n, E);
-  EGONN_REQUIRE(scratch && scratch_bytes >= (int64_t)L->total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "%s: scratch needs %lld bytes, 256-byte aligned", who, (long long)L->total);
-  return EGONN_OK;
+  *P = pg_span(scratch, n, E);
+  return span_check(who, scratch, scratch_bytes, P->total);
 }
 static inline bool pg_tol_ok(double v) { return v >= 0.0 && v < INFINITY; }
 
@@ -710,7 +691,7 @@ static inline unsigned pg_grid(int64_t items) { return (unsigned)cdiv(items > 0 
 
 API int64_t egonn_pose_graph_scratch_bytes(int64_t n, int64_t E, int pcg_iterations) {
   if (!pg_sizes_ok(n, E) || pcg_iterations < 1) return -1;
-  return (int64_t)pg_layout(n, E).total;                    // the PCG keeps no per-iteration record: the budget adds nothing
+  return (int64_t)pg_span(nullptr, n, E).total;                   // the PCG keeps no per-iteration record: the budget adds nothing
 }
 
 API int egonn_pose_graph_odometry(const double* poses, int64_t n, double* Z, int32_t* edge_index, void* stream) {
@@ -726,23 +707,20 @@ API int egonn_pose_graph_odometry(const double* poses, int64_t n, double* Z, int
 API int egonn_pose_graph_plan(const int32_t* edge_index, const double* Z, const double* weights, const uint8_t* fixed, int64_t n,
                               int64_t E, int32_t* edge_status, int32_t* graph_status, void* scratch, int64_t scratch_bytes,
                               void* stream) {
-  PgLayout L;
-  EGONN_TRY(pg_check_span("pose_graph_plan", n, E, scratch, scratch_bytes, &L));
+  PgSpan P;
+  EGONN_TRY(pg_check_span("pose_graph_plan", n, E, scratch, scratch_bytes, &P));
   EGONN_REQUIRE(graph_status && (E == 0 || (edge_index && Z && edge_status)), EGONN_ERR_INVALID, "pose_graph_plan: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const PgPtrs P = pg_ptrs(scratch, L);
-  char* base = (char*)scratch;
-  uint64_t *keys0 = (uint64_t*)(base + L.keys0), *keys1 = (uint64_t*)(base + L.keys1), *kres = nullptr;
-  uint32_t *vals0 = (uint32_t*)(base + L.vals0), *vals1 = (uint32_t*)(base + L.vals1), *vres = nullptr;
+  uint64_t *keys0 = P.keys[0], *keys1 = P.keys[1], *kres = nullptr;
+  uint32_t *vals0 = P.vals[0], *vals1 = P.vals[1], *vres = nullptr;
   HIP_CHECK(hipMemsetAsync(graph_status, 0, sizeof(int32_t), st));
   if (E > 0) {
     hipLaunchKernelGGL(pg_validate_kernel, dim3(pg_grid(E)), dim3(PG_WG), 0, st, edge_index, Z, weights, (int32_t)n, (int32_t)E, P.ab,
                        P.weff, P.pstat, edge_status, keys0, vals0);
     int nbits = 1;
     while ((n >> nbits) != 0) ++nbits;                       // keys are 0 .. n
-    Arena ws = Arena::view(base + L.sort, L.sort_bytes);
     kres = keys1, vres = vals1;
-    EGONN_TRY(radix_sort_pairs(ws, keys0, vals0, keys1, vals1, 2 * E, nbits, st, nullptr, &kres, &vres));
+    EGONN_TRY(radix_sort_pairs(P.sort_ws, keys0, vals0, keys1, vals1, 2 * E, nbits, st, nullptr, &kres, &vres));
   }
   const int64_t threads = 2 * E > n + 1 ? 2 * E : n + 1;
   hipLaunchKernelGGL(pg_csr_kernel, dim3(pg_grid(threads)), dim3(PG_WG), 0, st, kres, vres, (int32_t)(2 * E), (int32_t)n, fixed,
@@ -754,13 +732,12 @@ API int egonn_pose_graph_plan(const int32_t* edge_index, const double* Z, const 
 API int egonn_pose_graph_cost(const double* poses, int64_t n, int64_t E, const double* Z, double robust_delta, double* cost,
                               double* residuals, double* rho, double* s, double* gradient, int32_t* edge_status, void* scratch,
                               int64_t scratch_bytes, void* stream) {
-  PgLayout L;
-  EGONN_TRY(pg_check_span("pose_graph_cost", n, E, scratch, scratch_bytes, &L));
+  PgSpan P;
+  EGONN_TRY(pg_check_span("pose_graph_cost", n, E, scratch, scratch_bytes, &P));
   EGONN_REQUIRE(poses && cost && gradient && (E == 0 || (Z && residuals && rho && s && edge_status)), EGONN_ERR_INVALID,
                 "pose_graph_cost: null pointer");
   EGONN_REQUIRE(pg_tol_ok(robust_delta), EGONN_ERR_INVALID, "pose_graph_cost: robust_delta=%g is negative or not finite", robust_delta);
   hipStream_t st = (hipStream_t)stream;
-  const PgPtrs P = pg_ptrs(scratch, L);
   const int nwg = (int)cdiv(n, PG_WG);
   hipLaunchKernelGGL(pg_init_kernel, dim3(1), dim3(PG_WG), 0, st, P.state, 0.0, (double*)nullptr, (int32_t*)nullptr, 0);
   if (E > 0)
@@ -777,13 +754,12 @@ API int egonn_pose_graph_cost(const double* poses, int64_t n, int64_t E, const d
 API int egonn_pose_graph_hessvec(const double* poses, int64_t n, int64_t E, const double* Z, double robust_delta, double lambda,
                                  const double* p, double* out, int32_t* edge_status, void* scratch, int64_t scratch_bytes,
                                  void* stream) {
-  PgLayout L;
-  EGONN_TRY(pg_check_span("pose_graph_hessvec", n, E, scratch, scratch_bytes, &L));
+  PgSpan P;
+  EGONN_TRY(pg_check_span("pose_graph_hessvec", n, E, scratch, scratch_bytes, &P));
   EGONN_REQUIRE(poses && p && out && (E == 0 || (Z && edge_status)), EGONN_ERR_INVALID, "pose_graph_hessvec: null pointer");
   EGONN_REQUIRE(pg_tol_ok(robust_delta) && pg_tol_ok(lambda), EGONN_ERR_INVALID,
                 "pose_graph_hessvec: robust_delta=%g or lambda=%g is negative or not finite", robust_delta, lambda);
   hipStream_t st = (hipStream_t)stream;
-  const PgPtrs P = pg_ptrs(scratch, L);
   const int nwg = (int)cdiv(n, PG_WG);
   hipLaunchKernelGGL(pg_init_kernel, dim3(1), dim3(PG_WG), 0, st, P.state, lambda, (double*)nullptr, (int32_t*)nullptr, 0);
   if (E > 0)
@@ -800,8 +776,8 @@ API int egonn_pose_graph_optimize(const double* poses, int64_t n, int64_t E, con
                                   double rel_tol, double grad_tol, double* poses_out, double* cost_trace, int32_t* accept_trace,
                                   int32_t* counters, double* lambda_out, int32_t* edge_status, int32_t* graph_status, void* scratch,
                                   int64_t scratch_bytes, void* stream) {
-  PgLayout L;
-  EGONN_TRY(pg_check_span("pose_graph_optimize", n, E, scratch, scratch_bytes, &L));
+  PgSpan P;
+  EGONN_TRY(pg_check_span("pose_graph_optimize", n, E, scratch, scratch_bytes, &P));
   EGONN_REQUIRE(poses && poses_out && cost_trace && accept_trace && counters && lambda_out && graph_status &&
                     (E == 0 || (Z && edge_status)),
                 EGONN_ERR_INVALID, "pose_graph_optimize: null pointer");
@@ -814,7 +790,6 @@ API int egonn_pose_graph_optimize(const double* poses, int64_t n, int64_t E, con
                 "pose_graph_optimize: 0 < lambda_min <= lambda_init <= lambda_max < inf expected, got %g, %g, %g", lambda_min,
                 lambda_init, lambda_max);
   hipStream_t st = (hipStream_t)stream;
-  const PgPtrs P = pg_ptrs(scratch, L);
   const int nwg = (int)cdiv(n, PG_WG);
   const int32_t nn = (int32_t)n, ee = (int32_t)E;
   const dim3 gn(nwg), ge(pg_grid(E)), blk(PG_WG);

@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/egonn_hip.h"
 #include "common.h"
+#include "compact.h"
 
 #pragma clang fp contract(off)
 
@@ -71,40 +72,21 @@ __device__ static inline bool vm_pick_range(const int64_t* __restrict__ off, int
 __global__ __launch_bounds__(VM_WG) static void vm_offsets_kernel(const int64_t* __restrict__ off, int64_t n_bank, int64_t n_clouds,
                                                                   const int32_t* __restrict__ pick, int n_obs, int64_t points_capacity,
                                                                   int64_t* __restrict__ obs_off, int32_t* __restrict__ status) {
-  __shared__ int64_t s_sum[VM_WG + 1];
-  const int t = threadIdx.x;
-  const int per = (n_obs + VM_WG - 1) / VM_WG;
-  const int k0 = min(t * per, n_obs), k1 = min(k0 + per, n_obs);
-  int64_t s = 0;
   bool bad = false;
-  for (int k = k0; k < k1; ++k) {
+  auto size = [&](int64_t k) {
     int64_t lo, hi;
     bad = !vm_pick_range(off, n_bank, n_clouds, pick[k], &lo, &hi) || bad;
-    s += hi - lo;
-  }
+    return hi - lo;
+  };
+  // more points than the caller made room for: no point at all
+  const int64_t total = wg_scan<VM_WG>(n_obs, size, [&](int64_t k, int64_t before, int64_t all) {
+    obs_off[k] = all > points_capacity ? 0 : before;
+  });
   if (bad) atomicOr(status, EGONN_VMAP_STATUS_BAD_INDEX);
-  s_sum[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int64_t acc = 0;
-    for (int k = 0; k < VM_WG; ++k) {
-      const int64_t v = s_sum[k];
-      s_sum[k] = acc;
-      acc += v;
-    }
-    s_sum[VM_WG] = acc;
-    if (acc > points_capacity) atomicOr(status, EGONN_VMAP_STATUS_CAPACITY);
+  if (threadIdx.x == 0) {
+    if (total > points_capacity) atomicOr(status, EGONN_VMAP_STATUS_CAPACITY);
+    obs_off[n_obs] = total > points_capacity ? 0 : total;
   }
-  __syncthreads();
-  const bool fail = s_sum[VM_WG] > points_capacity;      // more points than the caller made room for: no point at all
-  int64_t acc = s_sum[t];
-  for (int k = k0; k < k1; ++k) {
-    int64_t lo, hi;
-    vm_pick_range(off, n_bank, n_clouds, pick[k], &lo, &hi);
-    obs_off[k] = fail ? 0 : acc;
-    acc += hi - lo;
-  }
-  if (t == 0) obs_off[n_obs] = fail ? 0 : s_sum[VM_WG];
 }
 
 // point i of a call: the last observation k with obs_off[k] <= i (its cloud is not empty, i < total) and the bank row, -1 when

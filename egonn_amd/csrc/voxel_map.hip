@@ -18,9 +18,14 @@
 // select      sel_slab (a box owns one contiguous key range: two binary searches on the x index), sel_count, sel_scan,
 //             sel_write: the slab is cut into slices, each slice counts, then writes behind the scanned counts.
 //
+// Counting flags per workgroup, scanning the counts in one workgroup, ranking a flagged row and the bounds of a run inside a
+// wave are compact.h (wg_count, wg_scan, wg_rank, wave_run); what a head is stays here (vm_is_head).  The carves of a caller's
+// scratch are one function per entry point (vm_span, mg_span, sel_span) over common.h's Carve.
+//
 // No call synchronises with the host; grids are sized from capacities and the live counts stay on the device.
 #include "../../include/egonn_hip.h"
 #include "common.h"
+#include "compact.h"                                     // wg_count / wg_scan / wg_rank, wave_run
 #include "voxel_key.h"                                   // the frame, the key and the residuals of a point; shared with ndt.hip
 
 #pragma clang fp contract(off)
@@ -44,34 +49,6 @@ struct VmCRec {
 };
 
 __device__ static inline int64_t vm_min(int64_t a, int64_t b) { return a < b ? a : b; }
-
-// one workgroup: exclusive scan of cnt[0..n) in place, the total to every thread
-__device__ static inline int64_t vm_block_scan(int32_t* __restrict__ cnt, int64_t n, int64_t* s_sum) {
-  const int t = threadIdx.x;
-  const int64_t per = (n + VM_WG - 1) / VM_WG;
-  const int64_t b0 = vm_min(t * per, n), b1 = vm_min(b0 + per, n);
-  int64_t s = 0;
-  for (int64_t b = b0; b < b1; ++b) s += cnt[b];
-  s_sum[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int64_t acc = 0;
-    for (int k = 0; k < VM_WG; ++k) {
-      const int64_t v = s_sum[k];
-      s_sum[k] = acc;
-      acc += v;
-    }
-    s_sum[VM_WG] = acc;
-  }
-  __syncthreads();
-  int64_t acc = s_sum[t];
-  for (int64_t b = b0; b < b1; ++b) {
-    const int32_t v = cnt[b];
-    cnt[b] = (int32_t)acc;
-    acc += v;
-  }
-  return s_sum[VM_WG];
-}
 
 // ------------------------------------------------------------------ integrate
 // vm_offsets_kernel (voxel_key.h): the picked clouds' offsets, BAD_INDEX, the point capacity
@@ -104,21 +81,15 @@ __device__ static inline bool vm_is_head(const uint64_t* __restrict__ keys, int6
 
 __global__ __launch_bounds__(VM_WG) void vm_count_kernel(const uint64_t* __restrict__ keys, const int64_t* __restrict__ n_dev, int64_t cap,
                                                          int32_t* __restrict__ blockcnt) {
-  __shared__ int s_w[4];
-  const int t = threadIdx.x;
-  const bool head = vm_is_head(keys, vm_live(n_dev, cap), (int64_t)blockIdx.x * VM_WG + t);
-  const unsigned long long bal = __ballot(head);
-  if ((t & 63) == 0) s_w[t >> 6] = __popcll(bal);
-  __syncthreads();
-  if (t == 0) blockcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  const int heads = wg_count<VM_WG>(vm_is_head(keys, vm_live(n_dev, cap), (int64_t)blockIdx.x * VM_WG + threadIdx.x));
+  if (threadIdx.x == 0) blockcnt[blockIdx.x] = heads;
 }
 
 // one workgroup: exclusive scan of the block counts, the number of voxels against the capacity.  meta[0] = 1: go on
 __global__ __launch_bounds__(VM_WG) void vm_scan_kernel(int32_t* __restrict__ blockcnt, int64_t nb, int64_t capacity,
                                                         int64_t* __restrict__ n_out, int32_t* __restrict__ status,
                                                         int32_t* __restrict__ meta) {
-  __shared__ int64_t s_sum[VM_WG + 1];
-  const int64_t total = vm_block_scan(blockcnt, nb, s_sum);
+  const int64_t total = wg_scan<VM_WG>(blockcnt, nb);
   if (threadIdx.x == 0) {
     const bool fail = total > capacity;
     if (fail) atomicOr(status, EGONN_VMAP_STATUS_CAPACITY);
@@ -131,16 +102,10 @@ __global__ __launch_bounds__(VM_WG) void vm_scan_kernel(int32_t* __restrict__ bl
 __global__ __launch_bounds__(VM_WG) void vm_head_kernel(const uint64_t* __restrict__ keys, const int64_t* __restrict__ n_dev, int64_t cap,
                                                         const int32_t* __restrict__ blockpre, const int32_t* __restrict__ meta, VmRec out,
                                                         int64_t capacity) {
-  __shared__ int s_w[4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int64_t i = (int64_t)blockIdx.x * VM_WG + t;
+  const int64_t i = (int64_t)blockIdx.x * VM_WG + threadIdx.x;
   const bool head = meta[0] && vm_is_head(keys, vm_live(n_dev, cap), i);
-  const unsigned long long bal = __ballot(head);
-  if (lane == 0) s_w[w] = __popcll(bal);
-  __syncthreads();
+  const int64_t o = (int64_t)blockpre[blockIdx.x] + wg_rank<VM_WG>(__ballot(head));
   if (!head) return;
-  int64_t o = blockpre[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-  for (int k = 0; k < w; ++k) o += s_w[k];
   if (o >= capacity) return;                  // cannot happen (vm_scan compared the total); keeps the stores in bounds regardless
   out.keys[o] = keys[i];
   out.sums[o * 3] = out.sums[o * 3 + 1] = out.sums[o * 3 + 2] = 0;
@@ -152,21 +117,16 @@ __global__ __launch_bounds__(VM_WG) void vm_reduce_kernel(const uint64_t* __rest
                                                           const int4* __restrict__ q4, const int64_t* __restrict__ n_dev, int64_t cap,
                                                           const int32_t* __restrict__ blockpre, const int32_t* __restrict__ meta,
                                                           VmRec out, int64_t capacity) {
-  __shared__ int s_w[4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int64_t i = (int64_t)blockIdx.x * VM_WG + t;
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * VM_WG + threadIdx.x;
   const int64_t n = vm_live(n_dev, cap);
   const bool go = meta[0] != 0;
   const uint64_t key = i < n ? keys[i] : VM_INVALID;
   const bool valid = go && key != VM_INVALID;
   const bool head = valid && (i == 0 || keys[i - 1] != key);
   const unsigned long long bal = __ballot(head), vbal = __ballot(valid);
-  if (lane == 0) s_w[w] = __popcll(bal);
-  __syncthreads();
+  const int64_t o = (int64_t)blockpre[blockIdx.x] + wg_rank<VM_WG>(bal) + (head ? 1 : 0) - 1;       // the record of this point's run
   if (vbal == 0ull) return;                                                 // a wave behind the last valid point
-  const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);          // lanes <= this one
-  int64_t o = (int64_t)blockpre[blockIdx.x] + __popcll(bal & upto) - 1;    // the record of this point's run
-  for (int k = 0; k < w; ++k) o += s_w[k];
   int4 q = make_int4(0, 0, 0, -1);
   if (valid) {
     const uint32_t v = vals[i];
@@ -180,21 +140,19 @@ __global__ __launch_bounds__(VM_WG) void vm_reduce_kernel(const uint64_t* __rest
   }
   long long sx = q.x, sy = q.y, sz = q.z;
   int cnt = valid ? 1 : 0, ob = valid && (head || kprev != q.w) ? 1 : 0;
-  const unsigned long long hb = bal & upto;
-  const int start = hb ? 63 - __clzll((long long)hb) : 0;                   // first lane of this point's run inside the wave
+  const WaveRun run = wave_run(bal);
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
     const long long ax = __shfl_up(sx, d), ay = __shfl_up(sy, d), az = __shfl_up(sz, d);
     const int ac = __shfl_up(cnt, d), ao = __shfl_up(ob, d);
-    if (lane - d >= start) sx += ax, sy += ay, sz += az, cnt += ac, ob += ao;
+    if (lane - d >= run.start) sx += ax, sy += ay, sz += az, cnt += ac, ob += ao;
   }
   // the last lane of a run's piece holds the piece's sums
   const bool next_valid = lane < 63 && ((vbal >> (lane + 1)) & 1ull), next_head = lane < 63 && ((bal >> (lane + 1)) & 1ull);
   if (!valid || (lane < 63 && next_valid && !next_head)) return;
   if (o < 0 || o >= capacity) return;                                       // cannot happen; keeps the stores in bounds regardless
-  const bool begins_here = (bal >> start) & 1ull;
   const bool ends_here = i + 1 >= n || keys[i + 1] != key;
-  if (begins_here && ends_here) {                                            // the whole run inside this wave: nobody else adds
+  if (run.begins_here && ends_here) {                                        // the whole run inside this wave: nobody else adds
     out.sums[o * 3] = sx, out.sums[o * 3 + 1] = sy, out.sums[o * 3 + 2] = sz;
     out.count[o] = cnt;
     out.obs[o] = ob;
@@ -208,26 +166,31 @@ __global__ __launch_bounds__(VM_WG) void vm_reduce_kernel(const uint64_t* __rest
   }
 }
 
-struct VmLayout {
-  size_t obs_off, keys0, keys1, vals0, vals1, q4, blockcnt, meta, sort, sort_bytes, total;
-  int64_t nb;
+// The carves of the caller's scratch, one function per entry point.  With scratch = nullptr only `total` means anything
+struct VmSpan {
+  int64_t nb;               // workgroups over the points
+  int64_t* obs_off;
+  uint64_t* keys[2];        // ping-pong buffers of the sort
+  uint32_t* vals[2];
+  int4* q4;
+  int32_t *blockcnt, *meta;
+  Arena sort_ws;
+  size_t total;
 };
-static VmLayout vm_layout(int64_t points_capacity, int n_obs) {
-  VmLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+static VmSpan vm_span(void* scratch, int64_t points_capacity, int n_obs) {
+  VmSpan S;
+  Carve c(scratch);
   const size_t m = (size_t)(points_capacity > 0 ? points_capacity : 1);
-  L.nb = cdiv((int64_t)m, VM_WG);
-  L.obs_off = take((size_t)(n_obs + 1) * 8);
-  L.keys0 = take(m * 8), L.keys1 = take(m * 8), L.vals0 = take(m * 4), L.vals1 = take(m * 4);
-  L.q4 = take(m * 16);
-  L.blockcnt = take((size_t)(L.nb + 1) * 4);
-  L.meta = take(256);
-  // + 512: the sort carves two arrays out of this span and Arena::alloc aligns each carve to 256
-  L.sort_bytes = align_up(radix_sort_scratch_bytes((int64_t)m) + 512, 256);
-  L.sort = take(L.sort_bytes);
-  L.total = o;
-  return L;
+  S.nb = cdiv((int64_t)m, VM_WG);
+  S.obs_off = c.take<int64_t>((size_t)n_obs + 1);
+  for (int k = 0; k < 2; ++k) S.keys[k] = c.take<uint64_t>(m);
+  for (int k = 0; k < 2; ++k) S.vals[k] = c.take<uint32_t>(m);
+  S.q4 = c.take<int4>(m);
+  S.blockcnt = c.take<int32_t>((size_t)S.nb + 1);
+  S.meta = c.take<int32_t>(64);
+  S.sort_ws = c.sort_arena(radix_sort_scratch_bytes((int64_t)m));
+  S.total = c.total();
+  return S;
 }
 
 // ------------------------------------------------------------------ merge
@@ -236,9 +199,7 @@ static constexpr uint32_t MG_MATCHED = 0x80000000u;
 __global__ __launch_bounds__(VM_WG) void mg_search_kernel(const uint64_t* __restrict__ a_keys, const int64_t* __restrict__ n_a, int64_t cap_a,
                                                           const uint64_t* __restrict__ b_keys, const int64_t* __restrict__ n_b, int64_t cap_b,
                                                           uint32_t* __restrict__ lb_a, int32_t* __restrict__ blockcnt) {
-  __shared__ int s_w[4];
-  const int t = threadIdx.x;
-  const int64_t j = (int64_t)blockIdx.x * VM_WG + t;
+  const int64_t j = (int64_t)blockIdx.x * VM_WG + threadIdx.x;
   const int64_t na = vm_live(n_a, cap_a), nb = vm_live(n_b, cap_b);
   bool only = false;
   if (j < nb) {
@@ -248,18 +209,15 @@ __global__ __launch_bounds__(VM_WG) void mg_search_kernel(const uint64_t* __rest
     lb_a[j] = (uint32_t)lb | (matched ? MG_MATCHED : 0u);
     only = !matched;
   }
-  const unsigned long long bal = __ballot(only);
-  if ((t & 63) == 0) s_w[t >> 6] = __popcll(bal);
-  __syncthreads();
-  if (t == 0) blockcnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  const int onlys = wg_count<VM_WG>(only);
+  if (threadIdx.x == 0) blockcnt[blockIdx.x] = onlys;
 }
 
 // meta[0] = 1: the union fits, meta[1] = B-only rows
 __global__ __launch_bounds__(VM_WG) void mg_scan_kernel(int32_t* __restrict__ blockcnt, int64_t nblk, const int64_t* __restrict__ n_a,
                                                         int64_t cap_a, int64_t capacity_out, int64_t* __restrict__ n_out,
                                                         int32_t* __restrict__ status, int32_t* __restrict__ meta) {
-  __shared__ int64_t s_sum[VM_WG + 1];
-  const int64_t only = vm_block_scan(blockcnt, nblk, s_sum);
+  const int64_t only = wg_scan<VM_WG>(blockcnt, nblk);
   if (threadIdx.x == 0) {
     const int64_t na = vm_live(n_a, cap_a);
     const bool fail = na + only > capacity_out;
@@ -274,19 +232,12 @@ __global__ __launch_bounds__(VM_WG) void mg_scan_kernel(int32_t* __restrict__ bl
 __global__ __launch_bounds__(VM_WG) void mg_rank_kernel(const uint32_t* __restrict__ lb_a, const int64_t* __restrict__ n_b, int64_t cap_b,
                                                         const int32_t* __restrict__ blockpre, const int32_t* __restrict__ meta,
                                                         int32_t* __restrict__ rank) {
-  __shared__ int s_w[4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int64_t j = (int64_t)blockIdx.x * VM_WG + t;
+  const int64_t j = (int64_t)blockIdx.x * VM_WG + threadIdx.x;
   const int64_t nb = vm_live(n_b, cap_b);
   const bool only = j < nb && !(lb_a[j] & MG_MATCHED);
-  const unsigned long long bal = __ballot(only);
-  if (lane == 0) s_w[w] = __popcll(bal);
-  __syncthreads();
+  const int r = blockpre[blockIdx.x] + wg_rank<VM_WG>(__ballot(only));
   if (j > nb) return;
-  if (j == nb) { rank[j] = meta[1]; return; }
-  int r = blockpre[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-  for (int k = 0; k < w; ++k) r += s_w[k];
-  rank[j] = r;
+  rank[j] = j == nb ? meta[1] : r;
 }
 
 __global__ __launch_bounds__(VM_WG) void mg_place_a_kernel(VmCRec A, const int64_t* __restrict__ n_a, int64_t cap_a,
@@ -325,22 +276,23 @@ __global__ __launch_bounds__(VM_WG) void mg_place_b_kernel(VmCRec B, const int64
   }
 }
 
-struct MgLayout {
-  size_t lb_a, rank, blockcnt, meta, total;
-  int64_t nblk;
+struct MgSpan {
+  int64_t nblk;             // workgroups over the B rows
+  uint32_t* lb_a;
+  int32_t *rank, *blockcnt, *meta;
+  size_t total;
 };
-static MgLayout mg_layout(int64_t capacity_b) {
-  MgLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+static MgSpan mg_span(void* scratch, int64_t capacity_b) {
+  MgSpan S;
+  Carve c(scratch);
   const size_t m = (size_t)(capacity_b > 0 ? capacity_b : 1);
-  L.nblk = cdiv((int64_t)m, VM_WG);
-  L.lb_a = take(m * 4);
-  L.rank = take((m + 1) * 4);
-  L.blockcnt = take((size_t)(L.nblk + 1) * 4);
-  L.meta = take(256);
-  L.total = o;
-  return L;
+  S.nblk = cdiv((int64_t)m, VM_WG);
+  S.lb_a = c.take<uint32_t>(m);
+  S.rank = c.take<int32_t>(m + 1);
+  S.blockcnt = c.take<int32_t>((size_t)S.nblk + 1);
+  S.meta = c.take<int32_t>(64);
+  S.total = c.total();
+  return S;
 }
 static bool mg_shape_ok(int64_t capacity_a, int64_t capacity_b, int64_t capacity_out) {
   return capacity_a >= 0 && capacity_b >= 0 && capacity_a < (1ll << 31) && capacity_b < (1ll << 31) && capacity_out >= capacity_a &&
@@ -402,7 +354,6 @@ __device__ static inline void sel_slice(const int64_t* __restrict__ slab, int b,
 
 __global__ __launch_bounds__(VM_WG) void sel_count_kernel(VmCRec M, VmFrame F, SelRule R, const double* __restrict__ boxes,
                                                           const int64_t* __restrict__ slab, int S, int32_t* __restrict__ cnts) {
-  __shared__ int s_w[4];
   const int s = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
   int64_t a, e;
   sel_slice(slab, b, s, S, &a, &e);
@@ -412,18 +363,16 @@ __global__ __launch_bounds__(VM_WG) void sel_count_kernel(VmCRec M, VmFrame F, S
   for (int64_t i = a + t; i < e; i += VM_WG) mine += sel_take(M, i, F, R, box, c) ? 1 : 0;
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d);
-  if ((t & 63) == 0) s_w[t >> 6] = mine;
-  __syncthreads();
-  if (t == 0) cnts[(int64_t)b * S + s] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  const int taken = wg_wave_sum<VM_WG>(mine);                                // lane 0 holds its wave's sum
+  if (t == 0) cnts[(int64_t)b * S + s] = taken;
 }
 
 // meta[0] = 1: write.  sizing (no out_points): the offsets only
 __global__ __launch_bounds__(VM_WG) void sel_scan_kernel(int32_t* __restrict__ cnts, int n_seg, int S, int64_t capacity, int sizing,
                                                          int64_t* __restrict__ out_offsets, int32_t* __restrict__ status,
                                                          int32_t* __restrict__ meta) {
-  __shared__ int64_t s_sum[VM_WG + 1];
   __shared__ int s_fail;
-  const int64_t total = vm_block_scan(cnts, (int64_t)n_seg * S, s_sum);
+  const int64_t total = wg_scan<VM_WG>(cnts, (int64_t)n_seg * S);
   if (threadIdx.x == 0) {
     s_fail = total > (sizing ? (int64_t)INT32_MAX : capacity);      // sizing: the offsets must fit the int32 scan
     if (s_fail) atomicOr(status, EGONN_VMAP_STATUS_CAPACITY);
@@ -440,9 +389,8 @@ __global__ __launch_bounds__(VM_WG) void sel_write_kernel(VmCRec M, VmFrame F, S
                                                           const int32_t* __restrict__ meta, double* __restrict__ out_points,
                                                           int32_t* __restrict__ out_count, int32_t* __restrict__ out_obs,
                                                           int64_t capacity) {
-  __shared__ int s_w[4];
   if (!meta[0]) return;
-  const int s = blockIdx.x, b = blockIdx.y, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int s = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
   int64_t a, e;
   sel_slice(slab, b, s, S, &a, &e);
   const double* box = boxes ? boxes + (int64_t)b * 6 : nullptr;
@@ -451,13 +399,9 @@ __global__ __launch_bounds__(VM_WG) void sel_write_kernel(VmCRec M, VmFrame F, S
     const int64_t i = i0 + t;
     double c[3] = {0.0, 0.0, 0.0};
     const bool take = i < e && sel_take(M, i, F, R, box, c);
-    const unsigned long long bal = __ballot(take);
-    __syncthreads();                                                        // the previous tile's s_w has been read
-    if (lane == 0) s_w[w] = __popcll(bal);
-    __syncthreads();
+    int taken;
+    const int64_t o = base + wg_rank<VM_WG>(__ballot(take), &taken);
     if (take) {
-      int64_t o = base + __popcll(bal & ((1ull << lane) - 1ull));
-      for (int k = 0; k < w; ++k) o += s_w[k];
       if (o < capacity) {                                                   // always (sel_scan compared the total)
 #pragma unroll
         for (int k = 0; k < 3; ++k) out_points[o * 3 + k] = R.relative && box ? c[k] - box[k] : c[k];
@@ -465,27 +409,28 @@ __global__ __launch_bounds__(VM_WG) void sel_write_kernel(VmCRec M, VmFrame F, S
         if (out_obs) out_obs[o] = M.obs[i];
       }
     }
-    base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    base += taken;
   }
 }
 
-struct SelLayout {
-  size_t slab, cnts, meta, total;
-  int n_seg, S;
+struct SelSpan {
+  int n_seg, S;             // boxes (one without boxes), slices per box
+  int64_t* slab;
+  int32_t *cnts, *meta;
+  size_t total;
 };
-static SelLayout sel_layout(int64_t capacity_map, int n_boxes) {
-  SelLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes, 256); return at; };
+static SelSpan sel_span(void* scratch, int64_t capacity_map, int n_boxes) {
+  SelSpan L;
+  Carve c(scratch);
   L.n_seg = n_boxes > 0 ? n_boxes : 1;
   int64_t S = cdiv(capacity_map > 0 ? capacity_map : 1, 2048);            // slices per box: about 2048 records each at a full slab
   const int64_t most = VM_MAX_SLICE_ROWS / L.n_seg;
   S = S > most ? most : S;
   L.S = (int)(S < 1 ? 1 : (S > 1024 ? 1024 : S));
-  L.slab = take((size_t)L.n_seg * 16);
-  L.cnts = take(((size_t)L.n_seg * L.S + 1) * 4);
-  L.meta = take(256);
-  L.total = o;
+  L.slab = c.take<int64_t>((size_t)L.n_seg * 2);
+  L.cnts = c.take<int32_t>((size_t)L.n_seg * L.S + 1);
+  L.meta = c.take<int32_t>(64);
+  L.total = c.total();
   return L;
 }
 static bool sel_shape_ok(int64_t capacity_map, int n_boxes) {
@@ -499,7 +444,7 @@ using namespace egonn;
 // ------------------------------------------------------------------ entry points
 API int64_t egonn_voxel_map_integrate_scratch_bytes(int64_t points_capacity, int n_obs) {
   if (!vm_integrate_shape_ok(points_capacity, n_obs)) return -1;
-  return (int64_t)vm_layout(points_capacity, n_obs).total;
+  return (int64_t)vm_span(nullptr, points_capacity, n_obs).total;
 }
 
 API int egonn_voxel_map_integrate(const double* bank, int64_t n_bank, const int64_t* bank_offsets, int64_t n_clouds, const int32_t* pick,
@@ -515,42 +460,32 @@ API int egonn_voxel_map_integrate(const double* bank, int64_t n_bank, const int6
   EGONN_REQUIRE(bank_offsets && pick && poses && n_out && status && scratch && (n_bank == 0 || bank) &&
                     (capacity == 0 || (out_keys && out_sums && out_count && out_obs)),
                 EGONN_ERR_INVALID, "voxel_map_integrate: null pointer");
-  const VmLayout L = vm_layout(points_capacity, n_obs);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "voxel_map_integrate: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  VmSpan S = vm_span(scratch, points_capacity, n_obs);
+  EGONN_TRY(span_check("voxel_map_integrate", scratch, scratch_bytes, S.total));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  int64_t* obs_off = (int64_t*)(base + L.obs_off);
-  uint64_t *k0 = (uint64_t*)(base + L.keys0), *k1 = (uint64_t*)(base + L.keys1);
-  uint32_t *v0 = (uint32_t*)(base + L.vals0), *v1 = (uint32_t*)(base + L.vals1);
-  int4* q4 = (int4*)(base + L.q4);
-  int32_t* blockcnt = (int32_t*)(base + L.blockcnt);
-  int32_t* meta = (int32_t*)(base + L.meta);
   VmFrame F = {{origin[0], origin[1], origin[2]}, voxel};
   const VmRec out = {out_keys, out_sums, out_count, out_obs};
-  const dim3 grid((unsigned)L.nb), wg(VM_WG);
-  const int64_t* total = obs_off + n_obs;
-  hipLaunchKernelGGL(vm_offsets_kernel, dim3(1), wg, 0, st, bank_offsets, n_bank, n_clouds, pick, n_obs, points_capacity, obs_off,
+  const dim3 grid((unsigned)S.nb), wg(VM_WG);
+  const int64_t* total = S.obs_off + n_obs;
+  hipLaunchKernelGGL(vm_offsets_kernel, dim3(1), wg, 0, st, bank_offsets, n_bank, n_clouds, pick, n_obs, points_capacity, S.obs_off,
                      status);
-  hipLaunchKernelGGL(vm_key_kernel, grid, wg, 0, st, bank, n_bank, bank_offsets, n_clouds, pick, poses, n_obs, F, obs_off,
-                     points_capacity, k0, v0, q4, status);
-  uint64_t* keys = k0;
-  uint32_t* vals = v0;
-  if (points_capacity > 0) {
-    Arena sort_ws = Arena::view(base + L.sort, L.sort_bytes);
-    EGONN_TRY(radix_sort_pairs(sort_ws, k0, v0, k1, v1, points_capacity, 64, st, total, &keys, &vals));
-  }
-  hipLaunchKernelGGL(vm_count_kernel, grid, wg, 0, st, keys, total, points_capacity, blockcnt);
-  hipLaunchKernelGGL(vm_scan_kernel, dim3(1), wg, 0, st, blockcnt, L.nb, capacity, n_out, status, meta);
-  hipLaunchKernelGGL(vm_head_kernel, grid, wg, 0, st, keys, total, points_capacity, blockcnt, meta, out, capacity);
-  hipLaunchKernelGGL(vm_reduce_kernel, grid, wg, 0, st, keys, vals, q4, total, points_capacity, blockcnt, meta, out, capacity);
+  hipLaunchKernelGGL(vm_key_kernel, grid, wg, 0, st, bank, n_bank, bank_offsets, n_clouds, pick, poses, n_obs, F, S.obs_off,
+                     points_capacity, S.keys[0], S.vals[0], S.q4, status);
+  uint64_t* keys = S.keys[0];
+  uint32_t* vals = S.vals[0];
+  if (points_capacity > 0)
+    EGONN_TRY(radix_sort_pairs(S.sort_ws, S.keys[0], S.vals[0], S.keys[1], S.vals[1], points_capacity, 64, st, total, &keys, &vals));
+  hipLaunchKernelGGL(vm_count_kernel, grid, wg, 0, st, keys, total, points_capacity, S.blockcnt);
+  hipLaunchKernelGGL(vm_scan_kernel, dim3(1), wg, 0, st, S.blockcnt, S.nb, capacity, n_out, status, S.meta);
+  hipLaunchKernelGGL(vm_head_kernel, grid, wg, 0, st, keys, total, points_capacity, S.blockcnt, S.meta, out, capacity);
+  hipLaunchKernelGGL(vm_reduce_kernel, grid, wg, 0, st, keys, vals, S.q4, total, points_capacity, S.blockcnt, S.meta, out, capacity);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
 
 API int64_t egonn_voxel_map_merge_scratch_bytes(int64_t capacity_a, int64_t capacity_b, int64_t capacity_out) {
   if (!mg_shape_ok(capacity_a, capacity_b, capacity_out)) return -1;
-  return (int64_t)mg_layout(capacity_b).total;
+  return (int64_t)mg_span(nullptr, capacity_b).total;
 }
 
 API int egonn_voxel_map_merge(const uint64_t* a_keys, const int64_t* a_sums, const int32_t* a_count, const int32_t* a_obs,
@@ -567,33 +502,28 @@ API int egonn_voxel_map_merge(const uint64_t* a_keys, const int64_t* a_sums, con
                 EGONN_ERR_INVALID, "voxel_map_merge: null pointer");
   EGONN_REQUIRE(capacity_out == 0 || (out_keys != a_keys && out_keys != b_keys), EGONN_ERR_INVALID,
                 "voxel_map_merge: out must not be A or B");
-  const MgLayout L = mg_layout(capacity_b);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "voxel_map_merge: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  const MgSpan S = mg_span(scratch, capacity_b);
+  EGONN_TRY(span_check("voxel_map_merge", scratch, scratch_bytes, S.total));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  uint32_t* lb_a = (uint32_t*)(base + L.lb_a);
-  int32_t* rank = (int32_t*)(base + L.rank);
-  int32_t* blockcnt = (int32_t*)(base + L.blockcnt);
-  int32_t* meta = (int32_t*)(base + L.meta);
   const VmCRec A = {a_keys, a_sums, a_count, a_obs}, B = {b_keys, b_sums, b_count, b_obs};
   const VmRec out = {out_keys, out_sums, out_count, out_obs};
-  const dim3 wg(VM_WG), grid_b((unsigned)L.nblk);
-  hipLaunchKernelGGL(mg_search_kernel, grid_b, wg, 0, st, a_keys, n_a, capacity_a, b_keys, n_b, capacity_b, lb_a, blockcnt);
-  hipLaunchKernelGGL(mg_scan_kernel, dim3(1), wg, 0, st, blockcnt, L.nblk, n_a, capacity_a, capacity_out, n_out, status, meta);
-  hipLaunchKernelGGL(mg_rank_kernel, dim3((unsigned)cdiv(capacity_b + 1, VM_WG)), wg, 0, st, lb_a, n_b, capacity_b, blockcnt, meta, rank);
+  const dim3 wg(VM_WG), grid_b((unsigned)S.nblk);
+  hipLaunchKernelGGL(mg_search_kernel, grid_b, wg, 0, st, a_keys, n_a, capacity_a, b_keys, n_b, capacity_b, S.lb_a, S.blockcnt);
+  hipLaunchKernelGGL(mg_scan_kernel, dim3(1), wg, 0, st, S.blockcnt, S.nblk, n_a, capacity_a, capacity_out, n_out, status, S.meta);
+  hipLaunchKernelGGL(mg_rank_kernel, dim3((unsigned)cdiv(capacity_b + 1, VM_WG)), wg, 0, st, S.lb_a, n_b, capacity_b, S.blockcnt, S.meta,
+                     S.rank);
   if (capacity_a > 0)
     hipLaunchKernelGGL(mg_place_a_kernel, dim3((unsigned)cdiv(capacity_a, VM_WG)), wg, 0, st, A, n_a, capacity_a, b_keys, n_b, capacity_b,
-                       rank, meta, out, capacity_out);
+                       S.rank, S.meta, out, capacity_out);
   if (capacity_b > 0)
-    hipLaunchKernelGGL(mg_place_b_kernel, grid_b, wg, 0, st, B, n_b, capacity_b, lb_a, rank, meta, out, capacity_out);
+    hipLaunchKernelGGL(mg_place_b_kernel, grid_b, wg, 0, st, B, n_b, capacity_b, S.lb_a, S.rank, S.meta, out, capacity_out);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }
 
 API int64_t egonn_voxel_map_select_scratch_bytes(int64_t capacity_map, int n_boxes) {
   if (!sel_shape_ok(capacity_map, n_boxes)) return -1;
-  return (int64_t)sel_layout(capacity_map, n_boxes).total;
+  return (int64_t)sel_span(nullptr, capacity_map, n_boxes).total;
 }
 
 API int egonn_voxel_map_select(const uint64_t* keys, const int64_t* sums, const int32_t* count, const int32_t* obs, const int64_t* n_dev,
@@ -611,23 +541,21 @@ API int egonn_voxel_map_select(const uint64_t* keys, const int64_t* sums, const 
   EGONN_REQUIRE(n_dev && out_offsets && status && scratch && (capacity_map == 0 || (keys && sums && count && obs)) &&
                     (out_points || (!out_count && !out_obs)),
                 EGONN_ERR_INVALID, "voxel_map_select: null pointer");
-  const SelLayout L = sel_layout(capacity_map, n_boxes);
-  EGONN_REQUIRE(scratch_bytes >= (int64_t)L.total && ((uintptr_t)scratch & 255) == 0, EGONN_ERR_INVALID,
-                "voxel_map_select: scratch needs %lld bytes, 256-byte aligned", (long long)L.total);
+  const SelSpan L = sel_span(scratch, capacity_map, n_boxes);
+  EGONN_TRY(span_check("voxel_map_select", scratch, scratch_bytes, L.total));
   hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)scratch;
-  int64_t* slab = (int64_t*)(base + L.slab);
-  int32_t* cnts = (int32_t*)(base + L.cnts);
-  int32_t* meta = (int32_t*)(base + L.meta);
   VmFrame F = {{origin[0], origin[1], origin[2]}, voxel};
   const SelRule R = {min_count, min_obs, relative ? 1 : 0};
   const VmCRec M = {keys, sums, count, obs};
   const dim3 wg(VM_WG), grid((unsigned)L.S, (unsigned)L.n_seg);
-  hipLaunchKernelGGL(sel_slab_kernel, dim3((unsigned)cdiv(L.n_seg, VM_WG)), wg, 0, st, keys, n_dev, capacity_map, F, boxes, L.n_seg, slab);
-  hipLaunchKernelGGL(sel_count_kernel, grid, wg, 0, st, M, F, R, boxes, slab, L.S, cnts);
-  hipLaunchKernelGGL(sel_scan_kernel, dim3(1), wg, 0, st, cnts, L.n_seg, L.S, capacity, out_points ? 0 : 1, out_offsets, status, meta);
+  hipLaunchKernelGGL(sel_slab_kernel, dim3((unsigned)cdiv(L.n_seg, VM_WG)), wg, 0, st, keys, n_dev, capacity_map, F, boxes, L.n_seg,
+                     L.slab);
+  hipLaunchKernelGGL(sel_count_kernel, grid, wg, 0, st, M, F, R, boxes, L.slab, L.S, L.cnts);
+  hipLaunchKernelGGL(sel_scan_kernel, dim3(1), wg, 0, st, L.cnts, L.n_seg, L.S, capacity, out_points ? 0 : 1, out_offsets, status,
+                     L.meta);
   if (out_points)
-    hipLaunchKernelGGL(sel_write_kernel, grid, wg, 0, st, M, F, R, boxes, slab, L.S, cnts, meta, out_points, out_count, out_obs, capacity);
+    hipLaunchKernelGGL(sel_write_kernel, grid, wg, 0, st, M, F, R, boxes, L.slab, L.S, L.cnts, L.meta, out_points, out_count, out_obs,
+                       capacity);
   HIP_CHECK(hipGetLastError());
   return EGONN_OK;
 }

@@ -128,6 +128,23 @@ def test_downsample_where_the_sort_loops_wrap(gpu):
         assert st.tolist() == [0] and np.array_equal(alone[0], pts[i]) and np.array_equal(cnt_alone[0], cnt[i])
 
 
+def test_downsample_where_the_block_scan_wraps(gpu):
+    """one cloud of 65 537 points is 257 workgroups: in the one-workgroup scan of their head counts a thread owns two counters.
+    And a batch of (256, 0, 512, 255, 1) points: every cloud boundary lies on a multiple of 256 or one short of it and the
+    total is exactly four workgroups, so the end of the last cloud lies behind the last workgroup's counter"""
+    rng = np.random.default_rng(65537)
+    big = rng.uniform(-40, 40, size=(65537, 3)).astype(np.float32)
+    pts, cnt, status, off = _downsample(gpu, [big], 0.5)
+    assert status.tolist() == [0] and off.tolist() == [0, len(pts[0])] and len(pts[0]) > 40000
+    _check_downsample(pts[0], cnt[0], big, 0.5)
+    clouds = [rng.uniform(-2, 2, size=(n, 3)).astype(np.float32) for n in (256, 0, 512, 255, 1)]
+    pts, cnt, status, off = _downsample(gpu, clouds, 0.5)
+    assert (status == 0).all() and off[0] == 0 and off[-1] == sum(len(p) for p in pts) and len(pts[1]) == 0
+    for i, c in enumerate(clouds):
+        _check_downsample(pts[i], cnt[i], c, 0.5)
+    assert np.array_equal(pts[4], clouds[4].astype(np.float64)) and cnt[4].tolist() == [1]
+
+
 def test_downsample_edges(gpu):
     p = np.array([[0.0, 0, 0], [0.04, 0.04, 0.04], [0.06, 0, 0], [1.0, 1.0, 1.0], [-0.3, 5, 5], [0.5, 0.2, 0.1]], np.float32)
     # crop: the point exactly on min_x (0.0) is dropped, the one exactly on max_x (1.0) is kept; NaN / None = no bound

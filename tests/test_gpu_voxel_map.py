@@ -136,13 +136,16 @@ def _shifts(parts, step=0.0):
 
 
 # ------------------------------------------------------------------ integrate
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1025])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1025, 65536, 65537])
 def test_integrate_at_the_wave_and_tile_edges(gpu, n):
-    """n points in three clouds: every point in its own voxel, all points in one voxel, and a clustered mix"""
+    """n points in three clouds: every point in its own voxel, all points in one voxel, and a clustered mix.  65 536 and 65 537
+    points are 256 and 257 workgroups: in the one-workgroup scan of their head counts a thread owns one counter, then two"""
     rng = np.random.default_rng(n)
     off, poses = _split(n, 3), _shifts(3)
-    cells = rng.permutation(40 * 40)[:n]
-    own = np.stack([cells // 40 - 20, cells % 40 - 20, rng.integers(-3, 3, n)], axis=1) * VOXEL + rng.uniform(0.01, 0.24, (n, 3)) + ORIGIN
+    side = max(40, int(np.ceil(np.sqrt(n))))                     # side * side >= n cells
+    cells = rng.permutation(side * side)[:n]
+    own = np.stack([cells // side - side // 2, cells % side - side // 2, rng.integers(-3, 3, n)], axis=1) * VOXEL \
+        + rng.uniform(0.01, 0.24, (n, 3)) + ORIGIN
     want = _check_integrate(own, off, [0, 1, 2], poses)
     assert len(want["keys"]) == n and (want["count"] == 1).all()
     one = ORIGIN + np.array([-3, 2, 5]) * VOXEL + rng.uniform(0.0, VOXEL * 0.999, (n, 3))
@@ -276,8 +279,9 @@ def _merge(A, B, capacity_out=None, rows_a=None, rows_b=None):
     return _download(out, status), out
 
 
-@pytest.mark.parametrize("n", [1, 64, 65, 256, 257])
+@pytest.mark.parametrize("n", [1, 64, 65, 256, 257, 65537])
 def test_merge_key_sets(gpu, n):
+    """65 537 rows are 257 workgroups: the scan of the B-only counts and the ranks behind it with two counters per thread"""
     rng = np.random.default_rng(n)
     pool = np.unique(rng.integers(0, 2 ** 63 - 1, 4 * n + 8, dtype=np.int64).astype(np.uint64))
     pool = pool[rng.permutation(len(pool))]
@@ -350,6 +354,25 @@ def test_insert_in_batches_and_reversed(gpu, scene, reserved):
         assert ref.same(_map_records(gpu.build_map(bank, poses, VOXEL, origin=ORIGIN)), ref.integrate(bank_np, off, np.arange(7), poses, ORIGIN, VOXEL))
 
 
+@pytest.mark.parametrize("n_obs", [257, 513])
+def test_insert_more_observations_than_scan_threads(gpu, n_obs):
+    """one call with 257 and 513 observations of a handful of points each, every seventh cloud empty and some clouds picked
+    twice: the one-workgroup scan of the clouds' sizes gives a thread two, then three observations"""
+    rng = np.random.default_rng(n_obs)
+    sizes = rng.integers(1, 9, n_obs)
+    sizes[::7] = 0
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    pts = rng.uniform(-3, 3, (int(off[-1]), 3)) + ORIGIN
+    pick = np.arange(n_obs)
+    pick[5::50] = 3
+    poses = _shifts(n_obs, 0.013)
+    want = ref.integrate(pts, off, pick, poses, ORIGIN, VOXEL)
+    assert want["status"] == 0 and want["count"].sum() == sizes[pick].sum() and want["obs"].max() > 1
+    got = _map_records(gpu.VoxelMap(VOXEL, ORIGIN).insert(_bank_of(gpu, pts, off), poses, pick))
+    assert got["status"] == 0 and ref.same(got, want)
+    _check_integrate(pts, off, pick, poses)                            # the entry point itself, its buffers exactly full
+
+
 # ------------------------------------------------------------------ select
 def _scene_map(gpu, scene):
     bank_np, off, poses = scene
@@ -390,6 +413,29 @@ def test_select_filters_boxes_and_offsets(gpu, scene):
     assert _np(fit["offsets"]).tolist() == want["offsets"].tolist() and _same_points(_np(fit["points"]), want["points"])
     short = vm.submaps(centers, half, min_count=2, relative=False, capacity=total - 1)
     assert int(short["status"]) == ref.CAPACITY and _np(short["offsets"]).tolist() == [0] * (len(centers) + 1)
+
+
+def test_select_many_boxes_of_a_sliced_map(gpu):
+    """a map of 4 097 records (three slices per box) and 200 boxes: 600 slice counters, two or three per thread of the scan"""
+    rng = np.random.default_rng(4097)
+    cells = rng.permutation(70 * 70)[:4097]
+    pts = np.stack([cells // 70 - 35, cells % 70 - 35, rng.integers(-2, 2, 4097)], axis=1) * VOXEL + rng.uniform(0.01, 0.24, (4097, 3)) + ORIGIN
+    off = _split(4097, 3)
+    rec = ref.integrate(pts, off, [0, 1, 2], _shifts(3), ORIGIN, VOXEL)
+    assert len(rec["keys"]) == 4097
+    vm = gpu.VoxelMap(VOXEL, ORIGIN, capacity=4097).insert(_bank_of(gpu, pts, off), _shifts(3))
+    assert ref.same(_map_records(vm), rec) and 4096 < vm.records["keys"].shape[0] <= 6144, "three slices of 2048 records"
+    centers = np.concatenate([rng.uniform(-9, 9, (199, 2)), np.zeros((199, 1))], axis=1) + ORIGIN
+    centers = np.concatenate([centers, [[500.0, 0.0, 0.0]]])                                  # the last box is empty
+    half = (1.5, 2.5, 1.0)
+    boxes = np.concatenate([centers, np.broadcast_to(np.asarray(half), (200, 3))], axis=1)
+    for relative in (True, False):
+        got = vm.submaps(centers, half, relative=relative)
+        want = ref.select(rec, ORIGIN, VOXEL, 1, 1, boxes, relative)
+        assert int(got["status"]) == 0 and _np(got["offsets"]).tolist() == want["offsets"].tolist()
+        assert _same_points(_np(got["points"]), want["points"]), relative
+    sizes = np.diff(want["offsets"])
+    assert sizes[-1] == 0 and (sizes[:-1] > 0).sum() > 150 and sizes.sum() > 4097, "filled boxes that overlap"
 
 
 def test_select_faces(gpu):

@@ -2,7 +2,8 @@
 perturbed init, 200 rounds allowed).  Per P: ms per pair from device events around whole calls, rounds run, the wall time
 of the float64 restatement (tests/test_icp_host.py) on the same pairs for scale, and, with --kernel-split, the split of the
 device time between the search kernel and the rest from a `rocprofv3 --kernel-trace --stats` run of this script in a child
-process.  Records, not gates.  Writes one JSON file.
+process.  And voxel_downsample on its own: the 2 P raw clouds of each P as one batch, voxel 0.1.  Records, not gates.  Writes one
+JSON file.
 
     python tools/time_icp.py --out profiles/icp_timing.json [--commit HASH] [--kernel-split]
 """
@@ -61,6 +62,32 @@ def _device_rows(args, pairs):
     return rows
 
 
+def _downsample_rows(args, pairs):
+    """voxel_downsample alone: the raw clouds of P pairs as one batch of 2 P clouds"""
+    import egonn_amd
+    rows = []
+    for P in args.pairs:
+        clouds = [c.astype(np.float32) for i in range(P) for c in pairs[i % DISTINCT][:2]]
+        off = np.zeros(len(clouds) + 1, np.int64)
+        off[1:] = np.cumsum([len(c) for c in clouds])
+        pts, off = torch.from_numpy(np.concatenate(clouds)).cuda(), torch.from_numpy(off).cuda()
+        for _ in range(3):
+            r = egonn_amd.voxel_downsample(pts, off, 0.1)
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(4 * args.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = egonn_amd.voxel_downsample(pts, off, 0.1)
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        rows.append({"clouds": len(clouds), "raw_points": int(len(pts)), "voxels": int(r["offsets"][-1]),
+                     "ms_per_call": {"median": float(np.median(ms)), "min": float(np.min(ms)), "max": float(np.max(ms)), "calls": len(ms)}})
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def _kernel_split(args):
     """this script again under rocprofv3 (a fresh child process; the program goes after `--`), P = the largest batch"""
     with tempfile.TemporaryDirectory() as d:
@@ -108,7 +135,8 @@ def main():
     out = {"device": torch.cuda.get_device_name(0), "commit": args.commit,
            "workload": f"planted_scan_pair(100 + i, {args.n_points}), {DISTINCT} distinct pairs tiled up to P; voxel 0.1, max_dist 1.2",
            "timer": "device events around one whole call (two downsamples + ICP, fixed launch sequence of max_iteration rounds); "
-                    "median over the calls after 2 warm-up calls", "rows": rows}
+                    "median over the calls after 2 warm-up calls", "rows": rows,
+           "voxel_downsample": _downsample_rows(args, pairs)}
     if not args.child:
         from tests.test_icp_host import downsample_f64, icp_f64
         t0 = time.perf_counter()
