@@ -172,6 +172,15 @@ _SIGS = [
     ("egonn_voxel_map_select_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
     ("egonn_voxel_map_select", C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int, _P,
                                          C.c_int, C.c_int, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P]),
+    ("egonn_voxel_map_integrate_moments_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
+    ("egonn_voxel_map_integrate_moments", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_double,
+                                                    C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
+    ("egonn_voxel_map_merge_moments_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    ("egonn_voxel_map_merge_moments", C.c_int, [_P] * 7 + [C.c_int64] + [_P] * 7 + [C.c_int64] + [_P] * 6 +
+     [C.c_int64, _P, _P, _P, C.c_int64, _P]),
+    ("egonn_voxel_map_subtract_scratch_bytes", C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    ("egonn_voxel_map_subtract", C.c_int, [_P] * 7 + [C.c_int64] + [_P] * 7 + [C.c_int64] + [_P] * 6 +
+     [C.c_int64, _P, _P, _P, C.c_int64, _P]),
     ("egonn_ndt_accumulate_scratch_bytes", C.c_int64, [C.c_int64, C.c_int]),
     ("egonn_ndt_accumulate", C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int64,
                                        _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),

@@ -10,9 +10,13 @@ torch or numpy fallback for the device arithmetic.
 Gaussian per voxel (mean, information matrix, eigenvalues, normal), and scan-to-map registration against them, which needs
 no submap, no per-call grid and no sort.  `refine_against_map(method="ndt")` and `Relocalizer(ndt_map=...)` run on it.
 
-Not here: removing observations again (the integer sums make it possible later), cutting the sort's 63 key bits by a known
-extent, moments carried through `insert` / merge for an incrementally growing NDT map (an `NDTMap` is a snapshot), the full
-Newton step of the NDT score with a line search, and distribution-to-distribution NDT."""
+A map can give observations back: `remove` integrates them again and subtracts, exactly; with `track=True`
+the map keeps a host ledger of what it holds and `repose` re-fuses the scans a pose-graph correction moved.  With
+`moments=True` the records carry the NDT moments, `NDTMap.from_map` / `NDTMap.update` snapshot them and `build_ndt_map(...,
+moments=True)` reads every point once.
+
+Not here: cutting the sort's 63 key bits by a known extent, a device-side ledger, a `finalize` of only the touched rows, the
+full Newton step of the NDT score with a line search, and distribution-to-distribution NDT."""
 from __future__ import annotations
 
 import ctypes
@@ -26,8 +30,9 @@ from . import registration as _reg
 
 MAX_OBS = 4096
 MAX_BOXES = 4096
-STATUS_RANGE, STATUS_CAPACITY, STATUS_BAD_INDEX = 1, 2, 4
+STATUS_RANGE, STATUS_CAPACITY, STATUS_BAD_INDEX, STATUS_MISMATCH = 1, 2, 4, 8
 _FIELDS = ("keys", "sums", "count", "obs")
+_MOMENTS = ("s1", "s2")
 
 
 def _check_poses(name, poses, n=None):
@@ -56,15 +61,24 @@ def _check_boxes(name, centers, half_extent) -> np.ndarray:
     return np.array(half, dtype=np.float64)          # a writable copy: torch.from_numpy wants one
 
 
-def _records(rows: int, dev) -> Dict[str, torch.Tensor]:
+def _records(rows: int, dev, moments: bool = False) -> Dict[str, torch.Tensor]:
     rows = max(int(rows), 1)
-    return {"keys": torch.empty((rows,), dtype=torch.int64, device=dev), "sums": torch.empty((rows, 3), dtype=torch.int64, device=dev),
-            "count": torch.empty((rows,), dtype=torch.int32, device=dev), "obs": torch.empty((rows,), dtype=torch.int32, device=dev),
-            "n": torch.zeros((), dtype=torch.int64, device=dev)}
+    r = {"keys": torch.empty((rows,), dtype=torch.int64, device=dev), "sums": torch.empty((rows, 3), dtype=torch.int64, device=dev),
+         "count": torch.empty((rows,), dtype=torch.int32, device=dev), "obs": torch.empty((rows,), dtype=torch.int32, device=dev),
+         "n": torch.zeros((), dtype=torch.int64, device=dev)}
+    if moments:
+        r["s1"] = torch.empty((rows, 3), dtype=torch.int64, device=dev)
+        r["s2"] = torch.empty((rows, 6), dtype=torch.int64, device=dev)
+    return r
 
 
 def _rec_ptrs(r):
     return r["keys"].data_ptr(), r["sums"].data_ptr(), r["count"].data_ptr(), r["obs"].data_ptr()
+
+
+def _mrec_ptrs(r):
+    """the six arrays of a record set for the `_moments` entry points and subtract; s1 / s2 null without moments"""
+    return _rec_ptrs(r) + (_lib._ptr(r.get("s1")), _lib._ptr(r.get("s2")))
 
 
 def _scratch256(nbytes: int, dev) -> torch.Tensor:
@@ -80,10 +94,13 @@ class VoxelMap:
     axis around it.  capacity=None: the record buffers grow as needed and `insert` takes one [SYNC] per chunk to size them, as
     `CloudBank.add` does.  capacity=rows reserves two record buffers of that size: `insert` then has no host synchronisation
     (device picks and poses, explicit points_capacity) and can be captured; a chunk that would overflow is dropped whole and
-    sets STATUS_CAPACITY, the map keeps what it holds."""
+    sets STATUS_CAPACITY, the map keeps what it holds.
+    moments=True: the records carry the NDT layer's integer moments (`records` gains 's1' (rows,3) and 's2' (rows,6) int64;
+    `NDTMap.from_map` reads them).  track=True: the map keeps a host `ledger` of the (pick, pose) it holds, which `remove`
+    checks and `repose` needs; it takes host picks and host poses."""
 
     def __init__(self, voxel_size: float = 0.2, origin=None, capacity: Optional[int] = None, device=None,
-                 chunk_points: int = 4_000_000):
+                 chunk_points: int = 4_000_000, moments: bool = False, track: bool = False):
         v = float(voxel_size)
         if not (v > 0.0 and np.isfinite(v)):
             raise ValueError("VoxelMap: voxel_size must be positive and finite")
@@ -97,6 +114,8 @@ class VoxelMap:
             raise ValueError("VoxelMap: chunk_points must be positive")
         self.voxel_size, self.origin, self.capacity = v, origin, None if capacity is None else int(capacity)
         self.device, self.chunk_points = device, int(chunk_points)
+        self.moments, self.track = bool(moments), bool(track)
+        self._ledger_pick, self._ledger_pose = [], []        # what the map holds, in insertion order (track=True)
         self._buf = [None, None]          # ping-pong record buffers
         self._cur = 0
         self._status = None
@@ -113,14 +132,15 @@ class VoxelMap:
             dev = self._dev()
             self._status = torch.zeros((), dtype=torch.int32, device=dev)
             rows = self.capacity if self.capacity is not None else 1
-            self._buf = [_records(rows, dev), _records(rows, dev)]
+            self._buf = [_records(rows, dev, self.moments), _records(rows, dev, self.moments)]
 
     def _origin_c(self):
         return (ctypes.c_double * 3)(*[float(v) for v in self.origin])
 
     @property
     def records(self) -> Dict[str, torch.Tensor]:
-        """the live buffer: keys (rows) int64 (the 63-bit key), sums (rows,3) int64, count, obs (rows) int32, n () int64"""
+        """the live buffer: keys (rows) int64 (the 63-bit key), sums (rows,3) int64, count, obs (rows) int32, n () int64; with
+        moments s1 (rows,3) and s2 (rows,6) int64"""
         self._ensure()
         return self._buf[self._cur]
 
@@ -134,8 +154,16 @@ class VoxelMap:
         """[SYNC] OR of the STATUS_* bits of every call so far"""
         return 0 if self._status is None else int(self._status.item())
 
+    @property
+    def ledger(self):
+        """(pick (n,) int32, poses (n,4,4) float64) of the observations the map holds, in insertion order (track=True)"""
+        n = len(self._ledger_pick)
+        return (np.asarray(self._ledger_pick, dtype=np.int32).reshape(n),
+                np.asarray(self._ledger_pose, dtype=np.float64).reshape(n, 4, 4))
+
     def clear(self) -> "VoxelMap":
-        """empty map, status 0, buffers kept"""
+        """empty map, status 0, empty ledger, buffers kept"""
+        self._ledger_pick, self._ledger_pose = [], []
         if self._status is not None:
             self._cur = 0
             self._buf[0]["n"].zero_()
@@ -143,31 +171,54 @@ class VoxelMap:
         return self
 
     # ------------------------------------------------------------------ insert
-    def _chunk(self, bank, pk, ps, n_obs: int, points_capacity: int):
+    def _chunk(self, bank, pk, ps, n_obs: int, points_capacity: int, subtract: bool = False):
         lib = _lib.load()
         dev = self._dev()
         key = (int(points_capacity), int(n_obs))
         work = self._work.get(key)
         if work is None:
-            work = {"rec": _records(points_capacity, dev),
+            work = {"rec": _records(points_capacity, dev, self.moments),
                     "s_int": _scratch256(lib.egonn_voxel_map_integrate_scratch_bytes(points_capacity, n_obs), dev)}
             if self.capacity is not None:
                 self._work[key] = work
         chunk = work["rec"]
         rows_c = max(int(points_capacity), 1)
         n_bank = bank.n_points
-        _lib.call(dev, lib.egonn_voxel_map_integrate, _lib._ptr(bank.points) if n_bank else None, n_bank, bank.offsets().data_ptr(),
-                  len(bank), pk.data_ptr(), ps.data_ptr(), n_obs, self._origin_c(), self.voxel_size, int(points_capacity),
-                  *_rec_ptrs(chunk), rows_c, chunk["n"].data_ptr(), self._status.data_ptr(), work["s_int"].data_ptr(),
-                  work["s_int"].numel() * 8)
+        if self.moments:                 # the scratch is integrate's (egonn_voxel_map_integrate_moments_scratch_bytes)
+            _lib.call(dev, lib.egonn_voxel_map_integrate_moments, _lib._ptr(bank.points) if n_bank else None, n_bank,
+                      bank.offsets().data_ptr(), len(bank), pk.data_ptr(), ps.data_ptr(), n_obs, self._origin_c(), self.voxel_size,
+                      int(points_capacity), *_mrec_ptrs(chunk), rows_c, chunk["n"].data_ptr(), self._status.data_ptr(),
+                      work["s_int"].data_ptr(), work["s_int"].numel() * 8)
+        else:
+            _lib.call(dev, lib.egonn_voxel_map_integrate, _lib._ptr(bank.points) if n_bank else None, n_bank, bank.offsets().data_ptr(),
+                      len(bank), pk.data_ptr(), ps.data_ptr(), n_obs, self._origin_c(), self.voxel_size, int(points_capacity),
+                      *_rec_ptrs(chunk), rows_c, chunk["n"].data_ptr(), self._status.data_ptr(), work["s_int"].data_ptr(),
+                      work["s_int"].numel() * 8)
         A = self._buf[self._cur]
         rows_a = A["keys"].shape[0]
+        if subtract:                     # out = A - chunk: never more rows than A has
+            out = self._buf[1 - self._cur]
+            if out["keys"].shape[0] < rows_a:
+                out = self._buf[1 - self._cur] = _records(rows_a, dev, self.moments)
+            rows_o = out["keys"].shape[0]
+            skey = ("subtract", rows_a, rows_c, rows_o)
+            s_sub = self._work.get(skey)
+            if s_sub is None:
+                s_sub = _scratch256(lib.egonn_voxel_map_subtract_scratch_bytes(rows_a, rows_c, rows_o), dev)
+                if self.capacity is not None:
+                    self._work[skey] = s_sub
+            _lib.call(dev, lib.egonn_voxel_map_subtract, *_mrec_ptrs(A), A["n"].data_ptr(), rows_a, *_mrec_ptrs(chunk),
+                      chunk["n"].data_ptr(), rows_c, *_mrec_ptrs(out), rows_o, out["n"].data_ptr(), self._status.data_ptr(),
+                      s_sub.data_ptr(), s_sub.numel() * 8)
+            out["_keep"] = (chunk, work, s_sub, pk, ps)
+            self._cur = 1 - self._cur
+            return
         if self.capacity is None:
             n_a, n_c = torch.stack([A["n"], chunk["n"]]).tolist()            # [SYNC] one copy per chunk: sizes the next buffer
             need = n_a + n_c
             out = self._buf[1 - self._cur]
             if out["keys"].shape[0] < max(need, rows_a):
-                out = self._buf[1 - self._cur] = _records(max(need + need // 2, rows_a), dev)
+                out = self._buf[1 - self._cur] = _records(max(need + need // 2, rows_a), dev, self.moments)
         else:
             out = self._buf[1 - self._cur]
         rows_o = out["keys"].shape[0]
@@ -177,32 +228,77 @@ class VoxelMap:
             s_mrg = _scratch256(lib.egonn_voxel_map_merge_scratch_bytes(rows_a, rows_c, rows_o), dev)
             if self.capacity is not None:
                 self._work[mkey] = s_mrg
-        _lib.call(dev, lib.egonn_voxel_map_merge, *_rec_ptrs(A), A["n"].data_ptr(), rows_a, *_rec_ptrs(chunk), chunk["n"].data_ptr(),
-                  rows_c, *_rec_ptrs(out), rows_o, out["n"].data_ptr(), self._status.data_ptr(), s_mrg.data_ptr(), s_mrg.numel() * 8)
+        if self.moments:                 # the scratch is merge's (egonn_voxel_map_merge_moments_scratch_bytes)
+            _lib.call(dev, lib.egonn_voxel_map_merge_moments, *_mrec_ptrs(A), A["n"].data_ptr(), rows_a, *_mrec_ptrs(chunk),
+                      chunk["n"].data_ptr(), rows_c, *_mrec_ptrs(out), rows_o, out["n"].data_ptr(), self._status.data_ptr(),
+                      s_mrg.data_ptr(), s_mrg.numel() * 8)
+        else:
+            _lib.call(dev, lib.egonn_voxel_map_merge, *_rec_ptrs(A), A["n"].data_ptr(), rows_a, *_rec_ptrs(chunk), chunk["n"].data_ptr(),
+                      rows_c, *_rec_ptrs(out), rows_o, out["n"].data_ptr(), self._status.data_ptr(), s_mrg.data_ptr(),
+                      s_mrg.numel() * 8)
         out["_keep"] = (chunk, work, s_mrg, pk, ps)
         self._cur = 1 - self._cur
+
+    def _observations(self, name, bank, poses, pick, points_capacity):
+        """the argument checks `insert` and `remove` share, before a device is asked for -> (n, on_dev, p, sizes)"""
+        n_bank = len(bank)
+        on_dev = torch.is_tensor(pick) and pick.is_cuda
+        n = n_bank if pick is None else len(pick)
+        _check_poses(name, poses, n)
+        if n < 1:
+            raise ValueError(f"{name}: at least one observation")
+        p = sizes = None
+        if on_dev:
+            if self.track:
+                raise ValueError(f"{name}: a tracked map (track=True) takes host picks and host poses")
+            if points_capacity is None or not 0 <= int(points_capacity) < 2 ** 31:
+                raise ValueError(f"{name}: device picks need points_capacity in [0, 2^31)")
+            if n > MAX_OBS:
+                raise ValueError(f"{name}: at most {MAX_OBS} device picks per call, got {n}")
+        else:
+            p = np.arange(n_bank, dtype=np.int64) if pick is None else np.asarray(pick, dtype=np.int64).reshape(-1)
+            if p.size and (p.min() < 0 or p.max() >= n_bank):
+                raise ValueError(f"{name}: pick outside [0, {n_bank})")
+            sizes = bank.sizes()[p]
+        if self.track and torch.is_tensor(poses) and poses.is_cuda:
+            raise ValueError(f"{name}: a tracked map (track=True) takes host picks and host poses")
+        return n, on_dev, p, sizes
+
+    def _chunks(self, bank, ps, n, on_dev, pick, p, sizes, points_capacity, subtract, held=None):
+        """held (n,) bool, host picks: set for the observations of every chunk the map took.  Only a reserved map can drop a
+        chunk (STATUS_CAPACITY); there each chunk runs on a cleared status word that is read back ([SYNC]) and OR-ed in again"""
+        dev = self._dev()
+        if on_dev:
+            self._chunk(bank, _lib.as_dev(pick, dev, torch.int32), ps, n, int(points_capacity), subtract)
+            return
+        lo = 0
+        while lo < n:
+            hi, rows = lo + 1, int(sizes[lo])
+            while hi < n and hi - lo < MAX_OBS and rows + int(sizes[hi]) <= self.chunk_points:
+                rows += int(sizes[hi])
+                hi += 1
+            pk = torch.from_numpy(p[lo:hi].astype(np.int32)).to(dev)
+            if held is None or self.capacity is None:
+                self._chunk(bank, pk, ps[lo:hi].contiguous(), hi - lo, rows, subtract)
+                took = True
+            else:
+                before = self._status.clone()
+                self._status.zero_()
+                self._chunk(bank, pk, ps[lo:hi].contiguous(), hi - lo, rows, subtract)
+                took = not int(self._status.item()) & STATUS_CAPACITY              # [SYNC]
+                self._status |= before
+            if held is not None:
+                held[lo:hi] = took
+            lo = hi
 
     def insert(self, bank, poses, pick=None, points_capacity: Optional[int] = None) -> "VoxelMap":
         """Fuses clouds pick[k] of `bank` (a `CloudBank`; pick=None: all of them, in order) under poses[k] ((n,4,4) float64, scan
         frame -> map frame) into the map.  Host picks are chunked to <= 4096 observations and about `chunk_points` points; each
         chunk is integrated, then merged into the other record buffer.  Device picks (one chunk, <= 4096) need
-        points_capacity, a bound on their clouds' total.  Returns self."""
-        n_bank = len(bank)
-        on_dev = torch.is_tensor(pick) and pick.is_cuda
-        n = n_bank if pick is None else len(pick)
-        _check_poses("VoxelMap.insert", poses, n)
-        if n < 1:
-            raise ValueError("VoxelMap.insert: at least one observation")
-        if on_dev:
-            if points_capacity is None or not 0 <= int(points_capacity) < 2 ** 31:
-                raise ValueError("VoxelMap.insert: device picks need points_capacity in [0, 2^31)")
-            if n > MAX_OBS:
-                raise ValueError(f"VoxelMap.insert: at most {MAX_OBS} device picks per call, got {n}")
-        else:
-            p = np.arange(n_bank, dtype=np.int64) if pick is None else np.asarray(pick, dtype=np.int64).reshape(-1)
-            if p.size and (p.min() < 0 or p.max() >= n_bank):
-                raise ValueError(f"VoxelMap.insert: pick outside [0, {n_bank})")
-            sizes = bank.sizes()[p]
+        points_capacity, a bound on their clouds' total.  A tracked map appends (pick, pose) to its ledger; on a reserved map
+        it reads the status after every chunk ([SYNC]) and a chunk dropped for STATUS_CAPACITY does not enter the ledger: the
+        ledger is what the map holds.  Returns self."""
+        n, on_dev, p, sizes = self._observations("VoxelMap.insert", bank, poses, pick, points_capacity)
         if self.origin is None:
             if torch.is_tensor(poses) and poses.is_cuda:
                 raise ValueError("VoxelMap.insert: device poses need an explicit origin")
@@ -211,21 +307,83 @@ class VoxelMap:
                 raise ValueError("VoxelMap.insert: the first pose's translation is not finite; give an origin")
             self.origin = o
         self._ensure()
-        dev = self._dev()
-        ps = _lib.as_dev(poses, dev, torch.float64)
-        if on_dev:
-            self._chunk(bank, _lib.as_dev(pick, dev, torch.int32), ps, n, int(points_capacity))
-            return self
-        lo = 0
-        while lo < n:
-            hi, rows = lo + 1, int(sizes[lo])
-            while hi < n and hi - lo < MAX_OBS and rows + int(sizes[hi]) <= self.chunk_points:
-                rows += int(sizes[hi])
-                hi += 1
-            pk = torch.from_numpy(p[lo:hi].astype(np.int32)).to(dev)
-            self._chunk(bank, pk, ps[lo:hi].contiguous(), hi - lo, rows)
-            lo = hi
+        ps = _lib.as_dev(poses, self._dev(), torch.float64)
+        held = np.zeros(n, dtype=bool) if self.track else None
+        self._chunks(bank, ps, n, on_dev, pick, p, sizes, points_capacity, False, held)
+        if self.track:
+            host = np.asarray(poses, dtype=np.float64).reshape(n, 4, 4)
+            self._ledger_pick += [int(p[k]) for k in range(n) if held[k]]
+            self._ledger_pose += [host[k].copy() for k in range(n) if held[k]]
+            self._held = held                                                    # `repose` reads it
         return self
+
+    # ------------------------------------------------------------------ remove, repose
+    def _ledger_match(self, name, p, host):
+        """ledger positions of the (pick, pose) pairs, each entry used once; the pose is matched by its bytes"""
+        free = {}
+        for at, (lp, lx) in enumerate(zip(self._ledger_pick, self._ledger_pose)):
+            free.setdefault((lp, lx.tobytes()), []).append(at)
+        hit = []
+        for k in range(len(p)):
+            slots = free.get((int(p[k]), np.ascontiguousarray(host[k]).tobytes()))
+            if not slots:
+                raise ValueError(f"{name}: observation {k} (cloud {int(p[k])}) under this pose is not in the ledger")
+            hit.append(slots.pop(0))
+        return hit
+
+    def remove(self, bank, poses, pick=None, points_capacity: Optional[int] = None) -> "VoxelMap":
+        """Takes clouds pick[k] of `bank` under poses[k] out of the map again: the arguments, the chunking and the device-pick
+        rule of `insert`; each chunk is integrated, then subtracted into the other record buffer (exactly: the sums are
+        integers), and voxels left without points leave the map.  A tracked map checks every (pick, pose) against its ledger
+        first (the pose by its bytes; each match uses one entry up, so a cloud inserted twice can be removed twice) and raises
+        ValueError before any launch when one is missing.  Without tracking exactness is the caller's: the pose, the bank, the
+        origin and the voxel size must be those of the insert, to the bit.  A chunk the map does not hold (a voxel absent, or
+        fewer points or observations than the chunk has) sets STATUS_MISMATCH and leaves the map as it was before that chunk;
+        earlier chunks of the call stay removed.  Returns self."""
+        n, on_dev, p, sizes = self._observations("VoxelMap.remove", bank, poses, pick, points_capacity)
+        hit = None
+        if self.track:
+            hit = self._ledger_match("VoxelMap.remove", p, np.asarray(poses, dtype=np.float64).reshape(n, 4, 4))
+        if self._status is None:
+            raise ValueError("VoxelMap.remove: the map is empty (nothing inserted)")
+        ps = _lib.as_dev(poses, self._dev(), torch.float64)
+        self._chunks(bank, ps, n, on_dev, pick, p, sizes, points_capacity, True)
+        if hit is not None:
+            gone = set(hit)
+            self._ledger_pick = [v for at, v in enumerate(self._ledger_pick) if at not in gone]
+            self._ledger_pose = [v for at, v in enumerate(self._ledger_pose) if at not in gone]
+        return self
+
+    def repose(self, bank, poses_new, rot_tol: float = 0.0, trans_tol: float = 0.0) -> int:
+        """After a pose-graph correction: poses_new (len(ledger),4,4) host float64 in ledger order (track=True).  Entry k has
+        moved iff max |R_new - R_old| > rot_tol or max |t_new - t_old| > trans_tol (elementwise, float64, on the host).
+        The moved entries are removed at their ledger poses and inserted at the new ones; the ledger keeps its order and
+        takes the new poses of the moved entries.  The tolerances trade map error for work; at their default 0 every pose
+        that differs is fused again and the map is, bit for bit, the map built at poses_new.  On a reserved map a chunk of
+        the re-insert that does not fit is dropped (STATUS_CAPACITY) and its entries leave the ledger with it.
+        -> the number of entries moved."""
+        if not self.track:
+            raise ValueError("VoxelMap.repose: needs a tracked map (track=True)")
+        if not (float(rot_tol) >= 0.0 and float(trans_tol) >= 0.0):
+            raise ValueError("VoxelMap.repose: rot_tol and trans_tol are at least 0")
+        picks, old = self.ledger
+        _check_poses("VoxelMap.repose", poses_new, len(picks))
+        if torch.is_tensor(poses_new) and poses_new.is_cuda:
+            raise ValueError("VoxelMap.repose: poses_new on the host")
+        new = np.array(poses_new, dtype=np.float64).reshape(len(picks), 4, 4)
+        d = np.abs(new - old)
+        d_rot = d[:, :3, :3].reshape(-1, 9).max(axis=1, initial=0.0)
+        d_trans = d[:, :3, 3].max(axis=1, initial=0.0)
+        at = np.flatnonzero((d_rot > float(rot_tol)) | (d_trans > float(trans_tol)))
+        if at.size:
+            self.remove(bank, old[at], picks[at])
+            self.insert(bank, new[at], picks[at])
+            old[at] = new[at]
+            keep = np.ones(len(picks), dtype=bool)
+            keep[at] = self._held                                                # a dropped chunk's entries are gone
+            self._ledger_pick = [int(picks[k]) for k in range(len(picks)) if keep[k]]
+            self._ledger_pose = [old[k].copy() for k in range(len(picks)) if keep[k]]
+        return int(at.size)
 
     # ------------------------------------------------------------------ read
     def _select(self, boxes, n_boxes, relative, min_count, min_obs, capacity, with_counts):
@@ -284,31 +442,53 @@ class VoxelMap:
 
     # ------------------------------------------------------------------ files
     def save(self, path: str) -> None:
-        """one .npz: the records, voxel_size, origin.  [SYNC]"""
+        """one .npz: the records, voxel_size, origin; the moments and the ledger when the map has them.  [SYNC]"""
         if self._status is None:
             raise ValueError("VoxelMap.save: the map is empty (nothing inserted)")
         R, n = self.records, self.n_voxels
+        extra = {f: R[f][:n].cpu().numpy() for f in _MOMENTS} if self.moments else {}
+        if self.track:
+            extra["ledger_pick"], extra["ledger_poses"] = self.ledger
         np.savez(path, voxel_size=np.float64(self.voxel_size), origin=np.asarray(self.origin, dtype=np.float64),
-                 status=np.int32(self.status), **{f: R[f][:n].cpu().numpy() for f in _FIELDS})
+                 status=np.int32(self.status), **{f: R[f][:n].cpu().numpy() for f in _FIELDS}, **extra)
 
     @classmethod
-    def load(cls, path: str, capacity: Optional[int] = None, device=None) -> "VoxelMap":
+    def load(cls, path: str, capacity: Optional[int] = None, device=None, moments: Optional[bool] = None,
+             track: Optional[bool] = None) -> "VoxelMap":
+        """moments / track = None: as the file has them.  A file with moments loads only into a moments map and a file
+        without them only into a plain one; track=True needs a file with a ledger."""
         with np.load(path) as z:
             missing = [k for k in _FIELDS + ("voxel_size", "origin") if k not in z.files]
             if missing:
                 raise ValueError(f"{path}: not a voxel map (missing {missing})")
             data = {k: z[k] for k in z.files}
+        has_m, has_l = all(f in data for f in _MOMENTS), "ledger_pick" in data and "ledger_poses" in data
+        if moments is not None and bool(moments) != has_m:
+            raise ValueError(f"{path}: a voxel map {'with' if has_m else 'without'} moments does not load into a map "
+                             f"{'with' if moments else 'without'} them")
+        if track and not has_l:
+            raise ValueError(f"{path}: a voxel map without a ledger does not load into a tracked map")
         n = len(data["keys"])
         if capacity is not None and int(capacity) < n:
             raise ValueError(f"VoxelMap.load: capacity {capacity} below the file's {n} voxels")
-        m = cls(float(data["voxel_size"]), data["origin"], capacity, device)
+        if not has_m and not has_l:
+            m = cls(float(data["voxel_size"]), data["origin"], capacity, device)
+        else:
+            m = cls(float(data["voxel_size"]), data["origin"], capacity, device, moments=has_m,
+                    track=has_l if track is None else bool(track))
         m._ensure()
         if capacity is None:
-            m._buf[0] = _records(n, m._dev())
-        for f in _FIELDS:
+            m._buf[0] = _records(n, m._dev(), has_m)
+        for f in _FIELDS + (_MOMENTS if has_m else ()):
             m._buf[0][f][:n] = torch.from_numpy(data[f]).to(m._dev())
         m._buf[0]["n"].fill_(n)
         m._status.fill_(int(data.get("status", 0)))
+        if m.track:
+            lp = np.asarray(data["ledger_pick"]).reshape(-1)
+            lx = np.asarray(data["ledger_poses"], dtype=np.float64).reshape(-1, 4, 4)
+            if len(lp) != len(lx):
+                raise ValueError(f"{path}: the ledger's picks and poses differ in number")
+            m._ledger_pick, m._ledger_pose = [int(v) for v in lp], [lx[k].copy() for k in range(len(lx))]
         return m
 
 
@@ -339,6 +519,42 @@ class NDTMap:
         n = vmap.n_voxels                                                     # [SYNC]
         self._init(vmap.records["keys"][:n].clone(), vmap.voxel_size, vmap.origin, min_points, min_eig_ratio, chunk_points, vmap._dev())
 
+    @classmethod
+    def from_map(cls, vmap: VoxelMap, min_points: int = NDT_MIN_POINTS, min_eig_ratio: float = NDT_MIN_EIG_RATIO,
+                 chunk_points: int = 4_000_000) -> "NDTMap":
+        """The layer of a map that carries its moments (`VoxelMap(moments=True)`): keys / cnt / s1 / s2 are copies of the map's
+        live records, `missed` is 0, and no point is read again.  The synchronisation is `update`'s."""
+        cls._check_rule(min_points, min_eig_ratio)
+        if int(chunk_points) < 1:
+            raise ValueError("NDTMap: chunk_points must be positive")
+        m = cls.__new__(cls)
+        m.min_points, m.min_eig_ratio, m.chunk_points = int(min_points), float(min_eig_ratio), int(chunk_points)
+        m.keys = None
+        return m.update(vmap)
+
+    def update(self, vmap: VoxelMap) -> "NDTMap":
+        """Snapshots `vmap` (with moments) again after it grew, shrank or was re-posed, and drops the Gaussians: `finalize`
+        anew.  A map with a reserved `capacity` is copied at that size together with its device count: no host
+        synchronisation.  `gaussians` then have `capacity` rows (zeros from the live count on); `keys`, `cnt`, `s1` and `s2`
+        hold whatever the map's buffer held behind the live count (no kernel reads those rows), and the first read of
+        `n_voxels`, which `save` takes, is a [SYNC].  Otherwise one [SYNC] for the count, as the constructor takes."""
+        if not isinstance(vmap, VoxelMap) or vmap._status is None:
+            raise ValueError("NDTMap: the voxel map is empty (nothing inserted)")
+        if not vmap.moments:
+            raise ValueError("NDTMap: the voxel map carries no moments (VoxelMap(moments=True))")
+        if self.keys is not None and (float(vmap.voxel_size) != self.voxel_size or
+                                      not np.array_equal(np.asarray(vmap.origin, np.float64), self.origin)):
+            raise ValueError("NDTMap.update: another voxel size or origin than the layer's")
+        R, dev = vmap.records, vmap._dev()
+        n = R["keys"].shape[0] if vmap.capacity is not None else vmap.n_voxels            # [SYNC] without a capacity
+        self._init(R["keys"][:n], vmap.voxel_size, vmap.origin, self.min_points, self.min_eig_ratio, self.chunk_points, dev)
+        self.cnt[:n], self.s1[:n], self.s2[:n] = R["count"][:n], R["s1"][:n], R["s2"][:n]
+        self._status.copy_(vmap._status)
+        if vmap.capacity is not None:
+            self._n.copy_(R["n"])
+            self._n_host = None
+        return self
+
     @staticmethod
     def _check_rule(min_points, min_eig_ratio):
         if int(min_points) < 3:
@@ -351,7 +567,7 @@ class NDTMap:
         rows = max(n, 1)
         self.device, self.voxel_size, self.origin = dev, float(voxel_size), np.asarray(origin, dtype=np.float64).copy()
         self.min_points, self.min_eig_ratio, self.chunk_points = int(min_points), float(min_eig_ratio), int(chunk_points)
-        self.n_voxels = n
+        self._n_host = n                                                      # None: only the device knows (`update`)
         self.keys = torch.zeros((rows,), dtype=torch.int64, device=dev)
         self.keys[:n] = keys
         self._n = torch.full((), n, dtype=torch.int64, device=dev)
@@ -365,6 +581,13 @@ class NDTMap:
 
     def _origin_c(self):
         return (ctypes.c_double * 3)(*[float(v) for v in self.origin])
+
+    @property
+    def n_voxels(self) -> int:
+        """the rows of the layer; [SYNC] once after an `update` from a map with a reserved capacity"""
+        if self._n_host is None:
+            self._n_host = int(self._n.item())
+        return self._n_host
 
     @property
     def missed(self) -> int:
@@ -423,7 +646,7 @@ class NDTMap:
                   self.s2.data_ptr(), self.voxel_size, self.min_points, self.min_eig_ratio, g["mean"].data_ptr(), g["info"].data_ptr(),
                   g["eigenvalues"].data_ptr(), g["normal"].data_ptr(), g["valid"].data_ptr(), g["n_valid"].data_ptr(),
                   _lib._ptr(g.get("cov")))
-        n = self.n_voxels
+        n = rows if self._n_host is None else self._n_host
         self._layer = g
         self.gaussians = {k: (v if v.dim() == 0 else v[:n]) for k, v in g.items()}
         return self.gaussians
@@ -502,10 +725,18 @@ class NDTMap:
 
 
 def build_ndt_map(bank, poses, voxel_size: float = 1.0, min_points: int = NDT_MIN_POINTS, min_eig_ratio: float = NDT_MIN_EIG_RATIO,
-                  **kw) -> NDTMap:
+                  moments: bool = False, **kw) -> NDTMap:
     """every cloud of `bank` under its pose as an NDT map: build_map, NDTMap(...).accumulate(bank, poses), finalize().  1.0 m by
-    default, not the voxel map's 0.2 m: a Gaussian needs points (at 0.2 m a voxel of the 0.1 m downsample holds a handful)."""
+    default, not the voxel map's 0.2 m: a Gaussian needs points (at 0.2 m a voxel of the 0.1 m downsample holds a handful).
+    moments=True reads every point once: a map with moments, `NDTMap.from_map`, finalize(); the map is the result's `.vmap`
+    (insert into it, remove from it or repose it, then `update` and `finalize` the layer).  The same bits either way."""
     NDTMap._check_rule(min_points, min_eig_ratio)
+    if moments:
+        vm = build_map(bank, poses, voxel_size, moments=True, **kw)
+        m = NDTMap.from_map(vm, min_points, min_eig_ratio)
+        m.finalize()
+        m.vmap = vm
+        return m
     m = NDTMap(build_map(bank, poses, voxel_size, **kw), min_points, min_eig_ratio)
     m.accumulate(bank, poses).finalize()
     return m

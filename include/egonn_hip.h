@@ -972,6 +972,53 @@ int egonn_voxel_map_select(const uint64_t* keys, const int64_t* sums, const int3
                            int n_boxes, int relative, double* out_points, int64_t* out_offsets, int32_t* out_count, int32_t* out_obs,
                            int64_t capacity, int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------ map update (csrc/voxel_map.hip)
+ * Records with moments, and taking observations out again.  A map may carry two more arrays per voxel beside keys / sums /
+ * count / obs: s1 (rows,3) int64 and s2 (rows,6) int64, exactly the NDT layer's moments below (m_a = q_a >> 10, s1 = sum m,
+ * s2 = sum m_a m_b in the order xx, xy, xz, yy, yz, zz) over the points of the voxel; count is that layer's cnt.  In each of
+ * the calls of this section the moment arrays of ALL operands (A, B, out) are either all given or all null; a mixed set is
+ * refused before the first HIP call.  With all of them null a call is its plain counterpart.  The rules of the voxel-map
+ * section hold (scratch, no host synchronisation, capturable, live counts on the device, *status OR-ed into).
+ *
+ * integrate_moments: keys / sums / count / obs / n_out / status are those of egonn_voxel_map_integrate, bit for bit; s1 / s2
+ *   are what egonn_ndt_accumulate gives over those keys for the same observations.  The moments are formed from the q of a
+ *   point's row while its run is reduced: no extra per-point storage (the scratch is integrate's), integer atomics only.
+ * merge_moments: egonn_voxel_map_merge (positions, the capacity rule out = A with B dropped whole, the bits of the four
+ *   arrays) with s1 / s2 added on matched rows and copied on the others.
+ * subtract: out = A - B.  For a B row with key k let r = A[k] - B[k], field by field over sums, count, obs, s1, s2 (int64 sums
+ *   wrap as the additions did).  The B row is LEGAL iff k is in A and either r.count > 0 and r.obs > 0, or every field of r is
+ *   zero.  If every B row is legal, out holds in ascending key order A's rows with r in place of the matched ones, the rows
+ *   with r.count == 0 left out, and n_out = n_a - (rows left out).  If any B row is not legal, EGONN_VMAP_STATUS_MISMATCH is
+ *   OR-ed into *status and out becomes A unchanged (n_out = n_a, moments included): a map never loses what it holds.
+ *   capacity_out >= capacity_a, so CAPACITY is never set; out is neither A nor B; rows from n_out on are not written;
+ *   n_b = 0 gives out = A.  B's keys are ascending and unique, as every record set is.
+ *   What subtract does NOT prove: that B is what was once added.  An observation re-integrated under a wrong pose that happens
+ *   to hit the same voxels with smaller counts passes and leaves wrong sums.  Exactness is the caller's: remove an
+ *   observation under the pose (to the bit), the origin and the voxel size it was inserted with (Python keeps a ledger). */
+enum { EGONN_VMAP_STATUS_MISMATCH = 8 };  /* subtract: a B row that A does not hold (absent key, or more than A holds): out = A */
+int64_t egonn_voxel_map_integrate_moments_scratch_bytes(int64_t points_capacity, int n_obs);
+int egonn_voxel_map_integrate_moments(const double* bank, int64_t n_bank, const int64_t* bank_offsets, int64_t n_clouds,
+                                      const int32_t* pick, const double* poses, int n_obs, const double* origin, double voxel,
+                                      int64_t points_capacity, uint64_t* out_keys, int64_t* out_sums, int32_t* out_count,
+                                      int32_t* out_obs, int64_t* out_s1, int64_t* out_s2, int64_t capacity, int64_t* n_out,
+                                      int32_t* status, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t egonn_voxel_map_merge_moments_scratch_bytes(int64_t capacity_a, int64_t capacity_b, int64_t capacity_out);
+int egonn_voxel_map_merge_moments(const uint64_t* a_keys, const int64_t* a_sums, const int32_t* a_count, const int32_t* a_obs,
+                                  const int64_t* a_s1, const int64_t* a_s2, const int64_t* n_a, int64_t capacity_a,
+                                  const uint64_t* b_keys, const int64_t* b_sums, const int32_t* b_count, const int32_t* b_obs,
+                                  const int64_t* b_s1, const int64_t* b_s2, const int64_t* n_b, int64_t capacity_b,
+                                  uint64_t* out_keys, int64_t* out_sums, int32_t* out_count, int32_t* out_obs, int64_t* out_s1,
+                                  int64_t* out_s2, int64_t capacity_out, int64_t* n_out, int32_t* status, void* scratch,
+                                  int64_t scratch_bytes, void* stream);
+int64_t egonn_voxel_map_subtract_scratch_bytes(int64_t capacity_a, int64_t capacity_b, int64_t capacity_out);
+int egonn_voxel_map_subtract(const uint64_t* a_keys, const int64_t* a_sums, const int32_t* a_count, const int32_t* a_obs,
+                             const int64_t* a_s1, const int64_t* a_s2, const int64_t* n_a, int64_t capacity_a,
+                             const uint64_t* b_keys, const int64_t* b_sums, const int32_t* b_count, const int32_t* b_obs,
+                             const int64_t* b_s1, const int64_t* b_s2, const int64_t* n_b, int64_t capacity_b, uint64_t* out_keys,
+                             int64_t* out_sums, int32_t* out_count, int32_t* out_obs, int64_t* out_s1, int64_t* out_s2,
+                             int64_t capacity_out, int64_t* n_out, int32_t* status, void* scratch, int64_t scratch_bytes,
+                             void* stream);
+
 /* ------------------------------------------------------------------ NDT layer (csrc/ndt.hip)
  * One Gaussian per voxel over the keys of a voxel map, and the normal-distributions transform against them.  The layer lies
  * over a fixed, ascending, unique key array keys[0 .. n) (n = *n_dev clipped to capacity_map: a snapshot of a map's keys) and
